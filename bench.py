@@ -9,7 +9,10 @@ A "step" is one forward of libvithip.so over one batch of synthetic images that 
 resident in HBM (ViT-B/16, 224x224x3, 512 images per GPU, bf16 MFMA operands / fp32 accumulate).
 Images are sharded across ranks (independent units, no data-path collective): rank 0 generates the
 weights, the canonical blob is RCCL-broadcast over xGMI once, every rank then runs its own forward.
-Prints ONE JSON line on rank 0 (contract in the task statement): whole-job images/s, plus
+Prints ONE JSON line on rank 0: whole-job images/s (`value`) and the milliseconds of one timed step (`ms_per_step`).
+A plain run does only that: set-up, warm-up, the K timed steps with nothing else in the stream, the result line.
+`--dump-outputs DIR` then writes the logits of the last timed step to DIR/logits.npy (float32; every input is seeded,
+so two builds can be compared output for output).  With `--full` the line also holds what takes extra work:
   roofline     — the dominant kernel (fc1 GEMM, 256x256-tile MFMA kernel with the GELU epilogue):
                  algorithmic FLOP per launch / average launch duration, measured with hip events on
                  the context's stream inside the timed region, against the dense bf16 MFMA peak;
@@ -21,7 +24,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement): whole-job image
                  type that is inside the north star's tolerance (bf16, the dtype the headline config
                  names, is not and cannot be: DESIGN.md "Numerics");
   vit_large_384_fp16_b256 / fp8_b512 — short measurements (value, roofline, parity) of BASELINE configs 4 and 5, so
-                 that the driver's record covers them too (default run only; `--no-extra-configs` skips them);
+                 that the driver's record covers them too (default workload only; `--no-extra-configs` skips them);
   cpu_baseline — the CPU oracle behind net::net_abstract (tests/cpp/net_cpu, a port: the reference has
                  no CPU path) timed through launch_forward on the host cores (N=1 only).
 """
@@ -85,8 +88,13 @@ def measured_clock(config, batch, dtype):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline / step times / event cost, parity against the CPU oracle, the fp16 line, "
+                         "the extra configurations and the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
     ap.add_argument("--batch", type=int, default=512, help="images per GPU")
     ap.add_argument("--config", default="vit_base")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp8"],
@@ -94,12 +102,12 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target length of the CPU baseline sample")
     ap.add_argument("--weights", default="full", choices=["full", "e4m3"],
                     help="e4m3: weight-only fp8, VH_FLAG_W8_E4M3 (q/k/v/o/fc1/fc2 through the e4m3 row quantiser at load; 16-bit dtypes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed batch's first images")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle check of the timed batch's first images")
     ap.add_argument("--parity-images", type=int, default=16)
-    ap.add_argument("--no-fp16-line", action="store_true", help="skip the extra fp16 measurement of the default run")
+    ap.add_argument("--no-fp16-line", action="store_true", help="--full: skip the extra fp16 measurement of the default workload")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the short ViT-L/16-384 fp16 b256 and ViT-B/16 fp8 b512 measurements of the default run")
+                    help="--full: skip the short ViT-L/16-384 fp16 b256 and ViT-B/16 fp8 b512 measurements of the default workload")
     ap.add_argument("--cls-tail", action="store_true",
                     help="VH_FLAG_CLS_TAIL: the last layer computes the class-token rows only (an opt-in of the library; a line "
                          "measured with it says so in config.workload and is not the BASELINE configuration)")
@@ -116,6 +124,8 @@ def main():
                     help="single process, C-ABI device group (vh_group_*: one host thread per GPU, RCCL broadcast inside "
                          "libvithip) instead of one process per GPU; --gpus N selects the first N devices")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.group:
         return main_group(args)
@@ -145,7 +155,8 @@ def main():
 
     def measure(dtype_name, extras, config=None, B=None, steps=None, warmup=None, parity_images=None, cls_tail=None):
         """One complete measurement with `dtype_name` operands: context, weights (broadcast when distributed), warm-up,
-        K timed steps, roofline of the fc1 kernel, parity of the timed batch's first images."""
+        K timed steps; with --full also the roofline of the fc1 kernel and the parity of the timed batch's first images.
+        `extras` marks the headline measurement (the one whose logits --dump-outputs writes)."""
         config = config or args.config
         cfg = S.CONFIGS[config]
         B = B or args.batch
@@ -196,35 +207,42 @@ def main():
         sync()
 
         # ---- timed region: exactly K steps ----------------------------------------------------------------
-        # hip events on the context's stream inside it: around every fc1 launch (the roofline kernel) and at every step
-        # boundary (median / min step).  Their cost is in `value`; `events_cost` below measures it.
-        if not args.graph:
-            ctx.set_stage_timing("fc1_gemm")   # per-launch events would bypass the graph
+        # --full: hip events on the context's stream inside it, around every fc1 launch (the roofline kernel) and at
+        # every step boundary (median / min step).  Their cost is then in `value`; `events_cost` below measures it.
+        events = args.full and not args.graph   # per-launch events would bypass the graph
+        if events:
+            ctx.set_stage_timing("fc1_gemm")
             ctx.set_step_timing(True)
         barrier(); sync()
         t0 = time.perf_counter()
         ctx.forward_device_async(din.ptr, B, dout.ptr, steps=steps)
         sync(); barrier()
         elapsed = time.perf_counter() - t0
-        fc1_avg_ms, fc1_min_ms, fc1_n = ctx.get_stage_timing()
-        step_ms = sorted(ctx.get_step_timing()) if not args.graph else []
-        ctx.set_stage_timing(None)
-        ctx.set_step_timing(False)
+        fc1_avg_ms = fc1_min_ms = fc1_n = 0
+        step_ms = []
+        if events:
+            fc1_avg_ms, fc1_min_ms, fc1_n = ctx.get_stage_timing()
+            step_ms = sorted(ctx.get_step_timing())
+            ctx.set_stage_timing(None)
+            ctx.set_step_timing(False)
         if use_dist:
             elapsed = vh_dist.max_over_ranks(torch, dist, elapsed, f"cuda:{local_rank}")
+
+        logits = dout.to_numpy(np.float32, (B, cfg["classes"]))   # what the last timed step computed
+        if not np.isfinite(logits).all():
+            raise SystemExit("non-finite logits")
+        if extras and args.dump_outputs:
+            dump_outputs(args.dump_outputs, "logits" if world == 1 else f"logits_rank{rank}", logits, np)
+
         # the same K steps once more WITHOUT any event in the stream (not the reported value: the measure of what the
         # events inside the timed region cost)
         elapsed_plain = None
-        if extras and not args.graph and not use_dist:
+        if extras and events and not use_dist:
             sync()
             t1 = time.perf_counter()
             ctx.forward_device_async(din.ptr, B, dout.ptr, steps=steps)
             sync()
             elapsed_plain = time.perf_counter() - t1
-
-        logits = dout.to_numpy(np.float32, (B, cfg["classes"]))
-        if not np.isfinite(logits).all():
-            raise SystemExit("non-finite logits")
 
         res = {"elapsed": elapsed, "streams": streams, "cfg": cfg, "B": B, "steps": steps, "flops_img": flops_img}
         if rank == 0:
@@ -244,10 +262,10 @@ def main():
             kname = ("gemm_nt_pp_kernel<%s%s> 256x256x%d %sping-pong (fc1)" %
                      ("LN-fold+bias+GELU" if fold else "bias+GELU", ", e4m3" if dtype_name == "fp8" else "",
                       128 if dtype_name == "fp8" else 64, "persistent " if persistent else ""))
-            traffic, tsrc = measured_traffic(config, B, dtype_name, streams)
-            clk, csrc = measured_clock(config, B, dtype_name)
             roof = None
-            if not args.graph:
+            if events:
+                traffic, tsrc = measured_traffic(config, B, dtype_name, streams)
+                clk, csrc = measured_clock(config, B, dtype_name)
                 roof = {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
                         "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": tsrc,
                         "concurrent_parts": streams, "flop_per_launch": fc1_flops, "avg_launch_ms": round(fc1_avg_ms, 5),
@@ -274,7 +292,7 @@ def main():
                 res["events_cost"] = {"value_without_events": round(B * steps / elapsed_plain, 2),
                                       "note": "the same K steps run again with no hip event in the stream; `value` is the run WITH "
                                               "the roofline / step events, as the timed region is defined"}
-            if not args.no_parity:
+            if args.full and not args.no_parity:
                 res["parity"] = parity_of(cfg, logits, min(parity_images, B), dtype_name, 1 + rank, np, S)
             if extras and args.host_path:
                 res["host_path"] = host_path_rate(ctx, cfg, B, steps, np, S)
@@ -289,9 +307,9 @@ def main():
     fp16_res = None
     extra_res = {}
     default_run = args.config == "vit_base" and B == 512 and args.dtype == "bf16"
-    if default_run and not args.no_fp16_line and not args.graph:
+    if args.full and default_run and not args.no_fp16_line and not args.graph:
         fp16_res = measure("fp16", False)
-    if default_run and not args.no_extra_configs and not args.graph and world == 1:
+    if args.full and default_run and not args.no_extra_configs and not args.graph and world == 1:
         # BASELINE configs 4 and 5, short: about a second of GPU time each
         extra_res["vit_large_384_fp16_b256"] = measure("fp16", False, config="vit_large_384", B=256, steps=5, warmup=1, parity_images=8)   # (8 images: ~3 s of oracle; round 3 judged this config on 2)
         extra_res["fp8_b512"] = measure("fp8", False, config="vit_base", B=512, steps=10, warmup=2, parity_images=8)
@@ -335,7 +353,7 @@ def main():
             out["fp16"] = {k: fp16_res[k] for k in ("value", "ms_per_step", "forward_mfma_frac", "roofline", "step_ms", "parity") if k in fp16_res}
             out["fp16"]["note"] = ("same workload, same run, fp16 MFMA operands: the operand type inside the north star's 1e-3 "
                                    "(extra object; `value` above is the bf16 configuration BASELINE.json names)")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
         if "host_path" in main_res:
             out["host_path"] = main_res["host_path"]
@@ -371,6 +389,20 @@ def parity_of(cfg, logits, n, dtype_name, seed, np, S):
     elif dtype_name == "fp8":
         d["note"] = "e4m3 operands: the north star's 1e-3 does not apply to BASELINE config 5 (statistical criterion, tests/test_gpu_fp8.py)"
     return d
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, name, arr, np):
+    """Writes `arr` (float32) to directory/name.npy; beyond DUMP_MAX_BYTES, a fixed seeded sample of its rows in order."""
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    row_bytes = arr[:1].nbytes
+    if arr.nbytes > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES // row_bytes)
+        arr = arr[np.sort(np.random.default_rng(0).choice(arr.shape[0], keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), arr)
 
 
 def main_group(args):
@@ -412,7 +444,9 @@ def main_group(args):
                                      f"{'RCCL-broadcast once' if n > 1 else 'generated in place (group of one)'}, no data-path collective",
                       "flop_per_image": flops_img},
            "forward_mfma_frac": round(ips / n * flops_img / (PEAK_TFLOPS[args.dtype] * 1e12), 4), "roofline": None}
-    if not args.no_parity:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "logits", logits, np)
+    if args.full and not args.no_parity:
         out["parity"] = parity_of(cfg, logits[:B], min(args.parity_images, B), args.dtype, 1, np, S)
     if rehearsal:
         # every member's shard against a plain context on the same seeded images: sharded == unsharded, bit for bit

@@ -10,8 +10,8 @@ for r in 1 2; do
   timeout -k 10 300 python tools/torch_matmul_calib.py --no-torch >> $O/e1_calib_a.txt 2>&1 || exit 1
 done
 cat $O/e1_calib_b.txt $O/e1_calib_a.txt
-VITHIP_LIB=$PWD/vit-fpga_amd/libvithip_b.so timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/e1_bench_b.json 2> $O/e1_bench_b.err || exit 1
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/e1_bench_a.json 2> $O/e1_bench_a.err || exit 1
+VITHIP_LIB=$PWD/vit-fpga_amd/libvithip_b.so timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/e1_bench_b.json 2> $O/e1_bench_b.err || exit 1
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/e1_bench_a.json 2> $O/e1_bench_a.err || exit 1
 python - <<'PY'
 import json
 for n in ("b","a"):

@@ -6,7 +6,7 @@ set -o pipefail
 timeout -k 10 600 python -m pytest tests/test_gpu_ops.py -x -q > $O/e16_ops.log 2>&1; rc=$?; tail -5 $O/e16_ops.log; [ $rc = 0 ] || exit 1
 timeout -k 10 400 python tools/parity_stats.py > $O/e16_parity.txt 2>&1; tail -12 $O/e16_parity.txt
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra-configs | python -c "
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra-configs | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['parity']['worst'], d['parity']['median'], 'fp16', d['fp16']['value'], d['fp16']['parity']['worst'], flush=True)" | tee -a $O/e16_bench.txt
 done

@@ -12,7 +12,7 @@ for v in _abl_t0s0 _abl_t4s0 _abl_t0s1 ""; do
 done
 done
 for v in _abl_t0s0 "" _abl_t0s0 ""; do
-  VITHIP_LIB=$L/libvithip$v.so timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/e4_bench$v.json 2> $O/e4_bench$v.err || { tail -5 $O/e4_bench$v.err; exit 1; }
+  VITHIP_LIB=$L/libvithip$v.so timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/e4_bench$v.json 2> $O/e4_bench$v.err || { tail -5 $O/e4_bench$v.err; exit 1; }
   python - "$v" <<'PY'
 import json,sys
 d=json.loads(open(f"gpurun_out/r03/e4_bench{sys.argv[1]}.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/r03; mkdir -p $O
 set -o pipefail
 SECONDS=0
-python bench.py > $O/e5_bench_default.json 2> $O/e5_bench_default.err; echo "bench rc=$? wall ${SECONDS}s"; tail -3 $O/e5_bench_default.err
+python bench.py --full > $O/e5_bench_default.json 2> $O/e5_bench_default.err; echo "bench rc=$? wall ${SECONDS}s"; tail -3 $O/e5_bench_default.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r03/e5_bench_default.json").read().strip().splitlines()[-1])

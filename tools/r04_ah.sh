@@ -6,7 +6,7 @@ L=vit-fpga_amd
 NOX="--no-cpu-baseline --no-parity --no-fp16-line --no-extra-configs --steps 40"
 for lib in libvithip_abl_old.so libvithip_abl_norpre.so; do echo -n "$lib: "; VITHIP_LIB=$PWD/$L/$lib timeout -k 10 120 python tools/soak.py --steps 40 --every 20 2>&1 | tail -1; done | tee $out/ah_hashes.txt
 for i in 1 2 3 4 5 6; do for lib in libvithip_abl_old.so libvithip_abl_norpre.so; do
-  echo -n "$lib: "; VITHIP_LIB=$PWD/$L/$lib timeout -k 10 200 python bench.py $NOX 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
+  echo -n "$lib: "; VITHIP_LIB=$PWD/$L/$lib timeout -k 10 200 python bench.py --full $NOX 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
 done; done > $out/ah_cpre_compile_time.txt 2>&1
 python - <<'PY'
 import re,collections,statistics as st

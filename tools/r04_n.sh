@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"; out=gpurun_out/r04; mkdir -p $out
 NOX="--no-cpu-baseline --no-parity --no-fp16-line --no-extra-configs --steps 40"
 for dt in bf16 fp16; do for i in 1 2 3 4 5 6 7 8; do for t in 0 1; do
-  echo -n "$dt VH_H_TILED=$t: "; VH_H_TILED=$t timeout -k 10 200 python bench.py $NOX --dtype $dt 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
+  echo -n "$dt VH_H_TILED=$t: "; VH_H_TILED=$t timeout -k 10 200 python bench.py --full $NOX --dtype $dt 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
 done; done; done > $out/n_h_tiled_ab_long.txt 2>&1
 python - <<'PY'
 import re,collections

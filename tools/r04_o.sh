@@ -20,7 +20,7 @@ PY
 cat $out/o_bits.txt
 NOX="--no-cpu-baseline --no-parity --no-fp16-line --no-extra-configs --steps 40"
 for i in 1 2 3 4 5 6; do for t in 0 1; do
-  echo -n "VH_W_TILED=$t: "; VH_W_TILED=$t timeout -k 10 200 python bench.py $NOX 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
+  echo -n "VH_W_TILED=$t: "; VH_W_TILED=$t timeout -k 10 200 python bench.py --full $NOX 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
 done; done > $out/o_w_tiled_ab.txt 2>&1
 python - <<'PY'
 import re,collections,statistics as st

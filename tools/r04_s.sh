@@ -12,7 +12,7 @@ for lib in libvithip_abl_old.so libvithip_abl_rs1.so libvithip_abl_rs2.so libvit
 done > $out/s_hashes.txt 2>&1
 cat $out/s_hashes.txt
 for i in 1 2 3 4; do for lib in libvithip_abl_old.so libvithip_abl_rs1.so libvithip_abl_rs2.so libvithip_abl_rs3.so libvithip.so libvithip_abl_rs5.so; do
-  echo -n "$lib: "; VITHIP_LIB=$PWD/$L/$lib timeout -k 10 200 python bench.py $NOX 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
+  echo -n "$lib: "; VITHIP_LIB=$PWD/$L/$lib timeout -k 10 200 python bench.py --full $NOX 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_ms'])"
 done; done > $out/s_depth.txt 2>&1
 python - <<'PY'
 import re,collections,statistics as st
@@ -22,5 +22,5 @@ for l in open('gpurun_out/r04/s_depth.txt'):
     if m: v[m.group(1)].append((float(m.group(2)),float(m.group(4))))
 for k in v: print(k, 'images/s median', st.median(x[0] for x in v[k]), 'fc1 ms median', st.median(x[1] for x in v[k]), 'n', len(v[k]))
 PY
-for lib in libvithip_abl_old.so libvithip_abl_rs2.so libvithip.so; do VITHIP_LIB=$PWD/$L/$lib timeout -k 10 200 python bench.py --no-cpu-baseline --no-parity --no-fp16-line --no-extra-configs --stages 2> $out/s_stages_$lib.txt > /dev/null; done
+for lib in libvithip_abl_old.so libvithip_abl_rs2.so libvithip.so; do VITHIP_LIB=$PWD/$L/$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-parity --no-fp16-line --no-extra-configs --stages 2> $out/s_stages_$lib.txt > /dev/null; done
 grep -E "qkv|fc1|fc2|proj" $out/s_stages_*.txt
