@@ -61,7 +61,8 @@ extern "C" {
 /* Vision-Transformer shape.  Replaces the role `net::net_data` (def/defines.h:14-23) plays
  * for the MLP: it is what sizes the device buffers (_init_kernel, netFPGA.cpp:402-441). */
 typedef struct vh_config {
-    int32_t image_size; /* square input side, e.g. 224                     */
+    int32_t image_size; /* square input side, e.g. 224; tokens = (image_size / patch_size)^2 + 1 <= 4097, and
+                         * max_batch x tokens <= 640 x 2^20                                                   */
     int32_t patch_size; /* e.g. 16                                         */
     int32_t channels;   /* 3                                               */
     int32_t dim;        /* D, hidden size (multiple of 64)                 */
@@ -342,6 +343,11 @@ int vh_op_layernorm(const float* x_dev, int64_t rows, int dim, int64_t row_strid
 #define VH_ATTN_Q_SCALE 0.18033688011112042f
 int vh_op_attention(const void* qkv16_dev, int batch, int tokens, int heads, void* out16_dev,
                     int dtype, void* stream);
+/* The K/V-streaming attention kernel on its own: the same operation as vh_op_attention, for any tokens in 1..4097 and
+ * heads <= 32 (vh_op_attention uses it itself above 640 tokens, where a head's K and V no longer fit in LDS; this tap
+ * runs it at every token count).  dtype VH_DTYPE_FP8: bf16 q|k|v in, e4m3 out [batch*tokens, heads*64]. */
+int vh_op_attention_stream(const void* qkv16_dev, int batch, int tokens, int heads, void* out16_dev,
+                           int dtype, void* stream);
 /* NHWC fp32 images -> patch matrix [batch*np, patch*patch*channels] in `dtype` */
 int vh_op_im2col(const float* in_nhwc_dev, int batch, int image, int patch, int channels,
                  void* out16_dev, int dtype, void* stream);

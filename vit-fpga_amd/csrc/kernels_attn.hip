@@ -976,6 +976,8 @@ hipError_t launch_attention(const void* qkv16, int batch, int tokens, int heads,
         return dtype == VH_DTYPE_BF16 ? launch_attn_t<BF16, BF16, true>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed)
                                       : launch_attn_t<FP16, FP16, true>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed);
     }
+    // a head's K and V do not fit in LDS (tokens > 640): the K/V-streaming kernel (kernels_attn_stream.hip; no ticket)
+    if (attention_lds_bytes(tokens) > 160 * 1024) return launch_attention_stream(qkv16, batch, tokens, heads, out16, dtype, s);
     if (dtype == VH_DTYPE_FP8) return launch_attn_t<BF16, E4M3>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed);  // bf16 in, e4m3 out
     return dtype == VH_DTYPE_BF16 ? launch_attn_t<BF16>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed)
                                   : launch_attn_t<FP16>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed);

@@ -83,6 +83,12 @@ bool attention_tiled_applies(int batch, int tokens, int heads);
 // class-token query only: out16 [batch][heads * 64] (VH_FLAG_CLS_TAIL); 16-bit dtypes, tokens <= 1024
 hipError_t launch_attention_cls(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, hipStream_t stream);
 size_t attention_lds_bytes(int tokens);
+// K/V-streaming attention (kernels_attn_stream.hip): the same operation in a fixed 24 KiB LDS ring, any token count
+// 1..kAttnStreamMaxTokens, heads <= 32, row-major q|k|v and output; dtype VH_DTYPE_FP8 = bf16 in, e4m3 out.  No work-queue
+// counter and no allocation (graph capture, split batches).  launch_attention sends a row-major call here when the resident
+// forms cannot hold the head (attention_lds_bytes(tokens) > 160 KiB).
+constexpr int kAttnStreamMaxTokens = 4097;   // 64 x 64 patches + the class token
+hipError_t launch_attention_stream(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, hipStream_t stream);
 hipError_t launch_im2col(const float* in_nhwc, int batch, int image, int patch, int channels,
                          void* out16, int dtype, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's

@@ -129,8 +129,11 @@ const char* check_config(const vh_config& c) {
     // allocation: vh_blob_file_config feeds this function)
     if (c.image_size > 4096 || c.patch_size > 256 || c.channels > 64) return "image_size <= 4096, patch_size <= 256, channels <= 64";
     if (c.layers > 4096 || c.classes > (1 << 20) || c.mlp_dim > (1 << 16) || c.max_batch > (1 << 20)) return "layers <= 4096, classes <= 2^20, mlp_dim <= 2^16, max_batch <= 2^20";
+    // tokens: up to 64 x 64 patches + the class token (the K/V-streaming attention's range); rows: at most 640 x 2^20, the
+    // largest row count (max_batch x tokens) any model reached while the attention was bounded at 640 tokens
     const int g = c.image_size / c.patch_size;
-    if (attention_lds_bytes(g * g + 1) > 160 * 1024) return "token count too large for the LDS-resident attention kernel";
+    if (g > 64) return "tokens <= 4097 (image_size / patch_size <= 64)";
+    if ((int64_t)c.max_batch * (g * g + 1) > (640ll << 20)) return "max_batch x tokens <= 640 x 2^20";
     return nullptr;
 }
 
@@ -1800,7 +1803,8 @@ int vh_op_layernorm(const float* x, int64_t rows, int dim, int64_t row_stride, c
 }
 int vh_op_attention(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, void* stream) {
     if (!qkv16 || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
-    if (batch <= 0 || tokens <= 0 || heads <= 0 || attention_lds_bytes(tokens) > 160 * 1024)
+    if (batch <= 0 || tokens <= 0 || heads <= 0 || tokens > kAttnStreamMaxTokens ||
+        (attention_lds_bytes(tokens) > 160 * 1024 && heads > 32))
         return fail(nullptr, VH_ERR_INVALID, "attention: unsupported shape");
     // The work-queue counter is owned by THIS call (allocated, used, freed): taps may run concurrently from several host
     // threads, and a context carries its own counters in its arena.
@@ -1810,6 +1814,16 @@ int vh_op_attention(const void* qkv16, int batch, int tokens, int heads, void* o
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     hipFree(ticket);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "attention failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+int vh_op_attention_stream(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, void* stream) {
+    if (!qkv16 || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
+    if (batch <= 0 || tokens <= 0 || tokens > kAttnStreamMaxTokens || heads <= 0 || heads > 32)
+        return fail(nullptr, VH_ERR_INVALID, "attention_stream: unsupported shape");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8)
+        return fail(nullptr, VH_ERR_INVALID, "attention_stream: unsupported dtype");
+    OPCHK(launch_attention_stream(qkv16, batch, tokens, heads, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_op_im2col(const float* in, int batch, int image, int patch, int channels, void* out16, int dtype, void* stream) {

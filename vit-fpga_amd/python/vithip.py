@@ -107,6 +107,7 @@ SYMBOLS = {
     "vh_op_fold_ln": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "vh_op_layernorm": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _i, _vp]),
     "vh_op_attention": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
+    "vh_op_attention_stream": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
@@ -682,6 +683,11 @@ def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr
 
 def op_attention(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
     _check(lib().vh_op_attention(qkv_ptr, batch, tokens, heads, out_ptr, dtype, None))
+
+
+def op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
+    """The K/V-streaming attention kernel at any token count 1..4097 (op_attention uses it above 640 tokens)."""
+    _check(lib().vh_op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype, None))
 
 
 def op_im2col(in_ptr, batch, image, patch, channels, out_ptr, dtype):
