@@ -63,8 +63,9 @@ extern "C" {
 typedef struct vh_config {
     int32_t image_size; /* square input side, e.g. 224; tokens = (image_size / patch_size)^2 + 1 <= 4097, and
                          * max_batch x tokens <= 640 x 2^20                                                   */
-    int32_t patch_size; /* e.g. 16                                         */
-    int32_t channels;   /* 3                                               */
+    int32_t patch_size; /* any divisor of image_size up to 256, e.g. 14 or 16 (the patch GEMM runs on the patch
+                         * vector patch^2 * channels zero-padded to a multiple of 64)                         */
+    int32_t channels;   /* 1..64, e.g. 3                                   */
     int32_t dim;        /* D, hidden size (multiple of 64)                 */
     int32_t heads;      /* H, dim/heads must be 64                         */
     int32_t mlp_dim;    /* M (multiple of 64)                              */
@@ -351,6 +352,11 @@ int vh_op_attention_stream(const void* qkv16_dev, int batch, int tokens, int hea
 /* NHWC fp32 images -> patch matrix [batch*np, patch*patch*channels] in `dtype` */
 int vh_op_im2col(const float* in_nhwc_dev, int batch, int image, int patch, int channels,
                  void* out16_dev, int dtype, void* stream);
+/* The same for any patch and channel count: patch matrix [batch*np, kpad] in `dtype` (VH_DTYPE_BF16 or VH_DTYPE_FP16),
+ * columns patch*patch*channels .. kpad-1 zero.  kpad >= patch*patch*channels and a multiple of 8 (the forward uses the
+ * patch vector rounded up to 64).  vh_op_im2col needs patch*channels to be a multiple of 4 and writes no padding. */
+int vh_op_im2col_padded(const float* in_nhwc_dev, int batch, int image, int patch, int channels, int kpad,
+                        void* out16_dev, int dtype, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,

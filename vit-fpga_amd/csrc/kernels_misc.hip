@@ -102,9 +102,52 @@ im2col_kernel(const float* __restrict__ in, typename T::elem* __restrict__ out, 
     }
 }
 
-hipError_t launch_im2col(const float* in, int batch, int image, int patch, int channels, void* out16, int dtype,
+// ---- im2col + cast into a row padded to kpad columns (any patch * ch; kpad >= patch^2 * ch, 8 | kpad) ---------------------
+// one thread owns 8 consecutive output elements and stores them as one 16-byte vector; consecutive lanes own consecutive
+// chunks of a row.  Element k is (ky, kx, c) of the same k order as im2col_kernel; columns kp <= k < kpad are written as
+// zero on every call (the patch-matrix buffer is scratch for the class-token tail in between).
+template <typename T>
+__global__ void __launch_bounds__(256)
+im2col_pad_kernel(const float* __restrict__ in, typename T::elem* __restrict__ out, int64_t n8, int image, int patch,
+                  int ch, int kpad) {
+    const int pc = patch * ch;               // floats per patch row: contiguous in the image
+    const int kp = patch * pc;
+    const int cpr = kpad / 8;                // chunks per output row
+    const int g = image / patch;
+    for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < n8; f += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t orow = f / cpr;        // (b * g + py) * g + px
+        const int k0 = (int)(f - orow * cpr) * 8;
+        const int64_t b = orow / (g * g);
+        const int p = (int)(orow - b * g * g);
+        const int py = p / g, px = p - py * g;
+        const float* src = in + ((b * image + (int64_t)py * patch) * image + (int64_t)px * patch) * ch;
+        int ky = k0 / pc, r = k0 - ky * pc;
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            v[i] = k0 + i < kp ? src[((int64_t)ky * image) * ch + r] : 0.f;
+            if (++r == pc) { r = 0; ++ky; }
+        }
+        const typename T::vec4 lo = pack4<T>(v[0], v[1], v[2], v[3]), hi = pack4<T>(v[4], v[5], v[6], v[7]);
+        *(typename T::vec8*)(out + f * 8) = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+}
+
+hipError_t launch_im2col(const float* in, int batch, int image, int patch, int channels, int kpad, void* out16, int dtype,
                          hipStream_t s) {
-    if ((patch * channels) % 4 || image % patch) return hipErrorInvalidValue;
+    if (patch <= 0 || image % patch) return hipErrorInvalidValue;
+    const int kp = patch * patch * channels;
+    if (kpad != kp || (patch * channels) % 4) {
+        if (kpad < kp || kpad % 8) return hipErrorInvalidValue;
+        const int g = image / patch;
+        const int64_t n8 = (int64_t)batch * g * g * (kpad / 8);
+        const unsigned grid = (unsigned)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384);
+        if (dtype == VH_DTYPE_BF16)
+            hipLaunchKernelGGL(im2col_pad_kernel<BF16>, dim3(grid), dim3(256), 0, s, in, (BF16::elem*)out16, n8, image, patch, channels, kpad);
+        else
+            hipLaunchKernelGGL(im2col_pad_kernel<FP16>, dim3(grid), dim3(256), 0, s, in, (FP16::elem*)out16, n8, image, patch, channels, kpad);
+        return hipGetLastError();
+    }
     const int64_t n4 = (int64_t)batch * image * image * channels / 4;
     const unsigned grid = (unsigned)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
     if (dtype == VH_DTYPE_BF16)
@@ -356,7 +399,26 @@ permute_patch_kernel(const float* __restrict__ w, int dim, int ch, int patch, ty
     const int c = k % ch, kx = (k / ch) % patch, ky = k / (ch * patch);
     o[i] = (typename T::elem)w[(((int64_t)d * ch + c) * patch + ky) * patch + kx];
 }
-hipError_t launch_permute_patch(const float* w, int dim, int channels, int patch, void* w16, int dtype, hipStream_t s) {
+// the same into rows of kpad columns, zeros in the columns kp <= k < kpad
+template <typename T>
+__global__ void __launch_bounds__(256)
+permute_patch_pad_kernel(const float* __restrict__ w, int dim, int ch, int patch, int kpad, typename T::elem* __restrict__ o) {
+    const int kp = patch * patch * ch;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)dim * kpad) return;
+    const int d = (int)(i / kpad), k = (int)(i - (int64_t)d * kpad);
+    const int c = k % ch, kx = (k / ch) % patch, ky = k / (ch * patch);
+    o[i] = (typename T::elem)(k < kp ? w[(((int64_t)d * ch + c) * patch + ky) * patch + kx] : 0.f);
+}
+hipError_t launch_permute_patch(const float* w, int dim, int channels, int patch, int kpad, void* w16, int dtype, hipStream_t s) {
+    if (kpad != patch * patch * channels || (patch * channels) % 4) {
+        if (kpad < patch * patch * channels) return hipErrorInvalidValue;
+        const int64_t n = (int64_t)dim * kpad;
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        if (dtype == VH_DTYPE_BF16) hipLaunchKernelGGL(permute_patch_pad_kernel<BF16>, grid, block, 0, s, w, dim, channels, patch, kpad, (BF16::elem*)w16);
+        else hipLaunchKernelGGL(permute_patch_pad_kernel<FP16>, grid, block, 0, s, w, dim, channels, patch, kpad, (FP16::elem*)w16);
+        return hipGetLastError();
+    }
     const int64_t n = (int64_t)dim * patch * patch * channels;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (dtype == VH_DTYPE_BF16) hipLaunchKernelGGL(permute_patch_kernel<BF16>, grid, block, 0, s, w, dim, channels, patch, (BF16::elem*)w16);

@@ -89,7 +89,9 @@ size_t attention_lds_bytes(int tokens);
 // forms cannot hold the head (attention_lds_bytes(tokens) > 160 KiB).
 constexpr int kAttnStreamMaxTokens = 4097;   // 64 x 64 patches + the class token
 hipError_t launch_attention_stream(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, hipStream_t stream);
-hipError_t launch_im2col(const float* in_nhwc, int batch, int image, int patch, int channels,
+// patch matrix [batch*np, kpad] of NHWC fp32 images.  kpad == patch^2 * channels with 4 | patch * channels: im2col_kernel
+// (one float4 per thread); otherwise im2col_pad_kernel (kpad >= patch^2 * channels, 8 | kpad, zeros in the pad columns)
+hipError_t launch_im2col(const float* in_nhwc, int batch, int image, int patch, int channels, int kpad,
                          void* out16, int dtype, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
@@ -113,7 +115,8 @@ hipError_t launch_quantize_rows(const float* w, int rows, int cols, float post, 
 hipError_t launch_pack_qkv(const float* qw, const float* qb, const float* kw, const float* kb,
                            const float* vw, const float* vb, int dim, float q_scale, void* w16,
                            float* b32, int dtype, hipStream_t stream);
-hipError_t launch_permute_patch(const float* w_nchw, int dim, int channels, int patch, void* w16,
+// conv weight [D][C][P][P] -> [D][kpad] in the im2col k order; the same two forms as launch_im2col
+hipError_t launch_permute_patch(const float* w_nchw, int dim, int channels, int patch, int kpad, void* w16,
                                 int dtype, hipStream_t stream);
 // folded LayerNorm helpers
 // amax_guard (optional, e4m3 rows only): running maximum of |x| over the first guard_rows rows, as float bits

@@ -70,7 +70,8 @@ struct LayerOff {  // offsets in floats from the start of the parameter region
 };
 
 struct Layout {
-    int T, NP, KP;
+    int T, NP, KP;   // KP = patch^2 * channels: the patch vector in the blob
+    int KPA;         // KP rounded up to 64: the compute width of the 16-bit patch operands (wp16, col16, the patch GEMM's K)
     size_t patch_w, patch_b, cls, pos, lnfw, lnfb, headw, headb, total;
     std::vector<LayerOff> layer;
 };
@@ -82,6 +83,7 @@ Layout make_layout(const vh_config& c) {
     L.NP = g * g;
     L.T = L.NP + 1;
     L.KP = c.patch_size * c.patch_size * c.channels;
+    L.KPA = (L.KP + 63) / 64 * 64;
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += n; return r; };
     L.patch_w = take(D * L.KP); L.patch_b = take(D); L.cls = take(D); L.pos = take((size_t)L.T * D);
@@ -109,8 +111,7 @@ size_t blob_bytes_of(const vh_config& c) {
 
 const char* check_config(const vh_config& c) {
     if (c.image_size <= 0 || c.patch_size <= 0 || c.image_size % c.patch_size) return "image_size must be a positive multiple of patch_size";
-    if (c.channels <= 0 || (c.patch_size * c.channels) % 4) return "patch_size*channels must be a multiple of 4";
-    if ((c.patch_size * c.patch_size * c.channels) % 64) return "patch_size^2*channels must be a multiple of 64";
+    if (c.channels <= 0) return "channels must be positive";
     if (c.dim <= 0 || c.dim % 64) return "dim must be a multiple of 64";
     if (c.heads <= 0 || c.dim != c.heads * 64) return "dim/heads must be 64";
     if (c.mlp_dim <= 0 || c.mlp_dim % 64) return "mlp_dim must be a multiple of 64";
@@ -160,7 +161,7 @@ struct vh_ctx {
     char* blob = nullptr;
     float* params = nullptr;  // blob + 64
     char* w16 = nullptr;      // arena of 16-bit matrices
-    void* wp16 = nullptr;     // [D, KP]
+    void* wp16 = nullptr;     // [D, KPA]
     std::vector<void*> wqkv16, wo16, w1_16, w2_16;
     // fc2's weights once more in the 16-row-blocked layout of the tiled hidden activation (h_tiled; 16-bit folded path): the MLP
     // hidden activation then leaves fc1's epilogue straight from the registers (gemm_epilogue.h OTILED) and fc2's operand DMA reads
@@ -209,7 +210,7 @@ struct vh_ctx {
     void* qkv16 = nullptr;    //                 [B*T, 3D]
     void* att16 = nullptr;    //                 [B*T, D]
     void* h16 = nullptr;      //                 [B*T, M]
-    void* col16 = nullptr;    // patch matrix    [B*NP, KP]
+    void* col16 = nullptr;    // patch matrix    [B*NP, KPA]
     float* clsn32 = nullptr;  // final-LN'd CLS  [B, D] fp32 (the head runs in fp32 on the blob's own weights)
     float* in_dev = nullptr;  // staging for the host-pointer forward
     float* logits_dev = nullptr;
@@ -300,7 +301,7 @@ int prepare_weights(vh_ctx* c) {
     const int D = f.dim, M = f.mlp_dim;
     hipStream_t s = c->stream;
     const float* P = c->params;
-    HIPCHK(&c->err, launch_permute_patch(P + L.patch_w, D, f.channels, f.patch_size, c->wp16, c->dt16, s));
+    HIPCHK(&c->err, launch_permute_patch(P + L.patch_w, D, f.channels, f.patch_size, L.KPA, c->wp16, c->dt16, s));
     for (int l = 0; l < f.layers && c->fp8 && c->ln_fold; ++l) {
         // folded LayerNorm on e4m3 operands: W' = gamma o W through the row quantiser, its scales, c and d (launch_fold_ln_f8)
         const LayerOff& o = L.layer[l];
@@ -436,7 +437,7 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
     char* const qkv16 = (char*)c->qkv16 + r0 * 3 * D * esz;
     char* const att16 = (char*)c->att16 + r0 * D * esz_op;
     char* const h16 = (char*)c->h16 + r0 * M * esz_op;
-    char* const col16 = (char*)c->col16 + (size_t)img0 * L.NP * L.KP * esz;
+    char* const col16 = (char*)c->col16 + (size_t)img0 * L.NP * L.KPA * esz;
     float* const clsn32 = c->clsn32 + (size_t)img0 * D;
     // the attention launches' work-queue counters: one word per layer, all zeroed by ONE memset per forward (a memset per
     // launch is a 5 us fill kernel in front of every attention kernel)
@@ -486,11 +487,17 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
     // Patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip; the split residual of the 16-bit paths):
     // VH_PATCH_FUSED=1 selects it -- measured, DESIGN.md 4.4 -- the default is the im2col pass + the persistent GEMM.
     const bool fused_patch = c->patch_fused && c->split && !c->fp8 && nl > 0 && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
-    if (!fused_patch) HIPCHK(&c->err, launch_im2col(in, batch, f.image_size, f.patch_size, f.channels, col16, dt16, s));
+    if (!fused_patch) {
+        if ((rc = tmark(ST_IM2COL))) return rc;
+        HIPCHK(&c->err, launch_im2col(in, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
+        if ((rc = tmark(ST_IM2COL))) return rc;
+    }
     if ((rc = mark(ST_IM2COL))) return rc;
     if (fused_patch) {
+        if ((rc = tmark(ST_PATCH))) return rc;
         HIPCHK(&c->err, launch_patch_fused(in, batch, f.image_size, f.patch_size, f.channels, c->wp16, P + L.patch_b, P + L.pos, xn16, xlo16,
                                            partials_p, rows_g, D, dt16, s));
+        if ((rc = tmark(ST_PATCH))) return rc;
         if ((rc = mark(ST_PATCH))) return rc;
         HIPCHK(&c->err, launch_cls_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, batch, T, D, dt16, s));
         if ((rc = mark(ST_CLS))) return rc;
@@ -501,16 +508,20 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         // partial sums (PATCH_SPLIT epilogue; the class-token rows from their own small kernel) -- no fp32 x, no separate
         // row-statistics pass over it (round 3: -0.1 ms per forward).  The partial sums are laid out for rows_g rows, like
         // every later layer's.
-        GemmArgs g{col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KP, VH_EPI_PATCH_SPLIT, P + L.pos, L.NP, dt16, 0};
+        GemmArgs g{col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, P + L.pos, L.NP, dt16, 0};
         g.out16 = xlo16; g.partials = partials_p; g.prow = rows_g;
+        if ((rc = tmark(ST_PATCH))) return rc;
         HIPCHK(&c->err, launch_gemm(g, s));
+        if ((rc = tmark(ST_PATCH))) return rc;
         if ((rc = mark(ST_PATCH))) return rc;
         HIPCHK(&c->err, launch_cls_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, batch, T, D, dt16, s));
         if ((rc = mark(ST_CLS))) return rc;
         HIPCHK(&c->err, launch_finalize_stats(partials_p, D / 64, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
         if ((rc = mark(ST_LNSTATS))) return rc;
     } else {
-        HIPCHK(&c->err, gemm(col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KP, VH_EPI_PATCH, P + L.pos, L.NP));
+        if ((rc = tmark(ST_PATCH))) return rc;
+        HIPCHK(&c->err, gemm(col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, P + L.pos, L.NP));
+        if ((rc = tmark(ST_PATCH))) return rc;
         if ((rc = mark(ST_PATCH))) return rc;
         HIPCHK(&c->err, launch_cls_rows(x, P + L.cls, P + L.pos, batch, T, D, s));
         if ((rc = mark(ST_CLS))) return rc;
@@ -525,7 +536,7 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
     }
     // the class-token tail needs the split planes of the folded 16-bit path, the whole model, and room in the patch-matrix buffer
     const bool tail = c->cls_tail && c->ln_fold && c->split && !c->fp8 && nl == f.layers && c->run_layers < 0 && T <= 1024 &&
-                      (size_t)L.NP * L.KP * esz >= 2 * ((size_t)D * esz + 256);
+                      (size_t)L.NP * L.KPA * esz >= 2 * ((size_t)D * esz + 256);
     // tiled hidden activation: both MLP GEMMs must take the persistent form (whole 256-row tiles, enough of them), the 16-bit split path
     const bool h_tiled = c->h_tiled && c->split && !c->fp8 && c->weights_ready_tiled && gemm_tiled_applies(rows_g, M, D) && gemm_tiled_applies(rows_g, D, M);
     // e4m3 operands: the e4m3 hidden activation in the tiled layout of the e4m3 operand (fc1's epilogue writes it, fc2's DMA reads it)
@@ -979,7 +990,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     // 16-bit weights
     size_t w16_bytes = 0;
     auto carve16 = [&](size_t elems) { size_t o = w16_bytes; w16_bytes += align_up(elems * 2, 256); return o; };
-    const size_t o_wp = carve16(D * L.KP);
+    const size_t o_wp = carve16(D * L.KPA);
     std::vector<size_t> o_qkv(cfg->layers), o_o(cfg->layers), o_1(cfg->layers), o_2(cfg->layers), o_2t(cfg->layers);
     const bool want_tiled_any = D % 256 == 0 && M % 256 == 0 && !(getenv("VH_H_TILED") && getenv("VH_H_TILED")[0] == '0');
     const bool want_tiled = cfg->dtype != VH_DTYPE_FP8 && want_tiled_any;
@@ -1048,7 +1059,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     // so the padding may reach up to 255 rows past the last real row
     const size_t rows_p = rows + 256;
     const size_t o_x = carve(rows_p * D * 4), o_xn = carve(rows_p * D * 2), o_qkvA = carve(rows_p * 3 * D * 2),
-                 o_att = carve(rows_p * D * 2), o_h = carve(rows_p * M * 2), o_col = carve(B * L.NP * (size_t)L.KP * 2),
+                 o_att = carve(rows_p * D * 2), o_h = carve(rows_p * M * 2), o_col = carve(B * L.NP * (size_t)L.KPA * 2),
                  o_cls = carve(B * D * 4),
                  o_in = carve(B * (size_t)cfg->image_size * cfg->image_size * cfg->channels * 4), o_lg = carve(B * C * 4),
                  o_st = carve(rows_p * 2 * 4), o_pt = carve((D / 64 + 1) * rows_p * 2 * 4), o_xlo = carve(rows_p * D * 2),   // lo plane: one byte per element (16-bit paths) or bf16 (fp8 path)
@@ -1830,7 +1841,18 @@ int vh_op_im2col(const float* in, int batch, int image, int patch, int channels,
     if (!in || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
     if (batch <= 0 || patch <= 0 || image <= 0 || image % patch || (patch * channels) % 4)
         return fail(nullptr, VH_ERR_INVALID, "im2col: unsupported shape");
-    OPCHK(launch_im2col(in, batch, image, patch, channels, out16, dtype, (hipStream_t)stream));
+    OPCHK(launch_im2col(in, batch, image, patch, channels, patch * patch * channels, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_im2col_padded(const float* in, int batch, int image, int patch, int channels, int kpad, void* out16, int dtype,
+                        void* stream) {
+    if (!in || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
+    if (batch <= 0 || patch <= 0 || image <= 0 || image % patch || channels <= 0 || patch > 256 || channels > 64 ||
+        kpad < patch * patch * channels || kpad % 8)
+        return fail(nullptr, VH_ERR_INVALID, "im2col_padded: unsupported shape");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16) return fail(nullptr, VH_ERR_INVALID, "im2col_padded: unsupported dtype");
+    OPCHK(launch_im2col(in, batch, image, patch, channels, kpad, out16, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }

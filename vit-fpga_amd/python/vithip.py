@@ -109,6 +109,7 @@ SYMBOLS = {
     "vh_op_attention": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_stream": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -692,6 +693,12 @@ def op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
 
 def op_im2col(in_ptr, batch, image, patch, channels, out_ptr, dtype):
     _check(lib().vh_op_im2col(in_ptr, batch, image, patch, channels, out_ptr, dtype, None))
+
+
+def op_im2col_padded(in_ptr, batch, image, patch, channels, kpad, out_ptr, dtype):
+    """Patch matrix [batch*np, kpad] for any patch and channel count: columns patch^2*channels..kpad-1 are zero.
+    kpad >= patch^2*channels and a multiple of 8; dtype bf16 or fp16."""
+    _check(lib().vh_op_im2col_padded(in_ptr, batch, image, patch, channels, kpad, out_ptr, dtype, None))
 
 
 def op_cast(in_ptr, out_ptr, n, dtype):
