@@ -67,7 +67,7 @@ typedef struct vh_config {
                          * vector patch^2 * channels zero-padded to a multiple of 64)                         */
     int32_t channels;   /* 1..64, e.g. 3                                   */
     int32_t dim;        /* D, hidden size (multiple of 64)                 */
-    int32_t heads;      /* H, dim/heads must be 64                         */
+    int32_t heads;      /* H, divides dim; head dim dim/heads is 32, 48, 64, 80, 96, 112 or 128 */
     int32_t mlp_dim;    /* M (multiple of 64)                              */
     int32_t layers;     /* L                                               */
     int32_t classes;    /* C (multiple of 4)                               */
@@ -349,6 +349,11 @@ int vh_op_attention(const void* qkv16_dev, int batch, int tokens, int heads, voi
  * runs it at every token count).  dtype VH_DTYPE_FP8: bf16 q|k|v in, e4m3 out [batch*tokens, heads*64]. */
 int vh_op_attention_stream(const void* qkv16_dev, int batch, int tokens, int heads, void* out16_dev,
                            int dtype, void* stream);
+/* Attention at head dims 32, 48, ..., 128 (the kernel the forward runs for every head dim other than 64; this tap runs it
+ * at 64 as well): qkv16 [batch*tokens, 3*heads*head_dim] -> out16 [batch*tokens, heads*head_dim], q pre-scaled by
+ * head_dim^-1/2 * log2(e), tokens 1..4097, heads*head_dim <= 2048.  dtype VH_DTYPE_FP8: bf16 q|k|v in, e4m3 out. */
+int vh_op_attention_hd(const void* qkv16_dev, int batch, int tokens, int heads, int head_dim, void* out16_dev,
+                       int dtype, void* stream);
 /* NHWC fp32 images -> patch matrix [batch*np, patch*patch*channels] in `dtype` */
 int vh_op_im2col(const float* in_nhwc_dev, int batch, int image, int patch, int channels,
                  void* out16_dev, int dtype, void* stream);

@@ -89,6 +89,18 @@ size_t attention_lds_bytes(int tokens);
 // forms cannot hold the head (attention_lds_bytes(tokens) > 160 KiB).
 constexpr int kAttnStreamMaxTokens = 4097;   // 64 x 64 patches + the class token
 hipError_t launch_attention_stream(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, hipStream_t stream);
+// K/V-streaming attention at head dims 32, 48, ..., 128 (kernels_attn_hd.hip): row-major q|k|v [batch*tokens][3*heads*head_dim]
+// with q pre-scaled by head_dim^-1/2 * log2(e) (attention_q_scale) -> row-major [batch*tokens][heads*head_dim]; tokens
+// 1..kAttnStreamMaxTokens, heads * head_dim <= kAttnHdMaxWidth; dtype VH_DTYPE_FP8 = bf16 in, e4m3 out.  No work-queue counter,
+// no allocation.  The forward uses it for every head dim other than 64.
+constexpr int kAttnHdMaxWidth = 2048;
+bool attention_hd_supported(int head_dim);
+hipError_t launch_attention_hd(const void* qkv16, int batch, int tokens, int heads, int head_dim, void* out16, int dtype,
+                               hipStream_t stream);
+// the factor folded into Wq and bq: head_dim^-1/2 * log2(e); exactly kAttnQScale at head dim 64
+inline float attention_q_scale(int head_dim) {
+    return head_dim == 64 ? kAttnQScale : (float)(1.4426950408889634 / __builtin_sqrt((double)head_dim));
+}
 // patch matrix [batch*np, kpad] of NHWC fp32 images.  kpad == patch^2 * channels with 4 | patch * channels: im2col_kernel
 // (one float4 per thread); otherwise im2col_pad_kernel (kpad >= patch^2 * channels, 8 | kpad, zeros in the pad columns)
 hipError_t launch_im2col(const float* in_nhwc, int batch, int image, int patch, int channels, int kpad,

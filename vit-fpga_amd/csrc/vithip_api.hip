@@ -113,7 +113,8 @@ const char* check_config(const vh_config& c) {
     if (c.image_size <= 0 || c.patch_size <= 0 || c.image_size % c.patch_size) return "image_size must be a positive multiple of patch_size";
     if (c.channels <= 0) return "channels must be positive";
     if (c.dim <= 0 || c.dim % 64) return "dim must be a multiple of 64";
-    if (c.heads <= 0 || c.dim != c.heads * 64) return "dim/heads must be 64";
+    if (c.heads <= 0 || c.dim % c.heads) return "dim must be a multiple of heads";
+    if (!attention_hd_supported(c.dim / c.heads)) return "head dim (dim/heads) must be 32, 48, 64, 80, 96, 112 or 128";
     if (c.mlp_dim <= 0 || c.mlp_dim % 64) return "mlp_dim must be a multiple of 64";
     if (c.dim > 2048) return "dim > 2048 unsupported";
     if (c.layers <= 0) return "layers must be positive";
@@ -187,7 +188,9 @@ struct vh_ctx {
     // 3 B per element each way instead of the fp32 array plus its 16-bit copy.
     // VH_RESID_SPLIT=0 (A/B tools) keeps the fp32 array.
     bool split = false;
-    bool cls_tail = false;    // VH_FLAG_CLS_TAIL: the last layer computes the class-token rows only (folded 16-bit path)
+    bool cls_tail = false;    // VH_FLAG_CLS_TAIL: the last layer computes the class-token rows only (folded 16-bit path, head dim 64)
+    int head_dim = 64;        // dim / heads: 64 takes launch_attention and its layouts, any other launch_attention_hd (row-major)
+    float q_scale = kAttnQScale;   // head_dim^-1/2 * log2(e), folded into Wq and bq (attention_q_scale)
     bool patch_fused = false; // VH_PATCH_FUSED=1 (read when the context is created): patch gather inside the GEMM's A loader
     void* xlo16 = nullptr;    // [B*T, D] bytes
     // Run-time guard on the fold: the kernels that produce the row statistics keep a running maximum of
@@ -308,7 +311,7 @@ int prepare_weights(vh_ctx* c) {
         float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M);
         char* wq = (char*)c->wqkv16[l];
         const size_t dd = (size_t)D * D;
-        HIPCHK(&c->err, launch_fold_ln_f8(P + o.qw, P + o.qb, P + o.ln1w, P + o.ln1b, D, D, kAttnQScale, wq, c->sqkv[l], cd, cd + 3 * D, s));
+        HIPCHK(&c->err, launch_fold_ln_f8(P + o.qw, P + o.qb, P + o.ln1w, P + o.ln1b, D, D, c->q_scale, wq, c->sqkv[l], cd, cd + 3 * D, s));
         HIPCHK(&c->err, launch_fold_ln_f8(P + o.kw, P + o.kb, P + o.ln1w, P + o.ln1b, D, D, 1.0f, wq + dd, c->sqkv[l] + D, cd + D, cd + 4 * D, s));
         HIPCHK(&c->err, launch_fold_ln_f8(P + o.vw, P + o.vb, P + o.ln1w, P + o.ln1b, D, D, 1.0f, wq + 2 * dd, c->sqkv[l] + 2 * D, cd + 2 * D, cd + 5 * D, s));
         HIPCHK(&c->err, launch_quantize_rows(P + o.ow, D, D, 1.0f, c->wo16[l], c->so[l], s));
@@ -320,12 +323,12 @@ int prepare_weights(vh_ctx* c) {
     for (int l = 0; l < f.layers && c->fp8 && !c->ln_fold; ++l) {
         const LayerOff& o = L.layer[l];
         // bias [bq/8 ; bk ; bv] from the 16-bit packer (its 16-bit matrix is overwritten right after), then
-        // e4m3 rows + scales; the softmax scale 64^-1/2 * log2(e) (kAttnQScale) goes into the q rows' fp32 scales
-        HIPCHK(&c->err, launch_pack_qkv(P + o.qw, P + o.qb, P + o.kw, P + o.kb, P + o.vw, P + o.vb, D, kAttnQScale,
+        // e4m3 rows + scales; the softmax scale head_dim^-1/2 * log2(e) (q_scale) goes into the q rows' fp32 scales
+        HIPCHK(&c->err, launch_pack_qkv(P + o.qw, P + o.qb, P + o.kw, P + o.kb, P + o.vw, P + o.vb, D, c->q_scale,
                                         c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, c->dt16, s));
         char* wq = (char*)c->wqkv16[l];
         const size_t dd = (size_t)D * D;
-        HIPCHK(&c->err, launch_quantize_rows(P + o.qw, D, D, kAttnQScale, wq, c->sqkv[l], s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.qw, D, D, c->q_scale, wq, c->sqkv[l], s));
         HIPCHK(&c->err, launch_quantize_rows(P + o.kw, D, D, 1.0f, wq + dd, c->sqkv[l] + D, s));
         HIPCHK(&c->err, launch_quantize_rows(P + o.vw, D, D, 1.0f, wq + 2 * dd, c->sqkv[l] + 2 * D, s));
         HIPCHK(&c->err, launch_quantize_rows(P + o.ow, D, D, 1.0f, c->wo16[l], c->so[l], s));
@@ -355,16 +358,16 @@ int prepare_weights(vh_ctx* c) {
         }
         const float* B = c->params;   // biases and LayerNorm parameters stay where they are
         if (c->ln_fold) {
-            // W' = gamma o W (q rows also carry the softmax scale kAttnQScale), c = row sums of W', d = beta.W + b
+            // W' = gamma o W (q rows also carry the softmax scale q_scale), c = row sums of W', d = beta.W + b
             float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M);
             char* wq = (char*)c->wqkv16[l];
             const size_t dd2 = (size_t)D * D * 2;
-            HIPCHK(&c->err, launch_fold_ln(P + o.qw, B + o.qb, B + o.ln1w, B + o.ln1b, D, D, kAttnQScale, wq, cd, cd + 3 * D, f.dtype, s));
+            HIPCHK(&c->err, launch_fold_ln(P + o.qw, B + o.qb, B + o.ln1w, B + o.ln1b, D, D, c->q_scale, wq, cd, cd + 3 * D, f.dtype, s));
             HIPCHK(&c->err, launch_fold_ln(P + o.kw, B + o.kb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + dd2, cd + D, cd + 4 * D, f.dtype, s));
             HIPCHK(&c->err, launch_fold_ln(P + o.vw, B + o.vb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + 2 * dd2, cd + 2 * D, cd + 5 * D, f.dtype, s));
             HIPCHK(&c->err, launch_fold_ln(P + o.f1w, B + o.f1b, B + o.ln2w, B + o.ln2b, M, D, 1.0f, c->w1_16[l], cd + 6 * D, cd + 6 * D + M, f.dtype, s));
         } else {
-            HIPCHK(&c->err, launch_pack_qkv(P + o.qw, B + o.qb, P + o.kw, B + o.kb, P + o.vw, B + o.vb, D, kAttnQScale,
+            HIPCHK(&c->err, launch_pack_qkv(P + o.qw, B + o.qb, P + o.kw, B + o.kb, P + o.vw, B + o.vb, D, c->q_scale,
                                             c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, f.dtype, s));
             HIPCHK(&c->err, launch_cast(P + o.f1w, c->w1_16[l], (int64_t)M * D, f.dtype, s));
         }
@@ -535,17 +538,20 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         }
     }
     // the class-token tail needs the split planes of the folded 16-bit path, the whole model, and room in the patch-matrix buffer
-    const bool tail = c->cls_tail && c->ln_fold && c->split && !c->fp8 && nl == f.layers && c->run_layers < 0 && T <= 1024 &&
+    // (head dim 64 only: the class-row kernel is 64 wide; other head dims run the full last layer)
+    const bool hd64 = c->head_dim == 64;
+    const bool tail = c->cls_tail && hd64 && c->ln_fold && c->split && !c->fp8 && nl == f.layers && c->run_layers < 0 && T <= 1024 &&
                       (size_t)L.NP * L.KPA * esz >= 2 * ((size_t)D * esz + 256);
     // tiled hidden activation: both MLP GEMMs must take the persistent form (whole 256-row tiles, enough of them), the 16-bit split path
     const bool h_tiled = c->h_tiled && c->split && !c->fp8 && c->weights_ready_tiled && gemm_tiled_applies(rows_g, M, D) && gemm_tiled_applies(rows_g, D, M);
     // e4m3 operands: the e4m3 hidden activation in the tiled layout of the e4m3 operand (fc1's epilogue writes it, fc2's DMA reads it)
     const bool h_tiled8 = c->h_tiled && c->split && c->fp8 && c->weights_ready_tiled && gemm_tiled_applies_f8(rows_g, M, D) && gemm_tiled_applies_f8(rows_g, D, M);
     // the attention output likewise (16-bit ring forms -> the out-projection's tiled operand DMA); VH_ATT_TILED=0 keeps it row-major
-    const bool att_tiled = h_tiled && c->att_tiled && gemm_tiled_applies(rows_g, D, D) && attention_tiled_applies(batch, T, f.heads) && !tail;
-    const bool att_tiled8 = h_tiled8 && c->att_tiled && gemm_tiled_applies_f8(rows_g, D, D) && attention_tiled_applies(batch, T, f.heads);
+    // (both 64-wide forms: any other head dim keeps q|k|v and the attention output row-major)
+    const bool att_tiled = hd64 && h_tiled && c->att_tiled && gemm_tiled_applies(rows_g, D, D) && attention_tiled_applies(batch, T, f.heads) && !tail;
+    const bool att_tiled8 = hd64 && h_tiled8 && c->att_tiled && gemm_tiled_applies_f8(rows_g, D, D) && attention_tiled_applies(batch, T, f.heads);
     // q|k|v head-major between the projection's epilogue and attention's operand DMA (same condition + the persistent form for N = 3 D)
-    const bool qkv_hm = c->qkv_hm && ((att_tiled && gemm_tiled_applies(rows_g, 3 * D, D)) || (att_tiled8 && gemm_tiled_applies_f8(rows_g, 3 * D, D)));
+    const bool qkv_hm = hd64 && c->qkv_hm && ((att_tiled && gemm_tiled_applies(rows_g, 3 * D, D)) || (att_tiled8 && gemm_tiled_applies_f8(rows_g, 3 * D, D)));
     c->last_h_tiled = (h_tiled || h_tiled8) && nl > 0 && c->ln_fold;
     c->last_qkv_hm = qkv_hm && nl > 0 && c->ln_fold;
     for (int l = 0; l < nl && c->ln_fold; ++l) {
@@ -596,8 +602,11 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
             return VH_OK;
         }
         if ((rc = tmark(ST_ATTN))) return rc;
-        HIPCHK(&c->err, launch_attention(qkv16, batch, T, f.heads, att16, c->fp8 ? VH_DTYPE_FP8 : dt16, tickets_part + l, s, true, att_tiled || att_tiled8,
-                                         qkv_hm ? (int64_t)rows_g : 0));
+        if (hd64)
+            HIPCHK(&c->err, launch_attention(qkv16, batch, T, f.heads, att16, c->fp8 ? VH_DTYPE_FP8 : dt16, tickets_part + l, s, true, att_tiled || att_tiled8,
+                                             qkv_hm ? (int64_t)rows_g : 0));
+        else
+            HIPCHK(&c->err, launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, c->fp8 ? VH_DTYPE_FP8 : dt16, s));
         if ((rc = tmark(ST_ATTN))) return rc;
         if ((rc = mark(ST_ATTN))) return rc;
         if ((rc = tmark(ST_PROJ))) return rc;
@@ -718,7 +727,8 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         if ((rc = tmark(ST_QKV))) return rc;
         if ((rc = mark(ST_QKV))) return rc;
         if ((rc = tmark(ST_ATTN))) return rc;
-        HIPCHK(&c->err, launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true));
+        if (c->head_dim == 64) HIPCHK(&c->err, launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true));
+        else HIPCHK(&c->err, launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, op_dt, s));
         if ((rc = tmark(ST_ATTN))) return rc;
         if ((rc = mark(ST_ATTN))) return rc;
         if ((rc = resid_gemm_ln(att16, c->wo16[l], P + o.ob, so, D, P + o.ln2w, P + o.ln2b, ST_PROJ))) return rc;
@@ -1027,6 +1037,8 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         c->ln_fold_cfg = c->ln_fold;
         c->split_cfg = c->split;
         c->cls_tail = (cfg->flags & VH_FLAG_CLS_TAIL) != 0;
+        c->head_dim = cfg->dim / cfg->heads;
+        c->q_scale = attention_q_scale(c->head_dim);
         c->h_tiled = want_tiled || want_tiled8;
         { const char* e = getenv("VH_ATT_TILED"); c->att_tiled = !(e && e[0] == '0'); }
         { const char* e = getenv("VH_QKV_HM"); c->qkv_hm = !(e && e[0] == '0'); }
@@ -1834,6 +1846,17 @@ int vh_op_attention_stream(const void* qkv16, int batch, int tokens, int heads, 
     if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8)
         return fail(nullptr, VH_ERR_INVALID, "attention_stream: unsupported dtype");
     OPCHK(launch_attention_stream(qkv16, batch, tokens, heads, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_attention_hd(const void* qkv16, int batch, int tokens, int heads, int head_dim, void* out16, int dtype, void* stream) {
+    if (!qkv16 || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
+    if (!attention_hd_supported(head_dim)) return fail(nullptr, VH_ERR_INVALID, "attention_hd: head_dim must be 32, 48, ..., 128");
+    if (batch <= 0 || tokens <= 0 || tokens > kAttnStreamMaxTokens || heads <= 0 || heads > kAttnHdMaxWidth / head_dim)
+        return fail(nullptr, VH_ERR_INVALID, "attention_hd: unsupported shape");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8)
+        return fail(nullptr, VH_ERR_INVALID, "attention_hd: unsupported dtype");
+    OPCHK(launch_attention_hd(qkv16, batch, tokens, heads, head_dim, out16, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }

@@ -108,6 +108,7 @@ SYMBOLS = {
     "vh_op_layernorm": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _i, _vp]),
     "vh_op_attention": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_stream": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
+    "vh_op_attention_hd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
@@ -689,6 +690,11 @@ def op_attention(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
 def op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
     """The K/V-streaming attention kernel at any token count 1..4097 (op_attention uses it above 640 tokens)."""
     _check(lib().vh_op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype, None))
+
+
+def op_attention_hd(qkv_ptr, batch, tokens, heads, head_dim, out_ptr, dtype):
+    """Attention at head dim 32, 48, ..., 128 (q pre-scaled by head_dim^-1/2 * log2(e)), any token count 1..4097."""
+    _check(lib().vh_op_attention_hd(qkv_ptr, batch, tokens, heads, head_dim, out_ptr, dtype, None))
 
 
 def op_im2col(in_ptr, batch, image, patch, channels, out_ptr, dtype):
