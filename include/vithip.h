@@ -120,6 +120,16 @@ typedef struct vh_config {
  * state returns them as of the layer before).  Folded 16-bit path only (ignored elsewhere).  Never used by the default bench
  * line: a forward that skips rows is reported as its own `cls_tail` object. */
 #define VH_FLAG_CLS_TAIL 8
+/* The two places where CLIP's vision towers differ from the canonical ViT block; independent of each other and of every flag above
+ * (OpenAI CLIP sets both, the LAION / OpenCLIP towers the first only).  They describe the MODEL, so the weight blob's header carries
+ * them too (flags word bit 1 = pre-LN, bit 2 = QuickGELU) and a blob whose bits differ from the context's is refused.
+ *   VH_FLAG_PRE_LN      a LayerNorm over the embedded tokens (patch embedding + class token + position embedding) in front of
+ *                       layer 0, CLIP's `ln_pre`.  The blob gains pre_ln.weight [D] and pre_ln.bias [D] directly after `pos`.
+ *   VH_FLAG_QUICK_GELU  the MLP activation is x * sigmoid(1.702 x) instead of erf GELU.  No tensor of its own.
+ * With patch.bias = 0, the final LayerNorm = ln_post and head = the visual projection (classes = embedding width, head.bias = 0)
+ * the logits of such a context are the CLIP image embedding. */
+#define VH_FLAG_PRE_LN 16
+#define VH_FLAG_QUICK_GELU 32
 
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
@@ -159,7 +169,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header.  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -177,7 +187,8 @@ int vh_export_weights_device(vh_ctx* ctx, void* dev_blob, size_t nbytes);
  * netFPGA.cpp:206-237, is a broken TODO and it has no file format).  The file is the canonical blob byte for
  * byte, plus an FNV-1a-64 checksum of the parameter bytes in header words that memory blobs leave zero.
  *   vh_blob_file_config: host only (no device needed) -- validates magic / shape / file length and fills the model
- *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create);
+ *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create;
+ *                        cfg->flags = the model bits VH_FLAG_PRE_LN / VH_FLAG_QUICK_GELU of the header);
  *   vh_save_weights_file: writes <path>.tmp then renames; vh_load_weights_file: verifies length, shape, checksum. */
 int vh_blob_file_config(const char* path, vh_config* cfg);
 /* host only: the file as a MEMORY blob (what vh_load_weights takes): length, header and checksum verified, checksum
@@ -290,6 +301,9 @@ int vh_debug_set_layers(vh_ctx* ctx, int n_layers);
                                 acc + bias + pos[tok(m)], plus that row's partial sums (partials[N/64][R][2], R = token rows) --
                                 EPI_PATCH and the first row-statistics pass in one epilogue.  out = hi, out16 = lo, aux /
                                 aux_i as EPI_PATCH; the class-token rows are not touched (vh_op_gemm_ex: R = images x tokens) */
+#define VH_EPI_BIAS_QGELU 10   /* out16[m,n] = qgelu(acc + bias[n]),  qgelu(v) = v * sigmoid(1.702 v); accepted wherever
+                                  VH_EPI_BIAS_GELU is, with the same shape rules                                           */
+#define VH_EPI_LNFOLD_QGELU 11 /* qgelu of VH_EPI_LNFOLD; accepted wherever VH_EPI_LNFOLD_GELU is                          */
 /* out = epilogue(A[M,K] * W[N,K]^T); A and W hold `dtype` elements, K contiguous.
  * aux: EPI_PATCH -> pos-emb fp32 [tokens, N] with aux_i = patches per image.
  * variant: 0 = auto, 1 = 128x128 tile, 2 = 256x256 two-stage, 5 = 256x256 ping-pong, 6 = persistent ping-pong. */
@@ -339,6 +353,15 @@ int vh_op_fold_ln(const float* w_dev, const float* b_dev, const float* gamma_dev
 int vh_op_layernorm(const float* x_dev, int64_t rows, int dim, int64_t row_stride,
                     const float* gamma_dev, const float* beta_dev, float eps, void* out16_dev,
                     int dtype, void* stream);
+/* The pre-LayerNorm of VH_FLAG_PRE_LN contexts on its own: y = LN(x[r, :]) * gamma + beta in fp32 for x fp32 [rows, dim]
+ * (dim % 4 == 0, dim <= 2048), written in the forms the forward's paths consume; each output pointer may be NULL, one of
+ * y32 / hi must be given, x may alias y32:
+ *   y32_dev   fp32 [rows, dim]                      the fp32 residual stream
+ *   hi_dev    `dtype` [rows, dim]                   T(y): the 16-bit (VH_DTYPE_FP8: e4m3) plane / operand copy
+ *   lo_dev    bytes [rows, dim] (VH_DTYPE_FP8: bf16) what that rounding dropped, as VH_EPI_RESID_SPLIT keeps it (needs hi_dev)
+ *   stats_dev [rows][2]                             (mean, rstd) of the NORMALISED row y: layer 0's LN1 statistics */
+int vh_op_pre_layernorm(const float* x_dev, int64_t rows, int dim, const float* gamma_dev, const float* beta_dev, float eps,
+                        float* y32_dev, void* hi_dev, void* lo_dev, float* stats_dev, int dtype, void* stream);
 /* qkv16 [batch*tokens, 3*heads*64] -> out16 [batch*tokens, heads*64].  The q columns arrive pre-scaled by
  * VH_ATTN_Q_SCALE = 64^-1/2 * log2(e) (the forward folds it into Wq/bq): the kernel's softmax works in the exp2 domain. */
 #define VH_ATTN_Q_SCALE 0.18033688011112042f

@@ -24,6 +24,7 @@
 #define I_CVTF32(i) "v_cvt_f32_f16 %" #i ", %8\n\t"
 #define I_CVTBF(i) "v_cvt_pk_bf16_f32 %" #i ", %8, %9\n\t"
 #define I_EXP(i) "v_exp_f32 %" #i ", %8\n\t"
+#define I_RCP(i) "v_rcp_f32 %" #i ", %8\n\t"
 #define I_PKADD32(i) "v_pk_add_f32 %" #i ", %8, %" #i "\n\t"
 #define I_PKMUL32(i) "v_pk_mul_f32 %" #i ", %8, %" #i "\n\t"
 #define I_MAX16(i) "v_pk_max_f16 %" #i ", %8, %" #i "\n\t"
@@ -64,7 +65,7 @@ __global__ void __launch_bounds__(1024) probe(unsigned long long* out, float see
         for (int r = 0; r < 256; ++r) {
 #define RUN(K, I) if constexpr (KIND == K) asm volatile(BODY4(I) : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b), "v"(c));
             RUN(0, I_FMA32) RUN(2, I_PKFMA16) RUN(3, I_PKMUL16) RUN(4, I_MED3) RUN(5, I_CVTPK16) RUN(6, I_CVTF32) RUN(7, I_CVTBF) RUN(8, I_EXP)
-            RUN(11, I_MAX16) RUN(12, I_FP8)
+            RUN(11, I_MAX16) RUN(12, I_FP8) RUN(13, I_RCP)
 #undef RUN
         }
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
@@ -114,6 +115,10 @@ int main() {
     run<7>("v_cvt_pk_bf16_f32", d);
     run<12>("v_cvt_pk_fp8_f32", d);
     run<8>("v_exp_f32", d);
+    run<13>("v_rcp_f32", d);
+    // QuickGELU (gemm_epilogue.h qgelu4) per PAIR of values: 3 packed operations + 2 v_exp_f32 + 2 v_rcp_f32; the erf fit of degree
+    // DEG: DEG + 4 packed operations.  Cycles per pair at two waves per SIMD = 3 x [v_pk_mul_f32] + 2 x [v_exp_f32] + 2 x [v_rcp_f32]
+    // against (DEG + 4) x [v_pk_fma_f32] from the rows above.
     hipFree(d);
     return 0;
 }

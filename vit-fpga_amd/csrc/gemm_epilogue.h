@@ -9,6 +9,7 @@
 //   BIAS_RESID / BIAS_F32   out32 (+)= acc + bias
 //   PATCH                   out32[row(m)] = acc + bias + pos[tok(m)]
 //   LNFOLD / LNFOLD_GELU    out16 = [gelu]( rstd_m * (acc - mean_m * c_n) + d_n )
+//   BIAS_QGELU / LNFOLD_QGELU   the two GELU forms with QuickGELU, v * sigmoid(1.702 v), as the activation (CLIP's OpenAI towers)
 //        LayerNorm folded into the GEMM: with W' = gamma o W the product LN(x) W^T equals
 //        rstd * (x W'^T - mean * c) + d,  c_n = sum_k W'_nk,  d_n = sum_k beta_k W_nk + b_n, so the
 //        GEMM runs on the RAW (16-bit rounded) residual rows and the per-row statistics enter here.
@@ -50,11 +51,11 @@ struct EpiArgs {
     int64_t prow;        // PATCH_SPLIT: row stride of `partials` (token rows); the other forms use M
 };
 
-constexpr bool epi_is_16bit(int epi) {
-    return epi == VH_EPI_BIAS || epi == VH_EPI_BIAS_GELU || epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU;
-}
-constexpr bool epi_has_gelu(int epi) { return epi == VH_EPI_BIAS_GELU || epi == VH_EPI_LNFOLD_GELU; }
-constexpr bool epi_is_lnfold(int epi) { return epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU; }
+constexpr bool epi_has_qgelu(int epi) { return epi == VH_EPI_BIAS_QGELU || epi == VH_EPI_LNFOLD_QGELU; }
+// "has an activation": erf GELU or QuickGELU (epi_value16 picks the function from the code)
+constexpr bool epi_has_act(int epi) { return epi == VH_EPI_BIAS_GELU || epi == VH_EPI_LNFOLD_GELU || epi_has_qgelu(epi); }
+constexpr bool epi_is_lnfold(int epi) { return epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU; }
+constexpr bool epi_is_16bit(int epi) { return epi == VH_EPI_BIAS || epi == VH_EPI_LNFOLD || epi_has_act(epi); }
 
 // exact-erf GELU: with x = |v|/sqrt(2), h = 0.5*erfc(x) = 0.5*poly(t)*t*exp(-x^2), t = 1/(1 + 0.3275911 x)
 // (Abramowitz & Stegun 7.1.26, |abs error| <= 1.5e-7 on erf: below fp32 rounding of the surrounding
@@ -129,6 +130,34 @@ template <typename T> struct GeluDeg { static constexpr int value = 9; };
 template <> struct GeluDeg<BF16> { static constexpr int value = 8; };
 template <> struct GeluDeg<E4M3> { static constexpr int value = 6; };
 
+// QuickGELU, v * sigmoid(1.702 v), for a quad of values: v * rcp(1 + exp2(-1.702 log2(e) v)) on the hardware v_exp_f32 / v_rcp_f32
+// (1 ulp each), i.e. per PAIR of values three packed operations (scale, + 1, * v) and four transcendentals.  The erf fit's scheme (a
+// polynomial in clamp01(1 - v^2 / c^2)) does not carry over: the sigmoid's tails are exponential, not Gaussian, and degree 12 still
+// leaves 1.7e-3.  Issue cost on one SIMD with two waves (tools/probe_valu.hip: 3.3 cycles per packed instruction, 6.1 per
+// transcendental): 3 x 3.3 + 4 x 6.1 = 34 cycles per pair against 43 / 40 / 33 for the erf fit of degree 9 / 8 / 6 -- so ONE form
+// serves every result type.  Error: the two transcendentals and the three roundings leave a few fp32 ulps, about 4e-7 |result|;
+// measured on the device over 3.1e5 inputs, -30 .. 30 about 2e-3 apart and out to +-3e38 (tests/test_gpu_clip.py, the activation
+// sweeps): a stored result is never further from the float64 function than half a unit in the last place of its type plus
+// 5.8e-7 (fp16), 5.3e-7 (bf16), 3.7e-8 (e4m3) -- against a limit of max(the erf fit's 7.7e-6 / 3.4e-5 / 5.7e-4, a quarter ulp).
+// No clamp: v -> +inf gives v (exp2 -> 0), v -> -huge gives -0 (exp2 -> inf, rcp -> 0; the product of a finite v
+// and 0), a NaN stays a NaN; v = -inf gives NaN like the defining expression -inf * 0.
+// The two pairs advance in step, as in gelu_poly4.
+__device__ __forceinline__ f32x4 qgelu4(f32x4 v) {
+    constexpr float K = -1.702f * 1.44269504088896341f;
+    f32x2 x[2] = {f32x2{v[0], v[1]}, f32x2{v[2], v[3]}}, t[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = x[h] * f32x2{K, K};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = f32x2{__builtin_amdgcn_exp2f(t[h][0]), __builtin_amdgcn_exp2f(t[h][1])};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = t[h] + f32x2{1.f, 1.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = f32x2{__builtin_amdgcn_rcpf(t[h][0]), __builtin_amdgcn_rcpf(t[h][1])};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) x[h] = x[h] * t[h];
+    return f32x4{x[0][0], x[0][1], x[1][0], x[1][1]};
+}
+
 // sum over the 16 lanes of a DPP row (lanes 16g .. 16g+15), result in every lane of the row
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
@@ -152,7 +181,9 @@ __device__ __forceinline__ f32x4 epi_value16(f32x4 acc, f32x4 bv, f32x4 cv, floa
     } else {
         v = acc + bv;
     }
-    if constexpr (epi_has_gelu(EPI) && !(VH_EPI_ABL & 32)) {
+    if constexpr (epi_has_qgelu(EPI) && !(VH_EPI_ABL & 32)) {
+        v = qgelu4(v);
+    } else if constexpr (epi_has_act(EPI) && !(VH_EPI_ABL & 32)) {
         v = gelu_poly4<GeluDeg<TR>::value>(v);
     }
     return v;
@@ -302,7 +333,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const f32x4 (&acc)[MI][NI],
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) asm volatile("" :: "v"(acc[mi][ni]));
-    } else if constexpr (epi_is_16bit(EPI) && epi_has_gelu(EPI) && MFULL && OTILED) {
+    } else if constexpr (epi_is_16bit(EPI) && epi_has_act(EPI) && MFULL && OTILED) {
         // The MLP hidden activation h in its TILED layout (round 4): [m / 16][N / 8 chunks][16 rows][8 values] -- the sixteen rows of a
         // 16-lane group are 256 contiguous bytes per chunk, so the result leaves the registers in 16-byte stores of whole 256-byte
         // segments with NO LDS transposition (the staged form below costs 32 ds_write_b64 + 16 ds_read_b128 per wave and tile; a
@@ -647,7 +678,7 @@ template <int EPI, int MI, int NI, int SMI, bool MFULL = false, bool OTILED = fa
 __device__ __forceinline__ void gemm_epilogue8(const f32x4 (&acc)[MI][NI], const EpiArgs& e, int m_w, int n_w, int lane,
                                                bool n_full, char* smem, int wave, bool cpre = false) {
     static_assert(NI == 4 && MI % SMI == 0, "64-column wave tile");
-    static_assert(EPI == VH_EPI_BIAS || EPI == VH_EPI_BIAS_GELU || EPI == VH_EPI_LNFOLD_GELU, "8-bit output: bias, bias+GELU or LN-fold+GELU");
+    static_assert(EPI == VH_EPI_BIAS || (epi_has_act(EPI)), "8-bit output: bias, bias + activation or LN-fold + activation");
     const int M = e.M, N = e.N;
     const int frow = lane & 15, fq = lane >> 4;
     uint8_t* const out = (uint8_t*)e.out;

@@ -119,7 +119,7 @@ __device__ __forceinline__ unsigned long long diag_hwid() {
 // an ordinary load then comes BEHIND the first pass's stores and, being vmcnt(0), waits for their acknowledgements too.  Removed.)
 template <int EPI, bool F8>
 __host__ __device__ constexpr bool pp_uses_cpre() {
-    return VH_PP_CPRE && epi_is_lnfold(EPI) && !(F8 && EPI == VH_EPI_LNFOLD_GELU);
+    return VH_PP_CPRE && epi_is_lnfold(EPI) && !(F8 && epi_has_act(EPI));
 }
 
 template <int N>
@@ -532,14 +532,14 @@ gemm_nt_pp_kernel(const void* __restrict__ Av, const void* __restrict__ Wv,
             static_assert(VH_PP_SMI == 2, "staging region of the persistent form: 8 waves x 4 KiB");
             // fp8 operands: GELU results leave as e4m3 (the next GEMM's A operand); RESID_LN writes an e4m3 copy of the rows, RESID_SPLIT
             // keeps the residual itself as an e4m3 plane (that operand) + a bf16 plane
-            if constexpr (F8 && epi_has_gelu(EPI))
+            if constexpr (F8 && epi_has_act(EPI))
                 gemm_epilogue8<EPI, MI, NI, VH_PP_SMI, true, OT>(acc, e, m_w, n_w, lane_e, true, stage_epi, wave, cpre);
             else if constexpr (F8 && (EPI == VH_EPI_RESID_LN || EPI == VH_EPI_RESID_SPLIT))
                 gemm_epilogue_staged<E4M3, EPI, MI, NI, VH_PP_SMI, true>(acc, e, m_w, n_w, lane_e, stage_epi + wave * SLICE);
             else
                 gemm_epilogue_staged<T, EPI, MI, NI, VH_PP_SMI, true, OT>(acc, e, m_w, n_w, lane_e, stage_epi + wave * SLICE, epi_is_16bit(EPI) ? grp : -1, cpre);
         } else {
-            if constexpr (F8 && epi_has_gelu(EPI))
+            if constexpr (F8 && epi_has_act(EPI))
                 gemm_epilogue8<EPI, MI, NI, VH_PP_SMI>(acc, e, m_w, n_w, lane_e, n_full, stage_epi, wave);
             else if constexpr (F8 && (EPI == VH_EPI_RESID_LN || EPI == VH_EPI_RESID_SPLIT))
                 gemm_epilogue<E4M3, EPI, MI, NI, 4, false>(acc, e, m_w, n_w, lane_e, n_full, m_full, stage_epi, wave);
@@ -642,7 +642,7 @@ static hipError_t launch_pp(const GemmArgs& g, int mode, hipStream_t s) {
             const int nfull = full_m * tiles_n;
             // (LNFOLD / BIAS with out_tiled: the q|k|v projection's HEAD-MAJOR result, gemm_epilogue.h)
             // (e4m3 operands: the GELU forms write the tiled e4m3 hidden activation, RESID_SPLIT reads it; LNFOLD's bf16 q|k|v goes head-major like the 16-bit path's)
-            if constexpr (EPI == VH_EPI_LNFOLD_GELU || EPI == VH_EPI_BIAS_GELU || EPI == VH_EPI_LNFOLD || (!F8 && EPI == VH_EPI_BIAS)) {
+            if constexpr (epi_has_act(EPI) || EPI == VH_EPI_LNFOLD || (!F8 && EPI == VH_EPI_BIAS)) {
                 if (g.out_tiled) return g.ab_tiled ? hipErrorInvalidValue : launch_pp_one<T, EPI, F8, true, 2, true, false>(g, nfull < num_cu ? nfull : num_cu, full_m, tiles_n, s);
             }
             if constexpr (F8 ? EPI == VH_EPI_RESID_SPLIT : (EPI == VH_EPI_RESID_SPLIT || EPI == VH_EPI_BIAS)) {
@@ -676,7 +676,9 @@ hipError_t launch_gemm_pingpong(const GemmArgs& g, int mode, hipStream_t s) {
     template hipError_t launch_gemm_pingpong<T, VH_EPI_LNFOLD_GELU>(const GemmArgs&, int, hipStream_t); \
     template hipError_t launch_gemm_pingpong<T, VH_EPI_RESID_LN>(const GemmArgs&, int, hipStream_t);   \
     template hipError_t launch_gemm_pingpong<T, VH_EPI_RESID_SPLIT>(const GemmArgs&, int, hipStream_t); \
-    template hipError_t launch_gemm_pingpong<T, VH_EPI_PATCH_SPLIT>(const GemmArgs&, int, hipStream_t);
+    template hipError_t launch_gemm_pingpong<T, VH_EPI_PATCH_SPLIT>(const GemmArgs&, int, hipStream_t); \
+    template hipError_t launch_gemm_pingpong<T, VH_EPI_BIAS_QGELU>(const GemmArgs&, int, hipStream_t);  \
+    template hipError_t launch_gemm_pingpong<T, VH_EPI_LNFOLD_QGELU>(const GemmArgs&, int, hipStream_t);
 VH_INST(BF16)
 VH_INST(FP16)
 
@@ -687,11 +689,13 @@ hipError_t launch_gemm_fp8(const GemmArgs& g, hipStream_t s) {
     switch (g.epilogue) {
         case VH_EPI_BIAS: return launch_pp<BF16, VH_EPI_BIAS, true>(g, mode, s);
         case VH_EPI_BIAS_GELU: return launch_pp<BF16, VH_EPI_BIAS_GELU, true>(g, mode, s);
+        case VH_EPI_BIAS_QGELU: return launch_pp<BF16, VH_EPI_BIAS_QGELU, true>(g, mode, s);
         case VH_EPI_BIAS_RESID: return launch_pp<BF16, VH_EPI_BIAS_RESID, true>(g, mode, s);
         case VH_EPI_BIAS_F32: return launch_pp<BF16, VH_EPI_BIAS_F32, true>(g, mode, s);
         // folded LayerNorm on e4m3 operands: `aux` = c_n, `wscale` = the weight scales, `stats` = (mean, rstd) per row
         case VH_EPI_LNFOLD: return g.wscale && g.stats && g.aux ? launch_pp<BF16, VH_EPI_LNFOLD, true>(g, mode, s) : hipErrorInvalidValue;
         case VH_EPI_LNFOLD_GELU: return g.wscale && g.stats && g.aux && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_LNFOLD_GELU, true>(g, mode, s) : hipErrorInvalidValue;
+        case VH_EPI_LNFOLD_QGELU: return g.wscale && g.stats && g.aux && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_LNFOLD_QGELU, true>(g, mode, s) : hipErrorInvalidValue;
         case VH_EPI_RESID_LN: return g.out16 && g.partials && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_RESID_LN, true>(g, mode, s) : hipErrorInvalidValue;
         // split residual of the fp8 path: out = the e4m3 hi plane (the next GEMM's operand), out16 = the bf16 lo plane
         case VH_EPI_RESID_SPLIT: return g.out16 && g.partials && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_RESID_SPLIT, true>(g, mode, s) : hipErrorInvalidValue;

@@ -633,6 +633,127 @@ hipError_t launch_rowstats_split(const float* x, int64_t rows, int dim, float ep
                                   : rowstats_t<FP16>(x, rows, dim, eps, hi, stats, s, lo);
 }
 
+// ---- pre-LayerNorm (VH_FLAG_PRE_LN, CLIP's ln_pre): the embedded rows, normalised BEFORE layer 0 ---------------------------
+// One pass, one wave per row, the row in registers (dim <= 2048: 8 float4 per lane; nothing goes through LDS): y = LN(x) * gamma
+// + beta in fp32, the same expression as layernorm_kernel.  y leaves in the forms the forward's paths consume, each optional:
+// the fp32 residual (y32, may alias x: a lane reads its chunks before it writes them), the hi / lo planes of the split residual
+// (or the plain operand copy: lo == NULL) exactly as rowstats_cast_kernel makes them, and layer 0's LN1 statistics (mean, rstd) of
+// the NORMALISED row, summed in rowstats_cast_kernel's order over the fp32 values y -- so a context gets the bits it would get
+// from that kernel run on y32, without the second pass.  The guard quantities of the real rows (row < guard_rows; rows behind are
+// tile padding): max |mean| * rstd (`guard`) and, e4m3 planes, max |y| (`amax_guard`).
+template <typename T, int CH>
+__global__ void __launch_bounds__(256)
+pre_layernorm_kernel(const float* x, int64_t rows, int dim, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                     float* y32, typename T::elem* __restrict__ hi, void* __restrict__ lo_, float* __restrict__ stats,
+                     int64_t guard_rows, unsigned int* __restrict__ guard, unsigned int* __restrict__ amax_guard) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nchunk = dim >> 2;
+    const f32x4* xr = (const f32x4*)(x + row * dim);
+    f32x4 v[CH];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = c < nchunk ? xr[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+        sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const float mean = sum / (float)dim;
+    float var = 0.f;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        if (lane + 64 * i < nchunk) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; var += d * d; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o);
+    const float rstd = 1.0f / sqrtf(var / (float)dim + eps);
+    // the normalised row replaces the raw one in the registers; its own sum on the way
+    float ysum = 0.f, amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nchunk) {
+            const f32x4 gm = ((const f32x4*)gamma)[c], bt = ((const f32x4*)beta)[c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] - mean) * rstd * gm[j] + bt[j];
+            if (y32) *(f32x4*)(y32 + row * dim + 4 * c) = v[i];
+        }
+        ysum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);   // (chunks beyond the row are zero)
+        if constexpr (std::is_same<T, E4M3>::value)
+            amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[i][0]), fabsf(v[i][1]))), fmaxf(fabsf(v[i][2]), fabsf(v[i][3])));
+    }
+    if (!hi && !stats) return;   // (kernel argument: uniform)
+    if constexpr (std::is_same<T, E4M3>::value) {
+        if (amax_guard) ln_guard_update(row < guard_rows ? amax : 0.f, amax_guard);   // whole wave = one row: uniform
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ysum += __shfl_xor(ysum, o);
+    const float ymean = ysum / (float)dim;
+    float yvar = 0.f;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nchunk) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const float d = v[i][j] - ymean; yvar += d * d; }
+            if (hi) {
+                const typename T::vec4 hq = pack4<T>(v[i][0], v[i][1], v[i][2], v[i][3]);
+                *(typename T::vec4*)(hi + row * dim + 4 * c) = hq;
+                if constexpr (!std::is_same<T, E4M3>::value) {
+                    uint8_t* const xlo = (uint8_t*)lo_;
+                    if (xlo) *(uint32_t*)(xlo + row * dim + 4 * c) = lo8_pack4<T>(v[i][0] - (float)hq[0], v[i][1] - (float)hq[1],
+                                                                                v[i][2] - (float)hq[2], v[i][3] - (float)hq[3]);
+                } else {
+                    typename BF16::elem* const xlo = (typename BF16::elem*)lo_;
+                    if (xlo) {
+                        const uint32_t w = (uint32_t)hq;
+                        *(typename BF16::vec4*)(xlo + row * dim + 4 * c) =
+                            pack4<BF16>(v[i][0] - __builtin_amdgcn_cvt_f32_fp8((int)w, 0), v[i][1] - __builtin_amdgcn_cvt_f32_fp8((int)w, 1),
+                                        v[i][2] - __builtin_amdgcn_cvt_f32_fp8((int)w, 2), v[i][3] - __builtin_amdgcn_cvt_f32_fp8((int)w, 3));
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) yvar += __shfl_xor(yvar, o);
+    const float yrstd = 1.0f / sqrtf(yvar / (float)dim + eps);
+    if (stats && lane == 0) *(float2*)(stats + 2 * row) = make_float2(ymean, yrstd);
+    if (guard) ln_guard_update(row < guard_rows ? fabsf(ymean) * yrstd : 0.f, guard);
+}
+
+template <typename T>
+static hipError_t pre_ln_t(const float* x, int64_t rows, int dim, const float* g, const float* b, float eps, float* y32, void* hi, void* lo,
+                           float* stats, hipStream_t s, int64_t guard_rows, unsigned int* guard, unsigned int* amax_guard) {
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    auto h = (typename T::elem*)hi;
+#define VH_PRE_LN(CH) hipLaunchKernelGGL((pre_layernorm_kernel<T, CH>), grid, block, 0, s, x, rows, dim, g, b, eps, y32, h, lo, stats, guard_rows, guard, amax_guard)
+    if (dim <= 256) VH_PRE_LN(1);
+    else if (dim <= 512) VH_PRE_LN(2);
+    else if (dim <= 768) VH_PRE_LN(3);
+    else if (dim <= 1024) VH_PRE_LN(4);
+    else if (dim <= 1280) VH_PRE_LN(5);
+    else if (dim <= 2048) VH_PRE_LN(8);
+    else return hipErrorInvalidValue;
+#undef VH_PRE_LN
+    return hipGetLastError();
+}
+hipError_t launch_pre_layernorm(const float* x, int64_t rows, int dim, const float* gamma, const float* beta, float eps, float* y32,
+                                void* hi, void* lo, float* stats, int dtype, hipStream_t s, int64_t guard_rows, unsigned int* guard,
+                                unsigned int* amax_guard) {
+    if (rows <= 0 || dim <= 0 || (dim & 3) || dim > 2048 || !x || !gamma || !beta || (!y32 && !hi) || (lo && !hi)) return hipErrorInvalidValue;
+    if (dtype == VH_DTYPE_FP8) return pre_ln_t<E4M3>(x, rows, dim, gamma, beta, eps, y32, hi, lo, stats, s, guard_rows, guard, amax_guard);
+    if (dtype == VH_DTYPE_BF16) return pre_ln_t<BF16>(x, rows, dim, gamma, beta, eps, y32, hi, lo, stats, s, guard_rows, guard, amax_guard);
+    if (dtype == VH_DTYPE_FP16) return pre_ln_t<FP16>(x, rows, dim, gamma, beta, eps, y32, hi, lo, stats, s, guard_rows, guard, amax_guard);
+    return hipErrorInvalidValue;
+}
+
 // LayerNorm of selected rows of the SPLIT residual (x = hi + lo: a 16-bit plane and a one-byte plane, Lo8<T>) -> fp32: the final LayerNorm of the
 // CLS rows in front of the fp32 head.  One wave per row, two-pass statistics like layernorm_kernel.
 template <typename T>

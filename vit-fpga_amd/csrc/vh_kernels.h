@@ -32,7 +32,7 @@ struct GemmArgs {
     // PATCH_SPLIT: row stride of `partials` = number of TOKEN rows the statistics buffer is laid out for (0 = images x tokens)
     int64_t prow = 0;
     // The MLP hidden activation in its TILED layout (gemm_epilogue.h, OTILED; persistent 16-bit form only: the launcher
-    // refuses otherwise -- ask gemm_tiled_applies first).  out_tiled: an LNFOLD_GELU / BIAS_GELU launch writes it; ab_tiled: A and W
+    // refuses otherwise -- ask gemm_tiled_applies first).  out_tiled: an LNFOLD_GELU / BIAS_GELU (or *_QGELU) launch writes it; ab_tiled: A and W
     // of this launch are both in that layout (16-row blocks).
     int out_tiled = 0, ab_tiled = 0;
 };
@@ -144,6 +144,12 @@ hipError_t launch_ln_guard(const float* stats, int64_t rows, unsigned int* guard
 // the fp32 LayerNorm of selected rows (the CLS rows) of the planes
 hipError_t launch_rowstats_split(const float* x, int64_t rows, int dim, float eps, void* hi, void* lo, float* stats, int dtype,
                                  hipStream_t stream, int64_t guard_rows = 0, unsigned int* amax_guard = nullptr);
+// pre-LayerNorm of VH_FLAG_PRE_LN contexts (kernels_misc.hip): y = LN(x) gamma + beta -> fp32 rows (y32, may alias x), the split
+// residual's planes / the plain operand copy (hi, lo) and layer 0's row statistics of y; every output is optional, one of
+// y32 / hi is needed.  guard / amax_guard as launch_finalize_stats / launch_rowstats_cast, over the first guard_rows rows.
+hipError_t launch_pre_layernorm(const float* x, int64_t rows, int dim, const float* gamma, const float* beta, float eps, float* y32,
+                                void* hi, void* lo, float* stats, int dtype, hipStream_t stream, int64_t guard_rows = 0,
+                                unsigned int* guard = nullptr, unsigned int* amax_guard = nullptr);
 hipError_t launch_layernorm_split(const void* hi, const void* lo, int64_t rows, int dim, int64_t row_stride, const float* gamma,
                                   const float* beta, float eps, float* out32, int dtype, hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln

@@ -54,10 +54,15 @@ struct BlobHeader {
     int32_t image_size, patch_size, channels, dim, heads, mlp_dim, layers, classes;
     float ln_eps;
     // on-disk files only (vh_save_weights_file): FNV-1a 64 of the parameter bytes, flags bit 0 = checksum present.
-    // Blobs built in memory leave all five words 0.
+    // Blobs built in memory leave the two checksum words, bit 0 and the padding 0.  flags bits 1 and 2 describe the MODEL, in
+    // memory and on disk alike: bit 1 = pre-LayerNorm (VH_FLAG_PRE_LN: two more tensors), bit 2 = QuickGELU (VH_FLAG_QUICK_GELU).
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
+constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobModelBits = kBlobPreLn | kBlobQuickGelu;
+uint32_t blob_model_bits(const vh_config& c) {
+    return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u);
+}
 
 uint64_t fnv1a64(const void* data, size_t n, uint64_t h = 0xCBF29CE484222325ull) {
     const unsigned char* p = (const unsigned char*)data;
@@ -73,6 +78,7 @@ struct Layout {
     int T, NP, KP;   // KP = patch^2 * channels: the patch vector in the blob
     int KPA;         // KP rounded up to 64: the compute width of the 16-bit patch operands (wp16, col16, the patch GEMM's K)
     size_t patch_w, patch_b, cls, pos, lnfw, lnfb, headw, headb, total;
+    size_t prew = 0, preb = 0;   // VH_FLAG_PRE_LN: pre_ln.weight / pre_ln.bias [D], directly after pos
     std::vector<LayerOff> layer;
 };
 
@@ -87,6 +93,7 @@ Layout make_layout(const vh_config& c) {
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += n; return r; };
     L.patch_w = take(D * L.KP); L.patch_b = take(D); L.cls = take(D); L.pos = take((size_t)L.T * D);
+    if (c.flags & VH_FLAG_PRE_LN) { L.prew = take(D); L.preb = take(D); }
     L.layer.resize(c.layers);
     for (int l = 0; l < c.layers; ++l) {
         LayerOff& p = L.layer[l];
@@ -106,7 +113,8 @@ size_t blob_bytes_of(const vh_config& c) {
     const size_t D = c.dim, M = c.mlp_dim, C = c.classes, g = (size_t)(c.image_size / c.patch_size);
     const size_t T = g * g + 1, KP = (size_t)c.patch_size * c.patch_size * c.channels;
     const size_t per_layer = 2 * D + 4 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D);
-    return sizeof(BlobHeader) + 4 * (D * KP + D + D + T * D + (size_t)c.layers * per_layer + 2 * D + C * D + C);
+    const size_t pre_ln = (c.flags & VH_FLAG_PRE_LN) ? 2 * D : 0;
+    return sizeof(BlobHeader) + 4 * (D * KP + D + D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * D + C);
 }
 
 const char* check_config(const vh_config& c) {
@@ -123,7 +131,7 @@ const char* check_config(const vh_config& c) {
     if (c.dtype == VH_DTYPE_FP8 && (c.dim % 128 || c.mlp_dim % 128)) return "VH_DTYPE_FP8 needs dim and mlp_dim to be multiples of 128";
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
-    if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL)) return "unknown bits in flags";
+    if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU)) return "unknown bits in flags";
     if ((c.flags & VH_FLAG_W8_E4M3) && c.dtype == VH_DTYPE_FP8) return "flags: VH_FLAG_W8_E4M3 is for the 16-bit dtypes (VH_DTYPE_FP8 quantises both operands)";
     if ((c.flags & VH_FLAG_W8_E4M3) && (c.dim % 4 || c.mlp_dim % 4)) return "flags: VH_FLAG_W8_E4M3 needs dim and mlp_dim multiples of 4";
     if ((c.flags & VH_FLAG_LN_FOLD_OFF) && (c.flags & VH_FLAG_LN_FOLD_ON)) return "flags: VH_FLAG_LN_FOLD_OFF and VH_FLAG_LN_FOLD_ON exclude each other";
@@ -139,9 +147,9 @@ const char* check_config(const vh_config& c) {
     return nullptr;
 }
 
-enum Stage { ST_IM2COL, ST_PATCH, ST_CLS, ST_LN, ST_QKV, ST_ATTN, ST_PROJ, ST_FC1, ST_FC2, ST_LNF, ST_HEAD, ST_LNSTATS, ST_COUNT };
+enum Stage { ST_IM2COL, ST_PATCH, ST_CLS, ST_LN, ST_QKV, ST_ATTN, ST_PROJ, ST_FC1, ST_FC2, ST_LNF, ST_HEAD, ST_LNSTATS, ST_PRELN, ST_COUNT };
 const char* kStageNames[ST_COUNT] = {"im2col", "patch_gemm", "cls_rows", "layernorm", "qkv_gemm", "attention",
-                                     "proj_gemm", "fc1_gemm", "fc2_gemm", "final_layernorm", "head_gemm", "ln_stats"};
+                                     "proj_gemm", "fc1_gemm", "fc2_gemm", "final_layernorm", "head_gemm", "ln_stats", "pre_layernorm"};
 
 }  // namespace
 
@@ -405,6 +413,13 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if (h.image_size != f.image_size || h.patch_size != f.patch_size || h.channels != f.channels || h.dim != f.dim ||
         h.heads != f.heads || h.mlp_dim != f.mlp_dim || h.layers != f.layers || h.classes != f.classes)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: shape differs from the context's vh_config");
+    const uint32_t want = blob_model_bits(f);
+    if ((h.flags ^ want) & kBlobPreLn)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 1 (pre-LayerNorm) is %d, the context's VH_FLAG_PRE_LN is %d",
+                    (h.flags & kBlobPreLn) != 0, (want & kBlobPreLn) != 0);
+    if ((h.flags ^ want) & kBlobQuickGelu)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 2 (QuickGELU) is %d, the context's VH_FLAG_QUICK_GELU is %d",
+                    (h.flags & kBlobQuickGelu) != 0, (want & kBlobQuickGelu) != 0);
     return VH_OK;
 }
 
@@ -466,7 +481,7 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         g.partials = partials_p;
         if (wscale) {              // e4m3 operands (folded-LN layer loop of the fp8 path)
             g.dtype = VH_DTYPE_FP8;
-            if (epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU) g.wscale = wscale;   // `aux` carries c_n there
+            if (epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU) g.wscale = wscale;   // `aux` carries c_n there
             else g.aux = wscale;
             return launch_gemm_fp8(g, s);
         }
@@ -489,7 +504,12 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
     const int nl = (c->run_layers < 0 || c->run_layers > f.layers) ? f.layers : c->run_layers;
     // Patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip; the split residual of the 16-bit paths):
     // VH_PATCH_FUSED=1 selects it -- measured, DESIGN.md 4.4 -- the default is the im2col pass + the persistent GEMM.
-    const bool fused_patch = c->patch_fused && c->split && !c->fp8 && nl > 0 && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
+    // VH_FLAG_PRE_LN: a LayerNorm needs whole rows, which no patch-GEMM tile holds -- such a context embeds through the fp32-x branch
+    // and one pre_layernorm_kernel pass turns x into what its path consumes (no PATCH_SPLIT, no fused patch path, no rowstats pass)
+    const bool pre_ln = (f.flags & VH_FLAG_PRE_LN) != 0;
+    const int epi_fc1 = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_LNFOLD_QGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
+    const int epi_fc1_plain = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_BIAS_QGELU : VH_EPI_BIAS_GELU;       // plain layer loop
+    const bool fused_patch = !pre_ln && c->patch_fused && c->split && !c->fp8 && nl > 0 && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
     if (!fused_patch) {
         if ((rc = tmark(ST_IM2COL))) return rc;
         HIPCHK(&c->err, launch_im2col(in, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
@@ -506,7 +526,7 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         if ((rc = mark(ST_CLS))) return rc;
         HIPCHK(&c->err, launch_finalize_stats(partials_p, D / 64, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
         if ((rc = mark(ST_LNSTATS))) return rc;
-    } else if (c->split && !c->fp8 && nl > 0) {
+    } else if (c->split && !c->fp8 && nl > 0 && !pre_ln) {
         // Split residual: the patch embedding lands DIRECTLY in the two 16-bit planes, with the first row statistics'
         // partial sums (PATCH_SPLIT epilogue; the class-token rows from their own small kernel) -- no fp32 x, no separate
         // row-statistics pass over it (round 3: -0.1 ms per forward).  The partial sums are laid out for rows_g rows, like
@@ -528,7 +548,17 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         if ((rc = mark(ST_PATCH))) return rc;
         HIPCHK(&c->err, launch_cls_rows(x, P + L.cls, P + L.pos, batch, T, D, s));
         if ((rc = mark(ST_CLS))) return rc;
-        if (c->ln_fold && nl > 0) {
+        if (pre_ln) {
+            // x <- LN(x) pre_ln.weight + pre_ln.bias, in the form the path consumes: the fp32 array (plain loop, non-split fold, no
+            // layer at all), the 16-bit operand copy / the split planes, layer 0's LN1 statistics of the normalised rows and the guards
+            const bool fold0 = c->ln_fold && nl > 0;
+            if ((rc = tmark(ST_PRELN))) return rc;
+            HIPCHK(&c->err, launch_pre_layernorm(x, fold0 ? rows_g : rows, D, P + L.prew, P + L.preb, f.ln_eps, fold0 && c->split ? nullptr : x,
+                                                 fold0 ? xn16 : nullptr, fold0 && c->split ? xlo16 : nullptr, fold0 ? stats_p : nullptr,
+                                                 c->fp8 ? VH_DTYPE_FP8 : dt16, s, rows, fold0 ? c->guard_dev : nullptr, fold0 ? amax_guard : nullptr));
+            if ((rc = tmark(ST_PRELN))) return rc;
+            if ((rc = mark(ST_PRELN))) return rc;
+        } else if (c->ln_fold && nl > 0) {
             // layer 0's LN1 statistics: its input comes from the patch embedding, not from a RESID_LN epilogue
             // (fp8 path with the split residual: the patch embedding stays the bf16 fp32-out GEMM; this pass makes the planes)
             if (c->split) HIPCHK(&c->err, launch_rowstats_split(x, rows_g, D, f.ln_eps, xn16, xlo16, stats_p, c->fp8 ? VH_DTYPE_FP8 : dt16, s, rows, amax_guard));
@@ -586,7 +616,7 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
             if ((rc = mark(ST_PROJ))) return rc;
             HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, batch, D, f.ln_eps, stats_p, s, batch, c->guard_dev));
             if ((rc = mark(ST_LNSTATS))) return rc;
-            GemmArgs g1{hc, c->w1_16[l], cd + 6 * D + M, h16, batch, M, D, VH_EPI_LNFOLD_GELU, cd + 6 * D, 0, dt16, 0};
+            GemmArgs g1{hc, c->w1_16[l], cd + 6 * D + M, h16, batch, M, D, epi_fc1, cd + 6 * D, 0, dt16, 0};
             g1.stats = stats_p;
             HIPCHK(&c->err, launch_gemm(g1, s));
             if ((rc = mark(ST_FC1))) return rc;
@@ -627,15 +657,15 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         if ((rc = mark(ST_LNSTATS))) return rc;
         if ((rc = tmark(ST_FC1))) return rc;
         if (h_tiled) {   // h in its tiled layout: written straight from fc1's registers, read by fc2's DMA (same values, same bits)
-            GemmArgs g1{xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, VH_EPI_LNFOLD_GELU, cd + 6 * D, 0, dt16, 0};
+            GemmArgs g1{xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D, 0, dt16, 0};
             g1.stats = stats_p; g1.out_tiled = 1;
             HIPCHK(&c->err, launch_gemm(g1, s));
         } else if (h_tiled8) {
-            GemmArgs g1{xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, VH_EPI_LNFOLD_GELU, cd + 6 * D, 0, VH_DTYPE_FP8, 0};
+            GemmArgs g1{xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D, 0, VH_DTYPE_FP8, 0};
             g1.stats = stats_p; g1.wscale = s1; g1.out_tiled = 1;
             HIPCHK(&c->err, launch_gemm_fp8(g1, s));
         } else
-        HIPCHK(&c->err, gemm(xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, VH_EPI_LNFOLD_GELU, cd + 6 * D, 0, s1));
+        HIPCHK(&c->err, gemm(xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D, 0, s1));
         if ((rc = tmark(ST_FC1))) return rc;
         if ((rc = mark(ST_FC1))) return rc;
         if ((rc = tmark(ST_FC2))) return rc;
@@ -733,7 +763,7 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
         if ((rc = mark(ST_ATTN))) return rc;
         if ((rc = resid_gemm_ln(att16, c->wo16[l], P + o.ob, so, D, P + o.ln2w, P + o.ln2b, ST_PROJ))) return rc;
         if ((rc = tmark(ST_FC1))) return rc;
-        HIPCHK(&c->err, gemm_any(xn16, c->w1_16[l], P + o.f1b, s1, h16, M, D, VH_EPI_BIAS_GELU, 0, 0));
+        HIPCHK(&c->err, gemm_any(xn16, c->w1_16[l], P + o.f1b, s1, h16, M, D, epi_fc1_plain, 0, 0));
         if ((rc = tmark(ST_FC1))) return rc;
         if ((rc = mark(ST_FC1))) return rc;
         const bool more = l + 1 < nl;   // the next layer's LN1 follows this layer's fc2
@@ -1195,6 +1225,7 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
     memcpy(h.magic, "VHBLOB1", 8);
     h.image_size = f.image_size; h.patch_size = f.patch_size; h.channels = f.channels; h.dim = f.dim;
     h.heads = f.heads; h.mlp_dim = f.mlp_dim; h.layers = f.layers; h.classes = f.classes; h.ln_eps = f.ln_eps;
+    h.flags = blob_model_bits(f);
     c->weights_ready = false;
     HIPCHK(&c->err, hipMemcpy(c->blob, &h, sizeof h, hipMemcpyHostToDevice));
     const size_t D = f.dim, M = f.mlp_dim, C = f.classes;
@@ -1206,6 +1237,7 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
     GEN(L.patch_b, D, TID_PATCH_B, sb, 0.f);
     GEN(L.cls, D, TID_CLS, sw, 0.f);
     GEN(L.pos, (size_t)L.T * D, TID_POS, sw, 0.f);
+    if (f.flags & VH_FLAG_PRE_LN) { GEN(L.prew, D, TID_PRE_LN_W, sg, 1.f); GEN(L.preb, D, TID_PRE_LN_B, sb, 0.f); }
     for (int l = 0; l < f.layers; ++l) {
         const LayerOff& o = L.layer[l];
         const uint32_t t = TID_LAYER0 + 16u * (uint32_t)l;
@@ -1254,6 +1286,8 @@ static int blob_file_header(const char* path, vh_config* cfg, size_t* need_out) 
     c.image_size = h.image_size; c.patch_size = h.patch_size; c.channels = h.channels; c.dim = h.dim; c.heads = h.heads;
     c.mlp_dim = h.mlp_dim; c.layers = h.layers; c.classes = h.classes; c.ln_eps = h.ln_eps;
     c.dtype = VH_DTYPE_BF16; c.max_batch = 1;
+    if (h.flags & ~(kBlobSum | kBlobModelBits)) return fail(nullptr, VH_ERR_INVALID, "%s: unknown bits in the header's flags word", path);
+    c.flags = ((h.flags & kBlobPreLn) ? VH_FLAG_PRE_LN : 0) | ((h.flags & kBlobQuickGelu) ? VH_FLAG_QUICK_GELU : 0);
     // check_config bounds every field, so the size arithmetic below cannot overflow and nothing is allocated from the header
     if (const char* why = check_config(c)) return fail(nullptr, VH_ERR_INVALID, "%s: header describes an unsupported model (%s)", path, why);
     const size_t need = blob_bytes_of(c);
@@ -1282,12 +1316,13 @@ int vh_blob_file_read(const char* path, void* host_blob, size_t nbytes) {
     if (got != need) return fail(nullptr, VH_ERR_INVALID, "%s: short read", path);
     BlobHeader h;
     memcpy(&h, host_blob, sizeof h);
-    if (h.flags & 1) {
+    if (h.flags & kBlobSum) {
         const uint64_t sum = fnv1a64((const char*)host_blob + sizeof h, need - sizeof h);
         if ((uint32_t)sum != h.sum_lo || (uint32_t)(sum >> 32) != h.sum_hi)
             return fail(nullptr, VH_ERR_INVALID, "%s: checksum mismatch (file damaged)", path);
     }
-    h.sum_lo = h.sum_hi = h.flags = 0;   // memory form
+    h.sum_lo = h.sum_hi = 0;   // memory form: the model bits stay
+    h.flags &= kBlobModelBits;
     h.pad[0] = h.pad[1] = 0;
     memcpy(host_blob, &h, sizeof h);
     return VH_OK;
@@ -1303,7 +1338,7 @@ int vh_save_weights_file(vh_ctx* c, const char* path) {
     BlobHeader h;
     memcpy(&h, buf.data(), sizeof h);
     const uint64_t sum = fnv1a64(buf.data() + sizeof h, need - sizeof h);
-    h.sum_lo = (uint32_t)sum; h.sum_hi = (uint32_t)(sum >> 32); h.flags = 1; h.pad[0] = h.pad[1] = 0;
+    h.sum_lo = (uint32_t)sum; h.sum_hi = (uint32_t)(sum >> 32); h.flags = kBlobSum | blob_model_bits(c->cfg); h.pad[0] = h.pad[1] = 0;
     memcpy(buf.data(), &h, sizeof h);
     const std::string tmp = std::string(path) + ".tmp";
     FILE* f = fopen(tmp.c_str(), "wb");
@@ -1328,13 +1363,14 @@ int vh_load_weights_file(vh_ctx* c, const char* path) {
     memcpy(&h, buf.data(), sizeof h);
     int rc = check_blob_header(c, h);
     if (rc) return rc;
-    if (h.flags & 1) {
+    if (h.flags & kBlobSum) {
         const uint64_t sum = fnv1a64(buf.data() + sizeof h, need - sizeof h);
         if ((uint32_t)sum != h.sum_lo || (uint32_t)(sum >> 32) != h.sum_hi)
             return fail(&c->err, VH_ERR_INVALID, "%s: checksum mismatch (file damaged)", path);
     }
     // the resident blob is the memory form: checksum words cleared, so export == what make_blob-style writers produce
-    h.sum_lo = h.sum_hi = h.flags = 0;
+    h.sum_lo = h.sum_hi = 0;
+    h.flags &= kBlobModelBits;
     memcpy(buf.data(), &h, sizeof h);
     return vh_load_weights(c, buf.data(), need);
 }
@@ -1750,7 +1786,7 @@ int vh_op_gemm_fp8(const void* a8, const void* w8, const float* w_scale, const f
     if (!a8 || !w8 || !w_scale || !bias || !out) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8: null pointer");
     if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 4) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8: need K %% 128 == 0 and N %% 4 == 0");
     if (M > 0x7FFFFFFF / 2) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8: M too large");
-    if (epi != VH_EPI_BIAS && epi != VH_EPI_BIAS_GELU && epi != VH_EPI_BIAS_RESID && epi != VH_EPI_BIAS_F32)
+    if (epi != VH_EPI_BIAS && epi != VH_EPI_BIAS_GELU && epi != VH_EPI_BIAS_QGELU && epi != VH_EPI_BIAS_RESID && epi != VH_EPI_BIAS_F32)
         return fail(nullptr, VH_ERR_UNSUPPORTED, "gemm_fp8: epilogue %d not available", epi);
     GemmArgs g{a8, w8, bias, out, M, N, K, epi, w_scale, 0, VH_DTYPE_FP8, variant};
     OPCHK(launch_gemm_fp8(g, (hipStream_t)stream));
@@ -1763,11 +1799,12 @@ int vh_op_gemm_fp8_ex(const void* a8, const void* w8, const float* w_scale, cons
     if (!a8 || !w8 || !w_scale || !bias || !out) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: null pointer");
     if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 4) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: need K %% 128 == 0 and N %% 4 == 0");
     if (M > 0x7FFFFFFF / 2) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: M too large");
-    const bool fold = epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU, resid = epi == VH_EPI_RESID_LN || epi == VH_EPI_RESID_SPLIT;
+    const bool fold_act = epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU;
+    const bool fold = epi == VH_EPI_LNFOLD || fold_act, resid = epi == VH_EPI_RESID_LN || epi == VH_EPI_RESID_SPLIT;
     if (!fold && !resid) return fail(nullptr, VH_ERR_UNSUPPORTED, "gemm_fp8_ex: epilogue %d not available", epi);
     if (fold && (!c_dev || !stats)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: LNFOLD needs c and stats");
     if (resid && (!out16 || !partials)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: RESID_* needs out16 and partials");
-    if ((resid || epi == VH_EPI_LNFOLD_GELU) && N % 256) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: N %% 256 != 0");
+    if ((resid || fold_act) && N % 256) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: N %% 256 != 0");
     GemmArgs g{a8, w8, bias, out, M, N, K, epi, fold ? c_dev : w_scale, 0, VH_DTYPE_FP8, variant};
     if (fold) g.wscale = w_scale;
     g.stats = stats; g.out16 = out16; g.partials = partials;
@@ -1800,6 +1837,18 @@ int vh_op_rowstats_cast(const float* x, int64_t rows, int dim, float eps, void* 
 int vh_op_rowstats_split(const float* x, int64_t rows, int dim, float eps, void* hi, void* lo, float* stats, int dtype, void* stream) {
     if (!x || !hi || !lo || !stats || rows <= 0 || dim <= 0 || dim % 4 || dim > 2048) return fail(nullptr, VH_ERR_INVALID, "rowstats_split: bad argument");
     OPCHK(launch_rowstats_split(x, rows, dim, eps, hi, lo, stats, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_pre_layernorm(const float* x, int64_t rows, int dim, const float* gamma, const float* beta, float eps, float* y32, void* hi,
+                        void* lo, float* stats, int dtype, void* stream) {
+    if (!x || !gamma || !beta) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: null pointer");
+    if (!y32 && !hi) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: one of y32 / hi is needed");
+    if (lo && !hi) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: the lo plane needs the hi plane");
+    if (rows <= 0 || dim <= 0 || dim % 4 || dim > 2048) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: need rows > 0, dim %% 4 == 0, dim <= 2048");
+    if (!(eps > 0.f)) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: eps must be positive");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: dtype");
+    OPCHK(launch_pre_layernorm(x, rows, dim, gamma, beta, eps, y32, hi, lo, stats, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
@@ -1903,7 +1952,7 @@ int vh_bench_gemm(int device, int64_t M, int N, int K, int epilogue, int dtype, 
     const int aux_i = 196;
     // the layer epilogues of the folded path: LNFOLD* read per-row (mean, rstd) and c_n (`aux`), RESID_LN / RESID_SPLIT
     // write a second 16-bit plane and the per-64-column row sums
-    const bool fold = epilogue == VH_EPI_LNFOLD || epilogue == VH_EPI_LNFOLD_GELU;
+    const bool fold = epilogue == VH_EPI_LNFOLD || epilogue == VH_EPI_LNFOLD_GELU || epilogue == VH_EPI_LNFOLD_QGELU;
     const bool resid2 = epilogue == VH_EPI_RESID_LN || epilogue == VH_EPI_RESID_SPLIT || epilogue == VH_EPI_PATCH_SPLIT;
     const size_t out_rows = (epilogue == VH_EPI_PATCH || epilogue == VH_EPI_PATCH_SPLIT) ? (size_t)(M / aux_i + 1) * (aux_i + 1) : (size_t)M;
     hipEvent_t e0 = nullptr, e1 = nullptr;

@@ -16,11 +16,13 @@ LIB_PATH = os.environ.get("VITHIP_LIB") or os.path.join(PKG_ROOT, "libvithip.so"
 
 DTYPE_BF16, DTYPE_FP16, DTYPE_FP8 = 0, 1, 2
 FLAG_LN_FOLD_OFF, FLAG_LN_FOLD_ON, FLAG_W8_E4M3, FLAG_CLS_TAIL = 1, 2, 4, 8   # vh_config.flags
+FLAG_PRE_LN, FLAG_QUICK_GELU = 16, 32   # CLIP's vision towers: LayerNorm in front of layer 0, x * sigmoid(1.702 x) in the MLP
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
+EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
 ACT_IDENTITY, ACT_RELU2, ACT_RELU, ACT_HARDTANH, ACT_GELU = range(5)
 
 STAGES = ["im2col", "patch_gemm", "cls_rows", "layernorm", "qkv_gemm", "attention", "proj_gemm",
-          "fc1_gemm", "fc2_gemm", "final_layernorm", "head_gemm", "ln_stats"]
+          "fc1_gemm", "fc2_gemm", "final_layernorm", "head_gemm", "ln_stats", "pre_layernorm"]
 
 
 class VhError(RuntimeError):
@@ -103,6 +105,7 @@ SYMBOLS = {
     "vh_op_gemm_ex": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "vh_op_rowstats_cast": (_i, [_vp, _i64, _i, _f, _vp, _vp, _i, _vp]),
     "vh_op_finalize_stats": (_i, [_vp, _i, _i64, _i, _f, _vp, _vp]),
+    "vh_op_pre_layernorm": (_i, [_vp, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp]),
     "vh_op_rowstats_split": (_i, [_vp, _i64, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "vh_op_fold_ln": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "vh_op_layernorm": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _i, _vp]),
@@ -175,6 +178,58 @@ def blob_file_config(path):
     c = Config()
     _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
     return {k: getattr(c, k) for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")}, c.ln_eps
+
+
+def blob_file_flags(path):
+    """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN | FLAG_QUICK_GELU); host only."""
+    c = Config()
+    _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
+    return c.flags
+
+
+def blob_from_clip_state_dict(sd, cfg, ln_eps=1e-5):
+    """Canonical blob of a CLIP vision tower from a dict of arrays under the Hugging Face `CLIPVisionModelWithProjection`
+    parameter names (numpy only; torch tensors: pass `{k: v.numpy() for k, v in model.state_dict().items()}`).
+    `cfg`: the model shape with classes = the projection width, plus `flags` (FLAG_PRE_LN always; FLAG_QUICK_GELU for
+    hidden_act == "quick_gelu").  CLIP's patch convolution and projection have no bias: both are written as zeros; the
+    header carries the model bits.  A missing or wrongly shaped tensor is refused by name."""
+    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
+    g = cfg["image_size"] // cfg["patch_size"]
+    flags = cfg.get("flags", FLAG_PRE_LN)
+    if not flags & FLAG_PRE_LN:
+        raise ValueError("blob_from_clip_state_dict: every CLIP vision tower has ln_pre: cfg['flags'] needs FLAG_PRE_LN")
+    if flags & ~(FLAG_PRE_LN | FLAG_QUICK_GELU):
+        raise ValueError("blob_from_clip_state_dict: cfg['flags'] takes the model bits FLAG_PRE_LN | FLAG_QUICK_GELU only")
+
+    def take(name, shape):
+        if name not in sd:
+            raise KeyError(f"blob_from_clip_state_dict: missing tensor {name}")
+        a = np.asarray(sd[name], dtype=np.float32)
+        if a.shape != tuple(shape):
+            raise ValueError(f"blob_from_clip_state_dict: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}")
+        return np.ascontiguousarray(a).reshape(-1)
+
+    v, emb = "vision_model.", "vision_model.embeddings."
+    parts = [take(emb + "patch_embedding.weight", (D, CH, P, P)), np.zeros(D, np.float32),
+             take(emb + "class_embedding", (D,)), take(emb + "position_embedding.weight", (g * g + 1, D)),
+             take(v + "pre_layrnorm.weight", (D,)), take(v + "pre_layrnorm.bias", (D,))]
+    for l in range(cfg["layers"]):
+        b = f"{v}encoder.layers.{l}."
+        parts += [take(b + "layer_norm1.weight", (D,)), take(b + "layer_norm1.bias", (D,))]
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            parts += [take(f"{b}self_attn.{n}.weight", (D, D)), take(f"{b}self_attn.{n}.bias", (D,))]
+        parts += [take(b + "layer_norm2.weight", (D,)), take(b + "layer_norm2.bias", (D,)),
+                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,)),
+                  take(b + "mlp.fc2.weight", (D, M)), take(b + "mlp.fc2.bias", (D,))]
+    parts += [take(v + "post_layernorm.weight", (D,)), take(v + "post_layernorm.bias", (D,)),
+              take("visual_projection.weight", (E, D)), np.zeros(E, np.float32)]
+    h = np.zeros(64, dtype=np.uint8)
+    h[:7] = np.frombuffer(b"VHBLOB1", dtype=np.uint8)
+    h[8:40] = np.array([cfg[k] for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")],
+                       dtype=np.int32).view(np.uint8)
+    h[40:44] = np.array([ln_eps], dtype=np.float32).view(np.uint8)
+    h[52:56] = np.array([2 | (4 if flags & FLAG_QUICK_GELU else 0)], dtype=np.uint32).view(np.uint8)   # header flags word: bit 1 pre-LN, bit 2 QuickGELU
+    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
 
 
 def device_free_bytes(device=0):
@@ -662,6 +717,10 @@ def op_rowstats_cast(x_ptr, rows, dim, eps, x16_ptr, stats_ptr, dtype):
 
 def op_rowstats_split(x_ptr, rows, dim, eps, hi_ptr, lo_ptr, stats_ptr, dtype):
     _check(lib().vh_op_rowstats_split(x_ptr, rows, dim, eps, hi_ptr, lo_ptr, stats_ptr, dtype, None))
+
+
+def op_pre_layernorm(x_ptr, rows, dim, gamma_ptr, beta_ptr, eps, y32_ptr, hi_ptr, lo_ptr, stats_ptr, dtype):
+    _check(lib().vh_op_pre_layernorm(x_ptr, rows, dim, gamma_ptr, beta_ptr, eps, y32_ptr, hi_ptr, lo_ptr, stats_ptr, dtype, None))
 
 
 def op_finalize_stats(partials_ptr, nblk, rows, dim, eps, stats_ptr):
