@@ -377,6 +377,20 @@ int vh_op_attention_stream(const void* qkv16_dev, int batch, int tokens, int hea
  * head_dim^-1/2 * log2(e), tokens 1..4097, heads*head_dim <= 2048.  dtype VH_DTYPE_FP8: bf16 q|k|v in, e4m3 out. */
 int vh_op_attention_hd(const void* qkv16_dev, int batch, int tokens, int heads, int head_dim, void* out16_dev,
                        int dtype, void* stream);
+/* Test tap: the one-query attention kernel of VH_FLAG_CLS_TAIL on its own.  qkv16 [batch*tokens, 3*heads*64] (q pre-scaled as
+ * above) -> out16 [batch, heads*64]: attention of every image's row 0 over all its keys / values.  tokens 1..1024, dtype
+ * VH_DTYPE_BF16 or VH_DTYPE_FP16; anything else is VH_ERR_INVALID. */
+int vh_op_attention_cls(const void* qkv16_dev, int batch, int tokens, int heads, void* out16_dev,
+                        int dtype, void* stream);
+/* Test tap: vh_op_attention with the two layouts the forward uses between the projections:
+ *   out_tiled != 0   the result in the 16-row-blocked layout [rows / 16][heads*64 / 8][16 rows][8 values] (VH_DTYPE_FP8: e4m3,
+ *                    [rows / 16][heads*64 / 16][16 rows][16 B]); out16 holds batch*tokens rounded up to 16 rows, and the rows
+ *                    beyond batch*tokens are not written.  Ring forms with an even head count only.
+ *   in_hm_rows != 0  q|k|v arrives head-major, [3][heads][in_hm_rows][64] with in_hm_rows >= batch*tokens (needs out_tiled).
+ * With both 0 it is vh_op_attention.  VH_ERR_INVALID wherever the launch would refuse: the tiled output at a shape that does not
+ * run a ring form or with an odd head count, head-major input without the tiled output, in_hm_rows < batch*tokens. */
+int vh_op_attention_layout(const void* qkv16_dev, int batch, int tokens, int heads, void* out16_dev,
+                           int dtype, int out_tiled, int64_t in_hm_rows, void* stream);
 /* NHWC fp32 images -> patch matrix [batch*np, patch*patch*channels] in `dtype` */
 int vh_op_im2col(const float* in_nhwc_dev, int batch, int image, int patch, int channels,
                  void* out16_dev, int dtype, void* stream);

@@ -1909,6 +1909,36 @@ int vh_op_attention_hd(const void* qkv16, int batch, int tokens, int heads, int 
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
+int vh_op_attention_cls(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, void* stream) {
+    if (!qkv16 || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
+    if (batch <= 0 || tokens <= 0 || tokens > 1024 || heads <= 0) return fail(nullptr, VH_ERR_INVALID, "attention_cls: unsupported shape");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16) return fail(nullptr, VH_ERR_INVALID, "attention_cls: unsupported dtype");
+    OPCHK(launch_attention_cls(qkv16, batch, tokens, heads, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_attention_layout(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, int out_tiled, int64_t in_hm_rows,
+                           void* stream) {
+    if (!qkv16 || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
+    if (batch <= 0 || tokens <= 0 || heads <= 0 || tokens > kAttnStreamMaxTokens ||
+        (attention_lds_bytes(tokens) > 160 * 1024 && heads > 32))
+        return fail(nullptr, VH_ERR_INVALID, "attention_layout: unsupported shape");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8)
+        return fail(nullptr, VH_ERR_INVALID, "attention_layout: unsupported dtype");
+    // what launch_attention refuses, refused here with a reason and before anything is allocated
+    if (in_hm_rows < 0 || (in_hm_rows && !out_tiled)) return fail(nullptr, VH_ERR_INVALID, "attention_layout: head-major q|k|v needs the tiled output");
+    if (in_hm_rows && (in_hm_rows < (int64_t)batch * tokens || in_hm_rows * heads * 64 * 4 >= (1ll << 32)))
+        return fail(nullptr, VH_ERR_INVALID, "attention_layout: in_hm_rows must hold batch * tokens rows (and 4 * in_hm_rows * heads * 64 < 2^32)");
+    if (out_tiled && !attention_tiled_applies(batch, tokens, heads))
+        return fail(nullptr, VH_ERR_INVALID, "attention_layout: the tiled output exists in the ring forms with an even head count only");
+    unsigned int* ticket = nullptr;   // owned by this call, as in vh_op_attention
+    OPCHK(hipMalloc((void**)&ticket, 256));
+    hipError_t e = launch_attention(qkv16, batch, tokens, heads, out16, dtype, ticket, (hipStream_t)stream, false, out_tiled != 0, in_hm_rows);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(ticket);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "attention_layout failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
 int vh_op_im2col(const float* in, int batch, int image, int patch, int channels, void* out16, int dtype, void* stream) {
     if (!in || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
     if (batch <= 0 || patch <= 0 || image <= 0 || image % patch || (patch * channels) % 4)

@@ -112,6 +112,8 @@ SYMBOLS = {
     "vh_op_attention": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_stream": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_hd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vh_op_attention_cls": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
+    "vh_op_attention_layout": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _vp]),
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
@@ -260,6 +262,38 @@ def to16(a, dtype):
 
 def from16(b, dtype):
     return from_bf16_bits(b) if dtype == DTYPE_BF16 else np.ascontiguousarray(b, dtype=np.uint16).view(np.float16).astype(np.float32)
+
+
+# ---- the layouts q|k|v and the attention output take between the projections (test taps) ----
+def pack_head_major(qkv, heads, hm_rows, fill=0):
+    """Row-major q|k|v [rows][3 * heads * 64] (any element type) -> head-major [3][heads][hm_rows][64]; rows beyond the
+    input's (hm_rows > rows: the padding of the persistent projection's row tiles) hold `fill`."""
+    qkv = np.ascontiguousarray(qkv)
+    rows = qkv.shape[0]
+    assert qkv.shape[1] == 3 * heads * 64 and hm_rows >= rows
+    out = np.full((3, heads, hm_rows, 64), fill, dtype=qkv.dtype)
+    out[:, :, :rows] = qkv.reshape(rows, 3, heads, 64).transpose(1, 2, 0, 3)
+    return out
+
+
+def unpack_tiled(tiled, rows, dim, chunk=8):
+    """The 16-row-blocked layout [ceil(rows / 16)][dim / chunk][16 rows][chunk] -> row-major [rows][dim].  chunk = elements per
+    16-byte piece: 8 for 2-byte elements, 16 for e4m3 bytes (what launch_tile_bytes writes for weights)."""
+    nb = (rows + 15) // 16
+    t = np.ascontiguousarray(tiled).reshape(nb, dim // chunk, 16, chunk)
+    return np.ascontiguousarray(t.transpose(0, 2, 1, 3).reshape(nb * 16, dim)[:rows])
+
+
+def pack_tiled(a, chunk=8, fill=0):
+    """Inverse of unpack_tiled: row-major [rows][dim] -> [ceil(rows / 16)][dim / chunk][16][chunk]; the rows that pad the last
+    block hold `fill`."""
+    a = np.ascontiguousarray(a)
+    rows, dim = a.shape
+    assert dim % chunk == 0
+    nb = (rows + 15) // 16
+    full = np.full((nb * 16, dim), fill, dtype=a.dtype)
+    full[:rows] = a
+    return np.ascontiguousarray(full.reshape(nb, 16, dim // chunk, chunk).transpose(0, 2, 1, 3))
 
 
 class DeviceBuffer:
@@ -754,6 +788,16 @@ def op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
 def op_attention_hd(qkv_ptr, batch, tokens, heads, head_dim, out_ptr, dtype):
     """Attention at head dim 32, 48, ..., 128 (q pre-scaled by head_dim^-1/2 * log2(e)), any token count 1..4097."""
     _check(lib().vh_op_attention_hd(qkv_ptr, batch, tokens, heads, head_dim, out_ptr, dtype, None))
+
+
+def op_attention_cls(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
+    """Test tap: attention of every image's row 0 only (the VH_FLAG_CLS_TAIL kernel): out [batch][heads * 64], tokens <= 1024."""
+    _check(lib().vh_op_attention_cls(qkv_ptr, batch, tokens, heads, out_ptr, dtype, None))
+
+
+def op_attention_layout(qkv_ptr, batch, tokens, heads, out_ptr, dtype, out_tiled=False, in_hm_rows=0):
+    """Test tap: op_attention with the 16-row-blocked output (unpack_tiled) and / or head-major q|k|v (pack_head_major)."""
+    _check(lib().vh_op_attention_layout(qkv_ptr, batch, tokens, heads, out_ptr, dtype, 1 if out_tiled else 0, in_hm_rows, None))
 
 
 def op_im2col(in_ptr, batch, image, patch, channels, out_ptr, dtype):
