@@ -209,6 +209,29 @@ int vh_forward_device(vh_ctx* ctx, const float* in_nhwc_dev, int batch, float* l
 int vh_forward_device_async(vh_ctx* ctx, const float* in_nhwc_dev, int batch,
                             float* logits_dev, int steps);
 int vh_synchronize(vh_ctx* ctx);
+
+/* ---- 8-bit images -------------------------------------------------------------------------------------------------
+ * What a decoder, a camera or a dataloader emits: batch x image x image x channels bytes, NHWC.  CONTRACT: pixel p
+ * (0..255) of channel c enters the model as the fp32 value
+ *       x = fmaf((float)p, scale[c], shift[c])                       (ONE rounding)
+ * computed inside the patch gather and then rounded to the MFMA operand type exactly as an fp32 input is.  The logits of
+ * a u8 forward are therefore BIT-IDENTICAL to those of the fp32 entry point given the host-computed array x, on every
+ * path (folded, plain, split, fp8, pre-LN, any patch size and head dim, VH_FLAG_CLS_TAIL, graphs, streams): everything
+ * behind the patch matrix is the same code.  The input crosses PCIe and is read by the gather at 1 byte per element
+ * instead of 4.  VH_PATCH_FUSED=1 contexts run the ordinary gather + patch GEMM for u8 input (the fused loader reads fp32).
+ *   vh_set_input_norm   scale, shift: [channels] floats each, all finite (else VH_ERR_INVALID); NULL, NULL restores the
+ *                       default scale = 1/255, shift = 0; exactly one NULL is VH_ERR_INVALID.  For the usual
+ *                       (p / 255 - mean) / std: scale = 1 / (255 std), shift = -mean / std.  Per-context state; the call waits
+ *                       for the context's stream and drops the cached graphs (vh_set_graph), as a weight load does.
+ *   vh_get_input_norm   the pair in force: [channels] floats each.
+ *   vh_forward_u8, vh_forward_device_u8, vh_forward_device_u8_async: vh_forward, vh_forward_device and
+ *                       vh_forward_device_async under the contract above.  A device input pointer that is not 16-byte
+ *                       aligned is VH_ERR_INVALID. */
+int vh_set_input_norm(vh_ctx* ctx, const float* scale, const float* shift);
+int vh_get_input_norm(const vh_ctx* ctx, float* scale, float* shift);
+int vh_forward_u8(vh_ctx* ctx, const uint8_t* in_nhwc_host, int batch, float* logits_host);
+int vh_forward_device_u8(vh_ctx* ctx, const uint8_t* in_nhwc_dev, int batch, float* logits_dev);
+int vh_forward_device_u8_async(vh_ctx* ctx, const uint8_t* in_nhwc_dev, int batch, float* logits_dev, int steps);
 /* uniform[-1,1) synthetic images written straight into HBM (value range of the reference,
  * def/defines.h:11-12) */
 int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_dev);
@@ -229,6 +252,15 @@ int vh_ring_free_slots(const vh_ctx* ctx, int* n);
 int vh_ring_input(vh_ctx* ctx, float** pinned_in_nhwc);
 int vh_ring_submit(vh_ctx* ctx, const float* in_nhwc_host, int batch);
 int vh_ring_collect(vh_ctx* ctx, float* logits_host, int* batch);
+/* The same ring with slots that stage 8-bit images (a quarter of the pinned and of the device memory, a quarter of the
+ * bytes per upload).  Each pixel enters as fmaf((float)p, scale[c], shift[c]) (vh_set_input_norm; one rounding), so a
+ * collected batch has the bits vh_forward_u8 / vh_forward of that fp32 array return.  vh_ring_collect,
+ * vh_ring_free_slots and vh_ring_destroy serve both kinds of ring; a context has one ring at a time.  The input calls
+ * are per kind: vh_ring_input / vh_ring_submit on a u8 ring, and vh_ring_input_u8 / vh_ring_submit_u8 on an fp32 ring,
+ * return VH_ERR_STATE. */
+int vh_ring_create_u8(vh_ctx* ctx, int slots, int batch_per_slot);
+int vh_ring_input_u8(vh_ctx* ctx, uint8_t** pinned_in_nhwc);
+int vh_ring_submit_u8(vh_ctx* ctx, const uint8_t* in_nhwc_host, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -399,6 +431,13 @@ int vh_op_im2col(const float* in_nhwc_dev, int batch, int image, int patch, int 
  * patch vector rounded up to 64).  vh_op_im2col needs patch*channels to be a multiple of 4 and writes no padding. */
 int vh_op_im2col_padded(const float* in_nhwc_dev, int batch, int image, int patch, int channels, int kpad,
                         void* out16_dev, int dtype, void* stream);
+/* The patch gather of the 8-bit entry points on its own: NHWC bytes -> patch matrix [batch*np, kpad] in `dtype`
+ * (VH_DTYPE_BF16 or VH_DTYPE_FP16), element = dtype(fmaf((float)p, scale[c], shift[c])) with ONE rounding before the
+ * conversion, i.e. the bits vh_op_im2col_padded gives for that fp32 array; columns patch*patch*channels .. kpad-1 zero.
+ * Any patch <= 256 and channels <= 64, kpad >= patch*patch*channels and a multiple of 8; scale_host / shift_host: HOST
+ * arrays [channels], finite; in_nhwc_dev 16-byte aligned (else VH_ERR_INVALID). */
+int vh_op_im2col_u8(const uint8_t* in_nhwc_dev, int batch, int image, int patch, int channels, int kpad,
+                    const float* scale_host, const float* shift_host, void* out16_dev, int dtype, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,

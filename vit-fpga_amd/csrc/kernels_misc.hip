@@ -157,6 +157,86 @@ hipError_t launch_im2col(const float* in, int batch, int image, int patch, int c
     return hipGetLastError();
 }
 
+// ---- im2col of 8-bit NHWC images with the input normalisation fused in ---------------------------------------------------
+// Pixel p (0..255) of channel c enters as x = fmaf((float)p, scale[c], shift[c]) -- ONE rounding, written as the builtin so
+// that nothing depends on contraction -- and is then rounded by the same pack4<T> as in the kernels above: the patch matrix has
+// the bits launch_im2col produces from the host-computed fp32 array x.  Same thread mapping, k order and zero padding as
+// im2col_pad_kernel.  VEC8 (8 | patch * ch, 8 | image * ch, 8-byte aligned base): the 8 source bytes of a chunk are contiguous
+// and 8-byte aligned in the image, one load; otherwise byte loads with the per-element (ky, r) walk.  The channel of element k
+// is k % ch (patch * ch is a multiple of ch).  scale | shift arrive as kernel arguments and are put in LDS once per block.
+struct U8Norm { float scale[kMaxChannels], shift[kMaxChannels]; };
+
+template <typename T, bool VEC8>
+__global__ void __launch_bounds__(256)
+im2col_u8_kernel(const uint8_t* __restrict__ in, typename T::elem* __restrict__ out, int64_t n8, int image, int patch,
+                 int ch, int kpad, const U8Norm norm) {
+    __shared__ float s_scale[kMaxChannels], s_shift[kMaxChannels];
+    if ((int)threadIdx.x < ch) {
+        s_scale[threadIdx.x] = norm.scale[threadIdx.x];
+        s_shift[threadIdx.x] = norm.shift[threadIdx.x];
+    }
+    __syncthreads();
+    const int pc = patch * ch;               // bytes per patch row: contiguous in the image
+    const int kp = patch * pc;
+    const int cpr = kpad / 8;                // chunks per output row
+    const int g = image / patch;
+    for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < n8; f += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t orow = f / cpr;        // (b * g + py) * g + px
+        const int k0 = (int)(f - orow * cpr) * 8;
+        const int64_t b = orow / (g * g);
+        const int p = (int)(orow - b * g * g);
+        const int py = p / g, px = p - py * g;
+        const uint8_t* src = in + ((b * image + (int64_t)py * patch) * image + (int64_t)px * patch) * ch;
+        int ky = k0 / pc, r = k0 - ky * pc;
+        int c = k0 % ch;
+        float v[8];
+        if constexpr (VEC8) {                // 8 | pc and 8 | kp: the chunk lies inside one patch row, or wholly in the padding
+            u32x2 w{0u, 0u};
+            if (k0 < kp) w = *(const u32x2*)(src + ((int64_t)ky * image) * ch + r);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float pix = (float)((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
+                v[i] = k0 < kp ? __builtin_fmaf(pix, s_scale[c], s_shift[c]) : 0.f;
+                if (++c == ch) c = 0;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                v[i] = k0 + i < kp ? __builtin_fmaf((float)src[((int64_t)ky * image) * ch + r], s_scale[c], s_shift[c]) : 0.f;
+                if (++r == pc) { r = 0; ++ky; }
+                if (++c == ch) c = 0;
+            }
+        }
+        const typename T::vec4 lo = pack4<T>(v[0], v[1], v[2], v[3]), hi = pack4<T>(v[4], v[5], v[6], v[7]);
+        *(typename T::vec8*)(out + f * 8) = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+}
+
+hipError_t launch_im2col_u8(const uint8_t* in, int batch, int image, int patch, int channels, int kpad, const float* scale,
+                            const float* shift, void* out16, int dtype, hipStream_t s) {
+    if (patch <= 0 || image % patch || channels < 1 || channels > kMaxChannels || batch < 1) return hipErrorInvalidValue;
+    const int kp = patch * patch * channels;
+    if (kpad < kp || kpad % 8 || (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16)) return hipErrorInvalidValue;
+    U8Norm norm;
+    for (int c = 0; c < kMaxChannels; ++c) {
+        norm.scale[c] = c < channels ? scale[c] : 0.f;
+        norm.shift[c] = c < channels ? shift[c] : 0.f;
+    }
+    const int g = image / patch;
+    const int64_t n8 = (int64_t)batch * g * g * (kpad / 8);
+    const unsigned grid = (unsigned)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384);
+    const bool vec8 = (patch * channels) % 8 == 0 && (image * channels) % 8 == 0 && ((uintptr_t)in & 7) == 0;
+    auto go = [&](auto kern, auto* o) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, in, o, n8, image, patch, channels, kpad, norm); };
+    if (dtype == VH_DTYPE_BF16) {
+        if (vec8) go(im2col_u8_kernel<BF16, true>, (BF16::elem*)out16);
+        else go(im2col_u8_kernel<BF16, false>, (BF16::elem*)out16);
+    } else {
+        if (vec8) go(im2col_u8_kernel<FP16, true>, (FP16::elem*)out16);
+        else go(im2col_u8_kernel<FP16, false>, (FP16::elem*)out16);
+    }
+    return hipGetLastError();
+}
+
 // ---- x[b, 0, :] = cls + pos[0] ------------------------------------------------------------------
 __global__ void cls_rows_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
                                 int batch, int tokens, int dim) {

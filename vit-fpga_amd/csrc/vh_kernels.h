@@ -105,6 +105,13 @@ inline float attention_q_scale(int head_dim) {
 // (one float4 per thread); otherwise im2col_pad_kernel (kpad >= patch^2 * channels, 8 | kpad, zeros in the pad columns)
 hipError_t launch_im2col(const float* in_nhwc, int batch, int image, int patch, int channels, int kpad,
                          void* out16, int dtype, hipStream_t stream);
+// The same patch matrix from 8-bit NHWC images: pixel p of channel c enters as fmaf((float)p, scale[c], shift[c]) (one
+// rounding) and takes the same RNE conversion, so the matrix has the bits launch_im2col gives for that fp32 array.  Any
+// patch / channel count, kpad >= patch^2 * channels, 8 | kpad, pad columns zero; scale / shift: host arrays [channels].
+// 8-byte loads where 8 | patch * channels, 8 | image * channels and the base is 8-byte aligned, byte loads otherwise.
+constexpr int kMaxChannels = 64;
+hipError_t launch_im2col_u8(const uint8_t* in_nhwc, int batch, int image, int patch, int channels, int kpad,
+                            const float* scale, const float* shift, void* out16, int dtype, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
 bool patch_fused_supported(int image, int patch, int channels, int dim);

@@ -10,6 +10,7 @@
 #include <dlfcn.h>
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -153,6 +154,16 @@ const char* kStageNames[ST_COUNT] = {"im2col", "patch_gemm", "cls_rows", "layern
 
 }  // namespace
 
+// The images of one forward: fp32 NHWC values the caller has normalised, or 8-bit NHWC pixels that the im2col kernel
+// normalises (im2col_u8_kernel).  Only the im2col call site of enqueue_forward looks at the kind.
+struct ImgIn {
+    const void* p;
+    bool u8;
+    size_t elem() const { return u8 ? 1 : 4; }
+    ImgIn skip(size_t elements) const { return ImgIn{(const char*)p + elements * elem(), u8}; }
+    bool operator==(const ImgIn& o) const { return p == o.p && u8 == o.u8; }
+};
+
 struct vh_ctx {
     vh_config cfg;
     int device;
@@ -223,18 +234,22 @@ struct vh_ctx {
     void* h16 = nullptr;      //                 [B*T, M]
     void* col16 = nullptr;    // patch matrix    [B*NP, KPA]
     float* clsn32 = nullptr;  // final-LN'd CLS  [B, D] fp32 (the head runs in fp32 on the blob's own weights)
-    float* in_dev = nullptr;  // staging for the host-pointer forward
+    float* in_dev = nullptr;  // staging for the host-pointer forward (fp32 images; vh_forward_u8 stages its bytes in the same buffer)
+    // Input normalisation of the 8-bit entry points (vh_set_input_norm): pixel p of channel c enters the model as
+    // fmaf((float)p, in_scale[c], in_shift[c]).  Passed to im2col_u8_kernel by value, so captured graphs hold a copy.
+    float in_scale[kMaxChannels], in_shift[kMaxChannels];
     float* logits_dev = nullptr;
     int64_t last_us = 0;
     bool timed = false;
     int last_batch = 0;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
     struct RingSlot {
-        float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+        float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;   // h_in / d_in hold bytes in a u8 ring
         hipEvent_t in_done = nullptr, fwd_done = nullptr, out_done = nullptr;
         int batch = 0;
     };
     std::vector<RingSlot> ring;
+    bool ring_u8 = false;     // vh_ring_create_u8: the slots stage 8-bit pixels (a quarter of the pinned and device memory)
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     int ring_batch = 0, ring_wr = 0, ring_rd = 0, ring_used = 0;
     // tail overlap (enqueue_forward, resid_gemm_ln): helper stream + events, CU count; VH_TAIL_OVERLAP=1 enables
@@ -246,9 +261,9 @@ struct vh_ctx {
     int tail_splits = 0;   // residual GEMMs of the last forward that were launched as [full rounds] + [tail round] (debug tap 2)
     int num_cu = 256;
     // optional hipGraph replay of the forward's launch sequence (vh_set_graph): one instantiated graph per
-    // (input pointer, logits pointer, batch); a batch size runs eagerly once before it is captured
+    // (input pointer, input kind, logits pointer, batch); a batch size runs eagerly once before it is captured
     bool use_graph = false;
-    struct GraphEntry { const float* in; float* out; int batch; hipGraph_t graph; hipGraphExec_t exec; };
+    struct GraphEntry { ImgIn in; float* out; int batch; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
     std::vector<int> graph_warm;   // batch sizes that have run eagerly (kernel attributes are set)
     // optional per-launch timing of ONE stage inside the timed region (bench.py's roofline)
@@ -426,7 +441,7 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
 // the launch sequence of ONE forward; `ev` (optional) receives an event after every stage
 // `img0`: first image of this part inside the activation arena (a batch can be split into parts that run on
 // different streams: rows of different images never interact), `s`: the stream to enqueue on.
-int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::vector<std::pair<int, hipEvent_t>>* ev,
+int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<std::pair<int, hipEvent_t>>* ev,
                     hipStream_t s, int img0, bool allow_tail = false, bool may_pad = true) {
     const vh_config& f = c->cfg;
     const Layout& L = c->L;
@@ -509,16 +524,21 @@ int enqueue_forward(vh_ctx* c, const float* in, int batch, float* logits, std::v
     const bool pre_ln = (f.flags & VH_FLAG_PRE_LN) != 0;
     const int epi_fc1 = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_LNFOLD_QGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
     const int epi_fc1_plain = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_BIAS_QGELU : VH_EPI_BIAS_GELU;       // plain layer loop
-    const bool fused_patch = !pre_ln && c->patch_fused && c->split && !c->fp8 && nl > 0 && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
+    // 8-bit images: always the im2col pass (which normalises) + the ordinary patch GEMM; the fused loader reads fp32 only
+    const bool fused_patch = !in.u8 && !pre_ln && c->patch_fused && c->split && !c->fp8 && nl > 0 && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
     if (!fused_patch) {
         if ((rc = tmark(ST_IM2COL))) return rc;
-        HIPCHK(&c->err, launch_im2col(in, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
+        if (in.u8)
+            HIPCHK(&c->err, launch_im2col_u8((const uint8_t*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale, c->in_shift,
+                                             col16, dt16, s));
+        else
+            HIPCHK(&c->err, launch_im2col((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
         if ((rc = tmark(ST_IM2COL))) return rc;
     }
     if ((rc = mark(ST_IM2COL))) return rc;
     if (fused_patch) {
         if ((rc = tmark(ST_PATCH))) return rc;
-        HIPCHK(&c->err, launch_patch_fused(in, batch, f.image_size, f.patch_size, f.channels, c->wp16, P + L.patch_b, P + L.pos, xn16, xlo16,
+        HIPCHK(&c->err, launch_patch_fused((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, c->wp16, P + L.patch_b, P + L.pos, xn16, xlo16,
                                            partials_p, rows_g, D, dt16, s));
         if ((rc = tmark(ST_PATCH))) return rc;
         if ((rc = mark(ST_PATCH))) return rc;
@@ -808,8 +828,8 @@ int guard_poll(vh_ctx* c) {
 
 // one complete forward of `batch` images on the context's stream(s): the (optional) concurrent parts are forked
 // from and joined back into c->stream, so everything that follows on c->stream sees the finished logits
-int enqueue_step(vh_ctx* c, const float* in, int batch, float* logits) {
-    const size_t img_floats = (size_t)c->cfg.image_size * c->cfg.image_size * c->cfg.channels;
+int enqueue_step(vh_ctx* c, ImgIn in, int batch, float* logits) {
+    const size_t img_elems = (size_t)c->cfg.image_size * c->cfg.image_size * c->cfg.channels;
     const int parts = batch < c->nstreams ? batch : c->nstreams;
     int rc;
     if (parts > 1) {
@@ -822,7 +842,7 @@ int enqueue_step(vh_ctx* c, const float* in, int batch, float* logits) {
             const int nb = batch / parts + (p < batch % parts ? 1 : 0);
             hipStream_t st = p == 0 ? c->stream : c->xstream[p - 1];
             if (p) HIPCHK(&c->err, hipStreamWaitEvent(st, c->ev_fork, 0));
-            if ((rc = enqueue_forward(c, in + (size_t)b0 * img_floats, nb, logits + (size_t)b0 * c->cfg.classes, nullptr, st, b0, false,
+            if ((rc = enqueue_forward(c, in.skip((size_t)b0 * img_elems), nb, logits + (size_t)b0 * c->cfg.classes, nullptr, st, b0, false,
                                       /*may_pad: only the last part has nothing behind its rows*/ p == parts - 1))) return rc;
             if (p) {
                 HIPCHK(&c->err, hipEventRecord(c->ev_join[p - 1], st));
@@ -847,7 +867,7 @@ void drop_graphs(vh_ctx* c) {
 
 // enqueue_step, or the replay of its captured launch sequence.  Small batches are launch-bound (ViT-B/16 at
 // batch 1: ~100 launches, 1.27 ms eager): the graph removes the per-launch API cost and the gaps between kernels.
-int run_step(vh_ctx* c, const float* in, int batch, float* logits) {
+int run_step(vh_ctx* c, ImgIn in, int batch, float* logits) {
     if (int rc = guard_poll(c)) return rc;
     if (!c->use_graph || c->timing_stage >= 0) return enqueue_step(c, in, batch, logits);
     for (auto& g : c->graphs)
@@ -890,7 +910,7 @@ int guard_calibrate(vh_ctx* c) {
     HIPCHK(&c->err, launch_fill(c->in_dev, n, 0xCA11B8A7Eull, TID_IMAGES, 0, 0.f, 0.f, c->stream));
     const int keep_stage = c->timing_stage;
     c->timing_stage = -1;
-    const int rc = enqueue_step(c, c->in_dev, 1, c->logits_dev);
+    const int rc = enqueue_step(c, ImgIn{c->in_dev, false}, 1, c->logits_dev);
     c->timing_stage = keep_stage;
     if (rc) return rc;
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
@@ -903,6 +923,75 @@ int check_forward_args(vh_ctx* c, const void* in, int batch, const void* out) {
     if (batch <= 0 || batch > c->cfg.max_batch)
         return fail(&c->err, VH_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->cfg.max_batch);
     if (!c->weights_ready) return fail(&c->err, VH_ERR_STATE, "forward before weights were loaded");
+    return VH_OK;
+}
+
+int check_u8_ptr(vh_ctx* c, const void* in_dev) {
+    if (c && ((uintptr_t)in_dev & 15)) return fail(&c->err, VH_ERR_INVALID, "8-bit device input %p is not 16-byte aligned", in_dev);
+    return VH_OK;
+}
+
+// the bodies of vh_forward_device_async / vh_forward_device / vh_forward for either kind of input
+int forward_device_async(vh_ctx* c, ImgIn in, int batch, float* logits, int steps) {
+    int rc = check_forward_args(c, in.p, batch, logits);
+    if (rc) return rc;
+    if (steps <= 0) return fail(&c->err, VH_ERR_INVALID, "steps must be positive");
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    c->tev_used = 0;
+    c->sev_used = 0;
+    auto step_mark = [&]() -> int {
+        if (!c->step_timing) return VH_OK;
+        if (c->sev_used == c->sev.size()) {
+            hipEvent_t e;
+            HIPCHK(&c->err, hipEventCreate(&e));
+            c->sev.push_back(e);
+        }
+        HIPCHK(&c->err, hipEventRecord(c->sev[c->sev_used++], c->stream));
+        return VH_OK;
+    };
+    HIPCHK(&c->err, hipEventRecord(c->ev0, c->stream));
+    if ((rc = step_mark())) return rc;
+    for (int i = 0; i < steps; ++i) {
+        if ((rc = run_step(c, in, batch, logits))) return rc;
+        if ((rc = step_mark())) return rc;
+    }
+    HIPCHK(&c->err, hipEventRecord(c->ev1, c->stream));
+    c->timed = true;
+    return VH_OK;
+}
+
+int forward_device(vh_ctx* c, ImgIn in, int batch, float* logits) {
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    int rc = forward_device_async(c, in, batch, logits, 1);
+    if (rc) return rc;
+    rc = vh_synchronize(c);
+    if (rc) return rc;
+    c->last_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::high_resolution_clock::now() - t0).count();
+    return VH_OK;
+}
+
+int forward_host(vh_ctx* c, ImgIn in_host, int batch, float* logits_host) {
+    int rc = check_forward_args(c, in_host.p, batch, logits_host);
+    if (rc) return rc;
+    const vh_config& f = c->cfg;
+    // same timing window as the reference: H2D + device work + blocking D2H (netFPGA.cpp:262-284)
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t in_bytes = (size_t)batch * f.image_size * f.image_size * f.channels * in_host.elem();
+    const ImgIn staged{c->in_dev, in_host.u8};
+    HIPCHK(&c->err, hipMemcpyAsync(c->in_dev, in_host.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    rc = forward_device_async(c, staged, batch, c->logits_dev, 1);
+    if (rc) return rc;
+    HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    if (c->guard_auto && guard_exceeded(c)) {
+        // this (synchronous) forward itself ran folded on rows beyond the guard: run it again, now with the stand-alone LayerNorm
+        rc = forward_device_async(c, staged, batch, c->logits_dev, 1);   // (its run_step polls the guard and switches)
+        if (rc) return rc;
+        HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    }
+    c->last_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::high_resolution_clock::now() - t0).count();
     return VH_OK;
 }
 
@@ -1060,6 +1149,10 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     }
     c->fp8 = cfg->dtype == VH_DTYPE_FP8;
     c->dt16 = c->fp8 ? VH_DTYPE_BF16 : cfg->dtype;
+    for (int i = 0; i < kMaxChannels; ++i) {   // 8-bit input: x = p / 255 until vh_set_input_norm says otherwise
+        c->in_scale[i] = i < cfg->channels ? 1.0f / 255.0f : 0.f;
+        c->in_shift[i] = 0.f;
+    }
     {
         // (fp8 operands: the hi plane is e4m3 -- the GEMM operand itself -- and the lo plane bf16: 3 bytes per element as well)
         const char* e = getenv("VH_RESID_SPLIT");
@@ -1386,31 +1479,12 @@ int vh_export_weights_device(vh_ctx* c, void* dev_blob, size_t nbytes) {
 }
 
 int vh_forward_device_async(vh_ctx* c, const float* in, int batch, float* logits, int steps) {
-    int rc = check_forward_args(c, in, batch, logits);
-    if (rc) return rc;
-    if (steps <= 0) return fail(&c->err, VH_ERR_INVALID, "steps must be positive");
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    c->tev_used = 0;
-    c->sev_used = 0;
-    auto step_mark = [&]() -> int {
-        if (!c->step_timing) return VH_OK;
-        if (c->sev_used == c->sev.size()) {
-            hipEvent_t e;
-            HIPCHK(&c->err, hipEventCreate(&e));
-            c->sev.push_back(e);
-        }
-        HIPCHK(&c->err, hipEventRecord(c->sev[c->sev_used++], c->stream));
-        return VH_OK;
-    };
-    HIPCHK(&c->err, hipEventRecord(c->ev0, c->stream));
-    if ((rc = step_mark())) return rc;
-    for (int i = 0; i < steps; ++i) {
-        if ((rc = run_step(c, in, batch, logits))) return rc;
-        if ((rc = step_mark())) return rc;
-    }
-    HIPCHK(&c->err, hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    return VH_OK;
+    return forward_device_async(c, ImgIn{in, false}, batch, logits, steps);
+}
+
+int vh_forward_device_u8_async(vh_ctx* c, const uint8_t* in, int batch, float* logits, int steps) {
+    if (int rc = check_u8_ptr(c, in)) return rc;
+    return forward_device_async(c, ImgIn{in, true}, batch, logits, steps);
 }
 
 int vh_synchronize(vh_ctx* c) {
@@ -1423,37 +1497,38 @@ int vh_synchronize(vh_ctx* c) {
     return VH_OK;
 }
 
-int vh_forward_device(vh_ctx* c, const float* in, int batch, float* logits) {
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    int rc = vh_forward_device_async(c, in, batch, logits, 1);
-    if (rc) return rc;
-    rc = vh_synchronize(c);
-    if (rc) return rc;
-    c->last_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::high_resolution_clock::now() - t0).count();
+int vh_forward_device(vh_ctx* c, const float* in, int batch, float* logits) { return forward_device(c, ImgIn{in, false}, batch, logits); }
+
+int vh_forward_device_u8(vh_ctx* c, const uint8_t* in, int batch, float* logits) {
+    if (int rc = check_u8_ptr(c, in)) return rc;
+    return forward_device(c, ImgIn{in, true}, batch, logits);
+}
+
+int vh_forward(vh_ctx* c, const float* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host, false}, batch, logits_host); }
+
+int vh_forward_u8(vh_ctx* c, const uint8_t* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host, true}, batch, logits_host); }
+
+// Input normalisation of the 8-bit entry points.  The constants travel to the im2col kernel as launch arguments, which a captured
+// graph holds by value: like a weight load, a change waits for the stream and drops the cached graphs.
+int vh_set_input_norm(vh_ctx* c, const float* scale, const float* shift) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
+    if ((scale == nullptr) != (shift == nullptr)) return fail(&c->err, VH_ERR_INVALID, "scale and shift: give both, or NULL for both (the default)");
+    const int ch = c->cfg.channels;
+    for (int i = 0; scale && i < ch; ++i)
+        if (!std::isfinite(scale[i]) || !std::isfinite(shift[i])) return fail(&c->err, VH_ERR_INVALID, "scale / shift of channel %d is not finite", i);
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < kMaxChannels; ++i) {
+        c->in_scale[i] = i < ch ? (scale ? scale[i] : 1.0f / 255.0f) : 0.f;
+        c->in_shift[i] = i < ch && shift ? shift[i] : 0.f;
+    }
+    drop_graphs(c);
     return VH_OK;
 }
 
-int vh_forward(vh_ctx* c, const float* in_host, int batch, float* logits_host) {
-    int rc = check_forward_args(c, in_host, batch, logits_host);
-    if (rc) return rc;
-    const vh_config& f = c->cfg;
-    // same timing window as the reference: H2D + device work + blocking D2H (netFPGA.cpp:262-284)
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)batch * f.image_size * f.image_size * f.channels * 4;
-    HIPCHK(&c->err, hipMemcpyAsync(c->in_dev, in_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    rc = vh_forward_device_async(c, c->in_dev, batch, c->logits_dev, 1);
-    if (rc) return rc;
-    HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if (c->guard_auto && guard_exceeded(c)) {
-        // this (synchronous) forward itself ran folded on rows beyond the guard: run it again, now with the stand-alone LayerNorm
-        rc = vh_forward_device_async(c, c->in_dev, batch, c->logits_dev, 1);   // (its run_step polls the guard and switches)
-        if (rc) return rc;
-        HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    }
-    c->last_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::high_resolution_clock::now() - t0).count();
+int vh_get_input_norm(const vh_ctx* c, float* scale, float* shift) {
+    if (!c || !scale || !shift) return fail(nullptr, VH_ERR_INVALID, "null argument");
+    for (int i = 0; i < c->cfg.channels; ++i) { scale[i] = c->in_scale[i]; shift[i] = c->in_shift[i]; }
     return VH_OK;
 }
 
@@ -1491,7 +1566,7 @@ int vh_profile_forward(vh_ctx* c, const float* in, int batch, float* logits, dou
     if (!stage_ms || n_slots < 2 * ST_COUNT) return fail(&c->err, VH_ERR_INVALID, "need %d stage slots (ms then launch counts)", 2 * ST_COUNT);
     HIPCHK(&c->err, hipSetDevice(c->device));
     std::vector<std::pair<int, hipEvent_t>> ev;
-    rc = enqueue_forward(c, in, batch, logits, &ev, c->stream, 0);
+    rc = enqueue_forward(c, ImgIn{in, false}, batch, logits, &ev, c->stream, 0);
     if (!rc) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) rc = fail(&c->err, VH_ERR_HIP, "sync: %s", hipGetErrorString(e)); }
     for (int i = 0; i < 2 * ST_COUNT; ++i) stage_ms[i] = 0.0;
     if (!rc)
@@ -1534,17 +1609,18 @@ int vh_ring_destroy(vh_ctx* c) {
     if (c->copy_out) hipStreamDestroy(c->copy_out);
     c->copy_in = c->copy_out = nullptr;
     c->ring_batch = c->ring_wr = c->ring_rd = c->ring_used = 0;
+    c->ring_u8 = false;
     return VH_OK;
 }
 
-int vh_ring_create(vh_ctx* c, int slots, int batch_per_slot) {
+static int ring_create(vh_ctx* c, int slots, int batch_per_slot, bool u8) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (slots < 1 || slots > 64) return fail(&c->err, VH_ERR_INVALID, "slots must be 1..64");
     if (batch_per_slot < 1 || batch_per_slot > c->cfg.max_batch)
         return fail(&c->err, VH_ERR_INVALID, "batch_per_slot %d outside 1..max_batch=%d", batch_per_slot, c->cfg.max_batch);
     vh_ring_destroy(c);
     HIPCHK(&c->err, hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)batch_per_slot * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * 4;
+    const size_t in_bytes = (size_t)batch_per_slot * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (u8 ? 1 : 4);
     const size_t out_bytes = (size_t)batch_per_slot * c->cfg.classes * 4;
     HIPCHK(&c->err, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
     HIPCHK(&c->err, hipStreamCreateWithFlags(&c->copy_out, hipStreamNonBlocking));
@@ -1563,8 +1639,12 @@ int vh_ring_create(vh_ctx* c, int slots, int batch_per_slot) {
         }
     }
     c->ring_batch = batch_per_slot;
+    c->ring_u8 = u8;
     return VH_OK;
 }
+
+int vh_ring_create(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, false); }
+int vh_ring_create_u8(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, true); }
 
 int vh_ring_free_slots(const vh_ctx* c, int* n) {
     if (!c || !n) return fail(nullptr, VH_ERR_INVALID, "null argument");
@@ -1572,29 +1652,34 @@ int vh_ring_free_slots(const vh_ctx* c, int* n) {
     return VH_OK;
 }
 
-int vh_ring_input(vh_ctx* c, float** pinned_in) {
+static int ring_input(vh_ctx* c, void** pinned_in, bool u8) {
     if (!c || !pinned_in) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
     if (c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "no ring: call vh_ring_create first");
+    if (c->ring_u8 != u8) return fail(&c->err, VH_ERR_STATE, "this ring stages %s images", c->ring_u8 ? "8-bit" : "fp32");
     if (c->ring_used == (int)c->ring.size()) return fail(&c->err, VH_ERR_RING_FULL, "ring full (PILA LLENA)");
     *pinned_in = c->ring[c->ring_wr].h_in;
     return VH_OK;
 }
 
-int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) {
+int vh_ring_input(vh_ctx* c, float** pinned_in) { return ring_input(c, (void**)pinned_in, false); }
+int vh_ring_input_u8(vh_ctx* c, uint8_t** pinned_in) { return ring_input(c, (void**)pinned_in, true); }
+
+static int ring_submit(vh_ctx* c, const void* in_host, int batch, bool u8) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "no ring: call vh_ring_create first");
+    if (c->ring_u8 != u8) return fail(&c->err, VH_ERR_STATE, "this ring stages %s images", c->ring_u8 ? "8-bit" : "fp32");
     if (!c->weights_ready) return fail(&c->err, VH_ERR_STATE, "submit before weights were loaded");
     if (batch < 1 || batch > c->ring_batch) return fail(&c->err, VH_ERR_INVALID, "batch %d outside 1..%d", batch, c->ring_batch);
     if (c->ring_used == (int)c->ring.size()) return fail(&c->err, VH_ERR_RING_FULL, "ring full (PILA LLENA)");
     HIPCHK(&c->err, hipSetDevice(c->device));
     vh_ctx::RingSlot& s = c->ring[c->ring_wr];
-    const size_t in_bytes = (size_t)batch * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * 4;
+    const size_t in_bytes = (size_t)batch * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (u8 ? 1 : 4);
     if (in_host && in_host != s.h_in) memcpy(s.h_in, in_host, in_bytes);  // NULL / the slot's own buffer: already filled in place
     s.batch = batch;
     HIPCHK(&c->err, hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, c->copy_in));
     HIPCHK(&c->err, hipEventRecord(s.in_done, c->copy_in));
     HIPCHK(&c->err, hipStreamWaitEvent(c->stream, s.in_done, 0));
-    int rc = run_step(c, s.d_in, batch, s.d_out);
+    int rc = run_step(c, ImgIn{s.d_in, u8}, batch, s.d_out);
     if (rc) return rc;
     HIPCHK(&c->err, hipEventRecord(s.fwd_done, c->stream));
     HIPCHK(&c->err, hipStreamWaitEvent(c->copy_out, s.fwd_done, 0));
@@ -1604,6 +1689,9 @@ int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) {
     ++c->ring_used;
     return VH_OK;
 }
+
+int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) { return ring_submit(c, in_host, batch, false); }
+int vh_ring_submit_u8(vh_ctx* c, const uint8_t* in_host, int batch) { return ring_submit(c, in_host, batch, true); }
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
     if (!c || !logits_host) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
@@ -1958,6 +2046,21 @@ int vh_op_im2col_padded(const float* in, int batch, int image, int patch, int ch
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
+int vh_op_im2col_u8(const uint8_t* in, int batch, int image, int patch, int channels, int kpad, const float* scale_host,
+                    const float* shift_host, void* out16, int dtype, void* stream) {
+    if (!in || !out16 || !scale_host || !shift_host) return fail(nullptr, VH_ERR_INVALID, "null buffer");
+    if (batch <= 0 || patch <= 0 || image <= 0 || image % patch || channels <= 0 || patch > 256 || channels > kMaxChannels ||
+        kpad < patch * patch * channels || kpad % 8)
+        return fail(nullptr, VH_ERR_INVALID, "im2col_u8: unsupported shape");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16) return fail(nullptr, VH_ERR_INVALID, "im2col_u8: unsupported dtype");
+    if ((uintptr_t)in & 15) return fail(nullptr, VH_ERR_INVALID, "im2col_u8: input %p is not 16-byte aligned", (const void*)in);
+    for (int i = 0; i < channels; ++i)
+        if (!std::isfinite(scale_host[i]) || !std::isfinite(shift_host[i])) return fail(nullptr, VH_ERR_INVALID, "im2col_u8: scale / shift of channel %d is not finite", i);
+    OPCHK(launch_im2col_u8(in, batch, image, patch, channels, kpad, scale_host, shift_host, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+
 int vh_op_cast(const float* in, void* out16, int64_t n, int dtype, void* stream) {
     if (!in || !out16 || n <= 0 || n % 4) return fail(nullptr, VH_ERR_INVALID, "cast: bad argument");
     OPCHK(launch_cast(in, out16, n, dtype, (hipStream_t)stream));

@@ -66,6 +66,11 @@ SYMBOLS = {
     "vh_forward_device": (_i, [_vp, _vp, _i, _vp]),
     "vh_forward_device_async": (_i, [_vp, _vp, _i, _vp, _i]),
     "vh_synchronize": (_i, [_vp]),
+    "vh_set_input_norm": (_i, [_vp, _vp, _vp]),
+    "vh_get_input_norm": (_i, [_vp, _vp, _vp]),
+    "vh_forward_u8": (_i, [_vp, _vp, _i, _vp]),
+    "vh_forward_device_u8": (_i, [_vp, _vp, _i, _vp]),
+    "vh_forward_device_u8_async": (_i, [_vp, _vp, _i, _vp, _i]),
     "vh_fill_input_seeded": (_i, [_vp, _u64, _i, _vp]),
     "vh_last_forward_us": (_i, [_vp, C.POINTER(_i64)]),
     "vh_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
@@ -88,6 +93,9 @@ SYMBOLS = {
     "vh_ring_input": (_i, [_vp, C.POINTER(C.POINTER(C.c_float))]),
     "vh_ring_submit": (_i, [_vp, _vp, _i]),
     "vh_ring_collect": (_i, [_vp, _vp, _pi]),
+    "vh_ring_create_u8": (_i, [_vp, _i, _i]),
+    "vh_ring_input_u8": (_i, [_vp, C.POINTER(C.POINTER(C.c_uint8))]),
+    "vh_ring_submit_u8": (_i, [_vp, _vp, _i]),
     "vh_set_graph": (_i, [_vp, _i]),
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
@@ -116,6 +124,7 @@ SYMBOLS = {
     "vh_op_attention_layout": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _vp]),
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vh_op_im2col_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -238,6 +247,15 @@ def device_free_bytes(device=0):
     free, total = C.c_size_t(0), C.c_size_t(0)
     _check(lib().vh_device_mem_info(device, C.byref(free), C.byref(total)))
     return free.value
+
+
+def input_norm_from_mean_std(mean, std):
+    """(scale, shift) for set_input_norm such that a pixel p enters as (p / 255 - mean) / std: scale = 1 / (255 std),
+    shift = -mean / std per channel, computed in float64 and rounded once to float32."""
+    mean, std = np.atleast_1d(np.asarray(mean, dtype=np.float64)), np.atleast_1d(np.asarray(std, dtype=np.float64))
+    if mean.shape != std.shape or mean.ndim != 1 or not (std != 0).all():
+        raise ValueError("input_norm_from_mean_std: mean and std are per-channel vectors of one length, std non-zero")
+    return (1.0 / (255.0 * std)).astype(np.float32), (-mean / std).astype(np.float32)
 
 
 def make_config(cfg, dtype=DTYPE_BF16, max_batch=1, ln_eps=1e-6, flags=0):
@@ -458,6 +476,44 @@ class VitContext:
     def synchronize(self):
         _check(lib().vh_synchronize(self.h), self.h)
 
+    # ---- 8-bit images: pixel p of channel c enters as fmaf(float(p), scale[c], shift[c]), one rounding ----
+    def set_input_norm(self, scale=None, shift=None):
+        """Per-channel constants of the u8 entry points ([channels] each; None, None = the default 1/255, 0)."""
+        if scale is None and shift is None:
+            _check(lib().vh_set_input_norm(self.h, None, None), self.h)
+            return
+        ch = self.cfg["channels"]
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+        sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float32).reshape(-1)
+        for a in (sc, sh):
+            if a is not None and a.size != ch:
+                raise ValueError(f"set_input_norm: expected {ch} values per array, got {a.size}")
+        _check(lib().vh_set_input_norm(self.h, None if sc is None else sc.ctypes.data, None if sh is None else sh.ctypes.data), self.h)
+
+    def get_input_norm(self):
+        ch = self.cfg["channels"]
+        sc, sh = np.empty(ch, dtype=np.float32), np.empty(ch, dtype=np.float32)
+        _check(lib().vh_get_input_norm(self.h, sc.ctypes.data, sh.ctypes.data), self.h)
+        return sc, sh
+
+    def forward_u8(self, images):
+        """images: [B, H, W, C] uint8 (host).  Returns [B, classes] fp32 logits: the bits forward() gives for the fp32 array
+        fmaf(p, scale[c], shift[c])."""
+        images = np.asarray(images)
+        if images.dtype != np.uint8:
+            raise TypeError(f"forward_u8 takes uint8 images, got {images.dtype}")
+        images = np.ascontiguousarray(images)
+        b = images.shape[0]
+        out = np.empty((b, self.cfg["classes"]), dtype=np.float32)
+        _check(lib().vh_forward_u8(self.h, images.ctypes.data, b, out.ctypes.data), self.h)
+        return out
+
+    def forward_device_u8(self, in_ptr, batch, out_ptr):
+        _check(lib().vh_forward_device_u8(self.h, in_ptr, batch, out_ptr), self.h)
+
+    def forward_device_u8_async(self, in_ptr, batch, out_ptr, steps=1):
+        _check(lib().vh_forward_device_u8_async(self.h, in_ptr, batch, out_ptr, steps), self.h)
+
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
 
@@ -479,9 +535,30 @@ class VitContext:
         return {STAGES[i]: (arr[i], int(arr[n + i])) for i in range(n)}
 
     # ---- pipelined host path (ring of in-flight batches) ----
-    def ring_create(self, slots, batch_per_slot):
-        _check(lib().vh_ring_create(self.h, slots, batch_per_slot), self.h)
+    def ring_create(self, slots, batch_per_slot, u8=False):
+        """u8=True: the slots stage 8-bit images (ring_input_u8 / ring_submit_u8); a quarter of the staging memory."""
+        _check((lib().vh_ring_create_u8 if u8 else lib().vh_ring_create)(self.h, slots, batch_per_slot), self.h)
         self._ring_batch = batch_per_slot
+
+    def ring_create_u8(self, slots, batch_per_slot):
+        self.ring_create(slots, batch_per_slot, u8=True)
+
+    def ring_input_u8(self, batch):
+        """numpy uint8 view of the pinned staging buffer the next ring_submit_u8 will use."""
+        p = C.POINTER(C.c_uint8)()
+        _check(lib().vh_ring_input_u8(self.h, C.byref(p)), self.h)
+        n = batch * self.cfg["image_size"] ** 2 * self.cfg["channels"]
+        return np.ctypeslib.as_array(p, shape=(n,)).reshape(batch, self.cfg["image_size"], self.cfg["image_size"], self.cfg["channels"])
+
+    def ring_submit_u8(self, images=None, batch=None):
+        if images is None:
+            _check(lib().vh_ring_submit_u8(self.h, None, batch), self.h)
+            return
+        images = np.asarray(images)
+        if images.dtype != np.uint8:
+            raise TypeError(f"ring_submit_u8 takes uint8 images, got {images.dtype}")
+        images = np.ascontiguousarray(images)
+        _check(lib().vh_ring_submit_u8(self.h, images.ctypes.data, images.shape[0]), self.h)
 
     def ring_free_slots(self):
         n = C.c_int(0)
@@ -808,6 +885,18 @@ def op_im2col_padded(in_ptr, batch, image, patch, channels, kpad, out_ptr, dtype
     """Patch matrix [batch*np, kpad] for any patch and channel count: columns patch^2*channels..kpad-1 are zero.
     kpad >= patch^2*channels and a multiple of 8; dtype bf16 or fp16."""
     _check(lib().vh_op_im2col_padded(in_ptr, batch, image, patch, channels, kpad, out_ptr, dtype, None))
+
+
+def op_im2col_u8(in_ptr, batch, image, patch, channels, kpad, scale, shift, out_ptr, dtype):
+    """Patch matrix [batch*np, kpad] of uint8 NHWC images: element = dtype(fmaf(float(p), scale[c], shift[c])), pad columns
+    zero.  scale / shift: host arrays [channels]; in_ptr 16-byte aligned."""
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+    sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float32).reshape(-1)
+    for a in (sc, sh):
+        if a is not None and a.size != channels:
+            raise ValueError(f"op_im2col_u8: expected {channels} values per array, got {a.size}")
+    _check(lib().vh_op_im2col_u8(in_ptr, batch, image, patch, channels, kpad, None if sc is None else sc.ctypes.data,
+                                 None if sh is None else sh.ctypes.data, out_ptr, dtype, None))
 
 
 def op_cast(in_ptr, out_ptr, n, dtype):
