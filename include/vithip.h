@@ -232,6 +232,38 @@ int vh_get_input_norm(const vh_ctx* ctx, float* scale, float* shift);
 int vh_forward_u8(vh_ctx* ctx, const uint8_t* in_nhwc_host, int batch, float* logits_host);
 int vh_forward_device_u8(vh_ctx* ctx, const uint8_t* in_nhwc_dev, int batch, float* logits_dev);
 int vh_forward_device_u8_async(vh_ctx* ctx, const uint8_t* in_nhwc_dev, int batch, float* logits_dev, int steps);
+/* ---- 8-bit frames: antialiased resize + crop on the GPU in front of the u8 forward -----------------------------------
+ * What a decoder or a camera emits is not image x image.  A FRAME is 8-bit interleaved pixels, height x width x channels
+ * (channels = the context's), rows row_stride bytes apart, starting `offset` bytes into the buffer of the call.  A BOX
+ * (x0, y0, x1, y1) = box[0..3] is given in source pixel coordinates, pixel j covering [j, j+1); it may be fractional and
+ * need not be square; 0 <= x0 < x1 <= width, and the same in y.  The box is resampled to S x S, S = image_size, with the
+ * antialiased triangle filter of torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False).
+ * CONTRACT, per axis, with n the source length, [lo, hi) the box, scale = (hi - lo) / S, sup = max(scale, 1): output i has
+ *       centre   c = lo + (i + 0.5) scale
+ *       taps     j in [max(floor(c - sup + 0.5), 0), min(floor(c + sup + 0.5), n))
+ *       weights  w_j = max(0, 1 - |(j + 0.5 - c) / sup|), zero weights dropped, the rest divided by their sum
+ * all in double on the host, each weight then rounded ONCE to fp32 (vh_resize_table returns exactly this table).  The
+ * kernel runs the horizontal pass, then the vertical pass; each accumulates in fp32 with fmaf in ascending tap order
+ * starting from 0, with no rounding between the passes; the result byte is rintf(min(max(v, 0), 255)).  From there on the
+ * forward IS vh_forward_u8 of that S x S x channels byte image: fmaf(p, scale[c], shift[c]) in the patch gather and
+ * vh_set_input_norm apply unchanged, and the logits are BIT-IDENTICAL to feeding vh_op_resize_u8's output to the u8 entry
+ * point.  Refused with VH_ERR_INVALID before anything is enqueued: width or height outside 1..8192; row_stride <
+ * width * channels; scale > 32 on an axis (at most 65 taps); a box outside the frame, or empty; a frame whose last byte
+ * lies beyond nbytes.  Frames of one call may all differ in size, stride and box; the descriptors are copied at the call.
+ *   vh_resize_table     host only, no device: first[n_out], count[n_out], weights[n_out][max_taps] (zero padded) of one
+ *                       axis; VH_ERR_INVALID for a bad box, scale > 32 or a row with more than max_taps taps.
+ *   vh_forward_frames_u8, vh_forward_device_frames_u8: vh_forward_u8 / vh_forward_device_u8 of the resized boxes;
+ *                       `nbytes` is the size of the frames buffer (host: copied whole; any alignment, any offsets).  The
+ *                       resize runs once on the context's stream before the forward (before the fork of vh_set_streams);
+ *                       stage "resize" of vh_set_stage_timing times it. */
+typedef struct vh_frame {
+    uint64_t offset;
+    int32_t height, width, row_stride;
+    float box[4];
+} vh_frame;
+int vh_resize_table(int n_in, double lo, double hi, int n_out, int32_t* first, int32_t* count, float* weights, int max_taps);
+int vh_forward_frames_u8(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch, float* logits_host);
+int vh_forward_device_frames_u8(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame* desc, int batch, float* logits_dev);
 /* uniform[-1,1) synthetic images written straight into HBM (value range of the reference,
  * def/defines.h:11-12) */
 int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_dev);
@@ -261,6 +293,16 @@ int vh_ring_collect(vh_ctx* ctx, float* logits_host, int* batch);
 int vh_ring_create_u8(vh_ctx* ctx, int slots, int batch_per_slot);
 int vh_ring_input_u8(vh_ctx* ctx, uint8_t** pinned_in_nhwc);
 int vh_ring_submit_u8(vh_ctx* ctx, const uint8_t* in_nhwc_host, int batch);
+/* The same ring with slots that stage FRAMES ("8-bit frames" above): each slot holds slot_bytes of pinned and of device
+ * memory for the frames of one submit, any sizes.  vh_ring_input_frames: the pinned buffer the next submit uploads and
+ * its capacity (= slot_bytes).  vh_ring_submit_frames: frames_host NULL (or the slot's own buffer) = filled in place;
+ * nbytes <= slot_bytes; the descriptors are checked and copied before anything is enqueued, and a refused submit leaves
+ * the ring as it was.  A collected batch has the bits vh_forward_frames_u8 returns.  vh_ring_collect, vh_ring_free_slots
+ * and vh_ring_destroy serve this kind too; the input and submit calls of the other two kinds return VH_ERR_STATE on a
+ * frames ring, and the frames calls return VH_ERR_STATE on the other kinds. */
+int vh_ring_create_frames(vh_ctx* ctx, int slots, int batch_per_slot, size_t slot_bytes);
+int vh_ring_input_frames(vh_ctx* ctx, uint8_t** pinned, size_t* capacity);
+int vh_ring_submit_frames(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -288,7 +330,8 @@ int vh_last_kernel_ms(vh_ctx* ctx, double* ms);
 int vh_profile_forward(vh_ctx* ctx, const float* in_nhwc_dev, int batch, float* logits_dev,
                        double* stage_ms, int n_stage_slots, int* n_stages_written);
 const char* vh_stage_name(int stage_index);
-/* Time every launch of ONE stage (index as in vh_stage_name; -1 = off) with hip events on the
+/* Time every launch of ONE stage (index as in vh_stage_name; -1 = off; the last index, "resize", is the resize launch of
+ * the frames entry points, which vh_profile_forward -- an fp32 forward -- never runs and does not report) with hip events on the
  * context's stream during the following vh_forward_device_async calls, then read the average /
  * minimum launch duration and the number of launches measured. */
 int vh_set_stage_timing(vh_ctx* ctx, int stage_index);
@@ -438,6 +481,11 @@ int vh_op_im2col_padded(const float* in_nhwc_dev, int batch, int image, int patc
  * arrays [channels], finite; in_nhwc_dev 16-byte aligned (else VH_ERR_INVALID). */
 int vh_op_im2col_u8(const uint8_t* in_nhwc_dev, int batch, int image, int patch, int channels, int kpad,
                     const float* scale_host, const float* shift_host, void* out16_dev, int dtype, void* stream);
+/* The resize of the frames entry points on its own ("8-bit frames"): frames_dev (any alignment, any offsets) ->
+ * out_u8_dev [batch][out_size][out_size][channels] bytes.  desc_host: HOST array [batch]; channels 1..64, out_size
+ * 1..4096.  Allocates and frees its table buffer: a test and measurement tap, not a hot path. */
+int vh_op_resize_u8(const uint8_t* frames_dev, size_t nbytes, const vh_frame* desc_host, int batch, int channels,
+                    int out_size, uint8_t* out_u8_dev, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,

@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""Frames measurements (run on the GPU box): what resizing and cropping on the GPU costs on the host path.
+
+  python tools/frames_bench.py [--out profiles] [--steps 30] [--passes 3] [--only NAME]
+
+In ONE process, for ViT-B/16 bf16 at batch 512, ViT-B/16 fp8 at batch 512 and CLIP ViT-B/32 bf16 at batch 256, three rings of 3
+slots (pinned host memory -> logits in host memory), interleaved `passes` times, the median pass reported with min and max:
+  (1) the u8 ring fed pre-resized 224 x 224 images -- the yardstick;
+  (2) the frames ring fed 256 x 256 frames with the 0.875 centre box (scale exactly 1: the resize is a crop);
+  (3) the frames ring fed 360 x 480 frames with the 0.875 centre box (315 x 315 -> 224, about 4 taps per axis).
+The images of (1) are the centre crops of the frames of (2), so those two rings compute the same logits, which is checked.
+Then the resize launch of (2) and (3) alone, hip events around it (vh_set_stage_timing("resize")), two interleaved passes: us per
+launch and the GB/s of source bytes inside the boxes.  Written to <out>/frames_host_path.txt and .json.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "vit-fpga_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import vh_synth as S  # noqa: E402
+import vithip  # noqa: E402
+
+DT = {"bf16": vithip.DTYPE_BF16, "fp8": vithip.DTYPE_FP8}
+CLIP_B32 = dict(image_size=224, patch_size=32, channels=3, dim=768, heads=12, mlp_dim=3072, layers=12, classes=512)
+RUNS = [("ViT-B/16 bf16 b512", "vit_b16_bf16", S.CONFIGS["vit_base"], "bf16", 512, 0, 1e-6),
+        ("ViT-B/16 fp8 b512", "vit_b16_fp8", S.CONFIGS["vit_base"], "fp8", 512, 0, 1e-6),
+        ("CLIP ViT-B/32 bf16 b256", "clip_b32_bf16", CLIP_B32, "bf16", 256, vithip.FLAG_PRE_LN | vithip.FLAG_QUICK_GELU, 1e-5)]
+SLOTS = 3
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+class Side:
+    """One context with one ring: u8 slots fed `images`, or frames slots fed `frames` (one [B, H, W, C] array) and one box."""
+
+    def __init__(self, cfg, dname, batch, flags, eps, scale, shift, images=None, frames=None, box=None):
+        self.batch, self.frames = batch, frames is not None
+        self.ctx = vithip.VitContext(cfg, dtype=DT[dname], max_batch=batch, flags=flags, ln_eps=eps)
+        self.ctx.init_weights_seeded(0)
+        self.ctx.set_input_norm(scale, shift)
+        if self.frames:
+            _, h, w, ch = frames.shape
+            self.nbytes = frames.nbytes
+            self.desc = (vithip.Frame * batch)()
+            for b in range(batch):
+                d = self.desc[b]
+                d.offset, d.height, d.width, d.row_stride = b * h * w * ch, h, w, w * ch
+                d.box[:] = box
+            self.box_bytes = batch * (box[2] - box[0]) * (box[3] - box[1]) * ch
+            self.ctx.ring_create_frames(SLOTS, batch, self.nbytes)
+        else:
+            self.nbytes = images.nbytes
+            self.ctx.ring_create(SLOTS, batch, u8=True)
+        for _ in range(SLOTS):   # fill every slot's pinned staging buffer once (a producer writes there in place); warms up too
+            if self.frames:
+                self.ctx.ring_input_frames()[:self.nbytes] = frames.reshape(-1)
+            else:
+                self.ctx.ring_input_u8(batch)[...] = images
+            self.submit()
+        self.first = [self.ctx.ring_collect().copy() for _ in range(SLOTS)][0]
+
+    def submit(self):
+        if self.frames:
+            self.ctx.ring_submit_frames_packed(None, self.nbytes, self.desc)
+        else:
+            self.ctx.ring_submit_u8(None, self.batch)
+
+    def ring_rate(self, steps):
+        self.ctx.synchronize()
+        t0 = time.perf_counter()
+        inflight = 0
+        for _ in range(steps):
+            if inflight == SLOTS:
+                self.ctx.ring_collect(); inflight -= 1
+            self.submit(); inflight += 1
+        while inflight:
+            self.ctx.ring_collect(); inflight -= 1
+        return self.batch * steps / (time.perf_counter() - t0)
+
+    def resize_us(self, steps):
+        self.ctx.set_stage_timing("resize")
+        for _ in range(steps):
+            self.submit()
+            self.ctx.ring_collect()
+        avg_ms, min_ms, launches = self.ctx.get_stage_timing()
+        self.ctx.set_stage_timing(None)
+        return avg_ms * 1e3, min_ms * 1e3, launches
+
+    def close(self):
+        self.ctx.close()
+
+
+def mid(v):
+    return float(np.median(v)), float(np.min(v)), float(np.max(v))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--only", default="")
+    a = ap.parse_args()
+    lines, rows = [], []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    scale, shift = vithip.input_norm_from_mean_std(MEAN, STD)
+    log(f"frames_bench: rings of {SLOTS} slots, {a.steps} steps per pass, {a.passes} interleaved passes (u8 ring 224x224, frames ring "
+        f"256x256, frames ring 360x480; 0.875 centre box); median pass [min .. max]; images/s")
+    for title, key, cfg, dname, batch, flags, eps in RUNS:
+        if a.only and a.only != key:
+            continue
+        rng = np.random.default_rng(3)
+        f256 = rng.integers(0, 256, size=(batch, 256, 256, 3), dtype=np.uint8)
+        f360 = rng.integers(0, 256, size=(batch, 360, 480, 3), dtype=np.uint8)
+        crops = np.ascontiguousarray(f256[:, 16:240, 16:240])
+        common = (cfg, dname, batch, flags, eps, scale, shift)
+        U = Side(*common, images=crops)
+        A = Side(*common, frames=f256, box=vithip.center_crop_box(256, 256))
+        B = Side(*common, frames=f360, box=vithip.center_crop_box(360, 480))
+        same = bool(np.array_equal(U.first.view(np.uint32), A.first.view(np.uint32)) and np.isfinite(U.first).all())
+        ru, ra, rb = [], [], []
+        for _ in range(a.passes):
+            ru.append(U.ring_rate(a.steps)); ra.append(A.ring_rate(a.steps)); rb.append(B.ring_rate(a.steps))
+        k = [A.resize_us(8), B.resize_us(8), A.resize_us(8), B.resize_us(8)]
+        r = dict(config=key, title=title, batch=batch, dtype=dname, logits_256_equal_u8_ring=same,
+                 ring_u8=mid(ru), ring_frames_256=mid(ra), ring_frames_360x480=mid(rb),
+                 h2d_MB_per_step=dict(u8=U.nbytes / 1e6, frames_256=A.nbytes / 1e6, frames_360x480=B.nbytes / 1e6),
+                 resize_256_us_avg=[k[0][0], k[2][0]], resize_360x480_us_avg=[k[1][0], k[3][0]],
+                 resize_256_us_min=min(k[0][1], k[2][1]), resize_360x480_us_min=min(k[1][1], k[3][1]),
+                 resize_launches=k[0][2], box_MB=dict(frames_256=A.box_bytes / 1e6, frames_360x480=B.box_bytes / 1e6))
+        rows.append(r)
+        base = r["ring_u8"][0]
+        log(f"{title}: logits of the 256x256 frames ring equal the u8 ring's on the centre crops: {same}")
+        for name, kk, mb in (("u8 ring, 224x224     ", "ring_u8", U.nbytes / 1e6), ("frames ring, 256x256 ", "ring_frames_256", A.nbytes / 1e6),
+                             ("frames ring, 360x480 ", "ring_frames_360x480", B.nbytes / 1e6)):
+            m, lo, hi = r[kk]
+            log(f"    {name}: {m:9.0f} [{lo:9.0f} .. {hi:9.0f}] = {100 * m / base:6.2f} % of the u8 ring | upload {mb:6.1f} MB per step = "
+                f"{mb * 1e-3 * m / batch:5.1f} GB/s")
+        for name, avg, mn, mb in (("256x256", r["resize_256_us_avg"], r["resize_256_us_min"], A.box_bytes / 1e6),
+                                  ("360x480", r["resize_360x480_us_avg"], r["resize_360x480_us_min"], B.box_bytes / 1e6)):
+            us = float(np.mean(avg))
+            log(f"    resize {name}: {us:8.1f} us per launch avg ({mn:.1f} min; passes {avg[0]:.1f} {avg[1]:.1f}; {r['resize_launches']} launches) | "
+                f"{mb:.1f} MB inside the boxes = {mb * 1e-3 / (us * 1e-6):.0f} GB/s | {100 * us * 1e-6 * base / batch:.2f} % of a u8-ring step")
+        U.close(); A.close(); B.close()
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "frames_host_path.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+    with open(os.path.join(a.out, "frames_host_path.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <vector>
 
 #include "vh_common.h"
 
@@ -112,6 +113,18 @@ hipError_t launch_im2col(const float* in_nhwc, int batch, int image, int patch, 
 constexpr int kMaxChannels = 64;
 hipError_t launch_im2col_u8(const uint8_t* in_nhwc, int batch, int image, int patch, int channels, int kpad,
                             const float* scale, const float* shift, void* out16, int dtype, hipStream_t stream);
+// Antialiased resize + crop of 8-bit interleaved frames to S x S (kernels_resize.hip; contract: vithip.h, "8-bit frames").
+// resize_axis_table: the table of one axis (host, double, one rounding to fp32; weights [n_out][max_taps], zero padded); 0 = ok.
+// resize_plan_build: checks every descriptor and fills `words` with [batch x 16-word frame record][tables] as the kernel reads
+// them; returns nullptr, or why the call is refused.  launch_resize_u8: one launch for the batch; plan_dev = those words in HBM.
+constexpr int kResizeMaxTaps = 65, kResizeMaxScale = 32, kResizeMaxSide = 8192;
+constexpr int kResizeLdsFloats = 16384;   // 64 KiB: two workgroups per CU
+constexpr int kResizeFrameWords = 16;
+int resize_axis_table(int n_in, double lo, double hi, int n_out, int32_t* first, int32_t* count, float* weights, int max_taps);
+const char* resize_plan_build(const vh_frame* desc, int batch, int channels, int S, size_t nbytes, bool base_aligned4,
+                              std::vector<uint32_t>* words, int* max_tiles);
+hipError_t launch_resize_u8(const uint8_t* frames, const uint32_t* plan_dev, int batch, int channels, int S, int max_tiles,
+                            uint8_t* out_u8, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
 bool patch_fused_supported(int image, int patch, int channels, int dim);

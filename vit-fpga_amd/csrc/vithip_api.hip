@@ -148,9 +148,12 @@ const char* check_config(const vh_config& c) {
     return nullptr;
 }
 
-enum Stage { ST_IM2COL, ST_PATCH, ST_CLS, ST_LN, ST_QKV, ST_ATTN, ST_PROJ, ST_FC1, ST_FC2, ST_LNF, ST_HEAD, ST_LNSTATS, ST_PRELN, ST_COUNT };
+enum Stage { ST_IM2COL, ST_PATCH, ST_CLS, ST_LN, ST_QKV, ST_ATTN, ST_PROJ, ST_FC1, ST_FC2, ST_LNF, ST_HEAD, ST_LNSTATS, ST_PRELN, ST_RESIZE, ST_COUNT };
+// ST_RESIZE is no stage of enqueue_forward: the frames entry points launch it in front of the forward.  vh_profile_forward (an
+// fp32 forward) keeps reporting the kProfiledStages stages before it, in the slot layout its callers were built against.
+constexpr int kProfiledStages = ST_RESIZE;
 const char* kStageNames[ST_COUNT] = {"im2col", "patch_gemm", "cls_rows", "layernorm", "qkv_gemm", "attention",
-                                     "proj_gemm", "fc1_gemm", "fc2_gemm", "final_layernorm", "head_gemm", "ln_stats", "pre_layernorm"};
+                                     "proj_gemm", "fc1_gemm", "fc2_gemm", "final_layernorm", "head_gemm", "ln_stats", "pre_layernorm", "resize"};
 
 }  // namespace
 
@@ -239,6 +242,17 @@ struct vh_ctx {
     // fmaf((float)p, in_scale[c], in_shift[c]).  Passed to im2col_u8_kernel by value, so captured graphs hold a copy.
     float in_scale[kMaxChannels], in_shift[kMaxChannels];
     float* logits_dev = nullptr;
+    // 8-bit frames (vh_forward_frames_u8, the frames ring; kernels_resize.hip).  All of it is allocated at the first frames call
+    // and grown only when a call needs more than any before it: rz_u8 = the resized images [max_batch][S][S][C] the forward then
+    // reads through ImgIn{rz_u8, u8}; rz_plan_dev = descriptors + tables in HBM (uploaded on the stream that runs the resize, so one
+    // buffer serves every ring slot); rz_plan_host = their pinned staging for the synchronous entry points (a ring slot has its own);
+    // rz_frames = device staging of vh_forward_frames_u8's host frames; rz_words = the host scratch the plan is built in.
+    uint8_t* rz_u8 = nullptr;
+    uint32_t *rz_plan_dev = nullptr, *rz_plan_host = nullptr;
+    size_t rz_plan_dev_cap = 0, rz_plan_host_cap = 0;   // words
+    uint8_t* rz_frames = nullptr;
+    size_t rz_frames_cap = 0;
+    std::vector<uint32_t> rz_words;
     int64_t last_us = 0;
     bool timed = false;
     int last_batch = 0;
@@ -247,9 +261,15 @@ struct vh_ctx {
         float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;   // h_in / d_in hold bytes in a u8 ring
         hipEvent_t in_done = nullptr, fwd_done = nullptr, out_done = nullptr;
         int batch = 0;
+        uint32_t* h_plan = nullptr;   // frames ring: pinned staging of the slot's descriptors + tables
+        size_t plan_cap = 0;          // words
     };
     std::vector<RingSlot> ring;
-    bool ring_u8 = false;     // vh_ring_create_u8: the slots stage 8-bit pixels (a quarter of the pinned and device memory)
+    // what the slots stage: fp32 images, 8-bit images (a quarter of the pinned and device memory), or 8-bit frames of any size
+    // (ring_slot_bytes each; resized on the context's stream in front of the forward)
+    enum RingKind { RING_F32, RING_U8, RING_FRAMES };
+    RingKind ring_kind = RING_F32;
+    size_t ring_slot_bytes = 0;
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     int ring_batch = 0, ring_wr = 0, ring_rd = 0, ring_used = 0;
     // tail overlap (enqueue_forward, resid_gemm_ln): helper stream + events, CU count; VH_TAIL_OVERLAP=1 enables
@@ -931,8 +951,78 @@ int check_u8_ptr(vh_ctx* c, const void* in_dev) {
     return VH_OK;
 }
 
-// the bodies of vh_forward_device_async / vh_forward_device / vh_forward for either kind of input
-int forward_device_async(vh_ctx* c, ImgIn in, int batch, float* logits, int steps) {
+// ---- 8-bit frames: plan, buffers, the resize launch ---------------------------------------------------------------------------
+// One resize in front of a forward: the frames in HBM and the descriptors + tables (c->rz_words) in pinned memory.
+struct FrameJob {
+    const uint8_t* frames_dev;
+    const uint32_t* plan_host;   // pinned; stays untouched until the upload below has run
+    size_t words;
+    int max_tiles;
+};
+
+// checks the descriptors of one call and builds its plan in c->rz_words; nothing is enqueued
+int frames_plan(vh_ctx* c, const vh_frame* desc, int batch, size_t nbytes, bool base_aligned4, int* max_tiles) {
+    if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
+    const char* why = resize_plan_build(desc, batch, c->cfg.channels, c->cfg.image_size, nbytes, base_aligned4, &c->rz_words, max_tiles);
+    if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
+    return VH_OK;
+}
+
+// grow-only: the resized images (once), and room for `plan_words` words in HBM (and, host_too, in the context's pinned staging)
+// and for `frame_bytes` of staged host frames.  A buffer is replaced only after the stream that may still read it has drained.
+int frames_reserve(vh_ctx* c, size_t plan_words, bool host_too, size_t frame_bytes) {
+    const vh_config& f = c->cfg;
+    if (!c->rz_u8) HIPCHK(&c->err, hipMalloc((void**)&c->rz_u8, (size_t)f.max_batch * f.image_size * f.image_size * f.channels));
+    if (plan_words > c->rz_plan_dev_cap) {
+        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+        if (c->rz_plan_dev) hipFree(c->rz_plan_dev);
+        c->rz_plan_dev = nullptr; c->rz_plan_dev_cap = 0;
+        const size_t cap = plan_words * 2 > 16384 ? plan_words * 2 : 16384;
+        HIPCHK(&c->err, hipMalloc((void**)&c->rz_plan_dev, cap * 4));
+        c->rz_plan_dev_cap = cap;
+    }
+    if (host_too && plan_words > c->rz_plan_host_cap) {
+        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+        if (c->rz_plan_host) hipHostFree(c->rz_plan_host);
+        c->rz_plan_host = nullptr; c->rz_plan_host_cap = 0;
+        const size_t cap = plan_words * 2 > 16384 ? plan_words * 2 : 16384;
+        HIPCHK(&c->err, hipHostMalloc((void**)&c->rz_plan_host, cap * 4, hipHostMallocDefault));
+        c->rz_plan_host_cap = cap;
+    }
+    if (frame_bytes > c->rz_frames_cap) {
+        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+        if (c->rz_frames) hipFree(c->rz_frames);
+        c->rz_frames = nullptr; c->rz_frames_cap = 0;
+        const size_t cap = frame_bytes + frame_bytes / 2;
+        HIPCHK(&c->err, hipMalloc((void**)&c->rz_frames, cap));
+        c->rz_frames_cap = cap;
+    }
+    return VH_OK;
+}
+
+// plan upload + the one resize launch, on the context's stream (ahead of the fork of vh_set_streams); c->rz_u8 then holds the
+// batch the forward reads.  Stage "resize" of vh_set_stage_timing brackets the launch.
+int enqueue_resize(vh_ctx* c, const FrameJob& j, int batch) {
+    auto tmark = [&]() -> int {
+        if (c->timing_stage != ST_RESIZE) return VH_OK;
+        if (c->tev_used == c->tev.size()) {
+            hipEvent_t e;
+            HIPCHK(&c->err, hipEventCreate(&e));
+            c->tev.push_back(e);
+        }
+        HIPCHK(&c->err, hipEventRecord(c->tev[c->tev_used++], c->stream));
+        return VH_OK;
+    };
+    int rc;
+    HIPCHK(&c->err, hipMemcpyAsync(c->rz_plan_dev, j.plan_host, j.words * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = tmark())) return rc;
+    HIPCHK(&c->err, launch_resize_u8(j.frames_dev, c->rz_plan_dev, batch, c->cfg.channels, c->cfg.image_size, j.max_tiles, c->rz_u8, c->stream));
+    return tmark();
+}
+
+// the bodies of vh_forward_device_async / vh_forward_device / vh_forward for either kind of input; `job`: the resize that
+// fills `in` (= c->rz_u8) first
+int forward_device_async(vh_ctx* c, ImgIn in, int batch, float* logits, int steps, const FrameJob* job = nullptr) {
     int rc = check_forward_args(c, in.p, batch, logits);
     if (rc) return rc;
     if (steps <= 0) return fail(&c->err, VH_ERR_INVALID, "steps must be positive");
@@ -951,6 +1041,7 @@ int forward_device_async(vh_ctx* c, ImgIn in, int batch, float* logits, int step
     };
     HIPCHK(&c->err, hipEventRecord(c->ev0, c->stream));
     if ((rc = step_mark())) return rc;
+    if (job && (rc = enqueue_resize(c, *job, batch))) return rc;
     for (int i = 0; i < steps; ++i) {
         if ((rc = run_step(c, in, batch, logits))) return rc;
         if ((rc = step_mark())) return rc;
@@ -960,9 +1051,9 @@ int forward_device_async(vh_ctx* c, ImgIn in, int batch, float* logits, int step
     return VH_OK;
 }
 
-int forward_device(vh_ctx* c, ImgIn in, int batch, float* logits) {
+int forward_device(vh_ctx* c, ImgIn in, int batch, float* logits, const FrameJob* job = nullptr) {
     const auto t0 = std::chrono::high_resolution_clock::now();
-    int rc = forward_device_async(c, in, batch, logits, 1);
+    int rc = forward_device_async(c, in, batch, logits, 1, job);
     if (rc) return rc;
     rc = vh_synchronize(c);
     if (rc) return rc;
@@ -970,23 +1061,24 @@ int forward_device(vh_ctx* c, ImgIn in, int batch, float* logits) {
     return VH_OK;
 }
 
-int forward_host(vh_ctx* c, ImgIn in_host, int batch, float* logits_host) {
+// `job`: in_host holds `frame_bytes` of frames, staged in c->rz_frames (= job->frames_dev) and resized into c->rz_u8
+int forward_host(vh_ctx* c, ImgIn in_host, int batch, float* logits_host, const FrameJob* job = nullptr, size_t frame_bytes = 0) {
     int rc = check_forward_args(c, in_host.p, batch, logits_host);
     if (rc) return rc;
     const vh_config& f = c->cfg;
     // same timing window as the reference: H2D + device work + blocking D2H (netFPGA.cpp:262-284)
     const auto t0 = std::chrono::high_resolution_clock::now();
     HIPCHK(&c->err, hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)batch * f.image_size * f.image_size * f.channels * in_host.elem();
-    const ImgIn staged{c->in_dev, in_host.u8};
-    HIPCHK(&c->err, hipMemcpyAsync(c->in_dev, in_host.p, in_bytes, hipMemcpyHostToDevice, c->stream));
-    rc = forward_device_async(c, staged, batch, c->logits_dev, 1);
+    const size_t in_bytes = job ? frame_bytes : (size_t)batch * f.image_size * f.image_size * f.channels * in_host.elem();
+    const ImgIn staged = job ? ImgIn{c->rz_u8, true} : ImgIn{c->in_dev, in_host.u8};
+    HIPCHK(&c->err, hipMemcpyAsync(job ? (void*)c->rz_frames : (void*)c->in_dev, in_host.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    rc = forward_device_async(c, staged, batch, c->logits_dev, 1, job);
     if (rc) return rc;
     HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
     if (c->guard_auto && guard_exceeded(c)) {
         // this (synchronous) forward itself ran folded on rows beyond the guard: run it again, now with the stand-alone LayerNorm
-        rc = forward_device_async(c, staged, batch, c->logits_dev, 1);   // (its run_step polls the guard and switches)
+        rc = forward_device_async(c, staged, batch, c->logits_dev, 1);   // (its run_step polls the guard and switches; resized frames are still in place)
         if (rc) return rc;
         HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(&c->err, hipStreamSynchronize(c->stream));
@@ -1220,6 +1312,10 @@ int vh_destroy(vh_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     drop_graphs(c);
     if (c->guard_host) hipHostFree(c->guard_host);
+    if (c->rz_plan_host) hipHostFree(c->rz_plan_host);
+    if (c->rz_plan_dev) hipFree(c->rz_plan_dev);
+    if (c->rz_frames) hipFree(c->rz_frames);
+    if (c->rz_u8) hipFree(c->rz_u8);
     if (c->arena) hipFree(c->arena);
     if (c->w16) hipFree(c->w16);
     if (c->blob) hipFree(c->blob);
@@ -1508,6 +1604,37 @@ int vh_forward(vh_ctx* c, const float* in_host, int batch, float* logits_host) {
 
 int vh_forward_u8(vh_ctx* c, const uint8_t* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host, true}, batch, logits_host); }
 
+// 8-bit frames: check + plan on the host (nothing enqueued on a refusal), then resize -> u8 forward on the context's stream
+int vh_forward_device_frames_u8(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame* desc, int batch, float* logits_dev) {
+    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan(c, desc, batch, nbytes, ((uintptr_t)frames_dev & 3) == 0, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles};
+    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+}
+
+int vh_forward_frames_u8(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch, float* logits_host) {
+    int rc = check_forward_args(c, frames_host, batch, logits_host);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan(c, desc, batch, nbytes, true, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles};
+    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+}
+
+int vh_resize_table(int n_in, double lo, double hi, int n_out, int32_t* first, int32_t* count, float* weights, int max_taps) {
+    if (resize_axis_table(n_in, lo, hi, n_out, first, count, weights, max_taps))
+        return fail(nullptr, VH_ERR_INVALID, "resize table: bad argument, box outside 0..n_in or empty, scale > %d, or more than max_taps taps", kResizeMaxScale);
+    return VH_OK;
+}
+
 // Input normalisation of the 8-bit entry points.  The constants travel to the im2col kernel as launch arguments, which a captured
 // graph holds by value: like a weight load, a change waits for the stream and drops the cached graphs.
 int vh_set_input_norm(vh_ctx* c, const float* scale, const float* shift) {
@@ -1563,21 +1690,21 @@ const char* vh_stage_name(int i) { return (i >= 0 && i < ST_COUNT) ? kStageNames
 int vh_profile_forward(vh_ctx* c, const float* in, int batch, float* logits, double* stage_ms, int n_slots, int* n_written) {
     int rc = check_forward_args(c, in, batch, logits);
     if (rc) return rc;
-    if (!stage_ms || n_slots < 2 * ST_COUNT) return fail(&c->err, VH_ERR_INVALID, "need %d stage slots (ms then launch counts)", 2 * ST_COUNT);
+    if (!stage_ms || n_slots < 2 * kProfiledStages) return fail(&c->err, VH_ERR_INVALID, "need %d stage slots (ms then launch counts)", 2 * kProfiledStages);
     HIPCHK(&c->err, hipSetDevice(c->device));
     std::vector<std::pair<int, hipEvent_t>> ev;
     rc = enqueue_forward(c, ImgIn{in, false}, batch, logits, &ev, c->stream, 0);
     if (!rc) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) rc = fail(&c->err, VH_ERR_HIP, "sync: %s", hipGetErrorString(e)); }
-    for (int i = 0; i < 2 * ST_COUNT; ++i) stage_ms[i] = 0.0;
+    for (int i = 0; i < 2 * kProfiledStages; ++i) stage_ms[i] = 0.0;
     if (!rc)
         for (size_t i = 1; i < ev.size(); ++i) {
             float t = 0.f;
             hipEventElapsedTime(&t, ev[i - 1].second, ev[i].second);
             stage_ms[ev[i].first] += t;
-            stage_ms[ST_COUNT + ev[i].first] += 1.0;
+            stage_ms[kProfiledStages + ev[i].first] += 1.0;
         }
     for (auto& p : ev) hipEventDestroy(p.second);
-    if (n_written) *n_written = ST_COUNT;
+    if (n_written) *n_written = kProfiledStages;
     return rc;
 }
 
@@ -1598,6 +1725,7 @@ int vh_ring_destroy(vh_ctx* c) {
     for (auto& s : c->ring) {
         if (s.h_in) hipHostFree(s.h_in);
         if (s.h_out) hipHostFree(s.h_out);
+        if (s.h_plan) hipHostFree(s.h_plan);
         if (s.d_in) hipFree(s.d_in);
         if (s.d_out) hipFree(s.d_out);
         if (s.in_done) hipEventDestroy(s.in_done);
@@ -1609,18 +1737,27 @@ int vh_ring_destroy(vh_ctx* c) {
     if (c->copy_out) hipStreamDestroy(c->copy_out);
     c->copy_in = c->copy_out = nullptr;
     c->ring_batch = c->ring_wr = c->ring_rd = c->ring_used = 0;
-    c->ring_u8 = false;
+    c->ring_kind = vh_ctx::RING_F32;
+    c->ring_slot_bytes = 0;
     return VH_OK;
 }
 
-static int ring_create(vh_ctx* c, int slots, int batch_per_slot, bool u8) {
+static const char* ring_kind_name(vh_ctx::RingKind k) { return k == vh_ctx::RING_FRAMES ? "8-bit frames" : k == vh_ctx::RING_U8 ? "8-bit images" : "fp32 images"; }
+
+static int ring_create(vh_ctx* c, int slots, int batch_per_slot, vh_ctx::RingKind kind, size_t slot_bytes = 0) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (slots < 1 || slots > 64) return fail(&c->err, VH_ERR_INVALID, "slots must be 1..64");
     if (batch_per_slot < 1 || batch_per_slot > c->cfg.max_batch)
         return fail(&c->err, VH_ERR_INVALID, "batch_per_slot %d outside 1..max_batch=%d", batch_per_slot, c->cfg.max_batch);
+    const bool frames = kind == vh_ctx::RING_FRAMES;
+    if (frames && slot_bytes < 1) return fail(&c->err, VH_ERR_INVALID, "slot_bytes must be positive");
     vh_ring_destroy(c);
     HIPCHK(&c->err, hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)batch_per_slot * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (u8 ? 1 : 4);
+    const size_t in_bytes = frames ? slot_bytes : (size_t)batch_per_slot * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (kind == vh_ctx::RING_U8 ? 1 : 4);
+    // frames: the resized-image buffer and a first plan buffer now, and per slot room for a plan of two tables of ~8 taps
+    const size_t plan_words = (size_t)batch_per_slot * kResizeFrameWords + 2 * (size_t)c->cfg.image_size * 10;
+    if (frames)
+        if (int rc = frames_reserve(c, plan_words, false, 0)) return rc;
     const size_t out_bytes = (size_t)batch_per_slot * c->cfg.classes * 4;
     HIPCHK(&c->err, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
     HIPCHK(&c->err, hipStreamCreateWithFlags(&c->copy_out, hipStreamNonBlocking));
@@ -1630,6 +1767,10 @@ static int ring_create(vh_ctx* c, int slots, int batch_per_slot, bool u8) {
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_out, out_bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc((void**)&s.d_in, in_bytes);
         if (e == hipSuccess) e = hipMalloc((void**)&s.d_out, out_bytes);
+        if (e == hipSuccess && frames) {
+            e = hipHostMalloc((void**)&s.h_plan, plan_words * 4, hipHostMallocDefault);
+            if (e == hipSuccess) s.plan_cap = plan_words;
+        }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.in_done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.fwd_done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.out_done, hipEventDisableTiming);
@@ -1639,12 +1780,16 @@ static int ring_create(vh_ctx* c, int slots, int batch_per_slot, bool u8) {
         }
     }
     c->ring_batch = batch_per_slot;
-    c->ring_u8 = u8;
+    c->ring_kind = kind;
+    c->ring_slot_bytes = frames ? slot_bytes : 0;
     return VH_OK;
 }
 
-int vh_ring_create(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, false); }
-int vh_ring_create_u8(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, true); }
+int vh_ring_create(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, vh_ctx::RING_F32); }
+int vh_ring_create_u8(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, vh_ctx::RING_U8); }
+int vh_ring_create_frames(vh_ctx* c, int slots, int batch_per_slot, size_t slot_bytes) {
+    return ring_create(c, slots, batch_per_slot, vh_ctx::RING_FRAMES, slot_bytes);
+}
 
 int vh_ring_free_slots(const vh_ctx* c, int* n) {
     if (!c || !n) return fail(nullptr, VH_ERR_INVALID, "null argument");
@@ -1652,34 +1797,63 @@ int vh_ring_free_slots(const vh_ctx* c, int* n) {
     return VH_OK;
 }
 
-static int ring_input(vh_ctx* c, void** pinned_in, bool u8) {
+static int ring_input(vh_ctx* c, void** pinned_in, vh_ctx::RingKind kind) {
     if (!c || !pinned_in) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
     if (c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "no ring: call vh_ring_create first");
-    if (c->ring_u8 != u8) return fail(&c->err, VH_ERR_STATE, "this ring stages %s images", c->ring_u8 ? "8-bit" : "fp32");
+    if (c->ring_kind != kind) return fail(&c->err, VH_ERR_STATE, "this ring stages %s", ring_kind_name(c->ring_kind));
     if (c->ring_used == (int)c->ring.size()) return fail(&c->err, VH_ERR_RING_FULL, "ring full (PILA LLENA)");
     *pinned_in = c->ring[c->ring_wr].h_in;
     return VH_OK;
 }
 
-int vh_ring_input(vh_ctx* c, float** pinned_in) { return ring_input(c, (void**)pinned_in, false); }
-int vh_ring_input_u8(vh_ctx* c, uint8_t** pinned_in) { return ring_input(c, (void**)pinned_in, true); }
+int vh_ring_input(vh_ctx* c, float** pinned_in) { return ring_input(c, (void**)pinned_in, vh_ctx::RING_F32); }
+int vh_ring_input_u8(vh_ctx* c, uint8_t** pinned_in) { return ring_input(c, (void**)pinned_in, vh_ctx::RING_U8); }
+int vh_ring_input_frames(vh_ctx* c, uint8_t** pinned, size_t* capacity) {
+    if (!capacity) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
+    if (int rc = ring_input(c, (void**)pinned, vh_ctx::RING_FRAMES)) return rc;
+    *capacity = c->ring_slot_bytes;
+    return VH_OK;
+}
 
-static int ring_submit(vh_ctx* c, const void* in_host, int batch, bool u8) {
+// frames ring: in_host holds `frame_bytes` of frames described by `desc`; the slot's upload is followed by the resize into
+// c->rz_u8 on the context's stream (forwards are ordered on that stream, so one resized buffer serves every slot)
+static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const vh_frame* desc = nullptr) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "no ring: call vh_ring_create first");
-    if (c->ring_u8 != u8) return fail(&c->err, VH_ERR_STATE, "this ring stages %s images", c->ring_u8 ? "8-bit" : "fp32");
+    if (c->ring_kind != kind) return fail(&c->err, VH_ERR_STATE, "this ring stages %s", ring_kind_name(c->ring_kind));
     if (!c->weights_ready) return fail(&c->err, VH_ERR_STATE, "submit before weights were loaded");
     if (batch < 1 || batch > c->ring_batch) return fail(&c->err, VH_ERR_INVALID, "batch %d outside 1..%d", batch, c->ring_batch);
     if (c->ring_used == (int)c->ring.size()) return fail(&c->err, VH_ERR_RING_FULL, "ring full (PILA LLENA)");
+    const bool frames = kind == vh_ctx::RING_FRAMES;
+    int rc, max_tiles = 0;
+    if (frames) {   // every check, and the plan, before anything is enqueued or the slot is touched
+        if (frame_bytes < 1 || frame_bytes > c->ring_slot_bytes) return fail(&c->err, VH_ERR_INVALID, "nbytes %zu outside 1..slot_bytes=%zu", frame_bytes, c->ring_slot_bytes);
+        if ((rc = frames_plan(c, desc, batch, frame_bytes, true, &max_tiles))) return rc;
+    }
     HIPCHK(&c->err, hipSetDevice(c->device));
     vh_ctx::RingSlot& s = c->ring[c->ring_wr];
-    const size_t in_bytes = (size_t)batch * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (u8 ? 1 : 4);
+    const size_t in_bytes = frames ? frame_bytes : (size_t)batch * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (kind == vh_ctx::RING_U8 ? 1 : 4);
+    if (frames) {
+        const size_t words = c->rz_words.size();
+        if (words > s.plan_cap) {   // a free slot: its last upload ran before its batch was collected
+            if (s.h_plan) hipHostFree(s.h_plan);
+            s.h_plan = nullptr; s.plan_cap = 0;
+            HIPCHK(&c->err, hipHostMalloc((void**)&s.h_plan, words * 8, hipHostMallocDefault));
+            s.plan_cap = words * 2;
+        }
+        if ((rc = frames_reserve(c, words, false, 0))) return rc;
+        memcpy(s.h_plan, c->rz_words.data(), words * 4);
+    }
     if (in_host && in_host != s.h_in) memcpy(s.h_in, in_host, in_bytes);  // NULL / the slot's own buffer: already filled in place
     s.batch = batch;
     HIPCHK(&c->err, hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, c->copy_in));
     HIPCHK(&c->err, hipEventRecord(s.in_done, c->copy_in));
     HIPCHK(&c->err, hipStreamWaitEvent(c->stream, s.in_done, 0));
-    int rc = run_step(c, ImgIn{s.d_in, u8}, batch, s.d_out);
+    if (frames) {
+        const FrameJob job{(const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles};
+        if ((rc = enqueue_resize(c, job, batch))) return rc;
+    }
+    rc = run_step(c, frames ? ImgIn{c->rz_u8, true} : ImgIn{s.d_in, kind == vh_ctx::RING_U8}, batch, s.d_out);
     if (rc) return rc;
     HIPCHK(&c->err, hipEventRecord(s.fwd_done, c->stream));
     HIPCHK(&c->err, hipStreamWaitEvent(c->copy_out, s.fwd_done, 0));
@@ -1690,8 +1864,11 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, bool u8) {
     return VH_OK;
 }
 
-int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) { return ring_submit(c, in_host, batch, false); }
-int vh_ring_submit_u8(vh_ctx* c, const uint8_t* in_host, int batch) { return ring_submit(c, in_host, batch, true); }
+int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_F32); }
+int vh_ring_submit_u8(vh_ctx* c, const uint8_t* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_U8); }
+int vh_ring_submit_frames(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc);
+}
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
     if (!c || !logits_host) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
@@ -2058,6 +2235,24 @@ int vh_op_im2col_u8(const uint8_t* in, int batch, int image, int patch, int chan
         if (!std::isfinite(scale_host[i]) || !std::isfinite(shift_host[i])) return fail(nullptr, VH_ERR_INVALID, "im2col_u8: scale / shift of channel %d is not finite", i);
     OPCHK(launch_im2col_u8(in, batch, image, patch, channels, kpad, scale_host, shift_host, out16, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+
+int vh_op_resize_u8(const uint8_t* frames, size_t nbytes, const vh_frame* desc, int batch, int channels, int out_size, uint8_t* out,
+                    void* stream) {
+    if (!frames || !desc || !out) return fail(nullptr, VH_ERR_INVALID, "null buffer");
+    std::vector<uint32_t> words;
+    int max_tiles = 0;
+    if (const char* why = resize_plan_build(desc, batch, channels, out_size, nbytes, ((uintptr_t)frames & 3) == 0, &words, &max_tiles))
+        return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    uint32_t* plan = nullptr;
+    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
+    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = launch_resize_u8(frames, plan, batch, channels, out_size, max_tiles, out, (hipStream_t)stream);
+    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(plan);
+    OPCHK(e);
+    OPCHK(es);
     return VH_OK;
 }
 

@@ -23,6 +23,10 @@ ACT_IDENTITY, ACT_RELU2, ACT_RELU, ACT_HARDTANH, ACT_GELU = range(5)
 
 STAGES = ["im2col", "patch_gemm", "cls_rows", "layernorm", "qkv_gemm", "attention", "proj_gemm",
           "fc1_gemm", "fc2_gemm", "final_layernorm", "head_gemm", "ln_stats", "pre_layernorm"]
+# the stages of a forward (what profile_forward reports), and behind them the one launch that is no part of it: the resize of the
+# frames entry points (vh_stage_name(len(STAGES)); set_stage_timing takes it like any other)
+STAGE_RESIZE = "resize"
+TIMED_STAGES = STAGES + [STAGE_RESIZE]
 
 
 class VhError(RuntimeError):
@@ -36,6 +40,12 @@ class Config(C.Structure):
                 ("dim", C.c_int32), ("heads", C.c_int32), ("mlp_dim", C.c_int32),
                 ("layers", C.c_int32), ("classes", C.c_int32), ("dtype", C.c_int32),
                 ("max_batch", C.c_int32), ("ln_eps", C.c_float), ("flags", C.c_int32)]
+
+
+class Frame(C.Structure):
+    """vh_frame: one 8-bit interleaved frame inside the buffer of a call, and the box to resample to image_size^2."""
+    _fields_ = [("offset", C.c_uint64), ("height", C.c_int32), ("width", C.c_int32), ("row_stride", C.c_int32),
+                ("box", C.c_float * 4)]
 
 
 # every exported symbol of include/vithip.h: name -> (restype, argtypes)
@@ -71,6 +81,9 @@ SYMBOLS = {
     "vh_forward_u8": (_i, [_vp, _vp, _i, _vp]),
     "vh_forward_device_u8": (_i, [_vp, _vp, _i, _vp]),
     "vh_forward_device_u8_async": (_i, [_vp, _vp, _i, _vp, _i]),
+    "vh_resize_table": (_i, [_i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _i]),
+    "vh_forward_frames_u8": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_u8": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_fill_input_seeded": (_i, [_vp, _u64, _i, _vp]),
     "vh_last_forward_us": (_i, [_vp, C.POINTER(_i64)]),
     "vh_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
@@ -96,6 +109,9 @@ SYMBOLS = {
     "vh_ring_create_u8": (_i, [_vp, _i, _i]),
     "vh_ring_input_u8": (_i, [_vp, C.POINTER(C.POINTER(C.c_uint8))]),
     "vh_ring_submit_u8": (_i, [_vp, _vp, _i]),
+    "vh_ring_create_frames": (_i, [_vp, _i, _i, _sz]),
+    "vh_ring_input_frames": (_i, [_vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(_sz)]),
+    "vh_ring_submit_frames": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_set_graph": (_i, [_vp, _i]),
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
@@ -125,6 +141,7 @@ SYMBOLS = {
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "vh_op_resize_u8": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -256,6 +273,50 @@ def input_norm_from_mean_std(mean, std):
     if mean.shape != std.shape or mean.ndim != 1 or not (std != 0).all():
         raise ValueError("input_norm_from_mean_std: mean and std are per-channel vectors of one length, std non-zero")
     return (1.0 / (255.0 * std)).astype(np.float32), (-mean / std).astype(np.float32)
+
+
+def center_crop_box(h, w, fraction=0.875):
+    """The centred square of side fraction * min(h, w) as a box (x0, y0, x1, y1): with the default fraction, what torchvision's
+    Resize(256) + CenterCrop(224) keeps of a frame."""
+    if h < 1 or w < 1 or not 0.0 < fraction <= 1.0:
+        raise ValueError("center_crop_box: h, w >= 1 and 0 < fraction <= 1")
+    side = fraction * min(h, w)
+    x0, y0 = (w - side) / 2.0, (h - side) / 2.0
+    return (x0, y0, x0 + side, y0 + side)
+
+
+def resize_table(n_in, lo, hi, n_out, max_taps=65):
+    """vh_resize_table: (first[n_out] int32, count[n_out] int32, weights[n_out, max_taps] float32) of one axis."""
+    first, count = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    weights = np.zeros((n_out, max_taps), np.float32)
+    _check(lib().vh_resize_table(n_in, lo, hi, n_out, first.ctypes.data, count.ctypes.data, weights.ctypes.data, max_taps))
+    return first, count, weights
+
+
+def pack_frames(frames, boxes=None, channels=None):
+    """A list of HWC (or HW) uint8 arrays -> (one uint8 buffer holding them back to back, the (Frame * n) descriptors).
+    boxes: one (x0, y0, x1, y1) per frame, None = the whole frame."""
+    frames = [np.asarray(f) for f in frames]
+    if boxes is None:
+        boxes = [None] * len(frames)
+    if not frames or len(boxes) != len(frames):
+        raise ValueError("pack_frames: one box (or None) per frame, at least one frame")
+    desc = (Frame * len(frames))()
+    parts, off = [], 0
+    for i, (f, box) in enumerate(zip(frames, boxes)):
+        if f.dtype != np.uint8 or f.ndim not in (2, 3):
+            raise TypeError(f"pack_frames: frame {i} is not an HWC uint8 array")
+        if f.ndim == 2:
+            f = f[:, :, None]
+        if channels is not None and f.shape[2] != channels:
+            raise ValueError(f"pack_frames: frame {i} has {f.shape[2]} channels, the model takes {channels}")
+        f = np.ascontiguousarray(f)
+        h, w, ch = f.shape
+        desc[i].offset, desc[i].height, desc[i].width, desc[i].row_stride = off, h, w, w * ch
+        desc[i].box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(v) for v in box)
+        parts.append(f.reshape(-1))
+        off += f.size
+    return np.concatenate(parts), desc
 
 
 def make_config(cfg, dtype=DTYPE_BF16, max_batch=1, ln_eps=1e-6, flags=0):
@@ -514,6 +575,22 @@ class VitContext:
     def forward_device_u8_async(self, in_ptr, batch, out_ptr, steps=1):
         _check(lib().vh_forward_device_u8_async(self.h, in_ptr, batch, out_ptr, steps), self.h)
 
+    # ---- 8-bit frames of any size: antialiased resize + crop on the GPU, then forward_u8 of the result ----
+    def forward_frames(self, frames, boxes=None):
+        """frames: a list of HWC uint8 arrays, any sizes; boxes: one (x0, y0, x1, y1) per frame in source pixels (None = the
+        whole frame).  Returns [len(frames), classes] fp32 logits: the bits forward_u8 gives for op_resize_u8's output."""
+        buf, desc = pack_frames(frames, boxes, self.cfg["channels"])
+        return self.forward_frames_packed(buf, desc)
+
+    def forward_frames_packed(self, buf, desc):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
+        _check(lib().vh_forward_frames_u8(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
+        return out
+
+    def forward_device_frames_u8(self, frames_ptr, nbytes, desc, out_ptr):
+        _check(lib().vh_forward_device_frames_u8(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
 
@@ -560,6 +637,29 @@ class VitContext:
         images = np.ascontiguousarray(images)
         _check(lib().vh_ring_submit_u8(self.h, images.ctypes.data, images.shape[0]), self.h)
 
+    def ring_create_frames(self, slots, batch_per_slot, slot_bytes):
+        """A ring whose slots stage up to slot_bytes of 8-bit frames each (ring_input_frames / ring_submit_frames)."""
+        _check(lib().vh_ring_create_frames(self.h, slots, batch_per_slot, slot_bytes), self.h)
+        self._ring_batch = batch_per_slot
+
+    def ring_input_frames(self):
+        """numpy uint8 view (all slot_bytes) of the pinned staging buffer the next ring_submit_frames will upload."""
+        p, cap = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+        _check(lib().vh_ring_input_frames(self.h, C.byref(p), C.byref(cap)), self.h)
+        return np.ctypeslib.as_array(p, shape=(cap.value,))
+
+    def ring_submit_frames(self, frames, boxes=None):
+        buf, desc = pack_frames(frames, boxes, self.cfg["channels"])
+        self.ring_submit_frames_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of frames that desc describes."""
+        ptr = None
+        if buf is not None:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            ptr = buf.ctypes.data
+        _check(lib().vh_ring_submit_frames(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+
     def ring_free_slots(self):
         n = C.c_int(0)
         _check(lib().vh_ring_free_slots(self.h, C.byref(n)), self.h)
@@ -602,7 +702,7 @@ class VitContext:
         return n.value
 
     def set_stage_timing(self, stage_name):
-        _check(lib().vh_set_stage_timing(self.h, STAGES.index(stage_name) if stage_name else -1), self.h)
+        _check(lib().vh_set_stage_timing(self.h, TIMED_STAGES.index(stage_name) if stage_name else -1), self.h)
 
     def get_stage_timing(self):
         avg, mn, n = C.c_double(0), C.c_double(0), C.c_int(0)
@@ -897,6 +997,12 @@ def op_im2col_u8(in_ptr, batch, image, patch, channels, kpad, scale, shift, out_
             raise ValueError(f"op_im2col_u8: expected {channels} values per array, got {a.size}")
     _check(lib().vh_op_im2col_u8(in_ptr, batch, image, patch, channels, kpad, None if sc is None else sc.ctypes.data,
                                  None if sh is None else sh.ctypes.data, out_ptr, dtype, None))
+
+
+def op_resize_u8(frames_ptr, nbytes, desc, channels, out_size, out_ptr):
+    """The resize of the frames entry points on its own: the frames at frames_ptr (device, any alignment) described by the
+    (Frame * n) array desc -> [n, out_size, out_size, channels] bytes at out_ptr."""
+    _check(lib().vh_op_resize_u8(frames_ptr, nbytes, C.addressof(desc), len(desc), channels, out_size, out_ptr, None))
 
 
 def op_cast(in_ptr, out_ptr, n, dtype):
