@@ -264,6 +264,64 @@ typedef struct vh_frame {
 int vh_resize_table(int n_in, double lo, double hi, int n_out, int32_t* first, int32_t* count, float* weights, int max_taps);
 int vh_forward_frames_u8(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch, float* logits_host);
 int vh_forward_device_frames_u8(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame* desc, int batch, float* logits_dev);
+/* ---- NV12 frames: colour conversion fused into the GPU resize ----------------------------------------------------------
+ * What a hardware video decoder (VCN through rocDecode or VA-API) and most camera stacks emit: 12 bits per pixel in two
+ * planes.  An NV12 FRAME is
+ *       a Y plane    height x width bytes, rows y_stride bytes apart, at y_offset, and
+ *       a UV plane   height/2 rows of width/2 interleaved (U, V) byte pairs, rows uv_stride bytes apart, at uv_offset,
+ * both offsets relative to the buffer of the call.  width and height are even and within 2..8192; y_stride >= width and
+ * uv_stride >= width; the last byte of each plane lies within nbytes; the planes need not be adjacent or aligned.  `box`
+ * means what it means in vh_frame: LUMA pixel coordinates, fractional allowed, 0 <= x0 < x1 <= width and the same in y.  The
+ * context must have channels == 3 (else VH_ERR_INVALID).
+ * RESAMPLING.  Each plane is resampled to S x S under the axis contract of "8-bit frames" (the same doubles, one rounding to
+ * fp32 per weight; vh_resize_table returns the luma tables): Y with n = width (height) and the box as given; UV as a
+ * 2-channel image of width/2 x height/2 whose box per axis is (lo / 2 + delta, hi / 2 + delta).  VH_CHROMA_CENTER (JPEG,
+ * MPEG-1): delta = 0 on both axes.  VH_CHROMA_LEFT (MPEG-2, H.264, HEVC default): delta = 0.25 horizontally, 0 vertically; the
+ * chroma box may then overhang the last chroma column by up to 0.25, which the tap clamp [max(.., 0), min(.., n)) and the
+ * renormalisation of the axis contract take (only this internal table relaxes hi <= n, by that quarter sample).  Each plane
+ * runs the horizontal pass, then the vertical pass, each an fp32 fmaf chain in ascending tap order from 0 with nothing
+ * rounded in between.
+ * CONVERSION.  With the UNROUNDED fp32 y, u, v of an output pixel and a row-major 3 x 4 fp32 matrix m,
+ *       out[k] = fmaf(m[4k], y, fmaf(m[4k+1], u, fmaf(m[4k+2], v, m[4k+3]))),   k = 0, 1, 2
+ * and the byte is rintf(min(max(out[k], 0), 255)): ONE rounding for resize and conversion together.  From there on the
+ * forward IS vh_forward_u8 of that S x S x 3 byte image: vh_set_input_norm applies unchanged and the logits are
+ * BIT-IDENTICAL to feeding vh_op_resize_nv12's output to the u8 entry point.
+ *   vh_yuv_matrix       host only, no device.  standard VH_YUV_BT601 (Kr 0.299, Kb 0.114), VH_YUV_BT709 (0.2126, 0.0722) or
+ *                       VH_YUV_BT2020 (0.2627, 0.0593); full_range 0 or 1; anything else is VH_ERR_INVALID.  Evaluated in
+ *                       double, no contraction, in exactly this order, each entry then rounded once to fp32:
+ *                           kg = 1.0 - kr - kb
+ *                           sy = 255.0 / 219.0, sc = 255.0 / 224.0, oy = 16.0     (full range: sy = sc = 1.0, oy = 0.0)
+ *                           rv = 2.0 * (1.0 - kr) * sc
+ *                           bu = 2.0 * (1.0 - kb) * sc
+ *                           gu = -(2.0 * kb * (1.0 - kb) / kg) * sc
+ *                           gv = -(2.0 * kr * (1.0 - kr) / kg) * sc
+ *                           yo = -(sy * oy)
+ *                           m  = { sy, 0.0, rv, yo - 128.0 * rv,
+ *                                  sy, gu,  gv, yo - 128.0 * gu - 128.0 * gv,
+ *                                  sy, bu, 0.0, yo - 128.0 * bu }                  (rows R, G, B; columns y, u, v, 1)
+ *   vh_set_frame_colour m: 12 floats, all finite (else VH_ERR_INVALID), any matrix (not only vh_yuv_matrix's); chroma_site
+ *                       VH_CHROMA_CENTER or VH_CHROMA_LEFT (else VH_ERR_INVALID).  m = NULL restores the default: BT.709
+ *                       limited range with left siting (chroma_site is ignored then), what an HD video decoder emits.
+ *                       Per-context state.  The resize runs outside the captured graph, so no graph is dropped.
+ *   vh_get_frame_colour the matrix and the siting in force (either pointer may be NULL).
+ *   vh_forward_frames_nv12, vh_forward_device_frames_nv12: vh_forward_frames_u8 / vh_forward_device_frames_u8 for NV12
+ *                       frames.  Every descriptor and argument is checked before anything is enqueued.  Stage "resize" of
+ *                       vh_set_stage_timing times this launch too. */
+#define VH_CHROMA_CENTER 0
+#define VH_CHROMA_LEFT 1
+#define VH_YUV_BT601 0
+#define VH_YUV_BT709 1
+#define VH_YUV_BT2020 2
+typedef struct vh_frame_nv12 {
+    uint64_t y_offset, uv_offset;
+    int32_t height, width, y_stride, uv_stride;
+    float box[4];
+} vh_frame_nv12;
+int vh_yuv_matrix(int standard, int full_range, float m[12]);
+int vh_set_frame_colour(vh_ctx* ctx, const float m[12], int chroma_site);
+int vh_get_frame_colour(const vh_ctx* ctx, float m[12], int* chroma_site);
+int vh_forward_frames_nv12(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_host);
+int vh_forward_device_frames_nv12(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev);
 /* uniform[-1,1) synthetic images written straight into HBM (value range of the reference,
  * def/defines.h:11-12) */
 int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_dev);
@@ -303,6 +361,11 @@ int vh_ring_submit_u8(vh_ctx* ctx, const uint8_t* in_nhwc_host, int batch);
 int vh_ring_create_frames(vh_ctx* ctx, int slots, int batch_per_slot, size_t slot_bytes);
 int vh_ring_input_frames(vh_ctx* ctx, uint8_t** pinned, size_t* capacity);
 int vh_ring_submit_frames(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch);
+/* NV12 frames ("NV12 frames" above) on the SAME frames ring: a slot is raw bytes, so one ring takes vh_ring_submit_frames and
+ * vh_ring_submit_frames_nv12 interleaved; vh_ring_input_frames and vh_ring_collect are unchanged.  The context must have
+ * channels == 3.  Checked and copied before anything is enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on
+ * the other two kinds of ring.  A collected batch has the bits vh_forward_frames_nv12 returns. */
+int vh_ring_submit_frames_nv12(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -486,6 +549,12 @@ int vh_op_im2col_u8(const uint8_t* in_nhwc_dev, int batch, int image, int patch,
  * 1..4096.  Allocates and frees its table buffer: a test and measurement tap, not a hot path. */
 int vh_op_resize_u8(const uint8_t* frames_dev, size_t nbytes, const vh_frame* desc_host, int batch, int channels,
                     int out_size, uint8_t* out_u8_dev, void* stream);
+/* The resize + colour conversion of the NV12 entry points on its own ("NV12 frames"): frames_dev (any alignment, any
+ * offsets) -> out_u8_dev [batch][out_size][out_size][3] bytes.  desc_host: HOST array [batch]; m12_host: HOST row-major
+ * 3 x 4 matrix, all finite; chroma_site VH_CHROMA_*; out_size 1..4096.  Every argument and descriptor is checked before a
+ * device is touched.  Allocates and frees its table buffer: a test and measurement tap, not a hot path. */
+int vh_op_resize_nv12(const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc_host, int batch, int out_size,
+                      const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,

@@ -11,6 +11,13 @@ slots (pinned host memory -> logits in host memory), interleaved `passes` times,
 The images of (1) are the centre crops of the frames of (2), so those two rings compute the same logits, which is checked.
 Then the resize launch of (2) and (3) alone, hip events around it (vh_set_stage_timing("resize")), two interleaved passes: us per
 launch and the GB/s of source bytes inside the boxes.  Written to <out>/frames_host_path.txt and .json.
+
+  python tools/frames_bench.py --nv12 [--out profiles] [--steps 30] [--passes 3]
+
+NV12 passes instead, ViT-B/16 bf16, in ONE process: the frames ring fed RGB frames against the frames ring fed the
+NV12 frames of the same pictures (nv12_ref.rgb_to_nv12, BT.709 limited range), at 360 x 480 (batch 512) and at 1080 x 1920 (batch
+64), 0.875 centre box, interleaved passes and medians as above; then the resize launch of each in us and GB/s of source bytes
+inside the boxes.  Written to <out>/nv12_host_path.txt and .json.
 """
 import argparse
 import json
@@ -96,6 +103,90 @@ class Side:
         self.ctx.close()
 
 
+class SideNV12(Side):
+    """One context with a frames ring fed NV12 frames: y [B, H, W] and uv [B, H/2, W/2, 2], each frame's planes back to back."""
+
+    def __init__(self, cfg, dname, batch, flags, eps, scale, shift, y, uv, box):
+        self.batch, self.frames = batch, True
+        self.ctx = vithip.VitContext(cfg, dtype=DT[dname], max_batch=batch, flags=flags, ln_eps=eps)
+        self.ctx.init_weights_seeded(0)
+        self.ctx.set_input_norm(scale, shift)
+        _, h, w = y.shape
+        per = h * w * 3 // 2
+        buf = np.empty((batch, per), np.uint8)
+        buf[:, :h * w] = y.reshape(batch, -1)
+        buf[:, h * w:] = uv.reshape(batch, -1)
+        self.nbytes = buf.nbytes
+        self.desc = (vithip.FrameNV12 * batch)()
+        for b in range(batch):
+            d = self.desc[b]
+            d.y_offset, d.uv_offset, d.height, d.width, d.y_stride, d.uv_stride = b * per, b * per + h * w, h, w, w, w
+            d.box[:] = box
+        self.box_bytes = batch * (box[2] - box[0]) * (box[3] - box[1]) * 1.5
+        self.ctx.ring_create_frames(SLOTS, batch, self.nbytes)
+        for _ in range(SLOTS):
+            self.ctx.ring_input_frames()[:self.nbytes] = buf.reshape(-1)
+            self.submit()
+        self.first = [self.ctx.ring_collect().copy() for _ in range(SLOTS)][0]
+
+    def submit(self):
+        self.ctx.ring_submit_frames_nv12_packed(None, self.nbytes, self.desc)
+
+
+def nv12_main(a):
+    import nv12_ref as N
+    lines, rows = [], []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    scale, shift = vithip.input_norm_from_mean_std(MEAN, STD)
+    title, key, cfg, dname, _, flags, eps = RUNS[0]
+    log(f"frames_bench --nv12: {title[:-5]}, frames rings of {SLOTS} slots, {a.steps} steps per pass, {a.passes} interleaved passes (RGB frames "
+        f"against the NV12 frames of the same pictures; 0.875 centre box); median pass [min .. max]; images/s")
+    for h, w, batch in ((360, 480, 512), (1080, 1920, 64)):
+        rng = np.random.default_rng(3)
+        small = rng.integers(0, 256, size=(batch, h // 8, w // 8, 3), dtype=np.uint8)
+        rgb = np.ascontiguousarray(np.repeat(np.repeat(small, 8, axis=1), 8, axis=2))     # pictures with structure: 8 x 8 blocks
+        rgb ^= rng.integers(0, 8, size=rgb.shape, dtype=np.uint8)                          # plus noise in the low bits
+        planes = [N.rgb_to_nv12(f) for f in rgb]
+        y, uv = np.stack([p[0] for p in planes]), np.stack([p[1] for p in planes])
+        box = vithip.center_crop_box(h, w)
+        common = (cfg, dname, batch, flags, eps, scale, shift)
+        A = Side(*common, frames=rgb, box=box)
+        B = SideNV12(*common, y=y, uv=uv, box=box)
+        diff = float(np.abs(A.first - B.first).max() / np.abs(A.first).max())
+        ra, rb = [], []
+        for _ in range(a.passes):
+            ra.append(A.ring_rate(a.steps)); rb.append(B.ring_rate(a.steps))
+        k = [A.resize_us(8), B.resize_us(8), A.resize_us(8), B.resize_us(8)]
+        r = dict(config=key, frame=[h, w], batch=batch, ring_rgb=mid(ra), ring_nv12=mid(rb),
+                 h2d_MB_per_step=dict(rgb=A.nbytes / 1e6, nv12=B.nbytes / 1e6), logits_rel_diff_rgb_vs_nv12=diff,
+                 resize_rgb_us_avg=[k[0][0], k[2][0]], resize_nv12_us_avg=[k[1][0], k[3][0]],
+                 resize_rgb_us_min=min(k[0][1], k[2][1]), resize_nv12_us_min=min(k[1][1], k[3][1]),
+                 box_MB=dict(rgb=A.box_bytes / 1e6, nv12=B.box_bytes / 1e6))
+        rows.append(r)
+        base = r["ring_rgb"][0]
+        log(f"{h}x{w}, batch {batch}: logits of the NV12 ring differ from the RGB ring's by {diff:.3e} of the largest logit (4:2:0 subsampling and "
+            f"the 8-bit round trip of the test pictures; not a parity figure)")
+        for name, kk, mb in (("frames ring, RGB  ", "ring_rgb", A.nbytes / 1e6), ("frames ring, NV12 ", "ring_nv12", B.nbytes / 1e6)):
+            m, lo, hi = r[kk]
+            log(f"    {name}: {m:9.0f} [{lo:9.0f} .. {hi:9.0f}] = {100 * m / base:6.2f} % of the RGB ring | upload {mb:7.1f} MB per step = "
+                f"{mb * 1e-3 * m / batch:5.1f} GB/s")
+        for name, avg, mn, mb in (("RGB ", r["resize_rgb_us_avg"], r["resize_rgb_us_min"], A.box_bytes / 1e6),
+                                  ("NV12", r["resize_nv12_us_avg"], r["resize_nv12_us_min"], B.box_bytes / 1e6)):
+            us = float(np.mean(avg))
+            log(f"    resize {name}: {us:8.1f} us per launch avg ({mn:.1f} min; passes {avg[0]:.1f} {avg[1]:.1f}) | "
+                f"{mb:.1f} MB inside the boxes = {mb * 1e-3 / (us * 1e-6):.0f} GB/s")
+        A.close(); B.close()
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "nv12_host_path.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+    with open(os.path.join(a.out, "nv12_host_path.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def mid(v):
     return float(np.median(v)), float(np.min(v)), float(np.max(v))
 
@@ -106,7 +197,10 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--only", default="")
+    ap.add_argument("--nv12", action="store_true", help="the NV12 passes (RGB frames ring against NV12 frames ring) instead")
     a = ap.parse_args()
+    if a.nv12:
+        return nv12_main(a)
     lines, rows = [], []
 
     def log(s):

@@ -28,8 +28,15 @@ namespace vh {
 // float64 transcription gives the same first / count and, after the one rounding, the same fp32 weights.
 #pragma clang fp contract(off)
 int resize_axis_table(int n_in, double lo, double hi, int n_out, int32_t* first, int32_t* count, float* weights, int max_taps) {
+    return resize_axis_table_over(n_in, lo, hi, 0.0, n_out, first, count, weights, max_taps);
+}
+
+// the same table with a box that may overhang the last sample by `over` (kernels_resize_nv12.hip: left-sited chroma, a quarter of
+// a sample); the tap clamp and the renormalisation below are what handles the overhang
+int resize_axis_table_over(int n_in, double lo, double hi, double over, int n_out, int32_t* first, int32_t* count, float* weights,
+                           int max_taps) {
     if (n_in < 1 || n_in > kResizeMaxSide || n_out < 1 || !first || !count || !weights || max_taps < 1) return 1;
-    if (!(lo >= 0.0 && lo < hi && hi <= (double)n_in)) return 1;   // written so that a NaN fails
+    if (!(lo >= 0.0 && lo < hi && hi <= (double)n_in + over)) return 1;   // written so that a NaN fails
     const double scale = (hi - lo) / (double)n_out;
     if (!(scale <= (double)kResizeMaxScale)) return 1;
     const double sup = scale > 1.0 ? scale : 1.0;

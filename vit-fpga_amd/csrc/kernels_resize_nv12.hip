@@ -1,0 +1,301 @@
+// kernels_resize_nv12.hip — NV12 video frames: antialiased resize + crop of both planes and the colour conversion in one launch,
+// in front of the u8 forward.
+//
+// CONTRACT (include/vithip.h, "NV12 frames").  The Y plane (height x width bytes) and the UV plane (height/2 rows of width/2
+// interleaved (U, V) pairs) are each resampled with the axis contract of the 8-bit frames (resize_axis_table: the same doubles,
+// one rounding to fp32): Y over the box as given, UV as a 2-channel image of width/2 x height/2 over (lo/2 + delta, hi/2 + delta),
+// delta = 0.25 horizontally for left-sited chroma and 0 otherwise.  Each plane runs the horizontal pass, then the vertical pass,
+// each an fp32 __builtin_fmaf chain in ascending tap order from 0, nothing rounded in between -- the arithmetic of
+// resize_u8_kernel.  The unrounded y, u, v of an output pixel then pass the 3 x 4 matrix m,
+//     out[k] = fmaf(m[4k], y, fmaf(m[4k+1], u, fmaf(m[4k+2], v, m[4k+3]))),
+// and the byte is rintf(min(max(out[k], 0), 255)): ONE rounding for resize and conversion together.
+//
+// KERNEL.  One launch for the whole batch, the structure of resize_u8_kernel: a 256-thread workgroup owns `band_rows` output rows x
+// `tile_cols` output columns of one frame.  It runs the horizontal pass of the luma rows AND of the chroma rows its band needs
+// into LDS as fp32 (UV [rows_c][cols][2] first, so that a pair is 8-byte aligned, then Y [rows_y][cols]), and after one barrier the
+// vertical pass of both planes out of LDS, the matrix, and three bytes per pixel.  The source is read from HBM about once; no fp32
+// and no YUV or RGB intermediate exists in HBM.  The host picks band_rows and tile_cols so that (rows_y + 2 rows_c) x cols floats
+// fit kResizeLdsFloats; the kernel recomputes both row ranges from the tables and does nothing if they would not fit the LDS or
+// either plane (they cannot, short of a corrupted table).  Loads: Y bytes; one 16-bit load per UV pair where uv_offset, uv_stride
+// and the base are even, two bytes otherwise.  Stores: bytes.  No atomics, no work queue, no allocation.
+#include <cmath>
+#include <cstring>
+
+#include "vh_kernels.h"
+
+namespace vh {
+
+// ---- host: descriptors + tables of one call --------------------------------------------------------------------------------
+// words = [batch x RzNv12][tables]; a table is first[S] | count[S] | weights[S][stride], as in kernels_resize.hip.  Frames that
+// share (length, lo, hi) on an axis share the table: a batch from one decoder builds four tables (luma x, luma y, chroma x,
+// chroma y).
+struct RzNv12 {
+    uint64_t y_off, uv_off;
+    int32_t h, w, y_stride, uv_stride;
+    int32_t xt, yt, cxt, cyt;      // word offsets of the tables: luma x, luma y, chroma x, chroma y
+    int32_t xs, ys, cxs, cys;      // their weight strides
+    int32_t band_rows, tile_cols;
+    int32_t uv16;                  // uv_offset, uv_stride and the base even: one 16-bit load per (U, V) pair
+    int32_t pad[5];
+};
+static_assert(sizeof(RzNv12) == 4 * kResizeNv12FrameWords, "RzNv12 layout");
+
+namespace {
+
+struct TableKey { int n; double lo, hi; int32_t at, stride; };
+struct BandKey { int32_t yt, cyt, band_rows, tile_cols; };
+
+// the most floats per output column any band of k rows keeps in LDS: luma rows + 2 x chroma rows
+int worst_cost(const int32_t* yf, const int32_t* yc, const int32_t* cf, const int32_t* cc, int S, int k) {
+    int worst = 0;
+    for (int r0 = 0; r0 < S; r0 += k) {
+        const int r1 = r0 + k < S ? r0 + k : S;
+        int ylo = yf[r0], yhi = yf[r0] + yc[r0], clo = cf[r0], chi = cf[r0] + cc[r0];
+        for (int r = r0 + 1; r < r1; ++r) {
+            if (yf[r] < ylo) ylo = yf[r];
+            if (yf[r] + yc[r] > yhi) yhi = yf[r] + yc[r];
+            if (cf[r] < clo) clo = cf[r];
+            if (cf[r] + cc[r] > chi) chi = cf[r] + cc[r];
+        }
+        const int cost = (yhi - ylo) + 2 * (chi - clo);
+        if (cost > worst) worst = cost;
+    }
+    return worst;
+}
+
+}  // namespace
+
+const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, size_t nbytes, bool base_aligned2, int chroma_site,
+                                   std::vector<uint32_t>* words, int* max_tiles) {
+    if (!desc || batch < 1 || S < 1 || S > 4096) return "resize_nv12: bad batch or output size";
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return "resize_nv12: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+    std::vector<TableKey> keys;
+    std::vector<BandKey> bands;
+    std::vector<int32_t> first(S), count(S);
+    std::vector<float> wts((size_t)S * kResizeMaxTaps);
+    words->assign((size_t)batch * kResizeNv12FrameWords, 0u);
+    *max_tiles = 1;
+    // the table of one axis: found among those built for this call, or built and appended.  `over`: how far the box may overhang
+    // the last sample (a quarter of a chroma sample with left siting; the tap clamp and the renormalisation take it)
+    auto axis = [&](int n, double lo, double hi, double over, TableKey* out) -> const char* {
+        for (const TableKey& k : keys)
+            if (k.n == n && k.lo == lo && k.hi == hi) { *out = k; return nullptr; }
+        if (resize_axis_table_over(n, lo, hi, over, S, first.data(), count.data(), wts.data(), kResizeMaxTaps)) return "resize_nv12: box outside the frame, empty, or scale > 32";
+        TableKey k{n, lo, hi, (int32_t)words->size(), 1};
+        for (int i = 0; i < S; ++i) if (count[i] > k.stride) k.stride = count[i];
+        const size_t at = words->size();
+        words->resize(at + 2 * (size_t)S + (size_t)S * k.stride);
+        uint32_t* t = words->data() + at;
+        memcpy(t, first.data(), 4 * (size_t)S);
+        memcpy(t + S, count.data(), 4 * (size_t)S);
+        for (int i = 0; i < S; ++i) memcpy(t + 2 * (size_t)S + (size_t)i * k.stride, wts.data() + (size_t)i * kResizeMaxTaps, 4 * (size_t)k.stride);
+        keys.push_back(k);
+        *out = k;
+        return nullptr;
+    };
+    const double dx = chroma_site == VH_CHROMA_LEFT ? 0.25 : 0.0;
+    for (int b = 0; b < batch; ++b) {
+        const vh_frame_nv12& d = desc[b];
+        if (d.width < 2 || d.width > kResizeMaxSide || d.height < 2 || d.height > kResizeMaxSide || d.width % 2 || d.height % 2)
+            return "resize_nv12: width and height must be even and 2..8192";
+        if (d.y_stride < d.width || d.uv_stride < d.width) return "resize_nv12: y_stride or uv_stride < width";
+        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)d.width;
+        const uint64_t cspan = (uint64_t)(d.height / 2 - 1) * (uint64_t)d.uv_stride + (uint64_t)d.width;
+        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return "resize_nv12: a Y plane ends beyond nbytes";
+        if (d.uv_offset > nbytes || cspan > nbytes - d.uv_offset) return "resize_nv12: a UV plane ends beyond nbytes";
+        const double x0 = (double)d.box[0], y0 = (double)d.box[1], x1 = (double)d.box[2], y1 = (double)d.box[3];
+        TableKey kx, ky, kcx, kcy;
+        if (const char* e = axis(d.width, x0, x1, 0.0, &kx)) return e;
+        if (const char* e = axis(d.height, y0, y1, 0.0, &ky)) return e;
+        if (const char* e = axis(d.width / 2, x0 / 2.0 + dx, x1 / 2.0 + dx, dx, &kcx)) return e;
+        if (const char* e = axis(d.height / 2, y0 / 2.0, y1 / 2.0, 0.0, &kcy)) return e;
+        // band height of this pair of vertical tables: the most output rows whose luma + chroma source rows fit the LDS at full
+        // width; else one row and fewer columns
+        BandKey bk{ky.at, kcy.at, 0, 0};
+        for (const BandKey& k : bands)
+            if (k.yt == ky.at && k.cyt == kcy.at) bk = k;
+        if (!bk.band_rows) {
+            const int32_t* yf = (const int32_t*)(words->data() + ky.at);
+            const int32_t* cf = (const int32_t*)(words->data() + kcy.at);
+            const int fit = kResizeLdsFloats / S;   // floats per output column at full width
+            const int cost1 = worst_cost(yf, yf + S, cf, cf + S, S, 1);
+            if (cost1 > fit) {
+                bk.band_rows = 1;
+                bk.tile_cols = kResizeLdsFloats / cost1;   // >= 1: at most 65 + 2 * 34 floats per column
+            } else {
+                // a further output row costs about scale luma rows + 2 x scale / 2 chroma rows
+                const double scale = (y1 - y0) / S;
+                int kk = (int)((fit - cost1) / (2.0 * (scale > 0.03125 ? scale : 0.03125))) + 1;
+                if (kk > S) kk = S;
+                while (kk > 1 && worst_cost(yf, yf + S, cf, cf + S, S, kk) > fit) --kk;
+                // a small batch: at least ~64 workgroups, while bands stay a few rows high
+                const int want = (64 + batch - 1) / batch;
+                const int cap = S / want > 1 ? S / want : 1;
+                bk.band_rows = kk < cap ? kk : cap;
+                bk.tile_cols = S;
+            }
+            bands.push_back(bk);
+        }
+        RzNv12 f{};
+        f.y_off = d.y_offset; f.uv_off = d.uv_offset; f.h = d.height; f.w = d.width; f.y_stride = d.y_stride; f.uv_stride = d.uv_stride;
+        f.xt = kx.at; f.xs = kx.stride; f.yt = ky.at; f.ys = ky.stride;
+        f.cxt = kcx.at; f.cxs = kcx.stride; f.cyt = kcy.at; f.cys = kcy.stride;
+        f.band_rows = bk.band_rows; f.tile_cols = bk.tile_cols;
+        f.uv16 = base_aligned2 && d.uv_offset % 2 == 0 && d.uv_stride % 2 == 0;
+        memcpy(words->data() + (size_t)b * kResizeNv12FrameWords, &f, sizeof f);
+        const int tiles = ((S + f.band_rows - 1) / f.band_rows) * ((S + f.tile_cols - 1) / f.tile_cols);
+        if (tiles > *max_tiles) *max_tiles = tiles;
+    }
+    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return "resize_nv12: too many tiles";
+    return nullptr;
+}
+
+// ---- the kernel ------------------------------------------------------------------------------------------------------------
+struct Nv12Matrix { float m[12]; };
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+
+__device__ __forceinline__ uint32_t nv12_byte(float v) { return (uint32_t)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
+
+__global__ void __launch_bounds__(256)
+resize_nv12_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan, uint8_t* __restrict__ out, int S, int max_tiles,
+                   Nv12Matrix mat) {
+    __shared__ __attribute__((aligned(16))) float lds[kResizeLdsFloats];
+    const int f = blockIdx.x / max_tiles, tile = blockIdx.x - f * max_tiles;
+    const RzNv12 d = *(const RzNv12*)(plan + (size_t)f * kResizeNv12FrameWords);
+    const int nc = (S + d.tile_cols - 1) / d.tile_cols, nb = (S + d.band_rows - 1) / d.band_rows;
+    if (tile >= nb * nc) return;
+    const int band = tile / nc;
+    const int r0 = band * d.band_rows, r1 = min(r0 + d.band_rows, S);
+    const int c0 = (tile - band * nc) * d.tile_cols, c1 = min(c0 + d.tile_cols, S);
+    const int32_t* xfirst = (const int32_t*)(plan + d.xt);
+    const int32_t* xcount = xfirst + S;
+    const float* xw = (const float*)(xcount + S);
+    const int32_t* yfirst = (const int32_t*)(plan + d.yt);
+    const int32_t* ycount = yfirst + S;
+    const float* yw = (const float*)(ycount + S);
+    const int32_t* cxfirst = (const int32_t*)(plan + d.cxt);
+    const int32_t* cxcount = cxfirst + S;
+    const float* cxw = (const float*)(cxcount + S);
+    const int32_t* cyfirst = (const int32_t*)(plan + d.cyt);
+    const int32_t* cycount = cyfirst + S;
+    const float* cyw = (const float*)(cycount + S);
+    int ylo = yfirst[r0], yhi = ylo + ycount[r0], clo = cyfirst[r0], chi = clo + cycount[r0];
+    for (int r = r0 + 1; r < r1; ++r) {
+        ylo = min(ylo, yfirst[r]);
+        yhi = max(yhi, yfirst[r] + ycount[r]);
+        clo = min(clo, cyfirst[r]);
+        chi = max(chi, cyfirst[r] + cycount[r]);
+    }
+    const int rows_y = yhi - ylo, rows_c = chi - clo, cols = c1 - c0;
+    if ((rows_y + 2 * rows_c) * cols > kResizeLdsFloats || ylo < 0 || yhi > d.h || clo < 0 || chi > d.h / 2) return;
+    float* ldc = lds;                             // [rows_c][cols][2]
+    float* ldy = lds + 2 * rows_c * cols;         // [rows_y][cols]
+    const uint8_t* ysrc = frames + d.y_off;
+    const uint8_t* csrc = frames + d.uv_off;
+    const int tid = threadIdx.x;
+
+    // horizontal pass: luma rows ylo .. yhi-1 and chroma rows clo .. chi-1, output columns c0 .. c1-1
+    const int ny = rows_y * cols, nuv = rows_c * cols;
+    for (int e = tid; e < ny + nuv; e += 256) {
+        if (e < ny) {
+            const int y = e / cols, x = c0 + (e - y * cols);
+            const int n = xcount[x];
+            const float* w = xw + (size_t)x * d.xs;
+            const uint8_t* p = ysrc + (size_t)(ylo + y) * d.y_stride + xfirst[x];
+            float acc = 0.f;
+            for (int t = 0; t < n; ++t) acc = __builtin_fmaf(w[t], (float)p[t], acc);
+            ldy[e] = acc;
+        } else {
+            const int ec = e - ny;
+            const int y = ec / cols, x = c0 + (ec - y * cols);
+            const int n = cxcount[x];
+            const float* w = cxw + (size_t)x * d.cxs;
+            const uint8_t* p = csrc + (size_t)(clo + y) * d.uv_stride + (size_t)cxfirst[x] * 2;
+            float u = 0.f, v = 0.f;
+            if (d.uv16) {
+                for (int t = 0; t < n; ++t) {
+                    const uint32_t q = *(const uint16_t*)(p + 2 * t);
+                    const float wt = w[t];
+                    u = __builtin_fmaf(wt, (float)(q & 0xffu), u);
+                    v = __builtin_fmaf(wt, (float)(q >> 8), v);
+                }
+            } else {
+                for (int t = 0; t < n; ++t) {
+                    const float wt = w[t];
+                    u = __builtin_fmaf(wt, (float)p[2 * t], u);
+                    v = __builtin_fmaf(wt, (float)p[2 * t + 1], v);
+                }
+            }
+            *(f32x2*)(ldc + (size_t)ec * 2) = f32x2{u, v};
+        }
+    }
+    __syncthreads();
+
+    // vertical pass of both planes out of LDS, the matrix, three bytes per pixel
+    for (int e = tid; e < (r1 - r0) * cols; e += 256) {
+        const int rl = e / cols, xl = e - rl * cols, r = r0 + rl;
+        float y = 0.f, u = 0.f, v = 0.f;
+        {
+            const int n = ycount[r];
+            const float* w = yw + (size_t)r * d.ys;
+            const float* col = ldy + (size_t)(yfirst[r] - ylo) * cols + xl;
+            for (int t = 0; t < n; ++t) y = __builtin_fmaf(w[t], col[(size_t)t * cols], y);
+        }
+        {
+            const int n = cycount[r];
+            const float* w = cyw + (size_t)r * d.cys;
+            const float* col = ldc + ((size_t)(cyfirst[r] - clo) * cols + xl) * 2;
+            for (int t = 0; t < n; ++t) {
+                const f32x2 q = *(const f32x2*)(col + (size_t)t * cols * 2);
+                const float wt = w[t];
+                u = __builtin_fmaf(wt, q[0], u);
+                v = __builtin_fmaf(wt, q[1], v);
+            }
+        }
+        uint8_t* o = out + (((size_t)f * S + r) * S + c0 + xl) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float c = __builtin_fmaf(mat.m[4 * k], y, __builtin_fmaf(mat.m[4 * k + 1], u, __builtin_fmaf(mat.m[4 * k + 2], v, mat.m[4 * k + 3])));
+            o[k] = (uint8_t)nv12_byte(c);
+        }
+    }
+}
+
+hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
+                              uint8_t* out, hipStream_t s) {
+    if (!frames || !plan_dev || !out || !m12 || batch < 1 || S < 1 || max_tiles < 1 || (int64_t)batch * max_tiles > 0x7fffffffll)
+        return hipErrorInvalidValue;
+    Nv12Matrix mat;
+    memcpy(mat.m, m12, sizeof mat.m);
+    hipLaunchKernelGGL(resize_nv12_kernel, dim3((unsigned)(batch * max_tiles)), dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    return hipGetLastError();
+}
+
+// ---- host: the colour matrix -----------------------------------------------------------------------------------------------
+// Every expression is written as include/vithip.h states it and evaluated in IEEE double with no contraction, so that a numpy
+// float64 transcription gives, after the one rounding, the same fp32 entries.
+#pragma clang fp contract(off)
+int yuv_matrix(int standard, int full_range, float m[12]) {
+    double kr, kb;
+    switch (standard) {
+        case VH_YUV_BT601: kr = 0.299; kb = 0.114; break;
+        case VH_YUV_BT709: kr = 0.2126; kb = 0.0722; break;
+        case VH_YUV_BT2020: kr = 0.2627; kb = 0.0593; break;
+        default: return 1;
+    }
+    if (!m || (full_range != 0 && full_range != 1)) return 1;
+    const double kg = 1.0 - kr - kb;
+    const double sy = full_range ? 1.0 : 255.0 / 219.0, sc = full_range ? 1.0 : 255.0 / 224.0, oy = full_range ? 0.0 : 16.0;
+    const double rv = 2.0 * (1.0 - kr) * sc;
+    const double bu = 2.0 * (1.0 - kb) * sc;
+    const double gu = -(2.0 * kb * (1.0 - kb) / kg) * sc;
+    const double gv = -(2.0 * kr * (1.0 - kr) / kg) * sc;
+    const double yo = -(sy * oy);
+    const double v[12] = {sy, 0.0, rv, yo - 128.0 * rv,
+                          sy, gu, gv, yo - 128.0 * gu - 128.0 * gv,
+                          sy, bu, 0.0, yo - 128.0 * bu};
+    for (int i = 0; i < 12; ++i) m[i] = (float)v[i];
+    return 0;
+}
+
+}  // namespace vh

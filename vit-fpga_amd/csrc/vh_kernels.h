@@ -125,6 +125,19 @@ const char* resize_plan_build(const vh_frame* desc, int batch, int channels, int
                               std::vector<uint32_t>* words, int* max_tiles);
 hipError_t launch_resize_u8(const uint8_t* frames, const uint32_t* plan_dev, int batch, int channels, int S, int max_tiles,
                             uint8_t* out_u8, hipStream_t stream);
+// NV12 frames (kernels_resize_nv12.hip; contract: vithip.h, "NV12 frames"): both planes resampled with the tables above and the
+// 3 x 4 colour matrix applied to the unrounded y, u, v, one launch for the batch -> [batch][S][S][3] bytes.
+// resize_axis_table_over: resize_axis_table with hi <= n_in + over (left-sited chroma overhangs the last sample by 0.25).
+// resize_plan_build_nv12: checks every descriptor and fills `words` with [batch x 24-word frame record][tables]; nullptr, or why
+// the call is refused.  yuv_matrix: the matrix of a standard (VH_YUV_*) and range, host only; 0 = ok.
+constexpr int kResizeNv12FrameWords = 24;
+int resize_axis_table_over(int n_in, double lo, double hi, double over, int n_out, int32_t* first, int32_t* count, float* weights,
+                           int max_taps);
+const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, size_t nbytes, bool base_aligned2, int chroma_site,
+                                   std::vector<uint32_t>* words, int* max_tiles);
+hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12_host,
+                              uint8_t* out_u8, hipStream_t stream);
+int yuv_matrix(int standard, int full_range, float m[12]);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
 bool patch_fused_supported(int image, int patch, int channels, int dim);

@@ -253,6 +253,10 @@ struct vh_ctx {
     uint8_t* rz_frames = nullptr;
     size_t rz_frames_cap = 0;
     std::vector<uint32_t> rz_words;
+    // NV12 frames (vh_set_frame_colour): the 3 x 4 matrix and the chroma siting of the NV12 entry points.  The matrix travels to
+    // resize_nv12_kernel by value at each launch, outside any captured graph.
+    float nv12_m[12];
+    int nv12_site = VH_CHROMA_LEFT;
     int64_t last_us = 0;
     bool timed = false;
     int last_batch = 0;
@@ -958,12 +962,21 @@ struct FrameJob {
     const uint32_t* plan_host;   // pinned; stays untouched until the upload below has run
     size_t words;
     int max_tiles;
+    bool nv12 = false;           // NV12 frames: the plan of resize_plan_build_nv12, run by resize_nv12_kernel with the context's matrix
 };
 
 // checks the descriptors of one call and builds its plan in c->rz_words; nothing is enqueued
 int frames_plan(vh_ctx* c, const vh_frame* desc, int batch, size_t nbytes, bool base_aligned4, int* max_tiles) {
     if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
     const char* why = resize_plan_build(desc, batch, c->cfg.channels, c->cfg.image_size, nbytes, base_aligned4, &c->rz_words, max_tiles);
+    if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
+    return VH_OK;
+}
+
+int frames_plan_nv12(vh_ctx* c, const vh_frame_nv12* desc, int batch, size_t nbytes, bool base_aligned2, int* max_tiles) {
+    if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
+    if (c->cfg.channels != 3) return fail(&c->err, VH_ERR_INVALID, "NV12 frames need a model with 3 channels, this one has %d", c->cfg.channels);
+    const char* why = resize_plan_build_nv12(desc, batch, c->cfg.image_size, nbytes, base_aligned2, c->nv12_site, &c->rz_words, max_tiles);
     if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
     return VH_OK;
 }
@@ -1016,7 +1029,10 @@ int enqueue_resize(vh_ctx* c, const FrameJob& j, int batch) {
     int rc;
     HIPCHK(&c->err, hipMemcpyAsync(c->rz_plan_dev, j.plan_host, j.words * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = tmark())) return rc;
-    HIPCHK(&c->err, launch_resize_u8(j.frames_dev, c->rz_plan_dev, batch, c->cfg.channels, c->cfg.image_size, j.max_tiles, c->rz_u8, c->stream));
+    if (j.nv12)
+        HIPCHK(&c->err, launch_resize_nv12(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->nv12_m, c->rz_u8, c->stream));
+    else
+        HIPCHK(&c->err, launch_resize_u8(j.frames_dev, c->rz_plan_dev, batch, c->cfg.channels, c->cfg.image_size, j.max_tiles, c->rz_u8, c->stream));
     return tmark();
 }
 
@@ -1245,6 +1261,8 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         c->in_scale[i] = i < cfg->channels ? 1.0f / 255.0f : 0.f;
         c->in_shift[i] = 0.f;
     }
+    yuv_matrix(VH_YUV_BT709, 0, c->nv12_m);   // NV12 frames: what an HD video decoder emits, until vh_set_frame_colour says otherwise
+    c->nv12_site = VH_CHROMA_LEFT;
     {
         // (fp8 operands: the hi plane is e4m3 -- the GEMM operand itself -- and the lo plane bf16: 3 bytes per element as well)
         const char* e = getenv("VH_RESID_SPLIT");
@@ -1629,6 +1647,61 @@ int vh_forward_frames_u8(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, c
     return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
 }
 
+// NV12 frames: the same two entry points with the plan of resize_plan_build_nv12 (both planes + the colour matrix in one launch)
+int vh_forward_device_frames_nv12(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev) {
+    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, ((uintptr_t)frames_dev & 1) == 0, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, true};
+    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+}
+
+int vh_forward_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_host) {
+    int rc = check_forward_args(c, frames_host, batch, logits_host);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, true, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, true};
+    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+}
+
+int vh_yuv_matrix(int standard, int full_range, float m[12]) {
+    if (yuv_matrix(standard, full_range, m))
+        return fail(nullptr, VH_ERR_INVALID, "yuv matrix: standard must be VH_YUV_BT601, _BT709 or _BT2020, full_range 0 or 1, m not NULL");
+    return VH_OK;
+}
+
+// Colour matrix and chroma siting of the NV12 entry points.  The resize runs outside the captured graph and takes the matrix by
+// value at each launch: no graph to drop, nothing in flight to wait for.
+int vh_set_frame_colour(vh_ctx* c, const float m[12], int chroma_site) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
+    if (!m) {
+        yuv_matrix(VH_YUV_BT709, 0, c->nv12_m);
+        c->nv12_site = VH_CHROMA_LEFT;
+        return VH_OK;
+    }
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return fail(&c->err, VH_ERR_INVALID, "chroma_site %d is neither VH_CHROMA_CENTER nor VH_CHROMA_LEFT", chroma_site);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(m[i])) return fail(&c->err, VH_ERR_INVALID, "colour matrix entry %d is not finite", i);
+    memcpy(c->nv12_m, m, sizeof c->nv12_m);
+    c->nv12_site = chroma_site;
+    return VH_OK;
+}
+
+int vh_get_frame_colour(const vh_ctx* c, float m[12], int* chroma_site) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
+    if (m) memcpy(m, c->nv12_m, sizeof c->nv12_m);
+    if (chroma_site) *chroma_site = c->nv12_site;
+    return VH_OK;
+}
+
 int vh_resize_table(int n_in, double lo, double hi, int n_out, int32_t* first, int32_t* count, float* weights, int max_taps) {
     if (resize_axis_table(n_in, lo, hi, n_out, first, count, weights, max_taps))
         return fail(nullptr, VH_ERR_INVALID, "resize table: bad argument, box outside 0..n_in or empty, scale > %d, or more than max_taps taps", kResizeMaxScale);
@@ -1817,7 +1890,9 @@ int vh_ring_input_frames(vh_ctx* c, uint8_t** pinned, size_t* capacity) {
 
 // frames ring: in_host holds `frame_bytes` of frames described by `desc`; the slot's upload is followed by the resize into
 // c->rz_u8 on the context's stream (forwards are ordered on that stream, so one resized buffer serves every slot)
-static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const vh_frame* desc = nullptr) {
+// (desc12: the submit carries NV12 frames instead; a slot is raw bytes, so one frames ring takes both)
+static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const vh_frame* desc = nullptr,
+                       const vh_frame_nv12* desc12 = nullptr, bool nv12 = false) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "no ring: call vh_ring_create first");
     if (c->ring_kind != kind) return fail(&c->err, VH_ERR_STATE, "this ring stages %s", ring_kind_name(c->ring_kind));
@@ -1828,7 +1903,7 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     int rc, max_tiles = 0;
     if (frames) {   // every check, and the plan, before anything is enqueued or the slot is touched
         if (frame_bytes < 1 || frame_bytes > c->ring_slot_bytes) return fail(&c->err, VH_ERR_INVALID, "nbytes %zu outside 1..slot_bytes=%zu", frame_bytes, c->ring_slot_bytes);
-        if ((rc = frames_plan(c, desc, batch, frame_bytes, true, &max_tiles))) return rc;
+        if ((rc = nv12 ? frames_plan_nv12(c, desc12, batch, frame_bytes, true, &max_tiles) : frames_plan(c, desc, batch, frame_bytes, true, &max_tiles))) return rc;
     }
     HIPCHK(&c->err, hipSetDevice(c->device));
     vh_ctx::RingSlot& s = c->ring[c->ring_wr];
@@ -1850,7 +1925,7 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     HIPCHK(&c->err, hipEventRecord(s.in_done, c->copy_in));
     HIPCHK(&c->err, hipStreamWaitEvent(c->stream, s.in_done, 0));
     if (frames) {
-        const FrameJob job{(const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles};
+        const FrameJob job{(const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles, nv12};
         if ((rc = enqueue_resize(c, job, batch))) return rc;
     }
     rc = run_step(c, frames ? ImgIn{c->rz_u8, true} : ImgIn{s.d_in, kind == vh_ctx::RING_U8}, batch, s.d_out);
@@ -1868,6 +1943,9 @@ int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) { return ring_sub
 int vh_ring_submit_u8(vh_ctx* c, const uint8_t* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_U8); }
 int vh_ring_submit_frames(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch) {
     return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc);
+}
+int vh_ring_submit_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, nullptr, desc, true);
 }
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
@@ -2249,6 +2327,27 @@ int vh_op_resize_u8(const uint8_t* frames, size_t nbytes, const vh_frame* desc, 
     OPCHK(hipMalloc((void**)&plan, words.size() * 4));
     hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e == hipSuccess) e = launch_resize_u8(frames, plan, batch, channels, out_size, max_tiles, out, (hipStream_t)stream);
+    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(plan);
+    OPCHK(e);
+    OPCHK(es);
+    return VH_OK;
+}
+
+int vh_op_resize_nv12(const uint8_t* frames, size_t nbytes, const vh_frame_nv12* desc, int batch, int out_size, const float* m12,
+                      int chroma_site, uint8_t* out, void* stream) {
+    // every check before a device is touched
+    if (!frames || !desc || !m12 || !out) return fail(nullptr, VH_ERR_INVALID, "null buffer");
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "resize_nv12: colour matrix entry %d is not finite", i);
+    std::vector<uint32_t> words;
+    int max_tiles = 0;
+    if (const char* why = resize_plan_build_nv12(desc, batch, out_size, nbytes, ((uintptr_t)frames & 1) == 0, chroma_site, &words, &max_tiles))
+        return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    uint32_t* plan = nullptr;
+    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
+    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = launch_resize_nv12(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream);
     const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
     hipFree(plan);
     OPCHK(e);

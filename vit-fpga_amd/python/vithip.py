@@ -48,6 +48,16 @@ class Frame(C.Structure):
                 ("box", C.c_float * 4)]
 
 
+class FrameNV12(C.Structure):
+    """vh_frame_nv12: one NV12 frame (a Y plane and a plane of interleaved U,V pairs) inside the buffer of a call, and the box (in
+    luma pixels) to resample to image_size^2."""
+    _fields_ = [("y_offset", C.c_uint64), ("uv_offset", C.c_uint64), ("height", C.c_int32), ("width", C.c_int32),
+                ("y_stride", C.c_int32), ("uv_stride", C.c_int32), ("box", C.c_float * 4)]
+
+
+CHROMA_CENTER, CHROMA_LEFT = 0, 1          # vh_set_frame_colour / vh_op_resize_nv12: JPEG / MPEG-1 siting, MPEG-2 / H.264 / HEVC siting
+YUV_BT601, YUV_BT709, YUV_BT2020 = 0, 1, 2  # vh_yuv_matrix
+
 # every exported symbol of include/vithip.h: name -> (restype, argtypes)
 _vp, _i, _i64, _u64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float
 _pi = C.POINTER(C.c_int)
@@ -84,6 +94,11 @@ SYMBOLS = {
     "vh_resize_table": (_i, [_i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _i]),
     "vh_forward_frames_u8": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_device_frames_u8": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_yuv_matrix": (_i, [_i, _i, _vp]),
+    "vh_set_frame_colour": (_i, [_vp, _vp, _i]),
+    "vh_get_frame_colour": (_i, [_vp, _vp, _pi]),
+    "vh_forward_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_fill_input_seeded": (_i, [_vp, _u64, _i, _vp]),
     "vh_last_forward_us": (_i, [_vp, C.POINTER(_i64)]),
     "vh_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
@@ -112,6 +127,7 @@ SYMBOLS = {
     "vh_ring_create_frames": (_i, [_vp, _i, _i, _sz]),
     "vh_ring_input_frames": (_i, [_vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(_sz)]),
     "vh_ring_submit_frames": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_set_graph": (_i, [_vp, _i]),
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
@@ -142,6 +158,7 @@ SYMBOLS = {
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "vh_op_resize_u8": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp]),
+    "vh_op_resize_nv12": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -316,6 +333,38 @@ def pack_frames(frames, boxes=None, channels=None):
         desc[i].box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(v) for v in box)
         parts.append(f.reshape(-1))
         off += f.size
+    return np.concatenate(parts), desc
+
+
+def yuv_matrix(standard=YUV_BT709, full_range=False):
+    """vh_yuv_matrix: the row-major 3 x 4 float32 matrix (rows R, G, B; columns y, u, v, 1) of a standard and range."""
+    m = np.zeros(12, np.float32)
+    _check(lib().vh_yuv_matrix(standard, 1 if full_range else 0, m.ctypes.data))
+    return m.reshape(3, 4)
+
+
+def pack_frames_nv12(planes, boxes=None):
+    """A list of (Y [H, W] uint8, UV [H/2, W/2, 2] uint8) pairs -> (one uint8 buffer, the (FrameNV12 * n) descriptors).  Each frame
+    lies as a decoder writes it: its Y plane, then its UV plane, rows unpadded (y_stride = uv_stride = W), frames back to back.
+    boxes: one (x0, y0, x1, y1) per frame in luma pixels, None = the whole frame."""
+    planes = [(np.asarray(y), np.asarray(uv)) for y, uv in planes]
+    if boxes is None:
+        boxes = [None] * len(planes)
+    if not planes or len(boxes) != len(planes):
+        raise ValueError("pack_frames_nv12: one box (or None) per frame, at least one frame")
+    desc = (FrameNV12 * len(planes))()
+    parts, off = [], 0
+    for i, ((y, uv), box) in enumerate(zip(planes, boxes)):
+        if y.dtype != np.uint8 or uv.dtype != np.uint8 or y.ndim != 2 or uv.ndim != 3 or uv.shape[2] != 2:
+            raise TypeError(f"pack_frames_nv12: frame {i} is not a ([H, W], [H/2, W/2, 2]) pair of uint8 arrays")
+        h, w = y.shape
+        if h % 2 or w % 2 or uv.shape[:2] != (h // 2, w // 2):
+            raise ValueError(f"pack_frames_nv12: frame {i}: Y is {h} x {w}, UV is {uv.shape[0]} x {uv.shape[1]} pairs; want even sides and UV of half each")
+        desc[i].y_offset, desc[i].uv_offset = off, off + h * w
+        desc[i].height, desc[i].width, desc[i].y_stride, desc[i].uv_stride = h, w, w, w
+        desc[i].box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(v) for v in box)
+        parts += [np.ascontiguousarray(y).reshape(-1), np.ascontiguousarray(uv).reshape(-1)]
+        off += h * w + h * w // 2
     return np.concatenate(parts), desc
 
 
@@ -591,6 +640,37 @@ class VitContext:
     def forward_device_frames_u8(self, frames_ptr, nbytes, desc, out_ptr):
         _check(lib().vh_forward_device_frames_u8(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
 
+    # ---- NV12 video frames: both planes resized and the colour matrix applied on the GPU, then forward_u8 of the result ----
+    def set_frame_colour(self, m=None, chroma_site=CHROMA_LEFT):
+        """m: 12 floats (row-major 3 x 4, see yuv_matrix); None restores the default, BT.709 limited range with left siting."""
+        if m is None:
+            _check(lib().vh_set_frame_colour(self.h, None, 0), self.h)
+            return
+        m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+        if m.size != 12:
+            raise ValueError(f"set_frame_colour: expected 12 values, got {m.size}")
+        _check(lib().vh_set_frame_colour(self.h, m.ctypes.data, chroma_site), self.h)
+
+    def get_frame_colour(self):
+        m, site = np.empty(12, np.float32), C.c_int(0)
+        _check(lib().vh_get_frame_colour(self.h, m.ctypes.data, C.byref(site)), self.h)
+        return m.reshape(3, 4), site.value
+
+    def forward_frames_nv12(self, planes, boxes=None):
+        """planes: a list of (Y [H, W], UV [H/2, W/2, 2]) uint8 pairs, any even sizes; boxes as forward_frames, in luma pixels.
+        Returns [len(planes), classes] fp32 logits: the bits forward_u8 gives for op_resize_nv12's output."""
+        buf, desc = pack_frames_nv12(planes, boxes)
+        return self.forward_frames_nv12_packed(buf, desc)
+
+    def forward_frames_nv12_packed(self, buf, desc):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
+        _check(lib().vh_forward_frames_nv12(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
+        return out
+
+    def forward_device_frames_nv12(self, frames_ptr, nbytes, desc, out_ptr):
+        _check(lib().vh_forward_device_frames_nv12(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
 
@@ -659,6 +739,19 @@ class VitContext:
             buf = np.ascontiguousarray(buf, dtype=np.uint8)
             ptr = buf.ctypes.data
         _check(lib().vh_ring_submit_frames(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+
+    def ring_submit_frames_nv12(self, planes, boxes=None):
+        """NV12 frames into the next slot of a frames ring (ring_create_frames); RGB and NV12 submits may alternate."""
+        buf, desc = pack_frames_nv12(planes, boxes)
+        self.ring_submit_frames_nv12_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_nv12_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
+        ptr = None
+        if buf is not None:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            ptr = buf.ctypes.data
+        _check(lib().vh_ring_submit_frames_nv12(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
 
     def ring_free_slots(self):
         n = C.c_int(0)
@@ -1003,6 +1096,15 @@ def op_resize_u8(frames_ptr, nbytes, desc, channels, out_size, out_ptr):
     """The resize of the frames entry points on its own: the frames at frames_ptr (device, any alignment) described by the
     (Frame * n) array desc -> [n, out_size, out_size, channels] bytes at out_ptr."""
     _check(lib().vh_op_resize_u8(frames_ptr, nbytes, C.addressof(desc), len(desc), channels, out_size, out_ptr, None))
+
+
+def op_resize_nv12(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """The resize + colour conversion of the NV12 entry points on its own: the planes at frames_ptr (device, any alignment)
+    described by the (FrameNV12 * n) array desc -> [n, out_size, out_size, 3] bytes at out_ptr.  m: 12 floats, row-major 3 x 4."""
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+    if m.size != 12:
+        raise ValueError(f"op_resize_nv12: expected 12 matrix entries, got {m.size}")
+    _check(lib().vh_op_resize_nv12(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
 
 
 def op_cast(in_ptr, out_ptr, n, dtype):
