@@ -322,6 +322,49 @@ int vh_set_frame_colour(vh_ctx* ctx, const float m[12], int chroma_site);
 int vh_get_frame_colour(const vh_ctx* ctx, float m[12], int* chroma_site);
 int vh_forward_frames_nv12(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_host);
 int vh_forward_device_frames_nv12(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev);
+/* ---- Planar YUV frames: I420 / YV12 and JPEG's 4:4:4, 4:2:2, 4:2:0, 4:4:0 planes ------------------------------------------
+ * What software video decoders (ffmpeg's yuv420p, libvpx, dav1d, libde265) and JPEG decoders in raw-data mode (libjpeg-turbo,
+ * TurboJPEG tjDecompressToYUVPlanes, rocJPEG) emit: three separate byte planes.  A PLANAR FRAME is
+ *       a Y plane    height x width bytes, rows y_stride bytes apart, at y_offset,
+ *       a U plane    ch x cw bytes, rows u_stride bytes apart, at u_offset, and
+ *       a V plane    ch x cw bytes, rows v_stride bytes apart, at v_offset,
+ * cw = (width + sub_x - 1) / sub_x, ch = (height + sub_y - 1) / sub_y (the JPEG and ffmpeg rule for odd sizes), all offsets
+ * relative to the buffer of the call.  width and height are within 1..8192 and of ANY parity; sub_x and sub_y are 1 or 2:
+ * 4:4:4 = (1, 1), 4:2:2 = (2, 1), 4:2:0 = (2, 2), 4:4:0 = (1, 2).  y_stride >= width, u_stride >= cw, v_stride >= cw; the last
+ * byte of each plane lies within nbytes; the planes may lie in any order, need not be adjacent or aligned.  YV12 is I420 with
+ * u_offset and v_offset exchanged: no separate mode.  `box` means what it means in vh_frame: LUMA pixel coordinates, fractional
+ * allowed, 0 <= x0 < x1 <= width and the same in y.  The context must have channels == 3 (else VH_ERR_INVALID).
+ * Layout: sizeof(vh_frame_yuv) == 72; y_offset 0, u_offset 8, v_offset 16, height 24, width 28, y_stride 32, u_stride 36,
+ * v_stride 40, sub_x 44, sub_y 48, box 52, reserved 68 (ignored).
+ * RESAMPLING.  Each plane goes through the axis contract of "8-bit frames" unchanged (the same doubles, one rounding to fp32
+ * per weight): Y with n = width (height) and the box as given; U and V each as a 1-channel image of cw x ch whose box per axis
+ * is (lo / sub + delta, hi / sub + delta), delta = 0.25 on the horizontal axis only when sub_x == 2 and the context's siting is
+ * VH_CHROMA_LEFT, 0 otherwise.  With sub == 1 on an axis the chroma table of that axis is the luma table.  The only relaxation
+ * of hi <= n is the quarter-sample overhang of left siting (even widths), as in "NV12 frames"; with centre siting and odd sizes
+ * hi / 2 <= cw holds by construction.  Each plane runs the horizontal pass, then the vertical pass, each an fp32 fmaf chain in
+ * ascending tap order from 0 with nothing rounded in between.
+ * CONVERSION AND STATE are those of "NV12 frames", word for word: the unrounded y, u, v pass the 3 x 4 matrix with the same nested
+ * fmaf expression, the byte is rintf(min(max(out[k], 0), 255)), and the matrix and the siting are the context's
+ * (vh_set_frame_colour): there is no second colour state.  The default (BT.709 limited range, left siting) is the VIDEO one.  A
+ * JPEG caller sets vh_yuv_matrix(VH_YUV_BT601, 1, m) with VH_CHROMA_CENTER: JFIF is full-range BT.601 with centre-sited chroma.
+ * From there on the forward IS vh_forward_u8 of that S x S x 3 byte image, and the logits are BIT-IDENTICAL to feeding
+ * vh_op_resize_yuv's output to the u8 entry point.  An I420 frame of even size gives the bytes vh_op_resize_nv12 gives for
+ * the same planes interleaved.
+ * REFUSED with VH_ERR_INVALID before a device is touched or anything is enqueued, each with a message of its own: width or
+ * height outside 1..8192; sub_x or sub_y not 1 or 2; y_stride < width; u_stride < cw or v_stride < cw; a plane whose last byte
+ * lies beyond nbytes; a box outside the frame, or empty; scale > 32 on an axis; channels != 3; null pointers.
+ *   vh_forward_frames_yuv, vh_forward_device_frames_yuv: vh_forward_frames_nv12 / vh_forward_device_frames_nv12 for planar
+ *                       frames.  Stage "resize" of vh_set_stage_timing times this launch too. */
+typedef struct vh_frame_yuv {
+    uint64_t y_offset, u_offset, v_offset;
+    int32_t height, width;
+    int32_t y_stride, u_stride, v_stride;
+    int32_t sub_x, sub_y;
+    float box[4];
+    int32_t reserved;
+} vh_frame_yuv;
+int vh_forward_frames_yuv(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host);
+int vh_forward_device_frames_yuv(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev);
 /* uniform[-1,1) synthetic images written straight into HBM (value range of the reference,
  * def/defines.h:11-12) */
 int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_dev);
@@ -366,6 +409,10 @@ int vh_ring_submit_frames(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes
  * channels == 3.  Checked and copied before anything is enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on
  * the other two kinds of ring.  A collected batch has the bits vh_forward_frames_nv12 returns. */
 int vh_ring_submit_frames_nv12(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch);
+/* Planar YUV frames ("Planar YUV frames" above) on the SAME frames ring: RGB, NV12 and planar submits interleave on one ring.
+ * The context must have channels == 3.  Checked and copied before anything is enqueued; a refused submit leaves the ring as it
+ * was; VH_ERR_STATE on the other two kinds of ring.  A collected batch has the bits vh_forward_frames_yuv returns. */
+int vh_ring_submit_frames_yuv(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -555,6 +602,10 @@ int vh_op_resize_u8(const uint8_t* frames_dev, size_t nbytes, const vh_frame* de
  * device is touched.  Allocates and frees its table buffer: a test and measurement tap, not a hot path. */
 int vh_op_resize_nv12(const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc_host, int batch, int out_size,
                       const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
+/* The same tap for planar frames ("Planar YUV frames"): the arguments of vh_op_resize_nv12 with vh_frame_yuv descriptors.
+ * Every argument and descriptor is checked before a device is touched. */
+int vh_op_resize_yuv(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc_host, int batch, int out_size,
+                     const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,

@@ -18,6 +18,12 @@ NV12 passes instead, ViT-B/16 bf16, in ONE process: the frames 
 NV12 frames of the same pictures (nv12_ref.rgb_to_nv12, BT.709 limited range), at 360 x 480 (batch 512) and at 1080 x 1920 (batch
 64), 0.875 centre box, interleaved passes and medians as above; then the resize launch of each in us and GB/s of source bytes
 inside the boxes.  Written to <out>/nv12_host_path.txt and .json.
+
+  python tools/frames_bench.py --yuv420p [--out profiles] [--steps 30] [--passes 3]
+
+Planar passes, ViT-B/16 bf16, in ONE process: the frames ring fed NV12 frames -- the yardstick, it moves the same
+bytes -- against the frames ring fed the I420 (yuv420p) planes of the same pictures, the same two shapes, boxes, passes and medians;
+the two rings compute the same logits, which is checked.  Written to <out>/yuv_planar_host_path.txt and .json.
 """
 import argparse
 import json
@@ -133,6 +139,93 @@ class SideNV12(Side):
         self.ctx.ring_submit_frames_nv12_packed(None, self.nbytes, self.desc)
 
 
+class SideYUV(SideNV12):
+    """One context with a frames ring fed I420 frames: y [B, H, W], u and v [B, H/2, W/2], each frame's planes back to back."""
+
+    def __init__(self, cfg, dname, batch, flags, eps, scale, shift, y, u, v, box):
+        self.batch, self.frames = batch, True
+        self.ctx = vithip.VitContext(cfg, dtype=DT[dname], max_batch=batch, flags=flags, ln_eps=eps)
+        self.ctx.init_weights_seeded(0)
+        self.ctx.set_input_norm(scale, shift)
+        _, h, w = y.shape
+        q = (h // 2) * (w // 2)
+        per = h * w + 2 * q
+        buf = np.empty((batch, per), np.uint8)
+        buf[:, :h * w] = y.reshape(batch, -1)
+        buf[:, h * w:h * w + q] = u.reshape(batch, -1)
+        buf[:, h * w + q:] = v.reshape(batch, -1)
+        self.nbytes = buf.nbytes
+        self.desc = (vithip.FrameYUV * batch)()
+        for b in range(batch):
+            d = self.desc[b]
+            d.y_offset, d.u_offset, d.v_offset = b * per, b * per + h * w, b * per + h * w + q
+            d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, w, w // 2, w // 2, 2, 2
+            d.box[:] = box
+        self.box_bytes = batch * (box[2] - box[0]) * (box[3] - box[1]) * 1.5
+        self.ctx.ring_create_frames(SLOTS, batch, self.nbytes)
+        for _ in range(SLOTS):
+            self.ctx.ring_input_frames()[:self.nbytes] = buf.reshape(-1)
+            self.submit()
+        self.first = [self.ctx.ring_collect().copy() for _ in range(SLOTS)][0]
+
+    def submit(self):
+        self.ctx.ring_submit_frames_yuv_packed(None, self.nbytes, self.desc)
+
+
+def yuv420p_main(a):
+    import nv12_ref as N
+    lines, rows = [], []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    scale, shift = vithip.input_norm_from_mean_std(MEAN, STD)
+    title, key, cfg, dname, _, flags, eps = RUNS[0]
+    log(f"frames_bench --yuv420p: {title[:-5]}, frames rings of {SLOTS} slots, {a.steps} steps per pass, {a.passes} interleaved passes (NV12 frames "
+        f"against the I420 planes of the same pictures; 0.875 centre box); median pass [min .. max]; images/s")
+    for h, w, batch in ((360, 480, 512), (1080, 1920, 64)):
+        rng = np.random.default_rng(3)
+        small = rng.integers(0, 256, size=(batch, h // 8, w // 8, 3), dtype=np.uint8)
+        rgb = np.ascontiguousarray(np.repeat(np.repeat(small, 8, axis=1), 8, axis=2))     # the pictures of --nv12
+        rgb ^= rng.integers(0, 8, size=rgb.shape, dtype=np.uint8)
+        planes = [N.rgb_to_nv12(f) for f in rgb]
+        del rgb
+        y, uv = np.stack([p[0] for p in planes]), np.stack([p[1] for p in planes])
+        box = vithip.center_crop_box(h, w)
+        common = (cfg, dname, batch, flags, eps, scale, shift)
+        A = SideNV12(*common, y=y, uv=uv, box=box)
+        B = SideYUV(*common, y=y, u=np.ascontiguousarray(uv[..., 0]), v=np.ascontiguousarray(uv[..., 1]), box=box)
+        same = bool(np.array_equal(A.first.view(np.uint32), B.first.view(np.uint32)) and np.isfinite(A.first).all())
+        ra, rb = [], []
+        for _ in range(a.passes):
+            ra.append(A.ring_rate(a.steps)); rb.append(B.ring_rate(a.steps))
+        k = [A.resize_us(8), B.resize_us(8), A.resize_us(8), B.resize_us(8)]
+        r = dict(config=key, frame=[h, w], batch=batch, ring_nv12=mid(ra), ring_i420=mid(rb),
+                 h2d_MB_per_step=dict(nv12=A.nbytes / 1e6, i420=B.nbytes / 1e6), logits_i420_equal_nv12=same,
+                 resize_nv12_us_avg=[k[0][0], k[2][0]], resize_i420_us_avg=[k[1][0], k[3][0]],
+                 resize_nv12_us_min=min(k[0][1], k[2][1]), resize_i420_us_min=min(k[1][1], k[3][1]),
+                 box_MB=dict(nv12=A.box_bytes / 1e6, i420=B.box_bytes / 1e6))
+        rows.append(r)
+        base = r["ring_nv12"][0]
+        log(f"{h}x{w}, batch {batch}: logits of the I420 ring equal the NV12 ring's bit for bit: {same}")
+        for name, kk, mb in (("frames ring, NV12 ", "ring_nv12", A.nbytes / 1e6), ("frames ring, I420 ", "ring_i420", B.nbytes / 1e6)):
+            m, lo, hi = r[kk]
+            log(f"    {name}: {m:9.0f} [{lo:9.0f} .. {hi:9.0f}] = {100 * m / base:6.2f} % of the NV12 ring | upload {mb:7.1f} MB per step = "
+                f"{mb * 1e-3 * m / batch:5.1f} GB/s")
+        for name, avg, mn, mb in (("NV12", r["resize_nv12_us_avg"], r["resize_nv12_us_min"], A.box_bytes / 1e6),
+                                  ("I420", r["resize_i420_us_avg"], r["resize_i420_us_min"], B.box_bytes / 1e6)):
+            us = float(np.mean(avg))
+            log(f"    resize {name}: {us:8.1f} us per launch avg ({mn:.1f} min; passes {avg[0]:.1f} {avg[1]:.1f}) | "
+                f"{mb:.1f} MB inside the boxes = {mb * 1e-3 / (us * 1e-6):.0f} GB/s")
+        A.close(); B.close()
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "yuv_planar_host_path.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+    with open(os.path.join(a.out, "yuv_planar_host_path.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def nv12_main(a):
     import nv12_ref as N
     lines, rows = [], []
@@ -198,7 +291,10 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--only", default="")
     ap.add_argument("--nv12", action="store_true", help="the NV12 passes (RGB frames ring against NV12 frames ring) instead")
+    ap.add_argument("--yuv420p", action="store_true", help="the planar passes (NV12 frames ring against I420 frames ring) instead")
     a = ap.parse_args()
+    if a.yuv420p:
+        return yuv420p_main(a)
     if a.nv12:
         return nv12_main(a)
     lines, rows = [], []

@@ -1,0 +1,104 @@
+"""Host-side check of the planar YUV resize: builds tools/yuv_host_check (the planner and the kernel body of
+kernels_resize_nv12.hip as host code under AddressSanitizer and UBSan, one thread per work-item, exact-size heap blocks), runs it over
+the operator cases of tests/test_yuv_planar.py at every sub-sampling, odd layouts, left-sited boxes that reach or overhang the last
+chroma column, a mixed batch, 40 small frames, one 1080 x 1920 frame and the two frames either side of the 4:4:4 planner boundary,
+and compares each output with the fp32 emulation of tests/yuv_ref.py byte for byte.  CPU only; no device is touched.
+
+    python tools/yuv_host_check.py            (needs libvithip.so: make -C vit-fpga_amd)"""
+import os
+import struct
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "vit-fpga_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import nv12_ref as N  # noqa: E402
+import vithip  # noqa: E402
+import yuv_ref as Y  # noqa: E402
+from test_gpu_nv12 import lay_out as lay_out_nv12  # noqa: E402
+from test_gpu_yuv_planar import lay_out, planner_boundary_444  # noqa: E402
+from test_nv12 import make_nv12  # noqa: E402
+from test_yuv_planar import COLOURS, OP_CASES, SUBS, make_yuv  # noqa: E402
+
+EXE = os.path.join(ROOT, "tools", "yuv_host_check")
+PKG = os.path.join(ROOT, "vit-fpga_amd")
+
+
+def build():
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g",
+                           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tools", "yuv_host_check.hip"), "-o", EXE, "-L" + PKG, "-lvithip", "-Wl,-rpath," + PKG, "-lpthread"])
+
+
+def run(tmp, label, planes, boxes, s, m, site, subs, **layout):
+    """One call of the host build; returns False if its bytes differ from the emulation.  subs None: `planes` are NV12 pairs (the
+    other instantiation of the same body)."""
+    buf, desc = lay_out_nv12(planes, boxes, **layout) if subs is None else lay_out(planes, boxes, subs, **layout)
+    case, out = os.path.join(tmp, "case.bin"), os.path.join(tmp, "out.bin")
+    with open(case, "wb") as f:
+        f.write(struct.pack("<4i", 0 if subs is None else 1, s, len(planes), site))
+        f.write(np.ascontiguousarray(m, np.float32).tobytes())
+        f.write(struct.pack("<Q", buf.nbytes))
+        f.write(bytes(desc))
+        f.write(buf.tobytes())
+    p = subprocess.run([EXE, case, out], capture_output=True, text=True)
+    if p.returncode:
+        print(f"FAIL {label}: exit {p.returncode}\n{p.stdout}{p.stderr}")
+        return False
+    got = np.fromfile(out, np.uint8).reshape(len(planes), s, s, 3)
+    if subs is None:
+        want = np.stack([N.resize_nv12_f32(y, uv, box, s, m, site) for (y, uv), box in zip(planes, boxes)])
+    else:
+        want = np.stack([Y.resize_yuv_f32(*yuv, box, s, m, site, sub) for yuv, box, sub in zip(planes, boxes, subs)])
+    same = np.array_equal(got, want)
+    print(f"{'ok  ' if same else 'DIFF'} {label}: {p.stdout.strip()}")
+    return same
+
+
+def main():
+    build()
+    good = True
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, (h, w, box, s) in OP_CASES.items():
+            for key, sub in SUBS.items():
+                for colour, (std, full, site) in COLOURS.items():
+                    good &= run(tmp, f"{name} {key} {colour}", [make_yuv(h, w, sub, seed=h + w)], [box], s, N.yuv_matrix(std, full), site, [sub])
+        m = N.yuv_matrix(N.BT709, False)
+        # left siting: an odd width reaches into the half-covered last chroma column, an even one overhangs it by a quarter sample
+        for h, w in ((37, 53), (38, 54), (33, 2), (1, 1)):
+            for key in ("420", "422"):
+                good &= run(tmp, f"left-sited whole frame {h}x{w} {key}", [make_yuv(h, w, SUBS[key], seed=5)], [None], 16, m, N.CHROMA_LEFT, [SUBS[key]])
+        planes = [make_yuv(37, 53, (2, 2), seed=21), make_yuv(42, 31, (2, 1), seed=31), make_yuv(29, 30, (1, 1), seed=41)]
+        boxes, subs = [None, (0.5, 3.0, 29.5, 40.0), None], [(2, 2), (2, 1), (1, 1)]
+        for lay in (dict(pads=(6, 10, 2)), dict(pads=(5, 0, 0), lead=2), dict(pads=(0, 3, 0)), dict(lead=3, gap=7), dict(lead=1, gap=2, pads=(5, 7, 3)),
+                    dict(order="yvu"), dict(gap=64, order="uvy"), dict(lead=5, gap=1, order="vyu", pads=(1, 0, 2))):
+            good &= run(tmp, f"layout {lay}", planes, boxes, 16, m, N.CHROMA_LEFT, subs, **lay)
+        shapes = [(37, 53, "420"), (64, 64, "444"), (20, 24, "422"), (98, 132, "440"), (270, 480, "420"), (1, 1, "420"), (33, 2, "422")]
+        planes = [make_yuv(h, w, SUBS[k], seed=40 + i) for i, (h, w, k) in enumerate(shapes)]
+        boxes = [None, None, (2.0, 1.0, 22.0, 19.5), (10.0, 5.0, 101.0, 96.0), vithip.center_crop_box(270, 480), None, None]
+        good &= run(tmp, "mixed batch of 7", planes, boxes, 32, m, N.CHROMA_LEFT, [SUBS[k] for _, _, k in shapes], lead=1, gap=3)
+        keys = list(SUBS)
+        subs = [SUBS[keys[i % 4]] for i in range(40)]
+        planes = [make_yuv(41, 39, subs[i], seed=100 + i) for i in range(40)]
+        good &= run(tmp, "40 frames of 41x39 (tall bands)", planes, [None if i % 2 else (0.5, 1.0, 38.25, 40.0) for i in range(40)], 32,
+                    N.yuv_matrix(N.BT601, True), N.CHROMA_CENTER, subs)
+        y, uv = make_nv12(1080, 1920, seed=3)
+        good &= run(tmp, "1080x1920 I420 -> 224", [(y, np.ascontiguousarray(uv[..., 0]), np.ascontiguousarray(uv[..., 1]))],
+                    [vithip.center_crop_box(1080, 1920)], 224, m, N.CHROMA_LEFT, [(2, 2)])
+        # the NV12 instantiation: 16-bit UV loads (even offsets and strides) and byte loads (odd), left-sited overhang
+        nv = [make_nv12(38, 54, seed=21), make_nv12(42, 30, seed=31)]
+        for lay in (dict(), dict(y_pad=6, uv_pad=10), dict(lead=1, gap=2, y_pad=5, uv_pad=7), dict(gap=64, uv_first=True)):
+            good &= run(tmp, f"NV12 layout {lay}", nv, [None, (0.5, 3.0, 29.5, 40.0)], 16, m, N.CHROMA_LEFT, None, **lay)
+        for h in planner_boundary_444(130):
+            good &= run(tmp, f"4:4:4 planner boundary, {h}x36 -> 130", [make_yuv(h, 36, (1, 1), seed=7)], [None], 130, m, N.CHROMA_LEFT, [(1, 1)])
+    print("every output equals the fp32 emulation; no sanitizer report" if good else "FAILED")
+    return 0 if good else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

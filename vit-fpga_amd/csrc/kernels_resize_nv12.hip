@@ -18,6 +18,13 @@
 // fit kResizeLdsFloats; the kernel recomputes both row ranges from the tables and does nothing if they would not fit the LDS or
 // either plane (they cannot, short of a corrupted table).  Loads: Y bytes; one 16-bit load per UV pair where uv_offset, uv_stride
 // and the base are even, two bytes otherwise.  Stores: bytes.  No atomics, no work queue, no allocation.
+//
+// PLANAR YUV (include/vithip.h, "Planar YUV frames").  The same body with the chroma source a template parameter:
+// U and V are two byte planes of cw x ch, cw = ceil(width / sub_x), ch = ceil(height / sub_y), sub 1 or 2 per axis, any parity of
+// width and height.  Only the chroma half of the horizontal loop differs (p_u[t] and p_v[t] instead of the pair p[2t], p[2t+1]);
+// the (u, v) pair lies in LDS as above, so the vertical pass, the matrix and the stores are shared.  With sub == 1 on an axis the
+// chroma table of that axis IS the luma table (same key).  The body is a __host__ __device__ function of (block, thread) with the
+// barrier passed in, so that tools/yuv_host_check.hip runs the very same text on the CPU under the sanitizers.
 #include <cmath>
 #include <cstring>
 
@@ -30,13 +37,16 @@ namespace vh {
 // share (length, lo, hi) on an axis share the table: a batch from one decoder builds four tables (luma x, luma y, chroma x,
 // chroma y).
 struct RzNv12 {
-    uint64_t y_off, uv_off;
+    uint64_t y_off, uv_off;        // planar: uv_off = the U plane
     int32_t h, w, y_stride, uv_stride;
     int32_t xt, yt, cxt, cyt;      // word offsets of the tables: luma x, luma y, chroma x, chroma y
     int32_t xs, ys, cxs, cys;      // their weight strides
     int32_t band_rows, tile_cols;
-    int32_t uv16;                  // uv_offset, uv_stride and the base even: one 16-bit load per (U, V) pair
-    int32_t pad[5];
+    int32_t uv16;                  // NV12: uv_offset, uv_stride and the base even: one 16-bit load per (U, V) pair
+    int32_t ch;                    // rows of the chroma plane(s): h / 2 (NV12), ceil(h / sub_y) (planar)
+    uint64_t v_off;                // planar: the V plane, rows v_stride apart
+    int32_t v_stride;
+    int32_t pad;
 };
 static_assert(sizeof(RzNv12) == 4 * kResizeNv12FrameWords, "RzNv12 layout");
 
@@ -63,12 +73,20 @@ int worst_cost(const int32_t* yf, const int32_t* yc, const int32_t* cf, const in
     return worst;
 }
 
-}  // namespace
+// one frame of either layout, checked by its caller: what the shared planner reads
+struct YuvSrc {
+    uint64_t y_off, u_off, v_off;   // NV12: u_off = the UV plane, v_off unused
+    int32_t h, w, cw, ch;           // luma size and the size of the chroma plane(s) in chroma samples
+    int32_t y_stride, u_stride, v_stride;
+    int32_t sub_x, sub_y;
+    int32_t uv16;
+    double box[4];
+};
 
-const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, size_t nbytes, bool base_aligned2, int chroma_site,
-                                   std::vector<uint32_t>* words, int* max_tiles) {
-    if (!desc || batch < 1 || S < 1 || S > 4096) return "resize_nv12: bad batch or output size";
-    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return "resize_nv12: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+// tables, band heights and frame records of one call (both layouts); box_msg: the refusal when a table cannot be built
+const char* plan_frames(const std::vector<YuvSrc>& src, int S, int chroma_site, const char* box_msg, std::vector<uint32_t>* words,
+                        int* max_tiles) {
+    const int batch = (int)src.size();
     std::vector<TableKey> keys;
     std::vector<BandKey> bands;
     std::vector<int32_t> first(S), count(S);
@@ -80,7 +98,7 @@ const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, 
     auto axis = [&](int n, double lo, double hi, double over, TableKey* out) -> const char* {
         for (const TableKey& k : keys)
             if (k.n == n && k.lo == lo && k.hi == hi) { *out = k; return nullptr; }
-        if (resize_axis_table_over(n, lo, hi, over, S, first.data(), count.data(), wts.data(), kResizeMaxTaps)) return "resize_nv12: box outside the frame, empty, or scale > 32";
+        if (resize_axis_table_over(n, lo, hi, over, S, first.data(), count.data(), wts.data(), kResizeMaxTaps)) return box_msg;
         TableKey k{n, lo, hi, (int32_t)words->size(), 1};
         for (int i = 0; i < S; ++i) if (count[i] > k.stride) k.stride = count[i];
         const size_t at = words->size();
@@ -93,22 +111,17 @@ const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, 
         *out = k;
         return nullptr;
     };
-    const double dx = chroma_site == VH_CHROMA_LEFT ? 0.25 : 0.0;
     for (int b = 0; b < batch; ++b) {
-        const vh_frame_nv12& d = desc[b];
-        if (d.width < 2 || d.width > kResizeMaxSide || d.height < 2 || d.height > kResizeMaxSide || d.width % 2 || d.height % 2)
-            return "resize_nv12: width and height must be even and 2..8192";
-        if (d.y_stride < d.width || d.uv_stride < d.width) return "resize_nv12: y_stride or uv_stride < width";
-        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)d.width;
-        const uint64_t cspan = (uint64_t)(d.height / 2 - 1) * (uint64_t)d.uv_stride + (uint64_t)d.width;
-        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return "resize_nv12: a Y plane ends beyond nbytes";
-        if (d.uv_offset > nbytes || cspan > nbytes - d.uv_offset) return "resize_nv12: a UV plane ends beyond nbytes";
-        const double x0 = (double)d.box[0], y0 = (double)d.box[1], x1 = (double)d.box[2], y1 = (double)d.box[3];
+        const YuvSrc& d = src[b];
+        const double x0 = d.box[0], y0 = d.box[1], x1 = d.box[2], y1 = d.box[3];
+        // horizontally sub-sampled, left-sited chroma: sample k sits on luma sample 2k
+        const double dx = d.sub_x == 2 && chroma_site == VH_CHROMA_LEFT ? 0.25 : 0.0;
+        const double sx = (double)d.sub_x, sy = (double)d.sub_y;
         TableKey kx, ky, kcx, kcy;
-        if (const char* e = axis(d.width, x0, x1, 0.0, &kx)) return e;
-        if (const char* e = axis(d.height, y0, y1, 0.0, &ky)) return e;
-        if (const char* e = axis(d.width / 2, x0 / 2.0 + dx, x1 / 2.0 + dx, dx, &kcx)) return e;
-        if (const char* e = axis(d.height / 2, y0 / 2.0, y1 / 2.0, 0.0, &kcy)) return e;
+        if (const char* e = axis(d.w, x0, x1, 0.0, &kx)) return e;
+        if (const char* e = axis(d.h, y0, y1, 0.0, &ky)) return e;
+        if (const char* e = axis(d.cw, x0 / sx + dx, x1 / sx + dx, dx, &kcx)) return e;   // sub == 1: the luma key, the luma table
+        if (const char* e = axis(d.ch, y0 / sy, y1 / sy, 0.0, &kcy)) return e;
         // band height of this pair of vertical tables: the most output rows whose luma + chroma source rows fit the LDS at full
         // width; else one row and fewer columns
         BandKey bk{ky.at, kcy.at, 0, 0};
@@ -121,11 +134,11 @@ const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, 
             const int cost1 = worst_cost(yf, yf + S, cf, cf + S, S, 1);
             if (cost1 > fit) {
                 bk.band_rows = 1;
-                bk.tile_cols = kResizeLdsFloats / cost1;   // >= 1: at most 65 + 2 * 34 floats per column
+                bk.tile_cols = kResizeLdsFloats / cost1;   // >= 1: at most 3 x 65 floats per column (4:4:4 at scale 32)
             } else {
-                // a further output row costs about scale luma rows + 2 x scale / 2 chroma rows
+                // a further output row costs about scale luma rows + 2 x scale / sub_y chroma rows
                 const double scale = (y1 - y0) / S;
-                int kk = (int)((fit - cost1) / (2.0 * (scale > 0.03125 ? scale : 0.03125))) + 1;
+                int kk = (int)((fit - cost1) / ((1.0 + 2.0 / sy) * (scale > 0.03125 ? scale : 0.03125))) + 1;
                 if (kk > S) kk = S;
                 while (kk > 1 && worst_cost(yf, yf + S, cf, cf + S, S, kk) > fit) --kk;
                 // a small batch: at least ~64 workgroups, while bands stay a few rows high
@@ -137,16 +150,84 @@ const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, 
             bands.push_back(bk);
         }
         RzNv12 f{};
-        f.y_off = d.y_offset; f.uv_off = d.uv_offset; f.h = d.height; f.w = d.width; f.y_stride = d.y_stride; f.uv_stride = d.uv_stride;
+        f.y_off = d.y_off; f.uv_off = d.u_off; f.v_off = d.v_off; f.h = d.h; f.w = d.w; f.ch = d.ch;
+        f.y_stride = d.y_stride; f.uv_stride = d.u_stride; f.v_stride = d.v_stride;
         f.xt = kx.at; f.xs = kx.stride; f.yt = ky.at; f.ys = ky.stride;
         f.cxt = kcx.at; f.cxs = kcx.stride; f.cyt = kcy.at; f.cys = kcy.stride;
         f.band_rows = bk.band_rows; f.tile_cols = bk.tile_cols;
-        f.uv16 = base_aligned2 && d.uv_offset % 2 == 0 && d.uv_stride % 2 == 0;
+        f.uv16 = d.uv16;
         memcpy(words->data() + (size_t)b * kResizeNv12FrameWords, &f, sizeof f);
         const int tiles = ((S + f.band_rows - 1) / f.band_rows) * ((S + f.tile_cols - 1) / f.tile_cols);
         if (tiles > *max_tiles) *max_tiles = tiles;
     }
+    return nullptr;
+}
+
+}  // namespace
+
+const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, size_t nbytes, bool base_aligned2, int chroma_site,
+                                   std::vector<uint32_t>* words, int* max_tiles) {
+    if (!desc || batch < 1 || S < 1 || S > 4096) return "resize_nv12: bad batch or output size";
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return "resize_nv12: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+    std::vector<YuvSrc> src((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        const vh_frame_nv12& d = desc[b];
+        if (d.width < 2 || d.width > kResizeMaxSide || d.height < 2 || d.height > kResizeMaxSide || d.width % 2 || d.height % 2)
+            return "resize_nv12: width and height must be even and 2..8192";
+        if (d.y_stride < d.width || d.uv_stride < d.width) return "resize_nv12: y_stride or uv_stride < width";
+        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)d.width;
+        const uint64_t cspan = (uint64_t)(d.height / 2 - 1) * (uint64_t)d.uv_stride + (uint64_t)d.width;
+        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return "resize_nv12: a Y plane ends beyond nbytes";
+        if (d.uv_offset > nbytes || cspan > nbytes - d.uv_offset) return "resize_nv12: a UV plane ends beyond nbytes";
+        YuvSrc& s = src[b];
+        s.y_off = d.y_offset; s.u_off = d.uv_offset; s.v_off = 0;
+        s.h = d.height; s.w = d.width; s.cw = d.width / 2; s.ch = d.height / 2;
+        s.y_stride = d.y_stride; s.u_stride = d.uv_stride; s.v_stride = 0;
+        s.sub_x = 2; s.sub_y = 2;
+        s.uv16 = base_aligned2 && d.uv_offset % 2 == 0 && d.uv_stride % 2 == 0;
+        for (int i = 0; i < 4; ++i) s.box[i] = (double)d.box[i];
+    }
+    if (const char* e = plan_frames(src, S, chroma_site, "resize_nv12: box outside the frame, empty, or scale > 32", words, max_tiles)) return e;
     if ((int64_t)batch * *max_tiles > 0x7fffffffll) return "resize_nv12: too many tiles";
+    return nullptr;
+}
+
+// every refusal of the planar contract has a message of its own, in the order the header lists them
+const char* resize_plan_build_yuv(const vh_frame_yuv* desc, int batch, int S, size_t nbytes, int chroma_site, std::vector<uint32_t>* words,
+                                  int* max_tiles) {
+    if (!desc || batch < 1 || S < 1 || S > 4096) return "resize_yuv: bad batch or output size";
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return "resize_yuv: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+    std::vector<YuvSrc> src((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        const vh_frame_yuv& d = desc[b];
+        if (d.width < 1 || d.width > kResizeMaxSide || d.height < 1 || d.height > kResizeMaxSide)
+            return "resize_yuv: width and height must be 1..8192";
+        if ((d.sub_x != 1 && d.sub_x != 2) || (d.sub_y != 1 && d.sub_y != 2)) return "resize_yuv: sub_x and sub_y must be 1 or 2";
+        const int cw = (d.width + d.sub_x - 1) / d.sub_x, ch = (d.height + d.sub_y - 1) / d.sub_y;
+        if (d.y_stride < d.width) return "resize_yuv: y_stride < width";
+        if (d.u_stride < cw || d.v_stride < cw) return "resize_yuv: u_stride or v_stride < the chroma width, ceil(width / sub_x)";
+        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)d.width;
+        const uint64_t uspan = (uint64_t)(ch - 1) * (uint64_t)d.u_stride + (uint64_t)cw;
+        const uint64_t vspan = (uint64_t)(ch - 1) * (uint64_t)d.v_stride + (uint64_t)cw;
+        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return "resize_yuv: a Y plane ends beyond nbytes";
+        if (d.u_offset > nbytes || uspan > nbytes - d.u_offset) return "resize_yuv: a U plane ends beyond nbytes";
+        if (d.v_offset > nbytes || vspan > nbytes - d.v_offset) return "resize_yuv: a V plane ends beyond nbytes";
+        YuvSrc& s = src[b];
+        for (int i = 0; i < 4; ++i) s.box[i] = (double)d.box[i];
+        // written so that a NaN fails
+        if (!(s.box[0] >= 0.0 && s.box[0] < s.box[2] && s.box[2] <= (double)d.width && s.box[1] >= 0.0 && s.box[1] < s.box[3] &&
+              s.box[3] <= (double)d.height))
+            return "resize_yuv: box outside the frame, or empty";
+        if (!((s.box[2] - s.box[0]) / (double)S <= (double)kResizeMaxScale && (s.box[3] - s.box[1]) / (double)S <= (double)kResizeMaxScale))
+            return "resize_yuv: scale > 32 on an axis";
+        s.y_off = d.y_offset; s.u_off = d.u_offset; s.v_off = d.v_offset;
+        s.h = d.height; s.w = d.width; s.cw = cw; s.ch = ch;
+        s.y_stride = d.y_stride; s.u_stride = d.u_stride; s.v_stride = d.v_stride;
+        s.sub_x = d.sub_x; s.sub_y = d.sub_y;
+        s.uv16 = 0;
+    }
+    if (const char* e = plan_frames(src, S, chroma_site, "resize_yuv: a table of the box could not be built", words, max_tiles)) return e;
+    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return "resize_yuv: too many tiles";
     return nullptr;
 }
 
@@ -154,19 +235,21 @@ const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, 
 struct Nv12Matrix { float m[12]; };
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
-__device__ __forceinline__ uint32_t nv12_byte(float v) { return (uint32_t)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
+__host__ __device__ __forceinline__ uint32_t nv12_byte(float v) { return (uint32_t)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
 
-__global__ void __launch_bounds__(256)
-resize_nv12_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan, uint8_t* __restrict__ out, int S, int max_tiles,
-                   Nv12Matrix mat) {
-    __shared__ __attribute__((aligned(16))) float lds[kResizeLdsFloats];
-    const int f = blockIdx.x / max_tiles, tile = blockIdx.x - f * max_tiles;
+// The work of thread `tid` of workgroup `block`.  PLANAR: U and V are two byte planes, else one plane of (U, V) pairs.  `barrier`
+// is __syncthreads() on the device; every return in front of it is taken by the whole workgroup.
+template <bool PLANAR, class Barrier>
+__host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan,
+                                                         uint8_t* __restrict__ out, int S, int max_tiles, const Nv12Matrix& mat, float* lds,
+                                                         int block, int tid, Barrier barrier) {
+    const int f = block / max_tiles, tile = block - f * max_tiles;
     const RzNv12 d = *(const RzNv12*)(plan + (size_t)f * kResizeNv12FrameWords);
     const int nc = (S + d.tile_cols - 1) / d.tile_cols, nb = (S + d.band_rows - 1) / d.band_rows;
     if (tile >= nb * nc) return;
     const int band = tile / nc;
-    const int r0 = band * d.band_rows, r1 = min(r0 + d.band_rows, S);
-    const int c0 = (tile - band * nc) * d.tile_cols, c1 = min(c0 + d.tile_cols, S);
+    const int r0 = band * d.band_rows, r1 = r0 + d.band_rows < S ? r0 + d.band_rows : S;
+    const int c0 = (tile - band * nc) * d.tile_cols, c1 = c0 + d.tile_cols < S ? c0 + d.tile_cols : S;
     const int32_t* xfirst = (const int32_t*)(plan + d.xt);
     const int32_t* xcount = xfirst + S;
     const float* xw = (const float*)(xcount + S);
@@ -181,18 +264,18 @@ resize_nv12_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restric
     const float* cyw = (const float*)(cycount + S);
     int ylo = yfirst[r0], yhi = ylo + ycount[r0], clo = cyfirst[r0], chi = clo + cycount[r0];
     for (int r = r0 + 1; r < r1; ++r) {
-        ylo = min(ylo, yfirst[r]);
-        yhi = max(yhi, yfirst[r] + ycount[r]);
-        clo = min(clo, cyfirst[r]);
-        chi = max(chi, cyfirst[r] + cycount[r]);
+        ylo = yfirst[r] < ylo ? yfirst[r] : ylo;
+        yhi = yfirst[r] + ycount[r] > yhi ? yfirst[r] + ycount[r] : yhi;
+        clo = cyfirst[r] < clo ? cyfirst[r] : clo;
+        chi = cyfirst[r] + cycount[r] > chi ? cyfirst[r] + cycount[r] : chi;
     }
     const int rows_y = yhi - ylo, rows_c = chi - clo, cols = c1 - c0;
-    if ((rows_y + 2 * rows_c) * cols > kResizeLdsFloats || ylo < 0 || yhi > d.h || clo < 0 || chi > d.h / 2) return;
+    if ((rows_y + 2 * rows_c) * cols > kResizeLdsFloats || ylo < 0 || yhi > d.h || clo < 0 || chi > d.ch) return;
     float* ldc = lds;                             // [rows_c][cols][2]
     float* ldy = lds + 2 * rows_c * cols;         // [rows_y][cols]
     const uint8_t* ysrc = frames + d.y_off;
     const uint8_t* csrc = frames + d.uv_off;
-    const int tid = threadIdx.x;
+    const uint8_t* vsrc = frames + d.v_off;       // PLANAR only
 
     // horizontal pass: luma rows ylo .. yhi-1 and chroma rows clo .. chi-1, output columns c0 .. c1-1
     const int ny = rows_y * cols, nuv = rows_c * cols;
@@ -210,26 +293,36 @@ resize_nv12_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restric
             const int y = ec / cols, x = c0 + (ec - y * cols);
             const int n = cxcount[x];
             const float* w = cxw + (size_t)x * d.cxs;
-            const uint8_t* p = csrc + (size_t)(clo + y) * d.uv_stride + (size_t)cxfirst[x] * 2;
             float u = 0.f, v = 0.f;
-            if (d.uv16) {
+            if constexpr (PLANAR) {
+                const uint8_t* pu = csrc + (size_t)(clo + y) * d.uv_stride + cxfirst[x];
+                const uint8_t* pv = vsrc + (size_t)(clo + y) * d.v_stride + cxfirst[x];
                 for (int t = 0; t < n; ++t) {
-                    const uint32_t q = *(const uint16_t*)(p + 2 * t);
                     const float wt = w[t];
-                    u = __builtin_fmaf(wt, (float)(q & 0xffu), u);
-                    v = __builtin_fmaf(wt, (float)(q >> 8), v);
+                    u = __builtin_fmaf(wt, (float)pu[t], u);
+                    v = __builtin_fmaf(wt, (float)pv[t], v);
                 }
             } else {
-                for (int t = 0; t < n; ++t) {
-                    const float wt = w[t];
-                    u = __builtin_fmaf(wt, (float)p[2 * t], u);
-                    v = __builtin_fmaf(wt, (float)p[2 * t + 1], v);
+                const uint8_t* p = csrc + (size_t)(clo + y) * d.uv_stride + (size_t)cxfirst[x] * 2;
+                if (d.uv16) {
+                    for (int t = 0; t < n; ++t) {
+                        const uint32_t q = *(const uint16_t*)(p + 2 * t);
+                        const float wt = w[t];
+                        u = __builtin_fmaf(wt, (float)(q & 0xffu), u);
+                        v = __builtin_fmaf(wt, (float)(q >> 8), v);
+                    }
+                } else {
+                    for (int t = 0; t < n; ++t) {
+                        const float wt = w[t];
+                        u = __builtin_fmaf(wt, (float)p[2 * t], u);
+                        v = __builtin_fmaf(wt, (float)p[2 * t + 1], v);
+                    }
                 }
             }
             *(f32x2*)(ldc + (size_t)ec * 2) = f32x2{u, v};
         }
     }
-    __syncthreads();
+    barrier();
 
     // vertical pass of both planes out of LDS, the matrix, three bytes per pixel
     for (int e = tid; e < (r1 - r0) * cols; e += 256) {
@@ -261,15 +354,39 @@ resize_nv12_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restric
     }
 }
 
-hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
-                              uint8_t* out, hipStream_t s) {
+#ifndef VH_HOST_CHECK   // tools/yuv_host_check.hip takes the planner and the body above and no device code
+template <bool PLANAR>
+__global__ void __launch_bounds__(256)
+resize_yuv_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan, uint8_t* __restrict__ out, int S, int max_tiles,
+                  Nv12Matrix mat) {
+    __shared__ __attribute__((aligned(16))) float lds[kResizeLdsFloats];
+    resize_yuv_body<PLANAR>(frames, plan, out, S, max_tiles, mat, lds, (int)blockIdx.x, (int)threadIdx.x, [] { __syncthreads(); });
+}
+
+static hipError_t launch_resize_any(bool planar, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
+                                    const float* m12, uint8_t* out, hipStream_t s) {
     if (!frames || !plan_dev || !out || !m12 || batch < 1 || S < 1 || max_tiles < 1 || (int64_t)batch * max_tiles > 0x7fffffffll)
         return hipErrorInvalidValue;
     Nv12Matrix mat;
     memcpy(mat.m, m12, sizeof mat.m);
-    hipLaunchKernelGGL(resize_nv12_kernel, dim3((unsigned)(batch * max_tiles)), dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    const dim3 grid((unsigned)(batch * max_tiles));
+    if (planar)
+        hipLaunchKernelGGL(resize_yuv_kernel<true>, grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    else
+        hipLaunchKernelGGL(resize_yuv_kernel<false>, grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     return hipGetLastError();
 }
+
+hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
+                              uint8_t* out, hipStream_t s) {
+    return launch_resize_any(false, frames, plan_dev, batch, S, max_tiles, m12, out, s);
+}
+
+hipError_t launch_resize_yuv(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
+                             uint8_t* out, hipStream_t s) {
+    return launch_resize_any(true, frames, plan_dev, batch, S, max_tiles, m12, out, s);
+}
+#endif
 
 // ---- host: the colour matrix -----------------------------------------------------------------------------------------------
 // Every expression is written as include/vithip.h states it and evaluated in IEEE double with no contraction, so that a numpy

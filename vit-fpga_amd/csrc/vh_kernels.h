@@ -138,6 +138,13 @@ const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, 
 hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12_host,
                               uint8_t* out_u8, hipStream_t stream);
 int yuv_matrix(int standard, int full_range, float m[12]);
+// Planar YUV frames (the same file and kernel body; contract: vithip.h, "Planar YUV frames"): three byte planes, chroma
+// sub-sampled by 1 or 2 per axis, any parity of the luma size.  resize_plan_build_yuv: as resize_plan_build_nv12, the same record
+// and tables; every refusal has a message of its own.  launch_resize_yuv: the planar instantiation of the kernel.
+const char* resize_plan_build_yuv(const vh_frame_yuv* desc, int batch, int S, size_t nbytes, int chroma_site, std::vector<uint32_t>* words,
+                                  int* max_tiles);
+hipError_t launch_resize_yuv(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12_host,
+                             uint8_t* out_u8, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
 bool patch_fused_supported(int image, int patch, int channels, int dim);

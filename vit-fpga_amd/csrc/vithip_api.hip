@@ -253,8 +253,8 @@ struct vh_ctx {
     uint8_t* rz_frames = nullptr;
     size_t rz_frames_cap = 0;
     std::vector<uint32_t> rz_words;
-    // NV12 frames (vh_set_frame_colour): the 3 x 4 matrix and the chroma siting of the NV12 entry points.  The matrix travels to
-    // resize_nv12_kernel by value at each launch, outside any captured graph.
+    // NV12 and planar YUV frames (vh_set_frame_colour): the 3 x 4 matrix and the chroma siting of both kinds of entry points.  The
+    // matrix travels to resize_yuv_kernel by value at each launch, outside any captured graph.
     float nv12_m[12];
     int nv12_site = VH_CHROMA_LEFT;
     int64_t last_us = 0;
@@ -957,12 +957,13 @@ int check_u8_ptr(vh_ctx* c, const void* in_dev) {
 
 // ---- 8-bit frames: plan, buffers, the resize launch ---------------------------------------------------------------------------
 // One resize in front of a forward: the frames in HBM and the descriptors + tables (c->rz_words) in pinned memory.
+enum { FRAMES_RGB = 0, FRAMES_NV12 = 1, FRAMES_YUV = 2 };
 struct FrameJob {
     const uint8_t* frames_dev;
     const uint32_t* plan_host;   // pinned; stays untouched until the upload below has run
     size_t words;
     int max_tiles;
-    bool nv12 = false;           // NV12 frames: the plan of resize_plan_build_nv12, run by resize_nv12_kernel with the context's matrix
+    int kind = FRAMES_RGB;       // FRAMES_NV12 / FRAMES_YUV: the plan of resize_plan_build_nv12 / _yuv, run by resize_yuv_kernel with the context's matrix
 };
 
 // checks the descriptors of one call and builds its plan in c->rz_words; nothing is enqueued
@@ -977,6 +978,14 @@ int frames_plan_nv12(vh_ctx* c, const vh_frame_nv12* desc, int batch, size_t nby
     if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
     if (c->cfg.channels != 3) return fail(&c->err, VH_ERR_INVALID, "NV12 frames need a model with 3 channels, this one has %d", c->cfg.channels);
     const char* why = resize_plan_build_nv12(desc, batch, c->cfg.image_size, nbytes, base_aligned2, c->nv12_site, &c->rz_words, max_tiles);
+    if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
+    return VH_OK;
+}
+
+int frames_plan_yuv(vh_ctx* c, const vh_frame_yuv* desc, int batch, size_t nbytes, int* max_tiles) {
+    if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
+    if (c->cfg.channels != 3) return fail(&c->err, VH_ERR_INVALID, "planar YUV frames need a model with 3 channels, this one has %d", c->cfg.channels);
+    const char* why = resize_plan_build_yuv(desc, batch, c->cfg.image_size, nbytes, c->nv12_site, &c->rz_words, max_tiles);
     if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
     return VH_OK;
 }
@@ -1029,8 +1038,10 @@ int enqueue_resize(vh_ctx* c, const FrameJob& j, int batch) {
     int rc;
     HIPCHK(&c->err, hipMemcpyAsync(c->rz_plan_dev, j.plan_host, j.words * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = tmark())) return rc;
-    if (j.nv12)
+    if (j.kind == FRAMES_NV12)
         HIPCHK(&c->err, launch_resize_nv12(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->nv12_m, c->rz_u8, c->stream));
+    else if (j.kind == FRAMES_YUV)
+        HIPCHK(&c->err, launch_resize_yuv(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->nv12_m, c->rz_u8, c->stream));
     else
         HIPCHK(&c->err, launch_resize_u8(j.frames_dev, c->rz_plan_dev, batch, c->cfg.channels, c->cfg.image_size, j.max_tiles, c->rz_u8, c->stream));
     return tmark();
@@ -1656,7 +1667,7 @@ int vh_forward_device_frames_nv12(vh_ctx* c, const uint8_t* frames_dev, size_t n
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, true};
+    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_NV12};
     return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
 }
 
@@ -1668,7 +1679,32 @@ int vh_forward_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nbytes,
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, true};
+    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_NV12};
+    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+}
+
+// planar YUV frames: the same two entry points with the plan of resize_plan_build_yuv
+int vh_forward_device_frames_yuv(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev) {
+    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_YUV};
+    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+}
+
+int vh_forward_frames_yuv(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host) {
+    int rc = check_forward_args(c, frames_host, batch, logits_host);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_YUV};
     return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
 }
 
@@ -1890,9 +1926,10 @@ int vh_ring_input_frames(vh_ctx* c, uint8_t** pinned, size_t* capacity) {
 
 // frames ring: in_host holds `frame_bytes` of frames described by `desc`; the slot's upload is followed by the resize into
 // c->rz_u8 on the context's stream (forwards are ordered on that stream, so one resized buffer serves every slot)
-// (desc12: the submit carries NV12 frames instead; a slot is raw bytes, so one frames ring takes both)
-static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const vh_frame* desc = nullptr,
-                       const vh_frame_nv12* desc12 = nullptr, bool nv12 = false) {
+// (fkind FRAMES_NV12 / FRAMES_YUV: `desc` points to vh_frame_nv12 / vh_frame_yuv descriptors instead; a slot is raw bytes, so one
+// frames ring takes all three)
+static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const void* desc = nullptr,
+                       int fkind = FRAMES_RGB) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "no ring: call vh_ring_create first");
     if (c->ring_kind != kind) return fail(&c->err, VH_ERR_STATE, "this ring stages %s", ring_kind_name(c->ring_kind));
@@ -1903,7 +1940,10 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     int rc, max_tiles = 0;
     if (frames) {   // every check, and the plan, before anything is enqueued or the slot is touched
         if (frame_bytes < 1 || frame_bytes > c->ring_slot_bytes) return fail(&c->err, VH_ERR_INVALID, "nbytes %zu outside 1..slot_bytes=%zu", frame_bytes, c->ring_slot_bytes);
-        if ((rc = nv12 ? frames_plan_nv12(c, desc12, batch, frame_bytes, true, &max_tiles) : frames_plan(c, desc, batch, frame_bytes, true, &max_tiles))) return rc;
+        if (fkind == FRAMES_NV12) rc = frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, frame_bytes, true, &max_tiles);
+        else if (fkind == FRAMES_YUV) rc = frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, frame_bytes, &max_tiles);
+        else rc = frames_plan(c, (const vh_frame*)desc, batch, frame_bytes, true, &max_tiles);
+        if (rc) return rc;
     }
     HIPCHK(&c->err, hipSetDevice(c->device));
     vh_ctx::RingSlot& s = c->ring[c->ring_wr];
@@ -1925,7 +1965,7 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     HIPCHK(&c->err, hipEventRecord(s.in_done, c->copy_in));
     HIPCHK(&c->err, hipStreamWaitEvent(c->stream, s.in_done, 0));
     if (frames) {
-        const FrameJob job{(const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles, nv12};
+        const FrameJob job{(const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles, fkind};
         if ((rc = enqueue_resize(c, job, batch))) return rc;
     }
     rc = run_step(c, frames ? ImgIn{c->rz_u8, true} : ImgIn{s.d_in, kind == vh_ctx::RING_U8}, batch, s.d_out);
@@ -1945,7 +1985,10 @@ int vh_ring_submit_frames(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, 
     return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc);
 }
 int vh_ring_submit_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch) {
-    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, nullptr, desc, true);
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_NV12);
+}
+int vh_ring_submit_frames_yuv(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_YUV);
 }
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
@@ -2348,6 +2391,27 @@ int vh_op_resize_nv12(const uint8_t* frames, size_t nbytes, const vh_frame_nv12*
     OPCHK(hipMalloc((void**)&plan, words.size() * 4));
     hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e == hipSuccess) e = launch_resize_nv12(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream);
+    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(plan);
+    OPCHK(e);
+    OPCHK(es);
+    return VH_OK;
+}
+
+int vh_op_resize_yuv(const uint8_t* frames, size_t nbytes, const vh_frame_yuv* desc, int batch, int out_size, const float* m12,
+                     int chroma_site, uint8_t* out, void* stream) {
+    // every check before a device is touched
+    if (!frames || !desc || !m12 || !out) return fail(nullptr, VH_ERR_INVALID, "resize_yuv: null buffer");
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "resize_yuv: colour matrix entry %d is not finite", i);
+    std::vector<uint32_t> words;
+    int max_tiles = 0;
+    if (const char* why = resize_plan_build_yuv(desc, batch, out_size, nbytes, chroma_site, &words, &max_tiles))
+        return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    uint32_t* plan = nullptr;
+    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
+    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = launch_resize_yuv(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream);
     const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
     hipFree(plan);
     OPCHK(e);

@@ -55,6 +55,14 @@ class FrameNV12(C.Structure):
                 ("y_stride", C.c_int32), ("uv_stride", C.c_int32), ("box", C.c_float * 4)]
 
 
+class FrameYUV(C.Structure):
+    """vh_frame_yuv: one planar YUV frame (three byte planes; chroma sub-sampled by sub_x, sub_y = 1 or 2) inside the buffer of a
+    call, and the box (in luma pixels) to resample to image_size^2.  72 bytes."""
+    _fields_ = [("y_offset", C.c_uint64), ("u_offset", C.c_uint64), ("v_offset", C.c_uint64), ("height", C.c_int32),
+                ("width", C.c_int32), ("y_stride", C.c_int32), ("u_stride", C.c_int32), ("v_stride", C.c_int32),
+                ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("box", C.c_float * 4), ("reserved", C.c_int32)]
+
+
 CHROMA_CENTER, CHROMA_LEFT = 0, 1          # vh_set_frame_colour / vh_op_resize_nv12: JPEG / MPEG-1 siting, MPEG-2 / H.264 / HEVC siting
 YUV_BT601, YUV_BT709, YUV_BT2020 = 0, 1, 2  # vh_yuv_matrix
 
@@ -99,6 +107,8 @@ SYMBOLS = {
     "vh_get_frame_colour": (_i, [_vp, _vp, _pi]),
     "vh_forward_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_device_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_frames_yuv": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_yuv": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_fill_input_seeded": (_i, [_vp, _u64, _i, _vp]),
     "vh_last_forward_us": (_i, [_vp, C.POINTER(_i64)]),
     "vh_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
@@ -128,6 +138,7 @@ SYMBOLS = {
     "vh_ring_input_frames": (_i, [_vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(_sz)]),
     "vh_ring_submit_frames": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_ring_submit_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_yuv": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_set_graph": (_i, [_vp, _i]),
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
@@ -159,6 +170,7 @@ SYMBOLS = {
     "vh_op_im2col_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "vh_op_resize_u8": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp]),
     "vh_op_resize_nv12": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "vh_op_resize_yuv": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -365,6 +377,51 @@ def pack_frames_nv12(planes, boxes=None):
         desc[i].box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(v) for v in box)
         parts += [np.ascontiguousarray(y).reshape(-1), np.ascontiguousarray(uv).reshape(-1)]
         off += h * w + h * w // 2
+    return np.concatenate(parts), desc
+
+
+def yuv_subsampling(y_shape, u_shape, v_shape):
+    """(sub_x, sub_y) of a (Y, U, V) triple of plane shapes under the ceiling rule cw = ceil(W / sub_x), ch = ceil(H / sub_y), or
+    ValueError.  Where a side is so short that both factors give the same chroma size (1 -> 1) the answer is 1."""
+    (h, w), sub = y_shape, []
+    if tuple(u_shape) != tuple(v_shape):
+        raise ValueError(f"U is {tuple(u_shape)}, V is {tuple(v_shape)}: the chroma planes differ in size")
+    for n, c, name in ((w, u_shape[1], "width"), (h, u_shape[0], "height")):
+        s = 1 if c == n else 2 if c == (n + 1) // 2 else 0
+        if not s:
+            raise ValueError(f"luma {name} {n} with chroma {name} {c}: neither {n} (sub 1) nor {(n + 1) // 2} (sub 2)")
+        sub.append(s)
+    return sub[0], sub[1]
+
+
+def pack_frames_yuv(planes, boxes=None):
+    """A list of (Y [H, W], U [ch, cw], V [ch, cw]) uint8 triples -> (one uint8 buffer, the (FrameYUV * n) descriptors).  The
+    sub-sampling of each frame is inferred from the shapes (yuv_subsampling) and an inconsistent triple is refused.  Each frame
+    lies as a decoder writes I420: Y, U, V, rows unpadded, frames back to back.  boxes: one (x0, y0, x1, y1) per frame in luma
+    pixels, None = the whole frame."""
+    planes = [tuple(np.asarray(p) for p in t) for t in planes]
+    if boxes is None:
+        boxes = [None] * len(planes)
+    if not planes or len(boxes) != len(planes):
+        raise ValueError("pack_frames_yuv: one box (or None) per frame, at least one frame")
+    desc = (FrameYUV * len(planes))()
+    parts, off = [], 0
+    for i, (t, box) in enumerate(zip(planes, boxes)):
+        if len(t) != 3 or any(p.dtype != np.uint8 or p.ndim != 2 or p.size == 0 for p in t):
+            raise TypeError(f"pack_frames_yuv: frame {i} is not a (Y, U, V) triple of 2-d uint8 arrays")
+        y, u, v = t
+        try:
+            sx, sy = yuv_subsampling(y.shape, u.shape, v.shape)
+        except ValueError as e:
+            raise ValueError(f"pack_frames_yuv: frame {i}: {e}") from None
+        h, w = y.shape
+        ch, cw = u.shape
+        d = desc[i]
+        d.y_offset, d.u_offset, d.v_offset = off, off + h * w, off + h * w + ch * cw
+        d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, w, cw, cw, sx, sy
+        d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
+        parts += [np.ascontiguousarray(p).reshape(-1) for p in (y, u, v)]
+        off += h * w + 2 * ch * cw
     return np.concatenate(parts), desc
 
 
@@ -671,6 +728,23 @@ class VitContext:
     def forward_device_frames_nv12(self, frames_ptr, nbytes, desc, out_ptr):
         _check(lib().vh_forward_device_frames_nv12(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
 
+    # ---- planar YUV frames (I420 / YV12, JPEG's 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0 planes): the same, from three planes ----
+    def forward_frames_yuv(self, planes, boxes=None):
+        """planes: a list of (Y [H, W], U [ch, cw], V [ch, cw]) uint8 triples, any sizes and sub-samplings; boxes as
+        forward_frames, in luma pixels.  The colour matrix and siting are set_frame_colour's (a JPEG caller sets
+        yuv_matrix(YUV_BT601, True) with CHROMA_CENTER).  Returns the bits forward_u8 gives for op_resize_yuv's output."""
+        buf, desc = pack_frames_yuv(planes, boxes)
+        return self.forward_frames_yuv_packed(buf, desc)
+
+    def forward_frames_yuv_packed(self, buf, desc):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
+        _check(lib().vh_forward_frames_yuv(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
+        return out
+
+    def forward_device_frames_yuv(self, frames_ptr, nbytes, desc, out_ptr):
+        _check(lib().vh_forward_device_frames_yuv(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
 
@@ -752,6 +826,19 @@ class VitContext:
             buf = np.ascontiguousarray(buf, dtype=np.uint8)
             ptr = buf.ctypes.data
         _check(lib().vh_ring_submit_frames_nv12(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+
+    def ring_submit_frames_yuv(self, planes, boxes=None):
+        """Planar YUV frames into the next slot of a frames ring; RGB, NV12 and planar submits may alternate."""
+        buf, desc = pack_frames_yuv(planes, boxes)
+        self.ring_submit_frames_yuv_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_yuv_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
+        ptr = None
+        if buf is not None:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            ptr = buf.ctypes.data
+        _check(lib().vh_ring_submit_frames_yuv(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
 
     def ring_free_slots(self):
         n = C.c_int(0)
@@ -1096,6 +1183,15 @@ def op_resize_u8(frames_ptr, nbytes, desc, channels, out_size, out_ptr):
     """The resize of the frames entry points on its own: the frames at frames_ptr (device, any alignment) described by the
     (Frame * n) array desc -> [n, out_size, out_size, channels] bytes at out_ptr."""
     _check(lib().vh_op_resize_u8(frames_ptr, nbytes, C.addressof(desc), len(desc), channels, out_size, out_ptr, None))
+
+
+def op_resize_yuv(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """The resize + colour conversion of the planar YUV entry points on its own: the planes at frames_ptr (device, any alignment)
+    described by the (FrameYUV * n) array desc -> [n, out_size, out_size, 3] bytes at out_ptr.  m: 12 floats, row-major 3 x 4."""
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+    if m.size != 12:
+        raise ValueError(f"op_resize_yuv: expected 12 matrix entries, got {m.size}")
+    _check(lib().vh_op_resize_yuv(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
 
 
 def op_resize_nv12(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
