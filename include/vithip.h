@@ -365,6 +365,70 @@ typedef struct vh_frame_yuv {
 } vh_frame_yuv;
 int vh_forward_frames_yuv(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host);
 int vh_forward_device_frames_yuv(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev);
+/* ---- 16-bit YUV frames: P010 / P012 / P016 and planar yuv4xxpNNle ----------------------------------------------------------
+ * What a 10-bit stream decodes to.  HEVC Main10, AV1 and VP9 profile 2 come out of VCN (rocDecode, VA-API) as P010: NV12's
+ * layout with 16-bit little-endian words, the code in the HIGH bits.  Software decoders (ffmpeg's yuv420p10le, yuv422p10le,
+ * yuv444p12le; dav1d, libde265) emit the planar equivalent with the code in the LOW bits.  A 16-BIT FRAME is an NV12 frame
+ * (vh_frame_nv12) or a planar frame (vh_frame_yuv) whose samples are 16-bit little-endian words; both descriptor structs are
+ * reused unchanged:
+ *       width, height, sub_x, sub_y and box count SAMPLES, as in the 8-bit layouts;
+ *       every *_offset and *_stride is in BYTES and must be even;
+ *       y_stride >= 2 * width; semi-planar: uv_stride >= 2 * width (a chroma row holds width / 2 pairs of 4 bytes); planar:
+ *       u_stride >= 2 * cw and v_stride >= 2 * cw;
+ *       the last byte of each plane lies within nbytes;
+ *       a DEVICE frames pointer must be 2-byte aligned; a host pointer may have any alignment, because it is copied.
+ * Parity and size rules are those of the 8-bit layout: semi-planar needs even sizes within 2..8192, planar takes any parity
+ * within 1..8192.  Big-endian words and packed formats (Y210, Y410, v210) are not taken.
+ * SAMPLE VALUES.  The word enters the arithmetic AS IS, as the fp32 value of the unsigned integer 0..65535 (exact).  The kernel
+ * does not shift, mask or scale: depth and alignment live in the matrix alone.  A P010 word with non-zero low bits is simply a
+ * P016 value.
+ * RESAMPLING and CONVERSION are those of "NV12 frames" and "Planar YUV frames", word for word: the same axis tables
+ * (vh_resize_table) and the same chroma boxes and siting rule; horizontal then vertical fp32 fmaf chains in ascending tap order
+ * from 0, nothing rounded in between; the same nested-fmaf matrix expression; the byte is rintf(min(max(out[k], 0), 255)).
+ * The output is still an S x S x 3 BYTE image, and from there on the forward IS vh_forward_u8: the logits are BIT-IDENTICAL
+ * to feeding vh_op_resize_p016's / vh_op_resize_yuv16's output to the u8 entry point.  Scaling by a power of two commutes with
+ * every rounding of the chain, so a P010 frame holding (byte << 8) under the default 16-bit state gives the bytes of the NV12
+ * frame under the default 8-bit state.
+ * TRANSFER FUNCTIONS are not part of this: a PQ or HLG stream is converted with the linear matrix, as swscale does without a
+ * tone-mapping filter.  Top-left siting (BT.2020's vertical 0.25 offset) is not offered either; VH_CHROMA_* is unchanged.
+ *   vh_yuv_matrix16     host only, no device.  standard and full_range as in vh_yuv_matrix; bits 8..16; msb_aligned 0 or 1
+ *                       (P010, P012 and P016: 1; yuv4xxpNNle: 0); anything else is VH_ERR_INVALID.  Evaluated in double, no
+ *                       contraction, in exactly this order, each entry then rounded once to fp32 (kr, kb as in vh_yuv_matrix):
+ *                           kg  = 1.0 - kr - kb
+ *                           a   = msb_aligned ? 2^(16 - bits) : 1.0                   (word = code * a)
+ *                           q   = 2^(bits - 8)
+ *                           limited range:  sy = 255.0 / (219.0 * q * a), sc = 255.0 / (224.0 * q * a), oy = 16.0 * q * a
+ *                           full range:     sy = sc = 255.0 / ((2^bits - 1.0) * a),   oy = 0.0
+ *                           mid = 2^(bits - 1) * a
+ *                           rv = 2.0 * (1.0 - kr) * sc
+ *                           bu = 2.0 * (1.0 - kb) * sc
+ *                           gu = -(2.0 * kb * (1.0 - kb) / kg) * sc
+ *                           gv = -(2.0 * kr * (1.0 - kr) / kg) * sc
+ *                           yo = -(sy * oy)
+ *                           m  = { sy, 0.0, rv, yo - mid * rv,
+ *                                  sy, gu,  gv, yo - mid * gu - mid * gv,
+ *                                  sy, bu, 0.0, yo - mid * bu }
+ *                       bits = 8, msb_aligned = 0 gives vh_yuv_matrix bit for bit; the limited-range bits = 10, msb_aligned = 1
+ *                       matrix is the 8-bit one with its first three columns multiplied by 2^-8, bit for bit.
+ *   vh_set_frame_colour16, vh_get_frame_colour16: a SECOND colour state, for the 16-bit entry points alone, under the rules of
+ *                       vh_set_frame_colour (one frames ring interleaves 8-bit and 16-bit submits, so one matrix cannot serve
+ *                       both).  Default, and what m = NULL restores: BT.709 limited range, 10 bits, MSB-aligned, left siting:
+ *                       P010 as VCN writes it.  The two states do not touch each other.
+ *   vh_forward_frames_p016, vh_forward_device_frames_p016: vh_forward_frames_nv12 / vh_forward_device_frames_nv12 for
+ *                       semi-planar 16-bit frames (P010, P012, P016), the same argument list.
+ *   vh_forward_frames_yuv16, vh_forward_device_frames_yuv16: vh_forward_frames_yuv / vh_forward_device_frames_yuv for planar
+ *                       16-bit frames.  Stage "resize" of vh_set_stage_timing times these launches too; the resize runs before
+ *                       the fork of vh_set_streams and outside the captured graph.
+ * REFUSED with VH_ERR_INVALID before a device is touched or anything is enqueued, each with a message of its own: an odd offset;
+ * an odd stride; a stride below the byte widths above; a plane whose last byte lies beyond nbytes; an odd device frames pointer;
+ * and every refusal of the 8-bit twin (sizes, sub_x / sub_y, box, scale > 32, channels != 3, null pointers). */
+int vh_yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, float m[12]);
+int vh_set_frame_colour16(vh_ctx* ctx, const float m[12], int chroma_site);
+int vh_get_frame_colour16(const vh_ctx* ctx, float m[12], int* chroma_site);
+int vh_forward_frames_p016(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_host);
+int vh_forward_device_frames_p016(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev);
+int vh_forward_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host);
+int vh_forward_device_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev);
 /* uniform[-1,1) synthetic images written straight into HBM (value range of the reference,
  * def/defines.h:11-12) */
 int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_dev);
@@ -413,6 +477,12 @@ int vh_ring_submit_frames_nv12(vh_ctx* ctx, const uint8_t* frames_host, size_t n
  * The context must have channels == 3.  Checked and copied before anything is enqueued; a refused submit leaves the ring as it
  * was; VH_ERR_STATE on the other two kinds of ring.  A collected batch has the bits vh_forward_frames_yuv returns. */
 int vh_ring_submit_frames_yuv(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch);
+/* 16-bit YUV frames ("16-bit YUV frames" above) on the SAME frames ring: RGB, NV12, planar, P016 and planar 16-bit submits
+ * interleave on one ring; the 16-bit ones use the second colour state.  The same rules: checked and copied before anything is
+ * enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other two kinds of ring.  A collected batch has the
+ * bits vh_forward_frames_p016 / vh_forward_frames_yuv16 returns. */
+int vh_ring_submit_frames_p016(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch);
+int vh_ring_submit_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -606,6 +676,12 @@ int vh_op_resize_nv12(const uint8_t* frames_dev, size_t nbytes, const vh_frame_n
  * Every argument and descriptor is checked before a device is touched. */
 int vh_op_resize_yuv(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc_host, int batch, int out_size,
                      const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
+/* The same two taps for 16-bit samples ("16-bit YUV frames"): the arguments of their 8-bit twins; frames_dev must be 2-byte
+ * aligned, offsets and strides even.  Every argument and descriptor is checked before a device is touched. */
+int vh_op_resize_p016(const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc_host, int batch, int out_size,
+                      const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
+int vh_op_resize_yuv16(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc_host, int batch, int out_size,
+                       const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,

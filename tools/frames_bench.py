@@ -24,6 +24,14 @@ inside the boxes.  Written to <out>/nv12_host_path.txt and .json.
 Planar passes, ViT-B/16 bf16, in ONE process: the frames ring fed NV12 frames -- the yardstick, it moves the same
 bytes -- against the frames ring fed the I420 (yuv420p) planes of the same pictures, the same two shapes, boxes, passes and medians;
 the two rings compute the same logits, which is checked.  Written to <out>/yuv_planar_host_path.txt and .json.
+
+  python tools/frames_bench.py --p010 [--out profiles] [--steps 30] [--passes 3]
+
+10-bit passes, ViT-B/16 bf16, in ONE process: the frames ring fed RGB frames, the frames ring fed the NV12 frames of
+the same pictures and the frames ring fed their P010 frames (10-bit code = 8-bit code x 4, in the high bits of the word: byte << 8),
+the same two shapes, boxes, passes and medians.  P010 uploads 3 bytes per pixel, as RGB does and twice what NV12 does.  Under the two
+default colour states the NV12 and the P010 ring compute the same logits, which is checked.  Then the resize launch of each of the
+three.  Written to <out>/yuv16_host_path.txt and .json.
 """
 import argparse
 import json
@@ -172,6 +180,94 @@ class SideYUV(SideNV12):
         self.ctx.ring_submit_frames_yuv_packed(None, self.nbytes, self.desc)
 
 
+class SideP010(SideNV12):
+    """One context with a frames ring fed P010 frames: y [B, H, W] and uv [B, H/2, W/2, 2] uint16, each frame's planes back to back."""
+
+    def __init__(self, cfg, dname, batch, flags, eps, scale, shift, y, uv, box):
+        self.batch, self.frames = batch, True
+        self.ctx = vithip.VitContext(cfg, dtype=DT[dname], max_batch=batch, flags=flags, ln_eps=eps)
+        self.ctx.init_weights_seeded(0)
+        self.ctx.set_input_norm(scale, shift)
+        _, h, w = y.shape
+        per = h * w * 3 // 2                                                               # words per frame
+        buf = np.empty((batch, per), "<u2")
+        buf[:, :h * w] = y.reshape(batch, -1)
+        buf[:, h * w:] = uv.reshape(batch, -1)
+        self.nbytes = buf.nbytes
+        self.desc = (vithip.FrameNV12 * batch)()
+        for b in range(batch):
+            d = self.desc[b]
+            d.y_offset, d.uv_offset, d.height, d.width, d.y_stride, d.uv_stride = 2 * b * per, 2 * (b * per + h * w), h, w, 2 * w, 2 * w
+            d.box[:] = box
+        self.box_bytes = batch * (box[2] - box[0]) * (box[3] - box[1]) * 3.0
+        self.ctx.ring_create_frames(SLOTS, batch, self.nbytes)
+        for _ in range(SLOTS):
+            self.ctx.ring_input_frames()[:self.nbytes] = buf.reshape(-1).view(np.uint8)
+            self.submit()
+        self.first = [self.ctx.ring_collect().copy() for _ in range(SLOTS)][0]
+
+    def submit(self):
+        self.ctx.ring_submit_frames_p016_packed(None, self.nbytes, self.desc)
+
+
+def p010_main(a):
+    import nv12_ref as N
+    lines, rows = [], []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    scale, shift = vithip.input_norm_from_mean_std(MEAN, STD)
+    title, key, cfg, dname, _, flags, eps = RUNS[0]
+    log(f"frames_bench --p010: {title[:-5]}, frames rings of {SLOTS} slots, {a.steps} steps per pass, {a.passes} interleaved passes (RGB frames, "
+        f"the NV12 frames and the P010 frames of the same pictures, word = byte << 8; 0.875 centre box); median pass [min .. max]; images/s")
+    for h, w, batch in ((360, 480, 512), (1080, 1920, 64)):
+        rng = np.random.default_rng(3)
+        small = rng.integers(0, 256, size=(batch, h // 8, w // 8, 3), dtype=np.uint8)
+        rgb = np.ascontiguousarray(np.repeat(np.repeat(small, 8, axis=1), 8, axis=2))     # the pictures of --nv12
+        rgb ^= rng.integers(0, 8, size=rgb.shape, dtype=np.uint8)
+        planes = [N.rgb_to_nv12(f) for f in rgb]
+        y, uv = np.stack([p[0] for p in planes]), np.stack([p[1] for p in planes])
+        del planes
+        box = vithip.center_crop_box(h, w)
+        common = (cfg, dname, batch, flags, eps, scale, shift)
+        sides = dict(rgb=Side(*common, frames=rgb, box=box), nv12=SideNV12(*common, y=y, uv=uv, box=box),
+                     p010=SideP010(*common, y=y.astype(np.uint16) << 8, uv=uv.astype(np.uint16) << 8, box=box))
+        del rgb
+        same = bool(np.array_equal(sides["nv12"].first.view(np.uint32), sides["p010"].first.view(np.uint32)) and np.isfinite(sides["p010"].first).all())
+        rates = {k: [] for k in sides}
+        for _ in range(a.passes):
+            for k, sd in sides.items():
+                rates[k].append(sd.ring_rate(a.steps))
+        us = {k: [] for k in sides}
+        for _ in range(2):                                                                 # two interleaved passes of the launch alone
+            for k, sd in sides.items():
+                us[k].append(sd.resize_us(8))
+        r = dict(config=key, frame=[h, w], batch=batch, logits_p010_equal_nv12=same,
+                 ring={k: mid(v) for k, v in rates.items()}, h2d_MB_per_step={k: sd.nbytes / 1e6 for k, sd in sides.items()},
+                 resize_us_avg={k: [t[0] for t in v] for k, v in us.items()}, resize_us_min={k: min(t[1] for t in v) for k, v in us.items()},
+                 box_MB={k: sd.box_bytes / 1e6 for k, sd in sides.items()})
+        rows.append(r)
+        log(f"{h}x{w}, batch {batch}: logits of the P010 ring equal the NV12 ring's bit for bit: {same}")
+        for k, sd in sides.items():
+            m, lo, hi = r["ring"][k]
+            log(f"    frames ring, {k.upper():4s}: {m:9.0f} [{lo:9.0f} .. {hi:9.0f}] = {100 * m / r['ring']['nv12'][0]:6.2f} % of the NV12 ring, "
+                f"{100 * m / r['ring']['rgb'][0]:6.2f} % of the RGB ring | upload {sd.nbytes / 1e6:7.1f} MB per step = {sd.nbytes * 1e-9 * m / batch:5.1f} GB/s")
+        for k, sd in sides.items():
+            avg, mb = r["resize_us_avg"][k], sd.box_bytes / 1e6
+            t = float(np.mean(avg))
+            log(f"    resize {k.upper():4s}: {t:8.1f} us per launch avg ({r['resize_us_min'][k]:.1f} min; passes {avg[0]:.1f} {avg[1]:.1f}) | "
+                f"{mb:.1f} MB inside the boxes = {mb * 1e-3 / (t * 1e-6):.0f} GB/s")
+        for sd in sides.values():
+            sd.close()
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "yuv16_host_path.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+    with open(os.path.join(a.out, "yuv16_host_path.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def yuv420p_main(a):
     import nv12_ref as N
     lines, rows = [], []
@@ -292,7 +388,10 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--nv12", action="store_true", help="the NV12 passes (RGB frames ring against NV12 frames ring) instead")
     ap.add_argument("--yuv420p", action="store_true", help="the planar passes (NV12 frames ring against I420 frames ring) instead")
+    ap.add_argument("--p010", action="store_true", help="the 10-bit passes (RGB, NV12 and P010 frames rings of the same pictures) instead")
     a = ap.parse_args()
+    if a.p010:
+        return p010_main(a)
     if a.yuv420p:
         return yuv420p_main(a)
     if a.nv12:

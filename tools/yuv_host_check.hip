@@ -12,8 +12,10 @@
 // Use: yuv_host_check CASE OUT.  tools/yuv_host_check.py writes the case files, runs this program over them and compares OUT with the
 // fp32 emulation of tests/yuv_ref.py.
 //
-// CASE (little endian): int32 planar (1: vh_frame_yuv descriptors, 0: vh_frame_nv12), S, batch, chroma_site; float m[12];
-// uint64 nbytes; the descriptors; nbytes of frames.  OUT: [batch][S][S][3] bytes.
+// CASE (little endian): int32 layout (bit 0: 1 = vh_frame_yuv descriptors, 0 = vh_frame_nv12; bit 1: 16-bit samples), S, batch,
+// chroma_site; float m[12]; uint64 nbytes; the descriptors; nbytes of frames.  OUT: [batch][S][S][3] bytes.
+// With 16-bit samples UBSan's alignment check watches every uint16_t and uint32_t load: the planner's even-offset rule (and its
+// multiple-of-4 rule for the pair load) has to be what makes them aligned.
 #include <pthread.h>
 
 #include <cstdio>
@@ -41,11 +43,12 @@ int main(int argc, char** argv) {
     if (argc != 3) return die("usage: yuv_host_check CASE OUT");
     FILE* f = fopen(argv[1], "rb");
     if (!f) return die("cannot open the case file");
-    int32_t planar, S, batch, site;
+    int32_t layout, S, batch, site;
     float m[12];
     uint64_t nbytes;
-    if (!rd(f, &planar) || !rd(f, &S) || !rd(f, &batch) || !rd(f, &site) || !rd(f, m, 12) || !rd(f, &nbytes) || batch < 1 || batch > 4096)
+    if (!rd(f, &layout) || !rd(f, &S) || !rd(f, &batch) || !rd(f, &site) || !rd(f, m, 12) || !rd(f, &nbytes) || batch < 1 || batch > 4096)
         return die("short case file");
+    const bool planar = layout & 1, wide = layout & 2;
     std::vector<vh_frame_yuv> dy(planar ? batch : 0);
     std::vector<vh_frame_nv12> dn(planar ? 0 : batch);
     if (planar ? !rd(f, dy.data(), (size_t)batch) : !rd(f, dn.data(), (size_t)batch)) return die("short descriptors");
@@ -55,8 +58,9 @@ int main(int argc, char** argv) {
 
     std::vector<uint32_t> words;
     int max_tiles = 0;
-    const char* why = planar ? vh::resize_plan_build_yuv(dy.data(), batch, S, (size_t)nbytes, site, &words, &max_tiles)
-                             : vh::resize_plan_build_nv12(dn.data(), batch, S, (size_t)nbytes, ((uintptr_t)frames & 1) == 0, site, &words, &max_tiles);
+    const uintptr_t base = (uintptr_t)frames;
+    const char* why = planar ? vh::resize_plan_build_yuv(dy.data(), batch, S, (size_t)nbytes, (base & 1) == 0, site, wide ? 2 : 1, &words, &max_tiles)
+                             : vh::resize_plan_build_nv12(dn.data(), batch, S, (size_t)nbytes, (unsigned)(base & 3), site, wide ? 2 : 1, &words, &max_tiles);
     if (why) {
         printf("refused: %s\n", why);
         return 3;
@@ -78,8 +82,10 @@ int main(int argc, char** argv) {
     auto item = [&](int tid) {
         auto barrier = [&] { pthread_barrier_wait(&bar); };
         for (int b = 0; b < blocks; ++b) {
-            if (planar) vh::resize_yuv_body<true>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
-            else vh::resize_yuv_body<false>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            if (planar && wide) vh::resize_yuv_body<true, uint16_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            else if (planar) vh::resize_yuv_body<true, uint8_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            else if (wide) vh::resize_yuv_body<false, uint16_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            else vh::resize_yuv_body<false, uint8_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
             pthread_barrier_wait(&bar);
         }
     };

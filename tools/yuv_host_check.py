@@ -2,7 +2,11 @@
 kernels_resize_nv12.hip as host code under AddressSanitizer and UBSan, one thread per work-item, exact-size heap blocks), runs it over
 the operator cases of tests/test_yuv_planar.py at every sub-sampling, odd layouts, left-sited boxes that reach or overhang the last
 chroma column, a mixed batch, 40 small frames, one 1080 x 1920 frame and the two frames either side of the 4:4:4 planner boundary,
-and compares each output with the fp32 emulation of tests/yuv_ref.py byte for byte.  CPU only; no device is touched.
+and compares each output with the fp32 emulation of tests/yuv_ref.py byte for byte.  Then the 16-bit instantiations:
+the same operator cases with real 10 / 12 / 16-bit planes, all-0xFFFF words, even offsets and strides that are no multiple of 4
+(UBSan's alignment check on every uint16_t and uint32_t load is what shows that the planner's even-offset rule suffices), both pair-load
+paths of P016, a mixed batch, 40 small frames, one 1080 x 1920 P010 frame and the 4:4:4 planner boundary.  CPU only; no device is
+touched.
 
     python tools/yuv_host_check.py            (needs libvithip.so: make -C vit-fpga_amd)"""
 import os
@@ -21,9 +25,12 @@ import nv12_ref as N  # noqa: E402
 import vithip  # noqa: E402
 import yuv_ref as Y  # noqa: E402
 from test_gpu_nv12 import lay_out as lay_out_nv12  # noqa: E402
+from test_gpu_yuv16 import lay_out16, lay_out_p016, pairs_of  # noqa: E402
 from test_gpu_yuv_planar import lay_out, planner_boundary_444  # noqa: E402
 from test_nv12 import make_nv12  # noqa: E402
+from test_yuv16 import COLOURS16, make_yuv16  # noqa: E402
 from test_yuv_planar import COLOURS, OP_CASES, SUBS, make_yuv  # noqa: E402
+import yuv16_ref as W  # noqa: E402
 
 EXE = os.path.join(ROOT, "tools", "yuv_host_check")
 PKG = os.path.join(ROOT, "vit-fpga_amd")
@@ -35,13 +42,16 @@ def build():
                            os.path.join(ROOT, "tools", "yuv_host_check.hip"), "-o", EXE, "-L" + PKG, "-lvithip", "-Wl,-rpath," + PKG, "-lpthread"])
 
 
-def run(tmp, label, planes, boxes, s, m, site, subs, **layout):
+def run(tmp, label, planes, boxes, s, m, site, subs, wide=False, **layout):
     """One call of the host build; returns False if its bytes differ from the emulation.  subs None: `planes` are NV12 pairs (the
-    other instantiation of the same body)."""
-    buf, desc = lay_out_nv12(planes, boxes, **layout) if subs is None else lay_out(planes, boxes, subs, **layout)
+    other instantiation of the same body).  wide: uint16 planes, the two 16-bit instantiations."""
+    if wide:
+        buf, desc = lay_out_p016(planes, boxes, **layout) if subs is None else lay_out16(planes, boxes, subs, **layout)
+    else:
+        buf, desc = lay_out_nv12(planes, boxes, **layout) if subs is None else lay_out(planes, boxes, subs, **layout)
     case, out = os.path.join(tmp, "case.bin"), os.path.join(tmp, "out.bin")
     with open(case, "wb") as f:
-        f.write(struct.pack("<4i", 0 if subs is None else 1, s, len(planes), site))
+        f.write(struct.pack("<4i", (0 if subs is None else 1) | (2 if wide else 0), s, len(planes), site))
         f.write(np.ascontiguousarray(m, np.float32).tobytes())
         f.write(struct.pack("<Q", buf.nbytes))
         f.write(bytes(desc))
@@ -58,6 +68,55 @@ def run(tmp, label, planes, boxes, s, m, site, subs, **layout):
     same = np.array_equal(got, want)
     print(f"{'ok  ' if same else 'DIFF'} {label}: {p.stdout.strip()}")
     return same
+
+
+def main16(tmp):
+    """The 16-bit instantiations."""
+    good = True
+    mats = {k: (W.yuv_matrix16(std, full, bits, msb), site) for k, (std, full, bits, msb, site) in COLOURS16.items()}
+    for name, (h, w, box, s) in OP_CASES.items():
+        for key, sub in SUBS.items():
+            for colour, (m, site) in mats.items():
+                good &= run(tmp, f"16-bit {name} {key} {colour}", [make_yuv16(h, w, sub, h + w, colour)], [box], s, m, site, [sub], wide=True)
+        if h % 2 == 0 and w % 2 == 0:
+            for colour in ("bt709_limited_10_msb_left", "bt709_full_16_msb_centre"):
+                m, site = mats[colour]
+                good &= run(tmp, f"P016 {name} {colour}", pairs_of([make_yuv16(h, w, (2, 2), h + w, colour)]), [box], s, m, site, None, wide=True)
+    # words above 0x7fff
+    unit = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32) * np.float32(255.0 / 65535.0)
+    ones = lambda *shape: np.full(shape, 0xFFFF, np.uint16)
+    good &= run(tmp, "all-0xFFFF planar 4:2:0", [(ones(38, 54), ones(19, 27), ones(19, 27))], [None], 16, unit, N.CHROMA_LEFT, [(2, 2)], wide=True)
+    for lay in (dict(), dict(lead=2)):
+        good &= run(tmp, f"all-0xFFFF P016 {lay}", [(ones(38, 54), ones(19, 27, 2))], [None], 16, unit, N.CHROMA_LEFT, None, wide=True, **lay)
+    # even offsets and strides that are no multiple of 4: every 16-bit load aligned by the planner's rule alone
+    colour = "bt601_full_12_lsb_centre"
+    m, site = mats[colour]
+    planes = [make_yuv16(37, 53, (2, 2), 21, colour), make_yuv16(42, 31, (2, 1), 31, colour), make_yuv16(29, 30, (1, 1), 41, colour)]
+    boxes, subs = [None, (0.5, 3.0, 29.5, 40.0), None], [(2, 2), (2, 1), (1, 1)]
+    for lay in (dict(pads=(6, 10, 2)), dict(pads=(4, 0, 0), lead=2), dict(pads=(0, 2, 0)), dict(lead=6, gap=2), dict(order="yvu"), dict(gap=64, order="uvy"),
+                dict(lead=10, gap=6, order="vyu", pads=(2, 0, 4))):
+        good &= run(tmp, f"16-bit layout {lay}", planes, boxes, 16, m, site, subs, wide=True, **lay)
+    # P016: one 32-bit load per pair (uv_offset, uv_stride = 0 mod 4) and two 16-bit loads (either = 2 mod 4)
+    m, site = mats["bt709_limited_10_msb_left"]
+    p010 = "bt709_limited_10_msb_left"
+    pairs = pairs_of([make_yuv16(38, 54, (2, 2), 21, p010), make_yuv16(42, 30, (2, 2), 31, p010)])
+    for lay in (dict(), dict(lead=2), dict(uv_pad=2), dict(lead=4), dict(y_pad=6, uv_pad=12), dict(lead=2, gap=2, y_pad=2, uv_pad=6), dict(gap=64, uv_first=True)):
+        good &= run(tmp, f"P016 layout {lay}", pairs, [None, (0.5, 3.0, 29.5, 40.0)], 16, m, site, None, wide=True, **lay)
+    shapes = [(37, 53, "420"), (64, 64, "444"), (20, 24, "422"), (98, 132, "440"), (270, 480, "420"), (1, 1, "420"), (33, 2, "422")]
+    planes = [make_yuv16(h, w, SUBS[k], 40 + i, p010) for i, (h, w, k) in enumerate(shapes)]
+    boxes = [None, None, (2.0, 1.0, 22.0, 19.5), (10.0, 5.0, 101.0, 96.0), vithip.center_crop_box(270, 480), None, None]
+    good &= run(tmp, "16-bit mixed batch of 7", planes, boxes, 32, m, site, [SUBS[k] for _, _, k in shapes], wide=True, lead=2, gap=6)
+    keys = list(SUBS)
+    subs = [SUBS[keys[i % 4]] for i in range(40)]
+    planes = [make_yuv16(41, 39, subs[i], 100 + i, p010) for i in range(40)]
+    good &= run(tmp, "16-bit 40 frames of 41x39 (tall bands)", planes, [None if i % 2 else (0.5, 1.0, 38.25, 40.0) for i in range(40)], 32, m, site, subs, wide=True)
+    from test_nv12 import make_rgb
+    big = [W.rgb_to_yuv16_planes(make_rgb(1080, 1920, 3), 2, 2, 10, True)]
+    good &= run(tmp, "1080x1920 P010 -> 64", pairs_of(big), [vithip.center_crop_box(1080, 1920)], 64, m, site, None, wide=True)
+    m, site = mats[colour]
+    for h in planner_boundary_444(130):
+        good &= run(tmp, f"16-bit 4:4:4 planner boundary, {h}x36 -> 130", [make_yuv16(h, 36, (1, 1), 7, colour)], [None], 130, m, site, [(1, 1)], wide=True)
+    return good
 
 
 def main():
@@ -96,6 +155,7 @@ def main():
             good &= run(tmp, f"NV12 layout {lay}", nv, [None, (0.5, 3.0, 29.5, 40.0)], 16, m, N.CHROMA_LEFT, None, **lay)
         for h in planner_boundary_444(130):
             good &= run(tmp, f"4:4:4 planner boundary, {h}x36 -> 130", [make_yuv(h, 36, (1, 1), seed=7)], [None], 130, m, N.CHROMA_LEFT, [(1, 1)])
+        good &= main16(tmp)
     print("every output equals the fp32 emulation; no sanitizer report" if good else "FAILED")
     return 0 if good else 1
 

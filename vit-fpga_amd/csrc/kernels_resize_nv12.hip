@@ -25,6 +25,14 @@
 // the (u, v) pair lies in LDS as above, so the vertical pass, the matrix and the stores are shared.  With sub == 1 on an axis the
 // chroma table of that axis IS the luma table (same key).  The body is a __host__ __device__ function of (block, thread) with the
 // barrier passed in, so that tools/yuv_host_check.hip runs the very same text on the CPU under the sanitizers.
+//
+// 16-BIT SAMPLES (include/vithip.h, "16-bit YUV frames").  The same body again with the sample type T a template
+// parameter beside PLANAR: P010 / P012 / P016 (T = uint16_t, semi-planar) and yuv4xxpNNle (T = uint16_t, planar).  Only the loads
+// of the horizontal pass differ: a sample is one UNSIGNED 16-bit word that enters the fmaf chain as (float)word, unshifted and
+// unmasked (depth and alignment live in the matrix); a semi-planar (U, V) pair is one 32-bit load where uv_offset, uv_stride and
+// the base are multiples of 4 (the record's uv16 field) and two 16-bit loads otherwise.  The planner takes the sample width for
+// its stride, span and evenness checks; the tables, the bands, the LDS layout (fp32 either way), the vertical pass, the matrix and
+// the byte stores are those of the 8-bit instantiations, whose text is unchanged.
 #include <cmath>
 #include <cstring>
 
@@ -42,7 +50,7 @@ struct RzNv12 {
     int32_t xt, yt, cxt, cyt;      // word offsets of the tables: luma x, luma y, chroma x, chroma y
     int32_t xs, ys, cxs, cys;      // their weight strides
     int32_t band_rows, tile_cols;
-    int32_t uv16;                  // NV12: uv_offset, uv_stride and the base even: one 16-bit load per (U, V) pair
+    int32_t uv16;                  // semi-planar: uv_offset, uv_stride and the base multiples of one (U, V) pair: one load per pair
     int32_t ch;                    // rows of the chroma plane(s): h / 2 (NV12), ceil(h / sub_y) (planar)
     uint64_t v_off;                // planar: the V plane, rows v_stride apart
     int32_t v_stride;
@@ -165,69 +173,92 @@ const char* plan_frames(const std::vector<YuvSrc>& src, int S, int chroma_site, 
 
 }  // namespace
 
-const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, size_t nbytes, bool base_aligned2, int chroma_site,
-                                   std::vector<uint32_t>* words, int* max_tiles) {
-    if (!desc || batch < 1 || S < 1 || S > 4096) return "resize_nv12: bad batch or output size";
-    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return "resize_nv12: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+// sample_bytes 1: NV12.  2: P010 / P012 / P016, whose offsets, strides and base must be even; base_mod4 = the base address & 3
+// (0 for a host buffer, which is copied).  A message per refusal and per sample width.
+const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, size_t nbytes, unsigned base_mod4, int chroma_site,
+                                   int sample_bytes, std::vector<uint32_t>* words, int* max_tiles) {
+    const bool wide = sample_bytes == 2;
+    if (sample_bytes != 1 && !wide) return "resize_nv12: sample_bytes must be 1 or 2";
+    if (!desc || batch < 1 || S < 1 || S > 4096) return wide ? "resize_p016: bad batch or output size" : "resize_nv12: bad batch or output size";
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT)
+        return wide ? "resize_p016: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT" : "resize_nv12: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+    if (wide && base_mod4 % 2) return "resize_p016: the device frames pointer is odd; 16-bit samples need a 2-byte aligned base";
+    const unsigned pair = 2u * (unsigned)sample_bytes;   // bytes of one (U, V) pair
     std::vector<YuvSrc> src((size_t)batch);
     for (int b = 0; b < batch; ++b) {
         const vh_frame_nv12& d = desc[b];
         if (d.width < 2 || d.width > kResizeMaxSide || d.height < 2 || d.height > kResizeMaxSide || d.width % 2 || d.height % 2)
-            return "resize_nv12: width and height must be even and 2..8192";
-        if (d.y_stride < d.width || d.uv_stride < d.width) return "resize_nv12: y_stride or uv_stride < width";
-        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)d.width;
-        const uint64_t cspan = (uint64_t)(d.height / 2 - 1) * (uint64_t)d.uv_stride + (uint64_t)d.width;
-        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return "resize_nv12: a Y plane ends beyond nbytes";
-        if (d.uv_offset > nbytes || cspan > nbytes - d.uv_offset) return "resize_nv12: a UV plane ends beyond nbytes";
+            return wide ? "resize_p016: width and height must be even and 2..8192" : "resize_nv12: width and height must be even and 2..8192";
+        if (wide && (d.y_offset % 2 || d.uv_offset % 2)) return "resize_p016: y_offset or uv_offset is odd; 16-bit samples need even byte offsets";
+        if (wide && (d.y_stride % 2 || d.uv_stride % 2)) return "resize_p016: y_stride or uv_stride is odd; 16-bit samples need even byte strides";
+        if (d.y_stride < sample_bytes * d.width || d.uv_stride < sample_bytes * d.width)
+            return wide ? "resize_p016: y_stride or uv_stride < 2 * width bytes" : "resize_nv12: y_stride or uv_stride < width";
+        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)sample_bytes * (uint64_t)d.width;
+        const uint64_t cspan = (uint64_t)(d.height / 2 - 1) * (uint64_t)d.uv_stride + (uint64_t)sample_bytes * (uint64_t)d.width;
+        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return wide ? "resize_p016: a Y plane ends beyond nbytes" : "resize_nv12: a Y plane ends beyond nbytes";
+        if (d.uv_offset > nbytes || cspan > nbytes - d.uv_offset) return wide ? "resize_p016: a UV plane ends beyond nbytes" : "resize_nv12: a UV plane ends beyond nbytes";
         YuvSrc& s = src[b];
         s.y_off = d.y_offset; s.u_off = d.uv_offset; s.v_off = 0;
         s.h = d.height; s.w = d.width; s.cw = d.width / 2; s.ch = d.height / 2;
         s.y_stride = d.y_stride; s.u_stride = d.uv_stride; s.v_stride = 0;
         s.sub_x = 2; s.sub_y = 2;
-        s.uv16 = base_aligned2 && d.uv_offset % 2 == 0 && d.uv_stride % 2 == 0;
+        s.uv16 = base_mod4 % pair == 0 && d.uv_offset % pair == 0 && (unsigned)d.uv_stride % pair == 0;
         for (int i = 0; i < 4; ++i) s.box[i] = (double)d.box[i];
     }
-    if (const char* e = plan_frames(src, S, chroma_site, "resize_nv12: box outside the frame, empty, or scale > 32", words, max_tiles)) return e;
-    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return "resize_nv12: too many tiles";
+    if (const char* e = plan_frames(src, S, chroma_site, wide ? "resize_p016: box outside the frame, empty, or scale > 32" : "resize_nv12: box outside the frame, empty, or scale > 32",
+                                    words, max_tiles))
+        return e;
+    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return wide ? "resize_p016: too many tiles" : "resize_nv12: too many tiles";
     return nullptr;
 }
 
-// every refusal of the planar contract has a message of its own, in the order the header lists them
-const char* resize_plan_build_yuv(const vh_frame_yuv* desc, int batch, int S, size_t nbytes, int chroma_site, std::vector<uint32_t>* words,
-                                  int* max_tiles) {
-    if (!desc || batch < 1 || S < 1 || S > 4096) return "resize_yuv: bad batch or output size";
-    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return "resize_yuv: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+// every refusal of the planar contract has a message of its own, in the order the header lists them.  sample_bytes 1: byte planes.
+// 2: yuv4xxpNNle, whose offsets, strides and base (base_even) must be even.
+const char* resize_plan_build_yuv(const vh_frame_yuv* desc, int batch, int S, size_t nbytes, bool base_even, int chroma_site, int sample_bytes,
+                                  std::vector<uint32_t>* words, int* max_tiles) {
+    const bool wide = sample_bytes == 2;
+    if (sample_bytes != 1 && !wide) return "resize_yuv: sample_bytes must be 1 or 2";
+    if (!desc || batch < 1 || S < 1 || S > 4096) return wide ? "resize_yuv16: bad batch or output size" : "resize_yuv: bad batch or output size";
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT)
+        return wide ? "resize_yuv16: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT" : "resize_yuv: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+    if (wide && !base_even) return "resize_yuv16: the device frames pointer is odd; 16-bit samples need a 2-byte aligned base";
     std::vector<YuvSrc> src((size_t)batch);
     for (int b = 0; b < batch; ++b) {
         const vh_frame_yuv& d = desc[b];
         if (d.width < 1 || d.width > kResizeMaxSide || d.height < 1 || d.height > kResizeMaxSide)
-            return "resize_yuv: width and height must be 1..8192";
-        if ((d.sub_x != 1 && d.sub_x != 2) || (d.sub_y != 1 && d.sub_y != 2)) return "resize_yuv: sub_x and sub_y must be 1 or 2";
+            return wide ? "resize_yuv16: width and height must be 1..8192" : "resize_yuv: width and height must be 1..8192";
+        if ((d.sub_x != 1 && d.sub_x != 2) || (d.sub_y != 1 && d.sub_y != 2))
+            return wide ? "resize_yuv16: sub_x and sub_y must be 1 or 2" : "resize_yuv: sub_x and sub_y must be 1 or 2";
         const int cw = (d.width + d.sub_x - 1) / d.sub_x, ch = (d.height + d.sub_y - 1) / d.sub_y;
-        if (d.y_stride < d.width) return "resize_yuv: y_stride < width";
-        if (d.u_stride < cw || d.v_stride < cw) return "resize_yuv: u_stride or v_stride < the chroma width, ceil(width / sub_x)";
-        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)d.width;
-        const uint64_t uspan = (uint64_t)(ch - 1) * (uint64_t)d.u_stride + (uint64_t)cw;
-        const uint64_t vspan = (uint64_t)(ch - 1) * (uint64_t)d.v_stride + (uint64_t)cw;
-        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return "resize_yuv: a Y plane ends beyond nbytes";
-        if (d.u_offset > nbytes || uspan > nbytes - d.u_offset) return "resize_yuv: a U plane ends beyond nbytes";
-        if (d.v_offset > nbytes || vspan > nbytes - d.v_offset) return "resize_yuv: a V plane ends beyond nbytes";
+        if (wide && (d.y_offset % 2 || d.u_offset % 2 || d.v_offset % 2)) return "resize_yuv16: y_offset, u_offset or v_offset is odd; 16-bit samples need even byte offsets";
+        if (wide && (d.y_stride % 2 || d.u_stride % 2 || d.v_stride % 2)) return "resize_yuv16: y_stride, u_stride or v_stride is odd; 16-bit samples need even byte strides";
+        if (d.y_stride < sample_bytes * d.width) return wide ? "resize_yuv16: y_stride < 2 * width bytes" : "resize_yuv: y_stride < width";
+        if (d.u_stride < sample_bytes * cw || d.v_stride < sample_bytes * cw)
+            return wide ? "resize_yuv16: u_stride or v_stride < 2 * cw bytes, cw = ceil(width / sub_x)" : "resize_yuv: u_stride or v_stride < the chroma width, ceil(width / sub_x)";
+        const uint64_t yspan = (uint64_t)(d.height - 1) * (uint64_t)d.y_stride + (uint64_t)sample_bytes * (uint64_t)d.width;
+        const uint64_t uspan = (uint64_t)(ch - 1) * (uint64_t)d.u_stride + (uint64_t)sample_bytes * (uint64_t)cw;
+        const uint64_t vspan = (uint64_t)(ch - 1) * (uint64_t)d.v_stride + (uint64_t)sample_bytes * (uint64_t)cw;
+        if (d.y_offset > nbytes || yspan > nbytes - d.y_offset) return wide ? "resize_yuv16: a Y plane ends beyond nbytes" : "resize_yuv: a Y plane ends beyond nbytes";
+        if (d.u_offset > nbytes || uspan > nbytes - d.u_offset) return wide ? "resize_yuv16: a U plane ends beyond nbytes" : "resize_yuv: a U plane ends beyond nbytes";
+        if (d.v_offset > nbytes || vspan > nbytes - d.v_offset) return wide ? "resize_yuv16: a V plane ends beyond nbytes" : "resize_yuv: a V plane ends beyond nbytes";
         YuvSrc& s = src[b];
         for (int i = 0; i < 4; ++i) s.box[i] = (double)d.box[i];
         // written so that a NaN fails
         if (!(s.box[0] >= 0.0 && s.box[0] < s.box[2] && s.box[2] <= (double)d.width && s.box[1] >= 0.0 && s.box[1] < s.box[3] &&
               s.box[3] <= (double)d.height))
-            return "resize_yuv: box outside the frame, or empty";
+            return wide ? "resize_yuv16: box outside the frame, or empty" : "resize_yuv: box outside the frame, or empty";
         if (!((s.box[2] - s.box[0]) / (double)S <= (double)kResizeMaxScale && (s.box[3] - s.box[1]) / (double)S <= (double)kResizeMaxScale))
-            return "resize_yuv: scale > 32 on an axis";
+            return wide ? "resize_yuv16: scale > 32 on an axis" : "resize_yuv: scale > 32 on an axis";
         s.y_off = d.y_offset; s.u_off = d.u_offset; s.v_off = d.v_offset;
         s.h = d.height; s.w = d.width; s.cw = cw; s.ch = ch;
         s.y_stride = d.y_stride; s.u_stride = d.u_stride; s.v_stride = d.v_stride;
         s.sub_x = d.sub_x; s.sub_y = d.sub_y;
         s.uv16 = 0;
     }
-    if (const char* e = plan_frames(src, S, chroma_site, "resize_yuv: a table of the box could not be built", words, max_tiles)) return e;
-    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return "resize_yuv: too many tiles";
+    if (const char* e = plan_frames(src, S, chroma_site, wide ? "resize_yuv16: a table of the box could not be built" : "resize_yuv: a table of the box could not be built",
+                                    words, max_tiles))
+        return e;
+    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return wide ? "resize_yuv16: too many tiles" : "resize_yuv: too many tiles";
     return nullptr;
 }
 
@@ -237,9 +268,10 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 __host__ __device__ __forceinline__ uint32_t nv12_byte(float v) { return (uint32_t)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
 
-// The work of thread `tid` of workgroup `block`.  PLANAR: U and V are two byte planes, else one plane of (U, V) pairs.  `barrier`
+// The work of thread `tid` of workgroup `block`.  PLANAR: U and V are two planes, else one plane of (U, V) pairs.  T: the sample,
+// uint8_t or uint16_t (unsigned: a word above 0x7fff must not sign-extend); strides and offsets are bytes either way.  `barrier`
 // is __syncthreads() on the device; every return in front of it is taken by the whole workgroup.
-template <bool PLANAR, class Barrier>
+template <bool PLANAR, class T, class Barrier>
 __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan,
                                                          uint8_t* __restrict__ out, int S, int max_tiles, const Nv12Matrix& mat, float* lds,
                                                          int block, int tid, Barrier barrier) {
@@ -284,7 +316,7 @@ __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restri
             const int y = e / cols, x = c0 + (e - y * cols);
             const int n = xcount[x];
             const float* w = xw + (size_t)x * d.xs;
-            const uint8_t* p = ysrc + (size_t)(ylo + y) * d.y_stride + xfirst[x];
+            const T* p = (const T*)(ysrc + (size_t)(ylo + y) * d.y_stride) + xfirst[x];
             float acc = 0.f;
             for (int t = 0; t < n; ++t) acc = __builtin_fmaf(w[t], (float)p[t], acc);
             ldy[e] = acc;
@@ -295,12 +327,29 @@ __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restri
             const float* w = cxw + (size_t)x * d.cxs;
             float u = 0.f, v = 0.f;
             if constexpr (PLANAR) {
-                const uint8_t* pu = csrc + (size_t)(clo + y) * d.uv_stride + cxfirst[x];
-                const uint8_t* pv = vsrc + (size_t)(clo + y) * d.v_stride + cxfirst[x];
+                const T* pu = (const T*)(csrc + (size_t)(clo + y) * d.uv_stride) + cxfirst[x];
+                const T* pv = (const T*)(vsrc + (size_t)(clo + y) * d.v_stride) + cxfirst[x];
                 for (int t = 0; t < n; ++t) {
                     const float wt = w[t];
                     u = __builtin_fmaf(wt, (float)pu[t], u);
                     v = __builtin_fmaf(wt, (float)pv[t], v);
+                }
+            } else if constexpr (sizeof(T) == 2) {
+                const uint8_t* p = csrc + (size_t)(clo + y) * d.uv_stride + (size_t)cxfirst[x] * 4;
+                if (d.uv16) {
+                    for (int t = 0; t < n; ++t) {
+                        const uint32_t q = *(const uint32_t*)(p + 4 * t);
+                        const float wt = w[t];
+                        u = __builtin_fmaf(wt, (float)(q & 0xffffu), u);
+                        v = __builtin_fmaf(wt, (float)(q >> 16), v);
+                    }
+                } else {
+                    const uint16_t* p16 = (const uint16_t*)p;
+                    for (int t = 0; t < n; ++t) {
+                        const float wt = w[t];
+                        u = __builtin_fmaf(wt, (float)p16[2 * t], u);
+                        v = __builtin_fmaf(wt, (float)p16[2 * t + 1], v);
+                    }
                 }
             } else {
                 const uint8_t* p = csrc + (size_t)(clo + y) * d.uv_stride + (size_t)cxfirst[x] * 2;
@@ -355,36 +404,50 @@ __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restri
 }
 
 #ifndef VH_HOST_CHECK   // tools/yuv_host_check.hip takes the planner and the body above and no device code
-template <bool PLANAR>
+template <bool PLANAR, class T>
 __global__ void __launch_bounds__(256)
 resize_yuv_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan, uint8_t* __restrict__ out, int S, int max_tiles,
                   Nv12Matrix mat) {
     __shared__ __attribute__((aligned(16))) float lds[kResizeLdsFloats];
-    resize_yuv_body<PLANAR>(frames, plan, out, S, max_tiles, mat, lds, (int)blockIdx.x, (int)threadIdx.x, [] { __syncthreads(); });
+    resize_yuv_body<PLANAR, T>(frames, plan, out, S, max_tiles, mat, lds, (int)blockIdx.x, (int)threadIdx.x, [] { __syncthreads(); });
 }
 
-static hipError_t launch_resize_any(bool planar, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
+static hipError_t launch_resize_any(bool planar, bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
                                     const float* m12, uint8_t* out, hipStream_t s) {
     if (!frames || !plan_dev || !out || !m12 || batch < 1 || S < 1 || max_tiles < 1 || (int64_t)batch * max_tiles > 0x7fffffffll)
         return hipErrorInvalidValue;
     Nv12Matrix mat;
     memcpy(mat.m, m12, sizeof mat.m);
     const dim3 grid((unsigned)(batch * max_tiles));
-    if (planar)
-        hipLaunchKernelGGL(resize_yuv_kernel<true>, grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    if (planar && wide)
+        hipLaunchKernelGGL((resize_yuv_kernel<true, uint16_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    else if (planar)
+        hipLaunchKernelGGL((resize_yuv_kernel<true, uint8_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    else if (wide)
+        hipLaunchKernelGGL((resize_yuv_kernel<false, uint16_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     else
-        hipLaunchKernelGGL(resize_yuv_kernel<false>, grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+        hipLaunchKernelGGL((resize_yuv_kernel<false, uint8_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     return hipGetLastError();
 }
 
 hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
                               uint8_t* out, hipStream_t s) {
-    return launch_resize_any(false, frames, plan_dev, batch, S, max_tiles, m12, out, s);
+    return launch_resize_any(false, false, frames, plan_dev, batch, S, max_tiles, m12, out, s);
 }
 
 hipError_t launch_resize_yuv(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
                              uint8_t* out, hipStream_t s) {
-    return launch_resize_any(true, frames, plan_dev, batch, S, max_tiles, m12, out, s);
+    return launch_resize_any(true, false, frames, plan_dev, batch, S, max_tiles, m12, out, s);
+}
+
+hipError_t launch_resize_p016(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
+                              uint8_t* out, hipStream_t s) {
+    return launch_resize_any(false, true, frames, plan_dev, batch, S, max_tiles, m12, out, s);
+}
+
+hipError_t launch_resize_yuv16(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
+                               uint8_t* out, hipStream_t s) {
+    return launch_resize_any(true, true, frames, plan_dev, batch, S, max_tiles, m12, out, s);
 }
 #endif
 
@@ -411,6 +474,36 @@ int yuv_matrix(int standard, int full_range, float m[12]) {
     const double v[12] = {sy, 0.0, rv, yo - 128.0 * rv,
                           sy, gu, gv, yo - 128.0 * gu - 128.0 * gv,
                           sy, bu, 0.0, yo - 128.0 * bu};
+    for (int i = 0; i < 12; ++i) m[i] = (float)v[i];
+    return 0;
+}
+
+// The matrix of 16-bit words: `bits` significant bits, in the high bits of the word (msb_aligned: P010 / P012 / P016) or the low
+// ones (yuv4xxpNNle).  bits = 8, msb_aligned = 0 gives yuv_matrix bit for bit (every factor it adds is then exactly 1).
+int yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, float m[12]) {
+    double kr, kb;
+    switch (standard) {
+        case VH_YUV_BT601: kr = 0.299; kb = 0.114; break;
+        case VH_YUV_BT709: kr = 0.2126; kb = 0.0722; break;
+        case VH_YUV_BT2020: kr = 0.2627; kb = 0.0593; break;
+        default: return 1;
+    }
+    if (!m || (full_range != 0 && full_range != 1) || bits < 8 || bits > 16 || (msb_aligned != 0 && msb_aligned != 1)) return 1;
+    const double kg = 1.0 - kr - kb;
+    const double a = msb_aligned ? (double)(1 << (16 - bits)) : 1.0;   // word = code * a
+    const double q = (double)(1 << (bits - 8));
+    const double sy = full_range ? 255.0 / (((double)(1 << bits) - 1.0) * a) : 255.0 / (219.0 * q * a);
+    const double sc = full_range ? sy : 255.0 / (224.0 * q * a);
+    const double oy = full_range ? 0.0 : 16.0 * q * a;
+    const double mid = (double)(1 << (bits - 1)) * a;
+    const double rv = 2.0 * (1.0 - kr) * sc;
+    const double bu = 2.0 * (1.0 - kb) * sc;
+    const double gu = -(2.0 * kb * (1.0 - kb) / kg) * sc;
+    const double gv = -(2.0 * kr * (1.0 - kr) / kg) * sc;
+    const double yo = -(sy * oy);
+    const double v[12] = {sy, 0.0, rv, yo - mid * rv,
+                          sy, gu, gv, yo - mid * gu - mid * gv,
+                          sy, bu, 0.0, yo - mid * bu};
     for (int i = 0; i < 12; ++i) m[i] = (float)v[i];
     return 0;
 }

@@ -257,6 +257,9 @@ struct vh_ctx {
     // matrix travels to resize_yuv_kernel by value at each launch, outside any captured graph.
     float nv12_m[12];
     int nv12_site = VH_CHROMA_LEFT;
+    // 16-bit YUV frames (vh_set_frame_colour16): a second state, because one frames ring interleaves 8-bit and 16-bit submits
+    float yuv16_m[12];
+    int yuv16_site = VH_CHROMA_LEFT;
     int64_t last_us = 0;
     bool timed = false;
     int last_batch = 0;
@@ -957,7 +960,7 @@ int check_u8_ptr(vh_ctx* c, const void* in_dev) {
 
 // ---- 8-bit frames: plan, buffers, the resize launch ---------------------------------------------------------------------------
 // One resize in front of a forward: the frames in HBM and the descriptors + tables (c->rz_words) in pinned memory.
-enum { FRAMES_RGB = 0, FRAMES_NV12 = 1, FRAMES_YUV = 2 };
+enum { FRAMES_RGB = 0, FRAMES_NV12 = 1, FRAMES_YUV = 2, FRAMES_P016 = 3, FRAMES_YUV16 = 4 };   // the last two: 16-bit samples, the second colour state
 struct FrameJob {
     const uint8_t* frames_dev;
     const uint32_t* plan_host;   // pinned; stays untouched until the upload below has run
@@ -974,18 +977,23 @@ int frames_plan(vh_ctx* c, const vh_frame* desc, int batch, size_t nbytes, bool 
     return VH_OK;
 }
 
-int frames_plan_nv12(vh_ctx* c, const vh_frame_nv12* desc, int batch, size_t nbytes, bool base_aligned2, int* max_tiles) {
+// wide: P010 / P012 / P016 (16-bit words, the second colour state's siting); base: the frames address, 0 for a host buffer
+int frames_plan_nv12(vh_ctx* c, const vh_frame_nv12* desc, int batch, size_t nbytes, uintptr_t base, int* max_tiles, bool wide = false) {
     if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
-    if (c->cfg.channels != 3) return fail(&c->err, VH_ERR_INVALID, "NV12 frames need a model with 3 channels, this one has %d", c->cfg.channels);
-    const char* why = resize_plan_build_nv12(desc, batch, c->cfg.image_size, nbytes, base_aligned2, c->nv12_site, &c->rz_words, max_tiles);
+    if (c->cfg.channels != 3)
+        return fail(&c->err, VH_ERR_INVALID, "%s frames need a model with 3 channels, this one has %d", wide ? "P016" : "NV12", c->cfg.channels);
+    const char* why = resize_plan_build_nv12(desc, batch, c->cfg.image_size, nbytes, (unsigned)(base & 3), wide ? c->yuv16_site : c->nv12_site,
+                                             wide ? 2 : 1, &c->rz_words, max_tiles);
     if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
     return VH_OK;
 }
 
-int frames_plan_yuv(vh_ctx* c, const vh_frame_yuv* desc, int batch, size_t nbytes, int* max_tiles) {
+int frames_plan_yuv(vh_ctx* c, const vh_frame_yuv* desc, int batch, size_t nbytes, uintptr_t base, int* max_tiles, bool wide = false) {
     if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
-    if (c->cfg.channels != 3) return fail(&c->err, VH_ERR_INVALID, "planar YUV frames need a model with 3 channels, this one has %d", c->cfg.channels);
-    const char* why = resize_plan_build_yuv(desc, batch, c->cfg.image_size, nbytes, c->nv12_site, &c->rz_words, max_tiles);
+    if (c->cfg.channels != 3)
+        return fail(&c->err, VH_ERR_INVALID, "planar %sYUV frames need a model with 3 channels, this one has %d", wide ? "16-bit " : "", c->cfg.channels);
+    const char* why = resize_plan_build_yuv(desc, batch, c->cfg.image_size, nbytes, (base & 1) == 0, wide ? c->yuv16_site : c->nv12_site, wide ? 2 : 1,
+                                            &c->rz_words, max_tiles);
     if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
     return VH_OK;
 }
@@ -1042,6 +1050,10 @@ int enqueue_resize(vh_ctx* c, const FrameJob& j, int batch) {
         HIPCHK(&c->err, launch_resize_nv12(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->nv12_m, c->rz_u8, c->stream));
     else if (j.kind == FRAMES_YUV)
         HIPCHK(&c->err, launch_resize_yuv(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->nv12_m, c->rz_u8, c->stream));
+    else if (j.kind == FRAMES_P016)
+        HIPCHK(&c->err, launch_resize_p016(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->yuv16_m, c->rz_u8, c->stream));
+    else if (j.kind == FRAMES_YUV16)
+        HIPCHK(&c->err, launch_resize_yuv16(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->yuv16_m, c->rz_u8, c->stream));
     else
         HIPCHK(&c->err, launch_resize_u8(j.frames_dev, c->rz_plan_dev, batch, c->cfg.channels, c->cfg.image_size, j.max_tiles, c->rz_u8, c->stream));
     return tmark();
@@ -1274,6 +1286,8 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     }
     yuv_matrix(VH_YUV_BT709, 0, c->nv12_m);   // NV12 frames: what an HD video decoder emits, until vh_set_frame_colour says otherwise
     c->nv12_site = VH_CHROMA_LEFT;
+    yuv_matrix16(VH_YUV_BT709, 0, 10, 1, c->yuv16_m);   // 16-bit frames: P010 as VCN writes it, until vh_set_frame_colour16 says otherwise
+    c->yuv16_site = VH_CHROMA_LEFT;
     {
         // (fp8 operands: the hi plane is e4m3 -- the GEMM operand itself -- and the lo plane bf16: 3 bytes per element as well)
         const char* e = getenv("VH_RESID_SPLIT");
@@ -1663,7 +1677,7 @@ int vh_forward_device_frames_nv12(vh_ctx* c, const uint8_t* frames_dev, size_t n
     int rc = check_forward_args(c, frames_dev, batch, logits_dev);
     if (rc) return rc;
     int max_tiles = 0;
-    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, ((uintptr_t)frames_dev & 1) == 0, &max_tiles))) return rc;
+    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, (uintptr_t)frames_dev, &max_tiles))) return rc;
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
@@ -1675,7 +1689,7 @@ int vh_forward_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nbytes,
     int rc = check_forward_args(c, frames_host, batch, logits_host);
     if (rc) return rc;
     int max_tiles = 0;
-    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, true, &max_tiles))) return rc;
+    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, 0, &max_tiles))) return rc;
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
@@ -1688,7 +1702,7 @@ int vh_forward_device_frames_yuv(vh_ctx* c, const uint8_t* frames_dev, size_t nb
     int rc = check_forward_args(c, frames_dev, batch, logits_dev);
     if (rc) return rc;
     int max_tiles = 0;
-    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, &max_tiles))) return rc;
+    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, 0, &max_tiles))) return rc;
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
@@ -1700,12 +1714,55 @@ int vh_forward_frames_yuv(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, 
     int rc = check_forward_args(c, frames_host, batch, logits_host);
     if (rc) return rc;
     int max_tiles = 0;
-    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, &max_tiles))) return rc;
+    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, 0, &max_tiles))) return rc;
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
     const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_YUV};
     return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+}
+
+// 16-bit YUV frames: the four entry points share one body each way; `planar` picks the descriptor type and the planner, both run
+// the uint16_t instantiation of the kernel with the second colour state
+static int forward_device_frames16(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const void* desc, int batch, float* logits_dev, bool planar) {
+    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
+    if (rc) return rc;
+    int max_tiles = 0;
+    rc = planar ? frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, nbytes, (uintptr_t)frames_dev, &max_tiles, true)
+                : frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, nbytes, (uintptr_t)frames_dev, &max_tiles, true);
+    if (rc) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, planar ? FRAMES_YUV16 : FRAMES_P016};
+    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+}
+
+static int forward_frames16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const void* desc, int batch, float* logits_host, bool planar) {
+    int rc = check_forward_args(c, frames_host, batch, logits_host);
+    if (rc) return rc;
+    int max_tiles = 0;
+    rc = planar ? frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, nbytes, 0, &max_tiles, true)
+                : frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, nbytes, 0, &max_tiles, true);
+    if (rc) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, planar ? FRAMES_YUV16 : FRAMES_P016};
+    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+}
+
+int vh_forward_device_frames_p016(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev) {
+    return forward_device_frames16(c, frames_dev, nbytes, desc, batch, logits_dev, false);
+}
+int vh_forward_frames_p016(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_host) {
+    return forward_frames16(c, frames_host, nbytes, desc, batch, logits_host, false);
+}
+int vh_forward_device_frames_yuv16(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev) {
+    return forward_device_frames16(c, frames_dev, nbytes, desc, batch, logits_dev, true);
+}
+int vh_forward_frames_yuv16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host) {
+    return forward_frames16(c, frames_host, nbytes, desc, batch, logits_host, true);
 }
 
 int vh_yuv_matrix(int standard, int full_range, float m[12]) {
@@ -1735,6 +1792,36 @@ int vh_get_frame_colour(const vh_ctx* c, float m[12], int* chroma_site) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (m) memcpy(m, c->nv12_m, sizeof c->nv12_m);
     if (chroma_site) *chroma_site = c->nv12_site;
+    return VH_OK;
+}
+
+int vh_yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, float m[12]) {
+    if (yuv_matrix16(standard, full_range, bits, msb_aligned, m))
+        return fail(nullptr, VH_ERR_INVALID, "yuv matrix16: standard must be VH_YUV_BT601, _BT709 or _BT2020, full_range 0 or 1, bits 8..16, msb_aligned 0 or 1, m not NULL");
+    return VH_OK;
+}
+
+// The second colour state: matrix and siting of the 16-bit entry points, under the rules of vh_set_frame_colour.  Neither call
+// touches the other's state.
+int vh_set_frame_colour16(vh_ctx* c, const float m[12], int chroma_site) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
+    if (!m) {
+        yuv_matrix16(VH_YUV_BT709, 0, 10, 1, c->yuv16_m);
+        c->yuv16_site = VH_CHROMA_LEFT;
+        return VH_OK;
+    }
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return fail(&c->err, VH_ERR_INVALID, "chroma_site %d is neither VH_CHROMA_CENTER nor VH_CHROMA_LEFT", chroma_site);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(m[i])) return fail(&c->err, VH_ERR_INVALID, "16-bit colour matrix entry %d is not finite", i);
+    memcpy(c->yuv16_m, m, sizeof c->yuv16_m);
+    c->yuv16_site = chroma_site;
+    return VH_OK;
+}
+
+int vh_get_frame_colour16(const vh_ctx* c, float m[12], int* chroma_site) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
+    if (m) memcpy(m, c->yuv16_m, sizeof c->yuv16_m);
+    if (chroma_site) *chroma_site = c->yuv16_site;
     return VH_OK;
 }
 
@@ -1926,8 +2013,9 @@ int vh_ring_input_frames(vh_ctx* c, uint8_t** pinned, size_t* capacity) {
 
 // frames ring: in_host holds `frame_bytes` of frames described by `desc`; the slot's upload is followed by the resize into
 // c->rz_u8 on the context's stream (forwards are ordered on that stream, so one resized buffer serves every slot)
-// (fkind FRAMES_NV12 / FRAMES_YUV: `desc` points to vh_frame_nv12 / vh_frame_yuv descriptors instead; a slot is raw bytes, so one
-// frames ring takes all three)
+// (fkind FRAMES_NV12 / FRAMES_YUV: `desc` points to vh_frame_nv12 / vh_frame_yuv descriptors instead, FRAMES_P016 / FRAMES_YUV16: the
+// same two with 16-bit samples; a slot is raw bytes, so one frames ring takes all five.  A slot's device buffer comes from hipMalloc,
+// so its base is aligned for any sample)
 static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const void* desc = nullptr,
                        int fkind = FRAMES_RGB) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
@@ -1940,8 +2028,8 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     int rc, max_tiles = 0;
     if (frames) {   // every check, and the plan, before anything is enqueued or the slot is touched
         if (frame_bytes < 1 || frame_bytes > c->ring_slot_bytes) return fail(&c->err, VH_ERR_INVALID, "nbytes %zu outside 1..slot_bytes=%zu", frame_bytes, c->ring_slot_bytes);
-        if (fkind == FRAMES_NV12) rc = frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, frame_bytes, true, &max_tiles);
-        else if (fkind == FRAMES_YUV) rc = frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, frame_bytes, &max_tiles);
+        if (fkind == FRAMES_NV12 || fkind == FRAMES_P016) rc = frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, frame_bytes, 0, &max_tiles, fkind == FRAMES_P016);
+        else if (fkind == FRAMES_YUV || fkind == FRAMES_YUV16) rc = frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, frame_bytes, 0, &max_tiles, fkind == FRAMES_YUV16);
         else rc = frames_plan(c, (const vh_frame*)desc, batch, frame_bytes, true, &max_tiles);
         if (rc) return rc;
     }
@@ -1989,6 +2077,12 @@ int vh_ring_submit_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nby
 }
 int vh_ring_submit_frames_yuv(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch) {
     return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_YUV);
+}
+int vh_ring_submit_frames_p016(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_P016);
+}
+int vh_ring_submit_frames_yuv16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_YUV16);
 }
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
@@ -2385,7 +2479,7 @@ int vh_op_resize_nv12(const uint8_t* frames, size_t nbytes, const vh_frame_nv12*
         if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "resize_nv12: colour matrix entry %d is not finite", i);
     std::vector<uint32_t> words;
     int max_tiles = 0;
-    if (const char* why = resize_plan_build_nv12(desc, batch, out_size, nbytes, ((uintptr_t)frames & 1) == 0, chroma_site, &words, &max_tiles))
+    if (const char* why = resize_plan_build_nv12(desc, batch, out_size, nbytes, (unsigned)((uintptr_t)frames & 3), chroma_site, 1, &words, &max_tiles))
         return fail(nullptr, VH_ERR_INVALID, "%s", why);
     uint32_t* plan = nullptr;
     OPCHK(hipMalloc((void**)&plan, words.size() * 4));
@@ -2406,7 +2500,7 @@ int vh_op_resize_yuv(const uint8_t* frames, size_t nbytes, const vh_frame_yuv* d
         if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "resize_yuv: colour matrix entry %d is not finite", i);
     std::vector<uint32_t> words;
     int max_tiles = 0;
-    if (const char* why = resize_plan_build_yuv(desc, batch, out_size, nbytes, chroma_site, &words, &max_tiles))
+    if (const char* why = resize_plan_build_yuv(desc, batch, out_size, nbytes, true, chroma_site, 1, &words, &max_tiles))
         return fail(nullptr, VH_ERR_INVALID, "%s", why);
     uint32_t* plan = nullptr;
     OPCHK(hipMalloc((void**)&plan, words.size() * 4));
@@ -2417,6 +2511,43 @@ int vh_op_resize_yuv(const uint8_t* frames, size_t nbytes, const vh_frame_yuv* d
     OPCHK(e);
     OPCHK(es);
     return VH_OK;
+}
+
+// the 16-bit taps: `planar` picks the descriptor type, the planner and the launcher
+static int op_resize16(const uint8_t* frames, size_t nbytes, const void* desc, int batch, int out_size, const float* m12, int chroma_site, uint8_t* out,
+                       void* stream, bool planar) {
+    // every check before a device is touched
+    const char* tag = planar ? "resize_yuv16" : "resize_p016";
+    if (!frames || !desc || !m12 || !out) return fail(nullptr, VH_ERR_INVALID, "%s: null buffer", tag);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "%s: colour matrix entry %d is not finite", tag, i);
+    std::vector<uint32_t> words;
+    int max_tiles = 0;
+    const uintptr_t base = (uintptr_t)frames;
+    if (const char* why = planar ? resize_plan_build_yuv((const vh_frame_yuv*)desc, batch, out_size, nbytes, (base & 1) == 0, chroma_site, 2, &words, &max_tiles)
+                                 : resize_plan_build_nv12((const vh_frame_nv12*)desc, batch, out_size, nbytes, (unsigned)(base & 3), chroma_site, 2, &words, &max_tiles))
+        return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    uint32_t* plan = nullptr;
+    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
+    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = planar ? launch_resize_yuv16(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream)
+                   : launch_resize_p016(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream);
+    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(plan);
+    OPCHK(e);
+    OPCHK(es);
+    return VH_OK;
+}
+
+int vh_op_resize_p016(const uint8_t* frames, size_t nbytes, const vh_frame_nv12* desc, int batch, int out_size, const float* m12,
+                      int chroma_site, uint8_t* out, void* stream) {
+    return op_resize16(frames, nbytes, desc, batch, out_size, m12, chroma_site, out, stream, false);
+}
+
+int vh_op_resize_yuv16(const uint8_t* frames, size_t nbytes, const vh_frame_yuv* desc, int batch, int out_size, const float* m12,
+                       int chroma_site, uint8_t* out, void* stream) {
+    return op_resize16(frames, nbytes, desc, batch, out_size, m12, chroma_site, out, stream, true);
 }
 
 int vh_op_cast(const float* in, void* out16, int64_t n, int dtype, void* stream) {

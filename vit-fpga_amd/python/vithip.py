@@ -109,6 +109,13 @@ SYMBOLS = {
     "vh_forward_device_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_frames_yuv": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_device_frames_yuv": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_yuv_matrix16": (_i, [_i, _i, _i, _i, _vp]),
+    "vh_set_frame_colour16": (_i, [_vp, _vp, _i]),
+    "vh_get_frame_colour16": (_i, [_vp, _vp, _pi]),
+    "vh_forward_frames_p016": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_p016": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_frames_yuv16": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_yuv16": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_fill_input_seeded": (_i, [_vp, _u64, _i, _vp]),
     "vh_last_forward_us": (_i, [_vp, C.POINTER(_i64)]),
     "vh_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
@@ -139,6 +146,8 @@ SYMBOLS = {
     "vh_ring_submit_frames": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_ring_submit_frames_nv12": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_ring_submit_frames_yuv": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_p016": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_yuv16": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_set_graph": (_i, [_vp, _i]),
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
@@ -171,6 +180,8 @@ SYMBOLS = {
     "vh_op_resize_u8": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp]),
     "vh_op_resize_nv12": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_yuv": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "vh_op_resize_p016": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "vh_op_resize_yuv16": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -422,6 +433,75 @@ def pack_frames_yuv(planes, boxes=None):
         d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
         parts += [np.ascontiguousarray(p).reshape(-1) for p in (y, u, v)]
         off += h * w + 2 * ch * cw
+    return np.concatenate(parts), desc
+
+
+def yuv_matrix16(standard=YUV_BT709, full_range=False, bits=10, msb_aligned=True):
+    """vh_yuv_matrix16: the 3 x 4 float32 matrix for 16-bit words that carry `bits`-bit codes (8..16) in their high bits
+    (msb_aligned: P010, P012, P016) or their low bits (yuv420p10le and its kin).  The default is P010 as a hardware decoder
+    writes it."""
+    m = np.zeros(12, np.float32)
+    _check(lib().vh_yuv_matrix16(standard, 1 if full_range else 0, bits, 1 if msb_aligned else 0, m.ctypes.data))
+    return m.reshape(3, 4)
+
+
+def _le16_bytes(a):
+    """A uint16 array as the bytes of little-endian words."""
+    return np.ascontiguousarray(a, dtype="<u2").reshape(-1).view(np.uint8)
+
+
+def pack_frames_p016(planes, boxes=None):
+    """pack_frames_nv12 for 16-bit samples (P010 / P012 / P016): a list of (Y [H, W] uint16, UV [H/2, W/2, 2] uint16) pairs ->
+    (one uint8 buffer of little-endian words, the (FrameNV12 * n) descriptors).  Offsets and strides are bytes
+    (y_stride = uv_stride = 2 W); width, height and box count samples."""
+    planes = [(np.asarray(y), np.asarray(uv)) for y, uv in planes]
+    if boxes is None:
+        boxes = [None] * len(planes)
+    if not planes or len(boxes) != len(planes):
+        raise ValueError("pack_frames_p016: one box (or None) per frame, at least one frame")
+    desc = (FrameNV12 * len(planes))()
+    parts, off = [], 0
+    for i, ((y, uv), box) in enumerate(zip(planes, boxes)):
+        if y.dtype != np.uint16 or uv.dtype != np.uint16 or y.ndim != 2 or uv.ndim != 3 or uv.shape[2] != 2:
+            raise TypeError(f"pack_frames_p016: frame {i} is not a ([H, W], [H/2, W/2, 2]) pair of uint16 arrays")
+        h, w = y.shape
+        if h % 2 or w % 2 or uv.shape[:2] != (h // 2, w // 2):
+            raise ValueError(f"pack_frames_p016: frame {i}: Y is {h} x {w}, UV is {uv.shape[0]} x {uv.shape[1]} pairs; want even sides and UV of half each")
+        desc[i].y_offset, desc[i].uv_offset = off, off + 2 * h * w
+        desc[i].height, desc[i].width, desc[i].y_stride, desc[i].uv_stride = h, w, 2 * w, 2 * w
+        desc[i].box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(v) for v in box)
+        parts += [_le16_bytes(y), _le16_bytes(uv)]
+        off += 3 * h * w
+    return np.concatenate(parts), desc
+
+
+def pack_frames_yuv16(planes, boxes=None):
+    """pack_frames_yuv for 16-bit samples (yuv420p10le, yuv422p10le, yuv444p12le, ...): a list of (Y, U, V) uint16 triples -> (one
+    uint8 buffer of little-endian words, the (FrameYUV * n) descriptors).  Offsets and strides are bytes; width, height, sub_x,
+    sub_y and box count samples."""
+    planes = [tuple(np.asarray(p) for p in t) for t in planes]
+    if boxes is None:
+        boxes = [None] * len(planes)
+    if not planes or len(boxes) != len(planes):
+        raise ValueError("pack_frames_yuv16: one box (or None) per frame, at least one frame")
+    desc = (FrameYUV * len(planes))()
+    parts, off = [], 0
+    for i, (t, box) in enumerate(zip(planes, boxes)):
+        if len(t) != 3 or any(p.dtype != np.uint16 or p.ndim != 2 or p.size == 0 for p in t):
+            raise TypeError(f"pack_frames_yuv16: frame {i} is not a (Y, U, V) triple of 2-d uint16 arrays")
+        y, u, v = t
+        try:
+            sx, sy = yuv_subsampling(y.shape, u.shape, v.shape)
+        except ValueError as e:
+            raise ValueError(f"pack_frames_yuv16: frame {i}: {e}") from None
+        h, w = y.shape
+        ch, cw = u.shape
+        d = desc[i]
+        d.y_offset, d.u_offset, d.v_offset = off, off + 2 * h * w, off + 2 * (h * w + ch * cw)
+        d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, 2 * w, 2 * cw, 2 * cw, sx, sy
+        d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
+        parts += [_le16_bytes(p) for p in (y, u, v)]
+        off += 2 * (h * w + 2 * ch * cw)
     return np.concatenate(parts), desc
 
 
@@ -745,6 +825,54 @@ class VitContext:
     def forward_device_frames_yuv(self, frames_ptr, nbytes, desc, out_ptr):
         _check(lib().vh_forward_device_frames_yuv(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
 
+    # ---- 16-bit YUV frames (P010 / P012 / P016 and planar yuv4xxpNNle): the same again, with a colour state of their own ----
+    def set_frame_colour16(self, m=None, chroma_site=CHROMA_LEFT):
+        """The colour state of the 16-bit entry points.  m: 12 floats (see yuv_matrix16); None restores the default, BT.709 limited
+        range, 10 bits, MSB-aligned (P010), left siting.  set_frame_colour's state is not touched."""
+        if m is None:
+            _check(lib().vh_set_frame_colour16(self.h, None, 0), self.h)
+            return
+        m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+        if m.size != 12:
+            raise ValueError(f"set_frame_colour16: expected 12 values, got {m.size}")
+        _check(lib().vh_set_frame_colour16(self.h, m.ctypes.data, chroma_site), self.h)
+
+    def get_frame_colour16(self):
+        m, site = np.empty(12, np.float32), C.c_int(0)
+        _check(lib().vh_get_frame_colour16(self.h, m.ctypes.data, C.byref(site)), self.h)
+        return m.reshape(3, 4), site.value
+
+    def forward_frames_p016(self, planes, boxes=None):
+        """planes: a list of (Y [H, W], UV [H/2, W/2, 2]) uint16 pairs (P010 / P012 / P016 words), any even sizes.  Returns the
+        bits forward_u8 gives for op_resize_p016's output under set_frame_colour16's state."""
+        buf, desc = pack_frames_p016(planes, boxes)
+        return self.forward_frames_p016_packed(buf, desc)
+
+    def forward_frames_p016_packed(self, buf, desc):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
+        _check(lib().vh_forward_frames_p016(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
+        return out
+
+    def forward_device_frames_p016(self, frames_ptr, nbytes, desc, out_ptr):
+        _check(lib().vh_forward_device_frames_p016(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+
+    def forward_frames_yuv16(self, planes, boxes=None):
+        """planes: a list of (Y [H, W], U [ch, cw], V [ch, cw]) uint16 triples, any sizes and sub-samplings.  Returns the bits
+        forward_u8 gives for op_resize_yuv16's output under set_frame_colour16's state (a yuv420p10le caller sets
+        yuv_matrix16(bits=10, msb_aligned=False))."""
+        buf, desc = pack_frames_yuv16(planes, boxes)
+        return self.forward_frames_yuv16_packed(buf, desc)
+
+    def forward_frames_yuv16_packed(self, buf, desc):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
+        _check(lib().vh_forward_frames_yuv16(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
+        return out
+
+    def forward_device_frames_yuv16(self, frames_ptr, nbytes, desc, out_ptr):
+        _check(lib().vh_forward_device_frames_yuv16(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
 
@@ -839,6 +967,32 @@ class VitContext:
             buf = np.ascontiguousarray(buf, dtype=np.uint8)
             ptr = buf.ctypes.data
         _check(lib().vh_ring_submit_frames_yuv(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+
+    def ring_submit_frames_p016(self, planes, boxes=None):
+        """P010 / P012 / P016 frames into the next slot of a frames ring; every kind of frames submit may alternate."""
+        buf, desc = pack_frames_p016(planes, boxes)
+        self.ring_submit_frames_p016_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_p016_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
+        ptr = None
+        if buf is not None:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            ptr = buf.ctypes.data
+        _check(lib().vh_ring_submit_frames_p016(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+
+    def ring_submit_frames_yuv16(self, planes, boxes=None):
+        """Planar 16-bit YUV frames into the next slot of a frames ring; every kind of frames submit may alternate."""
+        buf, desc = pack_frames_yuv16(planes, boxes)
+        self.ring_submit_frames_yuv16_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_yuv16_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
+        ptr = None
+        if buf is not None:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            ptr = buf.ctypes.data
+        _check(lib().vh_ring_submit_frames_yuv16(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
 
     def ring_free_slots(self):
         n = C.c_int(0)
@@ -1192,6 +1346,22 @@ def op_resize_yuv(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
     if m.size != 12:
         raise ValueError(f"op_resize_yuv: expected 12 matrix entries, got {m.size}")
     _check(lib().vh_op_resize_yuv(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
+
+
+def op_resize_p016(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """op_resize_nv12 for 16-bit samples: frames_ptr (device, 2-byte aligned), offsets and strides in bytes and even."""
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+    if m.size != 12:
+        raise ValueError(f"op_resize_p016: expected 12 matrix entries, got {m.size}")
+    _check(lib().vh_op_resize_p016(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
+
+
+def op_resize_yuv16(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """op_resize_yuv for 16-bit samples: frames_ptr (device, 2-byte aligned), offsets and strides in bytes and even."""
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+    if m.size != 12:
+        raise ValueError(f"op_resize_yuv16: expected 12 matrix entries, got {m.size}")
+    _check(lib().vh_op_resize_yuv16(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
 
 
 def op_resize_nv12(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
