@@ -412,8 +412,9 @@ resize_yuv_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restrict
     resize_yuv_body<PLANAR, T>(frames, plan, out, S, max_tiles, mat, lds, (int)blockIdx.x, (int)threadIdx.x, [] { __syncthreads(); });
 }
 
-static hipError_t launch_resize_any(bool planar, bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
-                                    const float* m12, uint8_t* out, hipStream_t s) {
+// the one launcher of the four instantiations; planar: three planes, not Y + interleaved UV.  wide: 16-bit samples
+hipError_t launch_resize_yuv_any(bool planar, bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
+                                 const float* m12, uint8_t* out, hipStream_t s) {
     if (!frames || !plan_dev || !out || !m12 || batch < 1 || S < 1 || max_tiles < 1 || (int64_t)batch * max_tiles > 0x7fffffffll)
         return hipErrorInvalidValue;
     Nv12Matrix mat;
@@ -429,57 +430,14 @@ static hipError_t launch_resize_any(bool planar, bool wide, const uint8_t* frame
         hipLaunchKernelGGL((resize_yuv_kernel<false, uint8_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     return hipGetLastError();
 }
-
-hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
-                              uint8_t* out, hipStream_t s) {
-    return launch_resize_any(false, false, frames, plan_dev, batch, S, max_tiles, m12, out, s);
-}
-
-hipError_t launch_resize_yuv(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
-                             uint8_t* out, hipStream_t s) {
-    return launch_resize_any(true, false, frames, plan_dev, batch, S, max_tiles, m12, out, s);
-}
-
-hipError_t launch_resize_p016(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
-                              uint8_t* out, hipStream_t s) {
-    return launch_resize_any(false, true, frames, plan_dev, batch, S, max_tiles, m12, out, s);
-}
-
-hipError_t launch_resize_yuv16(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
-                               uint8_t* out, hipStream_t s) {
-    return launch_resize_any(true, true, frames, plan_dev, batch, S, max_tiles, m12, out, s);
-}
 #endif
 
 // ---- host: the colour matrix -----------------------------------------------------------------------------------------------
 // Every expression is written as include/vithip.h states it and evaluated in IEEE double with no contraction, so that a numpy
 // float64 transcription gives, after the one rounding, the same fp32 entries.
 #pragma clang fp contract(off)
-int yuv_matrix(int standard, int full_range, float m[12]) {
-    double kr, kb;
-    switch (standard) {
-        case VH_YUV_BT601: kr = 0.299; kb = 0.114; break;
-        case VH_YUV_BT709: kr = 0.2126; kb = 0.0722; break;
-        case VH_YUV_BT2020: kr = 0.2627; kb = 0.0593; break;
-        default: return 1;
-    }
-    if (!m || (full_range != 0 && full_range != 1)) return 1;
-    const double kg = 1.0 - kr - kb;
-    const double sy = full_range ? 1.0 : 255.0 / 219.0, sc = full_range ? 1.0 : 255.0 / 224.0, oy = full_range ? 0.0 : 16.0;
-    const double rv = 2.0 * (1.0 - kr) * sc;
-    const double bu = 2.0 * (1.0 - kb) * sc;
-    const double gu = -(2.0 * kb * (1.0 - kb) / kg) * sc;
-    const double gv = -(2.0 * kr * (1.0 - kr) / kg) * sc;
-    const double yo = -(sy * oy);
-    const double v[12] = {sy, 0.0, rv, yo - 128.0 * rv,
-                          sy, gu, gv, yo - 128.0 * gu - 128.0 * gv,
-                          sy, bu, 0.0, yo - 128.0 * bu};
-    for (int i = 0; i < 12; ++i) m[i] = (float)v[i];
-    return 0;
-}
-
 // The matrix of 16-bit words: `bits` significant bits, in the high bits of the word (msb_aligned: P010 / P012 / P016) or the low
-// ones (yuv4xxpNNle).  bits = 8, msb_aligned = 0 gives yuv_matrix bit for bit (every factor it adds is then exactly 1).
+// ones (yuv4xxpNNle).
 int yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, float m[12]) {
     double kr, kb;
     switch (standard) {
@@ -507,5 +465,9 @@ int yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, float 
     for (int i = 0; i < 12; ++i) m[i] = (float)v[i];
     return 0;
 }
+
+// The matrix of bytes is the one of 8-bit codes in the low bits of the word, bit for bit: every factor yuv_matrix16 adds (a, q) is
+// then exactly 1, mid is exactly 128 and 2^8 - 1 is exactly 255, so each double expression has the value it had without them.
+int yuv_matrix(int standard, int full_range, float m[12]) { return yuv_matrix16(standard, full_range, 8, 0, m); }
 
 }  // namespace vh

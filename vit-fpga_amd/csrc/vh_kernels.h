@@ -135,26 +135,22 @@ int resize_axis_table_over(int n_in, double lo, double hi, double over, int n_ou
                            int max_taps);
 const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, size_t nbytes, unsigned base_mod4, int chroma_site,
                                    int sample_bytes, std::vector<uint32_t>* words, int* max_tiles);
-hipError_t launch_resize_nv12(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12_host,
-                              uint8_t* out_u8, hipStream_t stream);
 int yuv_matrix(int standard, int full_range, float m[12]);
 // Planar YUV frames (the same file and kernel body; contract: vithip.h, "Planar YUV frames"): three byte planes, chroma
 // sub-sampled by 1 or 2 per axis, any parity of the luma size.  resize_plan_build_yuv: as resize_plan_build_nv12, the same record
-// and tables; every refusal has a message of its own.  launch_resize_yuv: the planar instantiation of the kernel.
+// and tables; every refusal has a message of its own.
 const char* resize_plan_build_yuv(const vh_frame_yuv* desc, int batch, int S, size_t nbytes, bool base_even, int chroma_site, int sample_bytes,
                                   std::vector<uint32_t>* words, int* max_tiles);
-hipError_t launch_resize_yuv(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12_host,
-                             uint8_t* out_u8, hipStream_t stream);
 // 16-bit YUV frames (the same file, planners and kernel body; contract: vithip.h, "16-bit YUV frames").  Both planners take the
 // sample width: sample_bytes 1 = the byte layouts above, 2 = little-endian 16-bit words (P010 / P012 / P016, yuv4xxpNNle), whose
 // strides and spans are checked in bytes and whose offsets, strides and base must be even.  base_mod4: the frames address & 3 (0
-// for a host buffer); base_even: the same address is even.  launch_resize_p016 / _yuv16: the uint16_t instantiations.
+// for a host buffer); base_even: the same address is even.
 // yuv_matrix16: the matrix of `bits`-bit codes in the high (msb_aligned) or low bits of the word, host only; 0 = ok.
-hipError_t launch_resize_p016(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12_host,
-                              uint8_t* out_u8, hipStream_t stream);
-hipError_t launch_resize_yuv16(const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12_host,
-                               uint8_t* out_u8, hipStream_t stream);
 int yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, float m[12]);
+// launch_resize_yuv_any: one launch for the batch of any of the four layouts; planar picks the three-plane instantiations (a plan of
+// resize_plan_build_yuv) over the Y + UV ones (resize_plan_build_nv12), wide the uint16_t ones (plans built with sample_bytes 2).
+hipError_t launch_resize_yuv_any(bool planar, bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
+                                 const float* m12_host, uint8_t* out_u8, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
 bool patch_fused_supported(int image, int patch, int channels, int dim);

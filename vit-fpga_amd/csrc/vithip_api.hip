@@ -253,13 +253,11 @@ struct vh_ctx {
     uint8_t* rz_frames = nullptr;
     size_t rz_frames_cap = 0;
     std::vector<uint32_t> rz_words;
-    // NV12 and planar YUV frames (vh_set_frame_colour): the 3 x 4 matrix and the chroma siting of both kinds of entry points.  The
-    // matrix travels to resize_yuv_kernel by value at each launch, outside any captured graph.
-    float nv12_m[12];
-    int nv12_site = VH_CHROMA_LEFT;
-    // 16-bit YUV frames (vh_set_frame_colour16): a second state, because one frames ring interleaves 8-bit and 16-bit submits
-    float yuv16_m[12];
-    int yuv16_site = VH_CHROMA_LEFT;
+    // colour[0]: NV12 and planar YUV frames (vh_set_frame_colour): the 3 x 4 matrix and the chroma siting of both kinds of entry
+    // points.  The matrix travels to resize_yuv_kernel by value at each launch, outside any captured graph.
+    // colour[1]: 16-bit YUV frames (vh_set_frame_colour16): a second state, because one frames ring interleaves 8-bit and 16-bit submits
+    struct FrameColour { float m[12]; int site = VH_CHROMA_LEFT; };
+    FrameColour colour[2];
     int64_t last_us = 0;
     bool timed = false;
     int last_batch = 0;
@@ -959,41 +957,70 @@ int check_u8_ptr(vh_ctx* c, const void* in_dev) {
 }
 
 // ---- 8-bit frames: plan, buffers, the resize launch ---------------------------------------------------------------------------
+// One row per frame format: what differs between the formats, and nothing else.  Adding a format = one planner, one kernel
+// instantiation (or kernel), one row here and five one-line exports.
+// plan: checks `batch` descriptors of the row's type and builds the plan in `words`; nullptr, or why the call is refused.  base:
+// the device address of the frames, 0 for a host buffer or a ring slot (copied into hipMalloc'ed, hence aligned, memory).
+// launch: the one resize launch; m12: the matrix of the row's colour state.
+struct FrameFormat {
+    const char* tag;      // prefix of the operator tap's messages
+    const char* label;    // "<label> frames need a model with 3 channels"
+    const char* op_null;  // the tap's null-argument message: two of the five carry no tag
+    bool three_channels;  // the model must take 3 channels (a colour matrix has three rows)
+    int colour;           // index into vh_ctx::colour, -1: the format takes no matrix and no siting
+    const char* (*plan)(const void* desc, int batch, int channels, int S, size_t nbytes, uintptr_t base, int chroma_site,
+                        std::vector<uint32_t>* words, int* max_tiles);
+    hipError_t (*launch)(const uint8_t* frames, const uint32_t* plan_dev, int batch, int channels, int S, int max_tiles, const float* m12,
+                         uint8_t* out, hipStream_t stream);
+};
+
+template <int SAMPLE_BYTES>
+const char* plan_semi_planar(const void* desc, int batch, int, int S, size_t nbytes, uintptr_t base, int chroma_site, std::vector<uint32_t>* words,
+                             int* max_tiles) {
+    return resize_plan_build_nv12((const vh_frame_nv12*)desc, batch, S, nbytes, (unsigned)(base & 3), chroma_site, SAMPLE_BYTES, words, max_tiles);
+}
+template <int SAMPLE_BYTES>
+const char* plan_planar(const void* desc, int batch, int, int S, size_t nbytes, uintptr_t base, int chroma_site, std::vector<uint32_t>* words,
+                        int* max_tiles) {
+    return resize_plan_build_yuv((const vh_frame_yuv*)desc, batch, S, nbytes, (base & 1) == 0, chroma_site, SAMPLE_BYTES, words, max_tiles);
+}
+template <bool PLANAR, bool WIDE>
+hipError_t launch_yuv(const uint8_t* frames, const uint32_t* plan_dev, int batch, int, int S, int max_tiles, const float* m12, uint8_t* out,
+                      hipStream_t stream) {
+    return launch_resize_yuv_any(PLANAR, WIDE, frames, plan_dev, batch, S, max_tiles, m12, out, stream);
+}
+
+const char* plan_rgb(const void* desc, int batch, int channels, int S, size_t nbytes, uintptr_t base, int, std::vector<uint32_t>* words, int* max_tiles) {
+    return resize_plan_build((const vh_frame*)desc, batch, channels, S, nbytes, (base & 3) == 0, words, max_tiles);
+}
+hipError_t launch_rgb(const uint8_t* frames, const uint32_t* plan_dev, int batch, int channels, int S, int max_tiles, const float*, uint8_t* out,
+                      hipStream_t stream) {
+    return launch_resize_u8(frames, plan_dev, batch, channels, S, max_tiles, out, stream);
+}
+
+const FrameFormat kFramesRGB = {"resize_u8", "", "null buffer", false, -1, plan_rgb, launch_rgb};
+const FrameFormat kFramesNV12 = {"resize_nv12", "NV12", "null buffer", true, 0, plan_semi_planar<1>, launch_yuv<false, false>};
+// (the planar planner reads base_even only for 16-bit samples: whichever address reaches this row, its plan is the same)
+const FrameFormat kFramesYUV = {"resize_yuv", "planar YUV", "resize_yuv: null buffer", true, 0, plan_planar<1>, launch_yuv<true, false>};
+const FrameFormat kFramesP016 = {"resize_p016", "P016", "resize_p016: null buffer", true, 1, plan_semi_planar<2>, launch_yuv<false, true>};
+const FrameFormat kFramesYUV16 = {"resize_yuv16", "planar 16-bit YUV", "resize_yuv16: null buffer", true, 1, plan_planar<2>, launch_yuv<true, true>};
+
 // One resize in front of a forward: the frames in HBM and the descriptors + tables (c->rz_words) in pinned memory.
-enum { FRAMES_RGB = 0, FRAMES_NV12 = 1, FRAMES_YUV = 2, FRAMES_P016 = 3, FRAMES_YUV16 = 4 };   // the last two: 16-bit samples, the second colour state
 struct FrameJob {
+    const FrameFormat& fmt;
     const uint8_t* frames_dev;
     const uint32_t* plan_host;   // pinned; stays untouched until the upload below has run
     size_t words;
     int max_tiles;
-    int kind = FRAMES_RGB;       // FRAMES_NV12 / FRAMES_YUV: the plan of resize_plan_build_nv12 / _yuv, run by resize_yuv_kernel with the context's matrix
 };
 
 // checks the descriptors of one call and builds its plan in c->rz_words; nothing is enqueued
-int frames_plan(vh_ctx* c, const vh_frame* desc, int batch, size_t nbytes, bool base_aligned4, int* max_tiles) {
+int frames_plan(vh_ctx* c, const FrameFormat& fmt, const void* desc, int batch, size_t nbytes, uintptr_t base, int* max_tiles) {
     if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
-    const char* why = resize_plan_build(desc, batch, c->cfg.channels, c->cfg.image_size, nbytes, base_aligned4, &c->rz_words, max_tiles);
-    if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
-    return VH_OK;
-}
-
-// wide: P010 / P012 / P016 (16-bit words, the second colour state's siting); base: the frames address, 0 for a host buffer
-int frames_plan_nv12(vh_ctx* c, const vh_frame_nv12* desc, int batch, size_t nbytes, uintptr_t base, int* max_tiles, bool wide = false) {
-    if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
-    if (c->cfg.channels != 3)
-        return fail(&c->err, VH_ERR_INVALID, "%s frames need a model with 3 channels, this one has %d", wide ? "P016" : "NV12", c->cfg.channels);
-    const char* why = resize_plan_build_nv12(desc, batch, c->cfg.image_size, nbytes, (unsigned)(base & 3), wide ? c->yuv16_site : c->nv12_site,
-                                             wide ? 2 : 1, &c->rz_words, max_tiles);
-    if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
-    return VH_OK;
-}
-
-int frames_plan_yuv(vh_ctx* c, const vh_frame_yuv* desc, int batch, size_t nbytes, uintptr_t base, int* max_tiles, bool wide = false) {
-    if (!desc) return fail(&c->err, VH_ERR_INVALID, "null frame descriptors");
-    if (c->cfg.channels != 3)
-        return fail(&c->err, VH_ERR_INVALID, "planar %sYUV frames need a model with 3 channels, this one has %d", wide ? "16-bit " : "", c->cfg.channels);
-    const char* why = resize_plan_build_yuv(desc, batch, c->cfg.image_size, nbytes, (base & 1) == 0, wide ? c->yuv16_site : c->nv12_site, wide ? 2 : 1,
-                                            &c->rz_words, max_tiles);
+    if (fmt.three_channels && c->cfg.channels != 3)
+        return fail(&c->err, VH_ERR_INVALID, "%s frames need a model with 3 channels, this one has %d", fmt.label, c->cfg.channels);
+    const int site = fmt.colour < 0 ? 0 : c->colour[fmt.colour].site;
+    const char* why = fmt.plan(desc, batch, c->cfg.channels, c->cfg.image_size, nbytes, base, site, &c->rz_words, max_tiles);
     if (why) return fail(&c->err, VH_ERR_INVALID, "%s", why);
     return VH_OK;
 }
@@ -1046,16 +1073,8 @@ int enqueue_resize(vh_ctx* c, const FrameJob& j, int batch) {
     int rc;
     HIPCHK(&c->err, hipMemcpyAsync(c->rz_plan_dev, j.plan_host, j.words * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = tmark())) return rc;
-    if (j.kind == FRAMES_NV12)
-        HIPCHK(&c->err, launch_resize_nv12(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->nv12_m, c->rz_u8, c->stream));
-    else if (j.kind == FRAMES_YUV)
-        HIPCHK(&c->err, launch_resize_yuv(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->nv12_m, c->rz_u8, c->stream));
-    else if (j.kind == FRAMES_P016)
-        HIPCHK(&c->err, launch_resize_p016(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->yuv16_m, c->rz_u8, c->stream));
-    else if (j.kind == FRAMES_YUV16)
-        HIPCHK(&c->err, launch_resize_yuv16(j.frames_dev, c->rz_plan_dev, batch, c->cfg.image_size, j.max_tiles, c->yuv16_m, c->rz_u8, c->stream));
-    else
-        HIPCHK(&c->err, launch_resize_u8(j.frames_dev, c->rz_plan_dev, batch, c->cfg.channels, c->cfg.image_size, j.max_tiles, c->rz_u8, c->stream));
+    HIPCHK(&c->err, j.fmt.launch(j.frames_dev, c->rz_plan_dev, batch, c->cfg.channels, c->cfg.image_size, j.max_tiles,
+                                 j.fmt.colour < 0 ? nullptr : c->colour[j.fmt.colour].m, c->rz_u8, c->stream));
     return tmark();
 }
 
@@ -1284,10 +1303,8 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         c->in_scale[i] = i < cfg->channels ? 1.0f / 255.0f : 0.f;
         c->in_shift[i] = 0.f;
     }
-    yuv_matrix(VH_YUV_BT709, 0, c->nv12_m);   // NV12 frames: what an HD video decoder emits, until vh_set_frame_colour says otherwise
-    c->nv12_site = VH_CHROMA_LEFT;
-    yuv_matrix16(VH_YUV_BT709, 0, 10, 1, c->yuv16_m);   // 16-bit frames: P010 as VCN writes it, until vh_set_frame_colour16 says otherwise
-    c->yuv16_site = VH_CHROMA_LEFT;
+    yuv_matrix(VH_YUV_BT709, 0, c->colour[0].m);   // NV12 frames: what an HD video decoder emits, until vh_set_frame_colour says otherwise
+    yuv_matrix16(VH_YUV_BT709, 0, 10, 1, c->colour[1].m);   // 16-bit frames: P010 as VCN writes it, until vh_set_frame_colour16 says otherwise
     {
         // (fp8 operands: the hi plane is e4m3 -- the GEMM operand itself -- and the lo plane bf16: 3 bytes per element as well)
         const char* e = getenv("VH_RESID_SPLIT");
@@ -1647,151 +1664,73 @@ int vh_forward(vh_ctx* c, const float* in_host, int batch, float* logits_host) {
 
 int vh_forward_u8(vh_ctx* c, const uint8_t* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host, true}, batch, logits_host); }
 
-// 8-bit frames: check + plan on the host (nothing enqueued on a refusal), then resize -> u8 forward on the context's stream
+// Frames of any format: check + plan on the host (nothing enqueued on a refusal), then resize -> u8 forward on the context's stream.
+// The plan sees the device address, because the alignment of the frames decides which loads the kernel may use.
+static int forward_frames_device(vh_ctx* c, const FrameFormat& fmt, const uint8_t* frames_dev, size_t nbytes, const void* desc, int batch,
+                                 float* logits_dev) {
+    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan(c, fmt, desc, batch, nbytes, (uintptr_t)frames_dev, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{fmt, frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles};
+    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+}
+
+// the same from host memory: the frames are staged in c->rz_frames, whose base (hipMalloc) is aligned for any sample: base 0
+static int forward_frames_host(vh_ctx* c, const FrameFormat& fmt, const uint8_t* frames_host, size_t nbytes, const void* desc, int batch,
+                               float* logits_host) {
+    int rc = check_forward_args(c, frames_host, batch, logits_host);
+    if (rc) return rc;
+    int max_tiles = 0;
+    if ((rc = frames_plan(c, fmt, desc, batch, nbytes, 0, &max_tiles))) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
+    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
+    const FrameJob job{fmt, c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles};
+    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+}
+
+// 8-bit interleaved frames (kernels_resize.hip)
 int vh_forward_device_frames_u8(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame* desc, int batch, float* logits_dev) {
-    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
-    if (rc) return rc;
-    int max_tiles = 0;
-    if ((rc = frames_plan(c, desc, batch, nbytes, ((uintptr_t)frames_dev & 3) == 0, &max_tiles))) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles};
-    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+    return forward_frames_device(c, kFramesRGB, frames_dev, nbytes, desc, batch, logits_dev);
 }
-
 int vh_forward_frames_u8(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch, float* logits_host) {
-    int rc = check_forward_args(c, frames_host, batch, logits_host);
-    if (rc) return rc;
-    int max_tiles = 0;
-    if ((rc = frames_plan(c, desc, batch, nbytes, true, &max_tiles))) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles};
-    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+    return forward_frames_host(c, kFramesRGB, frames_host, nbytes, desc, batch, logits_host);
 }
-
-// NV12 frames: the same two entry points with the plan of resize_plan_build_nv12 (both planes + the colour matrix in one launch)
+// NV12 frames: the plan of resize_plan_build_nv12 (both planes + the colour matrix in one launch)
 int vh_forward_device_frames_nv12(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev) {
-    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
-    if (rc) return rc;
-    int max_tiles = 0;
-    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, (uintptr_t)frames_dev, &max_tiles))) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_NV12};
-    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+    return forward_frames_device(c, kFramesNV12, frames_dev, nbytes, desc, batch, logits_dev);
 }
-
 int vh_forward_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_host) {
-    int rc = check_forward_args(c, frames_host, batch, logits_host);
-    if (rc) return rc;
-    int max_tiles = 0;
-    if ((rc = frames_plan_nv12(c, desc, batch, nbytes, 0, &max_tiles))) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_NV12};
-    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+    return forward_frames_host(c, kFramesNV12, frames_host, nbytes, desc, batch, logits_host);
 }
-
-// planar YUV frames: the same two entry points with the plan of resize_plan_build_yuv
+// planar YUV frames: the plan of resize_plan_build_yuv
 int vh_forward_device_frames_yuv(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev) {
-    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
-    if (rc) return rc;
-    int max_tiles = 0;
-    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, 0, &max_tiles))) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_YUV};
-    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+    return forward_frames_device(c, kFramesYUV, frames_dev, nbytes, desc, batch, logits_dev);
 }
-
 int vh_forward_frames_yuv(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host) {
-    int rc = check_forward_args(c, frames_host, batch, logits_host);
-    if (rc) return rc;
-    int max_tiles = 0;
-    if ((rc = frames_plan_yuv(c, desc, batch, nbytes, 0, &max_tiles))) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, FRAMES_YUV};
-    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+    return forward_frames_host(c, kFramesYUV, frames_host, nbytes, desc, batch, logits_host);
 }
-
-// 16-bit YUV frames: the four entry points share one body each way; `planar` picks the descriptor type and the planner, both run
-// the uint16_t instantiation of the kernel with the second colour state
-static int forward_device_frames16(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const void* desc, int batch, float* logits_dev, bool planar) {
-    int rc = check_forward_args(c, frames_dev, batch, logits_dev);
-    if (rc) return rc;
-    int max_tiles = 0;
-    rc = planar ? frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, nbytes, (uintptr_t)frames_dev, &max_tiles, true)
-                : frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, nbytes, (uintptr_t)frames_dev, &max_tiles, true);
-    if (rc) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles, planar ? FRAMES_YUV16 : FRAMES_P016};
-    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
-}
-
-static int forward_frames16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const void* desc, int batch, float* logits_host, bool planar) {
-    int rc = check_forward_args(c, frames_host, batch, logits_host);
-    if (rc) return rc;
-    int max_tiles = 0;
-    rc = planar ? frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, nbytes, 0, &max_tiles, true)
-                : frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, nbytes, 0, &max_tiles, true);
-    if (rc) return rc;
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
-    memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
-    const FrameJob job{c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles, planar ? FRAMES_YUV16 : FRAMES_P016};
-    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
-}
-
+// 16-bit YUV frames: the same two descriptor types and planners, the uint16_t instantiations of the kernel, the second colour state
 int vh_forward_device_frames_p016(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev) {
-    return forward_device_frames16(c, frames_dev, nbytes, desc, batch, logits_dev, false);
+    return forward_frames_device(c, kFramesP016, frames_dev, nbytes, desc, batch, logits_dev);
 }
 int vh_forward_frames_p016(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_host) {
-    return forward_frames16(c, frames_host, nbytes, desc, batch, logits_host, false);
+    return forward_frames_host(c, kFramesP016, frames_host, nbytes, desc, batch, logits_host);
 }
 int vh_forward_device_frames_yuv16(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev) {
-    return forward_device_frames16(c, frames_dev, nbytes, desc, batch, logits_dev, true);
+    return forward_frames_device(c, kFramesYUV16, frames_dev, nbytes, desc, batch, logits_dev);
 }
 int vh_forward_frames_yuv16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host) {
-    return forward_frames16(c, frames_host, nbytes, desc, batch, logits_host, true);
+    return forward_frames_host(c, kFramesYUV16, frames_host, nbytes, desc, batch, logits_host);
 }
 
 int vh_yuv_matrix(int standard, int full_range, float m[12]) {
     if (yuv_matrix(standard, full_range, m))
         return fail(nullptr, VH_ERR_INVALID, "yuv matrix: standard must be VH_YUV_BT601, _BT709 or _BT2020, full_range 0 or 1, m not NULL");
-    return VH_OK;
-}
-
-// Colour matrix and chroma siting of the NV12 entry points.  The resize runs outside the captured graph and takes the matrix by
-// value at each launch: no graph to drop, nothing in flight to wait for.
-int vh_set_frame_colour(vh_ctx* c, const float m[12], int chroma_site) {
-    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
-    if (!m) {
-        yuv_matrix(VH_YUV_BT709, 0, c->nv12_m);
-        c->nv12_site = VH_CHROMA_LEFT;
-        return VH_OK;
-    }
-    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return fail(&c->err, VH_ERR_INVALID, "chroma_site %d is neither VH_CHROMA_CENTER nor VH_CHROMA_LEFT", chroma_site);
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(m[i])) return fail(&c->err, VH_ERR_INVALID, "colour matrix entry %d is not finite", i);
-    memcpy(c->nv12_m, m, sizeof c->nv12_m);
-    c->nv12_site = chroma_site;
-    return VH_OK;
-}
-
-int vh_get_frame_colour(const vh_ctx* c, float m[12], int* chroma_site) {
-    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
-    if (m) memcpy(m, c->nv12_m, sizeof c->nv12_m);
-    if (chroma_site) *chroma_site = c->nv12_site;
     return VH_OK;
 }
 
@@ -1801,29 +1740,43 @@ int vh_yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, flo
     return VH_OK;
 }
 
-// The second colour state: matrix and siting of the 16-bit entry points, under the rules of vh_set_frame_colour.  Neither call
-// touches the other's state.
-int vh_set_frame_colour16(vh_ctx* c, const float m[12], int chroma_site) {
+// Colour matrix and chroma siting of one of the two colour states.  The resize runs outside the captured graph and takes the matrix
+// by value at each launch: no graph to drop, nothing in flight to wait for.  m NULL: `dflt`, left siting.  word: "" or "16-bit ".
+static int set_frame_colour(vh_ctx* c, int which, const float m[12], int chroma_site, const float dflt[12], const char* word) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
-    if (!m) {
-        yuv_matrix16(VH_YUV_BT709, 0, 10, 1, c->yuv16_m);
-        c->yuv16_site = VH_CHROMA_LEFT;
-        return VH_OK;
+    if (m) {
+        if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return fail(&c->err, VH_ERR_INVALID, "chroma_site %d is neither VH_CHROMA_CENTER nor VH_CHROMA_LEFT", chroma_site);
+        for (int i = 0; i < 12; ++i)
+            if (!std::isfinite(m[i])) return fail(&c->err, VH_ERR_INVALID, "%scolour matrix entry %d is not finite", word, i);
     }
-    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT) return fail(&c->err, VH_ERR_INVALID, "chroma_site %d is neither VH_CHROMA_CENTER nor VH_CHROMA_LEFT", chroma_site);
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(m[i])) return fail(&c->err, VH_ERR_INVALID, "16-bit colour matrix entry %d is not finite", i);
-    memcpy(c->yuv16_m, m, sizeof c->yuv16_m);
-    c->yuv16_site = chroma_site;
+    memcpy(c->colour[which].m, m ? m : dflt, sizeof c->colour[which].m);
+    c->colour[which].site = m ? chroma_site : VH_CHROMA_LEFT;
     return VH_OK;
 }
 
-int vh_get_frame_colour16(const vh_ctx* c, float m[12], int* chroma_site) {
+static int get_frame_colour(const vh_ctx* c, int which, float m[12], int* chroma_site) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
-    if (m) memcpy(m, c->yuv16_m, sizeof c->yuv16_m);
-    if (chroma_site) *chroma_site = c->yuv16_site;
+    if (m) memcpy(m, c->colour[which].m, sizeof c->colour[which].m);
+    if (chroma_site) *chroma_site = c->colour[which].site;
     return VH_OK;
 }
+
+// the state of the NV12 and planar YUV entry points; default: BT.709 limited range
+int vh_set_frame_colour(vh_ctx* c, const float m[12], int chroma_site) {
+    float dflt[12];
+    yuv_matrix(VH_YUV_BT709, 0, dflt);
+    return set_frame_colour(c, 0, m, chroma_site, dflt, "");
+}
+int vh_get_frame_colour(const vh_ctx* c, float m[12], int* chroma_site) { return get_frame_colour(c, 0, m, chroma_site); }
+
+// The second colour state: matrix and siting of the 16-bit entry points, under the same rules; default: the same for P010.  Neither
+// call touches the other's state.
+int vh_set_frame_colour16(vh_ctx* c, const float m[12], int chroma_site) {
+    float dflt[12];
+    yuv_matrix16(VH_YUV_BT709, 0, 10, 1, dflt);
+    return set_frame_colour(c, 1, m, chroma_site, dflt, "16-bit ");
+}
+int vh_get_frame_colour16(const vh_ctx* c, float m[12], int* chroma_site) { return get_frame_colour(c, 1, m, chroma_site); }
 
 int vh_resize_table(int n_in, double lo, double hi, int n_out, int32_t* first, int32_t* count, float* weights, int max_taps) {
     if (resize_axis_table(n_in, lo, hi, n_out, first, count, weights, max_taps))
@@ -2013,11 +1966,10 @@ int vh_ring_input_frames(vh_ctx* c, uint8_t** pinned, size_t* capacity) {
 
 // frames ring: in_host holds `frame_bytes` of frames described by `desc`; the slot's upload is followed by the resize into
 // c->rz_u8 on the context's stream (forwards are ordered on that stream, so one resized buffer serves every slot)
-// (fkind FRAMES_NV12 / FRAMES_YUV: `desc` points to vh_frame_nv12 / vh_frame_yuv descriptors instead, FRAMES_P016 / FRAMES_YUV16: the
-// same two with 16-bit samples; a slot is raw bytes, so one frames ring takes all five.  A slot's device buffer comes from hipMalloc,
-// so its base is aligned for any sample)
+// (`desc` points to descriptors of the type `fmt` plans; a slot is raw bytes, so one frames ring takes all five formats.  A slot's
+// device buffer comes from hipMalloc, so its base is aligned for any sample: base 0)
 static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const void* desc = nullptr,
-                       int fkind = FRAMES_RGB) {
+                       const FrameFormat& fmt = kFramesRGB) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "no ring: call vh_ring_create first");
     if (c->ring_kind != kind) return fail(&c->err, VH_ERR_STATE, "this ring stages %s", ring_kind_name(c->ring_kind));
@@ -2028,10 +1980,7 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     int rc, max_tiles = 0;
     if (frames) {   // every check, and the plan, before anything is enqueued or the slot is touched
         if (frame_bytes < 1 || frame_bytes > c->ring_slot_bytes) return fail(&c->err, VH_ERR_INVALID, "nbytes %zu outside 1..slot_bytes=%zu", frame_bytes, c->ring_slot_bytes);
-        if (fkind == FRAMES_NV12 || fkind == FRAMES_P016) rc = frames_plan_nv12(c, (const vh_frame_nv12*)desc, batch, frame_bytes, 0, &max_tiles, fkind == FRAMES_P016);
-        else if (fkind == FRAMES_YUV || fkind == FRAMES_YUV16) rc = frames_plan_yuv(c, (const vh_frame_yuv*)desc, batch, frame_bytes, 0, &max_tiles, fkind == FRAMES_YUV16);
-        else rc = frames_plan(c, (const vh_frame*)desc, batch, frame_bytes, true, &max_tiles);
-        if (rc) return rc;
+        if ((rc = frames_plan(c, fmt, desc, batch, frame_bytes, 0, &max_tiles))) return rc;
     }
     HIPCHK(&c->err, hipSetDevice(c->device));
     vh_ctx::RingSlot& s = c->ring[c->ring_wr];
@@ -2053,7 +2002,7 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     HIPCHK(&c->err, hipEventRecord(s.in_done, c->copy_in));
     HIPCHK(&c->err, hipStreamWaitEvent(c->stream, s.in_done, 0));
     if (frames) {
-        const FrameJob job{(const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles, fkind};
+        const FrameJob job{fmt, (const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles};
         if ((rc = enqueue_resize(c, job, batch))) return rc;
     }
     rc = run_step(c, frames ? ImgIn{c->rz_u8, true} : ImgIn{s.d_in, kind == vh_ctx::RING_U8}, batch, s.d_out);
@@ -2070,19 +2019,19 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
 int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_F32); }
 int vh_ring_submit_u8(vh_ctx* c, const uint8_t* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_U8); }
 int vh_ring_submit_frames(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch) {
-    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc);
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesRGB);
 }
 int vh_ring_submit_frames_nv12(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch) {
-    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_NV12);
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesNV12);
 }
 int vh_ring_submit_frames_yuv(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch) {
-    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_YUV);
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesYUV);
 }
 int vh_ring_submit_frames_p016(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch) {
-    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_P016);
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesP016);
 }
 int vh_ring_submit_frames_yuv16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch) {
-    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, FRAMES_YUV16);
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesYUV16);
 }
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
@@ -2453,101 +2402,48 @@ int vh_op_im2col_u8(const uint8_t* in, int batch, int image, int patch, int chan
     return VH_OK;
 }
 
+// The resize of one format on its own: plan, upload, launch, wait.  m12 and chroma_site: of the formats that have a colour state.
+static int op_resize(const FrameFormat& fmt, const uint8_t* frames, size_t nbytes, const void* desc, int batch, int channels, int out_size,
+                     const float* m12, int chroma_site, uint8_t* out, void* stream) {
+    // every check before a device is touched
+    const bool colour = fmt.colour >= 0;
+    if (!frames || !desc || !out || (colour && !m12)) return fail(nullptr, VH_ERR_INVALID, "%s", fmt.op_null);
+    for (int i = 0; colour && i < 12; ++i)
+        if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "%s: colour matrix entry %d is not finite", fmt.tag, i);
+    std::vector<uint32_t> words;
+    int max_tiles = 0;
+    if (const char* why = fmt.plan(desc, batch, channels, out_size, nbytes, (uintptr_t)frames, chroma_site, &words, &max_tiles))
+        return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    uint32_t* plan = nullptr;
+    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
+    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = fmt.launch(frames, plan, batch, channels, out_size, max_tiles, m12, out, (hipStream_t)stream);
+    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(plan);
+    OPCHK(e);
+    OPCHK(es);
+    return VH_OK;
+}
+
 int vh_op_resize_u8(const uint8_t* frames, size_t nbytes, const vh_frame* desc, int batch, int channels, int out_size, uint8_t* out,
                     void* stream) {
-    if (!frames || !desc || !out) return fail(nullptr, VH_ERR_INVALID, "null buffer");
-    std::vector<uint32_t> words;
-    int max_tiles = 0;
-    if (const char* why = resize_plan_build(desc, batch, channels, out_size, nbytes, ((uintptr_t)frames & 3) == 0, &words, &max_tiles))
-        return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    uint32_t* plan = nullptr;
-    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
-    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = launch_resize_u8(frames, plan, batch, channels, out_size, max_tiles, out, (hipStream_t)stream);
-    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(plan);
-    OPCHK(e);
-    OPCHK(es);
-    return VH_OK;
+    return op_resize(kFramesRGB, frames, nbytes, desc, batch, channels, out_size, nullptr, 0, out, stream);
 }
-
 int vh_op_resize_nv12(const uint8_t* frames, size_t nbytes, const vh_frame_nv12* desc, int batch, int out_size, const float* m12,
                       int chroma_site, uint8_t* out, void* stream) {
-    // every check before a device is touched
-    if (!frames || !desc || !m12 || !out) return fail(nullptr, VH_ERR_INVALID, "null buffer");
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "resize_nv12: colour matrix entry %d is not finite", i);
-    std::vector<uint32_t> words;
-    int max_tiles = 0;
-    if (const char* why = resize_plan_build_nv12(desc, batch, out_size, nbytes, (unsigned)((uintptr_t)frames & 3), chroma_site, 1, &words, &max_tiles))
-        return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    uint32_t* plan = nullptr;
-    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
-    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = launch_resize_nv12(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream);
-    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(plan);
-    OPCHK(e);
-    OPCHK(es);
-    return VH_OK;
+    return op_resize(kFramesNV12, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
 }
-
 int vh_op_resize_yuv(const uint8_t* frames, size_t nbytes, const vh_frame_yuv* desc, int batch, int out_size, const float* m12,
                      int chroma_site, uint8_t* out, void* stream) {
-    // every check before a device is touched
-    if (!frames || !desc || !m12 || !out) return fail(nullptr, VH_ERR_INVALID, "resize_yuv: null buffer");
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "resize_yuv: colour matrix entry %d is not finite", i);
-    std::vector<uint32_t> words;
-    int max_tiles = 0;
-    if (const char* why = resize_plan_build_yuv(desc, batch, out_size, nbytes, true, chroma_site, 1, &words, &max_tiles))
-        return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    uint32_t* plan = nullptr;
-    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
-    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = launch_resize_yuv(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream);
-    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(plan);
-    OPCHK(e);
-    OPCHK(es);
-    return VH_OK;
+    return op_resize(kFramesYUV, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
 }
-
-// the 16-bit taps: `planar` picks the descriptor type, the planner and the launcher
-static int op_resize16(const uint8_t* frames, size_t nbytes, const void* desc, int batch, int out_size, const float* m12, int chroma_site, uint8_t* out,
-                       void* stream, bool planar) {
-    // every check before a device is touched
-    const char* tag = planar ? "resize_yuv16" : "resize_p016";
-    if (!frames || !desc || !m12 || !out) return fail(nullptr, VH_ERR_INVALID, "%s: null buffer", tag);
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(m12[i])) return fail(nullptr, VH_ERR_INVALID, "%s: colour matrix entry %d is not finite", tag, i);
-    std::vector<uint32_t> words;
-    int max_tiles = 0;
-    const uintptr_t base = (uintptr_t)frames;
-    if (const char* why = planar ? resize_plan_build_yuv((const vh_frame_yuv*)desc, batch, out_size, nbytes, (base & 1) == 0, chroma_site, 2, &words, &max_tiles)
-                                 : resize_plan_build_nv12((const vh_frame_nv12*)desc, batch, out_size, nbytes, (unsigned)(base & 3), chroma_site, 2, &words, &max_tiles))
-        return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    uint32_t* plan = nullptr;
-    OPCHK(hipMalloc((void**)&plan, words.size() * 4));
-    hipError_t e = hipMemcpyAsync(plan, words.data(), words.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess)
-        e = planar ? launch_resize_yuv16(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream)
-                   : launch_resize_p016(frames, plan, batch, out_size, max_tiles, m12, out, (hipStream_t)stream);
-    const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(plan);
-    OPCHK(e);
-    OPCHK(es);
-    return VH_OK;
-}
-
 int vh_op_resize_p016(const uint8_t* frames, size_t nbytes, const vh_frame_nv12* desc, int batch, int out_size, const float* m12,
                       int chroma_site, uint8_t* out, void* stream) {
-    return op_resize16(frames, nbytes, desc, batch, out_size, m12, chroma_site, out, stream, false);
+    return op_resize(kFramesP016, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
 }
-
 int vh_op_resize_yuv16(const uint8_t* frames, size_t nbytes, const vh_frame_yuv* desc, int batch, int out_size, const float* m12,
                        int chroma_site, uint8_t* out, void* stream) {
-    return op_resize16(frames, nbytes, desc, batch, out_size, m12, chroma_site, out, stream, true);
+    return op_resize(kFramesYUV16, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
 }
 
 int vh_op_cast(const float* in, void* out16, int64_t n, int dtype, void* stream) {

@@ -366,29 +366,41 @@ def yuv_matrix(standard=YUV_BT709, full_range=False):
     return m.reshape(3, 4)
 
 
-def pack_frames_nv12(planes, boxes=None):
-    """A list of (Y [H, W] uint8, UV [H/2, W/2, 2] uint8) pairs -> (one uint8 buffer, the (FrameNV12 * n) descriptors).  Each frame
-    lies as a decoder writes it: its Y plane, then its UV plane, rows unpadded (y_stride = uv_stride = W), frames back to back.
-    boxes: one (x0, y0, x1, y1) per frame in luma pixels, None = the whole frame."""
+def _sample_bytes(a):
+    """An array of samples as bytes: 16-bit words little-endian."""
+    return np.ascontiguousarray(a, dtype=a.dtype.newbyteorder("<")).reshape(-1).view(np.uint8)
+
+
+def _pack_semi_planar(name, dtype, planes, boxes):
+    """The body of pack_frames_nv12 / pack_frames_p016: (Y, UV) pairs of `dtype` samples -> (bytes, (FrameNV12 * n)); offsets and
+    strides in bytes."""
+    sb, tn = np.dtype(dtype).itemsize, np.dtype(dtype).name
     planes = [(np.asarray(y), np.asarray(uv)) for y, uv in planes]
     if boxes is None:
         boxes = [None] * len(planes)
     if not planes or len(boxes) != len(planes):
-        raise ValueError("pack_frames_nv12: one box (or None) per frame, at least one frame")
+        raise ValueError(f"{name}: one box (or None) per frame, at least one frame")
     desc = (FrameNV12 * len(planes))()
     parts, off = [], 0
     for i, ((y, uv), box) in enumerate(zip(planes, boxes)):
-        if y.dtype != np.uint8 or uv.dtype != np.uint8 or y.ndim != 2 or uv.ndim != 3 or uv.shape[2] != 2:
-            raise TypeError(f"pack_frames_nv12: frame {i} is not a ([H, W], [H/2, W/2, 2]) pair of uint8 arrays")
+        if y.dtype != dtype or uv.dtype != dtype or y.ndim != 2 or uv.ndim != 3 or uv.shape[2] != 2:
+            raise TypeError(f"{name}: frame {i} is not a ([H, W], [H/2, W/2, 2]) pair of {tn} arrays")
         h, w = y.shape
         if h % 2 or w % 2 or uv.shape[:2] != (h // 2, w // 2):
-            raise ValueError(f"pack_frames_nv12: frame {i}: Y is {h} x {w}, UV is {uv.shape[0]} x {uv.shape[1]} pairs; want even sides and UV of half each")
-        desc[i].y_offset, desc[i].uv_offset = off, off + h * w
-        desc[i].height, desc[i].width, desc[i].y_stride, desc[i].uv_stride = h, w, w, w
+            raise ValueError(f"{name}: frame {i}: Y is {h} x {w}, UV is {uv.shape[0]} x {uv.shape[1]} pairs; want even sides and UV of half each")
+        desc[i].y_offset, desc[i].uv_offset = off, off + sb * h * w
+        desc[i].height, desc[i].width, desc[i].y_stride, desc[i].uv_stride = h, w, sb * w, sb * w
         desc[i].box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(v) for v in box)
-        parts += [np.ascontiguousarray(y).reshape(-1), np.ascontiguousarray(uv).reshape(-1)]
-        off += h * w + h * w // 2
+        parts += [_sample_bytes(y), _sample_bytes(uv)]
+        off += sb * (h * w + h * w // 2)
     return np.concatenate(parts), desc
+
+
+def pack_frames_nv12(planes, boxes=None):
+    """A list of (Y [H, W] uint8, UV [H/2, W/2, 2] uint8) pairs -> (one uint8 buffer, the (FrameNV12 * n) descriptors).  Each frame
+    lies as a decoder writes it: its Y plane, then its UV plane, rows unpadded (y_stride = uv_stride = W), frames back to back.
+    boxes: one (x0, y0, x1, y1) per frame in luma pixels, None = the whole frame."""
+    return _pack_semi_planar("pack_frames_nv12", np.uint8, planes, boxes)
 
 
 def yuv_subsampling(y_shape, u_shape, v_shape):
@@ -405,35 +417,42 @@ def yuv_subsampling(y_shape, u_shape, v_shape):
     return sub[0], sub[1]
 
 
+def _pack_planar(name, dtype, planes, boxes):
+    """The body of pack_frames_yuv / pack_frames_yuv16: (Y, U, V) triples of `dtype` samples -> (bytes, (FrameYUV * n)); offsets and
+    strides in bytes."""
+    sb, tn = np.dtype(dtype).itemsize, np.dtype(dtype).name
+    planes = [tuple(np.asarray(p) for p in t) for t in planes]
+    if boxes is None:
+        boxes = [None] * len(planes)
+    if not planes or len(boxes) != len(planes):
+        raise ValueError(f"{name}: one box (or None) per frame, at least one frame")
+    desc = (FrameYUV * len(planes))()
+    parts, off = [], 0
+    for i, (t, box) in enumerate(zip(planes, boxes)):
+        if len(t) != 3 or any(p.dtype != dtype or p.ndim != 2 or p.size == 0 for p in t):
+            raise TypeError(f"{name}: frame {i} is not a (Y, U, V) triple of 2-d {tn} arrays")
+        y, u, v = t
+        try:
+            sx, sy = yuv_subsampling(y.shape, u.shape, v.shape)
+        except ValueError as e:
+            raise ValueError(f"{name}: frame {i}: {e}") from None
+        h, w = y.shape
+        ch, cw = u.shape
+        d = desc[i]
+        d.y_offset, d.u_offset, d.v_offset = off, off + sb * h * w, off + sb * (h * w + ch * cw)
+        d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, sb * w, sb * cw, sb * cw, sx, sy
+        d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
+        parts += [_sample_bytes(p) for p in (y, u, v)]
+        off += sb * (h * w + 2 * ch * cw)
+    return np.concatenate(parts), desc
+
+
 def pack_frames_yuv(planes, boxes=None):
     """A list of (Y [H, W], U [ch, cw], V [ch, cw]) uint8 triples -> (one uint8 buffer, the (FrameYUV * n) descriptors).  The
     sub-sampling of each frame is inferred from the shapes (yuv_subsampling) and an inconsistent triple is refused.  Each frame
     lies as a decoder writes I420: Y, U, V, rows unpadded, frames back to back.  boxes: one (x0, y0, x1, y1) per frame in luma
     pixels, None = the whole frame."""
-    planes = [tuple(np.asarray(p) for p in t) for t in planes]
-    if boxes is None:
-        boxes = [None] * len(planes)
-    if not planes or len(boxes) != len(planes):
-        raise ValueError("pack_frames_yuv: one box (or None) per frame, at least one frame")
-    desc = (FrameYUV * len(planes))()
-    parts, off = [], 0
-    for i, (t, box) in enumerate(zip(planes, boxes)):
-        if len(t) != 3 or any(p.dtype != np.uint8 or p.ndim != 2 or p.size == 0 for p in t):
-            raise TypeError(f"pack_frames_yuv: frame {i} is not a (Y, U, V) triple of 2-d uint8 arrays")
-        y, u, v = t
-        try:
-            sx, sy = yuv_subsampling(y.shape, u.shape, v.shape)
-        except ValueError as e:
-            raise ValueError(f"pack_frames_yuv: frame {i}: {e}") from None
-        h, w = y.shape
-        ch, cw = u.shape
-        d = desc[i]
-        d.y_offset, d.u_offset, d.v_offset = off, off + h * w, off + h * w + ch * cw
-        d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, w, cw, cw, sx, sy
-        d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
-        parts += [np.ascontiguousarray(p).reshape(-1) for p in (y, u, v)]
-        off += h * w + 2 * ch * cw
-    return np.concatenate(parts), desc
+    return _pack_planar("pack_frames_yuv", np.uint8, planes, boxes)
 
 
 def yuv_matrix16(standard=YUV_BT709, full_range=False, bits=10, msb_aligned=True):
@@ -445,64 +464,18 @@ def yuv_matrix16(standard=YUV_BT709, full_range=False, bits=10, msb_aligned=True
     return m.reshape(3, 4)
 
 
-def _le16_bytes(a):
-    """A uint16 array as the bytes of little-endian words."""
-    return np.ascontiguousarray(a, dtype="<u2").reshape(-1).view(np.uint8)
-
-
 def pack_frames_p016(planes, boxes=None):
     """pack_frames_nv12 for 16-bit samples (P010 / P012 / P016): a list of (Y [H, W] uint16, UV [H/2, W/2, 2] uint16) pairs ->
     (one uint8 buffer of little-endian words, the (FrameNV12 * n) descriptors).  Offsets and strides are bytes
     (y_stride = uv_stride = 2 W); width, height and box count samples."""
-    planes = [(np.asarray(y), np.asarray(uv)) for y, uv in planes]
-    if boxes is None:
-        boxes = [None] * len(planes)
-    if not planes or len(boxes) != len(planes):
-        raise ValueError("pack_frames_p016: one box (or None) per frame, at least one frame")
-    desc = (FrameNV12 * len(planes))()
-    parts, off = [], 0
-    for i, ((y, uv), box) in enumerate(zip(planes, boxes)):
-        if y.dtype != np.uint16 or uv.dtype != np.uint16 or y.ndim != 2 or uv.ndim != 3 or uv.shape[2] != 2:
-            raise TypeError(f"pack_frames_p016: frame {i} is not a ([H, W], [H/2, W/2, 2]) pair of uint16 arrays")
-        h, w = y.shape
-        if h % 2 or w % 2 or uv.shape[:2] != (h // 2, w // 2):
-            raise ValueError(f"pack_frames_p016: frame {i}: Y is {h} x {w}, UV is {uv.shape[0]} x {uv.shape[1]} pairs; want even sides and UV of half each")
-        desc[i].y_offset, desc[i].uv_offset = off, off + 2 * h * w
-        desc[i].height, desc[i].width, desc[i].y_stride, desc[i].uv_stride = h, w, 2 * w, 2 * w
-        desc[i].box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(v) for v in box)
-        parts += [_le16_bytes(y), _le16_bytes(uv)]
-        off += 3 * h * w
-    return np.concatenate(parts), desc
+    return _pack_semi_planar("pack_frames_p016", np.uint16, planes, boxes)
 
 
 def pack_frames_yuv16(planes, boxes=None):
     """pack_frames_yuv for 16-bit samples (yuv420p10le, yuv422p10le, yuv444p12le, ...): a list of (Y, U, V) uint16 triples -> (one
     uint8 buffer of little-endian words, the (FrameYUV * n) descriptors).  Offsets and strides are bytes; width, height, sub_x,
     sub_y and box count samples."""
-    planes = [tuple(np.asarray(p) for p in t) for t in planes]
-    if boxes is None:
-        boxes = [None] * len(planes)
-    if not planes or len(boxes) != len(planes):
-        raise ValueError("pack_frames_yuv16: one box (or None) per frame, at least one frame")
-    desc = (FrameYUV * len(planes))()
-    parts, off = [], 0
-    for i, (t, box) in enumerate(zip(planes, boxes)):
-        if len(t) != 3 or any(p.dtype != np.uint16 or p.ndim != 2 or p.size == 0 for p in t):
-            raise TypeError(f"pack_frames_yuv16: frame {i} is not a (Y, U, V) triple of 2-d uint16 arrays")
-        y, u, v = t
-        try:
-            sx, sy = yuv_subsampling(y.shape, u.shape, v.shape)
-        except ValueError as e:
-            raise ValueError(f"pack_frames_yuv16: frame {i}: {e}") from None
-        h, w = y.shape
-        ch, cw = u.shape
-        d = desc[i]
-        d.y_offset, d.u_offset, d.v_offset = off, off + 2 * h * w, off + 2 * (h * w + ch * cw)
-        d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, 2 * w, 2 * cw, 2 * cw, sx, sy
-        d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
-        parts += [_le16_bytes(p) for p in (y, u, v)]
-        off += 2 * (h * w + 2 * ch * cw)
-    return np.concatenate(parts), desc
+    return _pack_planar("pack_frames_yuv16", np.uint16, planes, boxes)
 
 
 def make_config(cfg, dtype=DTYPE_BF16, max_batch=1, ln_eps=1e-6, flags=0):
@@ -761,6 +734,37 @@ class VitContext:
     def forward_device_u8_async(self, in_ptr, batch, out_ptr, steps=1):
         _check(lib().vh_forward_device_u8_async(self.h, in_ptr, batch, out_ptr, steps), self.h)
 
+    # ---- frames of any format: one body per job; `fn` is the format's C entry point, `desc` its descriptor array ----
+    def _forward_frames_host(self, fn, buf, desc):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
+        _check(fn(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
+        return out
+
+    def _forward_frames_device(self, fn, frames_ptr, nbytes, desc, out_ptr):
+        _check(fn(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+
+    def _ring_submit_frames(self, fn, buf, nbytes, desc):
+        ptr = None
+        if buf is not None:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            ptr = buf.ctypes.data
+        _check(fn(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+
+    def _set_colour(self, name, fn, m, chroma_site):
+        if m is None:
+            _check(fn(self.h, None, 0), self.h)
+            return
+        m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+        if m.size != 12:
+            raise ValueError(f"{name}: expected 12 values, got {m.size}")
+        _check(fn(self.h, m.ctypes.data, chroma_site), self.h)
+
+    def _get_colour(self, fn):
+        m, site = np.empty(12, np.float32), C.c_int(0)
+        _check(fn(self.h, m.ctypes.data, C.byref(site)), self.h)
+        return m.reshape(3, 4), site.value
+
     # ---- 8-bit frames of any size: antialiased resize + crop on the GPU, then forward_u8 of the result ----
     def forward_frames(self, frames, boxes=None):
         """frames: a list of HWC uint8 arrays, any sizes; boxes: one (x0, y0, x1, y1) per frame in source pixels (None = the
@@ -769,29 +773,18 @@ class VitContext:
         return self.forward_frames_packed(buf, desc)
 
     def forward_frames_packed(self, buf, desc):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
-        _check(lib().vh_forward_frames_u8(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
-        return out
+        return self._forward_frames_host(lib().vh_forward_frames_u8, buf, desc)
 
     def forward_device_frames_u8(self, frames_ptr, nbytes, desc, out_ptr):
-        _check(lib().vh_forward_device_frames_u8(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+        self._forward_frames_device(lib().vh_forward_device_frames_u8, frames_ptr, nbytes, desc, out_ptr)
 
     # ---- NV12 video frames: both planes resized and the colour matrix applied on the GPU, then forward_u8 of the result ----
     def set_frame_colour(self, m=None, chroma_site=CHROMA_LEFT):
         """m: 12 floats (row-major 3 x 4, see yuv_matrix); None restores the default, BT.709 limited range with left siting."""
-        if m is None:
-            _check(lib().vh_set_frame_colour(self.h, None, 0), self.h)
-            return
-        m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
-        if m.size != 12:
-            raise ValueError(f"set_frame_colour: expected 12 values, got {m.size}")
-        _check(lib().vh_set_frame_colour(self.h, m.ctypes.data, chroma_site), self.h)
+        self._set_colour("set_frame_colour", lib().vh_set_frame_colour, m, chroma_site)
 
     def get_frame_colour(self):
-        m, site = np.empty(12, np.float32), C.c_int(0)
-        _check(lib().vh_get_frame_colour(self.h, m.ctypes.data, C.byref(site)), self.h)
-        return m.reshape(3, 4), site.value
+        return self._get_colour(lib().vh_get_frame_colour)
 
     def forward_frames_nv12(self, planes, boxes=None):
         """planes: a list of (Y [H, W], UV [H/2, W/2, 2]) uint8 pairs, any even sizes; boxes as forward_frames, in luma pixels.
@@ -800,13 +793,10 @@ class VitContext:
         return self.forward_frames_nv12_packed(buf, desc)
 
     def forward_frames_nv12_packed(self, buf, desc):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
-        _check(lib().vh_forward_frames_nv12(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
-        return out
+        return self._forward_frames_host(lib().vh_forward_frames_nv12, buf, desc)
 
     def forward_device_frames_nv12(self, frames_ptr, nbytes, desc, out_ptr):
-        _check(lib().vh_forward_device_frames_nv12(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+        self._forward_frames_device(lib().vh_forward_device_frames_nv12, frames_ptr, nbytes, desc, out_ptr)
 
     # ---- planar YUV frames (I420 / YV12, JPEG's 4:4:4 / 4:2:2 / 4:2:0 / 4:4:0 planes): the same, from three planes ----
     def forward_frames_yuv(self, planes, boxes=None):
@@ -817,30 +807,19 @@ class VitContext:
         return self.forward_frames_yuv_packed(buf, desc)
 
     def forward_frames_yuv_packed(self, buf, desc):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
-        _check(lib().vh_forward_frames_yuv(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
-        return out
+        return self._forward_frames_host(lib().vh_forward_frames_yuv, buf, desc)
 
     def forward_device_frames_yuv(self, frames_ptr, nbytes, desc, out_ptr):
-        _check(lib().vh_forward_device_frames_yuv(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+        self._forward_frames_device(lib().vh_forward_device_frames_yuv, frames_ptr, nbytes, desc, out_ptr)
 
     # ---- 16-bit YUV frames (P010 / P012 / P016 and planar yuv4xxpNNle): the same again, with a colour state of their own ----
     def set_frame_colour16(self, m=None, chroma_site=CHROMA_LEFT):
         """The colour state of the 16-bit entry points.  m: 12 floats (see yuv_matrix16); None restores the default, BT.709 limited
         range, 10 bits, MSB-aligned (P010), left siting.  set_frame_colour's state is not touched."""
-        if m is None:
-            _check(lib().vh_set_frame_colour16(self.h, None, 0), self.h)
-            return
-        m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
-        if m.size != 12:
-            raise ValueError(f"set_frame_colour16: expected 12 values, got {m.size}")
-        _check(lib().vh_set_frame_colour16(self.h, m.ctypes.data, chroma_site), self.h)
+        self._set_colour("set_frame_colour16", lib().vh_set_frame_colour16, m, chroma_site)
 
     def get_frame_colour16(self):
-        m, site = np.empty(12, np.float32), C.c_int(0)
-        _check(lib().vh_get_frame_colour16(self.h, m.ctypes.data, C.byref(site)), self.h)
-        return m.reshape(3, 4), site.value
+        return self._get_colour(lib().vh_get_frame_colour16)
 
     def forward_frames_p016(self, planes, boxes=None):
         """planes: a list of (Y [H, W], UV [H/2, W/2, 2]) uint16 pairs (P010 / P012 / P016 words), any even sizes.  Returns the
@@ -849,13 +828,10 @@ class VitContext:
         return self.forward_frames_p016_packed(buf, desc)
 
     def forward_frames_p016_packed(self, buf, desc):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
-        _check(lib().vh_forward_frames_p016(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
-        return out
+        return self._forward_frames_host(lib().vh_forward_frames_p016, buf, desc)
 
     def forward_device_frames_p016(self, frames_ptr, nbytes, desc, out_ptr):
-        _check(lib().vh_forward_device_frames_p016(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+        self._forward_frames_device(lib().vh_forward_device_frames_p016, frames_ptr, nbytes, desc, out_ptr)
 
     def forward_frames_yuv16(self, planes, boxes=None):
         """planes: a list of (Y [H, W], U [ch, cw], V [ch, cw]) uint16 triples, any sizes and sub-samplings.  Returns the bits
@@ -865,13 +841,10 @@ class VitContext:
         return self.forward_frames_yuv16_packed(buf, desc)
 
     def forward_frames_yuv16_packed(self, buf, desc):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        out = np.empty((len(desc), self.cfg["classes"]), dtype=np.float32)
-        _check(lib().vh_forward_frames_yuv16(self.h, buf.ctypes.data, buf.nbytes, C.addressof(desc), len(desc), out.ctypes.data), self.h)
-        return out
+        return self._forward_frames_host(lib().vh_forward_frames_yuv16, buf, desc)
 
     def forward_device_frames_yuv16(self, frames_ptr, nbytes, desc, out_ptr):
-        _check(lib().vh_forward_device_frames_yuv16(self.h, frames_ptr, nbytes, C.addressof(desc), len(desc), out_ptr), self.h)
+        self._forward_frames_device(lib().vh_forward_device_frames_yuv16, frames_ptr, nbytes, desc, out_ptr)
 
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
@@ -936,11 +909,7 @@ class VitContext:
 
     def ring_submit_frames_packed(self, buf, nbytes, desc):
         """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of frames that desc describes."""
-        ptr = None
-        if buf is not None:
-            buf = np.ascontiguousarray(buf, dtype=np.uint8)
-            ptr = buf.ctypes.data
-        _check(lib().vh_ring_submit_frames(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+        self._ring_submit_frames(lib().vh_ring_submit_frames, buf, nbytes, desc)
 
     def ring_submit_frames_nv12(self, planes, boxes=None):
         """NV12 frames into the next slot of a frames ring (ring_create_frames); RGB and NV12 submits may alternate."""
@@ -949,11 +918,7 @@ class VitContext:
 
     def ring_submit_frames_nv12_packed(self, buf, nbytes, desc):
         """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
-        ptr = None
-        if buf is not None:
-            buf = np.ascontiguousarray(buf, dtype=np.uint8)
-            ptr = buf.ctypes.data
-        _check(lib().vh_ring_submit_frames_nv12(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+        self._ring_submit_frames(lib().vh_ring_submit_frames_nv12, buf, nbytes, desc)
 
     def ring_submit_frames_yuv(self, planes, boxes=None):
         """Planar YUV frames into the next slot of a frames ring; RGB, NV12 and planar submits may alternate."""
@@ -962,11 +927,7 @@ class VitContext:
 
     def ring_submit_frames_yuv_packed(self, buf, nbytes, desc):
         """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
-        ptr = None
-        if buf is not None:
-            buf = np.ascontiguousarray(buf, dtype=np.uint8)
-            ptr = buf.ctypes.data
-        _check(lib().vh_ring_submit_frames_yuv(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+        self._ring_submit_frames(lib().vh_ring_submit_frames_yuv, buf, nbytes, desc)
 
     def ring_submit_frames_p016(self, planes, boxes=None):
         """P010 / P012 / P016 frames into the next slot of a frames ring; every kind of frames submit may alternate."""
@@ -975,11 +936,7 @@ class VitContext:
 
     def ring_submit_frames_p016_packed(self, buf, nbytes, desc):
         """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
-        ptr = None
-        if buf is not None:
-            buf = np.ascontiguousarray(buf, dtype=np.uint8)
-            ptr = buf.ctypes.data
-        _check(lib().vh_ring_submit_frames_p016(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+        self._ring_submit_frames(lib().vh_ring_submit_frames_p016, buf, nbytes, desc)
 
     def ring_submit_frames_yuv16(self, planes, boxes=None):
         """Planar 16-bit YUV frames into the next slot of a frames ring; every kind of frames submit may alternate."""
@@ -988,11 +945,7 @@ class VitContext:
 
     def ring_submit_frames_yuv16_packed(self, buf, nbytes, desc):
         """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
-        ptr = None
-        if buf is not None:
-            buf = np.ascontiguousarray(buf, dtype=np.uint8)
-            ptr = buf.ctypes.data
-        _check(lib().vh_ring_submit_frames_yuv16(self.h, ptr, nbytes, C.addressof(desc), len(desc)), self.h)
+        self._ring_submit_frames(lib().vh_ring_submit_frames_yuv16, buf, nbytes, desc)
 
     def ring_free_slots(self):
         n = C.c_int(0)
@@ -1339,38 +1292,34 @@ def op_resize_u8(frames_ptr, nbytes, desc, channels, out_size, out_ptr):
     _check(lib().vh_op_resize_u8(frames_ptr, nbytes, C.addressof(desc), len(desc), channels, out_size, out_ptr, None))
 
 
+def _op_resize_colour(name, fn, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """The body of the four taps that take a colour matrix; `fn` is the format's C tap."""
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+    if m.size != 12:
+        raise ValueError(f"{name}: expected 12 matrix entries, got {m.size}")
+    _check(fn(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
+
+
 def op_resize_yuv(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
     """The resize + colour conversion of the planar YUV entry points on its own: the planes at frames_ptr (device, any alignment)
     described by the (FrameYUV * n) array desc -> [n, out_size, out_size, 3] bytes at out_ptr.  m: 12 floats, row-major 3 x 4."""
-    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
-    if m.size != 12:
-        raise ValueError(f"op_resize_yuv: expected 12 matrix entries, got {m.size}")
-    _check(lib().vh_op_resize_yuv(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
+    _op_resize_colour("op_resize_yuv", lib().vh_op_resize_yuv, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
 
 
 def op_resize_p016(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
     """op_resize_nv12 for 16-bit samples: frames_ptr (device, 2-byte aligned), offsets and strides in bytes and even."""
-    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
-    if m.size != 12:
-        raise ValueError(f"op_resize_p016: expected 12 matrix entries, got {m.size}")
-    _check(lib().vh_op_resize_p016(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
+    _op_resize_colour("op_resize_p016", lib().vh_op_resize_p016, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
 
 
 def op_resize_yuv16(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
     """op_resize_yuv for 16-bit samples: frames_ptr (device, 2-byte aligned), offsets and strides in bytes and even."""
-    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
-    if m.size != 12:
-        raise ValueError(f"op_resize_yuv16: expected 12 matrix entries, got {m.size}")
-    _check(lib().vh_op_resize_yuv16(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
+    _op_resize_colour("op_resize_yuv16", lib().vh_op_resize_yuv16, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
 
 
 def op_resize_nv12(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
     """The resize + colour conversion of the NV12 entry points on its own: the planes at frames_ptr (device, any alignment)
     described by the (FrameNV12 * n) array desc -> [n, out_size, out_size, 3] bytes at out_ptr.  m: 12 floats, row-major 3 x 4."""
-    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
-    if m.size != 12:
-        raise ValueError(f"op_resize_nv12: expected 12 matrix entries, got {m.size}")
-    _check(lib().vh_op_resize_nv12(frames_ptr, nbytes, C.addressof(desc), len(desc), out_size, m.ctypes.data, chroma_site, out_ptr, None))
+    _op_resize_colour("op_resize_nv12", lib().vh_op_resize_nv12, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
 
 
 def op_cast(in_ptr, out_ptr, n, dtype):
