@@ -378,7 +378,8 @@ int vh_forward_device_frames_yuv(vh_ctx* ctx, const uint8_t* frames_dev, size_t 
  *       the last byte of each plane lies within nbytes;
  *       a DEVICE frames pointer must be 2-byte aligned; a host pointer may have any alignment, because it is copied.
  * Parity and size rules are those of the 8-bit layout: semi-planar needs even sizes within 2..8192, planar takes any parity
- * within 1..8192.  Big-endian words and packed formats (Y210, Y410, v210) are not taken.
+ * within 1..8192.  Big-endian words are not taken; packed 4:2:2 words (Y210, Y216, v210) go to "Packed 4:2:2 frames" below; packed
+ * 4:4:4 (Y410, AYUV) is not taken.
  * SAMPLE VALUES.  The word enters the arithmetic AS IS, as the fp32 value of the unsigned integer 0..65535 (exact).  The kernel
  * does not shift, mask or scale: depth and alignment live in the matrix alone.  A P010 word with non-zero low bits is simply a
  * P016 value.
@@ -429,6 +430,58 @@ int vh_forward_frames_p016(vh_ctx* ctx, const uint8_t* frames_host, size_t nbyte
 int vh_forward_device_frames_p016(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_nv12* desc, int batch, float* logits_dev);
 int vh_forward_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host);
 int vh_forward_device_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_dev);
+/* ---- Packed 4:2:2 frames: YUY2 / UYVY, Y210 / Y216 and v210 ---------------------------------------------------------------------
+ * What cameras and capture cards deliver: UVC webcams and V4L2 write YUYV (YUY2); HDMI / SDI capture cards (DeckLink, AJA,
+ * Magewell) and AVFoundation write UYVY (2vuy) in 8 bit and v210 in 10 bit; D3D / VA-API surfaces and ffmpeg's y210le are Y210 /
+ * Y216.  A PACKED FRAME is ONE plane of macropixels at `offset`, rows row_stride bytes apart; all formats share vh_frame_yuy2.
+ * MACROPIXEL.  A row is cw = (width + 1) / 2 macropixels of two luma samples and one (U, V) pair.  width and height count luma
+ * SAMPLES, are within 1..8192 and of ANY parity; an odd width leaves the second luma of the last macropixel unread (it must still
+ * lie within the row and within nbytes).  `box` means what it means in vh_frame_yuv: luma pixel coordinates.  The context must have
+ * channels == 3.  Layout: sizeof(vh_frame_yuy2) == 40; offset 0, height 8, width 12, row_stride 16, layout 20, box 24.
+ * 8-BIT ENTRY POINTS (_yuy2).  A macropixel is 4 bytes in the order of `layout`: VH_422_YUYV = Y0 U Y1 V, VH_422_UYVY = U Y0 V Y1,
+ * VH_422_YVYU = Y0 V Y1 U, VH_422_VYUY = V Y0 U Y1.  row_stride >= 4 * cw.  Base, offset and stride may have any alignment.  The
+ * matrix and the siting are those of vh_set_frame_colour.  VH_422_V210 is refused.
+ * 16-BIT ENTRY POINTS (_y210), layouts 0..3.  A macropixel is four little-endian 16-bit words in the order of `layout`: Y210 / Y212 /
+ * Y216 with VH_422_YUYV.  row_stride >= 8 * cw; offset and row_stride must be even and a DEVICE frames pointer 2-byte aligned (a
+ * host pointer may have any alignment, because it is copied).  The word enters the arithmetic AS IS, as in P016 ("16-bit YUV
+ * frames", SAMPLE VALUES).  The matrix and the siting are those of vh_set_frame_colour16, whose default, 10 bits MSB-aligned, is
+ * Y210 as drivers write it.
+ * VH_422_V210 (16-bit entry points only).  A row is ceil(width / 6) blocks of four little-endian 32-bit words.  The twelve 10-bit
+ * codes of a block sit in bits 0-9, 10-19 and 20-29 of the successive words, in the order
+ *       U0 Y0 V0 | Y1 U1 Y2 | V1 Y3 U2 | Y4 V2 Y5;
+ * bits 30-31 are ignored.  row_stride >= 16 * ceil(width / 6); offset and row_stride must be multiples of 4 and a device frames
+ * pointer 4-byte aligned.  A code enters the arithmetic as the fp32 value code * 64 (exact): the Y210 / P010 word of that code.  A
+ * v210 frame and the Y210 frame of the same codes therefore share the colour state and give the SAME BYTES.
+ * EVERYTHING ELSE is "Planar YUV frames" / "16-bit YUV frames" with sub_x = 2, sub_y = 1, word for word: the luma box as given, the
+ * chroma box (lo / 2 + delta, hi / 2 + delta) with delta = 0.25 under VH_CHROMA_LEFT and the quarter-sample overhang that goes with
+ * it, the axis tables (vh_resize_table), horizontal then vertical fp32 fmaf chains in ascending tap order from 0 with nothing rounded
+ * in between, the nested-fmaf matrix expression and the one rounding rintf(min(max(out[k], 0), 255)).  EQUIVALENCE: the output bytes
+ * are those of vh_op_resize_yuv (vh_op_resize_yuv16) on the de-interleaved planes (Y height x width, U and V height x cw, sub_x = 2,
+ * sub_y = 1), BIT FOR BIT, and the logits are BIT-IDENTICAL to vh_forward_u8 of vh_op_resize_yuy2's (vh_op_resize_y210's) output.
+ * Packed 4:4:4 (AYUV, Y410, v410), 4:1:1 and big-endian words are not taken.
+ * REFUSED with VH_ERR_INVALID before a device is touched or anything is enqueued, each with a message of its own: width or height
+ * outside 1..8192; a layout that is none of VH_422_*, or VH_422_V210 on the 8-bit entry points; row_stride below the widths above;
+ * an offset, a stride or a device frames pointer that is odd (16-bit words) or no multiple of 4 (v210); a frame whose last byte
+ * lies beyond nbytes; a box outside the frame, or empty; scale > 32 on an axis; channels != 3; null pointers.
+ *   vh_forward_frames_yuy2, vh_forward_device_frames_yuy2: vh_forward_frames_yuv / vh_forward_device_frames_yuv for 8-bit packed
+ *                       frames, the same argument list with vh_frame_yuy2 descriptors.
+ *   vh_forward_frames_y210, vh_forward_device_frames_y210: vh_forward_frames_yuv16 / vh_forward_device_frames_yuv16 for Y210 /
+ *                       Y216 / v210 frames.  Stage "resize" of vh_set_stage_timing times these launches too. */
+#define VH_422_YUYV 0   /* Y0 U Y1 V   (YUY2, V4L2 YUYV)            */
+#define VH_422_UYVY 1   /* U Y0 V Y1   (UYVY, 2vuy, HDYC)           */
+#define VH_422_YVYU 2   /* Y0 V Y1 U                                */
+#define VH_422_VYUY 3   /* V Y0 U Y1                                */
+#define VH_422_V210 4   /* 10-bit, three codes per 32-bit word; 16-bit entry points only */
+typedef struct vh_frame_yuy2 {
+    uint64_t offset;
+    int32_t height, width, row_stride;   /* samples, samples, bytes */
+    int32_t layout;                      /* VH_422_*               */
+    float box[4];
+} vh_frame_yuy2;
+int vh_forward_frames_yuy2(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_host);
+int vh_forward_device_frames_yuy2(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_dev);
+int vh_forward_frames_y210(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_host);
+int vh_forward_device_frames_y210(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_dev);
 /* uniform[-1,1) synthetic images written straight into HBM (value range of the reference,
  * def/defines.h:11-12) */
 int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_dev);
@@ -483,6 +536,12 @@ int vh_ring_submit_frames_yuv(vh_ctx* ctx, const uint8_t* frames_host, size_t nb
  * bits vh_forward_frames_p016 / vh_forward_frames_yuv16 returns. */
 int vh_ring_submit_frames_p016(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch);
 int vh_ring_submit_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch);
+/* Packed 4:2:2 frames ("Packed 4:2:2 frames" above) on the SAME frames ring, interleaved with every other kind of submit; _yuy2
+ * uses the first colour state, _y210 (Y210 / Y216 / v210) the second.  The same rules: checked and copied before anything is
+ * enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other two kinds of ring.  A collected batch has the
+ * bits vh_forward_frames_yuy2 / vh_forward_frames_y210 returns. */
+int vh_ring_submit_frames_yuy2(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch);
+int vh_ring_submit_frames_y210(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -682,6 +741,13 @@ int vh_op_resize_p016(const uint8_t* frames_dev, size_t nbytes, const vh_frame_n
                       const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 int vh_op_resize_yuv16(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuv* desc_host, int batch, int out_size,
                        const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
+/* The same tap for packed 4:2:2 frames ("Packed 4:2:2 frames"): the arguments of vh_op_resize_yuv / vh_op_resize_yuv16 with
+ * vh_frame_yuy2 descriptors.  _yuy2: any alignment.  _y210: frames_dev 2-byte aligned, offsets and strides even (v210: multiples
+ * of 4).  Every argument and descriptor is checked before a device is touched. */
+int vh_op_resize_yuy2(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc_host, int batch, int out_size,
+                      const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
+int vh_op_resize_y210(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc_host, int batch, int out_size,
+                      const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,

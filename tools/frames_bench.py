@@ -32,6 +32,14 @@ the same pictures and the frames ring fed their P010 frames (10-bit code = 8-bit
 the same two shapes, boxes, passes and medians.  P010 uploads 3 bytes per pixel, as RGB does and twice what NV12 does.  Under the two
 default colour states the NV12 and the P010 ring compute the same logits, which is checked.  Then the resize launch of each of the
 three.  Written to <out>/yuv16_host_path.txt and .json.
+
+  python tools/frames_bench.py --yuy2 [--out profiles] [--steps 30] [--passes 3]
+
+Packed 4:2:2 passes, ViT-B/16 bf16, in ONE process: the frames rings fed RGB frames, the NV12 frames, the planar
+4:2:2 planes, the YUY2 frames of those planes and their v210 frames (10-bit code = 8-bit code x 4), the same two shapes, boxes, passes
+and medians.  YUY2 uploads 2 bytes per pixel, v210 16 bytes per 6 pixels.  The planar 4:2:2, the YUY2 and the v210 ring compute the
+same logits under the two default colour states, which is checked.  Then the resize launch of each of the five.  Written to
+<out>/packed422_host_path.txt and .json.
 """
 import argparse
 import json
@@ -208,6 +216,106 @@ class SideP010(SideNV12):
 
     def submit(self):
         self.ctx.ring_submit_frames_p016_packed(None, self.nbytes, self.desc)
+
+
+class SideRaw(SideNV12):
+    """One context with a frames ring fed `buf` [B, bytes per frame] as `desc` describes it; submit: the name of the ring submit."""
+
+    def __init__(self, cfg, dname, batch, flags, eps, scale, shift, buf, desc, box_bytes, submit):
+        self.batch, self.frames = batch, True
+        self.ctx = vithip.VitContext(cfg, dtype=DT[dname], max_batch=batch, flags=flags, ln_eps=eps)
+        self.ctx.init_weights_seeded(0)
+        self.ctx.set_input_norm(scale, shift)
+        self.nbytes, self.desc, self.box_bytes = buf.nbytes, desc, box_bytes
+        self.call = getattr(self.ctx, submit)
+        self.ctx.ring_create_frames(SLOTS, batch, self.nbytes)
+        for _ in range(SLOTS):
+            self.ctx.ring_input_frames()[:self.nbytes] = buf.reshape(-1)
+            self.submit()
+        self.first = [self.ctx.ring_collect().copy() for _ in range(SLOTS)][0]
+
+    def submit(self):
+        self.call(None, self.nbytes, self.desc)
+
+
+def yuy2_main(a):
+    import nv12_ref as N
+    import packed422_ref as P
+    import yuv_ref as Y
+    lines, rows = [], []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    scale, shift = vithip.input_norm_from_mean_std(MEAN, STD)
+    title, key, cfg, dname, _, flags, eps = RUNS[0]
+    log(f"frames_bench --yuy2: {title[:-5]}, frames rings of {SLOTS} slots, {a.steps} steps per pass, {a.passes} interleaved passes (RGB frames, "
+        f"the NV12 frames, the planar 4:2:2 planes, the YUY2 and the v210 frames of the same pictures, v210 code = byte x 4; 0.875 centre box); "
+        f"median pass [min .. max]; images/s")
+    for h, w, batch in ((360, 480, 512), (1080, 1920, 64)):
+        rng = np.random.default_rng(3)
+        small = rng.integers(0, 256, size=(batch, h // 8, w // 8, 3), dtype=np.uint8)
+        rgb = np.ascontiguousarray(np.repeat(np.repeat(small, 8, axis=1), 8, axis=2))     # the pictures of --nv12
+        rgb ^= rng.integers(0, 8, size=rgb.shape, dtype=np.uint8)
+        box = vithip.center_crop_box(h, w)
+        inside = batch * (box[2] - box[0]) * (box[3] - box[1])
+        common = (cfg, dname, batch, flags, eps, scale, shift)
+        nv = [N.rgb_to_nv12(f) for f in rgb]
+        p422 = [Y.rgb_to_yuv_planes(f, 2, 1) for f in rgb]
+        cw = w // 2
+        planar = np.stack([np.concatenate([p.reshape(-1) for p in t]) for t in p422])
+        yuy2 = np.stack([P.interleave(*t, P.YUYV).reshape(-1) for t in p422])
+        v210 = np.stack([P.to_v210(*(p.astype(np.uint16) << 2 for p in t)).astype("<u4").view(np.uint8).reshape(-1) for t in p422])
+        dpl, dyu, dv2 = (vithip.FrameYUV * batch)(), (vithip.FrameYUY2 * batch)(), (vithip.FrameYUY2 * batch)()
+        for b in range(batch):
+            d, per = dpl[b], planar.shape[1]
+            d.y_offset, d.u_offset, d.v_offset = b * per, b * per + h * w, b * per + h * w + h * cw
+            d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, w, cw, cw, 2, 1
+            d.box[:] = box
+            for d, buf, lay in ((dyu[b], yuy2, P.YUYV), (dv2[b], v210, P.V210)):
+                d.offset, d.height, d.width, d.row_stride, d.layout = b * buf.shape[1], h, w, buf.shape[1] // h, lay
+                d.box[:] = box
+        sides = dict(rgb=Side(*common, frames=rgb, box=box),
+                     nv12=SideNV12(*common, y=np.stack([p[0] for p in nv]), uv=np.stack([p[1] for p in nv]), box=box),
+                     p422=SideRaw(*common, planar, dpl, inside * 2.0, "ring_submit_frames_yuv_packed"),
+                     yuy2=SideRaw(*common, yuy2, dyu, inside * 2.0, "ring_submit_frames_yuy2_packed"),
+                     v210=SideRaw(*common, v210, dv2, inside * 16.0 / 6.0, "ring_submit_frames_y210_packed"))
+        del rgb, nv, p422, planar, yuy2, v210
+        bits = lambda k: sides[k].first.view(np.uint32)
+        same = bool(np.array_equal(bits("p422"), bits("yuy2")) and np.array_equal(bits("p422"), bits("v210")) and np.isfinite(sides["yuy2"].first).all())
+        rates = {k: [] for k in sides}
+        for _ in range(a.passes):
+            for k, sd in sides.items():
+                rates[k].append(sd.ring_rate(a.steps))
+        us = {k: [] for k in sides}
+        for _ in range(2):                                                                 # two interleaved passes of the launch alone
+            for k, sd in sides.items():
+                us[k].append(sd.resize_us(8))
+        r = dict(config=key, frame=[h, w], batch=batch, logits_yuy2_and_v210_equal_planar_422=same,
+                 ring={k: mid(v) for k, v in rates.items()}, h2d_MB_per_step={k: sd.nbytes / 1e6 for k, sd in sides.items()},
+                 bytes_per_pixel={k: sd.nbytes / (batch * h * w) for k, sd in sides.items()},
+                 resize_us_avg={k: [t[0] for t in v] for k, v in us.items()}, resize_us_min={k: min(t[1] for t in v) for k, v in us.items()},
+                 box_MB={k: sd.box_bytes / 1e6 for k, sd in sides.items()})
+        rows.append(r)
+        log(f"{h}x{w}, batch {batch}: logits of the YUY2 and the v210 ring equal the planar 4:2:2 ring's bit for bit: {same}")
+        for k, sd in sides.items():
+            m, lo, hi = r["ring"][k]
+            log(f"    frames ring, {k.upper():4s}: {m:9.0f} [{lo:9.0f} .. {hi:9.0f}] = {100 * m / r['ring']['rgb'][0]:6.2f} % of the RGB ring, "
+                f"{100 * m / r['ring']['p422'][0]:6.2f} % of the planar 4:2:2 ring | upload {sd.nbytes / 1e6:7.1f} MB per step "
+                f"({r['bytes_per_pixel'][k]:.3f} bytes per pixel) = {sd.nbytes * 1e-9 * m / batch:5.1f} GB/s")
+        for k, sd in sides.items():
+            avg, mb = r["resize_us_avg"][k], sd.box_bytes / 1e6
+            t = float(np.mean(avg))
+            log(f"    resize {k.upper():4s}: {t:8.1f} us per launch avg ({r['resize_us_min'][k]:.1f} min; passes {avg[0]:.1f} {avg[1]:.1f}) | "
+                f"{mb:.1f} MB inside the boxes = {mb * 1e-3 / (t * 1e-6):.0f} GB/s")
+        for sd in sides.values():
+            sd.close()
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "packed422_host_path.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+    with open(os.path.join(a.out, "packed422_host_path.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 def p010_main(a):
@@ -389,7 +497,10 @@ def main():
     ap.add_argument("--nv12", action="store_true", help="the NV12 passes (RGB frames ring against NV12 frames ring) instead")
     ap.add_argument("--yuv420p", action="store_true", help="the planar passes (NV12 frames ring against I420 frames ring) instead")
     ap.add_argument("--p010", action="store_true", help="the 10-bit passes (RGB, NV12 and P010 frames rings of the same pictures) instead")
+    ap.add_argument("--yuy2", action="store_true", help="the packed 4:2:2 passes (RGB, NV12, planar 4:2:2, YUY2 and v210 frames rings) instead")
     a = ap.parse_args()
+    if a.yuy2:
+        return yuy2_main(a)
     if a.p010:
         return p010_main(a)
     if a.yuv420p:

@@ -12,10 +12,13 @@
 // Use: yuv_host_check CASE OUT.  tools/yuv_host_check.py writes the case files, runs this program over them and compares OUT with the
 // fp32 emulation of tests/yuv_ref.py.
 //
-// CASE (little endian): int32 layout (bit 0: 1 = vh_frame_yuv descriptors, 0 = vh_frame_nv12; bit 1: 16-bit samples), S, batch,
-// chroma_site; float m[12]; uint64 nbytes; the descriptors; nbytes of frames.  OUT: [batch][S][S][3] bytes.
+// CASE (little endian): int32 layout (bit 0: 1 = vh_frame_yuv descriptors, 0 = vh_frame_nv12; bit 1: 16-bit samples; bit 2: packed
+// 4:2:2, vh_frame_yuy2 descriptors, bit 0 then unread; bit 3: the frames start one sample (1 or 2 bytes) into their heap block, so
+// that the base itself is what breaks the macropixel alignment), S, batch, chroma_site; float m[12]; uint64 nbytes; the
+// descriptors; nbytes of frames.  OUT: [batch][S][S][3] bytes.
 // With 16-bit samples UBSan's alignment check watches every uint16_t and uint32_t load: the planner's even-offset rule (and its
-// multiple-of-4 rule for the pair load) has to be what makes them aligned.
+// multiple-of-4 rule for the pair load) has to be what makes them aligned.  The same holds for the packed layouts' 32-bit and 64-bit
+// macropixel loads and for v210's 32-bit words.
 #include <pthread.h>
 
 #include <cstdio>
@@ -48,19 +51,24 @@ int main(int argc, char** argv) {
     uint64_t nbytes;
     if (!rd(f, &layout) || !rd(f, &S) || !rd(f, &batch) || !rd(f, &site) || !rd(f, m, 12) || !rd(f, &nbytes) || batch < 1 || batch > 4096)
         return die("short case file");
-    const bool planar = layout & 1, wide = layout & 2;
+    const bool packed = layout & 4, planar = !packed && (layout & 1), wide = layout & 2;
+    const size_t shift = layout & 8 ? (wide ? 2 : 1) : 0;
     std::vector<vh_frame_yuv> dy(planar ? batch : 0);
-    std::vector<vh_frame_nv12> dn(planar ? 0 : batch);
-    if (planar ? !rd(f, dy.data(), (size_t)batch) : !rd(f, dn.data(), (size_t)batch)) return die("short descriptors");
-    uint8_t* frames = (uint8_t*)malloc(nbytes);                      // exact size: the byte behind the last plane is poisoned
-    if (!frames || !rd(f, frames, (size_t)nbytes)) return die("short frames");
+    std::vector<vh_frame_nv12> dn(planar || packed ? 0 : batch);
+    std::vector<vh_frame_yuy2> dp(packed ? batch : 0);
+    if (packed ? !rd(f, dp.data(), (size_t)batch) : planar ? !rd(f, dy.data(), (size_t)batch) : !rd(f, dn.data(), (size_t)batch))
+        return die("short descriptors");
+    uint8_t* block = (uint8_t*)malloc(nbytes + shift);               // exact size: the byte behind the last plane is poisoned
+    uint8_t* frames = block + shift;
+    if (!block || !rd(f, frames, (size_t)nbytes)) return die("short frames");
     fclose(f);
 
     std::vector<uint32_t> words;
     int max_tiles = 0;
     const uintptr_t base = (uintptr_t)frames;
-    const char* why = planar ? vh::resize_plan_build_yuv(dy.data(), batch, S, (size_t)nbytes, (base & 1) == 0, site, wide ? 2 : 1, &words, &max_tiles)
-                             : vh::resize_plan_build_nv12(dn.data(), batch, S, (size_t)nbytes, (unsigned)(base & 3), site, wide ? 2 : 1, &words, &max_tiles);
+    const char* why = packed ? vh::resize_plan_build_yuy2(dp.data(), batch, S, (size_t)nbytes, (unsigned)(base & 7), site, wide ? 2 : 1, &words, &max_tiles)
+                    : planar ? vh::resize_plan_build_yuv(dy.data(), batch, S, (size_t)nbytes, (base & 1) == 0, site, wide ? 2 : 1, &words, &max_tiles)
+                    : vh::resize_plan_build_nv12(dn.data(), batch, S, (size_t)nbytes, (unsigned)(base & 3), site, wide ? 2 : 1, &words, &max_tiles);
     if (why) {
         printf("refused: %s\n", why);
         return 3;
@@ -82,7 +90,9 @@ int main(int argc, char** argv) {
     auto item = [&](int tid) {
         auto barrier = [&] { pthread_barrier_wait(&bar); };
         for (int b = 0; b < blocks; ++b) {
-            if (planar && wide) vh::resize_yuv_body<true, uint16_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            if (packed && wide) vh::resize_yuv_body<true, uint16_t, true>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            else if (packed) vh::resize_yuv_body<true, uint8_t, true>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            else if (planar && wide) vh::resize_yuv_body<true, uint16_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
             else if (planar) vh::resize_yuv_body<true, uint8_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
             else if (wide) vh::resize_yuv_body<false, uint16_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
             else vh::resize_yuv_body<false, uint8_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
@@ -94,18 +104,21 @@ int main(int argc, char** argv) {
     for (std::thread& t : pool) t.join();
     pthread_barrier_destroy(&bar);
 
-    int bands = 0, tiles = 0;
+    int bands = 0, tiles = 0, wide_loads = 0;
     for (int b = 0; b < batch; ++b) {
         vh::RzNv12 r;
         memcpy(&r, plan + (size_t)b * vh::kResizeNv12FrameWords, sizeof r);
         const int nb = (S + r.band_rows - 1) / r.band_rows, nc = (S + r.tile_cols - 1) / r.tile_cols;
         if (nb > bands) bands = nb;
         if (nc > tiles) tiles = nc;
+        wide_loads += r.uv16;
     }
-    printf("ok: %d frame(s) -> %d, %zu plan words, %d workgroups (at most %d bands x %d column tiles a frame)\n", batch, S, words.size(), blocks, bands, tiles);
+    printf("ok: %d frame(s) -> %d, %zu plan words, %d workgroups (at most %d bands x %d column tiles a frame)", batch, S, words.size(), blocks, bands, tiles);
+    if (packed) printf(", %d frame(s) with one load per macropixel", wide_loads);
+    printf("\n");
     FILE* g = fopen(argv[2], "wb");
     if (!g || fwrite(out, 1, nout, g) != nout) return die("cannot write the output");
     fclose(g);
-    free(lds); free(out); free(plan); free(frames);
+    free(lds); free(out); free(plan); free(block);
     return 0;
 }

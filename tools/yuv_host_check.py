@@ -5,10 +5,14 @@ chroma column, a mixed batch, 40 small frames, one 1080 x 1920 frame and the two
 and compares each output with the fp32 emulation of tests/yuv_ref.py byte for byte.  Then the 16-bit instantiations:
 the same operator cases with real 10 / 12 / 16-bit planes, all-0xFFFF words, even offsets and strides that are no multiple of 4
 (UBSan's alignment check on every uint16_t and uint32_t load is what shows that the planner's even-offset rule suffices), both pair-load
-paths of P016, a mixed batch, 40 small frames, one 1080 x 1920 P010 frame and the 4:4:4 planner boundary.  CPU only; no device is
-touched.
+paths of P016, a mixed batch, 40 small frames, one 1080 x 1920 P010 frame and the 4:4:4 planner boundary.  Then the packed 4:2:2
+instantiations: every layout of YUY2 and Y210 over the cases of tests/test_packed422.py, v210 at every width mod 6
+with bits 30-31 set, every offset, stride padding and base alignment either side of the one-load-per-macropixel rule, a mixed batch,
+40 small frames and one 1080 x 1920 UYVY and v210 frame, each compared with the emulation of the DE-INTERLEAVED planes.  CPU only;
+no device is touched.
 
-    python tools/yuv_host_check.py            (needs libvithip.so: make -C vit-fpga_amd)"""
+    python tools/yuv_host_check.py            (needs libvithip.so: make -C vit-fpga_amd)
+    python tools/yuv_host_check.py --packed   (the packed 4:2:2 cases alone)"""
 import os
 import struct
 import subprocess
@@ -31,6 +35,8 @@ from test_nv12 import make_nv12  # noqa: E402
 from test_yuv16 import COLOURS16, make_yuv16  # noqa: E402
 from test_yuv_planar import COLOURS, OP_CASES, SUBS, make_yuv  # noqa: E402
 import yuv16_ref as W  # noqa: E402
+import packed422_ref as P  # noqa: E402
+from test_packed422 import PACKED_CASES, V210_WIDTHS  # noqa: E402
 
 EXE = os.path.join(ROOT, "tools", "yuv_host_check")
 PKG = os.path.join(ROOT, "vit-fpga_amd")
@@ -68,6 +74,100 @@ def run(tmp, label, planes, boxes, s, m, site, subs, wide=False, **layout):
     same = np.array_equal(got, want)
     print(f"{'ok  ' if same else 'DIFF'} {label}: {p.stdout.strip()}")
     return same
+
+
+def run_packed(tmp, label, planes, boxes, s, m, site, layouts, shift_base=False, **layout):
+    """One call of the packed instantiations; `planes` are the de-interleaved (Y, U, V) triples (v210: 10-bit codes), the emulation
+    is that of the planar 4:2:2 frame (v210: of the codes << 6)."""
+    wide = planes[0][0].dtype == np.uint16
+    buf, desc = P.lay_out(planes, boxes, layouts, **layout)
+    case, out = os.path.join(tmp, "case.bin"), os.path.join(tmp, "out.bin")
+    with open(case, "wb") as f:
+        f.write(struct.pack("<4i", 4 | (2 if wide else 0) | (8 if shift_base else 0), s, len(planes), site))
+        f.write(np.ascontiguousarray(m, np.float32).tobytes())
+        f.write(struct.pack("<Q", buf.nbytes))
+        f.write(bytes(desc))
+        f.write(buf.tobytes())
+    p = subprocess.run([EXE, case, out], capture_output=True, text=True)
+    if p.returncode:
+        print(f"FAIL {label}: exit {p.returncode}\n{p.stdout}{p.stderr}")
+        return False
+    got = np.fromfile(out, np.uint8).reshape(len(planes), s, s, 3)
+    words = lambda yuv, d: tuple((a << 6).astype(np.uint16) for a in yuv) if d.layout == P.V210 else yuv
+    want = np.stack([Y.resize_yuv_f32(*words(yuv, d), box, s, m, site, P.SUB) for yuv, box, d in zip(planes, boxes, desc)])
+    same = np.array_equal(got, want)
+    print(f"{'ok  ' if same else 'DIFF'} packed {label}: {p.stdout.strip()}")
+    return same
+
+
+CODES10 = "bt2020_limited_10_lsb_left"   # make_yuv16 planes of 10-bit codes in the low bits: what v210 carries
+
+
+def main_packed(tmp):
+    """The packed 4:2:2 instantiations."""
+    good = True
+    mats8 = {k: (N.yuv_matrix(std, full), site) for k, (std, full, site) in COLOURS.items()}
+    mats16 = {k: (W.yuv_matrix16(std, full, bits, msb), site) for k, (std, full, bits, msb, site) in COLOURS16.items()}
+    two16 = ("bt709_limited_10_msb_left", "bt709_full_16_msb_centre")
+    for name, (h, w, box, s) in PACKED_CASES.items():
+        for lay in (P.YUYV, P.UYVY, P.YVYU, P.VYUY):
+            for colour, (m, site) in mats8.items():
+                good &= run_packed(tmp, f"{P.NAMES[lay]} {name} {colour}", [make_yuv(h, w, P.SUB, seed=h + w)], [box], s, m, site, lay)
+            for colour in two16:
+                m, site = mats16[colour]
+                good &= run_packed(tmp, f"16-bit {P.NAMES[lay]} {name} {colour}", [make_yuv16(h, w, P.SUB, h + w, colour)], [box], s, m, site, lay)
+        for colour in two16:
+            m, site = mats16[colour]
+            good &= run_packed(tmp, f"v210 {name} {colour}", [make_yuv16(h, w, P.SUB, h + w, CODES10)], [box], s, m, site, P.V210, high_bits=3)
+    # v210 at every width mod 6, codes 0 and 1023 in every plane, bits 30-31 set; 1918 x 4: 320 blocks a row (-> 64: scale <= 32)
+    for w in V210_WIDTHS:
+        h, s = (4, 64) if w == 1918 else (5, 16)
+        yuv = make_yuv16(h, w, P.SUB, w, CODES10)
+        for a in yuv:
+            a[0, 0], a[-1, -1] = 0, 1023
+        for colour in two16:
+            m, site = mats16[colour]
+            good &= run_packed(tmp, f"v210 {h}x{w} {colour}", [yuv], [None], s, m, site, P.V210, high_bits=2)
+    # either side of the one-load-per-macropixel rule: offsets, row padding and the base itself
+    boxes = [None, (0.5, 3.0, 29.5, 40.0)]
+    m, site = mats8["bt709_limited_left"]
+    planes = [make_yuv(37, 53, P.SUB, seed=21), make_yuv(42, 30, P.SUB, seed=31)]
+    for lead in (0, 1, 2, 3):
+        for pad in (0, 1, 2):
+            for shift in (False, True):
+                good &= run_packed(tmp, f"8-bit alignment lead {lead} pad {pad} base+{int(shift)}", planes, boxes, 16, m, site, [P.UYVY, P.YVYU], shift, lead=lead, pad=pad, gap=lead)
+    m, site = mats16["bt709_limited_10_msb_left"]
+    planes = [make_yuv16(37, 53, P.SUB, 21, "bt709_limited_10_msb_left"), make_yuv16(42, 30, P.SUB, 31, "bt709_limited_10_msb_left")]
+    for lead in (0, 2, 4, 6):
+        for pad in (0, 2):
+            for shift in (False, True):
+                good &= run_packed(tmp, f"16-bit alignment lead {lead} pad {pad} base+{2 * int(shift)}", planes, boxes, 16, m, site, [P.YUYV, P.VYUY], shift, lead=lead, pad=pad, gap=lead)
+    planes = [make_yuv16(37, 53, P.SUB, 21, CODES10), make_yuv16(42, 30, P.SUB, 31, CODES10)]
+    for lead in (0, 4, 8, 12):
+        for pad in (0, 4):
+            good &= run_packed(tmp, f"v210 alignment lead {lead} pad {pad}", planes, boxes, 16, m, site, P.V210, lead=lead, pad=pad, gap=lead, high_bits=1)
+    # bands and batches
+    shapes = [(37, 53), (64, 64), (20, 24), (98, 132), (270, 480), (1, 1), (33, 2)]
+    boxes = [None, None, (2.0, 1.0, 22.0, 19.5), (10.0, 5.0, 101.0, 96.0), vithip.center_crop_box(270, 480), None, None]
+    m8, site8 = mats8["bt709_limited_left"]
+    good &= run_packed(tmp, "8-bit mixed batch of 7", [make_yuv(h, w, P.SUB, seed=40 + i) for i, (h, w) in enumerate(shapes)], boxes, 32, m8, site8,
+                       [i % 4 for i in range(7)], lead=1, gap=3, pad=1)
+    good &= run_packed(tmp, "16-bit + v210 mixed batch of 7", [make_yuv16(h, w, P.SUB, 40 + i, CODES10) for i, (h, w) in enumerate(shapes)], boxes, 32,
+                       W.yuv_matrix16(N.BT2020, False, 10, False), N.CHROMA_LEFT, [P.YUYV, P.UYVY, P.YVYU, P.VYUY, P.YUYV, P.UYVY, P.VYUY], lead=4, gap=4)
+    mixed = [P.YUYV, P.V210, P.YVYU, P.V210, P.V210, P.UYVY, P.V210]
+    planes = [make_yuv16(h, w, P.SUB, 40 + i, CODES10) for i, (h, w) in enumerate(shapes)]
+    planes = [yuv if lay == P.V210 else tuple((a << 6).astype(np.uint16) for a in yuv) for yuv, lay in zip(planes, mixed)]
+    good &= run_packed(tmp, "Y210 and v210 frames in one batch of 7", planes, boxes, 32, m, site, mixed, lead=4, gap=4)
+    small = [None if i % 2 else (0.5, 1.0, 38.25, 40.0) for i in range(40)]
+    good &= run_packed(tmp, "8-bit 40 frames of 41x39 (tall bands)", [make_yuv(41, 39, P.SUB, seed=100 + i) for i in range(40)], small, 32, m8, site8,
+                       [i % 4 for i in range(40)])
+    good &= run_packed(tmp, "v210 40 frames of 41x39 (tall bands)", [make_yuv16(41, 39, P.SUB, 100 + i, CODES10) for i in range(40)], small, 32, m, site, P.V210)
+    from test_nv12 import make_rgb
+    rgb = make_rgb(1080, 1920, 3)
+    crop = [vithip.center_crop_box(1080, 1920)]
+    good &= run_packed(tmp, "1080x1920 UYVY -> 64", [Y.rgb_to_yuv_planes(rgb, *P.SUB)], crop, 64, m8, site8, P.UYVY)
+    good &= run_packed(tmp, "1080x1920 v210 -> 64", [W.rgb_to_yuv16_planes(rgb, *P.SUB, 10, False)], crop, 64, m, site, P.V210)
+    return good
 
 
 def main16(tmp):
@@ -122,6 +222,11 @@ def main16(tmp):
 def main():
     build()
     good = True
+    if "--packed" in sys.argv[1:]:
+        with tempfile.TemporaryDirectory() as tmp:
+            good = main_packed(tmp)
+        print("every output equals the fp32 emulation; no sanitizer report" if good else "FAILED")
+        return 0 if good else 1
     with tempfile.TemporaryDirectory() as tmp:
         for name, (h, w, box, s) in OP_CASES.items():
             for key, sub in SUBS.items():
@@ -156,6 +261,7 @@ def main():
         for h in planner_boundary_444(130):
             good &= run(tmp, f"4:4:4 planner boundary, {h}x36 -> 130", [make_yuv(h, 36, (1, 1), seed=7)], [None], 130, m, N.CHROMA_LEFT, [(1, 1)])
         good &= main16(tmp)
+        good &= main_packed(tmp)
     print("every output equals the fp32 emulation; no sanitizer report" if good else "FAILED")
     return 0 if good else 1
 

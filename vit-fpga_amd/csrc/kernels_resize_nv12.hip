@@ -33,8 +33,18 @@
 // the base are multiples of 4 (the record's uv16 field) and two 16-bit loads otherwise.  The planner takes the sample width for
 // its stride, span and evenness checks; the tables, the bands, the LDS layout (fp32 either way), the vertical pass, the matrix and
 // the byte stores are those of the 8-bit instantiations, whose text is unchanged.
+//
+// PACKED 4:2:2 (include/vithip.h, "Packed 4:2:2 frames").  The body once more with the memory layout a third template
+// parameter, PACKED: YUY2 / UYVY / YVYU / VYUY (T = uint8_t), Y210 / Y216 (T = uint16_t) and v210 (T = uint16_t, the record's layout
+// = VH_422_V210).  A packed frame IS the planar 4:2:2 frame (sub_x = 2, sub_y = 1) of its de-interleaved planes: the planner feeds
+// plan_frames that YuvSrc, so tables and bands are the planar ones, and only the loads of the horizontal pass differ.  Luma sample j
+// is sample 2j + (layout & 1) of the row; a chroma tap takes its (U, V) from one macropixel, one 32-bit (64-bit) load where the
+// record's uv16 says that base + offset and stride are multiples of the macropixel, single samples otherwise.  v210: sample slot s of
+// a row is bits 10 (s % 3) .. 10 (s % 3) + 9 of 32-bit word s / 3 (three codes per word, four words per block of twelve slots); luma j
+// is slot 2j + 1, U k slot 4k, V k slot 4k + 2; a code enters the arithmetic as (float)code * 64.0f, the Y210 word of that code.
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "vh_kernels.h"
 
@@ -51,10 +61,11 @@ struct RzNv12 {
     int32_t xs, ys, cxs, cys;      // their weight strides
     int32_t band_rows, tile_cols;
     int32_t uv16;                  // semi-planar: uv_offset, uv_stride and the base multiples of one (U, V) pair: one load per pair
+                                   // (packed: of one macropixel)
     int32_t ch;                    // rows of the chroma plane(s): h / 2 (NV12), ceil(h / sub_y) (planar)
     uint64_t v_off;                // planar: the V plane, rows v_stride apart
     int32_t v_stride;
-    int32_t pad;
+    int32_t layout;                // packed 4:2:2: VH_422_*; y_off = uv_off = the frame, y_stride = uv_stride = row_stride, ch = h
 };
 static_assert(sizeof(RzNv12) == 4 * kResizeNv12FrameWords, "RzNv12 layout");
 
@@ -88,6 +99,7 @@ struct YuvSrc {
     int32_t y_stride, u_stride, v_stride;
     int32_t sub_x, sub_y;
     int32_t uv16;
+    int32_t layout;                 // packed 4:2:2 only
     double box[4];
 };
 
@@ -163,7 +175,7 @@ const char* plan_frames(const std::vector<YuvSrc>& src, int S, int chroma_site, 
         f.xt = kx.at; f.xs = kx.stride; f.yt = ky.at; f.ys = ky.stride;
         f.cxt = kcx.at; f.cxs = kcx.stride; f.cyt = kcy.at; f.cys = kcy.stride;
         f.band_rows = bk.band_rows; f.tile_cols = bk.tile_cols;
-        f.uv16 = d.uv16;
+        f.uv16 = d.uv16; f.layout = d.layout;
         memcpy(words->data() + (size_t)b * kResizeNv12FrameWords, &f, sizeof f);
         const int tiles = ((S + f.band_rows - 1) / f.band_rows) * ((S + f.tile_cols - 1) / f.tile_cols);
         if (tiles > *max_tiles) *max_tiles = tiles;
@@ -203,6 +215,7 @@ const char* resize_plan_build_nv12(const vh_frame_nv12* desc, int batch, int S, 
         s.y_stride = d.y_stride; s.u_stride = d.uv_stride; s.v_stride = 0;
         s.sub_x = 2; s.sub_y = 2;
         s.uv16 = base_mod4 % pair == 0 && d.uv_offset % pair == 0 && (unsigned)d.uv_stride % pair == 0;
+        s.layout = 0;
         for (int i = 0; i < 4; ++i) s.box[i] = (double)d.box[i];
     }
     if (const char* e = plan_frames(src, S, chroma_site, wide ? "resize_p016: box outside the frame, empty, or scale > 32" : "resize_nv12: box outside the frame, empty, or scale > 32",
@@ -253,12 +266,70 @@ const char* resize_plan_build_yuv(const vh_frame_yuv* desc, int batch, int S, si
         s.h = d.height; s.w = d.width; s.cw = cw; s.ch = ch;
         s.y_stride = d.y_stride; s.u_stride = d.u_stride; s.v_stride = d.v_stride;
         s.sub_x = d.sub_x; s.sub_y = d.sub_y;
-        s.uv16 = 0;
+        s.uv16 = 0; s.layout = 0;
     }
     if (const char* e = plan_frames(src, S, chroma_site, wide ? "resize_yuv16: a table of the box could not be built" : "resize_yuv: a table of the box could not be built",
                                     words, max_tiles))
         return e;
     if ((int64_t)batch * *max_tiles > 0x7fffffffll) return wide ? "resize_yuv16: too many tiles" : "resize_yuv: too many tiles";
+    return nullptr;
+}
+
+// packed 4:2:2: every refusal of the contract has a message of its own, in the order the header lists them.  sample_bytes 1: YUY2 and
+// its three permutations.  2: Y210 / Y216 (layouts 0..3; offset, stride and base even) and v210 (multiples of 4).  base_mod8 = the
+// base address & 7 (0 for a host buffer, which is copied).  The YuvSrc is the planar 4:2:2 frame of the de-interleaved planes.
+const char* resize_plan_build_yuy2(const vh_frame_yuy2* desc, int batch, int S, size_t nbytes, unsigned base_mod8, int chroma_site,
+                                   int sample_bytes, std::vector<uint32_t>* words, int* max_tiles) {
+    const bool wide = sample_bytes == 2;
+    if (sample_bytes != 1 && !wide) return "resize_yuy2: sample_bytes must be 1 or 2";
+    if (!desc || batch < 1 || S < 1 || S > 4096) return wide ? "resize_y210: bad batch or output size" : "resize_yuy2: bad batch or output size";
+    if (chroma_site != VH_CHROMA_CENTER && chroma_site != VH_CHROMA_LEFT)
+        return wide ? "resize_y210: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT" : "resize_yuy2: chroma_site must be VH_CHROMA_CENTER or VH_CHROMA_LEFT";
+    std::vector<YuvSrc> src((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        const vh_frame_yuy2& d = desc[b];
+        if (d.width < 1 || d.width > kResizeMaxSide || d.height < 1 || d.height > kResizeMaxSide)
+            return wide ? "resize_y210: width and height must be 1..8192" : "resize_yuy2: width and height must be 1..8192";
+        if (!wide && d.layout == VH_422_V210) return "resize_yuy2: VH_422_V210 is a 10-bit layout; it goes to the 16-bit (_y210) entry points";
+        if (d.layout < VH_422_YUYV || d.layout > VH_422_V210) return wide ? "resize_y210: layout must be one of VH_422_*" : "resize_yuy2: layout must be VH_422_YUYV, _UYVY, _YVYU or _VYUY";
+        const bool v210 = d.layout == VH_422_V210;
+        const int cw = (d.width + 1) / 2;
+        // bytes of one row, and of the unit whose multiple base + offset and stride must be for the one-load chroma tap
+        const int64_t row = v210 ? 16 * (int64_t)((d.width + 5) / 6) : 4 * (int64_t)sample_bytes * cw;
+        const unsigned macro = 4u * (unsigned)sample_bytes;
+        if (d.row_stride < row)
+            return v210 ? "resize_y210: row_stride < 16 * ceil(width / 6) bytes (v210)" : wide ? "resize_y210: row_stride < 8 * cw bytes, cw = (width + 1) / 2"
+                                                                                               : "resize_yuy2: row_stride < 4 * cw bytes, cw = (width + 1) / 2";
+        if (v210) {
+            if (d.offset % 4) return "resize_y210: offset is no multiple of 4; v210 words need 4-byte aligned offsets";
+            if (d.row_stride % 4) return "resize_y210: row_stride is no multiple of 4; v210 words need 4-byte aligned rows";
+            if (base_mod8 % 4) return "resize_y210: the device frames pointer is no multiple of 4; v210 words need a 4-byte aligned base";
+        } else if (wide) {
+            if (d.offset % 2) return "resize_y210: offset is odd; 16-bit samples need even byte offsets";
+            if (d.row_stride % 2) return "resize_y210: row_stride is odd; 16-bit samples need even byte strides";
+            if (base_mod8 % 2) return "resize_y210: the device frames pointer is odd; 16-bit samples need a 2-byte aligned base";
+        }
+        const uint64_t span = (uint64_t)(d.height - 1) * (uint64_t)d.row_stride + (uint64_t)row;
+        if (d.offset > nbytes || span > nbytes - d.offset) return wide ? "resize_y210: a frame ends beyond nbytes" : "resize_yuy2: a frame ends beyond nbytes";
+        YuvSrc& s = src[b];
+        for (int i = 0; i < 4; ++i) s.box[i] = (double)d.box[i];
+        // written so that a NaN fails
+        if (!(s.box[0] >= 0.0 && s.box[0] < s.box[2] && s.box[2] <= (double)d.width && s.box[1] >= 0.0 && s.box[1] < s.box[3] &&
+              s.box[3] <= (double)d.height))
+            return wide ? "resize_y210: box outside the frame, or empty" : "resize_yuy2: box outside the frame, or empty";
+        if (!((s.box[2] - s.box[0]) / (double)S <= (double)kResizeMaxScale && (s.box[3] - s.box[1]) / (double)S <= (double)kResizeMaxScale))
+            return wide ? "resize_y210: scale > 32 on an axis" : "resize_yuy2: scale > 32 on an axis";
+        s.y_off = s.u_off = s.v_off = d.offset;
+        s.h = d.height; s.w = d.width; s.cw = cw; s.ch = d.height;
+        s.y_stride = s.u_stride = s.v_stride = d.row_stride;
+        s.sub_x = 2; s.sub_y = 1;
+        s.uv16 = !v210 && (base_mod8 + d.offset) % macro == 0 && (unsigned)d.row_stride % macro == 0;
+        s.layout = d.layout;
+    }
+    if (const char* e = plan_frames(src, S, chroma_site, wide ? "resize_y210: a table of the box could not be built" : "resize_yuy2: a table of the box could not be built",
+                                    words, max_tiles))
+        return e;
+    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return wide ? "resize_y210: too many tiles" : "resize_yuy2: too many tiles";
     return nullptr;
 }
 
@@ -268,10 +339,17 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 __host__ __device__ __forceinline__ uint32_t nv12_byte(float v) { return (uint32_t)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
 
+// sample slot s of a v210 row, as the Y210 word of its code: exact (code < 2^10)
+__host__ __device__ __forceinline__ float v210_sample(const uint32_t* __restrict__ row, uint32_t s) {
+    const uint32_t wd = s / 3u;
+    return (float)((row[wd] >> (10u * (s - 3u * wd))) & 0x3ffu) * 64.0f;
+}
+
 // The work of thread `tid` of workgroup `block`.  PLANAR: U and V are two planes, else one plane of (U, V) pairs.  T: the sample,
 // uint8_t or uint16_t (unsigned: a word above 0x7fff must not sign-extend); strides and offsets are bytes either way.  `barrier`
-// is __syncthreads() on the device; every return in front of it is taken by the whole workgroup.
-template <bool PLANAR, class T, class Barrier>
+// is __syncthreads() on the device; every return in front of it is taken by the whole workgroup.  PACKED: one plane of 4:2:2
+// macropixels (PLANAR is then not read); its loads are the only text the other instantiations do not share.
+template <bool PLANAR, class T, bool PACKED = false, class Barrier>
 __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan,
                                                          uint8_t* __restrict__ out, int S, int max_tiles, const Nv12Matrix& mat, float* lds,
                                                          int block, int tid, Barrier barrier) {
@@ -316,9 +394,20 @@ __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restri
             const int y = e / cols, x = c0 + (e - y * cols);
             const int n = xcount[x];
             const float* w = xw + (size_t)x * d.xs;
-            const T* p = (const T*)(ysrc + (size_t)(ylo + y) * d.y_stride) + xfirst[x];
             float acc = 0.f;
-            for (int t = 0; t < n; ++t) acc = __builtin_fmaf(w[t], (float)p[t], acc);
+            if constexpr (PACKED) {
+                const uint8_t* row = ysrc + (size_t)(ylo + y) * d.y_stride;
+                if (sizeof(T) == 2 && d.layout == VH_422_V210) {
+                    const uint32_t s0 = 2u * (uint32_t)xfirst[x] + 1u;
+                    for (int t = 0; t < n; ++t) acc = __builtin_fmaf(w[t], v210_sample((const uint32_t*)row, s0 + 2u * (uint32_t)t), acc);
+                } else {
+                    const T* p = (const T*)row + 2 * (size_t)xfirst[x] + (d.layout & 1);
+                    for (int t = 0; t < n; ++t) acc = __builtin_fmaf(w[t], (float)p[2 * t], acc);
+                }
+            } else {
+                const T* p = (const T*)(ysrc + (size_t)(ylo + y) * d.y_stride) + xfirst[x];
+                for (int t = 0; t < n; ++t) acc = __builtin_fmaf(w[t], (float)p[t], acc);
+            }
             ldy[e] = acc;
         } else {
             const int ec = e - ny;
@@ -326,7 +415,36 @@ __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restri
             const int n = cxcount[x];
             const float* w = cxw + (size_t)x * d.cxs;
             float u = 0.f, v = 0.f;
-            if constexpr (PLANAR) {
+            if constexpr (PACKED) {
+                // positions of U and V among the four samples of a macropixel: YUYV 1 3, UYVY 0 2, YVYU 3 1, VYUY 2 0
+                const int upos = (d.layout ^ 1) & 3, vpos = upos ^ 2;
+                const uint8_t* row = csrc + (size_t)(clo + y) * d.uv_stride;
+                if (sizeof(T) == 2 && d.layout == VH_422_V210) {
+                    const uint32_t s0 = 4u * (uint32_t)cxfirst[x];
+                    for (int t = 0; t < n; ++t) {
+                        const float wt = w[t];
+                        u = __builtin_fmaf(wt, v210_sample((const uint32_t*)row, s0 + 4u * (uint32_t)t), u);
+                        v = __builtin_fmaf(wt, v210_sample((const uint32_t*)row, s0 + 4u * (uint32_t)t + 2u), v);
+                    }
+                } else if (d.uv16) {
+                    typedef typename std::conditional<sizeof(T) == 2, uint64_t, uint32_t>::type Q;   // one macropixel
+                    const Q* p = (const Q*)row + cxfirst[x];
+                    const int ush = 8 * (int)sizeof(T) * upos, vsh = 8 * (int)sizeof(T) * vpos;
+                    for (int t = 0; t < n; ++t) {
+                        const Q q = p[t];
+                        const float wt = w[t];
+                        u = __builtin_fmaf(wt, (float)(T)(q >> ush), u);
+                        v = __builtin_fmaf(wt, (float)(T)(q >> vsh), v);
+                    }
+                } else {
+                    const T* p = (const T*)row + 4 * (size_t)cxfirst[x];
+                    for (int t = 0; t < n; ++t) {
+                        const float wt = w[t];
+                        u = __builtin_fmaf(wt, (float)p[4 * t + upos], u);
+                        v = __builtin_fmaf(wt, (float)p[4 * t + vpos], v);
+                    }
+                }
+            } else if constexpr (PLANAR) {
                 const T* pu = (const T*)(csrc + (size_t)(clo + y) * d.uv_stride) + cxfirst[x];
                 const T* pv = (const T*)(vsrc + (size_t)(clo + y) * d.v_stride) + cxfirst[x];
                 for (int t = 0; t < n; ++t) {
@@ -428,6 +546,30 @@ hipError_t launch_resize_yuv_any(bool planar, bool wide, const uint8_t* frames, 
         hipLaunchKernelGGL((resize_yuv_kernel<false, uint16_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     else
         hipLaunchKernelGGL((resize_yuv_kernel<false, uint8_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    return hipGetLastError();
+}
+
+// packed 4:2:2: the same body behind a kernel of its own, so that the four instantiations above keep their names and their code
+template <class T>
+__global__ void __launch_bounds__(256)
+resize_packed422_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan, uint8_t* __restrict__ out, int S, int max_tiles,
+                        Nv12Matrix mat) {
+    __shared__ __attribute__((aligned(16))) float lds[kResizeLdsFloats];
+    resize_yuv_body<true, T, true>(frames, plan, out, S, max_tiles, mat, lds, (int)blockIdx.x, (int)threadIdx.x, [] { __syncthreads(); });
+}
+
+// wide: the 16-bit layouts (Y210 / Y216 and v210, told apart per frame by the record's layout); a plan of resize_plan_build_yuy2
+hipError_t launch_resize_yuy2(bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
+                              uint8_t* out, hipStream_t s) {
+    if (!frames || !plan_dev || !out || !m12 || batch < 1 || S < 1 || max_tiles < 1 || (int64_t)batch * max_tiles > 0x7fffffffll)
+        return hipErrorInvalidValue;
+    Nv12Matrix mat;
+    memcpy(mat.m, m12, sizeof mat.m);
+    const dim3 grid((unsigned)(batch * max_tiles));
+    if (wide)
+        hipLaunchKernelGGL((resize_packed422_kernel<uint16_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    else
+        hipLaunchKernelGGL((resize_packed422_kernel<uint8_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     return hipGetLastError();
 }
 #endif

@@ -151,6 +151,14 @@ int yuv_matrix16(int standard, int full_range, int bits, int msb_aligned, float 
 // resize_plan_build_yuv) over the Y + UV ones (resize_plan_build_nv12), wide the uint16_t ones (plans built with sample_bytes 2).
 hipError_t launch_resize_yuv_any(bool planar, bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
                                  const float* m12_host, uint8_t* out_u8, hipStream_t stream);
+// Packed 4:2:2 frames (the same file, record and kernel body; contract: vithip.h, "Packed 4:2:2 frames"): YUY2 / UYVY / YVYU / VYUY
+// (sample_bytes 1), Y210 / Y216 and v210 (sample_bytes 2).  resize_plan_build_yuy2 plans the planar 4:2:2 frame of the de-interleaved
+// planes (the same tables and bands) and puts the layout into the record; base_mod8: the frames address & 7 (0 for a host buffer).
+// launch_resize_yuy2: one launch for the batch; wide: a plan built with sample_bytes 2.
+const char* resize_plan_build_yuy2(const vh_frame_yuy2* desc, int batch, int S, size_t nbytes, unsigned base_mod8, int chroma_site,
+                                   int sample_bytes, std::vector<uint32_t>* words, int* max_tiles);
+hipError_t launch_resize_yuy2(bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
+                              const float* m12_host, uint8_t* out_u8, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
 bool patch_fused_supported(int image, int patch, int channels, int dim);

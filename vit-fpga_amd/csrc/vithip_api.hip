@@ -965,7 +965,7 @@ int check_u8_ptr(vh_ctx* c, const void* in_dev) {
 struct FrameFormat {
     const char* tag;      // prefix of the operator tap's messages
     const char* label;    // "<label> frames need a model with 3 channels"
-    const char* op_null;  // the tap's null-argument message: two of the five carry no tag
+    const char* op_null;  // the tap's null-argument message: RGB and NV12 carry no tag
     bool three_channels;  // the model must take 3 channels (a colour matrix has three rows)
     int colour;           // index into vh_ctx::colour, -1: the format takes no matrix and no siting
     const char* (*plan)(const void* desc, int batch, int channels, int S, size_t nbytes, uintptr_t base, int chroma_site,
@@ -990,6 +990,17 @@ hipError_t launch_yuv(const uint8_t* frames, const uint32_t* plan_dev, int batch
     return launch_resize_yuv_any(PLANAR, WIDE, frames, plan_dev, batch, S, max_tiles, m12, out, stream);
 }
 
+template <int SAMPLE_BYTES>
+const char* plan_packed422(const void* desc, int batch, int, int S, size_t nbytes, uintptr_t base, int chroma_site, std::vector<uint32_t>* words,
+                           int* max_tiles) {
+    return resize_plan_build_yuy2((const vh_frame_yuy2*)desc, batch, S, nbytes, (unsigned)(base & 7), chroma_site, SAMPLE_BYTES, words, max_tiles);
+}
+template <bool WIDE>
+hipError_t launch_packed422(const uint8_t* frames, const uint32_t* plan_dev, int batch, int, int S, int max_tiles, const float* m12, uint8_t* out,
+                            hipStream_t stream) {
+    return launch_resize_yuy2(WIDE, frames, plan_dev, batch, S, max_tiles, m12, out, stream);
+}
+
 const char* plan_rgb(const void* desc, int batch, int channels, int S, size_t nbytes, uintptr_t base, int, std::vector<uint32_t>* words, int* max_tiles) {
     return resize_plan_build((const vh_frame*)desc, batch, channels, S, nbytes, (base & 3) == 0, words, max_tiles);
 }
@@ -1004,6 +1015,8 @@ const FrameFormat kFramesNV12 = {"resize_nv12", "NV12", "null buffer", true, 0, 
 const FrameFormat kFramesYUV = {"resize_yuv", "planar YUV", "resize_yuv: null buffer", true, 0, plan_planar<1>, launch_yuv<true, false>};
 const FrameFormat kFramesP016 = {"resize_p016", "P016", "resize_p016: null buffer", true, 1, plan_semi_planar<2>, launch_yuv<false, true>};
 const FrameFormat kFramesYUV16 = {"resize_yuv16", "planar 16-bit YUV", "resize_yuv16: null buffer", true, 1, plan_planar<2>, launch_yuv<true, true>};
+const FrameFormat kFramesYUY2 = {"resize_yuy2", "packed 4:2:2", "resize_yuy2: null buffer", true, 0, plan_packed422<1>, launch_packed422<false>};
+const FrameFormat kFramesY210 = {"resize_y210", "packed 16-bit 4:2:2", "resize_y210: null buffer", true, 1, plan_packed422<2>, launch_packed422<true>};
 
 // One resize in front of a forward: the frames in HBM and the descriptors + tables (c->rz_words) in pinned memory.
 struct FrameJob {
@@ -1727,6 +1740,19 @@ int vh_forward_device_frames_yuv16(vh_ctx* c, const uint8_t* frames_dev, size_t 
 int vh_forward_frames_yuv16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch, float* logits_host) {
     return forward_frames_host(c, kFramesYUV16, frames_host, nbytes, desc, batch, logits_host);
 }
+// packed 4:2:2 frames: the plan of resize_plan_build_yuy2; 8-bit layouts under the first colour state, Y210 / Y216 / v210 under the second
+int vh_forward_device_frames_yuy2(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_dev) {
+    return forward_frames_device(c, kFramesYUY2, frames_dev, nbytes, desc, batch, logits_dev);
+}
+int vh_forward_frames_yuy2(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_host) {
+    return forward_frames_host(c, kFramesYUY2, frames_host, nbytes, desc, batch, logits_host);
+}
+int vh_forward_device_frames_y210(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_dev) {
+    return forward_frames_device(c, kFramesY210, frames_dev, nbytes, desc, batch, logits_dev);
+}
+int vh_forward_frames_y210(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_host) {
+    return forward_frames_host(c, kFramesY210, frames_host, nbytes, desc, batch, logits_host);
+}
 
 int vh_yuv_matrix(int standard, int full_range, float m[12]) {
     if (yuv_matrix(standard, full_range, m))
@@ -1966,7 +1992,7 @@ int vh_ring_input_frames(vh_ctx* c, uint8_t** pinned, size_t* capacity) {
 
 // frames ring: in_host holds `frame_bytes` of frames described by `desc`; the slot's upload is followed by the resize into
 // c->rz_u8 on the context's stream (forwards are ordered on that stream, so one resized buffer serves every slot)
-// (`desc` points to descriptors of the type `fmt` plans; a slot is raw bytes, so one frames ring takes all five formats.  A slot's
+// (`desc` points to descriptors of the type `fmt` plans; a slot is raw bytes, so one frames ring takes every format.  A slot's
 // device buffer comes from hipMalloc, so its base is aligned for any sample: base 0)
 static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKind kind, size_t frame_bytes = 0, const void* desc = nullptr,
                        const FrameFormat& fmt = kFramesRGB) {
@@ -2032,6 +2058,12 @@ int vh_ring_submit_frames_p016(vh_ctx* c, const uint8_t* frames_host, size_t nby
 }
 int vh_ring_submit_frames_yuv16(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch) {
     return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesYUV16);
+}
+int vh_ring_submit_frames_yuy2(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesYUY2);
+}
+int vh_ring_submit_frames_y210(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesY210);
 }
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
@@ -2444,6 +2476,14 @@ int vh_op_resize_p016(const uint8_t* frames, size_t nbytes, const vh_frame_nv12*
 int vh_op_resize_yuv16(const uint8_t* frames, size_t nbytes, const vh_frame_yuv* desc, int batch, int out_size, const float* m12,
                        int chroma_site, uint8_t* out, void* stream) {
     return op_resize(kFramesYUV16, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
+}
+int vh_op_resize_yuy2(const uint8_t* frames, size_t nbytes, const vh_frame_yuy2* desc, int batch, int out_size, const float* m12,
+                      int chroma_site, uint8_t* out, void* stream) {
+    return op_resize(kFramesYUY2, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
+}
+int vh_op_resize_y210(const uint8_t* frames, size_t nbytes, const vh_frame_yuy2* desc, int batch, int out_size, const float* m12,
+                      int chroma_site, uint8_t* out, void* stream) {
+    return op_resize(kFramesY210, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
 }
 
 int vh_op_cast(const float* in, void* out16, int64_t n, int dtype, void* stream) {

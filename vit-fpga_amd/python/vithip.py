@@ -63,6 +63,14 @@ class FrameYUV(C.Structure):
                 ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("box", C.c_float * 4), ("reserved", C.c_int32)]
 
 
+class FrameYUY2(C.Structure):
+    """vh_frame_yuy2: one packed 4:2:2 frame (one plane of macropixels in the order of `layout`, L422_*) inside the buffer of a call,
+    and the box (in luma pixels) to resample to image_size^2.  40 bytes."""
+    _fields_ = [("offset", C.c_uint64), ("height", C.c_int32), ("width", C.c_int32), ("row_stride", C.c_int32),
+                ("layout", C.c_int32), ("box", C.c_float * 4)]
+
+
+L422_YUYV, L422_UYVY, L422_YVYU, L422_VYUY, L422_V210 = range(5)   # vh_frame_yuy2.layout (VH_422_*); V210: the 16-bit entry points only
 CHROMA_CENTER, CHROMA_LEFT = 0, 1          # vh_set_frame_colour / vh_op_resize_nv12: JPEG / MPEG-1 siting, MPEG-2 / H.264 / HEVC siting
 YUV_BT601, YUV_BT709, YUV_BT2020 = 0, 1, 2  # vh_yuv_matrix
 
@@ -116,6 +124,10 @@ SYMBOLS = {
     "vh_forward_device_frames_p016": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_frames_yuv16": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_device_frames_yuv16": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_frames_yuy2": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_yuy2": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_frames_y210": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_y210": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_fill_input_seeded": (_i, [_vp, _u64, _i, _vp]),
     "vh_last_forward_us": (_i, [_vp, C.POINTER(_i64)]),
     "vh_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
@@ -148,6 +160,8 @@ SYMBOLS = {
     "vh_ring_submit_frames_yuv": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_ring_submit_frames_p016": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_ring_submit_frames_yuv16": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_yuy2": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_y210": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_set_graph": (_i, [_vp, _i]),
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
@@ -182,6 +196,8 @@ SYMBOLS = {
     "vh_op_resize_yuv": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_p016": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_yuv16": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "vh_op_resize_yuy2": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "vh_op_resize_y210": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -476,6 +492,74 @@ def pack_frames_yuv16(planes, boxes=None):
     uint8 buffer of little-endian words, the (FrameYUV * n) descriptors).  Offsets and strides are bytes; width, height, sub_x,
     sub_y and box count samples."""
     return _pack_planar("pack_frames_yuv16", np.uint16, planes, boxes)
+
+
+def v210_rows(y, u, v):
+    """(Y [H, W], U [H, cw], V [H, cw]) uint16 codes 0..1023, cw = (W + 1) // 2 -> the v210 rows as [H, 4 * ceil(W / 6)] uint32 words:
+    twelve codes per block in the order U0 Y0 V0 | Y1 U1 Y2 | V1 Y3 U2 | Y4 V2 Y5, three per word from bit 0, the unused slots of the
+    last block zero."""
+    y, u, v = (np.asarray(p).astype(np.uint32) for p in (y, u, v))
+    h, w = y.shape
+    cw = (w + 1) // 2
+    if u.shape != (h, cw) or v.shape != (h, cw):
+        raise ValueError(f"v210_rows: Y is {h} x {w}, U is {u.shape}, V is {v.shape}; want chroma planes of {h} x {cw}")
+    if max(int(y.max()), int(u.max()), int(v.max())) > 1023:
+        raise ValueError("v210_rows: a code is above 1023")
+    blocks = (w + 5) // 6
+    slots = np.zeros((h, 12 * blocks), np.uint32)
+    slots[:, 1:2 * w:2] = y
+    slots[:, 0:4 * cw:4] = u
+    slots[:, 2:4 * cw:4] = v
+    s3 = slots.reshape(h, 4 * blocks, 3)
+    return s3[:, :, 0] | (s3[:, :, 1] << np.uint32(10)) | (s3[:, :, 2] << np.uint32(20))
+
+
+def pack_frames_yuy2(planes, layouts=L422_YUYV, boxes=None):
+    """A list of (Y [H, W], U [H, cw], V [H, cw]) triples, cw = (W + 1) // 2, interleaved into packed 4:2:2 frames -> (one uint8
+    buffer, the (FrameYUY2 * n) descriptors).  layouts: one L422_* for all frames or one per frame.  uint8 planes give the 8-bit
+    layouts (forward_frames_yuy2); uint16 planes give Y210 / Y216 words in the order of the layout, or, with L422_V210, v210 blocks
+    of the 10-bit codes in the planes (forward_frames_y210).  Rows are unpadded, frames back to back, each v210 frame 4-byte and
+    each 16-bit frame 8-byte aligned by construction.  With an odd width the second luma of the last macropixel is zero."""
+    planes = [tuple(np.asarray(p) for p in t) for t in planes]
+    if isinstance(layouts, int):
+        layouts = [layouts] * len(planes)
+    if boxes is None:
+        boxes = [None] * len(planes)
+    if not planes or len(boxes) != len(planes) or len(layouts) != len(planes):
+        raise ValueError("pack_frames_yuy2: one layout and one box (or None) per frame, at least one frame")
+    dtype = planes[0][0].dtype
+    if dtype not in (np.uint8, np.uint16):
+        raise TypeError("pack_frames_yuy2: planes must be uint8 or uint16 arrays")
+    desc = (FrameYUY2 * len(planes))()
+    parts, off = [], 0
+    for i, (t, lay, box) in enumerate(zip(planes, layouts, boxes)):
+        if len(t) != 3 or any(p.dtype != dtype or p.ndim != 2 or p.size == 0 for p in t):
+            raise TypeError(f"pack_frames_yuy2: frame {i} is not a (Y, U, V) triple of 2-d {np.dtype(dtype).name} arrays")
+        y, u, v = t
+        h, w = y.shape
+        cw = (w + 1) // 2
+        if u.shape != (h, cw) or v.shape != (h, cw):
+            raise ValueError(f"pack_frames_yuy2: frame {i}: Y is {h} x {w}, chroma is {u.shape} / {v.shape}; want {h} x {cw} (4:2:2)")
+        if lay == L422_V210:
+            if dtype != np.uint16:
+                raise ValueError(f"pack_frames_yuy2: frame {i}: L422_V210 takes uint16 planes of 10-bit codes")
+            rows = _sample_bytes(v210_rows(y, u, v))
+        elif lay in (L422_YUYV, L422_UYVY, L422_YVYU, L422_VYUY):
+            m = np.zeros((h, cw, 4), dtype)
+            ypos, upos = lay & 1, (lay ^ 1) & 3
+            m[:, :(w + 1) // 2, ypos] = y[:, 0::2]
+            m[:, :w // 2, ypos + 2] = y[:, 1::2]
+            m[:, :, upos] = u
+            m[:, :, upos ^ 2] = v
+            rows = _sample_bytes(m)
+        else:
+            raise ValueError(f"pack_frames_yuy2: frame {i}: layout {lay} is none of L422_*")
+        d = desc[i]
+        d.offset, d.height, d.width, d.row_stride, d.layout = off, h, w, rows.size // h, lay
+        d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
+        parts.append(rows)
+        off += rows.size
+    return np.concatenate(parts), desc
 
 
 def make_config(cfg, dtype=DTYPE_BF16, max_batch=1, ln_eps=1e-6, flags=0):
@@ -846,6 +930,31 @@ class VitContext:
     def forward_device_frames_yuv16(self, frames_ptr, nbytes, desc, out_ptr):
         self._forward_frames_device(lib().vh_forward_device_frames_yuv16, frames_ptr, nbytes, desc, out_ptr)
 
+    # ---- packed 4:2:2 frames (YUY2 / UYVY / YVYU / VYUY; Y210 / Y216 / v210): the planar 4:2:2 arithmetic on interleaved memory ----
+    def forward_frames_yuy2(self, planes, layouts=L422_YUYV, boxes=None):
+        """planes: a list of (Y [H, W], U [H, cw], V [H, cw]) uint8 triples, interleaved here (pack_frames_yuy2) in the order of
+        `layouts`.  Returns the bits forward_u8 gives for op_resize_yuy2's output under set_frame_colour's state."""
+        buf, desc = pack_frames_yuy2(planes, layouts, boxes)
+        return self.forward_frames_yuy2_packed(buf, desc)
+
+    def forward_frames_yuy2_packed(self, buf, desc):
+        return self._forward_frames_host(lib().vh_forward_frames_yuy2, buf, desc)
+
+    def forward_device_frames_yuy2(self, frames_ptr, nbytes, desc, out_ptr):
+        self._forward_frames_device(lib().vh_forward_device_frames_yuy2, frames_ptr, nbytes, desc, out_ptr)
+
+    def forward_frames_y210(self, planes, layouts=L422_YUYV, boxes=None):
+        """planes: uint16 triples as above: Y210 / Y216 words, or 10-bit codes with L422_V210.  Returns the bits forward_u8 gives
+        for op_resize_y210's output under set_frame_colour16's state."""
+        buf, desc = pack_frames_yuy2(planes, layouts, boxes)
+        return self.forward_frames_y210_packed(buf, desc)
+
+    def forward_frames_y210_packed(self, buf, desc):
+        return self._forward_frames_host(lib().vh_forward_frames_y210, buf, desc)
+
+    def forward_device_frames_y210(self, frames_ptr, nbytes, desc, out_ptr):
+        self._forward_frames_device(lib().vh_forward_device_frames_y210, frames_ptr, nbytes, desc, out_ptr)
+
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
 
@@ -946,6 +1055,24 @@ class VitContext:
     def ring_submit_frames_yuv16_packed(self, buf, nbytes, desc):
         """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of planes that desc describes."""
         self._ring_submit_frames(lib().vh_ring_submit_frames_yuv16, buf, nbytes, desc)
+
+    def ring_submit_frames_yuy2(self, planes, layouts=L422_YUYV, boxes=None):
+        """8-bit packed 4:2:2 frames into the next slot of a frames ring; every kind of frames submit may alternate."""
+        buf, desc = pack_frames_yuy2(planes, layouts, boxes)
+        self.ring_submit_frames_yuy2_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_yuy2_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of frames that desc describes."""
+        self._ring_submit_frames(lib().vh_ring_submit_frames_yuy2, buf, nbytes, desc)
+
+    def ring_submit_frames_y210(self, planes, layouts=L422_YUYV, boxes=None):
+        """Y210 / Y216 / v210 frames into the next slot of a frames ring; every kind of frames submit may alternate."""
+        buf, desc = pack_frames_yuy2(planes, layouts, boxes)
+        self.ring_submit_frames_y210_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_y210_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of frames that desc describes."""
+        self._ring_submit_frames(lib().vh_ring_submit_frames_y210, buf, nbytes, desc)
 
     def ring_free_slots(self):
         n = C.c_int(0)
@@ -1293,7 +1420,7 @@ def op_resize_u8(frames_ptr, nbytes, desc, channels, out_size, out_ptr):
 
 
 def _op_resize_colour(name, fn, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
-    """The body of the four taps that take a colour matrix; `fn` is the format's C tap."""
+    """The body of the taps that take a colour matrix; `fn` is the format's C tap."""
     m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
     if m.size != 12:
         raise ValueError(f"{name}: expected 12 matrix entries, got {m.size}")
@@ -1314,6 +1441,16 @@ def op_resize_p016(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
 def op_resize_yuv16(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
     """op_resize_yuv for 16-bit samples: frames_ptr (device, 2-byte aligned), offsets and strides in bytes and even."""
     _op_resize_colour("op_resize_yuv16", lib().vh_op_resize_yuv16, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
+
+
+def op_resize_yuy2(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """op_resize_yuv for 8-bit packed 4:2:2 frames: (FrameYUY2 * n) descriptors, frames_ptr of any alignment."""
+    _op_resize_colour("op_resize_yuy2", lib().vh_op_resize_yuy2, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
+
+
+def op_resize_y210(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """op_resize_yuv16 for Y210 / Y216 / v210 frames: frames_ptr 2-byte aligned, offsets and strides even (v210: multiples of 4)."""
+    _op_resize_colour("op_resize_y210", lib().vh_op_resize_y210, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
 
 
 def op_resize_nv12(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
