@@ -379,7 +379,7 @@ int vh_forward_device_frames_yuv(vh_ctx* ctx, const uint8_t* frames_dev, size_t 
  *       a DEVICE frames pointer must be 2-byte aligned; a host pointer may have any alignment, because it is copied.
  * Parity and size rules are those of the 8-bit layout: semi-planar needs even sizes within 2..8192, planar takes any parity
  * within 1..8192.  Big-endian words are not taken; packed 4:2:2 words (Y210, Y216, v210) go to "Packed 4:2:2 frames" below; packed
- * 4:4:4 (Y410, AYUV) is not taken.
+ * 4:4:4 words (Y410, Y416) go to "Packed 4:4:4 frames".
  * SAMPLE VALUES.  The word enters the arithmetic AS IS, as the fp32 value of the unsigned integer 0..65535 (exact).  The kernel
  * does not shift, mask or scale: depth and alignment live in the matrix alone.  A P010 word with non-zero low bits is simply a
  * P016 value.
@@ -458,7 +458,7 @@ int vh_forward_device_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_dev, size_
  * in between, the nested-fmaf matrix expression and the one rounding rintf(min(max(out[k], 0), 255)).  EQUIVALENCE: the output bytes
  * are those of vh_op_resize_yuv (vh_op_resize_yuv16) on the de-interleaved planes (Y height x width, U and V height x cw, sub_x = 2,
  * sub_y = 1), BIT FOR BIT, and the logits are BIT-IDENTICAL to vh_forward_u8 of vh_op_resize_yuy2's (vh_op_resize_y210's) output.
- * Packed 4:4:4 (AYUV, Y410, v410), 4:1:1 and big-endian words are not taken.
+ * Packed 4:4:4 (AYUV, Y410, v410) goes to "Packed 4:4:4 frames" below; 4:1:1 and big-endian words are not taken.
  * REFUSED with VH_ERR_INVALID before a device is touched or anything is enqueued, each with a message of its own: width or height
  * outside 1..8192; a layout that is none of VH_422_*, or VH_422_V210 on the 8-bit entry points; row_stride below the widths above;
  * an offset, a stride or a device frames pointer that is odd (16-bit words) or no multiple of 4 (v210); a frame whose last byte
@@ -482,6 +482,75 @@ int vh_forward_frames_yuy2(vh_ctx* ctx, const uint8_t* frames_host, size_t nbyte
 int vh_forward_device_frames_yuy2(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_dev);
 int vh_forward_frames_y210(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_host);
 int vh_forward_device_frames_y210(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_dev);
+/* ---- Packed 4:4:4 frames: BGR / BGRA / RGBA / ARGB, YUV24 / AYUV and Y410 / Y416 ------------------------------------------------------
+ * What most callers hold: OpenCV's Mat is BGR, screen and window capture, GPU colour converters and VA-API / D3D / AMF RGB surfaces
+ * are BGRA / RGBA / ARGB; 4:4:4 HEVC / AV1 decode surfaces, screen-content codecs and SDI 4:4:4 capture are AYUV, Y410, v410 and Y416.
+ * A PACKED 4:4:4 FRAME is ONE plane of pixels at `offset`, rows row_stride bytes apart; all formats share vh_frame_bgra.  width and
+ * height count PIXELS, are within 1..8192 and of ANY parity; `box` is in pixel coordinates as in vh_frame.  The context must have
+ * channels == 3.  Layout: sizeof(vh_frame_bgra) == 40; offset 0, height 8, width 12, row_stride 16, layout 20, box 24.
+ * LAYOUT WORD.  VH_444(p0, p1, p2, four, yuv) = p0 | p1 << 2 | p2 << 4 | (four ? 64 : 0) | (yuv ? 128 : 0): p_k is the index (0..3)
+ * within the pixel of the sample that becomes output component k (R, G, B; with `yuv`: Y, U, V); `four`: the pixel has four samples,
+ * else three; `yuv`: the three samples pass the colour matrix.  Any such word is taken, named or not; the named ones carry the MEMORY
+ * ORDER in the name.  The 4th sample (A or X) is never read as data.  Bits 8 and 9 belong to the two 10-bit layouts alone.
+ * 8-BIT ENTRY POINTS (_bgra).  A pixel is 3 or 4 bytes: VH_444_RGB, _BGR; _RGBA, _BGRA, _ARGB, _ABGR (RGBX, BGRX, XRGB, XBGR are the
+ * same layouts); VH_444_YUV24 = Y U V (V4L2 YUV24); VH_444_VUYA = V U Y A (Microsoft's AYUV FourCC, ffmpeg vuya / vuyx); VH_444_AYUV =
+ * A Y U V (ffmpeg ayuv).  Row bytes R = 3 * width or 4 * width; row_stride >= R.  Base, offset and stride may have any alignment.
+ * YUV layouts use the matrix of vh_set_frame_colour.
+ * 16-BIT ENTRY POINTS (_y410), YUV only.  VH_444_Y416 = U Y V A (Y416 / Y412, XV36) and VH_444_AYUV64 = A Y U V (ffmpeg ayuv64le):
+ * four little-endian 16-bit words per pixel, R = 8 * width; offset and row_stride must be even and a DEVICE frames pointer 2-byte
+ * aligned (a host pointer may have any alignment, because it is copied).  The word enters the arithmetic AS IS ("16-bit YUV frames",
+ * SAMPLE VALUES).  A layout word names positions, not a width: VH_444_Y416 on the _bgra entry points is the 8-bit pixel U Y V A.
+ * VH_444_Y410 (ffmpeg xv30le) and VH_444_V410: ONE little-endian 32-bit word per pixel, R = 4 * width; Y410 holds U in bits 0-9, Y in
+ * 10-19, V in 20-29 and ignores bits 30-31; V410 holds U in bits 2-11, Y in 12-21, V in 22-31 and ignores bits 0-1.  offset and
+ * row_stride must be multiples of 4 and a device frames pointer 4-byte aligned.  A 10-bit code enters the arithmetic as the fp32 value
+ * code * 64 (exact), as a v210 code does: the Y416 / P010 word of that code.  The matrix is that of vh_set_frame_colour16, whose
+ * default, 10 bits MSB-aligned, is Y410 under this rule.
+ * SPAN.  The frame's span is (height - 1) * row_stride + R <= nbytes - offset, and no load touches a byte outside it.
+ * RESAMPLING.  All three components use the ONE table pair (x, y) of the box: the axis contract's tables (vh_resize_table).  The
+ * horizontal pass runs first, then the vertical pass, each an fp32 fmaf chain in ascending tap order from 0, nothing rounded in
+ * between.  Chroma siting has no effect: nothing is sub-sampled.  YUV layouts: the unrounded y, u, v pass the nested-fmaf 3 x 4 matrix
+ * of "NV12 frames" and the byte is rintf(min(max(out[k], 0), 255)).  RGB layouts: no matrix and no colour state; the byte of output
+ * channel k is rintf(min(max(v_k, 0), 255)) of the resampled sample p_k.
+ * EQUIVALENCES, BIT FOR BIT.  An RGB layout gives the bytes of vh_op_resize_u8 (channels 3) on the frame with its pixels rewritten
+ * as tight R G B.  A YUV layout gives the bytes of vh_op_resize_yuv (vh_op_resize_yuv16) on the de-interleaved planes with sub_x =
+ * sub_y = 1 and the same matrix.  A Y410 and a V410 frame give the bytes of the Y416 frame holding code << 6.  The logits are
+ * BIT-IDENTICAL to vh_forward_u8 of vh_op_resize_bgra's (vh_op_resize_y410's) output.
+ * NOT TAKEN: RGB words of 10 / 16 bits (x2rgb10, rgb48, rgba64), big-endian words, alpha blending (A is skipped, not applied).
+ * REFUSED with VH_ERR_INVALID before a device is touched or anything is enqueued, each with a message of its own; per descriptor
+ * the checks run in this order: width or height outside 1..8192; a layout with bits outside the defined ones; a position 3 in a
+ * three-sample pixel; a 10-bit layout on the _bgra entry points; on the _y410 entry points a 10-bit layout that is neither
+ * VH_444_Y410 nor VH_444_V410, or a word layout without `yuv` or without `four`; row_stride < R; an offset, a stride or a device
+ * frames pointer (each separately) that is odd (16-bit words) or no multiple of 4 (Y410 / V410); a frame whose span ends beyond
+ * nbytes; a box outside the frame, or empty; scale > 32 on an axis.  Ahead of the descriptors: null pointers, a bad batch, channels
+ * != 3.
+ *   vh_forward_frames_bgra, vh_forward_device_frames_bgra: vh_forward_frames_yuy2 / vh_forward_device_frames_yuy2 for 8-bit packed
+ *                       4:4:4 frames, the same argument list with vh_frame_bgra descriptors.
+ *   vh_forward_frames_y410, vh_forward_device_frames_y410: vh_forward_frames_y210 / vh_forward_device_frames_y210 for Y416 /
+ *                       AYUV64 / Y410 / V410 frames.  Stage "resize" of vh_set_stage_timing times these launches too. */
+#define VH_444(p0, p1, p2, four, yuv) ((p0) | (p1) << 2 | (p2) << 4 | ((four) ? 64 : 0) | ((yuv) ? 128 : 0))
+#define VH_444_RGB VH_444(0, 1, 2, 0, 0)      /* R G B                                   */
+#define VH_444_BGR VH_444(2, 1, 0, 0, 0)      /* B G R        (OpenCV)                   */
+#define VH_444_RGBA VH_444(0, 1, 2, 1, 0)     /* R G B A      (RGBX)                     */
+#define VH_444_BGRA VH_444(2, 1, 0, 1, 0)     /* B G R A      (BGRX; D3D, GDI, VA-API)   */
+#define VH_444_ARGB VH_444(1, 2, 3, 1, 0)     /* A R G B      (XRGB)                     */
+#define VH_444_ABGR VH_444(3, 2, 1, 1, 0)     /* A B G R      (XBGR)                     */
+#define VH_444_YUV24 VH_444(0, 1, 2, 0, 1)    /* Y U V        (V4L2 YUV24)               */
+#define VH_444_VUYA VH_444(2, 1, 0, 1, 1)     /* V U Y A      (the AYUV FourCC; vuya, vuyx) */
+#define VH_444_AYUV VH_444(1, 2, 3, 1, 1)     /* A Y U V      (ffmpeg ayuv)              */
+#define VH_444_Y416 VH_444(1, 0, 2, 1, 1)     /* U Y V A, 16-bit words (Y416, Y412, XV36); _y410 entry points */
+#define VH_444_AYUV64 VH_444(1, 2, 3, 1, 1)   /* A Y U V, 16-bit words (ayuv64le);         _y410 entry points */
+#define VH_444_Y410 (VH_444(1, 0, 2, 1, 1) | 256)         /* one 32-bit word: U 0-9, Y 10-19, V 20-29; _y410 entry points */
+#define VH_444_V410 (VH_444(1, 0, 2, 1, 1) | 256 | 512)   /* one 32-bit word: U 2-11, Y 12-21, V 22-31; _y410 entry points */
+typedef struct vh_frame_bgra {
+    uint64_t offset;
+    int32_t height, width, row_stride;   /* pixels, pixels, bytes */
+    int32_t layout;                      /* VH_444_*             */
+    float box[4];
+} vh_frame_bgra;
+int vh_forward_frames_bgra(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_host);
+int vh_forward_device_frames_bgra(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_dev);
+int vh_forward_frames_y410(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_host);
+int vh_forward_device_frames_y410(vh_ctx* ctx, const uint8_t* frames_dev, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_dev);
 /* uniform[-1,1) synthetic images written straight into HBM (value range of the reference,
  * def/defines.h:11-12) */
 int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_dev);
@@ -542,6 +611,12 @@ int vh_ring_submit_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_host, size_t 
  * bits vh_forward_frames_yuy2 / vh_forward_frames_y210 returns. */
 int vh_ring_submit_frames_yuy2(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch);
 int vh_ring_submit_frames_y210(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch);
+/* Packed 4:4:4 frames ("Packed 4:4:4 frames" above) on the SAME frames ring, interleaved with every other kind of submit; _bgra
+ * uses the first colour state (YUV layouts; RGB layouts use none), _y410 (Y416 / AYUV64 / Y410 / V410) the second.  The same rules:
+ * checked and copied before anything is enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other two kinds
+ * of ring.  A collected batch has the bits vh_forward_frames_bgra / vh_forward_frames_y410 returns. */
+int vh_ring_submit_frames_bgra(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch);
+int vh_ring_submit_frames_y410(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -747,6 +822,14 @@ int vh_op_resize_yuv16(const uint8_t* frames_dev, size_t nbytes, const vh_frame_
 int vh_op_resize_yuy2(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc_host, int batch, int out_size,
                       const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 int vh_op_resize_y210(const uint8_t* frames_dev, size_t nbytes, const vh_frame_yuy2* desc_host, int batch, int out_size,
+                      const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
+/* The same tap for packed 4:4:4 frames ("Packed 4:4:4 frames"): the arguments of vh_op_resize_yuy2 / vh_op_resize_y210 with
+ * vh_frame_bgra descriptors.  m12_host must be given and finite even where every layout is RGB (it is then unused); chroma_site is
+ * accepted and has no effect.  _bgra: any alignment.  _y410: frames_dev 2-byte aligned, offsets and strides even (Y410 / V410:
+ * multiples of 4).  Every argument and descriptor is checked before a device is touched. */
+int vh_op_resize_bgra(const uint8_t* frames_dev, size_t nbytes, const vh_frame_bgra* desc_host, int batch, int out_size,
+                      const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
+int vh_op_resize_y410(const uint8_t* frames_dev, size_t nbytes, const vh_frame_bgra* desc_host, int batch, int out_size,
                       const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);

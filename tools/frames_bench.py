@@ -40,6 +40,15 @@ Packed 4:2:2 passes, ViT-B/16 bf16, in ONE process: the frames 
 and medians.  YUY2 uploads 2 bytes per pixel, v210 16 bytes per 6 pixels.  The planar 4:2:2, the YUY2 and the v210 ring compute the
 same logits under the two default colour states, which is checked.  Then the resize launch of each of the five.  Written to
 <out>/packed422_host_path.txt and .json.
+
+  python tools/frames_bench.py --bgra [--out profiles] [--steps 30] [--passes 3]
+
+Packed 4:4:4 passes, ViT-B/16 bf16, in ONE process: the frames rings fed the SAME pictures as RGB frames, as their
+BGRA frames, as the planar 4:4:4 planes, as the VUYA frames of those planes and as their Y410 frames (10-bit code = 8-bit code x 4),
+the same two shapes, boxes, passes and medians.  BGRA, VUYA and Y410 upload 4 bytes per pixel, RGB and planar 4:4:4 three.  The BGRA
+ring computes the RGB ring's logits, the VUYA and the Y410 ring the planar ring's, which is checked.  Then the resize launch of each
+of the five, and the two ratios measured in this process: packed against planar 4:4:4 and BGRA against RGB.  Written to
+<out>/packed444_host_path.txt and .json.
 """
 import argparse
 import json
@@ -318,6 +327,90 @@ def yuy2_main(a):
         f.write("\n".join(lines) + "\n")
 
 
+def bgra_main(a):
+    import packed444_ref as Q
+    import yuv_ref as Y
+    lines, rows = [], []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    scale, shift = vithip.input_norm_from_mean_std(MEAN, STD)
+    title, key, cfg, dname, _, flags, eps = RUNS[0]
+    log(f"frames_bench --bgra: {title[:-5]}, frames rings of {SLOTS} slots, {a.steps} steps per pass, {a.passes} interleaved passes (RGB frames, "
+        f"their BGRA frames, the planar 4:4:4 planes, the VUYA and the Y410 frames of those planes, Y410 code = byte x 4; 0.875 centre box); "
+        f"median pass [min .. max]; images/s")
+    for h, w, batch in ((360, 480, 512), (1080, 1920, 64)):
+        rng = np.random.default_rng(3)
+        small = rng.integers(0, 256, size=(batch, h // 8, w // 8, 3), dtype=np.uint8)
+        rgb = np.ascontiguousarray(np.repeat(np.repeat(small, 8, axis=1), 8, axis=2))     # the pictures of --nv12
+        rgb ^= rng.integers(0, 8, size=rgb.shape, dtype=np.uint8)
+        box = vithip.center_crop_box(h, w)
+        inside = batch * (box[2] - box[0]) * (box[3] - box[1])
+        common = (cfg, dname, batch, flags, eps, scale, shift)
+        p444 = [Y.rgb_to_yuv_planes(f, 1, 1) for f in rgb]
+        planar = np.stack([np.concatenate([p.reshape(-1) for p in t]) for t in p444])
+        bgra = np.stack([Q.row_bytes(tuple(f[..., k] for k in range(3)), Q.BGRA).reshape(-1) for f in rgb])
+        vuya = np.stack([Q.row_bytes(t, Q.VUYA).reshape(-1) for t in p444])
+        y410 = np.stack([Q.row_bytes(tuple(p.astype(np.uint16) << 2 for p in t), Q.Y410).reshape(-1) for t in p444])
+        dpl = (vithip.FrameYUV * batch)()
+        dbg, dvu, dy4 = ((vithip.FrameBGRA * batch)() for _ in range(3))
+        for b in range(batch):
+            d, per = dpl[b], planar.shape[1]
+            d.y_offset, d.u_offset, d.v_offset = b * per, b * per + h * w, b * per + 2 * h * w
+            d.height, d.width, d.y_stride, d.u_stride, d.v_stride, d.sub_x, d.sub_y = h, w, w, w, w, 1, 1
+            d.box[:] = box
+            for d, buf, lay in ((dbg[b], bgra, Q.BGRA), (dvu[b], vuya, Q.VUYA), (dy4[b], y410, Q.Y410)):
+                d.offset, d.height, d.width, d.row_stride, d.layout = b * buf.shape[1], h, w, buf.shape[1] // h, lay
+                d.box[:] = box
+        sides = dict(rgb=Side(*common, frames=rgb, box=box),
+                     bgra=SideRaw(*common, bgra, dbg, inside * 4.0, "ring_submit_frames_bgra_packed"),
+                     p444=SideRaw(*common, planar, dpl, inside * 3.0, "ring_submit_frames_yuv_packed"),
+                     vuya=SideRaw(*common, vuya, dvu, inside * 4.0, "ring_submit_frames_bgra_packed"),
+                     y410=SideRaw(*common, y410, dy4, inside * 4.0, "ring_submit_frames_y410_packed"))
+        del rgb, p444, planar, bgra, vuya, y410
+        bits = lambda k: sides[k].first.view(np.uint32)
+        same_rgb = bool(np.array_equal(bits("rgb"), bits("bgra")) and np.isfinite(sides["bgra"].first).all())
+        same_yuv = bool(np.array_equal(bits("p444"), bits("vuya")) and np.array_equal(bits("p444"), bits("y410")) and np.isfinite(sides["vuya"].first).all())
+        rates = {k: [] for k in sides}
+        for _ in range(a.passes):
+            for k, sd in sides.items():
+                rates[k].append(sd.ring_rate(a.steps))
+        us = {k: [] for k in sides}
+        for _ in range(2):                                                                 # two interleaved passes of the launch alone
+            for k, sd in sides.items():
+                us[k].append(sd.resize_us(8))
+        t = {k: float(np.mean([x[0] for x in v])) for k, v in us.items()}
+        r = dict(config=key, frame=[h, w], batch=batch, logits_bgra_equal_rgb=same_rgb, logits_vuya_and_y410_equal_planar_444=same_yuv,
+                 ring={k: mid(v) for k, v in rates.items()}, h2d_MB_per_step={k: sd.nbytes / 1e6 for k, sd in sides.items()},
+                 bytes_per_pixel={k: sd.nbytes / (batch * h * w) for k, sd in sides.items()},
+                 resize_us_avg={k: [x[0] for x in v] for k, v in us.items()}, resize_us_min={k: min(x[1] for x in v) for k, v in us.items()},
+                 box_MB={k: sd.box_bytes / 1e6 for k, sd in sides.items()},
+                 resize_ratio=dict(vuya_over_planar_444=t["vuya"] / t["p444"], y410_over_planar_444=t["y410"] / t["p444"], bgra_over_rgb=t["bgra"] / t["rgb"]))
+        rows.append(r)
+        log(f"{h}x{w}, batch {batch}: logits of the BGRA ring equal the RGB ring's bit for bit: {same_rgb}; of the VUYA and the Y410 ring the planar 4:4:4 ring's: {same_yuv}")
+        for k, sd in sides.items():
+            m, lo, hi = r["ring"][k]
+            log(f"    frames ring, {k.upper():4s}: {m:9.0f} [{lo:9.0f} .. {hi:9.0f}] = {100 * m / r['ring']['rgb'][0]:6.2f} % of the RGB ring, "
+                f"{100 * m / r['ring']['p444'][0]:6.2f} % of the planar 4:4:4 ring | upload {sd.nbytes / 1e6:7.1f} MB per step "
+                f"({r['bytes_per_pixel'][k]:.3f} bytes per pixel) = {sd.nbytes * 1e-9 * m / batch:5.1f} GB/s")
+        for k, sd in sides.items():
+            avg, mb = r["resize_us_avg"][k], sd.box_bytes / 1e6
+            log(f"    resize {k.upper():4s}: {t[k]:8.1f} us per launch avg ({r['resize_us_min'][k]:.1f} min; passes {avg[0]:.1f} {avg[1]:.1f}) | "
+                f"{mb:.1f} MB inside the boxes = {mb * 1e-3 / (t[k] * 1e-6):.0f} GB/s")
+        q = r["resize_ratio"]
+        log(f"    resize launch, same process: VUYA / planar 4:4:4 = {q['vuya_over_planar_444']:.3f}, Y410 / planar 4:4:4 = {q['y410_over_planar_444']:.3f}, "
+            f"BGRA / RGB = {q['bgra_over_rgb']:.3f}")
+        for sd in sides.values():
+            sd.close()
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "packed444_host_path.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+    with open(os.path.join(a.out, "packed444_host_path.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def p010_main(a):
     import nv12_ref as N
     lines, rows = [], []
@@ -498,7 +591,10 @@ def main():
     ap.add_argument("--yuv420p", action="store_true", help="the planar passes (NV12 frames ring against I420 frames ring) instead")
     ap.add_argument("--p010", action="store_true", help="the 10-bit passes (RGB, NV12 and P010 frames rings of the same pictures) instead")
     ap.add_argument("--yuy2", action="store_true", help="the packed 4:2:2 passes (RGB, NV12, planar 4:2:2, YUY2 and v210 frames rings) instead")
+    ap.add_argument("--bgra", action="store_true", help="the packed 4:4:4 passes (RGB, BGRA, planar 4:4:4, VUYA and Y410 frames rings) instead")
     a = ap.parse_args()
+    if a.bgra:
+        return bgra_main(a)
     if a.yuy2:
         return yuy2_main(a)
     if a.p010:

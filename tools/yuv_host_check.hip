@@ -15,10 +15,13 @@
 // CASE (little endian): int32 layout (bit 0: 1 = vh_frame_yuv descriptors, 0 = vh_frame_nv12; bit 1: 16-bit samples; bit 2: packed
 // 4:2:2, vh_frame_yuy2 descriptors, bit 0 then unread; bit 3: the frames start one sample (1 or 2 bytes) into their heap block, so
 // that the base itself is what breaks the macropixel alignment), S, batch, chroma_site; float m[12]; uint64 nbytes; the
-// descriptors; nbytes of frames.  OUT: [batch][S][S][3] bytes.
+// descriptors; nbytes of frames.  OUT: [batch][S][S][3] bytes.  Bit 4: packed 4:4:4, vh_frame_bgra descriptors and
+// resize_packed444_body, bits 0 and 2 then unread; bits 8-10 of the word are then the number of bytes (0..7) the frames start into
+// their heap block, so that the base takes every residue the one-load-per-pixel rule asks about.
 // With 16-bit samples UBSan's alignment check watches every uint16_t and uint32_t load: the planner's even-offset rule (and its
 // multiple-of-4 rule for the pair load) has to be what makes them aligned.  The same holds for the packed layouts' 32-bit and 64-bit
-// macropixel loads and for v210's 32-bit words.
+// macropixel loads and for v210's 32-bit words, and for the 32-bit and 64-bit pixel loads of the packed 4:4:4 body; its 3-byte pixels
+// end an exact-size block, so that a load wider than a byte at the last pixel is an AddressSanitizer report.
 #include <pthread.h>
 
 #include <cstdio>
@@ -51,12 +54,13 @@ int main(int argc, char** argv) {
     uint64_t nbytes;
     if (!rd(f, &layout) || !rd(f, &S) || !rd(f, &batch) || !rd(f, &site) || !rd(f, m, 12) || !rd(f, &nbytes) || batch < 1 || batch > 4096)
         return die("short case file");
-    const bool packed = layout & 4, planar = !packed && (layout & 1), wide = layout & 2;
-    const size_t shift = layout & 8 ? (wide ? 2 : 1) : 0;
+    const bool p444 = layout & 16, packed = !p444 && (layout & 4), planar = !packed && !p444 && (layout & 1), wide = layout & 2;
+    const size_t shift = p444 ? (size_t)((layout >> 8) & 7) : layout & 8 ? (wide ? 2 : 1) : 0;
     std::vector<vh_frame_yuv> dy(planar ? batch : 0);
-    std::vector<vh_frame_nv12> dn(planar || packed ? 0 : batch);
+    std::vector<vh_frame_nv12> dn(planar || packed || p444 ? 0 : batch);
     std::vector<vh_frame_yuy2> dp(packed ? batch : 0);
-    if (packed ? !rd(f, dp.data(), (size_t)batch) : planar ? !rd(f, dy.data(), (size_t)batch) : !rd(f, dn.data(), (size_t)batch))
+    std::vector<vh_frame_bgra> d4(p444 ? batch : 0);
+    if (p444 ? !rd(f, d4.data(), (size_t)batch) : packed ? !rd(f, dp.data(), (size_t)batch) : planar ? !rd(f, dy.data(), (size_t)batch) : !rd(f, dn.data(), (size_t)batch))
         return die("short descriptors");
     uint8_t* block = (uint8_t*)malloc(nbytes + shift);               // exact size: the byte behind the last plane is poisoned
     uint8_t* frames = block + shift;
@@ -66,7 +70,8 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> words;
     int max_tiles = 0;
     const uintptr_t base = (uintptr_t)frames;
-    const char* why = packed ? vh::resize_plan_build_yuy2(dp.data(), batch, S, (size_t)nbytes, (unsigned)(base & 7), site, wide ? 2 : 1, &words, &max_tiles)
+    const char* why = p444 ? vh::resize_plan_build_bgra(d4.data(), batch, S, (size_t)nbytes, (unsigned)(base & 7), wide ? 2 : 1, &words, &max_tiles)
+                    : packed ? vh::resize_plan_build_yuy2(dp.data(), batch, S, (size_t)nbytes, (unsigned)(base & 7), site, wide ? 2 : 1, &words, &max_tiles)
                     : planar ? vh::resize_plan_build_yuv(dy.data(), batch, S, (size_t)nbytes, (base & 1) == 0, site, wide ? 2 : 1, &words, &max_tiles)
                     : vh::resize_plan_build_nv12(dn.data(), batch, S, (size_t)nbytes, (unsigned)(base & 3), site, wide ? 2 : 1, &words, &max_tiles);
     if (why) {
@@ -90,7 +95,9 @@ int main(int argc, char** argv) {
     auto item = [&](int tid) {
         auto barrier = [&] { pthread_barrier_wait(&bar); };
         for (int b = 0; b < blocks; ++b) {
-            if (packed && wide) vh::resize_yuv_body<true, uint16_t, true>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            if (p444 && wide) vh::resize_packed444_body<uint16_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            else if (p444) vh::resize_packed444_body<uint8_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
+            else if (packed && wide) vh::resize_yuv_body<true, uint16_t, true>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
             else if (packed) vh::resize_yuv_body<true, uint8_t, true>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
             else if (planar && wide) vh::resize_yuv_body<true, uint16_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
             else if (planar) vh::resize_yuv_body<true, uint8_t>(frames, plan, out, S, max_tiles, mat, lds, b, tid, barrier);
@@ -115,6 +122,7 @@ int main(int argc, char** argv) {
     }
     printf("ok: %d frame(s) -> %d, %zu plan words, %d workgroups (at most %d bands x %d column tiles a frame)", batch, S, words.size(), blocks, bands, tiles);
     if (packed) printf(", %d frame(s) with one load per macropixel", wide_loads);
+    if (p444) printf(", %d frame(s) with one load per pixel, base %% 8 = %u", wide_loads, (unsigned)(base & 7));
     printf("\n");
     FILE* g = fopen(argv[2], "wb");
     if (!g || fwrite(out, 1, nout, g) != nout) return die("cannot write the output");

@@ -8,11 +8,16 @@ the same operator cases with real 10 / 12 / 16-bit planes, all-0xFFFF words, eve
 paths of P016, a mixed batch, 40 small frames, one 1080 x 1920 P010 frame and the 4:4:4 planner boundary.  Then the packed 4:2:2
 instantiations: every layout of YUY2 and Y210 over the cases of tests/test_packed422.py, v210 at every width mod 6
 with bits 30-31 set, every offset, stride padding and base alignment either side of the one-load-per-macropixel rule, a mixed batch,
-40 small frames and one 1080 x 1920 UYVY and v210 frame, each compared with the emulation of the DE-INTERLEAVED planes.  CPU only;
-no device is touched.
+40 small frames and one 1080 x 1920 UYVY and v210 frame, each compared with the emulation of the DE-INTERLEAVED planes.  With
+--packed444 the packed 4:4:4 body instead (the modes above are unchanged and do not run it): every 8-bit layout, Y416
+and AYUV64, Y410 and V410 with their ignored bits set over the cases of tests/test_packed444.py, every offset, row padding and base
+residue either side of the one-load-per-pixel rule, 3-byte and 4-byte pixels that end an exact-size heap block, mixed batches, 40
+small frames, one 1080 x 1920 BGRA and Y410 frame and the 4:4:4 planner boundary, each compared with the emulation of the
+de-interleaved planes (RGB layouts: under the pass-through matrix, which the body does not read).  CPU only; no device is touched.
 
-    python tools/yuv_host_check.py            (needs libvithip.so: make -C vit-fpga_amd)
-    python tools/yuv_host_check.py --packed   (the packed 4:2:2 cases alone)"""
+    python tools/yuv_host_check.py               (needs libvithip.so: make -C vit-fpga_amd)
+    python tools/yuv_host_check.py --packed      (the packed 4:2:2 cases alone)
+    python tools/yuv_host_check.py --packed444   (the packed 4:4:4 cases)"""
 import os
 import struct
 import subprocess
@@ -37,6 +42,8 @@ from test_yuv_planar import COLOURS, OP_CASES, SUBS, make_yuv  # noqa: E402
 import yuv16_ref as W  # noqa: E402
 import packed422_ref as P  # noqa: E402
 from test_packed422 import PACKED_CASES, V210_WIDTHS  # noqa: E402
+import packed444_ref as Q  # noqa: E402
+from test_packed444 import PACKED_CASES as CASES444  # noqa: E402
 
 EXE = os.path.join(ROOT, "tools", "yuv_host_check")
 PKG = os.path.join(ROOT, "vit-fpga_amd")
@@ -170,6 +177,110 @@ def main_packed(tmp):
     return good
 
 
+PASS_THROUGH = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32)
+GARBAGE = np.full((3, 4), 1e30, np.float32)   # what an RGB layout is handed as its matrix: it must not be read
+
+
+def run_444(tmp, label, frames, boxes, s, m, layouts, shift=0, **layout):
+    """One call of the packed 4:4:4 body; `frames` are component triples in output order (10-bit layouts: codes), the emulation is
+    that of the planar 4:4:4 frame (10-bit: of the codes << 6; RGB layouts: under the pass-through matrix)."""
+    wide = frames[0][0].dtype == np.uint16
+    buf, desc = Q.lay_out(frames, boxes, layouts, **layout)
+    case, out = os.path.join(tmp, "case.bin"), os.path.join(tmp, "out.bin")
+    with open(case, "wb") as f:
+        f.write(struct.pack("<4i", 16 | (2 if wide else 0) | (shift << 8), s, len(frames), 0))
+        f.write(np.ascontiguousarray(m, np.float32).tobytes())
+        f.write(struct.pack("<Q", buf.nbytes))
+        f.write(bytes(desc))
+        f.write(buf.tobytes())
+    p = subprocess.run([EXE, case, out], capture_output=True, text=True)
+    if p.returncode:
+        print(f"FAIL {label}: exit {p.returncode}\n{p.stdout}{p.stderr}")
+        return False
+    got = np.fromfile(out, np.uint8).reshape(len(frames), s, s, 3)
+    words = lambda c, d: tuple((a << 6).astype(np.uint16) for a in c) if d.layout & 256 else c
+    want = np.stack([Y.resize_yuv_f32(*words(c, d), box, s, m if Q.is_yuv(d.layout) else PASS_THROUGH, N.CHROMA_CENTER, Q.SUB)
+                     for c, box, d in zip(frames, boxes, desc)])
+    same = np.array_equal(got, want)
+    print(f"{'ok  ' if same else 'DIFF'} packed 4:4:4 {label}: {p.stdout.strip()}")
+    return same
+
+
+def rgb_planes(h, w, seed):
+    from test_nv12 import make_rgb
+    rgb = make_rgb(h, w, seed)
+    return tuple(np.ascontiguousarray(rgb[..., k]) for k in range(3))
+
+
+def main_packed444(tmp):
+    """The packed 4:4:4 instantiations."""
+    good = True
+    m8 = N.yuv_matrix(N.BT709, False)
+    mats16 = {k: W.yuv_matrix16(std, full, bits, msb) for k, (std, full, bits, msb, _) in COLOURS16.items()}
+    m10, m16 = mats16["bt709_limited_10_msb_left"], mats16["bt709_full_16_msb_centre"]
+    for name, (h, w, box, s) in CASES444.items():
+        for key, lay in Q.RGB_LAYOUTS.items():
+            good &= run_444(tmp, f"{key} {name}", [rgb_planes(h, w, h + w)], [box], s, GARBAGE, lay)
+        for key, lay in Q.YUV_LAYOUTS.items():
+            for colour, (std, full, _) in COLOURS.items():
+                good &= run_444(tmp, f"{key} {name} {colour}", [make_yuv(h, w, Q.SUB, seed=h + w)], [box], s, N.yuv_matrix(std, full), lay)
+        for key, lay in Q.WORD_LAYOUTS.items():
+            good &= run_444(tmp, f"{key} {name} 10 bits msb", [make_yuv16(h, w, Q.SUB, h + w, "bt709_limited_10_msb_left")], [box], s, m10, lay)
+            good &= run_444(tmp, f"{key} {name} 16 bits", [make_yuv16(h, w, Q.SUB, h + w, "bt709_full_16_msb_centre")], [box], s, m16, lay)
+        codes = make_yuv16(h, w, Q.SUB, h + w, CODES10)
+        for a in codes:
+            a[0, 0], a[-1, -1] = 0, 1023
+        for key, lay in (("y410", Q.Y410), ("v410", Q.V410)):
+            good &= run_444(tmp, f"{key} {name}", [codes], [box], s, m10, lay, ignored=3)
+    # either side of the one-load-per-pixel rule: offsets, row padding and the base itself, every residue mod 8 that matters
+    boxes = [None, (0.5, 3.0, 29.5, 40.0)]
+    frames = [rgb_planes(37, 53, 21), make_yuv(42, 30, Q.SUB, seed=31)]
+    for lead in (0, 1, 2, 3, 4, 6):
+        for pad in (0, 1, 2, 3, 4):
+            for shift in (0, 1, 2, 3):
+                good &= run_444(tmp, f"4-byte pixels lead {lead} pad {pad} base+{shift}", frames, boxes, 16, m8, [Q.BGRA, Q.VUYA], shift, lead=lead, pad=pad, gap=lead)
+    for lead in (0, 1, 3):
+        for pad in (0, 1, 2):
+            good &= run_444(tmp, f"3-byte pixels lead {lead} pad {pad}", frames, boxes, 16, m8, [Q.BGR, Q.YUV24], lead, lead=lead, pad=pad, gap=lead)
+    frames = [make_yuv16(37, 53, Q.SUB, 21, "bt709_limited_10_msb_left"), make_yuv16(42, 30, Q.SUB, 31, "bt709_limited_10_msb_left")]
+    for lead in (0, 2, 4, 6):
+        for pad in (0, 2, 4, 6):
+            for shift in (0, 2, 4, 6):
+                good &= run_444(tmp, f"16-bit words lead {lead} pad {pad} base+{shift}", frames, boxes, 16, m10, [Q.Y416, Q.AYUV64], shift, lead=lead, pad=pad, gap=lead)
+    frames = [make_yuv16(37, 53, Q.SUB, 21, CODES10), make_yuv16(42, 30, Q.SUB, 31, CODES10)]
+    for lead in (0, 4, 12):
+        for pad in (0, 4):
+            for shift in (0, 4):
+                good &= run_444(tmp, f"10-bit words lead {lead} pad {pad} base+{shift}", frames, boxes, 16, m10, [Q.Y410, Q.V410], shift, lead=lead, pad=pad, gap=lead, ignored=1)
+    # a frame that ends with the heap block: the last pixel of a 3-byte and of a 4-byte layout, at every base residue
+    for shift in (0, 1, 2, 3):
+        for key, lay in (("bgr", Q.BGR), ("yuv24", Q.YUV24), ("bgra", Q.BGRA), ("argb", Q.ARGB)):
+            good &= run_444(tmp, f"{key} 5x3 ends its block, base+{shift}", [rgb_planes(5, 3, 9)], [None], 16, m8, lay, shift, pad=shift)
+            good &= run_444(tmp, f"{key} 7x54 ends its block, base+{shift}", [rgb_planes(7, 54, 9)], [None], 16, m8, lay, shift)
+    # bands and batches
+    shapes = [(37, 53), (64, 64), (20, 24), (98, 132), (270, 480), (1, 1), (33, 2)]
+    boxes = [None, None, (2.0, 1.0, 22.0, 19.5), (10.0, 5.0, 101.0, 96.0), vithip.center_crop_box(270, 480), None, None]
+    lays = [Q.BGR, Q.BGRA, Q.ARGB, Q.VUYA, Q.RGB, Q.AYUV, Q.YUV24]
+    frames = [make_yuv(h, w, Q.SUB, seed=40 + i) if Q.is_yuv(lay) else rgb_planes(h, w, 40 + i) for i, ((h, w), lay) in enumerate(zip(shapes, lays))]
+    good &= run_444(tmp, "8-bit mixed batch of 7", frames, boxes, 32, m8, lays, lead=1, gap=3, pad=1)
+    mixed = [Q.Y416, Q.Y410, Q.V410, Q.AYUV64, Q.V410, Q.Y416, Q.Y410]
+    frames = [make_yuv16(h, w, Q.SUB, 40 + i, CODES10) for i, (h, w) in enumerate(shapes)]
+    frames = [c if lay & 256 else tuple((a << 6).astype(np.uint16) for a in c) for c, lay in zip(frames, mixed)]
+    good &= run_444(tmp, "Y416, AYUV64, Y410 and V410 frames in one batch of 7", frames, boxes, 32, m10, mixed, lead=4, gap=4)
+    small = [None if i % 2 else (0.5, 1.0, 38.25, 40.0) for i in range(40)]
+    every8 = list(Q.RGB_LAYOUTS.values()) + list(Q.YUV_LAYOUTS.values())
+    lays = [every8[i % 9] for i in range(40)]
+    good &= run_444(tmp, "8-bit 40 frames of 41x39 (tall bands)", [make_yuv(41, 39, Q.SUB, seed=100 + i) for i in range(40)], small, 32, m8, lays)
+    good &= run_444(tmp, "Y410 40 frames of 41x39 (tall bands)", [make_yuv16(41, 39, Q.SUB, 100 + i, CODES10) for i in range(40)], small, 32, m10, Q.Y410)
+    crop = [vithip.center_crop_box(1080, 1920)]
+    good &= run_444(tmp, "1080x1920 BGRA -> 64", [rgb_planes(1080, 1920, 3)], crop, 64, GARBAGE, Q.BGRA)
+    good &= run_444(tmp, "1080x1920 Y410 -> 64", [make_yuv16(1080, 1920, Q.SUB, 3, CODES10)], crop, 64, m10, Q.Y410)
+    for h in planner_boundary_444(130):
+        good &= run_444(tmp, f"4:4:4 planner boundary, VUYA {h}x36 -> 130", [make_yuv(h, 36, Q.SUB, seed=7)], [None], 130, m8, Q.VUYA)
+        good &= run_444(tmp, f"4:4:4 planner boundary, Y416 {h}x36 -> 130", [make_yuv16(h, 36, Q.SUB, 7, "bt709_limited_10_msb_left")], [None], 130, m10, Q.Y416)
+    return good
+
+
 def main16(tmp):
     """The 16-bit instantiations."""
     good = True
@@ -222,6 +333,11 @@ def main16(tmp):
 def main():
     build()
     good = True
+    if "--packed444" in sys.argv[1:]:
+        with tempfile.TemporaryDirectory() as tmp:
+            good = main_packed444(tmp)
+        print("every output equals the fp32 emulation; no sanitizer report" if good else "FAILED")
+        return 0 if good else 1
     if "--packed" in sys.argv[1:]:
         with tempfile.TemporaryDirectory() as tmp:
             good = main_packed(tmp)

@@ -42,6 +42,15 @@
 // record's uv16 says that base + offset and stride are multiples of the macropixel, single samples otherwise.  v210: sample slot s of
 // a row is bits 10 (s % 3) .. 10 (s % 3) + 9 of 32-bit word s / 3 (three codes per word, four words per block of twelve slots); luma j
 // is slot 2j + 1, U k slot 4k, V k slot 4k + 2; a code enters the arithmetic as (float)code * 64.0f, the Y210 word of that code.
+//
+// PACKED 4:4:4 (include/vithip.h, "Packed 4:4:4 frames").  BGR / BGRA / RGBA / ARGB, YUV24 / VUYA / AYUV (T = uint8_t),
+// Y416 / AYUV64 and Y410 / v410 (T = uint16_t).  A packed 4:4:4 frame IS the planar 4:4:4 frame (sub_x = sub_y = 1) of its
+// de-interleaved samples: the planner feeds plan_frames that YuvSrc, so tables and bands are the planar ones (one table per axis, three
+// floats per column and source row).  The body is a text of its own, resize_packed444_body, because here ONE work item of the
+// horizontal pass computes all three sums of a pixel: one 32-bit (64-bit) load per tap where the record's uv16 says the pixel is
+// naturally aligned, single samples otherwise and always for 3-sample pixels (a wide load at the last pixel would leave the frame).
+// Positions and shifts come from the record's layout word (VH_444: p0 | p1 << 2 | p2 << 4 | four << 6 | yuv << 7; bit 8: one 32-bit
+// word of three 10-bit codes per pixel, bit 9: those codes start at bit 2); no branch names a format.  LDS: fp32 [rows][cols][3].
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -66,6 +75,7 @@ struct RzNv12 {
     uint64_t v_off;                // planar: the V plane, rows v_stride apart
     int32_t v_stride;
     int32_t layout;                // packed 4:2:2: VH_422_*; y_off = uv_off = the frame, y_stride = uv_stride = row_stride, ch = h
+                                   // (packed 4:4:4: VH_444_*, the same fields; uv16: one load per pixel)
 };
 static_assert(sizeof(RzNv12) == 4 * kResizeNv12FrameWords, "RzNv12 layout");
 
@@ -333,6 +343,68 @@ const char* resize_plan_build_yuy2(const vh_frame_yuy2* desc, int batch, int S, 
     return nullptr;
 }
 
+// packed 4:4:4: every refusal of the contract has a message of its own, in the order the header lists them.  sample_bytes 1: three or
+// four bytes per pixel.  2: four 16-bit words per pixel (offset, stride and base even) or one 32-bit word of three 10-bit codes
+// (multiples of 4), told apart per frame by the layout word.  base_mod8 = the base address & 7 (0 for a host buffer, which is copied).  The YuvSrc is the planar 4:4:4 frame of the de-interleaved samples; siting has nothing to act on.
+const char* resize_plan_build_bgra(const vh_frame_bgra* desc, int batch, int S, size_t nbytes, unsigned base_mod8, int sample_bytes,
+                                   std::vector<uint32_t>* words, int* max_tiles) {
+    const bool wide = sample_bytes == 2;
+    if (sample_bytes != 1 && !wide) return "resize_bgra: sample_bytes must be 1 or 2";
+    if (!desc || batch < 1 || S < 1 || S > 4096) return wide ? "resize_y410: bad batch or output size" : "resize_bgra: bad batch or output size";
+    std::vector<YuvSrc> src((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        const vh_frame_bgra& d = desc[b];
+        if (d.width < 1 || d.width > kResizeMaxSide || d.height < 1 || d.height > kResizeMaxSide)
+            return wide ? "resize_y410: width and height must be 1..8192" : "resize_bgra: width and height must be 1..8192";
+        if (d.layout < 0 || (d.layout & ~0x3ff) || ((d.layout & 0x200) && !(d.layout & 0x100)))
+            return wide ? "resize_y410: layout has bits outside those of VH_444 and the two 10-bit words" : "resize_bgra: layout has bits outside those of VH_444";
+        const bool four = d.layout & 64, yuv = d.layout & 128, w10 = d.layout & 0x100;
+        if (!four && ((d.layout & 3) == 3 || ((d.layout >> 2) & 3) == 3 || ((d.layout >> 4) & 3) == 3))
+            return wide ? "resize_y410: position 3 in a pixel of three samples" : "resize_bgra: position 3 in a pixel of three samples";
+        if (!wide && w10) return "resize_bgra: VH_444_Y410 / VH_444_V410 are 10-bit layouts; they go to the 16-bit (_y410) entry points";
+        if (wide && w10 && d.layout != VH_444_Y410 && d.layout != VH_444_V410) return "resize_y410: a 10-bit layout must be VH_444_Y410 or VH_444_V410";
+        if (wide && !w10 && !yuv) return "resize_y410: RGB words of 10 / 16 bits are not taken; the layout must have the yuv bit";
+        if (wide && !w10 && !four) return "resize_y410: a pixel of 16-bit words has four samples; the layout must have the four bit";
+        // bytes of one pixel; the unit whose multiple base + offset and stride must be for the one-load tap
+        const int64_t px = w10 ? 4 : (four ? 4 : 3) * (int64_t)sample_bytes;
+        const int64_t row = px * d.width;
+        if (d.row_stride < row)
+            return w10 ? "resize_y410: row_stride < 4 * width bytes (Y410 / V410)" : wide ? "resize_y410: row_stride < 8 * width bytes"
+                       : four ? "resize_bgra: row_stride < 4 * width bytes" : "resize_bgra: row_stride < 3 * width bytes";
+        if (w10) {
+            if (d.offset % 4) return "resize_y410: offset is no multiple of 4; Y410 / V410 words need 4-byte aligned offsets";
+            if (d.row_stride % 4) return "resize_y410: row_stride is no multiple of 4; Y410 / V410 words need 4-byte aligned rows";
+            if (base_mod8 % 4) return "resize_y410: the device frames pointer is no multiple of 4; Y410 / V410 words need a 4-byte aligned base";
+        } else if (wide) {
+            if (d.offset % 2) return "resize_y410: offset is odd; 16-bit samples need even byte offsets";
+            if (d.row_stride % 2) return "resize_y410: row_stride is odd; 16-bit samples need even byte strides";
+            if (base_mod8 % 2) return "resize_y410: the device frames pointer is odd; 16-bit samples need a 2-byte aligned base";
+        }
+        const uint64_t span = (uint64_t)(d.height - 1) * (uint64_t)d.row_stride + (uint64_t)row;
+        if (d.offset > nbytes || span > nbytes - d.offset) return wide ? "resize_y410: a frame ends beyond nbytes" : "resize_bgra: a frame ends beyond nbytes";
+        YuvSrc& s = src[b];
+        for (int i = 0; i < 4; ++i) s.box[i] = (double)d.box[i];
+        // written so that a NaN fails
+        if (!(s.box[0] >= 0.0 && s.box[0] < s.box[2] && s.box[2] <= (double)d.width && s.box[1] >= 0.0 && s.box[1] < s.box[3] &&
+              s.box[3] <= (double)d.height))
+            return wide ? "resize_y410: box outside the frame, or empty" : "resize_bgra: box outside the frame, or empty";
+        if (!((s.box[2] - s.box[0]) / (double)S <= (double)kResizeMaxScale && (s.box[3] - s.box[1]) / (double)S <= (double)kResizeMaxScale))
+            return wide ? "resize_y410: scale > 32 on an axis" : "resize_bgra: scale > 32 on an axis";
+        s.y_off = s.u_off = s.v_off = d.offset;
+        s.h = d.height; s.w = d.width; s.cw = d.width; s.ch = d.height;
+        s.y_stride = s.u_stride = s.v_stride = d.row_stride;
+        s.sub_x = 1; s.sub_y = 1;
+        // one load per pixel: a 10-bit pixel IS one aligned word; 3-sample pixels never (the load would leave the frame at its last pixel)
+        s.uv16 = w10 || (four && (base_mod8 + d.offset) % (uint64_t)px == 0 && (int64_t)d.row_stride % px == 0);
+        s.layout = d.layout;
+    }
+    if (const char* e = plan_frames(src, S, VH_CHROMA_CENTER, wide ? "resize_y410: a table of the box could not be built" : "resize_bgra: a table of the box could not be built",
+                                    words, max_tiles))
+        return e;
+    if ((int64_t)batch * *max_tiles > 0x7fffffffll) return wide ? "resize_y410: too many tiles" : "resize_bgra: too many tiles";
+    return nullptr;
+}
+
 // ---- the kernel ------------------------------------------------------------------------------------------------------------
 struct Nv12Matrix { float m[12]; };
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -521,6 +593,113 @@ __host__ __device__ __forceinline__ void resize_yuv_body(const uint8_t* __restri
     }
 }
 
+// Packed 4:4:4: the work of thread `tid` of workgroup `block`.  T: the sample, uint8_t (3 or 4 per pixel) or uint16_t (4 words per
+// pixel, or one 32-bit word of three 10-bit codes).  All three components share the x and the y table of the record (xt, yt), so one
+// item of the horizontal pass takes one pixel per tap and feeds three fmaf chains; LDS holds fp32 [rows][cols][3].  The branches on
+// the layout word and on uv16 are uniform over the workgroup (one frame per workgroup), so a batch may mix layouts.
+template <class T, class Barrier>
+__host__ __device__ __forceinline__ void resize_packed444_body(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan,
+                                                               uint8_t* __restrict__ out, int S, int max_tiles, const Nv12Matrix& mat, float* lds,
+                                                               int block, int tid, Barrier barrier) {
+    const int f = block / max_tiles, tile = block - f * max_tiles;
+    const RzNv12 d = *(const RzNv12*)(plan + (size_t)f * kResizeNv12FrameWords);
+    const int nc = (S + d.tile_cols - 1) / d.tile_cols, nb = (S + d.band_rows - 1) / d.band_rows;
+    if (tile >= nb * nc) return;
+    const int band = tile / nc;
+    const int r0 = band * d.band_rows, r1 = r0 + d.band_rows < S ? r0 + d.band_rows : S;
+    const int c0 = (tile - band * nc) * d.tile_cols, c1 = c0 + d.tile_cols < S ? c0 + d.tile_cols : S;
+    const int32_t* xfirst = (const int32_t*)(plan + d.xt);
+    const int32_t* xcount = xfirst + S;
+    const float* xw = (const float*)(xcount + S);
+    const int32_t* yfirst = (const int32_t*)(plan + d.yt);
+    const int32_t* ycount = yfirst + S;
+    const float* yw = (const float*)(ycount + S);
+    int ylo = yfirst[r0], yhi = ylo + ycount[r0];
+    for (int r = r0 + 1; r < r1; ++r) {
+        ylo = yfirst[r] < ylo ? yfirst[r] : ylo;
+        yhi = yfirst[r] + ycount[r] > yhi ? yfirst[r] + ycount[r] : yhi;
+    }
+    const int rows = yhi - ylo, cols = c1 - c0;
+    if (3 * rows * cols > kResizeLdsFloats || ylo < 0 || yhi > d.h) return;   // what plan_frames prices at sub 1, 1: rows + 2 rows
+    const uint8_t* src = frames + d.y_off;
+    // the sample of the pixel that becomes output component k
+    const int p0 = d.layout & 3, p1 = (d.layout >> 2) & 3, p2 = (d.layout >> 4) & 3;
+
+    // horizontal pass: source rows ylo .. yhi-1, output columns c0 .. c1-1, three sums per item
+    for (int e = tid; e < rows * cols; e += 256) {
+        const int y = e / cols, x = c0 + (e - y * cols);
+        const int n = xcount[x];
+        const float* w = xw + (size_t)x * d.xs;
+        const uint8_t* row = src + (size_t)(ylo + y) * d.y_stride;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        if (sizeof(T) == 2 && (d.layout & 0x100)) {
+            // one 32-bit word per pixel, 10-bit codes at bits 10 p (+ 2); a code enters as the 16-bit word code << 6 (exact)
+            const int lsb = (d.layout & 0x200) ? 2 : 0;
+            const int s0 = 10 * p0 + lsb, s1 = 10 * p1 + lsb, s2 = 10 * p2 + lsb;
+            const uint32_t* p = (const uint32_t*)row + xfirst[x];
+            for (int t = 0; t < n; ++t) {
+                const uint32_t q = p[t];
+                const float wt = w[t];
+                a0 = __builtin_fmaf(wt, (float)((q >> s0) & 0x3ffu) * 64.0f, a0);
+                a1 = __builtin_fmaf(wt, (float)((q >> s1) & 0x3ffu) * 64.0f, a1);
+                a2 = __builtin_fmaf(wt, (float)((q >> s2) & 0x3ffu) * 64.0f, a2);
+            }
+        } else if (d.uv16) {
+            typedef typename std::conditional<sizeof(T) == 2, uint64_t, uint32_t>::type Q;   // one pixel of four samples
+            const int s0 = 8 * (int)sizeof(T) * p0, s1 = 8 * (int)sizeof(T) * p1, s2 = 8 * (int)sizeof(T) * p2;
+            const Q* p = (const Q*)row + xfirst[x];
+            for (int t = 0; t < n; ++t) {
+                const Q q = p[t];
+                const float wt = w[t];
+                a0 = __builtin_fmaf(wt, (float)(T)(q >> s0), a0);
+                a1 = __builtin_fmaf(wt, (float)(T)(q >> s1), a1);
+                a2 = __builtin_fmaf(wt, (float)(T)(q >> s2), a2);
+            }
+        } else {
+            const int ns = (d.layout & 64) ? 4 : 3;   // samples per pixel
+            const T* p = (const T*)row + (size_t)ns * xfirst[x];
+            for (int t = 0; t < n; ++t) {
+                const float wt = w[t];
+                a0 = __builtin_fmaf(wt, (float)p[ns * t + p0], a0);
+                a1 = __builtin_fmaf(wt, (float)p[ns * t + p1], a1);
+                a2 = __builtin_fmaf(wt, (float)p[ns * t + p2], a2);
+            }
+        }
+        float* l = lds + (size_t)e * 3;
+        l[0] = a0; l[1] = a1; l[2] = a2;
+    }
+    barrier();
+
+    // vertical pass out of LDS, the matrix (YUV layouts) or the samples as they are (RGB layouts), three bytes per pixel
+    const bool yuv = d.layout & 128;
+    for (int e = tid; e < (r1 - r0) * cols; e += 256) {
+        const int rl = e / cols, xl = e - rl * cols, r = r0 + rl;
+        const int n = ycount[r];
+        const float* w = yw + (size_t)r * d.ys;
+        const float* col = lds + ((size_t)(yfirst[r] - ylo) * cols + xl) * 3;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        for (int t = 0; t < n; ++t) {
+            const float* q = col + (size_t)t * cols * 3;
+            const float wt = w[t];
+            a0 = __builtin_fmaf(wt, q[0], a0);
+            a1 = __builtin_fmaf(wt, q[1], a1);
+            a2 = __builtin_fmaf(wt, q[2], a2);
+        }
+        uint8_t* o = out + (((size_t)f * S + r) * S + c0 + xl) * 3;
+        if (yuv) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float c = __builtin_fmaf(mat.m[4 * k], a0, __builtin_fmaf(mat.m[4 * k + 1], a1, __builtin_fmaf(mat.m[4 * k + 2], a2, mat.m[4 * k + 3])));
+                o[k] = (uint8_t)nv12_byte(c);
+            }
+        } else {
+            o[0] = (uint8_t)nv12_byte(a0);
+            o[1] = (uint8_t)nv12_byte(a1);
+            o[2] = (uint8_t)nv12_byte(a2);
+        }
+    }
+}
+
 #ifndef VH_HOST_CHECK   // tools/yuv_host_check.hip takes the planner and the body above and no device code
 template <bool PLANAR, class T>
 __global__ void __launch_bounds__(256)
@@ -570,6 +749,30 @@ hipError_t launch_resize_yuy2(bool wide, const uint8_t* frames, const uint32_t* 
         hipLaunchKernelGGL((resize_packed422_kernel<uint16_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     else
         hipLaunchKernelGGL((resize_packed422_kernel<uint8_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    return hipGetLastError();
+}
+
+// packed 4:4:4: a body and a kernel of its own; the six kernels above keep their names and their code
+template <class T>
+__global__ void __launch_bounds__(256)
+resize_packed444_kernel(const uint8_t* __restrict__ frames, const uint32_t* __restrict__ plan, uint8_t* __restrict__ out, int S, int max_tiles,
+                        Nv12Matrix mat) {
+    __shared__ __attribute__((aligned(16))) float lds[kResizeLdsFloats];
+    resize_packed444_body<T>(frames, plan, out, S, max_tiles, mat, lds, (int)blockIdx.x, (int)threadIdx.x, [] { __syncthreads(); });
+}
+
+// wide: the 16-bit layouts (Y416 / AYUV64 and Y410 / V410, told apart per frame by the record's layout); a plan of resize_plan_build_bgra
+hipError_t launch_resize_bgra(bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles, const float* m12,
+                              uint8_t* out, hipStream_t s) {
+    if (!frames || !plan_dev || !out || !m12 || batch < 1 || S < 1 || max_tiles < 1 || (int64_t)batch * max_tiles > 0x7fffffffll)
+        return hipErrorInvalidValue;
+    Nv12Matrix mat;
+    memcpy(mat.m, m12, sizeof mat.m);
+    const dim3 grid((unsigned)(batch * max_tiles));
+    if (wide)
+        hipLaunchKernelGGL((resize_packed444_kernel<uint16_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
+    else
+        hipLaunchKernelGGL((resize_packed444_kernel<uint8_t>), grid, dim3(256), 0, s, frames, plan_dev, out, S, max_tiles, mat);
     return hipGetLastError();
 }
 #endif

@@ -159,6 +159,14 @@ const char* resize_plan_build_yuy2(const vh_frame_yuy2* desc, int batch, int S, 
                                    int sample_bytes, std::vector<uint32_t>* words, int* max_tiles);
 hipError_t launch_resize_yuy2(bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
                               const float* m12_host, uint8_t* out_u8, hipStream_t stream);
+// Packed 4:4:4 frames (the same file and record, a body of its own; contract: vithip.h, "Packed 4:4:4 frames"): BGR / BGRA / RGBA /
+// ARGB, YUV24 / VUYA / AYUV (sample_bytes 1), Y416 / AYUV64 and Y410 / V410 (sample_bytes 2).  resize_plan_build_bgra plans the planar
+// 4:4:4 frame of the de-interleaved samples (the same tables and bands) and puts the layout word into the record; base_mod8: the frames
+// address & 7 (0 for a host buffer).  launch_resize_bgra: one launch for the batch; wide: a plan built with sample_bytes 2.
+const char* resize_plan_build_bgra(const vh_frame_bgra* desc, int batch, int S, size_t nbytes, unsigned base_mod8, int sample_bytes,
+                                   std::vector<uint32_t>* words, int* max_tiles);
+hipError_t launch_resize_bgra(bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
+                              const float* m12_host, uint8_t* out_u8, hipStream_t stream);
 // patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
 // planes + the first row statistics' partial sums, no patch matrix in memory
 bool patch_fused_supported(int image, int patch, int channels, int dim);

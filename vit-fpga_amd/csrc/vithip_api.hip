@@ -1001,6 +1001,16 @@ hipError_t launch_packed422(const uint8_t* frames, const uint32_t* plan_dev, int
     return launch_resize_yuy2(WIDE, frames, plan_dev, batch, S, max_tiles, m12, out, stream);
 }
 
+template <int SAMPLE_BYTES>
+const char* plan_packed444(const void* desc, int batch, int, int S, size_t nbytes, uintptr_t base, int, std::vector<uint32_t>* words, int* max_tiles) {
+    return resize_plan_build_bgra((const vh_frame_bgra*)desc, batch, S, nbytes, (unsigned)(base & 7), SAMPLE_BYTES, words, max_tiles);
+}
+template <bool WIDE>
+hipError_t launch_packed444(const uint8_t* frames, const uint32_t* plan_dev, int batch, int, int S, int max_tiles, const float* m12, uint8_t* out,
+                            hipStream_t stream) {
+    return launch_resize_bgra(WIDE, frames, plan_dev, batch, S, max_tiles, m12, out, stream);
+}
+
 const char* plan_rgb(const void* desc, int batch, int channels, int S, size_t nbytes, uintptr_t base, int, std::vector<uint32_t>* words, int* max_tiles) {
     return resize_plan_build((const vh_frame*)desc, batch, channels, S, nbytes, (base & 3) == 0, words, max_tiles);
 }
@@ -1017,6 +1027,8 @@ const FrameFormat kFramesP016 = {"resize_p016", "P016", "resize_p016: null buffe
 const FrameFormat kFramesYUV16 = {"resize_yuv16", "planar 16-bit YUV", "resize_yuv16: null buffer", true, 1, plan_planar<2>, launch_yuv<true, true>};
 const FrameFormat kFramesYUY2 = {"resize_yuy2", "packed 4:2:2", "resize_yuy2: null buffer", true, 0, plan_packed422<1>, launch_packed422<false>};
 const FrameFormat kFramesY210 = {"resize_y210", "packed 16-bit 4:2:2", "resize_y210: null buffer", true, 1, plan_packed422<2>, launch_packed422<true>};
+const FrameFormat kFramesBGRA = {"resize_bgra", "packed 4:4:4", "resize_bgra: null buffer", true, 0, plan_packed444<1>, launch_packed444<false>};
+const FrameFormat kFramesY410 = {"resize_y410", "packed 16-bit 4:4:4", "resize_y410: null buffer", true, 1, plan_packed444<2>, launch_packed444<true>};
 
 // One resize in front of a forward: the frames in HBM and the descriptors + tables (c->rz_words) in pinned memory.
 struct FrameJob {
@@ -1753,6 +1765,20 @@ int vh_forward_device_frames_y210(vh_ctx* c, const uint8_t* frames_dev, size_t n
 int vh_forward_frames_y210(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch, float* logits_host) {
     return forward_frames_host(c, kFramesY210, frames_host, nbytes, desc, batch, logits_host);
 }
+// packed 4:4:4 frames: the plan of resize_plan_build_bgra; 8-bit layouts under the first colour state (RGB layouts read none), Y416 /
+// AYUV64 / Y410 / V410 under the second
+int vh_forward_device_frames_bgra(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_dev) {
+    return forward_frames_device(c, kFramesBGRA, frames_dev, nbytes, desc, batch, logits_dev);
+}
+int vh_forward_frames_bgra(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_host) {
+    return forward_frames_host(c, kFramesBGRA, frames_host, nbytes, desc, batch, logits_host);
+}
+int vh_forward_device_frames_y410(vh_ctx* c, const uint8_t* frames_dev, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_dev) {
+    return forward_frames_device(c, kFramesY410, frames_dev, nbytes, desc, batch, logits_dev);
+}
+int vh_forward_frames_y410(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch, float* logits_host) {
+    return forward_frames_host(c, kFramesY410, frames_host, nbytes, desc, batch, logits_host);
+}
 
 int vh_yuv_matrix(int standard, int full_range, float m[12]) {
     if (yuv_matrix(standard, full_range, m))
@@ -2064,6 +2090,12 @@ int vh_ring_submit_frames_yuy2(vh_ctx* c, const uint8_t* frames_host, size_t nby
 }
 int vh_ring_submit_frames_y210(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch) {
     return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesY210);
+}
+int vh_ring_submit_frames_bgra(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesBGRA);
+}
+int vh_ring_submit_frames_y410(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch) {
+    return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesY410);
 }
 
 int vh_ring_collect(vh_ctx* c, float* logits_host, int* batch) {
@@ -2484,6 +2516,14 @@ int vh_op_resize_yuy2(const uint8_t* frames, size_t nbytes, const vh_frame_yuy2*
 int vh_op_resize_y210(const uint8_t* frames, size_t nbytes, const vh_frame_yuy2* desc, int batch, int out_size, const float* m12,
                       int chroma_site, uint8_t* out, void* stream) {
     return op_resize(kFramesY210, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
+}
+int vh_op_resize_bgra(const uint8_t* frames, size_t nbytes, const vh_frame_bgra* desc, int batch, int out_size, const float* m12,
+                      int chroma_site, uint8_t* out, void* stream) {
+    return op_resize(kFramesBGRA, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
+}
+int vh_op_resize_y410(const uint8_t* frames, size_t nbytes, const vh_frame_bgra* desc, int batch, int out_size, const float* m12,
+                      int chroma_site, uint8_t* out, void* stream) {
+    return op_resize(kFramesY410, frames, nbytes, desc, batch, 3, out_size, m12, chroma_site, out, stream);
 }
 
 int vh_op_cast(const float* in, void* out16, int64_t n, int dtype, void* stream) {

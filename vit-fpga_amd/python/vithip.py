@@ -71,6 +71,26 @@ class FrameYUY2(C.Structure):
 
 
 L422_YUYV, L422_UYVY, L422_YVYU, L422_VYUY, L422_V210 = range(5)   # vh_frame_yuy2.layout (VH_422_*); V210: the 16-bit entry points only
+class FrameBGRA(C.Structure):
+    """vh_frame_bgra: one packed 4:4:4 frame (one plane of pixels whose samples lie as `layout`, L444_*, says) inside the buffer of a
+    call, and the box (in pixels) to resample to image_size^2.  40 bytes."""
+    _fields_ = [("offset", C.c_uint64), ("height", C.c_int32), ("width", C.c_int32), ("row_stride", C.c_int32),
+                ("layout", C.c_int32), ("box", C.c_float * 4)]
+
+
+def layout_444(p0, p1, p2, four, yuv):
+    """VH_444: p_k = the index within the pixel of the sample that becomes output component k; four: 4 samples per pixel, else 3;
+    yuv: the samples pass the colour matrix."""
+    return p0 | p1 << 2 | p2 << 4 | (64 if four else 0) | (128 if yuv else 0)
+
+
+# vh_frame_bgra.layout (VH_444_*), memory order in the name
+L444_RGB, L444_BGR = layout_444(0, 1, 2, 0, 0), layout_444(2, 1, 0, 0, 0)
+L444_RGBA, L444_BGRA, L444_ARGB, L444_ABGR = (layout_444(0, 1, 2, 1, 0), layout_444(2, 1, 0, 1, 0), layout_444(1, 2, 3, 1, 0),
+                                              layout_444(3, 2, 1, 1, 0))
+L444_YUV24, L444_VUYA, L444_AYUV = layout_444(0, 1, 2, 0, 1), layout_444(2, 1, 0, 1, 1), layout_444(1, 2, 3, 1, 1)
+L444_Y416, L444_AYUV64 = layout_444(1, 0, 2, 1, 1), layout_444(1, 2, 3, 1, 1)     # 16-bit words: the _y410 entry points
+L444_Y410, L444_V410 = layout_444(1, 0, 2, 1, 1) | 256, layout_444(1, 0, 2, 1, 1) | 768   # one 32-bit word of three 10-bit codes
 CHROMA_CENTER, CHROMA_LEFT = 0, 1          # vh_set_frame_colour / vh_op_resize_nv12: JPEG / MPEG-1 siting, MPEG-2 / H.264 / HEVC siting
 YUV_BT601, YUV_BT709, YUV_BT2020 = 0, 1, 2  # vh_yuv_matrix
 
@@ -128,6 +148,10 @@ SYMBOLS = {
     "vh_forward_device_frames_yuy2": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_frames_y210": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_device_frames_y210": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_frames_bgra": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_bgra": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_frames_y410": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
+    "vh_forward_device_frames_y410": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_fill_input_seeded": (_i, [_vp, _u64, _i, _vp]),
     "vh_last_forward_us": (_i, [_vp, C.POINTER(_i64)]),
     "vh_last_kernel_ms": (_i, [_vp, C.POINTER(C.c_double)]),
@@ -162,6 +186,8 @@ SYMBOLS = {
     "vh_ring_submit_frames_yuv16": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_ring_submit_frames_yuy2": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_ring_submit_frames_y210": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_bgra": (_i, [_vp, _vp, _sz, _vp, _i]),
+    "vh_ring_submit_frames_y410": (_i, [_vp, _vp, _sz, _vp, _i]),
     "vh_set_graph": (_i, [_vp, _i]),
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
@@ -198,6 +224,8 @@ SYMBOLS = {
     "vh_op_resize_yuv16": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_yuy2": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_y210": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "vh_op_resize_bgra": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "vh_op_resize_y410": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
@@ -554,6 +582,63 @@ def pack_frames_yuy2(planes, layouts=L422_YUYV, boxes=None):
             rows = _sample_bytes(m)
         else:
             raise ValueError(f"pack_frames_yuy2: frame {i}: layout {lay} is none of L422_*")
+        d = desc[i]
+        d.offset, d.height, d.width, d.row_stride, d.layout = off, h, w, rows.size // h, lay
+        d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
+        parts.append(rows)
+        off += rows.size
+    return np.concatenate(parts), desc
+
+
+def word10_rows(c0, c1, c2, layout):
+    """Three [H, W] arrays of 10-bit codes (Y, U, V) -> the Y410 / V410 rows as [H, W] uint32 words: component k at bits
+    10 p_k .. 10 p_k + 9 (V410: two bits higher), the other bits zero."""
+    comps = [np.asarray(p).astype(np.uint32) for p in (c0, c1, c2)]
+    if max(int(p.max()) for p in comps) > 1023:
+        raise ValueError("word10_rows: a code is above 1023")
+    lsb = 2 if layout & 512 else 0
+    word = np.zeros(comps[0].shape, np.uint32)
+    for k, p in enumerate(comps):
+        word |= p << np.uint32(10 * ((layout >> (2 * k)) & 3) + lsb)
+    return word
+
+
+def pack_frames_bgra(planes_or_pixels, layouts=L444_BGRA, boxes=None):
+    """A list of frames, each an [H, W, 3] array or a triple of [H, W] planes whose components are in OUTPUT order (R, G, B, or
+    Y, U, V for a layout with the yuv bit), interleaved into packed 4:4:4 frames -> (one uint8 buffer, the (FrameBGRA * n)
+    descriptors).  layouts: one L444_* for all frames or one per frame.  uint8 samples give the 8-bit layouts (forward_frames_bgra);
+    uint16 samples give four 16-bit words per pixel, or, with L444_Y410 / L444_V410, one 32-bit word of the 10-bit codes in the
+    arrays (forward_frames_y410).  The 4th sample is 0xff.. .  Rows are unpadded, frames back to back: 16-bit frames are 8-byte and
+    10-bit frames 4-byte aligned by construction."""
+    frames = [np.stack([np.asarray(p) for p in t], axis=-1) if isinstance(t, (tuple, list)) else np.asarray(t) for t in planes_or_pixels]
+    if isinstance(layouts, int):
+        layouts = [layouts] * len(frames)
+    if boxes is None:
+        boxes = [None] * len(frames)
+    if not frames or len(boxes) != len(frames) or len(layouts) != len(frames):
+        raise ValueError("pack_frames_bgra: one layout and one box (or None) per frame, at least one frame")
+    dtype = frames[0].dtype
+    if dtype not in (np.uint8, np.uint16):
+        raise TypeError("pack_frames_bgra: samples must be uint8 or uint16")
+    desc = (FrameBGRA * len(frames))()
+    parts, off = [], 0
+    for i, (px, lay, box) in enumerate(zip(frames, layouts, boxes)):
+        if px.dtype != dtype or px.ndim != 3 or px.shape[2] != 3 or px.size == 0:
+            raise TypeError(f"pack_frames_bgra: frame {i} is not [H, W, 3] {np.dtype(dtype).name} samples (or three [H, W] planes)")
+        h, w = px.shape[:2]
+        pos = [(lay >> (2 * k)) & 3 for k in range(3)]
+        if lay & 256:
+            if dtype != np.uint16 or lay not in (L444_Y410, L444_V410):
+                raise ValueError(f"pack_frames_bgra: frame {i}: a 10-bit layout is L444_Y410 or L444_V410 and takes uint16 codes")
+            rows = _sample_bytes(word10_rows(px[..., 0], px[..., 1], px[..., 2], lay))
+        else:
+            ns = 4 if lay & 64 else 3
+            if lay < 0 or lay > 255 or max(pos) >= ns:
+                raise ValueError(f"pack_frames_bgra: frame {i}: layout {lay} is no VH_444 word")
+            m = np.full((h, w, ns), np.iinfo(dtype).max, dtype)
+            for k in range(3):
+                m[:, :, pos[k]] = px[..., k]
+            rows = _sample_bytes(m)
         d = desc[i]
         d.offset, d.height, d.width, d.row_stride, d.layout = off, h, w, rows.size // h, lay
         d.box[:] = (0.0, 0.0, float(w), float(h)) if box is None else tuple(float(b) for b in box)
@@ -955,6 +1040,31 @@ class VitContext:
     def forward_device_frames_y210(self, frames_ptr, nbytes, desc, out_ptr):
         self._forward_frames_device(lib().vh_forward_device_frames_y210, frames_ptr, nbytes, desc, out_ptr)
 
+    # ---- packed 4:4:4 frames (BGR / BGRA / RGBA / ARGB, YUV24 / VUYA / AYUV; Y416 / AYUV64 / Y410 / V410) ----
+    def forward_frames_bgra(self, pixels, layouts=L444_BGRA, boxes=None):
+        """pixels: a list of [H, W, 3] uint8 frames (or plane triples) in output order, interleaved here (pack_frames_bgra) as
+        `layouts` say.  Returns the bits forward_u8 gives for op_resize_bgra's output under set_frame_colour's matrix."""
+        buf, desc = pack_frames_bgra(pixels, layouts, boxes)
+        return self.forward_frames_bgra_packed(buf, desc)
+
+    def forward_frames_bgra_packed(self, buf, desc):
+        return self._forward_frames_host(lib().vh_forward_frames_bgra, buf, desc)
+
+    def forward_device_frames_bgra(self, frames_ptr, nbytes, desc, out_ptr):
+        self._forward_frames_device(lib().vh_forward_device_frames_bgra, frames_ptr, nbytes, desc, out_ptr)
+
+    def forward_frames_y410(self, pixels, layouts=L444_Y410, boxes=None):
+        """pixels: uint16 frames as above: 16-bit words, or 10-bit codes with L444_Y410 / L444_V410.  Returns the bits forward_u8
+        gives for op_resize_y410's output under set_frame_colour16's matrix."""
+        buf, desc = pack_frames_bgra(pixels, layouts, boxes)
+        return self.forward_frames_y410_packed(buf, desc)
+
+    def forward_frames_y410_packed(self, buf, desc):
+        return self._forward_frames_host(lib().vh_forward_frames_y410, buf, desc)
+
+    def forward_device_frames_y410(self, frames_ptr, nbytes, desc, out_ptr):
+        self._forward_frames_device(lib().vh_forward_device_frames_y410, frames_ptr, nbytes, desc, out_ptr)
+
     def fill_input_seeded(self, seed, batch, in_ptr):
         _check(lib().vh_fill_input_seeded(self.h, seed, batch, in_ptr), self.h)
 
@@ -1073,6 +1183,24 @@ class VitContext:
     def ring_submit_frames_y210_packed(self, buf, nbytes, desc):
         """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of frames that desc describes."""
         self._ring_submit_frames(lib().vh_ring_submit_frames_y210, buf, nbytes, desc)
+
+    def ring_submit_frames_bgra(self, pixels, layouts=L444_BGRA, boxes=None):
+        """8-bit packed 4:4:4 frames into the next slot of a frames ring; every kind of frames submit may alternate."""
+        buf, desc = pack_frames_bgra(pixels, layouts, boxes)
+        self.ring_submit_frames_bgra_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_bgra_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of frames that desc describes."""
+        self._ring_submit_frames(lib().vh_ring_submit_frames_bgra, buf, nbytes, desc)
+
+    def ring_submit_frames_y410(self, pixels, layouts=L444_Y410, boxes=None):
+        """Y416 / AYUV64 / Y410 / V410 frames into the next slot of a frames ring; every kind of frames submit may alternate."""
+        buf, desc = pack_frames_bgra(pixels, layouts, boxes)
+        self.ring_submit_frames_y410_packed(buf, buf.nbytes, desc)
+
+    def ring_submit_frames_y410_packed(self, buf, nbytes, desc):
+        """buf None: the slot's pinned buffer (ring_input_frames) already holds the nbytes of frames that desc describes."""
+        self._ring_submit_frames(lib().vh_ring_submit_frames_y410, buf, nbytes, desc)
 
     def ring_free_slots(self):
         n = C.c_int(0)
@@ -1451,6 +1579,18 @@ def op_resize_yuy2(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
 def op_resize_y210(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
     """op_resize_yuv16 for Y210 / Y216 / v210 frames: frames_ptr 2-byte aligned, offsets and strides even (v210: multiples of 4)."""
     _op_resize_colour("op_resize_y210", lib().vh_op_resize_y210, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
+
+
+def op_resize_bgra(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """op_resize_yuv for 8-bit packed 4:4:4 frames: (FrameBGRA * n) descriptors, frames_ptr of any alignment.  RGB layouts ignore
+    m, and every layout ignores chroma_site."""
+    _op_resize_colour("op_resize_bgra", lib().vh_op_resize_bgra, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
+
+
+def op_resize_y410(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
+    """op_resize_yuv16 for Y416 / AYUV64 / Y410 / V410 frames: frames_ptr 2-byte aligned, offsets and strides even (Y410 / V410:
+    multiples of 4)."""
+    _op_resize_colour("op_resize_y410", lib().vh_op_resize_y410, frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr)
 
 
 def op_resize_nv12(frames_ptr, nbytes, desc, out_size, m, chroma_site, out_ptr):
