@@ -724,6 +724,34 @@ int vh_op_gemm_ex(const void* a16_dev, const void* w16_dev, const float* bias_de
                   int64_t M, int N, int K, int epilogue, const float* aux_dev, int aux_i,
                   const float* stats_dev, void* out16_dev, float* partials_dev,
                   int dtype, int variant, void* stream);
+/* Test and measurement taps: the forms of the GEMM that only a whole forward reaches otherwise (tests/gemm_exact.py).
+ * vh_op_gemm_layout is vh_op_gemm_ex, vh_op_gemm_fp8_layout is vh_op_gemm_fp8_ex (which here takes the epilogues of vh_op_gemm_fp8 as
+ * well: c_dev / stats_dev / out16 / partials may be NULL where the epilogue does not use them), plus
+ *   out_tiled != 0   activation epilogues (*_GELU, *_QGELU): the result in the 16-row-blocked layout of the MLP hidden activation,
+ *                    [M / 16][N / 8][16 rows][8 values] (e4m3 results: [M / 16][N / 16][16 rows][16 B]);
+ *                    VH_EPI_LNFOLD and 16-bit VH_EPI_BIAS: the result head-major, [N / 64][M][64] (the q|k|v projection)
+ *   ab_tiled != 0    A and W are both read from the 16-row-blocked layout ([rows / 16][K / 8][16][8]; e4m3: [rows / 16][K / 16][16][16 B]):
+ *                    VH_EPI_RESID_SPLIT, and VH_EPI_BIAS with 16-bit operands
+ *   tile_begin, tile_count   launch only tiles [tile_begin, tile_begin + tile_count) of the 256 x 256 tiles in n-fastest order,
+ *                    tile t = (t / tiles_n, t % tiles_n), tiles_n = ceil(N / 256); tile_count == 0 (with tile_begin == 0) = all tiles
+ * With all four 0 they are the calls they extend.  VH_ERR_INVALID, with a message and before a device is touched, for anything
+ * the launchers refuse: a tiled flag needs variant 6, M and N multiples of 256, at least two K-tiles (four with an LN-fold epilogue,
+ * except the e4m3-operand activation forms; a K-tile is 64 16-bit or 128 e4m3 elements), one of the epilogues named above, and
+ * excludes the other flag and a tile range; a tile range needs variant 5 or 7, tile_begin >= 0, tile_count >= 0,
+ * tile_begin + tile_count <= tiles, and tile_count > 0 where tile_begin != 0. */
+int vh_op_gemm_layout(const void* a16_dev, const void* w16_dev, const float* bias_dev, void* out_dev,
+                      int64_t M, int N, int K, int epilogue, const float* aux_dev, int aux_i,
+                      const float* stats_dev, void* out16_dev, float* partials_dev, int dtype, int variant,
+                      int out_tiled, int ab_tiled, int tile_begin, int tile_count, void* stream);
+int vh_op_gemm_fp8_layout(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M,
+                          int N, int K, int epilogue, const float* c_dev, const float* stats_dev, void* out16,
+                          float* partials, int variant, int out_tiled, int ab_tiled, int tile_begin, int tile_count,
+                          void* stream);
+/* Test tap: the kernels that put a weight matrix into the 16-row-blocked layout ab_tiled reads, on their own.
+ * dtype VH_DTYPE_BF16 / VH_DTYPE_FP16: in = fp32 [rows, cols] -> out = `dtype` [rows / 16][cols / 8][16][8] (round to nearest even);
+ * dtype VH_DTYPE_FP8: in = bytes [rows, cols] -> out = the same bytes [rows / 16][cols / 16][16][16].
+ * rows % 16 == 0 and cols % 8 == 0 (bytes: cols % 16 == 0), else VH_ERR_INVALID. */
+int vh_op_tile_rows(const void* in_dev, int rows, int cols, void* out_dev, int dtype, void* stream);
 /* row statistics helpers of the folded LayerNorm:
  *   vh_op_rowstats_cast: x fp32 [rows, dim] -> x16 [rows, dim] (plain cast) and stats [rows][2] = (mean, rstd)
  *   vh_op_finalize_stats: partials [nblk][rows][2] (sum, sumsq over 64-column blocks) -> stats [rows][2] */

@@ -1,0 +1,276 @@
+"""CPU self-test of tests/gemm_exact.py: the guard of the designs and the proof that the assertions of test_gpu_gemm_exact.py can
+fail.  A numpy emulation of the epilogues and layouts passes every assertion at every shape the GPU file uses; nine mutants of it
+-- a K-tile dropped, a K-tile used twice, the neighbouring row's (mean, rstd), c and d swapped, the chunks of a 64-column group
+left in the staging swizzle's order, a 16-row block index off by one in the tiled store, a head-major row stride other than M, a
+residual tile applied twice, a residual tile skipped -- fail the same assertions.
+
+Which (mutant, epilogue, layout) triples can fail is decided by the mathematics (gemm_exact.mutant_applies), not by what the
+emulation happens to give: the statistics mutants need an LN-fold epilogue, the swizzle needs a staged store (the tiled store has
+none), the block and stride mutants need their layout, and applying a tile twice is the identity for an epilogue that does not
+read its output.  Those triples are asserted to give the SAME bits; every other one must fail.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import gemm_exact as X
+import vithip
+
+E, BF16, FP16, FP8 = X.E, X.BF16, X.FP16, X.FP8
+DT = [BF16, FP16]
+_CASES = {}
+
+
+def case_of(M, N, K, f8):
+    """Generated once per shape and shared, unchanged, by the tests."""
+    key = (M, N, K, f8)
+    if key not in _CASES:
+        if (M * N > 1 << 22) or len(_CASES) > 12:
+            _CASES.clear()
+        _CASES[key] = X.Case(M, N, K, f8)
+    return _CASES[key]
+
+
+def epilogues(f8):
+    return X.EPI_E4M3_OPERANDS if f8 else X.EPI_16BIT_OPERANDS
+
+
+def layouts_of(epi, f8, name):
+    """The layouts the GPU file launches this epilogue in at this shape."""
+    if name == "S1r":
+        return ["row"]
+    out = [] if name == "S2" else ["row"]
+    if epi in X.ACT:
+        out.append("tiled")
+    if epi == E["LNFOLD"] or (epi == E["BIAS"] and not f8):
+        out.append("hm")
+    return out
+
+
+# the many-tile shape: one epilogue per layout family (host time), and each mutant on the family it belongs to
+S2_EPIS = {False: [E["LNFOLD_GELU"], E["LNFOLD"], E["BIAS"]], True: [E["LNFOLD_GELU"]]}
+S2_FAMILY = {E["LNFOLD_GELU"]: ("tiled", ("block_off_by_one", "ktile_dropped", "neighbour_stats")),
+             E["LNFOLD"]: ("hm", ("hm_stride", "c_d_swapped", "swizzle_kept")),
+             E["BIAS"]: ("row", ("ktile_twice", "resid_skipped", "resid_twice"))}
+
+
+def run_mutants(case, epi, dt, before, layout, tiles=None, mutants=X.MUTANTS):
+    ko, _ = X.out_kind(epi, dt, case.f8)
+    R = case.out_rows(epi)
+
+    def logical(res):
+        res = dict(res)
+        res["out"] = X.from_layout(res["out"], layout, ko, R, case.N)
+        return res
+
+    good = X.emulate(case, epi, dt, before, tiles, layout)
+    what = f"emulation {layout}"
+    X.check(case, epi, dt, before, logical(good), tiles, what)
+    if layout != "row":       # the stored buffer is the packed expectation, and nothing else was written
+        exp = X.expected(case, epi, dt, before, tiles)
+        if "out" in exp:
+            assert np.array_equal(np.asarray(good["out"]).reshape(-1), X.to_layout(exp["out"], layout, ko).reshape(-1))
+    for mutant in mutants:
+        mut = X.emulate(case, epi, dt, before, tiles, layout, mutant)
+        if not X.mutant_applies(mutant, epi, layout):
+            for k in good:
+                assert np.array_equal(good[k], mut[k]), (mutant, X.ENAME[epi], layout, k)     # the identity (module docstring)
+            continue
+        with pytest.raises(AssertionError):
+            X.check(case, epi, dt, before, logical(mut), tiles, f"{mutant} {layout}")
+
+
+@pytest.mark.parametrize("f8", [False, True], ids=["16bit", "e4m3"])
+@pytest.mark.parametrize("name", ["S0", "S1", "S1r"])
+def test_emulation_passes_and_every_mutant_fails(name, f8):
+    for epi in epilogues(f8):
+        case = case_of(*X.shape(name, f8, epi), f8)
+        for dt in ([BF16] if f8 else DT):
+            before = X.initial(case, epi, dt)
+            for layout in layouts_of(epi, f8, name):
+                run_mutants(case, epi, dt, before, layout)
+
+
+@pytest.mark.parametrize("f8", [False, True], ids=["16bit", "e4m3"])
+def test_emulation_and_mutants_on_tile_ranges(f8):
+    # S1r as 3 x 4 tiles: the first five tiles, the rest, the ragged last tile row alone
+    for epi in (E["BIAS"], E["RESID_LN"], E["RESID_SPLIT"]):
+        M, N, K = X.shape("S1r", f8, epi, four_tile_columns=True)
+        if N % 256:
+            N = 1024 - 252
+        case = case_of(M, N, K, f8)
+        assert (case.tiles_m, case.tiles_n) == (3, 4)
+        before = X.initial(case, epi, BF16)
+        for tiles in (range(0, 5), range(5, 12), range(8, 12)):
+            run_mutants(case, epi, BF16, before, "row", tiles)
+        # two launches that cover every tile once give the full launch
+        first = X.emulate(case, epi, BF16, before, range(0, 5))
+        second = X.emulate(case, epi, BF16, first, range(5, 12))
+        full = X.emulate(case, epi, BF16, before)
+        for k in full:
+            assert np.array_equal(second[k], full[k]), (X.ENAME[epi], k)
+
+
+@pytest.mark.parametrize("f8", [False, True], ids=["16bit", "e4m3"])
+def test_emulation_and_mutants_at_the_many_tile_shape(f8):
+    for epi in S2_EPIS[f8]:
+        case = case_of(*X.shape("S2", f8, epi), f8)
+        assert case.ntiles >= 2.5 * 256 and case.tiles_n == 7
+        layout, mutants = S2_FAMILY[epi]
+        run_mutants(case, epi, BF16, X.initial(case, epi, BF16), layout, mutants=mutants[:1] if f8 else mutants)
+
+
+@pytest.mark.parametrize("f8", [False, True], ids=["16bit", "e4m3"])
+@pytest.mark.parametrize("name", ["S0", "S1", "S1r", "S2"])
+def test_designs_hold_what_they_promise(name, f8):
+    """The caps that keep a test from hiding a failure."""
+    for epi in (S2_EPIS[f8] if name == "S2" else epilogues(f8)):
+        M, N, K = X.shape(name, f8, epi)
+        case = case_of(M, N, K, f8)
+        kw = X.ktile(f8)
+        # every row has one or two non-zeros from {+-1, +-2} in every K-tile, at columns that differ between neighbouring rows
+        nz = (case.a != 0).reshape(M, case.nk, kw)
+        cnt = nz.sum(2)
+        assert cnt.min() >= 1 and cnt.max() <= 2 and set(np.unique(case.a)) == {-2.0, -1.0, 0.0, 1.0, 2.0}
+        assert (nz[1:] != nz[:-1]).any(axis=(1, 2)).mean() > 0.95
+        assert np.abs(case.w).max() == 3 and not np.array_equal(case.w[:min(N, K), :min(N, K)], case.w[:min(N, K), :min(N, K)].T)
+        a8, w8 = case.operand_bits(BF16)
+        for t in ([FP8] if f8 else DT):      # operands exact in their type
+            assert np.array_equal(X.decode(X.encode(case.a, t), t), case.a) and np.array_equal(X.decode(X.encode(case.w, t), t), case.w)
+        assert np.array_equal(case.acc.astype(np.float64), (case.a.astype(np.float64) @ case.w.astype(np.float64).T) * case.ws)
+        assert len(set(case.mean[:16])) > 1 and set(case.rstd) == {0.5, 1.0, 2.0}
+        for dt in ([BF16] if f8 or name == "S2" else DT):
+            before = X.initial(case, epi, dt)
+            v = X.pre_value(case, epi, dt, before, np.float32 if name == "S2" else np.float64)
+            if M * N <= 1 << 22:
+                assert np.array_equal(v, X.pre_value(case, epi, dt, before, np.float32).astype(np.float64))     # exact in fp32
+            ko, k16 = X.out_kind(epi, dt, f8)
+            if epi in X.ACT:
+                assert np.abs(v).max() < 448       # no saturation of an e4m3 result either
+                assert np.mean(np.abs(v) < 4.5) > 0.05   # enough pre-activations inside the erf fit's interval
+                continue
+            v32 = v.astype(np.float32)
+            assert np.array_equal(v32.astype(np.float64), v)
+            if epi in X.SPLIT:
+                hi, lo = X.split_planes(v32, dt, f8)
+                assert np.array_equal(X.join_planes(hi, lo, dt, f8), v32), "the updated x must be exact in the pair"
+                assert np.mean(lo != 0) > 0.5, "most lo elements must carry something"
+                if epi == E["RESID_SPLIT"]:
+                    assert np.mean(before["out16"] != 0) > 0.5
+                    x_in = X.join_planes(before["out"], before["out16"], dt, f8)
+                    assert np.array_equal(x_in, case.x0 + np.float32(X.LO_FRAC[FP8 if f8 else dt]))
+                assert np.abs(v).max() < (448 if f8 else 256)
+            elif ko != "f32":
+                for t in DT:                   # exact in BOTH 16-bit types: at most 8 significant bits
+                    assert np.array_equal(vithip.from16(vithip.to16(v32, t), t), v32), (X.ENAME[epi], X.NAME[t])
+                assert np.abs(v).max() <= 256
+            if epi == E["RESID_LN"]:
+                if not f8:
+                    for t in DT:
+                        assert np.array_equal(vithip.from16(vithip.to16(v32, t), t), v32)
+                assert 64 * (v * v).max() * (4 if f8 else 1) < 2 ** 24
+                assert X.expected(case, epi, dt, before)["sumsq_exact"]
+            if epi in X.PATCHES:
+                assert 0 < case.np_img < 128 and M % case.np_img == 0
+
+
+def test_expected_values_in_float32_and_float64_agree():
+    for f8 in (False, True):
+        for epi in epilogues(f8):
+            case = case_of(*X.shape("S1", f8, epi), f8)
+            before = X.initial(case, epi, BF16)
+            e64, e32 = X.expected(case, epi, BF16, before), X.expected(case, epi, BF16, before, ft=np.float32)
+            for k in e64:
+                if k in ("sumsq_exact", "mask"):
+                    continue
+                assert np.array_equal(np.asarray(e64[k], dtype=np.float64), np.asarray(e32[k], dtype=np.float64), equal_nan=True), (X.ENAME[epi], k)
+
+
+def test_fast_e4m3_encoder_is_the_binding_s():
+    r = np.random.default_rng(3)
+    tab = vithip.e4m3_table()
+    fin = tab[np.isfinite(tab)].astype(np.float64)
+    mid = (np.sort(fin)[1:] + np.sort(fin)[:-1]) / 2                 # every tie
+    x = np.concatenate([fin, mid, mid * (1 + 1e-6), mid * (1 - 1e-6), r.standard_normal(200000) * 40, r.standard_normal(50000) * 0.01,
+                        [0.0, -0.0, 447.9, 448.0, 464.0, 1e9, -1e9, 2.0 ** -10, 2.0 ** -11, 3 * 2.0 ** -11]]).astype(np.float32)
+    assert np.array_equal(X.to_e4m3(x), vithip.to_e4m3(x))
+    for dt in DT:
+        assert np.array_equal(X.to_lo8(x / 64, dt), vithip.to_lo8(x / 64, dt))
+
+
+def test_layout_helpers_against_index_formulas():
+    r = np.random.default_rng(11)
+    for rows, dim, chunk, dtype in ((256, 256, 8, np.uint16), (512, 448, 8, np.uint16), (768, 896, 16, np.uint8), (48, 200, 8, np.uint16),
+                                    (48, 208, 16, np.uint8), (16, 8, 8, np.uint16), (16, 16, 16, np.uint8)):
+        a = r.integers(0, 251, size=(rows, dim)).astype(dtype)
+        t = vithip.pack_tiled(a, chunk).reshape(-1)
+        # element (m, k) at ((m / 16) * (dim / chunk) + k / chunk) * 16 * chunk + (m % 16) * chunk + k % chunk
+        want = np.empty(rows * dim, dtype=dtype)
+        for m in range(rows):
+            k = np.arange(dim)
+            want[((m // 16) * (dim // chunk) + k // chunk) * 16 * chunk + (m % 16) * chunk + k % chunk] = a[m]
+        assert np.array_equal(t, want)
+        assert np.array_equal(vithip.unpack_tiled(t, rows, dim, chunk), a)
+        assert np.array_equal(vithip.pack_tiled(vithip.unpack_tiled(t, rows, dim, chunk), chunk).reshape(-1), t)
+    for M, N in ((256, 256), (512, 768), (256, 1792)):
+        a = r.integers(0, 65536, size=(M, N)).astype(np.uint16)
+        hm = X.to_layout(a, "hm", BF16).reshape(-1)
+        want = np.empty(M * N, dtype=np.uint16)
+        for m in range(0, M, 37):
+            n = np.arange(N)
+            want[((n // 64) * M + m) * 64 + n % 64] = a[m]
+            assert np.array_equal(hm[((n // 64) * M + m) * 64 + n % 64], a[m])
+        assert np.array_equal(X.from_layout(hm, "hm", BF16, M, N), a)
+        if N % 192 == 0:     # the attention tap's packer: [3][heads][rows][64], exact row count
+            assert np.array_equal(vithip.pack_head_major(a, N // 192, M).reshape(-1), hm)
+            assert np.array_equal(vithip.pack_head_major(a, N // 192, M + 16, fill=7)[:, :, M:], np.full((3, N // 192, 16, 64), 7, np.uint16))
+
+
+def test_assertion_helpers_name_the_place():
+    case = case_of(*X.shape("S1", False, E["BIAS"]), False)
+    before = X.initial(case, E["BIAS"], FP16)
+    good = X.emulate(case, E["BIAS"], FP16, before)
+    bad = {k: v.copy() for k, v in good.items()}
+    bad["out"][300, 520] ^= 1
+    with pytest.raises(AssertionError, match=r"tile 5 = \(1, 2\), 16-row block 18, 8-column chunk 65, row 300, column 520"):
+        X.check(case, E["BIAS"], FP16, before, bad)
+    # the tiled store's off-by-one block is named by its first element: row 0 of 16-row block 0 holds another block's values
+    epi = E["LNFOLD_GELU"]
+    before = X.initial(case, epi, FP16)
+    mut = X.emulate(case, epi, FP16, before, layout="tiled", mutant="block_off_by_one")
+    mut["out"] = X.from_layout(mut["out"], "tiled", FP16, case.M, case.N)
+    with pytest.raises(AssertionError, match=r"activations outside the bound; worst at tile \d+ = \(\d, \d\), 16-row block \d+, 8-column chunk \d+, row"):
+        X.check(case, epi, FP16, before, mut)
+    epi = E["RESID_SPLIT"]
+    before = X.initial(case, epi, BF16)
+    good = X.emulate(case, epi, BF16, before)
+    bad = {k: v.copy() for k, v in good.items()}
+    bad["partials"][7, 33, 0] += 1
+    with pytest.raises(AssertionError, match=r"row sums differ; first at 64-column block 7 \(tile column 1\), 16-row block 2, row 33"):
+        X.check(case, epi, BF16, before, bad)
+    bad = {k: v.copy() for k, v in good.items()}
+    s = bad["partials"][2, 5, 1]
+    bad["partials"][2, 5, 1] = s * np.float32(1 + 70 * 2.0 ** -24)          # just beyond the derived bound ...
+    with pytest.raises(AssertionError, match=r"sums of squares outside the bound; first at 64-column block 2 "):
+        X.check(case, epi, BF16, before, bad)
+    bad["partials"][2, 5, 1] = np.float32(X.expected(case, epi, BF16, before)["sumsq64"][2, 5] * (1 + 55 * 2.0 ** -24))   # ... and inside it
+    X.check(case, epi, BF16, before, bad)
+    # the activation bound: half a unit in the last place passes, a whole one does not
+    pre = np.full((1, 64), 3.0)
+    mask = np.ones((1, 64), dtype=bool)
+    ref = X.act64(pre, E["BIAS_GELU"])
+    bits = vithip.to16(ref.astype(np.float32), FP16)
+    canary = np.full((1, 64), X.CANARY16, np.uint16)
+    X.assert_activation(bits, canary, pre, mask, E["BIAS_GELU"], FP16)
+    with pytest.raises(AssertionError):
+        X.assert_activation(bits + 1, canary, pre, mask, E["BIAS_GELU"], FP16)
+
+
+def test_activation_constants_are_those_of_the_activation_sweeps():
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_clip.py")).read()
+    for line in ("ERF_ABS = {FP16: 7.7e-6, BF16: 3.4e-5, FP8: 5.7e-4}", "MANT = {FP16: 10, BF16: 7, FP8: 3}", "MIN_EXP = {FP16: -14, BF16: -126, FP8: -6}"):
+        assert line in text, line
+    assert re.search(r"limit = np\.maximum\(ERF_ABS\[dt\], 0\.25 \* u\)", text) and "fn_err <= limit * 1.0001" in text
+    assert X.ERF_ABS == {FP16: 7.7e-6, BF16: 3.4e-5, FP8: 5.7e-4} and X.MANT == {FP16: 10, BF16: 7, FP8: 3} and X.MIN_EXP == {FP16: -14, BF16: -126, FP8: -6}

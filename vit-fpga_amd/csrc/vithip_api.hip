@@ -2321,6 +2321,84 @@ int vh_op_gemm_ex(const void* a, const void* w, const float* bias, void* out, in
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
+// ---- test taps: the GEMM's tiled / head-major layouts and tile ranges (GemmArgs::out_tiled, ab_tiled, tile_begin, tile_count) ----
+// What launch_pp (kernels_gemm5.hip) accepts, checked here with a reason and before a device is touched.  `tag` names the tap.
+static int gemm_layout_check(const char* tag, bool f8, int64_t M, int N, int K, int epi, int variant, int out_tiled, int ab_tiled,
+                             int tile_begin, int tile_count) {
+    const bool act = epi == VH_EPI_BIAS_GELU || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_BIAS_QGELU || epi == VH_EPI_LNFOLD_QGELU;
+    const bool fold = epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU;
+    if (out_tiled || ab_tiled) {
+        if (out_tiled && ab_tiled) return fail(nullptr, VH_ERR_INVALID, "%s: out_tiled and ab_tiled exclude each other", tag);
+        if (variant != 6) return fail(nullptr, VH_ERR_INVALID, "%s: the tiled layouts exist in the persistent form only (variant 6)", tag);
+        if (tile_begin || tile_count) return fail(nullptr, VH_ERR_INVALID, "%s: a tile range excludes the tiled layouts", tag);
+        if (M % 256 || N % 256) return fail(nullptr, VH_ERR_INVALID, "%s: the tiled layouts need M %% 256 == 0 and N %% 256 == 0", tag);
+        // K-tiles the persistent form demands: four where the LN-fold constants travel through LDS (every LN-fold epilogue
+        // but the e4m3-operand activation forms), two otherwise
+        const int nk = K / (f8 ? 128 : 64), need = fold && !(f8 && act) ? 4 : 2;
+        if (nk < need) return fail(nullptr, VH_ERR_INVALID, "%s: the tiled layouts need at least %d K-tiles with this epilogue", tag, need);
+        if (out_tiled && !(act || epi == VH_EPI_LNFOLD || (!f8 && epi == VH_EPI_BIAS)))
+            return fail(nullptr, VH_ERR_INVALID, "%s: out_tiled goes with the activation epilogues (tiled) or LNFOLD / 16-bit BIAS (head-major)", tag);
+        if (ab_tiled && !(epi == VH_EPI_RESID_SPLIT || (!f8 && epi == VH_EPI_BIAS)))
+            return fail(nullptr, VH_ERR_INVALID, "%s: ab_tiled goes with RESID_SPLIT or 16-bit BIAS", tag);
+    }
+    if (tile_begin < 0 || tile_count < 0) return fail(nullptr, VH_ERR_INVALID, "%s: negative tile range", tag);
+    if (tile_begin || tile_count) {
+        if (variant != 5 && variant != 7) return fail(nullptr, VH_ERR_INVALID, "%s: tile ranges exist in variants 5 and 7 only", tag);
+        if (!tile_count) return fail(nullptr, VH_ERR_INVALID, "%s: tile_begin != 0 needs tile_count > 0", tag);
+        const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
+        if ((int64_t)tile_begin + tile_count > tiles) return fail(nullptr, VH_ERR_INVALID, "%s: tile range beyond the %lld tiles", tag, (long long)tiles);
+    }
+    return VH_OK;
+}
+int vh_op_gemm_layout(const void* a, const void* w, const float* bias, void* out, int64_t M, int N, int K, int epi,
+                      const float* aux, int aux_i, const float* stats, void* out16, float* partials, int dtype, int variant,
+                      int out_tiled, int ab_tiled, int tile_begin, int tile_count, void* stream) {
+    GemmArgs g{a, w, bias, out, M, N, K, epi, aux, aux_i, dtype, variant};
+    g.stats = stats; g.out16 = out16; g.partials = partials;
+    if (const char* why = gemm_check(g)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    if (int rc = gemm_layout_check("gemm_layout", false, M, N, K, epi, variant, out_tiled, ab_tiled, tile_begin, tile_count)) return rc;
+    g.out_tiled = out_tiled; g.ab_tiled = ab_tiled; g.tile_begin = tile_begin; g.tile_count = tile_count;
+    hipError_t e = launch_gemm(g, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "gemm_layout failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+int vh_op_gemm_fp8_layout(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M, int N, int K,
+                          int epi, const float* c_dev, const float* stats, void* out16, float* partials, int variant,
+                          int out_tiled, int ab_tiled, int tile_begin, int tile_count, void* stream) {
+    if (variant != 0 && variant != 5 && variant != 6 && variant != 7) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: variant must be 0, 5, 6 or 7");
+    if (!a8 || !w8 || !w_scale || !bias || !out) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: null pointer");
+    if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 4) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: need K %% 128 == 0 and N %% 4 == 0");
+    if (M > 0x7FFFFFFF / 2) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: M too large");
+    const bool fold_act = epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU;
+    const bool fold = epi == VH_EPI_LNFOLD || fold_act, resid = epi == VH_EPI_RESID_LN || epi == VH_EPI_RESID_SPLIT;
+    const bool plain = epi == VH_EPI_BIAS || epi == VH_EPI_BIAS_GELU || epi == VH_EPI_BIAS_QGELU || epi == VH_EPI_BIAS_RESID || epi == VH_EPI_BIAS_F32;
+    if (!fold && !resid && !plain) return fail(nullptr, VH_ERR_UNSUPPORTED, "gemm_fp8_layout: epilogue %d not available", epi);
+    if (fold && (!c_dev || !stats)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: LNFOLD needs c and stats");
+    if (resid && (!out16 || !partials)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: RESID_* needs out16 and partials");
+    if ((resid || fold_act) && N % 256) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: N %% 256 != 0");
+    if (int rc = gemm_layout_check("gemm_fp8_layout", true, M, N, K, epi, variant, out_tiled, ab_tiled, tile_begin, tile_count)) return rc;
+    GemmArgs g{a8, w8, bias, out, M, N, K, epi, fold ? c_dev : w_scale, 0, VH_DTYPE_FP8, variant};
+    if (fold) g.wscale = w_scale;
+    g.stats = stats; g.out16 = out16; g.partials = partials;
+    g.out_tiled = out_tiled; g.ab_tiled = ab_tiled; g.tile_begin = tile_begin; g.tile_count = tile_count;
+    hipError_t e = launch_gemm_fp8(g, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "gemm_fp8_layout failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+int vh_op_tile_rows(const void* in, int rows, int cols, void* out, int dtype, void* stream) {
+    if (!in || !out) return fail(nullptr, VH_ERR_INVALID, "tile_rows: null pointer");
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8) return fail(nullptr, VH_ERR_INVALID, "tile_rows: dtype");
+    const int chunk = dtype == VH_DTYPE_FP8 ? 16 : 8;
+    if (rows <= 0 || cols <= 0 || rows % 16 || cols % chunk)
+        return fail(nullptr, VH_ERR_INVALID, "tile_rows: need rows %% 16 == 0 and cols %% %d == 0", chunk);
+    hipError_t e = dtype == VH_DTYPE_FP8 ? launch_tile_bytes(in, rows, cols, out, (hipStream_t)stream)
+                                         : launch_cast_tiled_w((const float*)in, rows, cols, out, dtype, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "tile_rows failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
 int vh_op_rowstats_cast(const float* x, int64_t rows, int dim, float eps, void* x16, float* stats, int dtype, void* stream) {
     if (!x || !x16 || !stats || rows <= 0 || dim <= 0 || dim % 4 || dim > 2048) return fail(nullptr, VH_ERR_INVALID, "rowstats_cast: bad argument");
     OPCHK(launch_rowstats_cast(x, rows, dim, eps, x16, stats, dtype, (hipStream_t)stream));

@@ -203,6 +203,9 @@ SYMBOLS = {
     "vh_op_gemm_fp8_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "vh_op_quantize_rows": (_i, [_vp, _i, _i, C.c_float, _vp, _vp, _vp]),
     "vh_op_gemm_ex": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "vh_op_gemm_layout": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "vh_op_gemm_fp8_layout": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vh_op_tile_rows": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "vh_op_rowstats_cast": (_i, [_vp, _i64, _i, _f, _vp, _vp, _i, _vp]),
     "vh_op_finalize_stats": (_i, [_vp, _i, _i64, _i, _f, _vp, _vp]),
     "vh_op_pre_layernorm": (_i, [_vp, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -1462,6 +1465,26 @@ def op_gemm_ex(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, dtype, aux_pt
                out16_ptr=None, partials_ptr=None, variant=0):
     _check(lib().vh_op_gemm_ex(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, aux_ptr, aux_i, stats_ptr, out16_ptr,
                                partials_ptr, dtype, variant, None))
+
+
+def op_gemm_layout(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, dtype, aux_ptr=None, aux_i=0, stats_ptr=None,
+                   out16_ptr=None, partials_ptr=None, variant=0, out_tiled=False, ab_tiled=False, tile_begin=0, tile_count=0):
+    """Test tap: op_gemm_ex with the tiled / head-major result (out_tiled: unpack_tiled, pack_head_major), tiled A and W
+    (ab_tiled: pack_tiled, op_tile_rows) or a range of the 256 x 256 tiles (variants 5 and 7)."""
+    _check(lib().vh_op_gemm_layout(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, aux_ptr, aux_i, stats_ptr, out16_ptr,
+                                   partials_ptr, dtype, variant, 1 if out_tiled else 0, 1 if ab_tiled else 0, tile_begin, tile_count, None))
+
+
+def op_gemm_fp8_layout(a8_ptr, w8_ptr, scale_ptr, bias_ptr, out_ptr, M, N, K, epilogue, c_ptr=None, stats_ptr=None, out16_ptr=None,
+                       partials_ptr=None, variant=0, out_tiled=False, ab_tiled=False, tile_begin=0, tile_count=0):
+    """Test tap: op_gemm_fp8 / op_gemm_fp8_ex with the same four extras as op_gemm_layout (e4m3 chunks are 16 bytes)."""
+    _check(lib().vh_op_gemm_fp8_layout(a8_ptr, w8_ptr, scale_ptr, bias_ptr, out_ptr, M, N, K, epilogue, c_ptr, stats_ptr, out16_ptr,
+                                       partials_ptr, variant, 1 if out_tiled else 0, 1 if ab_tiled else 0, tile_begin, tile_count, None))
+
+
+def op_tile_rows(in_ptr, rows, cols, out_ptr, dtype):
+    """Test tap: fp32 [rows, cols] -> 16-bit tiled (pack_tiled(to16(.), 8)), or with DTYPE_FP8 bytes -> tiled bytes (chunk 16)."""
+    _check(lib().vh_op_tile_rows(in_ptr, rows, cols, out_ptr, dtype, None))
 
 
 def op_rowstats_cast(x_ptr, rows, dim, eps, x16_ptr, stats_ptr, dtype):
