@@ -307,3 +307,16 @@ def test_the_new_epilogue_codes_check_their_arguments_on_the_host():
     assert _code(f8x, 1, 1, 1, 1, 1, 256, 256, 128, vithip.EPI_BIAS_QGELU) == VH_ERR_UNSUPPORTED
     assert _code(f8x, 1, 1, 1, 1, 1, 256, 256, 128, vithip.EPI_LNFOLD_QGELU) == VH_ERR_INVALID   # no c / stats
     assert _code(f8x, 1, 1, 1, 1, 1, 256, 260, 128, vithip.EPI_LNFOLD_QGELU, 1, 1) == VH_ERR_INVALID   # N % 256
+
+
+def test_the_e4m3_row_limit_is_checked_where_the_forward_launches():
+    """gemm_check is what launch_gemm asks first, so the limits the e4m3 taps state hold for every caller: M above 0x7fffffff / 2 is
+    refused through the layout tap with the reason, the limit itself passes the check (and is refused for its tile range only)."""
+    f8l = vithip.op_gemm_fp8_layout      # (a8, w8, scale, bias, out, M, N, K, epilogue, ...); pointers are never dereferenced
+    limit = 0x7FFFFFFF // 2
+    with pytest.raises(vithip.VhError) as e:
+        f8l(1, 1, 1, 1, 1, limit + 1, 256, 256, vithip.EPI_BIAS, variant=5, tile_count=1)
+    assert e.value.code == VH_ERR_INVALID and "gemm_fp8_layout: M too large" in str(e.value)
+    with pytest.raises(vithip.VhError) as e:
+        f8l(1, 1, 1, 1, 1, limit, 256, 256, vithip.EPI_BIAS, variant=5, tile_begin=limit, tile_count=5)
+    assert e.value.code == VH_ERR_INVALID and "tile range beyond the 4194304 tiles" in str(e.value)

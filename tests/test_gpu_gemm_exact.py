@@ -297,6 +297,7 @@ def test_tile_ranges(ops, epi, variant):
 
 # ---- 5. refusals -------------------------------------------------------------------------------------------------------------
 def test_layout_taps_refuse_what_the_launchers_refuse():
+    # (one text since gemm_check states both: the taps print its reason, launch_gemm asks it first, so every caller is refused alike)
     size = 1 << 20
     b = dev(np.full(size, GUARD, np.uint8))
     p = b.ptr

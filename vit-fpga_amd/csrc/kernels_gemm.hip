@@ -24,6 +24,7 @@
 //   * 1-D grid remapped so that the workgroups that share an XCD (blockIdx % 8) walk a
 //     contiguous run of tiles, n fastest: neighbours reuse the same A panel from that XCD's L2.
 //   * ragged M / N: loads clamp the row index, stores are predicated (N % 4 == 0, K % 64 == 0).
+#include <cstdio>
 #include <cstdlib>
 
 #include "gemm_epilogue.h"
@@ -196,39 +197,85 @@ int gemm_pick_variant(int64_t M, int N, int epilogue) {
     return t256 >= min_tiles ? gemm_pp_variant(epilogue) : 1;  // the 256x256 ping-pong kernel needs enough tiles for the 256 CUs
 }
 
-// the persistent ping-pong form runs (launch_pp): enough tiles for the ping-pong kernel, whole 256 x 256 tiles, at least four K-tiles (the forms that prefetch their epilogue's first loads need a W(k+2) slot in K-tile 1)
-bool gemm_tiled_applies(int64_t M, int N, int K) {
-    return M > 0 && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K / 64 >= 4 && gemm_pick_variant(M, N, VH_EPI_BIAS) == 6;
+// the persistent ping-pong form runs (launch_pp): enough tiles for the ping-pong kernel (e4m3 operands take it whenever whole tiles allow
+// it), whole 256 x 256 tiles, at least four K-tiles of 128 bytes (the forms that prefetch their epilogue's first loads need a W(k+2)
+// slot in K-tile 1)
+bool gemm_tiled_applies(int64_t M, int N, int K, int dtype) {
+    const bool f8 = dtype == VH_DTYPE_FP8;
+    const int kt = f8 ? 128 : 64;
+    return M > 0 && M % 256 == 0 && N % 256 == 0 && K % kt == 0 && K / kt >= 4 &&
+           (f8 ? gemm_pp_variant(VH_EPI_BIAS) : gemm_pick_variant(M, N, VH_EPI_BIAS)) == 6;
 }
 
-bool gemm_tiled_applies_f8(int64_t M, int N, int K) {   // (launch_gemm_fp8 takes the persistent form whenever whole tiles allow it)
-    return M > 0 && M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && K / 128 >= 4 && gemm_pp_variant(VH_EPI_BIAS) == 6;
-}
-
+// What a launch accepts, for both operand widths: the one statement of it.  launch_gemm asks first; the operator taps
+// (vithip_api.hip) print the reason.  The texts start "gemm:" (16-bit operands), "gemm_fp8:" (e4m3 operands) or "gemm_layout:" (the
+// tiled layouts and tile ranges of either width); a tap of the e4m3 form puts its own name there.  Host arithmetic only.
 const char* gemm_check(const GemmArgs& g) {
-    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return "gemm: empty shape";
-    if (g.K % 64) return "gemm: K must be a multiple of 64";
-    if (g.N % 4) return "gemm: N must be a multiple of 4";
-    if (g.M > 0x7fffffff) return "gemm: M too large";
-    if (g.epilogue < 0 || g.epilogue > VH_EPI_LNFOLD_QGELU) return "gemm: unknown epilogue";
-    if ((g.epilogue == VH_EPI_LNFOLD || g.epilogue == VH_EPI_LNFOLD_GELU || g.epilogue == VH_EPI_LNFOLD_QGELU) && (!g.stats || !g.aux)) return "gemm: LNFOLD needs stats and c (aux)";
-    if ((g.epilogue == VH_EPI_RESID_LN || g.epilogue == VH_EPI_RESID_SPLIT) && (!g.out16 || !g.partials || g.N % 256))
-        return "gemm: RESID_LN / RESID_SPLIT need out16, partials and N % 256 == 0";
-    if (g.epilogue == VH_EPI_PATCH && (!g.aux || g.aux_i <= 0)) return "gemm: EPI_PATCH needs pos-emb and patches/image";
-    if (g.epilogue == VH_EPI_PATCH_SPLIT && (!g.aux || g.aux_i <= 0 || !g.out16 || !g.partials || g.N % 256 || g.prow < 0))
-        return "gemm: EPI_PATCH_SPLIT needs pos-emb, patches/image, the lo plane, partials and N % 256 == 0";
-    if (g.dtype != VH_DTYPE_BF16 && g.dtype != VH_DTYPE_FP16) return "gemm: dtype";
-    if (g.variant < 0 || g.variant > 7) return "gemm: variant";
-    if (g.variant == 3 || g.variant == 4) return "gemm: variants 3/4 (BK=32 pipeline) were removed";
-    if (!g.a || !g.w || !g.bias || !g.out) return "gemm: null pointer";
+    const int epi = g.epilogue;
+    const bool f8 = g.dtype == VH_DTYPE_FP8;
+    const bool act = epi_has_act(epi), fold = epi_is_lnfold(epi), resid = epi == VH_EPI_RESID_LN || epi == VH_EPI_RESID_SPLIT;
+    if (f8) {   // e4m3 operands + per-channel weight scales: ping-pong forms only, 128-element K-tiles, no patch-row remap
+        if (g.variant != 0 && g.variant != 5 && g.variant != 6 && g.variant != 7) return "gemm_fp8: variant must be 0, 5, 6 or 7";
+        if (!g.a || !g.w || !g.wscale || !g.bias || !g.out) return "gemm_fp8: null pointer";
+        if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.K % 128 || g.N % 4) return "gemm_fp8: need K % 128 == 0 and N % 4 == 0";
+        if (g.M > 0x7FFFFFFF / 2) return "gemm_fp8: M too large";
+        if (!fold && !resid && !act && epi != VH_EPI_BIAS && epi != VH_EPI_BIAS_RESID && epi != VH_EPI_BIAS_F32)
+            return "gemm_fp8: epilogue not available";
+        if (fold && (!g.aux || !g.stats)) return "gemm_fp8: LNFOLD needs c and stats";
+        if (resid && (!g.out16 || !g.partials)) return "gemm_fp8: RESID_* needs out16 and partials";
+        if ((resid || (fold && act)) && g.N % 256) return "gemm_fp8: N % 256 != 0";
+    } else {
+        if (g.M <= 0 || g.N <= 0 || g.K <= 0) return "gemm: empty shape";
+        if (g.K % 64) return "gemm: K must be a multiple of 64";
+        if (g.N % 4) return "gemm: N must be a multiple of 4";
+        if (g.M > 0x7fffffff) return "gemm: M too large";
+        if (epi < 0 || epi > VH_EPI_LNFOLD_QGELU) return "gemm: unknown epilogue";
+        if (fold && (!g.stats || !g.aux)) return "gemm: LNFOLD needs stats and c (aux)";
+        if (resid && (!g.out16 || !g.partials || g.N % 256)) return "gemm: RESID_LN / RESID_SPLIT need out16, partials and N % 256 == 0";
+        if (epi == VH_EPI_PATCH && (!g.aux || g.aux_i <= 0)) return "gemm: EPI_PATCH needs pos-emb and patches/image";
+        if (epi == VH_EPI_PATCH_SPLIT && (!g.aux || g.aux_i <= 0 || !g.out16 || !g.partials || g.N % 256 || g.prow < 0))
+            return "gemm: EPI_PATCH_SPLIT needs pos-emb, patches/image, the lo plane, partials and N % 256 == 0";
+        if (g.dtype != VH_DTYPE_BF16 && g.dtype != VH_DTYPE_FP16) return "gemm: dtype";
+        if (g.variant < 0 || g.variant > 7) return "gemm: variant";
+        if (g.variant == 3 || g.variant == 4) return "gemm: variants 3/4 (BK=32 pipeline) were removed";
+        if (!g.a || !g.w || !g.bias || !g.out) return "gemm: null pointer";
+    }
+    // ---- the tiled / head-major layouts and tile ranges: what launch_pp (kernels_gemm5.hip) can run ----
+    if (g.out_tiled || g.ab_tiled) {
+        if (g.out_tiled && g.ab_tiled) return "gemm_layout: out_tiled and ab_tiled exclude each other";
+        if (g.variant != 6) return "gemm_layout: the tiled layouts exist in the persistent form only (variant 6)";
+        if (g.tile_begin || g.tile_count) return "gemm_layout: a tile range excludes the tiled layouts";
+        if (g.M % 256 || g.N % 256) return "gemm_layout: the tiled layouts need M % 256 == 0 and N % 256 == 0";
+        // K-tiles the persistent form demands: four where the LN-fold constants travel through LDS (every LN-fold epilogue but the
+        // e4m3-operand activation forms: pp_uses_cpre), two otherwise
+        const bool four = fold && !(f8 && act);
+        if (g.K / (f8 ? 128 : 64) < (four ? 4 : 2))
+            return four ? "gemm_layout: the tiled layouts need at least 4 K-tiles with this epilogue"
+                        : "gemm_layout: the tiled layouts need at least 2 K-tiles with this epilogue";
+        if (g.out_tiled && !(act || epi == VH_EPI_LNFOLD || (!f8 && epi == VH_EPI_BIAS)))
+            return "gemm_layout: out_tiled goes with the activation epilogues (tiled) or LNFOLD / 16-bit BIAS (head-major)";
+        if (g.ab_tiled && !(epi == VH_EPI_RESID_SPLIT || (!f8 && epi == VH_EPI_BIAS))) return "gemm_layout: ab_tiled goes with RESID_SPLIT or 16-bit BIAS";
+    }
+    if (g.tile_begin < 0 || g.tile_count < 0) return "gemm_layout: negative tile range";
+    if (g.tile_begin || g.tile_count) {
+        if (g.variant != 5 && g.variant != 7) return "gemm_layout: tile ranges exist in variants 5 and 7 only";
+        if (!g.tile_count) return "gemm_layout: tile_begin != 0 needs tile_count > 0";
+        const int64_t tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
+        if ((int64_t)g.tile_begin + g.tile_count > tiles) {
+            static thread_local char text[64];
+            snprintf(text, sizeof text, "gemm_layout: tile range beyond the %lld tiles", (long long)tiles);
+            return text;
+        }
+    }
     return nullptr;
 }
 
+hipError_t launch_gemm_fp8(const GemmArgs& g, hipStream_t s);   // kernels_gemm5.hip, beside the e4m3 instantiations
+
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t s) {
     if (gemm_check(g)) return hipErrorInvalidValue;
+    if (g.dtype == VH_DTYPE_FP8) return launch_gemm_fp8(g, s);
     const int variant = g.variant ? g.variant : gemm_pick_variant(g.M, g.N, g.epilogue);
-    if ((g.out_tiled || g.ab_tiled) && variant != 6) return hipErrorInvalidValue;   // tiled layouts exist in the persistent form only
-    if ((g.tile_count || g.tile_begin) && variant != 5 && variant != 7) return hipErrorInvalidValue;  // tile ranges: ping-pong forms only
     return g.dtype == VH_DTYPE_BF16 ? launch_epi<BF16>(g, variant, s) : launch_epi<FP16>(g, variant, s);
 }
 

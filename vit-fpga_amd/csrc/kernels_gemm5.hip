@@ -43,7 +43,8 @@
 //      L0: W fragments + X fragments of row blocks 0-3     C0: 16 MFMAs (row blocks 0-3)
 //      L1: X fragments of row blocks 4-7                   C1: 16 MFMAs (row blocks 4-7)
 // (same 512 matrix cycles per phase, same 64 fragment registers).  W carries one fp32 scale per output channel
-// (`aux`), applied to the accumulators before the epilogue; activations are unscaled (vh_common.h, E4M3).
+// (GemmArgs::wscale -> the kernel's `wscale`, with every epilogue; `aux` stays what the epilogue defines), applied to the
+// accumulators before the epilogue; activations are unscaled (vh_common.h, E4M3).
 #include <cstdlib>
 #include <type_traits>
 
@@ -608,22 +609,18 @@ static hipError_t launch_pp_one(const GemmArgs& g, int grid, int tiles_m, int ti
     if (hipError_t e = ensure_dynamic_lds((const void*)k, lds, lds_done); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, g.a, g.w, g.bias, g.out, (int)g.M, g.N, g.K, g.aux, g.aux_i, tiles_m,
                        tiles_n, g.stats, g.out16, g.partials, PERSIST ? 0 : g.tile_begin, (g.tile_count || g.tile_begin) ? 0 : gemm_super_columns(tiles_n),
-                       F8 ? (g.wscale ? g.wscale : g.aux) : (const float*)nullptr, gemm_prow(g)
+                       F8 ? g.wscale : (const float*)nullptr, gemm_prow(g)
                        VH_STAMP_ARG(g, EPI, F8, grid, PERSIST ? 6 : (AST == 3 ? 7 : 5)));
     return hipGetLastError();
 }
 
+// gemm_check(g) has passed (launch_gemm): a tile range comes with mode 0 / 2 and lies inside the tiles; a tiled layout comes with mode 1,
+// whole tiles, enough K-tiles and an epilogue that has the instantiation
 template <typename T, int EPI, bool F8>
 static hipError_t launch_pp(const GemmArgs& g, int mode, hipStream_t s) {
     if constexpr (EPI == VH_EPI_PATCH) { if (mode == 1) mode = 0; }   // the patch-row remap has no staged (full-line) epilogue
     const int tiles_m = (int)((g.M + 255) / 256), tiles_n = (g.N + 255) / 256;
-    int ntiles = tiles_m * tiles_n;
-    if (g.tile_count > 0) {   // a sub-range of the tiles (one tile per workgroup forms only)
-        if (mode == 1 || g.tile_begin < 0 || g.tile_begin + g.tile_count > ntiles) return hipErrorInvalidValue;
-        ntiles = g.tile_count;
-    } else if (g.tile_begin != 0) {
-        return hipErrorInvalidValue;
-    }
+    const int ntiles = g.tile_count > 0 ? g.tile_count : tiles_m * tiles_n;   // a sub-range of the tiles (one tile per workgroup forms only)
     if (mode == 2) return launch_pp_one<T, EPI, F8, false, 3>(g, ntiles, tiles_m, tiles_n, s);
     if constexpr (EPI != VH_EPI_PATCH) {
         // the persistent form runs FULL tiles of at least two K-tiles only: N must be a multiple of the tile, and a ragged
@@ -635,21 +632,19 @@ static hipError_t launch_pp(const GemmArgs& g, int mode, hipStream_t s) {
         // CUs while the rest idle (batch 128: fc2 2.74 ms per forward against 1.96 ms in the one-tile form).  The
         // persistent form gains ~3 %, so it is worth that only when forced (variant 6 asked for explicitly).
         if (mode == 1 && full_m != tiles_m && g.variant != 6) mode = 0;
-        if ((g.out_tiled || g.ab_tiled) && (mode != 1 || full_m != tiles_m)) return hipErrorInvalidValue;   // tiled layouts: persistent form on whole tiles only
         if (mode == 1) {
             const int num_cu = device_num_cu();   // of the device this launch goes to (a group has one thread per device)
             if (!num_cu) return hipErrorUnknown;
-            const int nfull = full_m * tiles_n;
+            const int nfull = full_m * tiles_n, grid = nfull < num_cu ? nfull : num_cu;
             // (LNFOLD / BIAS with out_tiled: the q|k|v projection's HEAD-MAJOR result, gemm_epilogue.h)
             // (e4m3 operands: the GELU forms write the tiled e4m3 hidden activation, RESID_SPLIT reads it; LNFOLD's bf16 q|k|v goes head-major like the 16-bit path's)
             if constexpr (epi_has_act(EPI) || EPI == VH_EPI_LNFOLD || (!F8 && EPI == VH_EPI_BIAS)) {
-                if (g.out_tiled) return g.ab_tiled ? hipErrorInvalidValue : launch_pp_one<T, EPI, F8, true, 2, true, false>(g, nfull < num_cu ? nfull : num_cu, full_m, tiles_n, s);
+                if (g.out_tiled) return launch_pp_one<T, EPI, F8, true, 2, true, false>(g, grid, full_m, tiles_n, s);
             }
             if constexpr (F8 ? EPI == VH_EPI_RESID_SPLIT : (EPI == VH_EPI_RESID_SPLIT || EPI == VH_EPI_BIAS)) {
-                if (g.ab_tiled) return g.out_tiled ? hipErrorInvalidValue : launch_pp_one<T, EPI, F8, true, 2, false, true>(g, nfull < num_cu ? nfull : num_cu, full_m, tiles_n, s);
+                if (g.ab_tiled) return launch_pp_one<T, EPI, F8, true, 2, false, true>(g, grid, full_m, tiles_n, s);
             }
-            if (g.out_tiled || g.ab_tiled) return hipErrorInvalidValue;
-            if (hipError_t e = launch_pp_one<T, EPI, F8, true, 2>(g, nfull < num_cu ? nfull : num_cu, full_m, tiles_n, s); e != hipSuccess) return e;
+            if (hipError_t e = launch_pp_one<T, EPI, F8, true, 2>(g, grid, full_m, tiles_n, s); e != hipSuccess) return e;
             if (full_m == tiles_m) return hipSuccess;
             GemmArgs tail = g;   // tiles [full_m * tiles_n, ntiles) of the n-fastest order = the ragged last row of tiles
             tail.tile_begin = nfull;
@@ -657,7 +652,6 @@ static hipError_t launch_pp(const GemmArgs& g, int mode, hipStream_t s) {
             return launch_pp_one<T, EPI, F8, false, 2>(tail, tiles_n, tiles_m, tiles_n, s);
         }
     }
-    if (g.out_tiled || g.ab_tiled) return hipErrorInvalidValue;
     return launch_pp_one<T, EPI, F8, false, 2>(g, ntiles, tiles_m, tiles_n, s);
 }
 
@@ -682,23 +676,23 @@ hipError_t launch_gemm_pingpong(const GemmArgs& g, int mode, hipStream_t s) {
 VH_INST(BF16)
 VH_INST(FP16)
 
-// fp8 operands: 16-bit results are bf16; fc1 writes e4m3 (gemm_epilogue8)
+// e4m3 operands (launch_gemm sends GemmArgs::dtype == VH_DTYPE_FP8 here, behind gemm_check): 16-bit results are bf16; fc1 writes e4m3
+// (gemm_epilogue8).  LNFOLD*: `aux` = c_n, `stats` = (mean, rstd) per row.  RESID_SPLIT: out = the e4m3 hi plane (the next GEMM's
+// operand), out16 = the bf16 lo plane.
 hipError_t launch_gemm_fp8(const GemmArgs& g, hipStream_t s) {
     const int v = g.variant ? g.variant : gemm_pp_variant(g.epilogue);
-    const int mode = v == 7 ? 2 : (v == 6 && !g.tile_count && !g.tile_begin ? 1 : 0);
+    const int mode = v == 7 ? 2 : (v == 6 ? 1 : 0);
     switch (g.epilogue) {
         case VH_EPI_BIAS: return launch_pp<BF16, VH_EPI_BIAS, true>(g, mode, s);
         case VH_EPI_BIAS_GELU: return launch_pp<BF16, VH_EPI_BIAS_GELU, true>(g, mode, s);
         case VH_EPI_BIAS_QGELU: return launch_pp<BF16, VH_EPI_BIAS_QGELU, true>(g, mode, s);
         case VH_EPI_BIAS_RESID: return launch_pp<BF16, VH_EPI_BIAS_RESID, true>(g, mode, s);
         case VH_EPI_BIAS_F32: return launch_pp<BF16, VH_EPI_BIAS_F32, true>(g, mode, s);
-        // folded LayerNorm on e4m3 operands: `aux` = c_n, `wscale` = the weight scales, `stats` = (mean, rstd) per row
-        case VH_EPI_LNFOLD: return g.wscale && g.stats && g.aux ? launch_pp<BF16, VH_EPI_LNFOLD, true>(g, mode, s) : hipErrorInvalidValue;
-        case VH_EPI_LNFOLD_GELU: return g.wscale && g.stats && g.aux && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_LNFOLD_GELU, true>(g, mode, s) : hipErrorInvalidValue;
-        case VH_EPI_LNFOLD_QGELU: return g.wscale && g.stats && g.aux && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_LNFOLD_QGELU, true>(g, mode, s) : hipErrorInvalidValue;
-        case VH_EPI_RESID_LN: return g.out16 && g.partials && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_RESID_LN, true>(g, mode, s) : hipErrorInvalidValue;
-        // split residual of the fp8 path: out = the e4m3 hi plane (the next GEMM's operand), out16 = the bf16 lo plane
-        case VH_EPI_RESID_SPLIT: return g.out16 && g.partials && g.N % 256 == 0 ? launch_pp<BF16, VH_EPI_RESID_SPLIT, true>(g, mode, s) : hipErrorInvalidValue;
+        case VH_EPI_LNFOLD: return launch_pp<BF16, VH_EPI_LNFOLD, true>(g, mode, s);
+        case VH_EPI_LNFOLD_GELU: return launch_pp<BF16, VH_EPI_LNFOLD_GELU, true>(g, mode, s);
+        case VH_EPI_LNFOLD_QGELU: return launch_pp<BF16, VH_EPI_LNFOLD_QGELU, true>(g, mode, s);
+        case VH_EPI_RESID_LN: return launch_pp<BF16, VH_EPI_RESID_LN, true>(g, mode, s);
+        case VH_EPI_RESID_SPLIT: return launch_pp<BF16, VH_EPI_RESID_SPLIT, true>(g, mode, s);
         default: return hipErrorInvalidValue;
     }
 }

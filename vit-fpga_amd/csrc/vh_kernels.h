@@ -9,40 +9,41 @@
 
 namespace vh {
 
+// One GEMM launch: out = epilogue(A[M,K] x W[N,K]^T).  `dtype` selects the operand form inside launch_gemm: VH_DTYPE_BF16 / FP16
+// (kernels_gemm.hip, kernels_gemm5.hip) or VH_DTYPE_FP8 = OCP e4m3 bytes with one fp32 scale per output channel (kernels_gemm5.hip:
+// K % 128 == 0, variants 0 / 5 / 6 / 7, 16-bit results are bf16, the activation epilogues write e4m3, no PATCH / PATCH_SPLIT).
+// gemm_check says what a launch accepts; launch_gemm asks it first.
 struct GemmArgs {
-    const void* a;      // [M, K] 16-bit, K contiguous
-    const void* w;      // [N, K] 16-bit, K contiguous
+    const void* a;      // [M, K], K contiguous
+    const void* w;      // [N, K], K contiguous
     const float* bias;  // [N]
-    void* out;          // 16-bit or fp32 [M(or remapped rows), N]
+    void* out;          // 16-bit, e4m3 or fp32 [M(or remapped rows), N]
     int64_t M;
     int N, K;
     int epilogue;       // VH_EPI_*
-    const float* aux;   // EPI_PATCH: pos-emb [tokens, N]
-    int aux_i;          // EPI_PATCH: patches per image
-    int dtype;          // VH_DTYPE_*
-    int variant;        // 0 auto, 1 = 128x128, 2 = 256x256 two-stage, 5 = ping-pong, 6 = persistent ping-pong
+    const float* aux;   // what the EPILOGUE defines, whatever the operands: PATCH / PATCH_SPLIT pos-emb [tokens, N]; LNFOLD* c_n [N]
+    int aux_i;          // PATCH / PATCH_SPLIT: patches per image
+    int dtype;          // VH_DTYPE_* of the operands
+    int variant;        // 0 auto, 1 = 128x128, 2 = 256x256 two-stage, 5 = ping-pong, 6 = persistent ping-pong, 7 = ping-pong, three A stages
     const float* stats = nullptr;  // LNFOLD*: [M][2] (mean, rstd)
-    void* out16 = nullptr;         // RESID_LN: 16-bit copy of the updated rows
-    float* partials = nullptr;     // RESID_LN: [N/64][M][2]
-    const float* wscale = nullptr; // launch_gemm_fp8 with an LNFOLD* epilogue: the per-output-channel weight scales [N]
-                                   // (`aux` carries c_n there); every other fp8 epilogue passes them in `aux`
+    void* out16 = nullptr;         // RESID_LN: 16-bit (e4m3 operands: e4m3) copy of the updated rows; RESID_SPLIT / PATCH_SPLIT: the lo plane
+    float* partials = nullptr;     // RESID_LN / RESID_SPLIT / PATCH_SPLIT: [N/64][M][2]
+    const float* wscale = nullptr; // e4m3 operands: the per-output-channel weight scales [N], with every epilogue; unused with 16-bit operands
     // ping-pong forms 5 / 7 only: launch tiles [tile_begin, tile_begin + tile_count) of the n-fastest 256x256 tile order
     // (tile t = (t / tiles_n, t % tiles_n)); tile_count == 0 = all tiles.  Lets a caller split off the last, partly
     // filled round of tiles and overlap it with other work (vithip_api.hip, tail overlap).
     int tile_begin = 0, tile_count = 0;
     // PATCH_SPLIT: row stride of `partials` = number of TOKEN rows the statistics buffer is laid out for (0 = images x tokens)
     int64_t prow = 0;
-    // The MLP hidden activation in its TILED layout (gemm_epilogue.h, OTILED; persistent 16-bit form only: the launcher
-    // refuses otherwise -- ask gemm_tiled_applies first).  out_tiled: an LNFOLD_GELU / BIAS_GELU (or *_QGELU) launch writes it; ab_tiled: A and W
-    // of this launch are both in that layout (16-row blocks).
+    // The TILED layouts (gemm_epilogue.h, OTILED; persistent form only, so variant 6 is spelled out and the shape is one
+    // gemm_tiled_applies accepts).  out_tiled: an activation epilogue writes the MLP hidden activation tiled, LNFOLD / 16-bit BIAS
+    // write q|k|v head-major; ab_tiled: A and W of this launch are both in the tiled layout (16-row blocks).
     int out_tiled = 0, ab_tiled = 0;
 };
-// does a 16-bit GEMM of this shape take the persistent form, the only one that reads / writes the tiled layout?
-bool gemm_tiled_applies(int64_t M, int N, int K);
-// W fp32 [rows, cols] -> 16-bit in the tiled layout (16-row blocks, natural column order)
+// does a GEMM of this shape and operand dtype take the persistent form, the only one that reads / writes the tiled layouts?
+bool gemm_tiled_applies(int64_t M, int N, int K, int dtype);
+// W fp32 [rows, cols] -> 16-bit in the tiled layout (16-row blocks, natural column order); e4m3: the byte matrix -> tiled copy
 hipError_t launch_cast_tiled_w(const float* w, int rows, int cols, void* w16, int dtype, hipStream_t stream);
-// e4m3 operands (launch_gemm_fp8): the same question for the 128-byte K-tiles of the fp8 form, and the byte matrix -> tiled copy
-bool gemm_tiled_applies_f8(int64_t M, int N, int K);
 hipError_t launch_tile_bytes(const void* w8, int rows, int cols, void* out, hipStream_t stream);
 
 // row stride of the partial-sum buffer a launch writes: PATCH_SPLIT lands on token rows (images x (patches + 1) unless the
@@ -52,12 +53,9 @@ inline int64_t gemm_prow(const GemmArgs& g) {
     return g.prow > 0 ? g.prow : (g.M / g.aux_i) * (int64_t)(g.aux_i + 1);
 }
 
-// every launcher only enqueues on `stream`; returns hipSuccess or the launch error
+// every launcher only enqueues on `stream`; returns hipSuccess or the launch error (hipErrorInvalidValue: gemm_check refuses)
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t stream);
-// fp8 form (kernels_gemm5.hip): a, w = e4m3 [M,K] / [N,K]; aux = per-output-channel weight scale [N];
-// epilogue BIAS (bf16 out), BIAS_GELU (e4m3 out), BIAS_RESID / BIAS_F32 (fp32 out).  K % 128 == 0, N % 4 == 0.
-hipError_t launch_gemm_fp8(const GemmArgs& g, hipStream_t stream);
-const char* gemm_check(const GemmArgs& g);  // NULL if the shape is supported, else the reason
+const char* gemm_check(const GemmArgs& g);  // NULL if the launch is accepted, else the reason; host arithmetic only, no HIP call
 int gemm_pick_variant(int64_t M, int N, int epilogue);
 int gemm_pp_variant(int epilogue);  // 5, 6 or 7 (default 6 = persistent; env VH_GEMM_PP forces one)
 

@@ -512,21 +512,6 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         ev->push_back({stage, e});
         return VH_OK;
     };
-    // `wscale` (fp8 operands only): the weight matrix's per-output-channel scales
-    auto gemm = [&](const void* a, const void* w, const float* bias, void* out, int64_t Mr, int N, int K, int epi,
-                    const float* aux, int aux_i, const float* wscale = nullptr) {
-        GemmArgs g{a, w, bias, out, Mr, N, K, epi, aux, aux_i, dt16, 0};
-        g.stats = stats_p;         // read by LNFOLD*, ignored otherwise
-        g.out16 = epi == VH_EPI_RESID_SPLIT ? xlo16 : xn16;   // RESID_LN: the 16-bit (fp8: e4m3) copy; RESID_SPLIT: the lo plane
-        g.partials = partials_p;
-        if (wscale) {              // e4m3 operands (folded-LN layer loop of the fp8 path)
-            g.dtype = VH_DTYPE_FP8;
-            if (epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU) g.wscale = wscale;   // `aux` carries c_n there
-            else g.aux = wscale;
-            return launch_gemm_fp8(g, s);
-        }
-        return launch_gemm(g, s);
-    };
     // hip events around every launch of the stage selected by vh_set_stage_timing()
     auto tmark = [&](int stage) -> int {
         if (stage != c->timing_stage) return VH_OK;
@@ -537,6 +522,31 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         }
         HIPCHK(&c->err, hipEventRecord(c->tev[c->tev_used++], s));
         return VH_OK;
+    };
+    // The one GemmArgs builder of this part.  It sets what every launch shares: the operand dtype (op_dt in the layer loops, dt16 for
+    // the patch GEMM) and this part's statistics slices (LNFOLD* reads stats, RESID_* / PATCH_SPLIT write partials, the others ignore
+    // both).  A launch adds what its epilogue and layout need: out16, wscale (null on the 16-bit paths), a layout flag, a tile range.
+    const int op_dt = c->fp8 ? VH_DTYPE_FP8 : dt16;   // type of the GEMM A operands produced by LN / attention / fc1
+    auto gemm_args = [&](int dtype, const void* a, const void* w, const float* bias, void* out, int64_t Mr, int N, int K, int epi,
+                         const float* aux = nullptr, int aux_i = 0) {
+        GemmArgs g{a, w, bias, out, Mr, N, K, epi, aux, aux_i, dtype, 0};
+        g.stats = stats_p;
+        g.partials = partials_p;
+        return g;
+    };
+    // the tiled layouts exist in the persistent form only, and a launch that asks for one names that form (gemm_check)
+    auto set_tiled = [](GemmArgs& g, bool out_tiled, bool ab_tiled) {
+        g.out_tiled = out_tiled;
+        g.ab_tiled = ab_tiled;
+        if (out_tiled || ab_tiled) g.variant = 6;
+    };
+    // the stage bracket: the stage-timing events around one launch, then the stage's profile event
+    auto stage = [&](int st, auto&& launch) -> int {
+        int r;
+        if ((r = tmark(st))) return r;
+        HIPCHK(&c->err, launch());
+        if ((r = tmark(st))) return r;
+        return mark(st);
     };
     int rc;
     if (img0 == 0) c->tail_splits = 0;
@@ -549,9 +559,11 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     const bool pre_ln = (f.flags & VH_FLAG_PRE_LN) != 0;
     const int epi_fc1 = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_LNFOLD_QGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
     const int epi_fc1_plain = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_BIAS_QGELU : VH_EPI_BIAS_GELU;       // plain layer loop
+    // the patch embedding lands directly in the split residual's planes (below): the 16-bit split path without a pre-LayerNorm
+    const bool patch_split = c->split && !c->fp8 && nl > 0 && !pre_ln;
     // 8-bit images: always the im2col pass (which normalises) + the ordinary patch GEMM; the fused loader reads fp32 only
-    const bool fused_patch = !in.u8 && !pre_ln && c->patch_fused && c->split && !c->fp8 && nl > 0 && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
-    if (!fused_patch) {
+    const bool fused_patch = patch_split && !in.u8 && c->patch_fused && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
+    if (!fused_patch) {   // (no stage bracket: the profile event is recorded with or without the pass)
         if ((rc = tmark(ST_IM2COL))) return rc;
         if (in.u8)
             HIPCHK(&c->err, launch_im2col_u8((const uint8_t*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale, c->in_shift,
@@ -561,55 +573,46 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         if ((rc = tmark(ST_IM2COL))) return rc;
     }
     if ((rc = mark(ST_IM2COL))) return rc;
-    if (fused_patch) {
-        if ((rc = tmark(ST_PATCH))) return rc;
-        HIPCHK(&c->err, launch_patch_fused((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, c->wp16, P + L.patch_b, P + L.pos, xn16, xlo16,
-                                           partials_p, rows_g, D, dt16, s));
-        if ((rc = tmark(ST_PATCH))) return rc;
-        if ((rc = mark(ST_PATCH))) return rc;
-        HIPCHK(&c->err, launch_cls_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, batch, T, D, dt16, s));
-        if ((rc = mark(ST_CLS))) return rc;
-        HIPCHK(&c->err, launch_finalize_stats(partials_p, D / 64, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
-        if ((rc = mark(ST_LNSTATS))) return rc;
-    } else if (c->split && !c->fp8 && nl > 0 && !pre_ln) {
+    if (patch_split) {
         // Split residual: the patch embedding lands DIRECTLY in the two 16-bit planes, with the first row statistics'
-        // partial sums (PATCH_SPLIT epilogue; the class-token rows from their own small kernel) -- no fp32 x, no separate
-        // row-statistics pass over it (round 3: -0.1 ms per forward).  The partial sums are laid out for rows_g rows, like
-        // every later layer's.
-        GemmArgs g{col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, P + L.pos, L.NP, dt16, 0};
-        g.out16 = xlo16; g.partials = partials_p; g.prow = rows_g;
-        if ((rc = tmark(ST_PATCH))) return rc;
-        HIPCHK(&c->err, launch_gemm(g, s));
-        if ((rc = tmark(ST_PATCH))) return rc;
-        if ((rc = mark(ST_PATCH))) return rc;
+        // partial sums (PATCH_SPLIT epilogue or the fused loader's; the class-token rows from their own small kernel) -- no fp32
+        // x, no separate row-statistics pass over it (round 3: -0.1 ms per forward).  The partial sums are laid out for rows_g
+        // rows, like every later layer's.
+        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, P + L.pos, L.NP);
+        g.out16 = xlo16;
+        g.prow = rows_g;
+        if ((rc = stage(ST_PATCH, [&] {
+                 return fused_patch ? launch_patch_fused((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, c->wp16, P + L.patch_b,
+                                                         P + L.pos, xn16, xlo16, partials_p, rows_g, D, dt16, s)
+                                    : launch_gemm(g, s);
+             })))
+            return rc;
         HIPCHK(&c->err, launch_cls_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, batch, T, D, dt16, s));
         if ((rc = mark(ST_CLS))) return rc;
         HIPCHK(&c->err, launch_finalize_stats(partials_p, D / 64, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
-        if ((rc = mark(ST_LNSTATS))) return rc;
+        if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark: ST_LNSTATS has no stage timing)
     } else {
-        if ((rc = tmark(ST_PATCH))) return rc;
-        HIPCHK(&c->err, gemm(col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, P + L.pos, L.NP));
-        if ((rc = tmark(ST_PATCH))) return rc;
-        if ((rc = mark(ST_PATCH))) return rc;
+        const GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, P + L.pos, L.NP);
+        if ((rc = stage(ST_PATCH, [&] { return launch_gemm(g, s); }))) return rc;
         HIPCHK(&c->err, launch_cls_rows(x, P + L.cls, P + L.pos, batch, T, D, s));
         if ((rc = mark(ST_CLS))) return rc;
         if (pre_ln) {
             // x <- LN(x) pre_ln.weight + pre_ln.bias, in the form the path consumes: the fp32 array (plain loop, non-split fold, no
             // layer at all), the 16-bit operand copy / the split planes, layer 0's LN1 statistics of the normalised rows and the guards
             const bool fold0 = c->ln_fold && nl > 0;
-            if ((rc = tmark(ST_PRELN))) return rc;
-            HIPCHK(&c->err, launch_pre_layernorm(x, fold0 ? rows_g : rows, D, P + L.prew, P + L.preb, f.ln_eps, fold0 && c->split ? nullptr : x,
-                                                 fold0 ? xn16 : nullptr, fold0 && c->split ? xlo16 : nullptr, fold0 ? stats_p : nullptr,
-                                                 c->fp8 ? VH_DTYPE_FP8 : dt16, s, rows, fold0 ? c->guard_dev : nullptr, fold0 ? amax_guard : nullptr));
-            if ((rc = tmark(ST_PRELN))) return rc;
-            if ((rc = mark(ST_PRELN))) return rc;
+            if ((rc = stage(ST_PRELN, [&] {
+                     return launch_pre_layernorm(x, fold0 ? rows_g : rows, D, P + L.prew, P + L.preb, f.ln_eps, fold0 && c->split ? nullptr : x,
+                                                 fold0 ? xn16 : nullptr, fold0 && c->split ? xlo16 : nullptr, fold0 ? stats_p : nullptr, op_dt, s,
+                                                 rows, fold0 ? c->guard_dev : nullptr, fold0 ? amax_guard : nullptr);
+                 })))
+                return rc;
         } else if (c->ln_fold && nl > 0) {
             // layer 0's LN1 statistics: its input comes from the patch embedding, not from a RESID_LN epilogue
             // (fp8 path with the split residual: the patch embedding stays the bf16 fp32-out GEMM; this pass makes the planes)
-            if (c->split) HIPCHK(&c->err, launch_rowstats_split(x, rows_g, D, f.ln_eps, xn16, xlo16, stats_p, c->fp8 ? VH_DTYPE_FP8 : dt16, s, rows, amax_guard));
-            else HIPCHK(&c->err, launch_rowstats_cast(x, rows_g, D, f.ln_eps, xn16, stats_p, c->fp8 ? VH_DTYPE_FP8 : dt16, s, rows, amax_guard));
+            if (c->split) HIPCHK(&c->err, launch_rowstats_split(x, rows_g, D, f.ln_eps, xn16, xlo16, stats_p, op_dt, s, rows, amax_guard));
+            else HIPCHK(&c->err, launch_rowstats_cast(x, rows_g, D, f.ln_eps, xn16, stats_p, op_dt, s, rows, amax_guard));
             HIPCHK(&c->err, launch_ln_guard(stats_p, rows, c->guard_dev, s));   // real rows only (rows_g - rows are tile padding)
-            if ((rc = mark(ST_LNSTATS))) return rc;
+            if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
         }
     }
     // the class-token tail needs the split planes of the folded 16-bit path, the whole model, and room in the patch-matrix buffer
@@ -617,56 +620,50 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     const bool hd64 = c->head_dim == 64;
     const bool tail = c->cls_tail && hd64 && c->ln_fold && c->split && !c->fp8 && nl == f.layers && c->run_layers < 0 && T <= 1024 &&
                       (size_t)L.NP * L.KPA * esz >= 2 * ((size_t)D * esz + 256);
-    // tiled hidden activation: both MLP GEMMs must take the persistent form (whole 256-row tiles, enough of them), the 16-bit split path
-    const bool h_tiled = c->h_tiled && c->split && !c->fp8 && c->weights_ready_tiled && gemm_tiled_applies(rows_g, M, D) && gemm_tiled_applies(rows_g, D, M);
-    // e4m3 operands: the e4m3 hidden activation in the tiled layout of the e4m3 operand (fc1's epilogue writes it, fc2's DMA reads it)
-    const bool h_tiled8 = c->h_tiled && c->split && c->fp8 && c->weights_ready_tiled && gemm_tiled_applies_f8(rows_g, M, D) && gemm_tiled_applies_f8(rows_g, D, M);
-    // the attention output likewise (16-bit ring forms -> the out-projection's tiled operand DMA); VH_ATT_TILED=0 keeps it row-major
-    // (both 64-wide forms: any other head dim keeps q|k|v and the attention output row-major)
-    const bool att_tiled = hd64 && h_tiled && c->att_tiled && gemm_tiled_applies(rows_g, D, D) && attention_tiled_applies(batch, T, f.heads) && !tail;
-    const bool att_tiled8 = hd64 && h_tiled8 && c->att_tiled && gemm_tiled_applies_f8(rows_g, D, D) && attention_tiled_applies(batch, T, f.heads);
+    // tiled hidden activation (16-bit or e4m3, in the operand's own tiled layout: fc1's epilogue writes it, fc2's DMA reads it): both
+    // MLP GEMMs must take the persistent form (whole 256-row tiles, enough of them), the split path
+    const bool h_tiled = c->h_tiled && c->split && c->weights_ready_tiled && gemm_tiled_applies(rows_g, M, D, op_dt) && gemm_tiled_applies(rows_g, D, M, op_dt);
+    // the attention output likewise (ring forms -> the out-projection's tiled operand DMA); VH_ATT_TILED=0 keeps it row-major
+    // (both 64-wide forms: any other head dim keeps q|k|v and the attention output row-major; the class-token tail, a 16-bit path, too)
+    const bool att_tiled = hd64 && h_tiled && c->att_tiled && gemm_tiled_applies(rows_g, D, D, op_dt) && attention_tiled_applies(batch, T, f.heads) && !tail;
     // q|k|v head-major between the projection's epilogue and attention's operand DMA (same condition + the persistent form for N = 3 D)
-    const bool qkv_hm = hd64 && c->qkv_hm && ((att_tiled && gemm_tiled_applies(rows_g, 3 * D, D)) || (att_tiled8 && gemm_tiled_applies_f8(rows_g, 3 * D, D)));
-    c->last_h_tiled = (h_tiled || h_tiled8) && nl > 0 && c->ln_fold;
+    const bool qkv_hm = c->qkv_hm && att_tiled && gemm_tiled_applies(rows_g, 3 * D, D, op_dt);
+    c->last_h_tiled = h_tiled && nl > 0 && c->ln_fold;
     c->last_qkv_hm = qkv_hm && nl > 0 && c->ln_fold;
     for (int l = 0; l < nl && c->ln_fold; ++l) {
         const LayerOff& o = L.layer[l];
         const float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M);
         const int nblk = D / 64;
-        if ((rc = tmark(ST_QKV))) return rc;
+        // e4m3 operands: the weight matrices' per-output-channel scales
         const float *sq = c->fp8 ? c->sqkv[l] : nullptr, *so = c->fp8 ? c->so[l] : nullptr;
         const float *s1 = c->fp8 ? c->s1[l] : nullptr, *s2 = c->fp8 ? c->s2[l] : nullptr;
-        if (qkv_hm) {
-            GemmArgs gq{xn16, c->wqkv16[l], cd + 3 * D, qkv16, rows_g, 3 * D, D, VH_EPI_LNFOLD, cd, 0, c->fp8 ? VH_DTYPE_FP8 : dt16, 0};
-            gq.stats = stats_p; gq.out_tiled = 1; gq.wscale = sq;   // (e4m3 operands: the weight scales; null otherwise)
-            HIPCHK(&c->err, c->fp8 ? launch_gemm_fp8(gq, s) : launch_gemm(gq, s));
-        } else
-        HIPCHK(&c->err, gemm(xn16, c->wqkv16[l], cd + 3 * D, qkv16, rows_g, 3 * D, D, VH_EPI_LNFOLD, cd, 0, sq));
-        if ((rc = tmark(ST_QKV))) return rc;
-        if ((rc = mark(ST_QKV))) return rc;
+        GemmArgs gq = gemm_args(op_dt, xn16, c->wqkv16[l], cd + 3 * D, qkv16, rows_g, 3 * D, D, VH_EPI_LNFOLD, cd);
+        gq.wscale = sq;
+        set_tiled(gq, qkv_hm, false);
+        if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
         if (tail && l + 1 == nl) {
             // VH_FLAG_CLS_TAIL, last layer: only the class-token row of every image reaches the head, so attention runs for that
             // one query (all keys and values), and out-proj, fc1 and fc2 run on the `batch` class rows, gathered into compact
             // planes (the idle patch-matrix buffer).  Same kernels, same per-row arithmetic as the full layer, except the
             // attention row (a VALU kernel with another summation order): logits agree to rounding, not bitwise.
+            // (no stage bracket in this branch: the tail has no stage timing, only the profile events)
             char* const hc = col16;
             char* const lc = col16 + (((size_t)batch * D * esz + 255) & ~(size_t)255);
             HIPCHK(&c->err, launch_attention_cls(qkv16, batch, T, f.heads, att16, dt16, s));
             if ((rc = mark(ST_ATTN))) return rc;
             HIPCHK(&c->err, hipMemcpy2DAsync(hc, (size_t)D * esz, xn16, (size_t)T * D * esz, (size_t)D * esz, batch, hipMemcpyDeviceToDevice, s));
             HIPCHK(&c->err, hipMemcpy2DAsync(lc, (size_t)D, xlo16, (size_t)T * D, (size_t)D, batch, hipMemcpyDeviceToDevice, s));
-            GemmArgs gp{att16, c->wo16[l], P + o.ob, hc, batch, D, D, VH_EPI_RESID_SPLIT, nullptr, 0, dt16, 0};
-            gp.out16 = lc; gp.partials = partials_p;
+            GemmArgs gp = gemm_args(op_dt, att16, c->wo16[l], P + o.ob, hc, batch, D, D, VH_EPI_RESID_SPLIT);
+            gp.out16 = lc;
             HIPCHK(&c->err, launch_gemm(gp, s));
             if ((rc = mark(ST_PROJ))) return rc;
             HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, batch, D, f.ln_eps, stats_p, s, batch, c->guard_dev));
             if ((rc = mark(ST_LNSTATS))) return rc;
-            GemmArgs g1{hc, c->w1_16[l], cd + 6 * D + M, h16, batch, M, D, epi_fc1, cd + 6 * D, 0, dt16, 0};
-            g1.stats = stats_p;
+            const GemmArgs g1 = gemm_args(op_dt, hc, c->w1_16[l], cd + 6 * D + M, h16, batch, M, D, epi_fc1, cd + 6 * D);
             HIPCHK(&c->err, launch_gemm(g1, s));
             if ((rc = mark(ST_FC1))) return rc;
-            GemmArgs g2{h16, c->w2_16[l], P + o.f2b, hc, batch, D, M, VH_EPI_RESID_SPLIT, nullptr, 0, dt16, 0};
-            g2.out16 = lc; g2.partials = partials_p;
+            GemmArgs g2 = gemm_args(op_dt, h16, c->w2_16[l], P + o.f2b, hc, batch, D, M, VH_EPI_RESID_SPLIT);
+            g2.out16 = lc;
             HIPCHK(&c->err, launch_gemm(g2, s));
             if ((rc = mark(ST_FC2))) return rc;
             HIPCHK(&c->err, launch_layernorm_split(hc, lc, batch, D, D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, dt16, s));
@@ -676,74 +673,39 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
             c->last_batch = batch;
             return VH_OK;
         }
-        if ((rc = tmark(ST_ATTN))) return rc;
-        if (hd64)
-            HIPCHK(&c->err, launch_attention(qkv16, batch, T, f.heads, att16, c->fp8 ? VH_DTYPE_FP8 : dt16, tickets_part + l, s, true, att_tiled || att_tiled8,
-                                             qkv_hm ? (int64_t)rows_g : 0));
-        else
-            HIPCHK(&c->err, launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, c->fp8 ? VH_DTYPE_FP8 : dt16, s));
-        if ((rc = tmark(ST_ATTN))) return rc;
-        if ((rc = mark(ST_ATTN))) return rc;
-        if ((rc = tmark(ST_PROJ))) return rc;
-        if (att_tiled) {
-            GemmArgs go{att16, c->wot_16[l], P + o.ob, xn16, rows_g, D, D, VH_EPI_RESID_SPLIT, nullptr, 0, dt16, 0};
-            go.out16 = xlo16; go.partials = partials_p; go.ab_tiled = 1;
-            HIPCHK(&c->err, launch_gemm(go, s));
-        } else if (att_tiled8) {
-            GemmArgs go{att16, c->wot_16[l], P + o.ob, xn16, rows_g, D, D, VH_EPI_RESID_SPLIT, so, 0, VH_DTYPE_FP8, 0};   // (`aux` = the weight scales)
-            go.out16 = xlo16; go.partials = partials_p; go.ab_tiled = 1;
-            HIPCHK(&c->err, launch_gemm_fp8(go, s));
-        } else
-        if (c->split) HIPCHK(&c->err, gemm(att16, c->wo16[l], P + o.ob, xn16, rows_g, D, D, VH_EPI_RESID_SPLIT, nullptr, 0, so));
-        else HIPCHK(&c->err, gemm(att16, c->wo16[l], P + o.ob, x, rows_g, D, D, VH_EPI_RESID_LN, nullptr, 0, so));
-        if ((rc = tmark(ST_PROJ))) return rc;
-        if ((rc = mark(ST_PROJ))) return rc;
+        if ((rc = stage(ST_ATTN, [&] {
+                 return hd64 ? launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true, att_tiled, qkv_hm ? (int64_t)rows_g : 0)
+                             : launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, op_dt, s);
+             })))
+            return rc;
+        // out-projection and fc2 add to the residual.  Split: (out, out16) = its (hi, lo) planes; otherwise the fp32 x and, with RESID_LN,
+        // the operand copy of the updated rows.  A tiled A operand goes with the weights' tiled copy.
+        GemmArgs go = gemm_args(op_dt, att16, att_tiled ? c->wot_16[l] : c->wo16[l], P + o.ob, c->split ? (void*)xn16 : x, rows_g, D, D,
+                                c->split ? VH_EPI_RESID_SPLIT : VH_EPI_RESID_LN);
+        go.out16 = c->split ? xlo16 : xn16;
+        go.wscale = so;
+        set_tiled(go, false, att_tiled);
+        if ((rc = stage(ST_PROJ, [&] { return launch_gemm(go, s); }))) return rc;
         HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
-        if ((rc = mark(ST_LNSTATS))) return rc;
-        if ((rc = tmark(ST_FC1))) return rc;
-        if (h_tiled) {   // h in its tiled layout: written straight from fc1's registers, read by fc2's DMA (same values, same bits)
-            GemmArgs g1{xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D, 0, dt16, 0};
-            g1.stats = stats_p; g1.out_tiled = 1;
-            HIPCHK(&c->err, launch_gemm(g1, s));
-        } else if (h_tiled8) {
-            GemmArgs g1{xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D, 0, VH_DTYPE_FP8, 0};
-            g1.stats = stats_p; g1.wscale = s1; g1.out_tiled = 1;
-            HIPCHK(&c->err, launch_gemm_fp8(g1, s));
-        } else
-        HIPCHK(&c->err, gemm(xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D, 0, s1));
-        if ((rc = tmark(ST_FC1))) return rc;
-        if ((rc = mark(ST_FC1))) return rc;
-        if ((rc = tmark(ST_FC2))) return rc;
-        if (h_tiled) {
-            GemmArgs g2{h16, c->w2t_16[l], P + o.f2b, xn16, rows_g, D, M, VH_EPI_RESID_SPLIT, nullptr, 0, dt16, 0};
-            g2.out16 = xlo16; g2.partials = partials_p; g2.ab_tiled = 1;
-            HIPCHK(&c->err, launch_gemm(g2, s));
-        } else if (h_tiled8) {
-            GemmArgs g2{h16, c->w2t_16[l], P + o.f2b, xn16, rows_g, D, M, VH_EPI_RESID_SPLIT, s2, 0, VH_DTYPE_FP8, 0};   // (`aux` = the weight scales)
-            g2.out16 = xlo16; g2.partials = partials_p; g2.ab_tiled = 1;
-            HIPCHK(&c->err, launch_gemm_fp8(g2, s));
-        } else
-        if (c->split) HIPCHK(&c->err, gemm(h16, c->w2_16[l], P + o.f2b, xn16, rows_g, D, M, VH_EPI_RESID_SPLIT, nullptr, 0, s2));
-        else HIPCHK(&c->err, gemm(h16, c->w2_16[l], P + o.f2b, x, rows_g, D, M, l + 1 < nl ? VH_EPI_RESID_LN : VH_EPI_BIAS_RESID, nullptr, 0, s2));
-        if ((rc = tmark(ST_FC2))) return rc;
-        if ((rc = mark(ST_FC2))) return rc;
+        if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
+        // h in its tiled layout: written straight from fc1's registers, read by fc2's DMA (same values, same bits)
+        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D);
+        g1.wscale = s1;
+        set_tiled(g1, h_tiled, false);
+        if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
+        GemmArgs g2 = gemm_args(op_dt, h16, h_tiled ? c->w2t_16[l] : c->w2_16[l], P + o.f2b, c->split ? (void*)xn16 : x, rows_g, D, M,
+                                c->split ? VH_EPI_RESID_SPLIT : (l + 1 < nl ? VH_EPI_RESID_LN : VH_EPI_BIAS_RESID));
+        g2.out16 = c->split ? xlo16 : xn16;
+        g2.wscale = s2;
+        set_tiled(g2, false, h_tiled);
+        if ((rc = stage(ST_FC2, [&] { return launch_gemm(g2, s); }))) return rc;
         if (l + 1 < nl) {
             HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
-            if ((rc = mark(ST_LNSTATS))) return rc;
+            if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
         }
     }
     // ---- the plain layer loop (bf16 / fp16 / fp8 operands) -----------------------------------------------------
     const bool plain = !c->ln_fold;
-    const int op_dt = c->fp8 ? VH_DTYPE_FP8 : dt16;   // type of the GEMM A operands produced by LN / attention / fc1
-    auto gemm_any = [&](const void* a, const void* w, const float* bias, const float* scale, void* out, int N, int K, int epi,
-                        int tile_begin, int tile_count) {
-        GemmArgs g{a, w, bias, out, rows, N, K, epi, c->fp8 ? scale : nullptr, 0, op_dt, 0};
-        g.tile_begin = tile_begin;
-        g.tile_count = tile_count;
-        // a range of tiles exists in the one-tile-per-workgroup forms only: the persistent default (6) hands it to form 5
-        if ((tile_begin || tile_count) && !c->fp8) g.variant = gemm_pick_variant(rows, N, epi) == 7 ? 7 : 5;
-        return c->fp8 ? launch_gemm_fp8(g, s) : launch_gemm(g, s);
-    };
     auto ln_rows = [&](int64_t r_begin, int64_t r_count, const float* w, const float* b, hipStream_t st) {
         return launch_layernorm(x + r_begin * D, r_count, D, D, w, b, f.ln_eps, xn16 + r_begin * D * esz_op, op_dt, st);
     };
@@ -762,23 +724,25 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
             split = ntile / c->num_cu * c->num_cu;
             split -= split % tiles_n;
         }
+        GemmArgs g = gemm_args(op_dt, a, w, bias, x, rows, D, K, VH_EPI_BIAS_RESID);
+        g.wscale = scale;
         int r;
-        if ((r = tmark(st_gemm))) return r;
         if (!split) {
-            HIPCHK(&c->err, gemm_any(a, w, bias, scale, x, D, K, VH_EPI_BIAS_RESID, 0, 0));
-            if ((r = tmark(st_gemm))) return r;
-            if ((r = mark(st_gemm))) return r;
-            if (!lnw) return VH_OK;
-            if ((r = tmark(ST_LN))) return r;
-            HIPCHK(&c->err, ln_rows(0, rows, lnw, lnb, s));
-            if ((r = tmark(ST_LN))) return r;
-            return mark(ST_LN);
+            if ((r = stage(st_gemm, [&] { return launch_gemm(g, s); }))) return r;
+            return lnw ? stage(ST_LN, [&] { return ln_rows(0, rows, lnw, lnb, s); }) : VH_OK;
         }
+        // (no stage bracket: one pair of stage-timing events around the whole split sequence and no profile event -- !ev)
         ++c->tail_splits;
         const int64_t rows_a = (int64_t)(split / tiles_n) * 256;
-        HIPCHK(&c->err, gemm_any(a, w, bias, scale, x, D, K, VH_EPI_BIAS_RESID, 0, split));
+        // a range of tiles exists in the one-tile-per-workgroup forms only: where the default is the persistent form (6), form 5 runs it
+        g.variant = gemm_pp_variant(g.epilogue) == 7 ? 7 : 5;
+        if ((r = tmark(st_gemm))) return r;
+        g.tile_count = split;
+        HIPCHK(&c->err, launch_gemm(g, s));
         HIPCHK(&c->err, hipEventRecord(c->ev_tail_a, s));
-        HIPCHK(&c->err, gemm_any(a, w, bias, scale, x, D, K, VH_EPI_BIAS_RESID, split, ntile - split));
+        g.tile_begin = split;
+        g.tile_count = ntile - split;
+        HIPCHK(&c->err, launch_gemm(g, s));
         HIPCHK(&c->err, hipStreamWaitEvent(c->tstream, c->ev_tail_a, 0));
         HIPCHK(&c->err, ln_rows(0, rows_a, lnw, lnb, c->tstream));
         HIPCHK(&c->err, hipEventRecord(c->ev_tail_l, c->tstream));
@@ -788,29 +752,24 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     };
     if (plain && nl > 0) {
         const LayerOff& o0 = L.layer[0];
-        if ((rc = tmark(ST_LN))) return rc;
-        HIPCHK(&c->err, ln_rows(0, rows, P + o0.ln1w, P + o0.ln1b, s));
-        if ((rc = tmark(ST_LN))) return rc;
-        if ((rc = mark(ST_LN))) return rc;
+        if ((rc = stage(ST_LN, [&] { return ln_rows(0, rows, P + o0.ln1w, P + o0.ln1b, s); }))) return rc;
     }
     for (int l = 0; l < nl && plain; ++l) {
         const LayerOff& o = L.layer[l];
         const float *sq = c->fp8 ? c->sqkv[l] : nullptr, *so = c->fp8 ? c->so[l] : nullptr;
         const float *s1 = c->fp8 ? c->s1[l] : nullptr, *s2 = c->fp8 ? c->s2[l] : nullptr;
-        if ((rc = tmark(ST_QKV))) return rc;
-        HIPCHK(&c->err, gemm_any(xn16, c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, sq, qkv16, 3 * D, D, VH_EPI_BIAS, 0, 0));
-        if ((rc = tmark(ST_QKV))) return rc;
-        if ((rc = mark(ST_QKV))) return rc;
-        if ((rc = tmark(ST_ATTN))) return rc;
-        if (c->head_dim == 64) HIPCHK(&c->err, launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true));
-        else HIPCHK(&c->err, launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, op_dt, s));
-        if ((rc = tmark(ST_ATTN))) return rc;
-        if ((rc = mark(ST_ATTN))) return rc;
+        GemmArgs gq = gemm_args(op_dt, xn16, c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, qkv16, rows, 3 * D, D, VH_EPI_BIAS);
+        gq.wscale = sq;
+        if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
+        if ((rc = stage(ST_ATTN, [&] {
+                 return hd64 ? launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true)
+                             : launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, op_dt, s);
+             })))
+            return rc;
         if ((rc = resid_gemm_ln(att16, c->wo16[l], P + o.ob, so, D, P + o.ln2w, P + o.ln2b, ST_PROJ))) return rc;
-        if ((rc = tmark(ST_FC1))) return rc;
-        HIPCHK(&c->err, gemm_any(xn16, c->w1_16[l], P + o.f1b, s1, h16, M, D, epi_fc1_plain, 0, 0));
-        if ((rc = tmark(ST_FC1))) return rc;
-        if ((rc = mark(ST_FC1))) return rc;
+        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], P + o.f1b, h16, rows, M, D, epi_fc1_plain);
+        g1.wscale = s1;
+        if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
         const bool more = l + 1 < nl;   // the next layer's LN1 follows this layer's fc2
         if ((rc = resid_gemm_ln(h16, c->w2_16[l], P + o.f2b, s2, M, more ? P + L.layer[l + 1].ln1w : nullptr,
                                 more ? P + L.layer[l + 1].ln1b : nullptr, ST_FC2))) return rc;
@@ -2265,126 +2224,73 @@ int vh_debug_set_layers(vh_ctx* c, int n_layers) {
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
+// ---- the six GEMM taps.  Each fills a GemmArgs from its parameters; this one body checks (gemm_check: the reason, before a device
+// is touched), launches, synchronises and maps the error.  `tag` names the tap: in "<tag> failed", and in front of gemm_check's reason
+// for e4m3 operands.  `offered8`: the e4m3 epilogues the tap has parameters for, a bit per VH_EPI_* code (0: a 16-bit tap, which has
+// no scale parameter and refuses e4m3 operands).
+constexpr unsigned kEpiPlain8 = 1u << VH_EPI_BIAS | 1u << VH_EPI_BIAS_GELU | 1u << VH_EPI_BIAS_QGELU | 1u << VH_EPI_BIAS_RESID | 1u << VH_EPI_BIAS_F32;
+constexpr unsigned kEpiFold8 = 1u << VH_EPI_LNFOLD | 1u << VH_EPI_LNFOLD_GELU | 1u << VH_EPI_LNFOLD_QGELU | 1u << VH_EPI_RESID_LN | 1u << VH_EPI_RESID_SPLIT;
+static int op_gemm_run(const char* tag, const GemmArgs& g, unsigned offered8, void* stream) {
+    const bool f8 = g.dtype == VH_DTYPE_FP8;
+    GemmArgs h = g;
+    if (f8 && !offered8) h.dtype = -1;   // no dtype of a 16-bit tap: the 16-bit rules speak, "gemm: dtype" in its turn
+    // an epilogue the tap lacks: the operands and the shape are judged first, as for the plainest launch, then the epilogue is unsupported
+    const bool lacks = f8 && offered8 && (g.epilogue < 0 || g.epilogue > VH_EPI_LNFOLD_QGELU || !(offered8 >> g.epilogue & 1));
+    if (lacks) { h.epilogue = VH_EPI_BIAS; h.out_tiled = h.ab_tiled = h.tile_begin = h.tile_count = 0; }
+    if (const char* why = gemm_check(h))
+        return f8 && offered8 ? fail(nullptr, VH_ERR_INVALID, "%s%s", tag, strchr(why, ':')) : fail(nullptr, VH_ERR_INVALID, "%s", why);
+    if (lacks) return fail(nullptr, VH_ERR_UNSUPPORTED, "%s: epilogue %d not available", tag, g.epilogue);
+    hipError_t e = launch_gemm(g, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "%s failed: %s", tag, hipGetErrorString(e));
+    return VH_OK;
+}
 int vh_op_gemm(const void* a, const void* w, const float* bias, void* out, int64_t M, int N, int K, int epi,
                const float* aux, int aux_i, int dtype, int variant, void* stream) {
-    GemmArgs g{a, w, bias, out, M, N, K, epi, aux, aux_i, dtype, variant};
-    if (const char* why = gemm_check(g)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    OPCHK(launch_gemm(g, (hipStream_t)stream));
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return VH_OK;
-}
-int vh_op_gemm_fp8(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M, int N, int K,
-                   int epi, int variant, void* stream) {
-    if (variant != 0 && variant != 5 && variant != 6 && variant != 7) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8: variant must be 0, 5, 6 or 7");
-    if (!a8 || !w8 || !w_scale || !bias || !out) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8: null pointer");
-    if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 4) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8: need K %% 128 == 0 and N %% 4 == 0");
-    if (M > 0x7FFFFFFF / 2) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8: M too large");
-    if (epi != VH_EPI_BIAS && epi != VH_EPI_BIAS_GELU && epi != VH_EPI_BIAS_QGELU && epi != VH_EPI_BIAS_RESID && epi != VH_EPI_BIAS_F32)
-        return fail(nullptr, VH_ERR_UNSUPPORTED, "gemm_fp8: epilogue %d not available", epi);
-    GemmArgs g{a8, w8, bias, out, M, N, K, epi, w_scale, 0, VH_DTYPE_FP8, variant};
-    OPCHK(launch_gemm_fp8(g, (hipStream_t)stream));
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return VH_OK;
-}
-int vh_op_gemm_fp8_ex(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M, int N, int K,
-                      int epi, const float* c_dev, const float* stats, void* out16, float* partials, int variant, void* stream) {
-    if (variant != 0 && variant != 5 && variant != 6 && variant != 7) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: variant must be 0, 5, 6 or 7");
-    if (!a8 || !w8 || !w_scale || !bias || !out) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: null pointer");
-    if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 4) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: need K %% 128 == 0 and N %% 4 == 0");
-    if (M > 0x7FFFFFFF / 2) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: M too large");
-    const bool fold_act = epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU;
-    const bool fold = epi == VH_EPI_LNFOLD || fold_act, resid = epi == VH_EPI_RESID_LN || epi == VH_EPI_RESID_SPLIT;
-    if (!fold && !resid) return fail(nullptr, VH_ERR_UNSUPPORTED, "gemm_fp8_ex: epilogue %d not available", epi);
-    if (fold && (!c_dev || !stats)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: LNFOLD needs c and stats");
-    if (resid && (!out16 || !partials)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: RESID_* needs out16 and partials");
-    if ((resid || fold_act) && N % 256) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_ex: N %% 256 != 0");
-    GemmArgs g{a8, w8, bias, out, M, N, K, epi, fold ? c_dev : w_scale, 0, VH_DTYPE_FP8, variant};
-    if (fold) g.wscale = w_scale;
-    g.stats = stats; g.out16 = out16; g.partials = partials;
-    OPCHK(launch_gemm_fp8(g, (hipStream_t)stream));
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return VH_OK;
-}
-int vh_op_quantize_rows(const float* w, int rows, int cols, float post_scale, void* w8, float* scale, void* stream) {
-    if (!w || !w8 || !scale || rows <= 0 || cols <= 0 || cols % 4) return fail(nullptr, VH_ERR_INVALID, "quantize_rows: bad argument");
-    OPCHK(launch_quantize_rows(w, rows, cols, post_scale, w8, scale, (hipStream_t)stream));
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return VH_OK;
+    const GemmArgs g{a, w, bias, out, M, N, K, epi, aux, aux_i, dtype, variant};
+    return op_gemm_run("gemm", g, 0, stream);
 }
 int vh_op_gemm_ex(const void* a, const void* w, const float* bias, void* out, int64_t M, int N, int K, int epi,
                   const float* aux, int aux_i, const float* stats, void* out16, float* partials, int dtype, int variant,
                   void* stream) {
     GemmArgs g{a, w, bias, out, M, N, K, epi, aux, aux_i, dtype, variant};
     g.stats = stats; g.out16 = out16; g.partials = partials;
-    if (const char* why = gemm_check(g)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    OPCHK(launch_gemm(g, (hipStream_t)stream));
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return VH_OK;
+    return op_gemm_run("gemm_ex", g, 0, stream);
 }
-// ---- test taps: the GEMM's tiled / head-major layouts and tile ranges (GemmArgs::out_tiled, ab_tiled, tile_begin, tile_count) ----
-// What launch_pp (kernels_gemm5.hip) accepts, checked here with a reason and before a device is touched.  `tag` names the tap.
-static int gemm_layout_check(const char* tag, bool f8, int64_t M, int N, int K, int epi, int variant, int out_tiled, int ab_tiled,
-                             int tile_begin, int tile_count) {
-    const bool act = epi == VH_EPI_BIAS_GELU || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_BIAS_QGELU || epi == VH_EPI_LNFOLD_QGELU;
-    const bool fold = epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU;
-    if (out_tiled || ab_tiled) {
-        if (out_tiled && ab_tiled) return fail(nullptr, VH_ERR_INVALID, "%s: out_tiled and ab_tiled exclude each other", tag);
-        if (variant != 6) return fail(nullptr, VH_ERR_INVALID, "%s: the tiled layouts exist in the persistent form only (variant 6)", tag);
-        if (tile_begin || tile_count) return fail(nullptr, VH_ERR_INVALID, "%s: a tile range excludes the tiled layouts", tag);
-        if (M % 256 || N % 256) return fail(nullptr, VH_ERR_INVALID, "%s: the tiled layouts need M %% 256 == 0 and N %% 256 == 0", tag);
-        // K-tiles the persistent form demands: four where the LN-fold constants travel through LDS (every LN-fold epilogue
-        // but the e4m3-operand activation forms), two otherwise
-        const int nk = K / (f8 ? 128 : 64), need = fold && !(f8 && act) ? 4 : 2;
-        if (nk < need) return fail(nullptr, VH_ERR_INVALID, "%s: the tiled layouts need at least %d K-tiles with this epilogue", tag, need);
-        if (out_tiled && !(act || epi == VH_EPI_LNFOLD || (!f8 && epi == VH_EPI_BIAS)))
-            return fail(nullptr, VH_ERR_INVALID, "%s: out_tiled goes with the activation epilogues (tiled) or LNFOLD / 16-bit BIAS (head-major)", tag);
-        if (ab_tiled && !(epi == VH_EPI_RESID_SPLIT || (!f8 && epi == VH_EPI_BIAS)))
-            return fail(nullptr, VH_ERR_INVALID, "%s: ab_tiled goes with RESID_SPLIT or 16-bit BIAS", tag);
-    }
-    if (tile_begin < 0 || tile_count < 0) return fail(nullptr, VH_ERR_INVALID, "%s: negative tile range", tag);
-    if (tile_begin || tile_count) {
-        if (variant != 5 && variant != 7) return fail(nullptr, VH_ERR_INVALID, "%s: tile ranges exist in variants 5 and 7 only", tag);
-        if (!tile_count) return fail(nullptr, VH_ERR_INVALID, "%s: tile_begin != 0 needs tile_count > 0", tag);
-        const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
-        if ((int64_t)tile_begin + tile_count > tiles) return fail(nullptr, VH_ERR_INVALID, "%s: tile range beyond the %lld tiles", tag, (long long)tiles);
-    }
-    return VH_OK;
-}
+// test taps: the tiled / head-major layouts and tile ranges (GemmArgs::out_tiled, ab_tiled, tile_begin, tile_count)
 int vh_op_gemm_layout(const void* a, const void* w, const float* bias, void* out, int64_t M, int N, int K, int epi,
                       const float* aux, int aux_i, const float* stats, void* out16, float* partials, int dtype, int variant,
                       int out_tiled, int ab_tiled, int tile_begin, int tile_count, void* stream) {
     GemmArgs g{a, w, bias, out, M, N, K, epi, aux, aux_i, dtype, variant};
     g.stats = stats; g.out16 = out16; g.partials = partials;
-    if (const char* why = gemm_check(g)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    if (int rc = gemm_layout_check("gemm_layout", false, M, N, K, epi, variant, out_tiled, ab_tiled, tile_begin, tile_count)) return rc;
     g.out_tiled = out_tiled; g.ab_tiled = ab_tiled; g.tile_begin = tile_begin; g.tile_count = tile_count;
-    hipError_t e = launch_gemm(g, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "gemm_layout failed: %s", hipGetErrorString(e));
-    return VH_OK;
+    return op_gemm_run("gemm_layout", g, 0, stream);
+}
+// e4m3 operands: w_scale = the per-output-channel weight scales (GemmArgs::wscale), c_dev = the LNFOLD* epilogues' c_n (`aux`)
+int vh_op_gemm_fp8(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M, int N, int K,
+                   int epi, int variant, void* stream) {
+    GemmArgs g{a8, w8, bias, out, M, N, K, epi, nullptr, 0, VH_DTYPE_FP8, variant};
+    g.wscale = w_scale;
+    return op_gemm_run("gemm_fp8", g, kEpiPlain8, stream);
+}
+int vh_op_gemm_fp8_ex(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M, int N, int K,
+                      int epi, const float* c_dev, const float* stats, void* out16, float* partials, int variant, void* stream) {
+    GemmArgs g{a8, w8, bias, out, M, N, K, epi, c_dev, 0, VH_DTYPE_FP8, variant};
+    g.wscale = w_scale; g.stats = stats; g.out16 = out16; g.partials = partials;
+    return op_gemm_run("gemm_fp8_ex", g, kEpiFold8, stream);
 }
 int vh_op_gemm_fp8_layout(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M, int N, int K,
                           int epi, const float* c_dev, const float* stats, void* out16, float* partials, int variant,
                           int out_tiled, int ab_tiled, int tile_begin, int tile_count, void* stream) {
-    if (variant != 0 && variant != 5 && variant != 6 && variant != 7) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: variant must be 0, 5, 6 or 7");
-    if (!a8 || !w8 || !w_scale || !bias || !out) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: null pointer");
-    if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 4) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: need K %% 128 == 0 and N %% 4 == 0");
-    if (M > 0x7FFFFFFF / 2) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: M too large");
-    const bool fold_act = epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU;
-    const bool fold = epi == VH_EPI_LNFOLD || fold_act, resid = epi == VH_EPI_RESID_LN || epi == VH_EPI_RESID_SPLIT;
-    const bool plain = epi == VH_EPI_BIAS || epi == VH_EPI_BIAS_GELU || epi == VH_EPI_BIAS_QGELU || epi == VH_EPI_BIAS_RESID || epi == VH_EPI_BIAS_F32;
-    if (!fold && !resid && !plain) return fail(nullptr, VH_ERR_UNSUPPORTED, "gemm_fp8_layout: epilogue %d not available", epi);
-    if (fold && (!c_dev || !stats)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: LNFOLD needs c and stats");
-    if (resid && (!out16 || !partials)) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: RESID_* needs out16 and partials");
-    if ((resid || fold_act) && N % 256) return fail(nullptr, VH_ERR_INVALID, "gemm_fp8_layout: N %% 256 != 0");
-    if (int rc = gemm_layout_check("gemm_fp8_layout", true, M, N, K, epi, variant, out_tiled, ab_tiled, tile_begin, tile_count)) return rc;
-    GemmArgs g{a8, w8, bias, out, M, N, K, epi, fold ? c_dev : w_scale, 0, VH_DTYPE_FP8, variant};
-    if (fold) g.wscale = w_scale;
-    g.stats = stats; g.out16 = out16; g.partials = partials;
+    GemmArgs g{a8, w8, bias, out, M, N, K, epi, c_dev, 0, VH_DTYPE_FP8, variant};
+    g.wscale = w_scale; g.stats = stats; g.out16 = out16; g.partials = partials;
     g.out_tiled = out_tiled; g.ab_tiled = ab_tiled; g.tile_begin = tile_begin; g.tile_count = tile_count;
-    hipError_t e = launch_gemm_fp8(g, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "gemm_fp8_layout failed: %s", hipGetErrorString(e));
+    return op_gemm_run("gemm_fp8_layout", g, kEpiPlain8 | kEpiFold8, stream);
+}
+int vh_op_quantize_rows(const float* w, int rows, int cols, float post_scale, void* w8, float* scale, void* stream) {
+    if (!w || !w8 || !scale || rows <= 0 || cols <= 0 || cols % 4) return fail(nullptr, VH_ERR_INVALID, "quantize_rows: bad argument");
+    OPCHK(launch_quantize_rows(w, rows, cols, post_scale, w8, scale, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_op_tile_rows(const void* in, int rows, int cols, void* out, int dtype, void* stream) {
