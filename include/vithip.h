@@ -232,6 +232,33 @@ int vh_get_input_norm(const vh_ctx* ctx, float* scale, float* shift);
 int vh_forward_u8(vh_ctx* ctx, const uint8_t* in_nhwc_host, int batch, float* logits_host);
 int vh_forward_device_u8(vh_ctx* ctx, const uint8_t* in_nhwc_dev, int batch, float* logits_dev);
 int vh_forward_device_u8_async(vh_ctx* ctx, const uint8_t* in_nhwc_dev, int batch, float* logits_dev, int steps);
+/* ---- Image tensors ------------------------------------------------------------------------------------------------
+ * The image batch as PyTorch, ONNX, torchvision and rocJPEG hold it, taken as it is.  An image tensor is DENSE and has one
+ * ELEMENT TYPE and one LAYOUT (S = image_size, C = channels):
+ *       VH_ELEM_F32, VH_ELEM_F16, VH_ELEM_BF16, VH_ELEM_U8       4, 2, 2, 1 bytes per element
+ *       VH_LAYOUT_NHWC  [batch][S][S][C]                          VH_LAYOUT_NCHW  [batch][C][S][S]
+ * CONTRACT: element (b, y, x, c) enters the model as the fp32 value v,
+ *       F32          the element itself;
+ *       F16 / BF16   the element widened exactly (no rounding; infinities, signed zeros and subnormals kept);
+ *       U8           fmaf((float)p, scale[c], shift[c]) with the context's vh_set_input_norm state, as on the 8-bit path;
+ * and v is then rounded to the MFMA operand type exactly as an fp32 input is.  Float elements are taken as already
+ * normalised: vh_set_input_norm does not touch them.  The logits are therefore BIT-IDENTICAL to vh_forward of the NHWC fp32
+ * array of v, on every path (folded, plain, split, fp8, pre-LN, any patch size and head dim, VH_FLAG_CLS_TAIL, graphs,
+ * streams): only the gather in front of the patch GEMM looks at the element type and the layout.  (NHWC, F32) and (NHWC, U8)
+ * are vh_forward and vh_forward_u8.  VH_PATCH_FUSED=1 contexts run the ordinary gather + patch GEMM for these inputs, as they
+ * do for u8.
+ *   vh_forward_tensor, vh_forward_device_tensor, vh_forward_device_tensor_async: vh_forward, vh_forward_device and
+ *                       vh_forward_device_async under the contract above.  VH_ERR_INVALID for an unknown elem or layout, a
+ *                       null pointer, a batch outside 1..max_batch, or a device input pointer that is not 16-byte aligned. */
+#define VH_ELEM_F32 0
+#define VH_ELEM_F16 1
+#define VH_ELEM_BF16 2
+#define VH_ELEM_U8 3
+#define VH_LAYOUT_NHWC 0
+#define VH_LAYOUT_NCHW 1
+int vh_forward_tensor(vh_ctx* ctx, const void* in_host, int elem, int layout, int batch, float* logits_host);
+int vh_forward_device_tensor(vh_ctx* ctx, const void* in_dev, int elem, int layout, int batch, float* logits_dev);
+int vh_forward_device_tensor_async(vh_ctx* ctx, const void* in_dev, int elem, int layout, int batch, float* logits_dev, int steps);
 /* ---- 8-bit frames: antialiased resize + crop on the GPU in front of the u8 forward -----------------------------------
  * What a decoder or a camera emits is not image x image.  A FRAME is 8-bit interleaved pixels, height x width x channels
  * (channels = the context's), rows row_stride bytes apart, starting `offset` bytes into the buffer of the call.  A BOX
@@ -585,7 +612,7 @@ int vh_ring_submit_u8(vh_ctx* ctx, const uint8_t* in_nhwc_host, int batch);
  * its capacity (= slot_bytes).  vh_ring_submit_frames: frames_host NULL (or the slot's own buffer) = filled in place;
  * nbytes <= slot_bytes; the descriptors are checked and copied before anything is enqueued, and a refused submit leaves
  * the ring as it was.  A collected batch has the bits vh_forward_frames_u8 returns.  vh_ring_collect, vh_ring_free_slots
- * and vh_ring_destroy serve this kind too; the input and submit calls of the other two kinds return VH_ERR_STATE on a
+ * and vh_ring_destroy serve this kind too; the input and submit calls of the other kinds return VH_ERR_STATE on a
  * frames ring, and the frames calls return VH_ERR_STATE on the other kinds. */
 int vh_ring_create_frames(vh_ctx* ctx, int slots, int batch_per_slot, size_t slot_bytes);
 int vh_ring_input_frames(vh_ctx* ctx, uint8_t** pinned, size_t* capacity);
@@ -593,30 +620,39 @@ int vh_ring_submit_frames(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes
 /* NV12 frames ("NV12 frames" above) on the SAME frames ring: a slot is raw bytes, so one ring takes vh_ring_submit_frames and
  * vh_ring_submit_frames_nv12 interleaved; vh_ring_input_frames and vh_ring_collect are unchanged.  The context must have
  * channels == 3.  Checked and copied before anything is enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on
- * the other two kinds of ring.  A collected batch has the bits vh_forward_frames_nv12 returns. */
+ * the other kinds of ring.  A collected batch has the bits vh_forward_frames_nv12 returns. */
 int vh_ring_submit_frames_nv12(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch);
 /* Planar YUV frames ("Planar YUV frames" above) on the SAME frames ring: RGB, NV12 and planar submits interleave on one ring.
  * The context must have channels == 3.  Checked and copied before anything is enqueued; a refused submit leaves the ring as it
- * was; VH_ERR_STATE on the other two kinds of ring.  A collected batch has the bits vh_forward_frames_yuv returns. */
+ * was; VH_ERR_STATE on the other kinds of ring.  A collected batch has the bits vh_forward_frames_yuv returns. */
 int vh_ring_submit_frames_yuv(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch);
 /* 16-bit YUV frames ("16-bit YUV frames" above) on the SAME frames ring: RGB, NV12, planar, P016 and planar 16-bit submits
  * interleave on one ring; the 16-bit ones use the second colour state.  The same rules: checked and copied before anything is
- * enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other two kinds of ring.  A collected batch has the
+ * enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other kinds of ring.  A collected batch has the
  * bits vh_forward_frames_p016 / vh_forward_frames_yuv16 returns. */
 int vh_ring_submit_frames_p016(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_nv12* desc, int batch);
 int vh_ring_submit_frames_yuv16(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuv* desc, int batch);
 /* Packed 4:2:2 frames ("Packed 4:2:2 frames" above) on the SAME frames ring, interleaved with every other kind of submit; _yuy2
  * uses the first colour state, _y210 (Y210 / Y216 / v210) the second.  The same rules: checked and copied before anything is
- * enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other two kinds of ring.  A collected batch has the
+ * enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other kinds of ring.  A collected batch has the
  * bits vh_forward_frames_yuy2 / vh_forward_frames_y210 returns. */
 int vh_ring_submit_frames_yuy2(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch);
 int vh_ring_submit_frames_y210(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_yuy2* desc, int batch);
 /* Packed 4:4:4 frames ("Packed 4:4:4 frames" above) on the SAME frames ring, interleaved with every other kind of submit; _bgra
  * uses the first colour state (YUV layouts; RGB layouts use none), _y410 (Y416 / AYUV64 / Y410 / V410) the second.  The same rules:
- * checked and copied before anything is enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other two kinds
+ * checked and copied before anything is enqueued; a refused submit leaves the ring as it was; VH_ERR_STATE on the other kinds
  * of ring.  A collected batch has the bits vh_forward_frames_bgra / vh_forward_frames_y410 returns. */
 int vh_ring_submit_frames_bgra(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch);
 int vh_ring_submit_frames_y410(vh_ctx* ctx, const uint8_t* frames_host, size_t nbytes, const vh_frame_bgra* desc, int batch);
+/* The same ring with slots that stage IMAGE TENSORS ("Image tensors" above) of ONE element type and layout, fixed when the ring
+ * is created: a slot holds batch_per_slot * S * S * C * sizeof(element) bytes of pinned and of device memory.
+ * vh_ring_input_tensor: the pinned buffer the next submit uploads and its capacity in bytes.  vh_ring_submit_tensor: in_host
+ * NULL (or the slot's own buffer) = filled in place.  A collected batch has the bits vh_forward_tensor returns.
+ * vh_ring_collect, vh_ring_free_slots and vh_ring_destroy serve this kind too; the input and submit calls of the other three
+ * kinds return VH_ERR_STATE on a tensor ring, and the tensor calls return VH_ERR_STATE on the other kinds. */
+int vh_ring_create_tensor(vh_ctx* ctx, int slots, int batch_per_slot, int elem, int layout);
+int vh_ring_input_tensor(vh_ctx* ctx, void** pinned, size_t* capacity_bytes);
+int vh_ring_submit_tensor(vh_ctx* ctx, const void* in_host, int batch);
 
 /* hipGraph replay.  With enable != 0 the launch sequence of a forward is captured once per (input pointer, logits
  * pointer, batch) and replayed with hipGraphLaunch; the first forward at a given batch size still runs eagerly.
@@ -823,6 +859,14 @@ int vh_op_im2col_padded(const float* in_nhwc_dev, int batch, int image, int patc
  * arrays [channels], finite; in_nhwc_dev 16-byte aligned (else VH_ERR_INVALID). */
 int vh_op_im2col_u8(const uint8_t* in_nhwc_dev, int batch, int image, int patch, int channels, int kpad,
                     const float* scale_host, const float* shift_host, void* out16_dev, int dtype, void* stream);
+/* The patch gather of the tensor entry points on its own ("Image tensors"): in_dev of elem VH_ELEM_* and layout VH_LAYOUT_* ->
+ * patch matrix [batch*np, kpad] in `dtype` (VH_DTYPE_BF16 or VH_DTYPE_FP16): the bits vh_op_im2col_padded gives for the NHWC
+ * fp32 array of the contract's values v; columns patch*patch*channels .. kpad-1 zero.  Any patch <= 256 and channels <= 64, kpad
+ * >= patch*patch*channels and a multiple of 8; scale_host / shift_host: HOST arrays [channels], finite, read for VH_ELEM_U8
+ * only (may be NULL otherwise); in_dev 16-byte aligned (else VH_ERR_INVALID).  Every argument is checked before a device is
+ * touched. */
+int vh_op_im2col_tensor(const void* in_dev, int elem, int layout, int batch, int image, int patch, int channels, int kpad,
+                        const float* scale_host, const float* shift_host, void* out16_dev, int dtype, void* stream);
 /* The resize of the frames entry points on its own ("8-bit frames"): frames_dev (any alignment, any offsets) ->
  * out_u8_dev [batch][out_size][out_size][channels] bytes.  desc_host: HOST array [batch]; channels 1..64, out_size
  * 1..4096.  Allocates and frees its table buffer: a test and measurement tap, not a hot path. */

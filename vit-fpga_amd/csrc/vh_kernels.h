@@ -111,6 +111,13 @@ hipError_t launch_im2col(const float* in_nhwc, int batch, int image, int patch, 
 constexpr int kMaxChannels = 64;
 hipError_t launch_im2col_u8(const uint8_t* in_nhwc, int batch, int image, int patch, int channels, int kpad,
                             const float* scale, const float* shift, void* out16, int dtype, hipStream_t stream);
+// The same patch matrix from an image TENSOR (kernels_gather.hip; contract: vithip.h, "Image tensors"): elem VH_ELEM_*, layout
+// VH_LAYOUT_*; the bits launch_im2col gives for the NHWC fp32 array of the widened (u8: normalised) elements.  (NHWC, F32) and
+// (NHWC, U8) ARE launch_im2col / launch_im2col_u8; NHWC 16-bit floats take the padded gather with a 16-bit source, NCHW a
+// gather that transposes (x, c) through LDS.  scale / shift: host arrays [channels], read for VH_ELEM_U8 only.
+// hipErrorInvalidValue for an unknown elem / layout / dtype, a null pointer or a shape the other two launches refuse.
+hipError_t launch_im2col_tensor(const void* in, int elem, int layout, int batch, int image, int patch, int channels, int kpad,
+                                const float* scale, const float* shift, void* out16, int dtype, hipStream_t stream);
 // Antialiased resize + crop of 8-bit interleaved frames to S x S (kernels_resize.hip; contract: vithip.h, "8-bit frames").
 // resize_axis_table: the table of one axis (host, double, one rounding to fp32; weights [n_out][max_taps], zero padded); 0 = ok.
 // resize_plan_build: checks every descriptor and fills `words` with [batch x 16-word frame record][tables] as the kernel reads

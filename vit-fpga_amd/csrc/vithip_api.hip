@@ -157,15 +157,20 @@ const char* kStageNames[ST_COUNT] = {"im2col", "patch_gemm", "cls_rows", "layern
 
 }  // namespace
 
-// The images of one forward: fp32 NHWC values the caller has normalised, or 8-bit NHWC pixels that the im2col kernel
-// normalises (im2col_u8_kernel).  Only the im2col call site of enqueue_forward looks at the kind.
+// The images of one forward: a dense tensor of one element type (VH_ELEM_*: floats the caller has normalised, or 8-bit pixels
+// that the gather normalises) in one layout (VH_LAYOUT_*).  Only the im2col call site of enqueue_forward looks at the kind.
 struct ImgIn {
     const void* p;
-    bool u8;
-    size_t elem() const { return u8 ? 1 : 4; }
-    ImgIn skip(size_t elements) const { return ImgIn{(const char*)p + elements * elem(), u8}; }
-    bool operator==(const ImgIn& o) const { return p == o.p && u8 == o.u8; }
+    int kind = VH_ELEM_F32;      // VH_ELEM_*
+    int layout = VH_LAYOUT_NHWC; // VH_LAYOUT_*
+    bool u8() const { return kind == VH_ELEM_U8; }
+    bool nhwc_f32() const { return kind == VH_ELEM_F32 && layout == VH_LAYOUT_NHWC; }
+    size_t elem() const { return kind == VH_ELEM_F32 ? 4 : kind == VH_ELEM_U8 ? 1 : 2; }
+    // the same kind of tensor `elements` further on: a whole number of images (the batch split), hence right for both layouts
+    ImgIn skip(size_t elements) const { return ImgIn{(const char*)p + elements * elem(), kind, layout}; }
+    bool operator==(const ImgIn& o) const { return p == o.p && kind == o.kind && layout == o.layout; }
 };
+constexpr int kU8 = VH_ELEM_U8;   // ImgIn{p, kU8}: NHWC bytes, the 8-bit entry points and the resized frames
 
 struct vh_ctx {
     vh_config cfg;
@@ -272,8 +277,10 @@ struct vh_ctx {
     std::vector<RingSlot> ring;
     // what the slots stage: fp32 images, 8-bit images (a quarter of the pinned and device memory), or 8-bit frames of any size
     // (ring_slot_bytes each; resized on the context's stream in front of the forward)
-    enum RingKind { RING_F32, RING_U8, RING_FRAMES };
+    // or image tensors of one element type and layout (ring_elem, ring_layout; slots sized by the element type)
+    enum RingKind { RING_F32, RING_U8, RING_FRAMES, RING_TENSOR };
     RingKind ring_kind = RING_F32;
+    int ring_elem = VH_ELEM_F32, ring_layout = VH_LAYOUT_NHWC;   // what a slot holds: fixed by the kind, chosen for RING_TENSOR
     size_t ring_slot_bytes = 0;
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     int ring_batch = 0, ring_wr = 0, ring_rd = 0, ring_used = 0;
@@ -561,15 +568,18 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     const int epi_fc1_plain = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_BIAS_QGELU : VH_EPI_BIAS_GELU;       // plain layer loop
     // the patch embedding lands directly in the split residual's planes (below): the 16-bit split path without a pre-LayerNorm
     const bool patch_split = c->split && !c->fp8 && nl > 0 && !pre_ln;
-    // 8-bit images: always the im2col pass (which normalises) + the ordinary patch GEMM; the fused loader reads fp32 only
-    const bool fused_patch = patch_split && !in.u8 && c->patch_fused && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
+    // 8-bit images and every other tensor kind: always the im2col pass + the ordinary patch GEMM; the fused loader reads NHWC fp32 only
+    const bool fused_patch = patch_split && in.nhwc_f32() && c->patch_fused && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
     if (!fused_patch) {   // (no stage bracket: the profile event is recorded with or without the pass)
         if ((rc = tmark(ST_IM2COL))) return rc;
-        if (in.u8)
+        if (in.layout == VH_LAYOUT_NHWC && in.u8())
             HIPCHK(&c->err, launch_im2col_u8((const uint8_t*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale, c->in_shift,
                                              col16, dt16, s));
-        else
+        else if (in.nhwc_f32())
             HIPCHK(&c->err, launch_im2col((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
+        else   // every other (element type, layout): kernels_gather.hip
+            HIPCHK(&c->err, launch_im2col_tensor(in.p, in.kind, in.layout, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale,
+                                                 c->in_shift, col16, dt16, s));
         if ((rc = tmark(ST_IM2COL))) return rc;
     }
     if ((rc = mark(ST_IM2COL))) return rc;
@@ -894,7 +904,7 @@ int guard_calibrate(vh_ctx* c) {
     HIPCHK(&c->err, launch_fill(c->in_dev, n, 0xCA11B8A7Eull, TID_IMAGES, 0, 0.f, 0.f, c->stream));
     const int keep_stage = c->timing_stage;
     c->timing_stage = -1;
-    const int rc = enqueue_step(c, ImgIn{c->in_dev, false}, 1, c->logits_dev);
+    const int rc = enqueue_step(c, ImgIn{c->in_dev}, 1, c->logits_dev);
     c->timing_stage = keep_stage;
     if (rc) return rc;
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
@@ -907,6 +917,18 @@ int check_forward_args(vh_ctx* c, const void* in, int batch, const void* out) {
     if (batch <= 0 || batch > c->cfg.max_batch)
         return fail(&c->err, VH_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->cfg.max_batch);
     if (!c->weights_ready) return fail(&c->err, VH_ERR_STATE, "forward before weights were loaded");
+    return VH_OK;
+}
+
+// elem / layout of the tensor entry points
+int check_tensor_kind(std::string* err, int elem, int layout) {
+    if (elem < VH_ELEM_F32 || elem > VH_ELEM_U8) return fail(err, VH_ERR_INVALID, "unknown elem %d (VH_ELEM_F32 .. VH_ELEM_U8 = 0..3)", elem);
+    if (layout != VH_LAYOUT_NHWC && layout != VH_LAYOUT_NCHW) return fail(err, VH_ERR_INVALID, "unknown layout %d (VH_LAYOUT_NHWC = 0, VH_LAYOUT_NCHW = 1)", layout);
+    return VH_OK;
+}
+
+int check_tensor_ptr(vh_ctx* c, const void* in_dev) {
+    if ((uintptr_t)in_dev & 15) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "tensor device input %p is not 16-byte aligned", in_dev);
     return VH_OK;
 }
 
@@ -1112,7 +1134,7 @@ int forward_host(vh_ctx* c, ImgIn in_host, int batch, float* logits_host, const 
     const auto t0 = std::chrono::high_resolution_clock::now();
     HIPCHK(&c->err, hipSetDevice(c->device));
     const size_t in_bytes = job ? frame_bytes : (size_t)batch * f.image_size * f.image_size * f.channels * in_host.elem();
-    const ImgIn staged = job ? ImgIn{c->rz_u8, true} : ImgIn{c->in_dev, in_host.u8};
+    const ImgIn staged = job ? ImgIn{c->rz_u8, kU8} : ImgIn{c->in_dev, in_host.kind, in_host.layout};
     HIPCHK(&c->err, hipMemcpyAsync(job ? (void*)c->rz_frames : (void*)c->in_dev, in_host.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     rc = forward_device_async(c, staged, batch, c->logits_dev, 1, job);
     if (rc) return rc;
@@ -1619,12 +1641,12 @@ int vh_export_weights_device(vh_ctx* c, void* dev_blob, size_t nbytes) {
 }
 
 int vh_forward_device_async(vh_ctx* c, const float* in, int batch, float* logits, int steps) {
-    return forward_device_async(c, ImgIn{in, false}, batch, logits, steps);
+    return forward_device_async(c, ImgIn{in}, batch, logits, steps);
 }
 
 int vh_forward_device_u8_async(vh_ctx* c, const uint8_t* in, int batch, float* logits, int steps) {
     if (int rc = check_u8_ptr(c, in)) return rc;
-    return forward_device_async(c, ImgIn{in, true}, batch, logits, steps);
+    return forward_device_async(c, ImgIn{in, kU8}, batch, logits, steps);
 }
 
 int vh_synchronize(vh_ctx* c) {
@@ -1637,16 +1659,32 @@ int vh_synchronize(vh_ctx* c) {
     return VH_OK;
 }
 
-int vh_forward_device(vh_ctx* c, const float* in, int batch, float* logits) { return forward_device(c, ImgIn{in, false}, batch, logits); }
+int vh_forward_device(vh_ctx* c, const float* in, int batch, float* logits) { return forward_device(c, ImgIn{in}, batch, logits); }
 
 int vh_forward_device_u8(vh_ctx* c, const uint8_t* in, int batch, float* logits) {
     if (int rc = check_u8_ptr(c, in)) return rc;
-    return forward_device(c, ImgIn{in, true}, batch, logits);
+    return forward_device(c, ImgIn{in, kU8}, batch, logits);
 }
 
-int vh_forward(vh_ctx* c, const float* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host, false}, batch, logits_host); }
+int vh_forward(vh_ctx* c, const float* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host}, batch, logits_host); }
 
-int vh_forward_u8(vh_ctx* c, const uint8_t* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host, true}, batch, logits_host); }
+int vh_forward_u8(vh_ctx* c, const uint8_t* in_host, int batch, float* logits_host) { return forward_host(c, ImgIn{in_host, kU8}, batch, logits_host); }
+
+// Image tensors: the forward entry points for any (element type, layout)
+int vh_forward_device_tensor_async(vh_ctx* c, const void* in, int elem, int layout, int batch, float* logits, int steps) {
+    if (int rc = check_tensor_kind(c ? &c->err : nullptr, elem, layout)) return rc;
+    if (int rc = check_tensor_ptr(c, in)) return rc;
+    return forward_device_async(c, ImgIn{in, elem, layout}, batch, logits, steps);
+}
+int vh_forward_device_tensor(vh_ctx* c, const void* in, int elem, int layout, int batch, float* logits) {
+    if (int rc = check_tensor_kind(c ? &c->err : nullptr, elem, layout)) return rc;
+    if (int rc = check_tensor_ptr(c, in)) return rc;
+    return forward_device(c, ImgIn{in, elem, layout}, batch, logits);
+}
+int vh_forward_tensor(vh_ctx* c, const void* in_host, int elem, int layout, int batch, float* logits_host) {
+    if (int rc = check_tensor_kind(c ? &c->err : nullptr, elem, layout)) return rc;
+    return forward_host(c, ImgIn{in_host, elem, layout}, batch, logits_host);
+}
 
 // Frames of any format: check + plan on the host (nothing enqueued on a refusal), then resize -> u8 forward on the context's stream.
 // The plan sees the device address, because the alignment of the frames decides which loads the kernel may use.
@@ -1660,7 +1698,7 @@ static int forward_frames_device(vh_ctx* c, const FrameFormat& fmt, const uint8_
     if ((rc = frames_reserve(c, c->rz_words.size(), true, 0))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
     const FrameJob job{fmt, frames_dev, c->rz_plan_host, c->rz_words.size(), max_tiles};
-    return forward_device(c, ImgIn{c->rz_u8, true}, batch, logits_dev, &job);
+    return forward_device(c, ImgIn{c->rz_u8, kU8}, batch, logits_dev, &job);
 }
 
 // the same from host memory: the frames are staged in c->rz_frames, whose base (hipMalloc) is aligned for any sample: base 0
@@ -1674,7 +1712,7 @@ static int forward_frames_host(vh_ctx* c, const FrameFormat& fmt, const uint8_t*
     if ((rc = frames_reserve(c, c->rz_words.size(), true, nbytes))) return rc;
     memcpy(c->rz_plan_host, c->rz_words.data(), c->rz_words.size() * 4);
     const FrameJob job{fmt, c->rz_frames, c->rz_plan_host, c->rz_words.size(), max_tiles};
-    return forward_host(c, ImgIn{frames_host, true}, batch, logits_host, &job, nbytes);
+    return forward_host(c, ImgIn{frames_host, kU8}, batch, logits_host, &job, nbytes);
 }
 
 // 8-bit interleaved frames (kernels_resize.hip)
@@ -1853,7 +1891,7 @@ int vh_profile_forward(vh_ctx* c, const float* in, int batch, float* logits, dou
     if (!stage_ms || n_slots < 2 * kProfiledStages) return fail(&c->err, VH_ERR_INVALID, "need %d stage slots (ms then launch counts)", 2 * kProfiledStages);
     HIPCHK(&c->err, hipSetDevice(c->device));
     std::vector<std::pair<int, hipEvent_t>> ev;
-    rc = enqueue_forward(c, ImgIn{in, false}, batch, logits, &ev, c->stream, 0);
+    rc = enqueue_forward(c, ImgIn{in}, batch, logits, &ev, c->stream, 0);
     if (!rc) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) rc = fail(&c->err, VH_ERR_HIP, "sync: %s", hipGetErrorString(e)); }
     for (int i = 0; i < 2 * kProfiledStages; ++i) stage_ms[i] = 0.0;
     if (!rc)
@@ -1898,13 +1936,19 @@ int vh_ring_destroy(vh_ctx* c) {
     c->copy_in = c->copy_out = nullptr;
     c->ring_batch = c->ring_wr = c->ring_rd = c->ring_used = 0;
     c->ring_kind = vh_ctx::RING_F32;
+    c->ring_elem = VH_ELEM_F32;
+    c->ring_layout = VH_LAYOUT_NHWC;
     c->ring_slot_bytes = 0;
     return VH_OK;
 }
 
-static const char* ring_kind_name(vh_ctx::RingKind k) { return k == vh_ctx::RING_FRAMES ? "8-bit frames" : k == vh_ctx::RING_U8 ? "8-bit images" : "fp32 images"; }
+static const char* ring_kind_name(vh_ctx::RingKind k) {
+    return k == vh_ctx::RING_FRAMES ? "8-bit frames" : k == vh_ctx::RING_U8 ? "8-bit images" : k == vh_ctx::RING_TENSOR ? "image tensors" : "fp32 images";
+}
 
-static int ring_create(vh_ctx* c, int slots, int batch_per_slot, vh_ctx::RingKind kind, size_t slot_bytes = 0) {
+// elem / layout: what a slot of an image ring holds (RING_F32: NHWC fp32, RING_U8: NHWC bytes, RING_TENSOR: the caller's choice)
+static int ring_create(vh_ctx* c, int slots, int batch_per_slot, vh_ctx::RingKind kind, size_t slot_bytes = 0, int elem = VH_ELEM_F32,
+                       int layout = VH_LAYOUT_NHWC) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (slots < 1 || slots > 64) return fail(&c->err, VH_ERR_INVALID, "slots must be 1..64");
     if (batch_per_slot < 1 || batch_per_slot > c->cfg.max_batch)
@@ -1913,7 +1957,7 @@ static int ring_create(vh_ctx* c, int slots, int batch_per_slot, vh_ctx::RingKin
     if (frames && slot_bytes < 1) return fail(&c->err, VH_ERR_INVALID, "slot_bytes must be positive");
     vh_ring_destroy(c);
     HIPCHK(&c->err, hipSetDevice(c->device));
-    const size_t in_bytes = frames ? slot_bytes : (size_t)batch_per_slot * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (kind == vh_ctx::RING_U8 ? 1 : 4);
+    const size_t in_bytes = frames ? slot_bytes : (size_t)batch_per_slot * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * ImgIn{nullptr, elem, layout}.elem();
     // frames: the resized-image buffer and a first plan buffer now, and per slot room for a plan of two tables of ~8 taps
     const size_t plan_words = (size_t)batch_per_slot * kResizeFrameWords + 2 * (size_t)c->cfg.image_size * 10;
     if (frames)
@@ -1941,12 +1985,19 @@ static int ring_create(vh_ctx* c, int slots, int batch_per_slot, vh_ctx::RingKin
     }
     c->ring_batch = batch_per_slot;
     c->ring_kind = kind;
-    c->ring_slot_bytes = frames ? slot_bytes : 0;
+    c->ring_elem = elem;
+    c->ring_layout = layout;
+    c->ring_slot_bytes = frames ? slot_bytes : kind == vh_ctx::RING_TENSOR ? in_bytes : 0;
     return VH_OK;
 }
 
 int vh_ring_create(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, vh_ctx::RING_F32); }
-int vh_ring_create_u8(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, vh_ctx::RING_U8); }
+int vh_ring_create_u8(vh_ctx* c, int slots, int batch_per_slot) { return ring_create(c, slots, batch_per_slot, vh_ctx::RING_U8, 0, VH_ELEM_U8); }
+int vh_ring_create_tensor(vh_ctx* c, int slots, int batch_per_slot, int elem, int layout) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
+    if (int rc = check_tensor_kind(&c->err, elem, layout)) return rc;
+    return ring_create(c, slots, batch_per_slot, vh_ctx::RING_TENSOR, 0, elem, layout);
+}
 int vh_ring_create_frames(vh_ctx* c, int slots, int batch_per_slot, size_t slot_bytes) {
     return ring_create(c, slots, batch_per_slot, vh_ctx::RING_FRAMES, slot_bytes);
 }
@@ -1968,6 +2019,12 @@ static int ring_input(vh_ctx* c, void** pinned_in, vh_ctx::RingKind kind) {
 
 int vh_ring_input(vh_ctx* c, float** pinned_in) { return ring_input(c, (void**)pinned_in, vh_ctx::RING_F32); }
 int vh_ring_input_u8(vh_ctx* c, uint8_t** pinned_in) { return ring_input(c, (void**)pinned_in, vh_ctx::RING_U8); }
+int vh_ring_input_tensor(vh_ctx* c, void** pinned, size_t* capacity_bytes) {
+    if (!capacity_bytes) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
+    if (int rc = ring_input(c, pinned, vh_ctx::RING_TENSOR)) return rc;
+    *capacity_bytes = c->ring_slot_bytes;
+    return VH_OK;
+}
 int vh_ring_input_frames(vh_ctx* c, uint8_t** pinned, size_t* capacity) {
     if (!capacity) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
     if (int rc = ring_input(c, (void**)pinned, vh_ctx::RING_FRAMES)) return rc;
@@ -1995,7 +2052,8 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     }
     HIPCHK(&c->err, hipSetDevice(c->device));
     vh_ctx::RingSlot& s = c->ring[c->ring_wr];
-    const size_t in_bytes = frames ? frame_bytes : (size_t)batch * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * (kind == vh_ctx::RING_U8 ? 1 : 4);
+    const ImgIn slot_in{s.d_in, c->ring_elem, c->ring_layout};   // an image ring's slot
+    const size_t in_bytes = frames ? frame_bytes : (size_t)batch * c->cfg.image_size * c->cfg.image_size * c->cfg.channels * slot_in.elem();
     if (frames) {
         const size_t words = c->rz_words.size();
         if (words > s.plan_cap) {   // a free slot: its last upload ran before its batch was collected
@@ -2016,7 +2074,7 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
         const FrameJob job{fmt, (const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles};
         if ((rc = enqueue_resize(c, job, batch))) return rc;
     }
-    rc = run_step(c, frames ? ImgIn{c->rz_u8, true} : ImgIn{s.d_in, kind == vh_ctx::RING_U8}, batch, s.d_out);
+    rc = run_step(c, frames ? ImgIn{c->rz_u8, kU8} : slot_in, batch, s.d_out);
     if (rc) return rc;
     HIPCHK(&c->err, hipEventRecord(s.fwd_done, c->stream));
     HIPCHK(&c->err, hipStreamWaitEvent(c->copy_out, s.fwd_done, 0));
@@ -2029,6 +2087,7 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
 
 int vh_ring_submit(vh_ctx* c, const float* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_F32); }
 int vh_ring_submit_u8(vh_ctx* c, const uint8_t* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_U8); }
+int vh_ring_submit_tensor(vh_ctx* c, const void* in_host, int batch) { return ring_submit(c, in_host, batch, vh_ctx::RING_TENSOR); }
 int vh_ring_submit_frames(vh_ctx* c, const uint8_t* frames_host, size_t nbytes, const vh_frame* desc, int batch) {
     return ring_submit(c, frames_host, batch, vh_ctx::RING_FRAMES, nbytes, desc, kFramesRGB);
 }
@@ -2446,6 +2505,25 @@ int vh_op_im2col_u8(const uint8_t* in, int batch, int image, int patch, int chan
     for (int i = 0; i < channels; ++i)
         if (!std::isfinite(scale_host[i]) || !std::isfinite(shift_host[i])) return fail(nullptr, VH_ERR_INVALID, "im2col_u8: scale / shift of channel %d is not finite", i);
     OPCHK(launch_im2col_u8(in, batch, image, patch, channels, kpad, scale_host, shift_host, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_im2col_tensor(const void* in, int elem, int layout, int batch, int image, int patch, int channels, int kpad, const float* scale_host,
+                        const float* shift_host, void* out16, int dtype, void* stream) {
+    if (int rc = check_tensor_kind(nullptr, elem, layout)) return rc;
+    if (!in || !out16 || (elem == VH_ELEM_U8 && (!scale_host || !shift_host))) return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: null buffer");
+    if (batch <= 0) return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: batch %d must be positive", batch);
+    if (patch <= 0 || patch > 256 || image <= 0 || image % patch)
+        return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: image %d is no multiple of patch %d (1..256)", image, patch);
+    if (channels <= 0 || channels > kMaxChannels) return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: channels %d outside 1..%d", channels, kMaxChannels);
+    if (kpad < patch * patch * channels || kpad % 8)
+        return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: kpad %d must be a multiple of 8 and at least patch * patch * channels = %d", kpad, patch * patch * channels);
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16) return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: unsupported dtype %d", dtype);
+    if ((uintptr_t)in & 15) return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: input %p is not 16-byte aligned", in);
+    if (elem == VH_ELEM_U8)
+        for (int i = 0; i < channels; ++i)
+            if (!std::isfinite(scale_host[i]) || !std::isfinite(shift_host[i])) return fail(nullptr, VH_ERR_INVALID, "im2col_tensor: scale / shift of channel %d is not finite", i);
+    OPCHK(launch_im2col_tensor(in, elem, layout, batch, image, patch, channels, kpad, scale_host, shift_host, out16, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }

@@ -19,6 +19,9 @@ FLAG_LN_FOLD_OFF, FLAG_LN_FOLD_ON, FLAG_W8_E4M3, FLAG_CLS_TAIL = 1, 2, 4, 8   # 
 FLAG_PRE_LN, FLAG_QUICK_GELU = 16, 32   # CLIP's vision towers: LayerNorm in front of layer 0, x * sigmoid(1.702 x) in the MLP
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
 EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
+ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = range(4)   # element type of an image tensor (VH_ELEM_*)
+LAYOUT_NHWC, LAYOUT_NCHW = 0, 1                      # its layout (VH_LAYOUT_*): [B][S][S][C] / [B][C][S][S]
+ELEM_BYTES = {ELEM_F32: 4, ELEM_F16: 2, ELEM_BF16: 2, ELEM_U8: 1}
 ACT_IDENTITY, ACT_RELU2, ACT_RELU, ACT_HARDTANH, ACT_GELU = range(5)
 
 STAGES = ["im2col", "patch_gemm", "cls_rows", "layernorm", "qkv_gemm", "attention", "proj_gemm",
@@ -127,6 +130,9 @@ SYMBOLS = {
     "vh_forward_u8": (_i, [_vp, _vp, _i, _vp]),
     "vh_forward_device_u8": (_i, [_vp, _vp, _i, _vp]),
     "vh_forward_device_u8_async": (_i, [_vp, _vp, _i, _vp, _i]),
+    "vh_forward_tensor": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "vh_forward_device_tensor": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "vh_forward_device_tensor_async": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "vh_resize_table": (_i, [_i, C.c_double, C.c_double, _i, _vp, _vp, _vp, _i]),
     "vh_forward_frames_u8": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     "vh_forward_device_frames_u8": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
@@ -177,6 +183,9 @@ SYMBOLS = {
     "vh_ring_create_u8": (_i, [_vp, _i, _i]),
     "vh_ring_input_u8": (_i, [_vp, C.POINTER(C.POINTER(C.c_uint8))]),
     "vh_ring_submit_u8": (_i, [_vp, _vp, _i]),
+    "vh_ring_create_tensor": (_i, [_vp, _i, _i, _i, _i]),
+    "vh_ring_input_tensor": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
+    "vh_ring_submit_tensor": (_i, [_vp, _vp, _i]),
     "vh_ring_create_frames": (_i, [_vp, _i, _i, _sz]),
     "vh_ring_input_frames": (_i, [_vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(_sz)]),
     "vh_ring_submit_frames": (_i, [_vp, _vp, _sz, _vp, _i]),
@@ -220,6 +229,7 @@ SYMBOLS = {
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "vh_op_im2col_tensor": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "vh_op_resize_u8": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp]),
     "vh_op_resize_nv12": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_yuv": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
@@ -706,6 +716,10 @@ def pack_tiled(a, chunk=8, fill=0):
     return np.ascontiguousarray(full.reshape(nb, 16, dim // chunk, chunk).transpose(0, 2, 1, 3))
 
 
+# numpy dtype -> ELEM_* (bf16 has no numpy dtype: uint16 bits with elem=ELEM_BF16 given)
+_NUMPY_ELEM = {np.dtype(np.float32): ELEM_F32, np.dtype(np.float16): ELEM_F16, np.dtype(np.uint8): ELEM_U8}
+
+
 class DeviceBuffer:
     """A raw HBM allocation owned through vh_malloc/vh_free."""
 
@@ -905,6 +919,62 @@ class VitContext:
 
     def forward_device_u8_async(self, in_ptr, batch, out_ptr, steps=1):
         _check(lib().vh_forward_device_u8_async(self.h, in_ptr, batch, out_ptr, steps), self.h)
+
+    # ---- image tensors: one element type (ELEM_*) and one layout (LAYOUT_*), taken as they are ----
+    def forward_tensor(self, array, layout, elem=None):
+        """array: a dense host batch, [B, S, S, C] for LAYOUT_NHWC or [B, C, S, S] for LAYOUT_NCHW, of dtype float32, float16 or
+        uint8 (elem inferred), or uint16 holding bf16 bits with elem=ELEM_BF16 given.  Returns [B, classes] fp32 logits: the
+        bits forward() gives for the NHWC fp32 array of the widened (uint8: normalised, set_input_norm) elements."""
+        array = np.asarray(array)
+        if elem is None:
+            elem = _NUMPY_ELEM.get(array.dtype)
+            if elem is None:
+                raise TypeError(f"forward_tensor takes float32, float16 or uint8 arrays, or uint16 with elem=ELEM_BF16; got {array.dtype}")
+        elif elem in ELEM_BYTES and array.dtype.itemsize != ELEM_BYTES[elem]:
+            raise TypeError(f"forward_tensor: elem {elem} has {ELEM_BYTES[elem]} bytes per element, {array.dtype} has {array.dtype.itemsize}")
+        array = np.ascontiguousarray(array)
+        b = array.shape[0]
+        out = np.empty((b, self.cfg["classes"]), dtype=np.float32)
+        _check(lib().vh_forward_tensor(self.h, array.ctypes.data, elem, layout, b, out.ctypes.data), self.h)
+        return out
+
+    def forward_device_tensor(self, in_ptr, elem, layout, batch, out_ptr):
+        _check(lib().vh_forward_device_tensor(self.h, in_ptr, elem, layout, batch, out_ptr), self.h)
+
+    def forward_device_tensor_async(self, in_ptr, elem, layout, batch, out_ptr, steps=1):
+        _check(lib().vh_forward_device_tensor_async(self.h, in_ptr, elem, layout, batch, out_ptr, steps), self.h)
+
+    def forward_torch(self, x):
+        """x: a torch tensor [B, C, S, S] of dtype float32, float16, bfloat16 or uint8.  A contiguous tensor goes in as NCHW, a
+        channels_last one as NHWC of the same memory; any other striding is made dense with .contiguous() first (one copy).
+        A tensor on this context's GPU is read in place through data_ptr(), after torch.cuda.current_stream(x.device) has been
+        synchronised (the context runs on its own stream), and the logits come back as a torch.float32 tensor on that device.
+        A CPU tensor takes the host entry point and returns a CPU tensor; a tensor on another GPU raises ValueError.
+        For GPU tensors import torch before this module loads libvithip.so (one HIP runtime per process), and
+        mind that the library wants data_ptr() 16-byte aligned (a view with a storage offset may not be)."""
+        import torch
+        elems = {torch.float32: ELEM_F32, torch.float16: ELEM_F16, torch.bfloat16: ELEM_BF16, torch.uint8: ELEM_U8}
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise TypeError("forward_torch takes a 4-d torch tensor [B, C, S, S]")
+        if x.dtype not in elems:
+            raise TypeError(f"forward_torch takes float32, float16, bfloat16 or uint8 tensors, got {x.dtype}")
+        elem = elems[x.dtype]
+        if x.is_contiguous():
+            layout = LAYOUT_NCHW
+        elif x.is_contiguous(memory_format=torch.channels_last):
+            layout = LAYOUT_NHWC
+        else:
+            x, layout = x.contiguous(), LAYOUT_NCHW
+        b = x.shape[0]
+        out = torch.empty((b, self.cfg["classes"]), dtype=torch.float32, device=x.device)
+        if x.device.type == "cpu":
+            _check(lib().vh_forward_tensor(self.h, x.data_ptr(), elem, layout, b, out.data_ptr()), self.h)
+            return out
+        if x.device.type != "cuda" or x.device.index != self.device:
+            raise ValueError(f"forward_torch: the tensor lives on {x.device}, this context on GPU {self.device}")
+        torch.cuda.current_stream(x.device).synchronize()   # x is complete (and `out` allocated) before the context's stream reads it
+        _check(lib().vh_forward_device_tensor(self.h, x.data_ptr(), elem, layout, b, out.data_ptr()), self.h)
+        return out
 
     # ---- frames of any format: one body per job; `fn` is the format's C entry point, `desc` its descriptor array ----
     def _forward_frames_host(self, fn, buf, desc):
@@ -1113,6 +1183,26 @@ class VitContext:
             raise TypeError(f"ring_submit_u8 takes uint8 images, got {images.dtype}")
         images = np.ascontiguousarray(images)
         _check(lib().vh_ring_submit_u8(self.h, images.ctypes.data, images.shape[0]), self.h)
+
+    def ring_create_tensor(self, slots, batch_per_slot, elem, layout):
+        """A ring whose slots stage image tensors of one element type and layout (ring_input_tensor / ring_submit_tensor)."""
+        _check(lib().vh_ring_create_tensor(self.h, slots, batch_per_slot, elem, layout), self.h)
+        self._ring_batch = batch_per_slot
+
+    def ring_input_tensor(self):
+        """numpy uint8 view (the whole slot: batch_per_slot * S * S * C * sizeof(element) bytes) of the pinned staging buffer the
+        next ring_submit_tensor will upload; .view() it as the element type."""
+        p, cap = C.c_void_p(), C.c_size_t(0)
+        _check(lib().vh_ring_input_tensor(self.h, C.byref(p), C.byref(cap)), self.h)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap.value,))
+
+    def ring_submit_tensor(self, array=None, batch=None):
+        """array: a dense host batch of the ring's element type and layout; None: the slot's pinned buffer already holds `batch` images."""
+        if array is None:
+            _check(lib().vh_ring_submit_tensor(self.h, None, batch), self.h)
+            return
+        array = np.ascontiguousarray(array)
+        _check(lib().vh_ring_submit_tensor(self.h, array.ctypes.data, array.shape[0]), self.h)
 
     def ring_create_frames(self, slots, batch_per_slot, slot_bytes):
         """A ring whose slots stage up to slot_bytes of 8-bit frames each (ring_input_frames / ring_submit_frames)."""
@@ -1562,6 +1652,18 @@ def op_im2col_u8(in_ptr, batch, image, patch, channels, kpad, scale, shift, out_
             raise ValueError(f"op_im2col_u8: expected {channels} values per array, got {a.size}")
     _check(lib().vh_op_im2col_u8(in_ptr, batch, image, patch, channels, kpad, None if sc is None else sc.ctypes.data,
                                  None if sh is None else sh.ctypes.data, out_ptr, dtype, None))
+
+
+def op_im2col_tensor(in_ptr, elem, layout, batch, image, patch, channels, kpad, out_ptr, dtype, scale=None, shift=None):
+    """Patch matrix [batch*np, kpad] of an image tensor (ELEM_*, LAYOUT_*) at in_ptr (device, 16-byte aligned): the bits
+    op_im2col_padded gives for the NHWC fp32 array of its widened elements; scale / shift: [channels], ELEM_U8 only."""
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+    sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float32).reshape(-1)
+    for a in (sc, sh):
+        if a is not None and a.size != channels:
+            raise ValueError(f"op_im2col_tensor: expected {channels} values per array, got {a.size}")
+    _check(lib().vh_op_im2col_tensor(in_ptr, elem, layout, batch, image, patch, channels, kpad, None if sc is None else sc.ctypes.data,
+                                     None if sh is None else sh.ctypes.data, out_ptr, dtype, None))
 
 
 def op_resize_u8(frames_ptr, nbytes, desc, channels, out_size, out_ptr):
