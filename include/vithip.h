@@ -706,6 +706,65 @@ int vh_debug_read(vh_ctx* ctx, int what, float* host_out, size_t n_floats);
 /* run only the first `n_layers` encoder layers on the next forwards (-1 = all) */
 int vh_debug_set_layers(vh_ctx* ctx, int n_layers);
 
+/* ---- Token features ----------------------------------------------------------------------
+ * What a feature backbone returns (DINOv2's x_norm_clstoken / x_norm_patchtokens, the linear probe's concat(cls, mean of
+ * the patch tokens), a CLIP tower's pre-projection vector and its raw penultimate-layer rows): the residual stream the LAST
+ * forward enqueued on the context left in HBM, written on the GPU into the caller's buffers, in the caller's element
+ * type, through the model's final LayerNorm or as it is.  A PULL interface: the calls read the state a forward left, and no
+ * forward entry point knows of them.
+ *
+ *   cls    [batch][D]        the class-token row of every image
+ *   patch  [batch][NP][D]    the other rows, NP = tokens - 1
+ *   mean   [batch][D]        the mean of an image's patch rows
+ * D = vh_config.dim, tokens = (image_size / patch_size)^2 + 1, batch = the last forward's (vh_features_dims).  A NULL pointer:
+ * that output is not wanted and nothing is written for it.
+ *
+ * WHICH FORWARD.  The last one enqueued on the context through any entry point (fp32, 8-bit, tensor, any frames format; eager or
+ * graph replay; 1..4 streams); after vh_forward_device_async(.., steps) the last step.  A weight load on a context whose LayerNorm
+ * fold is guarded (the default flags) runs one calibration image, which counts as a forward of batch 1, as it does for
+ * vh_debug_read.  With vh_debug_set_layers(n) the features are those after n layers: one layer at a time that is DINOv2's
+ * get_intermediate_layers(norm=True), and with VH_FEAT_RAW the penultimate-layer rows CLIP consumers take.  The calls read the
+ * context's arena and write the caller's buffers (vh_read_features stages through activation scratch that every forward
+ * rewrites before it reads it): logits, guards, cached graphs and a following forward are unaffected, and calling twice gives
+ * the same bits.
+ *
+ * ARITHMETIC, for bits.  x[r][k] = the residual element vh_debug_read(ctx, 0) returns: the fp32 element, or on the split paths
+ * (float)hi + lo with ONE fp32 add (16-bit hi + the decoded lo byte; VH_DTYPE_FP8: e4m3 + bf16).
+ *   VH_FEAT_RAW    v = x.
+ *   VH_FEAT_NORM   fp32, two passes: mean = sum(x) / D, var = sum((x - mean)^2) / D, rstd = 1 / sqrtf(var + ln_eps),
+ *                  v = fmaf((x - mean) * rstd, gamma[k], beta[k]) with the final LayerNorm's gamma / beta.  The order of the two
+ *                  row sums depends on D alone: never on the batch, the row, the element type or the outputs requested.
+ *   patch[b][p]    v of row b * tokens + 1 + p.
+ *   cls[b]         RAW: v of row b * tokens.  NORM: the vector the head multiplied (vh_debug_read(ctx, 1)), so that head(cls)
+ *                  reproduces the logits.
+ *   mean[b][k]     (((0 + v[b,1,k]) + v[b,2,k]) + ... + v[b,NP,k]) * inv: plain fp32 adds over the tokens ascending, of the
+ *                  UNROUNDED fp32 v, inv = (float)(1.0 / NP).
+ *   elem           a 16-bit output is the round-to-nearest-even of exactly the fp32 value VH_ELEM_F32 would have written.
+ * Image i's outputs never depend on the other images or on the batch size.
+ *
+ * REFUSED, each with a message of its own, nothing enqueued and no output touched.  VH_ERR_INVALID: a null context or
+ * descriptor; all three pointers NULL; elem not VH_ELEM_F32 / F16 / BF16; norm not 0 or 1; a device output pointer that is
+ * not 16-byte aligned.  VH_ERR_STATE: no forward has run; a ring exists on the context (its forwards belong to slots).
+ * VH_ERR_UNSUPPORTED: a VH_FLAG_CLS_TAIL context (its last layer does not update the other rows).
+ *
+ *   vh_features_dims               any of the four may be NULL; *batch = 0 before the first forward
+ *   vh_read_features               host buffers; synchronous
+ *   vh_read_features_device        device buffers; enqueues on the context's stream and waits
+ *   vh_read_features_device_async  device buffers; enqueues only (vh_synchronize, or stream order with a following call) */
+#define VH_FEAT_NORM 0   /* rows pass the model's final LayerNorm (lnf gamma/beta, cfg.ln_eps) */
+#define VH_FEAT_RAW  1   /* the residual stream as it is                                      */
+typedef struct vh_features {       /* sizeof == 32: cls 0, patch 8, mean 16, elem 24, norm 28 */
+    void* cls;     /* [batch][D]        or NULL: not wanted */
+    void* patch;   /* [batch][NP][D]    or NULL             */
+    void* mean;    /* [batch][D]        or NULL             */
+    int32_t elem;  /* VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16 */
+    int32_t norm;  /* VH_FEAT_NORM or VH_FEAT_RAW              */
+} vh_features;
+int vh_features_dims(const vh_ctx* ctx, int* batch, int* tokens, int* patches, int* dim);
+int vh_read_features(vh_ctx* ctx, const vh_features* out_host);
+int vh_read_features_device(vh_ctx* ctx, const vh_features* out_dev);
+int vh_read_features_device_async(vh_ctx* ctx, const vh_features* out_dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -905,6 +964,15 @@ int vh_op_resize_y410(const uint8_t* frames_dev, size_t nbytes, const vh_frame_b
                       const float* m12_host, int chroma_site, uint8_t* out_u8_dev, void* stream);
 /* fp32 -> dtype cast of n elements (n multiple of 4) */
 int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void* stream);
+/* The token-feature kernels on their own ("Token features"; the kernels vh_read_features* run): rows [batch * tokens, dim] given as
+ * split planes (form VH_DTYPE_BF16 / VH_DTYPE_FP16: 16-bit hi + one scaled e4m3 byte per element in lo_dev; VH_DTYPE_FP8: e4m3 hi +
+ * bf16 lo) or as fp32 rows (form -1, lo_dev NULL) -> patch_out_dev [batch][tokens - 1][dim] and mean_out_dev [batch][dim] of
+ * `elem` (VH_ELEM_F32 / F16 / BF16); either may be NULL, not both.  norm VH_FEAT_NORM: through LayerNorm(gamma_dev, beta_dev, eps);
+ * VH_FEAT_RAW: as they are (gamma_dev / beta_dev may be NULL).  dim % 8 == 0, 64 <= dim <= 2048, tokens 2..4097; every pointer
+ * 16-byte aligned.  Every argument is checked before a device is touched, each refusal with a message of its own. */
+int vh_op_token_features(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int dim,
+                         const float* gamma_dev, const float* beta_dev, float eps, int elem, int norm, void* patch_out_dev,
+                         void* mean_out_dev, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,
  * 2 = constant `sigma` */
 int vh_op_fill(float* out_dev, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,

@@ -1,0 +1,278 @@
+// kernels_features.hip — token features of the residual stream a forward left in HBM (gfx950): the rows as they are or
+// through the model's final LayerNorm, written in the caller's element type, and the mean over the patch tokens.
+// Contract: include/vithip.h, "Token features"; DESIGN.md 4.19.
+//
+//   feat_rows_kernel   one wave per row, four rows per workgroup.  The row's planes are read ONCE, 8 elements per lane and
+//                      piece (16-bit split path: 16 B of the hi plane + 8 B of the lo plane; fp8 split path: 8 B of e4m3 +
+//                      16 B of bf16; plain path: two 16-byte fp32 loads), the row stays in registers between the two
+//                      statistic passes, and each lane stores 16 bytes (fp32 results: two such stores).
+//   feat_mean_kernel   one thread per image and FOUR neighbouring columns, walking the patch tokens in ascending order: the
+//                      serial fp32 chain the contract names, independent of any launch geometry.  It reads the planes
+//                      again (coalesced across columns) and takes (mean, rstd) of a row from the statistics the row kernel
+//                      wrote, so the value it adds is, bit for bit, the fp32 value the row kernel converted and stored.
+// (The normalised class-token rows are the ones the head multiplied: a conversion copy of clsn32, made by launch_cast.)
+//
+// The arithmetic that both kernels must agree on lives in ONE place each: load_x (x = hi + lo, one fp32 add) and
+// feat_norm (fmaf((x - mean) * rstd, gamma, beta), explicit fmaf).  The row sums use explicit operations in an order that
+// depends on dim alone: per lane the pieces ascending (inside a piece a fixed tree), then the xor butterfly over the wave.
+#include <type_traits>
+
+#include "vh_kernels.h"
+
+namespace vh {
+
+namespace {
+
+// ---- the three forms of a residual row ---------------------------------------------------------------------------------
+template <typename T> struct InSplit16 { using hi_t = T; };   // T = BF16 / FP16: 16-bit hi plane + one scaled e4m3 byte (Lo8<T>)
+struct InSplit8 {};                                           // e4m3 hi plane + bf16 lo plane (VH_DTYPE_FP8 contexts)
+struct InF32 {};                                              // the fp32 array
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// N = 8 or 4 consecutive elements starting at element `e` (a multiple of N) -> fp32; x = hi + lo with ONE fp32 add (the
+// lo byte's scale is a power of two: decoding it is exact)
+template <typename IN, int N>
+__device__ __forceinline__ void load_x(const void* __restrict__ hi, const void* __restrict__ lo, int64_t e, float* v) {
+    static_assert(N == 8 || N == 4, "pieces of 8 or 4 elements");
+    if constexpr (std::is_same<IN, InF32>::value) {
+        const f32x4* p = (const f32x4*)((const float*)hi + e);
+#pragma unroll
+        for (int q = 0; q < N / 4; ++q) {
+            const f32x4 a = p[q];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[4 * q + j] = a[j];
+        }
+    } else if constexpr (std::is_same<IN, InSplit8>::value) {
+        const uint32_t* hp = (const uint32_t*)((const uint8_t*)hi + e);
+        uint32_t hw[N / 4];
+        if constexpr (N == 8) { const u32x2 t = *(const u32x2*)hp; hw[0] = t[0]; hw[1] = t[1]; }
+        else hw[0] = *hp;
+        using lvec = typename std::conditional<N == 8, bf16x8, bf16x4>::type;
+        const lvec l = *(const lvec*)((const __bf16*)lo + e);
+#pragma unroll
+        for (int q = 0; q < N / 4; ++q) {
+            const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)hw[q], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)hw[q], true);
+            v[4 * q + 0] = a[0] + (float)l[4 * q + 0];
+            v[4 * q + 1] = a[1] + (float)l[4 * q + 1];
+            v[4 * q + 2] = b[0] + (float)l[4 * q + 2];
+            v[4 * q + 3] = b[1] + (float)l[4 * q + 3];
+        }
+    } else {
+        using T = typename IN::hi_t;
+        using hvec = typename std::conditional<N == 8, typename T::vec8, typename T::vec4>::type;
+        const hvec h = *(const hvec*)((const typename T::elem*)hi + e);
+        const uint32_t* lp = (const uint32_t*)((const uint8_t*)lo + e);
+        uint32_t lw[N / 4];
+        if constexpr (N == 8) { const u32x2 t = *(const u32x2*)lp; lw[0] = t[0]; lw[1] = t[1]; }
+        else lw[0] = *lp;
+#pragma unroll
+        for (int q = 0; q < N / 4; ++q) {
+            const f32x4 l = lo8_unpack4<T>(lw[q]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[4 * q + j] = (float)h[4 * q + j] + l[j];
+        }
+    }
+}
+
+__device__ __forceinline__ float feat_norm(float x, float mean, float rstd, float g, float b) {
+    return __builtin_fmaf((x - mean) * rstd, g, b);
+}
+
+// ---- the three element types of a result: F32OUT, FP16, BF16 (vh_common.h); 16-bit results round to nearest even ---------
+template <typename OUT>
+__device__ __forceinline__ void store4(typename OUT::elem* p, const float* v) {
+    *(typename OUT::vec4*)p = pack4<OUT>(v[0], v[1], v[2], v[3]);
+}
+template <typename OUT>
+__device__ __forceinline__ void store8(typename OUT::elem* p, const float* v) {
+    if constexpr (std::is_same<OUT, F32OUT>::value) {
+        ((f32x4*)p)[0] = f32x4{v[0], v[1], v[2], v[3]};
+        ((f32x4*)p)[1] = f32x4{v[4], v[5], v[6], v[7]};
+    } else {
+        const typename OUT::vec4 a = pack4<OUT>(v[0], v[1], v[2], v[3]), b = pack4<OUT>(v[4], v[5], v[6], v[7]);
+        *(typename OUT::vec8*)p = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+}
+
+// rows = batch * tokens.  Row r = image r / tokens, token r % tokens: token 0 goes to cls_out [batch][dim], token t > 0 to
+// patch_out [batch][tokens - 1][dim]; either may be null.  norm != 0: the row passes LayerNorm(gamma, beta, eps), and
+// stats (optional) receives (mean, rstd) of every patch row.  A wave whose row has nothing to write leaves at once.
+template <typename IN, typename OUT, int CH>   // CH = pieces of 8 elements per lane (dim <= 512 * CH)
+__global__ void __launch_bounds__(256)
+feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t rows, int tokens, int dim,
+                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int norm,
+                 typename OUT::elem* __restrict__ cls_out, typename OUT::elem* __restrict__ patch_out, float* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t img = row / tokens;
+    const int t = (int)(row - img * tokens);
+    typename OUT::elem* out = nullptr;
+    if (t == 0) { if (cls_out) out = cls_out + img * dim; }
+    else if (patch_out) out = patch_out + (img * (tokens - 1) + (t - 1)) * dim;
+    const bool want_stats = norm && stats && t != 0;
+    if (!out && !want_stats) return;   // wave-uniform
+    const int npiece = dim >> 3;
+    float v[CH][8];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int c = lane + 64 * i;
+        if (c < npiece) load_x<IN, 8>(hi, lo, row * dim + 8 * c, v[i]);
+        else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+        }
+    }
+    float mean = 0.f, rstd = 1.f;
+    if (norm) {
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+            sum += ((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) + ((v[i][4] + v[i][5]) + (v[i][6] + v[i][7]));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        mean = sum / (float)dim;
+        float var = 0.f;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            if (lane + 64 * i < npiece) {
+                float q = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q = __builtin_fmaf(d, d, q); }
+                var += q;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o);
+        rstd = 1.0f / sqrtf(var / (float)dim + eps);
+        if (want_stats && lane == 0) *(f32x2*)(stats + 2 * row) = f32x2{mean, rstd};
+    }
+    if (!out) return;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int c = lane + 64 * i;
+        if (c < npiece) {
+            if (norm) {
+                const f32x4 g0 = ((const f32x4*)gamma)[2 * c], g1 = ((const f32x4*)gamma)[2 * c + 1];
+                const f32x4 b0 = ((const f32x4*)beta)[2 * c], b1 = ((const f32x4*)beta)[2 * c + 1];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[i][j] = feat_norm(v[i][j], mean, rstd, g0[j], b0[j]);
+                    v[i][4 + j] = feat_norm(v[i][4 + j], mean, rstd, g1[j], b1[j]);
+                }
+            }
+            store8<OUT>(out + 8 * c, v[i]);
+        }
+    }
+}
+
+// mean_out[b][k] = (((0 + v[b,1,k]) + v[b,2,k]) + ... + v[b,tokens-1,k]) * inv, v as feat_rows_kernel writes it in fp32.
+// One thread per image and four columns; n4 = batch * dim / 4 threads.
+template <typename IN, typename OUT>
+__global__ void __launch_bounds__(256)
+feat_mean_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t n4, int tokens, int dim,
+                 const float* __restrict__ gamma, const float* __restrict__ beta, int norm, const float* __restrict__ stats,
+                 float inv, typename OUT::elem* __restrict__ mean_out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n4) return;
+    const int q4 = dim >> 2;
+    const int64_t img = idx / q4;
+    const int k = (int)(idx - img * q4) * 4;
+    f32x4 g = {1.f, 1.f, 1.f, 1.f}, b = {0.f, 0.f, 0.f, 0.f};
+    if (norm) { g = *(const f32x4*)(gamma + k); b = *(const f32x4*)(beta + k); }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const int64_t row0 = img * tokens;
+#pragma unroll 4
+    for (int t = 1; t < tokens; ++t) {
+        const int64_t row = row0 + t;
+        float x[4];
+        load_x<IN, 4>(hi, lo, row * dim + k, x);
+        if (norm) {
+            const f32x2 st = *(const f32x2*)(stats + 2 * row);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[j] = feat_norm(x[j], st[0], st[1], g[j], b[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += x[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] *= inv;
+    store4<OUT>(mean_out + img * dim + k, acc);
+}
+
+template <typename IN, typename OUT>
+hipError_t feat_launch(const FeatureArgs& a, hipStream_t s) {
+    using E = typename OUT::elem;
+    const int64_t rows = (int64_t)a.batch * a.tokens;
+    const int norm = a.norm == VH_FEAT_NORM ? 1 : 0;   // the kernels' flag: 1 = through the LayerNorm
+    const bool mean_norm = a.mean && norm;
+    if (a.cls || a.patch || mean_norm) {   // (a raw mean needs no row pass: nothing to normalise, no statistics)
+        const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+        float* st = mean_norm ? a.stats : nullptr;
+#define VH_FEAT_ROWS(CH) hipLaunchKernelGGL((feat_rows_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, rows, a.tokens, a.dim, \
+                                            a.gamma, a.beta, a.eps, norm, (E*)a.cls, (E*)a.patch, st)
+        if (a.dim <= 512) VH_FEAT_ROWS(1);
+        else if (a.dim <= 1024) VH_FEAT_ROWS(2);
+        else if (a.dim <= 1536) VH_FEAT_ROWS(3);
+        else VH_FEAT_ROWS(4);
+#undef VH_FEAT_ROWS
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (a.mean) {
+        const int64_t n4 = (int64_t)a.batch * (a.dim >> 2);
+        const float inv = (float)(1.0 / (double)(a.tokens - 1));
+        hipLaunchKernelGGL((feat_mean_kernel<IN, OUT>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.hi, a.lo, n4, a.tokens, a.dim,
+                           a.gamma, a.beta, norm, a.stats, inv, (E*)a.mean);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+template <typename IN>
+hipError_t feat_launch_in(const FeatureArgs& a, hipStream_t s) {
+    if (a.elem == VH_ELEM_F32) return feat_launch<IN, F32OUT>(a, s);
+    if (a.elem == VH_ELEM_F16) return feat_launch<IN, FP16>(a, s);
+    if (a.elem == VH_ELEM_BF16) return feat_launch<IN, BF16>(a, s);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+const char* features_check(const FeatureArgs& a) {
+    if (!a.hi) return "token_features: null input";
+    if (a.form != VH_FEAT_FORM_F32 && a.form != VH_DTYPE_BF16 && a.form != VH_DTYPE_FP16 && a.form != VH_DTYPE_FP8)
+        return "token_features: form must be VH_DTYPE_BF16, VH_DTYPE_FP16, VH_DTYPE_FP8 (split planes) or -1 (fp32 rows)";
+    if (a.form == VH_FEAT_FORM_F32 && a.lo) return "token_features: fp32 rows take no lo plane";
+    if (a.form != VH_FEAT_FORM_F32 && !a.lo) return "token_features: split planes need the lo plane";
+    if (a.batch <= 0 || a.batch > (1 << 20)) return "token_features: batch outside 1..2^20";
+    if (a.tokens < 2) return "token_features: tokens below 2 (no patch token)";
+    if (a.tokens > kAttnStreamMaxTokens) return "token_features: tokens above 4097";
+    if (a.dim < 64) return "token_features: dim below 64";
+    if (a.dim > 2048) return "token_features: dim above 2048";
+    if (a.dim % 8) return "token_features: dim must be a multiple of 8";
+    if (!a.cls && !a.patch && !a.mean) return "token_features: no output requested";
+    if (a.elem != VH_ELEM_F32 && a.elem != VH_ELEM_F16 && a.elem != VH_ELEM_BF16)
+        return "token_features: elem must be VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16";
+    if (a.norm != VH_FEAT_NORM && a.norm != VH_FEAT_RAW) return "token_features: norm must be VH_FEAT_NORM or VH_FEAT_RAW";
+    if (a.norm == VH_FEAT_NORM) {
+        if (!a.gamma || !a.beta) return "token_features: VH_FEAT_NORM needs gamma and beta";
+        if (!(a.eps > 0.f)) return "token_features: eps must be positive";
+    }
+    const uintptr_t al = (uintptr_t)a.hi | (uintptr_t)a.lo | (uintptr_t)a.gamma | (uintptr_t)a.beta | (uintptr_t)a.cls | (uintptr_t)a.patch |
+                         (uintptr_t)a.mean;
+    if (al & 15) return "token_features: a device pointer is not 16-byte aligned";
+    if ((uintptr_t)a.stats & 7) return "token_features: the row statistics buffer is not 8-byte aligned";
+    return nullptr;
+}
+
+hipError_t launch_token_features(const FeatureArgs& a, hipStream_t s) {
+    if (features_check(a)) return hipErrorInvalidValue;
+    if (a.mean && a.norm == VH_FEAT_NORM && !a.stats) return hipErrorInvalidValue;   // the normalised mean needs the statistics scratch
+    if (a.form == VH_FEAT_FORM_F32) return feat_launch_in<InF32>(a, s);
+    if (a.form == VH_DTYPE_FP8) return feat_launch_in<InSplit8>(a, s);
+    return a.form == VH_DTYPE_BF16 ? feat_launch_in<InSplit16<BF16>>(a, s) : feat_launch_in<InSplit16<FP16>>(a, s);
+}
+
+}  // namespace vh

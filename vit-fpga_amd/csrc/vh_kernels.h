@@ -219,6 +219,30 @@ hipError_t launch_pre_layernorm(const float* x, int64_t rows, int dim, const flo
                                 unsigned int* guard = nullptr, unsigned int* amax_guard = nullptr);
 hipError_t launch_layernorm_split(const void* hi, const void* lo, int64_t rows, int dim, int64_t row_stride, const float* gamma,
                                   const float* beta, float eps, float* out32, int dtype, hipStream_t stream);
+// Token features (kernels_features.hip; contract: vithip.h, "Token features"): the rows of a residual stream [batch * tokens, dim]
+// -> the caller's element type (VH_ELEM_F32 / F16 / BF16), as they are (VH_FEAT_RAW) or through LayerNorm(gamma, beta, eps)
+// (VH_FEAT_NORM), and the mean over an image's patch tokens (tokens 1 .. tokens - 1, a serial fp32 chain in that order).
+// form: VH_DTYPE_BF16 / FP16 = split planes (hi 16-bit, lo one scaled e4m3 byte), VH_DTYPE_FP8 = e4m3 hi + bf16 lo,
+// VH_FEAT_FORM_F32 = fp32 rows in `hi`, lo null.  cls [batch][dim] <- token 0, patch [batch][tokens - 1][dim] <- the others, mean
+// [batch][dim]; any may be null, not all.  stats [batch * tokens][2]: scratch of the normalised mean (row kernel writes, mean
+// kernel reads).  features_check: nullptr, or why the launch is refused; host arithmetic only.
+constexpr int VH_FEAT_FORM_F32 = -1;
+struct FeatureArgs {
+    const void* hi;
+    const void* lo;
+    int form;
+    int batch, tokens, dim;
+    const float* gamma;
+    const float* beta;
+    float eps;
+    int elem, norm;
+    void* cls;
+    void* patch;
+    void* mean;
+    float* stats;
+};
+const char* features_check(const FeatureArgs& a);
+hipError_t launch_token_features(const FeatureArgs& a, hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln
 hipError_t launch_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim,
                              float scale, void* w8, float* wscale, float* c, float* d, hipStream_t stream);

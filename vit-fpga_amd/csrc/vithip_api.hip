@@ -2280,6 +2280,93 @@ int vh_debug_set_layers(vh_ctx* c, int n_layers) {
     return VH_OK;
 }
 
+// ---- token features (vithip.h "Token features"; kernels_features.hip) ---------------------------------------------------
+// A pull interface: these calls read what the last forward left in the arena -- the residual stream in the form its path keeps it
+// (the same choice vh_debug_read makes), clsn32, the final LayerNorm's parameters in the blob -- and no forward knows of them.
+// The normalised mean's row statistics go through c->stats, which is free between forwards (every path that reads it writes it
+// first); everything is enqueued on the context's main stream, where a forward on several streams has already joined.
+static int features_check_call(vh_ctx* c, const vh_features* f, bool device) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "read_features: null context");
+    if (!f) return fail(&c->err, VH_ERR_INVALID, "read_features: null descriptor");
+    if (!f->cls && !f->patch && !f->mean) return fail(&c->err, VH_ERR_INVALID, "read_features: no output requested (cls, patch and mean are all NULL)");
+    if (f->elem != VH_ELEM_F32 && f->elem != VH_ELEM_F16 && f->elem != VH_ELEM_BF16)
+        return fail(&c->err, VH_ERR_INVALID, "read_features: elem %d is not VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16", f->elem);
+    if (f->norm != VH_FEAT_NORM && f->norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "read_features: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", f->norm);
+    if (device && (((uintptr_t)f->cls | (uintptr_t)f->patch | (uintptr_t)f->mean) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "read_features: a device output pointer is not 16-byte aligned (cls %p, patch %p, mean %p)", f->cls, f->patch, f->mean);
+    if (c->cfg.flags & VH_FLAG_CLS_TAIL)
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "read_features: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "read_features: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
+    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "read_features: no forward has run");
+    return VH_OK;
+}
+static int features_enqueue(vh_ctx* c, const vh_features& f) {
+    const vh_config& g = c->cfg;
+    const int nl = (c->run_layers < 0 || c->run_layers > g.layers) ? g.layers : c->run_layers;
+    const bool planes = c->split && nl > 0;   // where the last forward left the rows: the two planes, or the fp32 array
+    const bool norm = f.norm == VH_FEAT_NORM;
+    FeatureArgs a{};
+    a.hi = planes ? (const void*)c->xn16 : (const void*)c->x;
+    a.lo = planes ? c->xlo16 : nullptr;
+    a.form = planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32;
+    a.batch = c->last_batch; a.tokens = c->L.T; a.dim = g.dim;
+    a.gamma = c->params + c->L.lnfw; a.beta = c->params + c->L.lnfb; a.eps = g.ln_eps;
+    a.elem = f.elem; a.norm = f.norm;
+    a.cls = norm ? nullptr : f.cls;   // the normalised class-token rows are the ones the head multiplied: a conversion copy of clsn32
+    a.patch = f.patch; a.mean = f.mean; a.stats = c->stats;
+    if (a.cls || a.patch || a.mean) {
+        if (const char* why = features_check(a)) return fail(&c->err, VH_ERR_INVALID, "read_features: %s", why);
+        HIPCHK(&c->err, launch_token_features(a, c->stream));
+    }
+    if (norm && f.cls) {
+        const int64_t n = (int64_t)c->last_batch * g.dim;
+        if (f.elem == VH_ELEM_F32) HIPCHK(&c->err, hipMemcpyAsync(f.cls, c->clsn32, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        else HIPCHK(&c->err, launch_cast(c->clsn32, f.cls, n, f.elem == VH_ELEM_BF16 ? VH_DTYPE_BF16 : VH_DTYPE_FP16, c->stream));
+    }
+    return VH_OK;
+}
+int vh_features_dims(const vh_ctx* c, int* batch, int* tokens, int* patches, int* dim) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "features_dims: null context");
+    if (batch) *batch = c->last_batch;
+    if (tokens) *tokens = c->L.T;
+    if (patches) *patches = c->L.NP;
+    if (dim) *dim = c->cfg.dim;
+    return VH_OK;
+}
+int vh_read_features_device_async(vh_ctx* c, const vh_features* f) {
+    if (int rc = features_check_call(c, f, true)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return features_enqueue(c, *f);
+}
+int vh_read_features_device(vh_ctx* c, const vh_features* f) {
+    if (int rc = vh_read_features_device_async(c, f)) return rc;
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return VH_OK;
+}
+int vh_read_features(vh_ctx* c, const vh_features* f) {
+    if (int rc = features_check_call(c, f, false)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    // staged in the q|k|v buffer: scratch between forwards (every forward writes its rows before attention reads them), and at
+    // 6 bytes per row element always large enough for fp32 patch rows + the two [batch][D] outputs
+    const size_t es = f->elem == VH_ELEM_F32 ? 4 : 2, D = c->cfg.dim, B = c->last_batch;
+    const size_t n_row = B * D * es, n_patch = B * (size_t)c->L.NP * D * es;
+    const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * D * 2;
+    char* const base = (char*)c->qkv16;
+    size_t at = 0;
+    auto take = [&](bool want, size_t bytes) -> void* { if (!want) return nullptr; void* p = base + at; at += align_up(bytes, 256); return p; };
+    vh_features d = *f;
+    d.patch = take(f->patch != nullptr, n_patch);
+    d.cls = take(f->cls != nullptr, n_row);
+    d.mean = take(f->mean != nullptr, n_row);
+    if (at > cap) return fail(&c->err, VH_ERR_STATE, "read_features: staging needs %zu bytes, the scratch holds %zu", at, cap);
+    if (int rc = features_enqueue(c, d)) return rc;
+    if (f->patch) HIPCHK(&c->err, hipMemcpyAsync(f->patch, d.patch, n_patch, hipMemcpyDeviceToHost, c->stream));
+    if (f->cls) HIPCHK(&c->err, hipMemcpyAsync(f->cls, d.cls, n_row, hipMemcpyDeviceToHost, c->stream));
+    if (f->mean) HIPCHK(&c->err, hipMemcpyAsync(f->mean, d.mean, n_row, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return VH_OK;
+}
+
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
@@ -2592,6 +2679,19 @@ int vh_op_cast(const float* in, void* out16, int64_t n, int dtype, void* stream)
     if (!in || !out16 || n <= 0 || n % 4) return fail(nullptr, VH_ERR_INVALID, "cast: bad argument");
     OPCHK(launch_cast(in, out16, n, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+// the token-feature kernels on caller-made rows; the normalised mean's row statistics take a scratch of the tap's own (a test
+// and measurement tap: the context calls use the context's statistics buffer and allocate nothing)
+int vh_op_token_features(const void* hi, const void* lo, int form, int batch, int tokens, int dim, const float* gamma, const float* beta,
+                         float eps, int elem, int norm, void* patch_out, void* mean_out, void* stream) {
+    FeatureArgs a{hi, lo, form, batch, tokens, dim, gamma, beta, eps, elem, norm, nullptr, patch_out, mean_out, nullptr};
+    if (const char* why = features_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    if (mean_out && norm == VH_FEAT_NORM) OPCHK(hipMalloc((void**)&a.stats, (size_t)batch * tokens * 2 * sizeof(float)));
+    hipError_t e = launch_token_features(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (a.stats) hipFree(a.stats);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "token_features failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 int vh_op_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind, float sigma, void* stream) {

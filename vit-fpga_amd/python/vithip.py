@@ -73,6 +73,16 @@ class FrameYUY2(C.Structure):
                 ("layout", C.c_int32), ("box", C.c_float * 4)]
 
 
+FEAT_NORM, FEAT_RAW = 0, 1   # vh_features.norm (VH_FEAT_*): through the model's final LayerNorm / the residual stream as it is
+FEAT_FORM_F32 = -1           # op_token_features: fp32 rows instead of split planes (DTYPE_* = the planes of that path)
+
+
+class Features(C.Structure):
+    """vh_features: where the token features of the last forward go (host or device pointers, None = not wanted), their element
+    type (ELEM_F32 / ELEM_F16 / ELEM_BF16) and FEAT_NORM / FEAT_RAW.  32 bytes."""
+    _fields_ = [("cls", C.c_void_p), ("patch", C.c_void_p), ("mean", C.c_void_p), ("elem", C.c_int32), ("norm", C.c_int32)]
+
+
 L422_YUYV, L422_UYVY, L422_YVYU, L422_VYUY, L422_V210 = range(5)   # vh_frame_yuy2.layout (VH_422_*); V210: the 16-bit entry points only
 class FrameBGRA(C.Structure):
     """vh_frame_bgra: one packed 4:4:4 frame (one plane of pixels whose samples lie as `layout`, L444_*, says) inside the buffer of a
@@ -207,6 +217,10 @@ SYMBOLS = {
     "vh_get_step_timing": (_i, [_vp, C.POINTER(C.c_double), _i, _pi]),
     "vh_debug_read": (_i, [_vp, _i, _vp, _sz]),
     "vh_debug_set_layers": (_i, [_vp, _i]),
+    "vh_features_dims": (_i, [_vp, _pi, _pi, _pi, _pi]),
+    "vh_read_features": (_i, [_vp, _vp]),
+    "vh_read_features_device": (_i, [_vp, _vp]),
+    "vh_read_features_device_async": (_i, [_vp, _vp]),
     "vh_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -240,6 +254,7 @@ SYMBOLS = {
     "vh_op_resize_bgra": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_y410": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
     "vh_group_create": (_i, [C.POINTER(Config), _pi, _i, C.POINTER(_vp)]),
@@ -1362,6 +1377,38 @@ class VitContext:
     def debug_set_layers(self, n):
         _check(lib().vh_debug_set_layers(self.h, n), self.h)
 
+    # ---- token features of the last forward (vithip.h "Token features") ----
+    def features_dims(self):
+        """(batch of the last forward, tokens, patches, dim)."""
+        b, t, n, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().vh_features_dims(self.h, C.byref(b), C.byref(t), C.byref(n), C.byref(d)), self.h)
+        return b.value, t.value, n.value, d.value
+
+    def read_features(self, cls=True, patch=True, mean=False, elem=ELEM_F32, norm=FEAT_NORM):
+        """The requested outputs of the last forward as numpy arrays: {"cls": [B, D], "patch": [B, NP, D], "mean": [B, D]} of
+        float32 / float16, or uint16 holding bf16 bits for ELEM_BF16 (from16 widens them)."""
+        b, _, n, d = self.features_dims()
+        dt = {ELEM_F32: np.float32, ELEM_F16: np.float16, ELEM_BF16: np.uint16}.get(elem, np.float32)
+        b1 = max(b, 1)   # (before the first forward the call is refused below, with the library's message)
+        out = {}
+        if cls:
+            out["cls"] = np.empty((b1, d), dtype=dt)
+        if patch:
+            out["patch"] = np.empty((b1, n, d), dtype=dt)
+        if mean:
+            out["mean"] = np.empty((b1, d), dtype=dt)
+        desc = Features(*(out[k].ctypes.data if k in out else None for k in ("cls", "patch", "mean")), elem, norm)
+        _check(lib().vh_read_features(self.h, C.byref(desc)), self.h)
+        return out
+
+    def read_features_device(self, desc):
+        """desc: a Features of device pointers (16-byte aligned); enqueues on the context's stream and waits."""
+        _check(lib().vh_read_features_device(self.h, C.byref(desc)), self.h)
+
+    def read_features_device_async(self, desc):
+        """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
+        _check(lib().vh_read_features_device_async(self.h, C.byref(desc)), self.h)
+
 
 def group_shard_bounds(batch, n, r):
     lo, hi = C.c_int(0), C.c_int(0)
@@ -1602,6 +1649,12 @@ def bench_gemm(M, N, K, epilogue, dtype=DTYPE_BF16, variant=0, iters=20, device=
     ms = C.c_double(0)
     _check(lib().vh_bench_gemm(device, M, N, K, epilogue, dtype, variant, iters, C.byref(ms)))
     return ms.value
+
+
+def op_token_features(hi_ptr, lo_ptr, form, batch, tokens, dim, gamma_ptr, beta_ptr, eps, elem, norm, patch_ptr, mean_ptr):
+    """The token-feature kernels on rows made by the caller: split planes (form DTYPE_BF16 / DTYPE_FP16 / DTYPE_FP8) or fp32 rows
+    (FEAT_FORM_F32, lo_ptr None) -> patch [batch, tokens - 1, dim] and / or mean [batch, dim] of `elem`."""
+    _check(lib().vh_op_token_features(hi_ptr, lo_ptr, form, batch, tokens, dim, gamma_ptr, beta_ptr, eps, elem, norm, patch_ptr, mean_ptr, None))
 
 
 def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr, dtype):
