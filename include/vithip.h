@@ -61,7 +61,7 @@ extern "C" {
 /* Vision-Transformer shape.  Replaces the role `net::net_data` (def/defines.h:14-23) plays
  * for the MLP: it is what sizes the device buffers (_init_kernel, netFPGA.cpp:402-441). */
 typedef struct vh_config {
-    int32_t image_size; /* square input side, e.g. 224; tokens = (image_size / patch_size)^2 + 1 <= 4097, and
+    int32_t image_size; /* square input side, e.g. 224; tokens = (image_size / patch_size)^2 + 1 + registers <= 4097, and
                          * max_batch x tokens <= 640 x 2^20                                                   */
     int32_t patch_size; /* any divisor of image_size up to 256, e.g. 14 or 16 (the patch GEMM runs on the patch
                          * vector patch^2 * channels zero-padded to a multiple of 64)                         */
@@ -130,6 +130,30 @@ typedef struct vh_config {
  * the logits of such a context are the CLIP image embedding. */
 #define VH_FLAG_PRE_LN 16
 #define VH_FLAG_QUICK_GELU 32
+/* Register tokens (DINOv2 "with registers" and every tower trained like it): R learned rows between the class token and the patch
+ * rows of every image.  The count travels in bits 9 .. 13 of flags (bit 8 stays an unknown bit, as it was), 0 .. 16 (17 .. 31 are refused); it describes the MODEL, so the
+ * blob header's flags word carries it in the same bits and a blob whose count differs from the context's is refused.  Independent
+ * of every other flag and of the dtype.
+ *   tokens T = (image_size / patch_size)^2 + 1 + R; the bounds on tokens (<= 4097, max_batch x tokens <= 640 x 2^20) apply to that
+ *   number, so a 64 x 64 grid takes no register.  VH_FLAG_CLS_TAIL keeps its T <= 1024 condition.
+ *   Blob: `pos` stays [(NP + 1)][D] (registers carry no position embedding); a tensor `reg` [R][D] follows it directly, in front
+ *   of pre_ln.* when both are present.  vh_init_weights_seeded: tensor id 7, sigma as `cls`, offset 0.
+ *   Row order of the residual stream (Hugging Face's hidden_states order), NP = patches per image:
+ *     row 0          = cls + pos[0]                      (one fp32 addition)
+ *     rows 1 .. R    = reg[r]                            (the fp32 value as it is)
+ *     row 1 + R + p  = patch embedding of p + pos[1 + p] (the bits of an R = 0 context's row 1 + p)
+ *   On the fp32 residual paths the leading rows hold exactly those fp32 numbers.  On the split-residual path (folded 16-bit, dim %
+ *   256 == 0) a leading row of value x is stored like every other row: hi = the 16-bit rounding of x, lo = the scaled e4m3 byte of
+ *   x - hi, with the per-64-column (sum, sum of squares) of the fp32 x beside it -- vh_debug_read returns hi + decode(lo).
+ *   With R = 0 every kernel writes the bytes it wrote before the flag existed.
+ * Token features skip the register rows: cls <- row 0, patch[b][p] <- row 1 + R + p, mean over those NP rows.  The register rows
+ * themselves (DINOv2's x_norm_regtokens) are not a field of vh_features, a fixed 32-byte struct; vh_debug_read of the hidden state
+ * returns them.  The opt-in fused patch loader (VH_PATCH_FUSED=1) is not extended: a context with R > 0 takes the im2col + GEMM
+ * path whatever the environment says. */
+#define VH_FLAG_REGISTERS(n) (((n) & 31) << 9)
+#define VH_FLAG_REGISTERS_MASK (31 << 9)
+#define VH_FLAG_REGISTERS_OF(flags) (((flags) & VH_FLAG_REGISTERS_MASK) >> 9)
+#define VH_MAX_REGISTERS 16
 
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
@@ -156,6 +180,8 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out);
 /* replaces cleanup() + ~net_fpga (netFPGA.cpp:613-651); frees ALL device memory. */
 int vh_destroy(vh_ctx* ctx);
 int vh_get_config(const vh_ctx* ctx, vh_config* out);
+/* the number of register tokens of the context (VH_FLAG_REGISTERS_OF(flags)); -1 for a NULL context */
+int vh_get_register_tokens(const vh_ctx* ctx);
 /* *on = 1 when this context folds its LayerNorms into the GEMMs (vh_config.flags, model shape, dtype) */
 int vh_get_ln_fold(const vh_ctx* ctx, int* on);
 /* the fold's run-time guard (see VH_FLAG_LN_FOLD_*): *max_ratio = the largest |row mean| / row sigma any LayerNorm input
@@ -169,7 +195,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -188,7 +214,7 @@ int vh_export_weights_device(vh_ctx* ctx, void* dev_blob, size_t nbytes);
  * byte, plus an FNV-1a-64 checksum of the parameter bytes in header words that memory blobs leave zero.
  *   vh_blob_file_config: host only (no device needed) -- validates magic / shape / file length and fills the model
  *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create;
- *                        cfg->flags = the model bits VH_FLAG_PRE_LN / VH_FLAG_QUICK_GELU of the header);
+ *                        cfg->flags = the model bits VH_FLAG_PRE_LN / VH_FLAG_QUICK_GELU / VH_FLAG_REGISTERS(n) of the header);
  *   vh_save_weights_file: writes <path>.tmp then renames; vh_load_weights_file: verifies length, shape, checksum. */
 int vh_blob_file_config(const char* path, vh_config* cfg);
 /* host only: the file as a MEMORY blob (what vh_load_weights takes): length, header and checksum verified, checksum
@@ -714,9 +740,10 @@ int vh_debug_set_layers(vh_ctx* ctx, int n_layers);
  * forward entry point knows of them.
  *
  *   cls    [batch][D]        the class-token row of every image
- *   patch  [batch][NP][D]    the other rows, NP = tokens - 1
+ *   patch  [batch][NP][D]    the patch rows, NP = (image_size / patch_size)^2 = tokens - 1 - R (R register tokens: rows 1 .. R of
+ *                            an image are skipped, VH_FLAG_REGISTERS)
  *   mean   [batch][D]        the mean of an image's patch rows
- * D = vh_config.dim, tokens = (image_size / patch_size)^2 + 1, batch = the last forward's (vh_features_dims).  A NULL pointer:
+ * D = vh_config.dim, tokens = NP + 1 + R, batch = the last forward's (vh_features_dims).  A NULL pointer:
  * that output is not wanted and nothing is written for it.
  *
  * WHICH FORWARD.  The last one enqueued on the context through any entry point (fp32, 8-bit, tensor, any frames format; eager or
@@ -734,10 +761,10 @@ int vh_debug_set_layers(vh_ctx* ctx, int n_layers);
  *   VH_FEAT_NORM   fp32, two passes: mean = sum(x) / D, var = sum((x - mean)^2) / D, rstd = 1 / sqrtf(var + ln_eps),
  *                  v = fmaf((x - mean) * rstd, gamma[k], beta[k]) with the final LayerNorm's gamma / beta.  The order of the two
  *                  row sums depends on D alone: never on the batch, the row, the element type or the outputs requested.
- *   patch[b][p]    v of row b * tokens + 1 + p.
+ *   patch[b][p]    v of row b * tokens + 1 + R + p.
  *   cls[b]         RAW: v of row b * tokens.  NORM: the vector the head multiplied (vh_debug_read(ctx, 1)), so that head(cls)
  *                  reproduces the logits.
- *   mean[b][k]     (((0 + v[b,1,k]) + v[b,2,k]) + ... + v[b,NP,k]) * inv: plain fp32 adds over the tokens ascending, of the
+ *   mean[b][k]     (((0 + v[b,1+R,k]) + v[b,2+R,k]) + ... + v[b,NP+R,k]) * inv: plain fp32 adds over the NP patch rows ascending, of the
  *                  UNROUNDED fp32 v, inv = (float)(1.0 / NP).
  *   elem           a 16-bit output is the round-to-nearest-even of exactly the fp32 value VH_ELEM_F32 would have written.
  * Image i's outputs never depend on the other images or on the batch size.
@@ -838,6 +865,20 @@ int vh_op_gemm_layout(const void* a16_dev, const void* w16_dev, const float* bia
                       int64_t M, int N, int K, int epilogue, const float* aux_dev, int aux_i,
                       const float* stats_dev, void* out16_dev, float* partials_dev, int dtype, int variant,
                       int out_tiled, int ab_tiled, int tile_begin, int tile_count, void* stream);
+/* Test taps of the register-token assembly (VH_FLAG_REGISTERS; every vh_op_gemm* tap above keeps lead = 1).
+ *   vh_op_gemm_lead  the VH_EPI_PATCH / VH_EPI_PATCH_SPLIT epilogues with `lead` = 1 + R rows in front of an image's patch rows:
+ *                    GEMM row m = img * aux_i + p lands on output row m + img * lead + lead and adds pos row 1 + p (aux_dev
+ *                    [(aux_i + 1)][N]).  M a whole number of images, 1 <= lead <= 17; out_dev (and out16_dev) hold
+ *                    (M / aux_i) * (aux_i + lead) rows; PATCH_SPLIT: partials_dev [N/64][prow][2], prow = 0 for that row count.
+ *   vh_op_lead_rows  the kernels that write the `lead` leading rows of every image: row 0 = cls + pos[0], row 1 + r = reg[r].
+ *                    lo_dev NULL: fp32 rows x_or_hi_dev [batch * tokens][dim] (partials_dev, prow, dtype unused); otherwise the
+ *                    split planes (hi 16-bit of `dtype`, lo one scaled e4m3 byte) and the rows' per-64-column (sum, sum of
+ *                    squares) in partials_dev [dim/64][prow][2], prow >= batch * tokens.  dim % 64 == 0, lead < tokens. */
+int vh_op_gemm_lead(const void* a16_dev, const void* w16_dev, const float* bias_dev, void* out_dev, int64_t M, int N, int K,
+                    int epilogue, const float* aux_dev, int aux_i, int lead, void* out16_dev, float* partials_dev, int64_t prow,
+                    int dtype, int variant, void* stream);
+int vh_op_lead_rows(void* x_or_hi_dev, void* lo_dev, float* partials_dev, int64_t prow, const float* cls_dev, const float* pos_dev,
+                    const float* reg_dev, int lead, int batch, int tokens, int dim, int dtype, void* stream);
 int vh_op_gemm_fp8_layout(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M,
                           int N, int K, int epilogue, const float* c_dev, const float* stats_dev, void* out16,
                           float* partials, int variant, int out_tiled, int ab_tiled, int tile_begin, int tile_count,

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """tools/isa_diff.py <dir A> <dir B>: compare, kernel by kernel, the gfx950 assembly of two builds of the csrc sources
 (directories of *-hip-amdgcn-amd-amdhsa-gfx950.s files as tools/isa.sh / -save-temps=obj leave them).  Prints the kernels whose
-instruction stream differs, the kernels only one side has, and per new kernel its register / spill numbers."""
+instruction stream differs, the kernels only one side has, and per new kernel its register / spill numbers.
+--ignore-params: match template kernels by name and template arguments alone, so that a kernel whose PARAMETER LIST changed (a
+mangled name with another tail) is still compared with its predecessor instead of showing up as one removed and one new."""
 import glob
 import os
 import re
@@ -36,17 +38,39 @@ def meta(path):
     return res
 
 
-a_dir, b_dir = sys.argv[1], sys.argv[2]
-same = diff = 0
+args = [a for a in sys.argv[1:] if a != "--ignore-params"]
+IGNORE_PARAMS = len(args) != len(sys.argv) - 1
+a_dir, b_dir = args[0], args[1]
+
+
+def key(name):
+    # _Z<name>I<template args>E E v <parameters>: a templated kernel returns void, so its parameters start behind the last "EEv"
+    i = name.rfind("EEv")
+    return name[:i + 2] if IGNORE_PARAMS and i > 0 else name
+
+
+def offsets_only(a, b):
+    """The same instructions except for the immediate offset of scalar loads from the kernel-argument segment: what a grown
+    parameter list does to a kernel that does not use the new parameter."""
+    if len(a) != len(b):
+        return False
+    strip = lambda t: re.sub(r"(s_load_dword\w*\s+s\S+\s+s\[\d+:\d+\],)\s*\S+$", r"\1", t)
+    return all(x == y or (x.startswith("s_load_dword") and strip(x) == strip(y)) for x, y in zip(a, b))
+
+
+same = diff = moved = 0
 for fa in sorted(glob.glob(os.path.join(a_dir, "*gfx950.s"))):
     fb = os.path.join(b_dir, os.path.basename(fa))
-    ka, kb = kernels(fa), kernels(fb)
-    mb = meta(fb)
+    ka, kb = ({key(k): v for k, v in kernels(f).items()} for f in (fa, fb))
+    mb = {key(k): v for k, v in meta(fb).items()}
     for k in sorted(ka):
         if k not in kb:
             print(f"ONLY IN A  {k}")
         elif ka[k] == kb[k]:
             same += 1
+        elif offsets_only(ka[k], kb[k]):
+            moved += 1
+            print(f"ARG OFFSET {k}  ({len(ka[k])} instructions; only the offsets of kernel-argument loads differ)")
         else:
             diff += 1
             print(f"DIFFERS    {k}  ({len(ka[k])} -> {len(kb[k])} instructions)")
@@ -55,4 +79,4 @@ for fa in sorted(glob.glob(os.path.join(a_dir, "*gfx950.s"))):
         nexp = sum(t.startswith(("v_exp_f32", "v_rcp_f32")) for t in kb[k])
         npk = sum(t.startswith("v_pk_") for t in kb[k])
         print(f"NEW        {k}  {n} instructions ({npk} packed, {nexp} v_exp/v_rcp)  sgpr/vgpr/spill {mb.get(k)}")
-print(f"{same} kernels identical, {diff} differ")
+print(f"{same} kernels identical, {moved} with moved kernel-argument offsets only, {diff} differ")

@@ -49,6 +49,7 @@ struct EpiArgs {
     void* out16;         // RESID_LN: 16-bit copy of the updated residual [M, N]
     float* partials;     // RESID_LN: [N/64][M][2] = per-64-column (sum, sum of squares)
     int64_t prow;        // PATCH_SPLIT: row stride of `partials` (token rows); the other forms use M
+    int lead;            // PATCH / PATCH_SPLIT: rows in front of an image's patch rows (class token + register tokens)
 };
 
 constexpr bool epi_has_qgelu(int epi) { return epi == VH_EPI_BIAS_QGELU || epi == VH_EPI_LNFOLD_QGELU; }
@@ -212,7 +213,7 @@ __device__ __forceinline__ void gemm_epilogue_impl(const f32x4 (&acc)[MI][NI], c
         const float* posrow = nullptr;
         if constexpr (EPI == VH_EPI_PATCH) {
             const int img = m / e.aux_i, p = m - img * e.aux_i;
-            orow = (int64_t)img * (e.aux_i + 1) + 1 + p;
+            orow = (int64_t)img * (e.aux_i + e.lead) + e.lead + p;
             posrow = e.aux + (int64_t)(1 + p) * N;
         }
         float rstd = 0.f, mr = 0.f;
@@ -493,7 +494,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const f32x4 (&acc)[MI][NI],
         // split residual: stage acc + bias as fp32 rows (256 B, chunk ^ (r & 15)) like the fp32 form, read back EIGHT columns per
         // lane (two chunks): the hi plane is accessed 16 B per lane / 128 B per row, the one-byte lo plane 8 B per lane / 64 B per row.  What the row
         // ADDS -- its own planes (RESID_SPLIT) or the position embedding's fp32 row (PATCH_SPLIT: the patch embedding lands
-        // directly in the split form, on the remapped row m + m / patches + 1, with the first row statistics) -- is loaded for
+        // directly in the split form, on the remapped row m + (m / patches + 1) * lead, with the first row statistics) -- is loaded for
         // pass h+1 before pass h is processed (same reason as in the fp32 form below).
         using vec8 = typename T::vec8;
         constexpr bool PATCHS = EPI == VH_EPI_PATCH_SPLIT;
@@ -505,18 +506,19 @@ __device__ __forceinline__ void gemm_epilogue_staged(const f32x4 (&acc)[MI][NI],
         // 8 fp32 addends per lane and line: RESID_SPLIT converts its two 16-bit planes on use, PATCH_SPLIT loads them as is
         struct Add { vec8 h; u32x2 l; f32x4 p0, p1; };
         Add xa[2][NL];
-        // PATCH_SPLIT: GEMM row m = image * patches + p lands on token row m + image + 1 and adds pos row 1 + p.  One scalar
+        // PATCH_SPLIT: GEMM row m = image * patches + p lands on token row m + (image + 1) * lead and adds pos row 1 + p.  One scalar
         // division per wave tile (m_w is wave-uniform), then a carry per row instead of a vector division per line.
         const int q0 = PATCHS ? m_w / e.aux_i : 0, r0 = PATCHS ? m_w - q0 * e.aux_i : 0;
+        const int lead0 = PATCHS ? (q0 + 1) * e.lead : 0;
         auto where = [&](int h, int i, int& m, int64_t& orow, int& p) {   // GEMM row m -> output row, element offset of the lane's 8 columns
             const int dr = h * FMI * 16 + i * 8 + rr;
             m = m_w + dr;
             p = 0;
             if constexpr (PATCHS) {
-                int img = q0;
+                int add = lead0;   // (image + 1) * lead
                 p = r0 + dr;
-                while (p >= e.aux_i) { p -= e.aux_i; ++img; }
-                orow = (int64_t)m + img + 1;
+                while (p >= e.aux_i) { p -= e.aux_i; add += e.lead; }
+                orow = (int64_t)m + add;
             } else {
                 orow = m;
             }

@@ -95,12 +95,12 @@ __device__ __forceinline__ void store8(typename OUT::elem* p, const float* v) {
     }
 }
 
-// rows = batch * tokens.  Row r = image r / tokens, token r % tokens: token 0 goes to cls_out [batch][dim], token t > 0 to
-// patch_out [batch][tokens - 1][dim]; either may be null.  norm != 0: the row passes LayerNorm(gamma, beta, eps), and
+// rows = batch * tokens.  Row r = image r / tokens, token r % tokens: token 0 goes to cls_out [batch][dim], token t >= lead to
+// patch_out [batch][tokens - lead][dim]; either may be null.  Tokens 1 .. lead - 1 (register tokens) go nowhere.  norm != 0: the row passes LayerNorm(gamma, beta, eps), and
 // stats (optional) receives (mean, rstd) of every patch row.  A wave whose row has nothing to write leaves at once.
 template <typename IN, typename OUT, int CH>   // CH = pieces of 8 elements per lane (dim <= 512 * CH)
 __global__ void __launch_bounds__(256)
-feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t rows, int tokens, int dim,
+feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t rows, int tokens, int lead, int dim,
                  const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int norm,
                  typename OUT::elem* __restrict__ cls_out, typename OUT::elem* __restrict__ patch_out, float* __restrict__ stats) {
     const int lane = threadIdx.x & 63;
@@ -110,8 +110,8 @@ feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64
     const int t = (int)(row - img * tokens);
     typename OUT::elem* out = nullptr;
     if (t == 0) { if (cls_out) out = cls_out + img * dim; }
-    else if (patch_out) out = patch_out + (img * (tokens - 1) + (t - 1)) * dim;
-    const bool want_stats = norm && stats && t != 0;
+    else if (t >= lead && patch_out) out = patch_out + (img * (tokens - lead) + (t - lead)) * dim;
+    const bool want_stats = norm && stats && t >= lead;
     if (!out && !want_stats) return;   // wave-uniform
     const int npiece = dim >> 3;
     float v[CH][8];
@@ -167,11 +167,11 @@ feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64
     }
 }
 
-// mean_out[b][k] = (((0 + v[b,1,k]) + v[b,2,k]) + ... + v[b,tokens-1,k]) * inv, v as feat_rows_kernel writes it in fp32.
+// mean_out[b][k] = (((0 + v[b,lead,k]) + v[b,lead+1,k]) + ... + v[b,tokens-1,k]) * inv, v as feat_rows_kernel writes it in fp32.
 // One thread per image and four columns; n4 = batch * dim / 4 threads.
 template <typename IN, typename OUT>
 __global__ void __launch_bounds__(256)
-feat_mean_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t n4, int tokens, int dim,
+feat_mean_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t n4, int tokens, int lead, int dim,
                  const float* __restrict__ gamma, const float* __restrict__ beta, int norm, const float* __restrict__ stats,
                  float inv, typename OUT::elem* __restrict__ mean_out) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -184,7 +184,7 @@ feat_mean_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     const int64_t row0 = img * tokens;
 #pragma unroll 4
-    for (int t = 1; t < tokens; ++t) {
+    for (int t = lead; t < tokens; ++t) {
         const int64_t row = row0 + t;
         float x[4];
         load_x<IN, 4>(hi, lo, row * dim + k, x);
@@ -210,7 +210,7 @@ hipError_t feat_launch(const FeatureArgs& a, hipStream_t s) {
     if (a.cls || a.patch || mean_norm) {   // (a raw mean needs no row pass: nothing to normalise, no statistics)
         const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
         float* st = mean_norm ? a.stats : nullptr;
-#define VH_FEAT_ROWS(CH) hipLaunchKernelGGL((feat_rows_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, rows, a.tokens, a.dim, \
+#define VH_FEAT_ROWS(CH) hipLaunchKernelGGL((feat_rows_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, rows, a.tokens, a.lead, a.dim, \
                                             a.gamma, a.beta, a.eps, norm, (E*)a.cls, (E*)a.patch, st)
         if (a.dim <= 512) VH_FEAT_ROWS(1);
         else if (a.dim <= 1024) VH_FEAT_ROWS(2);
@@ -222,8 +222,8 @@ hipError_t feat_launch(const FeatureArgs& a, hipStream_t s) {
     }
     if (a.mean) {
         const int64_t n4 = (int64_t)a.batch * (a.dim >> 2);
-        const float inv = (float)(1.0 / (double)(a.tokens - 1));
-        hipLaunchKernelGGL((feat_mean_kernel<IN, OUT>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.hi, a.lo, n4, a.tokens, a.dim,
+        const float inv = (float)(1.0 / (double)(a.tokens - a.lead));
+        hipLaunchKernelGGL((feat_mean_kernel<IN, OUT>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.hi, a.lo, n4, a.tokens, a.lead, a.dim,
                            a.gamma, a.beta, norm, a.stats, inv, (E*)a.mean);
         return hipGetLastError();
     }
@@ -248,6 +248,7 @@ const char* features_check(const FeatureArgs& a) {
     if (a.form != VH_FEAT_FORM_F32 && !a.lo) return "token_features: split planes need the lo plane";
     if (a.batch <= 0 || a.batch > (1 << 20)) return "token_features: batch outside 1..2^20";
     if (a.tokens < 2) return "token_features: tokens below 2 (no patch token)";
+    if (a.lead < 1 || a.lead >= a.tokens) return "token_features: lead rows outside 1 .. tokens - 1";
     if (a.tokens > kAttnStreamMaxTokens) return "token_features: tokens above 4097";
     if (a.dim < 64) return "token_features: dim below 64";
     if (a.dim > 2048) return "token_features: dim above 2048";

@@ -237,36 +237,44 @@ hipError_t launch_im2col_u8(const uint8_t* in, int batch, int image, int patch, 
     return hipGetLastError();
 }
 
-// ---- x[b, 0, :] = cls + pos[0] ------------------------------------------------------------------
-__global__ void cls_rows_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
-                                int batch, int tokens, int dim) {
+// ---- the leading rows of every image: x[b, 0, :] = cls + pos[0], x[b, 1 + r, :] = reg[r] (register tokens) ----
+// lead = 1 + R rows per image; reg is not read when lead == 1
+__global__ void lead_rows_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
+                                 const float* __restrict__ reg, int lead, int batch, int tokens, int dim) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)batch * dim) return;
-    const int b = (int)(i / dim), d = (int)(i - (int64_t)b * dim);
-    x[(int64_t)b * tokens * dim + d] = cls[d] + pos[d];
+    const int64_t per = (int64_t)lead * dim;
+    if (i >= (int64_t)batch * per) return;
+    const int b = (int)(i / per);
+    const int e = (int)(i - (int64_t)b * per);   // row j = e / dim of the image, column e % dim: the rows are contiguous
+    x[(int64_t)b * tokens * dim + e] = e < dim ? cls[e] + pos[e] : reg[e - dim];
 }
-hipError_t launch_cls_rows(float* x, const float* cls, const float* pos, int batch, int tokens, int dim, hipStream_t s) {
-    const int64_t n = (int64_t)batch * dim;
-    hipLaunchKernelGGL(cls_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, cls, pos, batch, tokens, dim);
+hipError_t launch_lead_rows(float* x, const float* cls, const float* pos, const float* reg, int lead, int batch, int tokens, int dim,
+                            hipStream_t s) {
+    if (batch <= 0 || lead < 1 || lead > tokens || (lead > 1 && !reg)) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)batch * lead * dim;
+    hipLaunchKernelGGL(lead_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, cls, pos, reg, lead, batch, tokens, dim);
     return hipGetLastError();
 }
 
-// the same rows for the SPLIT residual (PATCH_SPLIT path): planes hi = T(x), lo = T(x - hi) of x = cls + pos[0], and the
-// row's (sum, sum of squares) per 64-column block -- what the patch GEMM's epilogue writes for every other row.  One wave
-// per image; a lane owns column 64 * blk + lane of every block; fixed-order butterfly sums.
+// the same rows for the SPLIT residual (PATCH_SPLIT path): planes hi = T(x), lo = lo8(x - hi) of x = cls + pos[0] or reg[r], and
+// the row's (sum, sum of squares) per 64-column block -- what the patch GEMM's epilogue writes for every other row.  One wave
+// per (image, leading row); a lane owns column 64 * blk + lane of every block; fixed-order butterfly sums.
 template <typename T>
 __global__ void __launch_bounds__(256)
-cls_rows_split_kernel(typename T::elem* __restrict__ hi, uint8_t* __restrict__ lo, float* __restrict__ partials, int64_t prow,
-                      const float* __restrict__ cls, const float* __restrict__ pos, int batch, int tokens, int dim) {
+lead_rows_split_kernel(typename T::elem* __restrict__ hi, uint8_t* __restrict__ lo, float* __restrict__ partials, int64_t prow,
+                       const float* __restrict__ cls, const float* __restrict__ pos, const float* __restrict__ reg, int lead,
+                       int batch, int tokens, int dim) {
     const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = w / lead, j = w - b * lead;
     if (b >= batch) return;
-    const int64_t row = (int64_t)b * tokens;
+    const int64_t row = (int64_t)b * tokens + j;
+    const float* const src = j ? reg + (int64_t)(j - 1) * dim : cls;
     for (int blk = 0; blk * 64 < dim; ++blk) {
         const int d = blk * 64 + lane;
         float v = 0.f;
         if (d < dim) {
-            v = cls[d] + pos[d];
+            v = j ? src[d] : src[d] + pos[d];
             const typename T::elem h = (typename T::elem)v;
             hi[row * dim + d] = h;
             lo[row * dim + d] = lo8_pack1<T>(v - (float)h);
@@ -277,14 +285,14 @@ cls_rows_split_kernel(typename T::elem* __restrict__ hi, uint8_t* __restrict__ l
         if (lane == 0) *(float2*)(partials + 2 * ((int64_t)blk * prow + row)) = make_float2(s1, s2);
     }
 }
-hipError_t launch_cls_rows_split(void* hi, void* lo, float* partials, int64_t prow, const float* cls, const float* pos, int batch,
-                                 int tokens, int dim, int dtype, hipStream_t s) {
-    if (batch <= 0 || dim % 64) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((batch + 3) / 4));
+hipError_t launch_lead_rows_split(void* hi, void* lo, float* partials, int64_t prow, const float* cls, const float* pos, const float* reg,
+                                  int lead, int batch, int tokens, int dim, int dtype, hipStream_t s) {
+    if (batch <= 0 || dim % 64 || lead < 1 || lead > tokens || (lead > 1 && !reg) || prow < (int64_t)batch * tokens) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)batch * lead + 3) / 4));
     if (dtype == VH_DTYPE_BF16)
-        hipLaunchKernelGGL(cls_rows_split_kernel<BF16>, grid, dim3(256), 0, s, (BF16::elem*)hi, (uint8_t*)lo, partials, prow, cls, pos, batch, tokens, dim);
+        hipLaunchKernelGGL(lead_rows_split_kernel<BF16>, grid, dim3(256), 0, s, (BF16::elem*)hi, (uint8_t*)lo, partials, prow, cls, pos, reg, lead, batch, tokens, dim);
     else
-        hipLaunchKernelGGL(cls_rows_split_kernel<FP16>, grid, dim3(256), 0, s, (FP16::elem*)hi, (uint8_t*)lo, partials, prow, cls, pos, batch, tokens, dim);
+        hipLaunchKernelGGL(lead_rows_split_kernel<FP16>, grid, dim3(256), 0, s, (FP16::elem*)hi, (uint8_t*)lo, partials, prow, cls, pos, reg, lead, batch, tokens, dim);
     return hipGetLastError();
 }
 

@@ -131,7 +131,7 @@ patch_gemm_fused_kernel(const float* __restrict__ img, const typename T::elem* _
         if (kt + 1 < nk) write_a((kt + 1) & 1);            // the other stage: its last reader passed the barrier above
     }
 
-    const EpiArgs e{bias, hi, M, N, pos, np, nullptr, lo, partials, prow};
+    const EpiArgs e{bias, hi, M, N, pos, np, nullptr, lo, partials, prow, 1};   // (no register tokens on this path)
     gemm_epilogue<T, VH_EPI_PATCH_SPLIT, MI, NI>(acc, e, tile_m * BM + wm * 64, tile_n * BN + wn * 64, lane, true, (tile_m + 1) * BM <= M, smem, wave);
 }
 

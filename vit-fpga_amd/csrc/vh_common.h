@@ -190,7 +190,7 @@ __host__ __device__ __forceinline__ float rng_ih4(uint64_t stream, uint64_t i, d
 constexpr double kIH4Std = 37837.22725;
 
 // tensor ids of the canonical blob (same numbers as oracle/ and tests/, by specification)
-enum : uint32_t { TID_PATCH_W = 1, TID_PATCH_B = 2, TID_CLS = 3, TID_POS = 4, TID_PRE_LN_W = 5, TID_PRE_LN_B = 6, TID_LAYER0 = 16,
+enum : uint32_t { TID_PATCH_W = 1, TID_PATCH_B = 2, TID_CLS = 3, TID_POS = 4, TID_PRE_LN_W = 5, TID_PRE_LN_B = 6, TID_REG = 7, TID_LAYER0 = 16,
                   TID_FINAL = 0x7000, TID_IMAGES = 0x100 };
 
 }  // namespace vh

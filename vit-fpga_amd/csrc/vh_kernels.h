@@ -39,6 +39,9 @@ struct GemmArgs {
     // gemm_tiled_applies accepts).  out_tiled: an activation epilogue writes the MLP hidden activation tiled, LNFOLD / 16-bit BIAS
     // write q|k|v head-major; ab_tiled: A and W of this launch are both in the tiled layout (16-row blocks).
     int out_tiled = 0, ab_tiled = 0;
+    // PATCH / PATCH_SPLIT: rows in front of an image's patch rows (the class token + the register tokens): GEMM row m = img * aux_i + p
+    // lands on output row m + img * lead + lead and adds pos row 1 + p.  Every public vh_op_gemm* tap keeps 1.
+    int lead = 1;
 };
 // does a GEMM of this shape and operand dtype take the persistent form, the only one that reads / writes the tiled layouts?
 bool gemm_tiled_applies(int64_t M, int N, int K, int dtype);
@@ -46,11 +49,11 @@ bool gemm_tiled_applies(int64_t M, int N, int K, int dtype);
 hipError_t launch_cast_tiled_w(const float* w, int rows, int cols, void* w16, int dtype, hipStream_t stream);
 hipError_t launch_tile_bytes(const void* w8, int rows, int cols, void* out, hipStream_t stream);
 
-// row stride of the partial-sum buffer a launch writes: PATCH_SPLIT lands on token rows (images x (patches + 1) unless the
+// row stride of the partial-sum buffer a launch writes: PATCH_SPLIT lands on token rows (images x (patches + lead) unless the
 // caller's buffer is laid out for more, e.g. rows padded to whole tiles); the other forms use their own M inside the kernel
 inline int64_t gemm_prow(const GemmArgs& g) {
     if (g.epilogue != VH_EPI_PATCH_SPLIT) return g.M;
-    return g.prow > 0 ? g.prow : (g.M / g.aux_i) * (int64_t)(g.aux_i + 1);
+    return g.prow > 0 ? g.prow : (g.M / g.aux_i) * (int64_t)(g.aux_i + g.lead);
 }
 
 // every launcher only enqueues on `stream`; returns hipSuccess or the launch error (hipErrorInvalidValue: gemm_check refuses)
@@ -177,11 +180,13 @@ hipError_t launch_resize_bgra(bool wide, const uint8_t* frames, const uint32_t* 
 bool patch_fused_supported(int image, int patch, int channels, int dim);
 hipError_t launch_patch_fused(const float* images, int batch, int image, int patch, int channels, const void* wp16, const float* bias,
                               const float* pos, void* hi, void* lo, float* partials, int64_t prow, int dim, int dtype, hipStream_t stream);
-hipError_t launch_cls_rows(float* x, const float* cls, const float* pos, int batch, int tokens,
-                           int dim, hipStream_t stream);
-// the class-token rows of the SPLIT residual: (hi, lo) planes of cls + pos[0] and their per-64-column partial sums
-hipError_t launch_cls_rows_split(void* hi, void* lo, float* partials, int64_t prow, const float* cls, const float* pos, int batch,
-                                 int tokens, int dim, int dtype, hipStream_t stream);
+// the `lead` = 1 + R leading rows of every image (R register tokens, reg [R][dim], unread when lead == 1): row 0 = cls + pos[0],
+// row 1 + r = reg[r]
+hipError_t launch_lead_rows(float* x, const float* cls, const float* pos, const float* reg, int lead, int batch, int tokens,
+                            int dim, hipStream_t stream);
+// the same rows of the SPLIT residual: their (hi, lo) planes and their per-64-column partial sums
+hipError_t launch_lead_rows_split(void* hi, void* lo, float* partials, int64_t prow, const float* cls, const float* pos,
+                                  const float* reg, int lead, int batch, int tokens, int dim, int dtype, hipStream_t stream);
 hipError_t launch_cast(const float* in, void* out16, int64_t n, int dtype, hipStream_t stream);
 hipError_t launch_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,
                        float sigma, float offset, hipStream_t stream);
@@ -221,9 +226,10 @@ hipError_t launch_layernorm_split(const void* hi, const void* lo, int64_t rows, 
                                   const float* beta, float eps, float* out32, int dtype, hipStream_t stream);
 // Token features (kernels_features.hip; contract: vithip.h, "Token features"): the rows of a residual stream [batch * tokens, dim]
 // -> the caller's element type (VH_ELEM_F32 / F16 / BF16), as they are (VH_FEAT_RAW) or through LayerNorm(gamma, beta, eps)
-// (VH_FEAT_NORM), and the mean over an image's patch tokens (tokens 1 .. tokens - 1, a serial fp32 chain in that order).
+// (VH_FEAT_NORM), and the mean over an image's patch tokens (tokens lead .. tokens - 1, a serial fp32 chain in that order; lead = 1 + the register
+// tokens, which no output receives).
 // form: VH_DTYPE_BF16 / FP16 = split planes (hi 16-bit, lo one scaled e4m3 byte), VH_DTYPE_FP8 = e4m3 hi + bf16 lo,
-// VH_FEAT_FORM_F32 = fp32 rows in `hi`, lo null.  cls [batch][dim] <- token 0, patch [batch][tokens - 1][dim] <- the others, mean
+// VH_FEAT_FORM_F32 = fp32 rows in `hi`, lo null.  cls [batch][dim] <- token 0, patch [batch][tokens - lead][dim] <- tokens lead .., mean
 // [batch][dim]; any may be null, not all.  stats [batch * tokens][2]: scratch of the normalised mean (row kernel writes, mean
 // kernel reads).  features_check: nullptr, or why the launch is refused; host arithmetic only.
 constexpr int VH_FEAT_FORM_F32 = -1;
@@ -240,6 +246,7 @@ struct FeatureArgs {
     void* patch;
     void* mean;
     float* stats;
+    int lead = 1;   // rows in front of an image's patch rows: 1 .. tokens - 1
 };
 const char* features_check(const FeatureArgs& a);
 hipError_t launch_token_features(const FeatureArgs& a, hipStream_t stream);

@@ -56,13 +56,20 @@ struct BlobHeader {
     float ln_eps;
     // on-disk files only (vh_save_weights_file): FNV-1a 64 of the parameter bytes, flags bit 0 = checksum present.
     // Blobs built in memory leave the two checksum words, bit 0 and the padding 0.  flags bits 1 and 2 describe the MODEL, in
-    // memory and on disk alike: bit 1 = pre-LayerNorm (VH_FLAG_PRE_LN: two more tensors), bit 2 = QuickGELU (VH_FLAG_QUICK_GELU).
+    // memory and on disk alike: bit 1 = pre-LayerNorm (VH_FLAG_PRE_LN: two more tensors), bit 2 = QuickGELU (VH_FLAG_QUICK_GELU),
+    // bits 9 .. 13 = the number of register tokens (VH_FLAG_REGISTERS: the tensor reg), in the bits vh_config.flags keeps it in.
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
-constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobModelBits = kBlobPreLn | kBlobQuickGelu;
+constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobRegisters = VH_FLAG_REGISTERS_MASK,
+                   kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobRegisters;
 uint32_t blob_model_bits(const vh_config& c) {
-    return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u);
+    return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u) |
+           ((uint32_t)c.flags & kBlobRegisters);
+}
+// the model flags of a header's flags word (vh_blob_file_config)
+int32_t blob_model_flags(uint32_t bits) {
+    return ((bits & kBlobPreLn) ? VH_FLAG_PRE_LN : 0) | ((bits & kBlobQuickGelu) ? VH_FLAG_QUICK_GELU : 0) | (int32_t)(bits & kBlobRegisters);
 }
 
 uint64_t fnv1a64(const void* data, size_t n, uint64_t h = 0xCBF29CE484222325ull) {
@@ -77,9 +84,11 @@ struct LayerOff {  // offsets in floats from the start of the parameter region
 
 struct Layout {
     int T, NP, KP;   // KP = patch^2 * channels: the patch vector in the blob
+    int R = 0, lead = 1;   // VH_FLAG_REGISTERS: register tokens; lead = 1 + R rows in front of an image's patch rows, T = NP + lead
     int KPA;         // KP rounded up to 64: the compute width of the 16-bit patch operands (wp16, col16, the patch GEMM's K)
     size_t patch_w, patch_b, cls, pos, lnfw, lnfb, headw, headb, total;
-    size_t prew = 0, preb = 0;   // VH_FLAG_PRE_LN: pre_ln.weight / pre_ln.bias [D], directly after pos
+    size_t reg = 0;              // VH_FLAG_REGISTERS: reg [R][D], directly after pos ([(NP + 1)][D]: registers carry no position row)
+    size_t prew = 0, preb = 0;   // VH_FLAG_PRE_LN: pre_ln.weight / pre_ln.bias [D], directly after pos / reg
     std::vector<LayerOff> layer;
 };
 
@@ -88,12 +97,15 @@ Layout make_layout(const vh_config& c) {
     const size_t D = c.dim, M = c.mlp_dim, C = c.classes;
     const int g = c.image_size / c.patch_size;
     L.NP = g * g;
-    L.T = L.NP + 1;
+    L.R = VH_FLAG_REGISTERS_OF(c.flags);
+    L.lead = 1 + L.R;
+    L.T = L.NP + L.lead;
     L.KP = c.patch_size * c.patch_size * c.channels;
     L.KPA = (L.KP + 63) / 64 * 64;
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += n; return r; };
-    L.patch_w = take(D * L.KP); L.patch_b = take(D); L.cls = take(D); L.pos = take((size_t)L.T * D);
+    L.patch_w = take(D * L.KP); L.patch_b = take(D); L.cls = take(D); L.pos = take((size_t)(L.NP + 1) * D);
+    if (L.R) L.reg = take((size_t)L.R * D);
     if (c.flags & VH_FLAG_PRE_LN) { L.prew = take(D); L.preb = take(D); }
     L.layer.resize(c.layers);
     for (int l = 0; l < c.layers; ++l) {
@@ -112,7 +124,7 @@ Layout make_layout(const vh_config& c) {
 // expected blob size of a configuration computed WITHOUT building the layout (no allocation): used on untrusted headers
 size_t blob_bytes_of(const vh_config& c) {
     const size_t D = c.dim, M = c.mlp_dim, C = c.classes, g = (size_t)(c.image_size / c.patch_size);
-    const size_t T = g * g + 1, KP = (size_t)c.patch_size * c.patch_size * c.channels;
+    const size_t T = g * g + 1 + (size_t)VH_FLAG_REGISTERS_OF(c.flags), KP = (size_t)c.patch_size * c.patch_size * c.channels;   // (pos rows + reg rows)
     const size_t per_layer = 2 * D + 4 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D);
     const size_t pre_ln = (c.flags & VH_FLAG_PRE_LN) ? 2 * D : 0;
     return sizeof(BlobHeader) + 4 * (D * KP + D + D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * D + C);
@@ -132,7 +144,9 @@ const char* check_config(const vh_config& c) {
     if (c.dtype == VH_DTYPE_FP8 && (c.dim % 128 || c.mlp_dim % 128)) return "VH_DTYPE_FP8 needs dim and mlp_dim to be multiples of 128";
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
-    if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU)) return "unknown bits in flags";
+    if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK)) return "unknown bits in flags";
+    const int R = VH_FLAG_REGISTERS_OF(c.flags);
+    if (R > VH_MAX_REGISTERS) return "flags: VH_FLAG_REGISTERS takes 0 .. 16 register tokens";
     if ((c.flags & VH_FLAG_W8_E4M3) && c.dtype == VH_DTYPE_FP8) return "flags: VH_FLAG_W8_E4M3 is for the 16-bit dtypes (VH_DTYPE_FP8 quantises both operands)";
     if ((c.flags & VH_FLAG_W8_E4M3) && (c.dim % 4 || c.mlp_dim % 4)) return "flags: VH_FLAG_W8_E4M3 needs dim and mlp_dim multiples of 4";
     if ((c.flags & VH_FLAG_LN_FOLD_OFF) && (c.flags & VH_FLAG_LN_FOLD_ON)) return "flags: VH_FLAG_LN_FOLD_OFF and VH_FLAG_LN_FOLD_ON exclude each other";
@@ -144,7 +158,8 @@ const char* check_config(const vh_config& c) {
     // largest row count (max_batch x tokens) any model reached while the attention was bounded at 640 tokens
     const int g = c.image_size / c.patch_size;
     if (g > 64) return "tokens <= 4097 (image_size / patch_size <= 64)";
-    if ((int64_t)c.max_batch * (g * g + 1) > (640ll << 20)) return "max_batch x tokens <= 640 x 2^20";
+    if (g * g + 1 + R > 4097) return "tokens <= 4097: a 64 x 64 patch grid + the class token leaves no room for register tokens";
+    if ((int64_t)c.max_batch * (g * g + 1 + R) > (640ll << 20)) return "max_batch x tokens <= 640 x 2^20";
     return nullptr;
 }
 
@@ -467,6 +482,9 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if ((h.flags ^ want) & kBlobQuickGelu)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 2 (QuickGELU) is %d, the context's VH_FLAG_QUICK_GELU is %d",
                     (h.flags & kBlobQuickGelu) != 0, (want & kBlobQuickGelu) != 0);
+    if ((h.flags ^ want) & kBlobRegisters)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bits 9..13 say %d register tokens, the context's VH_FLAG_REGISTERS says %d",
+                    (int)VH_FLAG_REGISTERS_OF(h.flags), (int)VH_FLAG_REGISTERS_OF(want));
     return VH_OK;
 }
 
@@ -569,7 +587,8 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     // the patch embedding lands directly in the split residual's planes (below): the 16-bit split path without a pre-LayerNorm
     const bool patch_split = c->split && !c->fp8 && nl > 0 && !pre_ln;
     // 8-bit images and every other tensor kind: always the im2col pass + the ordinary patch GEMM; the fused loader reads NHWC fp32 only
-    const bool fused_patch = patch_split && in.nhwc_f32() && c->patch_fused && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
+    // register tokens: the fused loader knows one leading row only, so such a context takes the two-kernel path
+    const bool fused_patch = patch_split && L.R == 0 && in.nhwc_f32() && c->patch_fused && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
     if (!fused_patch) {   // (no stage bracket: the profile event is recorded with or without the pass)
         if ((rc = tmark(ST_IM2COL))) return rc;
         if (in.layout == VH_LAYOUT_NHWC && in.u8())
@@ -591,21 +610,24 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, P + L.pos, L.NP);
         g.out16 = xlo16;
         g.prow = rows_g;
+        g.lead = L.lead;
         if ((rc = stage(ST_PATCH, [&] {
                  return fused_patch ? launch_patch_fused((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, c->wp16, P + L.patch_b,
                                                          P + L.pos, xn16, xlo16, partials_p, rows_g, D, dt16, s)
                                     : launch_gemm(g, s);
              })))
             return rc;
-        HIPCHK(&c->err, launch_cls_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, batch, T, D, dt16, s));
-        if ((rc = mark(ST_CLS))) return rc;
+        if ((rc = stage(ST_CLS, [&] {
+                 return launch_lead_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, P + L.reg, L.lead, batch, T, D, dt16, s);
+             })))
+            return rc;
         HIPCHK(&c->err, launch_finalize_stats(partials_p, D / 64, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
         if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark: ST_LNSTATS has no stage timing)
     } else {
-        const GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, P + L.pos, L.NP);
+        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, P + L.pos, L.NP);
+        g.lead = L.lead;
         if ((rc = stage(ST_PATCH, [&] { return launch_gemm(g, s); }))) return rc;
-        HIPCHK(&c->err, launch_cls_rows(x, P + L.cls, P + L.pos, batch, T, D, s));
-        if ((rc = mark(ST_CLS))) return rc;
+        if ((rc = stage(ST_CLS, [&] { return launch_lead_rows(x, P + L.cls, P + L.pos, P + L.reg, L.lead, batch, T, D, s); }))) return rc;
         if (pre_ln) {
             // x <- LN(x) pre_ln.weight + pre_ln.bias, in the form the path consumes: the fp32 array (plain loop, non-split fold, no
             // layer at all), the 16-bit operand copy / the split planes, layer 0's LN1 statistics of the normalised rows and the guards
@@ -1408,6 +1430,7 @@ int vh_get_config(const vh_ctx* c, vh_config* out) {
     return VH_OK;
 }
 
+int vh_get_register_tokens(const vh_ctx* c) { return c ? c->L.R : -1; }
 int vh_get_ln_fold(const vh_ctx* c, int* on) {
     if (!c || !on) return fail(nullptr, VH_ERR_INVALID, "null argument");
     *on = c->ln_fold ? 1 : 0;
@@ -1491,7 +1514,8 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
     GEN(L.patch_w, D * L.KP, TID_PATCH_W, sw, 0.f);
     GEN(L.patch_b, D, TID_PATCH_B, sb, 0.f);
     GEN(L.cls, D, TID_CLS, sw, 0.f);
-    GEN(L.pos, (size_t)L.T * D, TID_POS, sw, 0.f);
+    GEN(L.pos, (size_t)(L.NP + 1) * D, TID_POS, sw, 0.f);
+    if (L.R) GEN(L.reg, (size_t)L.R * D, TID_REG, sw, 0.f);
     if (f.flags & VH_FLAG_PRE_LN) { GEN(L.prew, D, TID_PRE_LN_W, sg, 1.f); GEN(L.preb, D, TID_PRE_LN_B, sb, 0.f); }
     for (int l = 0; l < f.layers; ++l) {
         const LayerOff& o = L.layer[l];
@@ -1542,7 +1566,7 @@ static int blob_file_header(const char* path, vh_config* cfg, size_t* need_out) 
     c.mlp_dim = h.mlp_dim; c.layers = h.layers; c.classes = h.classes; c.ln_eps = h.ln_eps;
     c.dtype = VH_DTYPE_BF16; c.max_batch = 1;
     if (h.flags & ~(kBlobSum | kBlobModelBits)) return fail(nullptr, VH_ERR_INVALID, "%s: unknown bits in the header's flags word", path);
-    c.flags = ((h.flags & kBlobPreLn) ? VH_FLAG_PRE_LN : 0) | ((h.flags & kBlobQuickGelu) ? VH_FLAG_QUICK_GELU : 0);
+    c.flags = blob_model_flags(h.flags);
     // check_config bounds every field, so the size arithmetic below cannot overflow and nothing is allocated from the header
     if (const char* why = check_config(c)) return fail(nullptr, VH_ERR_INVALID, "%s: header describes an unsupported model (%s)", path, why);
     const size_t need = blob_bytes_of(c);
@@ -2309,7 +2333,7 @@ static int features_enqueue(vh_ctx* c, const vh_features& f) {
     a.hi = planes ? (const void*)c->xn16 : (const void*)c->x;
     a.lo = planes ? c->xlo16 : nullptr;
     a.form = planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32;
-    a.batch = c->last_batch; a.tokens = c->L.T; a.dim = g.dim;
+    a.batch = c->last_batch; a.tokens = c->L.T; a.lead = c->L.lead; a.dim = g.dim;
     a.gamma = c->params + c->L.lnfw; a.beta = c->params + c->L.lnfb; a.eps = g.ln_eps;
     a.elem = f.elem; a.norm = f.norm;
     a.cls = norm ? nullptr : f.cls;   // the normalised class-token rows are the ones the head multiplied: a conversion copy of clsn32
@@ -2411,6 +2435,34 @@ int vh_op_gemm_layout(const void* a, const void* w, const float* bias, void* out
     g.stats = stats; g.out16 = out16; g.partials = partials;
     g.out_tiled = out_tiled; g.ab_tiled = ab_tiled; g.tile_begin = tile_begin; g.tile_count = tile_count;
     return op_gemm_run("gemm_layout", g, 0, stream);
+}
+// test taps of the register-token assembly: the PATCH / PATCH_SPLIT epilogues with `lead` rows in front of an image's patch rows
+// (GemmArgs::lead; prow = row stride of `partials`, 0 = images x (aux_i + lead)), and the lead-row kernels on the caller's buffers
+int vh_op_gemm_lead(const void* a, const void* w, const float* bias, void* out, int64_t M, int N, int K, int epi, const float* aux,
+                    int aux_i, int lead, void* out16, float* partials, int64_t prow, int dtype, int variant, void* stream) {
+    if (epi != VH_EPI_PATCH && epi != VH_EPI_PATCH_SPLIT) return fail(nullptr, VH_ERR_INVALID, "gemm_lead: epilogue must be VH_EPI_PATCH or VH_EPI_PATCH_SPLIT");
+    if (aux_i > 0 && M % aux_i) return fail(nullptr, VH_ERR_INVALID, "gemm_lead: M must be a whole number of images (M %% aux_i == 0)");
+    GemmArgs g{a, w, bias, out, M, N, K, epi, aux, aux_i, dtype, variant};
+    g.out16 = out16; g.partials = partials; g.prow = prow; g.lead = lead;
+    if (epi == VH_EPI_PATCH_SPLIT && aux_i > 0 && prow && prow < (M / aux_i) * (int64_t)(aux_i + lead))
+        return fail(nullptr, VH_ERR_INVALID, "gemm_lead: prow is below images x (aux_i + lead)");
+    return op_gemm_run("gemm_lead", g, 0, stream);
+}
+int vh_op_lead_rows(void* x_or_hi, void* lo, float* partials, int64_t prow, const float* cls, const float* pos, const float* reg, int lead,
+                    int batch, int tokens, int dim, int dtype, void* stream) {
+    if (!x_or_hi || !cls || !pos || batch <= 0 || dim <= 0 || dim % 64 || lead < 1 || lead > 1 + VH_MAX_REGISTERS || lead >= tokens || (lead > 1 && !reg))
+        return fail(nullptr, VH_ERR_INVALID, "lead_rows: bad argument (dim %% 64 == 0, 1 <= lead <= 17, lead < tokens, reg for lead > 1)");
+    hipError_t e;
+    if (lo) {   // the split form: planes + partial sums
+        if (!partials || (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16) || prow < (int64_t)batch * tokens)
+            return fail(nullptr, VH_ERR_INVALID, "lead_rows: the split form needs partials, a 16-bit dtype and prow >= batch x tokens");
+        e = launch_lead_rows_split(x_or_hi, lo, partials, prow, cls, pos, reg, lead, batch, tokens, dim, dtype, (hipStream_t)stream);
+    } else {
+        e = launch_lead_rows((float*)x_or_hi, cls, pos, reg, lead, batch, tokens, dim, (hipStream_t)stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "lead_rows failed: %s", hipGetErrorString(e));
+    return VH_OK;
 }
 // e4m3 operands: w_scale = the per-output-channel weight scales (GemmArgs::wscale), c_dev = the LNFOLD* epilogues' c_n (`aux`)
 int vh_op_gemm_fp8(const void* a8, const void* w8, const float* w_scale, const float* bias, void* out, int64_t M, int N, int K,

@@ -17,6 +17,19 @@ LIB_PATH = os.environ.get("VITHIP_LIB") or os.path.join(PKG_ROOT, "libvithip.so"
 DTYPE_BF16, DTYPE_FP16, DTYPE_FP8 = 0, 1, 2
 FLAG_LN_FOLD_OFF, FLAG_LN_FOLD_ON, FLAG_W8_E4M3, FLAG_CLS_TAIL = 1, 2, 4, 8   # vh_config.flags
 FLAG_PRE_LN, FLAG_QUICK_GELU = 16, 32   # CLIP's vision towers: LayerNorm in front of layer 0, x * sigmoid(1.702 x) in the MLP
+FLAG_REGISTERS_MASK, MAX_REGISTERS = 31 << 9, 16
+
+
+def FLAG_REGISTERS(n):
+    """VH_FLAG_REGISTERS(n): n register tokens (0 .. 16) between the class token and the patch rows, in bits 9 .. 13 of flags."""
+    return (int(n) & 31) << 9
+
+
+def registers_of(flags):
+    """VH_FLAG_REGISTERS_OF(flags)."""
+    return (int(flags) & FLAG_REGISTERS_MASK) >> 9
+
+
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
 EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
 ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = range(4)   # element type of an image tensor (VH_ELEM_*)
@@ -122,6 +135,7 @@ SYMBOLS = {
     "vh_create": (_i, [C.POINTER(Config), _i, C.POINTER(_vp)]),
     "vh_destroy": (_i, [_vp]),
     "vh_get_config": (_i, [_vp, C.POINTER(Config)]),
+    "vh_get_register_tokens": (_i, [_vp]),
     "vh_get_ln_fold": (_i, [_vp, _pi]),
     "vh_get_ln_guard": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), _pi]),
     "vh_get_fp8_guard": (_i, [_vp, C.POINTER(_f), C.POINTER(_f)]),
@@ -227,6 +241,8 @@ SYMBOLS = {
     "vh_op_quantize_rows": (_i, [_vp, _i, _i, C.c_float, _vp, _vp, _vp]),
     "vh_op_gemm_ex": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "vh_op_gemm_layout": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "vh_op_gemm_lead": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _i, _i, _vp]),
+    "vh_op_lead_rows": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8_layout": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vh_op_tile_rows": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "vh_op_rowstats_cast": (_i, [_vp, _i64, _i, _f, _vp, _vp, _i, _vp]),
@@ -321,7 +337,7 @@ def blob_file_config(path):
 
 
 def blob_file_flags(path):
-    """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN | FLAG_QUICK_GELU); host only."""
+    """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN | FLAG_QUICK_GELU | FLAG_REGISTERS(n)); host only."""
     c = Config()
     _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
     return c.flags
@@ -369,6 +385,77 @@ def blob_from_clip_state_dict(sd, cfg, ln_eps=1e-5):
                        dtype=np.int32).view(np.uint8)
     h[40:44] = np.array([ln_eps], dtype=np.float32).view(np.uint8)
     h[52:56] = np.array([2 | (4 if flags & FLAG_QUICK_GELU else 0)], dtype=np.uint32).view(np.uint8)   # header flags word: bit 1 pre-LN, bit 2 QuickGELU
+    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+
+
+def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None):
+    """Canonical blob of a DINOv2 backbone from a dict of arrays under the Hugging Face `Dinov2Model` /
+    `Dinov2WithRegistersModel` parameter names (numpy only; torch tensors: `{k: v.numpy() for k, v in model.state_dict().items()}`).
+    `cfg`: the model shape, `registers` = the number of register tokens (0 for the models without), classes = the head's width.
+    LayerScale is folded into the layer it scales, exactly: W_o' = diag(lambda1) W_o, b_o' = lambda1 b_o, and fc2 with lambda2
+    likewise, computed in float64 and rounded once to fp32.  The backbone has no head: it is zero unless head = (weight
+    [classes, dim], bias [classes]) is given.  `embeddings.mask_token` is ignored.  Refused: a SwiGLU MLP (mlp.weights_in), a
+    position table whose row count is not NP + 1 of cfg (nothing is interpolated here), a register count other than
+    cfg['registers'], a missing or wrongly shaped tensor (by name)."""
+    me = "blob_from_dinov2_state_dict"
+    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
+    g = cfg["image_size"] // cfg["patch_size"]
+    R = int(cfg.get("registers", 0))
+    if not 0 <= R <= MAX_REGISTERS:
+        raise ValueError(f"{me}: cfg['registers'] = {R} is outside 0 .. {MAX_REGISTERS}")
+    if any(k.endswith("mlp.weights_in.weight") for k in sd):
+        raise ValueError(f"{me}: the checkpoint has a SwiGLU MLP (mlp.weights_in), which this library does not run")
+    emb = "embeddings."
+    have = int(np.asarray(sd[emb + "register_tokens"]).shape[-2]) if emb + "register_tokens" in sd else 0
+    if have != R:
+        raise ValueError(f"{me}: the checkpoint has {have} register tokens, cfg['registers'] is {R}")
+    if emb + "position_embeddings" in sd:
+        rows = int(np.asarray(sd[emb + "position_embeddings"]).shape[-2])
+        if rows != g * g + 1:
+            raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP + 1 = {g * g + 1} "
+                             "(interpolate the table to the image size first)")
+
+    def take(name, shape, f=np.float32):
+        if name not in sd:
+            raise KeyError(f"{me}: missing tensor {name}")
+        a = np.asarray(sd[name])
+        if a.shape != tuple(shape):
+            raise ValueError(f"{me}: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}")
+        return np.ascontiguousarray(a, dtype=f).reshape(-1)
+
+    def scaled(wname, bname, lname, n_in):
+        # diag(lambda) W and lambda b in float64, one rounding to fp32 (exact for lambda == 1)
+        lam = take(lname, (D,), np.float64)
+        w = take(wname, (D, n_in), np.float64).reshape(D, n_in) * lam[:, None]
+        return [w.astype(np.float32).reshape(-1), (take(bname, (D,), np.float64) * lam).astype(np.float32)]
+
+    parts = [take(emb + "patch_embeddings.projection.weight", (D, CH, P, P)), take(emb + "patch_embeddings.projection.bias", (D,)),
+             take(emb + "cls_token", (1, 1, D)), take(emb + "position_embeddings", (1, g * g + 1, D))]
+    if R:
+        parts.append(take(emb + "register_tokens", (1, R, D)))
+    for l in range(cfg["layers"]):
+        b = f"encoder.layer.{l}."
+        parts += [take(b + "norm1.weight", (D,)), take(b + "norm1.bias", (D,))]
+        for n in ("query", "key", "value"):
+            parts += [take(f"{b}attention.attention.{n}.weight", (D, D)), take(f"{b}attention.attention.{n}.bias", (D,))]
+        parts += scaled(b + "attention.output.dense.weight", b + "attention.output.dense.bias", b + "layer_scale1.lambda1", D)
+        parts += [take(b + "norm2.weight", (D,)), take(b + "norm2.bias", (D,)),
+                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,))]
+        parts += scaled(b + "mlp.fc2.weight", b + "mlp.fc2.bias", b + "layer_scale2.lambda1", M)
+    parts += [take("layernorm.weight", (D,)), take("layernorm.bias", (D,))]
+    if head is None:
+        parts += [np.zeros(E * D, np.float32), np.zeros(E, np.float32)]
+    else:
+        hw, hb = (np.asarray(a) for a in head)
+        if hw.shape != (E, D) or hb.shape != (E,):
+            raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, D)}, {(E,)}")
+        parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
+    h = np.zeros(64, dtype=np.uint8)
+    h[:7] = np.frombuffer(b"VHBLOB1", dtype=np.uint8)
+    h[8:40] = np.array([cfg[k] for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")],
+                       dtype=np.int32).view(np.uint8)
+    h[40:44] = np.array([ln_eps], dtype=np.float32).view(np.uint8)
+    h[52:56] = np.array([FLAG_REGISTERS(R)], dtype=np.uint32).view(np.uint8)   # header flags word: bits 9 .. 13 = register tokens
     return np.concatenate([h] + [p.view(np.uint8) for p in parts])
 
 
@@ -676,6 +763,14 @@ def pack_frames_bgra(planes_or_pixels, layouts=L444_BGRA, boxes=None):
 
 
 def make_config(cfg, dtype=DTYPE_BF16, max_batch=1, ln_eps=1e-6, flags=0):
+    """vh_config of a model dict.  cfg.get("registers", 0) register tokens are folded into `flags`; a caller may put
+    FLAG_REGISTERS(n) into `flags` itself instead (both, with different counts, is refused)."""
+    r = int(cfg.get("registers", 0))
+    if not 0 <= r <= 31:
+        raise ValueError(f"make_config: cfg['registers'] = {r} is outside 0 .. 31 (the library takes 0 .. {MAX_REGISTERS})")
+    if r and registers_of(flags) not in (0, r):
+        raise ValueError(f"make_config: cfg['registers'] = {r} but flags carry FLAG_REGISTERS({registers_of(flags)})")
+    flags |= FLAG_REGISTERS(r)
     return Config(cfg["image_size"], cfg["patch_size"], cfg["channels"], cfg["dim"], cfg["heads"],
                   cfg["mlp_dim"], cfg["layers"], cfg["classes"], dtype, max_batch, ln_eps, flags)
 
@@ -1378,8 +1473,12 @@ class VitContext:
         _check(lib().vh_debug_set_layers(self.h, n), self.h)
 
     # ---- token features of the last forward (vithip.h "Token features") ----
+    def register_tokens(self):
+        """The context's number of register tokens (vh_get_register_tokens)."""
+        return int(lib().vh_get_register_tokens(self.h))
+
     def features_dims(self):
-        """(batch of the last forward, tokens, patches, dim)."""
+        """(batch of the last forward, tokens, patches, dim); tokens = patches + 1 + register tokens."""
         b, t, n, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         _check(lib().vh_features_dims(self.h, C.byref(b), C.byref(t), C.byref(n), C.byref(d)), self.h)
         return b.value, t.value, n.value, d.value
@@ -1610,6 +1709,21 @@ def op_gemm_layout(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, dtype, au
     (ab_tiled: pack_tiled, op_tile_rows) or a range of the 256 x 256 tiles (variants 5 and 7)."""
     _check(lib().vh_op_gemm_layout(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, aux_ptr, aux_i, stats_ptr, out16_ptr,
                                    partials_ptr, dtype, variant, 1 if out_tiled else 0, 1 if ab_tiled else 0, tile_begin, tile_count, None))
+
+
+def op_gemm_lead(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, dtype, pos_ptr, patches, lead, out16_ptr=None, partials_ptr=None,
+                 prow=0, variant=0):
+    """Test tap: the EPI_PATCH / EPI_PATCH_SPLIT epilogues with `lead` = 1 + R rows in front of an image's `patches` patch rows:
+    GEMM row img * patches + p lands on output row img * (patches + lead) + lead + p and adds pos row 1 + p."""
+    _check(lib().vh_op_gemm_lead(a_ptr, w_ptr, bias_ptr, out_ptr, M, N, K, epilogue, pos_ptr, patches, lead, out16_ptr, partials_ptr,
+                                 prow, dtype, variant, None))
+
+
+def op_lead_rows(x_or_hi_ptr, cls_ptr, pos_ptr, reg_ptr, lead, batch, tokens, dim, lo_ptr=None, partials_ptr=None, prow=0,
+                 dtype=DTYPE_BF16):
+    """Test tap: the kernels that write the `lead` leading rows of every image (row 0 = cls + pos[0], row 1 + r = reg[r]): fp32
+    rows (lo_ptr None), or the split planes and the rows' per-64-column partial sums [dim / 64][prow][2]."""
+    _check(lib().vh_op_lead_rows(x_or_hi_ptr, lo_ptr, partials_ptr, prow, cls_ptr, pos_ptr, reg_ptr, lead, batch, tokens, dim, dtype, None))
 
 
 def op_gemm_fp8_layout(a8_ptr, w8_ptr, scale_ptr, bias_ptr, out_ptr, M, N, K, epilogue, c_ptr=None, stats_ptr=None, out16_ptr=None,
