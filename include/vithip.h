@@ -915,6 +915,46 @@ int vh_op_layernorm(const float* x_dev, int64_t rows, int dim, int64_t row_strid
  *   stats_dev [rows][2]                             (mean, rstd) of the NORMALISED row y: layer 0's LN1 statistics */
 int vh_op_pre_layernorm(const float* x_dev, int64_t rows, int dim, const float* gamma_dev, const float* beta_dev, float eps,
                         float* y32_dev, void* hi_dev, void* lo_dev, float* stats_dev, int dtype, void* stream);
+/* ---- Test taps of the row kernels (tests/rows_exact.py, tests/test_gpu_rows_exact.py).  Every tap checks pointers, shape and
+ * dtype on the host and returns VH_ERR_INVALID before anything is launched; dim % 4 == 0 and dim <= 2048 wherever a row is kept
+ * in registers; a dtype other than the ones named is VH_ERR_INVALID (vh_op_layernorm, vh_op_rowstats_cast / _split: VH_DTYPE_BF16,
+ * VH_DTYPE_FP16, VH_DTYPE_FP8; vh_op_fold_ln: the two 16-bit types).  They synchronise the stream like their neighbours.
+ * Guard words: one unsigned 32-bit word on the device that holds the bits of a non-negative float, raised by an atomic maximum
+ * over the first guard_rows rows (0 <= guard_rows <= rows; the rows behind them are tile padding and never count); a NaN's
+ * bits rank above +Inf's.  A word keeps a value that is already larger.
+ *   vh_op_rowstats_guard        vh_op_rowstats_cast (lo_dev NULL) / vh_op_rowstats_split with the guard: amax_guard_dev
+ *                               (VH_DTYPE_FP8 only, may be NULL) = max |x| of the guarded rows.  VH_DTYPE_FP8: hi = e4m3 bytes,
+ *                               lo = bf16 of the remainder.
+ *   vh_op_pre_layernorm_guard   vh_op_pre_layernorm with guard_dev = max |ymean| * yrstd of the normalised guarded rows and
+ *                               amax_guard_dev (VH_DTYPE_FP8 only) = max |y|; both may be NULL; they need hi_dev or stats_dev.
+ *   vh_op_finalize_stats_guard  vh_op_finalize_stats with guard_dev = max |mean| * rstd and amax_guard_dev = max over the
+ *                               guarded rows of sqrt(the largest block's sum of squares); both may be NULL.
+ *   vh_op_ln_guard              guard_dev = max(guard_dev, max_r |stats[r][0]| * stats[r][1]) over stats [rows][2].
+ *   vh_op_layernorm_f32         vh_op_layernorm with the fp32 result out32 [rows, dim] (the final LayerNorm of the plain path).
+ *   vh_op_layernorm_split       out32[r, :] = LN(hi[r * row_stride + k] + lo[r * row_stride + k]) * gamma + beta for the split
+ *                               residual's planes: dtype VH_DTYPE_BF16 / VH_DTYPE_FP16 = 16-bit hi + one scaled e4m3 byte,
+ *                               VH_DTYPE_FP8 = e4m3 hi + bf16 lo; row_stride >= dim, in elements.
+ *   vh_op_head_f32              logits[b, c] = sum_k y[b, k] * w[c, k] + bias[c], all fp32; classes % 4 == 0, dim % 16 == 0.
+ *   vh_op_fold_ln_f8            vh_op_fold_ln for e4m3 weights: w8 [rows, dim] bytes = e4m3(scale * gamma o W / s0), wscale[n] = s0
+ *                               = amax / 448 (1 for an all-zero row), c[n] = s0 * sum_k decode(w8[n, k]), d as vh_op_fold_ln.
+ *   vh_op_fake_quant_rows       out[r, :] = decode(e4m3(w[r, :] / s0)) * s0 with the same row quantiser; cols % 4 == 0. */
+int vh_op_rowstats_guard(const float* x_dev, int64_t rows, int dim, float eps, void* hi_dev, void* lo_dev, float* stats_dev,
+                         int dtype, int64_t guard_rows, unsigned int* amax_guard_dev, void* stream);
+int vh_op_pre_layernorm_guard(const float* x_dev, int64_t rows, int dim, const float* gamma_dev, const float* beta_dev, float eps,
+                              float* y32_dev, void* hi_dev, void* lo_dev, float* stats_dev, int dtype, int64_t guard_rows,
+                              unsigned int* guard_dev, unsigned int* amax_guard_dev, void* stream);
+int vh_op_finalize_stats_guard(const float* partials_dev, int nblk, int64_t rows, int dim, float eps, float* stats_dev,
+                               int64_t guard_rows, unsigned int* guard_dev, unsigned int* amax_guard_dev, void* stream);
+int vh_op_ln_guard(const float* stats_dev, int64_t rows, unsigned int* guard_dev, void* stream);
+int vh_op_layernorm_f32(const float* x_dev, int64_t rows, int dim, int64_t row_stride, const float* gamma_dev,
+                        const float* beta_dev, float eps, float* out32_dev, void* stream);
+int vh_op_layernorm_split(const void* hi_dev, const void* lo_dev, int64_t rows, int dim, int64_t row_stride,
+                          const float* gamma_dev, const float* beta_dev, float eps, float* out32_dev, int dtype, void* stream);
+int vh_op_head_f32(const float* y_dev, const float* w_dev, const float* bias_dev, float* out_dev, int batch, int classes,
+                   int dim, void* stream);
+int vh_op_fold_ln_f8(const float* w_dev, const float* b_dev, const float* gamma_dev, const float* beta_dev, int rows, int dim,
+                     float scale, void* w8_dev, float* wscale_dev, float* c_dev, float* d_dev, void* stream);
+int vh_op_fake_quant_rows(const float* w_dev, int rows, int cols, float* out_dev, void* stream);
 /* qkv16 [batch*tokens, 3*heads*64] -> out16 [batch*tokens, heads*64].  The q columns arrive pre-scaled by
  * VH_ATTN_Q_SCALE = 64^-1/2 * log2(e) (the forward folds it into Wq/bq): the kernel's softmax works in the exp2 domain. */
 #define VH_ATTN_Q_SCALE 0.18033688011112042f

@@ -8,6 +8,7 @@
 namespace vh {
 
 // ---- LayerNorm: one wave per row, row kept in registers, fp32 statistics ------------------
+// (per-element tests on exactly predictable rows: tests/rows_exact.py, test_rows_exact.py, test_gpu_rows_exact.py)
 // y[r,:] = (x[r,:] - mean) * rstd * gamma + beta  -> 16-bit.  dim % 4 == 0, dim <= 1024*?.
 template <typename T, int CH>  // CH = float4 chunks per lane (dim <= 256*CH)
 __global__ void __launch_bounds__(256)
@@ -74,8 +75,9 @@ hipError_t launch_layernorm(const float* x, int64_t rows, int dim, int64_t row_s
     if (rows <= 0 || dim <= 0 || (dim & 3) || (row_stride & 3)) return hipErrorInvalidValue;
     if (dtype == VH_DTYPE_F32_INTERNAL) return ln_t<F32OUT>(x, rows, dim, row_stride, gamma, beta, eps, out16, s);
     if (dtype == VH_DTYPE_FP8) return ln_t<E4M3>(x, rows, dim, row_stride, gamma, beta, eps, out16, s);  // 1 byte / element
-    return dtype == VH_DTYPE_BF16 ? ln_t<BF16>(x, rows, dim, row_stride, gamma, beta, eps, out16, s)
-                                  : ln_t<FP16>(x, rows, dim, row_stride, gamma, beta, eps, out16, s);
+    if (dtype == VH_DTYPE_BF16) return ln_t<BF16>(x, rows, dim, row_stride, gamma, beta, eps, out16, s);
+    if (dtype == VH_DTYPE_FP16) return ln_t<FP16>(x, rows, dim, row_stride, gamma, beta, eps, out16, s);
+    return hipErrorInvalidValue;   // an unknown dtype is no fp16
 }
 
 // ---- im2col + cast: NHWC fp32 image -> patch matrix [batch*np, patch*patch*ch] 16-bit -------
@@ -709,16 +711,18 @@ hipError_t launch_rowstats_cast(const float* x, int64_t rows, int dim, float eps
                                 hipStream_t s, int64_t guard_rows, unsigned int* amax_guard) {
     if (rows <= 0 || dim <= 0 || (dim & 3)) return hipErrorInvalidValue;
     if (dtype == VH_DTYPE_FP8) return rowstats_t<E4M3>(x, rows, dim, eps, x16, stats, s, nullptr, guard_rows, amax_guard);   // e4m3 copy of the raw rows (fp8 path, folded LN)
-    return dtype == VH_DTYPE_BF16 ? rowstats_t<BF16>(x, rows, dim, eps, x16, stats, s)
-                                  : rowstats_t<FP16>(x, rows, dim, eps, x16, stats, s);
+    if (dtype == VH_DTYPE_BF16) return rowstats_t<BF16>(x, rows, dim, eps, x16, stats, s);
+    if (dtype == VH_DTYPE_FP16) return rowstats_t<FP16>(x, rows, dim, eps, x16, stats, s);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_rowstats_split(const float* x, int64_t rows, int dim, float eps, void* hi, void* lo, float* stats, int dtype,
                                  hipStream_t s, int64_t guard_rows, unsigned int* amax_guard) {
     if (rows <= 0 || dim <= 0 || (dim & 3) || !lo) return hipErrorInvalidValue;
     if (dtype == VH_DTYPE_FP8) return rowstats_t<E4M3>(x, rows, dim, eps, hi, stats, s, lo, guard_rows, amax_guard);   // e4m3 hi plane + bf16 lo plane
-    return dtype == VH_DTYPE_BF16 ? rowstats_t<BF16>(x, rows, dim, eps, hi, stats, s, lo)
-                                  : rowstats_t<FP16>(x, rows, dim, eps, hi, stats, s, lo);
+    if (dtype == VH_DTYPE_BF16) return rowstats_t<BF16>(x, rows, dim, eps, hi, stats, s, lo);
+    if (dtype == VH_DTYPE_FP16) return rowstats_t<FP16>(x, rows, dim, eps, hi, stats, s, lo);
+    return hipErrorInvalidValue;
 }
 
 // ---- pre-LayerNorm (VH_FLAG_PRE_LN, CLIP's ln_pre): the embedded rows, normalised BEFORE layer 0 ---------------------------
@@ -880,8 +884,10 @@ hipError_t launch_layernorm_split(const void* hi, const void* lo, int64_t rows, 
         hipLaunchKernelGGL(layernorm_split_kernel<E4M3>, grid, block, 0, s, (const E4M3::elem*)hi, lo, rows, dim, row_stride, gamma, beta, eps, out32);
     else if (dtype == VH_DTYPE_BF16)
         hipLaunchKernelGGL(layernorm_split_kernel<BF16>, grid, block, 0, s, (const BF16::elem*)hi, (const void*)lo, rows, dim, row_stride, gamma, beta, eps, out32);
-    else
+    else if (dtype == VH_DTYPE_FP16)
         hipLaunchKernelGGL(layernorm_split_kernel<FP16>, grid, block, 0, s, (const FP16::elem*)hi, (const void*)lo, rows, dim, row_stride, gamma, beta, eps, out32);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -1036,7 +1042,8 @@ hipError_t launch_fold_ln(const float* w, const float* b, const float* gamma, co
     if (rows <= 0 || dim <= 0) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     if (dtype == VH_DTYPE_BF16) hipLaunchKernelGGL(fold_ln_kernel<BF16>, grid, block, 0, s, w, b, gamma, beta, rows, dim, scale, (BF16::elem*)w16, c, d);
-    else hipLaunchKernelGGL(fold_ln_kernel<FP16>, grid, block, 0, s, w, b, gamma, beta, rows, dim, scale, (FP16::elem*)w16, c, d);
+    else if (dtype == VH_DTYPE_FP16) hipLaunchKernelGGL(fold_ln_kernel<FP16>, grid, block, 0, s, w, b, gamma, beta, rows, dim, scale, (FP16::elem*)w16, c, d);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -2503,40 +2503,84 @@ int vh_op_tile_rows(const void* in, int rows, int cols, void* out, int dtype, vo
     if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "tile_rows failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
+// ---- the row-kernel taps (kernels_misc.hip: one wave per row).  Every tap judges pointers, shape and dtype here, before a launch.
+static bool row_dt16(int dtype) { return dtype == VH_DTYPE_BF16 || dtype == VH_DTYPE_FP16; }
+static bool row_dt(int dtype) { return row_dt16(dtype) || dtype == VH_DTYPE_FP8; }
+static bool row_shape(int64_t rows, int dim) { return rows > 0 && dim > 0 && dim % 4 == 0 && dim <= 2048; }
 int vh_op_rowstats_cast(const float* x, int64_t rows, int dim, float eps, void* x16, float* stats, int dtype, void* stream) {
-    if (!x || !x16 || !stats || rows <= 0 || dim <= 0 || dim % 4 || dim > 2048) return fail(nullptr, VH_ERR_INVALID, "rowstats_cast: bad argument");
-    OPCHK(launch_rowstats_cast(x, rows, dim, eps, x16, stats, dtype, (hipStream_t)stream));
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    return VH_OK;
+    return vh_op_rowstats_guard(x, rows, dim, eps, x16, nullptr, stats, dtype, 0, nullptr, stream);
 }
 int vh_op_rowstats_split(const float* x, int64_t rows, int dim, float eps, void* hi, void* lo, float* stats, int dtype, void* stream) {
-    if (!x || !hi || !lo || !stats || rows <= 0 || dim <= 0 || dim % 4 || dim > 2048) return fail(nullptr, VH_ERR_INVALID, "rowstats_split: bad argument");
-    OPCHK(launch_rowstats_split(x, rows, dim, eps, hi, lo, stats, dtype, (hipStream_t)stream));
+    if (!lo) return fail(nullptr, VH_ERR_INVALID, "rowstats_split: bad argument");
+    return vh_op_rowstats_guard(x, rows, dim, eps, hi, lo, stats, dtype, 0, nullptr, stream);
+}
+int vh_op_rowstats_guard(const float* x, int64_t rows, int dim, float eps, void* hi, void* lo, float* stats, int dtype, int64_t guard_rows,
+                         unsigned int* amax_guard, void* stream) {
+    if (!x || !hi || !stats || !row_shape(rows, dim)) return fail(nullptr, VH_ERR_INVALID, "rowstats: bad argument (rows > 0, dim %% 4 == 0, dim <= 2048)");
+    if (!row_dt(dtype)) return fail(nullptr, VH_ERR_INVALID, "rowstats: dtype");
+    if (guard_rows < 0 || guard_rows > rows) return fail(nullptr, VH_ERR_INVALID, "rowstats: guard_rows outside 0..rows");
+    if (amax_guard && dtype != VH_DTYPE_FP8) return fail(nullptr, VH_ERR_INVALID, "rowstats: amax_guard belongs to VH_DTYPE_FP8");
+    OPCHK(lo ? launch_rowstats_split(x, rows, dim, eps, hi, lo, stats, dtype, (hipStream_t)stream, guard_rows, amax_guard)
+             : launch_rowstats_cast(x, rows, dim, eps, hi, stats, dtype, (hipStream_t)stream, guard_rows, amax_guard));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_op_pre_layernorm(const float* x, int64_t rows, int dim, const float* gamma, const float* beta, float eps, float* y32, void* hi,
                         void* lo, float* stats, int dtype, void* stream) {
+    return vh_op_pre_layernorm_guard(x, rows, dim, gamma, beta, eps, y32, hi, lo, stats, dtype, 0, nullptr, nullptr, stream);
+}
+int vh_op_pre_layernorm_guard(const float* x, int64_t rows, int dim, const float* gamma, const float* beta, float eps, float* y32, void* hi,
+                              void* lo, float* stats, int dtype, int64_t guard_rows, unsigned int* guard, unsigned int* amax_guard,
+                              void* stream) {
     if (!x || !gamma || !beta) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: null pointer");
     if (!y32 && !hi) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: one of y32 / hi is needed");
     if (lo && !hi) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: the lo plane needs the hi plane");
     if (rows <= 0 || dim <= 0 || dim % 4 || dim > 2048) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: need rows > 0, dim %% 4 == 0, dim <= 2048");
     if (!(eps > 0.f)) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: eps must be positive");
     if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: dtype");
-    OPCHK(launch_pre_layernorm(x, rows, dim, gamma, beta, eps, y32, hi, lo, stats, dtype, (hipStream_t)stream));
+    if (guard_rows < 0 || guard_rows > rows) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: guard_rows outside 0..rows");
+    if (amax_guard && dtype != VH_DTYPE_FP8) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: amax_guard belongs to VH_DTYPE_FP8");
+    if ((guard || amax_guard) && !hi && !stats) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: the guards need hi or stats");
+    OPCHK(launch_pre_layernorm(x, rows, dim, gamma, beta, eps, y32, hi, lo, stats, dtype, (hipStream_t)stream, guard_rows, guard, amax_guard));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_op_finalize_stats(const float* partials, int nblk, int64_t rows, int dim, float eps, float* stats, void* stream) {
+    return vh_op_finalize_stats_guard(partials, nblk, rows, dim, eps, stats, 0, nullptr, nullptr, stream);
+}
+int vh_op_finalize_stats_guard(const float* partials, int nblk, int64_t rows, int dim, float eps, float* stats, int64_t guard_rows,
+                               unsigned int* guard, unsigned int* amax_guard, void* stream) {
     if (!partials || !stats || nblk <= 0 || rows <= 0 || dim <= 0) return fail(nullptr, VH_ERR_INVALID, "finalize_stats: bad argument");
-    OPCHK(launch_finalize_stats(partials, nblk, rows, dim, eps, stats, (hipStream_t)stream));
+    if (guard_rows < 0 || guard_rows > rows) return fail(nullptr, VH_ERR_INVALID, "finalize_stats: guard_rows outside 0..rows");
+    OPCHK(launch_finalize_stats(partials, nblk, rows, dim, eps, stats, (hipStream_t)stream, guard_rows, guard, amax_guard));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_ln_guard(const float* stats, int64_t rows, unsigned int* guard, void* stream) {
+    if (!stats || !guard || rows <= 0) return fail(nullptr, VH_ERR_INVALID, "ln_guard: bad argument");
+    OPCHK(launch_ln_guard(stats, rows, guard, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_op_fold_ln(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim, float scale,
                   void* w16, float* c, float* d, int dtype, void* stream) {
     if (!w || !b || !gamma || !beta || !w16 || !c || !d || rows <= 0 || dim <= 0) return fail(nullptr, VH_ERR_INVALID, "fold_ln: bad argument");
+    if (!row_dt16(dtype)) return fail(nullptr, VH_ERR_INVALID, "fold_ln: dtype (e4m3 weights: vh_op_fold_ln_f8)");
     OPCHK(launch_fold_ln(w, b, gamma, beta, rows, dim, scale, w16, c, d, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim, float scale,
+                     void* w8, float* wscale, float* c, float* d, void* stream) {
+    if (!w || !b || !gamma || !beta || !w8 || !wscale || !c || !d || rows <= 0 || dim <= 0 || dim % 4)
+        return fail(nullptr, VH_ERR_INVALID, "fold_ln_f8: bad argument (dim %% 4 == 0)");
+    OPCHK(launch_fold_ln_f8(w, b, gamma, beta, rows, dim, scale, w8, wscale, c, d, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_fake_quant_rows(const float* w, int rows, int cols, float* out, void* stream) {
+    if (!w || !out || rows <= 0 || cols <= 0 || cols % 4) return fail(nullptr, VH_ERR_INVALID, "fake_quant_rows: bad argument (cols %% 4 == 0)");
+    OPCHK(launch_fake_quant_rows(w, rows, cols, out, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
@@ -2544,7 +2588,33 @@ int vh_op_layernorm(const float* x, int64_t rows, int dim, int64_t row_stride, c
                     float eps, void* out16, int dtype, void* stream) {
     if (!x || !gamma || !beta || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
     if (dim <= 0 || dim % 4 || dim > 2048 || rows <= 0 || row_stride % 4) return fail(nullptr, VH_ERR_INVALID, "layernorm: unsupported shape");
+    if (!row_dt(dtype)) return fail(nullptr, VH_ERR_INVALID, "layernorm: dtype (the fp32 result: vh_op_layernorm_f32)");
     OPCHK(launch_layernorm(x, rows, dim, row_stride, gamma, beta, eps, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_layernorm_f32(const float* x, int64_t rows, int dim, int64_t row_stride, const float* gamma, const float* beta,
+                        float eps, float* out32, void* stream) {
+    if (!x || !gamma || !beta || !out32) return fail(nullptr, VH_ERR_INVALID, "layernorm_f32: null pointer");
+    if (!row_shape(rows, dim) || row_stride % 4 || row_stride < dim) return fail(nullptr, VH_ERR_INVALID, "layernorm_f32: unsupported shape");
+    OPCHK(launch_layernorm(x, rows, dim, row_stride, gamma, beta, eps, out32, VH_DTYPE_F32_INTERNAL, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_layernorm_split(const void* hi, const void* lo, int64_t rows, int dim, int64_t row_stride, const float* gamma,
+                          const float* beta, float eps, float* out32, int dtype, void* stream) {
+    if (!hi || !lo || !gamma || !beta || !out32) return fail(nullptr, VH_ERR_INVALID, "layernorm_split: null pointer");
+    if (!row_shape(rows, dim) || row_stride < dim) return fail(nullptr, VH_ERR_INVALID, "layernorm_split: unsupported shape");
+    if (!row_dt(dtype)) return fail(nullptr, VH_ERR_INVALID, "layernorm_split: dtype");
+    OPCHK(launch_layernorm_split(hi, lo, rows, dim, row_stride, gamma, beta, eps, out32, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_head_f32(const float* y, const float* w, const float* bias, float* out, int batch, int classes, int dim, void* stream) {
+    if (!y || !w || !bias || !out) return fail(nullptr, VH_ERR_INVALID, "head_f32: null pointer");
+    if (batch <= 0 || classes <= 0 || classes % 4 || dim <= 0 || dim % 16)
+        return fail(nullptr, VH_ERR_INVALID, "head_f32: need batch > 0, classes %% 4 == 0, dim %% 16 == 0");
+    OPCHK(launch_head_f32(y, w, bias, out, batch, classes, dim, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }

@@ -251,6 +251,15 @@ SYMBOLS = {
     "vh_op_rowstats_split": (_i, [_vp, _i64, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "vh_op_fold_ln": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "vh_op_layernorm": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _i, _vp]),
+    "vh_op_rowstats_guard": (_i, [_vp, _i64, _i, _f, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
+    "vh_op_pre_layernorm_guard": (_i, [_vp, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "vh_op_finalize_stats_guard": (_i, [_vp, _i, _i64, _i, _f, _vp, _i64, _vp, _vp, _vp]),
+    "vh_op_ln_guard": (_i, [_vp, _i64, _vp, _vp]),
+    "vh_op_layernorm_f32": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _vp]),
+    "vh_op_layernorm_split": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _i, _vp]),
+    "vh_op_head_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vh_op_fold_ln_f8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "vh_op_fake_quant_rows": (_i, [_vp, _i, _i, _vp, _vp]),
     "vh_op_attention": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_stream": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_hd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
@@ -1756,6 +1765,47 @@ def op_finalize_stats(partials_ptr, nblk, rows, dim, eps, stats_ptr):
 
 def op_fold_ln(w_ptr, b_ptr, gamma_ptr, beta_ptr, rows, dim, scale, w16_ptr, c_ptr, d_ptr, dtype):
     _check(lib().vh_op_fold_ln(w_ptr, b_ptr, gamma_ptr, beta_ptr, rows, dim, scale, w16_ptr, c_ptr, d_ptr, dtype, None))
+
+
+# ---- test taps of the row kernels (include/vithip.h, "Test taps of the row kernels"; tests/rows_exact.py) ----
+def op_rowstats_guard(x_ptr, rows, dim, eps, hi_ptr, lo_ptr, stats_ptr, dtype, guard_rows=0, amax_guard_ptr=None):
+    """op_rowstats_cast (lo_ptr None) / op_rowstats_split with the e4m3 form's |x| guard word over the first guard_rows rows."""
+    _check(lib().vh_op_rowstats_guard(x_ptr, rows, dim, eps, hi_ptr, lo_ptr, stats_ptr, dtype, guard_rows, amax_guard_ptr, None))
+
+
+def op_pre_layernorm_guard(x_ptr, rows, dim, gamma_ptr, beta_ptr, eps, y32_ptr, hi_ptr, lo_ptr, stats_ptr, dtype, guard_rows=0,
+                           guard_ptr=None, amax_guard_ptr=None):
+    _check(lib().vh_op_pre_layernorm_guard(x_ptr, rows, dim, gamma_ptr, beta_ptr, eps, y32_ptr, hi_ptr, lo_ptr, stats_ptr, dtype,
+                                           guard_rows, guard_ptr, amax_guard_ptr, None))
+
+
+def op_finalize_stats_guard(partials_ptr, nblk, rows, dim, eps, stats_ptr, guard_rows=0, guard_ptr=None, amax_guard_ptr=None):
+    _check(lib().vh_op_finalize_stats_guard(partials_ptr, nblk, rows, dim, eps, stats_ptr, guard_rows, guard_ptr, amax_guard_ptr, None))
+
+
+def op_ln_guard(stats_ptr, rows, guard_ptr):
+    _check(lib().vh_op_ln_guard(stats_ptr, rows, guard_ptr, None))
+
+
+def op_layernorm_f32(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out32_ptr):
+    _check(lib().vh_op_layernorm_f32(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out32_ptr, None))
+
+
+def op_layernorm_split(hi_ptr, lo_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out32_ptr, dtype):
+    """LayerNorm of rows of the split residual -> fp32: 16-bit hi + lo8 byte (DTYPE_BF16 / DTYPE_FP16), or e4m3 hi + bf16 lo (DTYPE_FP8)."""
+    _check(lib().vh_op_layernorm_split(hi_ptr, lo_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out32_ptr, dtype, None))
+
+
+def op_head_f32(y_ptr, w_ptr, bias_ptr, out_ptr, batch, classes, dim):
+    _check(lib().vh_op_head_f32(y_ptr, w_ptr, bias_ptr, out_ptr, batch, classes, dim, None))
+
+
+def op_fold_ln_f8(w_ptr, b_ptr, gamma_ptr, beta_ptr, rows, dim, scale, w8_ptr, wscale_ptr, c_ptr, d_ptr):
+    _check(lib().vh_op_fold_ln_f8(w_ptr, b_ptr, gamma_ptr, beta_ptr, rows, dim, scale, w8_ptr, wscale_ptr, c_ptr, d_ptr, None))
+
+
+def op_fake_quant_rows(w_ptr, rows, cols, out_ptr):
+    _check(lib().vh_op_fake_quant_rows(w_ptr, rows, cols, out_ptr, None))
 
 
 def bench_gemm(M, N, K, epilogue, dtype=DTYPE_BF16, variant=0, iters=20, device=0):
