@@ -1,4 +1,4 @@
-"""Exactly predictable inputs for the one-wave-per-row kernels of kernels_misc.hip, their closed-form expectations, a numpy
+"""Exactly predictable inputs for the one-wave-per-row kernels of kernels_rows.hip, their closed-form expectations, a numpy
 emulation of every kernel in the kernel's own order (with named mutants), the float64 references with derived bounds, and the
 checks that test_rows_exact.py (CPU, on the emulation) and test_gpu_rows_exact.py (GPU, on the taps) both run.  No GPU, no
 oracle.
@@ -52,7 +52,7 @@ COUNTS = [1, 63, 64, 65, 255, 256, 257, 600]
 NBLK = [1, 2, 15, 16, 17, 31, 32, 33]
 HEAD_BATCH, HEAD_CLASSES, HEAD_DIMS = [1, 15, 16, 17, 33], [4, 60, 64, 68, 1000], [16, 48, 192, 1280]
 POSITIONS = ("first", "middle", "last")
-CH_LN, CH_PRE = (1, 2, 3, 4, 8), (1, 2, 3, 4, 5, 8)
+CH_CLASSES = (1, 2, 3, 4, 5, 8)   # the one ladder of kernels_rows.hip: float4 chunks per lane
 
 MUTANTS = ("one_pass", "drop_last_chunk", "ch_small", "gamma_by_lane", "no_eps", "eps_on_sigma", "lo_scale_other",
            "guard_incl_pad", "guard_miss_last", "guard_store", "garbage_blocks", "head_no_batch_clamp", "head_image_wrap",
@@ -65,8 +65,8 @@ def _rng(seed, *key):
     return np.random.default_rng([int(seed)] + [int(k) for k in key])
 
 
-def ch_class(dim, pre=False):
-    return next(c for c in (CH_PRE if pre else CH_LN) if dim <= 256 * c)
+def ch_class(dim):
+    return next(c for c in CH_CLASSES if dim <= 256 * c)
 
 
 def pos_index(pos, n):
@@ -541,7 +541,7 @@ class Emulation:
     def layernorm(self, xflat, rows, dim, stride, gamma, beta, eps, dt):
         x = np.stack([xflat[r * stride:r * stride + dim] for r in range(rows)])
         CH = ch_class(dim)
-        v, ok = _layout(x, dim, CH, self.mutant, CH_LN)
+        v, ok = _layout(x, dim, CH, self.mutant, CH_CLASSES)
         mean, rstd = _two_pass(v, ok, dim, eps, self.mutant)
         y = _affine(v, ok, mean, rstd, gamma, beta, dim, CH, self.mutant)
         return _unlayout(to_bits(y, dt), ok, dim, canary((), dt))
@@ -549,7 +549,7 @@ class Emulation:
     def rowstats(self, x, eps, dt, split, guard_rows=0, amax0=None):
         rows, dim = x.shape
         CH = ch_class(dim)
-        v, ok = _layout(x, dim, CH, self.mutant, CH_LN)
+        v, ok = _layout(x, dim, CH, self.mutant, CH_CLASSES)
         mean, rstd = _two_pass(v, ok, dim, eps, self.mutant)
         hi = to_bits(np.nan_to_num(v), dt)
         other = {BF16: FP16, FP16: BF16}.get(dt) if self.mutant == "lo_scale_other" else None
@@ -561,8 +561,8 @@ class Emulation:
 
     def pre_ln(self, x, gamma, beta, eps, dt, outs, guard_rows=0, guard0=None, amax0=None):
         rows, dim = x.shape
-        CH = ch_class(dim, True)
-        v, ok = _layout(x, dim, CH, self.mutant, CH_PRE)
+        CH = ch_class(dim)
+        v, ok = _layout(x, dim, CH, self.mutant, CH_CLASSES)
         mean, rstd = _two_pass(v, ok, dim, eps, self.mutant)
         y = _affine(v, ok, mean, rstd, gamma, beta, dim, CH, self.mutant)
         res = dict(y32=None, hi=None, lo=None, stats=None, guard=None, amax=None)

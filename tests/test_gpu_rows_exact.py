@@ -1,4 +1,4 @@
-"""GPU, per element: the one-wave-per-row kernels of kernels_misc.hip on exactly predictable rows (tests/rows_exact.py).
+"""GPU, per element: the one-wave-per-row kernels of kernels_rows.hip on exactly predictable rows (tests/rows_exact.py).
 
 The operator tests of test_gpu_ops / test_gpu_clip / test_gpu_fp8 run these kernels on smooth random rows at a few dims and
 hold them to relative bounds; the guards, the fp32 head, layernorm_split, fold_ln_f8 and fake_quant_rows were reachable only

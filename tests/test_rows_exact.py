@@ -84,8 +84,7 @@ def test_emulation_passes_fold(dim):
 
 
 def test_designs_cover_what_they_claim():
-    assert [X.ch_class(d) for d in (256, 260, 512, 516, 768, 772, 1024, 1028, 2048)] == [1, 2, 2, 3, 3, 4, 4, 8, 8]
-    assert [X.ch_class(d, True) for d in (1024, 1028, 1280, 1284)] == [4, 5, 5, 8]
+    assert [X.ch_class(d) for d in (256, 260, 512, 516, 768, 772, 1024, 1028, 1280, 1284, 2048)] == [1, 2, 2, 3, 3, 4, 4, 5, 5, 8, 8]
     c = X.two_level(7, 260, 0)
     assert abs(c.m[0]) == 4096 and c.a[0] == 0.25 and (c.a == 0).any() and np.all(c.sign.reshape(7, -1, 4).sum(2) == 0)
     assert len({(g, b) for g, b in zip(c.gamma, c.beta)}) == 16

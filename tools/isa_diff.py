@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """tools/isa_diff.py <dir A> <dir B>: compare, kernel by kernel, the gfx950 assembly of two builds of the csrc sources
 (directories of *-hip-amdgcn-amd-amdhsa-gfx950.s files as tools/isa.sh / -save-temps=obj leave them).  Prints the kernels whose
-instruction stream differs, the kernels only one side has, and per new kernel its register / spill numbers.
+instruction stream differs (with instructions, sgpr / vgpr / spilled vgpr / scratch bytes of both sides), the kernels only one
+side has, and per new kernel the same numbers.  The kernels of all files of a directory are pooled, so a kernel that moved from one
+source file to another is compared with itself.
 --ignore-params: match template kernels by name and template arguments alone, so that a kernel whose PARAMETER LIST changed (a
 mangled name with another tail) is still compared with its predecessor instead of showing up as one removed and one new."""
 import glob
@@ -33,8 +35,8 @@ def kernels(path):
 def meta(path):
     txt = open(path).read()
     res = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.sgpr_count:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", txt):
-        res[m.group(1)] = (int(m.group(2)), int(m.group(3)), int(m.group(4)))
+    for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_count:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", txt):
+        res[m.group(1)] = (int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(2)))   # sgpr, vgpr, spilled vgpr, scratch bytes
     return res
 
 
@@ -58,25 +60,30 @@ def offsets_only(a, b):
     return all(x == y or (x.startswith("s_load_dword") and strip(x) == strip(y)) for x, y in zip(a, b))
 
 
+def pool(d):
+    k, m = {}, {}
+    for f in sorted(glob.glob(os.path.join(d, "*gfx950.s"))):
+        k.update({key(n): v for n, v in kernels(f).items()})
+        m.update({key(n): v for n, v in meta(f).items()})
+    return k, m
+
+
 same = diff = moved = 0
-for fa in sorted(glob.glob(os.path.join(a_dir, "*gfx950.s"))):
-    fb = os.path.join(b_dir, os.path.basename(fa))
-    ka, kb = ({key(k): v for k, v in kernels(f).items()} for f in (fa, fb))
-    mb = {key(k): v for k, v in meta(fb).items()}
-    for k in sorted(ka):
-        if k not in kb:
-            print(f"ONLY IN A  {k}")
-        elif ka[k] == kb[k]:
-            same += 1
-        elif offsets_only(ka[k], kb[k]):
-            moved += 1
-            print(f"ARG OFFSET {k}  ({len(ka[k])} instructions; only the offsets of kernel-argument loads differ)")
-        else:
-            diff += 1
-            print(f"DIFFERS    {k}  ({len(ka[k])} -> {len(kb[k])} instructions)")
-    for k in sorted(set(kb) - set(ka)):
-        n = len(kb[k])
-        nexp = sum(t.startswith(("v_exp_f32", "v_rcp_f32")) for t in kb[k])
-        npk = sum(t.startswith("v_pk_") for t in kb[k])
-        print(f"NEW        {k}  {n} instructions ({npk} packed, {nexp} v_exp/v_rcp)  sgpr/vgpr/spill {mb.get(k)}")
+(ka, ma), (kb, mb) = pool(a_dir), pool(b_dir)
+for k in sorted(ka):
+    if k not in kb:
+        print(f"ONLY IN A  {k}")
+    elif ka[k] == kb[k]:
+        same += 1
+    elif offsets_only(ka[k], kb[k]):
+        moved += 1
+        print(f"ARG OFFSET {k}  ({len(ka[k])} instructions; only the offsets of kernel-argument loads differ)")
+    else:
+        diff += 1
+        print(f"DIFFERS    {k}  ({len(ka[k])} -> {len(kb[k])} instructions)  sgpr/vgpr/spill/scratch {ma.get(k)} -> {mb.get(k)}")
+for k in sorted(set(kb) - set(ka)):
+    n = len(kb[k])
+    nexp = sum(t.startswith(("v_exp_f32", "v_rcp_f32")) for t in kb[k])
+    npk = sum(t.startswith("v_pk_") for t in kb[k])
+    print(f"NEW        {k}  {n} instructions ({npk} packed, {nexp} v_exp/v_rcp)  sgpr/vgpr/spill/scratch {mb.get(k)}")
 print(f"{same} kernels identical, {moved} with moved kernel-argument offsets only, {diff} differ")

@@ -54,9 +54,11 @@ struct FP16 {
 };
 
 // fp32 "output type" of the kernels templated on their result element (final LayerNorm of the CLS rows -> fp32 head)
+constexpr int VH_DTYPE_F32_INTERNAL = 100;   // its launcher code, next to the public VH_DTYPE_*; never crosses the C ABI
 struct F32OUT {
     using elem = float;
     using vec4 = f32x4;
+    static constexpr int id = VH_DTYPE_F32_INTERNAL;
 };
 
 // four fp32 -> one 8-byte vector of the storage type.  Converted as two PAIRS: element-wise casts made hipcc emit one
@@ -95,6 +97,15 @@ __device__ __forceinline__ uint32_t pack4<E4M3>(float a, float b, float c, float
 template <>
 __device__ __forceinline__ f32x4 pack4<F32OUT>(float a, float b, float c, float d) {
     return f32x4{a, b, c, d};
+}
+
+// dtype code -> element type: f(T{}) for the one T of Ts... whose id is `dtype`.  Every other value -- an unknown code, or a type
+// the kernel behind the launcher has no instantiation for -- is hipErrorInvalidValue; f returns the launch's hipError_t.
+template <typename... Ts, typename F>
+inline hipError_t dispatch_dtype(int dtype, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((dtype == Ts::id ? (e = f(Ts{}), true) : false) || ...);
+    return e;
 }
 
 // ---- lo plane of the split residual (x = hi + lo): ONE e4m3 byte per element ----------------------------
@@ -154,6 +165,23 @@ __device__ __forceinline__ void asm_lds_dma4(const void* base, uint32_t lane_off
 __device__ __forceinline__ void asm_atomic_add_ret_issue(unsigned int* base, uint32_t add, uint32_t& ret) {
     const uint32_t zero = 0;
     asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=&v"(ret) : "v"(zero), "v"(add), "s"(base) : "memory");
+}
+
+// ---- wave-wide reductions: the xor butterfly, offsets 32, 16, ... 1 in that order; every lane ends with the same bits -------
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
+    return x;
+}
+__device__ __forceinline__ unsigned int wave_max(unsigned int x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned int t = (unsigned int)__shfl_xor((int)x, o); x = t > x ? t : x; }
+    return x;
 }
 
 __device__ __forceinline__ float gelu_erf(float v) {

@@ -65,8 +65,7 @@ int gemm_pp_variant(int epilogue);  // 5, 6 or 7 (default 6 = persistent; env VH
 hipError_t launch_layernorm(const float* x, int64_t rows, int dim, int64_t row_stride,
                             const float* gamma, const float* beta, float eps, void* out16,
                             int dtype, hipStream_t stream);
-// dtype = VH_DTYPE_* (16-bit / e4m3 result) or VH_DTYPE_F32_INTERNAL (fp32 result: the final LayerNorm in front of the head)
-constexpr int VH_DTYPE_F32_INTERNAL = 100;
+// dtype = VH_DTYPE_* (16-bit / e4m3 result) or VH_DTYPE_F32_INTERNAL (vh_common.h; fp32 result: the final LayerNorm in front of the head)
 // classifier head, fp32 operands (exact-fp32 MFMA): logits[b, c] = y[b, :] . w[c, :] + bias[c]; classes % 4 == 0, dim % 16 == 0
 hipError_t launch_head_f32(const float* y, const float* w, const float* bias, float* out, int batch, int classes, int dim,
                            hipStream_t stream);
@@ -206,7 +205,7 @@ hipError_t launch_permute_patch(const float* w_nchw, int dim, int channels, int 
 // amax_guard (optional, e4m3 rows only): running maximum of |x| over the first guard_rows rows, as float bits
 hipError_t launch_rowstats_cast(const float* x, int64_t rows, int dim, float eps, void* x16, float* stats, int dtype,
                                 hipStream_t stream, int64_t guard_rows = 0, unsigned int* amax_guard = nullptr);
-// guard (optional): running maximum of |mean| * rstd over the first `guard_rows` rows, as float bits (kernels_misc.hip)
+// guard (optional): running maximum of |mean| * rstd over the first `guard_rows` rows, as float bits (kernels_rows.hip)
 // amax_guard (optional): running maximum of an upper bound of |x| (largest 64-column block's root sum of squares)
 hipError_t launch_finalize_stats(const float* partials, int nblk, int64_t rows, int dim, float eps, float* stats,
                                  hipStream_t stream, int64_t guard_rows = 0, unsigned int* guard = nullptr,
@@ -216,7 +215,7 @@ hipError_t launch_ln_guard(const float* stats, int64_t rows, unsigned int* guard
 // the fp32 LayerNorm of selected rows (the CLS rows) of the planes
 hipError_t launch_rowstats_split(const float* x, int64_t rows, int dim, float eps, void* hi, void* lo, float* stats, int dtype,
                                  hipStream_t stream, int64_t guard_rows = 0, unsigned int* amax_guard = nullptr);
-// pre-LayerNorm of VH_FLAG_PRE_LN contexts (kernels_misc.hip): y = LN(x) gamma + beta -> fp32 rows (y32, may alias x), the split
+// pre-LayerNorm of VH_FLAG_PRE_LN contexts (kernels_rows.hip): y = LN(x) gamma + beta -> fp32 rows (y32, may alias x), the split
 // residual's planes / the plain operand copy (hi, lo) and layer 0's row statistics of y; every output is optional, one of
 // y32 / hi is needed.  guard / amax_guard as launch_finalize_stats / launch_rowstats_cast, over the first guard_rows rows.
 hipError_t launch_pre_layernorm(const float* x, int64_t rows, int dim, const float* gamma, const float* beta, float eps, float* y32,

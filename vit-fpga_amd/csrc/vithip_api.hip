@@ -2503,7 +2503,7 @@ int vh_op_tile_rows(const void* in, int rows, int cols, void* out, int dtype, vo
     if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "tile_rows failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
-// ---- the row-kernel taps (kernels_misc.hip: one wave per row).  Every tap judges pointers, shape and dtype here, before a launch.
+// ---- the row-kernel taps (kernels_rows.hip: one wave per row).  Every tap judges pointers, shape and dtype here, before a launch.
 static bool row_dt16(int dtype) { return dtype == VH_DTYPE_BF16 || dtype == VH_DTYPE_FP16; }
 static bool row_dt(int dtype) { return row_dt16(dtype) || dtype == VH_DTYPE_FP8; }
 static bool row_shape(int64_t rows, int dim) { return rows > 0 && dim > 0 && dim % 4 == 0 && dim <= 2048; }
@@ -2535,9 +2535,9 @@ int vh_op_pre_layernorm_guard(const float* x, int64_t rows, int dim, const float
     if (!x || !gamma || !beta) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: null pointer");
     if (!y32 && !hi) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: one of y32 / hi is needed");
     if (lo && !hi) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: the lo plane needs the hi plane");
-    if (rows <= 0 || dim <= 0 || dim % 4 || dim > 2048) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: need rows > 0, dim %% 4 == 0, dim <= 2048");
+    if (!row_shape(rows, dim)) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: need rows > 0, dim %% 4 == 0, dim <= 2048");
     if (!(eps > 0.f)) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: eps must be positive");
-    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: dtype");
+    if (!row_dt(dtype)) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: dtype");
     if (guard_rows < 0 || guard_rows > rows) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: guard_rows outside 0..rows");
     if (amax_guard && dtype != VH_DTYPE_FP8) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: amax_guard belongs to VH_DTYPE_FP8");
     if ((guard || amax_guard) && !hi && !stats) return fail(nullptr, VH_ERR_INVALID, "pre_layernorm: the guards need hi or stats");
@@ -2587,7 +2587,7 @@ int vh_op_fake_quant_rows(const float* w, int rows, int cols, float* out, void* 
 int vh_op_layernorm(const float* x, int64_t rows, int dim, int64_t row_stride, const float* gamma, const float* beta,
                     float eps, void* out16, int dtype, void* stream) {
     if (!x || !gamma || !beta || !out16) return fail(nullptr, VH_ERR_INVALID, "null pointer");
-    if (dim <= 0 || dim % 4 || dim > 2048 || rows <= 0 || row_stride % 4) return fail(nullptr, VH_ERR_INVALID, "layernorm: unsupported shape");
+    if (!row_shape(rows, dim) || row_stride % 4) return fail(nullptr, VH_ERR_INVALID, "layernorm: unsupported shape");
     if (!row_dt(dtype)) return fail(nullptr, VH_ERR_INVALID, "layernorm: dtype (the fp32 result: vh_op_layernorm_f32)");
     OPCHK(launch_layernorm(x, rows, dim, row_stride, gamma, beta, eps, out16, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
