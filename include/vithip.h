@@ -147,8 +147,8 @@ typedef struct vh_config {
  *   x - hi, with the per-64-column (sum, sum of squares) of the fp32 x beside it -- vh_debug_read returns hi + decode(lo).
  *   With R = 0 every kernel writes the bytes it wrote before the flag existed.
  * Token features skip the register rows: cls <- row 0, patch[b][p] <- row 1 + R + p, mean over those NP rows.  The register rows
- * themselves (DINOv2's x_norm_regtokens) are not a field of vh_features, a fixed 32-byte struct; vh_debug_read of the hidden state
- * returns them.  The opt-in fused patch loader (VH_PATCH_FUSED=1) is not extended: a context with R > 0 takes the im2col + GEMM
+ * themselves (DINOv2's x_norm_regtokens) are not a field of vh_features, a fixed 32-byte struct: vh_layer_features.reg ("Layer
+ * features") returns them.  The opt-in fused patch loader (VH_PATCH_FUSED=1) is not extended: a context with R > 0 takes the im2col + GEMM
  * path whatever the environment says. */
 #define VH_FLAG_REGISTERS(n) (((n) & 31) << 9)
 #define VH_FLAG_REGISTERS_MASK (31 << 9)
@@ -792,6 +792,69 @@ int vh_read_features(vh_ctx* ctx, const vh_features* out_host);
 int vh_read_features_device(vh_ctx* ctx, const vh_features* out_dev);
 int vh_read_features_device_async(vh_ctx* ctx, const vh_features* out_dev);
 
+/* ---- Layer features ------------------------------------------------------------------------
+ * What a dense head takes from a backbone (DINOv2's get_intermediate_layers(x, n, reshape=True, return_class_token=True) in front
+ * of its DPT and linear heads, ViT-Adapter / Mask2Former-style decoders, a LLaVA-style consumer of layer -2): the residual stream
+ * after SEVERAL layers of ONE forward, each read out like the token features, the patch rows optionally channels-first, and the
+ * register rows.  Capture is a push -- the forward copies rows it has finished -- and the read-out is the pull interface above.
+ *
+ * THE LIST.  vh_set_feature_layers(ctx, layers, n): n <= VH_MAX_FEATURE_LAYERS entries, strictly ascending, each 1 .. cfg.layers;
+ * entry k = the residual stream after k layers (Hugging Face's hidden_states[k]).  n == 0 clears the list and frees the store.  The
+ * call waits for the context's stream, drops the cached graphs and allocates ONE capture store for the listed layers below
+ * cfg.layers: max_batch x tokens x dim elements per such layer, of 3 bytes where the context keeps the residual as two planes for
+ * good (folded LayerNorm with VH_FLAG_LN_FOLD_ON: 16-bit hi + one lo byte, VH_DTYPE_FP8: e4m3 hi + bf16 lo) and of 4 bytes
+ * everywhere else -- the fp32 residual, and every context whose guarded fold may still fall back to it (the default flags): the
+ * size is decided once, for the widest form.  ViT-B/16 at max_batch 512: 232 MB (3 bytes) / 310 MB (4 bytes) per layer.  When the
+ * allocation fails the call returns VH_ERR_HIP and the previous list stays in force.  vh_get_feature_layers reads the list back
+ * (layers: room for VH_MAX_FEATURE_LAYERS ints, or NULL).
+ *
+ * CAPTURE.  Every forward enqueued while a list is set copies, behind the second MLP GEMM of layer k - 1 for every listed k below
+ * the number of layers it runs, the real rows of its batch into the store in the form its path holds them (both planes, or the
+ * fp32 array): one small launch per listed layer, on the stream of the batch part, captured into graphs like every other launch,
+ * inside the profile event of the stage that follows.  A listed layer equal to the number of layers run is served from the live
+ * residual and costs nothing.  With an empty list a forward enqueues exactly what it enqueued before this section existed; with
+ * any list the logits keep their bits.
+ *
+ * READ-OUT.  vh_layer_features = vh_features + reg, layer and patch_layout:
+ *   layer         -1 or cfg.layers: the final state -- the values and bits of vh_read_features, the NORM class-token rows being the
+ *                 vector the head multiplied.  1 .. cfg.layers - 1: that layer of the LAST forward; it must have been in the list when
+ *                 that forward was enqueued, and the forward must have reached it (vh_debug_set_layers).  Its NORM class-token
+ *                 row is v of row b * tokens like any other row.
+ *   reg           [batch][R][D]: v of rows b * tokens + 1 .. b * tokens + R (DINOv2's x_norm_regtokens), R = vh_get_register_tokens.
+ *   patch_layout  VH_FEAT_ROWS: patch is [batch][NP][D].  VH_FEAT_NCHW: [batch][D][gh][gw], gh = gw = image_size / patch_size,
+ *                 out[b][k][p] = rows[b][p][k] (DINOv2's reshape=True): bit for bit the elements of the VH_FEAT_ROWS output,
+ *                 transposed.  Only the base pointer needs the 16-byte alignment.
+ * ARITHMETIC: exactly "Token features" -- x = hi + lo with one fp32 add, the two-pass fp32 LayerNorm whose sum order depends on D
+ * alone, with the model's FINAL LayerNorm parameters for every layer (DINOv2's norm=True), the serial fp32 mean chain over the NP
+ * patch rows, 16-bit outputs = the RNE of the fp32 ones.  A captured layer has the bits vh_read_features gives after
+ * vh_debug_set_layers(k) and a forward of the same images.  Image i's outputs never depend on the other images.
+ *
+ * REFUSED, each with a message of its own, nothing enqueued and no output touched.  VH_ERR_INVALID: a null context or descriptor;
+ * all four pointers NULL; elem, norm or patch_layout outside their values; layer outside -1, 1 .. cfg.layers; a device pointer
+ * that is not 16-byte aligned; reg on a context without register tokens.  VH_ERR_STATE: no forward has run; a ring exists; the
+ * layer was not in the list when the last forward was enqueued; the last forward did not reach the layer.  VH_ERR_UNSUPPORTED: a
+ * VH_FLAG_CLS_TAIL context (vh_set_feature_layers too).  vh_set_feature_layers: VH_ERR_INVALID for a null context, a bad count or
+ * a list that is not strictly ascending within 1 .. cfg.layers; VH_ERR_STATE while a ring exists.
+ * Not covered: rings, device groups, layer 0 (the embedding output). */
+#define VH_MAX_FEATURE_LAYERS 8
+#define VH_FEAT_ROWS 0   /* patch [batch][NP][D]                                  */
+#define VH_FEAT_NCHW 1   /* patch [batch][D][gh][gw]: the same elements, transposed */
+typedef struct vh_layer_features { /* sizeof == 48: cls 0, patch 8, mean 16, reg 24, elem 32, norm 36, layer 40, patch_layout 44 */
+    void* cls;            /* [batch][D]      or NULL: not wanted */
+    void* patch;          /* [batch][NP][D] / [batch][D][gh][gw] or NULL */
+    void* mean;           /* [batch][D]      or NULL             */
+    void* reg;            /* [batch][R][D]   or NULL             */
+    int32_t elem;         /* VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16 */
+    int32_t norm;         /* VH_FEAT_NORM or VH_FEAT_RAW              */
+    int32_t layer;        /* -1 / cfg.layers: the final state; 1 .. cfg.layers - 1: a listed layer */
+    int32_t patch_layout; /* VH_FEAT_ROWS or VH_FEAT_NCHW             */
+} vh_layer_features;
+int vh_set_feature_layers(vh_ctx* ctx, const int* layers, int n);
+int vh_get_feature_layers(const vh_ctx* ctx, int* layers, int* n);
+int vh_read_layer_features(vh_ctx* ctx, const vh_layer_features* out_host);
+int vh_read_layer_features_device(vh_ctx* ctx, const vh_layer_features* out_dev);
+int vh_read_layer_features_device_async(vh_ctx* ctx, const vh_layer_features* out_dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1054,6 +1117,14 @@ int vh_op_cast(const float* in_dev, void* out16_dev, int64_t n, int dtype, void*
 int vh_op_token_features(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int dim,
                          const float* gamma_dev, const float* beta_dev, float eps, int elem, int norm, void* patch_out_dev,
                          void* mean_out_dev, void* stream);
+/* vh_op_token_features with the rest of "Layer features": `lead` = 1 + the register rows in front of an image's patch rows (1 ..
+ * tokens - 1; patch and mean cover rows lead .. tokens - 1), reg_out_dev [batch][lead - 1][dim] <- rows 1 .. lead - 1 (refused where
+ * lead is 1), patch_layout VH_FEAT_ROWS ([batch][tokens - lead][dim]) or VH_FEAT_NCHW ([batch][dim][tokens - lead], the same elements
+ * transposed; only the base pointer's alignment matters).  Any of the three outputs may be NULL, not all.  Every argument is checked
+ * before a device is touched. */
+int vh_op_token_features2(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int lead, int dim,
+                          const float* gamma_dev, const float* beta_dev, float eps, int elem, int norm, void* patch_out_dev,
+                          int patch_layout, void* mean_out_dev, void* reg_out_dev, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,
  * 2 = constant `sigma` */
 int vh_op_fill(float* out_dev, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,

@@ -10,7 +10,10 @@
 //                      serial fp32 chain the contract names, independent of any launch geometry.  It reads the planes
 //                      again (coalesced across columns) and takes (mean, rstd) of a row from the statistics the row kernel
 //                      wrote, so the value it adds is, bit for bit, the fp32 value the row kernel converted and stored.
-// (The normalised class-token rows are the ones the head multiplied: a conversion copy of clsn32, made by launch_cast.)
+//   feat_nchw_kernel   the patch rows channels-first ([batch][dim][np]): 32 tokens of one image per workgroup, each row through the
+//                      row kernel's own three steps (row_load, row_stats, piece_norm), transposed through LDS.
+//   feat_capture_kernel  the copy of a tapped layer's rows into the capture store ("Layer features"), both planes in one launch.
+// (The normalised class-token rows of the final state are the ones the head multiplied: a conversion copy of clsn32, made by launch_cast.)
 //
 // The arithmetic that both kernels must agree on lives in ONE place each: load_x (x = hi + lo, one fp32 add) and
 // feat_norm (fmaf((x - mean) * rstd, gamma, beta), explicit fmaf).  The row sums use explicit operations in an order that
@@ -95,26 +98,12 @@ __device__ __forceinline__ void store8(typename OUT::elem* p, const float* v) {
     }
 }
 
-// rows = batch * tokens.  Row r = image r / tokens, token r % tokens: token 0 goes to cls_out [batch][dim], token t >= lead to
-// patch_out [batch][tokens - lead][dim]; either may be null.  Tokens 1 .. lead - 1 (register tokens) go nowhere.  norm != 0: the row passes LayerNorm(gamma, beta, eps), and
-// stats (optional) receives (mean, rstd) of every patch row.  A wave whose row has nothing to write leaves at once.
-template <typename IN, typename OUT, int CH>   // CH = pieces of 8 elements per lane (dim <= 512 * CH)
-__global__ void __launch_bounds__(256)
-feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t rows, int tokens, int lead, int dim,
-                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int norm,
-                 typename OUT::elem* __restrict__ cls_out, typename OUT::elem* __restrict__ patch_out, float* __restrict__ stats) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int64_t img = row / tokens;
-    const int t = (int)(row - img * tokens);
-    typename OUT::elem* out = nullptr;
-    if (t == 0) { if (cls_out) out = cls_out + img * dim; }
-    else if (t >= lead && patch_out) out = patch_out + (img * (tokens - lead) + (t - lead)) * dim;
-    const bool want_stats = norm && stats && t >= lead;
-    if (!out && !want_stats) return;   // wave-uniform
+// ---- one row in one wave: the three steps both row kernels are made of ---------------------------------------------------------
+// Lane `lane` holds pieces lane, lane + 64, .. of the row (a piece = 8 consecutive elements); pieces beyond dim hold zeros.
+template <typename IN, int CH>
+__device__ __forceinline__ void row_load(const void* __restrict__ hi, const void* __restrict__ lo, int64_t row, int dim, int lane,
+                                         float (&v)[CH][8]) {
     const int npiece = dim >> 3;
-    float v[CH][8];
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
         const int c = lane + 64 * i;
@@ -124,28 +113,73 @@ feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64
             for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
         }
     }
+}
+
+// (mean, rstd) of the row, two passes over the registers; the order of both sums depends on dim alone
+template <int CH>
+__device__ __forceinline__ void row_stats(const float (&v)[CH][8], int dim, int lane, float eps, float& mean, float& rstd) {
+    const int npiece = dim >> 3;
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+        sum += ((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) + ((v[i][4] + v[i][5]) + (v[i][6] + v[i][7]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    mean = sum / (float)dim;
+    float var = 0.f;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        if (lane + 64 * i < npiece) {
+            float q = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q = __builtin_fmaf(d, d, q); }
+            var += q;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o);
+    rstd = 1.0f / sqrtf(var / (float)dim + eps);
+}
+
+// piece i of the row through feat_norm, in place
+__device__ __forceinline__ void piece_norm(float (&p)[8], int c, float mean, float rstd, const float* __restrict__ gamma,
+                                           const float* __restrict__ beta) {
+    const f32x4 g0 = ((const f32x4*)gamma)[2 * c], g1 = ((const f32x4*)gamma)[2 * c + 1];
+    const f32x4 b0 = ((const f32x4*)beta)[2 * c], b1 = ((const f32x4*)beta)[2 * c + 1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        p[j] = feat_norm(p[j], mean, rstd, g0[j], b0[j]);
+        p[4 + j] = feat_norm(p[4 + j], mean, rstd, g1[j], b1[j]);
+    }
+}
+
+// rows = batch * tokens.  Row r = image r / tokens, token r % tokens: token 0 goes to cls_out [batch][dim], tokens 1 .. lead - 1
+// (register tokens) to reg_out [batch][lead - 1][dim], token t >= lead to patch_out [batch][tokens - lead][dim]; any may be null.
+// norm != 0: the row passes LayerNorm(gamma, beta, eps), and stats (optional) receives (mean, rstd) of every patch row.  A wave
+// whose row has nothing to write leaves at once.
+template <typename IN, typename OUT, int CH>   // CH = pieces of 8 elements per lane (dim <= 512 * CH)
+__global__ void __launch_bounds__(256)
+feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t rows, int tokens, int lead, int dim,
+                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int norm,
+                 typename OUT::elem* __restrict__ cls_out, typename OUT::elem* __restrict__ reg_out,
+                 typename OUT::elem* __restrict__ patch_out, float* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t img = row / tokens;
+    const int t = (int)(row - img * tokens);
+    typename OUT::elem* out = nullptr;
+    if (t == 0) { if (cls_out) out = cls_out + img * dim; }
+    else if (t < lead) { if (reg_out) out = reg_out + (img * (lead - 1) + (t - 1)) * dim; }
+    else if (patch_out) out = patch_out + (img * (tokens - lead) + (t - lead)) * dim;
+    const bool want_stats = norm && stats && t >= lead;
+    if (!out && !want_stats) return;   // wave-uniform
+    const int npiece = dim >> 3;
+    float v[CH][8];
+    row_load<IN, CH>(hi, lo, row, dim, lane, v);
     float mean = 0.f, rstd = 1.f;
     if (norm) {
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i)
-            sum += ((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) + ((v[i][4] + v[i][5]) + (v[i][6] + v[i][7]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        mean = sum / (float)dim;
-        float var = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            if (lane + 64 * i < npiece) {
-                float q = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q = __builtin_fmaf(d, d, q); }
-                var += q;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o);
-        rstd = 1.0f / sqrtf(var / (float)dim + eps);
+        row_stats<CH>(v, dim, lane, eps, mean, rstd);
         if (want_stats && lane == 0) *(f32x2*)(stats + 2 * row) = f32x2{mean, rstd};
     }
     if (!out) return;
@@ -153,17 +187,99 @@ feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64
     for (int i = 0; i < CH; ++i) {
         const int c = lane + 64 * i;
         if (c < npiece) {
-            if (norm) {
-                const f32x4 g0 = ((const f32x4*)gamma)[2 * c], g1 = ((const f32x4*)gamma)[2 * c + 1];
-                const f32x4 b0 = ((const f32x4*)beta)[2 * c], b1 = ((const f32x4*)beta)[2 * c + 1];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[i][j] = feat_norm(v[i][j], mean, rstd, g0[j], b0[j]);
-                    v[i][4 + j] = feat_norm(v[i][4 + j], mean, rstd, g1[j], b1[j]);
-                }
-            }
+            if (norm) piece_norm(v[i], c, mean, rstd, gamma, beta);
             store8<OUT>(out + 8 * c, v[i]);
         }
+    }
+}
+
+// The patch rows channels-first: out[b][k][p] = v of row b * tokens + lead + p, element k -- [batch][dim][np], np = tokens - lead,
+// the map a convolutional head takes.  One workgroup (16 waves) takes kNchwTile consecutive patch tokens of one image and all dim
+// columns; a wave takes two of the rows, one after the other through the steps of feat_rows_kernel, and keeps both in registers.
+// Then half a chunk of 512 columns at a time (elements 4 h .. 4 h + 3 of the pieces i of every lane: 256 columns) passes through
+// LDS: a wave writes element 4 h + j of its piece at [row][64 j + lane] (row stride 257 dwords: conflict-free dword stores), the
+// workgroup reads it back with the token index fastest across lanes ([p][..] at p * 257: 32 lanes, 32 banks) and stores runs of 32
+// consecutive p per channel.  33 KB of LDS: two workgroups (32 waves) per CU.  An output row is np elements long and np *
+// sizeof(elem) is no multiple of anything in particular: element stores, only `out` itself is aligned.  stats as in
+// feat_rows_kernel.  Tokens beyond np (the ragged last tile) are neither read nor written.
+constexpr int kNchwTile = 32, kNchwStride = 257;
+template <typename IN, typename OUT, int CH>
+__global__ void __launch_bounds__(1024)
+feat_nchw_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int tokens, int lead, int dim,
+                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int norm,
+                 typename OUT::elem* __restrict__ out, float* __restrict__ stats) {
+    __shared__ float tile[kNchwTile * kNchwStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int np = tokens - lead, npiece = dim >> 3;
+    const int tiles = (np + kNchwTile - 1) / kNchwTile;   // workgroup blockIdx.x = image * tiles + tile
+    const int64_t img = blockIdx.x / tiles;
+    const int p0 = (int)(blockIdx.x - img * tiles) * kNchwTile;
+    float v[2][CH][8];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int p = p0 + wave + 16 * q;
+        if (p < np) {   // wave-uniform
+            const int64_t row = img * tokens + lead + p;
+            row_load<IN, CH>(hi, lo, row, dim, lane, v[q]);
+            if (norm) {
+                float mean, rstd;
+                row_stats<CH>(v[q], dim, lane, eps, mean, rstd);
+                if (stats && lane == 0) *(f32x2*)(stats + 2 * row) = f32x2{mean, rstd};
+#pragma unroll
+                for (int i = 0; i < CH; ++i)
+                    if (lane + 64 * i < npiece) piece_norm(v[q][i], lane + 64 * i, mean, rstd, gamma, beta);
+            }
+        }
+    }
+    // the read side: token pl of the tile; positions ks, ks + 32, .. of the 256 of a half chunk.  Position kk holds element
+    // 4 h + (kk >> 6) of the piece of lane kk & 63: column 512 i + 8 (kk & 63) + 4 h + (kk >> 6)
+    const int pl = threadIdx.x & 31, ks = threadIdx.x >> 5;
+    const bool p_ok = p0 + pl < np;
+    typename OUT::elem* const obase = out + (img * dim) * np + p0 + pl;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (i || h) __syncthreads();   // the previous half chunk has been read
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if (p0 + wave + 16 * q < np && lane + 64 * i < npiece) {
+                    float* const w = tile + (wave + 16 * q) * kNchwStride + lane;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) w[64 * j] = v[q][i][4 * h + j];
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int kk = ks + 32 * m;
+                if (p_ok && (kk & 63) + 64 * i < npiece) {
+                    const float x = tile[pl * kNchwStride + kk];
+                    obase[(int64_t)(512 * i + 8 * (kk & 63) + 4 * h + (kk >> 6)) * np] = (typename OUT::elem)x;
+                }
+            }
+        }
+    }
+}
+
+// One launch that copies the real rows of a part's residual into the capture store of a tapped layer (vithip.h "Layer features"):
+// n_hi units of 16 bytes of the hi plane (or of the fp32 array), then n_lo of the lo plane.  1024 units per workgroup.
+__global__ void __launch_bounds__(256)
+feat_capture_kernel(const u32x4* __restrict__ src_hi, u32x4* __restrict__ dst_hi, int64_t n_hi, const u32x4* __restrict__ src_lo,
+                    u32x4* __restrict__ dst_lo, int64_t n_lo) {
+    const int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x;
+    u32x4 t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t u = base + 256 * k;
+        if (u < n_hi) t[k] = src_hi[u];
+        else if (u - n_hi < n_lo) t[k] = src_lo[u - n_hi];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t u = base + 256 * k;
+        if (u < n_hi) dst_hi[u] = t[k];
+        else if (u - n_hi < n_lo) dst_lo[u - n_hi] = t[k];
     }
 }
 
@@ -207,16 +323,33 @@ hipError_t feat_launch(const FeatureArgs& a, hipStream_t s) {
     const int64_t rows = (int64_t)a.batch * a.tokens;
     const int norm = a.norm == VH_FEAT_NORM ? 1 : 0;   // the kernels' flag: 1 = through the LayerNorm
     const bool mean_norm = a.mean && norm;
-    if (a.cls || a.patch || mean_norm) {   // (a raw mean needs no row pass: nothing to normalise, no statistics)
-        const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    // channels-first patch rows: their own kernel, which also writes the patch rows' statistics; the row kernel then serves cls / reg
+    const bool nchw = a.patch && a.patch_layout == VH_FEAT_NCHW;
+    if (nchw) {
+        const dim3 grid((unsigned)((a.tokens - a.lead + kNchwTile - 1) / kNchwTile) * (unsigned)a.batch), block(1024);
         float* st = mean_norm ? a.stats : nullptr;
-#define VH_FEAT_ROWS(CH) hipLaunchKernelGGL((feat_rows_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, rows, a.tokens, a.lead, a.dim, \
-                                            a.gamma, a.beta, a.eps, norm, (E*)a.cls, (E*)a.patch, st)
-        if (a.dim <= 512) VH_FEAT_ROWS(1);
-        else if (a.dim <= 1024) VH_FEAT_ROWS(2);
-        else if (a.dim <= 1536) VH_FEAT_ROWS(3);
-        else VH_FEAT_ROWS(4);
-#undef VH_FEAT_ROWS
+#define VH_FEAT_NCHW_L(CH) hipLaunchKernelGGL((feat_nchw_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, a.tokens, a.lead, a.dim, \
+                                              a.gamma, a.beta, a.eps, norm, (E*)a.patch, st)
+        if (a.dim <= 512) VH_FEAT_NCHW_L(1);
+        else if (a.dim <= 1024) VH_FEAT_NCHW_L(2);
+        else if (a.dim <= 1536) VH_FEAT_NCHW_L(3);
+        else VH_FEAT_NCHW_L(4);
+#undef VH_FEAT_NCHW_L
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    void* const patch_rows = nchw ? nullptr : a.patch;
+    const bool stats_rows = mean_norm && !nchw;
+    if (a.cls || a.reg || patch_rows || stats_rows) {   // (a raw mean needs no row pass: nothing to normalise, no statistics)
+        const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+        float* st = stats_rows ? a.stats : nullptr;
+#define VH_FEAT_ROWS_L(CH) hipLaunchKernelGGL((feat_rows_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, rows, a.tokens, a.lead, a.dim, \
+                                              a.gamma, a.beta, a.eps, norm, (E*)a.cls, (E*)a.reg, (E*)patch_rows, st)
+        if (a.dim <= 512) VH_FEAT_ROWS_L(1);
+        else if (a.dim <= 1024) VH_FEAT_ROWS_L(2);
+        else if (a.dim <= 1536) VH_FEAT_ROWS_L(3);
+        else VH_FEAT_ROWS_L(4);
+#undef VH_FEAT_ROWS_L
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -253,7 +386,9 @@ const char* features_check(const FeatureArgs& a) {
     if (a.dim < 64) return "token_features: dim below 64";
     if (a.dim > 2048) return "token_features: dim above 2048";
     if (a.dim % 8) return "token_features: dim must be a multiple of 8";
-    if (!a.cls && !a.patch && !a.mean) return "token_features: no output requested";
+    if (!a.cls && !a.patch && !a.mean && !a.reg) return "token_features: no output requested";
+    if (a.reg && a.lead < 2) return "token_features: register rows requested where lead is 1 (no register rows)";
+    if (a.patch_layout != VH_FEAT_ROWS && a.patch_layout != VH_FEAT_NCHW) return "token_features: patch_layout must be VH_FEAT_ROWS or VH_FEAT_NCHW";
     if (a.elem != VH_ELEM_F32 && a.elem != VH_ELEM_F16 && a.elem != VH_ELEM_BF16)
         return "token_features: elem must be VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16";
     if (a.norm != VH_FEAT_NORM && a.norm != VH_FEAT_RAW) return "token_features: norm must be VH_FEAT_NORM or VH_FEAT_RAW";
@@ -262,7 +397,7 @@ const char* features_check(const FeatureArgs& a) {
         if (!(a.eps > 0.f)) return "token_features: eps must be positive";
     }
     const uintptr_t al = (uintptr_t)a.hi | (uintptr_t)a.lo | (uintptr_t)a.gamma | (uintptr_t)a.beta | (uintptr_t)a.cls | (uintptr_t)a.patch |
-                         (uintptr_t)a.mean;
+                         (uintptr_t)a.mean | (uintptr_t)a.reg;
     if (al & 15) return "token_features: a device pointer is not 16-byte aligned";
     if ((uintptr_t)a.stats & 7) return "token_features: the row statistics buffer is not 8-byte aligned";
     return nullptr;
@@ -274,6 +409,16 @@ hipError_t launch_token_features(const FeatureArgs& a, hipStream_t s) {
     if (a.form == VH_FEAT_FORM_F32) return feat_launch_in<InF32>(a, s);
     if (a.form == VH_DTYPE_FP8) return feat_launch_in<InSplit8>(a, s);
     return a.form == VH_DTYPE_BF16 ? feat_launch_in<InSplit16<BF16>>(a, s) : feat_launch_in<InSplit16<FP16>>(a, s);
+}
+
+hipError_t launch_feature_capture(const void* src_hi, void* dst_hi, size_t bytes_hi, const void* src_lo, void* dst_lo, size_t bytes_lo,
+                                  hipStream_t s) {
+    const uintptr_t al = (uintptr_t)src_hi | (uintptr_t)dst_hi | (uintptr_t)src_lo | (uintptr_t)dst_lo | bytes_hi | bytes_lo;
+    if (!src_hi || !dst_hi || !bytes_hi || (bytes_lo && (!src_lo || !dst_lo)) || (al & 15)) return hipErrorInvalidValue;
+    const int64_t n_hi = (int64_t)(bytes_hi / 16), n_lo = (int64_t)(bytes_lo / 16);
+    hipLaunchKernelGGL(feat_capture_kernel, dim3((unsigned)((n_hi + n_lo + 1023) / 1024)), dim3(256), 0, s, (const u32x4*)src_hi, (u32x4*)dst_hi,
+                       n_hi, (const u32x4*)src_lo, (u32x4*)dst_lo, n_lo);
+    return hipGetLastError();
 }
 
 }  // namespace vh

@@ -226,7 +226,7 @@ hipError_t launch_layernorm_split(const void* hi, const void* lo, int64_t rows, 
 // Token features (kernels_features.hip; contract: vithip.h, "Token features"): the rows of a residual stream [batch * tokens, dim]
 // -> the caller's element type (VH_ELEM_F32 / F16 / BF16), as they are (VH_FEAT_RAW) or through LayerNorm(gamma, beta, eps)
 // (VH_FEAT_NORM), and the mean over an image's patch tokens (tokens lead .. tokens - 1, a serial fp32 chain in that order; lead = 1 + the register
-// tokens, which no output receives).
+// tokens, which go to `reg`).
 // form: VH_DTYPE_BF16 / FP16 = split planes (hi 16-bit, lo one scaled e4m3 byte), VH_DTYPE_FP8 = e4m3 hi + bf16 lo,
 // VH_FEAT_FORM_F32 = fp32 rows in `hi`, lo null.  cls [batch][dim] <- token 0, patch [batch][tokens - lead][dim] <- tokens lead .., mean
 // [batch][dim]; any may be null, not all.  stats [batch * tokens][2]: scratch of the normalised mean (row kernel writes, mean
@@ -246,9 +246,15 @@ struct FeatureArgs {
     void* mean;
     float* stats;
     int lead = 1;   // rows in front of an image's patch rows: 1 .. tokens - 1
+    void* reg = nullptr;               // [batch][lead - 1][dim] <- tokens 1 .. lead - 1 (the register rows); needs lead >= 2
+    int patch_layout = VH_FEAT_ROWS;   // VH_FEAT_NCHW: patch is [batch][dim][tokens - lead] (feat_nchw_kernel), the same elements transposed
 };
 const char* features_check(const FeatureArgs& a);
 hipError_t launch_token_features(const FeatureArgs& a, hipStream_t stream);
+// The rows of a tapped layer into the capture store (vithip.h "Layer features"): bytes_hi of the hi plane (or the fp32 array), then
+// bytes_lo of the lo plane (0: none), in ONE launch.  Pointers and byte counts are multiples of 16.
+hipError_t launch_feature_capture(const void* src_hi, void* dst_hi, size_t bytes_hi, const void* src_lo, void* dst_lo, size_t bytes_lo,
+                                  hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln
 hipError_t launch_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim,
                              float scale, void* w8, float* wscale, float* c, float* d, hipStream_t stream);

@@ -281,6 +281,15 @@ struct vh_ctx {
     int64_t last_us = 0;
     bool timed = false;
     int last_batch = 0;
+    // Layer features (vh_set_feature_layers): the listed layers and ONE capture store, a slot of feat_slot bytes for every listed
+    // layer below cfg.layers in list order.  A slot holds [max_batch * T][D] rows as the path keeps them: the hi plane (or the fp32
+    // array) at 0, the lo plane behind max_batch * T * D hi elements; it is sized at 3 bytes per element where the residual stays
+    // two planes for good, else 4 (decided once, at the call).  What the LAST forward captured (enqueue_forward records it; the list call clears it):
+    // cap_n listed layers cap_layers[], cap_nl = layers it ran, cap_form = the FeatureArgs form of the rows it copied.
+    int feat_layers[VH_MAX_FEATURE_LAYERS] = {0}, feat_n = 0;
+    char* feat_store = nullptr;
+    size_t feat_slot = 0;
+    int cap_layers[VH_MAX_FEATURE_LAYERS] = {0}, cap_n = 0, cap_nl = -1, cap_form = VH_FEAT_FORM_F32;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
     struct RingSlot {
         float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;   // h_in / d_in hold bytes in a u8 ring
@@ -577,6 +586,29 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     if (img0 == 0) c->tail_splits = 0;
     if ((rc = mark(-1))) return rc;
     const int nl = (c->run_layers < 0 || c->run_layers > f.layers) ? f.layers : c->run_layers;
+    // Layer features: behind fc2 of layer l, when l + 1 is listed and more layers follow, this part's real rows go to the capture
+    // store in the form the path holds them, at the part's row offset -- one launch.  (The listed layer that equals nl needs no copy:
+    // the live residual serves it.)  What was captured is recorded for the read-out; every part records the same values.
+    const int cap_form = c->split ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32;
+    c->cap_nl = nl;
+    c->cap_form = cap_form;
+    c->cap_n = c->feat_n;
+    for (int i = 0; i < c->cap_n; ++i) c->cap_layers[i] = c->feat_layers[i];
+    auto capture = [&](int l) -> int {
+        if (!c->feat_store || l + 1 >= nl) return VH_OK;
+        for (int i = 0; i < c->feat_n; ++i) {
+            if (c->feat_layers[i] != l + 1) continue;
+            char* const slot = c->feat_store + (size_t)i * c->feat_slot;
+            const size_t n = (size_t)rows * D, all = (size_t)f.max_batch * T * D;
+            if (cap_form == VH_FEAT_FORM_F32)
+                HIPCHK(&c->err, launch_feature_capture(x, slot + r0 * D * 4, n * 4, nullptr, nullptr, 0, s));
+            else {
+                const size_t hb = c->fp8 ? 1 : 2, lb = c->fp8 ? 2 : 1;
+                HIPCHK(&c->err, launch_feature_capture(xn16, slot + r0 * D * hb, n * hb, xlo16, slot + all * hb + r0 * D * lb, n * lb, s));
+            }
+        }
+        return VH_OK;
+    };
     // Patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip; the split residual of the 16-bit paths):
     // VH_PATCH_FUSED=1 selects it -- measured, DESIGN.md 4.4 -- the default is the im2col pass + the persistent GEMM.
     // VH_FLAG_PRE_LN: a LayerNorm needs whole rows, which no patch-GEMM tile holds -- such a context embeds through the fp32-x branch
@@ -731,6 +763,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         g2.wscale = s2;
         set_tiled(g2, false, h_tiled);
         if ((rc = stage(ST_FC2, [&] { return launch_gemm(g2, s); }))) return rc;
+        if ((rc = capture(l))) return rc;
         if (l + 1 < nl) {
             HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
             if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
@@ -805,6 +838,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         const bool more = l + 1 < nl;   // the next layer's LN1 follows this layer's fc2
         if ((rc = resid_gemm_ln(h16, c->w2_16[l], P + o.f2b, s2, M, more ? P + L.layer[l + 1].ln1w : nullptr,
                                 more ? P + L.layer[l + 1].ln1b : nullptr, ST_FC2))) return rc;
+        if ((rc = capture(l))) return rc;   // behind both launches of resid_gemm_ln: x is complete and nothing writes it
     }
     if (c->split && nl > 0)
         HIPCHK(&c->err, launch_layernorm_split(xn16, xlo16, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, c->fp8 ? VH_DTYPE_FP8 : dt16, s));
@@ -1405,6 +1439,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->rz_frames) hipFree(c->rz_frames);
     if (c->rz_u8) hipFree(c->rz_u8);
     if (c->arena) hipFree(c->arena);
+    if (c->feat_store) hipFree(c->feat_store);
     if (c->w16) hipFree(c->w16);
     if (c->blob) hipFree(c->blob);
     for (hipEvent_t e : c->tev) hipEventDestroy(e);
@@ -2324,30 +2359,63 @@ static int features_check_call(vh_ctx* c, const vh_features* f, bool device) {
     if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "read_features: no forward has run");
     return VH_OK;
 }
-static int features_enqueue(vh_ctx* c, const vh_features& f) {
+// where the rows of a read-out live, and whether its normalised class-token rows are the head's (the final state: clsn32)
+struct FeatSource { const void* hi; const void* lo; int form; bool head_cls; };
+static FeatSource features_live(const vh_ctx* c) {
     const vh_config& g = c->cfg;
     const int nl = (c->run_layers < 0 || c->run_layers > g.layers) ? g.layers : c->run_layers;
     const bool planes = c->split && nl > 0;   // where the last forward left the rows: the two planes, or the fp32 array
+    return FeatSource{planes ? (const void*)c->xn16 : (const void*)c->x, planes ? c->xlo16 : nullptr,
+                      planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32, true};
+}
+static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSource& src, const char* who) {
+    const vh_config& g = c->cfg;
     const bool norm = f.norm == VH_FEAT_NORM;
     FeatureArgs a{};
-    a.hi = planes ? (const void*)c->xn16 : (const void*)c->x;
-    a.lo = planes ? c->xlo16 : nullptr;
-    a.form = planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32;
+    a.hi = src.hi; a.lo = src.lo; a.form = src.form;
     a.batch = c->last_batch; a.tokens = c->L.T; a.lead = c->L.lead; a.dim = g.dim;
     a.gamma = c->params + c->L.lnfw; a.beta = c->params + c->L.lnfb; a.eps = g.ln_eps;
     a.elem = f.elem; a.norm = f.norm;
-    a.cls = norm ? nullptr : f.cls;   // the normalised class-token rows are the ones the head multiplied: a conversion copy of clsn32
+    const bool copy_cls = norm && src.head_cls;   // the normalised class-token rows the head multiplied: a conversion copy of clsn32
+    a.cls = copy_cls ? nullptr : f.cls;
     a.patch = f.patch; a.mean = f.mean; a.stats = c->stats;
-    if (a.cls || a.patch || a.mean) {
-        if (const char* why = features_check(a)) return fail(&c->err, VH_ERR_INVALID, "read_features: %s", why);
+    a.reg = f.reg; a.patch_layout = f.patch_layout;
+    if (a.cls || a.patch || a.mean || a.reg) {
+        if (const char* why = features_check(a)) return fail(&c->err, VH_ERR_INVALID, "%s: %s", who, why);
         HIPCHK(&c->err, launch_token_features(a, c->stream));
     }
-    if (norm && f.cls) {
+    if (copy_cls && f.cls) {
         const int64_t n = (int64_t)c->last_batch * g.dim;
         if (f.elem == VH_ELEM_F32) HIPCHK(&c->err, hipMemcpyAsync(f.cls, c->clsn32, n * 4, hipMemcpyDeviceToDevice, c->stream));
         else HIPCHK(&c->err, launch_cast(c->clsn32, f.cls, n, f.elem == VH_ELEM_BF16 ? VH_DTYPE_BF16 : VH_DTYPE_FP16, c->stream));
     }
     return VH_OK;
+}
+// the host form: the outputs are staged in the q|k|v buffer -- scratch between forwards (every forward writes its rows before
+// attention reads them), and at 6 bytes per row element always large enough for fp32 rows of every token + the two [batch][D] outputs
+static int features_read_host(vh_ctx* c, const vh_layer_features& f, const FeatSource& src, const char* who) {
+    const size_t es = f.elem == VH_ELEM_F32 ? 4 : 2, D = c->cfg.dim, B = c->last_batch;
+    const size_t n_row = B * D * es, n_patch = B * (size_t)c->L.NP * D * es, n_reg = B * (size_t)c->L.R * D * es;
+    const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * D * 2;
+    char* const base = (char*)c->qkv16;
+    size_t at = 0;
+    auto take = [&](bool want, size_t bytes) -> void* { if (!want) return nullptr; void* p = base + at; at += align_up(bytes, 256); return p; };
+    vh_layer_features d = f;
+    d.patch = take(f.patch != nullptr, n_patch);
+    d.cls = take(f.cls != nullptr, n_row);
+    d.mean = take(f.mean != nullptr, n_row);
+    d.reg = take(f.reg != nullptr, n_reg);
+    if (at > cap) return fail(&c->err, VH_ERR_STATE, "%s: staging needs %zu bytes, the scratch holds %zu", who, at, cap);
+    if (int rc = features_enqueue(c, d, src, who)) return rc;
+    if (f.patch) HIPCHK(&c->err, hipMemcpyAsync(f.patch, d.patch, n_patch, hipMemcpyDeviceToHost, c->stream));
+    if (f.cls) HIPCHK(&c->err, hipMemcpyAsync(f.cls, d.cls, n_row, hipMemcpyDeviceToHost, c->stream));
+    if (f.mean) HIPCHK(&c->err, hipMemcpyAsync(f.mean, d.mean, n_row, hipMemcpyDeviceToHost, c->stream));
+    if (f.reg) HIPCHK(&c->err, hipMemcpyAsync(f.reg, d.reg, n_reg, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return VH_OK;
+}
+static vh_layer_features features_final(const vh_features& f) {
+    return vh_layer_features{f.cls, f.patch, f.mean, nullptr, f.elem, f.norm, -1, VH_FEAT_ROWS};
 }
 int vh_features_dims(const vh_ctx* c, int* batch, int* tokens, int* patches, int* dim) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "features_dims: null context");
@@ -2360,7 +2428,7 @@ int vh_features_dims(const vh_ctx* c, int* batch, int* tokens, int* patches, int
 int vh_read_features_device_async(vh_ctx* c, const vh_features* f) {
     if (int rc = features_check_call(c, f, true)) return rc;
     HIPCHK(&c->err, hipSetDevice(c->device));
-    return features_enqueue(c, *f);
+    return features_enqueue(c, features_final(*f), features_live(c), "read_features");
 }
 int vh_read_features_device(vh_ctx* c, const vh_features* f) {
     if (int rc = vh_read_features_device_async(c, f)) return rc;
@@ -2370,25 +2438,113 @@ int vh_read_features_device(vh_ctx* c, const vh_features* f) {
 int vh_read_features(vh_ctx* c, const vh_features* f) {
     if (int rc = features_check_call(c, f, false)) return rc;
     HIPCHK(&c->err, hipSetDevice(c->device));
-    // staged in the q|k|v buffer: scratch between forwards (every forward writes its rows before attention reads them), and at
-    // 6 bytes per row element always large enough for fp32 patch rows + the two [batch][D] outputs
-    const size_t es = f->elem == VH_ELEM_F32 ? 4 : 2, D = c->cfg.dim, B = c->last_batch;
-    const size_t n_row = B * D * es, n_patch = B * (size_t)c->L.NP * D * es;
-    const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * D * 2;
-    char* const base = (char*)c->qkv16;
-    size_t at = 0;
-    auto take = [&](bool want, size_t bytes) -> void* { if (!want) return nullptr; void* p = base + at; at += align_up(bytes, 256); return p; };
-    vh_features d = *f;
-    d.patch = take(f->patch != nullptr, n_patch);
-    d.cls = take(f->cls != nullptr, n_row);
-    d.mean = take(f->mean != nullptr, n_row);
-    if (at > cap) return fail(&c->err, VH_ERR_STATE, "read_features: staging needs %zu bytes, the scratch holds %zu", at, cap);
-    if (int rc = features_enqueue(c, d)) return rc;
-    if (f->patch) HIPCHK(&c->err, hipMemcpyAsync(f->patch, d.patch, n_patch, hipMemcpyDeviceToHost, c->stream));
-    if (f->cls) HIPCHK(&c->err, hipMemcpyAsync(f->cls, d.cls, n_row, hipMemcpyDeviceToHost, c->stream));
-    if (f->mean) HIPCHK(&c->err, hipMemcpyAsync(f->mean, d.mean, n_row, hipMemcpyDeviceToHost, c->stream));
+    return features_read_host(c, features_final(*f), features_live(c), "read_features");
+}
+
+// ---- layer features (vithip.h "Layer features") ---------------------------------------------------------------------------
+// The list and the capture store; enqueue_forward copies into the store and records what it captured (cap_*).
+int vh_set_feature_layers(vh_ctx* c, const int* layers, int n) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "set_feature_layers: null context");
+    if (n < 0 || n > VH_MAX_FEATURE_LAYERS) return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: %d layers, outside 0..%d", n, VH_MAX_FEATURE_LAYERS);
+    if (n > 0 && !layers) return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: null list");
+    for (int i = 0; i < n; ++i) {
+        if (layers[i] < 1 || layers[i] > c->cfg.layers)
+            return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: entry %d is layer %d, outside 1..%d", i, layers[i], c->cfg.layers);
+        if (i && layers[i] <= layers[i - 1])
+            return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: the list must be strictly ascending (entry %d is %d after %d)", i, layers[i], layers[i - 1]);
+    }
+    if (n > 0 && (c->cfg.flags & VH_FLAG_CLS_TAIL))
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "set_feature_layers: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "set_feature_layers: a ring exists on this context; vh_ring_destroy first");
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    int slots = 0;
+    for (int i = 0; i < n; ++i) slots += layers[i] < c->cfg.layers;
+    // 3 bytes per element where the residual stays two planes for good; 4 where it is, or may become (the guarded fold), the fp32 array
+    const int eb = c->split_cfg && !c->guard_auto ? 3 : 4;
+    const size_t slot = align_up((size_t)c->cfg.max_batch * c->L.T * c->cfg.dim * eb, 256);
+    char* store = nullptr;
+    if (slots) {
+        const hipError_t e = hipMalloc((void**)&store, slot * slots);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(&c->err, VH_ERR_HIP, "set_feature_layers: no room for the capture store (%d layers x %zu bytes): %s; the previous list stays",
+                        slots, slot, hipGetErrorString(e));
+        }
+    }
+    drop_graphs(c);   // captured launch sequences hold the old list's copies and the old store
+    if (c->feat_store) hipFree(c->feat_store);
+    c->feat_store = store;
+    c->feat_slot = slot;
+    c->feat_n = n;
+    for (int i = 0; i < n; ++i) c->feat_layers[i] = layers[i];
+    c->cap_n = 0;     // what the last forward captured lived in the old store
+    return VH_OK;
+}
+int vh_get_feature_layers(const vh_ctx* c, int* layers, int* n) {
+    if (!c || !n) return fail(nullptr, VH_ERR_INVALID, "get_feature_layers: null argument");
+    *n = c->feat_n;
+    for (int i = 0; layers && i < c->feat_n; ++i) layers[i] = c->feat_layers[i];
+    return VH_OK;
+}
+
+// every refusal of the three read calls; on success *src says where the layer's rows live
+static int layer_features_check_call(vh_ctx* c, const vh_layer_features* f, bool device, FeatSource* src) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "read_layer_features: null context");
+    if (!f) return fail(&c->err, VH_ERR_INVALID, "read_layer_features: null descriptor");
+    if (!f->cls && !f->patch && !f->mean && !f->reg)
+        return fail(&c->err, VH_ERR_INVALID, "read_layer_features: no output requested (cls, patch, mean and reg are all NULL)");
+    if (f->elem != VH_ELEM_F32 && f->elem != VH_ELEM_F16 && f->elem != VH_ELEM_BF16)
+        return fail(&c->err, VH_ERR_INVALID, "read_layer_features: elem %d is not VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16", f->elem);
+    if (f->norm != VH_FEAT_NORM && f->norm != VH_FEAT_RAW)
+        return fail(&c->err, VH_ERR_INVALID, "read_layer_features: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", f->norm);
+    if (f->patch_layout != VH_FEAT_ROWS && f->patch_layout != VH_FEAT_NCHW)
+        return fail(&c->err, VH_ERR_INVALID, "read_layer_features: patch_layout %d is not VH_FEAT_ROWS (0) or VH_FEAT_NCHW (1)", f->patch_layout);
+    const int layers = c->cfg.layers;
+    if (f->layer != -1 && (f->layer < 1 || f->layer > layers))
+        return fail(&c->err, VH_ERR_INVALID, "read_layer_features: layer %d is not -1 or 1..%d", f->layer, layers);
+    if (device && (((uintptr_t)f->cls | (uintptr_t)f->patch | (uintptr_t)f->mean | (uintptr_t)f->reg) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "read_layer_features: a device output pointer is not 16-byte aligned (cls %p, patch %p, mean %p, reg %p)",
+                    f->cls, f->patch, f->mean, f->reg);
+    if (f->reg && c->L.R == 0) return fail(&c->err, VH_ERR_INVALID, "read_layer_features: reg on a context without register tokens (VH_FLAG_REGISTERS)");
+    if (c->cfg.flags & VH_FLAG_CLS_TAIL)
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "read_layer_features: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "read_layer_features: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
+    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "read_layer_features: no forward has run");
+    if (f->layer == -1) { *src = features_live(c); return VH_OK; }
+    int slot = -1;
+    for (int i = 0; i < c->cap_n; ++i) if (c->cap_layers[i] == f->layer) slot = i;
+    if (f->layer < layers && slot < 0)
+        return fail(&c->err, VH_ERR_STATE, "read_layer_features: layer %d was not in the list when the last forward was enqueued (vh_set_feature_layers)", f->layer);
+    if (f->layer > c->cap_nl)
+        return fail(&c->err, VH_ERR_STATE, "read_layer_features: the last forward ran %d layers and did not reach layer %d (vh_debug_set_layers)", c->cap_nl, f->layer);
+    if (f->layer == c->cap_nl) {   // the live residual; its normalised class-token rows are the head's for the whole model only
+        *src = features_live(c);
+        src->head_cls = f->layer == layers;
+        return VH_OK;
+    }
+    const char* const base = c->feat_store + (size_t)slot * c->feat_slot;
+    const size_t all = (size_t)c->cfg.max_batch * c->L.T * c->cfg.dim;
+    if (c->cap_form == VH_FEAT_FORM_F32) *src = FeatSource{base, nullptr, VH_FEAT_FORM_F32, false};
+    else *src = FeatSource{base, base + all * (c->cap_form == VH_DTYPE_FP8 ? 1 : 2), c->cap_form, false};
+    return VH_OK;
+}
+int vh_read_layer_features_device_async(vh_ctx* c, const vh_layer_features* f) {
+    FeatSource src{};
+    if (int rc = layer_features_check_call(c, f, true, &src)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return features_enqueue(c, *f, src, "read_layer_features");
+}
+int vh_read_layer_features_device(vh_ctx* c, const vh_layer_features* f) {
+    if (int rc = vh_read_layer_features_device_async(c, f)) return rc;
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
     return VH_OK;
+}
+int vh_read_layer_features(vh_ctx* c, const vh_layer_features* f) {
+    FeatSource src{};
+    if (int rc = layer_features_check_call(c, f, false, &src)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return features_read_host(c, *f, src, "read_layer_features");
 }
 
 // ---- operator-level entry points ------------------------------------------------------------------
@@ -2805,16 +2961,27 @@ int vh_op_cast(const float* in, void* out16, int64_t n, int dtype, void* stream)
 }
 // the token-feature kernels on caller-made rows; the normalised mean's row statistics take a scratch of the tap's own (a test
 // and measurement tap: the context calls use the context's statistics buffer and allocate nothing)
-int vh_op_token_features(const void* hi, const void* lo, int form, int batch, int tokens, int dim, const float* gamma, const float* beta,
-                         float eps, int elem, int norm, void* patch_out, void* mean_out, void* stream) {
-    FeatureArgs a{hi, lo, form, batch, tokens, dim, gamma, beta, eps, elem, norm, nullptr, patch_out, mean_out, nullptr};
+static int op_token_features_run(FeatureArgs a, void* stream) {
     if (const char* why = features_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
-    if (mean_out && norm == VH_FEAT_NORM) OPCHK(hipMalloc((void**)&a.stats, (size_t)batch * tokens * 2 * sizeof(float)));
+    if (a.mean && a.norm == VH_FEAT_NORM) OPCHK(hipMalloc((void**)&a.stats, (size_t)a.batch * a.tokens * 2 * sizeof(float)));
     hipError_t e = launch_token_features(a, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (a.stats) hipFree(a.stats);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "token_features failed: %s", hipGetErrorString(e));
     return VH_OK;
+}
+int vh_op_token_features(const void* hi, const void* lo, int form, int batch, int tokens, int dim, const float* gamma, const float* beta,
+                         float eps, int elem, int norm, void* patch_out, void* mean_out, void* stream) {
+    return op_token_features_run(FeatureArgs{hi, lo, form, batch, tokens, dim, gamma, beta, eps, elem, norm, nullptr, patch_out, mean_out, nullptr}, stream);
+}
+int vh_op_token_features2(const void* hi, const void* lo, int form, int batch, int tokens, int lead, int dim, const float* gamma,
+                          const float* beta, float eps, int elem, int norm, void* patch_out, int patch_layout, void* mean_out, void* reg_out,
+                          void* stream) {
+    FeatureArgs a{hi, lo, form, batch, tokens, dim, gamma, beta, eps, elem, norm, nullptr, patch_out, mean_out, nullptr};
+    a.lead = lead;
+    a.reg = reg_out;
+    a.patch_layout = patch_layout;
+    return op_token_features_run(a, stream);
 }
 int vh_op_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind, float sigma, void* stream) {
     if (!out || n <= 0 || kind < 0 || kind > 2) return fail(nullptr, VH_ERR_INVALID, "fill: bad argument");

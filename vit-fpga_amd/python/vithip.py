@@ -96,6 +96,17 @@ class Features(C.Structure):
     _fields_ = [("cls", C.c_void_p), ("patch", C.c_void_p), ("mean", C.c_void_p), ("elem", C.c_int32), ("norm", C.c_int32)]
 
 
+FEAT_ROWS, FEAT_NCHW = 0, 1   # vh_layer_features.patch_layout (VH_FEAT_*): patch [B, NP, D] / [B, D, gh, gw]
+MAX_FEATURE_LAYERS = 8
+
+
+class LayerFeatures(C.Structure):
+    """vh_layer_features: Features + reg (the register rows), layer (-1 / cfg.layers = the final state, else a listed layer of the
+    last forward) and patch_layout (FEAT_ROWS / FEAT_NCHW).  48 bytes."""
+    _fields_ = [("cls", C.c_void_p), ("patch", C.c_void_p), ("mean", C.c_void_p), ("reg", C.c_void_p), ("elem", C.c_int32),
+                ("norm", C.c_int32), ("layer", C.c_int32), ("patch_layout", C.c_int32)]
+
+
 L422_YUYV, L422_UYVY, L422_YVYU, L422_VYUY, L422_V210 = range(5)   # vh_frame_yuy2.layout (VH_422_*); V210: the 16-bit entry points only
 class FrameBGRA(C.Structure):
     """vh_frame_bgra: one packed 4:4:4 frame (one plane of pixels whose samples lie as `layout`, L444_*, says) inside the buffer of a
@@ -235,6 +246,11 @@ SYMBOLS = {
     "vh_read_features": (_i, [_vp, _vp]),
     "vh_read_features_device": (_i, [_vp, _vp]),
     "vh_read_features_device_async": (_i, [_vp, _vp]),
+    "vh_set_feature_layers": (_i, [_vp, _pi, _i]),
+    "vh_get_feature_layers": (_i, [_vp, _pi, _pi]),
+    "vh_read_layer_features": (_i, [_vp, _vp]),
+    "vh_read_layer_features_device": (_i, [_vp, _vp]),
+    "vh_read_layer_features_device_async": (_i, [_vp, _vp]),
     "vh_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -280,6 +296,7 @@ SYMBOLS = {
     "vh_op_resize_y410": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
+    "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
     "vh_group_create": (_i, [C.POINTER(Config), _pi, _i, C.POINTER(_vp)]),
@@ -1517,6 +1534,67 @@ class VitContext:
         """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
         _check(lib().vh_read_features_device_async(self.h, C.byref(desc)), self.h)
 
+    # ---- layer features: several layers of one forward (vithip.h "Layer features") ----
+    def set_feature_layers(self, layers):
+        """The layers every following forward captures: strictly ascending, each 1 .. layers (k = the residual stream after k
+        layers, Hugging Face's hidden_states[k]); an empty list clears it and frees the capture store."""
+        layers = [int(k) for k in layers]
+        arr = (C.c_int * max(len(layers), 1))(*layers)
+        _check(lib().vh_set_feature_layers(self.h, arr, len(layers)), self.h)
+
+    def feature_layers(self):
+        arr, n = (C.c_int * MAX_FEATURE_LAYERS)(), C.c_int(0)
+        _check(lib().vh_get_feature_layers(self.h, arr, C.byref(n)), self.h)
+        return [arr[i] for i in range(n.value)]
+
+    def read_layer_features(self, layer=-1, cls=True, patch=True, mean=False, reg=False, elem=ELEM_F32, norm=FEAT_NORM, nchw=False):
+        """read_features for `layer` of the last forward (-1 / the model's layer count: the final state; else a listed layer), plus
+        "reg": [B, R, D], and with nchw the patch rows as [B, D, gh, gw]."""
+        b, _, n, d = self.features_dims()
+        dt = {ELEM_F32: np.float32, ELEM_F16: np.float16, ELEM_BF16: np.uint16}.get(elem, np.float32)
+        b1 = max(b, 1)   # (before the first forward the call is refused below, with the library's message)
+        g = self.cfg["image_size"] // self.cfg["patch_size"]
+        out = {}
+        if cls:
+            out["cls"] = np.empty((b1, d), dtype=dt)
+        if patch:
+            out["patch"] = np.empty((b1, d, g, g) if nchw else (b1, n, d), dtype=dt)
+        if mean:
+            out["mean"] = np.empty((b1, d), dtype=dt)
+        if reg:
+            out["reg"] = np.empty((b1, max(self.register_tokens(), 1), d), dtype=dt)   # (no registers: refused below)
+        desc = LayerFeatures(*(out[k].ctypes.data if k in out else None for k in ("cls", "patch", "mean", "reg")), elem, norm, layer,
+                             FEAT_NCHW if nchw else FEAT_ROWS)
+        _check(lib().vh_read_layer_features(self.h, C.byref(desc)), self.h)
+        return out
+
+    def read_layer_features_device(self, desc):
+        """desc: a LayerFeatures of device pointers (16-byte aligned); enqueues on the context's stream and waits."""
+        _check(lib().vh_read_layer_features_device(self.h, C.byref(desc)), self.h)
+
+    def read_layer_features_device_async(self, desc):
+        """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
+        _check(lib().vh_read_layer_features_device_async(self.h, C.byref(desc)), self.h)
+
+    def get_intermediate_layers(self, n=1, reshape=False, return_class_token=False, norm=True):
+        """DINOv2's get_intermediate_layers for the images of the LAST forward: n an int = the last n layers, or a list of 0-based
+        block indices (block i = the residual stream after i + 1 layers).  Capture happens inside a forward: if the context's list
+        differs it is set here and the read is refused (VhError, state) until the caller has run the forward again -- set the list
+        first, or call this once before the first forward.  Returns a tuple with one entry per layer: the patch tokens
+        [B, NP, D], or [B, D, gh, gw] with reshape; with return_class_token (patch, cls [B, D])."""
+        total = self.cfg["layers"]
+        blocks = list(range(total - n, total)) if isinstance(n, int) else [int(i) for i in n]
+        if not blocks or min(blocks) < 0 or max(blocks) >= total or blocks != sorted(set(blocks)):
+            raise ValueError(f"get_intermediate_layers: blocks {blocks} are not ascending indices within 0..{total - 1}")
+        want = [i + 1 for i in blocks]
+        if self.feature_layers() != want:
+            self.set_feature_layers(want)
+        out = []
+        for k in want:
+            f = self.read_layer_features(k, cls=return_class_token, patch=True, norm=FEAT_NORM if norm else FEAT_RAW, nchw=reshape)
+            out.append((f["patch"], f["cls"]) if return_class_token else f["patch"])
+        return tuple(out)
+
 
 def group_shard_bounds(batch, n, r):
     lo, hi = C.c_int(0), C.c_int(0)
@@ -1819,6 +1897,14 @@ def op_token_features(hi_ptr, lo_ptr, form, batch, tokens, dim, gamma_ptr, beta_
     """The token-feature kernels on rows made by the caller: split planes (form DTYPE_BF16 / DTYPE_FP16 / DTYPE_FP8) or fp32 rows
     (FEAT_FORM_F32, lo_ptr None) -> patch [batch, tokens - 1, dim] and / or mean [batch, dim] of `elem`."""
     _check(lib().vh_op_token_features(hi_ptr, lo_ptr, form, batch, tokens, dim, gamma_ptr, beta_ptr, eps, elem, norm, patch_ptr, mean_ptr, None))
+
+
+def op_token_features2(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, elem, norm, patch_ptr, patch_layout,
+                       mean_ptr, reg_ptr):
+    """op_token_features with `lead` rows in front of an image's patch rows (1 + the register rows), reg [batch, lead - 1, dim] and
+    patch_layout FEAT_ROWS ([batch, tokens - lead, dim]) / FEAT_NCHW ([batch, dim, tokens - lead])."""
+    _check(lib().vh_op_token_features2(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, elem, norm, patch_ptr,
+                                       patch_layout, mean_ptr, reg_ptr, None))
 
 
 def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr, dtype):
