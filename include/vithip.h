@@ -148,8 +148,7 @@ typedef struct vh_config {
  *   With R = 0 every kernel writes the bytes it wrote before the flag existed.
  * Token features skip the register rows: cls <- row 0, patch[b][p] <- row 1 + R + p, mean over those NP rows.  The register rows
  * themselves (DINOv2's x_norm_regtokens) are not a field of vh_features, a fixed 32-byte struct: vh_layer_features.reg ("Layer
- * features") returns them.  The opt-in fused patch loader (VH_PATCH_FUSED=1) is not extended: a context with R > 0 takes the im2col + GEMM
- * path whatever the environment says. */
+ * features") returns them. */
 #define VH_FLAG_REGISTERS(n) (((n) & 31) << 9)
 #define VH_FLAG_REGISTERS_MASK (31 << 9)
 #define VH_FLAG_REGISTERS_OF(flags) (((flags) & VH_FLAG_REGISTERS_MASK) >> 9)
@@ -244,7 +243,7 @@ int vh_synchronize(vh_ctx* ctx);
  * a u8 forward are therefore BIT-IDENTICAL to those of the fp32 entry point given the host-computed array x, on every
  * path (folded, plain, split, fp8, pre-LN, any patch size and head dim, VH_FLAG_CLS_TAIL, graphs, streams): everything
  * behind the patch matrix is the same code.  The input crosses PCIe and is read by the gather at 1 byte per element
- * instead of 4.  VH_PATCH_FUSED=1 contexts run the ordinary gather + patch GEMM for u8 input (the fused loader reads fp32).
+ * instead of 4.
  *   vh_set_input_norm   scale, shift: [channels] floats each, all finite (else VH_ERR_INVALID); NULL, NULL restores the
  *                       default scale = 1/255, shift = 0; exactly one NULL is VH_ERR_INVALID.  For the usual
  *                       (p / 255 - mean) / std: scale = 1 / (255 std), shift = -mean / std.  Per-context state; the call waits
@@ -271,8 +270,7 @@ int vh_forward_device_u8_async(vh_ctx* ctx, const uint8_t* in_nhwc_dev, int batc
  * normalised: vh_set_input_norm does not touch them.  The logits are therefore BIT-IDENTICAL to vh_forward of the NHWC fp32
  * array of v, on every path (folded, plain, split, fp8, pre-LN, any patch size and head dim, VH_FLAG_CLS_TAIL, graphs,
  * streams): only the gather in front of the patch GEMM looks at the element type and the layout.  (NHWC, F32) and (NHWC, U8)
- * are vh_forward and vh_forward_u8.  VH_PATCH_FUSED=1 contexts run the ordinary gather + patch GEMM for these inputs, as they
- * do for u8.
+ * are vh_forward and vh_forward_u8.
  *   vh_forward_tensor, vh_forward_device_tensor, vh_forward_device_tensor_async: vh_forward, vh_forward_device and
  *                       vh_forward_device_async under the contract above.  VH_ERR_INVALID for an unknown elem or layout, a
  *                       null pointer, a batch outside 1..max_batch, or a device input pointer that is not 16-byte aligned. */
@@ -721,7 +719,7 @@ int vh_get_step_timing(vh_ctx* ctx, double* step_ms, int max_steps, int* steps);
 /* debug taps: copy an internal activation of the LAST forward to the host as fp32.
  * what: 0 = residual stream x [batch*T, D] after the last layer run,
  *       1 = final-LN'd CLS rows [batch, D],
- *       2 = one float: how many residual GEMMs of the last forward ran as a split launch (VH_TAIL_OVERLAP=1),
+ *       (2 is unused: VH_ERR_INVALID, like any other value not listed here,)
  *       3 = one float: 1 when the last forward kept the MLP hidden activation in its tiled (16-row-blocked) layout -- the
  *           default wherever both MLP GEMMs take the persistent form (16-bit folded path, whole 256-row tiles; VH_H_TILED=0 at
  *           context creation keeps it row-major): same values, same logit bits, fc1's result leaves the registers without an

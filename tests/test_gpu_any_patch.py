@@ -1,6 +1,6 @@
 """GPU parity at any patch size: the padded patch embedding (im2col_pad_kernel + permute_patch_pad_kernel, the patch GEMM on
 the patch vector zero-padded to a multiple of 64) through its own tap vh_op_im2col_padded, inside whole forwards of patch-14
-models against the CPU oracle and the patch-14 golden fixture, and across batch, streams, graph replay and VH_PATCH_FUSED.
+models against the CPU oracle and the patch-14 golden fixture, and across batch, streams and graph replay.
 Tolerances are the existing ones: test_gpu_vit's model-level bounds (fp16 1e-3, bf16 1e-2) and test_gpu_fp8's statistics.
 The patch-14 configurations are defined here (not in vh_synth.CONFIGS, whose every entry other tests run)."""
 import glob
@@ -171,7 +171,7 @@ def test_patch14_fixture_logits_match_the_golden_fp64_logits(path):
 
 
 @pytest.mark.parametrize("dt", DT, ids=lambda d: NAME[d])
-def test_same_bits_across_batch_streams_graph_replay_and_the_fused_patch_option(dt, monkeypatch):
+def test_same_bits_across_batch_streams_and_graph_replay(dt):
     cfg = TINY_P14
     blob = _tiny()["blob"]
     images = S.make_images(cfg, 8, 7)
@@ -188,13 +188,6 @@ def test_same_bits_across_batch_streams_graph_replay_and_the_fused_patch_option(
     for _ in range(3):   # eager, captured, replayed
         assert np.array_equal(ctx.forward(images), seven)
     ctx.set_graph(False)
-    ctx.close()
-    # VH_PATCH_FUSED=1 (read when a context is created) reports these shapes unsupported: the same im2col path, the same bits
-    monkeypatch.setenv("VH_PATCH_FUSED", "1")
-    ctx = vithip.VitContext(cfg, dtype=dt, max_batch=7)
-    monkeypatch.delenv("VH_PATCH_FUSED")
-    ctx.load_weights(blob)
-    assert np.array_equal(ctx.forward(images), seven)
     ctx.close()
 
 

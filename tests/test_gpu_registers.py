@@ -446,25 +446,3 @@ def test_a_blob_with_another_register_count_is_refused(tmp_path):
     with pytest.raises(vithip.VhError):
         c0.load_weights_file(path)
     c0.close()
-
-
-@pytest.mark.parametrize("dt", [BF16, FP16], ids=lambda d: NAME[d])
-def test_the_fused_patch_loader_is_not_taken_with_registers(dt):
-    cfg, regs = _cfg(64, 16, 256, 4, 512, 2), 4      # a shape the fused loader supports (patch 16, 768-wide patch vector)
-    blob, images = R.make_blob(cfg, 5, REG(regs)), S.make_images(cfg, 8, 5)
-    outs = []
-    for env in (None, "1"):
-        if env is not None:
-            os.environ["VH_PATCH_FUSED"] = env
-        try:
-            ctx = vithip.VitContext(cfg, dtype=dt, max_batch=5, flags=REG(regs))
-        finally:
-            os.environ.pop("VH_PATCH_FUSED", None)
-        ctx.load_weights(blob)
-        outs.append(ctx.forward(images))
-        ctx.debug_set_layers(1)
-        ctx.forward(images)
-        outs.append(hidden(ctx, 5))
-        ctx.close()
-    assert np.isfinite(outs[0]).all() and same_bits(outs[0], outs[2]) and same_bits(outs[1], outs[3])
-    assert rel(outs[0], R.forward(cfg, blob, images, REG(regs)).astype(np.float32)) <= MODEL_TOL[dt]

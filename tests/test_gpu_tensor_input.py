@@ -322,10 +322,10 @@ print("forward_torch ok")
 """
 
 
-def run_script(script, **env_extra):
+def run_script(script):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = os.pathsep.join([os.path.join(root, "tests"), os.path.join(root, "vit-fpga_amd", "python")])
-    env = dict(os.environ, PYTHONPATH=path + os.pathsep + os.environ.get("PYTHONPATH", ""), **env_extra)
+    env = dict(os.environ, PYTHONPATH=path + os.pathsep + os.environ.get("PYTHONPATH", ""))
     r = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, text=True, timeout=180)
     assert r.returncode == 0, r.stdout + r.stderr
     return r.stdout
@@ -339,27 +339,3 @@ def test_forward_torch():
     if importlib.util.find_spec("torch") is None:
         pytest.skip("torch is not installed")
     assert "forward_torch ok" in run_script(TORCH_SCRIPT)
-
-
-# ---- 6. VH_PATCH_FUSED=1: the ordinary gather + patch GEMM for tensors ------------------------------------------------------------------
-FUSED_SCRIPT = r"""
-import sys
-import numpy as np
-import tensor_ref as R, vithip
-from test_gpu_u8_input import FOLD_MICRO
-elem, layout = vithip.ELEM_F16, vithip.LAYOUT_NCHW
-ctx = vithip.VitContext(FOLD_MICRO, dtype=vithip.DTYPE_BF16, max_batch=3, flags=vithip.FLAG_LN_FOLD_ON)
-ctx.init_weights_seeded(17)
-assert ctx.ln_fold()
-nhwc = R.make_tensor(elem, 3, FOLD_MICRO["image_size"], 3, seed=6, extremes=False)
-got = ctx.forward_tensor(R.to_layout(nhwc, layout), layout)
-assert np.isfinite(got).all()
-sys.stdout.write(got.tobytes().hex())
-"""
-
-
-def test_patch_fused_context_gives_the_same_bits():
-    """VH_PATCH_FUSED is read when a context is created, so each setting runs in a process of its own (FOLD_MICRO: the split path,
-    the one the fused loader serves)."""
-    outs = [run_script(FUSED_SCRIPT, VH_PATCH_FUSED=fused) for fused in ("0", "1")]
-    assert outs[0] and outs[0] == outs[1]

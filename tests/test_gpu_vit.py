@@ -120,25 +120,6 @@ def test_fp16_is_inside_the_north_star_tolerance_on_64_vit_b_images(flags, label
     assert per.max() <= NORTH_STAR, per.max()
 
 
-@pytest.mark.parametrize("name,batch,dtype_name", [("vit_base", 3, "bf16"), ("vit_base", 70, "fp16"), ("vit_large_384", 1, "fp16")])
-def test_patch_embedding_with_the_gather_inside_the_gemm_gives_the_same_bits(monkeypatch, name, batch, dtype_name):
-    """VH_PATCH_FUSED=1: the patch GEMM reads the NHWC fp32 images itself (kernels_patch.hip: register-path A loader, no patch
-    matrix in memory) instead of im2col + GEMM.  Same conversion of every pixel, same k order in every MFMA, same epilogue:
-    the logits must be bit-identical -- also where the last row tile is ragged (batch 3 and 70: 588 / 13 720 GEMM rows)."""
-    cfg = S.CONFIGS[name]
-    dt = {"bf16": vithip.DTYPE_BF16, "fp16": vithip.DTYPE_FP16}[dtype_name]
-    images = S.make_images(cfg, 5, batch)
-    outs = []
-    for fused in ("0", "1"):
-        monkeypatch.setenv("VH_PATCH_FUSED", fused)
-        ctx = vithip.VitContext(cfg, dtype=dt, max_batch=batch)
-        ctx.init_weights_seeded(0)
-        assert ctx.ln_fold()
-        outs.append(ctx.forward(images))
-        ctx.close()
-    assert np.isfinite(outs[0]).all() and np.array_equal(outs[0], outs[1])
-
-
 @pytest.mark.parametrize("name,batch,dtype_name", [("vit_base", 256, "bf16"), ("vit_base", 300, "fp16"), ("vit_large_384", 64, "fp16")])
 def test_tiled_hidden_activation_gives_the_same_bits_as_the_row_major_one(monkeypatch, name, batch, dtype_name):
     """Round 4: where both MLP GEMMs take the persistent form, fc1 writes the hidden activation h in a 16-row-blocked layout
@@ -595,28 +576,6 @@ def test_ring_pipelined_submit_collect_is_fifo_and_equals_forward():
     assert np.array_equal(ctx.forward(batches[1]), refs[1])
     assert np.array_equal(ctx.ring_collect(), refs[2])
     ctx.close()
-
-
-def test_tail_overlap_split_launch_is_bit_identical(monkeypatch):
-    # VH_TAIL_OVERLAP=1: residual GEMMs are launched as [full rounds of tiles] + [tail round] and the LayerNorm of the
-    # finished rows runs beside the tail round on a helper stream.  Needs more tiles than CUs, i.e. a large batch.
-    cfg = S.CONFIGS["vit_mini"]                     # 37 tokens, dim 192: tiles_n = 1
-    B = 2200                                        # 81 400 rows = 318 M-tiles > 256 CUs, 62 in the tail round
-    outs = {}
-    for flag in ("0", "1"):
-        monkeypatch.setenv("VH_TAIL_OVERLAP", flag)
-        ctx = vithip.VitContext(cfg, dtype=vithip.DTYPE_BF16, max_batch=B)
-        ctx.init_weights_seeded(4)
-        din = vithip.DeviceBuffer(B * 96 * 96 * 3 * 4)
-        dout = vithip.DeviceBuffer(B * cfg["classes"] * 4)
-        ctx.fill_input_seeded(5, B, din.ptr)
-        ctx.forward_device(din.ptr, B, dout.ptr)
-        outs[flag] = dout.to_numpy(np.float32, (B, cfg["classes"]))
-        # the option must really split: 2 residual GEMMs per layer, the last fc2 has no LayerNorm behind it
-        splits = int(ctx.debug_read(2, 1)[0])
-        assert splits == (2 * cfg["layers"] - 1 if flag == "1" else 0), (flag, splits)
-        ctx.close()
-    assert np.isfinite(outs["0"]).all() and np.array_equal(outs["0"], outs["1"])
 
 
 def test_graph_replay_is_bit_identical_to_eager_launches():

@@ -4,8 +4,8 @@
     tools/forward_fingerprint.py --tree <checkout with a built vit-fpga_amd/libvithip.so> [--context NAME]
 
 For every context below -- the smallest at which each branch of enqueue_forward is taken -- it prints one line: the SHA-256 of the
-logits of a seeded batch (init_weights_seeded(0), fill_input_seeded(1, ...)), debug taps 2, 3 and 4 (split residual GEMMs, tiled
-hidden activation, head-major q|k|v) and the stages of profile_forward that recorded events, with their counts.  Two builds agree
+logits of a seeded batch (init_weights_seeded(0), fill_input_seeded(1, ...)), debug taps 3 and 4 (tiled hidden activation,
+head-major q|k|v) and the stages of profile_forward that recorded events, with their counts.  Two builds agree
 when the two outputs are the same text.  Every context runs in a child process of its own (VH_GEMM_PP and the other knobs are read
 once per process or per context); the first child that fails ends the run.
 """
@@ -27,12 +27,11 @@ CONTEXTS = {
     "fp16_b128": (FP16, 128, 0, {}, None),
     "fp16_b256": (FP16, 256, 0, {}, None),
     "fp16_b300": (FP16, 300, 0, {}, None),
-    "fp16_b300_plain_tail_overlap": (FP16, 300, LN_FOLD_OFF, {"VH_TAIL_OVERLAP": "1"}, None),
+    "fp16_b300_plain": (FP16, 300, LN_FOLD_OFF, {}, None),
     "fp16_b256_h_tiled_0": (FP16, 256, 0, {"VH_H_TILED": "0"}, None),
     "fp16_b256_att_tiled_0": (FP16, 256, 0, {"VH_ATT_TILED": "0"}, None),
     "fp16_b256_qkv_hm_0": (FP16, 256, 0, {"VH_QKV_HM": "0"}, None),
     "fp16_b256_resid_split_0": (FP16, 256, 0, {"VH_RESID_SPLIT": "0"}, None),
-    "fp16_b256_patch_fused_1": (FP16, 256, 0, {"VH_PATCH_FUSED": "1"}, None),
     "fp16_b256_cls_tail": (FP16, 256, CLS_TAIL, {}, None),
     "fp8_b256": (FP8, 256, 0, {}, None),
     "fp8_b256_h_tiled_0": (FP8, 256, 0, {"VH_H_TILED": "0"}, None),
@@ -72,10 +71,10 @@ def run_context(tree, name):
     for _ in range(3 if extra == "graph" else 1):
         ctx.forward_device(x.ptr, batch, y.ptr)
         shas.append(hashlib.sha256(y.to_numpy(np.float32, (batch, cfg["classes"])).tobytes()).hexdigest())
-    taps = [int(ctx.debug_read(t, 1)[0]) for t in (2, 3, 4)]
+    taps = [int(ctx.debug_read(t, 1)[0]) for t in (3, 4)]
     prof = ctx.profile_forward(x.ptr, batch, y.ptr)
     slots = " ".join(f"{i}:{prof[s][1]}" for i, s in enumerate(vithip.STAGES) if prof[s][1] or prof[s][0])
-    print(f"{name}: batch {batch} logits {' '.join(shas)} taps(2,3,4) {taps} profile slots(index:events) {slots}", flush=True)
+    print(f"{name}: batch {batch} logits {' '.join(shas)} taps(3,4) {taps} profile slots(index:events) {slots}", flush=True)
     ctx.close()
 
 

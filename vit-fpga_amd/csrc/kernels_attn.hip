@@ -12,11 +12,9 @@
 //     round trip); K is XOR-swizzled for conflict-free ds_read_b128 row reads, V for conflict-free
 //     ds_read_b64_tr_b16 transposed reads — the DMA destination is linear, so both swizzles are applied to
 //     the lane's global SOURCE address.
-//   * persistent workgroups (when two K/V images fit in LDS): a workgroup walks its items and DMA-prefetches
-//     the next item's K/V into the other LDS buffer (and its Q fragments into registers) while it computes
-//     the current one.  The kernel is HBM-bound (620 MB per launch for ViT-B/16 at batch 512); the one-shot
-//     form (load, barrier, compute, store) only reached 55 % of the HBM rate because each workgroup's loads
-//     and math serialise and only two workgroups fit per CU.
+//   * three forms (attn_plan): the one-shot kernel (load, barrier, compute, store; one item per workgroup) for short
+//     sequences, and the two ring forms further down, whose persistent workgroups refill one K/V image tile by tile
+//     under the math.  The kernel is HBM-bound (620 MB per launch for ViT-B/16 at batch 512).
 //   * S^T = K Q^T with v_mfma_f32_32x32x16 (keys on the accumulator rows, the query on the lane): a query's
 //     scores live in ONE lane pair (l, l^32), so the softmax row max / sum are 15 in-register ops + one
 //     cross-half shuffle — a wavefront reduction, no LDS.
@@ -24,7 +22,6 @@
 //     k-order of the accumulator rows); V^T fragments come from the hardware transposing LDS read.
 //     Scores/probabilities never touch LDS or HBM.
 //   * online softmax over 32-key tiles in the exp2 domain, fp32 statistics, keys >= T masked.
-#include <cstdlib>
 #include <type_traits>
 
 #include "vh_kernels.h"
@@ -60,16 +57,15 @@ __device__ __forceinline__ float cross_half_sum(float v) {
     return a + b;
 }
 
-template <typename T, bool PERSIST, typename TO = T>   // TO: output element (T, or E4M3 on the fp8 path)
-__global__ void __launch_bounds__(1024, PERSIST ? 2 : 4)   // one-shot form: <= 128 VGPRs, two 7-wave workgroups per CU put 4 waves on a SIMD
+template <typename T, typename TO = T>   // TO: output element (T, or E4M3 on the fp8 path)
+__global__ void __launch_bounds__(1024, 4)   // <= 128 VGPRs, two 7-wave workgroups per CU put 4 waves on a SIMD
 attention_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem* __restrict__ out,
-                 int tokens, int heads, int slabs, int ntiles, int nitems) {
+                 int tokens, int heads, int slabs, int ntiles) {
     using elem = typename T::elem;
     using vec8 = typename T::vec8;
     using vec4 = typename T::vec4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int kv_bytes = ntiles * 4096;      // one K (or V) image
-    const int buf_bytes = 2 * kv_bytes;      // K then V
+    const int kv_bytes = ntiles * 4096;      // one K (or V) image; K then V
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -78,35 +74,10 @@ attention_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem* __
     const int D = heads * 64;
     const int64_t ld = 3 * (int64_t)D;
 
-    // ---- DMA of one item's K and V: 1 KiB pieces = 8 rows x 128 B, lane -> (row, swizzled chunk) -------
-    const int lr = lane >> 3, pc = lane & 7;
-    const int ngroups = ntiles * 4;          // 8-row groups per matrix
-    auto issue_kv = [&](int item, int buf) {
-        const int bh = item / slabs;
-        const int b = bh / heads, h = bh - b * heads;
-        const elem* base = qkv + (int64_t)b * tokens * ld + h * 64;
-        char* kdst = smem + buf * buf_bytes;
-        for (int g = wave; g < ngroups; g += nw) {
-            const int row = g * 8 + lr;
-            const int rsrc = row < tokens ? row : tokens - 1;   // rows >= tokens replicate the last row
-            const elem* src = base + rsrc * ld;
-            const int ck = pc ^ ((row >> 1) & 7);
-            const int cv = pc ^ (((row >> 1) & 1) << 2);
-            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + D + ck * 8),
-                                             (void __attribute__((address_space(3)))*)(kdst + g * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + 2 * D + cv * 8),
-                                             (void __attribute__((address_space(3)))*)(kdst + kv_bytes + g * 1024), 16, 0, 0);
-        }
-    };
-    auto load_q = [&](int item, vec8 (&qf)[4]) {
-        const int bh = item / slabs, slab = item - bh * slabs;
-        const int b = bh / heads, h = bh - b * heads;
-        int qrow = (slab * nw + wave) * 32 + l31;
-        qrow = qrow < tokens ? qrow : tokens - 1;
-        const elem* qp = qkv + ((int64_t)b * tokens + qrow) * ld + h * 64 + 8 * hl;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const vec8*)(qp + 16 * ks);
-    };
+    // (hipcc's schedule follows the order of these declarations and of the two lambdas below: in this order the kernel is
+    // instruction for instruction the form that was measured)
+    const int lr = lane >> 3, pc = lane & 7;   // DMA: lane -> (row, chunk) of a 1 KiB piece
+    const int ngroups = ntiles * 4;            // 8-row groups per matrix
 
     // per-lane LDS offsets
     const int koff = l31 * 128;
@@ -115,142 +86,151 @@ attention_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem* __
     const int vrow0 = 4 * (g4 >> 1) + tq;             // + 32*kt + 16*s (+8)
     const int vcolb = (16 * (g4 & 1) + 4 * tp) * 2;   // byte offset inside the row, + 64*db
 
-    const int stride = PERSIST ? (int)gridDim.x : nitems;
-    int item = blockIdx.x;
-    int buf = 0;
-    vec8 qf[4], qn[4];
-    issue_kv(item, 0);
-    load_q(item, qf);
+    // the workgroup's item
+    const int item = blockIdx.x;
+    const int bh = item / slabs, slab = item - bh * slabs;
+    const int b = bh / heads, h = bh - b * heads;
+    const int q0 = (slab * nw + wave) * 32;
 
-    while (true) {
-        const int next = item + stride;
-        const bool has_next = PERSIST && next < nitems;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this item's K/V (and Q) have landed
-        __syncthreads();                                  // ... for every wave; previous item's reads are done
-        if (has_next) {
-            issue_kv(next, buf ^ 1);                      // flies under this item's math
-            load_q(next, qn);
+    // ---- DMA of the item's K and V: 1 KiB pieces = 8 rows x 128 B, lane -> (row, swizzled chunk) -------
+    auto issue_kv = [&]() {
+        const elem* base = qkv + (int64_t)b * tokens * ld + h * 64;
+        for (int g = wave; g < ngroups; g += nw) {
+            const int row = g * 8 + lr;
+            const int rsrc = row < tokens ? row : tokens - 1;   // rows >= tokens replicate the last row
+            const elem* src = base + rsrc * ld;
+            const int ck = pc ^ ((row >> 1) & 7);
+            const int cv = pc ^ (((row >> 1) & 1) << 2);
+            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + D + ck * 8),
+                                             (void __attribute__((address_space(3)))*)(smem + g * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + 2 * D + cv * 8),
+                                             (void __attribute__((address_space(3)))*)(smem + kv_bytes + g * 1024), 16, 0, 0);
         }
+    };
+    // ---- the wave's Q fragments ------------------------------------------------------------------------
+    vec8 qf[4];
+    auto load_q = [&]() {
+        int qrow = q0 + l31;
+        qrow = qrow < tokens ? qrow : tokens - 1;
+        const elem* qp = qkv + ((int64_t)b * tokens + qrow) * ld + h * 64 + 8 * hl;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const vec8*)(qp + 16 * ks);
+    };
+    issue_kv();
+    load_q();
 
-        const int bh = item / slabs, slab = item - bh * slabs;
-        const int b = bh / heads, h = bh - b * heads;
-        const int q0 = (slab * nw + wave) * 32;
-        const char* Ks = smem + buf * buf_bytes;
-        const char* Vs = Ks + kv_bytes;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the item's K/V (and Q) have landed
+    __syncthreads();                                  // ... for every wave
+    const char* Ks = smem;
+    const char* Vs = Ks + kv_bytes;
 
-        if (q0 < tokens) {  // wave-uniform
-            f32x16 o0, o1;
+    if (q0 < tokens) {  // wave-uniform
+        f32x16 o0, o1;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-            float m2 = -INFINITY;  // running row max, log2 domain
-            float lsum = 0.f;      // this lane's half of the row sum
+        for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+        float m2 = -INFINITY;  // running row max, log2 domain
+        float lsum = 0.f;      // this lane's half of the row sum
 
-            // lane-constant LDS addresses: K row reads (4 swizzled chunks) and the transposed V reads
-            // (two bases: the 32-column block db flips bit 6 of the swizzled byte offset)
-            const char* kbase = Ks + koff;
-            int kofs[4];
+        // lane-constant LDS addresses: K row reads (4 swizzled chunks) and the transposed V reads
+        // (two bases: the 32-column block db flips bit 6 of the swizzled byte offset)
+        const char* kbase = Ks + koff;
+        int kofs[4];
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) kofs[ks] = ((2 * ks + hl) ^ kswz) << 4;
-            const int vx = ((vrow0 >> 1) & 1) << 6;   // same for rows +8, +16, +32*kt
-            const char* vb0 = Vs + vrow0 * 128 + (vcolb ^ vx);
-            const char* vb1 = Vs + vrow0 * 128 + ((vcolb + 64) ^ vx);
+        for (int ks = 0; ks < 4; ++ks) kofs[ks] = ((2 * ks + hl) ^ kswz) << 4;
+        const int vx = ((vrow0 >> 1) & 1) << 6;   // same for rows +8, +16, +32*kt
+        const char* vb0 = Vs + vrow0 * 128 + (vcolb ^ vx);
+        const char* vb1 = Vs + vrow0 * 128 + ((vcolb + 64) ^ vx);
 
-            // S^T tile: 32 keys x 32 queries
-            auto qk = [&](int kt) {
-                f32x16 s;
+        // S^T tile: 32 keys x 32 queries
+        auto qk = [&](int kt) {
+            f32x16 s;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) s[r] = 0.f;
-                const char* kp = kbase + kt * 4096;
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+            const char* kp = kbase + kt * 4096;
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) s = T::mfma32(*(const vec8*)(kp + kofs[ks]), qf[ks], s);
-                return s;
-            };
-            // V^T fragments of one 32-key tile: [k-step][column block] (hardware-transposing reads)
-            struct VFrag { vec8 f[2][2]; };
-            auto load_v = [&](int kt) {
-                VFrag v;
-                const char* v0 = vb0 + kt * 4096;
-                const char* v1 = vb1 + kt * 4096;
+            for (int ks = 0; ks < 4; ++ks) s = T::mfma32(*(const vec8*)(kp + kofs[ks]), qf[ks], s);
+            return s;
+        };
+        // V^T fragments of one 32-key tile: [k-step][column block] (hardware-transposing reads)
+        struct VFrag { vec8 f[2][2]; };
+        auto load_v = [&](int kt) {
+            VFrag v;
+            const char* v0 = vb0 + kt * 4096;
+            const char* v1 = vb1 + kt * 4096;
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const vec4 a0 = T::tr_read(v0 + ks * 2048), c0 = T::tr_read(v0 + ks * 2048 + 1024);
-                    const vec4 a1 = T::tr_read(v1 + ks * 2048), c1 = T::tr_read(v1 + ks * 2048 + 1024);
+            for (int ks = 0; ks < 2; ++ks) {
+                const vec4 a0 = T::tr_read(v0 + ks * 2048), c0 = T::tr_read(v0 + ks * 2048 + 1024);
+                const vec4 a1 = T::tr_read(v1 + ks * 2048), c1 = T::tr_read(v1 + ks * 2048 + 1024);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { v.f[ks][0][j] = a0[j]; v.f[ks][0][4 + j] = c0[j]; v.f[ks][1][j] = a1[j]; v.f[ks][1][4 + j] = c1[j]; }
-                }
-                return v;
-            };
-            auto softmax_pv = [&](int kt, f32x16 s, const VFrag& vfr, auto masked) {
-                if constexpr (decltype(masked)::value) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-                        if (key >= tokens) s[r] = -INFINITY;
-                    }
-                }
-                // ---- online softmax (row = query = lane pair) --------------------------------------------
-                float mx = s[0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-                mx = cross_half_max(mx);
-                const float mnew = fmaxf(m2, mx);
-                // rescale the running sums only when some row's maximum moved (exact: alpha == 1 otherwise)
-                if (__builtin_amdgcn_ballot_w64(mnew != m2)) {
-                    const float alpha = __builtin_amdgcn_exp2f(m2 - mnew);
-                    lsum *= alpha;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-                    m2 = mnew;
-                }
-                float psum = 0.f;
+                for (int j = 0; j < 4; ++j) { v.f[ks][0][j] = a0[j]; v.f[ks][0][4 + j] = c0[j]; v.f[ks][1][j] = a1[j]; v.f[ks][1][4 + j] = c1[j]; }
+            }
+            return v;
+        };
+        auto softmax_pv = [&](int kt, f32x16 s, const VFrag& vfr, auto masked) {
+            if constexpr (decltype(masked)::value) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    s[r] = __builtin_amdgcn_exp2f(s[r] - mnew);
-                    psum += s[r];
+                    const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+                    if (key >= tokens) s[r] = -INFINITY;
                 }
-                lsum += psum;
-                // ---- O^T += V^T P^T ----------------------------------------------------------------------
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    vec8 pf;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[j] = (elem)s[8 * ks + j];
-                    o0 = T::mfma32(vfr.f[ks][0], pf, o0);
-                    o1 = T::mfma32(vfr.f[ks][1], pf, o1);
-                }
-            };
-            // software pipeline: the V fragments of tile k and the score MFMAs of tile k+1 are issued ahead of the
-            // softmax of tile k, so LDS latency and the matrix pipe sit under the wave's own exp/max/convert stream
-            f32x16 s_cur = qk(0);
-            for (int kt = 0; kt + 1 < ntiles; ++kt) {
-                const VFrag vfr = load_v(kt);
-                const f32x16 s_nxt = qk(kt + 1);
-                softmax_pv(kt, s_cur, vfr, std::false_type{});
-                s_cur = s_nxt;
             }
-            {
-                const VFrag vfr = load_v(ntiles - 1);
-                softmax_pv(ntiles - 1, s_cur, vfr, std::true_type{});   // only the last tile can hold keys >= tokens
+            // ---- online softmax (row = query = lane pair) --------------------------------------------
+            float mx = s[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
+            mx = cross_half_max(mx);
+            const float mnew = fmaxf(m2, mx);
+            // rescale the running sums only when some row's maximum moved (exact: alpha == 1 otherwise)
+            if (__builtin_amdgcn_ballot_w64(mnew != m2)) {
+                const float alpha = __builtin_amdgcn_exp2f(m2 - mnew);
+                lsum *= alpha;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+                m2 = mnew;
             }
+            float psum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                s[r] = __builtin_amdgcn_exp2f(s[r] - mnew);
+                psum += s[r];
+            }
+            lsum += psum;
+            // ---- O^T += V^T P^T ----------------------------------------------------------------------
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                vec8 pf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pf[j] = (elem)s[8 * ks + j];
+                o0 = T::mfma32(vfr.f[ks][0], pf, o0);
+                o1 = T::mfma32(vfr.f[ks][1], pf, o1);
+            }
+        };
+        // software pipeline: the V fragments of tile k and the score MFMAs of tile k+1 are issued ahead of the
+        // softmax of tile k, so LDS latency and the matrix pipe sit under the wave's own exp/max/convert stream
+        f32x16 s_cur = qk(0);
+        for (int kt = 0; kt + 1 < ntiles; ++kt) {
+            const VFrag vfr = load_v(kt);
+            const f32x16 s_nxt = qk(kt + 1);
+            softmax_pv(kt, s_cur, vfr, std::false_type{});
+            s_cur = s_nxt;
+        }
+        {
+            const VFrag vfr = load_v(ntiles - 1);
+            softmax_pv(ntiles - 1, s_cur, vfr, std::true_type{});   // only the last tile can hold keys >= tokens
+        }
 
-            // ---- normalise and store: lane holds O[q][32*db + 8*rg + 4*hl + 0..3] ------------------
-            const float ltot = cross_half_sum(lsum);
-            const float inv = 1.0f / ltot;
-            const int q = q0 + l31;
-            if (q < tokens) {
-                typename TO::elem* op = out + ((int64_t)b * tokens + q) * D + h * 64 + 4 * hl;
+        // ---- normalise and store: lane holds O[q][32*db + 8*rg + 4*hl + 0..3] ------------------
+        const float ltot = cross_half_sum(lsum);
+        const float inv = 1.0f / ltot;
+        const int q = q0 + l31;
+        if (q < tokens) {
+            typename TO::elem* op = out + ((int64_t)b * tokens + q) * D + h * 64 + 4 * hl;
 #pragma unroll
-                for (int rg = 0; rg < 4; ++rg) {
-                    *(typename TO::vec4*)(op + 8 * rg) = pack4<TO>(o0[4 * rg] * inv, o0[4 * rg + 1] * inv, o0[4 * rg + 2] * inv, o0[4 * rg + 3] * inv);
-                    *(typename TO::vec4*)(op + 32 + 8 * rg) = pack4<TO>(o1[4 * rg] * inv, o1[4 * rg + 1] * inv, o1[4 * rg + 2] * inv, o1[4 * rg + 3] * inv);
-                }
+            for (int rg = 0; rg < 4; ++rg) {
+                *(typename TO::vec4*)(op + 8 * rg) = pack4<TO>(o0[4 * rg] * inv, o0[4 * rg + 1] * inv, o0[4 * rg + 2] * inv, o0[4 * rg + 3] * inv);
+                *(typename TO::vec4*)(op + 32 + 8 * rg) = pack4<TO>(o1[4 * rg] * inv, o1[4 * rg + 1] * inv, o1[4 * rg + 2] * inv, o1[4 * rg + 3] * inv);
             }
         }
-        if (!has_next) break;
-        item = next;
-        buf ^= 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = qn[ks];
     }
 }
 
@@ -762,99 +742,75 @@ extern "C" int vh_diag_attn_read(unsigned long long* host, int n_words) {
 
 size_t attention_lds_bytes(int tokens) { return (size_t)((tokens + 31) / 32) * 8192; }
 
-// which form launch_attn_t picks for (tokens, batch, heads): 2 = staged-Q ring, 1 = ring, 0 = one-shot / persistent double-buffered
-static int attn_form(int batch, int tokens, int heads) {
-    const int ntiles = (tokens + 31) / 32, nqb = ntiles;
-    static const int max_waves = [] { const int e = env_int("VH_ATTN_WAVES", 16); return e < 1 || e > 16 ? 16 : e; }();
-    const int slabs = (nqb + max_waves - 1) / max_waves, nw = (nqb + slabs - 1) / slabs;
-    static const int want_ring = env_int("VH_ATTN_RING", 1);
+// The one place that decides how (tokens, layouts) run.  Each wave owns 32 queries; a workgroup has at most 16 waves
+// (T = 577: 10 waves share one K/V image instead of 7), so longer sequences take `slabs` workgroups per head.
+//   staged-Q ring (counted waits): one slab of at least four waves whose trimmed images + staging fit twice in a CU
+//   ring                         : needs the four DMA waves and at least three key tiles
+//   one-shot                     : everything shorter; row-major input and output only (the tiled output and the
+//                                  head-major input exist in the ring forms)
+// NONE: a head's K and V do not fit in LDS, or the layouts ask for a ring form that the shape does not take.
+enum class AttnForm { NONE, ONE_SHOT, RING, RING_QS };
+struct AttnPlan { AttnForm form; int slabs, nw; size_t lds; };
+static AttnPlan attn_plan(int tokens, bool out_tiled, bool in_head_major) {
+    constexpr int kMaxWaves = 16;
+    const int ntiles = (tokens + 31) / 32;   // key tiles = 32-query blocks
+    const int slabs = (ntiles + kMaxWaves - 1) / kMaxWaves, nw = (ntiles + slabs - 1) / slabs;
+    const size_t one = attention_lds_bytes(tokens);
+    if (one > 160 * 1024) return {AttnForm::NONE, slabs, nw, 0};
     const int G = (tokens + 7) / 8, G2 = (G + 1) & ~1;
-    const size_t qs_lds = (size_t)(G + G2 + 4 * nw) * 1024 + 16;
-    if (attention_lds_bytes(tokens) > 160 * 1024) return -1;
-    if (want_ring >= 1 && want_ring != 2 && slabs == 1 && nw >= 4 && 2 * qs_lds <= 160 * 1024) return 2;
-    if (want_ring && ntiles >= 3 && nw >= 4) return 1;
-    (void)batch; (void)heads;
-    return 0;
+    const size_t qs_lds = (size_t)(G + G2 + 4 * nw) * 1024 + 16;   // + the ticket word
+    if (slabs == 1 && nw >= 4 && 2 * qs_lds <= 160 * 1024) return {AttnForm::RING_QS, slabs, nw, qs_lds};
+    if (ntiles >= 3 && nw >= 4) return {AttnForm::RING, slabs, nw, one};
+    if (out_tiled || in_head_major) return {AttnForm::NONE, slabs, nw, 0};
+    return {AttnForm::ONE_SHOT, slabs, nw, one};
 }
-bool attention_tiled_applies(int batch, int tokens, int heads) { return attn_form(batch, tokens, heads) >= 1 && heads % 2 == 0; }
+bool attention_tiled_applies(int batch, int tokens, int heads) {
+    (void)batch;
+    return attn_plan(tokens, true, false).form != AttnForm::NONE && heads % 2 == 0;
+}
 
 template <typename T, typename TO = T, bool OTILE = false, bool IHM = false>
 static hipError_t launch_attn_t(const void* qkv, int batch, int tokens, int heads, void* out, unsigned int* ticket, hipStream_t s, bool tk_zeroed,
                                 int64_t hm_rows = 0) {
-    const int ntiles = (tokens + 31) / 32;
-    const int nqb = ntiles;
-    // waves per workgroup (each owns 32 queries): VH_ATTN_WAVES, default 16 (T = 577: 10 waves share one K/V image instead of 7)
-    static const int max_waves = [] { const int e = env_int("VH_ATTN_WAVES", 16); return e < 1 || e > 16 ? 16 : e; }();
-    const int slabs = (nqb + max_waves - 1) / max_waves;
-    const int nw = (nqb + slabs - 1) / slabs;
-    const size_t one = attention_lds_bytes(tokens);
-    if (one > 160 * 1024) return hipErrorInvalidValue;
+    const AttnPlan p = attn_plan(tokens, OTILE, IHM);
+    if (p.form == AttnForm::NONE) return hipErrorInvalidValue;
+    const int ntiles = (tokens + 31) / 32, slabs = p.slabs, nw = p.nw;
     const int nitems = batch * heads * slabs;
     const int num_cu = device_num_cu();
     if (!num_cu) return hipErrorUnknown;
-    // persistent double-buffered form when two K/V images fit and there is more than one item per CU
-    // VH_ATTN_PERSIST=1 selects it; measured slower at T=197 (7 waves/CU leave the softmax latency-bound), so
-    // the default is the one-shot form with two workgroups per CU.
-    static const int want_persist = env_int("VH_ATTN_PERSIST", 0);
-    const bool persist = want_persist && 2 * one <= 160 * 1024 && nitems > num_cu;
-    // ring forms (default): need the four DMA waves and at least three key tiles; VH_ATTN_RING=0 selects the one-shot
-    // form, 2 the ring without Q staging where the staged form would be used
-    static const int want_ring = env_int("VH_ATTN_RING", 1);
-    // staged-Q ring (counted waits): one slab of at least four waves whose trimmed images + staging fit twice in a CU
-    const int G = (tokens + 7) / 8, G2 = (G + 1) & ~1;
-    const size_t qs_lds = (size_t)(G + G2 + 4 * nw) * 1024 + 16;   // + the ticket word
-    if (want_ring >= 1 && want_ring != 2 && slabs == 1 && nw >= 4 && 2 * qs_lds <= 160 * 1024) {
+    if (p.form == AttnForm::RING_QS) {
         auto k = attention_ring_kernel<T, TO, true, OTILE, IHM>;
         static LdsDone lds_done;
-        if (hipError_t e = ensure_dynamic_lds((const void*)k, qs_lds, lds_done); e != hipSuccess) return e;
+        if (hipError_t e = ensure_dynamic_lds((const void*)k, p.lds, lds_done); e != hipSuccess) return e;
         const int grid = nitems < 2 * num_cu ? nitems : 2 * num_cu;
-        static const int want_dyn = env_int("VH_ATTN_DYN", 1);   // VH_ATTN_DYN=0: equal static shares
-        unsigned int* tk = want_dyn && nw >= 5 && nitems > 2 * grid ? ticket : nullptr;
+        // the device work queue (the kernel's comment: "QS with a ticket counter") where there is something left to draw
+        unsigned int* tk = nw >= 5 && nitems > 2 * grid ? ticket : nullptr;
         if (tk && !tk_zeroed) { if (hipError_t e = hipMemsetAsync(tk, 0, sizeof(unsigned int), s); e != hipSuccess) return e; }
         const unsigned int heads_rcp = (unsigned int)(((1ull << 32) + (unsigned)heads - 1) / (unsigned)heads);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(nw * 64), qs_lds, s, (const typename T::elem*)qkv, (typename TO::elem*)out,
+        hipLaunchKernelGGL(k, dim3(grid), dim3(nw * 64), p.lds, s, (const typename T::elem*)qkv, (typename TO::elem*)out,
                            tokens, heads, slabs, ntiles, nitems, tk, heads_rcp, hm_rows);
         return hipGetLastError();
     }
-    if (want_ring && ntiles >= 3 && nw >= 4) {
+    if (p.form == AttnForm::RING) {
         auto k = attention_ring_kernel<T, TO, false, OTILE, IHM>;
         static LdsDone lds_done;
-        if (hipError_t e = ensure_dynamic_lds((const void*)k, one, lds_done); e != hipSuccess) return e;
-        const int per_cu = (int)(160 * 1024 / one);       // co-resident workgroups per CU by LDS
+        if (hipError_t e = ensure_dynamic_lds((const void*)k, p.lds, lds_done); e != hipSuccess) return e;
+        const int per_cu = (int)(160 * 1024 / p.lds);     // co-resident workgroups per CU by LDS
         int grid = num_cu * (per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));
         if (grid > batch * heads) grid = batch * heads;   // a workgroup walks heads; the slabs of a head share its K/V image
-        hipLaunchKernelGGL(k, dim3(grid), dim3(nw * 64), one, s, (const typename T::elem*)qkv, (typename TO::elem*)out,
+        hipLaunchKernelGGL(k, dim3(grid), dim3(nw * 64), p.lds, s, (const typename T::elem*)qkv, (typename TO::elem*)out,
                            tokens, heads, slabs, ntiles, nitems, (unsigned int*)nullptr, 0u, hm_rows);
         return hipGetLastError();
     }
-    if constexpr (OTILE) return hipErrorInvalidValue;   // the tiled output exists in the ring forms only (attention_tiled_applies)
-    else
-    if constexpr (!std::is_same<T, TO>::value) {
-        auto k = attention_kernel<T, false, TO>;
+    if constexpr (OTILE || IHM) return hipErrorInvalidValue;   // (attn_plan never returns ONE_SHOT for these layouts)
+    else {
+        auto k = attention_kernel<T, TO>;
         static LdsDone lds_done;
-        if (hipError_t e = ensure_dynamic_lds((const void*)k, one, lds_done); e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(nitems), dim3(nw * 64), one, s, (const typename T::elem*)qkv, (typename TO::elem*)out,
-                           tokens, heads, slabs, ntiles, nitems);
+        if (hipError_t e = ensure_dynamic_lds((const void*)k, p.lds, lds_done); e != hipSuccess) return e;
+        hipLaunchKernelGGL(k, dim3(nitems), dim3(nw * 64), p.lds, s, (const typename T::elem*)qkv, (typename TO::elem*)out,
+                           tokens, heads, slabs, ntiles);
         return hipGetLastError();
-    } else
-    if (persist) {
-        const size_t lds = 2 * one;
-        auto k = attention_kernel<T, true>;
-        static LdsDone lds_done;
-        if (hipError_t e = ensure_dynamic_lds((const void*)k, lds, lds_done); e != hipSuccess) return e;
-        const int per_cu = (int)(160 * 1024 / lds);   // co-resident workgroups per CU by LDS
-        int grid = num_cu * (per_cu < 1 ? 1 : per_cu);
-        if (grid > nitems) grid = nitems;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(nw * 64), lds, s, (const typename T::elem*)qkv, (typename T::elem*)out,
-                           tokens, heads, slabs, ntiles, nitems);
-    } else {
-        auto k = attention_kernel<T, false>;
-        static LdsDone lds_done;
-        if (hipError_t e = ensure_dynamic_lds((const void*)k, one, lds_done); e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(nitems), dim3(nw * 64), one, s, (const typename T::elem*)qkv, (typename T::elem*)out,
-                           tokens, heads, slabs, ntiles, nitems);
     }
-    return hipGetLastError();
 }
 
 // ---- attention of the class token only (VH_FLAG_CLS_TAIL: the last layer computes what the logits need) ----------------

@@ -174,11 +174,6 @@ const char* resize_plan_build_bgra(const vh_frame_bgra* desc, int batch, int S, 
                                    std::vector<uint32_t>* words, int* max_tiles);
 hipError_t launch_resize_bgra(bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
                               const float* m12_host, uint8_t* out_u8, hipStream_t stream);
-// patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip): NHWC fp32 images -> the split residual's
-// planes + the first row statistics' partial sums, no patch matrix in memory
-bool patch_fused_supported(int image, int patch, int channels, int dim);
-hipError_t launch_patch_fused(const float* images, int batch, int image, int patch, int channels, const void* wp16, const float* bias,
-                              const float* pos, void* hi, void* lo, float* partials, int64_t prow, int dim, int dtype, hipStream_t stream);
 // the `lead` = 1 + R leading rows of every image (R register tokens, reg [R][dim], unread when lead == 1): row 0 = cls + pos[0],
 // row 1 + r = reg[r]
 hipError_t launch_lead_rows(float* x, const float* cls, const float* pos, const float* reg, int lead, int batch, int tokens,

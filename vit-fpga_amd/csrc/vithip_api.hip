@@ -233,7 +233,6 @@ struct vh_ctx {
     bool cls_tail = false;    // VH_FLAG_CLS_TAIL: the last layer computes the class-token rows only (folded 16-bit path, head dim 64)
     int head_dim = 64;        // dim / heads: 64 takes launch_attention and its layouts, any other launch_attention_hd (row-major)
     float q_scale = kAttnQScale;   // head_dim^-1/2 * log2(e), folded into Wq and bq (attention_q_scale)
-    bool patch_fused = false; // VH_PATCH_FUSED=1 (read when the context is created): patch gather inside the GEMM's A loader
     void* xlo16 = nullptr;    // [B*T, D] bytes
     // Run-time guard on the fold: the kernels that produce the row statistics keep a running maximum of
     // |mean| * rstd over the REAL rows (guard_dev: the bits of a non-negative float); every forward ends with an
@@ -308,13 +307,8 @@ struct vh_ctx {
     size_t ring_slot_bytes = 0;
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     int ring_batch = 0, ring_wr = 0, ring_rd = 0, ring_used = 0;
-    // tail overlap (enqueue_forward, resid_gemm_ln): helper stream + events, CU count; VH_TAIL_OVERLAP=1 enables
-    hipStream_t tstream = nullptr;
-    hipEvent_t ev_tail_a = nullptr, ev_tail_l = nullptr;
-    bool tail_overlap = false;
     bool last_h_tiled = false;   // debug tap 3
     bool last_qkv_hm = false;    // debug tap 4
-    int tail_splits = 0;   // residual GEMMs of the last forward that were launched as [full rounds] + [tail round] (debug tap 2)
     int num_cu = 256;
     // optional hipGraph replay of the forward's launch sequence (vh_set_graph): one instantiated graph per
     // (input pointer, input kind, logits pointer, batch); a batch size runs eagerly once before it is captured
@@ -501,7 +495,7 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
 // `img0`: first image of this part inside the activation arena (a batch can be split into parts that run on
 // different streams: rows of different images never interact), `s`: the stream to enqueue on.
 int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<std::pair<int, hipEvent_t>>* ev,
-                    hipStream_t s, int img0, bool allow_tail = false, bool may_pad = true) {
+                    hipStream_t s, int img0, bool may_pad = true) {
     const vh_config& f = c->cfg;
     const Layout& L = c->L;
     const int D = f.dim, M = f.mlp_dim, T = L.T;
@@ -583,7 +577,6 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         return mark(st);
     };
     int rc;
-    if (img0 == 0) c->tail_splits = 0;
     if ((rc = mark(-1))) return rc;
     const int nl = (c->run_layers < 0 || c->run_layers > f.layers) ? f.layers : c->run_layers;
     // Layer features: behind fc2 of layer l, when l + 1 is listed and more layers follow, this part's real rows go to the capture
@@ -609,46 +602,36 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         }
         return VH_OK;
     };
-    // Patch embedding with the gather inside the GEMM's A loader (kernels_patch.hip; the split residual of the 16-bit paths):
-    // VH_PATCH_FUSED=1 selects it -- measured, DESIGN.md 4.4 -- the default is the im2col pass + the persistent GEMM.
+    // Patch embedding: the im2col pass + the persistent GEMM.
     // VH_FLAG_PRE_LN: a LayerNorm needs whole rows, which no patch-GEMM tile holds -- such a context embeds through the fp32-x branch
-    // and one pre_layernorm_kernel pass turns x into what its path consumes (no PATCH_SPLIT, no fused patch path, no rowstats pass)
+    // and one pre_layernorm_kernel pass turns x into what its path consumes (no PATCH_SPLIT, no rowstats pass)
     const bool pre_ln = (f.flags & VH_FLAG_PRE_LN) != 0;
     const int epi_fc1 = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_LNFOLD_QGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
     const int epi_fc1_plain = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_BIAS_QGELU : VH_EPI_BIAS_GELU;       // plain layer loop
     // the patch embedding lands directly in the split residual's planes (below): the 16-bit split path without a pre-LayerNorm
     const bool patch_split = c->split && !c->fp8 && nl > 0 && !pre_ln;
-    // 8-bit images and every other tensor kind: always the im2col pass + the ordinary patch GEMM; the fused loader reads NHWC fp32 only
-    // register tokens: the fused loader knows one leading row only, so such a context takes the two-kernel path
-    const bool fused_patch = patch_split && L.R == 0 && in.nhwc_f32() && c->patch_fused && patch_fused_supported(f.image_size, f.patch_size, f.channels, D);
-    if (!fused_patch) {   // (no stage bracket: the profile event is recorded with or without the pass)
-        if ((rc = tmark(ST_IM2COL))) return rc;
-        if (in.layout == VH_LAYOUT_NHWC && in.u8())
-            HIPCHK(&c->err, launch_im2col_u8((const uint8_t*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale, c->in_shift,
-                                             col16, dt16, s));
-        else if (in.nhwc_f32())
-            HIPCHK(&c->err, launch_im2col((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
-        else   // every other (element type, layout): kernels_gather.hip
-            HIPCHK(&c->err, launch_im2col_tensor(in.p, in.kind, in.layout, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale,
-                                                 c->in_shift, col16, dt16, s));
-        if ((rc = tmark(ST_IM2COL))) return rc;
-    }
+    // (no stage bracket: the profile event is recorded once, behind the pass)
+    if ((rc = tmark(ST_IM2COL))) return rc;
+    if (in.layout == VH_LAYOUT_NHWC && in.u8())
+        HIPCHK(&c->err, launch_im2col_u8((const uint8_t*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale, c->in_shift,
+                                         col16, dt16, s));
+    else if (in.nhwc_f32())
+        HIPCHK(&c->err, launch_im2col((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
+    else   // every other (element type, layout): kernels_gather.hip
+        HIPCHK(&c->err, launch_im2col_tensor(in.p, in.kind, in.layout, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale,
+                                             c->in_shift, col16, dt16, s));
+    if ((rc = tmark(ST_IM2COL))) return rc;
     if ((rc = mark(ST_IM2COL))) return rc;
     if (patch_split) {
         // Split residual: the patch embedding lands DIRECTLY in the two 16-bit planes, with the first row statistics'
-        // partial sums (PATCH_SPLIT epilogue or the fused loader's; the class-token rows from their own small kernel) -- no fp32
+        // partial sums (PATCH_SPLIT epilogue; the class-token rows from their own small kernel) -- no fp32
         // x, no separate row-statistics pass over it (round 3: -0.1 ms per forward).  The partial sums are laid out for rows_g
         // rows, like every later layer's.
         GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, P + L.pos, L.NP);
         g.out16 = xlo16;
         g.prow = rows_g;
         g.lead = L.lead;
-        if ((rc = stage(ST_PATCH, [&] {
-                 return fused_patch ? launch_patch_fused((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, c->wp16, P + L.patch_b,
-                                                         P + L.pos, xn16, xlo16, partials_p, rows_g, D, dt16, s)
-                                    : launch_gemm(g, s);
-             })))
-            return rc;
+        if ((rc = stage(ST_PATCH, [&] { return launch_gemm(g, s); }))) return rc;
         if ((rc = stage(ST_CLS, [&] {
                  return launch_lead_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, P + L.reg, L.lead, batch, T, D, dt16, s);
              })))
@@ -771,53 +754,18 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     }
     // ---- the plain layer loop (bf16 / fp16 / fp8 operands) -----------------------------------------------------
     const bool plain = !c->ln_fold;
-    auto ln_rows = [&](int64_t r_begin, int64_t r_count, const float* w, const float* b, hipStream_t st) {
-        return launch_layernorm(x + r_begin * D, r_count, D, D, w, b, f.ln_eps, xn16 + r_begin * D * esz_op, op_dt, st);
-    };
-    // Residual GEMM (x += A W^T + bias) followed by the LayerNorm of the updated rows.  Tail overlap: the tiles of a
-    // 256x256 GEMM fill the 256 CUs in rounds and the last round is partly empty (N = dim = 768: 1182 tiles = 4.6
-    // rounds).  The GEMM is launched as the full rounds (whole M-tiles) and then the tail round; the LayerNorm of
-    // the rows finished by the first launch runs on a helper stream BESIDE the tail round, the rest after it.
-    // Same kernels, same arithmetic, same bits.
+    auto ln_rows = [&](const float* w, const float* b) { return launch_layernorm(x, rows, D, D, w, b, f.ln_eps, xn16, op_dt, s); };
+    // Residual GEMM (x += A W^T + bias) followed by the LayerNorm of the updated rows
     auto resid_gemm_ln = [&](const void* a, const void* w, const float* bias, const float* scale, int K, const float* lnw,
                              const float* lnb, int st_gemm) -> int {
-        const int tiles_n = (D + 255) / 256, ntile = (int)((rows + 255) / 256) * tiles_n;
-        int split = 0;
-        const bool pp = c->fp8 || gemm_pick_variant(rows, D, VH_EPI_BIAS_RESID) >= 5;   // any 256x256 ping-pong form (5, 6, 7)
-        if (allow_tail && c->tail_overlap && lnw && !ev && pp && ntile > c->num_cu && ntile % c->num_cu != 0 &&
-            c->timing_stage != ST_LN && c->timing_stage != ST_PROJ && c->timing_stage != ST_FC2) {
-            split = ntile / c->num_cu * c->num_cu;
-            split -= split % tiles_n;
-        }
         GemmArgs g = gemm_args(op_dt, a, w, bias, x, rows, D, K, VH_EPI_BIAS_RESID);
         g.wscale = scale;
-        int r;
-        if (!split) {
-            if ((r = stage(st_gemm, [&] { return launch_gemm(g, s); }))) return r;
-            return lnw ? stage(ST_LN, [&] { return ln_rows(0, rows, lnw, lnb, s); }) : VH_OK;
-        }
-        // (no stage bracket: one pair of stage-timing events around the whole split sequence and no profile event -- !ev)
-        ++c->tail_splits;
-        const int64_t rows_a = (int64_t)(split / tiles_n) * 256;
-        // a range of tiles exists in the one-tile-per-workgroup forms only: where the default is the persistent form (6), form 5 runs it
-        g.variant = gemm_pp_variant(g.epilogue) == 7 ? 7 : 5;
-        if ((r = tmark(st_gemm))) return r;
-        g.tile_count = split;
-        HIPCHK(&c->err, launch_gemm(g, s));
-        HIPCHK(&c->err, hipEventRecord(c->ev_tail_a, s));
-        g.tile_begin = split;
-        g.tile_count = ntile - split;
-        HIPCHK(&c->err, launch_gemm(g, s));
-        HIPCHK(&c->err, hipStreamWaitEvent(c->tstream, c->ev_tail_a, 0));
-        HIPCHK(&c->err, ln_rows(0, rows_a, lnw, lnb, c->tstream));
-        HIPCHK(&c->err, hipEventRecord(c->ev_tail_l, c->tstream));
-        HIPCHK(&c->err, ln_rows(rows_a, rows - rows_a, lnw, lnb, s));
-        HIPCHK(&c->err, hipStreamWaitEvent(s, c->ev_tail_l, 0));
-        return tmark(st_gemm);
+        if (int r = stage(st_gemm, [&] { return launch_gemm(g, s); })) return r;
+        return lnw ? stage(ST_LN, [&] { return ln_rows(lnw, lnb); }) : VH_OK;
     };
     if (plain && nl > 0) {
         const LayerOff& o0 = L.layer[0];
-        if ((rc = stage(ST_LN, [&] { return ln_rows(0, rows, P + o0.ln1w, P + o0.ln1b, s); }))) return rc;
+        if ((rc = stage(ST_LN, [&] { return ln_rows(P + o0.ln1w, P + o0.ln1b); }))) return rc;
     }
     for (int l = 0; l < nl && plain; ++l) {
         const LayerOff& o = L.layer[l];
@@ -892,7 +840,7 @@ int enqueue_step(vh_ctx* c, ImgIn in, int batch, float* logits) {
             const int nb = batch / parts + (p < batch % parts ? 1 : 0);
             hipStream_t st = p == 0 ? c->stream : c->xstream[p - 1];
             if (p) HIPCHK(&c->err, hipStreamWaitEvent(st, c->ev_fork, 0));
-            if ((rc = enqueue_forward(c, in.skip((size_t)b0 * img_elems), nb, logits + (size_t)b0 * c->cfg.classes, nullptr, st, b0, false,
+            if ((rc = enqueue_forward(c, in.skip((size_t)b0 * img_elems), nb, logits + (size_t)b0 * c->cfg.classes, nullptr, st, b0,
                                       /*may_pad: only the last part has nothing behind its rows*/ p == parts - 1))) return rc;
             if (p) {
                 HIPCHK(&c->err, hipEventRecord(c->ev_join[p - 1], st));
@@ -903,7 +851,7 @@ int enqueue_step(vh_ctx* c, ImgIn in, int batch, float* logits) {
         c->last_batch = batch;
         return guard_publish(c);
     }
-    if ((rc = enqueue_forward(c, in, batch, logits, nullptr, c->stream, 0, true))) return rc;
+    if ((rc = enqueue_forward(c, in, batch, logits, nullptr, c->stream, 0))) return rc;
     return guard_publish(c);
 }
 
@@ -1309,16 +1257,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         if (c->nstreams < 1) c->nstreams = 1;
         if (c->nstreams > vh_ctx::kMaxStreams) c->nstreams = vh_ctx::kMaxStreams;
     }
-    CK(hipStreamCreateWithFlags(&c->tstream, hipStreamNonBlocking));
-    CK(hipEventCreateWithFlags(&c->ev_tail_a, hipEventDisableTiming));
-    CK(hipEventCreateWithFlags(&c->ev_tail_l, hipEventDisableTiming));
     c->num_cu = prop.multiProcessorCount;
-    {
-        // opt-in: measured +-0.5 % on ViT-B/16 b512 (the forward is power-capped: filling idle CUs moves energy around
-        // instead of saving it), so the simpler single-launch sequence stays the default
-        const char* e = getenv("VH_TAIL_OVERLAP");
-        c->tail_overlap = e && e[0] == '1';
-    }
     {
         const char* e = getenv("VH_GRAPH");
         c->use_graph = e && e[0] == '1';
@@ -1379,8 +1318,6 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         c->h_tiled = want_tiled || want_tiled8;
         { const char* e = getenv("VH_ATT_TILED"); c->att_tiled = !(e && e[0] == '0'); }
         { const char* e = getenv("VH_QKV_HM"); c->qkv_hm = !(e && e[0] == '0'); }
-        const char* pf = getenv("VH_PATCH_FUSED");
-        c->patch_fused = pf && pf[0] == '1';
     }
     CK(hipHostMalloc((void**)&c->guard_host, 64, hipHostMallocDefault));
     *c->guard_host = 0.f;
@@ -1451,9 +1388,6 @@ int vh_destroy(vh_ctx* c) {
         if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]);
     }
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->tstream) { hipStreamSynchronize(c->tstream); hipStreamDestroy(c->tstream); }
-    if (c->ev_tail_a) hipEventDestroy(c->ev_tail_a);
-    if (c->ev_tail_l) hipEventDestroy(c->ev_tail_l);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return VH_OK;
@@ -2311,11 +2245,6 @@ int vh_debug_read(vh_ctx* c, int what, float* host_out, size_t n_floats) {
         const size_t n = (size_t)c->last_batch * D;
         if (n_floats != n) return fail(&c->err, VH_ERR_INVALID, "expected %zu floats", n);
         HIPCHK(&c->err, hipMemcpy(host_out, c->clsn32, n * 4, hipMemcpyDeviceToHost));
-        return VH_OK;
-    }
-    if (what == 2) {   // how many residual GEMMs of the last forward ran as a split launch (VH_TAIL_OVERLAP)
-        if (n_floats != 1) return fail(&c->err, VH_ERR_INVALID, "expected 1 float");
-        host_out[0] = (float)c->tail_splits;
         return VH_OK;
     }
     if (what == 3) {   // 1 when the last forward kept the MLP hidden activation in its tiled layout (h_tiled)
