@@ -154,6 +154,36 @@ typedef struct vh_config {
 #define VH_FLAG_REGISTERS_OF(flags) (((flags) & VH_FLAG_REGISTERS_MASK) >> 9)
 #define VH_MAX_REGISTERS 16
 
+/* Pooled heads and models without a class token (I-JEPA, DINOv2's ImageNet linear classifiers, timm's global_pool='avg', BEiT's
+ * pooler).  Two MODEL switches, in bits 15 .. 17 of flags and, with the same values, of the blob header's flags word; a blob whose
+ * bits differ from the context's is refused.  With both clear nothing changes: every kernel gets the arguments it got before.
+ *   VH_FLAG_POOL(m): what the head multiplies, [batch][W] fp32 (vh_debug_read(ctx, 1)); p runs over the NP patch rows ONLY, never
+ *   over the class token or the register rows; the LayerNorm is the blob's lnf.* in every mode.
+ *     VH_POOL_CLS         head(LN(row 0))                                W = D   (the default)
+ *     VH_POOL_AVG_NORM    head(mean_p LN(x_p))                           W = D   I-JEPA; timm global_pool='avg' with fc_norm=False
+ *     VH_POOL_AVG_FCNORM  head(LN(mean_p x_p))                           W = D   timm global_pool='avg' + fc_norm, BEiT's pooler
+ *     VH_POOL_CLS_AVG     head(concat(LN(row 0), mean_p LN(x_p)))        W = 2 D head.weight [C][2 D], class-token half first
+ *   ARITHMETIC, for bits ("Token features" below): the AVG_NORM vector is what vh_read_features(mean, VH_FEAT_NORM, VH_ELEM_F32)
+ *   returns after the same forward -- the two-pass fp32 row statistics, fmaf((x - mean) * rstd, gamma, beta), the serial fp32 chain
+ *   over the patch rows ascending, times (float)(1.0 / NP).  AVG_FCNORM: the VH_FEAT_RAW mean of the same definition, then the fp32
+ *   LayerNorm of vh_op_layernorm_f32 over [batch][D].  CLS_AVG: columns 0 .. D - 1 are the vector VH_POOL_CLS computes (the same
+ *   launch), columns D .. 2 D - 1 the AVG_NORM vector.  logits = the fp32 head over W columns.  The result never depends on the
+ *   batch, the launch geometry or the stream part an image runs in.
+ *   VH_FLAG_NO_CLS: the model has no class token.  tokens T = NP + R; the blob has no `cls` tensor and `pos` is [NP][D]; row order
+ *   reg[0 .. R - 1], then patch p + pos[p] (the bits of the class-token context's patch rows for the same tensors).  The pooling
+ *   mode must be VH_POOL_AVG_NORM or VH_POOL_AVG_FCNORM.
+ *   Refused by vh_create / vh_weight_blob_bytes, each with a message of its own: VH_FLAG_NO_CLS with VH_POOL_CLS or VH_POOL_CLS_AVG;
+ *   VH_FLAG_CLS_TAIL with either switch (its last layer does not update the patch rows).  The token bounds apply to the new T.
+ *   vh_init_weights_seeded keeps every tensor id; `head` is id "head" with its [C][W] shape. */
+#define VH_FLAG_NO_CLS (1 << 15)
+#define VH_FLAG_POOL(m) (((m) & 3) << 16)
+#define VH_FLAG_POOL_MASK (3 << 16)
+#define VH_FLAG_POOL_OF(flags) (((flags) & VH_FLAG_POOL_MASK) >> 16)
+#define VH_POOL_CLS 0
+#define VH_POOL_AVG_NORM 1
+#define VH_POOL_AVG_FCNORM 2
+#define VH_POOL_CLS_AVG 3
+
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
 
@@ -194,7 +224,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -718,7 +748,8 @@ int vh_get_step_timing(vh_ctx* ctx, double* step_ms, int max_steps, int* steps);
 
 /* debug taps: copy an internal activation of the LAST forward to the host as fp32.
  * what: 0 = residual stream x [batch*T, D] after the last layer run,
- *       1 = final-LN'd CLS rows [batch, D],
+ *       1 = the head's input [batch, W]: the final-LN'd CLS rows (W = D), or what the context's VH_FLAG_POOL mode computes
+ *           (W = D; 2 D for VH_POOL_CLS_AVG),
  *       (2 is unused: VH_ERR_INVALID, like any other value not listed here,)
  *       3 = one float: 1 when the last forward kept the MLP hidden activation in its tiled (16-row-blocked) layout -- the
  *           default wherever both MLP GEMMs take the persistent form (16-bit folded path, whole 256-row tiles; VH_H_TILED=0 at
@@ -772,7 +803,13 @@ int vh_debug_set_layers(vh_ctx* ctx, int n_layers);
  * not 16-byte aligned.  VH_ERR_STATE: no forward has run; a ring exists on the context (its forwards belong to slots).
  * VH_ERR_UNSUPPORTED: a VH_FLAG_CLS_TAIL context (its last layer does not update the other rows).
  *
- *   vh_features_dims               any of the four may be NULL; *batch = 0 before the first forward
+ * POOLED AND CLASS-TOKEN-FREE CONTEXTS (VH_FLAG_POOL, VH_FLAG_NO_CLS).  On a VH_FLAG_NO_CLS context tokens = NP + R, patch[b][p] <- row
+ * b * tokens + R + p, mean over those rows, reg <- rows 0 .. R - 1; a non-NULL cls is refused (VH_ERR_UNSUPPORTED, nothing enqueued).
+ * On a pooled context WITH a class token cls stays LN(row 0) (RAW: row 0): the head's input no longer is that vector, so the
+ * feature kernels compute it with the arithmetic above.
+ *
+ *   vh_features_dims               any of the four may be NULL; *batch = 0 before the first forward; *tokens = NP + 1 + R, or NP + R
+ *                                  on a VH_FLAG_NO_CLS context; *patches = NP
  *   vh_read_features               host buffers; synchronous
  *   vh_read_features_device        device buffers; enqueues on the context's stream and waits
  *   vh_read_features_device_async  device buffers; enqueues only (vh_synchronize, or stream order with a following call) */
@@ -934,7 +971,10 @@ int vh_op_gemm_layout(const void* a16_dev, const void* w16_dev, const float* bia
  *   vh_op_lead_rows  the kernels that write the `lead` leading rows of every image: row 0 = cls + pos[0], row 1 + r = reg[r].
  *                    lo_dev NULL: fp32 rows x_or_hi_dev [batch * tokens][dim] (partials_dev, prow, dtype unused); otherwise the
  *                    split planes (hi 16-bit of `dtype`, lo one scaled e4m3 byte) and the rows' per-64-column (sum, sum of
- *                    squares) in partials_dev [dim/64][prow][2], prow >= batch * tokens.  dim % 64 == 0, lead < tokens. */
+ *                    squares) in partials_dev [dim/64][prow][2], prow >= batch * tokens.  dim % 64 == 0, lead < tokens.
+ *                    cls_dev and pos_dev both NULL: the form of a VH_FLAG_NO_CLS context, whose `lead` rows (1 .. 16) are all
+ *                    register rows, row r = reg[r].  (vh_op_gemm_lead takes lead = 0 .. 17: with no row in front of the patch rows
+ *                    such a context hands the epilogue its [NP][D] position table one row early.) */
 int vh_op_gemm_lead(const void* a16_dev, const void* w16_dev, const float* bias_dev, void* out_dev, int64_t M, int N, int K,
                     int epilogue, const float* aux_dev, int aux_i, int lead, void* out16_dev, float* partials_dev, int64_t prow,
                     int dtype, int variant, void* stream);
@@ -1123,6 +1163,15 @@ int vh_op_token_features(const void* hi_or_x32_dev, const void* lo_dev, int form
 int vh_op_token_features2(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int lead, int dim,
                           const float* gamma_dev, const float* beta_dev, float eps, int elem, int norm, void* patch_out_dev,
                           int patch_layout, void* mean_out_dev, void* reg_out_dev, void* stream);
+/* The pooling kernel of the VH_FLAG_POOL modes on its own: mean_out_dev [batch][dim] fp32 <- the mean over rows lead .. tokens - 1
+ * of every image, of the rows as they are (VH_FEAT_RAW) or through LayerNorm(gamma_dev, beta_dev, eps) (VH_FEAT_NORM), with the
+ * arithmetic of "Token features": the bits vh_op_token_features2 writes into mean_out_dev for VH_ELEM_F32.  ONE pass over the rows
+ * (one workgroup per image; a wave keeps a row in registers, the rows of a group meet in LDS and are added in ascending token order).
+ * form / hi / lo as vh_op_token_features; lead 0 .. tokens - 1 (0: every row is a patch row, VH_FLAG_NO_CLS without registers),
+ * tokens 1 .. 4097, dim % 8 == 0, 64 <= dim <= 2048, every pointer 16-byte aligned.  Every argument is checked before a device is
+ * touched, each refusal with a message of its own. */
+int vh_op_pool_rows(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int lead, int dim,
+                    const float* gamma_dev, const float* beta_dev, float eps, int norm, float* mean_out_dev, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,
  * 2 = constant `sigma` */
 int vh_op_fill(float* out_dev, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,

@@ -12,6 +12,8 @@
 //                      wrote, so the value it adds is, bit for bit, the fp32 value the row kernel converted and stored.
 //   feat_nchw_kernel   the patch rows channels-first ([batch][dim][np]): 32 tokens of one image per workgroup, each row through the
 //                      row kernel's own three steps (row_load, row_stats, piece_norm), transposed through LDS.
+//   pool_rows_kernel   the same mean in ONE pass over the planes, inside the forward of a VH_FLAG_POOL context: one workgroup per
+//                      image, a row per wave through the row kernel's steps, the rows of a group added from LDS in token order.
 //   feat_capture_kernel  the copy of a tapped layer's rows into the capture store ("Layer features"), both planes in one launch.
 // (The normalised class-token rows of the final state are the ones the head multiplied: a conversion copy of clsn32, made by launch_cast.)
 //
@@ -156,10 +158,11 @@ __device__ __forceinline__ void piece_norm(float (&p)[8], int c, float mean, flo
 // rows = batch * tokens.  Row r = image r / tokens, token r % tokens: token 0 goes to cls_out [batch][dim], tokens 1 .. lead - 1
 // (register tokens) to reg_out [batch][lead - 1][dim], token t >= lead to patch_out [batch][tokens - lead][dim]; any may be null.
 // norm != 0: the row passes LayerNorm(gamma, beta, eps), and stats (optional) receives (mean, rstd) of every patch row.  A wave
-// whose row has nothing to write leaves at once.
+// whose row has nothing to write leaves at once.  ncls = 1; 0 for the rows of a context without a class token (FeatureArgs::no_cls):
+// tokens 0 .. lead - 1 are then all register rows, reg_out [batch][lead][dim], and lead may be 0.
 template <typename IN, typename OUT, int CH>   // CH = pieces of 8 elements per lane (dim <= 512 * CH)
 __global__ void __launch_bounds__(256)
-feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t rows, int tokens, int lead, int dim,
+feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64_t rows, int tokens, int lead, int ncls, int dim,
                  const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int norm,
                  typename OUT::elem* __restrict__ cls_out, typename OUT::elem* __restrict__ reg_out,
                  typename OUT::elem* __restrict__ patch_out, float* __restrict__ stats) {
@@ -169,8 +172,8 @@ feat_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int64
     const int64_t img = row / tokens;
     const int t = (int)(row - img * tokens);
     typename OUT::elem* out = nullptr;
-    if (t == 0) { if (cls_out) out = cls_out + img * dim; }
-    else if (t < lead) { if (reg_out) out = reg_out + (img * (lead - 1) + (t - 1)) * dim; }
+    if (t < ncls) { if (cls_out) out = cls_out + img * dim; }
+    else if (t < lead) { if (reg_out) out = reg_out + (img * (lead - ncls) + (t - ncls)) * dim; }
     else if (patch_out) out = patch_out + (img * (tokens - lead) + (t - lead)) * dim;
     const bool want_stats = norm && stats && t >= lead;
     if (!out && !want_stats) return;   // wave-uniform
@@ -343,8 +346,8 @@ hipError_t feat_launch(const FeatureArgs& a, hipStream_t s) {
     if (a.cls || a.reg || patch_rows || stats_rows) {   // (a raw mean needs no row pass: nothing to normalise, no statistics)
         const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
         float* st = stats_rows ? a.stats : nullptr;
-#define VH_FEAT_ROWS_L(CH) hipLaunchKernelGGL((feat_rows_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, rows, a.tokens, a.lead, a.dim, \
-                                              a.gamma, a.beta, a.eps, norm, (E*)a.cls, (E*)a.reg, (E*)patch_rows, st)
+#define VH_FEAT_ROWS_L(CH) hipLaunchKernelGGL((feat_rows_kernel<IN, OUT, CH>), grid, block, 0, s, a.hi, a.lo, rows, a.tokens, a.lead, \
+                                              a.no_cls ? 0 : 1, a.dim, a.gamma, a.beta, a.eps, norm, (E*)a.cls, (E*)a.reg, (E*)patch_rows, st)
         if (a.dim <= 512) VH_FEAT_ROWS_L(1);
         else if (a.dim <= 1024) VH_FEAT_ROWS_L(2);
         else if (a.dim <= 1536) VH_FEAT_ROWS_L(3);
@@ -371,7 +374,131 @@ hipError_t feat_launch_in(const FeatureArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
+// ---- the pooled head's input (VH_FLAG_POOL; vithip.h): the mean over an image's patch rows in ONE pass over the planes ----------
+// out[b][k] = (((0 + v[b,lead,k]) + v[b,lead+1,k]) + ... + v[b,tokens-1,k]) * inv: the bits feat_rows_kernel + feat_mean_kernel give,
+// because a row goes through the same row_load / row_stats / piece_norm and a column's chain is the same serial fp32 adds in
+// ascending token order.  One workgroup (16 waves) per image.  A group = `group` consecutive patch rows (min(16, 16384 / dim):
+// 64 KiB of LDS at most, two workgroups per CU): wave w < group takes row w of the group, keeps it in registers, normalises it and
+// parks the fp32 row in LDS; then thread t, which owns columns t and t + 1024, adds the group's values of its columns in row
+// order.  Nothing depends on the batch, on `group` or on which workgroup an image gets.  cls_in (optional, VH_POOL_CLS_AVG):
+// cls_out[b][0 .. dim) <- cls_in[b][0 .. dim).  One workgroup per image: a small batch of long sequences pools on few CUs.
+constexpr int kPoolWaves = 16, kPoolLdsFloats = 16384;
+template <typename IN, int CH>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(CH <= 2 ? 8 : 4)))   // dim <= 1024: 64 VGPRs, two workgroups per CU
+pool_rows_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int tokens, int lead, int dim, const float* __restrict__ gamma,
+                 const float* __restrict__ beta, float eps, int norm, int group, float inv, float* __restrict__ out, int64_t out_stride,
+                 const float* __restrict__ cls_in, float* __restrict__ cls_out) {
+    __shared__ __attribute__((aligned(16))) float park[kPoolLdsFloats];   // [group][dim]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int np = tokens - lead, npiece = dim >> 3;
+    const int64_t img = blockIdx.x;
+    const int64_t row0 = img * tokens + lead;
+    const bool loader = wave < group;   // wave-uniform
+    float acc[2] = {0.f, 0.f};
+    // CH == 1: the next group's row is loaded before the barrier (with the second register copy of the row 50 - 52 VGPRs, profiles/pool_isa.txt).  Wider rows
+    // load at the top of their group: two workgroups per CU hide each other's latency instead, which the second copy would forbid.
+    constexpr bool AHEAD = CH == 1;
+    float v[CH][8], vn[AHEAD ? CH : 1][8];
+    if (AHEAD && loader && wave < np) row_load<IN, CH>(hi, lo, row0 + wave, dim, lane, v);
+    for (int p0 = 0; p0 < np; p0 += group) {
+        const int p = p0 + wave;
+        const bool next = AHEAD && loader && p + group < np;
+        if constexpr (AHEAD) {
+            if (next) row_load<IN, CH>(hi, lo, row0 + p + group, dim, lane, vn);
+        } else {
+            if (loader && p < np) row_load<IN, CH>(hi, lo, row0 + p, dim, lane, v);
+        }
+        if (loader && p < np) {
+            float mean = 0.f, rstd = 1.f;
+            if (norm) row_stats<CH>(v, dim, lane, eps, mean, rstd);
+            float* const w = park + wave * dim;
+#pragma unroll
+            for (int i = 0; i < CH; ++i) {
+                const int c = lane + 64 * i;
+                if (c < npiece) {
+                    if (norm) piece_norm(v[i], c, mean, rstd, gamma, beta);
+                    ((f32x4*)(w + 8 * c))[0] = f32x4{v[i][0], v[i][1], v[i][2], v[i][3]};
+                    ((f32x4*)(w + 8 * c))[1] = f32x4{v[i][4], v[i][5], v[i][6], v[i][7]};
+                }
+            }
+        }
+        __syncthreads();
+        const int n = np - p0 < group ? np - p0 : group;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = threadIdx.x + 1024 * j;
+            if (col < dim)
+                for (int g = 0; g < n; ++g) acc[j] += park[g * dim + col];
+        }
+        __syncthreads();   // the group has been added: its LDS rows are free
+        if constexpr (AHEAD) {
+            if (next) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[0][j] = vn[0][j];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = threadIdx.x + 1024 * j;
+        if (col < dim) {
+            out[img * out_stride + col] = acc[j] * inv;
+            if (cls_in) cls_out[img * out_stride + col] = cls_in[img * dim + col];
+        }
+    }
+}
+
+template <typename IN>
+hipError_t pool_launch(const PoolArgs& a, hipStream_t s) {
+    const int norm = a.norm == VH_FEAT_NORM ? 1 : 0;
+    const int group = kPoolLdsFloats / a.dim < kPoolWaves ? kPoolLdsFloats / a.dim : kPoolWaves;
+    const float inv = (float)(1.0 / (double)(a.tokens - a.lead));
+    const int64_t stride = a.out_stride ? a.out_stride : a.dim;
+#define VH_POOL_L(CH) hipLaunchKernelGGL((pool_rows_kernel<IN, CH>), dim3((unsigned)a.batch), dim3(1024), 0, s, a.hi, a.lo, a.tokens, a.lead, a.dim, \
+                                         a.gamma, a.beta, a.eps, norm, group, inv, a.out, stride, a.cls_in, a.cls_out)
+    if (a.dim <= 512) VH_POOL_L(1);
+    else if (a.dim <= 1024) VH_POOL_L(2);
+    else if (a.dim <= 1536) VH_POOL_L(3);
+    else VH_POOL_L(4);
+#undef VH_POOL_L
+    return hipGetLastError();
+}
+
 }  // namespace
+
+const char* pool_check(const PoolArgs& a) {
+    if (!a.hi) return "pool_rows: null input";
+    if (a.form != VH_FEAT_FORM_F32 && a.form != VH_DTYPE_BF16 && a.form != VH_DTYPE_FP16 && a.form != VH_DTYPE_FP8)
+        return "pool_rows: form must be VH_DTYPE_BF16, VH_DTYPE_FP16, VH_DTYPE_FP8 (split planes) or -1 (fp32 rows)";
+    if (a.form == VH_FEAT_FORM_F32 && a.lo) return "pool_rows: fp32 rows take no lo plane";
+    if (a.form != VH_FEAT_FORM_F32 && !a.lo) return "pool_rows: split planes need the lo plane";
+    if (a.batch <= 0 || a.batch > (1 << 20)) return "pool_rows: batch outside 1..2^20";
+    if (a.tokens < 1) return "pool_rows: tokens below 1 (no patch token)";
+    if (a.tokens > kAttnStreamMaxTokens) return "pool_rows: tokens above 4097";
+    if (a.lead < 0 || a.lead >= a.tokens) return "pool_rows: lead rows outside 0 .. tokens - 1";
+    if (a.dim < 64) return "pool_rows: dim below 64";
+    if (a.dim > 2048) return "pool_rows: dim above 2048";
+    if (a.dim % 8) return "pool_rows: dim must be a multiple of 8";
+    if (!a.out) return "pool_rows: null output";
+    if (a.norm != VH_FEAT_NORM && a.norm != VH_FEAT_RAW) return "pool_rows: norm must be VH_FEAT_NORM or VH_FEAT_RAW";
+    if (a.norm == VH_FEAT_NORM) {
+        if (!a.gamma || !a.beta) return "pool_rows: VH_FEAT_NORM needs gamma and beta";
+        if (!(a.eps > 0.f)) return "pool_rows: eps must be positive";
+    }
+    if (a.out_stride && a.out_stride < a.dim) return "pool_rows: the output's row stride is below dim";
+    if ((a.cls_in != nullptr) != (a.cls_out != nullptr)) return "pool_rows: cls_in and cls_out go together";
+    const uintptr_t al = (uintptr_t)a.hi | (uintptr_t)a.lo | (uintptr_t)a.gamma | (uintptr_t)a.beta | (uintptr_t)a.out | (uintptr_t)a.cls_in |
+                         (uintptr_t)a.cls_out;
+    if (al & 15) return "pool_rows: a device pointer is not 16-byte aligned";
+    return nullptr;
+}
+
+hipError_t launch_pool_rows(const PoolArgs& a, hipStream_t s) {
+    if (pool_check(a)) return hipErrorInvalidValue;
+    if (a.form == VH_FEAT_FORM_F32) return pool_launch<InF32>(a, s);
+    if (a.form == VH_DTYPE_FP8) return pool_launch<InSplit8>(a, s);
+    return a.form == VH_DTYPE_BF16 ? pool_launch<InSplit16<BF16>>(a, s) : pool_launch<InSplit16<FP16>>(a, s);
+}
 
 const char* features_check(const FeatureArgs& a) {
     if (!a.hi) return "token_features: null input";
@@ -380,14 +507,21 @@ const char* features_check(const FeatureArgs& a) {
     if (a.form == VH_FEAT_FORM_F32 && a.lo) return "token_features: fp32 rows take no lo plane";
     if (a.form != VH_FEAT_FORM_F32 && !a.lo) return "token_features: split planes need the lo plane";
     if (a.batch <= 0 || a.batch > (1 << 20)) return "token_features: batch outside 1..2^20";
-    if (a.tokens < 2) return "token_features: tokens below 2 (no patch token)";
-    if (a.lead < 1 || a.lead >= a.tokens) return "token_features: lead rows outside 1 .. tokens - 1";
+    if (a.no_cls) {   // internal launches of a VH_FLAG_NO_CLS context only: no public tap sets it
+        if (a.tokens < 1) return "token_features: tokens below 1 (no patch token)";
+        if (a.lead < 0 || a.lead >= a.tokens) return "token_features: lead rows outside 0 .. tokens - 1";
+        if (a.cls) return "token_features: class-token rows requested where there is no class token";
+    } else {
+        if (a.tokens < 2) return "token_features: tokens below 2 (no patch token)";
+        if (a.lead < 1 || a.lead >= a.tokens) return "token_features: lead rows outside 1 .. tokens - 1";
+    }
     if (a.tokens > kAttnStreamMaxTokens) return "token_features: tokens above 4097";
     if (a.dim < 64) return "token_features: dim below 64";
     if (a.dim > 2048) return "token_features: dim above 2048";
     if (a.dim % 8) return "token_features: dim must be a multiple of 8";
     if (!a.cls && !a.patch && !a.mean && !a.reg) return "token_features: no output requested";
-    if (a.reg && a.lead < 2) return "token_features: register rows requested where lead is 1 (no register rows)";
+    if (a.reg && a.no_cls && a.lead < 1) return "token_features: register rows requested where lead is 0 (no register rows)";
+    if (a.reg && !a.no_cls && a.lead < 2) return "token_features: register rows requested where lead is 1 (no register rows)";
     if (a.patch_layout != VH_FEAT_ROWS && a.patch_layout != VH_FEAT_NCHW) return "token_features: patch_layout must be VH_FEAT_ROWS or VH_FEAT_NCHW";
     if (a.elem != VH_ELEM_F32 && a.elem != VH_ELEM_F16 && a.elem != VH_ELEM_BF16)
         return "token_features: elem must be VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16";

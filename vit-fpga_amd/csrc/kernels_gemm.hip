@@ -233,7 +233,7 @@ const char* gemm_check(const GemmArgs& g) {
         if (fold && (!g.stats || !g.aux)) return "gemm: LNFOLD needs stats and c (aux)";
         if (resid && (!g.out16 || !g.partials || g.N % 256)) return "gemm: RESID_LN / RESID_SPLIT need out16, partials and N % 256 == 0";
         if (epi == VH_EPI_PATCH && (!g.aux || g.aux_i <= 0)) return "gemm: EPI_PATCH needs pos-emb and patches/image";
-        if ((epi == VH_EPI_PATCH || epi == VH_EPI_PATCH_SPLIT) && (g.lead < 1 || g.lead > 1 + VH_MAX_REGISTERS)) return "gemm: EPI_PATCH* lead rows outside 1..17";
+        if ((epi == VH_EPI_PATCH || epi == VH_EPI_PATCH_SPLIT) && (g.lead < 0 || g.lead > 1 + VH_MAX_REGISTERS)) return "gemm: EPI_PATCH* lead rows outside 0..17";
         if (epi == VH_EPI_PATCH_SPLIT && (!g.aux || g.aux_i <= 0 || !g.out16 || !g.partials || g.N % 256 || g.prow < 0))
             return "gemm: EPI_PATCH_SPLIT needs pos-emb, patches/image, the lo plane, partials and N % 256 == 0";
         if (g.dtype != VH_DTYPE_BF16 && g.dtype != VH_DTYPE_FP16) return "gemm: dtype";

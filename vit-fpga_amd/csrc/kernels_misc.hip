@@ -163,7 +163,9 @@ hipError_t launch_im2col_u8(const uint8_t* in, int batch, int image, int patch, 
 }
 
 // ---- the leading rows of every image: x[b, 0, :] = cls + pos[0], x[b, 1 + r, :] = reg[r] (register tokens) ----
-// lead = 1 + R rows per image; reg is not read when lead == 1
+// lead = NCLS + R rows per image; reg is not read when lead == NCLS.  NCLS = 0 (VH_FLAG_NO_CLS): every leading row is a register
+// row, cls and pos are not read
+template <int NCLS>
 __global__ void lead_rows_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
                                  const float* __restrict__ reg, int lead, int batch, int tokens, int dim) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -171,20 +173,26 @@ __global__ void lead_rows_kernel(float* __restrict__ x, const float* __restrict_
     if (i >= (int64_t)batch * per) return;
     const int b = (int)(i / per);
     const int e = (int)(i - (int64_t)b * per);   // row j = e / dim of the image, column e % dim: the rows are contiguous
-    x[(int64_t)b * tokens * dim + e] = e < dim ? cls[e] + pos[e] : reg[e - dim];
+    if constexpr (NCLS) x[(int64_t)b * tokens * dim + e] = e < dim ? cls[e] + pos[e] : reg[e - dim];
+    else x[(int64_t)b * tokens * dim + e] = reg[e];
 }
 hipError_t launch_lead_rows(float* x, const float* cls, const float* pos, const float* reg, int lead, int batch, int tokens, int dim,
                             hipStream_t s) {
-    if (batch <= 0 || lead < 1 || lead > tokens || (lead > 1 && !reg)) return hipErrorInvalidValue;
+    const int ncls = cls ? 1 : 0;
+    if (batch <= 0 || lead < ncls || lead >= tokens + ncls || (lead > ncls && !reg) || (cls && !pos)) return hipErrorInvalidValue;
+    if (lead == 0) return hipSuccess;   // no class token, no register: the patch rows are the whole image
     const int64_t n = (int64_t)batch * lead * dim;
-    hipLaunchKernelGGL(lead_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, cls, pos, reg, lead, batch, tokens, dim);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (cls) hipLaunchKernelGGL(lead_rows_kernel<1>, grid, dim3(256), 0, s, x, cls, pos, reg, lead, batch, tokens, dim);
+    else hipLaunchKernelGGL(lead_rows_kernel<0>, grid, dim3(256), 0, s, x, cls, pos, reg, lead, batch, tokens, dim);
     return hipGetLastError();
 }
 
 // the same rows for the SPLIT residual (PATCH_SPLIT path): planes hi = T(x), lo = lo8(x - hi) of x = cls + pos[0] or reg[r], and
 // the row's (sum, sum of squares) per 64-column block -- what the patch GEMM's epilogue writes for every other row.  One wave
 // per (image, leading row); a lane owns column 64 * blk + lane of every block; fixed-order butterfly sums.
-template <typename T>
+// NCLS = 0 (VH_FLAG_NO_CLS): every leading row is a register row (row j = reg[j]), cls and pos are not read.
+template <typename T, int NCLS>
 __global__ void __launch_bounds__(256)
 lead_rows_split_kernel(typename T::elem* __restrict__ hi, uint8_t* __restrict__ lo, float* __restrict__ partials, int64_t prow,
                        const float* __restrict__ cls, const float* __restrict__ pos, const float* __restrict__ reg, int lead,
@@ -194,12 +202,13 @@ lead_rows_split_kernel(typename T::elem* __restrict__ hi, uint8_t* __restrict__ 
     const int b = w / lead, j = w - b * lead;
     if (b >= batch) return;
     const int64_t row = (int64_t)b * tokens + j;
-    const float* const src = j ? reg + (int64_t)(j - 1) * dim : cls;
+    const bool is_reg = NCLS == 0 || j != 0;
+    const float* const src = is_reg ? reg + (int64_t)(j - NCLS) * dim : cls;
     for (int blk = 0; blk * 64 < dim; ++blk) {
         const int d = blk * 64 + lane;
         float v = 0.f;
         if (d < dim) {
-            v = j ? src[d] : src[d] + pos[d];
+            v = is_reg ? src[d] : src[d] + pos[d];
             const typename T::elem h = (typename T::elem)v;
             hi[row * dim + d] = h;
             lo[row * dim + d] = lo8_pack1<T>(v - (float)h);
@@ -210,11 +219,15 @@ lead_rows_split_kernel(typename T::elem* __restrict__ hi, uint8_t* __restrict__ 
 }
 hipError_t launch_lead_rows_split(void* hi, void* lo, float* partials, int64_t prow, const float* cls, const float* pos, const float* reg,
                                   int lead, int batch, int tokens, int dim, int dtype, hipStream_t s) {
-    if (batch <= 0 || dim % 64 || lead < 1 || lead > tokens || (lead > 1 && !reg) || prow < (int64_t)batch * tokens) return hipErrorInvalidValue;
+    const int ncls = cls ? 1 : 0;
+    if (batch <= 0 || dim % 64 || lead < ncls || lead >= tokens + ncls || (lead > ncls && !reg) || (cls && !pos) || prow < (int64_t)batch * tokens)
+        return hipErrorInvalidValue;
+    if (lead == 0) return hipSuccess;   // no class token, no register: the patch rows are the whole image
     const dim3 grid((unsigned)(((int64_t)batch * lead + 3) / 4));
     return dispatch_dtype<BF16, FP16>(dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL(lead_rows_split_kernel<T>, grid, dim3(256), 0, s, (typename T::elem*)hi, (uint8_t*)lo, partials, prow, cls, pos, reg, lead, batch, tokens, dim);
+        if (cls) hipLaunchKernelGGL((lead_rows_split_kernel<T, 1>), grid, dim3(256), 0, s, (typename T::elem*)hi, (uint8_t*)lo, partials, prow, cls, pos, reg, lead, batch, tokens, dim);
+        else hipLaunchKernelGGL((lead_rows_split_kernel<T, 0>), grid, dim3(256), 0, s, (typename T::elem*)hi, (uint8_t*)lo, partials, prow, cls, pos, reg, lead, batch, tokens, dim);
         return hipGetLastError();
     });
 }

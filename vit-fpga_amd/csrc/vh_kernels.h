@@ -175,7 +175,8 @@ const char* resize_plan_build_bgra(const vh_frame_bgra* desc, int batch, int S, 
 hipError_t launch_resize_bgra(bool wide, const uint8_t* frames, const uint32_t* plan_dev, int batch, int S, int max_tiles,
                               const float* m12_host, uint8_t* out_u8, hipStream_t stream);
 // the `lead` = 1 + R leading rows of every image (R register tokens, reg [R][dim], unread when lead == 1): row 0 = cls + pos[0],
-// row 1 + r = reg[r]
+// row 1 + r = reg[r].  cls == nullptr (VH_FLAG_NO_CLS): no class-token row, rows 0 .. lead - 1 = reg[r], pos unread; lead == 0 then
+// makes no launch at all.  Both launchers.
 hipError_t launch_lead_rows(float* x, const float* cls, const float* pos, const float* reg, int lead, int batch, int tokens,
                             int dim, hipStream_t stream);
 // the same rows of the SPLIT residual: their (hi, lo) planes and their per-64-column partial sums
@@ -243,9 +244,32 @@ struct FeatureArgs {
     int lead = 1;   // rows in front of an image's patch rows: 1 .. tokens - 1
     void* reg = nullptr;               // [batch][lead - 1][dim] <- tokens 1 .. lead - 1 (the register rows); needs lead >= 2
     int patch_layout = VH_FEAT_ROWS;   // VH_FEAT_NCHW: patch is [batch][dim][tokens - lead] (feat_nchw_kernel), the same elements transposed
+    // the rows of a VH_FLAG_NO_CLS context (internal launches only; the public taps leave it 0 and keep their bounds): no class-token
+    // row, lead = 0 .. tokens - 1 rows that are ALL register rows (reg [batch][lead][dim]), cls refused
+    int no_cls = 0;
 };
 const char* features_check(const FeatureArgs& a);
 hipError_t launch_token_features(const FeatureArgs& a, hipStream_t stream);
+// The pooled head's input in one pass (kernels_features.hip pool_rows_kernel; contract: vithip.h VH_FLAG_POOL, vh_op_pool_rows):
+// out[b][0 .. dim) (row stride out_stride, 0 = dim) <- the fp32 mean over rows lead .. tokens - 1 of image b, the bits
+// launch_token_features gives for `mean`.  lead = 0 .. tokens - 1.  cls_in / cls_out (both or neither; VH_POOL_CLS_AVG): the same
+// launch copies cls_in [batch][dim] into cls_out [batch][0 .. dim) (row stride out_stride).  pool_check: nullptr, or why refused.
+struct PoolArgs {
+    const void* hi;
+    const void* lo;
+    int form;
+    int batch, tokens, lead, dim;
+    const float* gamma;
+    const float* beta;
+    float eps;
+    int norm;
+    float* out;
+    int64_t out_stride = 0;
+    const float* cls_in = nullptr;
+    float* cls_out = nullptr;
+};
+const char* pool_check(const PoolArgs& a);
+hipError_t launch_pool_rows(const PoolArgs& a, hipStream_t stream);
 // The rows of a tapped layer into the capture store (vithip.h "Layer features"): bytes_hi of the hi plane (or the fp32 array), then
 // bytes_lo of the lo plane (0: none), in ONE launch.  Pointers and byte counts are multiples of 16.
 hipError_t launch_feature_capture(const void* src_hi, void* dst_hi, size_t bytes_hi, const void* src_lo, void* dst_lo, size_t bytes_lo,

@@ -57,19 +57,21 @@ struct BlobHeader {
     // on-disk files only (vh_save_weights_file): FNV-1a 64 of the parameter bytes, flags bit 0 = checksum present.
     // Blobs built in memory leave the two checksum words, bit 0 and the padding 0.  flags bits 1 and 2 describe the MODEL, in
     // memory and on disk alike: bit 1 = pre-LayerNorm (VH_FLAG_PRE_LN: two more tensors), bit 2 = QuickGELU (VH_FLAG_QUICK_GELU),
-    // bits 9 .. 13 = the number of register tokens (VH_FLAG_REGISTERS: the tensor reg), in the bits vh_config.flags keeps it in.
+    // bits 9 .. 13 = the number of register tokens (VH_FLAG_REGISTERS: the tensor reg), in the bits vh_config.flags keeps it in;
+    // bit 15 = no class token (VH_FLAG_NO_CLS), bits 16 .. 17 = the pooling mode (VH_FLAG_POOL), likewise.
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
 constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobRegisters = VH_FLAG_REGISTERS_MASK,
-                   kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobRegisters;
+                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK,
+                   kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobRegisters | kBlobNoCls | kBlobPool;
 uint32_t blob_model_bits(const vh_config& c) {
     return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u) |
-           ((uint32_t)c.flags & kBlobRegisters);
+           ((uint32_t)c.flags & (kBlobRegisters | kBlobNoCls | kBlobPool));
 }
 // the model flags of a header's flags word (vh_blob_file_config)
 int32_t blob_model_flags(uint32_t bits) {
-    return ((bits & kBlobPreLn) ? VH_FLAG_PRE_LN : 0) | ((bits & kBlobQuickGelu) ? VH_FLAG_QUICK_GELU : 0) | (int32_t)(bits & kBlobRegisters);
+    return ((bits & kBlobPreLn) ? VH_FLAG_PRE_LN : 0) | ((bits & kBlobQuickGelu) ? VH_FLAG_QUICK_GELU : 0) | (int32_t)(bits & (kBlobRegisters | kBlobNoCls | kBlobPool));
 }
 
 uint64_t fnv1a64(const void* data, size_t n, uint64_t h = 0xCBF29CE484222325ull) {
@@ -85,6 +87,9 @@ struct LayerOff {  // offsets in floats from the start of the parameter region
 struct Layout {
     int T, NP, KP;   // KP = patch^2 * channels: the patch vector in the blob
     int R = 0, lead = 1;   // VH_FLAG_REGISTERS: register tokens; lead = 1 + R rows in front of an image's patch rows, T = NP + lead
+    // VH_FLAG_NO_CLS: no class-token row (ncls = 0: lead = R, no tensor cls, pos [NP][D]); VH_FLAG_POOL: the head's input and its
+    // width HW (D; 2 D for VH_POOL_CLS_AVG: headw [C][HW])
+    int ncls = 1, pool = VH_POOL_CLS, HW = 0;
     int KPA;         // KP rounded up to 64: the compute width of the 16-bit patch operands (wp16, col16, the patch GEMM's K)
     size_t patch_w, patch_b, cls, pos, lnfw, lnfb, headw, headb, total;
     size_t reg = 0;              // VH_FLAG_REGISTERS: reg [R][D], directly after pos ([(NP + 1)][D]: registers carry no position row)
@@ -98,13 +103,16 @@ Layout make_layout(const vh_config& c) {
     const int g = c.image_size / c.patch_size;
     L.NP = g * g;
     L.R = VH_FLAG_REGISTERS_OF(c.flags);
-    L.lead = 1 + L.R;
+    L.ncls = (c.flags & VH_FLAG_NO_CLS) ? 0 : 1;
+    L.pool = VH_FLAG_POOL_OF(c.flags);
+    L.HW = L.pool == VH_POOL_CLS_AVG ? 2 * c.dim : c.dim;
+    L.lead = L.ncls + L.R;
     L.T = L.NP + L.lead;
     L.KP = c.patch_size * c.patch_size * c.channels;
     L.KPA = (L.KP + 63) / 64 * 64;
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += n; return r; };
-    L.patch_w = take(D * L.KP); L.patch_b = take(D); L.cls = take(D); L.pos = take((size_t)(L.NP + 1) * D);
+    L.patch_w = take(D * L.KP); L.patch_b = take(D); L.cls = L.ncls ? take(D) : 0; L.pos = take((size_t)(L.NP + L.ncls) * D);
     if (L.R) L.reg = take((size_t)L.R * D);
     if (c.flags & VH_FLAG_PRE_LN) { L.prew = take(D); L.preb = take(D); }
     L.layer.resize(c.layers);
@@ -116,7 +124,7 @@ Layout make_layout(const vh_config& c) {
         p.ln2w = take(D); p.ln2b = take(D);
         p.f1w = take(M * D); p.f1b = take(M); p.f2w = take(D * M); p.f2b = take(D);
     }
-    L.lnfw = take(D); L.lnfb = take(D); L.headw = take(C * D); L.headb = take(C);
+    L.lnfw = take(D); L.lnfb = take(D); L.headw = take(C * (size_t)L.HW); L.headb = take(C);
     L.total = o;
     return L;
 }
@@ -124,10 +132,11 @@ Layout make_layout(const vh_config& c) {
 // expected blob size of a configuration computed WITHOUT building the layout (no allocation): used on untrusted headers
 size_t blob_bytes_of(const vh_config& c) {
     const size_t D = c.dim, M = c.mlp_dim, C = c.classes, g = (size_t)(c.image_size / c.patch_size);
-    const size_t T = g * g + 1 + (size_t)VH_FLAG_REGISTERS_OF(c.flags), KP = (size_t)c.patch_size * c.patch_size * c.channels;   // (pos rows + reg rows)
+    const size_t ncls = (c.flags & VH_FLAG_NO_CLS) ? 0 : 1, HW = VH_FLAG_POOL_OF(c.flags) == VH_POOL_CLS_AVG ? 2 * D : D;
+    const size_t T = g * g + ncls + (size_t)VH_FLAG_REGISTERS_OF(c.flags), KP = (size_t)c.patch_size * c.patch_size * c.channels;   // (pos rows + reg rows)
     const size_t per_layer = 2 * D + 4 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D);
     const size_t pre_ln = (c.flags & VH_FLAG_PRE_LN) ? 2 * D : 0;
-    return sizeof(BlobHeader) + 4 * (D * KP + D + D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * D + C);
+    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C);
 }
 
 const char* check_config(const vh_config& c) {
@@ -144,9 +153,16 @@ const char* check_config(const vh_config& c) {
     if (c.dtype == VH_DTYPE_FP8 && (c.dim % 128 || c.mlp_dim % 128)) return "VH_DTYPE_FP8 needs dim and mlp_dim to be multiples of 128";
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
-    if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK)) return "unknown bits in flags";
+    if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK |
+                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK)) return "unknown bits in flags";
     const int R = VH_FLAG_REGISTERS_OF(c.flags);
     if (R > VH_MAX_REGISTERS) return "flags: VH_FLAG_REGISTERS takes 0 .. 16 register tokens";
+    const int ncls = (c.flags & VH_FLAG_NO_CLS) ? 0 : 1, pool = VH_FLAG_POOL_OF(c.flags);
+    if (!ncls && (pool == VH_POOL_CLS || pool == VH_POOL_CLS_AVG))
+        return pool == VH_POOL_CLS ? "flags: VH_FLAG_NO_CLS needs VH_FLAG_POOL(VH_POOL_AVG_NORM) or VH_FLAG_POOL(VH_POOL_AVG_FCNORM): VH_POOL_CLS reads the class token"
+                                   : "flags: VH_FLAG_NO_CLS excludes VH_POOL_CLS_AVG: its first half is the class token";
+    if ((c.flags & VH_FLAG_CLS_TAIL) && !ncls) return "flags: VH_FLAG_CLS_TAIL excludes VH_FLAG_NO_CLS (its last layer computes the class-token rows only)";
+    if ((c.flags & VH_FLAG_CLS_TAIL) && pool != VH_POOL_CLS) return "flags: VH_FLAG_CLS_TAIL excludes VH_FLAG_POOL (its last layer does not update the patch rows)";
     if ((c.flags & VH_FLAG_W8_E4M3) && c.dtype == VH_DTYPE_FP8) return "flags: VH_FLAG_W8_E4M3 is for the 16-bit dtypes (VH_DTYPE_FP8 quantises both operands)";
     if ((c.flags & VH_FLAG_W8_E4M3) && (c.dim % 4 || c.mlp_dim % 4)) return "flags: VH_FLAG_W8_E4M3 needs dim and mlp_dim multiples of 4";
     if ((c.flags & VH_FLAG_LN_FOLD_OFF) && (c.flags & VH_FLAG_LN_FOLD_ON)) return "flags: VH_FLAG_LN_FOLD_OFF and VH_FLAG_LN_FOLD_ON exclude each other";
@@ -158,8 +174,10 @@ const char* check_config(const vh_config& c) {
     // largest row count (max_batch x tokens) any model reached while the attention was bounded at 640 tokens
     const int g = c.image_size / c.patch_size;
     if (g > 64) return "tokens <= 4097 (image_size / patch_size <= 64)";
-    if (g * g + 1 + R > 4097) return "tokens <= 4097: a 64 x 64 patch grid + the class token leaves no room for register tokens";
-    if ((int64_t)c.max_batch * (g * g + 1 + R) > (640ll << 20)) return "max_batch x tokens <= 640 x 2^20";
+    if (g * g + ncls + R > 4097)
+        return ncls ? "tokens <= 4097: a 64 x 64 patch grid + the class token leaves no room for register tokens"
+                    : "tokens <= 4097: a 64 x 64 patch grid without a class token leaves room for one register token";
+    if ((int64_t)c.max_batch * (g * g + ncls + R) > (640ll << 20)) return "max_batch x tokens <= 640 x 2^20";
     return nullptr;
 }
 
@@ -255,7 +273,8 @@ struct vh_ctx {
     void* att16 = nullptr;    //                 [B*T, D]
     void* h16 = nullptr;      //                 [B*T, M]
     void* col16 = nullptr;    // patch matrix    [B*NP, KPA]
-    float* clsn32 = nullptr;  // final-LN'd CLS  [B, D] fp32 (the head runs in fp32 on the blob's own weights)
+    float* clsn32 = nullptr;  // the head's input [B, W] fp32: the final-LN'd CLS rows (W = D), or what the VH_FLAG_POOL mode computes (W = L.HW)
+    float* pool32 = nullptr;  // [B, D] fp32 scratch of the pooled modes: CLS_AVG's LN'd class rows, AVG_FCNORM's raw mean
     float* in_dev = nullptr;  // staging for the host-pointer forward (fp32 images; vh_forward_u8 stages its bytes in the same buffer)
     // Input normalisation of the 8-bit entry points (vh_set_input_norm): pixel p of channel c enters the model as
     // fmaf((float)p, in_scale[c], in_shift[c]).  Passed to im2col_u8_kernel by value, so captured graphs hold a copy.
@@ -488,6 +507,12 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if ((h.flags ^ want) & kBlobRegisters)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bits 9..13 say %d register tokens, the context's VH_FLAG_REGISTERS says %d",
                     (int)VH_FLAG_REGISTERS_OF(h.flags), (int)VH_FLAG_REGISTERS_OF(want));
+    if ((h.flags ^ want) & kBlobNoCls)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 15 (no class token) is %d, the context's VH_FLAG_NO_CLS is %d",
+                    (h.flags & kBlobNoCls) != 0, (want & kBlobNoCls) != 0);
+    if ((h.flags ^ want) & kBlobPool)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bits 16..17 say pooling mode %d, the context's VH_FLAG_POOL says %d",
+                    (int)VH_FLAG_POOL_OF(h.flags), (int)VH_FLAG_POOL_OF(want));
     return VH_OK;
 }
 
@@ -524,7 +549,12 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     char* const att16 = (char*)c->att16 + r0 * D * esz_op;
     char* const h16 = (char*)c->h16 + r0 * M * esz_op;
     char* const col16 = (char*)c->col16 + (size_t)img0 * L.NP * L.KPA * esz;
-    float* const clsn32 = c->clsn32 + (size_t)img0 * D;
+    float* const clsn32 = c->clsn32 + (size_t)img0 * L.HW;   // this part's rows of the head's input [.][W]
+    float* const pool32 = c->pool32 + (size_t)img0 * D;
+    // VH_FLAG_NO_CLS: no class-token row.  The patch GEMM's epilogue adds "pos row 1 + p", so a context without pos[0] hands it the
+    // table one row early (inside the resident blob: the header and the patch tensors precede pos); the leading rows are all registers.
+    const float* const cls_p = L.ncls ? P + L.cls : nullptr;
+    const float* const pos_p = P + L.pos - (L.ncls ? 0 : D);
     // the attention launches' work-queue counters: one word per layer, all zeroed by ONE memset per forward (a memset per
     // launch is a 5 us fill kernel in front of every attention kernel)
     unsigned int* const tickets_part = c->tickets + (size_t)img0 * (f.layers > 0 ? f.layers : 1);
@@ -627,22 +657,22 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         // partial sums (PATCH_SPLIT epilogue; the class-token rows from their own small kernel) -- no fp32
         // x, no separate row-statistics pass over it (round 3: -0.1 ms per forward).  The partial sums are laid out for rows_g
         // rows, like every later layer's.
-        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, P + L.pos, L.NP);
+        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, pos_p, L.NP);
         g.out16 = xlo16;
         g.prow = rows_g;
         g.lead = L.lead;
         if ((rc = stage(ST_PATCH, [&] { return launch_gemm(g, s); }))) return rc;
         if ((rc = stage(ST_CLS, [&] {
-                 return launch_lead_rows_split(xn16, xlo16, partials_p, rows_g, P + L.cls, P + L.pos, P + L.reg, L.lead, batch, T, D, dt16, s);
+                 return launch_lead_rows_split(xn16, xlo16, partials_p, rows_g, cls_p, pos_p, P + L.reg, L.lead, batch, T, D, dt16, s);
              })))
             return rc;
         HIPCHK(&c->err, launch_finalize_stats(partials_p, D / 64, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
         if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark: ST_LNSTATS has no stage timing)
     } else {
-        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, P + L.pos, L.NP);
+        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, pos_p, L.NP);
         g.lead = L.lead;
         if ((rc = stage(ST_PATCH, [&] { return launch_gemm(g, s); }))) return rc;
-        if ((rc = stage(ST_CLS, [&] { return launch_lead_rows(x, P + L.cls, P + L.pos, P + L.reg, L.lead, batch, T, D, s); }))) return rc;
+        if ((rc = stage(ST_CLS, [&] { return launch_lead_rows(x, cls_p, pos_p, P + L.reg, L.lead, batch, T, D, s); }))) return rc;
         if (pre_ln) {
             // x <- LN(x) pre_ln.weight + pre_ln.bias, in the form the path consumes: the fp32 array (plain loop, non-split fold, no
             // layer at all), the 16-bit operand copy / the split planes, layer 0's LN1 statistics of the normalised rows and the guards
@@ -788,12 +818,28 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
                                 more ? P + L.layer[l + 1].ln1b : nullptr, ST_FC2))) return rc;
         if ((rc = capture(l))) return rc;   // behind both launches of resid_gemm_ln: x is complete and nothing writes it
     }
-    if (c->split && nl > 0)
-        HIPCHK(&c->err, launch_layernorm_split(xn16, xlo16, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, c->fp8 ? VH_DTYPE_FP8 : dt16, s));
-    else
-        HIPCHK(&c->err, launch_layernorm(x, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, VH_DTYPE_F32_INTERNAL, s));
+    // The head's input [batch][W] (vithip.h VH_FLAG_POOL).  VH_POOL_CLS: the final LayerNorm of row 0, as ever.  VH_POOL_CLS_AVG: the
+    // same launch into scratch, which the pool kernel copies into columns 0 .. D - 1 beside its own D .. 2 D - 1.  The pooled modes
+    // read the patch rows where the path left them (planes or the fp32 array) ONCE.  All of it under the final-LayerNorm stage.
+    const bool planes = c->split && nl > 0;
+    if (L.pool == VH_POOL_CLS || L.pool == VH_POOL_CLS_AVG) {
+        float* const cls_ln = L.pool == VH_POOL_CLS ? clsn32 : pool32;
+        if (planes)
+            HIPCHK(&c->err, launch_layernorm_split(xn16, xlo16, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, c->fp8 ? VH_DTYPE_FP8 : dt16, s));
+        else
+            HIPCHK(&c->err, launch_layernorm(x, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, VH_DTYPE_F32_INTERNAL, s));
+    }
+    if (L.pool != VH_POOL_CLS) {
+        PoolArgs pa{planes ? (const void*)xn16 : (const void*)x, planes ? xlo16 : nullptr, planes ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32,
+                    batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps, L.pool == VH_POOL_AVG_FCNORM ? VH_FEAT_RAW : VH_FEAT_NORM, clsn32};
+        if (L.pool == VH_POOL_CLS_AVG) { pa.out = clsn32 + D; pa.out_stride = 2 * D; pa.cls_in = pool32; pa.cls_out = clsn32; }
+        if (L.pool == VH_POOL_AVG_FCNORM) pa.out = pool32;   // LN(mean x): the raw mean, then the fp32 LayerNorm over [batch][D]
+        HIPCHK(&c->err, launch_pool_rows(pa, s));
+        if (L.pool == VH_POOL_AVG_FCNORM)
+            HIPCHK(&c->err, launch_layernorm(pool32, batch, D, D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, VH_DTYPE_F32_INTERNAL, s));
+    }
     if ((rc = mark(ST_LNF))) return rc;
-    HIPCHK(&c->err, launch_head_f32(clsn32, P + L.headw, P + L.headb, logits, batch, f.classes, D, s));
+    HIPCHK(&c->err, launch_head_f32(clsn32, P + L.headw, P + L.headb, logits, batch, f.classes, L.HW, s));
     if ((rc = mark(ST_HEAD))) return rc;
     c->last_batch = batch;
     return VH_OK;
@@ -1346,7 +1392,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     const size_t rows_p = rows + 256;
     const size_t o_x = carve(rows_p * D * 4), o_xn = carve(rows_p * D * 2), o_qkvA = carve(rows_p * 3 * D * 2),
                  o_att = carve(rows_p * D * 2), o_h = carve(rows_p * M * 2), o_col = carve(B * L.NP * (size_t)L.KPA * 2),
-                 o_cls = carve(B * D * 4),
+                 o_cls = carve(B * 2 * D * 4), o_pool = carve(B * D * 4),   // the head's input [B][W <= 2 D]; VH_FLAG_POOL scratch [B][D]
                  o_in = carve(B * (size_t)cfg->image_size * cfg->image_size * cfg->channels * 4), o_lg = carve(B * C * 4),
                  o_st = carve(rows_p * 2 * 4), o_pt = carve((D / 64 + 1) * rows_p * 2 * 4), o_xlo = carve(rows_p * D * 2),   // lo plane: one byte per element (16-bit paths) or bf16 (fp8 path)
                  o_tk = carve(B * 4 * (size_t)(cfg->layers > 0 ? cfg->layers : 1)),   // attention work-queue counters: one word per image and layer, a part uses its first image's
@@ -1356,6 +1402,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     CK(hipMemsetAsync(c->guard_dev, 0, 256, c->stream));
     c->x = (float*)(c->arena + o_x); c->xn16 = c->arena + o_xn; c->qkv16 = c->arena + o_qkvA; c->att16 = c->arena + o_att;
     c->h16 = c->arena + o_h; c->col16 = c->arena + o_col; c->clsn32 = (float*)(c->arena + o_cls);
+    c->pool32 = (float*)(c->arena + o_pool);
     c->in_dev = (float*)(c->arena + o_in); c->logits_dev = (float*)(c->arena + o_lg);
     c->stats = (float*)(c->arena + o_st); c->partials = (float*)(c->arena + o_pt); c->xlo16 = c->arena + o_xlo;
     c->tickets = (unsigned int*)(c->arena + o_tk);
@@ -1482,8 +1529,8 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
 #define GEN(off, count, tid, sigma, offs) HIPCHK(&c->err, launch_fill(P + (off), (int64_t)(count), seed, (tid), 1, (sigma), (offs), s))
     GEN(L.patch_w, D * L.KP, TID_PATCH_W, sw, 0.f);
     GEN(L.patch_b, D, TID_PATCH_B, sb, 0.f);
-    GEN(L.cls, D, TID_CLS, sw, 0.f);
-    GEN(L.pos, (size_t)(L.NP + 1) * D, TID_POS, sw, 0.f);
+    if (L.ncls) GEN(L.cls, D, TID_CLS, sw, 0.f);
+    GEN(L.pos, (size_t)(L.NP + L.ncls) * D, TID_POS, sw, 0.f);
     if (L.R) GEN(L.reg, (size_t)L.R * D, TID_REG, sw, 0.f);
     if (f.flags & VH_FLAG_PRE_LN) { GEN(L.prew, D, TID_PRE_LN_W, sg, 1.f); GEN(L.preb, D, TID_PRE_LN_B, sb, 0.f); }
     for (int l = 0; l < f.layers; ++l) {
@@ -1499,7 +1546,7 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
         GEN(o.f2w, D * M, t + 14, sw, 0.f); GEN(o.f2b, D, t + 15, sb, 0.f);
     }
     GEN(L.lnfw, D, TID_FINAL + 0, sg, 1.f); GEN(L.lnfb, D, TID_FINAL + 1, sb, 0.f);
-    GEN(L.headw, C * D, TID_FINAL + 2, sw, 0.f); GEN(L.headb, C, TID_FINAL + 3, sb, 0.f);
+    GEN(L.headw, C * (size_t)L.HW, TID_FINAL + 2, sw, 0.f); GEN(L.headb, C, TID_FINAL + 3, sb, 0.f);
 #undef GEN
     if (int rc = guard_reset(c)) return rc;
     if (int rc = prepare_weights(c)) return rc;
@@ -2242,7 +2289,7 @@ int vh_debug_read(vh_ctx* c, int what, float* host_out, size_t n_floats) {
         return VH_OK;
     }
     if (what == 1) {
-        const size_t n = (size_t)c->last_batch * D;
+        const size_t n = (size_t)c->last_batch * c->L.HW;   // the head's input [batch][W]
         if (n_floats != n) return fail(&c->err, VH_ERR_INVALID, "expected %zu floats", n);
         HIPCHK(&c->err, hipMemcpy(host_out, c->clsn32, n * 4, hipMemcpyDeviceToHost));
         return VH_OK;
@@ -2284,6 +2331,7 @@ static int features_check_call(vh_ctx* c, const vh_features* f, bool device) {
         return fail(&c->err, VH_ERR_INVALID, "read_features: a device output pointer is not 16-byte aligned (cls %p, patch %p, mean %p)", f->cls, f->patch, f->mean);
     if (c->cfg.flags & VH_FLAG_CLS_TAIL)
         return fail(&c->err, VH_ERR_UNSUPPORTED, "read_features: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
+    if (f->cls && !c->L.ncls) return fail(&c->err, VH_ERR_UNSUPPORTED, "read_features: cls on a context without a class token (VH_FLAG_NO_CLS)");
     if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "read_features: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
     if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "read_features: no forward has run");
     return VH_OK;
@@ -2295,7 +2343,7 @@ static FeatSource features_live(const vh_ctx* c) {
     const int nl = (c->run_layers < 0 || c->run_layers > g.layers) ? g.layers : c->run_layers;
     const bool planes = c->split && nl > 0;   // where the last forward left the rows: the two planes, or the fp32 array
     return FeatSource{planes ? (const void*)c->xn16 : (const void*)c->x, planes ? c->xlo16 : nullptr,
-                      planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32, true};
+                      planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32, c->L.pool == VH_POOL_CLS};   // (a pooled head's input is not LN(row 0))
 }
 static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSource& src, const char* who) {
     const vh_config& g = c->cfg;
@@ -2309,6 +2357,7 @@ static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSou
     a.cls = copy_cls ? nullptr : f.cls;
     a.patch = f.patch; a.mean = f.mean; a.stats = c->stats;
     a.reg = f.reg; a.patch_layout = f.patch_layout;
+    a.no_cls = c->L.ncls ? 0 : 1;   // VH_FLAG_NO_CLS: lead = R rows, all of them registers (an internal form: the public taps keep lead >= 1)
     if (a.cls || a.patch || a.mean || a.reg) {
         if (const char* why = features_check(a)) return fail(&c->err, VH_ERR_INVALID, "%s: %s", who, why);
         HIPCHK(&c->err, launch_token_features(a, c->stream));
@@ -2438,6 +2487,7 @@ static int layer_features_check_call(vh_ctx* c, const vh_layer_features* f, bool
     if (f->reg && c->L.R == 0) return fail(&c->err, VH_ERR_INVALID, "read_layer_features: reg on a context without register tokens (VH_FLAG_REGISTERS)");
     if (c->cfg.flags & VH_FLAG_CLS_TAIL)
         return fail(&c->err, VH_ERR_UNSUPPORTED, "read_layer_features: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
+    if (f->cls && !c->L.ncls) return fail(&c->err, VH_ERR_UNSUPPORTED, "read_layer_features: cls on a context without a class token (VH_FLAG_NO_CLS)");
     if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "read_layer_features: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
     if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "read_layer_features: no forward has run");
     if (f->layer == -1) { *src = features_live(c); return VH_OK; }
@@ -2449,7 +2499,7 @@ static int layer_features_check_call(vh_ctx* c, const vh_layer_features* f, bool
         return fail(&c->err, VH_ERR_STATE, "read_layer_features: the last forward ran %d layers and did not reach layer %d (vh_debug_set_layers)", c->cap_nl, f->layer);
     if (f->layer == c->cap_nl) {   // the live residual; its normalised class-token rows are the head's for the whole model only
         *src = features_live(c);
-        src->head_cls = f->layer == layers;
+        src->head_cls = src->head_cls && f->layer == layers;
         return VH_OK;
     }
     const char* const base = c->feat_store + (size_t)slot * c->feat_slot;
@@ -2535,7 +2585,10 @@ int vh_op_gemm_lead(const void* a, const void* w, const float* bias, void* out, 
 }
 int vh_op_lead_rows(void* x_or_hi, void* lo, float* partials, int64_t prow, const float* cls, const float* pos, const float* reg, int lead,
                     int batch, int tokens, int dim, int dtype, void* stream) {
-    if (!x_or_hi || !cls || !pos || batch <= 0 || dim <= 0 || dim % 64 || lead < 1 || lead > 1 + VH_MAX_REGISTERS || lead >= tokens || (lead > 1 && !reg))
+    // cls NULL (with pos NULL): the form of a VH_FLAG_NO_CLS context, whose `lead` rows are all register rows (1 <= lead <= 16, reg needed)
+    const bool no_cls = !cls && !pos;
+    if (!x_or_hi || (!no_cls && (!cls || !pos)) || batch <= 0 || dim <= 0 || dim % 64 || lead < 1 || lead > (no_cls ? 0 : 1) + VH_MAX_REGISTERS ||
+        lead >= tokens || ((no_cls || lead > 1) && !reg))
         return fail(nullptr, VH_ERR_INVALID, "lead_rows: bad argument (dim %% 64 == 0, 1 <= lead <= 17, lead < tokens, reg for lead > 1)");
     hipError_t e;
     if (lo) {   // the split form: planes + partial sums
@@ -2911,6 +2964,16 @@ int vh_op_token_features2(const void* hi, const void* lo, int form, int batch, i
     a.reg = reg_out;
     a.patch_layout = patch_layout;
     return op_token_features_run(a, stream);
+}
+// the pooled head's one-pass kernel on caller-made rows (VH_FLAG_POOL)
+int vh_op_pool_rows(const void* hi, const void* lo, int form, int batch, int tokens, int lead, int dim, const float* gamma, const float* beta,
+                    float eps, int norm, float* mean_out, void* stream) {
+    const PoolArgs a{hi, lo, form, batch, tokens, lead, dim, gamma, beta, eps, norm, mean_out};
+    if (const char* why = pool_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_pool_rows(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "pool_rows failed: %s", hipGetErrorString(e));
+    return VH_OK;
 }
 int vh_op_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind, float sigma, void* stream) {
     if (!out || n <= 0 || kind < 0 || kind > 2) return fail(nullptr, VH_ERR_INVALID, "fill: bad argument");

@@ -30,6 +30,22 @@ def registers_of(flags):
     return (int(flags) & FLAG_REGISTERS_MASK) >> 9
 
 
+# Pooled heads and models without a class token (VH_FLAG_NO_CLS, VH_FLAG_POOL; vithip.h): model bits, in the blob header too
+FLAG_NO_CLS, FLAG_POOL_MASK = 1 << 15, 3 << 16
+POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM, POOL_CLS_AVG = range(4)
+
+
+def FLAG_POOL(m):
+    """VH_FLAG_POOL(m): the head's input, POOL_CLS (LN(row 0)), POOL_AVG_NORM (mean LN(patch rows)), POOL_AVG_FCNORM (LN(mean patch
+    rows)) or POOL_CLS_AVG (concat of the first two, head [C, 2 D]), in bits 16 .. 17 of flags."""
+    return (int(m) & 3) << 16
+
+
+def pool_of(flags):
+    """VH_FLAG_POOL_OF(flags)."""
+    return (int(flags) & FLAG_POOL_MASK) >> 16
+
+
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
 EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
 ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = range(4)   # element type of an image tensor (VH_ELEM_*)
@@ -297,6 +313,7 @@ SYMBOLS = {
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
     "vh_group_create": (_i, [C.POINTER(Config), _pi, _i, C.POINTER(_vp)]),
@@ -369,6 +386,29 @@ def blob_file_flags(path):
     return c.flags
 
 
+def _blob_header(cfg, ln_eps, bits):
+    """The 64-byte header of a memory blob: magic, the model shape, ln_eps and the model bits of the flags word (byte 52)."""
+    h = np.zeros(64, dtype=np.uint8)
+    h[:7] = np.frombuffer(b"VHBLOB1", dtype=np.uint8)
+    h[8:40] = np.array([cfg[k] for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")],
+                       dtype=np.int32).view(np.uint8)
+    h[40:44] = np.array([ln_eps], dtype=np.float32).view(np.uint8)
+    h[52:56] = np.array([bits], dtype=np.uint32).view(np.uint8)
+    return h
+
+
+def _taker(sd, me):
+    """take(name, shape, f) of a converter: tensor `name` of the state dict, checked for presence and shape, flattened as type f."""
+    def take(name, shape, f=np.float32):
+        if name not in sd:
+            raise KeyError(f"{me}: missing tensor {name}")
+        a = np.asarray(sd[name])
+        if a.shape != tuple(shape):
+            raise ValueError(f"{me}: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}")
+        return np.ascontiguousarray(a, dtype=f).reshape(-1)
+    return take
+
+
 def blob_from_clip_state_dict(sd, cfg, ln_eps=1e-5):
     """Canonical blob of a CLIP vision tower from a dict of arrays under the Hugging Face `CLIPVisionModelWithProjection`
     parameter names (numpy only; torch tensors: pass `{k: v.numpy() for k, v in model.state_dict().items()}`).
@@ -405,16 +445,11 @@ def blob_from_clip_state_dict(sd, cfg, ln_eps=1e-5):
                   take(b + "mlp.fc2.weight", (D, M)), take(b + "mlp.fc2.bias", (D,))]
     parts += [take(v + "post_layernorm.weight", (D,)), take(v + "post_layernorm.bias", (D,)),
               take("visual_projection.weight", (E, D)), np.zeros(E, np.float32)]
-    h = np.zeros(64, dtype=np.uint8)
-    h[:7] = np.frombuffer(b"VHBLOB1", dtype=np.uint8)
-    h[8:40] = np.array([cfg[k] for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")],
-                       dtype=np.int32).view(np.uint8)
-    h[40:44] = np.array([ln_eps], dtype=np.float32).view(np.uint8)
-    h[52:56] = np.array([2 | (4 if flags & FLAG_QUICK_GELU else 0)], dtype=np.uint32).view(np.uint8)   # header flags word: bit 1 pre-LN, bit 2 QuickGELU
+    h = _blob_header(cfg, ln_eps, 2 | (4 if flags & FLAG_QUICK_GELU else 0))   # header flags word: bit 1 pre-LN, bit 2 QuickGELU
     return np.concatenate([h] + [p.view(np.uint8) for p in parts])
 
 
-def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None):
+def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
     """Canonical blob of a DINOv2 backbone from a dict of arrays under the Hugging Face `Dinov2Model` /
     `Dinov2WithRegistersModel` parameter names (numpy only; torch tensors: `{k: v.numpy() for k, v in model.state_dict().items()}`).
     `cfg`: the model shape, `registers` = the number of register tokens (0 for the models without), classes = the head's width.
@@ -422,9 +457,22 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None):
     likewise, computed in float64 and rounded once to fp32.  The backbone has no head: it is zero unless head = (weight
     [classes, dim], bias [classes]) is given.  `embeddings.mask_token` is ignored.  Refused: a SwiGLU MLP (mlp.weights_in), a
     position table whose row count is not NP + 1 of cfg (nothing is interpolated here), a register count other than
-    cfg['registers'], a missing or wrongly shaped tensor (by name)."""
+    cfg['registers'], a missing or wrongly shaped tensor (by name).
+    pool = POOL_CLS_AVG: the published ImageNet linear classifiers (`Dinov2ForImageClassification`,
+    `Dinov2WithRegistersForImageClassification`: head(concat(cls, mean of the patch tokens)), head weight [classes, 2 dim], the
+    class-token half first).  A state dict of those models is taken as it is: the `dinov2.` / `dinov2_with_registers.` prefix is
+    dropped and `classifier.*` is the head unless `head` is given.  The head's shape is checked against the mode ([classes, dim]
+    for POOL_CLS / POOL_AVG_NORM / POOL_AVG_FCNORM); the header carries FLAG_POOL(pool)."""
     me = "blob_from_dinov2_state_dict"
+    if pool not in (POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM, POOL_CLS_AVG):
+        raise ValueError(f"{me}: pool = {pool} is not POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM or POOL_CLS_AVG")
+    for prefix in ("dinov2.", "dinov2_with_registers."):
+        if any(k.startswith(prefix) for k in sd):
+            if head is None and "classifier.weight" in sd and "classifier.bias" in sd:
+                head = (sd["classifier.weight"], sd["classifier.bias"])
+            sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
     D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
+    W = 2 * D if pool == POOL_CLS_AVG else D
     g = cfg["image_size"] // cfg["patch_size"]
     R = int(cfg.get("registers", 0))
     if not 0 <= R <= MAX_REGISTERS:
@@ -441,13 +489,7 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None):
             raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP + 1 = {g * g + 1} "
                              "(interpolate the table to the image size first)")
 
-    def take(name, shape, f=np.float32):
-        if name not in sd:
-            raise KeyError(f"{me}: missing tensor {name}")
-        a = np.asarray(sd[name])
-        if a.shape != tuple(shape):
-            raise ValueError(f"{me}: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}")
-        return np.ascontiguousarray(a, dtype=f).reshape(-1)
+    take = _taker(sd, me)
 
     def scaled(wname, bname, lname, n_in):
         # diag(lambda) W and lambda b in float64, one rounding to fp32 (exact for lambda == 1)
@@ -470,18 +512,133 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None):
         parts += scaled(b + "mlp.fc2.weight", b + "mlp.fc2.bias", b + "layer_scale2.lambda1", M)
     parts += [take("layernorm.weight", (D,)), take("layernorm.bias", (D,))]
     if head is None:
+        parts += [np.zeros(E * W, np.float32), np.zeros(E, np.float32)]
+    else:
+        hw, hb = (np.asarray(a) for a in head)
+        if hw.shape != (E, W) or hb.shape != (E,):
+            raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, W)}, {(E,)}")
+        parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
+    h = _blob_header(cfg, ln_eps, FLAG_REGISTERS(R) | FLAG_POOL(pool))   # header flags word: bits 9 .. 13 = register tokens, 16 .. 17 = pooling
+    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+
+
+def blob_from_ijepa_state_dict(sd, cfg, ln_eps=1e-6, head=None):
+    """Canonical blob of an I-JEPA encoder from a dict of arrays under the Hugging Face `IJepaModel` / `IJepaForImageClassification`
+    parameter names (`ijepa.embeddings.*`, `ijepa.layers.N.attention.{q,k,v,o}_proj`, `layernorm_before` / `layernorm_after`,
+    `mlp.fc1` / `mlp.fc2`, `ijepa.layernorm`, `classifier`; an `IJepaModel` dict without the `ijepa.` prefix is taken too; numpy
+    only).  The model has no class token and its classifier is head(mean(LN(x))): the blob is one of a FLAG_NO_CLS |
+    FLAG_POOL(POOL_AVG_NORM) context -- no `cls` tensor, pos [NP, dim] -- and its header says so.  The head is `classifier.*`, else
+    head = (weight [classes, dim], bias [classes]), else zero.  `embeddings.mask_token` is ignored.  Refused: a `cls_token` in the
+    state dict, a position table whose row count is not NP of cfg, a wrongly shaped head, a missing or wrongly shaped tensor (by name)."""
+    me = "blob_from_ijepa_state_dict"
+    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
+    g = cfg["image_size"] // cfg["patch_size"]
+    if not any(k.startswith("ijepa.") for k in sd):
+        sd = dict({"ijepa." + k: v for k, v in sd.items() if not k.startswith("classifier.")},
+                  **{k: v for k, v in sd.items() if k.startswith("classifier.")})
+    emb = "ijepa.embeddings."
+    if emb + "cls_token" in sd:
+        raise ValueError(f"{me}: the checkpoint has a class token ({emb}cls_token); the blob of a FLAG_NO_CLS context has none")
+    if emb + "position_embeddings" in sd:
+        rows = int(np.asarray(sd[emb + "position_embeddings"]).shape[-2])
+        if rows != g * g:
+            raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP = {g * g} (no class-token row; "
+                             "interpolate the table to the image size first)")
+
+    take = _taker(sd, me)
+
+    parts = [take(emb + "patch_embeddings.projection.weight", (D, CH, P, P)), take(emb + "patch_embeddings.projection.bias", (D,)),
+             take(emb + "position_embeddings", (1, g * g, D))]
+    for l in range(cfg["layers"]):
+        b = f"ijepa.layers.{l}."
+        parts += [take(b + "layernorm_before.weight", (D,)), take(b + "layernorm_before.bias", (D,))]
+        for n in ("q_proj", "k_proj", "v_proj", "o_proj"):
+            parts += [take(f"{b}attention.{n}.weight", (D, D)), take(f"{b}attention.{n}.bias", (D,))]
+        parts += [take(b + "layernorm_after.weight", (D,)), take(b + "layernorm_after.bias", (D,)),
+                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,)),
+                  take(b + "mlp.fc2.weight", (D, M)), take(b + "mlp.fc2.bias", (D,))]
+    parts += [take("ijepa.layernorm.weight", (D,)), take("ijepa.layernorm.bias", (D,))]
+    if head is None and "classifier.weight" in sd and "classifier.bias" in sd:
+        head = (sd["classifier.weight"], sd["classifier.bias"])
+    if head is None:
         parts += [np.zeros(E * D, np.float32), np.zeros(E, np.float32)]
     else:
         hw, hb = (np.asarray(a) for a in head)
         if hw.shape != (E, D) or hb.shape != (E,):
             raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, D)}, {(E,)}")
         parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
-    h = np.zeros(64, dtype=np.uint8)
-    h[:7] = np.frombuffer(b"VHBLOB1", dtype=np.uint8)
-    h[8:40] = np.array([cfg[k] for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")],
-                       dtype=np.int32).view(np.uint8)
-    h[40:44] = np.array([ln_eps], dtype=np.float32).view(np.uint8)
-    h[52:56] = np.array([FLAG_REGISTERS(R)], dtype=np.uint32).view(np.uint8)   # header flags word: bits 9 .. 13 = register tokens
+    h = _blob_header(cfg, ln_eps, FLAG_NO_CLS | FLAG_POOL(POOL_AVG_NORM))
+    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+
+
+def blob_from_timm_vit_state_dict(sd, cfg, ln_eps=1e-6, global_pool="token", fc_norm=None):
+    """Canonical blob of a timm `VisionTransformer` classifier from a dict of arrays under timm's parameter names: `cls_token`,
+    `reg_token`, `pos_embed`, `patch_embed.proj.*`, `blocks.N.{norm1, attn.qkv, attn.proj, ls1.gamma, norm2, mlp.fc1, mlp.fc2,
+    ls2.gamma}`, `norm` / `fc_norm`, `head` (numpy only).  NOT run against a timm install (none was at hand): the names and
+    the pooling rules are timm's as documented, the test builds the state dict under those names from seeded tensors.
+      global_pool 'token' -> POOL_CLS; 'avg' with fc_norm (timm's default for 'avg') -> POOL_AVG_FCNORM, lnf = `fc_norm.*`; 'avg'
+      with fc_norm=False -> POOL_AVG_NORM, lnf = `norm.*`.  fc_norm = None means timm's default: global_pool == 'avg'.
+      No `cls_token` (class_token=False) -> FLAG_NO_CLS, which needs global_pool 'avg'.  cfg['registers'] = the rows of `reg_token`.
+      The fused qkv is split, LayerScale (`ls1.gamma`, `ls2.gamma`; optional) is folded as the DINOv2 converter folds it.
+      `pos_embed` has NP or NP + 1 rows, nothing else: with a class token, NP rows mean no_embed_class (the class token's position
+      row is zero); without one, NP rows are required.  (Register tokens carry no position row here, as in the library.)
+    Refused: a pooling other than 'token' / 'avg', 'token' without a class token, pos_embed rows other than those, a register
+    count other than cfg['registers'], a missing or wrongly shaped tensor (by name)."""
+    me = "blob_from_timm_vit_state_dict"
+    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
+    g = cfg["image_size"] // cfg["patch_size"]
+    NP, R = g * g, int(cfg.get("registers", 0))
+    if global_pool not in ("token", "avg"):
+        raise ValueError(f"{me}: global_pool = {global_pool!r} is not 'token' or 'avg'")
+    if fc_norm is None:
+        fc_norm = global_pool == "avg"
+    has_cls = "cls_token" in sd
+    if not has_cls and global_pool == "token":
+        raise ValueError(f"{me}: global_pool='token' needs a cls_token")
+    if fc_norm and global_pool != "avg":
+        raise ValueError(f"{me}: fc_norm goes with global_pool='avg'")
+    pool = POOL_CLS if global_pool == "token" else POOL_AVG_FCNORM if fc_norm else POOL_AVG_NORM
+    have = int(np.asarray(sd["reg_token"]).shape[-2]) if "reg_token" in sd else 0
+    if have != R:
+        raise ValueError(f"{me}: the checkpoint has {have} register tokens, cfg['registers'] is {R}")
+
+    take = _taker(sd, me)
+
+    if "pos_embed" not in sd:
+        raise KeyError(f"{me}: missing tensor pos_embed")
+    rows = int(np.asarray(sd["pos_embed"]).shape[-2])
+    if rows not in ((NP, NP + 1) if has_cls else (NP,)):
+        raise ValueError(f"{me}: pos_embed has {rows} rows, cfg needs " + (f"NP = {NP} or NP + 1 = {NP + 1}" if has_cls else f"NP = {NP}"))
+    pos = take("pos_embed", (1, rows, D))
+    if has_cls and rows == NP:   # no_embed_class: the class token carries no position
+        pos = np.concatenate([np.zeros(D, np.float32), pos])
+
+    def scaled(wname, bname, lname, n_in):
+        w, b = take(wname, (D, n_in), np.float64).reshape(D, n_in), take(bname, (D,), np.float64)
+        if lname in sd:
+            lam = take(lname, (D,), np.float64)
+            w, b = w * lam[:, None], b * lam
+        return [w.astype(np.float32).reshape(-1), b.astype(np.float32)]
+
+    parts = [take("patch_embed.proj.weight", (D, CH, P, P)), take("patch_embed.proj.bias", (D,))]
+    if has_cls:
+        parts.append(take("cls_token", (1, 1, D)))
+    parts.append(pos)
+    if R:
+        parts.append(take("reg_token", (1, R, D)))
+    for l in range(cfg["layers"]):
+        b = f"blocks.{l}."
+        parts += [take(b + "norm1.weight", (D,)), take(b + "norm1.bias", (D,))]
+        qkv_w, qkv_b = take(b + "attn.qkv.weight", (3 * D, D)).reshape(3, D * D), take(b + "attn.qkv.bias", (3 * D,)).reshape(3, D)
+        for i in range(3):
+            parts += [np.ascontiguousarray(qkv_w[i]), np.ascontiguousarray(qkv_b[i])]
+        parts += scaled(b + "attn.proj.weight", b + "attn.proj.bias", b + "ls1.gamma", D)
+        parts += [take(b + "norm2.weight", (D,)), take(b + "norm2.bias", (D,)),
+                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,))]
+        parts += scaled(b + "mlp.fc2.weight", b + "mlp.fc2.bias", b + "ls2.gamma", M)
+    ln = "fc_norm" if fc_norm else "norm"
+    parts += [take(ln + ".weight", (D,)), take(ln + ".bias", (D,)), take("head.weight", (E, D)), take("head.bias", (E,))]
+    h = _blob_header(cfg, ln_eps, FLAG_REGISTERS(R) | (0 if has_cls else FLAG_NO_CLS) | FLAG_POOL(pool))
     return np.concatenate([h] + [p.view(np.uint8) for p in parts])
 
 
@@ -1504,7 +1661,8 @@ class VitContext:
         return int(lib().vh_get_register_tokens(self.h))
 
     def features_dims(self):
-        """(batch of the last forward, tokens, patches, dim); tokens = patches + 1 + register tokens."""
+        """(batch of the last forward, tokens, patches, dim); tokens = patches + 1 + register tokens (FLAG_NO_CLS: patches +
+        register tokens)."""
         b, t, n, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         _check(lib().vh_features_dims(self.h, C.byref(b), C.byref(t), C.byref(n), C.byref(d)), self.h)
         return b.value, t.value, n.value, d.value
@@ -1581,7 +1739,10 @@ class VitContext:
         block indices (block i = the residual stream after i + 1 layers).  Capture happens inside a forward: if the context's list
         differs it is set here and the read is refused (VhError, state) until the caller has run the forward again -- set the list
         first, or call this once before the first forward.  Returns a tuple with one entry per layer: the patch tokens
-        [B, NP, D], or [B, D, gh, gw] with reshape; with return_class_token (patch, cls [B, D])."""
+        [B, NP, D], or [B, D, gh, gw] with reshape; with return_class_token (patch, cls [B, D]) -- which a FLAG_NO_CLS context,
+        having no class token, refuses (ValueError)."""
+        if return_class_token and self.c.flags & FLAG_NO_CLS:
+            raise ValueError("get_intermediate_layers: return_class_token on a context without a class token (FLAG_NO_CLS)")
         total = self.cfg["layers"]
         blocks = list(range(total - n, total)) if isinstance(n, int) else [int(i) for i in n]
         if not blocks or min(blocks) < 0 or max(blocks) >= total or blocks != sorted(set(blocks)):
@@ -1905,6 +2066,12 @@ def op_token_features2(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr
     patch_layout FEAT_ROWS ([batch, tokens - lead, dim]) / FEAT_NCHW ([batch, dim, tokens - lead])."""
     _check(lib().vh_op_token_features2(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, elem, norm, patch_ptr,
                                        patch_layout, mean_ptr, reg_ptr, None))
+
+
+def op_pool_rows(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, norm, mean_ptr):
+    """The pooled head's one-pass kernel on its own (vh_op_pool_rows): mean [batch, dim] fp32 over rows lead .. tokens - 1 of every image
+    (lead 0 .. tokens - 1), FEAT_RAW or through LayerNorm(gamma, beta, eps) -- the bits op_token_features2 writes for ELEM_F32."""
+    _check(lib().vh_op_pool_rows(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, norm, mean_ptr, None))
 
 
 def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr, dtype):
