@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/clip/*.npz -- the vectors that pin tests/clip_ref.py (and through it the device) on the two CLIP
+"""Generate tests/golden/clip/*.npz -- the vectors that pin tests/vit_ref.py (and through it the device) on the two CLIP
 switches.  Three micro cases, each an independent implementation from `transformers`, built from a random config (no download),
 loaded with this repository's seeded tensors, evaluated in float64 and float32 on seeded images, layer_norm_eps = 1e-5:
   clip_both     CLIPVisionModelWithProjection, hidden_act "quick_gelu"    VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU
   clip_preln    CLIPVisionModelWithProjection, hidden_act "gelu"          VH_FLAG_PRE_LN
   vit_quick     ViTForImageClassification,     hidden_act "quick_gelu"    VH_FLAG_QUICK_GELU
-CLIP has no patch-convolution bias and no projection bias: the CLIP cases use clip_ref.make_clip_tensors (both zero), and
+CLIP has no patch-convolution bias and no projection bias: the CLIP cases use hf_state_dicts.make_clip_tensors (both zero), and
 `logits` is the model's image_embeds.  Same npz layout as make_golden_headdim.py plus `ln_eps`, `zero_bias` and the flags in
 `meta`.  CLIP's hidden_states[0] is the encoder's input, i.e. the rows AFTER pre_layrnorm: the script checks that against
-clip_ref with n_layers = 0 before it writes anything.
+vit_ref with n_layers = 0 before it writes anything.
 
 Needs torch + transformers (build container only).  Re-run:  python tests/golden/make_golden_clip.py
 """
@@ -24,8 +24,9 @@ import numpy as np
 import torch
 from transformers import CLIPVisionConfig, CLIPVisionModelWithProjection, ViTConfig, ViTForImageClassification
 
-import clip_ref as R
+import hf_state_dicts as H
 import vh_synth as S
+import vit_ref as R
 
 CFG_KEYS = ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")
 EPS = 1e-5
@@ -85,7 +86,7 @@ def main():
     os.makedirs(os.path.join(HERE, "clip"), exist_ok=True)
     for name, cfg, flags, wseed, iseed, batch, rows in CASES:
         is_clip = bool(flags & PRE)
-        tensors = R.make_clip_tensors(cfg, wseed, flags) if is_clip else R.make_tensors(cfg, wseed, flags)
+        tensors = H.make_clip_tensors(cfg, wseed, flags) if is_clip else R.make_tensors(cfg, wseed, flags)
         images = S.make_images(cfg, iseed, batch)
         nchw = torch.from_numpy(images.transpose(0, 3, 1, 2).copy())
         out = {}
@@ -112,7 +113,7 @@ def main():
                             config=np.array([cfg[k] for k in CFG_KEYS], dtype=np.int64), ln_eps=np.array(EPS),
                             zero_bias=np.array(int(is_clip)),
                             **{k: (v.astype(np.float32) if k.endswith("f32") else v) for k, v in out.items()})
-        print(name, "hidden_states[0] vs clip_ref after ln_pre:", d0, "logits f64[0,:4] =", out["logits_f64"][0, :4], "->",
+        print(name, "hidden_states[0] vs vit_ref after ln_pre:", d0, "logits f64[0,:4] =", out["logits_f64"][0, :4], "->",
               os.path.relpath(path, HERE), os.path.getsize(path), "bytes")
 
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/pool/*.npz -- the vectors that pin tests/pool_ref.py (and through it the device) on the pooled heads and
+"""Generate tests/golden/pool/*.npz -- the vectors that pin tests/vit_ref.py (and through it the device) on the pooled heads and
 on models without a class token.  Four micro cases, each an independent implementation from `transformers`, built from a random
-config (no download), eager attention, float64, loaded with this repository's seeded tensors (pool_ref.make_tensors) under the
+config (no download), eager attention, float64, loaded with this repository's seeded tensors (vit_ref.make_tensors) under the
 Hugging Face names, evaluated on seeded images, layer_norm_eps = 1e-6:
   ijepa_a      IJepaForImageClassification                 NO_CLS | POOL_AVG_NORM   shape A
-  dinov2_a     Dinov2ForImageClassification                POOL_CLS_AVG             shape A, seeded LayerScale (reg_ref.layer_scale)
+  dinov2_a     Dinov2ForImageClassification                POOL_CLS_AVG             shape A, seeded LayerScale (hf_state_dicts.layer_scale)
   dinov2reg_b  Dinov2WithRegistersForImageClassification   POOL_CLS_AVG, R = 4      shape B, seeded LayerScale
   beit_a       BeitForImageClassification                  POOL_AVG_FCNORM          shape A; use_mean_pooling, absolute positions, no
                relative positions, no LayerScale.  BEiT has no key bias: the fixture's k.bias is zero.  Its encoder's final norm is
@@ -30,8 +30,9 @@ from transformers import (BeitConfig, BeitForImageClassification, Dinov2Config, 
                           Dinov2WithRegistersConfig, Dinov2WithRegistersForImageClassification, IJepaConfig,
                           IJepaForImageClassification)
 
-import pool_ref as PR
+import hf_state_dicts as H
 import vh_synth as S
+import vit_ref as PR
 
 CFG_KEYS = ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")
 EPS = 1e-6
@@ -52,7 +53,7 @@ def beit_state_dict(cfg, t):
     sd[e + "patch_embeddings.projection.weight"], sd[e + "patch_embeddings.projection.bias"] = t["patch.weight"], t["patch.bias"]
     for l in range(cfg["layers"]):
         b = f"beit.layers.{l}."
-        for ours, theirs in PR.HF_LAYER_NAMES:
+        for ours, theirs in H.HF_LAYER_NAMES:
             sd[b + theirs + ".weight"] = t[f"l{l}.{ours}.weight"]
             if ours != "k":
                 sd[b + theirs + ".bias"] = t[f"l{l}.{ours}.bias"]
@@ -87,9 +88,9 @@ def main():
     torch.set_num_threads(8)
     os.makedirs(os.path.join(HERE, "pool"), exist_ok=True)
     for name, kind, cfg, flags, wseed, iseed, batch in CASES:
-        t = PR.fixture_tensors(kind, cfg, flags, wseed)
-        sd = {"ijepa": lambda: PR.ijepa_state_dict(cfg, t), "beit": lambda: beit_state_dict(cfg, t),
-              "dinov2": lambda: PR.dinov2_classifier_state_dict(cfg, t, wseed)}[kind]()
+        t = H.fixture_tensors(kind, cfg, flags, wseed)
+        sd = {"ijepa": lambda: H.ijepa_state_dict(cfg, t), "beit": lambda: beit_state_dict(cfg, t),
+              "dinov2": lambda: H.dinov2_classifier_state_dict(cfg, t, wseed)}[kind]()
         images = S.make_images(cfg, iseed, batch)
         m = hf_model(kind, cfg, flags, sd)
         seen = {}

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/reg/*.npz -- the vectors that pin tests/reg_ref.py (and through it the device) on register tokens.
+"""Generate tests/golden/reg/*.npz -- the vectors that pin tests/vit_ref.py (and through it the device) on register tokens.
 Two micro cases, each an independent implementation: `transformers`' Dinov2WithRegistersModel, built from a random config (no
-download), eager attention, float64, loaded with this repository's seeded tensors (reg_ref.make_tensors) under the Hugging Face
-names plus seeded, non-trivial LayerScale vectors (reg_ref.layer_scale: uniform in 0.5 .. 1.5, tensor ids 0x6000 + layer and
+download), eager attention, float64, loaded with this repository's seeded tensors (vit_ref.make_tensors) under the Hugging Face
+names plus seeded, non-trivial LayerScale vectors (hf_state_dicts.layer_scale: uniform in 0.5 .. 1.5, tensor ids 0x6000 + layer and
 0x6100 + layer of the weight seed), evaluated on seeded images, layer_norm_eps = 1e-6:
   reg4_d128   image 56, patch 14, dim 128, heads 2, mlp 256, layers 2, R = 4, batch 3
   reg1_d256   image 32, patch 8,  dim 256, heads 4, mlp 512, layers 2, R = 1, batch 2   (dim 256: the fold and split-residual path)
@@ -24,8 +24,9 @@ import numpy as np
 import torch
 from transformers import Dinov2WithRegistersConfig, Dinov2WithRegistersModel
 
-import reg_ref as R
+import hf_state_dicts as H
 import vh_synth as S
+import vit_ref as R
 
 CFG_KEYS = ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")
 EPS = 1e-6
@@ -54,7 +55,7 @@ def main():
         assert cfg["mlp_dim"] % cfg["dim"] == 0
         flags = R.FLAG_REGISTERS(regs)
         tensors = R.make_tensors(cfg, wseed, flags)
-        sd = R.dinov2_state_dict(cfg, tensors, wseed)
+        sd = H.dinov2_state_dict(cfg, tensors, wseed)
         images = S.make_images(cfg, iseed, batch)
         m = hf_model(cfg, sd, regs)
         with torch.no_grad():
@@ -63,7 +64,7 @@ def main():
         hidden = np.stack([h.numpy() for h in r.hidden_states])
         T = R.tokens(cfg, flags)
         assert last.shape == (batch, T, cfg["dim"]) and hidden.shape == (cfg["layers"] + 1, batch, T, cfg["dim"]), (last.shape, hidden.shape)
-        # the embedded rows are the ones the row order of reg_ref.assemble states (independent of the LayerScale)
+        # the embedded rows are the ones the row order of vit_ref.assemble states (independent of the LayerScale)
         x0 = R.forward(cfg, R.pack_blob(cfg, tensors, flags, EPS), images, flags, EPS, n_layers=0, want_hidden=True)[1]
         d0 = float(np.abs(x0.reshape(batch, T, -1) - hidden[0]).max())
         assert d0 < 1e-12, (name, d0)
@@ -73,7 +74,7 @@ def main():
                             last_hidden_state=last, hidden_states=hidden,
                             weights_checksum=np.array([float(v.astype(np.float64).sum()) for v in tensors.values()][:8]),
                             images_checksum=np.array([float(images.astype(np.float64).sum())]))
-        print(name, "hidden_states[0] vs reg_ref.assemble:", d0, "last[0,0,:3] =", last[0, 0, :3], "->", os.path.relpath(path, HERE),
+        print(name, "hidden_states[0] vs vit_ref.assemble:", d0, "last[0,0,:3] =", last[0, 0, :3], "->", os.path.relpath(path, HERE),
               os.path.getsize(path), "bytes")
 
 

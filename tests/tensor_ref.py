@@ -11,7 +11,6 @@ infinities included)."""
 import numpy as np
 
 import vithip
-from test_u8_input import u8_reference
 
 ELEMS = [vithip.ELEM_F32, vithip.ELEM_F16, vithip.ELEM_BF16, vithip.ELEM_U8]
 LAYOUTS = [vithip.LAYOUT_NHWC, vithip.LAYOUT_NCHW]
@@ -59,6 +58,40 @@ def widen(arr, elem):
     return (arr.astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
+def assert_norm_in_precondition(scale, shift):
+    """The bounds under which u8_reference equals the single-rounding fma exactly (tests/test_u8_input.py's docstring)."""
+    scale, shift = np.asarray(scale, dtype=np.float32), np.asarray(shift, dtype=np.float32)
+    assert np.isfinite(scale).all() and np.isfinite(shift).all()
+    assert (np.abs(scale) >= 2.0 ** -12).all() and (np.abs(scale) < 8).all(), scale
+    assert (np.abs(shift) <= 8).all(), shift
+    assert ((shift == 0) | (np.abs(shift) >= 2.0 ** -12)).all(), shift
+
+
+def u8_reference(u8, scale, shift):
+    """The fp32 array a u8 forward is defined to consume: [..., C] uint8 -> float32, x = fma(p, scale[c], shift[c])."""
+    u8 = np.asarray(u8)
+    assert u8.dtype == np.uint8
+    scale, shift = np.asarray(scale, dtype=np.float32).reshape(-1), np.asarray(shift, dtype=np.float32).reshape(-1)
+    assert scale.shape == shift.shape == (u8.shape[-1],)
+    assert_norm_in_precondition(scale, shift)
+    return (u8.astype(np.float64) * scale.astype(np.float64) + shift.astype(np.float64)).astype(np.float32)
+
+
+def make_u8_images(batch, image, channels, seed):
+    """[batch, image, image, channels] uint8: every byte value appears, 0 and 255 sit at image corners."""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 256, size=(batch, image, image, channels), dtype=np.uint8)
+    row = image * channels
+    assert row * (image - 2) >= 256
+    a.reshape(-1)[row:row + 256] = np.arange(256, dtype=np.uint8)   # image 0 from row 1 on: clear of the corners
+    a[:, 0, 0, :] = 0
+    a[:, -1, -1, :] = 255
+    a[0, 0, -1, :] = 255
+    a[0, -1, 0, :] = 0
+    assert len(np.unique(a)) == 256
+    return a
+
+
 def tensor_reference(arr, elem, layout, scale=None, shift=None):
     """The NHWC fp32 array of v for a dense tensor of `elem` in `layout` (scale / shift: [C], ELEM_U8 only)."""
     nhwc = from_layout(arr, layout)
@@ -76,7 +109,6 @@ def make_tensor(elem, batch, image, channels, seed, extremes=True):
     rng = np.random.default_rng(seed)
     shape = (batch, image, image, channels)
     if elem == vithip.ELEM_U8:
-        from test_u8_input import make_u8_images
         return make_u8_images(batch, image, channels, seed)
     x = rng.standard_normal(shape).astype(np.float32)
     if elem == vithip.ELEM_F32:

@@ -12,6 +12,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import rel
 
 vithip = pytest.importorskip("vithip")
 
@@ -69,10 +70,6 @@ def test_more_than_4097_tokens_is_still_rejected_at_patch_14():
     assert S.tokens(cfg) == 4357
     assert _blob_bytes(cfg) == 0
     assert _blob_bytes(_cfg(896, 14, 384, 6, 1536, 12)) == 64 + 4 * S.param_count(_cfg(896, 14, 384, 6, 1536, 12))   # 64 x 64
-
-
-def rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 def test_patch14_fixture_present():

@@ -1,7 +1,7 @@
 """The two CLIP switches on the host: VH_FLAG_PRE_LN and VH_FLAG_QUICK_GELU are valid flags (alone, together, with every other
 flag and dtype), the blob grows by pre_ln.weight / pre_ln.bias exactly when the first is set, the blob header carries both as
 model bits, and the new taps and epilogue codes check their arguments before they touch a device.  The reference the GPU tests
-use, tests/clip_ref.py, is pinned here: against three fixtures computed by Hugging Face `transformers` models
+use, tests/vit_ref.py, is pinned here: against three fixtures computed by Hugging Face `transformers` models
 (tests/golden/make_golden_clip.py), and, with neither switch, against the C oracle.  No GPU needed."""
 import ctypes as C
 import glob
@@ -10,9 +10,11 @@ import os
 import numpy as np
 import pytest
 
-import clip_ref as R
+import hf_state_dicts as H
 import oracle_lib as O
 import vh_synth as S
+import vit_ref as R
+from vh_testlib import rel, vit_cfg
 
 vithip = pytest.importorskip("vithip")
 
@@ -24,16 +26,12 @@ PRE, QUICK = vithip.FLAG_PRE_LN, vithip.FLAG_QUICK_GELU
 VH_ERR_INVALID, VH_ERR_UNSUPPORTED = 1, 4
 
 
-def _cfg(image, patch, dim, heads, mlp, layers, classes):
-    return dict(image_size=image, patch_size=patch, channels=3, dim=dim, heads=heads, mlp_dim=mlp, layers=layers, classes=classes)
-
-
 # the vision towers of OpenAI CLIP and LAION / OpenCLIP; classes = the width of the image embedding
-CLIP = [("vit_b32_224", _cfg(224, 32, 768, 12, 3072, 12, 512), 50),
-        ("vit_b16_224", _cfg(224, 16, 768, 12, 3072, 12, 512), 197),
-        ("vit_l14_224", _cfg(224, 14, 1024, 16, 4096, 24, 768), 257),
-        ("vit_l14_336", _cfg(336, 14, 1024, 16, 4096, 24, 768), 577),
-        ("vit_h14_224", _cfg(224, 14, 1280, 16, 5120, 32, 1024), 257)]
+CLIP = [("vit_b32_224", vit_cfg(224, 32, 768, 12, 3072, 12, 512), 50),
+        ("vit_b16_224", vit_cfg(224, 16, 768, 12, 3072, 12, 512), 197),
+        ("vit_l14_224", vit_cfg(224, 14, 1024, 16, 4096, 24, 768), 257),
+        ("vit_l14_336", vit_cfg(336, 14, 1024, 16, 4096, 24, 768), 577),
+        ("vit_h14_224", vit_cfg(224, 14, 1280, 16, 5120, 32, 1024), 257)]
 MICRO = S.CONFIGS["vit_micro"]
 
 
@@ -42,12 +40,8 @@ def _blob_bytes(cfg, flags=0, dtype=BF16, max_batch=1):
     return vithip.lib().vh_weight_blob_bytes(C.byref(c))
 
 
-def rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
 def test_the_flag_and_epilogue_constants():
-    assert (PRE, QUICK) == (16, 32)
+    assert (PRE, QUICK) == (16, 32) == (R.FLAG_PRE_LN, R.FLAG_QUICK_GELU)
     assert (vithip.EPI_BIAS_QGELU, vithip.EPI_LNFOLD_QGELU) == (10, 11)
     assert vithip.STAGES[-1] == "pre_layernorm" and vithip.STAGES.index("ln_stats") == 11
     assert vithip.lib().vh_stage_name(12) == b"pre_layernorm" and vithip.lib().vh_abi_version() == 1
@@ -80,8 +74,8 @@ def test_unknown_flag_bits_and_the_other_rules_still_hold():
     for bad in (64, 128, 1 << 20, PRE | 64, QUICK | 256, -1):
         assert _blob_bytes(cfg, bad) == 0, bad
     assert _blob_bytes(cfg, PRE | vithip.FLAG_LN_FOLD_OFF | vithip.FLAG_LN_FOLD_ON) == 0      # still exclude each other
-    assert _blob_bytes(_cfg(224, 32, 576, 8, 2304, 2, 512), PRE | QUICK) == 0                   # head dim 72
-    assert _blob_bytes(_cfg(224, 32, 320, 4, 640, 2, 512), PRE | QUICK, FP8) == 0               # fp8: multiples of 128
+    assert _blob_bytes(vit_cfg(224, 32, 576, 8, 2304, 2, 512), PRE | QUICK) == 0                   # head dim 72
+    assert _blob_bytes(vit_cfg(224, 32, 320, 4, 640, 2, 512), PRE | QUICK, FP8) == 0               # fp8: multiples of 128
 
 
 def test_layout_of_the_blob_with_the_pre_layernorm():
@@ -142,7 +136,7 @@ def test_a_file_whose_bits_do_not_match_its_size_or_are_unknown_is_refused(tmp_p
         vithip.blob_file_flags(path)
 
 
-# ---- clip_ref against independent implementations ----------------------------------------------------------------------------
+# ---- the reference against independent implementations ----------------------------------------------------------------------------
 
 def test_the_three_fixtures_are_present():
     assert [os.path.basename(p).split("_s")[0] for p in GOLDEN] == ["clip_both", "clip_preln", "vit_quick"]
@@ -155,7 +149,7 @@ def test_clip_ref_matches_the_hugging_face_fixtures(path):
     wseed, iseed, batch, flags = [int(v) for v in g["meta"]]
     eps = float(g["ln_eps"])
     assert abs(eps - 1e-5) < 1e-12 and os.path.getsize(path) < 200 * 1024
-    tensors = R.make_clip_tensors(cfg, wseed, flags) if int(g["zero_bias"]) else R.make_tensors(cfg, wseed, flags)
+    tensors = H.make_clip_tensors(cfg, wseed, flags) if int(g["zero_bias"]) else R.make_tensors(cfg, wseed, flags)
     cs = np.array([float(v.astype(np.float64).sum()) for v in tensors.values()][:8])
     assert np.allclose(cs, g["weights_checksum"], rtol=0, atol=1e-9)
     images = S.make_images(cfg, iseed, batch)
@@ -192,7 +186,7 @@ def test_clip_ref_with_no_flag_is_the_oracle():
         a, b = R.forward(cfg, blob, images, 0, 1e-6, fp8=mine), O.vit_forward(cfg, blob, images, fp8=theirs)
         # the same rounding points; a value on an e4m3 boundary falls either way (numpy and the oracle sum in different orders), so
         # the two emulations agree as two realisations of one quantisation noise: closer to each other than either is to fp32
-        print(f"\n[clip] fp8 emulation {mine}: clip_ref vs oracle {rms(a, b):.3e}, oracle vs fp32 {rms(b, ref32):.3e}")
+        print(f"\n[clip] fp8 emulation {mine}: vit_ref vs oracle {rms(a, b):.3e}, oracle vs fp32 {rms(b, ref32):.3e}")
         assert rms(a, b) <= rms(b, ref32), (mine, rms(a, b), rms(b, ref32))
         assert abs(rms(a, ref32) - rms(b, ref32)) <= 0.25 * rms(b, ref32), mine
 
@@ -224,7 +218,7 @@ def _hf_clip(cfg, act):
 
 @pytest.mark.parametrize("act,flags", [("quick_gelu", PRE | QUICK), ("gelu", PRE)], ids=["openai", "laion"])
 def test_blob_from_clip_state_dict_reproduces_the_models_image_embeds(act, flags):
-    cfg = _cfg(64, 16, 128, 2, 256, 2, 48)
+    cfg = vit_cfg(64, 16, 128, 2, 256, 2, 48)
     m, torch = _hf_clip(cfg, act)
     sd = {k: v.detach().numpy() for k, v in m.state_dict().items()}
     blob = vithip.blob_from_clip_state_dict(sd, dict(cfg, flags=flags))
@@ -239,7 +233,7 @@ def test_blob_from_clip_state_dict_reproduces_the_models_image_embeds(act, flags
 
 
 def test_blob_from_clip_state_dict_refuses_by_name():
-    cfg = _cfg(64, 16, 128, 2, 256, 1, 48)
+    cfg = vit_cfg(64, 16, 128, 2, 256, 1, 48)
     D, M = 128, 256
     sd = {"vision_model.embeddings.patch_embedding.weight": np.zeros((D, 3, 16, 16), np.float32),
           "vision_model.embeddings.class_embedding": np.zeros(D, np.float32),

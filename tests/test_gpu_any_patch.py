@@ -11,6 +11,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -34,29 +35,9 @@ VIT_B14_224 = _cfg(224, 14, 768, 12, 3072, 12, classes=1000)      # 257 tokens
 DINO_S14_518 = _cfg(518, 14, 384, 6, 1536, 12, classes=1000)      # 1370 tokens: the K/V-streaming attention
 VIT_L14_224 = _cfg(224, 14, 1024, 16, 4096, 24, classes=1000)     # 257 tokens
 
-_KEEP = []
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
-
 
 def rnd16(a, dt):
     return O.round_bf16(a) if dt == BF16 else O.round_fp16(a)
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 # ---- the operator tap ----------------------------------------------------------------------------------------------------

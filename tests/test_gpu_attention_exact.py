@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import attn_exact as X
+from vh_testlib import _release_buffers, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -24,23 +25,8 @@ HEAD_DIMS = [32, 48, 64, 80, 96, 112, 128]   # test_gpu_head_dim.HEAD_DIMS
 # test_gpu_ops.test_attention_token_counts_around_every_kernel_boundary
 BOUNDARY_T = [33, 64, 65, 96, 97, 100, 128, 129, 160, 161, 193, 200, 208, 209, 224, 225, 256, 289, 384, 385, 512, 513, 608, 609, 640]
 
-_KEEP = []
 _CASES = {}
 _WORST = {}   # (tap, type) -> worst (|d| - step * |ref|) / max|V| seen: the margin under attn_exact.EXTRA_REL
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
 
 
 @pytest.fixture(scope="module", autouse=True)

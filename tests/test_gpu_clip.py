@@ -1,6 +1,6 @@
 """GPU parity of the two CLIP switches, VH_FLAG_PRE_LN and VH_FLAG_QUICK_GELU: the QuickGELU epilogues through the GEMM taps
 (16-bit and e4m3 results), the activation itself on a dense grid against the accuracy limit stated with it in gemm_epilogue.h,
-the pre-LayerNorm kernel through its tap, whole forwards on every LayerNorm path against tests/clip_ref.py (the C oracle has
+the pre-LayerNorm kernel through its tap, whole forwards on every LayerNorm path against tests/vit_ref.py (the C oracle has
 neither switch), the fp8 statistics, the Hugging Face fixtures, bit invariance, and the CLIP ViT-B/32 / ViT-L/14 shapes.
 Tolerances are the project's own: test_gpu_vit's model bounds (fp16 1e-3, bf16 1e-2), one 16-bit ulp for operators and
 test_gpu_fp8's `1.5 x emulation + 1e-3`."""
@@ -10,9 +10,11 @@ import os
 import numpy as np
 import pytest
 
-import clip_ref as R
+import hf_state_dicts as H
 import oracle_lib as O
 import vh_synth as S
+import vit_ref as R
+from vh_testlib import _KEEP, _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -45,29 +47,9 @@ HD80 = _cfg(64, 8, 1280, 16, 2560, 2)           # the ViT-H/14 block (head dim 8
 CLIP_B32 = _cfg(224, 32, 768, 12, 3072, 12, classes=512)    # 50 tokens
 CLIP_L14 = _cfg(224, 14, 1024, 16, 4096, 24, classes=768)   # 257 tokens
 
-_KEEP = []
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
-
 
 def rnd16(a, dt):
     return O.round_bf16(a) if dt == BF16 else O.round_fp16(a)
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 def ulp_at(v, dt):
@@ -375,7 +357,7 @@ def test_clip_fixture_logits_match_the_hugging_face_fp64_logits(path):
     cfg = dict(zip(CFG_KEYS, (int(v) for v in g["config"])))
     wseed, iseed, batch, flags = [int(v) for v in g["meta"]]
     eps = float(g["ln_eps"])
-    tensors = R.make_clip_tensors(cfg, wseed, flags) if int(g["zero_bias"]) else R.make_tensors(cfg, wseed, flags)
+    tensors = H.make_clip_tensors(cfg, wseed, flags) if int(g["zero_bias"]) else R.make_tensors(cfg, wseed, flags)
     blob, images = R.pack_blob(cfg, tensors, flags, eps), S.make_images(cfg, iseed, batch)
     for dt in DT:
         got, _ = _forward(cfg, blob, images, dt, flags, eps=eps)
@@ -413,14 +395,14 @@ def test_same_bits_across_batch_streams_graph_replay_and_the_class_token_tail_to
     # the class-token tail (head dim 64, folded path): the small fc1 launch with the QuickGELU code; logits to rounding
     base, _ = _forward(cfg, blob, images, dt, flags | vithip.FLAG_LN_FOLD_ON, eps=1e-5)
     tail, _ = _forward(cfg, blob, images, dt, flags | vithip.FLAG_LN_FOLD_ON | vithip.FLAG_CLS_TAIL, eps=1e-5)
-    print(f"\n[clip] class-token tail {NAME[dt]}: tail vs full {rel(tail, base):.3e}, tail vs clip_ref {rel(tail, ref):.3e}")
+    print(f"\n[clip] class-token tail {NAME[dt]}: tail vs full {rel(tail, base):.3e}, tail vs vit_ref {rel(tail, ref):.3e}")
     assert np.isfinite(tail).all() and rel(tail, ref) <= MODEL_TOL[dt] and rel(tail, base) <= MODEL_TOL[dt]
 
 
 @pytest.mark.parametrize("dt", DT, ids=lambda d: NAME[d])
 def test_hd80_with_both_flags_and_the_tiled_hidden_activation(dt):
     # the ViT-H/14 block at depth 2 with enough rows for the persistent GEMM form: fc1's QuickGELU result leaves in the tiled
-    # layout (debug tap 3); the first images against clip_ref, the whole batch against VH_H_TILED=0, bit for bit
+    # layout (debug tap 3); the first images against vit_ref, the whole batch against VH_H_TILED=0, bit for bit
     cfg, flags, n = HD80, PRE | QUICK, 420
     blob, images = R.make_blob(cfg, 3, flags, 1e-5), S.make_images(cfg, 4, n)
     ctx = vithip.VitContext(cfg, dtype=dt, max_batch=n, flags=flags, ln_eps=1e-5)
@@ -534,7 +516,7 @@ def test_clip_shapes_against_clip_ref_fp32(name, cfg, batch):
         got_c, _ = _forward(cfg, blob_c, images, dt, flags, eps=eps)
         got_p, _ = _forward(cfg, blob_p, images, dt, 0, eps=eps)
         e_c, e_p = rel(got_c, ref_c), rel(got_p, ref_p)
-        print(f"\n[clip] {name} {NAME[dt]} b{batch}: CLIP flags vs clip_ref fp32 {e_c:.3e}; no flag vs the oracle {e_p:.3e}; ratio {e_c / e_p:.2f}")
+        print(f"\n[clip] {name} {NAME[dt]} b{batch}: CLIP flags vs vit_ref fp32 {e_c:.3e}; no flag vs the oracle {e_p:.3e}; ratio {e_c / e_p:.2f}")
         assert np.isfinite(got_c).all() and np.isfinite(got_p).all()
         assert e_c <= 1.25 * e_p, (NAME[dt], e_c, e_p)
         assert e_c <= MODEL_TOL[dt], (NAME[dt], e_c)

@@ -13,7 +13,8 @@ import features_ref as R
 import oracle_lib as O
 import vh_synth as S
 import vithip
-from test_u8_input import DEFAULT_SCALE, make_u8_images, u8_reference
+from tensor_ref import make_u8_images, u8_reference
+from test_u8_input import DEFAULT_SCALE
 
 pytestmark = pytest.mark.gpu
 

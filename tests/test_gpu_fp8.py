@@ -13,30 +13,12 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
 
 vithip = pytest.importorskip("vithip")
 FP8 = vithip.DTYPE_FP8
-_KEEP = []
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 def test_cast_is_bit_exact_e4m3_rne_saturating():

@@ -13,7 +13,9 @@ import pytest
 import frames_ref as R
 import vh_synth as S
 import vithip
-from test_u8_input import IMAGENET_MEAN, IMAGENET_STD, u8_reference
+from tensor_ref import u8_reference
+from test_u8_input import IMAGENET_MEAN, IMAGENET_STD
+from vh_testlib import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -149,8 +151,6 @@ def test_large_batch_of_small_frames_runs_tall_bands():
 
 
 # ---- the forward ---------------------------------------------------------------------------------------------------------------
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 def forward_frames_set(s):

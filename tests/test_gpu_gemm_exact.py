@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import gemm_exact as X
+from vh_testlib import _release_buffers, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -27,22 +28,7 @@ vithip = pytest.importorskip("vithip")
 E, BF16, FP16, FP8 = X.E, X.BF16, X.FP16, X.FP8
 DT = [BF16, FP16]
 GUARD = 0xA5
-_KEEP = []
 _CASES = {}
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
 
 
 def case_of(M, N, K, f8):

@@ -12,6 +12,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -40,29 +41,9 @@ HD32_D256 = _cfg(64, 8, 256, 8, 512, 2)        # 65 tokens
 HD80_D320 = _cfg(64, 16, 320, 4, 640, 2)
 VIT_H14_224 = _cfg(224, 14, 1280, 16, 5120, 32, classes=1000)   # 257 tokens
 
-_KEEP = []
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
-
 
 def rnd16(a, dt):
     return O.round_bf16(a) if dt == BF16 else O.round_fp16(a)
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 def q_scale(hd):

@@ -10,8 +10,8 @@ import pytest
 
 import features_ref as R
 import layer_features_ref as LR
-import reg_ref as RR
 import vh_synth as S
+import vit_ref as RR
 import vithip
 from layer_features_ref import Guarded
 

@@ -8,6 +8,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import _KEEP, _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -29,29 +30,9 @@ TINY_256_8 = _cfg(256, 8, 128, 2, 256, 3)      # 1025 tokens (patch 8)
 TINY_448_16 = _cfg(448, 16, 256, 4, 512, 2)    # 785 tokens
 VIT_B16_512 = _cfg(512, 16, 768, 12, 3072, 12, classes=1000)
 
-_KEEP = []
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
-
 
 def rnd16(a, dt):
     return O.round_bf16(a) if dt == BF16 else O.round_fp16(a)
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 def prescale_q(qkv, D, dt):

@@ -12,6 +12,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import _release_buffers, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -22,25 +23,6 @@ ULP = {vithip.DTYPE_BF16: 2.0 ** -8, vithip.DTYPE_FP16: 2.0 ** -11}
 
 def rnd16(a, dt):
     return O.round_bf16(a) if dt == vithip.DTYPE_BF16 else O.round_fp16(a)
-
-
-_KEEP = []
-
-
-def dev(a):
-    """Upload and keep the allocation alive until the test ends (a temporary DeviceBuffer would be
-    freed by its destructor before the kernel that reads it runs)."""
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
 
 
 def assert_close16(got, ref, dt, extra=0.0):

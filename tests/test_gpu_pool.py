@@ -11,11 +11,13 @@ import numpy as np
 import pytest
 
 import features_ref as FR
-import pool_ref as PR
-import reg_ref as R
+import hf_state_dicts as H
 import vh_synth as S
+import vit_ref as R
 from test_gpu_features import Guarded
-from test_u8_input import DEFAULT_SCALE, make_u8_images, u8_reference
+from tensor_ref import make_u8_images, u8_reference
+from test_u8_input import DEFAULT_SCALE
+from vh_testlib import _KEEP, _release_buffers, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -44,25 +46,11 @@ PATHS = {"a_bf16": (A, BF16, 0, True), "a_fp16": (A, FP16, 0, True), "a_fp8": (A
 MODES = {"avg_norm": POOL(AVG_NORM), "avg_fcnorm": POOL(AVG_FCNORM), "cls_avg": POOL(CLS_AVG),
          "nocls_avg_norm_r4": NO_CLS | POOL(AVG_NORM) | REG(4), "nocls_avg_fcnorm": NO_CLS | POOL(AVG_FCNORM)}
 
-_KEEP = []
-
 
 def dev(a):
     b = vithip.DeviceBuffer.from_numpy(np.ascontiguousarray(a))
     _KEEP.append(b)
     return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 def same_bits(a, b):
@@ -73,14 +61,14 @@ def tensors_for(cfg, flags, seed=5):
     """The seeded tensors of the class-token model with this register count, reshaped for `flags`: without `cls` and pos[0] under
     NO_CLS, with a [C][2 D] head under CLS_AVG -- so that contexts of different flags hold the SAME model otherwise."""
     t = R.make_tensors(cfg, seed, flags & R.FLAG_REGISTERS_MASK)
-    if PR.pool_of(flags) == CLS_AVG:
-        t["head.weight"] = PR.make_tensors(cfg, seed, POOL(CLS_AVG))["head.weight"]
-    return PR.without_cls(t) if flags & NO_CLS else t
+    if R.pool_of(flags) == CLS_AVG:
+        t["head.weight"] = R.make_tensors(cfg, seed, POOL(CLS_AVG))["head.weight"]
+    return R.without_cls(t) if flags & NO_CLS else t
 
 
 def context(cfg, dt, flags, max_batch=MAX_BATCH, seed=5, extra=0):
     ctx = vithip.VitContext(cfg, dtype=dt, max_batch=max_batch, flags=flags | extra, ln_eps=EPS)
-    ctx.load_weights(PR.pack_blob(cfg, tensors_for(cfg, flags, seed), flags, EPS))
+    ctx.load_weights(R.pack_blob(cfg, tensors_for(cfg, flags, seed), flags, EPS))
     return ctx
 
 
@@ -151,8 +139,8 @@ def test_split_planes_and_row_statistics_without_row_0(regs, dt, batch):
 def test_head_input_is_the_token_features_of_the_same_forward(mode, path):
     cfg, dt, lnf, planes = PATHS[path]
     flags = MODES[mode]
-    pool, D, Cn = PR.pool_of(flags), cfg["dim"], cfg["classes"]
-    W = PR.head_width(cfg, flags)
+    pool, D, Cn = R.pool_of(flags), cfg["dim"], cfg["classes"]
+    W = R.head_width(cfg, flags)
     ctx = context(cfg, dt, flags, extra=lnf)
     assert ctx.ln_fold() == planes
     t = tensors_for(cfg, flags)
@@ -234,12 +222,12 @@ def fixture(path):
         z = np.load(path)
         cfg = dict(zip(CFG_KEYS, (int(v) for v in z["config"])))
         wseed, iseed, batch, flags = (int(v) for v in z["meta"])
-        blob = PR.pack_blob(cfg, PR.fixture_tensors(str(z["kind"]), cfg, flags, wseed), flags, float(z["ln_eps"]))
+        blob = R.pack_blob(cfg, H.fixture_tensors(str(z["kind"]), cfg, flags, wseed), flags, float(z["ln_eps"]))
         if str(z["kind"]) == "dinov2":   # (the LayerScale is folded by the converter)
-            sd = PR.dinov2_classifier_state_dict(cfg, PR.fixture_tensors("dinov2", cfg, flags, wseed), wseed)
-            blob = vithip.blob_from_dinov2_state_dict(sd, dict(cfg, registers=PR.registers_of(flags)), float(z["ln_eps"]), pool=CLS_AVG)
+            sd = H.dinov2_classifier_state_dict(cfg, H.fixture_tensors("dinov2", cfg, flags, wseed), wseed)
+            blob = vithip.blob_from_dinov2_state_dict(sd, dict(cfg, registers=R.registers_of(flags)), float(z["ln_eps"]), pool=CLS_AVG)
         images = S.make_images(cfg, iseed, batch)
-        _FIX[path] = (z, cfg, flags, blob, images, float(z["ln_eps"]), PR.forward(cfg, blob, images, flags, float(z["ln_eps"]), np.float64))
+        _FIX[path] = (z, cfg, flags, blob, images, float(z["ln_eps"]), R.forward(cfg, blob, images, flags, float(z["ln_eps"]), np.float64))
     return _FIX[path]
 
 
@@ -251,10 +239,10 @@ def test_fixtures_are_present():
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p).split("_s")[0] for p in GOLDEN])
 def test_fixture_logits_and_head_inputs(path, dt):
     z, cfg, flags, blob, images, eps, _ = fixture(path)
-    ctx = vithip.VitContext(dict(cfg, registers=PR.registers_of(flags)), dtype=dt, max_batch=len(images), flags=flags & ~R.FLAG_REGISTERS_MASK, ln_eps=eps)
+    ctx = vithip.VitContext(dict(cfg, registers=R.registers_of(flags)), dtype=dt, max_batch=len(images), flags=flags & ~R.FLAG_REGISTERS_MASK, ln_eps=eps)
     ctx.load_weights(blob)
     got = ctx.forward(images)
-    tap = ctx.debug_read(1, len(images) * PR.head_width(cfg, flags)).reshape(len(images), -1)
+    tap = ctx.debug_read(1, len(images) * R.head_width(cfg, flags)).reshape(len(images), -1)
     ctx.close()
     e_l, e_h = rel(got, z["logits"]), rel(tap, z["head_input"])
     print(f"\n[pool] {os.path.basename(path).split('_s')[0]} {NAME[dt]}: logits {e_l:.3e} head input {e_h:.3e} (bound {MODEL_TOL[dt]:g})")
@@ -267,12 +255,12 @@ def test_fp8_forwards_track_the_emulation(path):
     z, cfg, flags, blob, images, eps, ref64 = fixture(path)
     ref32 = ref64.astype(np.float32)
     rms = lambda a, b: float(np.sqrt(np.mean((a - b) ** 2)) / np.sqrt(np.mean(b ** 2)))
-    ctx = vithip.VitContext(dict(cfg, registers=PR.registers_of(flags)), dtype=FP8, max_batch=len(images), flags=flags & ~R.FLAG_REGISTERS_MASK, ln_eps=eps)
+    ctx = vithip.VitContext(dict(cfg, registers=R.registers_of(flags)), dtype=FP8, max_batch=len(images), flags=flags & ~R.FLAG_REGISTERS_MASK, ln_eps=eps)
     ctx.load_weights(blob)
     got, folded = ctx.forward(images), ctx.ln_fold()
-    tap = ctx.debug_read(1, len(images) * PR.head_width(cfg, flags)).reshape(len(images), -1)
+    tap = ctx.debug_read(1, len(images) * R.head_width(cfg, flags)).reshape(len(images), -1)
     ctx.close()
-    emu, emu_h = PR.forward(cfg, blob, images, flags, eps, fp8="folded" if folded else "plain", want_head=True)
+    emu, emu_h = R.forward(cfg, blob, images, flags, eps, fp8="folded" if folded else "plain", want_head=True)
     assert np.isfinite(got).all() and np.isfinite(tap).all()
     # the same criterion for the logits and for the head's input, each against its own fixture vector
     for what, g, e, ref in (("logits", got, emu, ref32), ("head input", tap, emu_h, z["head_input"].astype(np.float32))):
@@ -298,7 +286,7 @@ def test_same_logit_bits_alone_in_a_batch_across_streams_and_graph_replay(mode):
     assert same_bits(ctx.forward(images[1:4]), five[1:4])
     ctx.set_streams(2)
     assert same_bits(ctx.forward(images), five)
-    W = PR.head_width(A, flags)
+    W = R.head_width(A, flags)
     tap = ctx.debug_read(1, 5 * W)                                                    # the parts wrote their own slices of the head's input
     ctx.set_streams(1)
     ctx.forward(images)
@@ -344,11 +332,11 @@ def test_a_blob_with_other_pool_or_class_token_bits_is_refused(mode, tmp_path):
     bits 15 or 16 .. 17 differ from the context's is refused with the bit's own message, through vh_load_weights and
     vh_load_weights_file, and the refused loads change nothing."""
     flags = {"avg_norm": POOL(AVG_NORM), "nocls_avg_fcnorm_r4": NO_CLS | POOL(AVG_FCNORM) | REG(4)}[mode]
-    cfg, pool, regs = B, PR.pool_of(flags), flags & R.FLAG_REGISTERS_MASK
+    cfg, pool, regs = B, R.pool_of(flags), flags & R.FLAG_REGISTERS_MASK
     ctx = vithip.VitContext(cfg, dtype=FP16, max_batch=2, flags=flags, ln_eps=EPS)
     ctx.init_weights_seeded(17)
     blob = ctx.export_weights()
-    assert np.array_equal(blob, PR.make_blob(cfg, 17, flags))                         # the seeded tensors keep their ids; the bits in the header
+    assert np.array_equal(blob, R.make_blob(cfg, 17, flags))                         # the seeded tensors keep their ids; the bits in the header
     path, bad = str(tmp_path / "m.vhblob"), str(tmp_path / "forged.vhblob")
     ctx.save_weights_file(path)
     assert vithip.blob_file_flags(path) == flags
@@ -369,7 +357,7 @@ def test_a_blob_with_other_pool_or_class_token_bits_is_refused(mode, tmp_path):
             ctx.load_weights_file(bad)
     sizes = [regs | POOL(CLS_AVG), regs | POOL(AVG_NORM) if flags & NO_CLS else regs | NO_CLS | POOL(AVG_NORM)]
     for f in sizes:                                                                   # another size: a [C][2 D] head, a class token more / less
-        other = PR.make_blob(cfg, 17, f)
+        other = R.make_blob(cfg, 17, f)
         assert other.nbytes != blob.nbytes
         with pytest.raises(vithip.VhError, match="bytes"):
             ctx.load_weights(other)

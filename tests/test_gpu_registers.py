@@ -1,6 +1,6 @@
 """GPU suite of the register tokens (include/vithip.h, VH_FLAG_REGISTERS): the token assembly bit for bit -- through a context
 after zero layers (the fp32 rows of every path) and through the two taps for the split planes and their row statistics --, whole
-models against the Hugging Face fixtures and tests/reg_ref.py on every LayerNorm path, the token features shifted by R, the
+models against the Hugging Face fixtures and tests/vit_ref.py on every LayerNorm path, the token features shifted by R, the
 other routes into a forward (batch split, streams, graph replay, 8-bit ring, tensors, torch), the class-token tail, the
 pre-LayerNorm, a real DINOv2-S/14-reg shape and the refusals.  Tolerances are the project's own: test_gpu_vit's model bounds
 (fp16 1e-3, bf16 1e-2) and test_gpu_fp8's `1.5 x emulation + 1e-3`; everything else is equality of bits."""
@@ -14,9 +14,12 @@ import numpy as np
 import pytest
 
 import features_ref as FR
-import reg_ref as R
+import hf_state_dicts as H
 import vh_synth as S
-from test_u8_input import DEFAULT_SCALE, make_u8_images, u8_reference
+import vit_ref as R
+from tensor_ref import make_u8_images, u8_reference
+from test_u8_input import DEFAULT_SCALE
+from vh_testlib import _KEEP, _release_buffers, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -43,25 +46,11 @@ D256 = _cfg(32, 8, 256, 4, 512, 2)           # dims multiples of 256: fold + spl
 MODELS = {"d128": D128, "d256": D256}
 DINO_S14_REG = _cfg(224, 14, 384, 6, 1536, 12, classes=1000)   # 256 patches + class token + 4 registers = 261 tokens
 
-_KEEP = []
-
 
 def dev(a):
     b = vithip.DeviceBuffer.from_numpy(np.ascontiguousarray(a))
     _KEEP.append(b)
     return b
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    for b in _KEEP:
-        b.free()
-    _KEEP.clear()
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 def bits(a):
@@ -206,7 +195,7 @@ def load_fixture(path):
     cfg = dict(zip(CFG_KEYS, (int(v) for v in z["config"])))
     wseed, iseed, batch, regs = (int(v) for v in z["meta"])
     t = R.make_tensors(cfg, wseed, REG(regs))
-    sd = R.dinov2_state_dict(cfg, t, wseed)
+    sd = H.dinov2_state_dict(cfg, t, wseed)
     mcfg = dict(cfg, registers=regs)
     blob = vithip.blob_from_dinov2_state_dict(sd, mcfg, float(z["ln_eps"]), head=(t["head.weight"], t["head.bias"]))
     return z, cfg, mcfg, regs, blob, S.make_images(cfg, iseed, batch), float(z["ln_eps"])
@@ -341,7 +330,7 @@ def test_same_logit_bits_through_the_u8_ring_and_an_nchw_tensor(model):
 TORCH_SCRIPT = r"""
 import torch                      # before libvithip.so is loaded: one HIP runtime in the process (INTEGRATION.md)
 import numpy as np
-import reg_ref as R, vh_synth as S, vithip
+import vh_synth as S, vit_ref as R, vithip
 cfg = dict(image_size=32, patch_size=8, channels=3, dim=256, heads=4, mlp_dim=512, layers=2, classes=40, registers=4)
 ctx = vithip.VitContext(cfg, dtype=vithip.DTYPE_FP16, max_batch=3)
 ctx.load_weights(R.make_blob(cfg, 5, R.FLAG_REGISTERS(4)))
@@ -380,7 +369,7 @@ def test_class_token_tail_with_registers_agrees_to_the_model_bound(dt):
         outs.append(ctx.forward(images))
         ctx.close()
     base, tail = outs
-    print(f"\n[reg] class-token tail {NAME[dt]}: tail vs full {rel(tail, base):.3e}, tail vs reg_ref {rel(tail, ref):.3e}")
+    print(f"\n[reg] class-token tail {NAME[dt]}: tail vs full {rel(tail, base):.3e}, tail vs vit_ref {rel(tail, ref):.3e}")
     assert np.isfinite(tail).all() and not np.array_equal(tail, base)     # (another attention kernel: rounding, not bits)
     assert rel(tail, ref) <= MODEL_TOL[dt] and rel(tail, base) <= MODEL_TOL[dt] and rel(base, ref) <= MODEL_TOL[dt]
 

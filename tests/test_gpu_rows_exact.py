@@ -19,20 +19,13 @@ import numpy as np
 import pytest
 
 import rows_exact as X
+from vh_testlib import _KEEP, dev
 
 pytestmark = pytest.mark.gpu
 
 vithip = pytest.importorskip("vithip")
 BF16, FP16, FP8, F32 = X.BF16, X.FP16, X.FP8, X.F32
 ESZ = {BF16: 2, FP16: 2, FP8: 1, F32: 4}
-
-_KEEP = []
-
-
-def dev(a):
-    b = vithip.DeviceBuffer.from_numpy(a)
-    _KEEP.append(b)
-    return b
 
 
 def release():

@@ -15,6 +15,7 @@ import vh_synth as S
 import vithip
 from test_gpu_u8_input import FORWARD_CASES, OP_SHAPES, norm_for
 from test_u8_input import DEFAULT_SCALE, gather_patches
+from vh_testlib import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +26,6 @@ DTNAME = {vithip.DTYPE_BF16: "bf16", vithip.DTYPE_FP16: "fp16", vithip.DTYPE_FP8
 KINDS = [(e, l) for l in R.LAYOUTS for e in R.ELEMS]                      # all 8 (elem, layout) pairs
 KIND_ID = [f"{R.ELEM_NAME[e]}-{R.LAYOUT_NAME[l]}" for e, l in KINDS]
 VH_ERR_INVALID, VH_ERR_STATE, VH_ERR_RING_FULL, VH_ERR_RING_EMPTY = 1, 3, 6, 7
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 # ---- 1. the operator, bit for bit -------------------------------------------------------------------------------------------------

@@ -9,7 +9,9 @@ import pytest
 
 import vh_synth as S
 import vithip
-from test_u8_input import DEFAULT_SCALE, IMAGENET_MEAN, IMAGENET_STD, gather_patches, make_u8_images, u8_reference
+from tensor_ref import make_u8_images, u8_reference
+from test_u8_input import DEFAULT_SCALE, IMAGENET_MEAN, IMAGENET_STD, gather_patches
+from vh_testlib import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -118,10 +120,6 @@ def micro():
     ref.setflags(write=False)
     yield ctx, cfg, u8, ref
     ctx.close()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 # ---- 3. device entry points and streams -------------------------------------------------------------------------------------

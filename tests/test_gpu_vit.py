@@ -21,6 +21,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import rel
 
 pytestmark = pytest.mark.gpu
 
@@ -31,10 +32,6 @@ NAME = {vithip.DTYPE_FP16: "fp16", vithip.DTYPE_BF16: "bf16"}
 DT_PARAMS = [pytest.param(vithip.DTYPE_FP16, id="fp16-north_star_1e-3"),
              pytest.param(vithip.DTYPE_BF16, id="bf16-outside_north_star_tolerance-bound_1e-2")]
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def rel(got, ref):
-    return float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 @pytest.mark.parametrize("dt", DT_PARAMS)

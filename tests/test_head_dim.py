@@ -13,6 +13,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import rel
 
 vithip = pytest.importorskip("vithip")
 
@@ -117,10 +118,6 @@ def test_attention_hd_tap_checks_its_arguments_on_the_host():
     for args in bad:
         with pytest.raises(vithip.VhError):
             op(*args)
-
-
-def rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 def test_headdim_fixtures_present():

@@ -16,13 +16,10 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+from vh_testlib import rel
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = sorted(glob.glob(os.path.join(HERE, "golden", "*.npz")))
-
-
-def rel(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 def test_golden_fixtures_present():

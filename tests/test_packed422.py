@@ -11,6 +11,7 @@ import pytest
 import packed422_ref as P
 import vithip
 from test_yuv_planar import OP_CASES
+from vh_testlib import last_error
 
 VH_ERR_INVALID = 1
 # (h, w, box, S) of the packed taps, shared with the GPU suite and tools/yuv_host_check.py: the planar operator cases, the widths
@@ -21,10 +22,6 @@ PACKED_CASES = dict(OP_CASES, **{f"w{w}_5x{w}_16": (5, w, None, 16) for w in (1,
                     left_last_chroma_37x53_32=(37, 53, (10.5, 0.25, 53.0, 36.5), 32),
                     left_last_chroma_38x54_32=(38, 54, (10.5, 0.25, 54.0, 37.5), 32))
 V210_WIDTHS = (1, 5, 6, 7, 11, 12, 13, 53, 54, 1918)
-
-
-def last_error():
-    return vithip.lib().vh_last_error(None).decode()
 
 
 def row_of(w, layout, sample_bytes):

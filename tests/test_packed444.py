@@ -11,6 +11,7 @@ import pytest
 import packed444_ref as P
 import vithip
 from test_yuv_planar import OP_CASES
+from vh_testlib import last_error
 
 VH_ERR_INVALID = 1
 # (h, w, box, S) of the packed taps, shared with the GPU suite and tools/yuv_host_check.py: the planar operator cases, the widths
@@ -20,10 +21,6 @@ PACKED_CASES = dict(OP_CASES, **{f"w{w}_5x{w}_16": (5, w, None, 16) for w in (1,
                     fractional_box_37x53_32=(37, 53, (10.5, 0.25, 52.75, 36.5), 32),
                     upscale_9x11_32=(9, 11, (1.0, 0.5, 10.0, 8.5), 32))
 HDR = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vithip.h")).read()
-
-
-def last_error():
-    return vithip.lib().vh_last_error(None).decode()
 
 
 def row_of(w, layout, sample_bytes):

@@ -11,6 +11,7 @@ import pytest
 
 import tensor_ref as R
 import vithip
+from vh_testlib import last_error
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VH_ERR_INVALID = 1
@@ -98,8 +99,6 @@ def test_specials_round_differently_to_the_two_operand_types():
 
 
 # ---- refusals that need no device -------------------------------------------------------------------------------------------------
-def last_error():
-    return vithip.lib().vh_last_error(None).decode()
 
 
 GOOD = dict(in_dev=4096, elem=vithip.ELEM_F16, layout=vithip.LAYOUT_NCHW, batch=1, image=32, patch=16, channels=3, kpad=768,

@@ -3,7 +3,7 @@ and a numpy statement of the contract
 
     x = fmaf((float)p, scale[c], shift[c])            one rounding
 
-which the GPU suite (test_gpu_u8_input.py) imports as its reference array.
+(tensor_ref.u8_reference) which the GPU suite (test_gpu_u8_input.py) imports as its reference array.
 
 Why float64 numpy states it exactly: p has 8 significant bits and a float32 scale 24, so the float64 product p * scale is
 exact (32 bits).  Adding the float32 shift is exact in float64 when every bit of both terms lies inside one 53-bit window:
@@ -20,44 +20,11 @@ import pytest
 
 import vh_synth as S
 import vithip
+from tensor_ref import assert_norm_in_precondition, make_u8_images, u8_reference
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
 DEFAULT_SCALE = np.float32(1.0 / 255.0)
-
-
-def assert_norm_in_precondition(scale, shift):
-    """The bounds under which u8_reference equals the single-rounding fma exactly (module docstring)."""
-    scale, shift = np.asarray(scale, dtype=np.float32), np.asarray(shift, dtype=np.float32)
-    assert np.isfinite(scale).all() and np.isfinite(shift).all()
-    assert (np.abs(scale) >= 2.0 ** -12).all() and (np.abs(scale) < 8).all(), scale
-    assert (np.abs(shift) <= 8).all(), shift
-    assert ((shift == 0) | (np.abs(shift) >= 2.0 ** -12)).all(), shift
-
-
-def u8_reference(u8, scale, shift):
-    """The fp32 array a u8 forward is defined to consume: [..., C] uint8 -> float32, x = fma(p, scale[c], shift[c])."""
-    u8 = np.asarray(u8)
-    assert u8.dtype == np.uint8
-    scale, shift = np.asarray(scale, dtype=np.float32).reshape(-1), np.asarray(shift, dtype=np.float32).reshape(-1)
-    assert scale.shape == shift.shape == (u8.shape[-1],)
-    assert_norm_in_precondition(scale, shift)
-    return (u8.astype(np.float64) * scale.astype(np.float64) + shift.astype(np.float64)).astype(np.float32)
-
-
-def make_u8_images(batch, image, channels, seed):
-    """[batch, image, image, channels] uint8: every byte value appears, 0 and 255 sit at image corners."""
-    rng = np.random.default_rng(seed)
-    a = rng.integers(0, 256, size=(batch, image, image, channels), dtype=np.uint8)
-    row = image * channels
-    assert row * (image - 2) >= 256
-    a.reshape(-1)[row:row + 256] = np.arange(256, dtype=np.uint8)   # image 0 from row 1 on: clear of the corners
-    a[:, 0, 0, :] = 0
-    a[:, -1, -1, :] = 255
-    a[0, 0, -1, :] = 255
-    a[0, -1, 0, :] = 0
-    assert len(np.unique(a)) == 256
-    return a
 
 
 def gather_patches(x, patch, kpad):

@@ -13,6 +13,7 @@ import yuv16_ref as W
 import yuv_ref as Y
 from test_nv12 import make_rgb
 from test_yuv_planar import OP_CASES, SUBS
+from vh_testlib import last_error
 
 VH_ERR_INVALID = 1
 # name -> (standard, full_range, bits, msb_aligned, chroma_site)
@@ -26,10 +27,6 @@ def make_yuv16(h, w, sub, seed, colour):
     """(Y, U, V) uint16 planes of a synthetic picture (test_nv12.make_rgb) in the format of COLOURS16[colour]."""
     std, full, bits, msb, _ = COLOURS16[colour]
     return W.rgb_to_yuv16_planes(make_rgb(h, w, seed), *sub, bits, msb, std, full)
-
-
-def last_error():
-    return vithip.lib().vh_last_error(None).decode()
 
 
 # ---- the matrix -----------------------------------------------------------------------------------------------------------------

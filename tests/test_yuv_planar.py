@@ -10,6 +10,7 @@ import nv12_ref as N
 import vithip
 import yuv_ref as Y
 from test_nv12 import make_nv12, make_rgb
+from vh_testlib import last_error
 
 VH_ERR_INVALID = 1
 COLOURS = {"bt709_limited_left": (N.BT709, False, N.CHROMA_LEFT), "bt601_full_centre": (N.BT601, True, N.CHROMA_CENTER)}
@@ -31,10 +32,6 @@ OP_CASES = {
 def make_yuv(h, w, sub, seed):
     """(Y, U, V) planes of a synthetic picture (test_nv12.make_rgb) at sub = (sub_x, sub_y), any h and w."""
     return Y.rgb_to_yuv_planes(make_rgb(h, w, seed), *sub)
-
-
-def last_error():
-    return vithip.lib().vh_last_error(None).decode()
 
 
 # ---- refusals without a device --------------------------------------------------------------------------------------------------
