@@ -890,6 +890,77 @@ int vh_read_layer_features(vh_ctx* ctx, const vh_layer_features* out_host);
 int vh_read_layer_features_device(vh_ctx* ctx, const vh_layer_features* out_dev);
 int vh_read_layer_features_device_async(vh_ctx* ctx, const vh_layer_features* out_dev);
 
+/* ---- Attention maps --------------------------------------------------------------------------
+ * Where the model looked: the softmax rows of the class token (DINO's get_last_selfattention, class-attention token pruning) and of
+ * the register tokens, per head, for SEVERAL layers of ONE forward -- Hugging Face's attentions[k - 1][:, :, :Q, :].  The attention
+ * kernels keep their probabilities on chip; a listed layer runs one more small kernel behind its q|k|v projection that computes
+ * these rows on their own.  Capture is a push, the read-out a pull, as with "Layer features".
+ *
+ * THE LIST.  vh_set_attention_layers(ctx, layers, n, queries): n <= VH_MAX_ATTENTION_LAYERS entries, strictly ascending, each
+ * 1 .. cfg.layers; entry k = the attention of the k-th encoder layer.  queries: VH_ATTN_Q_CLS = row 0 only (Q = 1; refused on a
+ * VH_FLAG_NO_CLS context), VH_ATTN_Q_LEAD = every leading row, the class token and the registers (Q = 1 + R, or R without a class
+ * token; refused where there is none).  n == 0 clears the list and frees the store.  The call waits for the context's stream,
+ * drops the cached graphs and allocates ONE store [n][max_batch][heads][Q][tokens] of fp32 in 256-byte aligned slots: ViT-B/16 at
+ * max_batch 512, Q = 1: 4.8 MB per layer.  When the allocation fails the call returns VH_ERR_HIP and the previous list stays in
+ * force.  vh_get_attention_layers reads the list back (layers: room for VH_MAX_ATTENTION_LAYERS ints, or NULL; queries may be NULL).
+ *
+ * CAPTURE.  Every forward enqueued while a list is set runs, behind the q|k|v projection of every listed layer it reaches, one
+ * launch per batch part on that part's stream, captured into graphs like every other launch, inside the profile event of the
+ * attention stage.  It reads the q rows of the Q queries and the K third of q|k|v once, in the layout the part holds them.  With an
+ * empty list a forward enqueues exactly what it enqueued before this section existed; with any list the logits keep their bits.
+ *
+ * ARITHMETIC, for bits.  q arrives scaled by head_dim^-1/2 * log2(e), so everything is in the exp2 domain.  For query r, key t of
+ * one (image, head):
+ *   s[t] = the fp32 dot product q_r . k_t: per 8-column chunk an fmaf chain in ascending column order from 0, the chunks added by an
+ *          xor butterfly (1, 2, 4, 8) over the next power of two of head_dim / 8 lanes, absent chunks being 0 -- a function of
+ *          head_dim alone;
+ *   m = max_t s[t];  e[t] = exp2(s[t] - m) by v_exp_f32, arguments below -126 as exp2(x + 64) * 2^-64 (denormals are kept);
+ *   l = sum_t e[t]: lane i of 64 adds t = i, i + 64, ... in ascending order from 0, then the xor butterfly 32, 16, .., 1 -- a function
+ *          of tokens alone;
+ *   p[t] = e[t] / l, the IEEE fp32 division.
+ * An image's map therefore has the same bits whatever the batch, the batch part and stream, the q|k|v layout, eager or graph replay.
+ *
+ * READ-OUT.  vh_attention_maps, of the LAST forward; B = its batch (vh_attention_dims), H = cfg.heads:
+ *   probs      [B][H][Q][K] or NULL;  head_mean [B][Q][K] or NULL: (((0 + p[h=0]) + p[1]) + ... + p[H-1]) * (float)(1.0 / H), plain fp32
+ *              adds of the unrounded values in ascending head order (the serial-chain convention of the token features' mean).
+ *   elem       VH_ELEM_F32, or VH_ELEM_F16 / VH_ELEM_BF16 = the round-to-nearest-even of exactly the fp32 value.
+ *   layer      -1 = cfg.layers, or 1 .. cfg.layers: it must have been in the list when the last forward was enqueued, and that
+ *              forward must have reached it (vh_debug_set_layers).
+ *   keys       VH_ATTN_KEYS_ALL: K = tokens.  VH_ATTN_KEYS_PATCH: K = NP, key columns lead .. tokens - 1 (lead = the leading rows), so
+ *              probs is [B][H][Q][gh][gw] as it lies (DINO's attentions[:, :, 0, 1:] reshaped).  The values are NOT renormalised.
+ * vh_read_attention writes host buffers (staged through activation scratch) and waits; _device enqueues on the context's stream and
+ * waits; _device_async only enqueues.  Device pointers are 16-byte aligned.
+ *
+ * REFUSED, each with a message of its own, nothing enqueued and no output touched.  VH_ERR_INVALID: a null context or descriptor;
+ * both pointers NULL; elem, keys or layer outside their values; reserved != 0; a device pointer that is not 16-byte aligned.
+ * VH_ERR_UNSUPPORTED: a VH_FLAG_CLS_TAIL context, whose last layer runs another attention kernel (vh_set_attention_layers too).
+ * VH_ERR_STATE: a ring exists; no forward has run; the layer was not in the list when the last forward was enqueued; the last
+ * forward did not reach it.  vh_set_attention_layers: VH_ERR_INVALID for a null context, a bad count, a list that is not strictly
+ * ascending within 1 .. cfg.layers, a queries value that is neither constant or that the context has no rows for; VH_ERR_STATE
+ * while a ring exists.
+ * Not covered: all-query maps [tokens][tokens] (attention rollout), rings, device groups. */
+#define VH_MAX_ATTENTION_LAYERS 64
+#define VH_ATTN_Q_CLS 0      /* the class token's row                                      */
+#define VH_ATTN_Q_LEAD 1     /* every leading row: the class token and the register tokens */
+#define VH_ATTN_KEYS_ALL 0   /* all `tokens` key columns                                   */
+#define VH_ATTN_KEYS_PATCH 1 /* the NP patch columns                                       */
+typedef struct vh_attention_maps { /* sizeof == 32: probs 0, head_mean 8, elem 16, layer 20, keys 24, reserved 28 */
+    void* probs;          /* [batch][heads][Q][K] or NULL: not wanted */
+    void* head_mean;      /* [batch][Q][K]        or NULL             */
+    int32_t elem;         /* VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16 */
+    int32_t layer;        /* -1 / cfg.layers: the last layer; 1 .. cfg.layers: a listed layer */
+    int32_t keys;         /* VH_ATTN_KEYS_ALL or VH_ATTN_KEYS_PATCH   */
+    int32_t reserved;     /* 0 */
+} vh_attention_maps;
+int vh_set_attention_layers(vh_ctx* ctx, const int* layers, int n, int queries);
+int vh_get_attention_layers(const vh_ctx* ctx, int* layers, int* n, int* queries);
+/* any of the five may be NULL; *batch = 0 before the first forward; *queries = the Q of the list in force (0: none);
+ * *tokens = all key columns, *patches = NP */
+int vh_attention_dims(const vh_ctx* ctx, int* batch, int* heads, int* queries, int* tokens, int* patches);
+int vh_read_attention(vh_ctx* ctx, const vh_attention_maps* out_host);
+int vh_read_attention_device(vh_ctx* ctx, const vh_attention_maps* out_dev);
+int vh_read_attention_device_async(vh_ctx* ctx, const vh_attention_maps* out_dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1085,6 +1156,19 @@ int vh_op_attention_cls(const void* qkv16_dev, int batch, int tokens, int heads,
  * run a ring form or with an odd head count, head-major input without the tiled output, in_hm_rows < batch*tokens. */
 int vh_op_attention_layout(const void* qkv16_dev, int batch, int tokens, int heads, void* out16_dev,
                            int dtype, int out_tiled, int64_t in_hm_rows, void* stream);
+/* The capture kernel of "Attention maps" on its own: the softmax rows of the first `queries` (1..17, <= tokens) rows of every image
+ * -> probs_f32 [batch][heads][queries][tokens], by the arithmetic stated there.  qkv16 is row-major [batch*tokens, 3*heads*head_dim]
+ * (in_hm_rows == 0; head_dim 32, 48, ..., 128) or head-major [3][heads][in_hm_rows][64] (head_dim 64, in_hm_rows >= batch*tokens), q
+ * pre-scaled by head_dim^-1/2 * log2(e); tokens 1..4097, heads*head_dim <= 2048, dtype VH_DTYPE_BF16 or VH_DTYPE_FP16, both pointers
+ * 16-byte aligned.  Nothing outside [b][h][r][0 .. tokens) is written.  Every other argument is VH_ERR_INVALID, with a message of its
+ * own, before a device is touched. */
+int vh_op_attention_probs(const void* qkv16_dev, int batch, int tokens, int heads, int head_dim, int queries, int64_t in_hm_rows,
+                          int dtype, float* probs_f32_dev, void* stream);
+/* The read-out kernel of "Attention maps" on its own: store_f32 [batch][heads][queries][tokens] -> probs_out [batch][heads][queries][K]
+ * and / or head_mean_out [batch][queries][K] (either may be NULL, not both) in `elem`; keys VH_ATTN_KEYS_ALL: K = tokens,
+ * VH_ATTN_KEYS_PATCH: K = tokens - lead, columns lead .. tokens - 1 (lead 0 .. tokens-1).  Pointers 16-byte aligned. */
+int vh_op_attention_readout(const float* store_f32_dev, int batch, int heads, int queries, int tokens, int lead, int elem, int keys,
+                            void* probs_out_dev, void* head_mean_out_dev, void* stream);
 /* NHWC fp32 images -> patch matrix [batch*np, patch*patch*channels] in `dtype` */
 int vh_op_im2col(const float* in_nhwc_dev, int batch, int image, int patch, int channels,
                  void* out16_dev, int dtype, void* stream);

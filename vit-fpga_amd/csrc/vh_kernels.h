@@ -98,6 +98,21 @@ constexpr int kAttnHdMaxWidth = 2048;
 bool attention_hd_supported(int head_dim);
 hipError_t launch_attention_hd(const void* qkv16, int batch, int tokens, int heads, int head_dim, void* out16, int dtype,
                                hipStream_t stream);
+// Attention maps (kernels_attn_maps.hip; contract: vithip.h, "Attention maps").  launch_attention_probs: the softmax rows of the first
+// Q queries of every (image, head) -> probs [batch][heads][Q][tokens] fp32, from the q|k|v a projection wrote: row-major
+// [batch*tokens][3*heads*head_dim] (in_hm_rows == 0; head dims 32, 48, ..., 128) or head-major [3][heads][in_hm_rows][64] (head dim 64);
+// bf16 / fp16 elements, q pre-scaled by attention_q_scale.  tokens 1..kAttnStreamMaxTokens, Q 1..min(kAttnMapsMaxQueries, tokens),
+// heads * head_dim <= kAttnHdMaxWidth.  The raw scores are staged in probs itself: no LDS, no other scratch.
+// launch_attention_readout: such a store -> probs_out [batch][heads][Q][K] and / or mean_out [batch][Q][K] (the serial fp32 chain over
+// ascending heads, times (float)(1.0 / heads)) in `elem` (VH_ELEM_F32 / F16 / BF16); keys VH_ATTN_KEYS_ALL: K = tokens,
+// VH_ATTN_KEYS_PATCH: columns lead .. tokens - 1.  The *_check functions: nullptr, or why the launch is refused; host arithmetic only.
+constexpr int kAttnMapsMaxQueries = 17;   // the class token + up to 16 register tokens
+const char* attention_probs_check(int64_t in_hm_rows, int batch, int tokens, int heads, int head_dim, int Q, int dtype);
+hipError_t launch_attention_probs(const void* qkv16, int64_t in_hm_rows, int batch, int tokens, int heads, int head_dim, int Q, int dtype,
+                                  float* probs, hipStream_t stream);
+const char* attention_readout_check(int batch, int heads, int Q, int tokens, int lead, int elem, int keys);
+hipError_t launch_attention_readout(const float* store, int batch, int heads, int Q, int tokens, int lead, int elem, int keys, void* probs_out,
+                                    void* mean_out, hipStream_t stream);
 // the factor folded into Wq and bq: head_dim^-1/2 * log2(e); exactly kAttnQScale at head dim 64
 inline float attention_q_scale(int head_dim) {
     return head_dim == 64 ? kAttnQScale : (float)(1.4426950408889634 / __builtin_sqrt((double)head_dim));

@@ -308,6 +308,13 @@ struct vh_ctx {
     char* feat_store = nullptr;
     size_t feat_slot = 0;
     int cap_layers[VH_MAX_FEATURE_LAYERS] = {0}, cap_n = 0, cap_nl = -1, cap_form = VH_FEAT_FORM_F32;
+    // Attention maps (vh_set_attention_layers): the listed layers, the query rows Q of the list (attn_q; attn_mode = VH_ATTN_Q_*) and
+    // ONE store of fp32 probabilities, a slot of attn_slot bytes = [max_batch][heads][Q][T] per listed layer in list order.  What the
+    // LAST forward captured (enqueue_forward records it; the list call clears it): acap_n listed layers acap_layers[], acap_nl = layers it ran.
+    int attn_layers[VH_MAX_ATTENTION_LAYERS] = {0}, attn_n = 0, attn_q = 0, attn_mode = VH_ATTN_Q_CLS;
+    char* attn_store = nullptr;
+    size_t attn_slot = 0;
+    int acap_layers[VH_MAX_ATTENTION_LAYERS] = {0}, acap_n = 0, acap_nl = -1;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
     struct RingSlot {
         float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;   // h_in / d_in hold bytes in a u8 ring
@@ -632,6 +639,21 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         }
         return VH_OK;
     };
+    // Attention maps: behind the q|k|v projection of layer l, when l + 1 is listed, the softmax rows of this part's first attn_q
+    // queries go to the store at the part's image offset -- one launch, from the layout this part holds (hm_rows != 0: head-major).
+    // Head-major layout and rows_g are this part's own, which is why the capture is a push from here and not a later read of q|k|v.
+    c->acap_nl = nl;
+    c->acap_n = c->attn_n;
+    for (int i = 0; i < c->acap_n; ++i) c->acap_layers[i] = c->attn_layers[i];
+    auto capture_attention = [&](int l, int64_t hm_rows) -> int {
+        if (!c->attn_store) return VH_OK;
+        for (int i = 0; i < c->attn_n; ++i) {
+            if (c->attn_layers[i] != l + 1) continue;
+            float* const slot = (float*)(c->attn_store + (size_t)i * c->attn_slot) + (size_t)img0 * f.heads * c->attn_q * T;
+            HIPCHK(&c->err, launch_attention_probs(qkv16, hm_rows, batch, T, f.heads, c->head_dim, c->attn_q, dt16, slot, s));
+        }
+        return VH_OK;
+    };
     // Patch embedding: the im2col pass + the persistent GEMM.
     // VH_FLAG_PRE_LN: a LayerNorm needs whole rows, which no patch-GEMM tile holds -- such a context embeds through the fp32-x branch
     // and one pre_layernorm_kernel pass turns x into what its path consumes (no PATCH_SPLIT, no rowstats pass)
@@ -718,6 +740,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         gq.wscale = sq;
         set_tiled(gq, qkv_hm, false);
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
+        if ((rc = capture_attention(l, qkv_hm ? (int64_t)rows_g : 0))) return rc;
         if (tail && l + 1 == nl) {
             // VH_FLAG_CLS_TAIL, last layer: only the class-token row of every image reaches the head, so attention runs for that
             // one query (all keys and values), and out-proj, fc1 and fc2 run on the `batch` class rows, gathered into compact
@@ -804,6 +827,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         GemmArgs gq = gemm_args(op_dt, xn16, c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, qkv16, rows, 3 * D, D, VH_EPI_BIAS);
         gq.wscale = sq;
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
+        if ((rc = capture_attention(l, 0))) return rc;
         if ((rc = stage(ST_ATTN, [&] {
                  return hd64 ? launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true)
                              : launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, op_dt, s);
@@ -1424,6 +1448,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->rz_u8) hipFree(c->rz_u8);
     if (c->arena) hipFree(c->arena);
     if (c->feat_store) hipFree(c->feat_store);
+    if (c->attn_store) hipFree(c->attn_store);
     if (c->w16) hipFree(c->w16);
     if (c->blob) hipFree(c->blob);
     for (hipEvent_t e : c->tev) hipEventDestroy(e);
@@ -2526,6 +2551,134 @@ int vh_read_layer_features(vh_ctx* c, const vh_layer_features* f) {
     return features_read_host(c, *f, src, "read_layer_features");
 }
 
+// ---- attention maps (vithip.h "Attention maps"; kernels_attn_maps.hip) -------------------------------------------------------
+// The list and the store; enqueue_forward runs the capture kernel into the store and records what it captured (acap_*).
+int vh_set_attention_layers(vh_ctx* c, const int* layers, int n, int queries) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "set_attention_layers: null context");
+    if (n < 0 || n > VH_MAX_ATTENTION_LAYERS) return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: %d layers, outside 0..%d", n, VH_MAX_ATTENTION_LAYERS);
+    if (n > 0 && !layers) return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: null list");
+    for (int i = 0; i < n; ++i) {
+        if (layers[i] < 1 || layers[i] > c->cfg.layers)
+            return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: entry %d is layer %d, outside 1..%d", i, layers[i], c->cfg.layers);
+        if (i && layers[i] <= layers[i - 1])
+            return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: the list must be strictly ascending (entry %d is %d after %d)", i, layers[i], layers[i - 1]);
+    }
+    if (queries != VH_ATTN_Q_CLS && queries != VH_ATTN_Q_LEAD)
+        return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: queries %d is not VH_ATTN_Q_CLS (0) or VH_ATTN_Q_LEAD (1)", queries);
+    if (n > 0 && queries == VH_ATTN_Q_CLS && !c->L.ncls)
+        return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: VH_ATTN_Q_CLS on a context without a class token (VH_FLAG_NO_CLS)");
+    if (n > 0 && queries == VH_ATTN_Q_LEAD && c->L.lead < 1)
+        return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: VH_ATTN_Q_LEAD on a context without leading rows (no class token, no registers)");
+    const int Q = queries == VH_ATTN_Q_CLS ? 1 : c->L.lead;
+    if (n > 0 && Q > kAttnMapsMaxQueries)
+        return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: %d leading rows, the capture kernel takes at most %d", Q, kAttnMapsMaxQueries);
+    if (n > 0 && (c->cfg.flags & VH_FLAG_CLS_TAIL))
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "set_attention_layers: a VH_FLAG_CLS_TAIL context's last layer runs the class-token attention kernel");
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "set_attention_layers: a ring exists on this context; vh_ring_destroy first");
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    const size_t slot = align_up((size_t)c->cfg.max_batch * c->cfg.heads * Q * c->L.T * sizeof(float), 256);
+    char* store = nullptr;
+    if (n) {
+        const hipError_t e = hipMalloc((void**)&store, slot * n);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(&c->err, VH_ERR_HIP, "set_attention_layers: no room for the store (%d layers x %zu bytes): %s; the previous list stays",
+                        n, slot, hipGetErrorString(e));
+        }
+    }
+    drop_graphs(c);   // captured launch sequences hold the old list's launches and the old store
+    if (c->attn_store) hipFree(c->attn_store);
+    c->attn_store = store;
+    c->attn_slot = slot;
+    c->attn_n = n;
+    c->attn_q = n ? Q : 0;
+    c->attn_mode = queries;
+    for (int i = 0; i < n; ++i) c->attn_layers[i] = layers[i];
+    c->acap_n = 0;    // what the last forward captured lived in the old store
+    return VH_OK;
+}
+int vh_get_attention_layers(const vh_ctx* c, int* layers, int* n, int* queries) {
+    if (!c || !n) return fail(nullptr, VH_ERR_INVALID, "get_attention_layers: null argument");
+    *n = c->attn_n;
+    if (queries) *queries = c->attn_mode;
+    for (int i = 0; layers && i < c->attn_n; ++i) layers[i] = c->attn_layers[i];
+    return VH_OK;
+}
+int vh_attention_dims(const vh_ctx* c, int* batch, int* heads, int* queries, int* tokens, int* patches) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "attention_dims: null context");
+    if (batch) *batch = c->last_batch;
+    if (heads) *heads = c->cfg.heads;
+    if (queries) *queries = c->attn_q;
+    if (tokens) *tokens = c->L.T;
+    if (patches) *patches = c->L.NP;
+    return VH_OK;
+}
+// every refusal of the three read calls; on success *slot is the layer's slot of the store
+static int attention_check_call(vh_ctx* c, const vh_attention_maps* f, bool device, const float** slot) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "read_attention: null context");
+    if (!f) return fail(&c->err, VH_ERR_INVALID, "read_attention: null descriptor");
+    if (!f->probs && !f->head_mean) return fail(&c->err, VH_ERR_INVALID, "read_attention: no output requested (probs and head_mean are both NULL)");
+    if (f->elem != VH_ELEM_F32 && f->elem != VH_ELEM_F16 && f->elem != VH_ELEM_BF16)
+        return fail(&c->err, VH_ERR_INVALID, "read_attention: elem %d is not VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16", f->elem);
+    if (f->keys != VH_ATTN_KEYS_ALL && f->keys != VH_ATTN_KEYS_PATCH)
+        return fail(&c->err, VH_ERR_INVALID, "read_attention: keys %d is not VH_ATTN_KEYS_ALL (0) or VH_ATTN_KEYS_PATCH (1)", f->keys);
+    const int layers = c->cfg.layers;
+    if (f->layer != -1 && (f->layer < 1 || f->layer > layers))
+        return fail(&c->err, VH_ERR_INVALID, "read_attention: layer %d is not -1 or 1..%d", f->layer, layers);
+    if (f->reserved != 0) return fail(&c->err, VH_ERR_INVALID, "read_attention: reserved is %d, not 0", f->reserved);
+    if (device && (((uintptr_t)f->probs | (uintptr_t)f->head_mean) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "read_attention: a device output pointer is not 16-byte aligned (probs %p, head_mean %p)", f->probs, f->head_mean);
+    if (c->cfg.flags & VH_FLAG_CLS_TAIL)
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "read_attention: a VH_FLAG_CLS_TAIL context's last layer runs the class-token attention kernel");
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "read_attention: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
+    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "read_attention: no forward has run");
+    const int layer = f->layer == -1 ? layers : f->layer;
+    int at = -1;
+    for (int i = 0; i < c->acap_n; ++i) if (c->acap_layers[i] == layer) at = i;
+    if (at < 0)
+        return fail(&c->err, VH_ERR_STATE, "read_attention: layer %d was not in the list when the last forward was enqueued (vh_set_attention_layers)", layer);
+    if (layer > c->acap_nl)
+        return fail(&c->err, VH_ERR_STATE, "read_attention: the last forward ran %d layers and did not reach layer %d (vh_debug_set_layers)", c->acap_nl, layer);
+    *slot = (const float*)(c->attn_store + (size_t)at * c->attn_slot);
+    return VH_OK;
+}
+static int attention_enqueue(vh_ctx* c, const vh_attention_maps& f, const float* slot) {
+    HIPCHK(&c->err, launch_attention_readout(slot, c->last_batch, c->cfg.heads, c->attn_q, c->L.T, c->L.lead, f.elem, f.keys, f.probs, f.head_mean, c->stream));
+    return VH_OK;
+}
+int vh_read_attention_device_async(vh_ctx* c, const vh_attention_maps* f) {
+    const float* slot = nullptr;
+    if (int rc = attention_check_call(c, f, true, &slot)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return attention_enqueue(c, *f, slot);
+}
+int vh_read_attention_device(vh_ctx* c, const vh_attention_maps* f) {
+    if (int rc = vh_read_attention_device_async(c, f)) return rc;
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return VH_OK;
+}
+// the host form: staged in the q|k|v buffer, as features_read_host does (scratch between forwards)
+int vh_read_attention(vh_ctx* c, const vh_attention_maps* f) {
+    const float* slot = nullptr;
+    if (int rc = attention_check_call(c, f, false, &slot)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t es = f->elem == VH_ELEM_F32 ? 4 : 2, B = c->last_batch, Q = c->attn_q;
+    const size_t K = f->keys == VH_ATTN_KEYS_PATCH ? c->L.NP : c->L.T;
+    const size_t n_probs = B * c->cfg.heads * Q * K * es, n_mean = B * Q * K * es;
+    const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * c->cfg.dim * 2;
+    vh_attention_maps d = *f;
+    size_t at = 0;
+    if (f->probs) { d.probs = (char*)c->qkv16 + at; at += align_up(n_probs, 256); }
+    if (f->head_mean) { d.head_mean = (char*)c->qkv16 + at; at += align_up(n_mean, 256); }
+    if (at > cap) return fail(&c->err, VH_ERR_STATE, "read_attention: staging needs %zu bytes, the scratch holds %zu", at, cap);
+    if (int rc = attention_enqueue(c, d, slot)) return rc;
+    if (f->probs) HIPCHK(&c->err, hipMemcpyAsync(f->probs, d.probs, n_probs, hipMemcpyDeviceToHost, c->stream));
+    if (f->head_mean) HIPCHK(&c->err, hipMemcpyAsync(f->head_mean, d.head_mean, n_mean, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return VH_OK;
+}
+
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
@@ -2820,6 +2973,49 @@ int vh_op_attention_layout(const void* qkv16, int batch, int tokens, int heads, 
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     hipFree(ticket);
     if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? VH_ERR_INVALID : VH_ERR_HIP, "attention_layout failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+int vh_op_attention_probs(const void* qkv16, int batch, int tokens, int heads, int head_dim, int queries, int64_t in_hm_rows, int dtype,
+                          float* probs, void* stream) {
+    if (!qkv16 || !probs) return fail(nullptr, VH_ERR_INVALID, "attention_probs: null pointer");
+    if (batch <= 0) return fail(nullptr, VH_ERR_INVALID, "attention_probs: batch %d must be positive", batch);
+    if (tokens < 1 || tokens > kAttnStreamMaxTokens) return fail(nullptr, VH_ERR_INVALID, "attention_probs: tokens %d outside 1..%d", tokens, kAttnStreamMaxTokens);
+    if (!attention_hd_supported(head_dim)) return fail(nullptr, VH_ERR_INVALID, "attention_probs: head_dim %d is not 32, 48, ..., 128", head_dim);
+    if (heads <= 0 || heads > kAttnHdMaxWidth / head_dim)
+        return fail(nullptr, VH_ERR_INVALID, "attention_probs: heads %d x head_dim %d outside 1..%d", heads, head_dim, kAttnHdMaxWidth);
+    if (queries < 1 || queries > kAttnMapsMaxQueries || queries > tokens)
+        return fail(nullptr, VH_ERR_INVALID, "attention_probs: queries %d outside 1..min(%d, tokens)", queries, kAttnMapsMaxQueries);
+    if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16) return fail(nullptr, VH_ERR_INVALID, "attention_probs: dtype %d is not VH_DTYPE_BF16 or VH_DTYPE_FP16", dtype);
+    if (in_hm_rows && head_dim != 64) return fail(nullptr, VH_ERR_INVALID, "attention_probs: head-major q|k|v (in_hm_rows != 0) exists at head_dim 64 only, not %d", head_dim);
+    if (in_hm_rows && in_hm_rows < (int64_t)batch * tokens)
+        return fail(nullptr, VH_ERR_INVALID, "attention_probs: in_hm_rows %lld holds fewer than batch * tokens = %lld rows", (long long)in_hm_rows, (long long)batch * tokens);
+    if (((uintptr_t)qkv16 | (uintptr_t)probs) & 15)
+        return fail(nullptr, VH_ERR_INVALID, "attention_probs: a pointer is not 16-byte aligned (qkv16 %p, probs %p)", qkv16, (void*)probs);
+    if (const char* why = attention_probs_check(in_hm_rows, batch, tokens, heads, head_dim, queries, dtype)) return fail(nullptr, VH_ERR_INVALID, "attention_probs: %s", why);
+    OPCHK(launch_attention_probs(qkv16, in_hm_rows, batch, tokens, heads, head_dim, queries, dtype, probs, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_attention_readout(const float* store, int batch, int heads, int queries, int tokens, int lead, int elem, int keys, void* probs_out,
+                            void* head_mean_out, void* stream) {
+    if (!store) return fail(nullptr, VH_ERR_INVALID, "attention_readout: null store");
+    if (!probs_out && !head_mean_out) return fail(nullptr, VH_ERR_INVALID, "attention_readout: no output requested (probs_out and head_mean_out are both NULL)");
+    if (batch <= 0) return fail(nullptr, VH_ERR_INVALID, "attention_readout: batch %d must be positive", batch);
+    if (heads <= 0 || heads > kAttnHdMaxWidth / 32) return fail(nullptr, VH_ERR_INVALID, "attention_readout: heads %d outside 1..%d", heads, kAttnHdMaxWidth / 32);
+    if (tokens < 1 || tokens > kAttnStreamMaxTokens) return fail(nullptr, VH_ERR_INVALID, "attention_readout: tokens %d outside 1..%d", tokens, kAttnStreamMaxTokens);
+    if (queries < 1 || queries > kAttnMapsMaxQueries || queries > tokens)
+        return fail(nullptr, VH_ERR_INVALID, "attention_readout: queries %d outside 1..min(%d, tokens)", queries, kAttnMapsMaxQueries);
+    if (lead < 0 || lead >= tokens) return fail(nullptr, VH_ERR_INVALID, "attention_readout: lead %d outside 0..tokens-1", lead);
+    if (elem != VH_ELEM_F32 && elem != VH_ELEM_F16 && elem != VH_ELEM_BF16)
+        return fail(nullptr, VH_ERR_INVALID, "attention_readout: elem %d is not VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16", elem);
+    if (keys != VH_ATTN_KEYS_ALL && keys != VH_ATTN_KEYS_PATCH)
+        return fail(nullptr, VH_ERR_INVALID, "attention_readout: keys %d is not VH_ATTN_KEYS_ALL (0) or VH_ATTN_KEYS_PATCH (1)", keys);
+    if (((uintptr_t)store | (uintptr_t)probs_out | (uintptr_t)head_mean_out) & 15)
+        return fail(nullptr, VH_ERR_INVALID, "attention_readout: a pointer is not 16-byte aligned (store %p, probs_out %p, head_mean_out %p)", (const void*)store,
+                    probs_out, head_mean_out);
+    if (const char* why = attention_readout_check(batch, heads, queries, tokens, lead, elem, keys)) return fail(nullptr, VH_ERR_INVALID, "attention_readout: %s", why);
+    OPCHK(launch_attention_readout(store, batch, heads, queries, tokens, lead, elem, keys, probs_out, head_mean_out, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_op_im2col(const float* in, int batch, int image, int patch, int channels, void* out16, int dtype, void* stream) {

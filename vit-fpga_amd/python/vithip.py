@@ -123,6 +123,19 @@ class LayerFeatures(C.Structure):
                 ("norm", C.c_int32), ("layer", C.c_int32), ("patch_layout", C.c_int32)]
 
 
+MAX_ATTENTION_LAYERS = 64
+ATTN_Q_CLS, ATTN_Q_LEAD = 0, 1        # vh_set_attention_layers queries (VH_ATTN_Q_*): the class token's row / every leading row
+ATTN_KEYS_ALL, ATTN_KEYS_PATCH = 0, 1  # vh_attention_maps.keys (VH_ATTN_KEYS_*): all key columns / the patch columns
+
+
+class AttentionMaps(C.Structure):
+    """vh_attention_maps: where the attention maps of the last forward go (host or device pointers, None = not wanted): probs
+    [B, H, Q, K], head_mean [B, Q, K]; element type, layer (-1 = the last layer, else a listed layer), keys (ATTN_KEYS_*) and a
+    reserved 0.  32 bytes."""
+    _fields_ = [("probs", C.c_void_p), ("head_mean", C.c_void_p), ("elem", C.c_int32), ("layer", C.c_int32), ("keys", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 L422_YUYV, L422_UYVY, L422_YVYU, L422_VYUY, L422_V210 = range(5)   # vh_frame_yuy2.layout (VH_422_*); V210: the 16-bit entry points only
 class FrameBGRA(C.Structure):
     """vh_frame_bgra: one packed 4:4:4 frame (one plane of pixels whose samples lie as `layout`, L444_*, says) inside the buffer of a
@@ -267,6 +280,12 @@ SYMBOLS = {
     "vh_read_layer_features": (_i, [_vp, _vp]),
     "vh_read_layer_features_device": (_i, [_vp, _vp]),
     "vh_read_layer_features_device_async": (_i, [_vp, _vp]),
+    "vh_set_attention_layers": (_i, [_vp, _pi, _i, _i]),
+    "vh_get_attention_layers": (_i, [_vp, _pi, _pi, _pi]),
+    "vh_attention_dims": (_i, [_vp, _pi, _pi, _pi, _pi, _pi]),
+    "vh_read_attention": (_i, [_vp, _vp]),
+    "vh_read_attention_device": (_i, [_vp, _vp]),
+    "vh_read_attention_device_async": (_i, [_vp, _vp]),
     "vh_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -297,6 +316,8 @@ SYMBOLS = {
     "vh_op_attention_hd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_cls": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_layout": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _vp]),
+    "vh_op_attention_probs": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _i, _vp, _vp]),
+    "vh_op_attention_readout": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
@@ -1756,6 +1777,65 @@ class VitContext:
             out.append((f["patch"], f["cls"]) if return_class_token else f["patch"])
         return tuple(out)
 
+    # ---- attention maps: the class-token / register rows of listed layers (vithip.h "Attention maps") ----
+    def set_attention_layers(self, layers, queries=ATTN_Q_CLS):
+        """The layers whose attention every following forward keeps: strictly ascending, each 1 .. layers (k = the k-th encoder layer,
+        Hugging Face's attentions[k - 1]); queries ATTN_Q_CLS = row 0, ATTN_Q_LEAD = the class token and the registers.  An empty
+        list clears it and frees the store."""
+        layers = [int(k) for k in layers]
+        arr = (C.c_int * max(len(layers), 1))(*layers)
+        _check(lib().vh_set_attention_layers(self.h, arr, len(layers), queries), self.h)
+
+    def attention_layers(self):
+        """(the list, its queries constant)."""
+        arr, n, q = (C.c_int * MAX_ATTENTION_LAYERS)(), C.c_int(0), C.c_int(0)
+        _check(lib().vh_get_attention_layers(self.h, arr, C.byref(n), C.byref(q)), self.h)
+        return [arr[i] for i in range(n.value)], q.value
+
+    def attention_dims(self):
+        """(batch of the last forward, heads, query rows Q of the list in force, tokens, patches)."""
+        v = [C.c_int(0) for _ in range(5)]
+        _check(lib().vh_attention_dims(self.h, *(C.byref(x) for x in v)), self.h)
+        return tuple(x.value for x in v)
+
+    def read_attention(self, layer=-1, probs=True, head_mean=False, elem=ELEM_F32, keys=ATTN_KEYS_ALL):
+        """The attention maps of `layer` of the last forward as numpy arrays: {"probs": [B, H, Q, K], "head_mean": [B, Q, K]} of
+        float32 / float16, or uint16 holding bf16 bits for ELEM_BF16; K = tokens, or the patches with ATTN_KEYS_PATCH."""
+        b, h, q, t, n = self.attention_dims()
+        dt = {ELEM_F32: np.float32, ELEM_F16: np.float16, ELEM_BF16: np.uint16}.get(elem, np.float32)
+        b1, q1, k = max(b, 1), max(q, 1), (n if keys == ATTN_KEYS_PATCH else t)   # (no forward / no list: refused below)
+        out = {}
+        if probs:
+            out["probs"] = np.empty((b1, h, q1, k), dtype=dt)
+        if head_mean:
+            out["head_mean"] = np.empty((b1, q1, k), dtype=dt)
+        desc = AttentionMaps(*(out[x].ctypes.data if x in out else None for x in ("probs", "head_mean")), elem, layer, keys, 0)
+        _check(lib().vh_read_attention(self.h, C.byref(desc)), self.h)
+        return out
+
+    def read_attention_device(self, desc):
+        """desc: an AttentionMaps of device pointers (16-byte aligned); enqueues on the context's stream and waits."""
+        _check(lib().vh_read_attention_device(self.h, C.byref(desc)), self.h)
+
+    def read_attention_device_async(self, desc):
+        """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
+        _check(lib().vh_read_attention_device_async(self.h, C.byref(desc)), self.h)
+
+    def cls_attention(self, layer=-1, reshape=True):
+        """DINO's get_last_selfattention for the images of the LAST forward: the class token's softmax row per head, [B, H, gh, gw]
+        (attentions[:, :, 0, 1:] reshaped; the patch columns, not renormalised) or without reshape [B, H, tokens].  Capture happens
+        inside a forward: if `layer` is not listed the list is set here (ATTN_Q_CLS) and the read is refused (VhError, state)
+        until the caller has run the forward again."""
+        k = self.cfg["layers"] if layer == -1 else int(layer)
+        have, _ = self.attention_layers()
+        if k not in have:
+            self.set_attention_layers([k], ATTN_Q_CLS)
+        p = self.read_attention(k, keys=ATTN_KEYS_PATCH if reshape else ATTN_KEYS_ALL)["probs"][:, :, 0]
+        if not reshape:
+            return p
+        g = self.cfg["image_size"] // self.cfg["patch_size"]
+        return p.reshape(p.shape[0], p.shape[1], g, g)
+
 
 def group_shard_bounds(batch, n, r):
     lo, hi = C.c_int(0), C.c_int(0)
@@ -2100,6 +2180,18 @@ def op_attention_cls(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
 def op_attention_layout(qkv_ptr, batch, tokens, heads, out_ptr, dtype, out_tiled=False, in_hm_rows=0):
     """Test tap: op_attention with the 16-row-blocked output (unpack_tiled) and / or head-major q|k|v (pack_head_major)."""
     _check(lib().vh_op_attention_layout(qkv_ptr, batch, tokens, heads, out_ptr, dtype, 1 if out_tiled else 0, in_hm_rows, None))
+
+
+def op_attention_probs(qkv_ptr, batch, tokens, heads, head_dim, queries, dtype, probs_ptr, in_hm_rows=0):
+    """The capture kernel of the attention maps alone: the softmax rows of every image's first `queries` rows -> probs_ptr fp32
+    [batch, heads, queries, tokens]; q|k|v row-major, or head-major (pack_head_major) with in_hm_rows at head_dim 64."""
+    _check(lib().vh_op_attention_probs(qkv_ptr, batch, tokens, heads, head_dim, queries, in_hm_rows, dtype, probs_ptr, None))
+
+
+def op_attention_readout(store_ptr, batch, heads, queries, tokens, lead, elem, keys, probs_ptr, head_mean_ptr):
+    """The read-out kernel of the attention maps alone: store fp32 [batch, heads, queries, tokens] -> probs [batch, heads, queries, K]
+    and / or head_mean [batch, queries, K] in `elem`; K = tokens, or tokens - lead with ATTN_KEYS_PATCH."""
+    _check(lib().vh_op_attention_readout(store_ptr, batch, heads, queries, tokens, lead, elem, keys, probs_ptr, head_mean_ptr, None))
 
 
 def op_im2col(in_ptr, batch, image, patch, channels, out_ptr, dtype):
