@@ -1,4 +1,4 @@
-"""GPU parity beyond 640 tokens: the K/V-streaming attention kernel (kernels_attn_stream.hip) through vh_op_attention, through
+"""GPU parity beyond 640 tokens: the K/V-streaming attention kernel (kernels_attn_hd.hip at head dim 64) through vh_op_attention, through
 its own tap vh_op_attention_stream at every token count, and inside whole forwards of long-sequence models, against the CPU
 oracle.  Tolerances are the existing ones: ATT_TOL of test_gpu_ops for the operator, the model-level bounds of test_gpu_vit
 (fp16 1e-3, bf16 1e-2) and test_gpu_fp8 (fp8) for forwards.  The long-sequence configurations are defined here (not in

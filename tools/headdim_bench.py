@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
 """Head-dim measurements (run on the GPU box): models whose head dim is not 64 run their attention in kernels_attn_hd.hip.
 
-  python tools/headdim_bench.py [--out profiles] [--steps 20]
+  python tools/headdim_bench.py [--out profiles] [--steps 20] [--skip-forward]
 
   (1) whole forward, ViT-H/14-224 (head dim 80) at batch 128 in bf16, fp16 and fp8 and, as the head-dim-64 reference point of
       the same run, ViT-L/14-224 fp16 at batch 128: forward_device_async with step timing (device time per step), images/s,
       algorithmic FLOP/s over the 2.5 PF 16-bit peak;
   (2) the attention stage of the same forwards (hip events around its launches): device time per step, its FLOP/s (QK^T + PV,
       4 T^2 D per image and layer) and its share of the step;
-  (3) the attention kernels alone at T = 257 and 1025: vh_op_attention_hd at head dims 64, 80 and 128 against
-      vh_op_attention_stream (head dim 64) at equal batch x heads x T, bf16, in attention FLOP/s (host wall clock around
-      `reps` back-to-back calls; each call ends with a stream synchronisation, whose few microseconds are included).
+  (3) the attention kernel alone at T = 257 and 1025: vh_op_attention_hd at head dims 64, 80 and 128 at equal
+      batch x heads x T, bf16, in attention FLOP/s and relative to head dim 64 (host wall clock around `reps` back-to-back
+      calls; each call ends with a stream synchronisation, whose few microseconds are included).
 The ViT-H/14 and ViT-L/14 models are defined here: vh_synth.CONFIGS is shared by the test suite and bench.py.
 """
 import argparse
@@ -94,7 +94,7 @@ def forward_row(model, cfg, batch, dname, steps, log):
 def tap_rows(log, reps=10):
     rows = []
     for T, bh in TAP:
-        for name, hd in (("stream", 64), ("hd", 64), ("hd", 80), ("hd", 128)):
+        for hd in (64, 80, 128):
             heads = 16
             batch = bh // heads
             D = heads * hd
@@ -105,10 +105,7 @@ def tap_rows(log, reps=10):
             vithip.op_cast(f32.ptr, qkv.ptr, n, vithip.DTYPE_BF16)
             f32.free()
             out = vithip.DeviceBuffer(batch * T * D * 2)
-            if name == "stream":
-                call = lambda: vithip.op_attention_stream(qkv.ptr, batch, T, heads, out.ptr, vithip.DTYPE_BF16)
-            else:
-                call = lambda: vithip.op_attention_hd(qkv.ptr, batch, T, heads, hd, out.ptr, vithip.DTYPE_BF16)
+            call = lambda: vithip.op_attention_hd(qkv.ptr, batch, T, heads, hd, out.ptr, vithip.DTYPE_BF16)
             call()
             t0 = time.perf_counter()
             for _ in range(reps):
@@ -116,18 +113,18 @@ def tap_rows(log, reps=10):
             us = (time.perf_counter() - t0) * 1e6 / reps
             flop = 4.0 * T * T * hd * bh
             got = vithip.from16(out.to_numpy(np.uint16, (batch * T, D))[:64], vithip.DTYPE_BF16)
-            r = dict(kernel=name, tokens=T, head_dim=hd, batch_heads=bh, us_per_call=us, flops_per_s=flop / (us * 1e-6),
+            r = dict(kernel="hd", tokens=T, head_dim=hd, batch_heads=bh, us_per_call=us, flops_per_s=flop / (us * 1e-6),
                      finite=bool(np.isfinite(got).all()))
             rows.append(r)
-            log(f"tap T={T} batch*heads={bh} {name} hd={hd}: {us:.1f} us per call = {r['flops_per_s'] / 1e15:.3f} PF/s")
+            log(f"tap T={T} batch*heads={bh} hd={hd}: {us:.1f} us per call = {r['flops_per_s'] / 1e15:.3f} PF/s")
             qkv.free(); out.free()
     for T, _ in TAP:
-        ref = next(r for r in rows if r["tokens"] == T and r["kernel"] == "stream")
+        ref = next(r for r in rows if r["tokens"] == T and r["head_dim"] == 64)
         for r in rows:
             if r["tokens"] == T:
-                r["over_stream_hd64"] = r["flops_per_s"] / ref["flops_per_s"]
-        log(f"tap T={T}: FLOP/s over the streaming kernel at hd 64: " +
-            ", ".join(f"hd{r['head_dim']} {r['over_stream_hd64']:.3f}" for r in rows if r["tokens"] == T and r["kernel"] == "hd"))
+                r["over_hd64"] = r["flops_per_s"] / ref["flops_per_s"]
+        log(f"tap T={T}: FLOP/s over head dim 64: " +
+            ", ".join(f"hd{r['head_dim']} {r['over_hd64']:.3f}" for r in rows if r["tokens"] == T and r["head_dim"] != 64))
     return rows
 
 
@@ -136,6 +133,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--tag", default="headdim")
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--skip-forward", action="store_true", help="tap rows only")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     lines = []
@@ -144,15 +142,16 @@ def main():
         print(msg, flush=True)
         lines.append(msg)
 
-    rows = [forward_row(model, cfg, batch, dname, a.steps, log) for model, cfg, batch, dts in RUNS for dname in dts]
+    rows = [] if a.skip_forward else [forward_row(model, cfg, batch, dname, a.steps, log) for model, cfg, batch, dts in RUNS for dname in dts]
     taps = tap_rows(log)
-    h = next(r for r in rows if r["model"] == "ViT-H/14-224" and r["dtype"] == "fp16")
-    l14 = next(r for r in rows if r["model"] == "ViT-L/14-224" and r["dtype"] == "fp16")
-    summary = dict(h14_over_l14_flops_fp16=h["flops_per_s"] / l14["flops_per_s"],
-                   h14_over_l14_attention_flops_fp16=h["attention_flops_per_s"] / l14["attention_flops_per_s"],
-                   tap_over_stream={f"T{r['tokens']}_hd{r['head_dim']}": r["over_stream_hd64"] for r in taps if r["kernel"] == "hd"})
-    log(f"ViT-H/14-224 fp16 FLOP/s over ViT-L/14-224 fp16 FLOP/s (same run): {summary['h14_over_l14_flops_fp16']:.3f} "
-        f"(target >= 0.95); attention stage: {summary['h14_over_l14_attention_flops_fp16']:.3f}")
+    summary = dict(tap_over_hd64={f"T{r['tokens']}_hd{r['head_dim']}": r["over_hd64"] for r in taps})
+    if rows:
+        h = next(r for r in rows if r["model"] == "ViT-H/14-224" and r["dtype"] == "fp16")
+        l14 = next(r for r in rows if r["model"] == "ViT-L/14-224" and r["dtype"] == "fp16")
+        summary.update(h14_over_l14_flops_fp16=h["flops_per_s"] / l14["flops_per_s"],
+                       h14_over_l14_attention_flops_fp16=h["attention_flops_per_s"] / l14["attention_flops_per_s"])
+        log(f"ViT-H/14-224 fp16 FLOP/s over ViT-L/14-224 fp16 FLOP/s (same run): {summary['h14_over_l14_flops_fp16']:.3f} "
+            f"(target >= 0.95); attention stage: {summary['h14_over_l14_attention_flops_fp16']:.3f}")
     with open(os.path.join(a.out, f"{a.tag}_bench.json"), "w") as f:
         json.dump(dict(forward=rows, tap=taps, summary=summary), f, indent=1)
     with open(os.path.join(a.out, f"{a.tag}_bench.txt"), "w") as f:

@@ -24,38 +24,9 @@
 //   * online softmax over 32-key tiles in the exp2 domain, fp32 statistics, keys >= T masked.
 #include <type_traits>
 
-#include "vh_kernels.h"
+#include "attn_common.h"   // kTau, swap_halves / cross_half_max / cross_half_sum, ring_barrier, wait_vm
 
 namespace vh {
-
-// the running shift of a query row is re-centred only when a tile's scores exceed it by more than 2^kTau: between
-// re-centrings p = exp2(s - shift) <= 2^kTau, which fp32 sums and 16-bit P operands (fp16 max 65504) hold easily
-constexpr float kTau = 8.0f;
-
-// lanes l and l^32 hold the two halves of a query's row: combine them with one v_permlane32_swap
-// (a VALU exchange of the wave's halves) instead of a ds_bpermute round trip through the LDS crossbar
-// v_permlane32_swap vdst, src exchanges lanes 32-63 of vdst with lanes 0-31 of src IN PLACE, so the two
-// operands must be different registers: with one register it degenerates to a plain half swap.  The copy is
-// made opaque so the compiler cannot fold the operands back together.
-__device__ __forceinline__ void swap_halves(float v, float& lo_everywhere, float& hi_everywhere) {
-    // Whole exchange in one asm statement (hipcc 7.2 returned the same register for both results of
-    // __builtin_amdgcn_permlane32_swap here).  s_nop 1 = the 2 wait states of the "VALU write ->
-    // v_permlane read" hazard, which nobody pads inside inline asm; the trailing one covers the readers.
-    float a = v, b;
-    asm volatile("v_mov_b32 %1, %0\n\ts_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "=&v"(b));
-    lo_everywhere = a;  // {v[0..31], v[0..31]}
-    hi_everywhere = b;  // {v[32..63], v[32..63]}
-}
-__device__ __forceinline__ float cross_half_max(float v) {
-    float a, b;
-    swap_halves(v, a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float cross_half_sum(float v) {
-    float a, b;
-    swap_halves(v, a, b);
-    return a + b;
-}
 
 template <typename T, typename TO = T>   // TO: output element (T, or E4M3 on the fp8 path)
 __global__ void __launch_bounds__(1024, 4)   // <= 128 VGPRs, two 7-wave workgroups per CU put 4 waves on a SIMD
@@ -249,12 +220,6 @@ attention_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem* __
 #ifndef VH_ATTN_ABL
 #define VH_ATTN_ABL 0   // timing ablations (tools/ab_attn_abl.sh; results are wrong): 1 no exp, 2 no refill DMA, 4 no tile barriers, 8 no PV, 16 no QK, 32 no LDS reads, 64 no max
 #endif
-__device__ __forceinline__ void ring_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS reads of the slot about to be refilled are done
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
 // One LDS-DMA instruction (64 lanes x 16 B -> 1 KiB at the LDS address in M0), written as inline asm on purpose: hipcc
 // makes every ds_read_b64_tr_b16 (an intrinsic without a memory operand) wait for vmcnt(0) while a global_load_lds
 // it knows of is in flight, which would drain the ring at every tile.  The kernel's own waits (ring_wait_dma) cover
@@ -281,16 +246,7 @@ __device__ __forceinline__ unsigned long long attn_ct() {
 #define VH_ATT_T(i) do { } while (0)
 #endif
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (0..40: the counts of the staged form for up to 14 key tiles)
-__device__ __forceinline__ void ring_wait_vm(int n) {
-#define VH_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    switch (n) {
-        VH_W(1) VH_W(2) VH_W(3) VH_W(4) VH_W(5) VH_W(6) VH_W(7) VH_W(8) VH_W(9) VH_W(10) VH_W(11) VH_W(12) VH_W(13) VH_W(14)
-        VH_W(15) VH_W(16) VH_W(17) VH_W(18) VH_W(19) VH_W(20) VH_W(21) VH_W(22) VH_W(23) VH_W(24) VH_W(25) VH_W(26) VH_W(27)
-        VH_W(28) VH_W(29) VH_W(30) VH_W(31) VH_W(32) VH_W(33) VH_W(34) VH_W(35) VH_W(36) VH_W(37) VH_W(38) VH_W(39) VH_W(40)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-#undef VH_W
-}
+__device__ __forceinline__ void ring_wait_vm(int n) { wait_vm<40>(n); }
 __device__ __forceinline__ void ring_wait_dma() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -932,8 +888,8 @@ hipError_t launch_attention(const void* qkv16, int batch, int tokens, int heads,
         return dtype == VH_DTYPE_BF16 ? launch_attn_t<BF16, BF16, true>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed)
                                       : launch_attn_t<FP16, FP16, true>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed);
     }
-    // a head's K and V do not fit in LDS (tokens > 640): the K/V-streaming kernel (kernels_attn_stream.hip; no ticket)
-    if (attention_lds_bytes(tokens) > 160 * 1024) return launch_attention_stream(qkv16, batch, tokens, heads, out16, dtype, s);
+    // a head's K and V do not fit in LDS (tokens > 640): the K/V-streaming kernel (kernels_attn_hd.hip; no ticket)
+    if (attention_lds_bytes(tokens) > 160 * 1024) return launch_attention_hd(qkv16, batch, tokens, heads, 64, out16, dtype, s);
     if (dtype == VH_DTYPE_FP8) return launch_attn_t<BF16, E4M3>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed);  // bf16 in, e4m3 out
     return dtype == VH_DTYPE_BF16 ? launch_attn_t<BF16>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed)
                                   : launch_attn_t<FP16>(qkv16, batch, tokens, heads, out16, ticket, s, ticket_zeroed);

@@ -1,80 +1,148 @@
-// kernels_attn_hd.hip — K/V-streaming multi-head attention for head dims 32, 48, ..., 128 (gfx950).
+// kernels_attn_hd.hip — the K/V-streaming multi-head attention kernel, for every head dim 32, 48, ..., 128 (gfx950).
 //
-// The operation of kernels_attn_stream.hip at any head dim hd = 16 * NB16 (NB16 = 2..8): row-major q|k|v
-// [batch*T][3*H*hd] 16-bit with q pre-scaled by hd^-1/2 * log2(e), row-major output [batch*T][H*hd], any token count
-// 1..kAttnStreamMaxTokens.  The forward sends every model whose head dim is not 64 here (head dim 64 keeps its kernels).
+// Same operation as kernels_attn.hip at any head dim hd = 16 * NB16 (NB16 = 2..8): row-major q|k|v [batch*T][3*H*hd] 16-bit
+// with q pre-scaled by hd^-1/2 * log2(e), row-major output [batch*T][H*hd], any token count 1..kAttnStreamMaxTokens, without
+// the resident forms' bound (those keep a whole head's K and V in LDS: ceil(T/32) * 8 KiB <= 160 KiB, T <= 640).  Here K and
+// V pass through a fixed LDS ring of kSlots 32-key tiles, whatever T is.  The forward sends every model whose head dim is
+// not 64 here; head dim 64 arrives here beyond 640 tokens (launch_attention's fallback) and through the two taps.
 //
-// Differences from the 64-wide streaming kernel (same ring, DMA, wait / barrier and online-softmax structure):
-//   * S^T = K Q^T contracts over NB16 k-steps of v_mfma_f32_32x32x16 (Q fragments qf[NB16]); O^T = V^T P^T keeps
-//     NDB = ceil(hd / 32) 32x32 accumulators.  For hd = 48, 80, 112 the last block covers 16 real V columns: its other 16
-//     A rows re-read the real ones (same LDS addresses, a broadcast) and their output rows are not stored.  An MFMA output
-//     row depends only on its own A row, so they cannot touch the stored rows.
-//   * K/V tile image in LDS (one function for K and V, NB16 KiB per matrix and tile): the 32 x hd tile is cut into
-//     8-row x 16-column subtiles of 256 B -- exactly one bank row -- in the order [row group rg = row / 8][column pair
-//     p = chunk / 2]; inside a subtile, 16-byte chunk (row, chunk) sits at
-//         32 * ((row & 7) ^ 4 * (p & 1)) + 16 * ((chunk & 1) ^ (rg & 1)).
-//     ds_read_b128 of the K operand (16 lanes, one chunk, 16 rows that are distinct mod 16) lands on 16 distinct slots;
-//     ds_read_b64_tr_b16 of the V operand (a 32-lane half: 4 rows x 4 chunks x 2 halves in two neighbouring subtiles)
-//     lands on 32 distinct 8-byte pieces, the XOR by 4 * (p & 1) putting the odd subtile's rows on the other half of the
-//     bank row.  Conflict-free at every hd, with no assumption on the row pitch (160 B at hd 80).
-//   * LDS-DMA stays lane-linear: one 1 KiB instruction fills four consecutive subtiles, the permutation goes on the
-//     lane's global source address.  With NB16 >= 4 a DMA reads 8 rows x 128 contiguous bytes.
-//   * LDS per workgroup: kSlots * 2 * NB16 KiB (48 KiB at hd 128): at least three workgroups per CU at every hd.
-// Query rows >= T and keys >= T as in the 64-wide kernel; image, head and plane bases are 64-bit.
+// Design (CDNA4), the resident ring kernel's idioms on a streamed image:
+//   * work item = (image, head, query slab of nw*32 rows), one workgroup per item (nw <= kMaxWaves waves), blockIdx.x =
+//     (image * heads + head) * slabs + slab: the slabs of a head are neighbours in the grid, so their K/V reads meet in L2.
+//     No work-queue counter, no allocation: safe in a captured graph and when a batch is split across streams.
+//   * key tile t lives in slot t % kSlots.  Its 2 * NB16 pieces of 1 KiB (K and V) are moved by LDS-DMA (asm_lds_dma16:
+//     hipcc does not see the transfer, so it never drains vmcnt in front of ds_read_b64_tr_b16) by waves 0..NB16-1, or by
+//     fewer waves several pieces each.  The DMA destination is lane-linear; the tile image's permutation goes on the lane's
+//     global source address.
+//   * per tile t: wait until this wave's pieces of tile t have landed (a counted vmcnt that leaves tile t+1 in flight),
+//     barrier (every wave's pieces visible; every wave is done with tile t-1), refill tile t-1's slot with tile t+2, compute.
+//   * S^T = K Q^T contracts over NB16 k-steps of v_mfma_f32_32x32x16 (a query's scores in one lane pair), row max / sum
+//     finished with v_permlane32_swap, exp2-domain online softmax with the deferred rescale (the shift moves only when a
+//     tile's scores exceed it by 2^kTau; O and l are rescaled once, no probabilities are pending), the converted accumulator
+//     is the B operand of O^T = V^T P^T (NDB = ceil(hd / 32) 32x32 accumulators), V^T from ds_read_b64_tr_b16, widened
+//     output stores.  For hd = 48, 80, 112 the last block covers 16 real V columns: its other 16 A rows re-read the real
+//     ones (same LDS addresses, a broadcast) and their output rows are not stored.  An MFMA output row depends only on its
+//     own A row, so they cannot touch the stored rows.
+//   * keys >= T in the last tile are masked (their rows replicate row T-1: finite data under zero probabilities); query
+//     rows >= T are computed from the clamped row T-1 and not stored.  Image, head and plane bases are 64-bit.
+//   * LDS per workgroup: kSlots * 2 * NB16 KiB (24 KiB at hd 64, 48 KiB at hd 128): at least three workgroups per CU.
+// One skeleton, two tile images (TileImage below): the 128-byte-row image at head dim 64, the subtile image elsewhere.
 #include <climits>
 #include <type_traits>
 
-#include "vh_kernels.h"
+#include "attn_common.h"
 
 namespace vh {
 namespace {
 
-constexpr float kTau = 8.0f;     // as kernels_attn.hip
 constexpr int kSlots = 3;        // ring depth in 32-key tiles
 
-// waves per workgroup and the register budget: up to hd 64, 8 waves at <= 128 VGPRs (two workgroups per CU, as the
-// 64-wide kernel); beyond, the accumulators and fragments need more (hd 80 spills at 128), so 4 waves at <= 256 VGPRs
-// (at least two workgroups per CU)
+// Per head dim: waves per workgroup and the register budget, the counted wait's range and the form of the half exchange.
+//   * up to hd 64, 8 waves at <= 128 VGPRs (two workgroups of 8 fill a CU); beyond, the accumulators and fragments need more
+//     (hd 80 spills at 128), so 4 waves at <= 256 VGPRs (at least two workgroups per CU).
+//   * a wave moves at most 2 * NB16 pieces per tile.  Head dim 64 switches over exactly its 8 counts; the others keep one
+//     switch of 16.
+//   * head dim 64 exchanges the lane halves with the asm statement, every other head dim with the builtin (attn_common.h:
+//     a half last block needs the builtin).
 template <int NB16> struct HdShape {
     static constexpr int kMaxWaves = NB16 <= 4 ? 8 : 4;
     static constexpr int kWavesPerEU = NB16 <= 4 ? 4 : 2;
+    static constexpr int kWaitCases = NB16 == 4 ? 8 : 16;
+    static constexpr bool kAsmSwap = NB16 == 4;
 };
 
-// lanes l and l^32 hold the two halves of a query's row.  The builtin, not an asm statement as in the 64-wide kernel: with
-// a half last block the rows 16..31 of its accumulator are dead after the last MFMA, the register allocator reuses them, and
-// hipcc pads no wait states inside an asm string -- an asm write there races the MFMA's late result writes (WAW).  Same
-// values, same sums: lo + hi in every lane.
-__device__ __forceinline__ void hd_swap_halves(float v, float& lo_everywhere, float& hi_everywhere) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, v), __builtin_bit_cast(uint32_t, v), false, false);
-    lo_everywhere = __builtin_bit_cast(float, (uint32_t)r[0]);
-    hi_everywhere = __builtin_bit_cast(float, (uint32_t)r[1]);
-}
-__device__ __forceinline__ float hd_half_max(float v) {
-    float a, b;
-    hd_swap_halves(v, a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float hd_half_sum(float v) {
-    float a, b;
-    hd_swap_halves(v, a, b);
-    return a + b;
-}
-// s_waitcnt vmcnt(n) for a wave-uniform n in 0..16 (a wave moves at most 2 * 8 pieces per tile)
-__device__ __forceinline__ void hd_wait_vm(int n) {
-#define VH_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    switch (n) {
-        VH_W(1) VH_W(2) VH_W(3) VH_W(4) VH_W(5) VH_W(6) VH_W(7) VH_W(8)
-        VH_W(9) VH_W(10) VH_W(11) VH_W(12) VH_W(13) VH_W(14) VH_W(15) VH_W(16)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+// The image of one 32-key x hd tile of K or V in LDS (NB16 KiB per matrix and tile; K slots first, the V slots at kV), as
+// three answers, all static and inlined:
+//   * dma_piece: which global (row, K chunk, V chunk) lane ln of DMA piece g moves (16-byte chunks of the head's row; rows >=
+//     tokens replicate the last row), and the two transfers themselves; the piece lands lane-linear at g * 1024 in its slot.
+//     Byte offsets from `base` stay below 2^32: row < 4097, row pitch 3 D * 2 <= 12 KiB;
+//   * k_lane / k_odd, v_lane / v_second: this lane's offsets in a slot -- K for even k-steps and, from it, for odd ones; V for
+//     piece c = 0 of a k-step (keys 16 ks + 8 c + 0..7) in a whole or in a half last block and, from it, for piece 1;
+//     l31 = lane & 31 and hl = lane >> 5 are the kernel's own values (handing them in, not recomputing them, keeps hipcc's code);
+//   * k_frag / v_frag: from such an offset, the K fragment of k-step ks and the V^T piece c of (k-step ks, column block db).
+// `ring` is the start of the ring, `so` the slot's byte offset in it.  The kernel keeps the six lane offsets in registers
+// across the tile loop and has no image arithmetic of its own.
+//
+// Every head dim but 64: the tile is cut into 8-row x 16-column subtiles of 256 B -- exactly one bank row -- in the order
+// [row group rg = row / 8][column pair p = chunk / 2]; inside a subtile, 16-byte chunk (row, chunk) sits at
+//     32 * ((row & 7) ^ 4 * (p & 1)) + 16 * ((chunk & 1) ^ (rg & 1)).
+// ds_read_b128 of the K operand (16 lanes, one chunk, 16 rows that are distinct mod 16) lands on 16 distinct slots;
+// ds_read_b64_tr_b16 of the V operand (a 32-lane half: 4 rows x 4 chunks x 2 halves in two neighbouring subtiles) lands on
+// 32 distinct 8-byte pieces, the XOR by 4 * (p & 1) putting the odd subtile's rows on the other half of the bank row.
+// Conflict-free at every hd, with no assumption on the row pitch (160 B at hd 80).  One 1 KiB DMA fills four consecutive
+// subtiles (piece g = subtiles 4 g .. 4 g + 3); with NB16 >= 4 it reads 8 rows x 128 contiguous bytes.
+template <int NB16> struct TileImage {
+    static constexpr int kTile = NB16 * 1024;   // bytes of one matrix tile
+    static constexpr int kV = kSlots * kTile;   // offset of the V slots
+    static __device__ __forceinline__ void dma_piece(const void* base, uint32_t lds_k, uint32_t lds_v, int t, int g, int ln,
+                                                     int tokens, int64_t ld, int D) {
+        const int st = 4 * g + (ln >> 4), w = ln & 15;   // lane -> (row, chunk) inverts the layout above
+        const int rg = st / NB16, p = st - rg * NB16;
+        const int row = t * 32 + rg * 8 + ((w >> 1) ^ ((p & 1) << 2));
+        const int r = row < tokens ? row : tokens - 1;
+        const int ch = 2 * p + ((w & 1) ^ (rg & 1));
+        const uint32_t ok = (uint32_t)(r * (int)ld + ch * 8) * 2u + (uint32_t)D * 2u;
+        asm_lds_dma16(base, ok, lds_k + g * 1024);
+        asm_lds_dma16(base, ok + (uint32_t)D * 2u, lds_v + g * 1024);
     }
-#undef VH_W
-}
-__device__ __forceinline__ void hd_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS reads of the slot about to be refilled are done
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
+    // K (row l31, chunk 2 ks + hl): k_lane + 256 ks, bit 7 flipped on odd ks.  V^T (rows 4 hl + tq of row group rg = 2 ks + c,
+    // chunk 4 db + 2 (g4 & 1) + (tp >> 1), half tp & 1): v_lane + 256 (NB16 rg + 2 db), bit 4 flipped for c = 1; the half last
+    // block's offset drops the (g4 & 1) part (columns 16..31 of the block re-read columns 0..15)
+    static __device__ __forceinline__ int k_lane(int l31, int hl) {
+        return (l31 >> 3) * kTile / 4 + ((l31 & 7) << 5) + ((hl ^ ((l31 >> 3) & 1)) << 4);
+    }
+    static __device__ __forceinline__ int k_odd(int kl) { return kl ^ 128; }
+    static __device__ __forceinline__ int v_lane(int lane, int hl, bool half) {
+        const int g4 = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
+        const int vlo = (((tp >> 1)) << 4) + 8 * (tp & 1);
+        if (half) return kV + ((4 * hl + tq) << 5) + vlo;
+        return kV + (g4 & 1) * 256 + (((4 * hl + tq) ^ ((g4 & 1) << 2)) << 5) + vlo;
+    }
+    static __device__ __forceinline__ int v_second(int vl) { return vl ^ 16; }
+    static __device__ __forceinline__ const char* k_frag(const char* ring, int so, int kl, int ks) { return ring + so + kl + 256 * ks; }
+    static __device__ __forceinline__ const char* v_frag(const char* ring, int so, int vl, int ks, int db, int c) {
+        return ring + so + vl + 256 * (NB16 * (2 * ks + c) + 2 * db);
+    }
+};
+
+// Head dim 64: K and V rows of 128 bytes (piece g = rows 8 g .. 8 g + 7), a K chunk XOR-swizzled by (row >> 1) & 7 for the
+// ds_read_b128 row reads, a V chunk by ((row >> 1) & 1) << 2 for the transposing reads -- the image of the resident ring form
+// (kernels_attn.hip).  One lane offset serves every k-step and both pieces: the other K chunks are XORs (bits 4-5), the
+// second 32-column block of V flips bit 6.  Kept beside the subtile image because that one is slower here: 0.976x at 257 and
+// 0.989x at 1025 tokens (profiles/headdim_bench.txt), 1213 against 1128 instructions (profiles/attn_stream_merge_isa.txt).
+template <> struct TileImage<4> {
+    static constexpr int kTile = 4096;
+    static constexpr int kV = kSlots * kTile;
+    static __device__ __forceinline__ void dma_piece(const void* base, uint32_t lds_k, uint32_t lds_v, int t, int g, int ln,
+                                                     int tokens, int64_t ld, int D) {
+        const int lr_ = ln >> 3, pc_ = ln & 7;
+        const int row = t * 32 + g * 8 + lr_;
+        const int r = row < tokens ? row : tokens - 1;
+        const int ck = pc_ ^ ((row >> 1) & 7);
+        const int cv = pc_ ^ (((row >> 1) & 1) << 2);
+        const uint32_t ok = (uint32_t)(r * (int)ld + ck * 8) * 2u + (uint32_t)D * 2u;
+        const uint32_t ov = (uint32_t)(r * (int)ld + cv * 8) * 2u + (uint32_t)D * 4u;
+        asm_lds_dma16(base, ok, lds_k + g * 1024);
+        asm_lds_dma16(base, ov, lds_v + g * 1024);
+    }
+    static __device__ __forceinline__ int k_lane(int l31, int hl) {
+        const int kswz = (l31 >> 1) & 7;
+        return l31 * 128 + ((hl ^ kswz) << 4);
+    }
+    static __device__ __forceinline__ int k_odd(int kl) { return kl; }
+    static __device__ __forceinline__ int v_lane(int lane, int, bool) {
+        const int g4 = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
+        const int vrow0 = 4 * (g4 >> 1) + tq;
+        const int vcolb = (16 * (g4 & 1) + 4 * tp) * 2;
+        const int vx = ((vrow0 >> 1) & 1) << 6;
+        return kV + vrow0 * 128 + (vcolb ^ vx);
+    }
+    static __device__ __forceinline__ int v_second(int vl) { return vl; }
+    static __device__ __forceinline__ const char* k_frag(const char* ring, int so, int kl, int ks) { return ring + ((kl + so) ^ (ks << 5)); }
+    static __device__ __forceinline__ const char* v_frag(const char* ring, int so, int vl, int ks, int db, int c) {
+        return ring + ((vl + so) ^ (db << 6)) + ks * 2048 + c * 1024;
+    }
+};
 
 template <int NB16, typename T, typename TO>
 __global__ void __launch_bounds__(HdShape<NB16>::kMaxWaves * 64, HdShape<NB16>::kWavesPerEU)
@@ -83,11 +151,13 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
     using elem = typename T::elem;
     using vec8 = typename T::vec8;
     using vec4 = typename T::vec4;
+    using Image = TileImage<NB16>;
     constexpr int HD = 16 * NB16;
     constexpr int NDB = (NB16 + 1) / 2;          // 32-column output blocks
     constexpr bool HALF_LAST = (NB16 & 1) != 0;  // the last block holds 16 real columns
-    constexpr int kTile = NB16 * 1024;           // bytes of one matrix tile (32 rows x hd)
-    constexpr int kV = kSlots * kTile;           // offset of the V slots
+    constexpr bool ASM_SWAP = HdShape<NB16>::kAsmSwap;
+    static_assert(!(ASM_SWAP && HALF_LAST), "a half last block needs the builtin half exchange");
+    constexpr int kTile = Image::kTile, kV = Image::kV;
     __shared__ __attribute__((aligned(16))) char smem[2 * kSlots * kTile];   // K slots, then V slots
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
 
@@ -105,23 +175,12 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
     const int q0 = (slab * nw + wave) * 32;
 
     // ---- DMA of key tile t into slot t % kSlots: pieces g = wave, wave + nw, ... < NB16 of K and of V ------------------
-    // Piece g = subtiles 4 g .. 4 g + 3 of the image; lane -> (row, chunk) inverts the layout above.  Byte offsets from
-    // `base` stay below 2^32: row < 4097, row pitch 3 D * 2 <= 12 KiB.
     const int npieces = wave < NB16 ? (NB16 - wave + nw - 1) / nw : 0;   // per matrix and tile, wave-uniform
     auto issue_tile = [&](int t) {
         int ln = lane;
         asm volatile("" : "+v"(ln));   // recomputed per issue instead of hoisted into registers across the tile loop
         const uint32_t slot = (uint32_t)(t % kSlots) * (uint32_t)kTile;
-        for (int g = wave; g < NB16; g += nw) {
-            const int st = 4 * g + (ln >> 4), w = ln & 15;
-            const int rg = st / NB16, p = st - rg * NB16;
-            const int row = t * 32 + rg * 8 + ((w >> 1) ^ ((p & 1) << 2));
-            const int r = row < tokens ? row : tokens - 1;   // rows >= tokens replicate the last row
-            const int ch = 2 * p + ((w & 1) ^ (rg & 1));
-            const uint32_t ok = (uint32_t)(r * (int)ld + ch * 8) * 2u + (uint32_t)D * 2u;
-            asm_lds_dma16(base, ok, lds0 + slot + g * 1024);
-            asm_lds_dma16(base, ok + (uint32_t)D * 2u, lds0 + kV + slot + g * 1024);
-        }
+        for (int g = wave; g < NB16; g += nw) Image::dma_piece(base, lds0 + slot, lds0 + kV + slot, t, g, ln, tokens, ld, D);
     };
 
     // this wave's Q fragments (rows >= tokens: the last row), then the first kSlots - 1 tiles
@@ -135,17 +194,10 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
     }
     for (int t = 0; t < kSlots - 1 && t < ntiles; ++t) issue_tile(t);
 
-    // per-lane LDS offsets.  K (row l31, chunk 2 ks + hl): kb0 + 256 ks, bit 7 flipped on odd ks.  V^T (rows 4 hl + tq of
-    // row group rg, chunk 4 db + 2 (g4 & 1) + (tp >> 1), half tp & 1): vb[rg & 1] + 256 (NB16 rg + 2 db); the half last
-    // block reads through vh[], which drops the (g4 & 1) part (columns 16..31 of the block re-read columns 0..15)
-    const int g4 = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
-    const int kb0 = (l31 >> 3) * kTile / 4 + ((l31 & 7) << 5) + ((hl ^ ((l31 >> 3) & 1)) << 4);
-    const int kb1 = kb0 ^ 128;
-    const int vlo = (((tp >> 1)) << 4) + 8 * (tp & 1);
-    const int vb0 = kV + (g4 & 1) * 256 + (((4 * hl + tq) ^ ((g4 & 1) << 2)) << 5) + vlo;
-    const int vb1 = vb0 ^ 16;
-    const int vh0 = kV + ((4 * hl + tq) << 5) + vlo;
-    const int vh1 = vh0 ^ 16;
+    // this lane's fragment offsets in a slot: K for even / odd k-steps, V for the two pieces of a k-step, whole and half block
+    const int ke = Image::k_lane(l31, hl), ko = Image::k_odd(ke);
+    const int v0 = Image::v_lane(lane, hl, false), v1 = Image::v_second(v0);
+    const int h0 = Image::v_lane(lane, hl, true), h1 = Image::v_second(h0);
 
     f32x16 o[NDB];
 #pragma unroll
@@ -159,8 +211,8 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
     auto tile = [&](int kt, auto first_c, auto tail_c) {
         constexpr bool FIRST = decltype(first_c)::value, TAIL = decltype(tail_c)::value;
         // this wave's pieces of tile kt have landed (tile kt + 1 may stay in flight), then everyone's; tile kt - 1 is done
-        hd_wait_vm(kt + 1 < ntiles ? 2 * npieces : 0);
-        hd_barrier();
+        wait_vm<HdShape<NB16>::kWaitCases>(kt + 1 < ntiles ? 2 * npieces : 0);
+        ring_barrier();
         if (kt + kSlots - 1 < ntiles) issue_tile(kt + kSlots - 1);   // into tile kt - 1's slot
         const int so = (kt % kSlots) * kTile;
 
@@ -170,9 +222,8 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
 #pragma unroll
             for (int db = 0; db < NDB; ++db) {
                 const bool half = HALF_LAST && db == NDB - 1;
-                const int rga = 2 * ks, rgc = 2 * ks + 1;   // keys 16 ks + 0..7 and 16 ks + 8..15
-                const char* pa = smem + so + (half ? vh0 : vb0) + 256 * (NB16 * rga + 2 * db);
-                const char* pc = smem + so + (half ? vh1 : vb1) + 256 * (NB16 * rgc + 2 * db);
+                const char* pa = Image::v_frag(smem, so, half ? h0 : v0, ks, db, 0);   // keys 16 ks + 0..7
+                const char* pc = Image::v_frag(smem, so, half ? h1 : v1, ks, db, 1);   // keys 16 ks + 8..15
                 const vec4 a = T::tr_read(pa), c = T::tr_read(pc);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { vfr.f[ks][db][j] = a[j]; vfr.f[ks][db][4 + j] = c[j]; }
@@ -183,7 +234,7 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
         {
             vec8 kf[NB16];
 #pragma unroll
-            for (int ks = 0; ks < NB16; ++ks) kf[ks] = *(const vec8*)(smem + so + ((ks & 1) ? kb1 : kb0) + 256 * ks);
+            for (int ks = 0; ks < NB16; ++ks) kf[ks] = *(const vec8*)Image::k_frag(smem, so, (ks & 1) ? ko : ke, ks);
             __builtin_amdgcn_sched_barrier(0);
             const float init = FIRST ? 0.f : negm;
 #pragma unroll
@@ -199,9 +250,9 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
         float mx = s[0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-        mx = hd_half_max(mx);   // finite: every tile holds at least one key < tokens
+        mx = cross_half_max<ASM_SWAP>(mx);   // finite: every tile holds at least one key < tokens
         if constexpr (FIRST) {
-            negm = -mx;         // the row's shift = its maximum over tile 0
+            negm = -mx;                      // the row's shift = its maximum over tile 0
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[r] -= mx;
         } else if (__builtin_amdgcn_ballot_w64(mx > kTau)) {   // rare: some row outgrew its shift by 2^kTau
@@ -245,8 +296,8 @@ attention_hd_kernel(const typename T::elem* __restrict__ qkv, typename TO::elem*
         tile(ntiles - 1, std::false_type{}, std::true_type{});
     }
 
-    // ---- normalise and store: lane holds O[q][32*db + 8*rg + 4*hl + 0..3] (widened as in the 64-wide kernel) ----------
-    const float ltot = hd_half_sum(lsum);
+    // ---- normalise and store: lane holds O[q][32*db + 8*rg + 4*hl + 0..3] (widened as in the resident ring form) -------
+    const float ltot = cross_half_sum<ASM_SWAP>(lsum);
     const float inv = __builtin_amdgcn_rcpf(ltot);
     const int q = q0 + l31;
     const int64_t mrow = (int64_t)b * tokens + (q < tokens ? q : tokens - 1);

@@ -84,16 +84,13 @@ bool attention_tiled_applies(int batch, int tokens, int heads);
 // class-token query only: out16 [batch][heads * 64] (VH_FLAG_CLS_TAIL); 16-bit dtypes, tokens <= 1024
 hipError_t launch_attention_cls(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, hipStream_t stream);
 size_t attention_lds_bytes(int tokens);
-// K/V-streaming attention (kernels_attn_stream.hip): the same operation in a fixed 24 KiB LDS ring, any token count
-// 1..kAttnStreamMaxTokens, heads <= 32, row-major q|k|v and output; dtype VH_DTYPE_FP8 = bf16 in, e4m3 out.  No work-queue
-// counter and no allocation (graph capture, split batches).  launch_attention sends a row-major call here when the resident
-// forms cannot hold the head (attention_lds_bytes(tokens) > 160 KiB).
+// K/V-streaming attention at head dims 32, 48, ..., 128 (kernels_attn_hd.hip): the same operation in a fixed LDS ring (24 KiB at head
+// dim 64), row-major q|k|v [batch*tokens][3*heads*head_dim] with q pre-scaled by head_dim^-1/2 * log2(e) (attention_q_scale) ->
+// row-major [batch*tokens][heads*head_dim]; tokens 1..kAttnStreamMaxTokens, heads * head_dim <= kAttnHdMaxWidth (heads <= 32 at
+// head dim 64); dtype VH_DTYPE_FP8 = bf16 in, e4m3 out.  No work-queue counter and no allocation (graph capture, split batches).
+// The forward uses it for every head dim other than 64; at head dim 64 launch_attention sends a row-major call here when the
+// resident forms cannot hold the head (attention_lds_bytes(tokens) > 160 KiB).
 constexpr int kAttnStreamMaxTokens = 4097;   // 64 x 64 patches + the class token
-hipError_t launch_attention_stream(const void* qkv16, int batch, int tokens, int heads, void* out16, int dtype, hipStream_t stream);
-// K/V-streaming attention at head dims 32, 48, ..., 128 (kernels_attn_hd.hip): row-major q|k|v [batch*tokens][3*heads*head_dim]
-// with q pre-scaled by head_dim^-1/2 * log2(e) (attention_q_scale) -> row-major [batch*tokens][heads*head_dim]; tokens
-// 1..kAttnStreamMaxTokens, heads * head_dim <= kAttnHdMaxWidth; dtype VH_DTYPE_FP8 = bf16 in, e4m3 out.  No work-queue counter,
-// no allocation.  The forward uses it for every head dim other than 64.
 constexpr int kAttnHdMaxWidth = 2048;
 bool attention_hd_supported(int head_dim);
 hipError_t launch_attention_hd(const void* qkv16, int batch, int tokens, int heads, int head_dim, void* out16, int dtype,

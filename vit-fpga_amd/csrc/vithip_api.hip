@@ -2930,7 +2930,7 @@ int vh_op_attention_stream(const void* qkv16, int batch, int tokens, int heads, 
         return fail(nullptr, VH_ERR_INVALID, "attention_stream: unsupported shape");
     if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8)
         return fail(nullptr, VH_ERR_INVALID, "attention_stream: unsupported dtype");
-    OPCHK(launch_attention_stream(qkv16, batch, tokens, heads, out16, dtype, (hipStream_t)stream));
+    OPCHK(launch_attention_hd(qkv16, batch, tokens, heads, 64, out16, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
