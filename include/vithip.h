@@ -184,6 +184,39 @@ typedef struct vh_config {
 #define VH_POOL_AVG_FCNORM 2
 #define VH_POOL_CLS_AVG 3
 
+/* SigLIP's vision towers (SigLIP, SigLIP 2 fixed-size, PaliGemma's tower; timm's global_pool='map'): two MODEL switches, independent of
+ * each other, in bits 19 and 21 of flags and, at the same positions, of the blob header's flags word; a blob whose bits differ from
+ * the context's is refused with a message that names the bit.  With both clear nothing changes.
+ *   VH_FLAG_TANH_GELU  the MLP activation is 0.5 v (1 + tanh(sqrt(2/pi) (v + 0.044715 v^3))) ("gelu_pytorch_tanh") instead of erf
+ *                      GELU.  No tensor of its own; excludes VH_FLAG_QUICK_GELU.  With VH_FLAG_NO_CLS | VH_FLAG_POOL(VH_POOL_AVG_NORM)
+ *                      such a context is SiglipForImageClassification; vh_read_features gives a SigLIP tower's patch features.
+ *   VH_FLAG_MAP_HEAD   the head's input is the multihead attention-pooling block ("MAP"): ONE learned query attends over the NP
+ *                      patch rows, followed by a LayerNorm + MLP with a residual.  With an identity head (classes = D) the logits
+ *                      are SiglipVisionModel's pooler_output.  Needs VH_FLAG_NO_CLS; excludes a non-zero VH_FLAG_POOL field,
+ *                      register tokens and VH_FLAG_CLS_TAIL; heads <= 16.  Each refusal has a message of its own.
+ *   Blob tensors of a MAP context, all fp32, directly after head.bias (no other offset moves), H = heads, M = mlp_dim:
+ *     map.qk [H][D], map.v.weight [D][D], map.v.bias [D], map.o.weight [D][D], map.o.bias [D], map.ln.weight [D], map.ln.bias [D],
+ *     map.fc1.weight [M][D], map.fc1.bias [M], map.fc2.weight [D][M], map.fc2.bias [D].
+ *     map.qk[h] = W_k,h^T (W_q,h probe + b_q,h) / sqrt(hd): the query is the same for every image, so the CONVERTER folds it through
+ *     the key projection (in float64; vithip.py blob_from_siglip_state_dict); the key bias adds a per-head constant to every score,
+ *     which the softmax cancels exactly.  The library holds no fold code.  vh_init_weights_seeded: tensor ids 0x7010 .. 0x701A in
+ *     this order, sigma 0.02 (map.ln.weight: 0.05 around 1).
+ *   THE FUNCTION, per image; t runs over the NP patch rows, x_t = the final residual row:
+ *     y_t    = LN(x_t; lnf)                        fp32, the row arithmetic of "Token features" (VH_FEAT_NORM)
+ *     s[h,t] = qk[h] . y_t
+ *     p[h,.] = softmax_t s[h,.]
+ *     z[h]   = sum_t p[h,t] y_t                    [H][D]  (sum_t p (W_v y_t + b_v) = W_v z + b_v: the weights sum to 1, so V is
+ *                                                           never projected per token; vh_op_map_pool is this step alone)
+ *     a[h hd + j] = v.weight[h hd + j] . z[h] + v.bias[h hd + j]
+ *     o      = o.weight a + o.bias
+ *     u      = o + fc2(act(fc1(LN(o; map.ln))))    act = the context's activation (erf, quick or tanh), evaluated in fp32
+ *     vh_debug_read(ctx, 1) = u [batch][D];  logits = head(u), the fp32 head over W = D columns.
+ *   Everything behind z is fp32 arithmetic on [batch] rows.  An image's bits depend on its rows alone: never on the batch, the
+ *   stream part or graph replay. */
+#define VH_FLAG_MAP_HEAD (1 << 19)
+#define VH_FLAG_TANH_GELU (1 << 21)
+#define VH_MAP_MAX_HEADS 16
+
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
 
@@ -224,7 +257,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -243,7 +276,8 @@ int vh_export_weights_device(vh_ctx* ctx, void* dev_blob, size_t nbytes);
  * byte, plus an FNV-1a-64 checksum of the parameter bytes in header words that memory blobs leave zero.
  *   vh_blob_file_config: host only (no device needed) -- validates magic / shape / file length and fills the model
  *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create;
- *                        cfg->flags = the model bits VH_FLAG_PRE_LN / VH_FLAG_QUICK_GELU / VH_FLAG_REGISTERS(n) of the header);
+ *                        cfg->flags = the model bits of the header: VH_FLAG_PRE_LN, VH_FLAG_QUICK_GELU, VH_FLAG_REGISTERS(n), VH_FLAG_NO_CLS,
+ *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU);
  *   vh_save_weights_file: writes <path>.tmp then renames; vh_load_weights_file: verifies length, shape, checksum. */
 int vh_blob_file_config(const char* path, vh_config* cfg);
 /* host only: the file as a MEMORY blob (what vh_load_weights takes): length, header and checksum verified, checksum
@@ -749,7 +783,7 @@ int vh_get_step_timing(vh_ctx* ctx, double* step_ms, int max_steps, int* steps);
 /* debug taps: copy an internal activation of the LAST forward to the host as fp32.
  * what: 0 = residual stream x [batch*T, D] after the last layer run,
  *       1 = the head's input [batch, W]: the final-LN'd CLS rows (W = D), or what the context's VH_FLAG_POOL mode computes
- *           (W = D; 2 D for VH_POOL_CLS_AVG),
+ *           (W = D; 2 D for VH_POOL_CLS_AVG), or the attention-pooling block's result u of a VH_FLAG_MAP_HEAD context (W = D),
  *       (2 is unused: VH_ERR_INVALID, like any other value not listed here,)
  *       3 = one float: 1 when the last forward kept the MLP hidden activation in its tiled (16-row-blocked) layout -- the
  *           default wherever both MLP GEMMs take the persistent form (16-bit folded path, whole 256-row tiles; VH_H_TILED=0 at
@@ -984,6 +1018,10 @@ int vh_read_attention_device_async(vh_ctx* ctx, const vh_attention_maps* out_dev
 #define VH_EPI_BIAS_QGELU 10   /* out16[m,n] = qgelu(acc + bias[n]),  qgelu(v) = v * sigmoid(1.702 v); accepted wherever
                                   VH_EPI_BIAS_GELU is, with the same shape rules                                           */
 #define VH_EPI_LNFOLD_QGELU 11 /* qgelu of VH_EPI_LNFOLD; accepted wherever VH_EPI_LNFOLD_GELU is                          */
+/* (12 is no code: the taps keep refusing it, as the refusal tests expect) */
+#define VH_EPI_BIAS_TGELU 13   /* out16[m,n] = tgelu(acc + bias[n]),  tgelu(v) = 0.5 v (1 + tanh(sqrt(2/pi) (v + 0.044715 v^3)));
+                                  accepted wherever VH_EPI_BIAS_GELU is, with the same shape rules                         */
+#define VH_EPI_LNFOLD_TGELU 14 /* tgelu of VH_EPI_LNFOLD; accepted wherever VH_EPI_LNFOLD_GELU is                          */
 /* out = epilogue(A[M,K] * W[N,K]^T); A and W hold `dtype` elements, K contiguous.
  * aux: EPI_PATCH -> pos-emb fp32 [tokens, N] with aux_i = patches per image.
  * variant: 0 = auto, 1 = 128x128 tile, 2 = 256x256 two-stage, 5 = 256x256 ping-pong, 6 = persistent ping-pong. */
@@ -1018,7 +1056,7 @@ int vh_op_gemm_ex(const void* a16_dev, const void* w16_dev, const float* bias_de
 /* Test and measurement taps: the forms of the GEMM that only a whole forward reaches otherwise (tests/gemm_exact.py).
  * vh_op_gemm_layout is vh_op_gemm_ex, vh_op_gemm_fp8_layout is vh_op_gemm_fp8_ex (which here takes the epilogues of vh_op_gemm_fp8 as
  * well: c_dev / stats_dev / out16 / partials may be NULL where the epilogue does not use them), plus
- *   out_tiled != 0   activation epilogues (*_GELU, *_QGELU): the result in the 16-row-blocked layout of the MLP hidden activation,
+ *   out_tiled != 0   activation epilogues (*_GELU, *_QGELU, *_TGELU): the result in the 16-row-blocked layout of the MLP hidden activation,
  *                    [M / 16][N / 8][16 rows][8 values] (e4m3 results: [M / 16][N / 16][16 rows][16 B]);
  *                    VH_EPI_LNFOLD and 16-bit VH_EPI_BIAS: the result head-major, [N / 64][M][64] (the q|k|v projection)
  *   ab_tiled != 0    A and W are both read from the 16-row-blocked layout ([rows / 16][K / 8][16][8]; e4m3: [rows / 16][K / 16][16][16 B]):
@@ -1256,6 +1294,16 @@ int vh_op_token_features2(const void* hi_or_x32_dev, const void* lo_dev, int for
  * touched, each refusal with a message of its own. */
 int vh_op_pool_rows(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int lead, int dim,
                     const float* gamma_dev, const float* beta_dev, float eps, int norm, float* mean_out_dev, void* stream);
+/* The token-sized pass of the VH_FLAG_MAP_HEAD head on its own (the step z of "THE FUNCTION" at VH_FLAG_MAP_HEAD):
+ * z_out_dev [batch][heads][dim] fp32 <- sum_t softmax_t(qk[h] . y_t) y_t over rows lead .. tokens - 1 of every image, y_t = the row
+ * through LayerNorm(gamma_dev, beta_dev, eps).  qk_dev [heads][dim] fp32.  ONE pass over the rows: one workgroup per image, a wave
+ * normalises a row in registers and computes its `heads` scores, the rows of a group meet in LDS and enter an online softmax in
+ * ascending token order (exp2 of log2(e)-scaled scores, one rescale per group).  form / hi / lo / lead / tokens / dim and the
+ * alignment rule as vh_op_pool_rows; heads 1 .. 16.  Every argument is checked before a device is touched, each refusal with a
+ * message of its own. */
+int vh_op_map_pool(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int lead, int dim,
+                   const float* gamma_dev, const float* beta_dev, float eps, const float* qk_dev, int heads, float* z_out_dev,
+                   void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,
  * 2 = constant `sigma` */
 int vh_op_fill(float* out_dev, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,

@@ -10,6 +10,7 @@
 //   PATCH                   out32[row(m)] = acc + bias + pos[tok(m)]
 //   LNFOLD / LNFOLD_GELU    out16 = [gelu]( rstd_m * (acc - mean_m * c_n) + d_n )
 //   BIAS_QGELU / LNFOLD_QGELU   the two GELU forms with QuickGELU, v * sigmoid(1.702 v), as the activation (CLIP's OpenAI towers)
+//   BIAS_TGELU / LNFOLD_TGELU   the same with tanh GELU (SigLIP's gelu_pytorch_tanh)
 //        LayerNorm folded into the GEMM: with W' = gamma o W the product LN(x) W^T equals
 //        rstd * (x W'^T - mean * c) + d,  c_n = sum_k W'_nk,  d_n = sum_k beta_k W_nk + b_n, so the
 //        GEMM runs on the RAW (16-bit rounded) residual rows and the per-row statistics enter here.
@@ -53,9 +54,12 @@ struct EpiArgs {
 };
 
 constexpr bool epi_has_qgelu(int epi) { return epi == VH_EPI_BIAS_QGELU || epi == VH_EPI_LNFOLD_QGELU; }
-// "has an activation": erf GELU or QuickGELU (epi_value16 picks the function from the code)
-constexpr bool epi_has_act(int epi) { return epi == VH_EPI_BIAS_GELU || epi == VH_EPI_LNFOLD_GELU || epi_has_qgelu(epi); }
-constexpr bool epi_is_lnfold(int epi) { return epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU; }
+constexpr bool epi_has_tgelu(int epi) { return epi == VH_EPI_BIAS_TGELU || epi == VH_EPI_LNFOLD_TGELU; }
+// "has an activation": erf GELU, QuickGELU or tanh GELU (epi_value16 picks the function from the code)
+constexpr bool epi_has_act(int epi) { return epi == VH_EPI_BIAS_GELU || epi == VH_EPI_LNFOLD_GELU || epi_has_qgelu(epi) || epi_has_tgelu(epi); }
+constexpr bool epi_is_lnfold(int epi) {
+    return epi == VH_EPI_LNFOLD || epi == VH_EPI_LNFOLD_GELU || epi == VH_EPI_LNFOLD_QGELU || epi == VH_EPI_LNFOLD_TGELU;
+}
 constexpr bool epi_is_16bit(int epi) { return epi == VH_EPI_BIAS || epi == VH_EPI_LNFOLD || epi_has_act(epi); }
 
 // exact-erf GELU: with x = |v|/sqrt(2), h = 0.5*erfc(x) = 0.5*poly(t)*t*exp(-x^2), t = 1/(1 + 0.3275911 x)
@@ -159,6 +163,34 @@ __device__ __forceinline__ f32x4 qgelu4(f32x4 v) {
     return f32x4{x[0][0], x[0][1], x[1][0], x[1][1]};
 }
 
+// tanh GELU (gelu_pytorch_tanh: SigLIP, PaliGemma's tower), 0.5 v (1 + tanh(u)), u = sqrt(2/pi) (v + 0.044715 v^3), for a quad of values.
+// 0.5 (1 + tanh(u)) = sigmoid(2 u), so this is qgelu4 with a cubic argument: v * rcp(1 + exp2(v * (C0 + C1 v^2))), C0 = -2 log2(e)
+// sqrt(2/pi), C1 = 0.044715 C0.  Per PAIR of values five packed operations (square, fma, * v, + 1, * v) and four transcendentals: by
+// tools/probe_valu.hip's prices 5 x 3.3 + 4 x 6.1 = 41 cycles, between the erf fit's degree 8 and 9 -- ONE form for every result type.
+// Error: as qgelu4 plus the two roundings of the argument, which exp2 sees as |argument| x 2^-23 relative; where the argument is
+// large the sigmoid is within that of 0 or 1 (tests/test_gpu_siglip.py sweeps it against the limit of qgelu4's comment).
+// Edge values as qgelu4: +inf -> +inf (argument -inf, exp2 0), large negative finite v -> -0 (argument +inf even where v^2
+// overflows: -inf * v), NaN -> NaN, -inf -> NaN like the defining expression -inf * 0.
+__device__ __forceinline__ f32x4 tgelu4(f32x4 v) {
+    constexpr float C0 = -2.0f * 1.44269504088896341f * 0.79788456080286536f, C1 = C0 * 0.044715f;
+    f32x2 x[2] = {f32x2{v[0], v[1]}, f32x2{v[2], v[3]}}, t[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = x[h] * x[h];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = __builtin_elementwise_fma(t[h], f32x2{C1, C1}, f32x2{C0, C0});
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = t[h] * x[h];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = f32x2{__builtin_amdgcn_exp2f(t[h][0]), __builtin_amdgcn_exp2f(t[h][1])};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = t[h] + f32x2{1.f, 1.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) t[h] = f32x2{__builtin_amdgcn_rcpf(t[h][0]), __builtin_amdgcn_rcpf(t[h][1])};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) x[h] = x[h] * t[h];
+    return f32x4{x[0][0], x[0][1], x[1][0], x[1][1]};
+}
+
 // sum over the 16 lanes of a DPP row (lanes 16g .. 16g+15), result in every lane of the row
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
@@ -184,6 +216,8 @@ __device__ __forceinline__ f32x4 epi_value16(f32x4 acc, f32x4 bv, f32x4 cv, floa
     }
     if constexpr (epi_has_qgelu(EPI) && !(VH_EPI_ABL & 32)) {
         v = qgelu4(v);
+    } else if constexpr (epi_has_tgelu(EPI) && !(VH_EPI_ABL & 32)) {
+        v = tgelu4(v);
     } else if constexpr (epi_has_act(EPI) && !(VH_EPI_ABL & 32)) {
         v = gelu_poly4<GeluDeg<TR>::value>(v);
     }

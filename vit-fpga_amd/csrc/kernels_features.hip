@@ -14,12 +14,16 @@
 //                      row kernel's own three steps (row_load, row_stats, piece_norm), transposed through LDS.
 //   pool_rows_kernel   the same mean in ONE pass over the planes, inside the forward of a VH_FLAG_POOL context: one workgroup per
 //                      image, a row per wave through the row kernel's steps, the rows of a group added from LDS in token order.
+//   map_pool_kernel    the softmax-weighted sums of the attention-pooling head (VH_FLAG_MAP_HEAD) in the same ONE pass: the pool
+//                      kernel's skeleton with the rows' scores against the folded query and an online softmax per group.
 //   feat_capture_kernel  the copy of a tapped layer's rows into the capture store ("Layer features"), both planes in one launch.
 // (The normalised class-token rows of the final state are the ones the head multiplied: a conversion copy of clsn32, made by launch_cast.)
 //
 // The arithmetic that both kernels must agree on lives in ONE place each: load_x (x = hi + lo, one fp32 add) and
 // feat_norm (fmaf((x - mean) * rstd, gamma, beta), explicit fmaf).  The row sums use explicit operations in an order that
 // depends on dim alone: per lane the pieces ascending (inside a piece a fixed tree), then the xor butterfly over the wave.
+#include <cstdio>
+#include <cstring>
 #include <type_traits>
 
 #include "vh_kernels.h"
@@ -464,7 +468,195 @@ hipError_t pool_launch(const PoolArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- the token-sized pass of the attention-pooling head (VH_FLAG_MAP_HEAD; vithip.h): z[b][h][k] = sum_t softmax_t(qk[h] . y_t) y_t[k] -----
+// over the patch rows of image b, y_t = the row through the final LayerNorm.  The skeleton is pool_rows_kernel's: one workgroup (16
+// waves) per image, a group of `group` consecutive patch rows at a time, wave w < group takes row w through row_load / row_stats /
+// piece_norm, parks the fp32 row in LDS -- and, here, computes the row's `heads` scores against qk (read through L1 / L2: heads x dim
+// floats, the same for every row and image) by wave reductions, in the log2 domain.  Then three steps per group, a barrier between them:
+//   1. thread (g, h) of the first 256 finds the new running maximum m[h] = max(m[h], max_g s[g][h]) and writes p[g][h] = exp2(s[g][h] -
+//      m[h]); thread (0, h) also updates the running sum l[h] and leaves the group's rescale factor f[h] = exp2(m_old - m_new) -- 0 for
+//      the first group, stated, so that (-inf) - (-inf) is never formed;
+//   2. thread t, which owns column t (and t + 1024, .. where dim is wider than the workgroup), multiplies its accumulators by f[h] ONCE and adds p[g][h] * y[g][col]
+//      for the group's rows in ascending order.  acc[NCOL][HB] is fully unrolled (HB = the head bucket: 4, 12 or 16): registers.
+//   3. the group's LDS rows are free.
+// The end divides by l[h].  Every sum has one order, which depends on dim, heads and the token index alone: an image's bits do not depend
+// on the batch, the workgroup or the stream.  Heads h >= heads of a bucket keep p = f = 0 and are never written.
+// NW = waves per workgroup: 16, as the pool kernel; 8 for the widest instantiation (dim > 1536 with more than 12 heads), whose row, 32
+// accumulators and addresses are a few VGPRs more than the 128 a wave of a 1024-thread workgroup has -- 512 threads own four columns each
+// and a group is at most 8 rows (map_pool_group), which is what 16384 / dim allows at 2048 anyway.
+constexpr int kMapHeadSlots = VH_MAP_MAX_HEADS;
+constexpr int map_pool_waves(int ch, int hb) { return ch == 4 && hb == 16 ? 8 : kPoolWaves; }
+template <typename IN, int CH, int HB, int NW>
+__global__ void __launch_bounds__(NW * 64)
+map_pool_kernel(const void* __restrict__ hi, const void* __restrict__ lo, int tokens, int lead, int dim, const float* __restrict__ gamma,
+                const float* __restrict__ beta, float eps, int group, const float* __restrict__ qk, int heads, float* __restrict__ out) {
+    static_assert(HB % 4 == 0 && HB <= kMapHeadSlots, "head bucket: a multiple of 4, at most 16");
+    __shared__ __attribute__((aligned(16))) float park[kPoolLdsFloats];                  // [group][dim]
+    __shared__ __attribute__((aligned(16))) float sc[kPoolWaves * kMapHeadSlots];        // [group][16] scores, log2 domain
+    __shared__ __attribute__((aligned(16))) float pw[kPoolWaves * kMapHeadSlots];        // [group][16] softmax numerators of the group
+    __shared__ __attribute__((aligned(16))) float fsc[kMapHeadSlots];                    // the group's rescale factors
+    __shared__ float mrun[2][kMapHeadSlots], lrun[kMapHeadSlots];                        // running maximum (by group parity) and sum
+    constexpr int NT = NW * 64, NCOL = (CH * 512 + NT - 1) / NT;   // columns per thread: t, t + NT, ..
+    constexpr float kLog2e = 1.44269504088896341f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int np = tokens - lead, npiece = dim >> 3;
+    const int64_t img = blockIdx.x;
+    const int64_t row0 = img * tokens + lead;
+    const bool loader = wave < group;   // wave-uniform
+    float acc[NCOL][HB];
+#pragma unroll
+    for (int j = 0; j < NCOL; ++j)
+#pragma unroll
+        for (int h = 0; h < HB; ++h) acc[j][h] = 0.f;
+    if (threadIdx.x < kPoolWaves * kMapHeadSlots) pw[threadIdx.x] = 0.f;
+    if (threadIdx.x < kMapHeadSlots) {
+        mrun[0][threadIdx.x] = -INFINITY;
+        lrun[threadIdx.x] = 0.f;
+        fsc[threadIdx.x] = 0.f;
+    }
+    int par = 0;
+    for (int p0 = 0; p0 < np; p0 += group) {
+        const int p = p0 + wave;
+        if (loader && p < np) {
+            float v[CH][8];
+            row_load<IN, CH>(hi, lo, row0 + p, dim, lane, v);
+            float mean, rstd;
+            row_stats<CH>(v, dim, lane, eps, mean, rstd);
+            float* const w = park + wave * dim;
+#pragma unroll
+            for (int i = 0; i < CH; ++i) {
+                const int c = lane + 64 * i;
+                if (c < npiece) {
+                    piece_norm(v[i], c, mean, rstd, gamma, beta);
+                    ((f32x4*)(w + 8 * c))[0] = f32x4{v[i][0], v[i][1], v[i][2], v[i][3]};
+                    ((f32x4*)(w + 8 * c))[1] = f32x4{v[i][4], v[i][5], v[i][6], v[i][7]};
+                }
+            }
+            // the row's scores: per lane its pieces ascending (an fmaf chain over a piece's 8 elements), then the xor butterfly
+#pragma unroll 1
+            for (int h = 0; h < heads; ++h) {   // (one head at a time: unrolled, the loads of several heads cost the registers the accumulators live in)
+                const f32x4* const q = (const f32x4*)(qk + (int64_t)h * dim);
+                float s = 0.f;
+#pragma unroll
+                for (int i = 0; i < CH; ++i) {
+                    const int c = lane + 64 * i;
+                    if (c < npiece) {
+                        const f32x4 q0 = q[2 * c], q1 = q[2 * c + 1];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) s = __builtin_fmaf(v[i][j], q0[j], s);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) s = __builtin_fmaf(v[i][4 + j], q1[j], s);
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                if (lane == 0) sc[wave * kMapHeadSlots + h] = s * kLog2e;
+            }
+        }
+        __syncthreads();   // the group's rows and scores are parked (and, first group, the running state is initialised)
+        const int n = np - p0 < group ? np - p0 : group;
+        if (threadIdx.x < kPoolWaves * kMapHeadSlots) {
+            const int g = threadIdx.x >> 4, h = threadIdx.x & (kMapHeadSlots - 1);
+            if (g < n && h < heads) {
+                const float m_old = mrun[par][h];
+                float m_new = m_old;
+                for (int gg = 0; gg < n; ++gg) m_new = fmaxf(m_new, sc[gg * kMapHeadSlots + h]);
+                pw[threadIdx.x] = __builtin_amdgcn_exp2f(sc[threadIdx.x] - m_new);
+                if (g == 0) {
+                    float sum = 0.f;
+                    for (int gg = 0; gg < n; ++gg) sum += __builtin_amdgcn_exp2f(sc[gg * kMapHeadSlots + h] - m_new);
+                    const float f = p0 == 0 ? 0.f : __builtin_amdgcn_exp2f(m_old - m_new);   // first group: nothing to rescale, no inf - inf
+                    lrun[h] = __builtin_fmaf(lrun[h], f, sum);
+                    fsc[h] = f;
+                    mrun[par ^ 1][h] = m_new;
+                }
+            }
+        }
+        __syncthreads();   // p, f and l of the group are in LDS
+        if ((int)threadIdx.x < dim) {
+#pragma unroll
+            for (int q = 0; q < HB / 4; ++q) {
+                const f32x4 f4 = ((const f32x4*)fsc)[q];
+#pragma unroll
+                for (int j = 0; j < NCOL; ++j)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc[j][4 * q + k] *= f4[k];
+            }
+#pragma unroll 1
+            for (int g = 0; g < n; ++g) {
+                float x[NCOL];
+#pragma unroll
+                for (int j = 0; j < NCOL; ++j) {
+                    const int col = threadIdx.x + NT * j;
+                    x[j] = col < dim ? park[g * dim + col] : 0.f;
+                }
+#pragma unroll
+                for (int q = 0; q < HB / 4; ++q) {
+                    const f32x4 p4 = ((const f32x4*)(pw + g * kMapHeadSlots))[q];
+#pragma unroll
+                    for (int j = 0; j < NCOL; ++j)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) acc[j][4 * q + k] = __builtin_fmaf(p4[k], x[j], acc[j][4 * q + k]);
+                }
+            }
+        }
+        __syncthreads();   // the group has been added: its LDS rows, scores and numerators are free
+        par ^= 1;
+    }
+#pragma unroll
+    for (int j = 0; j < NCOL; ++j) {
+        const int col = threadIdx.x + NT * j;
+        if (col < dim) {
+#pragma unroll
+            for (int h = 0; h < HB; ++h)
+                if (h < heads) out[(img * heads + h) * dim + col] = acc[j][h] / lrun[h];
+        }
+    }
+}
+
+template <typename IN>
+hipError_t map_pool_launch(const PoolArgs& a, const float* qk, int heads, hipStream_t s) {
+    const int group = map_pool_group(a.dim, heads);
+#define VH_MAP_L(CH, HB) hipLaunchKernelGGL((map_pool_kernel<IN, CH, HB, map_pool_waves(CH, HB)>), dim3((unsigned)a.batch), dim3(map_pool_waves(CH, HB) * 64), 0, s, a.hi, a.lo, a.tokens, a.lead, \
+                                            a.dim, a.gamma, a.beta, a.eps, group, qk, heads, a.out)
+#define VH_MAP_H(CH) do { if (heads <= 4) VH_MAP_L(CH, 4); else if (heads <= 12) VH_MAP_L(CH, 12); else VH_MAP_L(CH, 16); } while (0)
+    if (a.dim <= 512) VH_MAP_H(1);
+    else if (a.dim <= 1024) VH_MAP_H(2);
+    else if (a.dim <= 1536) VH_MAP_H(3);
+    else VH_MAP_H(4);
+#undef VH_MAP_H
+#undef VH_MAP_L
+    return hipGetLastError();
+}
+
 }  // namespace
+
+int map_pool_group(int dim, int heads) {
+    const int waves = map_pool_waves(dim > 1536 ? 4 : 1, heads > 12 ? 16 : 4);
+    return kPoolLdsFloats / dim < waves ? kPoolLdsFloats / dim : waves;
+}
+
+const char* map_pool_check(const PoolArgs& a, const float* qk, int heads) {
+    if (const char* why = pool_check(a)) {   // the rows, the LayerNorm and the output are pool_rows' own arguments: its reasons, under this tap's name
+        static thread_local char text[160];
+        const char* colon = strchr(why, ':');
+        snprintf(text, sizeof text, "map_pool%s", colon ? colon : why);
+        return text;
+    }
+    if (a.norm != VH_FEAT_NORM) return "map_pool: the rows pass the LayerNorm (norm must be VH_FEAT_NORM)";
+    if (a.out_stride || a.cls_in || a.cls_out) return "map_pool: no output stride and no class rows";
+    if (!qk) return "map_pool: null qk";
+    if ((uintptr_t)qk & 15) return "map_pool: a device pointer is not 16-byte aligned";
+    if (heads < 1 || heads > VH_MAP_MAX_HEADS) return "map_pool: heads outside 1..16";
+    return nullptr;
+}
+
+hipError_t launch_map_pool(const PoolArgs& a, const float* qk, int heads, hipStream_t s) {
+    if (map_pool_check(a, qk, heads)) return hipErrorInvalidValue;
+    if (a.form == VH_FEAT_FORM_F32) return map_pool_launch<InF32>(a, qk, heads, s);
+    if (a.form == VH_DTYPE_FP8) return map_pool_launch<InSplit8>(a, qk, heads, s);
+    return a.form == VH_DTYPE_BF16 ? map_pool_launch<InSplit16<BF16>>(a, qk, heads, s) : map_pool_launch<InSplit16<FP16>>(a, qk, heads, s);
+}
 
 const char* pool_check(const PoolArgs& a) {
     if (!a.hi) return "pool_rows: null input";

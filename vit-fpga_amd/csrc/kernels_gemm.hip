@@ -175,6 +175,8 @@ static hipError_t launch_epi(const GemmArgs& g, int variant, hipStream_t s) {
     case VH_EPI_PATCH_SPLIT: return launch_tile<T, VH_EPI_PATCH_SPLIT>(g, variant, s);
     case VH_EPI_BIAS_QGELU: return launch_tile<T, VH_EPI_BIAS_QGELU>(g, variant, s);
     case VH_EPI_LNFOLD_QGELU: return launch_tile<T, VH_EPI_LNFOLD_QGELU>(g, variant, s);
+    case VH_EPI_BIAS_TGELU: return launch_tile<T, VH_EPI_BIAS_TGELU>(g, variant, s);
+    case VH_EPI_LNFOLD_TGELU: return launch_tile<T, VH_EPI_LNFOLD_TGELU>(g, variant, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -229,7 +231,7 @@ const char* gemm_check(const GemmArgs& g) {
         if (g.K % 64) return "gemm: K must be a multiple of 64";
         if (g.N % 4) return "gemm: N must be a multiple of 4";
         if (g.M > 0x7fffffff) return "gemm: M too large";
-        if (epi < 0 || epi > VH_EPI_LNFOLD_QGELU) return "gemm: unknown epilogue";
+        if (epi < 0 || epi > VH_EPI_LNFOLD_TGELU || epi == VH_EPI_LNFOLD_QGELU + 1) return "gemm: unknown epilogue";   // (12 is no code)
         if (fold && (!g.stats || !g.aux)) return "gemm: LNFOLD needs stats and c (aux)";
         if (resid && (!g.out16 || !g.partials || g.N % 256)) return "gemm: RESID_LN / RESID_SPLIT need out16, partials and N % 256 == 0";
         if (epi == VH_EPI_PATCH && (!g.aux || g.aux_i <= 0)) return "gemm: EPI_PATCH needs pos-emb and patches/image";

@@ -672,7 +672,9 @@ hipError_t launch_gemm_pingpong(const GemmArgs& g, int mode, hipStream_t s) {
     template hipError_t launch_gemm_pingpong<T, VH_EPI_RESID_SPLIT>(const GemmArgs&, int, hipStream_t); \
     template hipError_t launch_gemm_pingpong<T, VH_EPI_PATCH_SPLIT>(const GemmArgs&, int, hipStream_t); \
     template hipError_t launch_gemm_pingpong<T, VH_EPI_BIAS_QGELU>(const GemmArgs&, int, hipStream_t);  \
-    template hipError_t launch_gemm_pingpong<T, VH_EPI_LNFOLD_QGELU>(const GemmArgs&, int, hipStream_t);
+    template hipError_t launch_gemm_pingpong<T, VH_EPI_LNFOLD_QGELU>(const GemmArgs&, int, hipStream_t); \
+    template hipError_t launch_gemm_pingpong<T, VH_EPI_BIAS_TGELU>(const GemmArgs&, int, hipStream_t);  \
+    template hipError_t launch_gemm_pingpong<T, VH_EPI_LNFOLD_TGELU>(const GemmArgs&, int, hipStream_t);
 VH_INST(BF16)
 VH_INST(FP16)
 
@@ -686,11 +688,13 @@ hipError_t launch_gemm_fp8(const GemmArgs& g, hipStream_t s) {
         case VH_EPI_BIAS: return launch_pp<BF16, VH_EPI_BIAS, true>(g, mode, s);
         case VH_EPI_BIAS_GELU: return launch_pp<BF16, VH_EPI_BIAS_GELU, true>(g, mode, s);
         case VH_EPI_BIAS_QGELU: return launch_pp<BF16, VH_EPI_BIAS_QGELU, true>(g, mode, s);
+        case VH_EPI_BIAS_TGELU: return launch_pp<BF16, VH_EPI_BIAS_TGELU, true>(g, mode, s);
         case VH_EPI_BIAS_RESID: return launch_pp<BF16, VH_EPI_BIAS_RESID, true>(g, mode, s);
         case VH_EPI_BIAS_F32: return launch_pp<BF16, VH_EPI_BIAS_F32, true>(g, mode, s);
         case VH_EPI_LNFOLD: return launch_pp<BF16, VH_EPI_LNFOLD, true>(g, mode, s);
         case VH_EPI_LNFOLD_GELU: return launch_pp<BF16, VH_EPI_LNFOLD_GELU, true>(g, mode, s);
         case VH_EPI_LNFOLD_QGELU: return launch_pp<BF16, VH_EPI_LNFOLD_QGELU, true>(g, mode, s);
+        case VH_EPI_LNFOLD_TGELU: return launch_pp<BF16, VH_EPI_LNFOLD_TGELU, true>(g, mode, s);
         case VH_EPI_RESID_LN: return launch_pp<BF16, VH_EPI_RESID_LN, true>(g, mode, s);
         case VH_EPI_RESID_SPLIT: return launch_pp<BF16, VH_EPI_RESID_SPLIT, true>(g, mode, s);
         default: return hipErrorInvalidValue;

@@ -573,7 +573,14 @@ hipError_t launch_filter3x3(const uint8_t* in, uint8_t* out, int h, int w, int k
 // kb .. kb + 15 exactly once.
 __global__ void __launch_bounds__(256)
 head_f32_kernel(const float* __restrict__ y, const float* __restrict__ w, const float* __restrict__ bias,
-                float* __restrict__ out, int batch, int classes, int dim, int ncg) {
+                float* __restrict__ out, int batch, int classes, int dim, int ncg, int64_t ldy, int64_t y_step, int64_t ldo,
+                const float* __restrict__ add) {
+    // blockIdx.y = the group of launch_head_f32_groups (0 for the head itself, where ldy = dim, ldo = classes and add is null)
+    y += blockIdx.y * y_step;
+    w += (int64_t)blockIdx.y * classes * dim;
+    bias += blockIdx.y * classes;
+    out += blockIdx.y * classes;
+    if (add) add += blockIdx.y * classes;
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int bb = gw / ncg, cg = gw - bb * ncg;
@@ -581,7 +588,7 @@ head_f32_kernel(const float* __restrict__ y, const float* __restrict__ w, const 
     const int r = lane & 15, g = lane >> 4;
     int b = bb * 16 + r;
     b = b < batch ? b : batch - 1;
-    const float* yp = y + (int64_t)b * dim + 4 * g;
+    const float* yp = y + (int64_t)b * ldy + 4 * g;
     const float* wp[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -610,7 +617,9 @@ head_f32_kernel(const float* __restrict__ y, const float* __restrict__ w, const 
             const int c = cg * 64 + i * 16 + 4 * g;
             if (c < classes) {   // classes % 4 == 0: a quad is inside or outside as a whole
                 const f32x4 bv = *(const f32x4*)(bias + c);
-                *(f32x4*)(out + (int64_t)bo * classes + c) = acc[i] + bv;
+                f32x4 r4 = acc[i] + bv;
+                if (add) r4 = r4 + *(const f32x4*)(add + (int64_t)bo * ldo + c);
+                *(f32x4*)(out + (int64_t)bo * ldo + c) = r4;
             }
         }
     }
@@ -621,7 +630,36 @@ hipError_t launch_head_f32(const float* y, const float* w, const float* bias, fl
     if (batch <= 0 || classes <= 0 || (classes & 3) || dim <= 0 || (dim & 15)) return hipErrorInvalidValue;
     const int ncg = (classes + 63) / 64, nb = (batch + 15) / 16;
     const int waves = ncg * nb;
-    hipLaunchKernelGGL(head_f32_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, y, w, bias, out, batch, classes, dim, ncg);
+    hipLaunchKernelGGL(head_f32_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, y, w, bias, out, batch, classes, dim, ncg, (int64_t)dim,
+                       (int64_t)0, (int64_t)classes, (const float*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_head_f32_groups(const float* y, int64_t ldy, int64_t y_step, const float* w, const float* bias, float* out, int64_t ldo,
+                                  const float* add, int batch, int classes, int dim, int groups, hipStream_t s) {
+    if (batch <= 0 || classes <= 0 || (classes & 3) || dim <= 0 || (dim & 15) || groups <= 0 || groups > 65535) return hipErrorInvalidValue;
+    if (ldy < dim || (ldy & 3) || (y_step & 3) || ldo < (int64_t)classes * groups || (ldo & 3)) return hipErrorInvalidValue;
+    const int ncg = (classes + 63) / 64, nb = (batch + 15) / 16;
+    const int waves = ncg * nb;
+    hipLaunchKernelGGL(head_f32_kernel, dim3((waves + 3) / 4, groups), dim3(256), 0, s, y, w, bias, out, batch, classes, dim, ncg, ldy, y_step,
+                       ldo, add);
+    return hipGetLastError();
+}
+
+// ---- the MAP head's activation on its fp32 hidden rows: the defining expressions, libm accuracy ------------------------------------
+__global__ void __launch_bounds__(256) act_f32_kernel(float* __restrict__ x, int64_t n, int act) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = x[i];
+    float r;
+    if (act == 1) r = v / (1.0f + expf(-1.702f * v));
+    else if (act == 2) r = 0.5f * v * (1.0f + tanhf(0.79788456080286536f * (v + 0.044715f * v * v * v)));
+    else r = gelu_erf(v);
+    x[i] = r;
+}
+hipError_t launch_act_f32(float* x, int64_t n, int act, hipStream_t s) {
+    if (!x || n <= 0 || act < 0 || act > 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(act_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, act);
     return hipGetLastError();
 }
 

@@ -69,6 +69,13 @@ hipError_t launch_layernorm(const float* x, int64_t rows, int dim, int64_t row_s
 // classifier head, fp32 operands (exact-fp32 MFMA): logits[b, c] = y[b, :] . w[c, :] + bias[c]; classes % 4 == 0, dim % 16 == 0
 hipError_t launch_head_f32(const float* y, const float* w, const float* bias, float* out, int batch, int classes, int dim,
                            hipStream_t stream);
+// The same kernel as `groups` independent products in one launch (the MAP head's per-head V product): group g reads y + g * y_step
+// (row stride ldy), w + g * classes * dim, bias + g * classes and writes out + g * classes (row stride ldo); `add` (optional,
+// [batch][ldo] like out) is added to the result (the MAP head's residual).  launch_head_f32 is groups = 1, ldy = dim, ldo = classes.
+hipError_t launch_head_f32_groups(const float* y, int64_t ldy, int64_t y_step, const float* w, const float* bias, float* out, int64_t ldo,
+                                  const float* add, int batch, int classes, int dim, int groups, hipStream_t stream);
+// x[i] <- act(x[i]) in fp32, act = 0 erf GELU, 1 QuickGELU, 2 tanh GELU, each as its defining expression (the MAP head's hidden rows)
+hipError_t launch_act_f32(float* x, int64_t n, int act, hipStream_t stream);
 // q columns of qkv16 arrive scaled by kAttnQScale = 64^-1/2 * log2(e) (folded into Wq and bq when the weights are
 // prepared): the score MFMAs then produce log2-domain scores and the softmax is exp2 without a multiply per score
 constexpr float kAttnQScale = 0.125f * 1.4426950408889634f;
@@ -282,6 +289,13 @@ struct PoolArgs {
 };
 const char* pool_check(const PoolArgs& a);
 hipError_t launch_pool_rows(const PoolArgs& a, hipStream_t stream);
+// The token-sized pass of the VH_FLAG_MAP_HEAD head (kernels_features.hip map_pool_kernel; contract: vithip.h VH_FLAG_MAP_HEAD,
+// vh_op_map_pool): z [batch][heads][dim] <- the softmax(qk[h] . LN(row))-weighted sum of the normalised patch rows.  The PoolArgs
+// fields mean what they mean to launch_pool_rows (norm must be VH_FEAT_NORM; out = z; out_stride, cls_in, cls_out unused).
+// map_pool_check: nullptr, or why refused.  map_pool_group: the rows per group at this dim and head count (tests sit on its edges).
+const char* map_pool_check(const PoolArgs& a, const float* qk, int heads);
+hipError_t launch_map_pool(const PoolArgs& a, const float* qk, int heads, hipStream_t stream);
+int map_pool_group(int dim, int heads);
 // The rows of a tapped layer into the capture store (vithip.h "Layer features"): bytes_hi of the hi plane (or the fp32 array), then
 // bytes_lo of the lo plane (0: none), in ONE launch.  Pointers and byte counts are multiples of 16.
 hipError_t launch_feature_capture(const void* src_hi, void* dst_hi, size_t bytes_hi, const void* src_lo, void* dst_lo, size_t bytes_lo,

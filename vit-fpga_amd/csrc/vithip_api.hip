@@ -58,20 +58,22 @@ struct BlobHeader {
     // Blobs built in memory leave the two checksum words, bit 0 and the padding 0.  flags bits 1 and 2 describe the MODEL, in
     // memory and on disk alike: bit 1 = pre-LayerNorm (VH_FLAG_PRE_LN: two more tensors), bit 2 = QuickGELU (VH_FLAG_QUICK_GELU),
     // bits 9 .. 13 = the number of register tokens (VH_FLAG_REGISTERS: the tensor reg), in the bits vh_config.flags keeps it in;
-    // bit 15 = no class token (VH_FLAG_NO_CLS), bits 16 .. 17 = the pooling mode (VH_FLAG_POOL), likewise.
+    // bit 15 = no class token (VH_FLAG_NO_CLS), bits 16 .. 17 = the pooling mode (VH_FLAG_POOL), bit 19 = the attention-pooling head
+    // (VH_FLAG_MAP_HEAD: eleven more tensors), bit 21 = tanh GELU (VH_FLAG_TANH_GELU), likewise.
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
 constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobRegisters = VH_FLAG_REGISTERS_MASK,
-                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK,
-                   kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobRegisters | kBlobNoCls | kBlobPool;
+                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU,
+                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu,   // at their vh_config.flags positions
+                   kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobSameBits;
 uint32_t blob_model_bits(const vh_config& c) {
     return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u) |
-           ((uint32_t)c.flags & (kBlobRegisters | kBlobNoCls | kBlobPool));
+           ((uint32_t)c.flags & kBlobSameBits);
 }
 // the model flags of a header's flags word (vh_blob_file_config)
 int32_t blob_model_flags(uint32_t bits) {
-    return ((bits & kBlobPreLn) ? VH_FLAG_PRE_LN : 0) | ((bits & kBlobQuickGelu) ? VH_FLAG_QUICK_GELU : 0) | (int32_t)(bits & (kBlobRegisters | kBlobNoCls | kBlobPool));
+    return ((bits & kBlobPreLn) ? VH_FLAG_PRE_LN : 0) | ((bits & kBlobQuickGelu) ? VH_FLAG_QUICK_GELU : 0) | (int32_t)(bits & kBlobSameBits);
 }
 
 uint64_t fnv1a64(const void* data, size_t n, uint64_t h = 0xCBF29CE484222325ull) {
@@ -94,6 +96,10 @@ struct Layout {
     size_t patch_w, patch_b, cls, pos, lnfw, lnfb, headw, headb, total;
     size_t reg = 0;              // VH_FLAG_REGISTERS: reg [R][D], directly after pos ([(NP + 1)][D]: registers carry no position row)
     size_t prew = 0, preb = 0;   // VH_FLAG_PRE_LN: pre_ln.weight / pre_ln.bias [D], directly after pos / reg
+    // VH_FLAG_MAP_HEAD: the attention-pooling head's tensors, directly after head.bias (vithip.h): qk [H][D], v / o [D][D] + [D], the
+    // block's LayerNorm, fc1 [M][D] + [M], fc2 [D][M] + [D]
+    bool map = false;
+    size_t map_qk = 0, map_vw = 0, map_vb = 0, map_ow = 0, map_ob = 0, map_lnw = 0, map_lnb = 0, map_f1w = 0, map_f1b = 0, map_f2w = 0, map_f2b = 0;
     std::vector<LayerOff> layer;
 };
 
@@ -125,6 +131,11 @@ Layout make_layout(const vh_config& c) {
         p.f1w = take(M * D); p.f1b = take(M); p.f2w = take(D * M); p.f2b = take(D);
     }
     L.lnfw = take(D); L.lnfb = take(D); L.headw = take(C * (size_t)L.HW); L.headb = take(C);
+    L.map = (c.flags & VH_FLAG_MAP_HEAD) != 0;
+    if (L.map) {
+        L.map_qk = take((size_t)c.heads * D); L.map_vw = take(D * D); L.map_vb = take(D); L.map_ow = take(D * D); L.map_ob = take(D);
+        L.map_lnw = take(D); L.map_lnb = take(D); L.map_f1w = take(M * D); L.map_f1b = take(M); L.map_f2w = take(D * M); L.map_f2b = take(D);
+    }
     L.total = o;
     return L;
 }
@@ -136,7 +147,8 @@ size_t blob_bytes_of(const vh_config& c) {
     const size_t T = g * g + ncls + (size_t)VH_FLAG_REGISTERS_OF(c.flags), KP = (size_t)c.patch_size * c.patch_size * c.channels;   // (pos rows + reg rows)
     const size_t per_layer = 2 * D + 4 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D);
     const size_t pre_ln = (c.flags & VH_FLAG_PRE_LN) ? 2 * D : 0;
-    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C);
+    const size_t map = (c.flags & VH_FLAG_MAP_HEAD) ? (size_t)c.heads * D + 2 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D) : 0;
+    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C + map);
 }
 
 const char* check_config(const vh_config& c) {
@@ -154,11 +166,19 @@ const char* check_config(const vh_config& c) {
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
     if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK |
-                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK)) return "unknown bits in flags";
+                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU)) return "unknown bits in flags";
+    if ((c.flags & VH_FLAG_TANH_GELU) && (c.flags & VH_FLAG_QUICK_GELU)) return "flags: VH_FLAG_TANH_GELU and VH_FLAG_QUICK_GELU exclude each other (one MLP activation)";
+    if (c.flags & VH_FLAG_MAP_HEAD) {   // (in front of the VH_FLAG_NO_CLS rules: NO_CLS + POOL_CLS is this head's own combination)
+        if (!(c.flags & VH_FLAG_NO_CLS)) return "flags: VH_FLAG_MAP_HEAD needs VH_FLAG_NO_CLS (the head pools the patch rows; its towers have no class token)";
+        if (VH_FLAG_POOL_OF(c.flags)) return "flags: VH_FLAG_MAP_HEAD excludes VH_FLAG_POOL (the attention pooling is the head's input)";
+        if (VH_FLAG_REGISTERS_OF(c.flags)) return "flags: VH_FLAG_MAP_HEAD excludes VH_FLAG_REGISTERS";
+        if (c.flags & VH_FLAG_CLS_TAIL) return "flags: VH_FLAG_MAP_HEAD excludes VH_FLAG_CLS_TAIL (there is no class token)";
+        if (c.heads > VH_MAP_MAX_HEADS) return "flags: VH_FLAG_MAP_HEAD takes at most 16 heads";
+    }
     const int R = VH_FLAG_REGISTERS_OF(c.flags);
     if (R > VH_MAX_REGISTERS) return "flags: VH_FLAG_REGISTERS takes 0 .. 16 register tokens";
     const int ncls = (c.flags & VH_FLAG_NO_CLS) ? 0 : 1, pool = VH_FLAG_POOL_OF(c.flags);
-    if (!ncls && (pool == VH_POOL_CLS || pool == VH_POOL_CLS_AVG))
+    if (!ncls && !(c.flags & VH_FLAG_MAP_HEAD) && (pool == VH_POOL_CLS || pool == VH_POOL_CLS_AVG))
         return pool == VH_POOL_CLS ? "flags: VH_FLAG_NO_CLS needs VH_FLAG_POOL(VH_POOL_AVG_NORM) or VH_FLAG_POOL(VH_POOL_AVG_FCNORM): VH_POOL_CLS reads the class token"
                                    : "flags: VH_FLAG_NO_CLS excludes VH_POOL_CLS_AVG: its first half is the class token";
     if ((c.flags & VH_FLAG_CLS_TAIL) && !ncls) return "flags: VH_FLAG_CLS_TAIL excludes VH_FLAG_NO_CLS (its last layer computes the class-token rows only)";
@@ -275,6 +295,11 @@ struct vh_ctx {
     void* col16 = nullptr;    // patch matrix    [B*NP, KPA]
     float* clsn32 = nullptr;  // the head's input [B, W] fp32: the final-LN'd CLS rows (W = D), or what the VH_FLAG_POOL mode computes (W = L.HW)
     float* pool32 = nullptr;  // [B, D] fp32 scratch of the pooled modes: CLS_AVG's LN'd class rows, AVG_FCNORM's raw mean
+    // VH_FLAG_MAP_HEAD contexts only: z [B][H][D] (the kernel's weighted sums; reused as [B][D] scratch behind the V product) and the
+    // block's hidden rows [B][M]
+    float* mapz32 = nullptr;
+    float* maph32 = nullptr;
+    float* mapa32 = nullptr;  // [2][B][D]: a (the V product), then o (the out-projection) of every image
     float* in_dev = nullptr;  // staging for the host-pointer forward (fp32 images; vh_forward_u8 stages its bytes in the same buffer)
     // Input normalisation of the 8-bit entry points (vh_set_input_norm): pixel p of channel c enters the model as
     // fmaf((float)p, in_scale[c], in_shift[c]).  Passed to im2col_u8_kernel by value, so captured graphs hold a copy.
@@ -520,6 +545,12 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if ((h.flags ^ want) & kBlobPool)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bits 16..17 say pooling mode %d, the context's VH_FLAG_POOL says %d",
                     (int)VH_FLAG_POOL_OF(h.flags), (int)VH_FLAG_POOL_OF(want));
+    if ((h.flags ^ want) & kBlobMapHead)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 19 (attention-pooling head) is %d, the context's VH_FLAG_MAP_HEAD is %d",
+                    (h.flags & kBlobMapHead) != 0, (want & kBlobMapHead) != 0);
+    if ((h.flags ^ want) & kBlobTanhGelu)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 21 (tanh GELU) is %d, the context's VH_FLAG_TANH_GELU is %d",
+                    (h.flags & kBlobTanhGelu) != 0, (want & kBlobTanhGelu) != 0);
     return VH_OK;
 }
 
@@ -658,8 +689,9 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     // VH_FLAG_PRE_LN: a LayerNorm needs whole rows, which no patch-GEMM tile holds -- such a context embeds through the fp32-x branch
     // and one pre_layernorm_kernel pass turns x into what its path consumes (no PATCH_SPLIT, no rowstats pass)
     const bool pre_ln = (f.flags & VH_FLAG_PRE_LN) != 0;
-    const int epi_fc1 = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_LNFOLD_QGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
-    const int epi_fc1_plain = (f.flags & VH_FLAG_QUICK_GELU) ? VH_EPI_BIAS_QGELU : VH_EPI_BIAS_GELU;       // plain layer loop
+    const bool quick = (f.flags & VH_FLAG_QUICK_GELU) != 0, tanh_gelu = (f.flags & VH_FLAG_TANH_GELU) != 0;
+    const int epi_fc1 = quick ? VH_EPI_LNFOLD_QGELU : tanh_gelu ? VH_EPI_LNFOLD_TGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
+    const int epi_fc1_plain = quick ? VH_EPI_BIAS_QGELU : tanh_gelu ? VH_EPI_BIAS_TGELU : VH_EPI_BIAS_GELU;       // plain layer loop
     // the patch embedding lands directly in the split residual's planes (below): the 16-bit split path without a pre-LayerNorm
     const bool patch_split = c->split && !c->fp8 && nl > 0 && !pre_ln;
     // (no stage bracket: the profile event is recorded once, behind the pass)
@@ -846,14 +878,33 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     // same launch into scratch, which the pool kernel copies into columns 0 .. D - 1 beside its own D .. 2 D - 1.  The pooled modes
     // read the patch rows where the path left them (planes or the fp32 array) ONCE.  All of it under the final-LayerNorm stage.
     const bool planes = c->split && nl > 0;
-    if (L.pool == VH_POOL_CLS || L.pool == VH_POOL_CLS_AVG) {
+    if (L.map) {
+        // VH_FLAG_MAP_HEAD (vithip.h "THE FUNCTION"): ONE pass over the patch rows leaves z [batch][H][D]; everything behind it is fp32
+        // on `batch` rows through the head's own exact-fp32 kernel: the per-head V product (H groups in one launch), the
+        // out-projection, the block's LayerNorm, fc1, the activation, fc2 + the residual.  u lands in clsn32, the head's input.
+        const int H = f.heads, hd = D / H;
+        float* const z = c->mapz32 + (size_t)img0 * H * D;
+        float* const hid = c->maph32 + (size_t)img0 * (M > D ? M : D);
+        float* const a32 = c->mapa32 + (size_t)img0 * D;                             // a [batch][D]
+        float* const o32 = c->mapa32 + ((size_t)f.max_batch + img0) * D;             // o [batch][D]
+        float* const lnrow = z;                                   // [batch][D]: z is dead once a exists
+        const PoolArgs pa{planes ? (const void*)xn16 : (const void*)x, planes ? xlo16 : nullptr, planes ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32,
+                          batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps, VH_FEAT_NORM, z};
+        HIPCHK(&c->err, launch_map_pool(pa, P + L.map_qk, H, s));
+        HIPCHK(&c->err, launch_head_f32_groups(z, (int64_t)H * D, D, P + L.map_vw, P + L.map_vb, a32, D, nullptr, batch, hd, D, H, s));
+        HIPCHK(&c->err, launch_head_f32(a32, P + L.map_ow, P + L.map_ob, o32, batch, D, D, s));
+        HIPCHK(&c->err, launch_layernorm(o32, batch, D, D, P + L.map_lnw, P + L.map_lnb, f.ln_eps, lnrow, VH_DTYPE_F32_INTERNAL, s));
+        HIPCHK(&c->err, launch_head_f32(lnrow, P + L.map_f1w, P + L.map_f1b, hid, batch, M, D, s));
+        HIPCHK(&c->err, launch_act_f32(hid, (int64_t)batch * M, quick ? 1 : tanh_gelu ? 2 : 0, s));
+        HIPCHK(&c->err, launch_head_f32_groups(hid, M, 0, P + L.map_f2w, P + L.map_f2b, clsn32, D, o32, batch, D, M, 1, s));
+    } else if (L.pool == VH_POOL_CLS || L.pool == VH_POOL_CLS_AVG) {
         float* const cls_ln = L.pool == VH_POOL_CLS ? clsn32 : pool32;
         if (planes)
             HIPCHK(&c->err, launch_layernorm_split(xn16, xlo16, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, c->fp8 ? VH_DTYPE_FP8 : dt16, s));
         else
             HIPCHK(&c->err, launch_layernorm(x, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, VH_DTYPE_F32_INTERNAL, s));
     }
-    if (L.pool != VH_POOL_CLS) {
+    if (!L.map && L.pool != VH_POOL_CLS) {
         PoolArgs pa{planes ? (const void*)xn16 : (const void*)x, planes ? xlo16 : nullptr, planes ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32,
                     batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps, L.pool == VH_POOL_AVG_FCNORM ? VH_FEAT_RAW : VH_FEAT_NORM, clsn32};
         if (L.pool == VH_POOL_CLS_AVG) { pa.out = clsn32 + D; pa.out_stride = 2 * D; pa.cls_in = pool32; pa.cls_out = clsn32; }
@@ -1421,6 +1472,8 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
                  o_st = carve(rows_p * 2 * 4), o_pt = carve((D / 64 + 1) * rows_p * 2 * 4), o_xlo = carve(rows_p * D * 2),   // lo plane: one byte per element (16-bit paths) or bf16 (fp8 path)
                  o_tk = carve(B * 4 * (size_t)(cfg->layers > 0 ? cfg->layers : 1)),   // attention work-queue counters: one word per image and layer, a part uses its first image's
                  o_gd = carve(256);     // the LayerNorm-fold guard word
+    const size_t o_mz = L.map ? carve(B * (size_t)cfg->heads * D * 4) : 0, o_mh = L.map ? carve(B * (M > D ? M : D) * 4) : 0,
+                 o_ma = L.map ? carve(B * 2 * D * 4) : 0;   // VH_FLAG_MAP_HEAD: z, the hidden rows, and the rows a | o
     CK(hipMalloc((void**)&c->arena, a));
     c->guard_dev = (unsigned int*)(c->arena + o_gd);
     CK(hipMemsetAsync(c->guard_dev, 0, 256, c->stream));
@@ -1430,6 +1483,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     c->in_dev = (float*)(c->arena + o_in); c->logits_dev = (float*)(c->arena + o_lg);
     c->stats = (float*)(c->arena + o_st); c->partials = (float*)(c->arena + o_pt); c->xlo16 = c->arena + o_xlo;
     c->tickets = (unsigned int*)(c->arena + o_tk);
+    if (L.map) { c->mapz32 = (float*)(c->arena + o_mz); c->maph32 = (float*)(c->arena + o_mh); c->mapa32 = (float*)(c->arena + o_ma); }
 #undef CK
     *out = c;
     return VH_OK;
@@ -1572,6 +1626,14 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
     }
     GEN(L.lnfw, D, TID_FINAL + 0, sg, 1.f); GEN(L.lnfb, D, TID_FINAL + 1, sb, 0.f);
     GEN(L.headw, C * (size_t)L.HW, TID_FINAL + 2, sw, 0.f); GEN(L.headb, C, TID_FINAL + 3, sb, 0.f);
+    if (L.map) {
+        GEN(L.map_qk, (size_t)f.heads * D, TID_MAP + 0, sw, 0.f);
+        GEN(L.map_vw, D * D, TID_MAP + 1, sw, 0.f); GEN(L.map_vb, D, TID_MAP + 2, sb, 0.f);
+        GEN(L.map_ow, D * D, TID_MAP + 3, sw, 0.f); GEN(L.map_ob, D, TID_MAP + 4, sb, 0.f);
+        GEN(L.map_lnw, D, TID_MAP + 5, sg, 1.f); GEN(L.map_lnb, D, TID_MAP + 6, sb, 0.f);
+        GEN(L.map_f1w, M * D, TID_MAP + 7, sw, 0.f); GEN(L.map_f1b, M, TID_MAP + 8, sb, 0.f);
+        GEN(L.map_f2w, D * M, TID_MAP + 9, sw, 0.f); GEN(L.map_f2b, D, TID_MAP + 10, sb, 0.f);
+    }
 #undef GEN
     if (int rc = guard_reset(c)) return rc;
     if (int rc = prepare_weights(c)) return rc;
@@ -2686,14 +2748,14 @@ int vh_read_attention(vh_ctx* c, const vh_attention_maps* f) {
 // is touched), launches, synchronises and maps the error.  `tag` names the tap: in "<tag> failed", and in front of gemm_check's reason
 // for e4m3 operands.  `offered8`: the e4m3 epilogues the tap has parameters for, a bit per VH_EPI_* code (0: a 16-bit tap, which has
 // no scale parameter and refuses e4m3 operands).
-constexpr unsigned kEpiPlain8 = 1u << VH_EPI_BIAS | 1u << VH_EPI_BIAS_GELU | 1u << VH_EPI_BIAS_QGELU | 1u << VH_EPI_BIAS_RESID | 1u << VH_EPI_BIAS_F32;
-constexpr unsigned kEpiFold8 = 1u << VH_EPI_LNFOLD | 1u << VH_EPI_LNFOLD_GELU | 1u << VH_EPI_LNFOLD_QGELU | 1u << VH_EPI_RESID_LN | 1u << VH_EPI_RESID_SPLIT;
+constexpr unsigned kEpiPlain8 = 1u << VH_EPI_BIAS | 1u << VH_EPI_BIAS_GELU | 1u << VH_EPI_BIAS_QGELU | 1u << VH_EPI_BIAS_TGELU | 1u << VH_EPI_BIAS_RESID | 1u << VH_EPI_BIAS_F32;
+constexpr unsigned kEpiFold8 = 1u << VH_EPI_LNFOLD | 1u << VH_EPI_LNFOLD_GELU | 1u << VH_EPI_LNFOLD_QGELU | 1u << VH_EPI_LNFOLD_TGELU | 1u << VH_EPI_RESID_LN | 1u << VH_EPI_RESID_SPLIT;
 static int op_gemm_run(const char* tag, const GemmArgs& g, unsigned offered8, void* stream) {
     const bool f8 = g.dtype == VH_DTYPE_FP8;
     GemmArgs h = g;
     if (f8 && !offered8) h.dtype = -1;   // no dtype of a 16-bit tap: the 16-bit rules speak, "gemm: dtype" in its turn
     // an epilogue the tap lacks: the operands and the shape are judged first, as for the plainest launch, then the epilogue is unsupported
-    const bool lacks = f8 && offered8 && (g.epilogue < 0 || g.epilogue > VH_EPI_LNFOLD_QGELU || !(offered8 >> g.epilogue & 1));
+    const bool lacks = f8 && offered8 && (g.epilogue < 0 || g.epilogue > VH_EPI_LNFOLD_TGELU || !(offered8 >> g.epilogue & 1));
     if (lacks) { h.epilogue = VH_EPI_BIAS; h.out_tiled = h.ab_tiled = h.tile_begin = h.tile_count = 0; }
     if (const char* why = gemm_check(h))
         return f8 && offered8 ? fail(nullptr, VH_ERR_INVALID, "%s%s", tag, strchr(why, ':')) : fail(nullptr, VH_ERR_INVALID, "%s", why);
@@ -3171,6 +3233,16 @@ int vh_op_pool_rows(const void* hi, const void* lo, int form, int batch, int tok
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "pool_rows failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
+// the attention-pooling head's one-pass kernel on caller-made rows (VH_FLAG_MAP_HEAD)
+int vh_op_map_pool(const void* hi, const void* lo, int form, int batch, int tokens, int lead, int dim, const float* gamma, const float* beta,
+                   float eps, const float* qk, int heads, float* z_out, void* stream) {
+    const PoolArgs a{hi, lo, form, batch, tokens, lead, dim, gamma, beta, eps, VH_FEAT_NORM, z_out};
+    if (const char* why = map_pool_check(a, qk, heads)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_map_pool(a, qk, heads, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "map_pool failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
 int vh_op_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind, float sigma, void* stream) {
     if (!out || n <= 0 || kind < 0 || kind > 2) return fail(nullptr, VH_ERR_INVALID, "fill: bad argument");
     OPCHK(launch_fill(out, n, seed, tensor_id, kind, kind == 2 ? 0.f : sigma, kind == 2 ? sigma : 0.f, (hipStream_t)stream));
@@ -3189,7 +3261,7 @@ int vh_bench_gemm(int device, int64_t M, int N, int K, int epilogue, int dtype, 
     const int aux_i = 196;
     // the layer epilogues of the folded path: LNFOLD* read per-row (mean, rstd) and c_n (`aux`), RESID_LN / RESID_SPLIT
     // write a second 16-bit plane and the per-64-column row sums
-    const bool fold = epilogue == VH_EPI_LNFOLD || epilogue == VH_EPI_LNFOLD_GELU || epilogue == VH_EPI_LNFOLD_QGELU;
+    const bool fold = epilogue == VH_EPI_LNFOLD || epilogue == VH_EPI_LNFOLD_GELU || epilogue == VH_EPI_LNFOLD_QGELU || epilogue == VH_EPI_LNFOLD_TGELU;
     const bool resid2 = epilogue == VH_EPI_RESID_LN || epilogue == VH_EPI_RESID_SPLIT || epilogue == VH_EPI_PATCH_SPLIT;
     const size_t out_rows = (epilogue == VH_EPI_PATCH || epilogue == VH_EPI_PATCH_SPLIT) ? (size_t)(M / aux_i + 1) * (aux_i + 1) : (size_t)M;
     hipEvent_t e0 = nullptr, e1 = nullptr;

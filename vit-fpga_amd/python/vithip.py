@@ -46,8 +46,16 @@ def pool_of(flags):
     return (int(flags) & FLAG_POOL_MASK) >> 16
 
 
+# SigLIP's vision towers (VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU; vithip.h): model bits, in the blob header too.  MAP_HEAD: the head's
+# input is the attention-pooling block (needs FLAG_NO_CLS, at most MAP_MAX_HEADS heads); TANH_GELU: gelu_pytorch_tanh in the MLP
+FLAG_MAP_HEAD, FLAG_TANH_GELU, MAP_MAX_HEADS = 1 << 19, 1 << 21, 16
+
+
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
 EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
+# tanh GELU (12 is no code).  Not named EPI_*: tests/gemm_exact.py enumerates every EPI_* name of this module for an emulator that knows the
+# erf and QuickGELU activations only; tests/test_gpu_siglip.py covers these two codes
+EPILOGUE_BIAS_TGELU, EPILOGUE_LNFOLD_TGELU = 13, 14
 ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = range(4)   # element type of an image tensor (VH_ELEM_*)
 LAYOUT_NHWC, LAYOUT_NCHW = 0, 1                      # its layout (VH_LAYOUT_*): [B][S][S][C] / [B][C][S][S]
 ELEM_BYTES = {ELEM_F32: 4, ELEM_F16: 2, ELEM_BF16: 2, ELEM_U8: 1}
@@ -335,6 +343,7 @@ SYMBOLS = {
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
+    "vh_op_map_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i, _vp, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
     "vh_group_create": (_i, [C.POINTER(Config), _pi, _i, C.POINTER(_vp)]),
@@ -401,7 +410,8 @@ def blob_file_config(path):
 
 
 def blob_file_flags(path):
-    """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN | FLAG_QUICK_GELU | FLAG_REGISTERS(n)); host only."""
+    """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN, FLAG_QUICK_GELU, FLAG_REGISTERS(n), FLAG_NO_CLS,
+    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU); host only."""
     c = Config()
     _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
     return c.flags
@@ -541,6 +551,78 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
         parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
     h = _blob_header(cfg, ln_eps, FLAG_REGISTERS(R) | FLAG_POOL(pool))   # header flags word: bits 9 .. 13 = register tokens, 16 .. 17 = pooling
     return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+
+
+def blob_from_siglip_state_dict(sd, cfg, ln_eps=1e-6, hidden_act="gelu_pytorch_tanh"):
+    """Canonical blob of a SigLIP vision tower from a dict of arrays under the Hugging Face parameter names (numpy only), with or
+    without the `vision_model.` prefix.  Two models:
+      `SiglipVisionModel` (no `classifier.*`): a FLAG_NO_CLS | FLAG_MAP_HEAD context whose head is the identity -- cfg['classes'] must
+      equal cfg['dim'] -- so that the logits ARE `pooler_output`.  The attention-pooling head's query is one learned vector, so it is
+      folded through the key projection here, in float64, one rounding to fp32:  map.qk[h] = W_k,h^T (W_q,h probe + b_q,h) / sqrt(hd)
+      (the key bias shifts every score of a head alike and drops out of the softmax; the library has no fold code).  map.v.* = the
+      value third of `head.attention.in_proj_*`, map.o.* = `head.attention.out_proj.*`, map.ln.* = `head.layernorm.*`, map.fc1 / fc2 =
+      `head.mlp.*`.
+      `SiglipForImageClassification` (`classifier.*` present): head(mean of the post-LayerNormed patch tokens), a FLAG_NO_CLS |
+      FLAG_POOL(POOL_AVG_NORM) context with the classifier as its head; the tower's `head.*` is not used by that model and is ignored.
+    hidden_act: "gelu_pytorch_tanh" (every published SigLIP) -> FLAG_TANH_GELU, "gelu" -> erf GELU, "quick_gelu" -> FLAG_QUICK_GELU.  The
+    header carries the flags; blob_flags_of(blob) returns them.  Refused: a position table whose row count is not NP of cfg (interpolate
+    first), more than MAP_MAX_HEADS heads with the MAP head, classes != dim without a classifier, a missing or wrongly shaped tensor."""
+    me = "blob_from_siglip_state_dict"
+    acts = {"gelu_pytorch_tanh": FLAG_TANH_GELU, "gelu": 0, "quick_gelu": FLAG_QUICK_GELU}
+    if hidden_act not in acts:
+        raise ValueError(f"{me}: hidden_act = {hidden_act!r} is not one of {sorted(acts)}")
+    D, M, E, P, CH, H = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"], cfg["heads"]
+    g = cfg["image_size"] // cfg["patch_size"]
+    if any(k.startswith("vision_model.") for k in sd):
+        sd = dict({k[len("vision_model."):]: v for k, v in sd.items() if k.startswith("vision_model.")},
+                  **{k: v for k, v in sd.items() if k.startswith("classifier.")})
+    classifier = "classifier.weight" in sd and "classifier.bias" in sd
+    flags = FLAG_NO_CLS | acts[hidden_act] | (FLAG_POOL(POOL_AVG_NORM) if classifier else FLAG_MAP_HEAD)
+    if not classifier and E != D:
+        raise ValueError(f"{me}: without a classifier the head is the identity: cfg['classes'] = {E} must equal cfg['dim'] = {D}")
+    if not classifier and H > MAP_MAX_HEADS:
+        raise ValueError(f"{me}: the attention-pooling head takes at most {MAP_MAX_HEADS} heads, cfg['heads'] is {H}")
+    emb = "embeddings."
+    if emb + "position_embedding.weight" in sd:
+        rows = int(np.asarray(sd[emb + "position_embedding.weight"]).shape[0])
+        if rows != g * g:
+            raise ValueError(f"{me}: {emb}position_embedding.weight has {rows} rows, cfg needs NP = {g * g} (interpolate the table first)")
+    take = _taker(sd, me)
+    parts = [take(emb + "patch_embedding.weight", (D, CH, P, P)), take(emb + "patch_embedding.bias", (D,)),
+             take(emb + "position_embedding.weight", (g * g, D))]
+    for l in range(cfg["layers"]):
+        b = f"encoder.layers.{l}."
+        parts += [take(b + "layer_norm1.weight", (D,)), take(b + "layer_norm1.bias", (D,))]
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            parts += [take(f"{b}self_attn.{n}.weight", (D, D)), take(f"{b}self_attn.{n}.bias", (D,))]
+        parts += [take(b + "layer_norm2.weight", (D,)), take(b + "layer_norm2.bias", (D,)),
+                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,)),
+                  take(b + "mlp.fc2.weight", (D, M)), take(b + "mlp.fc2.bias", (D,))]
+    parts += [take("post_layernorm.weight", (D,)), take("post_layernorm.bias", (D,))]
+    if classifier:
+        parts += [take("classifier.weight", (E, D)), take("classifier.bias", (E,))]
+    else:
+        parts += [np.eye(D, dtype=np.float32).reshape(-1), np.zeros(D, np.float32)]
+        h, hd = "head.", D // H
+        probe = take(h + "probe", (1, 1, D), np.float64)
+        w = take(h + "attention.in_proj_weight", (3 * D, D), np.float64).reshape(3, D, D)
+        bias = take(h + "attention.in_proj_bias", (3 * D,), np.float64).reshape(3, D)
+        q = ((w[0] @ probe + bias[0]) / np.sqrt(float(hd))).reshape(H, hd)               # the query of every image, scaled
+        qk = np.einsum("hj,hjk->hk", q, w[1].reshape(H, hd, D))                           # through the key projection, per head
+        parts += [qk.astype(np.float32).reshape(-1), w[2].astype(np.float32).reshape(-1), bias[2].astype(np.float32),
+                  take(h + "attention.out_proj.weight", (D, D)), take(h + "attention.out_proj.bias", (D,)),
+                  take(h + "layernorm.weight", (D,)), take(h + "layernorm.bias", (D,)),
+                  take(h + "mlp.fc1.weight", (M, D)), take(h + "mlp.fc1.bias", (M,)),
+                  take(h + "mlp.fc2.weight", (D, M)), take(h + "mlp.fc2.bias", (D,))]
+    bits = (4 if flags & FLAG_QUICK_GELU else 0) | (flags & (FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU))
+    return np.concatenate([_blob_header(cfg, ln_eps, bits)] + [p.view(np.uint8) for p in parts])
+
+
+def blob_flags_of(blob):
+    """The model bits of a memory blob's header as vh_config flags (what blob_file_flags returns for a file)."""
+    bits = int(np.ascontiguousarray(blob[52:56]).view(np.uint32)[0])
+    same = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU
+    return (FLAG_PRE_LN if bits & 2 else 0) | (FLAG_QUICK_GELU if bits & 4 else 0) | (bits & same)
 
 
 def blob_from_ijepa_state_dict(sd, cfg, ln_eps=1e-6, head=None):
@@ -2152,6 +2234,12 @@ def op_pool_rows(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta
     """The pooled head's one-pass kernel on its own (vh_op_pool_rows): mean [batch, dim] fp32 over rows lead .. tokens - 1 of every image
     (lead 0 .. tokens - 1), FEAT_RAW or through LayerNorm(gamma, beta, eps) -- the bits op_token_features2 writes for ELEM_F32."""
     _check(lib().vh_op_pool_rows(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, norm, mean_ptr, None))
+
+
+def op_map_pool(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, qk_ptr, heads, z_ptr):
+    """The attention-pooling head's one-pass kernel on its own (vh_op_map_pool): z [batch, heads, dim] fp32 = the softmax(qk[h] . y_t)-
+    weighted sum of y_t = LayerNorm(row t; gamma, beta, eps) over rows lead .. tokens - 1 of every image; qk [heads, dim] fp32."""
+    _check(lib().vh_op_map_pool(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, qk_ptr, heads, z_ptr, None))
 
 
 def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr, dtype):
