@@ -217,6 +217,29 @@ typedef struct vh_config {
 #define VH_FLAG_TANH_GELU (1 << 21)
 #define VH_MAP_MAX_HEADS 16
 
+/* Rotary position embedding (DINOv3 ViT-S/B/L; the mechanism of EVA-02 and Pixtral-style towers): ONE MODEL switch, in bit 23 of
+ * flags and, at the same position, of the blob header's flags word; a blob whose bit differs from the context's is refused with a
+ * message that names the bit.  With the bit clear nothing changes: not one launch.
+ *   VH_FLAG_ROPE   q and k of every patch row are rotated by per-position angles in every layer, in front of attention.  The library
+ *                  holds no trigonometry: the angles are DATA.  Excludes VH_FLAG_CLS_TAIL (its one-query kernel reads q and k of the
+ *                  last layer on a path of its own), with a message of its own.  Every accepted head dim has hd / 2 a multiple of 8.
+ *   Blob tensors of a ROPE context, both fp32, at the VERY END of the blob (behind head.bias, and behind the map.* tensors where
+ *   there are any: no other offset moves), NP = patch rows, hd = dim / heads:
+ *     rope.cos [NP][hd / 2], rope.sin [NP][hd / 2].
+ *     vh_init_weights_seeded: tensor id 0x7030 (the ANGLES a[i] = pi * uniform[-1, 1) of the generator, i = p * hd / 2 + d); rope.cos =
+ *     (float)cos((double)a), rope.sin = (float)sin((double)a): a synthetic model is a true rotation.  pos stays in the blob (a
+ *     converter of a model without a position table writes zeros; a model with both kinds of position needs nothing more).
+ *   THE FUNCTION, per layer, per image and per head, on q and on k alike (v is not touched).  Row lead + p is patch row p; the `lead`
+ *   rows in front (class token, registers) pass through untouched, bit for bit.  For d < hd / 2, c = rope.cos[p][d], s = rope.sin[p][d]:
+ *     out[d]          = x[d] c - x[d + hd / 2] s
+ *     out[d + hd / 2] = x[d + hd / 2] c + x[d] s            (Hugging Face's rotate_half form)
+ *   The softmax scale the library folds into q is a scalar and commutes with the rotation.
+ *   ROUNDING: x is the STORED 16-bit q or k the projection wrote (one rounding, as in every model); it is widened to fp32, rotated in
+ *   fp32 as fmaf(x[d], c, -(x[d + hd/2] s)) and fmaf(x[d + hd/2], c, x[d] s), and rounded ONCE (RNE) back to the same 16-bit type, in
+ *   place.  A ROPE model's q and k therefore carry one rounding more than another model's.  fp8 contexts keep q|k|v in bf16.
+ *   Attention maps of a ROPE context are of the rotated q and k: the model's own.  An image's bits depend on its rows alone. */
+#define VH_FLAG_ROPE (1 << 23)
+
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
 
@@ -257,7 +280,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model, bit 23 = VH_FLAG_ROPE model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -277,7 +300,7 @@ int vh_export_weights_device(vh_ctx* ctx, void* dev_blob, size_t nbytes);
  *   vh_blob_file_config: host only (no device needed) -- validates magic / shape / file length and fills the model
  *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create;
  *                        cfg->flags = the model bits of the header: VH_FLAG_PRE_LN, VH_FLAG_QUICK_GELU, VH_FLAG_REGISTERS(n), VH_FLAG_NO_CLS,
- *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU);
+ *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU, VH_FLAG_ROPE);
  *   vh_save_weights_file: writes <path>.tmp then renames; vh_load_weights_file: verifies length, shape, checksum. */
 int vh_blob_file_config(const char* path, vh_config* cfg);
 /* host only: the file as a MEMORY blob (what vh_load_weights takes): length, header and checksum verified, checksum
@@ -1304,6 +1327,14 @@ int vh_op_pool_rows(const void* hi_or_x32_dev, const void* lo_dev, int form, int
 int vh_op_map_pool(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int lead, int dim,
                    const float* gamma_dev, const float* beta_dev, float eps, const float* qk_dev, int heads, float* z_out_dev,
                    void* stream);
+/* The rotation of a VH_FLAG_ROPE context on its own ("THE FUNCTION" at VH_FLAG_ROPE), in place on caller-made q|k|v of `dtype`
+ * (VH_DTYPE_BF16 / VH_DTYPE_FP16) elements: q and k of rows lead .. tokens - 1 of every image and head are rotated by cos_dev / sin_dev
+ * [tokens - lead][head_dim / 2] fp32; v, the lead rows and every row beyond batch * tokens are never written.
+ * hm_rows = 0: row-major [batch * tokens][3 * heads * head_dim], head_dim 32, 48, .. 128;  hm_rows != 0: head-major
+ * [3][heads][hm_rows][64], head_dim 64 only, hm_rows >= batch * tokens.  16-byte accesses: qkv16_dev is 16-byte aligned.  Every argument
+ * is checked before a device is touched, each refusal with a message of its own. */
+int vh_op_rope(void* qkv16_dev, int dtype, int batch, int tokens, int heads, int head_dim, int lead, int64_t hm_rows,
+               const float* cos_dev, const float* sin_dev, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,
  * 2 = constant `sigma` */
 int vh_op_fill(float* out_dev, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,

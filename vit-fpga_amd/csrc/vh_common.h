@@ -219,6 +219,6 @@ constexpr double kIH4Std = 37837.22725;
 
 // tensor ids of the canonical blob (same numbers as oracle/ and tests/, by specification)
 enum : uint32_t { TID_PATCH_W = 1, TID_PATCH_B = 2, TID_CLS = 3, TID_POS = 4, TID_PRE_LN_W = 5, TID_PRE_LN_B = 6, TID_REG = 7, TID_LAYER0 = 16,
-                  TID_FINAL = 0x7000, TID_MAP = 0x7010, TID_IMAGES = 0x100 };
+                  TID_FINAL = 0x7000, TID_MAP = 0x7010, TID_ROPE = 0x7030, TID_IMAGES = 0x100 };
 
 }  // namespace vh

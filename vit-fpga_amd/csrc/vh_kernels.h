@@ -114,6 +114,14 @@ constexpr int kAttnMapsMaxQueries = 17;   // the class token + up to 16 register
 const char* attention_probs_check(int64_t in_hm_rows, int batch, int tokens, int heads, int head_dim, int Q, int dtype);
 hipError_t launch_attention_probs(const void* qkv16, int64_t in_hm_rows, int batch, int tokens, int heads, int head_dim, int Q, int dtype,
                                   float* probs, hipStream_t stream);
+// Rotary position embedding (kernels_rope.hip; contract: vithip.h VH_FLAG_ROPE, vh_op_rope): q and k of rows lead .. tokens - 1 of
+// every image and head are rotated in place by cos_t / sin_t [tokens - lead][head_dim / 2] fp32 (16-byte aligned, like qkv16).  The
+// layouts are launch_attention_probs's: row-major (hm_rows == 0) at head dims 32, 48, ..., 128, head-major at head dim 64.  v, the lead
+// rows and rows beyond batch * tokens are never written.  No allocation (graph capture, split batches).  rope_check: nullptr, or why.
+const char* rope_check(const void* qkv16, int dtype, int batch, int tokens, int heads, int head_dim, int lead, int64_t hm_rows,
+                       const float* cos_t, const float* sin_t);
+hipError_t launch_rope(void* qkv16, int dtype, int batch, int tokens, int heads, int head_dim, int lead, int64_t hm_rows, const float* cos_t,
+                       const float* sin_t, hipStream_t stream);
 const char* attention_readout_check(int batch, int heads, int Q, int tokens, int lead, int elem, int keys);
 hipError_t launch_attention_readout(const float* store, int batch, int heads, int Q, int tokens, int lead, int elem, int keys, void* probs_out,
                                     void* mean_out, hipStream_t stream);

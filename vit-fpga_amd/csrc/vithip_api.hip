@@ -59,13 +59,14 @@ struct BlobHeader {
     // memory and on disk alike: bit 1 = pre-LayerNorm (VH_FLAG_PRE_LN: two more tensors), bit 2 = QuickGELU (VH_FLAG_QUICK_GELU),
     // bits 9 .. 13 = the number of register tokens (VH_FLAG_REGISTERS: the tensor reg), in the bits vh_config.flags keeps it in;
     // bit 15 = no class token (VH_FLAG_NO_CLS), bits 16 .. 17 = the pooling mode (VH_FLAG_POOL), bit 19 = the attention-pooling head
-    // (VH_FLAG_MAP_HEAD: eleven more tensors), bit 21 = tanh GELU (VH_FLAG_TANH_GELU), likewise.
+    // (VH_FLAG_MAP_HEAD: eleven more tensors), bit 21 = tanh GELU (VH_FLAG_TANH_GELU), bit 23 = rotary position embedding (VH_FLAG_ROPE: two
+    // more tensors, at the very end), likewise.
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
 constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobRegisters = VH_FLAG_REGISTERS_MASK,
-                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU,
-                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu,   // at their vh_config.flags positions
+                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU, kBlobRope = VH_FLAG_ROPE,
+                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu | kBlobRope,   // at their vh_config.flags positions
                    kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobSameBits;
 uint32_t blob_model_bits(const vh_config& c) {
     return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u) |
@@ -100,6 +101,9 @@ struct Layout {
     // block's LayerNorm, fc1 [M][D] + [M], fc2 [D][M] + [D]
     bool map = false;
     size_t map_qk = 0, map_vw = 0, map_vb = 0, map_ow = 0, map_ob = 0, map_lnw = 0, map_lnb = 0, map_f1w = 0, map_f1b = 0, map_f2w = 0, map_f2b = 0;
+    // VH_FLAG_ROPE: rope.cos / rope.sin [NP][hd / 2], the last two tensors of the blob (vithip.h)
+    bool rope = false;
+    size_t rope_cos = 0, rope_sin = 0;
     std::vector<LayerOff> layer;
 };
 
@@ -136,6 +140,8 @@ Layout make_layout(const vh_config& c) {
         L.map_qk = take((size_t)c.heads * D); L.map_vw = take(D * D); L.map_vb = take(D); L.map_ow = take(D * D); L.map_ob = take(D);
         L.map_lnw = take(D); L.map_lnb = take(D); L.map_f1w = take(M * D); L.map_f1b = take(M); L.map_f2w = take(D * M); L.map_f2b = take(D);
     }
+    L.rope = (c.flags & VH_FLAG_ROPE) != 0;
+    if (L.rope) { const size_t n = (size_t)L.NP * (size_t)(c.dim / c.heads / 2); L.rope_cos = take(n); L.rope_sin = take(n); }
     L.total = o;
     return L;
 }
@@ -148,7 +154,8 @@ size_t blob_bytes_of(const vh_config& c) {
     const size_t per_layer = 2 * D + 4 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D);
     const size_t pre_ln = (c.flags & VH_FLAG_PRE_LN) ? 2 * D : 0;
     const size_t map = (c.flags & VH_FLAG_MAP_HEAD) ? (size_t)c.heads * D + 2 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D) : 0;
-    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C + map);
+    const size_t rope = (c.flags & VH_FLAG_ROPE) ? 2 * g * g * (D / (size_t)c.heads / 2) : 0;
+    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C + map + rope);
 }
 
 const char* check_config(const vh_config& c) {
@@ -166,7 +173,8 @@ const char* check_config(const vh_config& c) {
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
     if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK |
-                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU)) return "unknown bits in flags";
+                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU | VH_FLAG_ROPE)) return "unknown bits in flags";
+    if ((c.flags & VH_FLAG_ROPE) && (c.flags & VH_FLAG_CLS_TAIL)) return "flags: VH_FLAG_ROPE excludes VH_FLAG_CLS_TAIL (the tail's one-query attention kernel reads unrotated q and k)";
     if ((c.flags & VH_FLAG_TANH_GELU) && (c.flags & VH_FLAG_QUICK_GELU)) return "flags: VH_FLAG_TANH_GELU and VH_FLAG_QUICK_GELU exclude each other (one MLP activation)";
     if (c.flags & VH_FLAG_MAP_HEAD) {   // (in front of the VH_FLAG_NO_CLS rules: NO_CLS + POOL_CLS is this head's own combination)
         if (!(c.flags & VH_FLAG_NO_CLS)) return "flags: VH_FLAG_MAP_HEAD needs VH_FLAG_NO_CLS (the head pools the patch rows; its towers have no class token)";
@@ -551,6 +559,9 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if ((h.flags ^ want) & kBlobTanhGelu)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 21 (tanh GELU) is %d, the context's VH_FLAG_TANH_GELU is %d",
                     (h.flags & kBlobTanhGelu) != 0, (want & kBlobTanhGelu) != 0);
+    if ((h.flags ^ want) & kBlobRope)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 23 (rotary position embedding) is %d, the context's VH_FLAG_ROPE is %d",
+                    (h.flags & kBlobRope) != 0, (want & kBlobRope) != 0);
     return VH_OK;
 }
 
@@ -685,6 +696,14 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         }
         return VH_OK;
     };
+    // VH_FLAG_ROPE: behind the q|k|v projection and in front of the capture above and of attention, q and k of this part's patch rows
+    // are rotated in place by the blob's tables -- one launch per layer, in the layout this part holds (hm_rows != 0: head-major).
+    // Without the flag: no launch.  (No stage of its own: it is neither the projection's time nor attention's.)
+    auto rope = [&](int64_t hm_rows) -> int {
+        if (!L.rope) return VH_OK;
+        HIPCHK(&c->err, launch_rope(qkv16, dt16, batch, T, f.heads, c->head_dim, L.lead, hm_rows, P + L.rope_cos, P + L.rope_sin, s));
+        return VH_OK;
+    };
     // Patch embedding: the im2col pass + the persistent GEMM.
     // VH_FLAG_PRE_LN: a LayerNorm needs whole rows, which no patch-GEMM tile holds -- such a context embeds through the fp32-x branch
     // and one pre_layernorm_kernel pass turns x into what its path consumes (no PATCH_SPLIT, no rowstats pass)
@@ -772,6 +791,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         gq.wscale = sq;
         set_tiled(gq, qkv_hm, false);
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
+        if ((rc = rope(qkv_hm ? (int64_t)rows_g : 0))) return rc;
         if ((rc = capture_attention(l, qkv_hm ? (int64_t)rows_g : 0))) return rc;
         if (tail && l + 1 == nl) {
             // VH_FLAG_CLS_TAIL, last layer: only the class-token row of every image reaches the head, so attention runs for that
@@ -859,6 +879,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         GemmArgs gq = gemm_args(op_dt, xn16, c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, qkv16, rows, 3 * D, D, VH_EPI_BIAS);
         gq.wscale = sq;
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
+        if ((rc = rope(0))) return rc;
         if ((rc = capture_attention(l, 0))) return rc;
         if ((rc = stage(ST_ATTN, [&] {
                  return hd64 ? launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true)
@@ -1635,6 +1656,21 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
         GEN(L.map_f2w, D * M, TID_MAP + 9, sw, 0.f); GEN(L.map_f2b, D, TID_MAP + 10, sb, 0.f);
     }
 #undef GEN
+    if (L.rope) {
+        // angles of the generator's uniform stream, a = pi u; the tables are their cosine and sine, made on the host in double and
+        // rounded once (the device holds no trigonometry): a synthetic model is a true rotation
+        const size_t n = (size_t)L.NP * (size_t)(c->head_dim / 2);
+        std::vector<float> cs(2 * n);
+        const uint64_t stream = rng_stream(seed, TID_ROPE);
+        for (size_t i = 0; i < n; ++i) {
+            const double a = 3.14159265358979323846 * (double)rng_uniform(stream, i);
+            cs[i] = (float)cos(a);
+            cs[n + i] = (float)sin(a);
+        }
+        HIPCHK(&c->err, hipMemcpyAsync(P + L.rope_cos, cs.data(), n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(&c->err, hipMemcpyAsync(P + L.rope_sin, cs.data() + n, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(&c->err, hipStreamSynchronize(s));   // cs leaves scope
+    }
     if (int rc = guard_reset(c)) return rc;
     if (int rc = prepare_weights(c)) return rc;
     return guard_calibrate(c);
@@ -3241,6 +3277,15 @@ int vh_op_map_pool(const void* hi, const void* lo, int form, int batch, int toke
     hipError_t e = launch_map_pool(a, qk, heads, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "map_pool failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the VH_FLAG_ROPE rotation on caller-made q|k|v
+int vh_op_rope(void* qkv16, int dtype, int batch, int tokens, int heads, int head_dim, int lead, int64_t hm_rows, const float* cos_t,
+               const float* sin_t, void* stream) {
+    if (const char* why = rope_check(qkv16, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_t, sin_t)) return fail(nullptr, VH_ERR_INVALID, "rope: %s", why);
+    hipError_t e = launch_rope(qkv16, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_t, sin_t, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "rope failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 int vh_op_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind, float sigma, void* stream) {

@@ -50,6 +50,10 @@ def pool_of(flags):
 # input is the attention-pooling block (needs FLAG_NO_CLS, at most MAP_MAX_HEADS heads); TANH_GELU: gelu_pytorch_tanh in the MLP
 FLAG_MAP_HEAD, FLAG_TANH_GELU, MAP_MAX_HEADS = 1 << 19, 1 << 21, 16
 
+# Rotary position embedding (VH_FLAG_ROPE; vithip.h): a model bit, in the blob header too.  q and k of the patch rows are rotated in
+# every layer by the blob's last two tensors rope.cos / rope.sin [NP][head_dim / 2]; excludes FLAG_CLS_TAIL
+FLAG_ROPE = 1 << 23
+
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
 EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
@@ -344,6 +348,7 @@ SYMBOLS = {
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "vh_op_map_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i, _vp, _vp]),
+    "vh_op_rope": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
     "vh_group_create": (_i, [C.POINTER(Config), _pi, _i, C.POINTER(_vp)]),
@@ -411,7 +416,7 @@ def blob_file_config(path):
 
 def blob_file_flags(path):
     """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN, FLAG_QUICK_GELU, FLAG_REGISTERS(n), FLAG_NO_CLS,
-    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU); host only."""
+    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU, FLAG_ROPE); host only."""
     c = Config()
     _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
     return c.flags
@@ -618,10 +623,88 @@ def blob_from_siglip_state_dict(sd, cfg, ln_eps=1e-6, hidden_act="gelu_pytorch_t
     return np.concatenate([_blob_header(cfg, ln_eps, bits)] + [p.view(np.uint8) for p in parts])
 
 
+def rope_tables_dinov3(grid, head_dim, theta=100.0):
+    """(cos, sin) [grid * grid, head_dim / 2] fp32: the rope.cos / rope.sin tensors of a DINOv3 ViT (Hugging Face
+    `DINOv3ViTRopePositionEmbedding` without augmentation).  Patch p = (y, x) of the grid has coordinates cy = 2 (y + 0.5) / grid - 1 and
+    cx likewise; column a < head_dim / 2, with i = a mod head_dim / 4, holds the angle 2 pi (cy if a < head_dim / 4 else cx)
+    theta^(-4 i / head_dim).  Computed in float64, rounded once."""
+    if head_dim % 4:
+        raise ValueError(f"rope_tables_dinov3: head_dim = {head_dim} is not a multiple of 4")
+    q = head_dim // 4
+    c = 2.0 * (np.arange(grid, dtype=np.float64) + 0.5) / grid - 1.0
+    cy, cx = (a.reshape(-1) for a in np.meshgrid(c, c, indexing="ij"))
+    inv = float(theta) ** (-4.0 * np.arange(q, dtype=np.float64) / head_dim)
+    ang = 2.0 * np.pi * np.concatenate([cy[:, None] * inv[None, :], cx[:, None] * inv[None, :]], axis=1)
+    return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+
+
+def blob_from_dinov3_state_dict(sd, cfg, ln_eps=1e-5, head=None, pool=POOL_CLS, theta=100.0):
+    """Canonical blob of a DINOv3 ViT-S/B/L backbone from a dict of arrays under the Hugging Face `DINOv3ViTModel` parameter names
+    (numpy only): `embeddings.{cls_token, register_tokens, patch_embeddings.{weight, bias}}`, `model.layer.N.` or `layer.N.` +
+    `{norm1, attention.{q,k,v,o}_proj, layer_scale1.lambda1, norm2, mlp.{up,down}_proj, layer_scale2.lambda1}`, `norm`.
+    `cfg`: the model shape, `registers` = the number of register tokens, classes = the head's width.  `embeddings.mask_token` is
+    ignored; a missing `k_proj.bias` is zeros (key_bias=False).  LayerScale is folded into o_proj and down_proj in float64, one
+    rounding, as blob_from_dinov2_state_dict does.  The model has no position table: pos is zeros; the last two tensors are
+    rope_tables_dinov3(grid, head dim, theta).  The head is zero unless head = (weight [classes, dim], bias [classes]) is given; with
+    an identity head `vh_read_features(VH_FEAT_NORM)` / debug tap 1 is the model's `pooler_output` (the normalised class token).
+    Header flags: FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool).  Refused by name: a gated MLP (mlp.gate_proj: the H+ and 7B
+    checkpoints), a register count other than cfg['registers'], a missing or wrongly shaped tensor."""
+    me = "blob_from_dinov3_state_dict"
+    if pool not in (POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM, POOL_CLS_AVG):
+        raise ValueError(f"{me}: pool = {pool} is not POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM or POOL_CLS_AVG")
+    D, M, E, P, CH, H = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"], cfg["heads"]
+    W = 2 * D if pool == POOL_CLS_AVG else D
+    g = cfg["image_size"] // cfg["patch_size"]
+    R = int(cfg.get("registers", 0))
+    if not 0 <= R <= MAX_REGISTERS:
+        raise ValueError(f"{me}: cfg['registers'] = {R} is outside 0 .. {MAX_REGISTERS}")
+    if any(k.endswith("mlp.gate_proj.weight") for k in sd):
+        raise ValueError(f"{me}: the checkpoint has a gated MLP (mlp.gate_proj), which this library does not run")
+    emb = "embeddings."
+    have = int(np.asarray(sd[emb + "register_tokens"]).shape[-2]) if emb + "register_tokens" in sd else 0
+    if have != R:
+        raise ValueError(f"{me}: the checkpoint has {have} register tokens, cfg['registers'] is {R}")
+    pre = "model.layer." if any(k.startswith("model.layer.") for k in sd) else "layer."
+    take = _taker(sd, me)
+
+    def scaled(wname, bname, lname, n_in):
+        lam = take(lname, (D,), np.float64)
+        w = take(wname, (D, n_in), np.float64).reshape(D, n_in) * lam[:, None]
+        return [w.astype(np.float32).reshape(-1), (take(bname, (D,), np.float64) * lam).astype(np.float32)]
+
+    parts = [take(emb + "patch_embeddings.weight", (D, CH, P, P)), take(emb + "patch_embeddings.bias", (D,)),
+             take(emb + "cls_token", (1, 1, D)), np.zeros((g * g + 1) * D, np.float32)]
+    if R:
+        parts.append(take(emb + "register_tokens", (1, R, D)))
+    for l in range(cfg["layers"]):
+        b = f"{pre}{l}."
+        parts += [take(b + "norm1.weight", (D,)), take(b + "norm1.bias", (D,))]
+        for n in ("q_proj", "k_proj", "v_proj"):
+            parts.append(take(f"{b}attention.{n}.weight", (D, D)))
+            parts.append(np.zeros(D, np.float32) if n == "k_proj" and f"{b}attention.{n}.bias" not in sd
+                         else take(f"{b}attention.{n}.bias", (D,)))
+        parts += scaled(b + "attention.o_proj.weight", b + "attention.o_proj.bias", b + "layer_scale1.lambda1", D)
+        parts += [take(b + "norm2.weight", (D,)), take(b + "norm2.bias", (D,)),
+                  take(b + "mlp.up_proj.weight", (M, D)), take(b + "mlp.up_proj.bias", (M,))]
+        parts += scaled(b + "mlp.down_proj.weight", b + "mlp.down_proj.bias", b + "layer_scale2.lambda1", M)
+    parts += [take("norm.weight", (D,)), take("norm.bias", (D,))]
+    if head is None:
+        parts += [np.zeros(E * W, np.float32), np.zeros(E, np.float32)]
+    else:
+        hw, hb = (np.asarray(a) for a in head)
+        if hw.shape != (E, W) or hb.shape != (E,):
+            raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, W)}, {(E,)}")
+        parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
+    cos, sin = rope_tables_dinov3(g, D // H, theta)
+    parts += [cos.reshape(-1), sin.reshape(-1)]
+    h = _blob_header(cfg, ln_eps, FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool))
+    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+
+
 def blob_flags_of(blob):
     """The model bits of a memory blob's header as vh_config flags (what blob_file_flags returns for a file)."""
     bits = int(np.ascontiguousarray(blob[52:56]).view(np.uint32)[0])
-    same = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU
+    same = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE
     return (FLAG_PRE_LN if bits & 2 else 0) | (FLAG_QUICK_GELU if bits & 4 else 0) | (bits & same)
 
 
@@ -2240,6 +2323,13 @@ def op_map_pool(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_
     """The attention-pooling head's one-pass kernel on its own (vh_op_map_pool): z [batch, heads, dim] fp32 = the softmax(qk[h] . y_t)-
     weighted sum of y_t = LayerNorm(row t; gamma, beta, eps) over rows lead .. tokens - 1 of every image; qk [heads, dim] fp32."""
     _check(lib().vh_op_map_pool(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, qk_ptr, heads, z_ptr, None))
+
+
+def op_rope(qkv_ptr, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_ptr, sin_ptr):
+    """The VH_FLAG_ROPE rotation on its own (vh_op_rope), in place: q and k of rows lead .. tokens - 1 of every image and head of the
+    q|k|v at qkv_ptr (`dtype` elements; hm_rows = 0: row-major [batch * tokens, 3 * heads * head_dim], else head-major
+    [3, heads, hm_rows, 64]) are rotated by the fp32 tables cos / sin [tokens - lead, head_dim / 2]."""
+    _check(lib().vh_op_rope(qkv_ptr, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_ptr, sin_ptr, None))
 
 
 def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr, dtype):
