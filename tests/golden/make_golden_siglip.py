@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/siglip/*.npz -- the vectors that pin tests/siglip_ref.py (and through it the device) on the two SigLIP flags,
+"""Generate tests/golden/siglip/*.npz -- the vectors that pin tests/vit_ref.py (and through it the device) on the two SigLIP flags,
 tanh GELU and the attention-pooling head.  Three micro cases, each an independent implementation from `transformers`, built from a
 random config (no download), eager attention, float64, hidden_act gelu_pytorch_tanh, layer_norm_eps = 1e-6, loaded with this
-repository's seeded tensors (siglip_ref.siglip_tensors: the backbone's and the head's under our names, plus a seeded probe and seeded
+repository's seeded tensors (hf_state_dicts.siglip_tensors: the backbone's and the head's under our names, plus a seeded probe and seeded
 q / k thirds of in_proj with ALL biases, so that the converter's fold -- and the key bias dropping out -- is part of what is pinned):
   vision_a  SiglipVisionModel             NO_CLS | MAP_HEAD | TANH_GELU         shape A, identity head: `pooler_output`
   vision_b  SiglipVisionModel             NO_CLS | MAP_HEAD | TANH_GELU         shape B
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 from transformers import SiglipConfig, SiglipForImageClassification, SiglipVisionConfig, SiglipVisionModel
 
-import siglip_ref as SR
+import hf_state_dicts as H
 import vh_synth as S
 
 CFG_KEYS = ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")
@@ -63,8 +63,8 @@ def main():
     torch.set_num_threads(8)
     os.makedirs(os.path.join(HERE, "siglip"), exist_ok=True)
     for name, classifier, cfg, wseed, iseed, batch in CASES:
-        t, raw, flags = SR.siglip_tensors(cfg, wseed, classifier)
-        sd = SR.siglip_state_dict(cfg, t, raw, classifier, prefix="vision_model." if classifier else "")
+        t, raw, flags = H.siglip_tensors(cfg, wseed, classifier)
+        sd = H.siglip_state_dict(cfg, t, raw, classifier, prefix="vision_model." if classifier else "")
         images = S.make_images(cfg, iseed, batch)
         m = hf_model(cfg, classifier, sd)
         px = torch.from_numpy(images.transpose(0, 3, 1, 2).copy()).to(torch.float64)

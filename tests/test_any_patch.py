@@ -3,7 +3,6 @@ patch * channels is not a multiple of 4) are valid shapes -- the patch GEMM runs
 of 64, and the blob keeps its size.  No GPU needed: vh_weight_blob_bytes and vh_blob_file_config run check_config only.  The
 patch-14 configurations are defined here, not in vh_synth.CONFIGS (whose every entry other tests run on the GPU); the oracle
 is pinned on a patch-14 model by tests/golden/patch14/ (tests/golden/make_golden_patch14.py)."""
-import ctypes as C
 import glob
 import os
 
@@ -12,7 +11,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
-from vh_testlib import rel
+from vh_testlib import lib_blob_bytes, rel
 
 vithip = pytest.importorskip("vithip")
 
@@ -35,11 +34,6 @@ TINY_P7 = _cfg(56, 7, 128, 2, 256, 2, classes=40)                   # patch vect
 PATCH14_MICRO = _cfg(56, 14, 128, 2, 256, 2, classes=40)            # the fixture's model (make_golden_patch14.py)
 
 
-def _blob_bytes(cfg, max_batch=1, dtype=vithip.DTYPE_BF16):
-    c = vithip.make_config(cfg, dtype, max_batch)
-    return vithip.lib().vh_weight_blob_bytes(C.byref(c))
-
-
 @pytest.mark.parametrize("name,cfg,tokens", [("vit_l14_224", VIT_L14_224, 257), ("vit_b14_224", VIT_B14_224, 257),
                                              ("dinov2_s14_518", DINO_S14_518, 1370), ("dinov2_b14_518", DINO_B14_518, 1370),
                                              ("gray_p14", GRAY_P14, 65), ("tiny_p7", TINY_P7, 65)])
@@ -48,7 +42,7 @@ def test_any_patch_models_are_valid(name, cfg, tokens):
     kp = cfg["patch_size"] ** 2 * cfg["channels"]
     assert kp % 64 or (cfg["patch_size"] * cfg["channels"]) % 4   # shapes the patch-alignment rules rejected
     for dt in (vithip.DTYPE_BF16, vithip.DTYPE_FP16, vithip.DTYPE_FP8):
-        assert _blob_bytes(cfg, dtype=dt) == 64 + 4 * S.param_count(cfg), (name, dt)
+        assert lib_blob_bytes(cfg, dtype=dt) == 64 + 4 * S.param_count(cfg), (name, dt)
 
 
 def test_patch14_blob_file_header_is_accepted_on_the_host(tmp_path):
@@ -61,15 +55,15 @@ def test_patch14_blob_file_header_is_accepted_on_the_host(tmp_path):
 
 
 def test_image_not_a_multiple_of_the_patch_is_still_rejected():
-    assert _blob_bytes(_cfg(225, 14, 768, 12, 3072, 12)) == 0
-    assert _blob_bytes(_cfg(224, 15, 768, 12, 3072, 12)) == 0
+    assert lib_blob_bytes(_cfg(225, 14, 768, 12, 3072, 12)) == 0
+    assert lib_blob_bytes(_cfg(224, 15, 768, 12, 3072, 12)) == 0
 
 
 def test_more_than_4097_tokens_is_still_rejected_at_patch_14():
     cfg = _cfg(924, 14, 384, 6, 1536, 12)   # 66 x 66 patches: 4357 tokens
     assert S.tokens(cfg) == 4357
-    assert _blob_bytes(cfg) == 0
-    assert _blob_bytes(_cfg(896, 14, 384, 6, 1536, 12)) == 64 + 4 * S.param_count(_cfg(896, 14, 384, 6, 1536, 12))   # 64 x 64
+    assert lib_blob_bytes(cfg) == 0
+    assert lib_blob_bytes(_cfg(896, 14, 384, 6, 1536, 12)) == 64 + 4 * S.param_count(_cfg(896, 14, 384, 6, 1536, 12))   # 64 x 64
 
 
 def test_patch14_fixture_present():

@@ -3,7 +3,7 @@ flag and dtype), the blob grows by pre_ln.weight / pre_ln.bias exactly when the 
 model bits, and the new taps and epilogue codes check their arguments before they touch a device.  The reference the GPU tests
 use, tests/vit_ref.py, is pinned here: against three fixtures computed by Hugging Face `transformers` models
 (tests/golden/make_golden_clip.py), and, with neither switch, against the C oracle.  No GPU needed."""
-import ctypes as C
+import functools
 import glob
 import os
 
@@ -14,7 +14,7 @@ import hf_state_dicts as H
 import oracle_lib as O
 import vh_synth as S
 import vit_ref as R
-from vh_testlib import rel, vit_cfg
+from vh_testlib import lib_blob_bytes, rel, vit_cfg
 
 vithip = pytest.importorskip("vithip")
 
@@ -35,9 +35,7 @@ CLIP = [("vit_b32_224", vit_cfg(224, 32, 768, 12, 3072, 12, 512), 50),
 MICRO = S.CONFIGS["vit_micro"]
 
 
-def _blob_bytes(cfg, flags=0, dtype=BF16, max_batch=1):
-    c = vithip.make_config(cfg, dtype, max_batch, 1e-5, flags)
-    return vithip.lib().vh_weight_blob_bytes(C.byref(c))
+_blob_bytes = functools.partial(lib_blob_bytes, ln_eps=1e-5)      # CLIP's layer_norm_eps
 
 
 def test_the_flag_and_epilogue_constants():

@@ -11,6 +11,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+import vit_ref as R
 from vh_testlib import _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
@@ -113,23 +114,9 @@ def test_tiny_patch14_fp8_forward_tracks_the_emulation():
         assert rel(got, d["ref"]) <= 0.25, label
 
 
-def _weight_only_e4m3_blob(cfg, blob):
-    """test_gpu_fp8.weight_only_e4m3_blob: q/k/v/o/fc1/fc2 through the oracle's e4m3 row quantiser and back."""
-    out = blob.copy()
-    off = 64
-    for name, shape, *_ in S.tensor_table(cfg):
-        n = int(np.prod(shape))
-        if name.endswith(".weight") and name.split(".")[1] in ("q", "k", "v", "o", "fc1", "fc2"):
-            w = out[off:off + 4 * n].view(np.float32).reshape(shape)
-            _, wq, sc = O.quantize_rows(w)
-            w[...] = wq * sc[:, None]
-        off += 4 * n
-    return out
-
-
 def test_tiny_patch14_weight_only_e4m3():
     d = _tiny()
-    blob_q = _weight_only_e4m3_blob(TINY_P14, d["blob"])
+    blob_q = R.weight_only_e4m3_blob(TINY_P14, d["blob"])
     got, _ = _forward(TINY_P14, d["blob"], d["images"], FP16, vithip.FLAG_W8_E4M3)
     host_quantised, _ = _forward(TINY_P14, blob_q, d["images"], FP16)
     e = rel(got, O.vit_forward(TINY_P14, blob_q, d["images"]))

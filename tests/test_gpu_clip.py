@@ -325,24 +325,11 @@ def test_fp8_forwards_track_the_emulation(flags, fname):
         assert r_gpuemu <= 1.5 * r_emu32 + 1e-3, label
 
 
-def _weight_only_e4m3_blob(cfg, blob, flags):
-    out = blob.copy()
-    off = 64
-    for name, shape, *_ in R.tensor_table(cfg, flags):
-        n = int(np.prod(shape))
-        if name.endswith(".weight") and name.split(".")[1] in ("q", "k", "v", "o", "fc1", "fc2"):
-            w = out[off:off + 4 * n].view(np.float32).reshape(shape)
-            _, wq, sc = O.quantize_rows(w)
-            w[...] = wq * sc[:, None]
-        off += 4 * n
-    return out
-
-
 @pytest.mark.parametrize("name,cfg", MODELS, ids=[m[0] for m in MODELS])
 def test_weight_only_e4m3(name, cfg):
     flags = PRE | QUICK
     blob, images, _ = _model(name, cfg, flags)
-    blob_q = _weight_only_e4m3_blob(cfg, blob, flags)
+    blob_q = R.weight_only_e4m3_blob(cfg, blob, flags)
     got, _ = _forward(cfg, blob, images, FP16, flags | vithip.FLAG_W8_E4M3, eps=1e-5)
     host_quantised, _ = _forward(cfg, blob_q, images, FP16, flags, eps=1e-5)
     e = rel(got, R.forward(cfg, blob_q, images, flags, 1e-5))

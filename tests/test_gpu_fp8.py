@@ -13,6 +13,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+import vit_ref as R
 from vh_testlib import _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
@@ -270,20 +271,6 @@ def test_full_size_config_5_vit_base_fp8_batch_512_properties():
     ctx.close()
 
 
-def weight_only_e4m3_blob(cfg, blob):
-    """The blob whose q/k/v/o/fc1/fc2 matrices went through the oracle's e4m3 row quantiser and back (fp32 values)."""
-    out = blob.copy()
-    off = 64
-    for name, shape, *_ in S.tensor_table(cfg):
-        n = int(np.prod(shape))
-        if name.endswith(".weight") and name.split(".")[1] in ("q", "k", "v", "o", "fc1", "fc2"):
-            w = out[off:off + 4 * n].view(np.float32).reshape(shape)
-            _, wq, sc = O.quantize_rows(w)
-            w[...] = wq * sc[:, None]
-        off += 4 * n
-    return out
-
-
 @pytest.mark.parametrize("dt,name", [(vithip.DTYPE_FP16, "fp16"), (vithip.DTYPE_BF16, "bf16")])
 def test_weight_only_e4m3_is_the_16_bit_forward_of_the_quantised_model(dt, name):
     # SURVEY.md section 7 option (a): e4m3 WEIGHTS (one scale per output channel), 16-bit activations, next to option
@@ -294,7 +281,7 @@ def test_weight_only_e4m3_is_the_16_bit_forward_of_the_quantised_model(dt, name)
     batch = 4
     blob, images = S.make_blob(cfg, 0), S.make_images(cfg, 1, batch)
     ref32 = O.vit_forward(cfg, blob, images)
-    blob_q = weight_only_e4m3_blob(cfg, blob)
+    blob_q = R.weight_only_e4m3_blob(cfg, blob)
     ref_q = O.vit_forward(cfg, blob_q, images)
     ctx = vithip.VitContext(cfg, dtype=dt, max_batch=batch, flags=vithip.FLAG_W8_E4M3)
     ctx.load_weights(blob)

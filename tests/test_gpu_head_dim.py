@@ -13,6 +13,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
+import vit_ref as R
 from vh_testlib import _release_buffers, dev, rel
 
 pytestmark = pytest.mark.gpu
@@ -278,24 +279,10 @@ def test_fp8_forwards_track_the_emulation(name, cfg):
         assert rel(got, ref32) <= 0.25, label
 
 
-def _weight_only_e4m3_blob(cfg, blob):
-    """test_gpu_fp8.weight_only_e4m3_blob: q/k/v/o/fc1/fc2 through the oracle's e4m3 row quantiser and back."""
-    out = blob.copy()
-    off = 64
-    for name, shape, *_ in S.tensor_table(cfg):
-        n = int(np.prod(shape))
-        if name.endswith(".weight") and name.split(".")[1] in ("q", "k", "v", "o", "fc1", "fc2"):
-            w = out[off:off + 4 * n].view(np.float32).reshape(shape)
-            _, wq, sc = O.quantize_rows(w)
-            w[...] = wq * sc[:, None]
-        off += 4 * n
-    return out
-
-
 @pytest.mark.parametrize("name,cfg", [("hd80_d320", HD80_D320), ("hd128_d256", HD128_D256)])
 def test_weight_only_e4m3(name, cfg):
     blob, images, _ = _model(name, cfg)
-    blob_q = _weight_only_e4m3_blob(cfg, blob)
+    blob_q = R.weight_only_e4m3_blob(cfg, blob)
     got, _, _ = _forward(cfg, blob, images, FP16, vithip.FLAG_W8_E4M3)
     host_quantised, _, _ = _forward(cfg, blob_q, images, FP16)
     e = rel(got, O.vit_forward(cfg, blob_q, images))

@@ -10,8 +10,7 @@ import os
 import numpy as np
 import pytest
 
-import rope_ref as RR
-import siglip_ref as SR
+import hf_state_dicts as HF
 import vh_synth as S
 import vit_ref as R
 from test_gpu_attention_maps import TOL as MAPS_TOL
@@ -26,13 +25,13 @@ ULP = {BF16: 2.0 ** -8, FP16: 2.0 ** -11}   # test_gpu_ops.ULP
 MODEL_TOL = {FP16: 1e-3, BF16: 1e-2}        # test_gpu_vit.TOL
 ROPE, REG = vithip.FLAG_ROPE, vithip.FLAG_REGISTERS
 HERE = os.path.dirname(os.path.abspath(__file__))
-EPS = RR.DINOV3_EPS
+EPS = HF.DINOV3_EPS
 CANARY = 4   # rows in front of and behind the buffer the kernel is given
 
 
 def fixture(name):
     path, = glob.glob(os.path.join(HERE, "golden", "dinov3", name + "_s*.npz"))
-    return np.load(path), RR.fixture_cfg(name), RR.fixture_flags(name), RR.fixture_blob(name)
+    return np.load(path), HF.fixture_cfg(name), HF.fixture_flags(name), HF.fixture_blob(name)
 
 
 # ---- 1. the kernel through vh_op_rope -----------------------------------------------------------------------------------------------
@@ -91,12 +90,12 @@ def test_rope_kernel(dt, layout, hd):
             want[:, lead:, :2, :, half:] = x[:, lead:, :2, :, :half]
             assert np.array_equal(got, want), (lead, NP)
             # seeded tables against float64 of the stated function
-            a = np.pi * S.fill(NP * half, 1000 + NP + lead, RR.TID_ROPE, 0).astype(np.float64).reshape(NP, half)
+            a = np.pi * S.fill(NP * half, 1000 + NP + lead, R.TID_ROPE, 0).astype(np.float64).reshape(NP, half)
             cos, sin = np.cos(a).astype(np.float32), np.sin(a).astype(np.float32)
             got = rowmajor(_run(buf, dt, batch, tokens, heads, hd, lead, hm_rows, cos, sin))
             assert np.array_equal(got[:, :lead], x[:, :lead]) and np.array_equal(got[:, :, 2], x[:, :, 2]), "v or a lead row was written"
             v64 = val.astype(np.float64).reshape(batch, tokens, 3, heads, hd)[:, lead:, :2]
-            ref = RR.rotate_rows(v64.transpose(0, 2, 3, 1, 4), cos.astype(np.float64), sin.astype(np.float64)).transpose(0, 3, 1, 2, 4)
+            ref = R.rotate_rows(v64.transpose(0, 2, 3, 1, 4), cos.astype(np.float64), sin.astype(np.float64)).transpose(0, 3, 1, 2, 4)
             g = vithip.from16(got, dt).astype(np.float64).reshape(got.shape)[:, lead:, :2]
             tol = ULP[dt] * (np.abs(ref) + np.abs(ref).max(-1, keepdims=True))
             bad = np.abs(g - ref) > tol
@@ -148,7 +147,7 @@ def test_fixture_outputs(name, dt, lnf):
 def test_fixture_is_missed_with_the_flag_cleared(name, dt):
     """The same blob minus its two tensors on a context without the flag: another function, more than ten bounds away."""
     z, cfg, flags, blob = fixture(name)
-    blob0, flags0 = RR.without_rope(cfg, blob, flags)
+    blob0, flags0 = R.without_rope(cfg, blob, flags)
     ctx = vithip.VitContext(cfg, dtype=dt, max_batch=len(z["images"]), flags=flags0, ln_eps=EPS)
     ctx.load_weights(blob0)
     got = ctx.forward(z["images"])
@@ -169,7 +168,7 @@ def test_fp8_forwards_track_the_emulation(name, lnf):
     ctx.load_weights(blob)
     got, folded = ctx.forward(images), ctx.ln_fold()
     ctx.close()
-    emu = RR.forward(cfg, blob, images, flags, EPS, fp8="folded" if folded else "plain")
+    emu = R.forward(cfg, blob, images, flags, EPS, fp8="folded" if folded else "plain")
     r_emu32, r_gpu32, r_gpuemu = rms(emu, ref32), rms(got, ref32), rms(got, emu)
     print(f"\n[rope fp8] {name} (folded {folded}): rms emu-fp32 {r_emu32:.3e} gpu-fp32 {r_gpu32:.3e} gpu-emu {r_gpuemu:.3e}")
     assert np.isfinite(got).all()
@@ -179,7 +178,7 @@ def test_fp8_forwards_track_the_emulation(name, lnf):
 # ---- 4. both q|k|v layouts ---------------------------------------------------------------------------------------------------------------
 def test_both_qkv_layouts_of_a_vit_b16_forward(monkeypatch):
     """ViT-B/16 shape, two layers, bf16 at batch 224 keeps q|k|v head-major; a context created under VH_QKV_HM=0 keeps it row-major
-    (test_gpu_attention_maps).  With FLAG_ROPE both are the same bits, and three of the images are within the bf16 bound of rope_ref
+    (test_gpu_attention_maps).  With FLAG_ROPE both are the same bits, and three of the images are within the bf16 bound of vit_ref
     (an image's logits do not depend on the batch, so the reference runs those three alone)."""
     cfg = dict(S.CONFIGS["vit_base"], layers=2)
     batch, pick = 224, [0, 100, 223]
@@ -201,17 +200,17 @@ def test_both_qkv_layouts_of_a_vit_b16_forward(monkeypatch):
     assert used == [1, 0], used
     assert np.isfinite(logits[0]).all() and np.array_equal(logits[0], logits[1])
     # the seeded tables are the reference's (host cosine and sine of the same angles: the same floats but for libm's last bit)
-    t = RR.unpack_blob(cfg, blob, ROPE)
-    cos, sin = RR.seeded_tables(cfg, 0)
+    t = R.unpack_blob(cfg, blob, ROPE)
+    cos, sin = R.seeded_tables(cfg, 0)
     assert np.abs(t["rope.cos"] - cos).max() <= 2.0 ** -24 and np.abs(t["rope.sin"] - sin).max() <= 2.0 ** -24
     images = np.stack([S.fill(px, 1, 0x100, 0, start=i * px) for i in pick]).reshape(len(pick), cfg["image_size"], cfg["image_size"], cfg["channels"])
     assert np.array_equal(images[0].reshape(-1), first)
-    ref = RR.forward(cfg, blob, images, ROPE)
+    ref = R.forward(cfg, blob, images, ROPE)
     e = rel(logits[0][pick], ref)
     print(f"\n[rope] ViT-B/16 x 2 layers bf16 b{batch}, head-major and row-major: {e:.3e} (bound {MODEL_TOL[BF16]:g})")
     assert e <= MODEL_TOL[BF16]
     # and the flag matters at this shape too
-    assert rel(SR.forward(cfg, RR.without_rope(cfg, blob, ROPE)[0], images, 0), ref) > 10 * MODEL_TOL[BF16]
+    assert rel(R.forward(cfg, R.without_rope(cfg, blob, ROPE)[0], images, 0), ref) > 10 * MODEL_TOL[BF16]
 
 
 # ---- 5. the same logit bits on every route into a forward ---------------------------------------------------------------------------------
@@ -222,7 +221,7 @@ HD80 = dict(image_size=24, patch_size=8, channels=3, dim=320, heads=4, mlp_dim=3
 
 def context(cfg, dt, flags, max_batch=5, seed=5):
     ctx = vithip.VitContext(cfg, dtype=dt, max_batch=max_batch, flags=flags, ln_eps=EPS)
-    ctx.load_weights(RR.make_blob(cfg, seed, flags, EPS))
+    ctx.load_weights(R.make_blob(cfg, seed, flags, EPS))
     return ctx
 
 
@@ -234,7 +233,7 @@ def test_same_logit_bits_alone_in_a_batch_across_streams_and_graph_replay(cfg, d
     five = ctx.forward(images)
     assert np.isfinite(five).all()
     if dt != FP8:   # a seeded model with a seeded head against the reference, at the model bound
-        assert rel(five, RR.forward(cfg, RR.make_blob(cfg, 5, flags, EPS), images, flags, EPS)) <= MODEL_TOL[dt]
+        assert rel(five, R.forward(cfg, R.make_blob(cfg, 5, flags, EPS), images, flags, EPS)) <= MODEL_TOL[dt]
     one = context(cfg, dt, flags, max_batch=1)
     assert same_bits(one.forward(images[2:3]), five[2:3])                             # image 2 alone at max_batch 1
     one.close()
@@ -251,9 +250,9 @@ def test_same_logit_bits_alone_in_a_batch_across_streams_and_graph_replay(cfg, d
     ctx.set_graph(False)
     # new weights drop the captured graphs: another seed is another function, the first seed again the first bits
     ctx.set_graph(True)
-    ctx.load_weights(RR.make_blob(cfg, 6, flags, EPS))
+    ctx.load_weights(R.make_blob(cfg, 6, flags, EPS))
     assert not same_bits(ctx.forward(images), five)
-    ctx.load_weights(RR.make_blob(cfg, 5, flags, EPS))
+    ctx.load_weights(R.make_blob(cfg, 5, flags, EPS))
     assert same_bits(ctx.forward(images), five)
     ctx.close()
 
@@ -269,11 +268,11 @@ def test_attention_maps_are_of_the_rotated_q_and_k(dt):
     ctx.forward(images)
     Q = ctx.attention_dims()[2]
     assert Q == 5
-    blob0, flags0 = RR.without_rope(cfg, blob, flags)
+    blob0, flags0 = R.without_rope(cfg, blob, flags)
     for k in range(1, L + 1):
         got = ctx.read_attention(k)["probs"]
-        ref = RR.forward(cfg, blob, images, flags, EPS, lead_probs=(k, Q))
-        unrotated = RR.forward(cfg, blob0, images, flags0, EPS, lead_probs=(k, Q))
+        ref = R.forward(cfg, blob, images, flags, EPS, lead_probs=(k, Q))
+        unrotated = R.forward(cfg, blob0, images, flags0, EPS, lead_probs=(k, Q))
         err = float(np.abs(got - ref).max())
         print(f"\n[rope] maps {NAME[dt]} layer {k}: max |p - p_ref| = {err:.3e} (tol {MAPS_TOL[dt]:.3e}); the unrotated model's rows differ by {np.abs(unrotated - ref).max():.3e}")
         assert got.shape == ref.shape and err <= MAPS_TOL[dt]
@@ -287,8 +286,8 @@ def test_a_blob_whose_bit_differs_is_refused_by_name(tmp_path):
     ctx = vithip.VitContext(cfg, dtype=FP16, max_batch=2, flags=flags, ln_eps=EPS)
     ctx.init_weights_seeded(17)
     blob = ctx.export_weights()
-    want_blob = RR.make_blob(cfg, 17, flags, EPS)
-    n = 2 * 4 * int(np.prod(RR.rope_shape(cfg)))
+    want_blob = R.make_blob(cfg, 17, flags, EPS)
+    n = 2 * 4 * int(np.prod(R.rope_shape(cfg)))
     assert np.array_equal(blob[:-n], want_blob[:-n])                                  # header bit 23 and every other tensor
     assert np.abs(blob[-n:].view(np.float32) - want_blob[-n:].view(np.float32)).max() <= 2.0 ** -24
     path = str(tmp_path / "m.vhblob")
@@ -304,11 +303,11 @@ def test_a_blob_whose_bit_differs_is_refused_by_name(tmp_path):
         ctx.load_weights(forged)
     assert e.value.code == 1
     with pytest.raises(vithip.VhError, match="bytes, expected"):                      # the blob of the model without the flag: its size speaks
-        ctx.load_weights(RR.without_rope(cfg, blob, flags)[0])
+        ctx.load_weights(R.without_rope(cfg, blob, flags)[0])
     assert same_bits(ctx.forward(images), want)                                       # the refused loads changed nothing
     ctx.close()
     plain = vithip.VitContext(cfg, dtype=FP16, max_batch=2, flags=REG(4), ln_eps=EPS)  # and the reverse
-    blob0 = RR.without_rope(cfg, blob, flags)[0]
+    blob0 = R.without_rope(cfg, blob, flags)[0]
     forged0 = blob0.copy()
     forged0[52:56] = np.array([int(REG(4)) | ROPE], np.uint32).view(np.uint8)
     with pytest.raises(vithip.VhError, match=r"header bit 23 \(rotary position embedding\) is 1, the context's VH_FLAG_ROPE is 0"):

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import features_ref as FR
+import hf_state_dicts as HF
 import oracle_lib as O
-import siglip_ref as SR
 import vh_synth as S
 import vit_ref as R
 from layer_features_ref import Guarded
@@ -33,7 +33,7 @@ NO_CLS, POOL, MAP, TANH = vithip.FLAG_NO_CLS, vithip.FLAG_POOL, vithip.FLAG_MAP_
 F32, NORM, RAW = vithip.ELEM_F32, vithip.FEAT_NORM, vithip.FEAT_RAW
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = sorted(glob.glob(os.path.join(HERE, "golden", "siglip", "*.npz")))
-EPS = SR.MAP_EPS
+EPS = HF.MAP_EPS
 # the activation's accuracy limit per result type (test_gpu_clip's): the larger of the erf fit's documented absolute
 # error and a quarter of the type's unit in the last place at the value
 ERF_ABS = {FP16: 7.7e-6, BF16: 3.4e-5, FP8: 5.7e-4}
@@ -54,7 +54,7 @@ def ulp_at(v, dt):
 
 
 def tgelu64(v):
-    return SR.tanh_gelu(np.asarray(v, dtype=np.float64))
+    return R.tanh_gelu(np.asarray(v, dtype=np.float64))
 
 
 def same_bits(a, b):
@@ -69,7 +69,7 @@ def assert_close16(got, ref, dt, extra=0.0):
 
 def context(cfg, dt, flags, max_batch=5, seed=5, extra=0):
     ctx = vithip.VitContext(cfg, dtype=dt, max_batch=max_batch, flags=flags | extra, ln_eps=EPS)
-    ctx.load_weights(SR.make_blob(cfg, seed, flags, EPS))
+    ctx.load_weights(R.make_blob(cfg, seed, flags, EPS))
     return ctx
 
 
@@ -221,13 +221,13 @@ def test_activation_sweep_e4m3():
 FORMS = {"bf16_planes": BF16, "fp16_planes": FP16, "fp8_planes": FP8, "fp32_rows": vithip.FEAT_FORM_F32}
 
 
-@pytest.mark.parametrize("dim", SR.MAP_DIMS)
+@pytest.mark.parametrize("dim", HF.MAP_DIMS)
 def test_map_pool_kernel_against_float64(dim):
-    """vh_op_map_pool on the inputs of siglip_ref.map_pool_cases, every case in all four input forms, canaries around the output: finite,
+    """vh_op_map_pool on the inputs of hf_state_dicts.map_pool_cases, every case in all four input forms, canaries around the output: finite,
     and max |z - z64| / max |z64| within MAP_BOUND of the case's class (4 x the float32 statement's error, tests/test_siglip.py)."""
     worst = {}
-    for heads, NP, lead, batch, order in SR.map_pool_cases(dim):
-        x, gamma, beta, qk = SR.map_pool_inputs(dim, heads, NP, lead, batch, order)
+    for heads, NP, lead, batch, order in HF.map_pool_cases(dim):
+        x, gamma, beta, qk = HF.map_pool_inputs(dim, heads, NP, lead, batch, order)
         d_g, d_b, d_q = dev(gamma), dev(beta), dev(qk)
         for form, fm in FORMS.items():
             hi, lo, xr = FR.split_planes(x.reshape(-1, dim), fm)
@@ -236,7 +236,7 @@ def test_map_pool_kernel_against_float64(dim):
             vithip.op_map_pool(d_hi.ptr, d_lo.ptr if d_lo else None, fm, batch, lead + NP, lead, dim, d_g.ptr, d_b.ptr, EPS, d_q.ptr, heads, g.ptr)
             got = g.read(np.float32, (batch, heads, dim))                                 # (the canaries are checked here)
             g.free()
-            z64, _ = SR.map_z64(xr.reshape(x.shape), gamma, beta, qk, lead)
+            z64, _ = HF.map_z64(xr.reshape(x.shape), gamma, beta, qk, lead)
             assert np.isfinite(got).all(), (dim, heads, NP, lead, batch, order, form)
             e = float(np.abs(got - z64).max() / np.abs(z64).max())
             worst[order] = max(worst.get(order, 0.0), e)
@@ -279,7 +279,7 @@ def test_fp8_forwards_track_the_emulation(path, lnf):
     ctx.load_weights(blob)
     got, folded = ctx.forward(images), ctx.ln_fold()
     ctx.close()
-    emu = SR.forward(cfg, blob, images, flags, eps, fp8="folded" if folded else "plain")
+    emu = R.forward(cfg, blob, images, flags, eps, fp8="folded" if folded else "plain")
     r_emu32, r_gpu32, r_gpuemu = rms(emu, ref32), rms(got, ref32), rms(got, emu)
     print(f"\n[siglip fp8] {os.path.basename(path).split('_s')[0]} (folded {folded}): rms emu-fp32 {r_emu32:.3e} gpu-fp32 {r_gpu32:.3e} gpu-emu {r_gpuemu:.3e}")
     assert np.isfinite(got).all()
@@ -291,7 +291,7 @@ def test_fp8_forwards_track_the_emulation(path, lnf):
 @pytest.mark.parametrize("cfg,dt", [(A, BF16), (A, FP8), (B, FP16)], ids=["a_bf16", "a_fp8", "b_fp16"])
 def test_head_stages(cfg, dt, act):
     """Tap 1 (u) against the float64 head of the context's OWN final rows (debug tap 0): the bound is 4 x the error of the float32
-    statement siglip_ref.map_head32 on those rows, as for the kernel.  The logits are the fp32 head of tap 1, bit for bit."""
+    statement hf_state_dicts.map_head32 on those rows, as for the kernel.  The logits are the fp32 head of tap 1, bit for bit."""
     flags, batch, D, H = NO_CLS | MAP | act, 3, cfg["dim"], cfg["heads"]
     ctx = context(cfg, dt, flags)
     logits = ctx.forward(S.make_images(cfg, 7, batch))
@@ -299,11 +299,11 @@ def test_head_stages(cfg, dt, act):
     x = ctx.debug_read(0, batch * T * D).reshape(batch, T, D)
     u = ctx.debug_read(1, batch * D).reshape(batch, D)
     ctx.close()
-    t = SR.unpack_blob(cfg, SR.make_blob(cfg, 5, flags, EPS), flags)
+    t = R.unpack_blob(cfg, R.make_blob(cfg, 5, flags, EPS), flags)
     t64 = {k: v.astype(np.float64) for k, v in t.items()}
     y64 = R.layernorm(x.astype(np.float64), t64["lnf.weight"], t64["lnf.bias"], EPS)
-    u64 = SR.map_head(y64, t64, H, SR.activation(flags), EPS)
-    e32 = rel(SR.map_head32(x, t, H, flags, EPS), u64)
+    u64 = R.map_head(y64, t64, H, R.activation(flags), EPS)
+    e32 = rel(HF.map_head32(x, t, H, flags, EPS), u64)
     e = rel(u, u64)
     print(f"\n[siglip] head stages {NAME[dt]} dim {D}: tap 1 vs float64 {e:.3e}; the float32 statement {e32:.3e} (bound 4 x)")
     assert np.isfinite(u).all() and e <= 4.0 * e32, (e, e32)
@@ -364,7 +364,7 @@ def _forge(blob, flags_bits):
 
 
 def _header_bits(flags):
-    return int(SR.blob_header(B, flags)[52:56].view(np.uint32)[0])
+    return int(R.blob_header(B, flags)[52:56].view(np.uint32)[0])
 
 
 @pytest.mark.parametrize("flags", [NO_CLS | POOL(vithip.POOL_AVG_NORM) | TANH, MAPF], ids=["tanh", "map_tanh"])
@@ -375,7 +375,7 @@ def test_a_blob_with_other_siglip_bits_is_refused(flags, tmp_path):
     ctx = vithip.VitContext(cfg, dtype=FP16, max_batch=2, flags=flags, ln_eps=EPS)
     ctx.init_weights_seeded(17)
     blob = ctx.export_weights()
-    assert np.array_equal(blob, SR.make_blob(cfg, 17, flags, EPS))                   # the seeded map.* tensors have their ids; the bits in the header
+    assert np.array_equal(blob, R.make_blob(cfg, 17, flags, EPS))                   # the seeded map.* tensors have their ids; the bits in the header
     path, bad = str(tmp_path / "m.vhblob"), str(tmp_path / "forged.vhblob")
     ctx.save_weights_file(path)
     assert vithip.blob_file_flags(path) == flags
@@ -392,7 +392,7 @@ def test_a_blob_with_other_siglip_bits_is_refused(flags, tmp_path):
         with pytest.raises(vithip.VhError, match=msg) as e:
             ctx.load_weights(_forge(blob, _header_bits(f)))
         assert e.value.code == 1
-        if SR.legal(cfg, f):                                                          # (a file's header must describe a legal model to get that far)
+        if R.legal(cfg, f):                                                          # (a file's header must describe a legal model to get that far)
             _forge(file_bytes, _header_bits(f)).tofile(bad)
             with pytest.raises(vithip.VhError):
                 ctx.load_weights_file(bad)
@@ -415,12 +415,12 @@ def test_features_equal_the_no_class_token_behaviour(cfg, dt):
     not touch the rows), and obey the same statements: raw = tap 0, normalised within NORM_BOUND of float64, mean = the fp32 chain."""
     batch, D = 3, cfg["dim"]
     images = S.make_images(cfg, 7, batch)
-    t = SR.make_tensors(cfg, 5, MAPF)
+    t = R.make_tensors(cfg, 5, MAPF)
     base_flags = NO_CLS | POOL(vithip.POOL_AVG_NORM) | TANH
     ctx = context(cfg, dt, MAPF)
     ctx.forward(images)
     base = vithip.VitContext(cfg, dtype=dt, max_batch=5, flags=base_flags, ln_eps=EPS)
-    base.load_weights(SR.pack_blob(cfg, t, base_flags, EPS))
+    base.load_weights(R.pack_blob(cfg, t, base_flags, EPS))
     base.forward(images)
     _, T, NP, _ = ctx.features_dims()
     assert T == NP

@@ -4,7 +4,6 @@ head dim is still rejected.  No GPU needed: vh_weight_blob_bytes and vh_blob_fil
 vh_op_attention_hd tap checks its arguments before it touches a device.  The configurations are defined here, not in
 vh_synth.CONFIGS (whose every entry other tests run on the GPU); the oracle is pinned on head dims 80 and 128 by
 tests/golden/headdim/ (tests/golden/make_golden_headdim.py)."""
-import ctypes as C
 import glob
 import os
 
@@ -13,7 +12,7 @@ import pytest
 
 import oracle_lib as O
 import vh_synth as S
-from vh_testlib import rel
+from vh_testlib import lib_blob_bytes, rel
 
 vithip = pytest.importorskip("vithip")
 
@@ -43,25 +42,20 @@ HD80_MICRO = _cfg(64, 16, 320, 4, 640, 2, classes=40)      # the fixtures' model
 HD128_MICRO = _cfg(64, 16, 256, 2, 512, 2, classes=40)
 
 
-def _blob_bytes(cfg, max_batch=1, dtype=BF16):
-    c = vithip.make_config(cfg, dtype, max_batch)
-    return vithip.lib().vh_weight_blob_bytes(C.byref(c))
-
-
 @pytest.mark.parametrize("name,cfg,hd", VALID, ids=[v[0] for v in VALID])
 def test_models_with_other_head_dims_are_valid(name, cfg, hd):
     assert cfg["dim"] // cfg["heads"] == hd and cfg["dim"] % cfg["heads"] == 0 and hd != 64
     for dt in (BF16, FP16, FP8):
         if dt == FP8 and (cfg["dim"] % 128 or cfg["mlp_dim"] % 128):
-            assert _blob_bytes(cfg, dtype=dt) == 0, (name, "fp8 keeps its multiples of 128")
+            assert lib_blob_bytes(cfg, dtype=dt) == 0, (name, "fp8 keeps its multiples of 128")
             continue
-        assert _blob_bytes(cfg, dtype=dt) == 64 + 4 * S.param_count(cfg), (name, dt)
+        assert lib_blob_bytes(cfg, dtype=dt) == 64 + 4 * S.param_count(cfg), (name, dt)
 
 
 def test_vit_h14_is_valid_in_every_dtype_and_its_blob_size():
     assert S.tokens(VIT_H14_224) == 257
     for dt in (BF16, FP16, FP8):
-        assert _blob_bytes(VIT_H14_224, max_batch=128, dtype=dt) == 64 + 4 * S.param_count(VIT_H14_224)
+        assert lib_blob_bytes(VIT_H14_224, max_batch=128, dtype=dt) == 64 + 4 * S.param_count(VIT_H14_224)
 
 
 @pytest.mark.parametrize("dim,heads", [(576, 8), (1408, 16), (256, 16), (576, 4), (768, 5), (640, 6), (1024, 3), (2048, 128)],
@@ -69,15 +63,15 @@ def test_vit_h14_is_valid_in_every_dtype_and_its_blob_size():
 def test_other_head_dims_are_rejected(dim, heads):
     cfg = _cfg(224, 16, dim, heads, 4 * dim, 2)
     for dt in (BF16, FP16):
-        assert _blob_bytes(cfg, dtype=dt) == 0, (dim, heads)
+        assert lib_blob_bytes(cfg, dtype=dt) == 0, (dim, heads)
 
 
 def test_the_other_rules_still_hold_at_head_dim_80():
-    assert _blob_bytes(_cfg(224, 16, 1280, 16, 5120, 2)) > 0
-    assert _blob_bytes(_cfg(224, 16, 1360, 17, 5120, 2)) == 0                     # dim not a multiple of 64
-    assert _blob_bytes(_cfg(224, 16, 320, 4, 640, 2), dtype=FP8) == 0              # fp8: dim a multiple of 128
-    assert _blob_bytes(_cfg(224, 16, 2560, 32, 5120, 2)) == 0                     # dim > 2048
-    assert _blob_bytes(_cfg(1040, 16, 1280, 16, 5120, 2)) == 0                    # 65 x 65 patches: > 4097 tokens
+    assert lib_blob_bytes(_cfg(224, 16, 1280, 16, 5120, 2)) > 0
+    assert lib_blob_bytes(_cfg(224, 16, 1360, 17, 5120, 2)) == 0                     # dim not a multiple of 64
+    assert lib_blob_bytes(_cfg(224, 16, 320, 4, 640, 2), dtype=FP8) == 0              # fp8: dim a multiple of 128
+    assert lib_blob_bytes(_cfg(224, 16, 2560, 32, 5120, 2)) == 0                     # dim > 2048
+    assert lib_blob_bytes(_cfg(1040, 16, 1280, 16, 5120, 2)) == 0                    # 65 x 65 patches: > 4097 tokens
 
 
 def test_vit_h14_blob_file_header_is_accepted_on_the_host(tmp_path):

@@ -175,8 +175,8 @@ def test_pool_ref_reproduces_the_transformers_fixture(path):
 def test_every_legal_flag_word_has_the_librarys_blob_bytes_and_a_header_that_round_trips(tmp_path):
     """The flag words profiles/ref_model_equivalence.txt lists: the CLIP switches, register counts, and NO_CLS x POOL x REG."""
     grid = [0, PRE, QUICK, PRE | QUICK, REG(1), REG(4), PRE | QUICK | REG(1)]
-    grid += [nc | POOL(m) | REG(n) for nc in (0, NO_CLS) for m in range(4) for n in (0, 4) if R.legal(nc | POOL(m))]
-    assert len(set(grid)) == 17 and not any(R.legal(NO_CLS | POOL(m)) for m in (CLS, CLS_AVG))
+    grid += [nc | POOL(m) | REG(n) for nc in (0, NO_CLS) for m in range(4) for n in (0, 4) if R.legal(MICRO, nc | POOL(m))]
+    assert len(set(grid)) == 17 and not any(R.legal(MICRO, NO_CLS | POOL(m)) for m in (CLS, CLS_AVG))
     for flags in grid:
         assert R.blob_bytes(MICRO, flags) == lib_blob_bytes(MICRO, flags) > 0, flags
         blob = R.make_blob(MICRO, 5, flags, 1e-5)

@@ -1,6 +1,6 @@
 """The rotary model switch on the host: VH_FLAG_ROPE is a valid setting beside every other model bit except VH_FLAG_CLS_TAIL, the blob
 gains rope.cos / rope.sin at its very end, the header carries bit 23, the refusals have their messages, and the DINOv3 converter and
-its tables are what the contract says.  The reference the GPU tests use, tests/rope_ref.py, is pinned here against three fixtures
+its tables are what the contract says.  The reference the GPU tests use, tests/vit_ref.py, is pinned here on this flag against three fixtures
 computed by Hugging Face `transformers` (DINOv3ViTModel in float64; tests/golden/make_golden_dinov3.py), which it misses with the flag
 cleared.  The fp16 model bound of the GPU tests rests on one rounding of q and k more than any other model has: its effect is
 measured here on the CPU.  No GPU needed.  (The named refusal of a blob whose bit differs from a CONTEXT's needs a context: it is in
@@ -12,11 +12,10 @@ import os
 import numpy as np
 import pytest
 
-import rope_ref as RR
-import siglip_ref as SR
+import hf_state_dicts as HF
 import vh_synth as S
 import vit_ref as R
-from vh_testlib import lib_blob_bytes, rel
+from vh_testlib import blob_digest, lib_blob_bytes, recorded_blob_digest, rel
 
 vithip = pytest.importorskip("vithip")
 
@@ -47,39 +46,41 @@ def load(name):
 
 
 def test_the_macro_values():
-    assert ROPE == 1 << 23 == RR.FLAG_ROPE
+    assert ROPE == 1 << 23 == R.FLAG_ROPE
     hdr = open(os.path.join(vithip.REPO_ROOT, "include", "vithip.h")).read()
     for text in ("#define VH_FLAG_ROPE (1 << 23)", "int vh_op_rope(", "tensor id 0x7030", "#define VH_ABI_VERSION 1"):
         assert text in hdr, text
-    assert "vh_op_rope" in vithip.SYMBOLS and RR.TID_ROPE == 0x7030
+    assert "vh_op_rope" in vithip.SYMBOLS and R.TID_ROPE == 0x7030
     assert vithip.lib().vh_abi_version() == 1
 
 
 def test_blob_bytes_with_and_without_the_flag():
     big = dict(image_size=224, patch_size=16, channels=3, dim=768, heads=12, mlp_dim=3072, layers=12, classes=768)
     for cfg in (MICRO, MID, HD80, big):
-        NP, half = RR.rope_shape(cfg)
+        NP, half = R.rope_shape(cfg)
         for flags in LEGAL:
             for more in (0, vithip.FLAG_W8_E4M3, vithip.FLAG_LN_FOLD_ON, vithip.FLAG_LN_FOLD_OFF):
-                assert RR.legal(cfg, flags), flags
-                want = SR.blob_bytes(cfg, RR.old(flags)) + 2 * 4 * NP * half
-                assert lib_blob_bytes(cfg, flags | more) == want == RR.blob_bytes(cfg, flags), (flags, more)
-                assert lib_blob_bytes(cfg, RR.old(flags) | more) == SR.blob_bytes(cfg, RR.old(flags)) == RR.blob_bytes(cfg, RR.old(flags))
-    assert np.array_equal(RR.make_blob(MICRO, 5, 0), R.make_blob(MICRO, 5, 0))          # without the flag: byte for byte what it was
-    assert lib_blob_bytes(MID, ROPE | REG(4), dtype=FP8) == RR.blob_bytes(MID, ROPE | REG(4))
+                assert R.legal(cfg, flags), flags
+                want = R.blob_bytes(cfg, flags & ~ROPE) + 2 * 4 * NP * half
+                assert lib_blob_bytes(cfg, flags | more) == want == R.blob_bytes(cfg, flags), (flags, more)
+                assert lib_blob_bytes(cfg, flags & ~ROPE | more) == R.blob_bytes(cfg, flags & ~ROPE)
+    # without the flag: byte for byte what it was (the digests recorded before the flag's module was merged into vit_ref)
+    for flags in [0] + [f & ~ROPE for f in LEGAL]:
+        assert blob_digest(R.make_blob(MICRO, 5, flags)) == recorded_blob_digest("vit_micro", 5, flags), flags
+    assert lib_blob_bytes(MID, ROPE | REG(4), dtype=FP8) == R.blob_bytes(MID, ROPE | REG(4))
 
 
 def test_layout_of_the_blob():
     # the two tensors are the LAST ones, behind head.bias and behind the map.* tensors; no existing offset moves
     for flags in (ROPE | REG(4), ROPE | MAP | NO_CLS | TANH):
-        names = [n for n, *_ in RR.tensor_table(MICRO, flags)]
+        names = [n for n, *_ in R.tensor_table(MICRO, flags)]
         assert names[-2:] == ["rope.cos", "rope.sin"] and names[-3] == ("map.fc2.bias" if flags & MAP else "head.bias")
-        with_rope, without = RR.make_blob(MICRO, 9, flags), SR.make_blob(MICRO, 9, RR.old(flags))
+        with_rope, without = R.make_blob(MICRO, 9, flags), R.make_blob(MICRO, 9, flags & ~ROPE)
         assert np.array_equal(with_rope[64:without.nbytes], without[64:])
         assert int(with_rope[52:56].view(np.uint32)[0]) == int(without[52:56].view(np.uint32)[0]) | (1 << 23)
-        back, f0 = RR.without_rope(MICRO, with_rope, flags)
-        assert np.array_equal(back, without) and f0 == RR.old(flags)
-    t = RR.make_tensors(MID, 9, ROPE)
+        back, f0 = R.without_rope(MICRO, with_rope, flags)
+        assert np.array_equal(back, without) and f0 == flags & ~ROPE
+    t = R.make_tensors(MID, 9, ROPE)
     c, s = t["rope.cos"].astype(np.float64), t["rope.sin"].astype(np.float64)
     assert c.shape == s.shape == (64, 32)
     assert np.abs(c * c + s * s - 1.0).max() < 2e-7 and c.std() > 0.5 and s.std() > 0.5     # a true rotation, over the whole circle
@@ -87,7 +88,7 @@ def test_layout_of_the_blob():
 
 def test_refusals_each_with_its_message():
     for f in (ROPE | vithip.FLAG_CLS_TAIL, ROPE | REG(4) | vithip.FLAG_CLS_TAIL):
-        assert not RR.legal(MICRO, f)
+        assert not R.legal(MICRO, f)
         assert lib_blob_bytes(MICRO, f) == 0
         rc, msg = _create_error(MICRO, f)
         assert rc == VH_ERR_INVALID and "VH_FLAG_ROPE excludes VH_FLAG_CLS_TAIL" in msg, msg
@@ -102,7 +103,7 @@ def test_refusals_each_with_its_message():
 
 def test_header_bit_round_trips_through_the_blob_file_entry_points(tmp_path):
     for flags in LEGAL:
-        blob = RR.make_blob(MICRO, 5, flags, 1e-5)
+        blob = R.make_blob(MICRO, 5, flags, 1e-5)
         path = tmp_path / f"micro_{flags}.vhblob"
         blob.tofile(path)
         got, eps = vithip.blob_file_config(path)
@@ -120,7 +121,7 @@ def test_forged_header_bits_are_refused(tmp_path):
         out[52:56] = np.array([bits], np.uint32).view(np.uint8)
         out.tofile(path)
 
-    plain, rope = R.make_blob(MICRO, 5, 0), RR.make_blob(MICRO, 5, ROPE)
+    plain, rope = R.make_blob(MICRO, 5, 0), R.make_blob(MICRO, 5, ROPE)
     with_bits(plain, ROPE)                                 # the bit over a blob without the two tensors: the length gives it away
     with pytest.raises(vithip.VhError, match="bytes, the header implies"):
         vithip.blob_file_config(path)
@@ -140,12 +141,12 @@ def test_fixtures_are_present():
     assert [os.path.basename(p).split("_s")[0] for p in GOLDEN] == ["a", "b", "c"], GOLDEN
     assert all(os.path.getsize(p) <= 300 * 1024 for p in GOLDEN)
     for name in "abc":
-        z, cfg = load(name), RR.fixture_cfg(name)
-        _, regs, key_bias, wseed, iseed, batch = RR.FIXTURES[name]
+        z, cfg = load(name), HF.fixture_cfg(name)
+        _, regs, key_bias, wseed, iseed, batch = HF.FIXTURES[name]
         assert [int(v) for v in z["meta"]] == [wseed, iseed, batch, regs, int(key_bias)]
         assert [int(v) for v in z["config"]] == [cfg[k] for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")]
-        assert np.array_equal(z["images"], RR.fixture_images(name))
-        sd = RR.dinov3_state_dict(name)
+        assert np.array_equal(z["images"], HF.fixture_images(name))
+        sd = HF.dinov3_state_dict(name)
         assert abs(sum(float(np.asarray(v, np.float64).sum()) for v in sd.values()) - float(z["state_checksum"][0])) < 1e-9
         lam = np.concatenate([v for k, v in sd.items() if "lambda1" in k])
         assert lam.std() > 0.2 and lam.min() > 0.0           # a spread of LayerScale values, not the constant initial value
@@ -156,7 +157,7 @@ def test_rope_tables_against_the_models_own():
     float32: two relative errors of 2^-24 on an angle of at most 2 pi, 7.5e-7 absolute, plus our own rounding to fp32 (6e-8): 1e-6.
     Measured: A 3.3e-7, B 5.6e-8, C 3.7e-7."""
     for name in "abc":
-        z, cfg = load(name), RR.fixture_cfg(name)
+        z, cfg = load(name), HF.fixture_cfg(name)
         g, hd = cfg["image_size"] // cfg["patch_size"], cfg["dim"] // cfg["heads"]
         cos, sin = vithip.rope_tables_dinov3(g, hd)
         assert cos.dtype == sin.dtype == np.float32 and cos.shape == sin.shape == (g * g, hd // 2)
@@ -176,20 +177,20 @@ def test_rope_tables_against_the_models_own():
 
 def test_converter_layout_and_fold():
     for name in "abc":
-        cfg, flags = RR.fixture_cfg(name), RR.fixture_flags(name)
-        sd = RR.dinov3_state_dict(name)
-        blob = RR.fixture_blob(name)
-        assert vithip.blob_flags_of(blob) == flags and blob.nbytes == RR.blob_bytes(cfg, flags) == lib_blob_bytes(cfg, flags)
+        cfg, flags = HF.fixture_cfg(name), HF.fixture_flags(name)
+        sd = HF.dinov3_state_dict(name)
+        blob = HF.fixture_blob(name)
+        assert vithip.blob_flags_of(blob) == flags and blob.nbytes == R.blob_bytes(cfg, flags) == lib_blob_bytes(cfg, flags)
         assert abs(float(blob[40:44].view(np.float32)[0]) - 1e-5) < 1e-12
-        t = RR.unpack_blob(cfg, blob, flags)
-        t0 = RR.fixture_model_tensors(name)
+        t = R.unpack_blob(cfg, blob, flags)
+        t0 = HF.fixture_model_tensors(name)
         assert not t["pos"].any() and np.array_equal(t["head.weight"], np.eye(cfg["dim"], dtype=np.float32))
         cos, sin = vithip.rope_tables_dinov3(cfg["image_size"] // cfg["patch_size"], cfg["dim"] // cfg["heads"])
         assert np.array_equal(t["rope.cos"], cos) and np.array_equal(t["rope.sin"], sin)
         for l in range(cfg["layers"]):
             assert np.array_equal(t[f"l{l}.q.weight"], t0[f"l{l}.q.weight"]) and np.array_equal(t[f"l{l}.fc1.bias"], t0[f"l{l}.fc1.bias"])
             kb = t[f"l{l}.k.bias"]
-            assert np.array_equal(kb, t0[f"l{l}.k.bias"]) if RR.FIXTURES[name][2] else not kb.any()       # key_bias=False: zeros
+            assert np.array_equal(kb, t0[f"l{l}.k.bias"]) if HF.FIXTURES[name][2] else not kb.any()       # key_bias=False: zeros
             for ours, i in (("o", 1), ("fc2", 2)):       # LayerScale folded in float64, one rounding
                 lam = sd[f"model.layer.{l}.layer_scale{i}.lambda1"].astype(np.float64)
                 assert np.array_equal(t[f"l{l}.{ours}.weight"], (t0[f"l{l}.{ours}.weight"].astype(np.float64) * lam[:, None]).astype(np.float32))
@@ -198,15 +199,15 @@ def test_converter_layout_and_fold():
         short = {k.replace("model.layer.", "layer."): v for k, v in sd.items() if k != "embeddings.mask_token"}
         D = cfg["dim"]
         assert np.array_equal(vithip.blob_from_dinov3_state_dict(short, cfg, head=(np.eye(D, dtype=np.float32), np.zeros(D, np.float32))), blob)
-        zero = RR.unpack_blob(cfg, vithip.blob_from_dinov3_state_dict(sd, cfg), flags)
+        zero = R.unpack_blob(cfg, vithip.blob_from_dinov3_state_dict(sd, cfg), flags)
         assert not zero["head.weight"].any() and not zero["head.bias"].any()
-    cfg = RR.fixture_cfg("b")
-    avg = vithip.blob_from_dinov3_state_dict(RR.dinov3_state_dict("b"), cfg, pool=vithip.POOL_AVG_NORM)
+    cfg = HF.fixture_cfg("b")
+    avg = vithip.blob_from_dinov3_state_dict(HF.dinov3_state_dict("b"), cfg, pool=vithip.POOL_AVG_NORM)
     assert vithip.blob_flags_of(avg) == ROPE | REG(4) | POOL(vithip.POOL_AVG_NORM)
 
 
 def test_converter_refusals_by_name():
-    cfg, sd = RR.fixture_cfg("b"), RR.dinov3_state_dict("b")
+    cfg, sd = HF.fixture_cfg("b"), HF.dinov3_state_dict("b")
     conv = vithip.blob_from_dinov3_state_dict
     with pytest.raises(ValueError, match=r"gated MLP \(mlp.gate_proj\)"):
         conv(dict(sd, **{"model.layer.0.mlp.gate_proj.weight": np.zeros((cfg["mlp_dim"], cfg["dim"]), np.float32)}), cfg)
@@ -230,20 +231,20 @@ def test_converter_refusals_by_name():
 
 @pytest.mark.parametrize("name", ["a", "b", "c"])
 def test_the_reference_reproduces_the_fixture(name):
-    """rope_ref.forward in float64 against Hugging Face's float64 model, 1e-9 relative, on the model's own numbers: its own tables and
-    the LayerScale product unrounded (rope_ref.fixture_tensors64).  Measured 1e-15.  The CONVERTED blob differs from that model by what
+    """vit_ref.forward in float64 against Hugging Face's float64 model, 1e-9 relative, on the model's own numbers: its own tables and
+    the LayerScale product unrounded (hf_state_dicts.fixture_tensors64).  Measured 1e-15.  The CONVERTED blob differs from that model by what
     the blob format rounds to fp32 -- the folded o / fc2 weights (2^-24 relative each) and the tables (test_rope_tables_against_the_
     models_own) -- and reproduces the fixture to 1e-6 (measured: A 4.4e-8, B 2.9e-8, C 7.0e-8)."""
-    z, cfg, flags = load(name), RR.fixture_cfg(name), RR.fixture_flags(name)
-    t = RR.fixture_tensors64(name, z["rope_cos"], z["rope_sin"])
-    logits, x = RR.forward(cfg, t, z["images"], flags, RR.DINOV3_EPS, np.float64, want_hidden=True)
-    last = RR.final_norm(cfg, t, x, flags, RR.DINOV3_EPS).reshape(z["last_hidden_state"].shape)
+    z, cfg, flags = load(name), HF.fixture_cfg(name), HF.fixture_flags(name)
+    t = HF.fixture_tensors64(name, z["rope_cos"], z["rope_sin"])
+    logits, x = R.forward(cfg, t, z["images"], flags, HF.DINOV3_EPS, np.float64, want_hidden=True)
+    last = R.final_norm(cfg, t, x, flags, HF.DINOV3_EPS).reshape(z["last_hidden_state"].shape)
     e = (rel(logits, z["pooler_output"]), rel(last, z["last_hidden_state"]))
     print(f"fixture {name}: float64 reference {e[0]:.3e} / {e[1]:.3e}")
     assert max(e) <= 1e-9
-    blob = RR.fixture_blob(name)
-    logits, x = RR.forward(cfg, blob, z["images"], flags, RR.DINOV3_EPS, np.float64, want_hidden=True)
-    last = RR.final_norm(cfg, blob, x, flags, RR.DINOV3_EPS).reshape(z["last_hidden_state"].shape)
+    blob = HF.fixture_blob(name)
+    logits, x = R.forward(cfg, blob, z["images"], flags, HF.DINOV3_EPS, np.float64, want_hidden=True)
+    last = R.final_norm(cfg, blob, x, flags, HF.DINOV3_EPS).reshape(z["last_hidden_state"].shape)
     e = (rel(logits, z["pooler_output"]), rel(last, z["last_hidden_state"]))
     print(f"fixture {name}: converted blob {e[0]:.3e} / {e[1]:.3e}")
     assert max(e) <= 1e-6
@@ -253,25 +254,28 @@ def test_the_reference_reproduces_the_fixture(name):
 def test_without_the_flag_the_fixture_is_missed(name):
     """The same model with FLAG_ROPE cleared (the blob minus its two tensors) is another function: measured A 0.16, B 0.29, C 0.28 of
     the output's largest magnitude, against fp16 / bf16 model bounds of 1e-3 / 1e-2 (ten times which the GPU test asks for)."""
-    z, cfg, flags = load(name), RR.fixture_cfg(name), RR.fixture_flags(name)
-    blob, f0 = RR.without_rope(cfg, RR.fixture_blob(name), flags)
-    assert f0 == flags & ~ROPE and blob.nbytes == SR.blob_bytes(cfg, f0)
-    e = rel(RR.forward(cfg, blob, z["images"], f0, RR.DINOV3_EPS), z["pooler_output"])
+    z, cfg, flags = load(name), HF.fixture_cfg(name), HF.fixture_flags(name)
+    blob, f0 = R.without_rope(cfg, HF.fixture_blob(name), flags)
+    assert f0 == flags & ~ROPE and blob.nbytes == R.blob_bytes(cfg, f0)
+    e = rel(R.forward(cfg, blob, z["images"], f0, HF.DINOV3_EPS), z["pooler_output"])
     print(f"fixture {name}: flag cleared {e:.3e}")
     assert e > 0.15
-    assert rel(SR.forward(cfg, blob, z["images"], f0, RR.DINOV3_EPS), z["pooler_output"]) == e     # rope_ref without the flag IS siglip_ref
+    # the forward without the flag is the forward WITH it and the identity rotation (cos 1, sin 0), to the bit: one function, two paths
+    t = dict(R.unpack_blob(cfg, blob, f0))
+    t["rope.cos"], t["rope.sin"] = np.ones(R.rope_shape(cfg), np.float32), np.zeros(R.rope_shape(cfg), np.float32)
+    assert rel(R.forward(cfg, t, z["images"], flags, HF.DINOV3_EPS), z["pooler_output"]) == e
 
 
 @pytest.mark.parametrize("name", ["a", "b", "c"])
 def test_the_extra_rounding_of_q_and_k_stays_inside_the_fp16_bound(name):
     """The GPU tests hold fp16 forwards of these fixtures to 1e-3; a ROPE model's q and k are rounded to fp16 twice (behind the
-    projection, behind the rotation).  rope_ref in float32 with exactly those two roundings and nothing else rounded to 16 bits:
+    projection, behind the rotation).  vit_ref in float32 with exactly those two roundings and nothing else rounded to 16 bits:
     measured A 1.9e-4, B 2.3e-4, C 2.1e-4 of the fixture (bf16, for the record: 1.6e-3, 1.6e-3, 1.9e-3 against its bound of 1e-2).  The
     device, which rounds every GEMM operand, measures 6.7e-4 / 4.7e-4 / 6.5e-4 in fp16 (tests/test_gpu_rope.py)."""
-    z, cfg, flags = load(name), RR.fixture_cfg(name), RR.fixture_flags(name)
-    blob = RR.fixture_blob(name)
-    e16 = rel(RR.forward(cfg, blob, z["images"], flags, RR.DINOV3_EPS, np.float32, q16=RR.fp16), z["pooler_output"])
-    eb = rel(RR.forward(cfg, blob, z["images"], flags, RR.DINOV3_EPS, np.float32, q16=R.bf16), z["pooler_output"])
+    z, cfg, flags = load(name), HF.fixture_cfg(name), HF.fixture_flags(name)
+    blob = HF.fixture_blob(name)
+    e16 = rel(R.forward(cfg, blob, z["images"], flags, HF.DINOV3_EPS, np.float32, q16=R.fp16), z["pooler_output"])
+    eb = rel(R.forward(cfg, blob, z["images"], flags, HF.DINOV3_EPS, np.float32, q16=R.bf16), z["pooler_output"])
     print(f"fixture {name}: q and k rounded twice: fp16 {e16:.3e}, bf16 {eb:.3e}")
     assert e16 <= 1e-3 and eb <= 1e-2
 
@@ -281,7 +285,7 @@ def test_rotation_of_the_reference_is_the_stated_function():
     batch, T, H, dh, lead = 2, 7, 3, 32, 2
     qkv = rng.standard_normal((batch * T, 3 * H * dh))
     a = rng.uniform(-np.pi, np.pi, (T - lead, dh // 2))
-    out = RR.rotate_qkv(qkv, np.cos(a), np.sin(a), batch, T, H, dh, lead).reshape(batch, T, 3, H, dh)
+    out = R.rotate_qkv(qkv, np.cos(a), np.sin(a), batch, T, H, dh, lead).reshape(batch, T, 3, H, dh)
     x = qkv.reshape(batch, T, 3, H, dh)
     assert np.array_equal(out[:, :lead], x[:, :lead]) and np.array_equal(out[:, :, 2], x[:, :, 2])
     b, p, w, h, d = 1, 3, 1, 2, 5

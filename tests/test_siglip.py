@@ -1,6 +1,6 @@
 """SigLIP's two switches on the host: VH_FLAG_TANH_GELU and VH_FLAG_MAP_HEAD are valid settings in the combinations the contract names,
 the blob gains the eleven map.* tensors behind head.bias, the header carries both bits, every refusal has its message, and the
-converter gives the reference's bytes.  The reference the GPU tests use, tests/siglip_ref.py, is pinned here: against three fixtures
+converter gives the reference's bytes.  The reference the GPU tests use, tests/vit_ref.py, is pinned here on these two flags: against three fixtures
 computed by Hugging Face `transformers` (SiglipVisionModel twice, SiglipForImageClassification; tests/golden/make_golden_siglip.py);
 its folded head against the literal multihead attention with K and V of every token; its blob sizes against the library.  The bound
 of the GPU kernel test (tests/test_gpu_siglip.py MAP_BOUND) is measured here from a float32 statement of the function.  No GPU needed."""
@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 
 import features_ref as FR
-import siglip_ref as SR
+import hf_state_dicts as HF
 import vh_synth as S
 import vit_ref as R
-from vh_testlib import lib_blob_bytes
+from vh_testlib import blob_digest, lib_blob_bytes, recorded_blob_digest
 
 vithip = pytest.importorskip("vithip")
 
@@ -32,7 +32,7 @@ MID = dict(image_size=64, patch_size=8, channels=3, dim=256, heads=4, mlp_dim=51
 LEGAL = [TANH, TANH | PRE, TANH | REG(4), TANH | POOL(vithip.POOL_CLS_AVG), TANH | NO_CLS | POOL(vithip.POOL_AVG_NORM),
          TANH | NO_CLS | POOL(vithip.POOL_AVG_FCNORM) | REG(2), MAP | NO_CLS, MAP | NO_CLS | TANH, MAP | NO_CLS | QUICK, MAP | NO_CLS | PRE,
          MAP | NO_CLS | TANH | PRE]
-# The GPU kernel test's bound per class of inputs (tests/siglip_ref.py map_pool_inputs): 4 x the largest error of the float32
+# The GPU kernel test's bound per class of inputs (tests/hf_state_dicts.py map_pool_inputs): 4 x the largest error of the float32
 # statement map_z32 against float64 over the kernel test's own inputs, as max |z32 - z64| / max |z64| of a case.  The factor covers
 # the summation order and the 1-ulp exp2 / rcp.  Measured by test_the_gpu_bound_is_four_times_the_float32_statements_error:
 #   random 3.63e-6, ascending 9.87e-7, descending 1.04e-6, gap 2.10e-4 (scores near 1000: their fp32 rounding, 6e-5 apiece, is the
@@ -49,8 +49,8 @@ def _create_error(cfg, flags=0, dtype=BF16, max_batch=1):
 
 
 def test_the_macro_values():
-    assert MAP == 1 << 19 == SR.FLAG_MAP_HEAD and TANH == 1 << 21 == SR.FLAG_TANH_GELU
-    assert (vithip.EPILOGUE_BIAS_TGELU, vithip.EPILOGUE_LNFOLD_TGELU) == (13, 14) and vithip.MAP_MAX_HEADS == 16 == SR.MAX_HEADS
+    assert MAP == 1 << 19 == R.FLAG_MAP_HEAD and TANH == 1 << 21 == R.FLAG_TANH_GELU
+    assert (vithip.EPILOGUE_BIAS_TGELU, vithip.EPILOGUE_LNFOLD_TGELU) == (13, 14) and vithip.MAP_MAX_HEADS == 16 == R.MAX_HEADS
     hdr = open(os.path.join(vithip.REPO_ROOT, "include", "vithip.h")).read()
     for text in ("#define VH_FLAG_MAP_HEAD (1 << 19)", "#define VH_FLAG_TANH_GELU (1 << 21)", "#define VH_EPI_BIAS_TGELU 13",
                  "#define VH_EPI_LNFOLD_TGELU 14", "#define VH_MAP_MAX_HEADS 16", "#define VH_ABI_VERSION 1", "int vh_op_map_pool("):
@@ -65,29 +65,29 @@ def test_blob_bytes_of_every_legal_combination():
         extra = 4 * (H * D + 2 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D))
         for flags in LEGAL:
             for more in (0, vithip.FLAG_W8_E4M3, vithip.FLAG_LN_FOLD_ON, vithip.FLAG_LN_FOLD_OFF):
-                assert SR.legal(cfg, flags), flags
-                want = R.blob_bytes(cfg, SR.old(flags)) + (extra if flags & MAP else 0)
-                assert lib_blob_bytes(cfg, flags | more) == want == SR.blob_bytes(cfg, flags), (flags, more)
-    # neither flag: the blob is byte for byte what it was
-    assert np.array_equal(SR.make_blob(MICRO, 5, 0), R.make_blob(MICRO, 5, 0)) and SR.blob_bytes(MICRO, 0) == 64 + 4 * S.param_count(MICRO)
+                assert R.legal(cfg, flags), flags
+                want = R.blob_bytes(cfg, flags & ~(MAP | TANH)) + (extra if flags & MAP else 0)
+                assert lib_blob_bytes(cfg, flags | more) == want == R.blob_bytes(cfg, flags), (flags, more)
+    # neither flag: the blob is byte for byte what it was (the digest recorded before the flags' module was merged into vit_ref)
+    assert blob_digest(R.make_blob(MICRO, 5, 0)) == recorded_blob_digest("vit_micro", 5, 0) and R.blob_bytes(MICRO, 0) == 64 + 4 * S.param_count(MICRO)
     # fp8 contexts take both
-    assert lib_blob_bytes(MID, MAP | NO_CLS | TANH, dtype=FP8) == SR.blob_bytes(MID, MAP | NO_CLS | TANH)
+    assert lib_blob_bytes(MID, MAP | NO_CLS | TANH, dtype=FP8) == R.blob_bytes(MID, MAP | NO_CLS | TANH)
 
 
 def test_layout_of_the_blob():
     flags = MAP | NO_CLS | TANH
-    names = [n for n, *_ in SR.tensor_table(MICRO, flags)]
+    names = [n for n, *_ in R.tensor_table(MICRO, flags)]
     assert names[-13:] == ["head.weight", "head.bias", "map.qk", "map.v.weight", "map.v.bias", "map.o.weight", "map.o.bias", "map.ln.weight",
                            "map.ln.bias", "map.fc1.weight", "map.fc1.bias", "map.fc2.weight", "map.fc2.bias"]
     # no existing offset moves: the MAP blob starts with the bytes of the same model without the head
     base = NO_CLS | POOL(vithip.POOL_AVG_NORM)
-    with_map, without = SR.make_blob(MICRO, 9, flags), R.make_blob(MICRO, 9, base)
+    with_map, without = R.make_blob(MICRO, 9, flags), R.make_blob(MICRO, 9, base)
     assert np.array_equal(with_map[64:without.nbytes], without[64:])
-    t = SR.make_tensors(MICRO, 9, flags)
+    t = R.make_tensors(MICRO, 9, flags)
     assert t["map.qk"].shape == (MICRO["heads"], MICRO["dim"]) and t["map.fc1.weight"].shape == (MICRO["mlp_dim"], MICRO["dim"])
     assert abs(float(t["map.ln.weight"].mean()) - 1.0) < 0.05
     assert with_map[52:56].view(np.uint32)[0] == (1 << 15) | (1 << 19) | (1 << 21)
-    assert SR.make_blob(MICRO, 9, TANH | PRE)[52:56].view(np.uint32)[0] == 2 | (1 << 21)
+    assert R.make_blob(MICRO, 9, TANH | PRE)[52:56].view(np.uint32)[0] == 2 | (1 << 21)
 
 
 def test_refusals_each_with_its_message():
@@ -103,7 +103,7 @@ def test_refusals_each_with_its_message():
                          (heads32, MAP | NO_CLS, "VH_FLAG_MAP_HEAD takes at most 16 heads"),
                          (MICRO, NO_CLS, "VH_POOL_CLS reads the class token"),                       # as before, without MAP_HEAD
                          (MICRO, NO_CLS | TANH, "VH_POOL_CLS reads the class token")):
-        assert not SR.legal(cfg, f), f
+        assert not R.legal(cfg, f), f
         assert lib_blob_bytes(cfg, f) == 0, f
         rc, msg = _create_error(cfg, f)
         assert rc == VH_ERR_INVALID and text in msg, (f, msg)
@@ -116,7 +116,7 @@ def test_refusals_each_with_its_message():
 
 def test_header_bits_round_trip_through_the_blob_file_entry_points(tmp_path):
     for flags in LEGAL:
-        blob = SR.make_blob(MICRO, 5, flags, 1e-5)
+        blob = R.make_blob(MICRO, 5, flags, 1e-5)
         path = tmp_path / f"micro_{flags}.vhblob"
         blob.tofile(path)
         got, eps = vithip.blob_file_config(path)
@@ -135,7 +135,7 @@ def test_forged_header_bits_are_refused(tmp_path):
         out.tofile(path)
         return out
 
-    plain = SR.make_blob(MICRO, 5, NO_CLS | POOL(vithip.POOL_AVG_NORM))
+    plain = R.make_blob(MICRO, 5, NO_CLS | POOL(vithip.POOL_AVG_NORM))
     with_bits(plain, NO_CLS | MAP)                         # the MAP bit over a blob without the eleven tensors: the length gives it away
     with pytest.raises(vithip.VhError, match="bytes, the header implies"):
         vithip.blob_file_config(path)
@@ -150,7 +150,7 @@ def test_forged_header_bits_are_refused(tmp_path):
         with pytest.raises(vithip.VhError, match="unknown bits in the header"):
             vithip.blob_file_config(path)
     # a tanh blob and an erf blob have the same size: only the header tells them apart, and the file entry points report the bit
-    erf, tanh = SR.make_blob(MICRO, 5, 0), SR.make_blob(MICRO, 5, TANH)
+    erf, tanh = R.make_blob(MICRO, 5, 0), R.make_blob(MICRO, 5, TANH)
     assert erf.nbytes == tanh.nbytes and np.array_equal(erf[64:], tanh[64:]) and not np.array_equal(erf[:64], tanh[:64])
     with_bits(erf, 1 << 21)
     assert vithip.blob_file_flags(path) == TANH
@@ -164,8 +164,8 @@ def load_fixture(path):
 
 
 def fixture_blob(cfg, wseed, classifier, eps, prefix=""):
-    t, raw, flags = SR.siglip_tensors(cfg, wseed, classifier)
-    return vithip.blob_from_siglip_state_dict(SR.siglip_state_dict(cfg, t, raw, classifier, prefix), cfg, eps), flags
+    t, raw, flags = HF.siglip_tensors(cfg, wseed, classifier)
+    return vithip.blob_from_siglip_state_dict(HF.siglip_state_dict(cfg, t, raw, classifier, prefix), cfg, eps), flags
 
 
 def test_fixtures_are_present():
@@ -175,17 +175,17 @@ def test_fixtures_are_present():
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p).split("_s")[0] for p in GOLDEN])
 def test_siglip_ref_reproduces_the_transformers_fixture(path):
-    """pooler_output / the logits and last_hidden_state of the transformers model (float64) against siglip_ref in float64, the blob
+    """pooler_output / the logits and last_hidden_state of the transformers model (float64) against vit_ref in float64, the blob
     made by the converter (its fold included).  The bound 1e-5 is tests/test_pool.py's for the same comparison: the fp32 rounding of
     the weights -- and here of the folded map.qk."""
     z, cfg, wseed, iseed, batch, flags, classifier, eps = load_fixture(path)
     blob, made = fixture_blob(cfg, wseed, classifier, eps)
-    assert made == flags == vithip.blob_flags_of(blob) and blob.nbytes == SR.blob_bytes(cfg, flags) == lib_blob_bytes(cfg, flags)
+    assert made == flags == vithip.blob_flags_of(blob) and blob.nbytes == R.blob_bytes(cfg, flags) == lib_blob_bytes(cfg, flags)
     assert bool(flags & MAP) != classifier and flags & TANH and flags & NO_CLS
     images = S.make_images(cfg, iseed, batch)
     assert abs(float(images.astype(np.float64).sum()) - float(z["images_checksum"][0])) < 1e-9
-    out, x = SR.forward(cfg, blob, images, flags, eps, np.float64, want_hidden=True)
-    t = SR.unpack_blob(cfg, blob, flags)
+    out, x = R.forward(cfg, blob, images, flags, eps, np.float64, want_hidden=True)
+    t = R.unpack_blob(cfg, blob, flags)
     last = R.layernorm(x, t["lnf.weight"].astype(np.float64), t["lnf.bias"].astype(np.float64), eps)
     for name, got, want in (("last_hidden_state", last.reshape(z["last_hidden_state"].shape), z["last_hidden_state"]), ("output", out, z["output"])):
         e = float(np.abs(got - want).max() / np.abs(want).max())
@@ -195,7 +195,7 @@ def test_siglip_ref_reproduces_the_transformers_fixture(path):
     if classifier:
         erf_blob = blob.copy()
         erf_blob[52:56] = np.array([flags & ~TANH], np.uint32).view(np.uint8)
-        wrong = SR.forward(cfg, erf_blob, images, flags & ~TANH, eps, np.float64)
+        wrong = R.forward(cfg, erf_blob, images, flags & ~TANH, eps, np.float64)
         assert float(np.abs(wrong - z["output"]).max() / np.abs(z["output"]).max()) > 2e-5
 
 
@@ -208,9 +208,9 @@ def test_the_folded_head_is_the_literal_multihead_attention():
         probe = rng.standard_normal(D) * 0.5
         in_w, in_b = rng.standard_normal((3 * D, D)) * 0.06, rng.standard_normal(3 * D) * 0.8      # large biases: the key bias must cancel
         out_w, out_b = rng.standard_normal((D, D)) * 0.06, rng.standard_normal(D) * 0.1
-        want = SR.literal_map(y, probe, in_w, in_b, out_w, out_b, H)
-        qk = SR.fold_qk(probe, in_w[:D], in_b[:D], in_w[D:2 * D], H)
-        z = SR.map_z(y, qk)
+        want = R.literal_map(y, probe, in_w, in_b, out_w, out_b, H)
+        qk = R.fold_qk(probe, in_w[:D], in_b[:D], in_w[D:2 * D], H)
+        z = R.map_z(y, qk)
         a = np.einsum("bhk,hjk->bhj", z, in_w[2 * D:].reshape(H, D // H, D)).reshape(batch, D) + in_b[2 * D:]
         got = a @ out_w.T + out_b
         e = float(np.abs(got - want).max() / np.abs(want).max())
@@ -225,12 +225,12 @@ def test_the_folded_head_is_the_literal_multihead_attention():
 def test_converter_gives_pack_blobs_bytes_and_refuses():
     A = dict(image_size=40, patch_size=8, channels=3, dim=256, heads=4, mlp_dim=512, layers=2, classes=256)
     for classifier, cfg in ((False, A), (True, dict(A, classes=8))):
-        t, raw, flags = SR.siglip_tensors(cfg, 7, classifier)
-        want = SR.pack_blob(cfg, SR.fixture_blob_tensors(cfg, t, raw, flags), flags, 1e-6)
+        t, raw, flags = HF.siglip_tensors(cfg, 7, classifier)
+        want = R.pack_blob(cfg, HF.fixture_blob_tensors(cfg, t, raw, flags), flags, 1e-6)
         for prefix in ("", "vision_model."):
-            sd = SR.siglip_state_dict(cfg, t, raw, classifier, prefix)
+            sd = HF.siglip_state_dict(cfg, t, raw, classifier, prefix)
             assert np.array_equal(vithip.blob_from_siglip_state_dict(sd, cfg, 1e-6), want), (classifier, prefix)
-    sd = SR.siglip_state_dict(A, *SR.siglip_tensors(A, 7, False)[:2], False)
+    sd = HF.siglip_state_dict(A, *HF.siglip_tensors(A, 7, False)[:2], False)
     conv = vithip.blob_from_siglip_state_dict
     assert vithip.blob_flags_of(conv(sd, A, hidden_act="gelu")) == NO_CLS | MAP
     assert vithip.blob_flags_of(conv(sd, A, hidden_act="quick_gelu")) == NO_CLS | MAP | QUICK
@@ -271,17 +271,17 @@ def test_the_gpu_bound_is_four_times_the_float32_statements_error():
     cases arranged as their names say."""
     forms = (vithip.FEAT_FORM_F32, BF16, FP16, FP8)
     worst = {}
-    for dim in SR.MAP_DIMS:
-        for heads, NP, lead, batch, order in SR.map_pool_cases(dim):
-            x, gamma, beta, qk = SR.map_pool_inputs(dim, heads, NP, lead, batch, order)
+    for dim in HF.MAP_DIMS:
+        for heads, NP, lead, batch, order in HF.map_pool_cases(dim):
+            x, gamma, beta, qk = HF.map_pool_inputs(dim, heads, NP, lead, batch, order)
             assert np.abs(x).max() == 300.0
             for fm in forms:
                 xr = FR.split_planes(x.reshape(-1, dim), fm)[2].reshape(x.shape)
-                z64, s = SR.map_z64(xr, gamma, beta, qk, lead)
+                z64, s = HF.map_z64(xr, gamma, beta, qk, lead)
                 assert np.isfinite(z64).all()
-                e = float(np.abs(SR.map_z32(xr, gamma, beta, qk, lead) - z64).max() / np.abs(z64).max())
+                e = float(np.abs(HF.map_z32(xr, gamma, beta, qk, lead) - z64).max() / np.abs(z64).max())
                 worst[order] = max(worst.get(order, 0.0), e)
-                g = SR.map_pool_group(dim, heads)
+                g = HF.map_pool_group(dim, heads)
                 if order == "ascending":
                     assert (np.diff(s, axis=-1) >= 0).all()
                 elif order == "descending":

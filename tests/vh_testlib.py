@@ -3,6 +3,9 @@
 A GPU module that uses `dev` imports the fixture by name with it, `from vh_testlib import dev, _release_buffers`: pytest runs an
 autouse fixture that stands in the module's namespace, and the buffers of a test are freed when it ends."""
 import ctypes as C
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -29,6 +32,17 @@ def vit_cfg(image, patch, dim, heads, mlp, layers, classes, channels=3):
 def lib_blob_bytes(cfg, flags=0, dtype=vithip.DTYPE_BF16, max_batch=1, ln_eps=1e-6):
     c = vithip.make_config(cfg, dtype, max_batch, ln_eps, flags)
     return vithip.lib().vh_weight_blob_bytes(C.byref(c))
+
+
+def blob_digest(blob):
+    return hashlib.sha256(np.ascontiguousarray(blob, dtype=np.uint8).tobytes()).hexdigest()
+
+
+def recorded_blob_digest(shape, seed, flags):
+    """The SHA-256 of the reference's make_blob(SHAPES[shape], seed, flags) as tests/golden/ref_digests.json records it
+    (tests/golden/make_ref_digests.py; shapes "vit_micro" and "hd80", seeds 5 and 9)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_digests.json")) as f:
+        return json.load(f)["make_blob"][shape][str(seed)][str(flags)]
 
 
 _KEEP = []

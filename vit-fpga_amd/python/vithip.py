@@ -422,15 +422,70 @@ def blob_file_flags(path):
     return c.flags
 
 
-def _blob_header(cfg, ln_eps, bits):
+# The header's flags word (byte 52) carries the model bits of vh_config flags: these two at header positions of their own, the rest at
+# their flag positions (bit 0 of the word belongs to the file form's checksum).
+_HEADER_BITS = ((FLAG_PRE_LN, 2), (FLAG_QUICK_GELU, 4))
+_SAME_BITS = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE
+
+
+def _blob_bits(flags):
+    """vh_config flags -> the model bits of a blob header's flags word."""
+    return sum(h for f, h in _HEADER_BITS if flags & f) | (flags & _SAME_BITS)
+
+
+def blob_flags_of(blob):
+    """The model bits of a memory blob's header as vh_config flags (what blob_file_flags returns for a file)."""
+    bits = int(np.ascontiguousarray(blob[52:56]).view(np.uint32)[0])
+    return sum(f for f, h in _HEADER_BITS if bits & h) | (bits & _SAME_BITS)
+
+
+def _blob_header(cfg, ln_eps, flags):
     """The 64-byte header of a memory blob: magic, the model shape, ln_eps and the model bits of the flags word (byte 52)."""
     h = np.zeros(64, dtype=np.uint8)
     h[:7] = np.frombuffer(b"VHBLOB1", dtype=np.uint8)
     h[8:40] = np.array([cfg[k] for k in ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")],
                        dtype=np.int32).view(np.uint8)
     h[40:44] = np.array([ln_eps], dtype=np.float32).view(np.uint8)
-    h[52:56] = np.array([bits], dtype=np.uint32).view(np.uint8)
+    h[52:56] = np.array([_blob_bits(flags)], dtype=np.uint32).view(np.uint8)
     return h
+
+
+def blob_tensor_table(cfg, flags=0):
+    """[(name, shape)] of the canonical blob's fp32 tensors behind the header, in blob order, for a context of these model flags: the
+    names of include/vithip.h's blob section.  The one statement of the order on the Python side; every converter packs through it."""
+    D, M, E, P, CH, H = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"], cfg["heads"]
+    NP = (cfg["image_size"] // P) ** 2
+    R, cls = registers_of(flags), 0 if flags & FLAG_NO_CLS else 1
+    t = [("patch.weight", (D, CH, P, P)), ("patch.bias", (D,))] + [("cls", (D,))] * cls + [("pos", (NP + cls, D))]
+    if R:
+        t.append(("reg", (R, D)))
+    if flags & FLAG_PRE_LN:
+        t += [("pre_ln.weight", (D,)), ("pre_ln.bias", (D,))]
+    rows = {"ln1": (D,), "q": (D, D), "k": (D, D), "v": (D, D), "o": (D, D), "ln2": (D,), "fc1": (M, D), "fc2": (D, M)}
+    for l in range(cfg["layers"]):
+        for n, shape in rows.items():
+            t += [(f"l{l}.{n}.weight", shape), (f"l{l}.{n}.bias", shape[:1])]
+    t += [("lnf.weight", (D,)), ("lnf.bias", (D,)), ("head.weight", (E, 2 * D if pool_of(flags) == POOL_CLS_AVG else D)), ("head.bias", (E,))]
+    if flags & FLAG_MAP_HEAD:
+        t += [("map.qk", (H, D)), ("map.v.weight", (D, D)), ("map.v.bias", (D,)), ("map.o.weight", (D, D)), ("map.o.bias", (D,)),
+              ("map.ln.weight", (D,)), ("map.ln.bias", (D,)), ("map.fc1.weight", (M, D)), ("map.fc1.bias", (M,)),
+              ("map.fc2.weight", (D, M)), ("map.fc2.bias", (D,))]
+    if flags & FLAG_ROPE:
+        t += [("rope.cos", (NP, D // H // 2)), ("rope.sin", (NP, D // H // 2))]
+    return t
+
+
+def _pack_blob(me, cfg, ln_eps, flags, tensors):
+    """The blob of a converter's `tensors` {blob_tensor_table name: array}: every name of the table, with exactly its element count."""
+    parts = [_blob_header(cfg, ln_eps, flags)]
+    for name, shape in blob_tensor_table(cfg, flags):
+        if name not in tensors:
+            raise KeyError(f"{me}: no tensor for {name}")
+        a = np.ascontiguousarray(tensors[name], dtype=np.float32).reshape(-1)
+        if a.size != int(np.prod(shape)):
+            raise ValueError(f"{me}: {name} has {a.size} elements, the blob holds {tuple(shape)}")
+        parts.append(a.view(np.uint8))
+    return np.concatenate(parts)
 
 
 def _taker(sd, me):
@@ -445,44 +500,88 @@ def _taker(sd, me):
     return take
 
 
+def _take_named(take, cfg, flags, top, layer_prefix, layer):
+    """{our name: tensor} for the rows of blob_tensor_table that a converter's name table covers.  top: {our name: their name, or
+    (their name, their shape) where it is not ours, or None for a row the converter fills itself}; layer: {ln1, q, ..: their
+    module} under layer_prefix.format(l)."""
+    names = {f"l{l}.{ours}.{wb}": f"{layer_prefix.format(l)}{theirs}.{wb}"
+             for l in range(cfg["layers"]) for ours, theirs in layer.items() for wb in ("weight", "bias")}
+    names.update(top)
+    out = {}
+    for name, shape in blob_tensor_table(cfg, flags):
+        theirs = names.get(name)
+        if theirs is not None:
+            out[name] = take(theirs, shape) if isinstance(theirs, str) else take(*theirs)
+    return out
+
+
+def _scaled(take, sd, D, n_in, module, lname, optional=False):
+    """LayerScale folded into the layer it scales: diag(lambda) W and lambda b in float64, one rounding to fp32 (exact for
+    lambda == 1).  optional: a checkpoint without `lname` has no LayerScale."""
+    w, b = take(module + ".weight", (D, n_in), np.float64).reshape(D, n_in), take(module + ".bias", (D,), np.float64)
+    if not optional or lname in sd:
+        lam = take(lname, (D,), np.float64)
+        w, b = w * lam[:, None], b * lam
+    return w.astype(np.float32).reshape(-1), b.astype(np.float32)
+
+
+def _head(me, head, E, W):
+    """(weight, bias) of a converter's `head` argument: zeros when there is none."""
+    if head is None:
+        return np.zeros(E * W, np.float32), np.zeros(E, np.float32)
+    hw, hb = (np.asarray(a) for a in head)
+    if hw.shape != (E, W) or hb.shape != (E,):
+        raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, W)}, {(E,)}")
+    return hw, hb
+
+
+def _register_count(me, cfg, sd, key):
+    """cfg['registers'], which must be the row count of the checkpoint's register tensor `key` (absent: 0)."""
+    R = int(cfg.get("registers", 0))
+    have = int(np.asarray(sd[key]).shape[-2]) if key in sd else 0
+    if have != R:
+        raise ValueError(f"{me}: the checkpoint has {have} register tokens, cfg['registers'] is {R}")
+    return R
+
+
+def _check_dino_args(me, cfg, pool):
+    if pool not in (POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM, POOL_CLS_AVG):
+        raise ValueError(f"{me}: pool = {pool} is not POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM or POOL_CLS_AVG")
+    R = int(cfg.get("registers", 0))
+    if not 0 <= R <= MAX_REGISTERS:
+        raise ValueError(f"{me}: cfg['registers'] = {R} is outside 0 .. {MAX_REGISTERS}")
+
+
+# their module of each of our layer tensors; o and fc2 are missing where LayerScale is folded into them
+_CLIP_LAYER = {"ln1": "layer_norm1", "q": "self_attn.q_proj", "k": "self_attn.k_proj", "v": "self_attn.v_proj", "o": "self_attn.out_proj",
+               "ln2": "layer_norm2", "fc1": "mlp.fc1", "fc2": "mlp.fc2"}
+_DINOV2_LAYER = {"ln1": "norm1", "q": "attention.attention.query", "k": "attention.attention.key", "v": "attention.attention.value",
+                 "ln2": "norm2", "fc1": "mlp.fc1"}
+_DINOV3_LAYER = {"ln1": "norm1", "q": "attention.q_proj", "k": "attention.k_proj", "v": "attention.v_proj", "ln2": "norm2", "fc1": "mlp.up_proj"}
+_IJEPA_LAYER = {"ln1": "layernorm_before", "q": "attention.q_proj", "k": "attention.k_proj", "v": "attention.v_proj", "o": "attention.o_proj",
+                "ln2": "layernorm_after", "fc1": "mlp.fc1", "fc2": "mlp.fc2"}
+_TIMM_LAYER = {"ln1": "norm1", "ln2": "norm2", "fc1": "mlp.fc1"}
+
+
 def blob_from_clip_state_dict(sd, cfg, ln_eps=1e-5):
     """Canonical blob of a CLIP vision tower from a dict of arrays under the Hugging Face `CLIPVisionModelWithProjection`
     parameter names (numpy only; torch tensors: pass `{k: v.numpy() for k, v in model.state_dict().items()}`).
     `cfg`: the model shape with classes = the projection width, plus `flags` (FLAG_PRE_LN always; FLAG_QUICK_GELU for
     hidden_act == "quick_gelu").  CLIP's patch convolution and projection have no bias: both are written as zeros; the
     header carries the model bits.  A missing or wrongly shaped tensor is refused by name."""
-    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
-    g = cfg["image_size"] // cfg["patch_size"]
+    me = "blob_from_clip_state_dict"
     flags = cfg.get("flags", FLAG_PRE_LN)
     if not flags & FLAG_PRE_LN:
-        raise ValueError("blob_from_clip_state_dict: every CLIP vision tower has ln_pre: cfg['flags'] needs FLAG_PRE_LN")
+        raise ValueError(f"{me}: every CLIP vision tower has ln_pre: cfg['flags'] needs FLAG_PRE_LN")
     if flags & ~(FLAG_PRE_LN | FLAG_QUICK_GELU):
-        raise ValueError("blob_from_clip_state_dict: cfg['flags'] takes the model bits FLAG_PRE_LN | FLAG_QUICK_GELU only")
-
-    def take(name, shape):
-        if name not in sd:
-            raise KeyError(f"blob_from_clip_state_dict: missing tensor {name}")
-        a = np.asarray(sd[name], dtype=np.float32)
-        if a.shape != tuple(shape):
-            raise ValueError(f"blob_from_clip_state_dict: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}")
-        return np.ascontiguousarray(a).reshape(-1)
-
+        raise ValueError(f"{me}: cfg['flags'] takes the model bits FLAG_PRE_LN | FLAG_QUICK_GELU only")
     v, emb = "vision_model.", "vision_model.embeddings."
-    parts = [take(emb + "patch_embedding.weight", (D, CH, P, P)), np.zeros(D, np.float32),
-             take(emb + "class_embedding", (D,)), take(emb + "position_embedding.weight", (g * g + 1, D)),
-             take(v + "pre_layrnorm.weight", (D,)), take(v + "pre_layrnorm.bias", (D,))]
-    for l in range(cfg["layers"]):
-        b = f"{v}encoder.layers.{l}."
-        parts += [take(b + "layer_norm1.weight", (D,)), take(b + "layer_norm1.bias", (D,))]
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            parts += [take(f"{b}self_attn.{n}.weight", (D, D)), take(f"{b}self_attn.{n}.bias", (D,))]
-        parts += [take(b + "layer_norm2.weight", (D,)), take(b + "layer_norm2.bias", (D,)),
-                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,)),
-                  take(b + "mlp.fc2.weight", (D, M)), take(b + "mlp.fc2.bias", (D,))]
-    parts += [take(v + "post_layernorm.weight", (D,)), take(v + "post_layernorm.bias", (D,)),
-              take("visual_projection.weight", (E, D)), np.zeros(E, np.float32)]
-    h = _blob_header(cfg, ln_eps, 2 | (4 if flags & FLAG_QUICK_GELU else 0))   # header flags word: bit 1 pre-LN, bit 2 QuickGELU
-    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+    top = {"patch.weight": emb + "patch_embedding.weight", "cls": emb + "class_embedding", "pos": emb + "position_embedding.weight",
+           "pre_ln.weight": v + "pre_layrnorm.weight", "pre_ln.bias": v + "pre_layrnorm.bias",
+           "lnf.weight": v + "post_layernorm.weight", "lnf.bias": v + "post_layernorm.bias", "head.weight": "visual_projection.weight"}
+    t = _take_named(_taker(sd, me), cfg, flags, top, v + "encoder.layers.{}.", _CLIP_LAYER)
+    t["patch.bias"], t["head.bias"] = np.zeros(cfg["dim"], np.float32), np.zeros(cfg["classes"], np.float32)
+    return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
 def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
@@ -500,62 +599,35 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
     dropped and `classifier.*` is the head unless `head` is given.  The head's shape is checked against the mode ([classes, dim]
     for POOL_CLS / POOL_AVG_NORM / POOL_AVG_FCNORM); the header carries FLAG_POOL(pool)."""
     me = "blob_from_dinov2_state_dict"
-    if pool not in (POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM, POOL_CLS_AVG):
-        raise ValueError(f"{me}: pool = {pool} is not POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM or POOL_CLS_AVG")
+    _check_dino_args(me, cfg, pool)
     for prefix in ("dinov2.", "dinov2_with_registers."):
         if any(k.startswith(prefix) for k in sd):
             if head is None and "classifier.weight" in sd and "classifier.bias" in sd:
                 head = (sd["classifier.weight"], sd["classifier.bias"])
             sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
-    W = 2 * D if pool == POOL_CLS_AVG else D
-    g = cfg["image_size"] // cfg["patch_size"]
-    R = int(cfg.get("registers", 0))
-    if not 0 <= R <= MAX_REGISTERS:
-        raise ValueError(f"{me}: cfg['registers'] = {R} is outside 0 .. {MAX_REGISTERS}")
+    D, M, E = cfg["dim"], cfg["mlp_dim"], cfg["classes"]
+    NP = (cfg["image_size"] // cfg["patch_size"]) ** 2
     if any(k.endswith("mlp.weights_in.weight") for k in sd):
         raise ValueError(f"{me}: the checkpoint has a SwiGLU MLP (mlp.weights_in), which this library does not run")
     emb = "embeddings."
-    have = int(np.asarray(sd[emb + "register_tokens"]).shape[-2]) if emb + "register_tokens" in sd else 0
-    if have != R:
-        raise ValueError(f"{me}: the checkpoint has {have} register tokens, cfg['registers'] is {R}")
+    R = _register_count(me, cfg, sd, emb + "register_tokens")
     if emb + "position_embeddings" in sd:
         rows = int(np.asarray(sd[emb + "position_embeddings"]).shape[-2])
-        if rows != g * g + 1:
-            raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP + 1 = {g * g + 1} "
+        if rows != NP + 1:
+            raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP + 1 = {NP + 1} "
                              "(interpolate the table to the image size first)")
-
+    flags = FLAG_REGISTERS(R) | FLAG_POOL(pool)
     take = _taker(sd, me)
-
-    def scaled(wname, bname, lname, n_in):
-        # diag(lambda) W and lambda b in float64, one rounding to fp32 (exact for lambda == 1)
-        lam = take(lname, (D,), np.float64)
-        w = take(wname, (D, n_in), np.float64).reshape(D, n_in) * lam[:, None]
-        return [w.astype(np.float32).reshape(-1), (take(bname, (D,), np.float64) * lam).astype(np.float32)]
-
-    parts = [take(emb + "patch_embeddings.projection.weight", (D, CH, P, P)), take(emb + "patch_embeddings.projection.bias", (D,)),
-             take(emb + "cls_token", (1, 1, D)), take(emb + "position_embeddings", (1, g * g + 1, D))]
-    if R:
-        parts.append(take(emb + "register_tokens", (1, R, D)))
+    top = {"patch.weight": emb + "patch_embeddings.projection.weight", "patch.bias": emb + "patch_embeddings.projection.bias",
+           "cls": (emb + "cls_token", (1, 1, D)), "pos": (emb + "position_embeddings", (1, NP + 1, D)),
+           "reg": (emb + "register_tokens", (1, R, D)), "lnf.weight": "layernorm.weight", "lnf.bias": "layernorm.bias"}
+    t = _take_named(take, cfg, flags, top, "encoder.layer.{}.", _DINOV2_LAYER)
     for l in range(cfg["layers"]):
         b = f"encoder.layer.{l}."
-        parts += [take(b + "norm1.weight", (D,)), take(b + "norm1.bias", (D,))]
-        for n in ("query", "key", "value"):
-            parts += [take(f"{b}attention.attention.{n}.weight", (D, D)), take(f"{b}attention.attention.{n}.bias", (D,))]
-        parts += scaled(b + "attention.output.dense.weight", b + "attention.output.dense.bias", b + "layer_scale1.lambda1", D)
-        parts += [take(b + "norm2.weight", (D,)), take(b + "norm2.bias", (D,)),
-                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,))]
-        parts += scaled(b + "mlp.fc2.weight", b + "mlp.fc2.bias", b + "layer_scale2.lambda1", M)
-    parts += [take("layernorm.weight", (D,)), take("layernorm.bias", (D,))]
-    if head is None:
-        parts += [np.zeros(E * W, np.float32), np.zeros(E, np.float32)]
-    else:
-        hw, hb = (np.asarray(a) for a in head)
-        if hw.shape != (E, W) or hb.shape != (E,):
-            raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, W)}, {(E,)}")
-        parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
-    h = _blob_header(cfg, ln_eps, FLAG_REGISTERS(R) | FLAG_POOL(pool))   # header flags word: bits 9 .. 13 = register tokens, 16 .. 17 = pooling
-    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+        t[f"l{l}.o.weight"], t[f"l{l}.o.bias"] = _scaled(take, sd, D, D, b + "attention.output.dense", b + "layer_scale1.lambda1")
+        t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.fc2", b + "layer_scale2.lambda1")
+    t["head.weight"], t["head.bias"] = _head(me, head, E, 2 * D if pool == POOL_CLS_AVG else D)
+    return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
 def blob_from_siglip_state_dict(sd, cfg, ln_eps=1e-6, hidden_act="gelu_pytorch_tanh"):
@@ -576,8 +648,8 @@ def blob_from_siglip_state_dict(sd, cfg, ln_eps=1e-6, hidden_act="gelu_pytorch_t
     acts = {"gelu_pytorch_tanh": FLAG_TANH_GELU, "gelu": 0, "quick_gelu": FLAG_QUICK_GELU}
     if hidden_act not in acts:
         raise ValueError(f"{me}: hidden_act = {hidden_act!r} is not one of {sorted(acts)}")
-    D, M, E, P, CH, H = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"], cfg["heads"]
-    g = cfg["image_size"] // cfg["patch_size"]
+    D, E, H = cfg["dim"], cfg["classes"], cfg["heads"]
+    NP = (cfg["image_size"] // cfg["patch_size"]) ** 2
     if any(k.startswith("vision_model.") for k in sd):
         sd = dict({k[len("vision_model."):]: v for k, v in sd.items() if k.startswith("vision_model.")},
                   **{k: v for k, v in sd.items() if k.startswith("classifier.")})
@@ -587,40 +659,30 @@ def blob_from_siglip_state_dict(sd, cfg, ln_eps=1e-6, hidden_act="gelu_pytorch_t
         raise ValueError(f"{me}: without a classifier the head is the identity: cfg['classes'] = {E} must equal cfg['dim'] = {D}")
     if not classifier and H > MAP_MAX_HEADS:
         raise ValueError(f"{me}: the attention-pooling head takes at most {MAP_MAX_HEADS} heads, cfg['heads'] is {H}")
-    emb = "embeddings."
+    emb, h = "embeddings.", "head."
     if emb + "position_embedding.weight" in sd:
         rows = int(np.asarray(sd[emb + "position_embedding.weight"]).shape[0])
-        if rows != g * g:
-            raise ValueError(f"{me}: {emb}position_embedding.weight has {rows} rows, cfg needs NP = {g * g} (interpolate the table first)")
+        if rows != NP:
+            raise ValueError(f"{me}: {emb}position_embedding.weight has {rows} rows, cfg needs NP = {NP} (interpolate the table first)")
     take = _taker(sd, me)
-    parts = [take(emb + "patch_embedding.weight", (D, CH, P, P)), take(emb + "patch_embedding.bias", (D,)),
-             take(emb + "position_embedding.weight", (g * g, D))]
-    for l in range(cfg["layers"]):
-        b = f"encoder.layers.{l}."
-        parts += [take(b + "layer_norm1.weight", (D,)), take(b + "layer_norm1.bias", (D,))]
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            parts += [take(f"{b}self_attn.{n}.weight", (D, D)), take(f"{b}self_attn.{n}.bias", (D,))]
-        parts += [take(b + "layer_norm2.weight", (D,)), take(b + "layer_norm2.bias", (D,)),
-                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,)),
-                  take(b + "mlp.fc2.weight", (D, M)), take(b + "mlp.fc2.bias", (D,))]
-    parts += [take("post_layernorm.weight", (D,)), take("post_layernorm.bias", (D,))]
+    top = {"patch.weight": emb + "patch_embedding.weight", "patch.bias": emb + "patch_embedding.bias", "pos": emb + "position_embedding.weight",
+           "lnf.weight": "post_layernorm.weight", "lnf.bias": "post_layernorm.bias",
+           "map.o.weight": h + "attention.out_proj.weight", "map.o.bias": h + "attention.out_proj.bias",
+           "map.ln.weight": h + "layernorm.weight", "map.ln.bias": h + "layernorm.bias", "map.fc1.weight": h + "mlp.fc1.weight",
+           "map.fc1.bias": h + "mlp.fc1.bias", "map.fc2.weight": h + "mlp.fc2.weight", "map.fc2.bias": h + "mlp.fc2.bias"}
     if classifier:
-        parts += [take("classifier.weight", (E, D)), take("classifier.bias", (E,))]
-    else:
-        parts += [np.eye(D, dtype=np.float32).reshape(-1), np.zeros(D, np.float32)]
-        h, hd = "head.", D // H
+        top.update({"head.weight": "classifier.weight", "head.bias": "classifier.bias"})
+    t = _take_named(take, cfg, flags, top, "encoder.layers.{}.", _CLIP_LAYER)
+    if not classifier:
+        t["head.weight"], t["head.bias"] = np.eye(D, dtype=np.float32), np.zeros(D, np.float32)
+        hd = D // H
         probe = take(h + "probe", (1, 1, D), np.float64)
         w = take(h + "attention.in_proj_weight", (3 * D, D), np.float64).reshape(3, D, D)
         bias = take(h + "attention.in_proj_bias", (3 * D,), np.float64).reshape(3, D)
         q = ((w[0] @ probe + bias[0]) / np.sqrt(float(hd))).reshape(H, hd)               # the query of every image, scaled
-        qk = np.einsum("hj,hjk->hk", q, w[1].reshape(H, hd, D))                           # through the key projection, per head
-        parts += [qk.astype(np.float32).reshape(-1), w[2].astype(np.float32).reshape(-1), bias[2].astype(np.float32),
-                  take(h + "attention.out_proj.weight", (D, D)), take(h + "attention.out_proj.bias", (D,)),
-                  take(h + "layernorm.weight", (D,)), take(h + "layernorm.bias", (D,)),
-                  take(h + "mlp.fc1.weight", (M, D)), take(h + "mlp.fc1.bias", (M,)),
-                  take(h + "mlp.fc2.weight", (D, M)), take(h + "mlp.fc2.bias", (D,))]
-    bits = (4 if flags & FLAG_QUICK_GELU else 0) | (flags & (FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU))
-    return np.concatenate([_blob_header(cfg, ln_eps, bits)] + [p.view(np.uint8) for p in parts])
+        t["map.qk"] = np.einsum("hj,hjk->hk", q, w[1].reshape(H, hd, D))                  # through the key projection, per head
+        t["map.v.weight"], t["map.v.bias"] = w[2], bias[2]
+    return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
 def rope_tables_dinov3(grid, head_dim, theta=100.0):
@@ -650,62 +712,30 @@ def blob_from_dinov3_state_dict(sd, cfg, ln_eps=1e-5, head=None, pool=POOL_CLS, 
     Header flags: FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool).  Refused by name: a gated MLP (mlp.gate_proj: the H+ and 7B
     checkpoints), a register count other than cfg['registers'], a missing or wrongly shaped tensor."""
     me = "blob_from_dinov3_state_dict"
-    if pool not in (POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM, POOL_CLS_AVG):
-        raise ValueError(f"{me}: pool = {pool} is not POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM or POOL_CLS_AVG")
-    D, M, E, P, CH, H = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"], cfg["heads"]
-    W = 2 * D if pool == POOL_CLS_AVG else D
+    _check_dino_args(me, cfg, pool)
+    D, M, E, H = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["heads"]
     g = cfg["image_size"] // cfg["patch_size"]
-    R = int(cfg.get("registers", 0))
-    if not 0 <= R <= MAX_REGISTERS:
-        raise ValueError(f"{me}: cfg['registers'] = {R} is outside 0 .. {MAX_REGISTERS}")
     if any(k.endswith("mlp.gate_proj.weight") for k in sd):
         raise ValueError(f"{me}: the checkpoint has a gated MLP (mlp.gate_proj), which this library does not run")
     emb = "embeddings."
-    have = int(np.asarray(sd[emb + "register_tokens"]).shape[-2]) if emb + "register_tokens" in sd else 0
-    if have != R:
-        raise ValueError(f"{me}: the checkpoint has {have} register tokens, cfg['registers'] is {R}")
+    R = _register_count(me, cfg, sd, emb + "register_tokens")
     pre = "model.layer." if any(k.startswith("model.layer.") for k in sd) else "layer."
+    flags = FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool)
     take = _taker(sd, me)
-
-    def scaled(wname, bname, lname, n_in):
-        lam = take(lname, (D,), np.float64)
-        w = take(wname, (D, n_in), np.float64).reshape(D, n_in) * lam[:, None]
-        return [w.astype(np.float32).reshape(-1), (take(bname, (D,), np.float64) * lam).astype(np.float32)]
-
-    parts = [take(emb + "patch_embeddings.weight", (D, CH, P, P)), take(emb + "patch_embeddings.bias", (D,)),
-             take(emb + "cls_token", (1, 1, D)), np.zeros((g * g + 1) * D, np.float32)]
-    if R:
-        parts.append(take(emb + "register_tokens", (1, R, D)))
+    top = {"patch.weight": emb + "patch_embeddings.weight", "patch.bias": emb + "patch_embeddings.bias", "cls": (emb + "cls_token", (1, 1, D)),
+           "reg": (emb + "register_tokens", (1, R, D)), "lnf.weight": "norm.weight", "lnf.bias": "norm.bias"}
+    no_key_bias = [f"l{l}.k.bias" for l in range(cfg["layers"]) if f"{pre}{l}.attention.k_proj.bias" not in sd]      # key_bias=False: zeros
+    top.update(dict.fromkeys(no_key_bias))
+    t = _take_named(take, cfg, flags, top, pre + "{}.", _DINOV3_LAYER)
+    t.update({n: np.zeros(D, np.float32) for n in no_key_bias})
+    t["pos"] = np.zeros((g * g + 1) * D, np.float32)                                      # the model has no position table
     for l in range(cfg["layers"]):
         b = f"{pre}{l}."
-        parts += [take(b + "norm1.weight", (D,)), take(b + "norm1.bias", (D,))]
-        for n in ("q_proj", "k_proj", "v_proj"):
-            parts.append(take(f"{b}attention.{n}.weight", (D, D)))
-            parts.append(np.zeros(D, np.float32) if n == "k_proj" and f"{b}attention.{n}.bias" not in sd
-                         else take(f"{b}attention.{n}.bias", (D,)))
-        parts += scaled(b + "attention.o_proj.weight", b + "attention.o_proj.bias", b + "layer_scale1.lambda1", D)
-        parts += [take(b + "norm2.weight", (D,)), take(b + "norm2.bias", (D,)),
-                  take(b + "mlp.up_proj.weight", (M, D)), take(b + "mlp.up_proj.bias", (M,))]
-        parts += scaled(b + "mlp.down_proj.weight", b + "mlp.down_proj.bias", b + "layer_scale2.lambda1", M)
-    parts += [take("norm.weight", (D,)), take("norm.bias", (D,))]
-    if head is None:
-        parts += [np.zeros(E * W, np.float32), np.zeros(E, np.float32)]
-    else:
-        hw, hb = (np.asarray(a) for a in head)
-        if hw.shape != (E, W) or hb.shape != (E,):
-            raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, W)}, {(E,)}")
-        parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
-    cos, sin = rope_tables_dinov3(g, D // H, theta)
-    parts += [cos.reshape(-1), sin.reshape(-1)]
-    h = _blob_header(cfg, ln_eps, FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool))
-    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
-
-
-def blob_flags_of(blob):
-    """The model bits of a memory blob's header as vh_config flags (what blob_file_flags returns for a file)."""
-    bits = int(np.ascontiguousarray(blob[52:56]).view(np.uint32)[0])
-    same = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE
-    return (FLAG_PRE_LN if bits & 2 else 0) | (FLAG_QUICK_GELU if bits & 4 else 0) | (bits & same)
+        t[f"l{l}.o.weight"], t[f"l{l}.o.bias"] = _scaled(take, sd, D, D, b + "attention.o_proj", b + "layer_scale1.lambda1")
+        t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.down_proj", b + "layer_scale2.lambda1")
+    t["head.weight"], t["head.bias"] = _head(me, head, E, 2 * D if pool == POOL_CLS_AVG else D)
+    t["rope.cos"], t["rope.sin"] = rope_tables_dinov3(g, D // H, theta)
+    return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
 def blob_from_ijepa_state_dict(sd, cfg, ln_eps=1e-6, head=None):
@@ -717,8 +747,8 @@ def blob_from_ijepa_state_dict(sd, cfg, ln_eps=1e-6, head=None):
     head = (weight [classes, dim], bias [classes]), else zero.  `embeddings.mask_token` is ignored.  Refused: a `cls_token` in the
     state dict, a position table whose row count is not NP of cfg, a wrongly shaped head, a missing or wrongly shaped tensor (by name)."""
     me = "blob_from_ijepa_state_dict"
-    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
-    g = cfg["image_size"] // cfg["patch_size"]
+    D, E = cfg["dim"], cfg["classes"]
+    NP = (cfg["image_size"] // cfg["patch_size"]) ** 2
     if not any(k.startswith("ijepa.") for k in sd):
         sd = dict({"ijepa." + k: v for k, v in sd.items() if not k.startswith("classifier.")},
                   **{k: v for k, v in sd.items() if k.startswith("classifier.")})
@@ -727,34 +757,17 @@ def blob_from_ijepa_state_dict(sd, cfg, ln_eps=1e-6, head=None):
         raise ValueError(f"{me}: the checkpoint has a class token ({emb}cls_token); the blob of a FLAG_NO_CLS context has none")
     if emb + "position_embeddings" in sd:
         rows = int(np.asarray(sd[emb + "position_embeddings"]).shape[-2])
-        if rows != g * g:
-            raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP = {g * g} (no class-token row; "
+        if rows != NP:
+            raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP = {NP} (no class-token row; "
                              "interpolate the table to the image size first)")
-
-    take = _taker(sd, me)
-
-    parts = [take(emb + "patch_embeddings.projection.weight", (D, CH, P, P)), take(emb + "patch_embeddings.projection.bias", (D,)),
-             take(emb + "position_embeddings", (1, g * g, D))]
-    for l in range(cfg["layers"]):
-        b = f"ijepa.layers.{l}."
-        parts += [take(b + "layernorm_before.weight", (D,)), take(b + "layernorm_before.bias", (D,))]
-        for n in ("q_proj", "k_proj", "v_proj", "o_proj"):
-            parts += [take(f"{b}attention.{n}.weight", (D, D)), take(f"{b}attention.{n}.bias", (D,))]
-        parts += [take(b + "layernorm_after.weight", (D,)), take(b + "layernorm_after.bias", (D,)),
-                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,)),
-                  take(b + "mlp.fc2.weight", (D, M)), take(b + "mlp.fc2.bias", (D,))]
-    parts += [take("ijepa.layernorm.weight", (D,)), take("ijepa.layernorm.bias", (D,))]
+    flags = FLAG_NO_CLS | FLAG_POOL(POOL_AVG_NORM)
+    top = {"patch.weight": emb + "patch_embeddings.projection.weight", "patch.bias": emb + "patch_embeddings.projection.bias",
+           "pos": (emb + "position_embeddings", (1, NP, D)), "lnf.weight": "ijepa.layernorm.weight", "lnf.bias": "ijepa.layernorm.bias"}
+    t = _take_named(_taker(sd, me), cfg, flags, top, "ijepa.layers.{}.", _IJEPA_LAYER)
     if head is None and "classifier.weight" in sd and "classifier.bias" in sd:
         head = (sd["classifier.weight"], sd["classifier.bias"])
-    if head is None:
-        parts += [np.zeros(E * D, np.float32), np.zeros(E, np.float32)]
-    else:
-        hw, hb = (np.asarray(a) for a in head)
-        if hw.shape != (E, D) or hb.shape != (E,):
-            raise ValueError(f"{me}: head has shapes {hw.shape}, {hb.shape}, expected {(E, D)}, {(E,)}")
-        parts += [np.ascontiguousarray(hw, dtype=np.float32).reshape(-1), np.ascontiguousarray(hb, dtype=np.float32)]
-    h = _blob_header(cfg, ln_eps, FLAG_NO_CLS | FLAG_POOL(POOL_AVG_NORM))
-    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+    t["head.weight"], t["head.bias"] = _head(me, head, E, D)
+    return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
 def blob_from_timm_vit_state_dict(sd, cfg, ln_eps=1e-6, global_pool="token", fc_norm=None):
@@ -771,9 +784,8 @@ def blob_from_timm_vit_state_dict(sd, cfg, ln_eps=1e-6, global_pool="token", fc_
     Refused: a pooling other than 'token' / 'avg', 'token' without a class token, pos_embed rows other than those, a register
     count other than cfg['registers'], a missing or wrongly shaped tensor (by name)."""
     me = "blob_from_timm_vit_state_dict"
-    D, M, E, P, CH = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["patch_size"], cfg["channels"]
-    g = cfg["image_size"] // cfg["patch_size"]
-    NP, R = g * g, int(cfg.get("registers", 0))
+    D, M = cfg["dim"], cfg["mlp_dim"]
+    NP = (cfg["image_size"] // cfg["patch_size"]) ** 2
     if global_pool not in ("token", "avg"):
         raise ValueError(f"{me}: global_pool = {global_pool!r} is not 'token' or 'avg'")
     if fc_norm is None:
@@ -784,48 +796,28 @@ def blob_from_timm_vit_state_dict(sd, cfg, ln_eps=1e-6, global_pool="token", fc_
     if fc_norm and global_pool != "avg":
         raise ValueError(f"{me}: fc_norm goes with global_pool='avg'")
     pool = POOL_CLS if global_pool == "token" else POOL_AVG_FCNORM if fc_norm else POOL_AVG_NORM
-    have = int(np.asarray(sd["reg_token"]).shape[-2]) if "reg_token" in sd else 0
-    if have != R:
-        raise ValueError(f"{me}: the checkpoint has {have} register tokens, cfg['registers'] is {R}")
-
+    R = _register_count(me, cfg, sd, "reg_token")
+    flags = FLAG_REGISTERS(R) | (0 if has_cls else FLAG_NO_CLS) | FLAG_POOL(pool)
     take = _taker(sd, me)
-
     if "pos_embed" not in sd:
         raise KeyError(f"{me}: missing tensor pos_embed")
     rows = int(np.asarray(sd["pos_embed"]).shape[-2])
     if rows not in ((NP, NP + 1) if has_cls else (NP,)):
         raise ValueError(f"{me}: pos_embed has {rows} rows, cfg needs " + (f"NP = {NP} or NP + 1 = {NP + 1}" if has_cls else f"NP = {NP}"))
+    ln = "fc_norm" if fc_norm else "norm"
+    top = {"patch.weight": "patch_embed.proj.weight", "patch.bias": "patch_embed.proj.bias", "cls": ("cls_token", (1, 1, D)),
+           "reg": ("reg_token", (1, R, D)), "lnf.weight": ln + ".weight", "lnf.bias": ln + ".bias", "head.weight": "head.weight", "head.bias": "head.bias"}
+    t = _take_named(take, cfg, flags, top, "blocks.{}.", _TIMM_LAYER)
     pos = take("pos_embed", (1, rows, D))
-    if has_cls and rows == NP:   # no_embed_class: the class token carries no position
-        pos = np.concatenate([np.zeros(D, np.float32), pos])
-
-    def scaled(wname, bname, lname, n_in):
-        w, b = take(wname, (D, n_in), np.float64).reshape(D, n_in), take(bname, (D,), np.float64)
-        if lname in sd:
-            lam = take(lname, (D,), np.float64)
-            w, b = w * lam[:, None], b * lam
-        return [w.astype(np.float32).reshape(-1), b.astype(np.float32)]
-
-    parts = [take("patch_embed.proj.weight", (D, CH, P, P)), take("patch_embed.proj.bias", (D,))]
-    if has_cls:
-        parts.append(take("cls_token", (1, 1, D)))
-    parts.append(pos)
-    if R:
-        parts.append(take("reg_token", (1, R, D)))
+    t["pos"] = np.concatenate([np.zeros(D, np.float32), pos]) if has_cls and rows == NP else pos   # no_embed_class: the class token carries no position
     for l in range(cfg["layers"]):
         b = f"blocks.{l}."
-        parts += [take(b + "norm1.weight", (D,)), take(b + "norm1.bias", (D,))]
         qkv_w, qkv_b = take(b + "attn.qkv.weight", (3 * D, D)).reshape(3, D * D), take(b + "attn.qkv.bias", (3 * D,)).reshape(3, D)
-        for i in range(3):
-            parts += [np.ascontiguousarray(qkv_w[i]), np.ascontiguousarray(qkv_b[i])]
-        parts += scaled(b + "attn.proj.weight", b + "attn.proj.bias", b + "ls1.gamma", D)
-        parts += [take(b + "norm2.weight", (D,)), take(b + "norm2.bias", (D,)),
-                  take(b + "mlp.fc1.weight", (M, D)), take(b + "mlp.fc1.bias", (M,))]
-        parts += scaled(b + "mlp.fc2.weight", b + "mlp.fc2.bias", b + "ls2.gamma", M)
-    ln = "fc_norm" if fc_norm else "norm"
-    parts += [take(ln + ".weight", (D,)), take(ln + ".bias", (D,)), take("head.weight", (E, D)), take("head.bias", (E,))]
-    h = _blob_header(cfg, ln_eps, FLAG_REGISTERS(R) | (0 if has_cls else FLAG_NO_CLS) | FLAG_POOL(pool))
-    return np.concatenate([h] + [p.view(np.uint8) for p in parts])
+        for i, n in enumerate("qkv"):
+            t[f"l{l}.{n}.weight"], t[f"l{l}.{n}.bias"] = qkv_w[i], qkv_b[i]
+        t[f"l{l}.o.weight"], t[f"l{l}.o.bias"] = _scaled(take, sd, D, D, b + "attn.proj", b + "ls1.gamma", optional=True)
+        t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.fc2", b + "ls2.gamma", optional=True)
+    return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
 def device_free_bytes(device=0):
