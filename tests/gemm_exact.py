@@ -14,9 +14,19 @@ expected planes are unambiguous and hi + lo reproduces x exactly.  The only inex
 as tests/test_gpu_clip.py bounds them: half a unit in the last place plus max(the erf fit's documented error, a quarter unit)) and
 the split residual's sum of squares (bounded by the fp32 noise of its 64 additions of positive terms, 64 * 2^-24 relative).
 
+Activations: erf GELU, QuickGELU and tanh GELU (float64 references and tables keyed per activation).  The bound separates every pair
+with 16-bit results.  With e4m3 results it does NOT separate the erf from the tanh form on the designs' grid (act_separated: no grid
+point fails; QuickGELU fails at 30 against either): the e4m3 forms check the layout, the pre-activation and the rounding of those two
+codes, not which of the two functions ran.  test_gemm_exact.py asserts exactly this set of pairs.
+
+The patch forms take `lead` rows in front of an image's patch rows (Case(lead=...), Case.with_lead): GEMM row img * np + p lands on
+output row img * (np + lead) + lead + p and adds position row 1 + p whatever the lead; lead rows, and the partial sums of lead rows
+and padding rows, keep their canaries.  lead_rows_expected is the reference of the kernel that writes those lead rows afterwards.
+
 Buffers are kept in their LOGICAL form here -- out [R][N], out16 [R][N], partials [N / 64][R][2], R = M (the patch forms: token
 rows) -- and the layouts (tiled, head-major) are conversions of `out`.
 """
+import copy
 import math
 
 import numpy as np
@@ -27,15 +37,16 @@ BF16, FP16, FP8 = vithip.DTYPE_BF16, vithip.DTYPE_FP16, vithip.DTYPE_FP8
 NAME = {BF16: "bf16", FP16: "fp16", FP8: "e4m3"}
 E = {n[4:]: getattr(vithip, n) for n in dir(vithip) if n.startswith("EPI_")}   # "BIAS" -> vithip.EPI_BIAS, ...
 ENAME = {v: k for k, v in E.items()}
-ACT = (E["BIAS_GELU"], E["LNFOLD_GELU"], E["BIAS_QGELU"], E["LNFOLD_QGELU"])
+ACT = (E["BIAS_GELU"], E["LNFOLD_GELU"], E["BIAS_QGELU"], E["LNFOLD_QGELU"], E["BIAS_TGELU"], E["LNFOLD_TGELU"])
 QACT = (E["BIAS_QGELU"], E["LNFOLD_QGELU"])
-FOLD = (E["LNFOLD"], E["LNFOLD_GELU"], E["LNFOLD_QGELU"])
+TACT = (E["BIAS_TGELU"], E["LNFOLD_TGELU"])
+FOLD = (E["LNFOLD"], E["LNFOLD_GELU"], E["LNFOLD_QGELU"], E["LNFOLD_TGELU"])
 SPLIT = (E["RESID_SPLIT"], E["PATCH_SPLIT"])
 PATCHES = (E["PATCH"], E["PATCH_SPLIT"])
 NEED_N256 = (E["RESID_LN"], E["RESID_SPLIT"], E["PATCH_SPLIT"])
 EPI_16BIT_OPERANDS = sorted(E.values())
-EPI_E4M3_OPERANDS = [E[k] for k in ("BIAS", "BIAS_GELU", "BIAS_QGELU", "BIAS_RESID", "BIAS_F32", "LNFOLD", "LNFOLD_GELU", "LNFOLD_QGELU",
-                                    "RESID_LN", "RESID_SPLIT")]
+EPI_E4M3_OPERANDS = [E[k] for k in ("BIAS", "BIAS_GELU", "BIAS_QGELU", "BIAS_TGELU", "BIAS_RESID", "BIAS_F32", "LNFOLD", "LNFOLD_GELU",
+                                    "LNFOLD_QGELU", "LNFOLD_TGELU", "RESID_LN", "RESID_SPLIT")]
 # tests/test_gpu_clip.py (the activation sweeps): the erf fit's documented absolute error per result type, mantissa bits, smallest
 # normal exponent
 ERF_ABS = {FP16: 7.7e-6, BF16: 3.4e-5, FP8: 5.7e-4}
@@ -63,12 +74,18 @@ def patches_per_image(M):
 
 class Case:
     """Operands and epilogue inputs of one shape.  a [M][K], w [N][K] fp32 integers; ws [N] the weight scale (ones for 16-bit
-    operands); acc = ws * (a w^T), exact; contrib(j) = K-tile j's share of it."""
+    operands); acc = ws * (a w^T), exact; contrib(j) = K-tile j's share of it.
 
-    def __init__(self, M, N, K, f8, seed=0):
+    The patch forms: np_img patches per image (patches_per_image(M) unless given), `lead` rows in front of an image's patch rows
+    (class token + register tokens; 0 = none), so GEMM row img * np_img + p lands on output row img * (np_img + lead) + lead + p.
+    The position row it adds is 1 + p of a table of np_img + 1 rows WHATEVER the lead: that is what the launch is handed (a context
+    without a class token passes its [np_img][N] table one row early).  pad_rows: rows of `partials` beyond the last token row."""
+
+    def __init__(self, M, N, K, f8, seed=0, lead=1, np_img=None, pad_rows=0):
         kw = ktile(f8)
-        assert K % kw == 0
+        assert K % kw == 0 and lead >= 0 and pad_rows >= 0
         self.M, self.N, self.K, self.f8, self.nk = M, N, K, f8, K // kw
+        self.lead, self.pad_rows = lead, pad_rows
         r = np.random.default_rng([seed, M, N, K, int(f8)])
         a = np.zeros((M, K), dtype=np.float32)
         rows = np.arange(M)
@@ -91,12 +108,12 @@ class Case:
         self.acc = (a @ self.w.T) * self.ws[None, :]                 # fp32 sgemm of small integers: exact
         self._seed, self._x0 = seed, None
         try:
-            self.np_img = patches_per_image(M)
+            self.np_img = np_img or patches_per_image(M)
         except ValueError:
             self.np_img = 0
         if self.np_img:
-            T = self.np_img + 1
-            self.pos = r.integers(-50, 51, size=(T, N)).astype(np.float32)
+            assert M % self.np_img == 0
+            self.pos = r.integers(-50, 51, size=(self.np_img + 1, N)).astype(np.float32)
         for arr in (self.a, self.w, self.acc):
             arr.setflags(write=False)
 
@@ -132,12 +149,30 @@ class Case:
         return vithip.to16(self.a, dt), vithip.to16(self.w, dt)
 
     # ---- the patch forms' row map --------------------------------------------------------------------------------------
+    def with_lead(self, lead, pad_rows=0):
+        """The same operands (shared, not copied) with another count of lead rows."""
+        c = copy.copy(self)
+        c.lead, c.pad_rows = lead, pad_rows
+        return c
+
+    @property
+    def tokens(self):
+        return self.np_img + self.lead
+
     def out_rows(self, epi):
-        return self.M // self.np_img * (self.np_img + 1) if epi in PATCHES else self.M
+        return self.M // self.np_img * self.tokens if epi in PATCHES else self.M
+
+    def partial_rows(self, epi):
+        """Row stride of `partials` (PATCH_SPLIT: the launch's prow)."""
+        return self.out_rows(epi) + (self.pad_rows if epi == E["PATCH_SPLIT"] else 0)
 
     def row_map(self, epi):
         m = np.arange(self.M)
-        return m + m // self.np_img + 1 if epi in PATCHES else m
+        return m + (m // self.np_img + 1) * self.lead if epi in PATCHES else m
+
+    def pos_rows(self):
+        """The position row of every GEMM row: 1 + p, not the output row's index inside its image (the two agree at lead 1 only)."""
+        return 1 + np.arange(self.M) % self.np_img
 
     def tile_mask(self, tiles):
         """[M][N] bool: the elements of the launched tiles (None = all), tile t = (t / tiles_n, t % tiles_n)."""
@@ -230,7 +265,7 @@ def initial(case, epi, dt):
     if k16 is not None and "out16" not in b:
         b["out16"] = np.full((R, N), canary(k16), dtype=np_dtype(k16))
     if epi in NEED_N256:
-        b["partials"] = np.full((N // 64, R, 2), CANARY_P, dtype=np.float32)
+        b["partials"] = np.full((N // 64, case.partial_rows(epi), 2), CANARY_P, dtype=np.float32)
     return b
 
 
@@ -246,8 +281,7 @@ def pre_value(case, epi, dt, before, ft=np.float64):
     elif epi == E["RESID_SPLIT"]:
         v += join_planes(before["out"], before["out16"], dt, case.f8).astype(ft)
     elif epi in PATCHES:
-        p = np.arange(case.M) % case.np_img
-        v += case.pos.astype(ft)[1 + p]
+        v += case.pos.astype(ft)[case.pos_rows()]
         if epi == E["PATCH_SPLIT"]:
             v += ft(LO_FRAC[dt])          # (the fraction that keeps lo busy rides on the position embedding)
     return v
@@ -281,9 +315,22 @@ def qgelu64(v):
         return v / (1.0 + np.exp(-1.702 * v))
 
 
-def act64(v, epi):
+def tgelu64(v):
+    """0.5 v (1 + tanh(sqrt(2 / pi) (v + 0.044715 v^3))) in float64 (gelu_pytorch_tanh; vithip.h VH_EPI_BIAS_TGELU)."""
     v = np.asarray(v, dtype=np.float64)
-    return qgelu64(v) if epi in QACT else gelu64(v)
+    return 0.5 * v * (1.0 + np.tanh(math.sqrt(2.0 / math.pi) * (v + 0.044715 * v * v * v)))
+
+
+ACT64 = {"gelu": gelu64, "qgelu": qgelu64, "tgelu": tgelu64}      # keyed per activation, as the tables of act_on_grid are
+
+
+def act_of(epi):
+    return "qgelu" if epi in QACT else ("tgelu" if epi in TACT else "gelu")
+
+
+def act64(v, epi, act=None):
+    """The activation of epilogue `epi` (or the named one: the wrong_activation mutants) in float64."""
+    return ACT64[act or act_of(epi)](np.asarray(v, dtype=np.float64))
 
 
 def act_tolerance(ref, kind):
@@ -295,22 +342,33 @@ def act_tolerance(ref, kind):
 _ACT_TABLES = {}
 
 
-def act_on_grid(pre, epi, kind, want=(0, 1, 2)):
+def act_on_grid(pre, epi, kind, want=(0, 1, 2), act=None):
     """(float64 activation, tolerance, stored bits of the rounded activation) of exact pre-activations, [M][N] each.  The designs'
     pre-activations are multiples of 1/8 below 1024: a table over that grid then serves the 4e7 elements of the many-tile shape;
     anything else is computed directly (same formulas)."""
     pre = np.asarray(pre)
     k = pre * pre.dtype.type(_ERF_GRID)
     if pre.size and np.abs(pre).max() <= 1024 and np.array_equal(k, np.rint(k)):
-        key = (epi in QACT, kind)
+        key = (act or act_of(epi), kind)
         if key not in _ACT_TABLES:
             x = np.arange(-1024 * _ERF_GRID, 1024 * _ERF_GRID + 1) / _ERF_GRID
-            ref = act64(x, epi)
+            ref = act64(x, epi, act)
             _ACT_TABLES[key] = (ref, act_tolerance(ref, kind), encode(ref.astype(np.float32), kind))
         idx = k.astype(np.int32) + 1024 * _ERF_GRID
         return tuple(t[idx] if i in want else None for i, t in enumerate(_ACT_TABLES[key]))
-    ref = act64(pre, epi)
+    ref = act64(pre, epi, act)
     return ref, act_tolerance(ref, kind), encode(ref.astype(np.float32), kind)
+
+
+def act_separated(act, other, kind, step=1.0 / _ERF_GRID, below=448.0):
+    """The grid points (multiples of `step`, |v| < below: no e4m3 result saturates) at which `other`, rounded to `kind`, misses the
+    bound that assert_activation puts around `act`.  Empty: the suite cannot tell the two functions apart in that result type on
+    that grid (e4m3 results: erf and tanh GELU, whose difference stays below the type's rounding step there)."""
+    n = int(math.ceil(below / step)) - 1
+    x = np.arange(-n, n + 1) * step
+    ref = ACT64[act](x)
+    got = decode(encode(ACT64[other](x).astype(np.float32), kind), kind).astype(np.float64)
+    return x[np.abs(got - ref) > act_tolerance(ref, kind)]
 
 
 def expected(case, epi, dt, before, tiles=None, ft=np.float64):
@@ -394,12 +452,28 @@ def from_layout(buf, layout, kind, M, N):
 
 
 # ---- numpy emulation of the kernel: fp32 arithmetic, K-tile by K-tile, stores by the kernels' address formulas -----------------
+ACT_MUTANTS = tuple("wrong_activation:" + a for a in ACT64)      # the emulation applies the named function whatever the epilogue's is
+LEAD_MUTANTS = ("lead_off_by_one", "pos_by_output_row", "lead_row_written", "image_stride_np_plus_1")
 MUTANTS = ("ktile_dropped", "ktile_twice", "neighbour_stats", "c_d_swapped", "swizzle_kept", "block_off_by_one", "hm_stride",
-           "resid_twice", "resid_skipped")
+           "resid_twice", "resid_skipped") + ACT_MUTANTS + LEAD_MUTANTS
 
 
-def mutant_applies(mutant, epi, layout):
-    """Does the mutant change what this (epilogue, layout) computes?  Where it cannot, the emulation must return the same bits."""
+def mutant_applies(mutant, epi, layout, case=None, dt=None):
+    """Does the mutant change what this (epilogue, layout) computes?  Where it cannot, the emulation must return the same bits.
+    `case` and `dt` (the lead count, the result type) matter to the activation and lead-row mutants only."""
+    if mutant in ACT_MUTANTS:
+        # another function than the epilogue's own; with e4m3 results, only where the grid of the designs separates the two at all
+        # (act_separated: erf and tanh GELU are NOT -- the suite's blind spot, stated by test_designs_hold_what_they_promise)
+        other = mutant.split(":")[1]
+        if epi not in ACT or other == act_of(epi):
+            return False
+        kind = out_kind(epi, dt, case.f8)[0]
+        return kind != FP8 or bool(len(act_separated(act_of(epi), other, FP8)))
+    if mutant in LEAD_MUTANTS:
+        if epi not in PATCHES:
+            return False
+        # at lead 1 "pos row of the output row" IS pos row 1 + p and the image stride IS np + 1: why lead 1 alone was blind to both
+        return case.lead != 1 if mutant in ("pos_by_output_row", "image_stride_np_plus_1") else True
     if mutant in ("neighbour_stats", "c_d_swapped"):
         return epi in FOLD
     if mutant == "swizzle_kept":
@@ -446,6 +520,22 @@ def emulate(case, epi, dt, before, tiles=None, layout="row", mutant=None):
     if mutant == "resid_skipped":
         mask = mask & ~victim
     rows = case.row_map(epi)
+    pos_rows = case.pos_rows() if epi in PATCHES else None
+    keep = slice(None)                                             # the GEMM rows whose output row lies inside the buffer: all of them
+    if epi in PATCHES:
+        img, p = np.arange(M) // case.np_img, np.arange(M) % case.np_img
+        if mutant == "lead_off_by_one":
+            rows = rows - 1
+        elif mutant == "image_stride_np_plus_1":
+            rows = img * (case.np_img + 1) + case.lead + p
+        elif mutant == "pos_by_output_row":
+            pos_rows = (case.lead + p) % (case.np_img + 1)        # (folded into the table: a row beyond it is no row at all)
+        inside = (rows >= 0) & (rows < case.out_rows(epi))         # a mutant's store outside the buffer is dropped (the guard slabs' business)
+        if not inside.all():
+            keep = np.flatnonzero(inside)
+            mask = mask & inside[:, None]
+            rows = np.clip(rows, 0, case.out_rows(epi) - 1)
+    wrong_act = mutant.split(":")[1] if mutant in ACT_MUTANTS else None
     state = {k: a.copy() for k, a in before.items()}
     res = {}
 
@@ -459,7 +549,7 @@ def emulate(case, epi, dt, before, tiles=None, layout="row", mutant=None):
         elif epi == E["RESID_SPLIT"]:
             v = v + join_planes(cur["out"], cur["out16"], dt, case.f8).astype(f32)
         elif epi in PATCHES:
-            v = v + pos_table(case, epi, dt)[1 + np.arange(M) % case.np_img]
+            v = v + pos_table(case, epi, dt)[pos_rows]
         return v.astype(f32)
 
     def apply(msk):
@@ -475,7 +565,7 @@ def emulate(case, epi, dt, before, tiles=None, layout="row", mutant=None):
             else:
                 vs[:, :nf] = _unswizzle_missing(v[:, :nf], 2)       # 16-bit staging: 8 chunks of 8 values, chunk ^ (r & 7)
         if epi in ACT:
-            o = act_on_grid(vs, epi, ko, want=(2,))[2]
+            o = act_on_grid(vs, epi, ko, want=(2,), act=wrong_act)[2]
             o16 = None
         elif epi in SPLIT:
             o, o16 = split_planes(vs, dt, case.f8)
@@ -485,20 +575,29 @@ def emulate(case, epi, dt, before, tiles=None, layout="row", mutant=None):
         for name, vals in (("out", o), ("out16", o16)):
             if vals is None:
                 continue
-            cur = state[name][rows]
-            cur[msk] = vals[msk]
-            state[name][rows] = cur
+            cur = state[name][rows[keep]]
+            cur[msk[keep]] = vals[keep][msk[keep]]
+            state[name][rows[keep]] = cur
         if "partials" in state:
             g = vs.reshape(M, N // 64, 64)
             s = np.stack([g.sum(2, dtype=f32), (g * g).sum(2, dtype=f32)], axis=2).transpose(1, 0, 2)
             bm = msk[:, ::64].T
-            cur = state["partials"][:, rows]
-            cur[bm] = s[bm]
-            state["partials"][:, rows] = cur
+            cur = state["partials"][:, rows[keep]]
+            cur[bm[:, keep]] = s[:, keep][bm[:, keep]]
+            state["partials"][:, rows[keep]] = cur
 
     apply(mask)
     if mutant == "resid_twice":
         apply(victim & mask)
+    if mutant == "lead_row_written" and epi in PATCHES:
+        # an image's first patch row is stored once more on the row in front of it: its last lead row (at lead 0, where there is
+        # none, the previous image's last patch row)
+        first = np.flatnonzero((p == 0) & (rows > 0))
+        for name in ("out", "out16"):
+            if name in state:
+                cur = state[name][rows[first] - 1]
+                cur[mask[first]] = state[name][rows[first]][mask[first]]
+                state[name][rows[first] - 1] = cur
     # ---- the store of `out` in its layout, by the kernels' address arithmetic (gemm_epilogue.h) ----
     out = state["out"]
     if layout == "row":
@@ -613,4 +712,55 @@ def check(case, epi, dt, before, got, tiles=None, what=""):
     if k16 is not None:
         assert_bits(got["out16"], exp["out16"], what + " out16")
     if "partials" in exp:
+        assert_partials(got["partials"], exp["partials"], exp["sumsq64"], exp["sumsq_exact"], what + " partials")
+
+
+# ---- the other half of the assembly: vh_op_lead_rows on the buffers a PATCH / PATCH_SPLIT launch left -------------------------------
+def lead_rows_inputs(dim, lead, no_cls, dt, split, seed=0):
+    """cls [dim], pos0 [dim] (position row 0), reg [lead - 1][dim] (no_cls: cls and pos0 None, reg [lead][dim]; None without a
+    register row): integers, cls and reg carrying the split form's fraction LO_FRAC[dt] so that the lo plane is busy.  Every row
+    x = cls + pos0 or reg[r] is exact in fp32 and in the pair of planes, |x| < 256."""
+    r = np.random.default_rng([seed, dim, lead, int(no_cls), 91])
+    frac = np.float32(LO_FRAC[dt] if split else 0.0)
+    regs = lead - (0 if no_cls else 1)
+    return {"cls": None if no_cls else r.integers(-120, 121, size=dim).astype(np.float32) + frac,
+            "pos0": None if no_cls else r.integers(-100, 101, size=dim).astype(np.float32),
+            "reg": r.integers(-200, 201, size=(regs, dim)).astype(np.float32) + frac if regs else None}
+
+
+def lead_rows_values(inp, ft=np.float32):
+    """x [lead][dim]: row 0 = cls + pos[0], row 1 + r = reg[r]; without a class token row r = reg[r]."""
+    rows = [] if inp["cls"] is None else [(inp["cls"].astype(ft) + inp["pos0"].astype(ft))[None, :]]
+    if inp["reg"] is not None:
+        rows.append(inp["reg"].astype(ft))
+    return np.concatenate(rows, axis=0)
+
+
+def lead_rows_expected(before, inp, batch, tokens, dt, split, ft=np.float64):
+    """The buffers {'out' [batch * tokens][dim], and in the split form 'out16', 'partials' [dim / 64][prow][2]} after the lead-row
+    kernel ran on `before`: the lead rows of every image written, every other element as it was.  Split form: also 'sumsq64' and
+    'sumsq_exact', as expected() gives them."""
+    x = lead_rows_values(inp, ft)
+    lead, dim = x.shape
+    res = {k: a.copy() for k, a in before.items()}
+    at = (np.arange(batch)[:, None] * tokens + np.arange(lead)[None, :]).reshape(-1)       # image-major, as x tiles
+    x32 = np.tile(x.astype(np.float32), (batch, 1))
+    if not split:
+        res["out"][at] = x32
+        return res
+    res["out"][at], res["out16"][at] = split_planes(x32, dt, False)
+    g = np.tile(x.astype(np.float64), (batch, 1)).reshape(batch * lead, dim // 64, 64)
+    s = np.stack([g.sum(2), (g * g).sum(2)], axis=2).transpose(1, 0, 2)                    # [dim / 64][batch * lead][2]
+    res["partials"][:, at] = s.astype(np.float32)
+    res["sumsq64"] = np.full(res["partials"].shape[:2], np.nan)
+    res["sumsq64"][:, at] = s[:, :, 1]
+    res["sumsq_exact"] = bool(s[:, :, 1].max() / LO_FRAC[dt] ** 2 < 2.0 ** 24)
+    return res
+
+
+def check_lead_rows(before, got, inp, batch, tokens, dt, split, what=""):
+    exp = lead_rows_expected(before, inp, batch, tokens, dt, split)
+    assert_bits(got["out"], exp["out"], what + " out")
+    if split:
+        assert_bits(got["out16"], exp["out16"], what + " out16")
         assert_partials(got["partials"], exp["partials"], exp["sumsq64"], exp["sumsq_exact"], what + " partials")

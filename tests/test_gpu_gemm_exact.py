@@ -6,8 +6,20 @@ range: the forms the forward runs by default were reached through whole forwards
 integers, so every epilogue but the activations is compared BIT FOR BIT, per element, in every layout (taps vh_op_gemm_layout,
 vh_op_gemm_fp8_layout, vh_op_tile_rows), and a failure names tile, 16-row block, 8-column chunk, row and column.
 test_gemm_exact.py proves on the CPU that these assertions fail for a dropped or repeated K-tile, a neighbouring row's statistics,
-swapped c / d, a kept staging swizzle, an off-by-one row block, a wrong head-major stride and a residual tile applied twice or not
-at all.
+swapped c / d, a kept staging swizzle, an off-by-one row block, a wrong head-major stride, a residual tile applied twice or not
+at all, another activation than the epilogue's, and the four ways a lead-row remap goes wrong.
+
+The three activations (erf, QuickGELU and tanh GELU; codes EPI_*_GELU / _QGELU / _TGELU) run through every form: row-major at every
+variant, the tiled hidden activation with 16-bit and e4m3 results, a tile range.  Their bound is the activation sweeps' (gemm_exact
+.act_tolerance).  What that bound cannot see: with e4m3 RESULTS the erf and the tanh GELU round alike at every pre-activation of
+the designs, so a kernel that ran one for the other would pass the e4m3 forms (test_gemm_exact.py asserts that this is so, and that
+every other pair, and every pair with 16-bit results, separates); the 16-bit forms of the same code paths catch it.
+
+The patch-embedding epilogues run through vh_op_gemm_lead with 0, 1, 5 and 17 rows in front of an image's patch rows -- registers,
+no-class-token models, SigLIP, DINOv3 -- with several column tiles, image boundaries inside every 128-row wave tile, a ragged last
+row tile, every variant: the patch rows, the untouched lead rows and the partial sums (a padded row stride) bit for bit.  At lead 1
+"pos row 1 + p" and "pos row of the output row" are one row; only the other leads tell them apart.  vh_op_lead_rows then completes
+the assembly on the same buffers and is compared with cls + pos[0] and reg[r] themselves, not with another run of the kernel.
 
 Every buffer a launch may write is exactly sized, pre-filled (canaries, or the residual it updates) and has a guard slab of 0xA5
 bytes in front of and behind it that must survive.
@@ -44,8 +56,9 @@ def case_of(M, N, K, f8):
 class Launch:
     """The device side of one (case, epilogue, type): operands, epilogue inputs and guarded output buffers holding `before`."""
 
-    def __init__(self, case, epi, dt, before, layout="row", ab_tiled=False, w_tiled_ptr=None):
-        self.case, self.epi, self.dt, self.layout, self.ab_tiled = case, epi, dt, layout, ab_tiled
+    def __init__(self, case, epi, dt, before, layout="row", ab_tiled=False, w_tiled_ptr=None, lead_tap=False):
+        self.case, self.epi, self.dt, self.layout, self.ab_tiled, self.lead_tap = case, epi, dt, layout, ab_tiled, lead_tap
+        assert lead_tap or (case.lead == 1 and not case.pad_rows), "every other tap keeps lead = 1 and prow = the token rows"
         self.ko, self.k16 = X.out_kind(epi, dt, case.f8)
         a, w = case.operand_bits(dt)
         chunk = 16 if case.f8 else 8
@@ -71,7 +84,11 @@ class Launch:
         tb, tc = (tiles[0], len(tiles)) if tiles is not None else (0, 0)
         extras = dict(out_tiled=self.layout != "row", ab_tiled=self.ab_tiled, tile_begin=tb, tile_count=tc)
         plain = not (extras["out_tiled"] or self.ab_tiled or tc)      # then the taps the layout taps extend
-        if c.f8:
+        if self.lead_tap:      # the patch forms with case.lead rows in front of an image's patch rows; prow as the case pads it
+            vithip.op_gemm_lead(self.a.ptr, self.w_ptr, self.bias.ptr, self.ptr("out"), c.M, c.N, c.K, epi, self.dt, self.pos.ptr if self.pos else None,
+                                c.np_img, c.lead, out16_ptr=self.ptr("out16"), partials_ptr=self.ptr("partials"),
+                                prow=c.partial_rows(epi) if c.pad_rows else 0, variant=variant)
+        elif c.f8:
             args = (self.a.ptr, self.w_ptr, self.ws.ptr, self.bias.ptr, self.ptr("out"), c.M, c.N, c.K, epi)
             kw = dict(c_ptr=self.c.ptr if self.c else None, stats_ptr=self.stats.ptr if self.stats else None, out16_ptr=self.ptr("out16"),
                       partials_ptr=self.ptr("partials"), variant=variant)
@@ -105,13 +122,17 @@ class Launch:
         return res
 
 
-def run_and_check(case, epi, dt, variant, layout="row", ab_tiled=False, w_tiled_ptr=None, tiles=None, stored=False):
+def run_and_check(case, epi, dt, variant, layout="row", ab_tiled=False, w_tiled_ptr=None, tiles=None, stored=False, lead_tap=False, keep=None):
     before = X.initial(case, epi, dt)
-    L = Launch(case, epi, dt, before, layout, ab_tiled, w_tiled_ptr)
+    L = Launch(case, epi, dt, before, layout, ab_tiled, w_tiled_ptr, lead_tap)
     L.launch(variant, tiles)
     what = f"variant {variant} {layout}{' ab_tiled' if ab_tiled else ''}{'' if tiles is None else f' tiles {tiles[0]}..{tiles[-1]}'}"
+    if lead_tap:
+        what += f" lead {case.lead}, {case.np_img} patches per image"
     got = L.read(what, stored)
     X.check(case, epi, dt, before, got, tiles, what)
+    if keep is not None:
+        keep.append(L)         # the device side, for a caller that goes on with the buffers
     return before, got
 
 
@@ -195,7 +216,8 @@ def test_tiled_operands(name, epi, dt):
     same_bits(host, devw, "W tiled on the device vs on the host")
 
 
-@pytest.mark.parametrize("form", ["tiled_LNFOLD_GELU", "tiled_BIAS_GELU", "tiled_LNFOLD_QGELU", "tiled_BIAS_QGELU", "hm_LNFOLD", "ab_RESID_SPLIT"])
+@pytest.mark.parametrize("form", ["tiled_LNFOLD_GELU", "tiled_BIAS_GELU", "tiled_LNFOLD_QGELU", "tiled_BIAS_QGELU", "tiled_LNFOLD_TGELU", "tiled_BIAS_TGELU",
+                                  "hm_LNFOLD", "ab_RESID_SPLIT"])
 @pytest.mark.parametrize("name", LAYOUT_SHAPES)
 def test_e4m3_operand_layouts(name, form):
     kind, ename = form.split("_", 1)
@@ -260,6 +282,17 @@ def test_tile_rows(dt):
 @pytest.mark.parametrize("epi", [E["BIAS"], E["RESID_LN"], E["RESID_SPLIT"]], ids=lambda e: X.ENAME[e])
 @pytest.mark.parametrize("ops", ["bf16", "fp16", "e4m3"])
 def test_tile_ranges(ops, epi, variant):
+    tile_ranges(ops, epi, variant)
+
+
+@pytest.mark.parametrize("variant", [5, 7])
+@pytest.mark.parametrize("ops", ["bf16", "fp16"])
+def test_tile_ranges_tanh_gelu(ops, variant):
+    # an activation epilogue in a tile range: the tiles outside it keep their canaries, the two ranges give the one launch's bits
+    tile_ranges(ops, E["BIAS_TGELU"], variant)
+
+
+def tile_ranges(ops, epi, variant):
     f8 = ops == "e4m3"
     dt = FP16 if ops == "fp16" else BF16
     M, N, K = X.shape("S1r", f8, epi, four_tile_columns=True)
@@ -281,7 +314,87 @@ def test_tile_ranges(ops, epi, variant):
     run_and_check(case, epi, dt, variant, tiles=range(8, 12))                                  # the ragged last tile row alone
 
 
-# ---- 5. refusals -------------------------------------------------------------------------------------------------------------
+# ---- 5. the patch forms with lead rows (vh_op_gemm_lead) and the lead-row kernels (vh_op_lead_rows) --------------------------------
+LEAD_VARIANTS = (0, 1, 2, 5, 6, 7)                 # what gemm_check accepts for EPI_PATCH / EPI_PATCH_SPLIT: everything but ...
+LEAD_REFUSED = {3: "variants 3/4 (BK=32 pipeline) were removed", 4: "variants 3/4 (BK=32 pipeline) were removed", 8: "gemm: variant", -1: "gemm: variant"}
+
+
+LEAD_FORMS = {"lead1": (False, 1), "lead5": (False, 5), "lead16": (False, 16), "no_cls4": (True, 4)}      # (no class token, lead rows)
+
+
+def refused(call, text):
+    with pytest.raises(vithip.VhError) as e:
+        call()
+    assert e.value.code == 1 and text in str(e.value), (text, str(e.value))
+
+
+@pytest.mark.parametrize("dt", DT, ids=lambda d: X.NAME[d])
+@pytest.mark.parametrize("lead", [0, 1, 5, 17])
+@pytest.mark.parametrize("epi", X.PATCHES, ids=lambda e: X.ENAME[e])
+@pytest.mark.parametrize("name", ["S1", "S1r"])
+def test_patch_epilogues_with_lead_rows(name, epi, lead, dt):
+    # bit for bit per element: the patch rows on output row img * (np + lead) + lead + p with pos row 1 + p; the lead rows of out and
+    # out16, the partial sums of the lead rows and of the 5 padding rows of `partials` keep their canaries; the guard slabs survive
+    M, N, K = X.shape(name, False, epi)
+    keep = []
+    for variant in LEAD_VARIANTS:
+        n = 768 if variant == 6 and N % 256 else N      # (test_row_major_16bit_operands' rule)
+        case = case_of(M, n, K, False).with_lead(lead, pad_rows=5)
+        assert case.np_img < 128 and case.out_rows(epi) == M // case.np_img * (case.np_img + lead)
+        before, got = run_and_check(case, epi, dt, variant, lead_tap=True, keep=keep)
+    L = keep[-1]
+    for variant, text in LEAD_REFUSED.items():
+        refused(lambda: L.launch(variant), text)
+
+    def tap(epi=epi, patches=case.np_img, lead=lead, prow=0):      # the last launch's own operands and buffers, one argument changed
+        return lambda: vithip.op_gemm_lead(L.a.ptr, L.w_ptr, L.bias.ptr, L.ptr("out"), M, n, K, epi, dt, L.pos.ptr, patches, lead,
+                                           out16_ptr=L.ptr("out16"), partials_ptr=L.ptr("partials"), prow=prow, variant=5)
+
+    refused(tap(lead=-1), "gemm: EPI_PATCH* lead rows outside 0..17")
+    refused(tap(lead=18), "gemm: EPI_PATCH* lead rows outside 0..17")
+    refused(tap(epi=E["BIAS_F32"]), "gemm_lead: epilogue must be VH_EPI_PATCH or VH_EPI_PATCH_SPLIT")
+    refused(tap(patches=case.np_img - 1), "gemm_lead: M must be a whole number of images")
+    if epi == E["PATCH_SPLIT"]:
+        refused(tap(prow=case.out_rows(epi) - 1), "gemm_lead: prow is below images x (aux_i + lead)")
+    same_bits(L.read("after the refused calls"), got, "a refused call wrote to its output:")
+
+
+@pytest.mark.parametrize("dim", [256, 768])
+@pytest.mark.parametrize("batch", [3, 20])
+@pytest.mark.parametrize("form", list(LEAD_FORMS))
+def test_lead_rows_kernel_exact(form, batch, dim):
+    # the whole assembly once: the patch GEMM through vh_op_gemm_lead (16 patches per image), then vh_op_lead_rows on the buffers it
+    # left.  fp32 form (EPI_PATCH): row 0 = cls + pos[0], row 1 + r = reg[r] bit for bit, every patch row untouched.  Split form
+    # (EPI_PATCH_SPLIT): planes by split_planes, sums exact, sums of squares within SQ_REL, no patch row's plane or partial sum and
+    # nothing beyond batch * tokens rows of `partials` touched.  no_cls4: cls and pos NULL, the 4 lead rows are all registers
+    no_cls, lead = LEAD_FORMS[form]
+    case = X.Case(batch * 16, dim, 128, False, lead=lead, np_img=16, pad_rows=3)
+    T = case.tokens
+    for dt in DT:
+        for epi in X.PATCHES:
+            split = epi == E["PATCH_SPLIT"]
+            keep = []
+            _, mid = run_and_check(case, epi, dt, 0, lead_tap=True, keep=keep)
+            L = keep[0]
+            inp = X.lead_rows_inputs(dim, lead, no_cls, dt, split)
+            ptr = {k: (dev(v).ptr if v is not None else None) for k, v in inp.items()}
+            extra = dict(lo_ptr=L.ptr("out16"), partials_ptr=L.ptr("partials"), prow=case.partial_rows(epi), dtype=dt) if split else {}
+            what = f"lead_rows {form} batch {batch} dim {dim} {X.NAME[dt]} {'split' if split else 'fp32'}"
+            vithip.op_lead_rows(L.ptr("out"), ptr["cls"], ptr["pos0"], ptr["reg"], lead, batch, T, dim, **extra)
+            got = L.read(what)
+            X.check_lead_rows(mid, got, inp, batch, T, dt, split, what)
+            # the tap's refusals, with the outputs untouched afterwards
+            text = "lead_rows: bad argument"
+            refused(lambda: vithip.op_lead_rows(L.ptr("out"), ptr["cls"], ptr["pos0"], ptr["reg"], lead, batch, T, dim - 32, **extra), text)     # dim % 64
+            refused(lambda: vithip.op_lead_rows(L.ptr("out"), ptr["cls"], ptr["pos0"], ptr["reg"], lead, batch, lead, dim, **extra), text)       # lead >= tokens
+            if split:
+                small = dict(extra, prow=batch * T - 1)
+                refused(lambda: vithip.op_lead_rows(L.ptr("out"), ptr["cls"], ptr["pos0"], ptr["reg"], lead, batch, T, dim, **small),
+                        "lead_rows: the split form needs partials, a 16-bit dtype and prow >= batch x tokens")
+            same_bits(L.read(what + " after the refused calls"), got, what + ": a refused call wrote to its output:")
+
+
+# ---- 6. refusals -------------------------------------------------------------------------------------------------------------
 def test_layout_taps_refuse_what_the_launchers_refuse():
     # (one text since gemm_check states both: the taps print its reason, launch_gemm asks it first, so every caller is refused alike)
     size = 1 << 20
@@ -320,6 +433,15 @@ def test_layout_taps_refuse_what_the_launchers_refuse():
         g8(256, 256, 128, E["RESID_SPLIT"], 6, ab=1), g8(256, 256, 512, E["RESID_LN"], 6, ab=1),
         g8(256, 256, 512, E["LNFOLD"], 6, ab=1), g8(256, 256, 512, E["RESID_SPLIT"], 6, ot=1),
         g8(512, 256, 512, E["LNFOLD_GELU"], 6, ot=1, ab=1), g8(300, 256, 512, E["LNFOLD_GELU"], 6, ot=1),
+        # the tanh-GELU codes, wherever an activation code stands above for a tiled flag
+        g16(256, 256, 256, E["LNFOLD_TGELU"], 5, ot=1), g16(256, 256, 256, E["LNFOLD_TGELU"], 0, ot=1), g16(256, 256, 256, E["BIAS_TGELU"], 7, ot=1),
+        g16(264, 256, 256, E["BIAS_TGELU"], 6, ot=1), g16(256, 260, 256, E["BIAS_TGELU"], 6, ot=1),
+        g16(256, 256, 64, E["BIAS_TGELU"], 6, ot=1), g16(256, 256, 192, E["LNFOLD_TGELU"], 6, ot=1),
+        g16(256, 256, 256, E["BIAS_TGELU"], 6, ab=1), g16(256, 256, 256, E["LNFOLD_TGELU"], 6, ab=1), g16(256, 256, 256, E["BIAS_TGELU"], 6, ot=1, ab=1),
+        g16(256, 256, 256, E["BIAS_TGELU"], 6, ot=1, tc=1),
+        g8(256, 256, 512, E["LNFOLD_TGELU"], 5, ot=1), g8(256, 256, 512, E["LNFOLD_TGELU"], 0, ot=1), g8(256, 256, 128, E["BIAS_TGELU"], 6, ot=1),
+        g8(256, 256, 128, E["LNFOLD_TGELU"], 6, ot=1), g8(256, 256, 512, E["BIAS_TGELU"], 6, ab=1),
+        g8(512, 256, 512, E["LNFOLD_TGELU"], 6, ot=1, ab=1), g8(300, 256, 512, E["LNFOLD_TGELU"], 6, ot=1),
         g8(600, 1024, 256, E["BIAS"], 6, tc=5), g8(600, 1024, 256, E["BIAS"], 0, tc=5), g8(600, 1024, 256, E["BIAS"], 5, tb=8, tc=5),
         g8(600, 1024, 256, E["BIAS"], 7, tb=2, tc=0), g8(600, 1024, 256, E["BIAS"], 5, tb=-1, tc=2),
         g8(256, 256, 192, E["BIAS"], 5), g8(256, 256, 256, E["PATCH"], 5), g8(256, 256, 256, E["BIAS"], 2),

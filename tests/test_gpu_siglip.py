@@ -3,7 +3,9 @@ and e4m3 results, direct and LN-fold codes) and the activation itself on test_gp
 QuickGELU form in gemm_epilogue.h; the one-pass kernel of the attention-pooling head through vh_op_map_pool against float64 with
 canaries around every output; whole forwards against the three Hugging Face fixtures; the head's stages; bit invariance across batch,
 streams, graph replay and the u8 ring; forged blobs; token features.  Tolerances: the project's model bounds (fp16 1e-3, bf16 1e-2,
-fp8 `1.5 x emulation + 1e-3`), one 16-bit ulp for operators, and for the kernel MAP_BOUND, which tests/test_siglip.py measures."""
+fp8 `1.5 x emulation + 1e-3`), one 16-bit ulp for operators, and for the kernel MAP_BOUND, which tests/test_siglip.py measures.
+The taps here store row-major on random data; the LAYOUTS of the two tanh codes -- the tiled hidden activation with 16-bit and e4m3
+results, a tile range, canaries per element -- are held by the exact suite (tests/test_gpu_gemm_exact.py) on exact pre-activations."""
 import glob
 import os
 

@@ -57,9 +57,11 @@ FLAG_ROPE = 1 << 23
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
 EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
-# tanh GELU (12 is no code).  Not named EPI_*: tests/gemm_exact.py enumerates every EPI_* name of this module for an emulator that knows the
-# erf and QuickGELU activations only; tests/test_gpu_siglip.py covers these two codes
-EPILOGUE_BIAS_TGELU, EPILOGUE_LNFOLD_TGELU = 13, 14
+# tanh GELU (12 is no code).  tests/gemm_exact.py enumerates every EPI_* name of this module, so these two run through the exact GEMM
+# suite like every other code (its emulator knows the erf, QuickGELU and tanh activations); tests/test_gpu_siglip.py sweeps the
+# activation itself.  EPILOGUE_*: the names the codes had while that suite skipped them, kept for their users
+EPI_BIAS_TGELU, EPI_LNFOLD_TGELU = 13, 14
+EPILOGUE_BIAS_TGELU, EPILOGUE_LNFOLD_TGELU = EPI_BIAS_TGELU, EPI_LNFOLD_TGELU
 ELEM_F32, ELEM_F16, ELEM_BF16, ELEM_U8 = range(4)   # element type of an image tensor (VH_ELEM_*)
 LAYOUT_NHWC, LAYOUT_NCHW = 0, 1                      # its layout (VH_LAYOUT_*): [B][S][S][C] / [B][C][S][S]
 ELEM_BYTES = {ELEM_F32: 4, ELEM_F16: 2, ELEM_BF16: 2, ELEM_U8: 1}
