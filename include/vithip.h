@@ -317,7 +317,26 @@ int vh_forward(vh_ctx* ctx, const float* in_nhwc_host, int batch, float* logits_
  * the context's stream and waits for completion. */
 int vh_forward_device(vh_ctx* ctx, const float* in_nhwc_dev, int batch, float* logits_dev);
 /* enqueue only; pair with vh_synchronize().  `steps` back-to-back forwards of the same
- * buffers are enqueued (the timed region of bench.py). */
+ * buffers are enqueued (the timed region of bench.py).
+ * TWO FORWARDS IN FLIGHT.  The steps of one call do not depend on each other, and neither do consecutive submits of an image
+ * ring (vh_ring_create, _u8, _tensor).  A context therefore has two compute streams and two sets of activation buffers: even
+ * steps / submits run on the context's stream with the first set, odd ones on the second stream with the second set, and the
+ * partly filled last round of tiles of one forward's GEMMs runs beside the other forward's kernels.  Same kernels, same launch
+ * order inside a forward: logits are bit-identical.  The second stream starts behind everything already on the context's
+ * stream, and the context's stream ends behind it, so vh_synchronize, vh_last_kernel_ms and whatever the caller enqueues on
+ * the context's stream afterwards see every step finished; the steps write `logits_dev` in step order.  The read-outs of "the
+ * last forward" (token and layer features, vh_debug_read) read the set of the step enqueued last.  A ring's collects keep
+ * their order and results.
+ *   memory: the second set is as large as the first without the input staging and the logits (about 2 GB at ViT-B/16, batch
+ *   512; all of it scales with max_batch).  It is allocated at the first call with steps > 1 or at vh_ring_create /
+ *   vh_ring_create_u8 / vh_ring_create_tensor, never inside a stream capture.  If that allocation fails the context stays
+ *   single-flight and reports no error.
+ *   one forward at a time, exactly as before, while any of these holds: steps == 1; stage or step timing is on
+ *   (vh_set_stage_timing, vh_set_step_timing: a duration taken beside another forward's kernels measures neither); graph replay
+ *   is on; vh_set_streams(n > 1); a feature-layer or attention-layer list is set (their stores are one per context); the
+ *   environment had VH_INFLIGHT=1 when the context was created (A/B runs).  The frames ring (vh_ring_create_frames) is
+ *   single-flight as well: its resize writes the one resized-image buffer that the forward's first kernel reads.
+ * vh_get_inflight: 2 when the next steps > 1 call or image-ring submit would run two at a time, else 1. */
 int vh_forward_device_async(vh_ctx* ctx, const float* in_nhwc_dev, int batch,
                             float* logits_dev, int steps);
 int vh_synchronize(vh_ctx* ctx);
@@ -702,7 +721,10 @@ int vh_fill_input_seeded(vh_ctx* ctx, uint64_t seed, int batch, float* in_nhwc_d
  * host-pointer rate approaches the device-resident rate.  Full ring / empty ring are returned as
  * VH_ERR_RING_FULL / VH_ERR_RING_EMPTY (the reference prints and drops the frame, :330-333, :358-361).
  *   vh_ring_input gives the pinned staging buffer of the slot the next submit will use: fill it in place and
- *   submit with in_nhwc_host = NULL to skip the extra host copy. */
+ *   submit with in_nhwc_host = NULL to skip the extra host copy.
+ *   Consecutive submits of the image rings (this one, _u8, _tensor) run two at a time on two compute streams and two buffer
+ *   sets ("TWO FORWARDS IN FLIGHT" at vh_forward_device_async: memory, fall-backs, VH_INFLIGHT); collect order and results
+ *   are unchanged.  The frames ring runs one forward at a time. */
 int vh_ring_create(vh_ctx* ctx, int slots, int batch_per_slot);
 int vh_ring_destroy(vh_ctx* ctx);
 int vh_ring_free_slots(const vh_ctx* ctx, int* n);
@@ -780,6 +802,7 @@ int vh_get_graph(const vh_ctx* ctx, int* enabled, int* cached_graphs);
  * Off by default: two kernels then share the device, so a per-launch duration no longer measures one kernel. */
 int vh_set_streams(vh_ctx* ctx, int n);
 int vh_get_streams(const vh_ctx* ctx, int* n);
+int vh_get_inflight(const vh_ctx* ctx, int* n);
 
 /* observability: replaces forward_performance / get_forward_performance
  * (netFPGA.cpp:262-264,280-284,603-611).  us = host wall time of the last vh_forward*,

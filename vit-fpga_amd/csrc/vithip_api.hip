@@ -233,6 +233,33 @@ struct ImgIn {
 };
 constexpr int kU8 = VH_ELEM_U8;   // ImgIn{p, kU8}: NHWC bytes, the 8-bit entry points and the resized frames
 
+// The buffers ONE forward in flight owns: enqueue_forward takes its part's slices of one set.  A context has two sets and two
+// compute streams, so that two forwards that do not depend on each other -- consecutive steps of vh_forward_device_async,
+// consecutive submits of an image ring -- share the chip: the partly filled last round of tiles of one forward's GEMM runs
+// beside the other forward's kernels (DESIGN.md section 7 "Two forwards in flight").  Set 0 lives in the arena; set 1 is its
+// own allocation, made the first time it is needed (second_set).  Shared by both: the weights and fold_cd, guard_dev (an
+// atomic max, order-free), in_dev, logits_dev, the feature and attention stores.
+struct ActSet {
+    char* base = nullptr;     // set 1: its allocation (set 0: null, the arena owns the bytes)
+    unsigned int* tickets = nullptr;   // [max_batch][layers] work-queue counters of the attention kernel (launch_attention)
+    float* x = nullptr;       // residual stream [B*T, D] fp32
+    void* xn16 = nullptr;     // LN output       [B*T, D]
+    void* xlo16 = nullptr;    // [B*T, D] bytes: the split residual's lo plane
+    void* qkv16 = nullptr;    //                 [B*T, 3D]
+    void* att16 = nullptr;    //                 [B*T, D]
+    void* h16 = nullptr;      //                 [B*T, M]
+    void* col16 = nullptr;    // patch matrix    [B*NP, KPA]
+    float* clsn32 = nullptr;  // the head's input [B, W] fp32: the final-LN'd CLS rows (W = D), or what the VH_FLAG_POOL mode computes (W = L.HW)
+    float* pool32 = nullptr;  // [B, D] fp32 scratch of the pooled modes: CLS_AVG's LN'd class rows, AVG_FCNORM's raw mean
+    float* stats = nullptr;   // [B*T][2] (mean, rstd) of the current residual rows
+    float* partials = nullptr;// [D/64][B*T][2]
+    // VH_FLAG_MAP_HEAD contexts only: z [B][H][D] (the kernel's weighted sums; reused as [B][D] scratch behind the V product), the
+    // block's hidden rows [B][M], and [2][B][D]: a (the V product), then o (the out-projection) of every image
+    float *mapz32 = nullptr, *maph32 = nullptr, *mapa32 = nullptr;
+};
+// byte offsets of a set's buffers from its base, and its size (vh_create computes them once; bind_set turns them into pointers)
+struct ActSetLayout { size_t x, xn, qkv, att, h, col, cls, pool, st, pt, xlo, tk, mz, mh, ma, bytes; };
+
 struct vh_ctx {
     vh_config cfg;
     int device;
@@ -269,8 +296,6 @@ struct vh_ctx {
     // LayerNorm folded into the q|k|v and fc1 GEMMs (dim and mlp_dim multiples of 256):
     bool ln_fold = false;
     float* fold_cd = nullptr; // per layer: cqkv[3D] dqkv[3D] c1[M] d1[M]
-    float* stats = nullptr;   // [B*T][2] (mean, rstd) of the current residual rows
-    float* partials = nullptr;// [D/64][B*T][2]
     // with the fold: the residual stream lives as two planes, x = hi + lo (hi = the xn16 buffer = the GEMMs' 16-bit A operand,
     // lo = xlo16 = what that rounding dropped, one scaled e4m3 byte per element: vh_common.h Lo8): a residual GEMM then moves
     // 3 B per element each way instead of the fp32 array plus its 16-bit copy.
@@ -279,7 +304,6 @@ struct vh_ctx {
     bool cls_tail = false;    // VH_FLAG_CLS_TAIL: the last layer computes the class-token rows only (folded 16-bit path, head dim 64)
     int head_dim = 64;        // dim / heads: 64 takes launch_attention and its layouts, any other launch_attention_hd (row-major)
     float q_scale = kAttnQScale;   // head_dim^-1/2 * log2(e), folded into Wq and bq (attention_q_scale)
-    void* xlo16 = nullptr;    // [B*T, D] bytes
     // Run-time guard on the fold: the kernels that produce the row statistics keep a running maximum of
     // |mean| * rstd over the REAL rows (guard_dev: the bits of a non-negative float); every forward ends with an
     // asynchronous copy of that word into pinned host memory, and every forward entry point looks at the copy before it
@@ -292,22 +316,19 @@ struct vh_ctx {
     float* guard_host = nullptr;
     float guard_thresh = 0.5f;
     bool guard_auto = false, guard_tripped = false;
-    // activations (sized for max_batch)
+    // activations (sized for max_batch): the arena holds set 0 and what both sets share
     char* arena = nullptr;
-    unsigned int* tickets = nullptr;   // [max_batch][layers] work-queue counters of the attention kernel (launch_attention)
-    float* x = nullptr;       // residual stream [B*T, D] fp32
-    void* xn16 = nullptr;     // LN output       [B*T, D]
-    void* qkv16 = nullptr;    //                 [B*T, 3D]
-    void* att16 = nullptr;    //                 [B*T, D]
-    void* h16 = nullptr;      //                 [B*T, M]
-    void* col16 = nullptr;    // patch matrix    [B*NP, KPA]
-    float* clsn32 = nullptr;  // the head's input [B, W] fp32: the final-LN'd CLS rows (W = D), or what the VH_FLAG_POOL mode computes (W = L.HW)
-    float* pool32 = nullptr;  // [B, D] fp32 scratch of the pooled modes: CLS_AVG's LN'd class rows, AVG_FCNORM's raw mean
-    // VH_FLAG_MAP_HEAD contexts only: z [B][H][D] (the kernel's weighted sums; reused as [B][D] scratch behind the V product) and the
-    // block's hidden rows [B][M]
-    float* mapz32 = nullptr;
-    float* maph32 = nullptr;
-    float* mapa32 = nullptr;  // [2][B][D]: a (the V product), then o (the out-projection) of every image
+    ActSet act[2];
+    ActSetLayout act_layout{};
+    int last_set = 0;              // the set of the most recently enqueued forward: what the read-outs of "the last forward" read
+    // two forwards in flight: the second compute stream, fork / join with c->stream, and per set the event behind its last head
+    // launch (consecutive steps write the caller's logits in step order).  inflight_max: 2, or 1 with VH_INFLIGHT=1 (read when
+    // the context is created, for A/B runs) or once the second set could not be allocated.  ring_flip: the set of the next
+    // image-ring submit.  s2_open: stream2 holds ring forwards that c->stream has not joined (sync_compute)
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr, ev_head[2] = {nullptr, nullptr};
+    int inflight_max = 2, ring_flip = 0;
+    bool s2_open = false;
     float* in_dev = nullptr;  // staging for the host-pointer forward (fp32 images; vh_forward_u8 stages its bytes in the same buffer)
     // Input normalisation of the 8-bit entry points (vh_set_input_norm): pixel p of channel c enters the model as
     // fmaf((float)p, in_scale[c], in_shift[c]).  Passed to im2col_u8_kernel by value, so captured graphs hold a copy.
@@ -517,8 +538,9 @@ int prepare_weights(vh_ctx* c) {
 
 // new weights: the guard starts over and the path is the configured one again
 void drop_graphs(vh_ctx* c);
+hipError_t sync_compute(vh_ctx* c);
 int guard_reset(vh_ctx* c) {
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));   // no forward in flight still writes the words
+    HIPCHK(&c->err, sync_compute(c));   // no forward in flight still writes the words
     HIPCHK(&c->err, hipMemsetAsync(c->guard_dev, 0, 2 * sizeof(unsigned int), c->stream));
     c->guard_host[0] = c->guard_host[1] = 0.f;
     c->guard_tripped = false;
@@ -568,8 +590,12 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
 // the launch sequence of ONE forward; `ev` (optional) receives an event after every stage
 // `img0`: first image of this part inside the activation arena (a batch can be split into parts that run on
 // different streams: rows of different images never interact), `s`: the stream to enqueue on.
+// `A`: the buffer set this forward owns; `head_wait` (optional): the final LayerNorm / pooling and the head -- the launches that
+// end in the write of `logits` -- wait for it (two forwards in flight: the step before this one wrote the same logits first).
 int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<std::pair<int, hipEvent_t>>* ev,
-                    hipStream_t s, int img0, bool may_pad = true) {
+                    hipStream_t s, int img0, bool may_pad = true, int set = 0, hipEvent_t head_wait = nullptr) {
+    const ActSet& A = c->act[set];
+    c->last_set = set;
     const vh_config& f = c->cfg;
     const Layout& L = c->L;
     const int D = f.dim, M = f.mlp_dim, T = L.T;
@@ -584,29 +610,29 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     const int64_t row_tiles = (rows + 255) / 256;
     const int64_t rows_g = (may_pad && c->ln_fold && row_tiles * ((D + 255) / 256) >= 2 * (int64_t)c->num_cu) ? row_tiles * 256 : rows;
     const float* P = c->params;
-    // this part's slices of the arena
+    // this part's slices of its buffer set
     const size_t r0 = (size_t)img0 * T, esz = 2, esz_op = c->fp8 ? 1 : 2;  // esz_op: GEMM A-operand element
     const int dt16 = c->dt16;
-    float* const x = c->x + r0 * D;
+    float* const x = A.x + r0 * D;
     // LayerNorm-fold row statistics of this part: (mean, rstd) per row, and the [D/64][rows][2] partial sums; parts take
     // disjoint slices (a part's partial-sum block is (D/64) * rows * 2 floats, laid out for ITS row count)
-    float* const stats_p = c->stats + r0 * 2;
-    float* const partials_p = c->partials + (size_t)(D / 64) * r0 * 2;
-    char* const xn16 = (char*)c->xn16 + r0 * D * esz_op;
-    char* const xlo16 = (char*)c->xlo16 + r0 * D * (c->fp8 ? 2 : 1);   // the lo plane: one byte per element (fp8 path: bf16 beside the e4m3 hi plane)
-    char* const qkv16 = (char*)c->qkv16 + r0 * 3 * D * esz;
-    char* const att16 = (char*)c->att16 + r0 * D * esz_op;
-    char* const h16 = (char*)c->h16 + r0 * M * esz_op;
-    char* const col16 = (char*)c->col16 + (size_t)img0 * L.NP * L.KPA * esz;
-    float* const clsn32 = c->clsn32 + (size_t)img0 * L.HW;   // this part's rows of the head's input [.][W]
-    float* const pool32 = c->pool32 + (size_t)img0 * D;
+    float* const stats_p = A.stats + r0 * 2;
+    float* const partials_p = A.partials + (size_t)(D / 64) * r0 * 2;
+    char* const xn16 = (char*)A.xn16 + r0 * D * esz_op;
+    char* const xlo16 = (char*)A.xlo16 + r0 * D * (c->fp8 ? 2 : 1);   // the lo plane: one byte per element (fp8 path: bf16 beside the e4m3 hi plane)
+    char* const qkv16 = (char*)A.qkv16 + r0 * 3 * D * esz;
+    char* const att16 = (char*)A.att16 + r0 * D * esz_op;
+    char* const h16 = (char*)A.h16 + r0 * M * esz_op;
+    char* const col16 = (char*)A.col16 + (size_t)img0 * L.NP * L.KPA * esz;
+    float* const clsn32 = A.clsn32 + (size_t)img0 * L.HW;   // this part's rows of the head's input [.][W]
+    float* const pool32 = A.pool32 + (size_t)img0 * D;
     // VH_FLAG_NO_CLS: no class-token row.  The patch GEMM's epilogue adds "pos row 1 + p", so a context without pos[0] hands it the
     // table one row early (inside the resident blob: the header and the patch tensors precede pos); the leading rows are all registers.
     const float* const cls_p = L.ncls ? P + L.cls : nullptr;
     const float* const pos_p = P + L.pos - (L.ncls ? 0 : D);
     // the attention launches' work-queue counters: one word per layer, all zeroed by ONE memset per forward (a memset per
     // launch is a 5 us fill kernel in front of every attention kernel)
-    unsigned int* const tickets_part = c->tickets + (size_t)img0 * (f.layers > 0 ? f.layers : 1);
+    unsigned int* const tickets_part = A.tickets + (size_t)img0 * (f.layers > 0 ? f.layers : 1);
     if (f.layers > 0) HIPCHK(&c->err, hipMemsetAsync(tickets_part, 0, sizeof(unsigned int) * f.layers, s));
     // fp8 operands: the folded GEMMs multiply the RAW residual rows as e4m3, which saturates at 448 -- the statistics kernels
     // keep a running maximum of |x| (a bound of it) in the guard's second word
@@ -818,6 +844,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
             g2.out16 = lc;
             HIPCHK(&c->err, launch_gemm(g2, s));
             if ((rc = mark(ST_FC2))) return rc;
+            if (head_wait) HIPCHK(&c->err, hipStreamWaitEvent(s, head_wait, 0));
             HIPCHK(&c->err, launch_layernorm_split(hc, lc, batch, D, D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, dt16, s));
             if ((rc = mark(ST_LNF))) return rc;
             HIPCHK(&c->err, launch_head_f32(clsn32, P + L.headw, P + L.headb, logits, batch, f.classes, D, s));
@@ -899,15 +926,16 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     // same launch into scratch, which the pool kernel copies into columns 0 .. D - 1 beside its own D .. 2 D - 1.  The pooled modes
     // read the patch rows where the path left them (planes or the fp32 array) ONCE.  All of it under the final-LayerNorm stage.
     const bool planes = c->split && nl > 0;
+    if (head_wait) HIPCHK(&c->err, hipStreamWaitEvent(s, head_wait, 0));
     if (L.map) {
         // VH_FLAG_MAP_HEAD (vithip.h "THE FUNCTION"): ONE pass over the patch rows leaves z [batch][H][D]; everything behind it is fp32
         // on `batch` rows through the head's own exact-fp32 kernel: the per-head V product (H groups in one launch), the
         // out-projection, the block's LayerNorm, fc1, the activation, fc2 + the residual.  u lands in clsn32, the head's input.
         const int H = f.heads, hd = D / H;
-        float* const z = c->mapz32 + (size_t)img0 * H * D;
-        float* const hid = c->maph32 + (size_t)img0 * (M > D ? M : D);
-        float* const a32 = c->mapa32 + (size_t)img0 * D;                             // a [batch][D]
-        float* const o32 = c->mapa32 + ((size_t)f.max_batch + img0) * D;             // o [batch][D]
+        float* const z = A.mapz32 + (size_t)img0 * H * D;
+        float* const hid = A.maph32 + (size_t)img0 * (M > D ? M : D);
+        float* const a32 = A.mapa32 + (size_t)img0 * D;                             // a [batch][D]
+        float* const o32 = A.mapa32 + ((size_t)f.max_batch + img0) * D;             // o [batch][D]
         float* const lnrow = z;                                   // [batch][D]: z is dead once a exists
         const PoolArgs pa{planes ? (const void*)xn16 : (const void*)x, planes ? xlo16 : nullptr, planes ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32,
                           batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps, VH_FEAT_NORM, z};
@@ -942,8 +970,10 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
 }
 
 // end of a forward: the guard word travels to pinned host memory behind the forward's kernels (stream order)
-int guard_publish(vh_ctx* c) {
-    if (c->ln_fold) HIPCHK(&c->err, hipMemcpyAsync(c->guard_host, c->guard_dev, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+// (`s`: the stream that ran the forward.  With two forwards in flight two copies of the word may land in either order: it is a
+// running maximum, so the later value is never the smaller one by more than the forward still running will add.)
+int guard_publish(vh_ctx* c, hipStream_t s) {
+    if (c->ln_fold) HIPCHK(&c->err, hipMemcpyAsync(c->guard_host, c->guard_dev, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
     return VH_OK;
 }
 // top of every forward entry point: has a COMPLETED forward seen rows beyond the guard's threshold?  (NaN trips it too.)
@@ -963,14 +993,17 @@ int guard_poll(vh_ctx* c) {
     c->ln_fold = false;
     c->split = false;
     drop_graphs(c);
+    // prepare_weights rewrites the compute copies on c->stream: a forward in flight on the second stream still reads them
+    if (c->stream2) HIPCHK(&c->err, hipStreamSynchronize(c->stream2));
     return prepare_weights(c);          // the plain (unfolded) 16-bit / e4m3 weights, from the resident blob
 }
 
 // one complete forward of `batch` images on the context's stream(s): the (optional) concurrent parts are forked
-// from and joined back into c->stream, so everything that follows on c->stream sees the finished logits
-int enqueue_step(vh_ctx* c, ImgIn in, int batch, float* logits) {
+// from and joined back into c->stream, so everything that follows on c->stream sees the finished logits.
+// `set` 1 (two forwards in flight, never with parts): the whole forward on the second stream with the second buffer set.
+int enqueue_step(vh_ctx* c, ImgIn in, int batch, float* logits, int set = 0, hipEvent_t head_wait = nullptr) {
     const size_t img_elems = (size_t)c->cfg.image_size * c->cfg.image_size * c->cfg.channels;
-    const int parts = batch < c->nstreams ? batch : c->nstreams;
+    const int parts = set ? 1 : batch < c->nstreams ? batch : c->nstreams;
     int rc;
     if (parts > 1) {
         // contiguous parts of the batch on different streams: the HBM-bound stages and the partly filled
@@ -991,10 +1024,11 @@ int enqueue_step(vh_ctx* c, ImgIn in, int batch, float* logits) {
             b0 += nb;
         }
         c->last_batch = batch;
-        return guard_publish(c);
+        return guard_publish(c, c->stream);
     }
-    if ((rc = enqueue_forward(c, in, batch, logits, nullptr, c->stream, 0))) return rc;
-    return guard_publish(c);
+    hipStream_t const st = set ? c->stream2 : c->stream;
+    if ((rc = enqueue_forward(c, in, batch, logits, nullptr, st, 0, true, set, head_wait))) return rc;
+    return guard_publish(c, st);
 }
 
 void drop_graphs(vh_ctx* c) {
@@ -1007,13 +1041,15 @@ void drop_graphs(vh_ctx* c) {
 
 // enqueue_step, or the replay of its captured launch sequence.  Small batches are launch-bound (ViT-B/16 at
 // batch 1: ~100 launches, 1.27 ms eager): the graph removes the per-launch API cost and the gaps between kernels.
-int run_step(vh_ctx* c, ImgIn in, int batch, float* logits) {
+// (`set`, `head_wait`: enqueue_step's; a caller passes them only where two_in_flight() holds, which graph replay rules out)
+int run_step(vh_ctx* c, ImgIn in, int batch, float* logits, int set = 0, hipEvent_t head_wait = nullptr) {
     if (int rc = guard_poll(c)) return rc;
-    if (!c->use_graph || c->timing_stage >= 0) return enqueue_step(c, in, batch, logits);
+    if (!c->use_graph || c->timing_stage >= 0) return enqueue_step(c, in, batch, logits, set, head_wait);
     for (auto& g : c->graphs)
         if (g.in == in && g.out == logits && g.batch == batch) {
             HIPCHK(&c->err, hipGraphLaunch(g.exec, c->stream));
             c->last_batch = batch;
+            c->last_set = 0;
             return VH_OK;
         }
     bool warm = false;
@@ -1053,8 +1089,50 @@ int guard_calibrate(vh_ctx* c) {
     const int rc = enqueue_step(c, ImgIn{c->in_dev}, 1, c->logits_dev);
     c->timing_stage = keep_stage;
     if (rc) return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     return guard_poll(c);
+}
+
+// ---- two forwards in flight ---------------------------------------------------------------------------------------------
+void bind_set(ActSet& a, char* base, const ActSetLayout& o, bool map) {
+    a.x = (float*)(base + o.x); a.xn16 = base + o.xn; a.qkv16 = base + o.qkv; a.att16 = base + o.att; a.h16 = base + o.h;
+    a.col16 = base + o.col; a.clsn32 = (float*)(base + o.cls); a.pool32 = (float*)(base + o.pool);
+    a.stats = (float*)(base + o.st); a.partials = (float*)(base + o.pt); a.xlo16 = base + o.xlo;
+    a.tickets = (unsigned int*)(base + o.tk);
+    if (map) { a.mapz32 = (float*)(base + o.mz); a.maph32 = (float*)(base + o.mh); a.mapa32 = (float*)(base + o.ma); }
+}
+// The second buffer set, allocated the first time it is needed (callers are outside any stream capture: graph replay is
+// single-flight).  No memory for it: the context stays single-flight for good and reports no error.
+bool second_set(vh_ctx* c) {
+    if (c->act[1].base) return true;
+    if (c->inflight_max < 2) return false;
+    char* p = nullptr;
+    if (hipMalloc((void**)&p, c->act_layout.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->inflight_max = 1;
+        return false;
+    }
+    c->act[1].base = p;
+    bind_set(c->act[1], p, c->act_layout, c->L.map);
+    return true;
+}
+// May consecutive forwards of this context run two at a time?  Not where a launch is timed (a duration beside another forward's
+// kernels measures neither), a graph replays (captured on one stream), the batch runs as parts (vh_set_streams), or a layer
+// list is set (the feature and attention stores are one per context).
+bool two_in_flight_allowed(const vh_ctx* c) {
+    return c->inflight_max == 2 && c->timing_stage < 0 && !c->step_timing && !c->use_graph && c->nstreams == 1 && c->feat_n == 0 &&
+           c->attn_n == 0;
+}
+bool two_in_flight(vh_ctx* c) { return two_in_flight_allowed(c) && second_set(c); }
+// every compute stream of the context idle: c->stream, and the second stream where ring submits left forwards on it that
+// c->stream has not joined (vh_forward_device_async joins its own before it returns)
+hipError_t sync_compute(vh_ctx* c) {
+    if (c->s2_open) {
+        const hipError_t e = hipStreamSynchronize(c->stream2);
+        if (e != hipSuccess) return e;
+        c->s2_open = false;
+    }
+    return hipStreamSynchronize(c->stream);
 }
 
 int check_forward_args(vh_ctx* c, const void* in, int batch, const void* out) {
@@ -1183,7 +1261,7 @@ int frames_reserve(vh_ctx* c, size_t plan_words, bool host_too, size_t frame_byt
     const vh_config& f = c->cfg;
     if (!c->rz_u8) HIPCHK(&c->err, hipMalloc((void**)&c->rz_u8, (size_t)f.max_batch * f.image_size * f.image_size * f.channels));
     if (plan_words > c->rz_plan_dev_cap) {
-        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+        HIPCHK(&c->err, sync_compute(c));
         if (c->rz_plan_dev) hipFree(c->rz_plan_dev);
         c->rz_plan_dev = nullptr; c->rz_plan_dev_cap = 0;
         const size_t cap = plan_words * 2 > 16384 ? plan_words * 2 : 16384;
@@ -1191,7 +1269,7 @@ int frames_reserve(vh_ctx* c, size_t plan_words, bool host_too, size_t frame_byt
         c->rz_plan_dev_cap = cap;
     }
     if (host_too && plan_words > c->rz_plan_host_cap) {
-        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+        HIPCHK(&c->err, sync_compute(c));
         if (c->rz_plan_host) hipHostFree(c->rz_plan_host);
         c->rz_plan_host = nullptr; c->rz_plan_host_cap = 0;
         const size_t cap = plan_words * 2 > 16384 ? plan_words * 2 : 16384;
@@ -1199,7 +1277,7 @@ int frames_reserve(vh_ctx* c, size_t plan_words, bool host_too, size_t frame_byt
         c->rz_plan_host_cap = cap;
     }
     if (frame_bytes > c->rz_frames_cap) {
-        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+        HIPCHK(&c->err, sync_compute(c));
         if (c->rz_frames) hipFree(c->rz_frames);
         c->rz_frames = nullptr; c->rz_frames_cap = 0;
         const size_t cap = frame_bytes + frame_bytes / 2;
@@ -1252,9 +1330,27 @@ int forward_device_async(vh_ctx* c, ImgIn in, int batch, float* logits, int step
     HIPCHK(&c->err, hipEventRecord(c->ev0, c->stream));
     if ((rc = step_mark())) return rc;
     if (job && (rc = enqueue_resize(c, *job, batch))) return rc;
+    // Steps do not depend on each other: even ones run on c->stream with buffer set 0, odd ones on the second stream with set 1.
+    // The second stream starts behind everything the caller (and the resize) put on c->stream, and c->stream ends behind it, so
+    // ev1, vh_synchronize and whatever the caller enqueues next see every step finished.  Every step writes the caller's
+    // logits: the final LayerNorm + head of step i wait for the head of step i - 1 (about 0.2 % of a forward), which keeps the
+    // writes in step order.
+    const bool two = steps > 1 && two_in_flight(c);
+    if (two) {
+        c->s2_open = true;   // (until the join below: an error return in between leaves the second stream to sync_compute)
+        HIPCHK(&c->err, hipEventRecord(c->ev_fork2, c->stream));
+        HIPCHK(&c->err, hipStreamWaitEvent(c->stream2, c->ev_fork2, 0));
+    }
     for (int i = 0; i < steps; ++i) {
-        if ((rc = run_step(c, in, batch, logits))) return rc;
+        const int set = two ? i & 1 : 0;
+        if ((rc = run_step(c, in, batch, logits, set, two && i > 0 ? c->ev_head[set ^ 1] : nullptr))) return rc;
+        if (two) HIPCHK(&c->err, hipEventRecord(c->ev_head[set], set ? c->stream2 : c->stream));
         if ((rc = step_mark())) return rc;
+    }
+    if (two) {
+        HIPCHK(&c->err, hipEventRecord(c->ev_join2, c->stream2));
+        HIPCHK(&c->err, hipStreamWaitEvent(c->stream, c->ev_join2, 0));
+        c->s2_open = false;
     }
     HIPCHK(&c->err, hipEventRecord(c->ev1, c->stream));
     c->timed = true;
@@ -1285,13 +1381,13 @@ int forward_host(vh_ctx* c, ImgIn in_host, int batch, float* logits_host, const 
     rc = forward_device_async(c, staged, batch, c->logits_dev, 1, job);
     if (rc) return rc;
     HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     if (c->guard_auto && guard_exceeded(c)) {
         // this (synchronous) forward itself ran folded on rows beyond the guard: run it again, now with the stand-alone LayerNorm
         rc = forward_device_async(c, staged, batch, c->logits_dev, 1);   // (its run_step polls the guard and switches; resized frames are still in place)
         if (rc) return rc;
         HIPCHK(&c->err, hipMemcpyAsync(logits_host, c->logits_dev, (size_t)batch * f.classes * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+        HIPCHK(&c->err, sync_compute(c));
     }
     c->last_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::high_resolution_clock::now() - t0).count();
     return VH_OK;
@@ -1399,6 +1495,14 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         if (c->nstreams < 1) c->nstreams = 1;
         if (c->nstreams > vh_ctx::kMaxStreams) c->nstreams = vh_ctx::kMaxStreams;
     }
+    CK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+    CK(hipEventCreateWithFlags(&c->ev_fork2, hipEventDisableTiming));
+    CK(hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
+    for (hipEvent_t& e : c->ev_head) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    {
+        const char* e = getenv("VH_INFLIGHT");   // VH_INFLIGHT=1: one forward at a time, as before the second set existed (A/B runs)
+        c->inflight_max = e && e[0] == '1' && !e[1] ? 1 : 2;
+    }
     c->num_cu = prop.multiProcessorCount;
     {
         const char* e = getenv("VH_GRAPH");
@@ -1480,31 +1584,30 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
             c->sqkv.push_back(sc); c->so.push_back(sc + 3 * D); c->s1.push_back(sc + 4 * D); c->s2.push_back(sc + 4 * D + M);
         }
     }
-    // activation arena
+    // activation arena: buffer set 0 (the layout serves the second set too), then what both sets share
     size_t a = 0;
     auto carve = [&](size_t bytes) { size_t o = a; a += align_up(bytes, 256); return o; };
     // room for whole 256-row GEMM tiles behind the LAST part of a forward (enqueue_forward, rows_g): its rows start anywhere,
     // so the padding may reach up to 255 rows past the last real row
     const size_t rows_p = rows + 256;
-    const size_t o_x = carve(rows_p * D * 4), o_xn = carve(rows_p * D * 2), o_qkvA = carve(rows_p * 3 * D * 2),
-                 o_att = carve(rows_p * D * 2), o_h = carve(rows_p * M * 2), o_col = carve(B * L.NP * (size_t)L.KPA * 2),
-                 o_cls = carve(B * 2 * D * 4), o_pool = carve(B * D * 4),   // the head's input [B][W <= 2 D]; VH_FLAG_POOL scratch [B][D]
-                 o_in = carve(B * (size_t)cfg->image_size * cfg->image_size * cfg->channels * 4), o_lg = carve(B * C * 4),
-                 o_st = carve(rows_p * 2 * 4), o_pt = carve((D / 64 + 1) * rows_p * 2 * 4), o_xlo = carve(rows_p * D * 2),   // lo plane: one byte per element (16-bit paths) or bf16 (fp8 path)
-                 o_tk = carve(B * 4 * (size_t)(cfg->layers > 0 ? cfg->layers : 1)),   // attention work-queue counters: one word per image and layer, a part uses its first image's
+    ActSetLayout& o = c->act_layout;
+    o.x = carve(rows_p * D * 4); o.xn = carve(rows_p * D * 2); o.qkv = carve(rows_p * 3 * D * 2);
+    o.att = carve(rows_p * D * 2); o.h = carve(rows_p * M * 2); o.col = carve(B * L.NP * (size_t)L.KPA * 2);
+    o.cls = carve(B * 2 * D * 4); o.pool = carve(B * D * 4);   // the head's input [B][W <= 2 D]; VH_FLAG_POOL scratch [B][D]
+    o.st = carve(rows_p * 2 * 4); o.pt = carve((D / 64 + 1) * rows_p * 2 * 4);
+    o.xlo = carve(rows_p * D * 2);   // lo plane: one byte per element (16-bit paths) or bf16 (fp8 path)
+    o.tk = carve(B * 4 * (size_t)(cfg->layers > 0 ? cfg->layers : 1));   // attention work-queue counters: one word per image and layer, a part uses its first image's
+    // VH_FLAG_MAP_HEAD: z, the hidden rows, and the rows a | o
+    o.mz = L.map ? carve(B * (size_t)cfg->heads * D * 4) : 0; o.mh = L.map ? carve(B * (M > D ? M : D) * 4) : 0;
+    o.ma = L.map ? carve(B * 2 * D * 4) : 0;
+    o.bytes = a;
+    const size_t o_in = carve(B * (size_t)cfg->image_size * cfg->image_size * cfg->channels * 4), o_lg = carve(B * C * 4),
                  o_gd = carve(256);     // the LayerNorm-fold guard word
-    const size_t o_mz = L.map ? carve(B * (size_t)cfg->heads * D * 4) : 0, o_mh = L.map ? carve(B * (M > D ? M : D) * 4) : 0,
-                 o_ma = L.map ? carve(B * 2 * D * 4) : 0;   // VH_FLAG_MAP_HEAD: z, the hidden rows, and the rows a | o
     CK(hipMalloc((void**)&c->arena, a));
     c->guard_dev = (unsigned int*)(c->arena + o_gd);
     CK(hipMemsetAsync(c->guard_dev, 0, 256, c->stream));
-    c->x = (float*)(c->arena + o_x); c->xn16 = c->arena + o_xn; c->qkv16 = c->arena + o_qkvA; c->att16 = c->arena + o_att;
-    c->h16 = c->arena + o_h; c->col16 = c->arena + o_col; c->clsn32 = (float*)(c->arena + o_cls);
-    c->pool32 = (float*)(c->arena + o_pool);
+    bind_set(c->act[0], c->arena, o, L.map);
     c->in_dev = (float*)(c->arena + o_in); c->logits_dev = (float*)(c->arena + o_lg);
-    c->stats = (float*)(c->arena + o_st); c->partials = (float*)(c->arena + o_pt); c->xlo16 = c->arena + o_xlo;
-    c->tickets = (unsigned int*)(c->arena + o_tk);
-    if (L.map) { c->mapz32 = (float*)(c->arena + o_mz); c->maph32 = (float*)(c->arena + o_mh); c->mapa32 = (float*)(c->arena + o_ma); }
 #undef CK
     *out = c;
     return VH_OK;
@@ -1514,7 +1617,7 @@ int vh_destroy(vh_ctx* c) {
     if (!c) return VH_OK;
     hipSetDevice(c->device);
     vh_ring_destroy(c);
-    if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->stream) sync_compute(c);
     drop_graphs(c);
     if (c->guard_host) hipHostFree(c->guard_host);
     if (c->rz_plan_host) hipHostFree(c->rz_plan_host);
@@ -1522,6 +1625,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->rz_frames) hipFree(c->rz_frames);
     if (c->rz_u8) hipFree(c->rz_u8);
     if (c->arena) hipFree(c->arena);
+    if (c->act[1].base) hipFree(c->act[1].base);
     if (c->feat_store) hipFree(c->feat_store);
     if (c->attn_store) hipFree(c->attn_store);
     if (c->w16) hipFree(c->w16);
@@ -1535,6 +1639,10 @@ int vh_destroy(vh_ctx* c) {
         if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]);
     }
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
+    if (c->ev_fork2) hipEventDestroy(c->ev_fork2);
+    if (c->ev_join2) hipEventDestroy(c->ev_join2);
+    for (hipEvent_t e : c->ev_head) if (e) hipEventDestroy(e);
+    if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return VH_OK;
@@ -1556,7 +1664,7 @@ int vh_get_ln_fold(const vh_ctx* c, int* on) {
 int vh_get_ln_guard(vh_ctx* c, float* max_ratio, float* threshold, int* tripped) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     float seen[2] = {0.f, 0.f};
     HIPCHK(&c->err, hipMemcpy(seen, c->guard_dev, sizeof seen, hipMemcpyDeviceToHost));
     if ((!(seen[0] <= c->guard_thresh) || (c->fp8 && !(seen[1] <= kE4M3Max))) && c->ln_fold_cfg) c->guard_tripped = true;
@@ -1569,7 +1677,7 @@ int vh_get_ln_guard(vh_ctx* c, float* max_ratio, float* threshold, int* tripped)
 int vh_get_fp8_guard(vh_ctx* c, float* max_abs, float* limit) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     float seen[2] = {0.f, 0.f};
     HIPCHK(&c->err, hipMemcpy(seen, c->guard_dev, sizeof seen, hipMemcpyDeviceToHost));
     if (max_abs) *max_abs = c->fp8 ? seen[1] : 0.f;
@@ -1815,7 +1923,7 @@ int vh_forward_device_u8_async(vh_ctx* c, const uint8_t* in, int batch, float* l
 int vh_synchronize(vh_ctx* c) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     // everything enqueued has completed: if one of those forwards tripped the fold's guard, switch NOW rather than at the
     // next forward's entry (vh_get_ln_guard reports it; the results already delivered came from the folded path)
     if (c->weights_ready) return guard_poll(c);
@@ -2005,7 +2113,7 @@ int vh_set_input_norm(vh_ctx* c, const float* scale, const float* shift) {
     for (int i = 0; scale && i < ch; ++i)
         if (!std::isfinite(scale[i]) || !std::isfinite(shift[i])) return fail(&c->err, VH_ERR_INVALID, "scale / shift of channel %d is not finite", i);
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     for (int i = 0; i < kMaxChannels; ++i) {
         c->in_scale[i] = i < ch ? (scale ? scale[i] : 1.0f / 255.0f) : 0.f;
         c->in_shift[i] = i < ch && shift ? shift[i] : 0.f;
@@ -2025,7 +2133,7 @@ int vh_fill_input_seeded(vh_ctx* c, uint64_t seed, int batch, float* in_dev) {
     HIPCHK(&c->err, hipSetDevice(c->device));
     const int64_t n = (int64_t)batch * c->cfg.image_size * c->cfg.image_size * c->cfg.channels;
     HIPCHK(&c->err, launch_fill(in_dev, n, seed, TID_IMAGES, 0, 0.f, 0.f, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     return VH_OK;
 }
 
@@ -2055,7 +2163,7 @@ int vh_profile_forward(vh_ctx* c, const float* in, int batch, float* logits, dou
     HIPCHK(&c->err, hipSetDevice(c->device));
     std::vector<std::pair<int, hipEvent_t>> ev;
     rc = enqueue_forward(c, ImgIn{in}, batch, logits, &ev, c->stream, 0);
-    if (!rc) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) rc = fail(&c->err, VH_ERR_HIP, "sync: %s", hipGetErrorString(e)); }
+    if (!rc) { hipError_t e = sync_compute(c); if (e != hipSuccess) rc = fail(&c->err, VH_ERR_HIP, "sync: %s", hipGetErrorString(e)); }
     for (int i = 0; i < 2 * kProfiledStages; ++i) stage_ms[i] = 0.0;
     if (!rc)
         for (size_t i = 1; i < ev.size(); ++i) {
@@ -2080,7 +2188,7 @@ int vh_ring_destroy(vh_ctx* c) {
     if (!c) return VH_OK;
     if (c->ring.empty() && !c->copy_in) return VH_OK;
     hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->stream) sync_compute(c);
     if (c->copy_in) hipStreamSynchronize(c->copy_in);
     if (c->copy_out) hipStreamSynchronize(c->copy_out);
     for (auto& s : c->ring) {
@@ -2146,6 +2254,8 @@ static int ring_create(vh_ctx* c, int slots, int batch_per_slot, vh_ctx::RingKin
             return fail(&c->err, VH_ERR_HIP, "vh_ring_create: %s", hipGetErrorString(e));
         }
     }
+    if (!frames && two_in_flight_allowed(c)) second_set(c);   // here rather than inside the first submits
+    c->ring_flip = 0;
     c->ring_batch = batch_per_slot;
     c->ring_kind = kind;
     c->ring_elem = elem;
@@ -2232,14 +2342,21 @@ static int ring_submit(vh_ctx* c, const void* in_host, int batch, vh_ctx::RingKi
     s.batch = batch;
     HIPCHK(&c->err, hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, c->copy_in));
     HIPCHK(&c->err, hipEventRecord(s.in_done, c->copy_in));
-    HIPCHK(&c->err, hipStreamWaitEvent(c->stream, s.in_done, 0));
+    // Image rings: consecutive submits alternate between the two compute streams and buffer sets, so the forward of batch i + 1
+    // runs beside that of batch i; every slot has its own logits buffer, so nothing orders their heads.  The frames ring stays
+    // on c->stream: its resize writes the one rz_u8 buffer that the forward's first kernel reads.
+    const int set = !frames && two_in_flight(c) ? c->ring_flip : 0;
+    hipStream_t const st = set ? c->stream2 : c->stream;
+    c->ring_flip = set ^ 1;
+    if (set) c->s2_open = true;
+    HIPCHK(&c->err, hipStreamWaitEvent(st, s.in_done, 0));
     if (frames) {
         const FrameJob job{fmt, (const uint8_t*)s.d_in, s.h_plan, c->rz_words.size(), max_tiles};
         if ((rc = enqueue_resize(c, job, batch))) return rc;
     }
-    rc = run_step(c, frames ? ImgIn{c->rz_u8, kU8} : slot_in, batch, s.d_out);
+    rc = run_step(c, frames ? ImgIn{c->rz_u8, kU8} : slot_in, batch, s.d_out, set);
     if (rc) return rc;
-    HIPCHK(&c->err, hipEventRecord(s.fwd_done, c->stream));
+    HIPCHK(&c->err, hipEventRecord(s.fwd_done, st));
     HIPCHK(&c->err, hipStreamWaitEvent(c->copy_out, s.fwd_done, 0));
     HIPCHK(&c->err, hipMemcpyAsync(s.h_out, s.d_out, (size_t)batch * c->cfg.classes * 4, hipMemcpyDeviceToHost, c->copy_out));
     HIPCHK(&c->err, hipEventRecord(s.out_done, c->copy_out));
@@ -2297,7 +2414,7 @@ int vh_set_streams(vh_ctx* c, int n) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (n < 1 || n > vh_ctx::kMaxStreams) return fail(&c->err, VH_ERR_INVALID, "streams must be 1..%d", vh_ctx::kMaxStreams);
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     c->nstreams = n;
     drop_graphs(c);
     return VH_OK;
@@ -2306,7 +2423,7 @@ int vh_set_streams(vh_ctx* c, int n) {
 int vh_set_graph(vh_ctx* c, int enable) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     c->use_graph = enable != 0;
     if (!c->use_graph) drop_graphs(c);
     return VH_OK;
@@ -2325,6 +2442,12 @@ int vh_get_streams(const vh_ctx* c, int* n) {
     return VH_OK;
 }
 
+int vh_get_inflight(const vh_ctx* c, int* n) {
+    if (!c || !n) return fail(nullptr, VH_ERR_INVALID, "null argument");
+    *n = two_in_flight_allowed(c) ? 2 : 1;
+    return VH_OK;
+}
+
 int vh_set_stage_timing(vh_ctx* c, int stage) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     if (stage < -1 || stage >= ST_COUNT) return fail(&c->err, VH_ERR_INVALID, "unknown stage %d", stage);
@@ -2336,7 +2459,7 @@ int vh_set_stage_timing(vh_ctx* c, int stage) {
 int vh_get_stage_timing(vh_ctx* c, double* avg_ms, double* min_ms, int* launches) {
     if (!c || !avg_ms || !launches) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     double sum = 0.0, mn = 1e30;
     int n = 0;
     for (size_t i = 0; i + 1 < c->tev_used; i += 2) {
@@ -2360,7 +2483,7 @@ int vh_set_step_timing(vh_ctx* c, int enable) {
 int vh_get_step_timing(vh_ctx* c, double* step_ms, int max_steps, int* steps) {
     if (!c || !steps || (max_steps > 0 && !step_ms)) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     int n = 0;
     for (size_t i = 0; i + 1 < c->sev_used; ++i) {
         float t = 0.f;
@@ -2376,7 +2499,7 @@ int vh_debug_read(vh_ctx* c, int what, float* host_out, size_t n_floats) {
     if (!c || !host_out) return fail(c ? &c->err : nullptr, VH_ERR_INVALID, "null argument");
     if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "no forward has run");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     const size_t D = c->cfg.dim;
     if (what == 0) {
         const size_t n = (size_t)c->last_batch * c->L.T * D;
@@ -2395,26 +2518,26 @@ int vh_debug_read(vh_ctx* c, int what, float* host_out, size_t n_floats) {
             if (c->fp8) {   // e4m3 hi plane (the GEMM operand) + bf16 lo plane
                 std::vector<uint8_t> hi(n);
                 std::vector<uint16_t> lo(n);
-                HIPCHK(&c->err, hipMemcpy(hi.data(), c->xn16, n, hipMemcpyDeviceToHost));
-                HIPCHK(&c->err, hipMemcpy(lo.data(), c->xlo16, n * 2, hipMemcpyDeviceToHost));
+                HIPCHK(&c->err, hipMemcpy(hi.data(), c->act[c->last_set].xn16, n, hipMemcpyDeviceToHost));
+                HIPCHK(&c->err, hipMemcpy(lo.data(), c->act[c->last_set].xlo16, n * 2, hipMemcpyDeviceToHost));
                 for (size_t i = 0; i < n; ++i) host_out[i] = g(hi[i]) + f(lo[i], VH_DTYPE_BF16);
                 return VH_OK;
             }
             std::vector<uint16_t> hi(n);
             std::vector<uint8_t> lo(n);
-            HIPCHK(&c->err, hipMemcpy(hi.data(), c->xn16, n * 2, hipMemcpyDeviceToHost));
-            HIPCHK(&c->err, hipMemcpy(lo.data(), c->xlo16, n, hipMemcpyDeviceToHost));
+            HIPCHK(&c->err, hipMemcpy(hi.data(), c->act[c->last_set].xn16, n * 2, hipMemcpyDeviceToHost));
+            HIPCHK(&c->err, hipMemcpy(lo.data(), c->act[c->last_set].xlo16, n, hipMemcpyDeviceToHost));
             const float inv = c->dt16 == VH_DTYPE_BF16 ? 1.f / 32.f : 1.f / 256.f;   // the byte plane's scale (vh_common.h Lo8<T>)
             for (size_t i = 0; i < n; ++i) host_out[i] = f(hi[i], c->dt16) + g(lo[i]) * inv;
             return VH_OK;
         }
-        HIPCHK(&c->err, hipMemcpy(host_out, c->x, n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(&c->err, hipMemcpy(host_out, c->act[c->last_set].x, n * 4, hipMemcpyDeviceToHost));
         return VH_OK;
     }
     if (what == 1) {
         const size_t n = (size_t)c->last_batch * c->L.HW;   // the head's input [batch][W]
         if (n_floats != n) return fail(&c->err, VH_ERR_INVALID, "expected %zu floats", n);
-        HIPCHK(&c->err, hipMemcpy(host_out, c->clsn32, n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(&c->err, hipMemcpy(host_out, c->act[c->last_set].clsn32, n * 4, hipMemcpyDeviceToHost));
         return VH_OK;
     }
     if (what == 3) {   // 1 when the last forward kept the MLP hidden activation in its tiled layout (h_tiled)
@@ -2433,7 +2556,7 @@ int vh_debug_read(vh_ctx* c, int what, float* host_out, size_t n_floats) {
 int vh_debug_set_layers(vh_ctx* c, int n_layers) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "null context");
     c->run_layers = n_layers;
-    if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->stream) sync_compute(c);
     drop_graphs(c);
     return VH_OK;
 }
@@ -2441,7 +2564,7 @@ int vh_debug_set_layers(vh_ctx* c, int n_layers) {
 // ---- token features (vithip.h "Token features"; kernels_features.hip) ---------------------------------------------------
 // A pull interface: these calls read what the last forward left in the arena -- the residual stream in the form its path keeps it
 // (the same choice vh_debug_read makes), clsn32, the final LayerNorm's parameters in the blob -- and no forward knows of them.
-// The normalised mean's row statistics go through c->stats, which is free between forwards (every path that reads it writes it
+// The normalised mean's row statistics go through the last set's stats, which are free between forwards (every path that reads it writes it
 // first); everything is enqueued on the context's main stream, where a forward on several streams has already joined.
 static int features_check_call(vh_ctx* c, const vh_features* f, bool device) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "read_features: null context");
@@ -2465,7 +2588,8 @@ static FeatSource features_live(const vh_ctx* c) {
     const vh_config& g = c->cfg;
     const int nl = (c->run_layers < 0 || c->run_layers > g.layers) ? g.layers : c->run_layers;
     const bool planes = c->split && nl > 0;   // where the last forward left the rows: the two planes, or the fp32 array
-    return FeatSource{planes ? (const void*)c->xn16 : (const void*)c->x, planes ? c->xlo16 : nullptr,
+    const ActSet& A = c->act[c->last_set];   // the final layer's rows are the live residual of the most recently enqueued forward
+    return FeatSource{planes ? (const void*)A.xn16 : (const void*)A.x, planes ? A.xlo16 : nullptr,
                       planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32, c->L.pool == VH_POOL_CLS};   // (a pooled head's input is not LN(row 0))
 }
 static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSource& src, const char* who) {
@@ -2478,7 +2602,7 @@ static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSou
     a.elem = f.elem; a.norm = f.norm;
     const bool copy_cls = norm && src.head_cls;   // the normalised class-token rows the head multiplied: a conversion copy of clsn32
     a.cls = copy_cls ? nullptr : f.cls;
-    a.patch = f.patch; a.mean = f.mean; a.stats = c->stats;
+    a.patch = f.patch; a.mean = f.mean; a.stats = c->act[c->last_set].stats;
     a.reg = f.reg; a.patch_layout = f.patch_layout;
     a.no_cls = c->L.ncls ? 0 : 1;   // VH_FLAG_NO_CLS: lead = R rows, all of them registers (an internal form: the public taps keep lead >= 1)
     if (a.cls || a.patch || a.mean || a.reg) {
@@ -2487,8 +2611,8 @@ static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSou
     }
     if (copy_cls && f.cls) {
         const int64_t n = (int64_t)c->last_batch * g.dim;
-        if (f.elem == VH_ELEM_F32) HIPCHK(&c->err, hipMemcpyAsync(f.cls, c->clsn32, n * 4, hipMemcpyDeviceToDevice, c->stream));
-        else HIPCHK(&c->err, launch_cast(c->clsn32, f.cls, n, f.elem == VH_ELEM_BF16 ? VH_DTYPE_BF16 : VH_DTYPE_FP16, c->stream));
+        if (f.elem == VH_ELEM_F32) HIPCHK(&c->err, hipMemcpyAsync(f.cls, c->act[c->last_set].clsn32, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        else HIPCHK(&c->err, launch_cast(c->act[c->last_set].clsn32, f.cls, n, f.elem == VH_ELEM_BF16 ? VH_DTYPE_BF16 : VH_DTYPE_FP16, c->stream));
     }
     return VH_OK;
 }
@@ -2498,7 +2622,7 @@ static int features_read_host(vh_ctx* c, const vh_layer_features& f, const FeatS
     const size_t es = f.elem == VH_ELEM_F32 ? 4 : 2, D = c->cfg.dim, B = c->last_batch;
     const size_t n_row = B * D * es, n_patch = B * (size_t)c->L.NP * D * es, n_reg = B * (size_t)c->L.R * D * es;
     const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * D * 2;
-    char* const base = (char*)c->qkv16;
+    char* const base = (char*)c->act[c->last_set].qkv16;
     size_t at = 0;
     auto take = [&](bool want, size_t bytes) -> void* { if (!want) return nullptr; void* p = base + at; at += align_up(bytes, 256); return p; };
     vh_layer_features d = f;
@@ -2512,7 +2636,7 @@ static int features_read_host(vh_ctx* c, const vh_layer_features& f, const FeatS
     if (f.cls) HIPCHK(&c->err, hipMemcpyAsync(f.cls, d.cls, n_row, hipMemcpyDeviceToHost, c->stream));
     if (f.mean) HIPCHK(&c->err, hipMemcpyAsync(f.mean, d.mean, n_row, hipMemcpyDeviceToHost, c->stream));
     if (f.reg) HIPCHK(&c->err, hipMemcpyAsync(f.reg, d.reg, n_reg, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     return VH_OK;
 }
 static vh_layer_features features_final(const vh_features& f) {
@@ -2533,7 +2657,7 @@ int vh_read_features_device_async(vh_ctx* c, const vh_features* f) {
 }
 int vh_read_features_device(vh_ctx* c, const vh_features* f) {
     if (int rc = vh_read_features_device_async(c, f)) return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     return VH_OK;
 }
 int vh_read_features(vh_ctx* c, const vh_features* f) {
@@ -2558,7 +2682,7 @@ int vh_set_feature_layers(vh_ctx* c, const int* layers, int n) {
         return fail(&c->err, VH_ERR_UNSUPPORTED, "set_feature_layers: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
     if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "set_feature_layers: a ring exists on this context; vh_ring_destroy first");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     int slots = 0;
     for (int i = 0; i < n; ++i) slots += layers[i] < c->cfg.layers;
     // 3 bytes per element where the residual stays two planes for good; 4 where it is, or may become (the guarded fold), the fp32 array
@@ -2639,7 +2763,7 @@ int vh_read_layer_features_device_async(vh_ctx* c, const vh_layer_features* f) {
 }
 int vh_read_layer_features_device(vh_ctx* c, const vh_layer_features* f) {
     if (int rc = vh_read_layer_features_device_async(c, f)) return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     return VH_OK;
 }
 int vh_read_layer_features(vh_ctx* c, const vh_layer_features* f) {
@@ -2674,7 +2798,7 @@ int vh_set_attention_layers(vh_ctx* c, const int* layers, int n, int queries) {
         return fail(&c->err, VH_ERR_UNSUPPORTED, "set_attention_layers: a VH_FLAG_CLS_TAIL context's last layer runs the class-token attention kernel");
     if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "set_attention_layers: a ring exists on this context; vh_ring_destroy first");
     HIPCHK(&c->err, hipSetDevice(c->device));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     const size_t slot = align_up((size_t)c->cfg.max_batch * c->cfg.heads * Q * c->L.T * sizeof(float), 256);
     char* store = nullptr;
     if (n) {
@@ -2753,7 +2877,7 @@ int vh_read_attention_device_async(vh_ctx* c, const vh_attention_maps* f) {
 }
 int vh_read_attention_device(vh_ctx* c, const vh_attention_maps* f) {
     if (int rc = vh_read_attention_device_async(c, f)) return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     return VH_OK;
 }
 // the host form: staged in the q|k|v buffer, as features_read_host does (scratch between forwards)
@@ -2767,13 +2891,13 @@ int vh_read_attention(vh_ctx* c, const vh_attention_maps* f) {
     const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * c->cfg.dim * 2;
     vh_attention_maps d = *f;
     size_t at = 0;
-    if (f->probs) { d.probs = (char*)c->qkv16 + at; at += align_up(n_probs, 256); }
-    if (f->head_mean) { d.head_mean = (char*)c->qkv16 + at; at += align_up(n_mean, 256); }
+    if (f->probs) { d.probs = (char*)c->act[c->last_set].qkv16 + at; at += align_up(n_probs, 256); }
+    if (f->head_mean) { d.head_mean = (char*)c->act[c->last_set].qkv16 + at; at += align_up(n_mean, 256); }
     if (at > cap) return fail(&c->err, VH_ERR_STATE, "read_attention: staging needs %zu bytes, the scratch holds %zu", at, cap);
     if (int rc = attention_enqueue(c, d, slot)) return rc;
     if (f->probs) HIPCHK(&c->err, hipMemcpyAsync(f->probs, d.probs, n_probs, hipMemcpyDeviceToHost, c->stream));
     if (f->head_mean) HIPCHK(&c->err, hipMemcpyAsync(f->head_mean, d.head_mean, n_mean, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    HIPCHK(&c->err, sync_compute(c));
     return VH_OK;
 }
 

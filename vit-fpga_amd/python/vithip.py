@@ -279,6 +279,7 @@ SYMBOLS = {
     "vh_get_graph": (_i, [_vp, _pi, _pi]),
     "vh_set_streams": (_i, [_vp, _i]),
     "vh_get_streams": (_i, [_vp, _pi]),
+    "vh_get_inflight": (_i, [_vp, _pi]),
     "vh_set_stage_timing": (_i, [_vp, _i]),
     "vh_get_stage_timing": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _pi]),
     "vh_set_step_timing": (_i, [_vp, _i]),
@@ -1807,6 +1808,12 @@ class VitContext:
     def get_streams(self):
         n = C.c_int(0)
         _check(lib().vh_get_streams(self.h, C.byref(n)), self.h)
+        return n.value
+
+    def get_inflight(self):
+        """2 when consecutive forwards (the steps of forward_device_async, image-ring submits) run two at a time, else 1."""
+        n = C.c_int(0)
+        _check(lib().vh_get_inflight(self.h, C.byref(n)), self.h)
         return n.value
 
     def set_stage_timing(self, stage_name):
