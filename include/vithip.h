@@ -240,6 +240,24 @@ typedef struct vh_config {
  *   Attention maps of a ROPE context are of the rotated q and k: the model's own.  An image's bits depend on its rows alone. */
 #define VH_FLAG_ROPE (1 << 23)
 
+/* SwiGLU MLP (DINOv2-g/14, DINOv3 ViT-H+/16 and 7B; the gated MLP of many later towers): ONE MODEL switch, in bit 25 of flags and, at
+ * the same position, of the blob header's flags word; a blob whose bit differs from the context's is refused with a message that names
+ * the bit.  With the bit clear nothing changes: not one launch.
+ *   VH_FLAG_SWIGLU  the MLP of every layer is gated.  mlp_dim = M is the GATED width: fc2's K (4096 for DINOv2-g/14).  Excludes, each
+ *                   with a message of its own (vh_weight_blob_bytes returns 0): VH_FLAG_QUICK_GELU and VH_FLAG_TANH_GELU (one MLP
+ *                   activation), VH_FLAG_MAP_HEAD (the head's own MLP block is not gated), VH_FLAG_CLS_TAIL, VH_FLAG_W8_E4M3 and
+ *                   VH_DTYPE_FP8 (an e4m3 h needs a rounding contract of its own and fc1 scales of width 2 M: the open step).
+ *   Blob tensors of a SWIGLU context: l{l}.fc1.weight is [2 M][D] and l{l}.fc1.bias is [2 M]; rows 0 .. M - 1 are the GATE (Hugging Face:
+ *   the first half of weights_in, or gate_proj), rows M .. 2 M - 1 the VALUE (the second half of weights_in, or up_proj).  fc2 stays
+ *   [D][M] + [D]; no other offset rule changes.  vh_init_weights_seeded fills the longer tensors from the same tensor ids (t + 12, t + 13).
+ *   THE FUNCTION, per layer and per row, with z = LN2(x) W1^T + b1 [2 M], g = z[0 .. M - 1], u = z[M .. 2 M - 1]:
+ *     x += (silu(g) * u) W2^T + b2,      silu(g) = g * sigmoid(g)
+ *   ROUNDING: fc1 stores z as 16-bit (one rounding MORE than a GELU model has: there the activation is applied to the fp32 accumulator);
+ *   the gate pass widens the stored g and u to fp32, computes r = rcp(1 + exp2(g * -log2(e))) on the hardware exp2 / rcp the QuickGELU
+ *   epilogue uses (1 ulp each) and h = (g * r) * u in fp32, and rounds ONCE (RNE) to the same 16-bit type: the h that fc2 reads.  g = 0
+ *   gives h = 0 for every finite u.  A row's bits depend on that row alone. */
+#define VH_FLAG_SWIGLU (1 << 25)
+
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
 
@@ -280,7 +298,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model, bit 23 = VH_FLAG_ROPE model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model, bit 23 = VH_FLAG_ROPE model, bit 25 = VH_FLAG_SWIGLU model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -300,7 +318,7 @@ int vh_export_weights_device(vh_ctx* ctx, void* dev_blob, size_t nbytes);
  *   vh_blob_file_config: host only (no device needed) -- validates magic / shape / file length and fills the model
  *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create;
  *                        cfg->flags = the model bits of the header: VH_FLAG_PRE_LN, VH_FLAG_QUICK_GELU, VH_FLAG_REGISTERS(n), VH_FLAG_NO_CLS,
- *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU, VH_FLAG_ROPE);
+ *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU, VH_FLAG_ROPE, VH_FLAG_SWIGLU);
  *   vh_save_weights_file: writes <path>.tmp then renames; vh_load_weights_file: verifies length, shape, checksum. */
 int vh_blob_file_config(const char* path, vh_config* cfg);
 /* host only: the file as a MEMORY blob (what vh_load_weights takes): length, header and checksum verified, checksum
@@ -1358,6 +1376,12 @@ int vh_op_map_pool(const void* hi_or_x32_dev, const void* lo_dev, int form, int 
  * is checked before a device is touched, each refusal with a message of its own. */
 int vh_op_rope(void* qkv16_dev, int dtype, int batch, int tokens, int heads, int head_dim, int lead, int64_t hm_rows,
                const float* cos_dev, const float* sin_dev, void* stream);
+/* The gate pass of a VH_FLAG_SWIGLU context on its own ("THE FUNCTION" at VH_FLAG_SWIGLU): gu16_dev [rows][2 * mlp_dim] row-major `dtype`
+ * (VH_DTYPE_BF16 / VH_DTYPE_FP16) elements, gate columns first -> h16_dev [rows][mlp_dim] = silu(g) * u of the same type: row-major
+ * (out_tiled = 0) or the 16-row-blocked operand layout [rows / 16][mlp_dim / 8][16][8] (out_tiled = 1; rows a multiple of 16).  mlp_dim is a
+ * multiple of 64; 16-byte accesses: both pointers are 16-byte aligned.  Nothing outside h16's rows * mlp_dim elements is written.  Every
+ * argument is checked before a device is touched, each refusal with a message of its own. */
+int vh_op_swiglu(const void* gu16_dev, int dtype, int64_t rows, int mlp_dim, void* h16_dev, int out_tiled, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,
  * 2 = constant `sigma` */
 int vh_op_fill(float* out_dev, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,

@@ -122,6 +122,12 @@ const char* rope_check(const void* qkv16, int dtype, int batch, int tokens, int 
                        const float* cos_t, const float* sin_t);
 hipError_t launch_rope(void* qkv16, int dtype, int batch, int tokens, int heads, int head_dim, int lead, int64_t hm_rows, const float* cos_t,
                        const float* sin_t, hipStream_t stream);
+// The gate pass of a SwiGLU MLP (kernels_swiglu.hip; contract: vithip.h VH_FLAG_SWIGLU, vh_op_swiglu): gu16 [rows][2 mlp_dim] row-major
+// (what fc1 writes with VH_EPI_LNFOLD / VH_EPI_BIAS and out_tiled = 0; gate columns first) -> h16 [rows][mlp_dim] = silu(g) * u, row-major
+// (out_tiled = 0) or in fc2's tiled operand layout [rows / 16][mlp_dim / 8][16][8] (out_tiled = 1: rows a multiple of 16).  Both
+// 16-byte aligned, mlp_dim a multiple of 64.  No allocation (graph capture, split batches).  swiglu_check: nullptr, or why.
+const char* swiglu_check(const void* gu16, int dtype, int64_t rows, int mlp_dim, const void* h16, int out_tiled);
+hipError_t launch_swiglu(const void* gu16, int dtype, int64_t rows, int mlp_dim, void* h16, int out_tiled, hipStream_t stream);
 const char* attention_readout_check(int batch, int heads, int Q, int tokens, int lead, int elem, int keys);
 hipError_t launch_attention_readout(const float* store, int batch, int heads, int Q, int tokens, int lead, int elem, int keys, void* probs_out,
                                     void* mean_out, hipStream_t stream);

@@ -60,13 +60,13 @@ struct BlobHeader {
     // bits 9 .. 13 = the number of register tokens (VH_FLAG_REGISTERS: the tensor reg), in the bits vh_config.flags keeps it in;
     // bit 15 = no class token (VH_FLAG_NO_CLS), bits 16 .. 17 = the pooling mode (VH_FLAG_POOL), bit 19 = the attention-pooling head
     // (VH_FLAG_MAP_HEAD: eleven more tensors), bit 21 = tanh GELU (VH_FLAG_TANH_GELU), bit 23 = rotary position embedding (VH_FLAG_ROPE: two
-    // more tensors, at the very end), likewise.
+    // more tensors, at the very end), bit 25 = SwiGLU MLP (VH_FLAG_SWIGLU: fc1 of every layer is [2 M][D] + [2 M]), likewise.
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
 constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobRegisters = VH_FLAG_REGISTERS_MASK,
-                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU, kBlobRope = VH_FLAG_ROPE,
-                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu | kBlobRope,   // at their vh_config.flags positions
+                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU, kBlobRope = VH_FLAG_ROPE, kBlobSwiglu = VH_FLAG_SWIGLU,
+                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu | kBlobRope | kBlobSwiglu,   // at their vh_config.flags positions
                    kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobSameBits;
 uint32_t blob_model_bits(const vh_config& c) {
     return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u) |
@@ -104,6 +104,9 @@ struct Layout {
     // VH_FLAG_ROPE: rope.cos / rope.sin [NP][hd / 2], the last two tensors of the blob (vithip.h)
     bool rope = false;
     size_t rope_cos = 0, rope_sin = 0;
+    // VH_FLAG_SWIGLU: fc1 of every layer is [M1][D] + [M1] with M1 = 2 M (gate rows, then value rows); M1 = M otherwise
+    bool swiglu = false;
+    int M1 = 0;
     std::vector<LayerOff> layer;
 };
 
@@ -118,6 +121,9 @@ Layout make_layout(const vh_config& c) {
     L.HW = L.pool == VH_POOL_CLS_AVG ? 2 * c.dim : c.dim;
     L.lead = L.ncls + L.R;
     L.T = L.NP + L.lead;
+    L.swiglu = (c.flags & VH_FLAG_SWIGLU) != 0;
+    L.M1 = L.swiglu ? 2 * c.mlp_dim : c.mlp_dim;
+    const size_t M1 = (size_t)L.M1;
     L.KP = c.patch_size * c.patch_size * c.channels;
     L.KPA = (L.KP + 63) / 64 * 64;
     size_t o = 0;
@@ -132,7 +138,7 @@ Layout make_layout(const vh_config& c) {
         p.qw = take(D * D); p.qb = take(D); p.kw = take(D * D); p.kb = take(D);
         p.vw = take(D * D); p.vb = take(D); p.ow = take(D * D); p.ob = take(D);
         p.ln2w = take(D); p.ln2b = take(D);
-        p.f1w = take(M * D); p.f1b = take(M); p.f2w = take(D * M); p.f2b = take(D);
+        p.f1w = take(M1 * D); p.f1b = take(M1); p.f2w = take(D * M); p.f2b = take(D);
     }
     L.lnfw = take(D); L.lnfb = take(D); L.headw = take(C * (size_t)L.HW); L.headb = take(C);
     L.map = (c.flags & VH_FLAG_MAP_HEAD) != 0;
@@ -151,7 +157,8 @@ size_t blob_bytes_of(const vh_config& c) {
     const size_t D = c.dim, M = c.mlp_dim, C = c.classes, g = (size_t)(c.image_size / c.patch_size);
     const size_t ncls = (c.flags & VH_FLAG_NO_CLS) ? 0 : 1, HW = VH_FLAG_POOL_OF(c.flags) == VH_POOL_CLS_AVG ? 2 * D : D;
     const size_t T = g * g + ncls + (size_t)VH_FLAG_REGISTERS_OF(c.flags), KP = (size_t)c.patch_size * c.patch_size * c.channels;   // (pos rows + reg rows)
-    const size_t per_layer = 2 * D + 4 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D);
+    const size_t M1 = (c.flags & VH_FLAG_SWIGLU) ? 2 * M : M;   // fc1's width (VH_FLAG_SWIGLU: gate and value rows)
+    const size_t per_layer = 2 * D + 4 * (D * D + D) + 2 * D + (M1 * D + M1) + (D * M + D);
     const size_t pre_ln = (c.flags & VH_FLAG_PRE_LN) ? 2 * D : 0;
     const size_t map = (c.flags & VH_FLAG_MAP_HEAD) ? (size_t)c.heads * D + 2 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D) : 0;
     const size_t rope = (c.flags & VH_FLAG_ROPE) ? 2 * g * g * (D / (size_t)c.heads / 2) : 0;
@@ -173,7 +180,14 @@ const char* check_config(const vh_config& c) {
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
     if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK |
-                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU | VH_FLAG_ROPE)) return "unknown bits in flags";
+                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU | VH_FLAG_ROPE | VH_FLAG_SWIGLU)) return "unknown bits in flags";
+    if (c.flags & VH_FLAG_SWIGLU) {
+        if (c.flags & (VH_FLAG_QUICK_GELU | VH_FLAG_TANH_GELU)) return "flags: VH_FLAG_SWIGLU excludes VH_FLAG_QUICK_GELU and VH_FLAG_TANH_GELU (one MLP activation)";
+        if (c.flags & VH_FLAG_MAP_HEAD) return "flags: VH_FLAG_SWIGLU excludes VH_FLAG_MAP_HEAD (the head's own MLP block is not gated)";
+        if (c.flags & VH_FLAG_CLS_TAIL) return "flags: VH_FLAG_SWIGLU excludes VH_FLAG_CLS_TAIL (the tail's class-row MLP has no gate pass)";
+        if (c.flags & VH_FLAG_W8_E4M3) return "flags: VH_FLAG_SWIGLU excludes VH_FLAG_W8_E4M3 (fc1's e4m3 scales are mlp_dim wide)";
+        if (c.dtype == VH_DTYPE_FP8) return "flags: VH_FLAG_SWIGLU excludes VH_DTYPE_FP8 (an e4m3 gated h has no rounding contract yet)";
+    }
     if ((c.flags & VH_FLAG_ROPE) && (c.flags & VH_FLAG_CLS_TAIL)) return "flags: VH_FLAG_ROPE excludes VH_FLAG_CLS_TAIL (the tail's one-query attention kernel reads unrotated q and k)";
     if ((c.flags & VH_FLAG_TANH_GELU) && (c.flags & VH_FLAG_QUICK_GELU)) return "flags: VH_FLAG_TANH_GELU and VH_FLAG_QUICK_GELU exclude each other (one MLP activation)";
     if (c.flags & VH_FLAG_MAP_HEAD) {   // (in front of the VH_FLAG_NO_CLS rules: NO_CLS + POOL_CLS is this head's own combination)
@@ -248,6 +262,7 @@ struct ActSet {
     void* qkv16 = nullptr;    //                 [B*T, 3D]
     void* att16 = nullptr;    //                 [B*T, D]
     void* h16 = nullptr;      //                 [B*T, M]
+    void* gu16 = nullptr;     // VH_FLAG_SWIGLU contexts only: fc1's output [B*T, 2 M] (gate | value), the gate pass's input
     void* col16 = nullptr;    // patch matrix    [B*NP, KPA]
     float* clsn32 = nullptr;  // the head's input [B, W] fp32: the final-LN'd CLS rows (W = D), or what the VH_FLAG_POOL mode computes (W = L.HW)
     float* pool32 = nullptr;  // [B, D] fp32 scratch of the pooled modes: CLS_AVG's LN'd class rows, AVG_FCNORM's raw mean
@@ -258,7 +273,7 @@ struct ActSet {
     float *mapz32 = nullptr, *maph32 = nullptr, *mapa32 = nullptr;
 };
 // byte offsets of a set's buffers from its base, and its size (vh_create computes them once; bind_set turns them into pointers)
-struct ActSetLayout { size_t x, xn, qkv, att, h, col, cls, pool, st, pt, xlo, tk, mz, mh, ma, bytes; };
+struct ActSetLayout { size_t x, xn, qkv, att, h, gu, col, cls, pool, st, pt, xlo, tk, mz, mh, ma, bytes; };
 
 struct vh_ctx {
     vh_config cfg;
@@ -286,6 +301,7 @@ struct vh_ctx {
     bool h_tiled = false;     // VH_H_TILED=0 (read when the context is created) keeps the row-major h (A/B, tests)
     bool att_tiled = true;    // VH_ATT_TILED=0 (read when the context is created) keeps the attention output row-major
     bool qkv_hm = true;       // VH_QKV_HM=0 keeps q|k|v row-major ([rows][3 D]) instead of head-major ([3][heads][rows][64]; needs att_tiled)
+    bool swiglu_skip = false; // VH_SWIGLU_SKIP=1 (measurement only, tools/swiglu_bench.py): a VH_FLAG_SWIGLU context leaves the gate pass out
     bool weights_ready_tiled = false;   // the tiled copies exist for the CURRENT weights (prepared with the fold on)
     float* bqkv = nullptr;    // [layers, 3D]
     // VH_DTYPE_FP8: the four per-layer matrices hold e4m3 bytes (in the same arena) + one fp32 scale per output channel;
@@ -295,7 +311,7 @@ struct vh_ctx {
     std::vector<float*> sqkv, so, s1, s2;
     // LayerNorm folded into the q|k|v and fc1 GEMMs (dim and mlp_dim multiples of 256):
     bool ln_fold = false;
-    float* fold_cd = nullptr; // per layer: cqkv[3D] dqkv[3D] c1[M] d1[M]
+    float* fold_cd = nullptr; // per layer: cqkv[3D] dqkv[3D] c1[M1] d1[M1] (M1 = fc1's width: M, or 2 M with VH_FLAG_SWIGLU)
     // with the fold: the residual stream lives as two planes, x = hi + lo (hi = the xn16 buffer = the GEMMs' 16-bit A operand,
     // lo = xlo16 = what that rounding dropped, one scaled e4m3 byte per element: vh_common.h Lo8): a residual GEMM then moves
     // 3 B per element each way instead of the fp32 array plus its 16-bit copy.
@@ -454,7 +470,7 @@ int set_device(std::string* err, int device) {
 int prepare_weights(vh_ctx* c) {
     const vh_config& f = c->cfg;
     const Layout& L = c->L;
-    const int D = f.dim, M = f.mlp_dim;
+    const int D = f.dim, M = f.mlp_dim, M1 = L.M1;   // M1: fc1's width (2 M on a VH_FLAG_SWIGLU context, which is never fp8 / W8)
     hipStream_t s = c->stream;
     const float* P = c->params;
     HIPCHK(&c->err, launch_permute_patch(P + L.patch_w, D, f.channels, f.patch_size, L.KPA, c->wp16, c->dt16, s));
@@ -512,17 +528,17 @@ int prepare_weights(vh_ctx* c) {
         const float* B = c->params;   // biases and LayerNorm parameters stay where they are
         if (c->ln_fold) {
             // W' = gamma o W (q rows also carry the softmax scale q_scale), c = row sums of W', d = beta.W + b
-            float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M);
+            float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M1);
             char* wq = (char*)c->wqkv16[l];
             const size_t dd2 = (size_t)D * D * 2;
             HIPCHK(&c->err, launch_fold_ln(P + o.qw, B + o.qb, B + o.ln1w, B + o.ln1b, D, D, c->q_scale, wq, cd, cd + 3 * D, f.dtype, s));
             HIPCHK(&c->err, launch_fold_ln(P + o.kw, B + o.kb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + dd2, cd + D, cd + 4 * D, f.dtype, s));
             HIPCHK(&c->err, launch_fold_ln(P + o.vw, B + o.vb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + 2 * dd2, cd + 2 * D, cd + 5 * D, f.dtype, s));
-            HIPCHK(&c->err, launch_fold_ln(P + o.f1w, B + o.f1b, B + o.ln2w, B + o.ln2b, M, D, 1.0f, c->w1_16[l], cd + 6 * D, cd + 6 * D + M, f.dtype, s));
+            HIPCHK(&c->err, launch_fold_ln(P + o.f1w, B + o.f1b, B + o.ln2w, B + o.ln2b, M1, D, 1.0f, c->w1_16[l], cd + 6 * D, cd + 6 * D + M1, f.dtype, s));
         } else {
             HIPCHK(&c->err, launch_pack_qkv(P + o.qw, B + o.qb, P + o.kw, B + o.kb, P + o.vw, B + o.vb, D, c->q_scale,
                                             c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, f.dtype, s));
-            HIPCHK(&c->err, launch_cast(P + o.f1w, c->w1_16[l], (int64_t)M * D, f.dtype, s));
+            HIPCHK(&c->err, launch_cast(P + o.f1w, c->w1_16[l], (int64_t)M1 * D, f.dtype, s));
         }
         HIPCHK(&c->err, launch_cast(P + o.ow, c->wo16[l], (int64_t)D * D, f.dtype, s));
         HIPCHK(&c->err, launch_cast(P + o.f2w, c->w2_16[l], (int64_t)D * M, f.dtype, s));
@@ -581,6 +597,9 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if ((h.flags ^ want) & kBlobTanhGelu)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 21 (tanh GELU) is %d, the context's VH_FLAG_TANH_GELU is %d",
                     (h.flags & kBlobTanhGelu) != 0, (want & kBlobTanhGelu) != 0);
+    if ((h.flags ^ want) & kBlobSwiglu)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 25 (SwiGLU MLP) is %d, the context's VH_FLAG_SWIGLU is %d",
+                    (h.flags & kBlobSwiglu) != 0, (want & kBlobSwiglu) != 0);
     if ((h.flags ^ want) & kBlobRope)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 23 (rotary position embedding) is %d, the context's VH_FLAG_ROPE is %d",
                     (h.flags & kBlobRope) != 0, (want & kBlobRope) != 0);
@@ -598,7 +617,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     c->last_set = set;
     const vh_config& f = c->cfg;
     const Layout& L = c->L;
-    const int D = f.dim, M = f.mlp_dim, T = L.T;
+    const int D = f.dim, M = f.mlp_dim, M1 = L.M1, T = L.T;   // M1: fc1's width (2 M on a VH_FLAG_SWIGLU context)
     const int64_t rows = (int64_t)batch * T;
     // Row count of the per-token GEMMs of the folded layer loop: rounded up to whole 256-row tiles when nothing lives behind
     // this part's rows in the arena (a single part, or the last of several; the arena itself is padded).  The persistent
@@ -623,6 +642,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     char* const qkv16 = (char*)A.qkv16 + r0 * 3 * D * esz;
     char* const att16 = (char*)A.att16 + r0 * D * esz_op;
     char* const h16 = (char*)A.h16 + r0 * M * esz_op;
+    char* const gu16 = L.swiglu ? (char*)A.gu16 + r0 * M1 * esz : nullptr;
     char* const col16 = (char*)A.col16 + (size_t)img0 * L.NP * L.KPA * esz;
     float* const clsn32 = A.clsn32 + (size_t)img0 * L.HW;   // this part's rows of the head's input [.][W]
     float* const pool32 = A.pool32 + (size_t)img0 * D;
@@ -730,13 +750,24 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         HIPCHK(&c->err, launch_rope(qkv16, dt16, batch, T, f.heads, c->head_dim, L.lead, hm_rows, P + L.rope_cos, P + L.rope_sin, s));
         return VH_OK;
     };
+    // VH_FLAG_SWIGLU: behind fc1, which wrote gu16 [rows][2 M] row-major, the gate pass leaves h16 = silu(g) * u in the layout fc2 reads
+    // (tiled under h_tiled's condition) -- one launch per layer.  Without the flag: no launch.  (No stage of its own, as for the rotation:
+    // the stage table is pinned; tools/swiglu_bench.py reports the pass as a step difference.  VH_SWIGLU_SKIP=1, read when the context
+    // is created, is that tool's switch: fc2 then reads whatever h16 holds, and the logits mean nothing.)
+    auto gate = [&](int64_t nrows, bool tiled) -> int {
+        if (!L.swiglu || c->swiglu_skip) return VH_OK;
+        HIPCHK(&c->err, launch_swiglu(gu16, dt16, nrows, M, h16, tiled ? 1 : 0, s));
+        return VH_OK;
+    };
     // Patch embedding: the im2col pass + the persistent GEMM.
     // VH_FLAG_PRE_LN: a LayerNorm needs whole rows, which no patch-GEMM tile holds -- such a context embeds through the fp32-x branch
     // and one pre_layernorm_kernel pass turns x into what its path consumes (no PATCH_SPLIT, no rowstats pass)
     const bool pre_ln = (f.flags & VH_FLAG_PRE_LN) != 0;
     const bool quick = (f.flags & VH_FLAG_QUICK_GELU) != 0, tanh_gelu = (f.flags & VH_FLAG_TANH_GELU) != 0;
-    const int epi_fc1 = quick ? VH_EPI_LNFOLD_QGELU : tanh_gelu ? VH_EPI_LNFOLD_TGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
-    const int epi_fc1_plain = quick ? VH_EPI_BIAS_QGELU : tanh_gelu ? VH_EPI_BIAS_TGELU : VH_EPI_BIAS_GELU;       // plain layer loop
+    // VH_FLAG_SWIGLU: fc1 keeps the GEMMs' plain epilogues (no activation) and writes gu16 row-major; the gate pass behind it makes h16
+    const bool swiglu = L.swiglu;
+    const int epi_fc1 = swiglu ? VH_EPI_LNFOLD : quick ? VH_EPI_LNFOLD_QGELU : tanh_gelu ? VH_EPI_LNFOLD_TGELU : VH_EPI_LNFOLD_GELU;          // folded layer loop
+    const int epi_fc1_plain = swiglu ? VH_EPI_BIAS : quick ? VH_EPI_BIAS_QGELU : tanh_gelu ? VH_EPI_BIAS_TGELU : VH_EPI_BIAS_GELU;       // plain layer loop
     // the patch embedding lands directly in the split residual's planes (below): the 16-bit split path without a pre-LayerNorm
     const bool patch_split = c->split && !c->fp8 && nl > 0 && !pre_ln;
     // (no stage bracket: the profile event is recorded once, behind the pass)
@@ -808,7 +839,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     c->last_qkv_hm = qkv_hm && nl > 0 && c->ln_fold;
     for (int l = 0; l < nl && c->ln_fold; ++l) {
         const LayerOff& o = L.layer[l];
-        const float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M);
+        const float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M1);
         const int nblk = D / 64;
         // e4m3 operands: the weight matrices' per-output-channel scales
         const float *sq = c->fp8 ? c->sqkv[l] : nullptr, *so = c->fp8 ? c->so[l] : nullptr;
@@ -868,10 +899,11 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
         if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
         // h in its tiled layout: written straight from fc1's registers, read by fc2's DMA (same values, same bits)
-        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], cd + 6 * D + M, h16, rows_g, M, D, epi_fc1, cd + 6 * D);
+        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], cd + 6 * D + M1, swiglu ? gu16 : h16, rows_g, M1, D, epi_fc1, cd + 6 * D);
         g1.wscale = s1;
-        set_tiled(g1, h_tiled, false);
+        set_tiled(g1, h_tiled && !swiglu, false);
         if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
+        if ((rc = gate(rows_g, h_tiled))) return rc;
         GemmArgs g2 = gemm_args(op_dt, h16, h_tiled ? c->w2t_16[l] : c->w2_16[l], P + o.f2b, c->split ? (void*)xn16 : x, rows_g, D, M,
                                 c->split ? VH_EPI_RESID_SPLIT : (l + 1 < nl ? VH_EPI_RESID_LN : VH_EPI_BIAS_RESID));
         g2.out16 = c->split ? xlo16 : xn16;
@@ -914,9 +946,10 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
              })))
             return rc;
         if ((rc = resid_gemm_ln(att16, c->wo16[l], P + o.ob, so, D, P + o.ln2w, P + o.ln2b, ST_PROJ))) return rc;
-        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], P + o.f1b, h16, rows, M, D, epi_fc1_plain);
+        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], P + o.f1b, swiglu ? gu16 : h16, rows, M1, D, epi_fc1_plain);
         g1.wscale = s1;
         if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
+        if ((rc = gate(rows, false))) return rc;
         const bool more = l + 1 < nl;   // the next layer's LN1 follows this layer's fc2
         if ((rc = resid_gemm_ln(h16, c->w2_16[l], P + o.f2b, s2, M, more ? P + L.layer[l + 1].ln1w : nullptr,
                                 more ? P + L.layer[l + 1].ln1b : nullptr, ST_FC2))) return rc;
@@ -1094,7 +1127,8 @@ int guard_calibrate(vh_ctx* c) {
 }
 
 // ---- two forwards in flight ---------------------------------------------------------------------------------------------
-void bind_set(ActSet& a, char* base, const ActSetLayout& o, bool map) {
+void bind_set(ActSet& a, char* base, const ActSetLayout& o, bool map, bool swiglu) {
+    if (swiglu) a.gu16 = base + o.gu;
     a.x = (float*)(base + o.x); a.xn16 = base + o.xn; a.qkv16 = base + o.qkv; a.att16 = base + o.att; a.h16 = base + o.h;
     a.col16 = base + o.col; a.clsn32 = (float*)(base + o.cls); a.pool32 = (float*)(base + o.pool);
     a.stats = (float*)(base + o.st); a.partials = (float*)(base + o.pt); a.xlo16 = base + o.xlo;
@@ -1113,7 +1147,7 @@ bool second_set(vh_ctx* c) {
         return false;
     }
     c->act[1].base = p;
-    bind_set(c->act[1], p, c->act_layout, c->L.map);
+    bind_set(c->act[1], p, c->act_layout, c->L.map, c->L.swiglu);
     return true;
 }
 // May consecutive forwards of this context run two at a time?  Not where a launch is timed (a duration beside another forward's
@@ -1479,7 +1513,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     }
     c->device = device;
     const Layout& L = c->L;
-    const size_t D = cfg->dim, M = cfg->mlp_dim, C = cfg->classes, B = cfg->max_batch;
+    const size_t D = cfg->dim, M = cfg->mlp_dim, M1 = (size_t)L.M1, C = cfg->classes, B = cfg->max_batch;   // M1: fc1's width (2 M with VH_FLAG_SWIGLU)
     const size_t rows = B * (size_t)L.T;
     auto bail = [&](int code) { vh_destroy(c); return code; };
 #define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return bail(VH_ERR_HIP); } } while (0)
@@ -1522,7 +1556,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     const bool want_tiled = cfg->dtype != VH_DTYPE_FP8 && want_tiled_any;
     const bool want_tiled8 = cfg->dtype == VH_DTYPE_FP8 && want_tiled_any;   // e4m3 operands: fc2's weights (bytes) in the tiled e4m3 layout
     for (int l = 0; l < cfg->layers; ++l) {
-        o_qkv[l] = carve16(3 * D * D); o_o[l] = carve16(D * D); o_1[l] = carve16(M * D); o_2[l] = carve16(D * M);
+        o_qkv[l] = carve16(3 * D * D); o_o[l] = carve16(D * D); o_1[l] = carve16(M1 * D); o_2[l] = carve16(D * M);
         o_2t[l] = want_tiled ? carve16(D * M) : want_tiled8 ? carve16((D * M + 1) / 2) : 0;
     }
     std::vector<size_t> o_ot(cfg->layers);
@@ -1564,11 +1598,12 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         c->h_tiled = want_tiled || want_tiled8;
         { const char* e = getenv("VH_ATT_TILED"); c->att_tiled = !(e && e[0] == '0'); }
         { const char* e = getenv("VH_QKV_HM"); c->qkv_hm = !(e && e[0] == '0'); }
+        { const char* e = getenv("VH_SWIGLU_SKIP"); c->swiglu_skip = e && e[0] == '1'; }
     }
     CK(hipHostMalloc((void**)&c->guard_host, 64, hipHostMallocDefault));
     *c->guard_host = 0.f;
     const size_t o_cd = w16_bytes;
-    w16_bytes += align_up((size_t)cfg->layers * (6 * D + 2 * M) * 4, 256);
+    w16_bytes += align_up((size_t)cfg->layers * (6 * D + 2 * M1) * 4, 256);
     const size_t o_sc = w16_bytes, sc_per_layer = 5 * D + M;  // fp8: scales of q|k|v (3D), o (D), fc1 (M), fc2 (D)
     if (c->fp8) w16_bytes += align_up((size_t)cfg->layers * sc_per_layer * 4, 256);
     CK(hipMalloc((void**)&c->w16, w16_bytes));
@@ -1600,13 +1635,14 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     // VH_FLAG_MAP_HEAD: z, the hidden rows, and the rows a | o
     o.mz = L.map ? carve(B * (size_t)cfg->heads * D * 4) : 0; o.mh = L.map ? carve(B * (M > D ? M : D) * 4) : 0;
     o.ma = L.map ? carve(B * 2 * D * 4) : 0;
+    o.gu = L.swiglu ? carve(rows_p * 2 * M * 2) : 0;   // VH_FLAG_SWIGLU: fc1's [rows][2 M] output, in both sets (part of o.bytes)
     o.bytes = a;
     const size_t o_in = carve(B * (size_t)cfg->image_size * cfg->image_size * cfg->channels * 4), o_lg = carve(B * C * 4),
                  o_gd = carve(256);     // the LayerNorm-fold guard word
     CK(hipMalloc((void**)&c->arena, a));
     c->guard_dev = (unsigned int*)(c->arena + o_gd);
     CK(hipMemsetAsync(c->guard_dev, 0, 256, c->stream));
-    bind_set(c->act[0], c->arena, o, L.map);
+    bind_set(c->act[0], c->arena, o, L.map, L.swiglu);
     c->in_dev = (float*)(c->arena + o_in); c->logits_dev = (float*)(c->arena + o_lg);
 #undef CK
     *out = c;
@@ -1750,7 +1786,7 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
         GEN(o.vw, D * D, t + 6, sw, 0.f); GEN(o.vb, D, t + 7, sb, 0.f);
         GEN(o.ow, D * D, t + 8, sw, 0.f); GEN(o.ob, D, t + 9, sb, 0.f);
         GEN(o.ln2w, D, t + 10, sg, 1.f); GEN(o.ln2b, D, t + 11, sb, 0.f);
-        GEN(o.f1w, M * D, t + 12, sw, 0.f); GEN(o.f1b, M, t + 13, sb, 0.f);
+        GEN(o.f1w, (size_t)L.M1 * D, t + 12, sw, 0.f); GEN(o.f1b, (size_t)L.M1, t + 13, sb, 0.f);   // (VH_FLAG_SWIGLU: 2 M rows, same tensor ids)
         GEN(o.f2w, D * M, t + 14, sw, 0.f); GEN(o.f2b, D, t + 15, sb, 0.f);
     }
     GEN(L.lnfw, D, TID_FINAL + 0, sg, 1.f); GEN(L.lnfb, D, TID_FINAL + 1, sb, 0.f);
@@ -3410,6 +3446,14 @@ int vh_op_rope(void* qkv16, int dtype, int batch, int tokens, int heads, int hea
     hipError_t e = launch_rope(qkv16, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_t, sin_t, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "rope failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the VH_FLAG_SWIGLU gate pass on caller-made fc1 output
+int vh_op_swiglu(const void* gu16, int dtype, int64_t rows, int mlp_dim, void* h16, int out_tiled, void* stream) {
+    if (const char* why = swiglu_check(gu16, dtype, rows, mlp_dim, h16, out_tiled)) return fail(nullptr, VH_ERR_INVALID, "swiglu: %s", why);
+    hipError_t e = launch_swiglu(gu16, dtype, rows, mlp_dim, h16, out_tiled, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "swiglu failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 int vh_op_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind, float sigma, void* stream) {

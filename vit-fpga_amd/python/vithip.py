@@ -54,6 +54,11 @@ FLAG_MAP_HEAD, FLAG_TANH_GELU, MAP_MAX_HEADS = 1 << 19, 1 << 21, 16
 # every layer by the blob's last two tensors rope.cos / rope.sin [NP][head_dim / 2]; excludes FLAG_CLS_TAIL
 FLAG_ROPE = 1 << 23
 
+# SwiGLU MLP (VH_FLAG_SWIGLU; vithip.h): a model bit, in the blob header too.  mlp_dim = M is the gated width; fc1 of every layer is
+# [2 M, dim] + [2 M] (gate rows, then value rows) and h = silu(g) * u is made by a pass of its own behind fc1.  Excludes FLAG_QUICK_GELU,
+# FLAG_TANH_GELU, FLAG_MAP_HEAD, FLAG_CLS_TAIL, FLAG_W8_E4M3 and DTYPE_FP8
+FLAG_SWIGLU = 1 << 25
+
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
 EPI_BIAS_QGELU, EPI_LNFOLD_QGELU = 10, 11
@@ -352,6 +357,7 @@ SYMBOLS = {
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "vh_op_map_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i, _vp, _vp]),
     "vh_op_rope": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "vh_op_swiglu": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
     "vh_group_create": (_i, [C.POINTER(Config), _pi, _i, C.POINTER(_vp)]),
@@ -419,7 +425,7 @@ def blob_file_config(path):
 
 def blob_file_flags(path):
     """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN, FLAG_QUICK_GELU, FLAG_REGISTERS(n), FLAG_NO_CLS,
-    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU, FLAG_ROPE); host only."""
+    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU, FLAG_ROPE, FLAG_SWIGLU); host only."""
     c = Config()
     _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
     return c.flags
@@ -428,7 +434,7 @@ def blob_file_flags(path):
 # The header's flags word (byte 52) carries the model bits of vh_config flags: these two at header positions of their own, the rest at
 # their flag positions (bit 0 of the word belongs to the file form's checksum).
 _HEADER_BITS = ((FLAG_PRE_LN, 2), (FLAG_QUICK_GELU, 4))
-_SAME_BITS = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE
+_SAME_BITS = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE | FLAG_SWIGLU
 
 
 def _blob_bits(flags):
@@ -464,7 +470,8 @@ def blob_tensor_table(cfg, flags=0):
         t.append(("reg", (R, D)))
     if flags & FLAG_PRE_LN:
         t += [("pre_ln.weight", (D,)), ("pre_ln.bias", (D,))]
-    rows = {"ln1": (D,), "q": (D, D), "k": (D, D), "v": (D, D), "o": (D, D), "ln2": (D,), "fc1": (M, D), "fc2": (D, M)}
+    rows = {"ln1": (D,), "q": (D, D), "k": (D, D), "v": (D, D), "o": (D, D), "ln2": (D,),
+            "fc1": (2 * M if flags & FLAG_SWIGLU else M, D), "fc2": (D, M)}   # FLAG_SWIGLU: gate rows, then value rows
     for l in range(cfg["layers"]):
         for n, shape in rows.items():
             t += [(f"l{l}.{n}.weight", shape), (f"l{l}.{n}.bias", shape[:1])]
@@ -547,6 +554,41 @@ def _register_count(me, cfg, sd, key):
     return R
 
 
+def _gated_mlp(me, take, sd, cfg, l, gate, up, down, lname):
+    """The four MLP tensors of layer l of a FLAG_SWIGLU blob from a gated checkpoint.  gate / up: (tensor name stem, first row, rows) of
+    the two halves of fc1 (one tensor `weights_in`, or `gate_proj` and `up_proj`); down: fc2's stem; LayerScale `lname` is folded into
+    fc2 in float64, one rounding.  A hidden width M' that is no multiple of 64 is zero-padded to cfg['mlp_dim'], a larger multiple of 64:
+    gate rows, value rows, both bias halves and fc2's columns -- exact, silu(0) * 0 = 0 meets zero columns.  Any other width is refused."""
+    D, M = cfg["dim"], cfg["mlp_dim"]
+    if down + ".weight" not in sd:
+        raise KeyError(f"{me}: missing tensor {down}.weight")
+    Mc = int(np.asarray(sd[down + ".weight"]).shape[-1])
+    if Mc != M and not (Mc % 64 and M > Mc and M % 64 == 0):
+        raise ValueError(f"{me}: {down}.weight has a hidden width of {Mc}, cfg['mlp_dim'] is {M}"
+                         " (only a width that is no multiple of 64 is zero-padded, to a larger multiple of 64)")
+    w1, b1 = np.zeros((2 * M, D), np.float32), np.zeros(2 * M, np.float32)
+    for half, (stem, r0, total) in enumerate((gate, up)):
+        w1[half * M:half * M + Mc] = take(stem + ".weight", (total, D)).reshape(total, D)[r0:r0 + Mc]
+        b1[half * M:half * M + Mc] = take(stem + ".bias", (total,))[r0:r0 + Mc]
+    w2c, b2 = _scaled(take, sd, D, Mc, down, lname)
+    w2 = np.zeros((D, M), np.float32)
+    w2[:, :Mc] = w2c.reshape(D, Mc)
+    return {f"l{l}.fc1.weight": w1, f"l{l}.fc1.bias": b1, f"l{l}.fc2.weight": w2, f"l{l}.fc2.bias": b2}
+
+
+def _gated_names(me, sd, swiglu, plain, gated):
+    """The refusals both DINO converters share, once swiglu=True is given: the checkpoint must have every name stem of `gated` in some
+    layer and none of `plain`."""
+    has = lambda stem: any(k.endswith(stem + ".weight") for k in sd)
+    if not swiglu:
+        return
+    if has(plain) and any(has(g) for g in gated):
+        raise ValueError(f"{me}: the checkpoint has both {plain} and a gated MLP ({gated[0]}): one of them is not this model's")
+    missing = [g for g in gated if not has(g)]
+    if missing:
+        raise ValueError(f"{me}: swiglu=True, but the checkpoint has no {missing[0]}")
+
+
 def _check_dino_args(me, cfg, pool):
     if pool not in (POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM, POOL_CLS_AVG):
         raise ValueError(f"{me}: pool = {pool} is not POOL_CLS, POOL_AVG_NORM, POOL_AVG_FCNORM or POOL_CLS_AVG")
@@ -587,7 +629,7 @@ def blob_from_clip_state_dict(sd, cfg, ln_eps=1e-5):
     return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
-def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
+def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS, swiglu=False):
     """Canonical blob of a DINOv2 backbone from a dict of arrays under the Hugging Face `Dinov2Model` /
     `Dinov2WithRegistersModel` parameter names (numpy only; torch tensors: `{k: v.numpy() for k, v in model.state_dict().items()}`).
     `cfg`: the model shape, `registers` = the number of register tokens (0 for the models without), classes = the head's width.
@@ -600,7 +642,11 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
     `Dinov2WithRegistersForImageClassification`: head(concat(cls, mean of the patch tokens)), head weight [classes, 2 dim], the
     class-token half first).  A state dict of those models is taken as it is: the `dinov2.` / `dinov2_with_registers.` prefix is
     dropped and `classifier.*` is the head unless `head` is given.  The head's shape is checked against the mode ([classes, dim]
-    for POOL_CLS / POOL_AVG_NORM / POOL_AVG_FCNORM); the header carries FLAG_POOL(pool)."""
+    for POOL_CLS / POOL_AVG_NORM / POOL_AVG_FCNORM); the header carries FLAG_POOL(pool).
+    swiglu=True (DINOv2-g/14, `use_swiglu_ffn`): a FLAG_SWIGLU blob from `mlp.weights_in.{weight, bias}` [2 M', dim] (gate half first)
+    and `mlp.weights_out.{weight, bias}`; cfg['mlp_dim'] is the gated width M', or a larger multiple of 64 where M' is none (688 -> 704, or 768
+    to reach the folded loop; the padding is zeros, and exact: _gated_mlp).  Refused by name: a checkpoint with `mlp.fc1` beside the gated names, or without one of
+    them.  Without swiglu=True a gated checkpoint is refused as before."""
     me = "blob_from_dinov2_state_dict"
     _check_dino_args(me, cfg, pool)
     for prefix in ("dinov2.", "dinov2_with_registers."):
@@ -610,8 +656,9 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
             sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
     D, M, E = cfg["dim"], cfg["mlp_dim"], cfg["classes"]
     NP = (cfg["image_size"] // cfg["patch_size"]) ** 2
-    if any(k.endswith("mlp.weights_in.weight") for k in sd):
+    if not swiglu and any(k.endswith("mlp.weights_in.weight") for k in sd):
         raise ValueError(f"{me}: the checkpoint has a SwiGLU MLP (mlp.weights_in), which this library does not run")
+    _gated_names(me, sd, swiglu, "mlp.fc1", ("mlp.weights_in", "mlp.weights_out"))
     emb = "embeddings."
     R = _register_count(me, cfg, sd, emb + "register_tokens")
     if emb + "position_embeddings" in sd:
@@ -619,16 +666,21 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS):
         if rows != NP + 1:
             raise ValueError(f"{me}: {emb}position_embeddings has {rows} rows, cfg needs NP + 1 = {NP + 1} "
                              "(interpolate the table to the image size first)")
-    flags = FLAG_REGISTERS(R) | FLAG_POOL(pool)
+    flags = FLAG_REGISTERS(R) | FLAG_POOL(pool) | (FLAG_SWIGLU if swiglu else 0)
     take = _taker(sd, me)
     top = {"patch.weight": emb + "patch_embeddings.projection.weight", "patch.bias": emb + "patch_embeddings.projection.bias",
            "cls": (emb + "cls_token", (1, 1, D)), "pos": (emb + "position_embeddings", (1, NP + 1, D)),
            "reg": (emb + "register_tokens", (1, R, D)), "lnf.weight": "layernorm.weight", "lnf.bias": "layernorm.bias"}
-    t = _take_named(take, cfg, flags, top, "encoder.layer.{}.", _DINOV2_LAYER)
+    t = _take_named(take, cfg, flags, top, "encoder.layer.{}.", {k: v for k, v in _DINOV2_LAYER.items() if not (swiglu and k == "fc1")})
     for l in range(cfg["layers"]):
         b = f"encoder.layer.{l}."
         t[f"l{l}.o.weight"], t[f"l{l}.o.bias"] = _scaled(take, sd, D, D, b + "attention.output.dense", b + "layer_scale1.lambda1")
-        t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.fc2", b + "layer_scale2.lambda1")
+        if swiglu:
+            Mc = int(np.asarray(sd[b + "mlp.weights_out.weight"]).shape[-1]) if b + "mlp.weights_out.weight" in sd else M
+            t.update(_gated_mlp(me, take, sd, cfg, l, (b + "mlp.weights_in", 0, 2 * Mc), (b + "mlp.weights_in", Mc, 2 * Mc), b + "mlp.weights_out",
+                                b + "layer_scale2.lambda1"))
+        else:
+            t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.fc2", b + "layer_scale2.lambda1")
     t["head.weight"], t["head.bias"] = _head(me, head, E, 2 * D if pool == POOL_CLS_AVG else D)
     return _pack_blob(me, cfg, ln_eps, flags, t)
 
@@ -703,7 +755,7 @@ def rope_tables_dinov3(grid, head_dim, theta=100.0):
     return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
 
 
-def blob_from_dinov3_state_dict(sd, cfg, ln_eps=1e-5, head=None, pool=POOL_CLS, theta=100.0):
+def blob_from_dinov3_state_dict(sd, cfg, ln_eps=1e-5, head=None, pool=POOL_CLS, theta=100.0, swiglu=False):
     """Canonical blob of a DINOv3 ViT-S/B/L backbone from a dict of arrays under the Hugging Face `DINOv3ViTModel` parameter names
     (numpy only): `embeddings.{cls_token, register_tokens, patch_embeddings.{weight, bias}}`, `model.layer.N.` or `layer.N.` +
     `{norm1, attention.{q,k,v,o}_proj, layer_scale1.lambda1, norm2, mlp.{up,down}_proj, layer_scale2.lambda1}`, `norm`.
@@ -713,29 +765,38 @@ def blob_from_dinov3_state_dict(sd, cfg, ln_eps=1e-5, head=None, pool=POOL_CLS, 
     rope_tables_dinov3(grid, head dim, theta).  The head is zero unless head = (weight [classes, dim], bias [classes]) is given; with
     an identity head `vh_read_features(VH_FEAT_NORM)` / debug tap 1 is the model's `pooler_output` (the normalised class token).
     Header flags: FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool).  Refused by name: a gated MLP (mlp.gate_proj: the H+ and 7B
-    checkpoints), a register count other than cfg['registers'], a missing or wrongly shaped tensor."""
+    checkpoints), a register count other than cfg['registers'], a missing or wrongly shaped tensor.
+    swiglu=True (ViT-H+/16 and 7B, `use_gated_mlp` with hidden_act = "silu"): a FLAG_ROPE | FLAG_SWIGLU blob; fc1 = `mlp.gate_proj` rows, then
+    `mlp.up_proj` rows, fc2 = `mlp.down_proj`; cfg['mlp_dim'] is `intermediate_size` (or a larger multiple of 64 where it is none: zero
+    padding, exact).  Refused by name: `mlp.fc1` beside the gated names, a missing gate_proj / up_proj / down_proj.  Without swiglu=True a
+    gated checkpoint is refused as before."""
     me = "blob_from_dinov3_state_dict"
     _check_dino_args(me, cfg, pool)
     D, M, E, H = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["heads"]
     g = cfg["image_size"] // cfg["patch_size"]
-    if any(k.endswith("mlp.gate_proj.weight") for k in sd):
+    if not swiglu and any(k.endswith("mlp.gate_proj.weight") for k in sd):
         raise ValueError(f"{me}: the checkpoint has a gated MLP (mlp.gate_proj), which this library does not run")
+    _gated_names(me, sd, swiglu, "mlp.fc1", ("mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"))
     emb = "embeddings."
     R = _register_count(me, cfg, sd, emb + "register_tokens")
     pre = "model.layer." if any(k.startswith("model.layer.") for k in sd) else "layer."
-    flags = FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool)
+    flags = FLAG_ROPE | FLAG_REGISTERS(R) | FLAG_POOL(pool) | (FLAG_SWIGLU if swiglu else 0)
     take = _taker(sd, me)
     top = {"patch.weight": emb + "patch_embeddings.weight", "patch.bias": emb + "patch_embeddings.bias", "cls": (emb + "cls_token", (1, 1, D)),
            "reg": (emb + "register_tokens", (1, R, D)), "lnf.weight": "norm.weight", "lnf.bias": "norm.bias"}
     no_key_bias = [f"l{l}.k.bias" for l in range(cfg["layers"]) if f"{pre}{l}.attention.k_proj.bias" not in sd]      # key_bias=False: zeros
     top.update(dict.fromkeys(no_key_bias))
-    t = _take_named(take, cfg, flags, top, pre + "{}.", _DINOV3_LAYER)
+    t = _take_named(take, cfg, flags, top, pre + "{}.", {k: v for k, v in _DINOV3_LAYER.items() if not (swiglu and k == "fc1")})
     t.update({n: np.zeros(D, np.float32) for n in no_key_bias})
     t["pos"] = np.zeros((g * g + 1) * D, np.float32)                                      # the model has no position table
     for l in range(cfg["layers"]):
         b = f"{pre}{l}."
         t[f"l{l}.o.weight"], t[f"l{l}.o.bias"] = _scaled(take, sd, D, D, b + "attention.o_proj", b + "layer_scale1.lambda1")
-        t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.down_proj", b + "layer_scale2.lambda1")
+        if swiglu:
+            Mc = int(np.asarray(sd[b + "mlp.down_proj.weight"]).shape[-1]) if b + "mlp.down_proj.weight" in sd else M
+            t.update(_gated_mlp(me, take, sd, cfg, l, (b + "mlp.gate_proj", 0, Mc), (b + "mlp.up_proj", 0, Mc), b + "mlp.down_proj", b + "layer_scale2.lambda1"))
+        else:
+            t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.down_proj", b + "layer_scale2.lambda1")
     t["head.weight"], t["head.bias"] = _head(me, head, E, 2 * D if pool == POOL_CLS_AVG else D)
     t["rope.cos"], t["rope.sin"] = rope_tables_dinov3(g, D // H, theta)
     return _pack_blob(me, cfg, ln_eps, flags, t)
@@ -2331,6 +2392,12 @@ def op_rope(qkv_ptr, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_p
     q|k|v at qkv_ptr (`dtype` elements; hm_rows = 0: row-major [batch * tokens, 3 * heads * head_dim], else head-major
     [3, heads, hm_rows, 64]) are rotated by the fp32 tables cos / sin [tokens - lead, head_dim / 2]."""
     _check(lib().vh_op_rope(qkv_ptr, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_ptr, sin_ptr, None))
+
+
+def op_swiglu(gu_ptr, dtype, rows, mlp_dim, h_ptr, out_tiled=False):
+    """The VH_FLAG_SWIGLU gate pass on its own (vh_op_swiglu): gu [rows, 2 * mlp_dim] row-major `dtype` elements (gate columns first) ->
+    h = silu(g) * u [rows, mlp_dim], row-major or (out_tiled; rows a multiple of 16) in the layout unpack_tiled reads."""
+    _check(lib().vh_op_swiglu(gu_ptr, dtype, rows, mlp_dim, h_ptr, 1 if out_tiled else 0, None))
 
 
 def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr, dtype):
