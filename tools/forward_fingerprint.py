@@ -5,8 +5,9 @@
 
 For every context below -- the smallest at which each branch of enqueue_forward is taken -- it prints one line: the SHA-256 of the
 logits of a seeded batch (init_weights_seeded(0), fill_input_seeded(1, ...)), debug taps 3 and 4 (tiled hidden activation,
-head-major q|k|v) and the stages of profile_forward that recorded events, with their counts.  Two builds agree
-when the two outputs are the same text.  Every context runs in a child process of its own (VH_GEMM_PP and the other knobs are read
+head-major q|k|v) and the stages of profile_forward that recorded events, with their counts.  The "readout" contexts add the
+SHA-256 of what the read-outs return for listed layers (read_outs below); "inflight" runs four steps of one asynchronous call, so
+both activation sets and both compute streams take part.  Two builds agree when the two outputs are the same text.  Every context runs in a child process of its own (VH_GEMM_PP and the other knobs are read
 once per process or per context); the first child that fails ends the run.
 """
 import argparse
@@ -19,7 +20,11 @@ import sys
 import numpy as np
 
 BF16, FP16, FP8 = 0, 1, 2
-LN_FOLD_OFF, CLS_TAIL, PRE_LN, QUICK_GELU = 1, 8, 16, 32
+LN_FOLD_OFF, LN_FOLD_ON, W8_E4M3, CLS_TAIL, PRE_LN, QUICK_GELU = 1, 2, 4, 8, 16, 32
+NO_CLS, MAP_HEAD, TANH_GELU, ROPE, SWIGLU = 1 << 15, 1 << 19, 1 << 21, 1 << 23, 1 << 25
+POOL_AVG_NORM, POOL_CLS_AVG = 1 << 16, 3 << 16
+REGISTERS_4 = 4 << 9
+FEAT_NORM, FEAT_RAW = 0, 1   # vh_features.norm: through the final LayerNorm / the residual stream as it is
 
 # name: (dtype, batch, flags, environment, extra)
 CONTEXTS = {
@@ -43,9 +48,41 @@ CONTEXTS = {
     "fp16_b4_graph": (FP16, 4, 0, {}, "graph"),
     "fp16_b256_gemm_pp_5": (FP16, 256, 0, {"VH_GEMM_PP": "5"}, None),
     "fp16_b256_gemm_pp_7": (FP16, 256, 0, {"VH_GEMM_PP": "7"}, None),
+    # one context per model family (LN_FOLD_ON: the guard cannot change the path)
+    "fp16_b256_swiglu": (FP16, 256, LN_FOLD_ON | SWIGLU, {}, None),
+    "fp16_b256_rope": (FP16, 256, LN_FOLD_ON | ROPE, {}, None),
+    "fp16_b256_registers_4": (FP16, 256, LN_FOLD_ON | REGISTERS_4, {}, None),
+    "fp16_b256_no_cls_avg_norm": (FP16, 256, LN_FOLD_ON | NO_CLS | POOL_AVG_NORM, {}, None),
+    "fp16_b256_cls_avg": (FP16, 256, LN_FOLD_ON | POOL_CLS_AVG, {}, None),
+    "fp16_b256_map_head": (FP16, 256, LN_FOLD_ON | NO_CLS | MAP_HEAD | TANH_GELU, {}, None),
+    "fp16_b256_w8": (FP16, 256, LN_FOLD_ON | W8_E4M3, {}, None),
+    "fp16_b32_inflight": (FP16, 32, 0, {}, "inflight"),
+    "fp16_b32_readout": (FP16, 32, LN_FOLD_ON, {}, "readout"),
+    "fp16_b32_plain_readout": (FP16, 32, LN_FOLD_OFF, {}, "readout"),
+    "fp8_b32_readout": (FP8, 32, LN_FOLD_ON, {}, "readout"),
 }
 VIT_BASE = dict(image_size=224, patch_size=16, channels=3, dim=768, heads=12, mlp_dim=3072, layers=12, classes=1000)
 CFG_KEYS = ("image_size", "patch_size", "channels", "dim", "heads", "mlp_dim", "layers", "classes")
+
+
+READOUT_LAYERS = [6, 12]
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def read_outs(ctx, batch, cfg):
+    """What the read-outs of the last forward return, hashed: the two debug taps, cls / patch / mean of the listed layers (fp32,
+    raw and normalised) and their class-token attention."""
+    tokens, dim = ctx.features_dims()[1], cfg["dim"]
+    out = [f"tap0 {sha(ctx.debug_read(0, batch * tokens * dim))}", f"tap1 {sha(ctx.debug_read(1, batch * dim))}"]
+    for k in READOUT_LAYERS:
+        for label, norm in (("raw", FEAT_RAW), ("norm", FEAT_NORM)):
+            f = ctx.read_layer_features(k, cls=True, patch=True, mean=True, norm=norm)
+            out += [f"layer{k}.{label}.{key} {sha(f[key])}" for key in ("cls", "patch", "mean")]
+        out.append(f"attention{k} {sha(ctx.read_attention(k)['probs'])}")
+    return out
 
 
 def run_context(tree, name):
@@ -67,14 +104,22 @@ def run_context(tree, name):
         ctx.set_streams(2)
     if extra == "graph":
         ctx.set_graph(True)
+    if extra == "readout":
+        ctx.set_feature_layers(READOUT_LAYERS)
+        ctx.set_attention_layers(READOUT_LAYERS)
     shas = []
     for _ in range(3 if extra == "graph" else 1):
-        ctx.forward_device(x.ptr, batch, y.ptr)
-        shas.append(hashlib.sha256(y.to_numpy(np.float32, (batch, cfg["classes"])).tobytes()).hexdigest())
+        if extra == "inflight":
+            ctx.forward_device_async(x.ptr, batch, y.ptr, steps=4)
+            ctx.synchronize()
+        else:
+            ctx.forward_device(x.ptr, batch, y.ptr)
+        shas.append(sha(y.to_numpy(np.float32, (batch, cfg["classes"]))))
     taps = [int(ctx.debug_read(t, 1)[0]) for t in (3, 4)]
+    more = "".join(" " + t for t in read_outs(ctx, batch, cfg)) if extra == "readout" else ""
     prof = ctx.profile_forward(x.ptr, batch, y.ptr)
     slots = " ".join(f"{i}:{prof[s][1]}" for i, s in enumerate(vithip.STAGES) if prof[s][1] or prof[s][0])
-    print(f"{name}: batch {batch} logits {' '.join(shas)} taps(3,4) {taps} profile slots(index:events) {slots}", flush=True)
+    print(f"{name}: batch {batch} logits {' '.join(shas)} taps(3,4) {taps} profile slots(index:events) {slots}{more}", flush=True)
     ctx.close()
 
 

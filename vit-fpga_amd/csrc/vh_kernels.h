@@ -30,8 +30,7 @@ struct GemmArgs {
     float* partials = nullptr;     // RESID_LN / RESID_SPLIT / PATCH_SPLIT: [N/64][M][2]
     const float* wscale = nullptr; // e4m3 operands: the per-output-channel weight scales [N], with every epilogue; unused with 16-bit operands
     // ping-pong forms 5 / 7 only: launch tiles [tile_begin, tile_begin + tile_count) of the n-fastest 256x256 tile order
-    // (tile t = (t / tiles_n, t % tiles_n)); tile_count == 0 = all tiles.  Lets a caller split off the last, partly
-    // filled round of tiles and overlap it with other work (vithip_api.hip, tail overlap).
+    // (tile t = (t / tiles_n, t % tiles_n)); tile_count == 0 = all tiles.
     int tile_begin = 0, tile_count = 0;
     // PATCH_SPLIT: row stride of `partials` = number of TOKEN rows the statistics buffer is laid out for (0 = images x tokens)
     int64_t prow = 0;

@@ -21,6 +21,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "vh_kernels.h"
@@ -251,7 +252,7 @@ constexpr int kU8 = VH_ELEM_U8;   // ImgIn{p, kU8}: NHWC bytes, the 8-bit entry 
 // compute streams, so that two forwards that do not depend on each other -- consecutive steps of vh_forward_device_async,
 // consecutive submits of an image ring -- share the chip: the partly filled last round of tiles of one forward's GEMM runs
 // beside the other forward's kernels (DESIGN.md section 7 "Two forwards in flight").  Set 0 lives in the arena; set 1 is its
-// own allocation, made the first time it is needed (second_set).  Shared by both: the weights and fold_cd, guard_dev (an
+// own allocation, made the first time it is needed (second_set).  Shared by both: the weights (LayerW), guard_dev (an
 // atomic max, order-free), in_dev, logits_dev, the feature and attention stores.
 struct ActSet {
     char* base = nullptr;     // set 1: its allocation (set 0: null, the arena owns the bytes)
@@ -272,8 +273,29 @@ struct ActSet {
     // block's hidden rows [B][M], and [2][B][D]: a (the V product), then o (the out-projection) of every image
     float *mapz32 = nullptr, *maph32 = nullptr, *mapa32 = nullptr;
 };
-// byte offsets of a set's buffers from its base, and its size (vh_create computes them once; bind_set turns them into pointers)
-struct ActSetLayout { size_t x, xn, qkv, att, h, gu, col, cls, pool, st, pt, xlo, tk, mz, mh, ma, bytes; };
+
+// One layer's compute weights: pointers into the w16 arena, built once by vh_create.  prepare_weights fills what they point to, the
+// layer loops read it.
+struct LayerW {
+    void *qkv = nullptr, *o = nullptr, *fc1 = nullptr, *fc2 = nullptr;   // the GEMMs' weight operands: 16-bit, or e4m3 bytes (VH_DTYPE_FP8)
+    // fc2's weights once more in the 16-row-blocked layout of the tiled hidden activation (h_tiled; folded path): the MLP hidden
+    // activation then leaves fc1's epilogue straight from the registers (gemm_epilogue.h OTILED) and fc2's operand DMA reads both
+    // operands in that layout -- same values, same k order, same bits as the row-major path.  The out-projection's likewise:
+    // attention writes its output tiled as well (att_tiled).  Null where the shape or VH_H_TILED=0 rules the layout out.
+    void *fc2_t = nullptr, *o_t = nullptr;
+    // VH_DTYPE_FP8: one fp32 scale per output channel of the four e4m3 matrices; null on 16-bit contexts
+    float *s_qkv = nullptr, *s_o = nullptr, *s_fc1 = nullptr, *s_fc2 = nullptr;
+    float* bqkv = nullptr;   // [3 D]: the plain path's q|k|v bias (q's part scaled like Wq)
+    // LayerNorm fold constants: c = row sums of W', d = beta.W + b, for q|k|v [3 D] and fc1 [M1] (M1 = fc1's width: M, or 2 M with VH_FLAG_SWIGLU)
+    float *c_qkv = nullptr, *d_qkv = nullptr, *c_fc1 = nullptr, *d_fc1 = nullptr;
+};
+
+// The residual stream's rows where a forward left them, in one of three forms: fp32 rows in hi (VH_FEAT_FORM_F32, lo null); a 16-bit
+// hi plane plus one scaled e4m3 byte per element (VH_DTYPE_BF16 / VH_DTYPE_FP16: vh_common.h Lo8); on fp8 contexts an e4m3 hi plane
+// -- the GEMM operand itself -- plus a bf16 lo plane (VH_DTYPE_FP8).  The planes hold 3 bytes per element either way.
+struct ResidView { const void* hi; const void* lo; int form; };
+static size_t hi_bytes(int form) { return form == VH_FEAT_FORM_F32 ? 4 : form == VH_DTYPE_FP8 ? 1 : 2; }
+static size_t lo_bytes(int form) { return form == VH_FEAT_FORM_F32 ? 0 : form == VH_DTYPE_FP8 ? 2 : 1; }
 
 struct vh_ctx {
     vh_config cfg;
@@ -293,29 +315,21 @@ struct vh_ctx {
     float* params = nullptr;  // blob + 64
     char* w16 = nullptr;      // arena of 16-bit matrices
     void* wp16 = nullptr;     // [D, KPA]
-    std::vector<void*> wqkv16, wo16, w1_16, w2_16;
-    // fc2's weights once more in the 16-row-blocked layout of the tiled hidden activation (h_tiled; 16-bit folded path): the MLP
-    // hidden activation then leaves fc1's epilogue straight from the registers (gemm_epilogue.h OTILED) and fc2's operand DMA reads
-    // both operands in that layout -- same values, same k order, same bits as the row-major path
-    std::vector<void*> w2t_16, wot_16;   // (+ the out-projection's: attention writes its output tiled as well, att_tiled below)
+    std::vector<LayerW> layer;   // the per-layer matrices, scales and constants in the arena
     bool h_tiled = false;     // VH_H_TILED=0 (read when the context is created) keeps the row-major h (A/B, tests)
     bool att_tiled = true;    // VH_ATT_TILED=0 (read when the context is created) keeps the attention output row-major
     bool qkv_hm = true;       // VH_QKV_HM=0 keeps q|k|v row-major ([rows][3 D]) instead of head-major ([3][heads][rows][64]; needs att_tiled)
     bool swiglu_skip = false; // VH_SWIGLU_SKIP=1 (measurement only, tools/swiglu_bench.py): a VH_FLAG_SWIGLU context leaves the gate pass out
     bool weights_ready_tiled = false;   // the tiled copies exist for the CURRENT weights (prepared with the fold on)
-    float* bqkv = nullptr;    // [layers, 3D]
     // VH_DTYPE_FP8: the four per-layer matrices hold e4m3 bytes (in the same arena) + one fp32 scale per output channel;
     // everything 16-bit (patch embedding, qkv, head) is bf16
     bool fp8 = false;
     int dt16 = VH_DTYPE_BF16;
-    std::vector<float*> sqkv, so, s1, s2;
     // LayerNorm folded into the q|k|v and fc1 GEMMs (dim and mlp_dim multiples of 256):
     bool ln_fold = false;
-    float* fold_cd = nullptr; // per layer: cqkv[3D] dqkv[3D] c1[M1] d1[M1] (M1 = fc1's width: M, or 2 M with VH_FLAG_SWIGLU)
-    // with the fold: the residual stream lives as two planes, x = hi + lo (hi = the xn16 buffer = the GEMMs' 16-bit A operand,
-    // lo = xlo16 = what that rounding dropped, one scaled e4m3 byte per element: vh_common.h Lo8): a residual GEMM then moves
-    // 3 B per element each way instead of the fp32 array plus its 16-bit copy.
-    // VH_RESID_SPLIT=0 (A/B tools) keeps the fp32 array.
+    // with the fold: the residual stream lives as two planes, x = hi + lo (ResidView: hi = the xn16 buffer = the GEMMs' A operand,
+    // lo = xlo16 = what that rounding dropped): a residual GEMM then moves 3 B per element each way instead of the fp32 array plus
+    // its 16-bit copy.  VH_RESID_SPLIT=0 (A/B tools) keeps the fp32 array.
     bool split = false;
     bool cls_tail = false;    // VH_FLAG_CLS_TAIL: the last layer computes the class-token rows only (folded 16-bit path, head dim 64)
     int head_dim = 64;        // dim / heads: 64 takes launch_attention and its layouts, any other launch_attention_hd (row-major)
@@ -335,7 +349,7 @@ struct vh_ctx {
     // activations (sized for max_batch): the arena holds set 0 and what both sets share
     char* arena = nullptr;
     ActSet act[2];
-    ActSetLayout act_layout{};
+    size_t act_bytes = 0;          // the size of one set (bind_set)
     int last_set = 0;              // the set of the most recently enqueued forward: what the read-outs of "the last forward" read
     // two forwards in flight: the second compute stream, fork / join with c->stream, and per set the event behind its last head
     // launch (consecutive steps write the caller's logits in step order).  inflight_max: 2, or 1 with VH_INFLIGHT=1 (read when
@@ -370,10 +384,9 @@ struct vh_ctx {
     bool timed = false;
     int last_batch = 0;
     // Layer features (vh_set_feature_layers): the listed layers and ONE capture store, a slot of feat_slot bytes for every listed
-    // layer below cfg.layers in list order.  A slot holds [max_batch * T][D] rows as the path keeps them: the hi plane (or the fp32
-    // array) at 0, the lo plane behind max_batch * T * D hi elements; it is sized at 3 bytes per element where the residual stays
-    // two planes for good, else 4 (decided once, at the call).  What the LAST forward captured (enqueue_forward records it; the list call clears it):
-    // cap_n listed layers cap_layers[], cap_nl = layers it ran, cap_form = the FeatureArgs form of the rows it copied.
+    // layer below cfg.layers in list order.  A slot holds [max_batch * T][D] rows as the path keeps them (slot_view; sized once, at
+    // the call).  What the LAST forward captured (enqueue_forward records it; the list call clears it): cap_n listed layers
+    // cap_layers[], cap_nl = layers it ran, cap_form = the ResidView form of the rows it copied.
     int feat_layers[VH_MAX_FEATURE_LAYERS] = {0}, feat_n = 0;
     char* feat_store = nullptr;
     size_t feat_slot = 0;
@@ -457,6 +470,94 @@ namespace {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ---- the buffers of an activation set: ONE table ------------------------------------------------------------------------------
+// A row per ActSet member, in the arena's carve order.  Allocation and stride differ where a path stores
+// narrower elements than the buffer is sized for (e4m3 operands on fp8 contexts, the one-byte lo plane on 16-bit ones); partials
+// has one spare 64-column block, clsn32 room for the widest head input (2 D), mapa32 two [max_batch][D] arrays, a then o.
+// PER_ROW: max_batch * T + 256 token rows, a part starts at row img0 * T.  The 256 are room for whole 256-row GEMM tiles behind the
+// LAST part of a forward (enqueue_forward, rows_g): its rows start anywhere, so the padding may reach up to 255 rows past the last
+// real row.  PER_IMAGE: max_batch images, a part starts at img0.
+enum ActUnit { PER_ROW, PER_IMAGE };
+template <class Row> void for_each_act_buffer(const vh_ctx* c, Row&& row) {
+    const vh_config& f = c->cfg;
+    const Layout& L = c->L;
+    const size_t D = f.dim, M = f.mlp_dim, op = c->fp8 ? 1 : 2;   // op: bytes of a GEMM A-operand element
+    const size_t tk = 4 * (size_t)(f.layers > 0 ? f.layers : 1);  // attention work-queue counters: one word per image and layer, a part uses its first image's
+    //  member             counted in  allocated                     stride                        exists
+    row(&ActSet::x,        PER_ROW,    D * 4,                        D * 4,                        true);
+    row(&ActSet::xn16,     PER_ROW,    D * 2,                        D * op,                       true);
+    row(&ActSet::qkv16,    PER_ROW,    3 * D * 2,                    3 * D * 2,                    true);
+    row(&ActSet::att16,    PER_ROW,    D * 2,                        D * op,                       true);
+    row(&ActSet::h16,      PER_ROW,    M * 2,                        M * op,                       true);
+    row(&ActSet::col16,    PER_IMAGE,  L.NP * (size_t)L.KPA * 2,     L.NP * (size_t)L.KPA * 2,     true);
+    row(&ActSet::clsn32,   PER_IMAGE,  2 * D * 4,                    (size_t)L.HW * 4,             true);
+    row(&ActSet::pool32,   PER_IMAGE,  D * 4,                        D * 4,                        true);
+    row(&ActSet::stats,    PER_ROW,    2 * 4,                        2 * 4,                        true);
+    row(&ActSet::partials, PER_ROW,    (D / 64 + 1) * 2 * 4,         D / 64 * 2 * 4,               true);
+    row(&ActSet::xlo16,    PER_ROW,    D * 2,                        D * (c->fp8 ? 2 : 1),         true);
+    row(&ActSet::tickets,  PER_IMAGE,  tk,                           tk,                           true);
+    row(&ActSet::mapz32,   PER_IMAGE,  (size_t)f.heads * D * 4,      (size_t)f.heads * D * 4,      L.map);
+    row(&ActSet::maph32,   PER_IMAGE,  (M > D ? M : D) * 4,          (M > D ? M : D) * 4,          L.map);
+    row(&ActSet::mapa32,   PER_IMAGE,  2 * D * 4,                    D * 4,                        L.map);
+    row(&ActSet::gu16,     PER_ROW,    2 * M * 2,                    2 * M * 2,                    L.swiglu);
+}
+size_t act_units(const vh_ctx* c, ActUnit u) { return u == PER_ROW ? (size_t)c->cfg.max_batch * c->L.T + 256 : (size_t)c->cfg.max_batch; }
+template <class T> void set_ptr(T*& dst, char* p) { dst = (T*)p; }
+// a set's buffers at `base`, in table order, each on a 256-byte boundary; returns the set's size (a null: the size only)
+size_t bind_set(const vh_ctx* c, ActSet* a, char* base) {
+    size_t at = 0;
+    for_each_act_buffer(c, [&](auto member, ActUnit u, size_t allocated, size_t, bool exists) {
+        if (!exists) return;
+        if (a) set_ptr(a->*member, base + at);
+        at += align_up(act_units(c, u) * allocated, 256);
+    });
+    return at;
+}
+// the slices of `whole` that belong to the part of a forward that starts at image img0 (a buffer the context lacks stays null)
+ActSet part_set(const vh_ctx* c, const ActSet& whole, int img0) {
+    ActSet part;
+    for_each_act_buffer(c, [&](auto member, ActUnit u, size_t, size_t stride, bool exists) {
+        if (exists) set_ptr(part.*member, (char*)(whole.*member) + (size_t)img0 * (u == PER_ROW ? c->L.T : 1) * stride);
+    });
+    return part;
+}
+// allocated bytes of one buffer of a set, named by its member (members of other types cannot be it)
+template <class T> size_t act_buffer_bytes(const vh_ctx* c, T* ActSet::*which) {
+    size_t bytes = 0;
+    for_each_act_buffer(c, [&](auto member, ActUnit u, size_t allocated, size_t, bool exists) {
+        if constexpr (std::is_same_v<decltype(member), T * ActSet::*>)
+            if (exists && member == which) bytes = act_units(c, u) * allocated;
+    });
+    return bytes;
+}
+
+// ---- the residual stream of a forward ----------------------------------------------------------------------------------------
+int layers_to_run(const vh_ctx* c) { return (c->run_layers < 0 || c->run_layers > c->cfg.layers) ? c->cfg.layers : c->run_layers; }
+// the form a forward over nl layers leaves the rows in on this context: the two planes from the first layer of the split path on
+int resid_form(const vh_ctx* c, int nl) { return c->split && nl > 0 ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32; }
+// ... and where, in buffer set (or part) `a`
+ResidView resid_view(const vh_ctx* c, const ActSet& a, int nl) {
+    const int form = resid_form(c, nl);
+    return form == VH_FEAT_FORM_F32 ? ResidView{a.x, nullptr, form} : ResidView{a.xn16, a.xlo16, form};
+}
+// slot `i` of the layer-feature capture store, holding rows of `form`: [max_batch * T][D] hi elements, the lo plane behind them
+ResidView slot_view(const vh_ctx* c, int i, int form) {
+    const char* const base = c->feat_store + (size_t)i * c->feat_slot;
+    const size_t all = (size_t)c->cfg.max_batch * c->L.T * c->cfg.dim;
+    return ResidView{base, lo_bytes(form) ? base + all * hi_bytes(form) : nullptr, form};
+}
+
+// records the next event of a grow-only pool on `s` (the stage-timing and step-timing events: created once, reused by every call)
+int record_next(vh_ctx* c, std::vector<hipEvent_t>& pool, size_t& used, hipStream_t s) {
+    if (used == pool.size()) {
+        hipEvent_t e;
+        HIPCHK(&c->err, hipEventCreate(&e));
+        pool.push_back(e);
+    }
+    HIPCHK(&c->err, hipEventRecord(pool[used++], s));
+    return VH_OK;
+}
+
 int set_device(std::string* err, int device) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -477,32 +578,32 @@ int prepare_weights(vh_ctx* c) {
     for (int l = 0; l < f.layers && c->fp8 && c->ln_fold; ++l) {
         // folded LayerNorm on e4m3 operands: W' = gamma o W through the row quantiser, its scales, c and d (launch_fold_ln_f8)
         const LayerOff& o = L.layer[l];
-        float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M);
-        char* wq = (char*)c->wqkv16[l];
+        const LayerW& w = c->layer[l];
+        char* wq = (char*)w.qkv;
         const size_t dd = (size_t)D * D;
-        HIPCHK(&c->err, launch_fold_ln_f8(P + o.qw, P + o.qb, P + o.ln1w, P + o.ln1b, D, D, c->q_scale, wq, c->sqkv[l], cd, cd + 3 * D, s));
-        HIPCHK(&c->err, launch_fold_ln_f8(P + o.kw, P + o.kb, P + o.ln1w, P + o.ln1b, D, D, 1.0f, wq + dd, c->sqkv[l] + D, cd + D, cd + 4 * D, s));
-        HIPCHK(&c->err, launch_fold_ln_f8(P + o.vw, P + o.vb, P + o.ln1w, P + o.ln1b, D, D, 1.0f, wq + 2 * dd, c->sqkv[l] + 2 * D, cd + 2 * D, cd + 5 * D, s));
-        HIPCHK(&c->err, launch_quantize_rows(P + o.ow, D, D, 1.0f, c->wo16[l], c->so[l], s));
-        if (c->h_tiled && c->wot_16[l]) HIPCHK(&c->err, launch_tile_bytes(c->wo16[l], D, D, c->wot_16[l], s));   // (att_tiled)
-        HIPCHK(&c->err, launch_fold_ln_f8(P + o.f1w, P + o.f1b, P + o.ln2w, P + o.ln2b, M, D, 1.0f, c->w1_16[l], c->s1[l], cd + 6 * D, cd + 6 * D + M, s));
-        HIPCHK(&c->err, launch_quantize_rows(P + o.f2w, D, M, 1.0f, c->w2_16[l], c->s2[l], s));
-        if (c->h_tiled && c->w2t_16[l]) HIPCHK(&c->err, launch_tile_bytes(c->w2_16[l], D, M, c->w2t_16[l], s));   // the same bytes, tiled (h_tiled)
+        HIPCHK(&c->err, launch_fold_ln_f8(P + o.qw, P + o.qb, P + o.ln1w, P + o.ln1b, D, D, c->q_scale, wq, w.s_qkv, w.c_qkv, w.d_qkv, s));
+        HIPCHK(&c->err, launch_fold_ln_f8(P + o.kw, P + o.kb, P + o.ln1w, P + o.ln1b, D, D, 1.0f, wq + dd, w.s_qkv + D, w.c_qkv + D, w.d_qkv + D, s));
+        HIPCHK(&c->err, launch_fold_ln_f8(P + o.vw, P + o.vb, P + o.ln1w, P + o.ln1b, D, D, 1.0f, wq + 2 * dd, w.s_qkv + 2 * D, w.c_qkv + 2 * D, w.d_qkv + 2 * D, s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.ow, D, D, 1.0f, w.o, w.s_o, s));
+        if (c->h_tiled && w.o_t) HIPCHK(&c->err, launch_tile_bytes(w.o, D, D, w.o_t, s));   // (att_tiled)
+        HIPCHK(&c->err, launch_fold_ln_f8(P + o.f1w, P + o.f1b, P + o.ln2w, P + o.ln2b, M1, D, 1.0f, w.fc1, w.s_fc1, w.c_fc1, w.d_fc1, s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.f2w, D, M, 1.0f, w.fc2, w.s_fc2, s));
+        if (c->h_tiled && w.fc2_t) HIPCHK(&c->err, launch_tile_bytes(w.fc2, D, M, w.fc2_t, s));   // the same bytes, tiled (h_tiled)
     }
     for (int l = 0; l < f.layers && c->fp8 && !c->ln_fold; ++l) {
         const LayerOff& o = L.layer[l];
+        const LayerW& w = c->layer[l];
         // bias [bq/8 ; bk ; bv] from the 16-bit packer (its 16-bit matrix is overwritten right after), then
         // e4m3 rows + scales; the softmax scale head_dim^-1/2 * log2(e) (q_scale) goes into the q rows' fp32 scales
-        HIPCHK(&c->err, launch_pack_qkv(P + o.qw, P + o.qb, P + o.kw, P + o.kb, P + o.vw, P + o.vb, D, c->q_scale,
-                                        c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, c->dt16, s));
-        char* wq = (char*)c->wqkv16[l];
+        HIPCHK(&c->err, launch_pack_qkv(P + o.qw, P + o.qb, P + o.kw, P + o.kb, P + o.vw, P + o.vb, D, c->q_scale, w.qkv, w.bqkv, c->dt16, s));
+        char* wq = (char*)w.qkv;
         const size_t dd = (size_t)D * D;
-        HIPCHK(&c->err, launch_quantize_rows(P + o.qw, D, D, c->q_scale, wq, c->sqkv[l], s));
-        HIPCHK(&c->err, launch_quantize_rows(P + o.kw, D, D, 1.0f, wq + dd, c->sqkv[l] + D, s));
-        HIPCHK(&c->err, launch_quantize_rows(P + o.vw, D, D, 1.0f, wq + 2 * dd, c->sqkv[l] + 2 * D, s));
-        HIPCHK(&c->err, launch_quantize_rows(P + o.ow, D, D, 1.0f, c->wo16[l], c->so[l], s));
-        HIPCHK(&c->err, launch_quantize_rows(P + o.f1w, M, D, 1.0f, c->w1_16[l], c->s1[l], s));
-        HIPCHK(&c->err, launch_quantize_rows(P + o.f2w, D, M, 1.0f, c->w2_16[l], c->s2[l], s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.qw, D, D, c->q_scale, wq, w.s_qkv, s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.kw, D, D, 1.0f, wq + dd, w.s_qkv + D, s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.vw, D, D, 1.0f, wq + 2 * dd, w.s_qkv + 2 * D, s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.ow, D, D, 1.0f, w.o, w.s_o, s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.f1w, M1, D, 1.0f, w.fc1, w.s_fc1, s));
+        HIPCHK(&c->err, launch_quantize_rows(P + o.f2w, D, M, 1.0f, w.fc2, w.s_fc2, s));
     }
     // VH_FLAG_W8_E4M3: the six matrices of a layer pass through the e4m3 quantiser (one scale per output channel) and back
     // before the 16-bit preparation -- weight-only fp8 with dequantisation at load (SURVEY.md section 7 option (a))
@@ -526,24 +627,23 @@ int prepare_weights(vh_ctx* c) {
             o.qw = 0; o.kw = dd1; o.vw = 2 * dd1; o.ow = 3 * dd1; o.f1w = 4 * dd1; o.f2w = 4 * dd1 + md1;
         }
         const float* B = c->params;   // biases and LayerNorm parameters stay where they are
+        const LayerW& w = c->layer[l];
         if (c->ln_fold) {
             // W' = gamma o W (q rows also carry the softmax scale q_scale), c = row sums of W', d = beta.W + b
-            float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M1);
-            char* wq = (char*)c->wqkv16[l];
+            char* wq = (char*)w.qkv;
             const size_t dd2 = (size_t)D * D * 2;
-            HIPCHK(&c->err, launch_fold_ln(P + o.qw, B + o.qb, B + o.ln1w, B + o.ln1b, D, D, c->q_scale, wq, cd, cd + 3 * D, f.dtype, s));
-            HIPCHK(&c->err, launch_fold_ln(P + o.kw, B + o.kb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + dd2, cd + D, cd + 4 * D, f.dtype, s));
-            HIPCHK(&c->err, launch_fold_ln(P + o.vw, B + o.vb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + 2 * dd2, cd + 2 * D, cd + 5 * D, f.dtype, s));
-            HIPCHK(&c->err, launch_fold_ln(P + o.f1w, B + o.f1b, B + o.ln2w, B + o.ln2b, M1, D, 1.0f, c->w1_16[l], cd + 6 * D, cd + 6 * D + M1, f.dtype, s));
+            HIPCHK(&c->err, launch_fold_ln(P + o.qw, B + o.qb, B + o.ln1w, B + o.ln1b, D, D, c->q_scale, wq, w.c_qkv, w.d_qkv, f.dtype, s));
+            HIPCHK(&c->err, launch_fold_ln(P + o.kw, B + o.kb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + dd2, w.c_qkv + D, w.d_qkv + D, f.dtype, s));
+            HIPCHK(&c->err, launch_fold_ln(P + o.vw, B + o.vb, B + o.ln1w, B + o.ln1b, D, D, 1.0f, wq + 2 * dd2, w.c_qkv + 2 * D, w.d_qkv + 2 * D, f.dtype, s));
+            HIPCHK(&c->err, launch_fold_ln(P + o.f1w, B + o.f1b, B + o.ln2w, B + o.ln2b, M1, D, 1.0f, w.fc1, w.c_fc1, w.d_fc1, f.dtype, s));
         } else {
-            HIPCHK(&c->err, launch_pack_qkv(P + o.qw, B + o.qb, P + o.kw, B + o.kb, P + o.vw, B + o.vb, D, c->q_scale,
-                                            c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, f.dtype, s));
-            HIPCHK(&c->err, launch_cast(P + o.f1w, c->w1_16[l], (int64_t)M1 * D, f.dtype, s));
+            HIPCHK(&c->err, launch_pack_qkv(P + o.qw, B + o.qb, P + o.kw, B + o.kb, P + o.vw, B + o.vb, D, c->q_scale, w.qkv, w.bqkv, f.dtype, s));
+            HIPCHK(&c->err, launch_cast(P + o.f1w, w.fc1, (int64_t)M1 * D, f.dtype, s));
         }
-        HIPCHK(&c->err, launch_cast(P + o.ow, c->wo16[l], (int64_t)D * D, f.dtype, s));
-        HIPCHK(&c->err, launch_cast(P + o.f2w, c->w2_16[l], (int64_t)D * M, f.dtype, s));
-        if (c->h_tiled && c->w2t_16[l]) HIPCHK(&c->err, launch_cast_tiled_w(P + o.f2w, D, M, c->w2t_16[l], f.dtype, s));
-        if (c->h_tiled && c->wot_16[l]) HIPCHK(&c->err, launch_cast_tiled_w(P + o.ow, D, D, c->wot_16[l], f.dtype, s));
+        HIPCHK(&c->err, launch_cast(P + o.ow, w.o, (int64_t)D * D, f.dtype, s));
+        HIPCHK(&c->err, launch_cast(P + o.f2w, w.fc2, (int64_t)D * M, f.dtype, s));
+        if (c->h_tiled && w.fc2_t) HIPCHK(&c->err, launch_cast_tiled_w(P + o.f2w, D, M, w.fc2_t, f.dtype, s));
+        if (c->h_tiled && w.o_t) HIPCHK(&c->err, launch_cast_tiled_w(P + o.ow, D, D, w.o_t, f.dtype, s));
         if (w8tmp) { HIPCHK(&c->err, hipStreamSynchronize(s)); }   // the scratch is reused by the next layer
     }
     HIPCHK(&c->err, hipStreamSynchronize(s));
@@ -613,7 +713,9 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
 // end in the write of `logits` -- wait for it (two forwards in flight: the step before this one wrote the same logits first).
 int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<std::pair<int, hipEvent_t>>* ev,
                     hipStream_t s, int img0, bool may_pad = true, int set = 0, hipEvent_t head_wait = nullptr) {
-    const ActSet& A = c->act[set];
+    // This part's slices of the set.  Parts take disjoint slices; a part's partial-sum block is (D/64) * rows * 2 floats, laid out
+    // for ITS row count.
+    const ActSet A = part_set(c, c->act[set], img0);
     c->last_set = set;
     const vh_config& f = c->cfg;
     const Layout& L = c->L;
@@ -629,31 +731,15 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     const int64_t row_tiles = (rows + 255) / 256;
     const int64_t rows_g = (may_pad && c->ln_fold && row_tiles * ((D + 255) / 256) >= 2 * (int64_t)c->num_cu) ? row_tiles * 256 : rows;
     const float* P = c->params;
-    // this part's slices of its buffer set
-    const size_t r0 = (size_t)img0 * T, esz = 2, esz_op = c->fp8 ? 1 : 2;  // esz_op: GEMM A-operand element
+    const size_t r0 = (size_t)img0 * T, esz = 2;   // r0: this part's first row of a capture slot; esz: a 16-bit element
     const int dt16 = c->dt16;
-    float* const x = A.x + r0 * D;
-    // LayerNorm-fold row statistics of this part: (mean, rstd) per row, and the [D/64][rows][2] partial sums; parts take
-    // disjoint slices (a part's partial-sum block is (D/64) * rows * 2 floats, laid out for ITS row count)
-    float* const stats_p = A.stats + r0 * 2;
-    float* const partials_p = A.partials + (size_t)(D / 64) * r0 * 2;
-    char* const xn16 = (char*)A.xn16 + r0 * D * esz_op;
-    char* const xlo16 = (char*)A.xlo16 + r0 * D * (c->fp8 ? 2 : 1);   // the lo plane: one byte per element (fp8 path: bf16 beside the e4m3 hi plane)
-    char* const qkv16 = (char*)A.qkv16 + r0 * 3 * D * esz;
-    char* const att16 = (char*)A.att16 + r0 * D * esz_op;
-    char* const h16 = (char*)A.h16 + r0 * M * esz_op;
-    char* const gu16 = L.swiglu ? (char*)A.gu16 + r0 * M1 * esz : nullptr;
-    char* const col16 = (char*)A.col16 + (size_t)img0 * L.NP * L.KPA * esz;
-    float* const clsn32 = A.clsn32 + (size_t)img0 * L.HW;   // this part's rows of the head's input [.][W]
-    float* const pool32 = A.pool32 + (size_t)img0 * D;
     // VH_FLAG_NO_CLS: no class-token row.  The patch GEMM's epilogue adds "pos row 1 + p", so a context without pos[0] hands it the
     // table one row early (inside the resident blob: the header and the patch tensors precede pos); the leading rows are all registers.
     const float* const cls_p = L.ncls ? P + L.cls : nullptr;
     const float* const pos_p = P + L.pos - (L.ncls ? 0 : D);
     // the attention launches' work-queue counters: one word per layer, all zeroed by ONE memset per forward (a memset per
     // launch is a 5 us fill kernel in front of every attention kernel)
-    unsigned int* const tickets_part = A.tickets + (size_t)img0 * (f.layers > 0 ? f.layers : 1);
-    if (f.layers > 0) HIPCHK(&c->err, hipMemsetAsync(tickets_part, 0, sizeof(unsigned int) * f.layers, s));
+    if (f.layers > 0) HIPCHK(&c->err, hipMemsetAsync(A.tickets, 0, sizeof(unsigned int) * f.layers, s));
     // fp8 operands: the folded GEMMs multiply the RAW residual rows as e4m3, which saturates at 448 -- the statistics kernels
     // keep a running maximum of |x| (a bound of it) in the guard's second word
     unsigned int* const amax_guard = c->fp8 ? c->guard_dev + 1 : nullptr;
@@ -666,16 +752,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         return VH_OK;
     };
     // hip events around every launch of the stage selected by vh_set_stage_timing()
-    auto tmark = [&](int stage) -> int {
-        if (stage != c->timing_stage) return VH_OK;
-        if (c->tev_used == c->tev.size()) {
-            hipEvent_t e;
-            HIPCHK(&c->err, hipEventCreate(&e));
-            c->tev.push_back(e);
-        }
-        HIPCHK(&c->err, hipEventRecord(c->tev[c->tev_used++], s));
-        return VH_OK;
-    };
+    auto tmark = [&](int stage) -> int { return stage == c->timing_stage ? record_next(c, c->tev, c->tev_used, s) : VH_OK; };
     // The one GemmArgs builder of this part.  It sets what every launch shares: the operand dtype (op_dt in the layer loops, dt16 for
     // the patch GEMM) and this part's statistics slices (LNFOLD* reads stats, RESID_* / PATCH_SPLIT write partials, the others ignore
     // both).  A launch adds what its epilogue and layout need: out16, wscale (null on the 16-bit paths), a layout flag, a tile range.
@@ -683,8 +760,8 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     auto gemm_args = [&](int dtype, const void* a, const void* w, const float* bias, void* out, int64_t Mr, int N, int K, int epi,
                          const float* aux = nullptr, int aux_i = 0) {
         GemmArgs g{a, w, bias, out, Mr, N, K, epi, aux, aux_i, dtype, 0};
-        g.stats = stats_p;
-        g.partials = partials_p;
+        g.stats = A.stats;
+        g.partials = A.partials;
         return g;
     };
     // the tiled layouts exist in the persistent form only, and a launch that asks for one names that form (gemm_check)
@@ -703,27 +780,23 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     };
     int rc;
     if ((rc = mark(-1))) return rc;
-    const int nl = (c->run_layers < 0 || c->run_layers > f.layers) ? f.layers : c->run_layers;
+    const int nl = layers_to_run(c);
+    // where this part's residual rows live behind every layer, and at the end of the forward
+    const ResidView resid = resid_view(c, A, nl);
     // Layer features: behind fc2 of layer l, when l + 1 is listed and more layers follow, this part's real rows go to the capture
     // store in the form the path holds them, at the part's row offset -- one launch.  (The listed layer that equals nl needs no copy:
     // the live residual serves it.)  What was captured is recorded for the read-out; every part records the same values.
-    const int cap_form = c->split ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32;
     c->cap_nl = nl;
-    c->cap_form = cap_form;
+    c->cap_form = resid.form;
     c->cap_n = c->feat_n;
     for (int i = 0; i < c->cap_n; ++i) c->cap_layers[i] = c->feat_layers[i];
     auto capture = [&](int l) -> int {
         if (!c->feat_store || l + 1 >= nl) return VH_OK;
         for (int i = 0; i < c->feat_n; ++i) {
             if (c->feat_layers[i] != l + 1) continue;
-            char* const slot = c->feat_store + (size_t)i * c->feat_slot;
-            const size_t n = (size_t)rows * D, all = (size_t)f.max_batch * T * D;
-            if (cap_form == VH_FEAT_FORM_F32)
-                HIPCHK(&c->err, launch_feature_capture(x, slot + r0 * D * 4, n * 4, nullptr, nullptr, 0, s));
-            else {
-                const size_t hb = c->fp8 ? 1 : 2, lb = c->fp8 ? 2 : 1;
-                HIPCHK(&c->err, launch_feature_capture(xn16, slot + r0 * D * hb, n * hb, xlo16, slot + all * hb + r0 * D * lb, n * lb, s));
-            }
+            const ResidView slot = slot_view(c, i, resid.form);
+            const size_t n = (size_t)rows * D, hb = hi_bytes(resid.form), lb = lo_bytes(resid.form);
+            HIPCHK(&c->err, launch_feature_capture(resid.hi, (char*)slot.hi + r0 * D * hb, n * hb, resid.lo, resid.lo ? (char*)slot.lo + r0 * D * lb : nullptr, n * lb, s));
         }
         return VH_OK;
     };
@@ -738,7 +811,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         for (int i = 0; i < c->attn_n; ++i) {
             if (c->attn_layers[i] != l + 1) continue;
             float* const slot = (float*)(c->attn_store + (size_t)i * c->attn_slot) + (size_t)img0 * f.heads * c->attn_q * T;
-            HIPCHK(&c->err, launch_attention_probs(qkv16, hm_rows, batch, T, f.heads, c->head_dim, c->attn_q, dt16, slot, s));
+            HIPCHK(&c->err, launch_attention_probs(A.qkv16, hm_rows, batch, T, f.heads, c->head_dim, c->attn_q, dt16, slot, s));
         }
         return VH_OK;
     };
@@ -747,7 +820,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     // Without the flag: no launch.  (No stage of its own: it is neither the projection's time nor attention's.)
     auto rope = [&](int64_t hm_rows) -> int {
         if (!L.rope) return VH_OK;
-        HIPCHK(&c->err, launch_rope(qkv16, dt16, batch, T, f.heads, c->head_dim, L.lead, hm_rows, P + L.rope_cos, P + L.rope_sin, s));
+        HIPCHK(&c->err, launch_rope(A.qkv16, dt16, batch, T, f.heads, c->head_dim, L.lead, hm_rows, P + L.rope_cos, P + L.rope_sin, s));
         return VH_OK;
     };
     // VH_FLAG_SWIGLU: behind fc1, which wrote gu16 [rows][2 M] row-major, the gate pass leaves h16 = silu(g) * u in the layout fc2 reads
@@ -756,7 +829,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     // is created, is that tool's switch: fc2 then reads whatever h16 holds, and the logits mean nothing.)
     auto gate = [&](int64_t nrows, bool tiled) -> int {
         if (!L.swiglu || c->swiglu_skip) return VH_OK;
-        HIPCHK(&c->err, launch_swiglu(gu16, dt16, nrows, M, h16, tiled ? 1 : 0, s));
+        HIPCHK(&c->err, launch_swiglu(A.gu16, dt16, nrows, M, A.h16, tiled ? 1 : 0, s));
         return VH_OK;
     };
     // Patch embedding: the im2col pass + the persistent GEMM.
@@ -774,12 +847,12 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     if ((rc = tmark(ST_IM2COL))) return rc;
     if (in.layout == VH_LAYOUT_NHWC && in.u8())
         HIPCHK(&c->err, launch_im2col_u8((const uint8_t*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale, c->in_shift,
-                                         col16, dt16, s));
+                                         A.col16, dt16, s));
     else if (in.nhwc_f32())
-        HIPCHK(&c->err, launch_im2col((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, col16, dt16, s));
+        HIPCHK(&c->err, launch_im2col((const float*)in.p, batch, f.image_size, f.patch_size, f.channels, L.KPA, A.col16, dt16, s));
     else   // every other (element type, layout): kernels_gather.hip
         HIPCHK(&c->err, launch_im2col_tensor(in.p, in.kind, in.layout, batch, f.image_size, f.patch_size, f.channels, L.KPA, c->in_scale,
-                                             c->in_shift, col16, dt16, s));
+                                             c->in_shift, A.col16, dt16, s));
     if ((rc = tmark(ST_IM2COL))) return rc;
     if ((rc = mark(ST_IM2COL))) return rc;
     if (patch_split) {
@@ -787,38 +860,38 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         // partial sums (PATCH_SPLIT epilogue; the class-token rows from their own small kernel) -- no fp32
         // x, no separate row-statistics pass over it (round 3: -0.1 ms per forward).  The partial sums are laid out for rows_g
         // rows, like every later layer's.
-        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, pos_p, L.NP);
-        g.out16 = xlo16;
+        GemmArgs g = gemm_args(dt16, A.col16, c->wp16, P + L.patch_b, A.xn16, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH_SPLIT, pos_p, L.NP);
+        g.out16 = A.xlo16;
         g.prow = rows_g;
         g.lead = L.lead;
         if ((rc = stage(ST_PATCH, [&] { return launch_gemm(g, s); }))) return rc;
         if ((rc = stage(ST_CLS, [&] {
-                 return launch_lead_rows_split(xn16, xlo16, partials_p, rows_g, cls_p, pos_p, P + L.reg, L.lead, batch, T, D, dt16, s);
+                 return launch_lead_rows_split(A.xn16, A.xlo16, A.partials, rows_g, cls_p, pos_p, P + L.reg, L.lead, batch, T, D, dt16, s);
              })))
             return rc;
-        HIPCHK(&c->err, launch_finalize_stats(partials_p, D / 64, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
+        HIPCHK(&c->err, launch_finalize_stats(A.partials, D / 64, rows_g, D, f.ln_eps, A.stats, s, rows, c->guard_dev, amax_guard));
         if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark: ST_LNSTATS has no stage timing)
     } else {
-        GemmArgs g = gemm_args(dt16, col16, c->wp16, P + L.patch_b, x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, pos_p, L.NP);
+        GemmArgs g = gemm_args(dt16, A.col16, c->wp16, P + L.patch_b, A.x, (int64_t)batch * L.NP, D, L.KPA, VH_EPI_PATCH, pos_p, L.NP);
         g.lead = L.lead;
         if ((rc = stage(ST_PATCH, [&] { return launch_gemm(g, s); }))) return rc;
-        if ((rc = stage(ST_CLS, [&] { return launch_lead_rows(x, cls_p, pos_p, P + L.reg, L.lead, batch, T, D, s); }))) return rc;
+        if ((rc = stage(ST_CLS, [&] { return launch_lead_rows(A.x, cls_p, pos_p, P + L.reg, L.lead, batch, T, D, s); }))) return rc;
         if (pre_ln) {
             // x <- LN(x) pre_ln.weight + pre_ln.bias, in the form the path consumes: the fp32 array (plain loop, non-split fold, no
             // layer at all), the 16-bit operand copy / the split planes, layer 0's LN1 statistics of the normalised rows and the guards
             const bool fold0 = c->ln_fold && nl > 0;
             if ((rc = stage(ST_PRELN, [&] {
-                     return launch_pre_layernorm(x, fold0 ? rows_g : rows, D, P + L.prew, P + L.preb, f.ln_eps, fold0 && c->split ? nullptr : x,
-                                                 fold0 ? xn16 : nullptr, fold0 && c->split ? xlo16 : nullptr, fold0 ? stats_p : nullptr, op_dt, s,
+                     return launch_pre_layernorm(A.x, fold0 ? rows_g : rows, D, P + L.prew, P + L.preb, f.ln_eps, fold0 && c->split ? nullptr : A.x,
+                                                 fold0 ? A.xn16 : nullptr, fold0 && c->split ? A.xlo16 : nullptr, fold0 ? A.stats : nullptr, op_dt, s,
                                                  rows, fold0 ? c->guard_dev : nullptr, fold0 ? amax_guard : nullptr);
                  })))
                 return rc;
         } else if (c->ln_fold && nl > 0) {
             // layer 0's LN1 statistics: its input comes from the patch embedding, not from a RESID_LN epilogue
             // (fp8 path with the split residual: the patch embedding stays the bf16 fp32-out GEMM; this pass makes the planes)
-            if (c->split) HIPCHK(&c->err, launch_rowstats_split(x, rows_g, D, f.ln_eps, xn16, xlo16, stats_p, op_dt, s, rows, amax_guard));
-            else HIPCHK(&c->err, launch_rowstats_cast(x, rows_g, D, f.ln_eps, xn16, stats_p, op_dt, s, rows, amax_guard));
-            HIPCHK(&c->err, launch_ln_guard(stats_p, rows, c->guard_dev, s));   // real rows only (rows_g - rows are tile padding)
+            if (c->split) HIPCHK(&c->err, launch_rowstats_split(A.x, rows_g, D, f.ln_eps, A.xn16, A.xlo16, A.stats, op_dt, s, rows, amax_guard));
+            else HIPCHK(&c->err, launch_rowstats_cast(A.x, rows_g, D, f.ln_eps, A.xn16, A.stats, op_dt, s, rows, amax_guard));
+            HIPCHK(&c->err, launch_ln_guard(A.stats, rows, c->guard_dev, s));   // real rows only (rows_g - rows are tile padding)
             if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
         }
     }
@@ -839,13 +912,10 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     c->last_qkv_hm = qkv_hm && nl > 0 && c->ln_fold;
     for (int l = 0; l < nl && c->ln_fold; ++l) {
         const LayerOff& o = L.layer[l];
-        const float* cd = c->fold_cd + (size_t)l * (6 * D + 2 * M1);
+        const LayerW& w = c->layer[l];
         const int nblk = D / 64;
-        // e4m3 operands: the weight matrices' per-output-channel scales
-        const float *sq = c->fp8 ? c->sqkv[l] : nullptr, *so = c->fp8 ? c->so[l] : nullptr;
-        const float *s1 = c->fp8 ? c->s1[l] : nullptr, *s2 = c->fp8 ? c->s2[l] : nullptr;
-        GemmArgs gq = gemm_args(op_dt, xn16, c->wqkv16[l], cd + 3 * D, qkv16, rows_g, 3 * D, D, VH_EPI_LNFOLD, cd);
-        gq.wscale = sq;
+        GemmArgs gq = gemm_args(op_dt, A.xn16, w.qkv, w.d_qkv, A.qkv16, rows_g, 3 * D, D, VH_EPI_LNFOLD, w.c_qkv);
+        gq.wscale = w.s_qkv;
         set_tiled(gq, qkv_hm, false);
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
         if ((rc = rope(qkv_hm ? (int64_t)rows_g : 0))) return rc;
@@ -856,73 +926,73 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
             // planes (the idle patch-matrix buffer).  Same kernels, same per-row arithmetic as the full layer, except the
             // attention row (a VALU kernel with another summation order): logits agree to rounding, not bitwise.
             // (no stage bracket in this branch: the tail has no stage timing, only the profile events)
-            char* const hc = col16;
-            char* const lc = col16 + (((size_t)batch * D * esz + 255) & ~(size_t)255);
-            HIPCHK(&c->err, launch_attention_cls(qkv16, batch, T, f.heads, att16, dt16, s));
+            char* const hc = (char*)A.col16;
+            char* const lc = hc + (((size_t)batch * D * esz + 255) & ~(size_t)255);
+            HIPCHK(&c->err, launch_attention_cls(A.qkv16, batch, T, f.heads, A.att16, dt16, s));
             if ((rc = mark(ST_ATTN))) return rc;
-            HIPCHK(&c->err, hipMemcpy2DAsync(hc, (size_t)D * esz, xn16, (size_t)T * D * esz, (size_t)D * esz, batch, hipMemcpyDeviceToDevice, s));
-            HIPCHK(&c->err, hipMemcpy2DAsync(lc, (size_t)D, xlo16, (size_t)T * D, (size_t)D, batch, hipMemcpyDeviceToDevice, s));
-            GemmArgs gp = gemm_args(op_dt, att16, c->wo16[l], P + o.ob, hc, batch, D, D, VH_EPI_RESID_SPLIT);
+            HIPCHK(&c->err, hipMemcpy2DAsync(hc, (size_t)D * esz, A.xn16, (size_t)T * D * esz, (size_t)D * esz, batch, hipMemcpyDeviceToDevice, s));
+            HIPCHK(&c->err, hipMemcpy2DAsync(lc, (size_t)D, A.xlo16, (size_t)T * D, (size_t)D, batch, hipMemcpyDeviceToDevice, s));
+            GemmArgs gp = gemm_args(op_dt, A.att16, w.o, P + o.ob, hc, batch, D, D, VH_EPI_RESID_SPLIT);
             gp.out16 = lc;
             HIPCHK(&c->err, launch_gemm(gp, s));
             if ((rc = mark(ST_PROJ))) return rc;
-            HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, batch, D, f.ln_eps, stats_p, s, batch, c->guard_dev));
+            HIPCHK(&c->err, launch_finalize_stats(A.partials, nblk, batch, D, f.ln_eps, A.stats, s, batch, c->guard_dev));
             if ((rc = mark(ST_LNSTATS))) return rc;
-            const GemmArgs g1 = gemm_args(op_dt, hc, c->w1_16[l], cd + 6 * D + M, h16, batch, M, D, epi_fc1, cd + 6 * D);
+            const GemmArgs g1 = gemm_args(op_dt, hc, w.fc1, w.d_fc1, A.h16, batch, M1, D, epi_fc1, w.c_fc1);   // (no gate pass: M1 = M here, check_config)
             HIPCHK(&c->err, launch_gemm(g1, s));
             if ((rc = mark(ST_FC1))) return rc;
-            GemmArgs g2 = gemm_args(op_dt, h16, c->w2_16[l], P + o.f2b, hc, batch, D, M, VH_EPI_RESID_SPLIT);
+            GemmArgs g2 = gemm_args(op_dt, A.h16, w.fc2, P + o.f2b, hc, batch, D, M, VH_EPI_RESID_SPLIT);
             g2.out16 = lc;
             HIPCHK(&c->err, launch_gemm(g2, s));
             if ((rc = mark(ST_FC2))) return rc;
             if (head_wait) HIPCHK(&c->err, hipStreamWaitEvent(s, head_wait, 0));
-            HIPCHK(&c->err, launch_layernorm_split(hc, lc, batch, D, D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, dt16, s));
+            HIPCHK(&c->err, launch_layernorm_split(hc, lc, batch, D, D, P + L.lnfw, P + L.lnfb, f.ln_eps, A.clsn32, dt16, s));
             if ((rc = mark(ST_LNF))) return rc;
-            HIPCHK(&c->err, launch_head_f32(clsn32, P + L.headw, P + L.headb, logits, batch, f.classes, D, s));
+            HIPCHK(&c->err, launch_head_f32(A.clsn32, P + L.headw, P + L.headb, logits, batch, f.classes, D, s));
             if ((rc = mark(ST_HEAD))) return rc;
             c->last_batch = batch;
             return VH_OK;
         }
         if ((rc = stage(ST_ATTN, [&] {
-                 return hd64 ? launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true, att_tiled, qkv_hm ? (int64_t)rows_g : 0)
-                             : launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, op_dt, s);
+                 return hd64 ? launch_attention(A.qkv16, batch, T, f.heads, A.att16, op_dt, A.tickets + l, s, true, att_tiled, qkv_hm ? (int64_t)rows_g : 0)
+                             : launch_attention_hd(A.qkv16, batch, T, f.heads, c->head_dim, A.att16, op_dt, s);
              })))
             return rc;
         // out-projection and fc2 add to the residual.  Split: (out, out16) = its (hi, lo) planes; otherwise the fp32 x and, with RESID_LN,
         // the operand copy of the updated rows.  A tiled A operand goes with the weights' tiled copy.
-        GemmArgs go = gemm_args(op_dt, att16, att_tiled ? c->wot_16[l] : c->wo16[l], P + o.ob, c->split ? (void*)xn16 : x, rows_g, D, D,
+        GemmArgs go = gemm_args(op_dt, A.att16, att_tiled ? w.o_t : w.o, P + o.ob, c->split ? A.xn16 : A.x, rows_g, D, D,
                                 c->split ? VH_EPI_RESID_SPLIT : VH_EPI_RESID_LN);
-        go.out16 = c->split ? xlo16 : xn16;
-        go.wscale = so;
+        go.out16 = c->split ? A.xlo16 : A.xn16;
+        go.wscale = w.s_o;
         set_tiled(go, false, att_tiled);
         if ((rc = stage(ST_PROJ, [&] { return launch_gemm(go, s); }))) return rc;
-        HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
+        HIPCHK(&c->err, launch_finalize_stats(A.partials, nblk, rows_g, D, f.ln_eps, A.stats, s, rows, c->guard_dev, amax_guard));
         if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
         // h in its tiled layout: written straight from fc1's registers, read by fc2's DMA (same values, same bits)
-        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], cd + 6 * D + M1, swiglu ? gu16 : h16, rows_g, M1, D, epi_fc1, cd + 6 * D);
-        g1.wscale = s1;
+        GemmArgs g1 = gemm_args(op_dt, A.xn16, w.fc1, w.d_fc1, swiglu ? A.gu16 : A.h16, rows_g, M1, D, epi_fc1, w.c_fc1);
+        g1.wscale = w.s_fc1;
         set_tiled(g1, h_tiled && !swiglu, false);
         if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
         if ((rc = gate(rows_g, h_tiled))) return rc;
-        GemmArgs g2 = gemm_args(op_dt, h16, h_tiled ? c->w2t_16[l] : c->w2_16[l], P + o.f2b, c->split ? (void*)xn16 : x, rows_g, D, M,
+        GemmArgs g2 = gemm_args(op_dt, A.h16, h_tiled ? w.fc2_t : w.fc2, P + o.f2b, c->split ? A.xn16 : A.x, rows_g, D, M,
                                 c->split ? VH_EPI_RESID_SPLIT : (l + 1 < nl ? VH_EPI_RESID_LN : VH_EPI_BIAS_RESID));
-        g2.out16 = c->split ? xlo16 : xn16;
-        g2.wscale = s2;
+        g2.out16 = c->split ? A.xlo16 : A.xn16;
+        g2.wscale = w.s_fc2;
         set_tiled(g2, false, h_tiled);
         if ((rc = stage(ST_FC2, [&] { return launch_gemm(g2, s); }))) return rc;
         if ((rc = capture(l))) return rc;
         if (l + 1 < nl) {
-            HIPCHK(&c->err, launch_finalize_stats(partials_p, nblk, rows_g, D, f.ln_eps, stats_p, s, rows, c->guard_dev, amax_guard));
+            HIPCHK(&c->err, launch_finalize_stats(A.partials, nblk, rows_g, D, f.ln_eps, A.stats, s, rows, c->guard_dev, amax_guard));
             if ((rc = mark(ST_LNSTATS))) return rc;   // (no tmark, as above)
         }
     }
     // ---- the plain layer loop (bf16 / fp16 / fp8 operands) -----------------------------------------------------
     const bool plain = !c->ln_fold;
-    auto ln_rows = [&](const float* w, const float* b) { return launch_layernorm(x, rows, D, D, w, b, f.ln_eps, xn16, op_dt, s); };
+    auto ln_rows = [&](const float* w, const float* b) { return launch_layernorm(A.x, rows, D, D, w, b, f.ln_eps, A.xn16, op_dt, s); };
     // Residual GEMM (x += A W^T + bias) followed by the LayerNorm of the updated rows
     auto resid_gemm_ln = [&](const void* a, const void* w, const float* bias, const float* scale, int K, const float* lnw,
                              const float* lnb, int st_gemm) -> int {
-        GemmArgs g = gemm_args(op_dt, a, w, bias, x, rows, D, K, VH_EPI_BIAS_RESID);
+        GemmArgs g = gemm_args(op_dt, a, w, bias, A.x, rows, D, K, VH_EPI_BIAS_RESID);
         g.wscale = scale;
         if (int r = stage(st_gemm, [&] { return launch_gemm(g, s); })) return r;
         return lnw ? stage(ST_LN, [&] { return ln_rows(lnw, lnb); }) : VH_OK;
@@ -933,70 +1003,66 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     }
     for (int l = 0; l < nl && plain; ++l) {
         const LayerOff& o = L.layer[l];
-        const float *sq = c->fp8 ? c->sqkv[l] : nullptr, *so = c->fp8 ? c->so[l] : nullptr;
-        const float *s1 = c->fp8 ? c->s1[l] : nullptr, *s2 = c->fp8 ? c->s2[l] : nullptr;
-        GemmArgs gq = gemm_args(op_dt, xn16, c->wqkv16[l], c->bqkv + (size_t)l * 3 * D, qkv16, rows, 3 * D, D, VH_EPI_BIAS);
-        gq.wscale = sq;
+        const LayerW& w = c->layer[l];
+        GemmArgs gq = gemm_args(op_dt, A.xn16, w.qkv, w.bqkv, A.qkv16, rows, 3 * D, D, VH_EPI_BIAS);
+        gq.wscale = w.s_qkv;
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
         if ((rc = rope(0))) return rc;
         if ((rc = capture_attention(l, 0))) return rc;
         if ((rc = stage(ST_ATTN, [&] {
-                 return hd64 ? launch_attention(qkv16, batch, T, f.heads, att16, op_dt, tickets_part + l, s, true)
-                             : launch_attention_hd(qkv16, batch, T, f.heads, c->head_dim, att16, op_dt, s);
+                 return hd64 ? launch_attention(A.qkv16, batch, T, f.heads, A.att16, op_dt, A.tickets + l, s, true)
+                             : launch_attention_hd(A.qkv16, batch, T, f.heads, c->head_dim, A.att16, op_dt, s);
              })))
             return rc;
-        if ((rc = resid_gemm_ln(att16, c->wo16[l], P + o.ob, so, D, P + o.ln2w, P + o.ln2b, ST_PROJ))) return rc;
-        GemmArgs g1 = gemm_args(op_dt, xn16, c->w1_16[l], P + o.f1b, swiglu ? gu16 : h16, rows, M1, D, epi_fc1_plain);
-        g1.wscale = s1;
+        if ((rc = resid_gemm_ln(A.att16, w.o, P + o.ob, w.s_o, D, P + o.ln2w, P + o.ln2b, ST_PROJ))) return rc;
+        GemmArgs g1 = gemm_args(op_dt, A.xn16, w.fc1, P + o.f1b, swiglu ? A.gu16 : A.h16, rows, M1, D, epi_fc1_plain);
+        g1.wscale = w.s_fc1;
         if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
         if ((rc = gate(rows, false))) return rc;
         const bool more = l + 1 < nl;   // the next layer's LN1 follows this layer's fc2
-        if ((rc = resid_gemm_ln(h16, c->w2_16[l], P + o.f2b, s2, M, more ? P + L.layer[l + 1].ln1w : nullptr,
+        if ((rc = resid_gemm_ln(A.h16, w.fc2, P + o.f2b, w.s_fc2, M, more ? P + L.layer[l + 1].ln1w : nullptr,
                                 more ? P + L.layer[l + 1].ln1b : nullptr, ST_FC2))) return rc;
         if ((rc = capture(l))) return rc;   // behind both launches of resid_gemm_ln: x is complete and nothing writes it
     }
     // The head's input [batch][W] (vithip.h VH_FLAG_POOL).  VH_POOL_CLS: the final LayerNorm of row 0, as ever.  VH_POOL_CLS_AVG: the
     // same launch into scratch, which the pool kernel copies into columns 0 .. D - 1 beside its own D .. 2 D - 1.  The pooled modes
     // read the patch rows where the path left them (planes or the fp32 array) ONCE.  All of it under the final-LayerNorm stage.
-    const bool planes = c->split && nl > 0;
     if (head_wait) HIPCHK(&c->err, hipStreamWaitEvent(s, head_wait, 0));
     if (L.map) {
         // VH_FLAG_MAP_HEAD (vithip.h "THE FUNCTION"): ONE pass over the patch rows leaves z [batch][H][D]; everything behind it is fp32
         // on `batch` rows through the head's own exact-fp32 kernel: the per-head V product (H groups in one launch), the
         // out-projection, the block's LayerNorm, fc1, the activation, fc2 + the residual.  u lands in clsn32, the head's input.
         const int H = f.heads, hd = D / H;
-        float* const z = A.mapz32 + (size_t)img0 * H * D;
-        float* const hid = A.maph32 + (size_t)img0 * (M > D ? M : D);
-        float* const a32 = A.mapa32 + (size_t)img0 * D;                             // a [batch][D]
-        float* const o32 = A.mapa32 + ((size_t)f.max_batch + img0) * D;             // o [batch][D]
-        float* const lnrow = z;                                   // [batch][D]: z is dead once a exists
-        const PoolArgs pa{planes ? (const void*)xn16 : (const void*)x, planes ? xlo16 : nullptr, planes ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32,
-                          batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps, VH_FEAT_NORM, z};
+        float *const z = A.mapz32, *const hid = A.maph32;
+        float* const a32 = A.mapa32;                                // a [batch][D]
+        float* const o32 = A.mapa32 + (size_t)f.max_batch * D;      // o [batch][D]: the buffer's second array
+        float* const lnrow = z;                                     // [batch][D]: z is dead once a exists
+        const PoolArgs pa{resid.hi, resid.lo, resid.form, batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps, VH_FEAT_NORM, z};
         HIPCHK(&c->err, launch_map_pool(pa, P + L.map_qk, H, s));
         HIPCHK(&c->err, launch_head_f32_groups(z, (int64_t)H * D, D, P + L.map_vw, P + L.map_vb, a32, D, nullptr, batch, hd, D, H, s));
         HIPCHK(&c->err, launch_head_f32(a32, P + L.map_ow, P + L.map_ob, o32, batch, D, D, s));
         HIPCHK(&c->err, launch_layernorm(o32, batch, D, D, P + L.map_lnw, P + L.map_lnb, f.ln_eps, lnrow, VH_DTYPE_F32_INTERNAL, s));
         HIPCHK(&c->err, launch_head_f32(lnrow, P + L.map_f1w, P + L.map_f1b, hid, batch, M, D, s));
         HIPCHK(&c->err, launch_act_f32(hid, (int64_t)batch * M, quick ? 1 : tanh_gelu ? 2 : 0, s));
-        HIPCHK(&c->err, launch_head_f32_groups(hid, M, 0, P + L.map_f2w, P + L.map_f2b, clsn32, D, o32, batch, D, M, 1, s));
+        HIPCHK(&c->err, launch_head_f32_groups(hid, M, 0, P + L.map_f2w, P + L.map_f2b, A.clsn32, D, o32, batch, D, M, 1, s));
     } else if (L.pool == VH_POOL_CLS || L.pool == VH_POOL_CLS_AVG) {
-        float* const cls_ln = L.pool == VH_POOL_CLS ? clsn32 : pool32;
-        if (planes)
-            HIPCHK(&c->err, launch_layernorm_split(xn16, xlo16, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, c->fp8 ? VH_DTYPE_FP8 : dt16, s));
+        float* const cls_ln = L.pool == VH_POOL_CLS ? A.clsn32 : A.pool32;
+        if (resid.lo)
+            HIPCHK(&c->err, launch_layernorm_split(resid.hi, resid.lo, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, resid.form, s));
         else
-            HIPCHK(&c->err, launch_layernorm(x, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, VH_DTYPE_F32_INTERNAL, s));
+            HIPCHK(&c->err, launch_layernorm(A.x, batch, D, (int64_t)T * D, P + L.lnfw, P + L.lnfb, f.ln_eps, cls_ln, VH_DTYPE_F32_INTERNAL, s));
     }
     if (!L.map && L.pool != VH_POOL_CLS) {
-        PoolArgs pa{planes ? (const void*)xn16 : (const void*)x, planes ? xlo16 : nullptr, planes ? (c->fp8 ? VH_DTYPE_FP8 : dt16) : VH_FEAT_FORM_F32,
-                    batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps, L.pool == VH_POOL_AVG_FCNORM ? VH_FEAT_RAW : VH_FEAT_NORM, clsn32};
-        if (L.pool == VH_POOL_CLS_AVG) { pa.out = clsn32 + D; pa.out_stride = 2 * D; pa.cls_in = pool32; pa.cls_out = clsn32; }
-        if (L.pool == VH_POOL_AVG_FCNORM) pa.out = pool32;   // LN(mean x): the raw mean, then the fp32 LayerNorm over [batch][D]
+        PoolArgs pa{resid.hi, resid.lo, resid.form, batch, T, L.lead, D, P + L.lnfw, P + L.lnfb, f.ln_eps,
+                    L.pool == VH_POOL_AVG_FCNORM ? VH_FEAT_RAW : VH_FEAT_NORM, A.clsn32};
+        if (L.pool == VH_POOL_CLS_AVG) { pa.out = A.clsn32 + D; pa.out_stride = 2 * D; pa.cls_in = A.pool32; pa.cls_out = A.clsn32; }
+        if (L.pool == VH_POOL_AVG_FCNORM) pa.out = A.pool32;   // LN(mean x): the raw mean, then the fp32 LayerNorm over [batch][D]
         HIPCHK(&c->err, launch_pool_rows(pa, s));
         if (L.pool == VH_POOL_AVG_FCNORM)
-            HIPCHK(&c->err, launch_layernorm(pool32, batch, D, D, P + L.lnfw, P + L.lnfb, f.ln_eps, clsn32, VH_DTYPE_F32_INTERNAL, s));
+            HIPCHK(&c->err, launch_layernorm(A.pool32, batch, D, D, P + L.lnfw, P + L.lnfb, f.ln_eps, A.clsn32, VH_DTYPE_F32_INTERNAL, s));
     }
     if ((rc = mark(ST_LNF))) return rc;
-    HIPCHK(&c->err, launch_head_f32(clsn32, P + L.headw, P + L.headb, logits, batch, f.classes, L.HW, s));
+    HIPCHK(&c->err, launch_head_f32(A.clsn32, P + L.headw, P + L.headb, logits, batch, f.classes, L.HW, s));
     if ((rc = mark(ST_HEAD))) return rc;
     c->last_batch = batch;
     return VH_OK;
@@ -1127,27 +1193,19 @@ int guard_calibrate(vh_ctx* c) {
 }
 
 // ---- two forwards in flight ---------------------------------------------------------------------------------------------
-void bind_set(ActSet& a, char* base, const ActSetLayout& o, bool map, bool swiglu) {
-    if (swiglu) a.gu16 = base + o.gu;
-    a.x = (float*)(base + o.x); a.xn16 = base + o.xn; a.qkv16 = base + o.qkv; a.att16 = base + o.att; a.h16 = base + o.h;
-    a.col16 = base + o.col; a.clsn32 = (float*)(base + o.cls); a.pool32 = (float*)(base + o.pool);
-    a.stats = (float*)(base + o.st); a.partials = (float*)(base + o.pt); a.xlo16 = base + o.xlo;
-    a.tickets = (unsigned int*)(base + o.tk);
-    if (map) { a.mapz32 = (float*)(base + o.mz); a.maph32 = (float*)(base + o.mh); a.mapa32 = (float*)(base + o.ma); }
-}
 // The second buffer set, allocated the first time it is needed (callers are outside any stream capture: graph replay is
 // single-flight).  No memory for it: the context stays single-flight for good and reports no error.
 bool second_set(vh_ctx* c) {
     if (c->act[1].base) return true;
     if (c->inflight_max < 2) return false;
     char* p = nullptr;
-    if (hipMalloc((void**)&p, c->act_layout.bytes) != hipSuccess) {
+    if (hipMalloc((void**)&p, c->act_bytes) != hipSuccess) {
         (void)hipGetLastError();
         c->inflight_max = 1;
         return false;
     }
     c->act[1].base = p;
-    bind_set(c->act[1], p, c->act_layout, c->L.map, c->L.swiglu);
+    bind_set(c, &c->act[1], p);
     return true;
 }
 // May consecutive forwards of this context run two at a time?  Not where a launch is timed (a duration beside another forward's
@@ -1324,16 +1382,7 @@ int frames_reserve(vh_ctx* c, size_t plan_words, bool host_too, size_t frame_byt
 // plan upload + the one resize launch, on the context's stream (ahead of the fork of vh_set_streams); c->rz_u8 then holds the
 // batch the forward reads.  Stage "resize" of vh_set_stage_timing brackets the launch.
 int enqueue_resize(vh_ctx* c, const FrameJob& j, int batch) {
-    auto tmark = [&]() -> int {
-        if (c->timing_stage != ST_RESIZE) return VH_OK;
-        if (c->tev_used == c->tev.size()) {
-            hipEvent_t e;
-            HIPCHK(&c->err, hipEventCreate(&e));
-            c->tev.push_back(e);
-        }
-        HIPCHK(&c->err, hipEventRecord(c->tev[c->tev_used++], c->stream));
-        return VH_OK;
-    };
+    auto tmark = [&]() -> int { return c->timing_stage == ST_RESIZE ? record_next(c, c->tev, c->tev_used, c->stream) : VH_OK; };
     int rc;
     HIPCHK(&c->err, hipMemcpyAsync(c->rz_plan_dev, j.plan_host, j.words * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = tmark())) return rc;
@@ -1351,16 +1400,7 @@ int forward_device_async(vh_ctx* c, ImgIn in, int batch, float* logits, int step
     HIPCHK(&c->err, hipSetDevice(c->device));
     c->tev_used = 0;
     c->sev_used = 0;
-    auto step_mark = [&]() -> int {
-        if (!c->step_timing) return VH_OK;
-        if (c->sev_used == c->sev.size()) {
-            hipEvent_t e;
-            HIPCHK(&c->err, hipEventCreate(&e));
-            c->sev.push_back(e);
-        }
-        HIPCHK(&c->err, hipEventRecord(c->sev[c->sev_used++], c->stream));
-        return VH_OK;
-    };
+    auto step_mark = [&]() -> int { return c->step_timing ? record_next(c, c->sev, c->sev_used, c->stream) : VH_OK; };
     HIPCHK(&c->err, hipEventRecord(c->ev0, c->stream));
     if ((rc = step_mark())) return rc;
     if (job && (rc = enqueue_resize(c, *job, batch))) return rc;
@@ -1514,7 +1554,6 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     c->device = device;
     const Layout& L = c->L;
     const size_t D = cfg->dim, M = cfg->mlp_dim, M1 = (size_t)L.M1, C = cfg->classes, B = cfg->max_batch;   // M1: fc1's width (2 M with VH_FLAG_SWIGLU)
-    const size_t rows = B * (size_t)L.T;
     auto bail = [&](int code) { vh_destroy(c); return code; };
 #define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return bail(VH_ERR_HIP); } } while (0)
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -1547,22 +1586,20 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     // canonical blob
     CK(hipMalloc((void**)&c->blob, sizeof(BlobHeader) + 4 * L.total));
     c->params = (float*)(c->blob + sizeof(BlobHeader));
-    // 16-bit weights
+    // the weight arena: offsets first; the layer records below, once it is allocated
     size_t w16_bytes = 0;
     auto carve16 = [&](size_t elems) { size_t o = w16_bytes; w16_bytes += align_up(elems * 2, 256); return o; };
     const size_t o_wp = carve16(D * L.KPA);
-    std::vector<size_t> o_qkv(cfg->layers), o_o(cfg->layers), o_1(cfg->layers), o_2(cfg->layers), o_2t(cfg->layers);
+    struct MatOff { size_t qkv, o, fc1, fc2, fc2_t, o_t; };
+    std::vector<MatOff> off(cfg->layers);
     const bool want_tiled_any = D % 256 == 0 && M % 256 == 0 && !(getenv("VH_H_TILED") && getenv("VH_H_TILED")[0] == '0');
     const bool want_tiled = cfg->dtype != VH_DTYPE_FP8 && want_tiled_any;
     const bool want_tiled8 = cfg->dtype == VH_DTYPE_FP8 && want_tiled_any;   // e4m3 operands: fc2's weights (bytes) in the tiled e4m3 layout
-    for (int l = 0; l < cfg->layers; ++l) {
-        o_qkv[l] = carve16(3 * D * D); o_o[l] = carve16(D * D); o_1[l] = carve16(M1 * D); o_2[l] = carve16(D * M);
-        o_2t[l] = want_tiled ? carve16(D * M) : want_tiled8 ? carve16((D * M + 1) / 2) : 0;
+    for (auto& o : off) {
+        o.qkv = carve16(3 * D * D); o.o = carve16(D * D); o.fc1 = carve16(M1 * D); o.fc2 = carve16(D * M);
+        o.fc2_t = want_tiled ? carve16(D * M) : want_tiled8 ? carve16((D * M + 1) / 2) : 0;
     }
-    std::vector<size_t> o_ot(cfg->layers);
-    for (int l = 0; l < cfg->layers; ++l) o_ot[l] = want_tiled ? carve16(D * D) : want_tiled8 ? carve16((D * D + 1) / 2) : 0;
-    const size_t o_bqkv = w16_bytes;
-    w16_bytes += align_up((size_t)cfg->layers * 3 * D * 4, 256);
+    for (auto& o : off) o.o_t = want_tiled ? carve16(D * D) : want_tiled8 ? carve16((D * D + 1) / 2) : 0;
     {
         // LayerNorm folded into the neighbouring GEMMs: a property of the MODEL SHAPE and of vh_config.flags only -- never of
         // max_batch, so that a context sized for 1 image and one sized for 512 give the same logit bits for the same image
@@ -1587,7 +1624,6 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     yuv_matrix(VH_YUV_BT709, 0, c->colour[0].m);   // NV12 frames: what an HD video decoder emits, until vh_set_frame_colour says otherwise
     yuv_matrix16(VH_YUV_BT709, 0, 10, 1, c->colour[1].m);   // 16-bit frames: P010 as VCN writes it, until vh_set_frame_colour16 says otherwise
     {
-        // (fp8 operands: the hi plane is e4m3 -- the GEMM operand itself -- and the lo plane bf16: 3 bytes per element as well)
         const char* e = getenv("VH_RESID_SPLIT");
         c->split = c->ln_fold && !(e && e[0] == '0');
         c->ln_fold_cfg = c->ln_fold;
@@ -1602,47 +1638,34 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     }
     CK(hipHostMalloc((void**)&c->guard_host, 64, hipHostMallocDefault));
     *c->guard_host = 0.f;
-    const size_t o_cd = w16_bytes;
-    w16_bytes += align_up((size_t)cfg->layers * (6 * D + 2 * M1) * 4, 256);
-    const size_t o_sc = w16_bytes, sc_per_layer = 5 * D + M;  // fp8: scales of q|k|v (3D), o (D), fc1 (M), fc2 (D)
-    if (c->fp8) w16_bytes += align_up((size_t)cfg->layers * sc_per_layer * 4, 256);
+    // per layer: the fold constants c_qkv[3D] d_qkv[3D] c_fc1[M1] d_fc1[M1]; on fp8 contexts the scales s_qkv[3D] s_o[D] s_fc1[M1] s_fc2[D]
+    const size_t cd_per_layer = 6 * D + 2 * M1, sc_per_layer = 5 * D + M1, nl = cfg->layers;   // in floats = two 16-bit elements
+    const size_t o_bqkv = carve16(nl * 3 * D * 2), o_cd = carve16(nl * cd_per_layer * 2), o_sc = c->fp8 ? carve16(nl * sc_per_layer * 2) : 0;
     CK(hipMalloc((void**)&c->w16, w16_bytes));
-    c->wp16 = c->w16 + o_wp; c->bqkv = (float*)(c->w16 + o_bqkv);
-    c->fold_cd = (float*)(c->w16 + o_cd);
+    c->wp16 = c->w16 + o_wp;
+    c->layer.resize(cfg->layers);
     for (int l = 0; l < cfg->layers; ++l) {
-        c->wqkv16.push_back(c->w16 + o_qkv[l]); c->wo16.push_back(c->w16 + o_o[l]);
-        c->w1_16.push_back(c->w16 + o_1[l]); c->w2_16.push_back(c->w16 + o_2[l]);
-        c->w2t_16.push_back(want_tiled || want_tiled8 ? c->w16 + o_2t[l] : nullptr);
-        c->wot_16.push_back(want_tiled || want_tiled8 ? c->w16 + o_ot[l] : nullptr);
+        LayerW& w = c->layer[l];
+        const MatOff& o = off[l];
+        w.qkv = c->w16 + o.qkv; w.o = c->w16 + o.o; w.fc1 = c->w16 + o.fc1; w.fc2 = c->w16 + o.fc2;
+        if (want_tiled || want_tiled8) { w.fc2_t = c->w16 + o.fc2_t; w.o_t = c->w16 + o.o_t; }
+        w.bqkv = (float*)(c->w16 + o_bqkv) + (size_t)l * 3 * D;
+        w.c_qkv = (float*)(c->w16 + o_cd) + (size_t)l * cd_per_layer;
+        w.d_qkv = w.c_qkv + 3 * D; w.c_fc1 = w.d_qkv + 3 * D; w.d_fc1 = w.c_fc1 + M1;
         if (c->fp8) {
-            float* sc = (float*)(c->w16 + o_sc) + (size_t)l * sc_per_layer;
-            c->sqkv.push_back(sc); c->so.push_back(sc + 3 * D); c->s1.push_back(sc + 4 * D); c->s2.push_back(sc + 4 * D + M);
+            w.s_qkv = (float*)(c->w16 + o_sc) + (size_t)l * sc_per_layer;
+            w.s_o = w.s_qkv + 3 * D; w.s_fc1 = w.s_o + D; w.s_fc2 = w.s_fc1 + M1;
         }
     }
-    // activation arena: buffer set 0 (the layout serves the second set too), then what both sets share
-    size_t a = 0;
+    // activation arena: buffer set 0 (the table serves the second set too), then what both sets share
+    size_t a = c->act_bytes = bind_set(c, nullptr, nullptr);
     auto carve = [&](size_t bytes) { size_t o = a; a += align_up(bytes, 256); return o; };
-    // room for whole 256-row GEMM tiles behind the LAST part of a forward (enqueue_forward, rows_g): its rows start anywhere,
-    // so the padding may reach up to 255 rows past the last real row
-    const size_t rows_p = rows + 256;
-    ActSetLayout& o = c->act_layout;
-    o.x = carve(rows_p * D * 4); o.xn = carve(rows_p * D * 2); o.qkv = carve(rows_p * 3 * D * 2);
-    o.att = carve(rows_p * D * 2); o.h = carve(rows_p * M * 2); o.col = carve(B * L.NP * (size_t)L.KPA * 2);
-    o.cls = carve(B * 2 * D * 4); o.pool = carve(B * D * 4);   // the head's input [B][W <= 2 D]; VH_FLAG_POOL scratch [B][D]
-    o.st = carve(rows_p * 2 * 4); o.pt = carve((D / 64 + 1) * rows_p * 2 * 4);
-    o.xlo = carve(rows_p * D * 2);   // lo plane: one byte per element (16-bit paths) or bf16 (fp8 path)
-    o.tk = carve(B * 4 * (size_t)(cfg->layers > 0 ? cfg->layers : 1));   // attention work-queue counters: one word per image and layer, a part uses its first image's
-    // VH_FLAG_MAP_HEAD: z, the hidden rows, and the rows a | o
-    o.mz = L.map ? carve(B * (size_t)cfg->heads * D * 4) : 0; o.mh = L.map ? carve(B * (M > D ? M : D) * 4) : 0;
-    o.ma = L.map ? carve(B * 2 * D * 4) : 0;
-    o.gu = L.swiglu ? carve(rows_p * 2 * M * 2) : 0;   // VH_FLAG_SWIGLU: fc1's [rows][2 M] output, in both sets (part of o.bytes)
-    o.bytes = a;
     const size_t o_in = carve(B * (size_t)cfg->image_size * cfg->image_size * cfg->channels * 4), o_lg = carve(B * C * 4),
                  o_gd = carve(256);     // the LayerNorm-fold guard word
     CK(hipMalloc((void**)&c->arena, a));
     c->guard_dev = (unsigned int*)(c->arena + o_gd);
     CK(hipMemsetAsync(c->guard_dev, 0, 256, c->stream));
-    bind_set(c->act[0], c->arena, o, L.map, L.swiglu);
+    bind_set(c, &c->act[0], c->arena);
     c->in_dev = (float*)(c->arena + o_in); c->logits_dev = (float*)(c->arena + o_lg);
 #undef CK
     *out = c;
@@ -2540,34 +2563,31 @@ int vh_debug_read(vh_ctx* c, int what, float* host_out, size_t n_floats) {
     if (what == 0) {
         const size_t n = (size_t)c->last_batch * c->L.T * D;
         if (n_floats != n) return fail(&c->err, VH_ERR_INVALID, "expected %zu floats", n);
-        const int nl = (c->run_layers < 0 || c->run_layers > c->cfg.layers) ? c->cfg.layers : c->run_layers;
-        if (c->split && nl > 0) {   // the residual stream lives as two planes: x = hi (16 bit) + lo (one scaled e4m3 byte)
-            auto f = [&](uint16_t b, int dt) {
-                if (dt == VH_DTYPE_BF16) { uint32_t u = (uint32_t)b << 16; float v; memcpy(&v, &u, 4); return v; }
-                _Float16 hv; memcpy(&hv, &b, 2); return (float)hv;
-            };
-            auto g = [&](uint8_t b) {   // OCP e4m3fn -> float
-                const int e = (b >> 3) & 15, m = b & 7;
-                float v = e ? ldexpf(1.f + m / 8.f, e - 7) : ldexpf(m / 8.f, -6);
-                return (b & 0x80) ? -v : v;
-            };
-            if (c->fp8) {   // e4m3 hi plane (the GEMM operand) + bf16 lo plane
-                std::vector<uint8_t> hi(n);
-                std::vector<uint16_t> lo(n);
-                HIPCHK(&c->err, hipMemcpy(hi.data(), c->act[c->last_set].xn16, n, hipMemcpyDeviceToHost));
-                HIPCHK(&c->err, hipMemcpy(lo.data(), c->act[c->last_set].xlo16, n * 2, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < n; ++i) host_out[i] = g(hi[i]) + f(lo[i], VH_DTYPE_BF16);
-                return VH_OK;
-            }
-            std::vector<uint16_t> hi(n);
-            std::vector<uint8_t> lo(n);
-            HIPCHK(&c->err, hipMemcpy(hi.data(), c->act[c->last_set].xn16, n * 2, hipMemcpyDeviceToHost));
-            HIPCHK(&c->err, hipMemcpy(lo.data(), c->act[c->last_set].xlo16, n, hipMemcpyDeviceToHost));
-            const float inv = c->dt16 == VH_DTYPE_BF16 ? 1.f / 32.f : 1.f / 256.f;   // the byte plane's scale (vh_common.h Lo8<T>)
-            for (size_t i = 0; i < n; ++i) host_out[i] = f(hi[i], c->dt16) + g(lo[i]) * inv;
+        const ResidView v = resid_view(c, c->act[c->last_set], layers_to_run(c));
+        if (!v.lo) {
+            HIPCHK(&c->err, hipMemcpy(host_out, v.hi, n * 4, hipMemcpyDeviceToHost));
             return VH_OK;
         }
-        HIPCHK(&c->err, hipMemcpy(host_out, c->act[c->last_set].x, n * 4, hipMemcpyDeviceToHost));
+        // two planes, x = hi + lo, decoded on the host: the view of the planes that shares no code with the kernels that read them
+        auto f = [&](const uint8_t* p, int dt) {   // two bytes of a 16-bit plane -> float
+            uint16_t b; memcpy(&b, p, 2);
+            if (dt == VH_DTYPE_BF16) { uint32_t u = (uint32_t)b << 16; float x; memcpy(&x, &u, 4); return x; }
+            _Float16 hv; memcpy(&hv, &b, 2); return (float)hv;
+        };
+        auto g = [&](uint8_t b) {   // OCP e4m3fn -> float
+            const int e = (b >> 3) & 15, m = b & 7;
+            float x = e ? ldexpf(1.f + m / 8.f, e - 7) : ldexpf(m / 8.f, -6);
+            return (b & 0x80) ? -x : x;
+        };
+        std::vector<uint8_t> hi(n * hi_bytes(v.form)), lo(n * lo_bytes(v.form));
+        HIPCHK(&c->err, hipMemcpy(hi.data(), v.hi, hi.size(), hipMemcpyDeviceToHost));
+        HIPCHK(&c->err, hipMemcpy(lo.data(), v.lo, lo.size(), hipMemcpyDeviceToHost));
+        if (v.form == VH_DTYPE_FP8) {   // e4m3 hi plane (the GEMM operand) + bf16 lo plane
+            for (size_t i = 0; i < n; ++i) host_out[i] = g(hi[i]) + f(&lo[2 * i], VH_DTYPE_BF16);
+            return VH_OK;
+        }
+        const float inv = v.form == VH_DTYPE_BF16 ? Lo8<BF16>::inv : Lo8<FP16>::inv;   // the byte plane's scale
+        for (size_t i = 0; i < n; ++i) host_out[i] = f(&hi[2 * i], v.form) + g(lo[i]) * inv;
         return VH_OK;
     }
     if (what == 1) {
@@ -2619,14 +2639,10 @@ static int features_check_call(vh_ctx* c, const vh_features* f, bool device) {
     return VH_OK;
 }
 // where the rows of a read-out live, and whether its normalised class-token rows are the head's (the final state: clsn32)
-struct FeatSource { const void* hi; const void* lo; int form; bool head_cls; };
+struct FeatSource : ResidView { bool head_cls; };
 static FeatSource features_live(const vh_ctx* c) {
-    const vh_config& g = c->cfg;
-    const int nl = (c->run_layers < 0 || c->run_layers > g.layers) ? g.layers : c->run_layers;
-    const bool planes = c->split && nl > 0;   // where the last forward left the rows: the two planes, or the fp32 array
-    const ActSet& A = c->act[c->last_set];   // the final layer's rows are the live residual of the most recently enqueued forward
-    return FeatSource{planes ? (const void*)A.xn16 : (const void*)A.x, planes ? A.xlo16 : nullptr,
-                      planes ? (c->fp8 ? VH_DTYPE_FP8 : c->dt16) : VH_FEAT_FORM_F32, c->L.pool == VH_POOL_CLS};   // (a pooled head's input is not LN(row 0))
+    // the final layer's rows are the live residual of the most recently enqueued forward
+    return FeatSource{resid_view(c, c->act[c->last_set], layers_to_run(c)), c->L.pool == VH_POOL_CLS};   // (a pooled head's input is not LN(row 0))
 }
 static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSource& src, const char* who) {
     const vh_config& g = c->cfg;
@@ -2654,19 +2670,27 @@ static int features_enqueue(vh_ctx* c, const vh_layer_features& f, const FeatSou
 }
 // the host form: the outputs are staged in the q|k|v buffer -- scratch between forwards (every forward writes its rows before
 // attention reads them), and at 6 bytes per row element always large enough for fp32 rows of every token + the two [batch][D] outputs
+struct Staging {
+    char* base;
+    size_t cap, at = 0;
+    explicit Staging(const vh_ctx* c) : base((char*)c->act[c->last_set].qkv16), cap(act_buffer_bytes(c, &ActSet::qkv16)) {}
+    void* take(const void* want, size_t bytes) {
+        if (!want) return nullptr;
+        void* const p = base + at;
+        at += align_up(bytes, 256);
+        return p;
+    }
+};
 static int features_read_host(vh_ctx* c, const vh_layer_features& f, const FeatSource& src, const char* who) {
     const size_t es = f.elem == VH_ELEM_F32 ? 4 : 2, D = c->cfg.dim, B = c->last_batch;
     const size_t n_row = B * D * es, n_patch = B * (size_t)c->L.NP * D * es, n_reg = B * (size_t)c->L.R * D * es;
-    const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * D * 2;
-    char* const base = (char*)c->act[c->last_set].qkv16;
-    size_t at = 0;
-    auto take = [&](bool want, size_t bytes) -> void* { if (!want) return nullptr; void* p = base + at; at += align_up(bytes, 256); return p; };
+    Staging st(c);
     vh_layer_features d = f;
-    d.patch = take(f.patch != nullptr, n_patch);
-    d.cls = take(f.cls != nullptr, n_row);
-    d.mean = take(f.mean != nullptr, n_row);
-    d.reg = take(f.reg != nullptr, n_reg);
-    if (at > cap) return fail(&c->err, VH_ERR_STATE, "%s: staging needs %zu bytes, the scratch holds %zu", who, at, cap);
+    d.patch = st.take(f.patch, n_patch);
+    d.cls = st.take(f.cls, n_row);
+    d.mean = st.take(f.mean, n_row);
+    d.reg = st.take(f.reg, n_reg);
+    if (st.at > st.cap) return fail(&c->err, VH_ERR_STATE, "%s: staging needs %zu bytes, the scratch holds %zu", who, st.at, st.cap);
     if (int rc = features_enqueue(c, d, src, who)) return rc;
     if (f.patch) HIPCHK(&c->err, hipMemcpyAsync(f.patch, d.patch, n_patch, hipMemcpyDeviceToHost, c->stream));
     if (f.cls) HIPCHK(&c->err, hipMemcpyAsync(f.cls, d.cls, n_row, hipMemcpyDeviceToHost, c->stream));
@@ -2704,16 +2728,21 @@ int vh_read_features(vh_ctx* c, const vh_features* f) {
 
 // ---- layer features (vithip.h "Layer features") ---------------------------------------------------------------------------
 // The list and the capture store; enqueue_forward copies into the store and records what it captured (cap_*).
-int vh_set_feature_layers(vh_ctx* c, const int* layers, int n) {
-    if (!c) return fail(nullptr, VH_ERR_INVALID, "set_feature_layers: null context");
-    if (n < 0 || n > VH_MAX_FEATURE_LAYERS) return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: %d layers, outside 0..%d", n, VH_MAX_FEATURE_LAYERS);
-    if (n > 0 && !layers) return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: null list");
+// a layer list of `who` (the call's name in the messages): at most max_n entries, each 1 .. layers, strictly ascending
+static int check_layer_list(vh_ctx* c, const char* who, const int* layers, int n, int max_n) {
+    if (n < 0 || n > max_n) return fail(&c->err, VH_ERR_INVALID, "%s: %d layers, outside 0..%d", who, n, max_n);
+    if (n > 0 && !layers) return fail(&c->err, VH_ERR_INVALID, "%s: null list", who);
     for (int i = 0; i < n; ++i) {
         if (layers[i] < 1 || layers[i] > c->cfg.layers)
-            return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: entry %d is layer %d, outside 1..%d", i, layers[i], c->cfg.layers);
+            return fail(&c->err, VH_ERR_INVALID, "%s: entry %d is layer %d, outside 1..%d", who, i, layers[i], c->cfg.layers);
         if (i && layers[i] <= layers[i - 1])
-            return fail(&c->err, VH_ERR_INVALID, "set_feature_layers: the list must be strictly ascending (entry %d is %d after %d)", i, layers[i], layers[i - 1]);
+            return fail(&c->err, VH_ERR_INVALID, "%s: the list must be strictly ascending (entry %d is %d after %d)", who, i, layers[i], layers[i - 1]);
     }
+    return VH_OK;
+}
+int vh_set_feature_layers(vh_ctx* c, const int* layers, int n) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "set_feature_layers: null context");
+    if (int rc = check_layer_list(c, "set_feature_layers", layers, n, VH_MAX_FEATURE_LAYERS)) return rc;
     if (n > 0 && (c->cfg.flags & VH_FLAG_CLS_TAIL))
         return fail(&c->err, VH_ERR_UNSUPPORTED, "set_feature_layers: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
     if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "set_feature_layers: a ring exists on this context; vh_ring_destroy first");
@@ -2721,9 +2750,10 @@ int vh_set_feature_layers(vh_ctx* c, const int* layers, int n) {
     HIPCHK(&c->err, sync_compute(c));
     int slots = 0;
     for (int i = 0; i < n; ++i) slots += layers[i] < c->cfg.layers;
-    // 3 bytes per element where the residual stays two planes for good; 4 where it is, or may become (the guarded fold), the fp32 array
-    const int eb = c->split_cfg && !c->guard_auto ? 3 : 4;
-    const size_t slot = align_up((size_t)c->cfg.max_batch * c->L.T * c->cfg.dim * eb, 256);
+    // sized for the planes where the residual stays two planes for good (the configured split, no guard that may leave it: split then
+    // equals split_cfg, so resid_form gives the planes' form); for fp32 rows where it is, or may become, the fp32 array
+    const int form = c->split_cfg && !c->guard_auto ? resid_form(c, c->cfg.layers) : VH_FEAT_FORM_F32;
+    const size_t slot = align_up((size_t)c->cfg.max_batch * c->L.T * c->cfg.dim * (hi_bytes(form) + lo_bytes(form)), 256);
     char* store = nullptr;
     if (slots) {
         const hipError_t e = hipMalloc((void**)&store, slot * slots);
@@ -2785,10 +2815,7 @@ static int layer_features_check_call(vh_ctx* c, const vh_layer_features* f, bool
         src->head_cls = src->head_cls && f->layer == layers;
         return VH_OK;
     }
-    const char* const base = c->feat_store + (size_t)slot * c->feat_slot;
-    const size_t all = (size_t)c->cfg.max_batch * c->L.T * c->cfg.dim;
-    if (c->cap_form == VH_FEAT_FORM_F32) *src = FeatSource{base, nullptr, VH_FEAT_FORM_F32, false};
-    else *src = FeatSource{base, base + all * (c->cap_form == VH_DTYPE_FP8 ? 1 : 2), c->cap_form, false};
+    *src = FeatSource{slot_view(c, slot, c->cap_form), false};
     return VH_OK;
 }
 int vh_read_layer_features_device_async(vh_ctx* c, const vh_layer_features* f) {
@@ -2813,14 +2840,7 @@ int vh_read_layer_features(vh_ctx* c, const vh_layer_features* f) {
 // The list and the store; enqueue_forward runs the capture kernel into the store and records what it captured (acap_*).
 int vh_set_attention_layers(vh_ctx* c, const int* layers, int n, int queries) {
     if (!c) return fail(nullptr, VH_ERR_INVALID, "set_attention_layers: null context");
-    if (n < 0 || n > VH_MAX_ATTENTION_LAYERS) return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: %d layers, outside 0..%d", n, VH_MAX_ATTENTION_LAYERS);
-    if (n > 0 && !layers) return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: null list");
-    for (int i = 0; i < n; ++i) {
-        if (layers[i] < 1 || layers[i] > c->cfg.layers)
-            return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: entry %d is layer %d, outside 1..%d", i, layers[i], c->cfg.layers);
-        if (i && layers[i] <= layers[i - 1])
-            return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: the list must be strictly ascending (entry %d is %d after %d)", i, layers[i], layers[i - 1]);
-    }
+    if (int rc = check_layer_list(c, "set_attention_layers", layers, n, VH_MAX_ATTENTION_LAYERS)) return rc;
     if (queries != VH_ATTN_Q_CLS && queries != VH_ATTN_Q_LEAD)
         return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: queries %d is not VH_ATTN_Q_CLS (0) or VH_ATTN_Q_LEAD (1)", queries);
     if (n > 0 && queries == VH_ATTN_Q_CLS && !c->L.ncls)
@@ -2924,12 +2944,11 @@ int vh_read_attention(vh_ctx* c, const vh_attention_maps* f) {
     const size_t es = f->elem == VH_ELEM_F32 ? 4 : 2, B = c->last_batch, Q = c->attn_q;
     const size_t K = f->keys == VH_ATTN_KEYS_PATCH ? c->L.NP : c->L.T;
     const size_t n_probs = B * c->cfg.heads * Q * K * es, n_mean = B * Q * K * es;
-    const size_t cap = ((size_t)c->cfg.max_batch * c->L.T + 256) * 3 * c->cfg.dim * 2;
+    Staging st(c);
     vh_attention_maps d = *f;
-    size_t at = 0;
-    if (f->probs) { d.probs = (char*)c->act[c->last_set].qkv16 + at; at += align_up(n_probs, 256); }
-    if (f->head_mean) { d.head_mean = (char*)c->act[c->last_set].qkv16 + at; at += align_up(n_mean, 256); }
-    if (at > cap) return fail(&c->err, VH_ERR_STATE, "read_attention: staging needs %zu bytes, the scratch holds %zu", at, cap);
+    d.probs = st.take(f->probs, n_probs);
+    d.head_mean = st.take(f->head_mean, n_mean);
+    if (st.at > st.cap) return fail(&c->err, VH_ERR_STATE, "read_attention: staging needs %zu bytes, the scratch holds %zu", st.at, st.cap);
     if (int rc = attention_enqueue(c, d, slot)) return rc;
     if (f->probs) HIPCHK(&c->err, hipMemcpyAsync(f->probs, d.probs, n_probs, hipMemcpyDeviceToHost, c->stream));
     if (f->head_mean) HIPCHK(&c->err, hipMemcpyAsync(f->head_mean, d.head_mean, n_mean, hipMemcpyDeviceToHost, c->stream));
