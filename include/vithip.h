@@ -258,6 +258,31 @@ typedef struct vh_config {
  *   gives h = 0 for every finite u.  A row's bits depend on that row alone. */
 #define VH_FLAG_SWIGLU (1 << 25)
 
+/* Attention bias (BEiT, BEiT v2 and data2vec-vision's relative position bias -- the BEiT-L backbones of MiDaS 3.1 / DPT --, timm's
+ * vit_relpos_*, any fixed additive mask): ONE MODEL switch, in bit 27 of flags and, at the same position, of the blob header's flags
+ * word; a blob whose bit differs from the context's is refused with a message that names the bit.  With the bit clear nothing changes:
+ * not one launch.
+ *   VH_FLAG_ATTN_BIAS  every layer's attention is softmax(q k^T / sqrt(hd) + B[l][h]) v.  Excludes, each with a message of its own
+ *                      (vh_weight_blob_bytes returns 0): VH_FLAG_CLS_TAIL (its one-query kernel adds no bias) and VH_DTYPE_FP8.
+ *                      vh_set_attention_layers with a non-empty list is refused (VH_ERR_UNSUPPORTED): the capture kernel would
+ *                      report maps without the bias.  Everything else combines: VH_FLAG_W8_E4M3, PRE_LN, registers, NO_CLS, the
+ *                      pool modes, ROPE, SWIGLU, two forwards in flight, graphs, rings, token and layer features.
+ *   Blob tensor of such a context, the LAST one (behind rope.* where both flags are set):
+ *     attn_bias [layers][H][T][T] fp32, T = ALL tokens (class token and registers included, in row order), [query][key], in
+ *     natural-log units: what the model adds to the scores after the hd^-1/2 scale.  vh_init_weights_seeded fills it from a
+ *     tensor id of the library's own (0x7040) with sigma 3.
+ *   VALUES: every entry is finite -- a contract, like finite activations.  A large negative finite entry (-1e4) masks its key: the
+ *   online softmax re-centres when a later tile outgrows the running shift.  +-inf and NaN are the caller's error.
+ *   ARITHMETIC, for bits.  At weight load every entry is multiplied ONCE in fp32 by (float)log2(e) = 1.44269502f (one rounding) and
+ *   stored in the kernel's fragment order (vh_op_attention_bias_image; queries and keys zero-padded to multiples of 32).  The kernel
+ *   works in the exp2 domain on q pre-scaled by hd^-1/2 * log2(e): the fp32 score accumulator of a (32 query, 32 key) tile STARTS
+ *   from that entry plus the negated running shift (first key tile: from the entry itself) and the MFMAs add q . k onto it; a zero
+ *   bias therefore gives the bits of vh_op_attention_hd.  Masks, row maximum, deferred rescale, sums, P rounding and P V are the
+ *   unbiased kernel's.  q|k|v and the attention output stay row-major at every head dim, 64 included (the routing the other head
+ *   dims take), so a head-dim-64 context with the flag runs the K/V-streaming kernel, not the resident forms.  An image's bits
+ *   depend on its rows alone (batch size, graph replay and split batches do not change them). */
+#define VH_FLAG_ATTN_BIAS (1 << 27)
+
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
 
@@ -298,7 +323,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model, bit 23 = VH_FLAG_ROPE model, bit 25 = VH_FLAG_SWIGLU model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model, bit 23 = VH_FLAG_ROPE model, bit 25 = VH_FLAG_SWIGLU model, bit 27 = VH_FLAG_ATTN_BIAS model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -318,7 +343,7 @@ int vh_export_weights_device(vh_ctx* ctx, void* dev_blob, size_t nbytes);
  *   vh_blob_file_config: host only (no device needed) -- validates magic / shape / file length and fills the model
  *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create;
  *                        cfg->flags = the model bits of the header: VH_FLAG_PRE_LN, VH_FLAG_QUICK_GELU, VH_FLAG_REGISTERS(n), VH_FLAG_NO_CLS,
- *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU, VH_FLAG_ROPE, VH_FLAG_SWIGLU);
+ *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU, VH_FLAG_ROPE, VH_FLAG_SWIGLU, VH_FLAG_ATTN_BIAS);
  *   vh_save_weights_file: writes <path>.tmp then renames; vh_load_weights_file: verifies length, shape, checksum. */
 int vh_blob_file_config(const char* path, vh_config* cfg);
 /* host only: the file as a MEMORY blob (what vh_load_weights takes): length, header and checksum verified, checksum
@@ -1244,6 +1269,18 @@ int vh_op_attention_stream(const void* qkv16_dev, int batch, int tokens, int hea
  * head_dim^-1/2 * log2(e), tokens 1..4097, heads*head_dim <= 2048.  dtype VH_DTYPE_FP8: bf16 q|k|v in, e4m3 out. */
 int vh_op_attention_hd(const void* qkv16_dev, int batch, int tokens, int heads, int head_dim, void* out16_dev,
                        int dtype, void* stream);
+/* Attention with an additive per-head bias on its own ("Attention bias" at VH_FLAG_ATTN_BIAS): the kernel of such a context.
+ *   vh_attention_bias_image_bytes: the size of the fragment image of one [heads][tokens][tokens] bias, heads * ceil(tokens / 32)^2 *
+ *     4096; 0 for heads outside 1..64 or tokens outside 1..4097.  Host only.
+ *   vh_op_attention_bias_image: bias_f32_dev [heads][tokens][tokens] (natural-log units, finite) -> image_dev (16-byte aligned, that
+ *     many bytes): entries * log2(e) in fp32, zero-padded, fragment order.
+ *   vh_op_attention_bias: vh_op_attention_hd's shapes and layouts plus the image; dtype VH_DTYPE_BF16 or VH_DTYPE_FP16.
+ * Arguments are checked on the host before a device is touched (VH_ERR_INVALID: null or misaligned pointers, tokens outside 1..4097,
+ * head dims other than 32, 48, ..., 128, heads * head_dim > 2048, VH_DTYPE_FP8). */
+size_t vh_attention_bias_image_bytes(int heads, int tokens);
+int vh_op_attention_bias_image(const float* bias_f32_dev, int heads, int tokens, float* image_dev, void* stream);
+int vh_op_attention_bias(const void* qkv16_dev, int batch, int tokens, int heads, int head_dim, const float* image_dev,
+                         void* out16_dev, int dtype, void* stream);
 /* Test tap: the one-query attention kernel of VH_FLAG_CLS_TAIL on its own.  qkv16 [batch*tokens, 3*heads*64] (q pre-scaled as
  * above) -> out16 [batch, heads*64]: attention of every image's row 0 over all its keys / values.  tokens 1..1024, dtype
  * VH_DTYPE_BF16 or VH_DTYPE_FP16; anything else is VH_ERR_INVALID. */

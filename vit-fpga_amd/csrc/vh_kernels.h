@@ -101,6 +101,14 @@ constexpr int kAttnHdMaxWidth = 2048;
 bool attention_hd_supported(int head_dim);
 hipError_t launch_attention_hd(const void* qkv16, int batch, int tokens, int heads, int head_dim, void* out16, int dtype,
                                hipStream_t stream);
+// The same with an additive per-head bias (kernels_attn_bias.hip; contract: vithip.h, "Attention bias"): softmax(q k^T + B[h]) v.  `image`
+// is the fragment image launch_attention_bias_image makes of the dense fp32 B [heads][tokens][tokens] (natural-log units; finite):
+// attention_bias_image_bytes(heads, tokens) bytes, 16-byte aligned.  bf16 and fp16; no scratch, no counter, no allocation.
+size_t attention_bias_image_bytes(int heads, int tokens);   // 0: heads outside 1..64 or tokens outside 1..kAttnStreamMaxTokens
+const char* attention_bias_check(int batch, int tokens, int heads, int head_dim, int dtype);   // null, or why the shape is refused
+hipError_t launch_attention_bias_image(const float* bias, int heads, int tokens, float* image, hipStream_t stream);
+hipError_t launch_attention_bias(const void* qkv16, int batch, int tokens, int heads, int head_dim, const float* image, void* out16,
+                                 int dtype, hipStream_t stream);
 // Attention maps (kernels_attn_maps.hip; contract: vithip.h, "Attention maps").  launch_attention_probs: the softmax rows of the first
 // Q queries of every (image, head) -> probs [batch][heads][Q][tokens] fp32, from the q|k|v a projection wrote: row-major
 // [batch*tokens][3*heads*head_dim] (in_hm_rows == 0; head dims 32, 48, ..., 128) or head-major [3][heads][in_hm_rows][64] (head dim 64);

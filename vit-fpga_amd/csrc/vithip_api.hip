@@ -61,13 +61,14 @@ struct BlobHeader {
     // bits 9 .. 13 = the number of register tokens (VH_FLAG_REGISTERS: the tensor reg), in the bits vh_config.flags keeps it in;
     // bit 15 = no class token (VH_FLAG_NO_CLS), bits 16 .. 17 = the pooling mode (VH_FLAG_POOL), bit 19 = the attention-pooling head
     // (VH_FLAG_MAP_HEAD: eleven more tensors), bit 21 = tanh GELU (VH_FLAG_TANH_GELU), bit 23 = rotary position embedding (VH_FLAG_ROPE: two
-    // more tensors, at the very end), bit 25 = SwiGLU MLP (VH_FLAG_SWIGLU: fc1 of every layer is [2 M][D] + [2 M]), likewise.
+    // more tensors, at the very end), bit 25 = SwiGLU MLP (VH_FLAG_SWIGLU: fc1 of every layer is [2 M][D] + [2 M]), likewise; bit 27 = additive
+    // attention bias (VH_FLAG_ATTN_BIAS: one more tensor behind everything else, rope.* included).
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
 constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobRegisters = VH_FLAG_REGISTERS_MASK,
-                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU, kBlobRope = VH_FLAG_ROPE, kBlobSwiglu = VH_FLAG_SWIGLU,
-                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu | kBlobRope | kBlobSwiglu,   // at their vh_config.flags positions
+                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU, kBlobRope = VH_FLAG_ROPE, kBlobSwiglu = VH_FLAG_SWIGLU, kBlobAttnBias = VH_FLAG_ATTN_BIAS,
+                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu | kBlobRope | kBlobSwiglu | kBlobAttnBias,   // at their vh_config.flags positions
                    kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobSameBits;
 uint32_t blob_model_bits(const vh_config& c) {
     return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u) |
@@ -108,6 +109,9 @@ struct Layout {
     // VH_FLAG_SWIGLU: fc1 of every layer is [M1][D] + [M1] with M1 = 2 M (gate rows, then value rows); M1 = M otherwise
     bool swiglu = false;
     int M1 = 0;
+    // VH_FLAG_ATTN_BIAS: attn_bias [layers][H][T][T], the last tensor of the blob (vithip.h)
+    bool abias = false;
+    size_t attn_bias = 0;
     std::vector<LayerOff> layer;
 };
 
@@ -149,6 +153,8 @@ Layout make_layout(const vh_config& c) {
     }
     L.rope = (c.flags & VH_FLAG_ROPE) != 0;
     if (L.rope) { const size_t n = (size_t)L.NP * (size_t)(c.dim / c.heads / 2); L.rope_cos = take(n); L.rope_sin = take(n); }
+    L.abias = (c.flags & VH_FLAG_ATTN_BIAS) != 0;
+    if (L.abias) L.attn_bias = take((size_t)c.layers * c.heads * L.T * L.T);
     L.total = o;
     return L;
 }
@@ -163,7 +169,8 @@ size_t blob_bytes_of(const vh_config& c) {
     const size_t pre_ln = (c.flags & VH_FLAG_PRE_LN) ? 2 * D : 0;
     const size_t map = (c.flags & VH_FLAG_MAP_HEAD) ? (size_t)c.heads * D + 2 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D) : 0;
     const size_t rope = (c.flags & VH_FLAG_ROPE) ? 2 * g * g * (D / (size_t)c.heads / 2) : 0;
-    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C + map + rope);
+    const size_t abias = (c.flags & VH_FLAG_ATTN_BIAS) ? (size_t)c.layers * c.heads * T * T : 0;
+    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C + map + rope + abias);
 }
 
 const char* check_config(const vh_config& c) {
@@ -181,7 +188,11 @@ const char* check_config(const vh_config& c) {
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
     if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK |
-                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU | VH_FLAG_ROPE | VH_FLAG_SWIGLU)) return "unknown bits in flags";
+                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU | VH_FLAG_ROPE | VH_FLAG_SWIGLU | VH_FLAG_ATTN_BIAS)) return "unknown bits in flags";
+    if (c.flags & VH_FLAG_ATTN_BIAS) {
+        if (c.flags & VH_FLAG_CLS_TAIL) return "flags: VH_FLAG_ATTN_BIAS excludes VH_FLAG_CLS_TAIL (the tail's one-query attention kernel adds no bias)";
+        if (c.dtype == VH_DTYPE_FP8) return "flags: VH_FLAG_ATTN_BIAS excludes VH_DTYPE_FP8 (the biased attention kernel is bf16 / fp16)";
+    }
     if (c.flags & VH_FLAG_SWIGLU) {
         if (c.flags & (VH_FLAG_QUICK_GELU | VH_FLAG_TANH_GELU)) return "flags: VH_FLAG_SWIGLU excludes VH_FLAG_QUICK_GELU and VH_FLAG_TANH_GELU (one MLP activation)";
         if (c.flags & VH_FLAG_MAP_HEAD) return "flags: VH_FLAG_SWIGLU excludes VH_FLAG_MAP_HEAD (the head's own MLP block is not gated)";
@@ -334,6 +345,10 @@ struct vh_ctx {
     bool cls_tail = false;    // VH_FLAG_CLS_TAIL: the last layer computes the class-token rows only (folded 16-bit path, head dim 64)
     int head_dim = 64;        // dim / heads: 64 takes launch_attention and its layouts, any other launch_attention_hd (row-major)
     float q_scale = kAttnQScale;   // head_dim^-1/2 * log2(e), folded into Wq and bq (attention_q_scale)
+    // VH_FLAG_ATTN_BIAS: the layers' fragment images of attn_bias * log2(e) (kernels_attn_bias.hip), bias_img_layer floats each, made by
+    // prepare_weights.  Such a context keeps q|k|v and the attention output row-major at every head dim, 64 included.
+    float* bias_img = nullptr;
+    size_t bias_img_layer = 0;
     // Run-time guard on the fold: the kernels that produce the row statistics keep a running maximum of
     // |mean| * rstd over the REAL rows (guard_dev: the bits of a non-negative float); every forward ends with an
     // asynchronous copy of that word into pinned host memory, and every forward entry point looks at the copy before it
@@ -646,6 +661,8 @@ int prepare_weights(vh_ctx* c) {
         if (c->h_tiled && w.o_t) HIPCHK(&c->err, launch_cast_tiled_w(P + o.ow, D, D, w.o_t, f.dtype, s));
         if (w8tmp) { HIPCHK(&c->err, hipStreamSynchronize(s)); }   // the scratch is reused by the next layer
     }
+    for (int l = 0; l < f.layers && L.abias; ++l)
+        HIPCHK(&c->err, launch_attention_bias_image(P + L.attn_bias + (size_t)l * f.heads * L.T * L.T, f.heads, L.T, c->bias_img + (size_t)l * c->bias_img_layer, s));
     HIPCHK(&c->err, hipStreamSynchronize(s));
     c->weights_ready = true;
     c->weights_ready_tiled = c->h_tiled && (!c->fp8 || c->ln_fold);   // (e4m3 operands: prepared in the folded branch only)
@@ -700,6 +717,9 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if ((h.flags ^ want) & kBlobSwiglu)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 25 (SwiGLU MLP) is %d, the context's VH_FLAG_SWIGLU is %d",
                     (h.flags & kBlobSwiglu) != 0, (want & kBlobSwiglu) != 0);
+    if ((h.flags ^ want) & kBlobAttnBias)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 27 (additive attention bias) is %d, the context's VH_FLAG_ATTN_BIAS is %d",
+                    (h.flags & kBlobAttnBias) != 0, (want & kBlobAttnBias) != 0);
     if ((h.flags ^ want) & kBlobRope)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 23 (rotary position embedding) is %d, the context's VH_FLAG_ROPE is %d",
                     (h.flags & kBlobRope) != 0, (want & kBlobRope) != 0);
@@ -897,7 +917,12 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     }
     // the class-token tail needs the split planes of the folded 16-bit path, the whole model, and room in the patch-matrix buffer
     // (head dim 64 only: the class-row kernel is 64 wide; other head dims run the full last layer)
-    const bool hd64 = c->head_dim == 64;
+    // (head dim 64 only; a VH_FLAG_ATTN_BIAS context takes the other head dims' routing -- row-major q|k|v and output -- at 64 too)
+    const bool hd64 = c->head_dim == 64 && !L.abias;
+    auto attention_rm = [&](int l) {   // the row-major K/V-streaming kernel, with this layer's bias image where the model has one
+        return L.abias ? launch_attention_bias(A.qkv16, batch, T, f.heads, c->head_dim, c->bias_img + (size_t)l * c->bias_img_layer, A.att16, op_dt, s)
+                       : launch_attention_hd(A.qkv16, batch, T, f.heads, c->head_dim, A.att16, op_dt, s);
+    };
     const bool tail = c->cls_tail && hd64 && c->ln_fold && c->split && !c->fp8 && nl == f.layers && c->run_layers < 0 && T <= 1024 &&
                       (size_t)L.NP * L.KPA * esz >= 2 * ((size_t)D * esz + 256);
     // tiled hidden activation (16-bit or e4m3, in the operand's own tiled layout: fc1's epilogue writes it, fc2's DMA reads it): both
@@ -955,7 +980,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         }
         if ((rc = stage(ST_ATTN, [&] {
                  return hd64 ? launch_attention(A.qkv16, batch, T, f.heads, A.att16, op_dt, A.tickets + l, s, true, att_tiled, qkv_hm ? (int64_t)rows_g : 0)
-                             : launch_attention_hd(A.qkv16, batch, T, f.heads, c->head_dim, A.att16, op_dt, s);
+                             : attention_rm(l);
              })))
             return rc;
         // out-projection and fc2 add to the residual.  Split: (out, out16) = its (hi, lo) planes; otherwise the fp32 x and, with RESID_LN,
@@ -1011,7 +1036,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         if ((rc = capture_attention(l, 0))) return rc;
         if ((rc = stage(ST_ATTN, [&] {
                  return hd64 ? launch_attention(A.qkv16, batch, T, f.heads, A.att16, op_dt, A.tickets + l, s, true)
-                             : launch_attention_hd(A.qkv16, batch, T, f.heads, c->head_dim, A.att16, op_dt, s);
+                             : attention_rm(l);
              })))
             return rc;
         if ((rc = resid_gemm_ln(A.att16, w.o, P + o.ob, w.s_o, D, P + o.ln2w, P + o.ln2b, ST_PROJ))) return rc;
@@ -1642,6 +1667,10 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
     const size_t cd_per_layer = 6 * D + 2 * M1, sc_per_layer = 5 * D + M1, nl = cfg->layers;   // in floats = two 16-bit elements
     const size_t o_bqkv = carve16(nl * 3 * D * 2), o_cd = carve16(nl * cd_per_layer * 2), o_sc = c->fp8 ? carve16(nl * sc_per_layer * 2) : 0;
     CK(hipMalloc((void**)&c->w16, w16_bytes));
+    if (L.abias) {
+        c->bias_img_layer = attention_bias_image_bytes(cfg->heads, L.T) / sizeof(float);
+        CK(hipMalloc((void**)&c->bias_img, (size_t)cfg->layers * c->bias_img_layer * sizeof(float)));
+    }
     c->wp16 = c->w16 + o_wp;
     c->layer.resize(cfg->layers);
     for (int l = 0; l < cfg->layers; ++l) {
@@ -1688,6 +1717,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->feat_store) hipFree(c->feat_store);
     if (c->attn_store) hipFree(c->attn_store);
     if (c->w16) hipFree(c->w16);
+    if (c->bias_img) hipFree(c->bias_img);
     if (c->blob) hipFree(c->blob);
     for (hipEvent_t e : c->tev) hipEventDestroy(e);
     for (hipEvent_t e : c->sev) hipEventDestroy(e);
@@ -1822,6 +1852,8 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
         GEN(L.map_f1w, M * D, TID_MAP + 7, sw, 0.f); GEN(L.map_f1b, M, TID_MAP + 8, sb, 0.f);
         GEN(L.map_f2w, D * M, TID_MAP + 9, sw, 0.f); GEN(L.map_f2b, D, TID_MAP + 10, sb, 0.f);
     }
+    if (L.abias) GEN(L.attn_bias, (size_t)f.layers * f.heads * L.T * L.T, TID_ATTN_BIAS, 3.0f, 0.f);   // sigma 3 (BEiT's trained tables span several units): it moves the logits of a seeded model, whose sigma 0.02 weights
+                                                                                                      // leave the scores near zero, by ~20 % in a float64 forward
 #undef GEN
     if (L.rope) {
         // angles of the generator's uniform stream, a = pi u; the tables are their cosine and sine, made on the host in double and
@@ -2850,6 +2882,8 @@ int vh_set_attention_layers(vh_ctx* c, const int* layers, int n, int queries) {
     const int Q = queries == VH_ATTN_Q_CLS ? 1 : c->L.lead;
     if (n > 0 && Q > kAttnMapsMaxQueries)
         return fail(&c->err, VH_ERR_INVALID, "set_attention_layers: %d leading rows, the capture kernel takes at most %d", Q, kAttnMapsMaxQueries);
+    if (n > 0 && (c->cfg.flags & VH_FLAG_ATTN_BIAS))
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "set_attention_layers: a VH_FLAG_ATTN_BIAS context's maps would leave the bias out (the capture kernel adds none)");
     if (n > 0 && (c->cfg.flags & VH_FLAG_CLS_TAIL))
         return fail(&c->err, VH_ERR_UNSUPPORTED, "set_attention_layers: a VH_FLAG_CLS_TAIL context's last layer runs the class-token attention kernel");
     if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "set_attention_layers: a ring exists on this context; vh_ring_destroy first");
@@ -3219,6 +3253,25 @@ int vh_op_attention_hd(const void* qkv16, int batch, int tokens, int heads, int 
     if (dtype != VH_DTYPE_BF16 && dtype != VH_DTYPE_FP16 && dtype != VH_DTYPE_FP8)
         return fail(nullptr, VH_ERR_INVALID, "attention_hd: unsupported dtype");
     OPCHK(launch_attention_hd(qkv16, batch, tokens, heads, head_dim, out16, dtype, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+// attention with an additive per-head bias: the image's size, the image from the dense tensor, the kernel on caller-made q|k|v
+size_t vh_attention_bias_image_bytes(int heads, int tokens) { return attention_bias_image_bytes(heads, tokens); }
+int vh_op_attention_bias_image(const float* bias_f32, int heads, int tokens, float* image, void* stream) {
+    if (!bias_f32 || !image) return fail(nullptr, VH_ERR_INVALID, "attention_bias_image: null pointer");
+    if (((uintptr_t)bias_f32 & 3) || ((uintptr_t)image & 15)) return fail(nullptr, VH_ERR_INVALID, "attention_bias_image: bias must be 4-byte, image 16-byte aligned");
+    if (tokens < 1 || tokens > kAttnStreamMaxTokens) return fail(nullptr, VH_ERR_INVALID, "attention_bias_image: tokens %d outside 1..%d", tokens, kAttnStreamMaxTokens);
+    if (heads < 1 || heads > kAttnHdMaxWidth / 32) return fail(nullptr, VH_ERR_INVALID, "attention_bias_image: heads %d outside 1..%d", heads, kAttnHdMaxWidth / 32);
+    OPCHK(launch_attention_bias_image(bias_f32, heads, tokens, image, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_attention_bias(const void* qkv16, int batch, int tokens, int heads, int head_dim, const float* image, void* out16, int dtype, void* stream) {
+    if (!qkv16 || !out16 || !image) return fail(nullptr, VH_ERR_INVALID, "attention_bias: null pointer");
+    if (((uintptr_t)qkv16 & 15) || ((uintptr_t)out16 & 15) || ((uintptr_t)image & 15)) return fail(nullptr, VH_ERR_INVALID, "attention_bias: q|k|v, image and out must be 16-byte aligned");
+    if (const char* why = attention_bias_check(batch, tokens, heads, head_dim, dtype)) return fail(nullptr, VH_ERR_INVALID, "attention_bias: %s", why);
+    OPCHK(launch_attention_bias(qkv16, batch, tokens, heads, head_dim, image, out16, dtype, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }

@@ -58,6 +58,9 @@ FLAG_ROPE = 1 << 23
 # [2 M, dim] + [2 M] (gate rows, then value rows) and h = silu(g) * u is made by a pass of its own behind fc1.  Excludes FLAG_QUICK_GELU,
 # FLAG_TANH_GELU, FLAG_MAP_HEAD, FLAG_CLS_TAIL, FLAG_W8_E4M3 and DTYPE_FP8
 FLAG_SWIGLU = 1 << 25
+# Additive per-head attention bias (VH_FLAG_ATTN_BIAS; vithip.h): a model bit, in the blob header too.  The blob's last tensor is
+# attn_bias [layers][heads][T][T] (natural-log units, finite).  Excludes FLAG_CLS_TAIL and DTYPE_FP8; no attention maps.
+FLAG_ATTN_BIAS = 1 << 27
 
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
@@ -334,6 +337,9 @@ SYMBOLS = {
     "vh_op_attention": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_stream": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_hd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vh_attention_bias_image_bytes": (C.c_size_t, [_i, _i]),
+    "vh_op_attention_bias_image": (_i, [_vp, _i, _i, _vp, _vp]),
+    "vh_op_attention_bias": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "vh_op_attention_cls": (_i, [_vp, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_attention_layout": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _vp]),
     "vh_op_attention_probs": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _i, _vp, _vp]),
@@ -425,7 +431,7 @@ def blob_file_config(path):
 
 def blob_file_flags(path):
     """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN, FLAG_QUICK_GELU, FLAG_REGISTERS(n), FLAG_NO_CLS,
-    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU, FLAG_ROPE, FLAG_SWIGLU); host only."""
+    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU, FLAG_ROPE, FLAG_SWIGLU, FLAG_ATTN_BIAS); host only."""
     c = Config()
     _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
     return c.flags
@@ -434,7 +440,7 @@ def blob_file_flags(path):
 # The header's flags word (byte 52) carries the model bits of vh_config flags: these two at header positions of their own, the rest at
 # their flag positions (bit 0 of the word belongs to the file form's checksum).
 _HEADER_BITS = ((FLAG_PRE_LN, 2), (FLAG_QUICK_GELU, 4))
-_SAME_BITS = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE | FLAG_SWIGLU
+_SAME_BITS = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE | FLAG_SWIGLU | FLAG_ATTN_BIAS
 
 
 def _blob_bits(flags):
@@ -482,6 +488,9 @@ def blob_tensor_table(cfg, flags=0):
               ("map.fc2.weight", (D, M)), ("map.fc2.bias", (D,))]
     if flags & FLAG_ROPE:
         t += [("rope.cos", (NP, D // H // 2)), ("rope.sin", (NP, D // H // 2))]
+    if flags & FLAG_ATTN_BIAS:
+        T = NP + cls + R
+        t.append(("attn_bias", (cfg["layers"], H, T, T)))
     return t
 
 
@@ -682,6 +691,66 @@ def blob_from_dinov2_state_dict(sd, cfg, ln_eps=1e-6, head=None, pool=POOL_CLS, 
         else:
             t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.fc2", b + "layer_scale2.lambda1")
     t["head.weight"], t["head.bias"] = _head(me, head, E, 2 * D if pool == POOL_CLS_AVG else D)
+    return _pack_blob(me, cfg, ln_eps, flags, t)
+
+
+def beit_relative_position_bias(table, grid):
+    """BEiT's relative position bias [H][T][T], T = grid^2 + 1 (class token first), from a layer's table [(2 grid - 1)^2 + 3][H]: patch
+    query (y_q, x_q) over patch key (y_k, x_k) takes row (y_q - y_k + grid - 1)(2 grid - 1) + (x_q - x_k + grid - 1); the class-token
+    query over every patch key row n - 3, every patch query over the class-token key row n - 2, class to class row n - 1."""
+    g = int(grid)
+    table = np.asarray(table)
+    n = (2 * g - 1) ** 2 + 3
+    if table.ndim != 2 or table.shape[0] != n:
+        raise ValueError(f"beit_relative_position_bias: the table has shape {table.shape}, grid {g} needs [{n}][heads]")
+    y, x = np.divmod(np.arange(g * g), g)
+    idx = np.empty((g * g + 1, g * g + 1), np.int64)
+    idx[1:, 1:] = (y[:, None] - y[None, :] + g - 1) * (2 * g - 1) + (x[:, None] - x[None, :] + g - 1)
+    idx[0, 1:], idx[1:, 0], idx[0, 0] = n - 3, n - 2, n - 1
+    return np.ascontiguousarray(np.moveaxis(table[idx], 2, 0))
+
+
+_BEIT_LAYER = {"ln1": "layernorm_before", "q": "attention.attention.query", "v": "attention.attention.value", "ln2": "layernorm_after",
+               "fc1": "intermediate.dense"}
+
+
+def blob_from_beit_state_dict(sd, cfg, ln_eps=1e-12, head=None):
+    """Canonical FLAG_ATTN_BIAS blob of a BEiT / BEiT v2 / data2vec-vision encoder from a dict of arrays under the Hugging Face
+    `BeitModel` / `BeitForImageClassification` / `Data2VecVisionModel` parameter names (numpy only).  `cfg`: the model shape, classes = the
+    head's width.  The `beit.` / `data2vec_vision.` prefix is dropped and `classifier.*` is the head unless `head` = (weight, bias) is
+    given; without either the head is zero.  The key projection has no bias: zeros.  `lambda_1` / `lambda_2` (optional) are folded into
+    the out-projection and fc2 as the DINOv2 converter folds LayerScale.  Without `embeddings.position_embeddings` the position table is
+    zeros.  attn_bias: beit_relative_position_bias of every layer's own table, or of the shared `encoder.relative_position_bias` table
+    for every layer.  `pooler.layernorm` (mean pooling) gives FLAG_POOL(POOL_AVG_FCNORM), otherwise `layernorm` and POOL_CLS.
+    `embeddings.mask_token` and the `relative_position_index` buffers are ignored; a missing or wrongly shaped tensor is refused by name."""
+    me = "blob_from_beit_state_dict"
+    for prefix in ("beit.", "data2vec_vision."):
+        if any(k.startswith(prefix) for k in sd):
+            if head is None and "classifier.weight" in sd and "classifier.bias" in sd:
+                head = (sd["classifier.weight"], sd["classifier.bias"])
+            sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    D, M, E, H, g = cfg["dim"], cfg["mlp_dim"], cfg["classes"], cfg["heads"], cfg["image_size"] // cfg["patch_size"]
+    NP, n = g * g, (2 * g - 1) ** 2 + 3
+    mean = "pooler.layernorm.weight" in sd
+    flags = FLAG_ATTN_BIAS | FLAG_POOL(POOL_AVG_FCNORM if mean else POOL_CLS)
+    take = _taker(sd, me)
+    emb, ln = "embeddings.", "pooler.layernorm." if mean else "layernorm."
+    top = {"patch.weight": emb + "patch_embeddings.projection.weight", "patch.bias": emb + "patch_embeddings.projection.bias",
+           "cls": (emb + "cls_token", (1, 1, D)), "lnf.weight": ln + "weight", "lnf.bias": ln + "bias",
+           "pos": (emb + "position_embeddings", (1, NP + 1, D)) if emb + "position_embeddings" in sd else None}
+    t = _take_named(take, cfg, flags, top, "encoder.layer.{}.", _BEIT_LAYER)
+    t.setdefault("pos", np.zeros((NP + 1) * D, np.float32))
+    shared = "encoder.relative_position_bias.relative_position_bias_table"
+    bias = []
+    for l in range(cfg["layers"]):
+        b = f"encoder.layer.{l}."
+        t[f"l{l}.k.weight"], t[f"l{l}.k.bias"] = take(b + "attention.attention.key.weight", (D, D)), np.zeros(D, np.float32)
+        t[f"l{l}.o.weight"], t[f"l{l}.o.bias"] = _scaled(take, sd, D, D, b + "attention.output.dense", b + "lambda_1", optional=True)
+        t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "output.dense", b + "lambda_2", optional=True)
+        own = b + "attention.attention.relative_position_bias.relative_position_bias_table"
+        bias.append(beit_relative_position_bias(take(own if own in sd or shared not in sd else shared, (n, H)).reshape(n, H), g))
+    t["attn_bias"] = np.stack(bias)
+    t["head.weight"], t["head.bias"] = _head(me, head, E, D)
     return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
@@ -2411,6 +2480,21 @@ def op_attention(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
 def op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype):
     """The K/V-streaming attention kernel at any token count 1..4097 (op_attention uses it above 640 tokens)."""
     _check(lib().vh_op_attention_stream(qkv_ptr, batch, tokens, heads, out_ptr, dtype, None))
+
+
+def attention_bias_image_bytes(heads, tokens):
+    """Bytes of the fragment image of one [heads][tokens][tokens] attention bias (0: heads outside 1..64 or tokens outside 1..4097)."""
+    return int(lib().vh_attention_bias_image_bytes(heads, tokens))
+
+
+def op_attention_bias_image(bias_ptr, heads, tokens, image_ptr):
+    """Dense fp32 bias [heads][tokens][tokens] (device) -> its fragment image (device, attention_bias_image_bytes bytes)."""
+    _check(lib().vh_op_attention_bias_image(bias_ptr, heads, tokens, image_ptr, None))
+
+
+def op_attention_bias(qkv_ptr, batch, tokens, heads, head_dim, image_ptr, out_ptr, dtype):
+    """op_attention_hd with an additive per-head bias (its fragment image); DTYPE_BF16 or DTYPE_FP16."""
+    _check(lib().vh_op_attention_bias(qkv_ptr, batch, tokens, heads, head_dim, image_ptr, out_ptr, dtype, None))
 
 
 def op_attention_hd(qkv_ptr, batch, tokens, heads, head_dim, out_ptr, dtype):
