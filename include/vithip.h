@@ -283,6 +283,33 @@ typedef struct vh_config {
  *   depend on its rows alone (batch size, graph replay and split batches do not change them). */
 #define VH_FLAG_ATTN_BIAS (1 << 27)
 
+/* LayerNorm inside the SwiGLU MLP (EVA-02-B/L, timm's scale_mlp = True: the eva02_*_patch14_* models and the EVA-02 CLIP vision towers):
+ * ONE MODEL switch, in bit 29 of flags and, at the same position, of the blob header's flags word; a blob whose bit differs from the
+ * context's is refused with a message that names the bit.  With the bit clear nothing changes: not one launch, buffer or offset.
+ *   VH_FLAG_SUB_LN  every layer computes x += fc2( LN( silu(g) * u ) ).  Needs VH_FLAG_SWIGLU and inherits its exclusions; excludes
+ *                   VH_FLAG_ATTN_BIAS (both put tensors at the very end of the blob) and mlp_dim > 4096; each is refused with a message
+ *                   of its own (vh_weight_blob_bytes returns 0).  The LayerNorm's epsilon is the context's ln_eps.
+ *   Blob tensors of such a context, all fp32, the LAST ones (behind rope.* where there is one):
+ *     subln.width  [1]            one fp32 word holding the integer n, the model's TRUE gated width: n = M unless the converter padded
+ *                                 the width (EVA-02-L: n = 2730 inside M = 2752 or 2816).  At load, a word that is no integer in 1 .. M is
+ *                                 refused with a message of its own.
+ *     subln.weight [layers][M]    the LayerNorm's weight and bias; columns >= n are zero (the converter writes them so).
+ *     subln.bias   [layers][M]
+ *   vh_init_weights_seeded fills n = M, the weight with sigma 0.05 around 1 and the bias with sigma 0.02 (tensor ids 0x7040 / 0x7041).
+ *   THE FUNCTION, for bits, per row, with g_j, u_j the 16-bit values fc1 stored (VH_FLAG_SWIGLU), everything in fp32 and unfused unless
+ *   written fma:
+ *     p_j  = (g_j * rcp(1 + exp2(g_j * -log2(e)))) * u_j          the gate pass's operations, NOT rounded to 16 bits
+ *     mean = (sum_{j<n} p_j) / n
+ *     var  = (sum_{j<n} (p_j - mean)^2) / n                        centred, on the values held on chip; each term fma(d, d, acc)
+ *     rstd = 1 / sqrt(var + ln_eps)
+ *     h_j  = fma((p_j - mean) * rstd, w_j, b_j)  rounded ONCE (RNE) to the element type;  h_j = +0 for j >= n
+ *   Both sums run in an order that is a function of M alone: lane l of a 64-lane wave adds the columns 8 (l + 64 i) .. + 7 for i = 0, 1, ...
+ *   in ascending order onto one accumulator that starts at 0, then the lanes meet in an xor butterfly (offsets 32, 16, 8, 4, 2, 1).  A
+ *   row's bits depend on that row alone: not on the batch, the stream part or a graph replay.  g and u are read in 16-byte chunks of 8
+ *   columns: the columns from 8 ceil(n / 8) on are never read; where n is no multiple of 8, the columns n .. 8 ceil(n / 8) - 1 are read
+ *   with their chunk and their values discarded (masked: not in the sums, h = +0 whatever g, u, w and b hold there). */
+#define VH_FLAG_SUB_LN (1 << 29)
+
 typedef struct vh_ctx vh_ctx; /* opaque ViT context (device, stream, weights, workspace) */
 typedef struct vh_mlp vh_mlp; /* opaque MLP-mode context (the reference's real semantics)  */
 
@@ -323,7 +350,7 @@ int vh_get_ln_guard(vh_ctx* ctx, float* max_ratio, float* threshold, int* trippe
 int vh_get_fp8_guard(vh_ctx* ctx, float* max_abs, float* limit);
 
 /* Weight blob = fp32 tensors in canonical order (DESIGN.md "weight blob") preceded by a
- * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model, bit 23 = VH_FLAG_ROPE model, bit 25 = VH_FLAG_SWIGLU model, bit 27 = VH_FLAG_ATTN_BIAS model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
+ * 64-byte header (its flags word: bit 0 = file checksum present, bit 1 = VH_FLAG_PRE_LN model, bit 2 = VH_FLAG_QUICK_GELU model, bits 9 .. 13 = the register-token count, bit 15 = VH_FLAG_NO_CLS model, bits 16 .. 17 = its VH_FLAG_POOL mode, bit 19 = VH_FLAG_MAP_HEAD model, bit 21 = VH_FLAG_TANH_GELU model, bit 23 = VH_FLAG_ROPE model, bit 25 = VH_FLAG_SWIGLU model, bit 27 = VH_FLAG_ATTN_BIAS model, bit 29 = VH_FLAG_SUB_LN model).  Replaces _load_params (netFPGA.cpp:484-515): uploads, converts to the
  * MFMA operand type, permutes the patch kernel to NHWC order and fuses q|k|v. */
 size_t vh_weight_blob_bytes(const vh_config* cfg);
 int vh_load_weights(vh_ctx* ctx, const void* host_blob, size_t nbytes);
@@ -343,7 +370,7 @@ int vh_export_weights_device(vh_ctx* ctx, void* dev_blob, size_t nbytes);
  *   vh_blob_file_config: host only (no device needed) -- validates magic / shape / file length and fills the model
  *                        fields of *cfg (dtype = VH_DTYPE_BF16, max_batch = 1: set what you need before vh_create;
  *                        cfg->flags = the model bits of the header: VH_FLAG_PRE_LN, VH_FLAG_QUICK_GELU, VH_FLAG_REGISTERS(n), VH_FLAG_NO_CLS,
- *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU, VH_FLAG_ROPE, VH_FLAG_SWIGLU, VH_FLAG_ATTN_BIAS);
+ *                        VH_FLAG_POOL(m), VH_FLAG_MAP_HEAD, VH_FLAG_TANH_GELU, VH_FLAG_ROPE, VH_FLAG_SWIGLU, VH_FLAG_ATTN_BIAS, VH_FLAG_SUB_LN);
  *   vh_save_weights_file: writes <path>.tmp then renames; vh_load_weights_file: verifies length, shape, checksum. */
 int vh_blob_file_config(const char* path, vh_config* cfg);
 /* host only: the file as a MEMORY blob (what vh_load_weights takes): length, header and checksum verified, checksum
@@ -1419,6 +1446,12 @@ int vh_op_rope(void* qkv16_dev, int dtype, int batch, int tokens, int heads, int
  * multiple of 64; 16-byte accesses: both pointers are 16-byte aligned.  Nothing outside h16's rows * mlp_dim elements is written.  Every
  * argument is checked before a device is touched, each refusal with a message of its own. */
 int vh_op_swiglu(const void* gu16_dev, int dtype, int64_t rows, int mlp_dim, void* h16_dev, int out_tiled, void* stream);
+/* The gate pass of a VH_FLAG_SUB_LN context on its own ("THE FUNCTION" at VH_FLAG_SUB_LN): vh_op_swiglu's gu16_dev, h16_dev and layouts;
+ * width = n in 1 .. mlp_dim, weight_dev / bias_dev fp32 [mlp_dim] (16-byte aligned), eps positive and finite, mlp_dim a multiple of 64 and
+ * at most 4096.  Columns >= width of h are written as +0; nothing outside h16's rows * mlp_dim elements is written.  Every argument is
+ * checked before a device is touched, each refusal with a message of its own. */
+int vh_op_swiglu_ln(const void* gu16_dev, int dtype, int64_t rows, int mlp_dim, int width, const float* weight_dev, const float* bias_dev,
+                    float eps, void* h16_dev, int out_tiled, void* stream);
 /* synthetic-data generator on the device: kind 0 = uniform[-1,1), 1 = Irwin-Hall(4) * sigma,
  * 2 = constant `sigma` */
 int vh_op_fill(float* out_dev, int64_t n, uint64_t seed, uint32_t tensor_id, int kind,

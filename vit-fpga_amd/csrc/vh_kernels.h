@@ -135,6 +135,13 @@ hipError_t launch_rope(void* qkv16, int dtype, int batch, int tokens, int heads,
 // 16-byte aligned, mlp_dim a multiple of 64.  No allocation (graph capture, split batches).  swiglu_check: nullptr, or why.
 const char* swiglu_check(const void* gu16, int dtype, int64_t rows, int mlp_dim, const void* h16, int out_tiled);
 hipError_t launch_swiglu(const void* gu16, int dtype, int64_t rows, int mlp_dim, void* h16, int out_tiled, hipStream_t stream);
+// The gate pass with the inner LayerNorm (kernels_swiglu_ln.hip; contract: vithip.h VH_FLAG_SUB_LN, vh_op_swiglu_ln): gu16 as above ->
+// h16 = LN(silu(g) * u) over the first `width` columns, times weight [mlp_dim] plus bias [mlp_dim] (fp32, 16-byte aligned); columns
+// >= width are written as +0.  Same layouts and alignment as launch_swiglu; mlp_dim at most 4096.  No allocation.
+const char* swiglu_ln_check(const void* gu16, int dtype, int64_t rows, int mlp_dim, int width, const float* weight, const float* bias,
+                            float eps, const void* h16, int out_tiled);
+hipError_t launch_swiglu_ln(const void* gu16, int dtype, int64_t rows, int mlp_dim, int width, const float* weight, const float* bias, float eps,
+                            void* h16, int out_tiled, hipStream_t stream);
 const char* attention_readout_check(int batch, int heads, int Q, int tokens, int lead, int elem, int keys);
 hipError_t launch_attention_readout(const float* store, int batch, int heads, int Q, int tokens, int lead, int elem, int keys, void* probs_out,
                                     void* mean_out, hipStream_t stream);

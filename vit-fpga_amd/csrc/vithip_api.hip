@@ -62,13 +62,14 @@ struct BlobHeader {
     // bit 15 = no class token (VH_FLAG_NO_CLS), bits 16 .. 17 = the pooling mode (VH_FLAG_POOL), bit 19 = the attention-pooling head
     // (VH_FLAG_MAP_HEAD: eleven more tensors), bit 21 = tanh GELU (VH_FLAG_TANH_GELU), bit 23 = rotary position embedding (VH_FLAG_ROPE: two
     // more tensors, at the very end), bit 25 = SwiGLU MLP (VH_FLAG_SWIGLU: fc1 of every layer is [2 M][D] + [2 M]), likewise; bit 27 = additive
-    // attention bias (VH_FLAG_ATTN_BIAS: one more tensor behind everything else, rope.* included).
+    // attention bias (VH_FLAG_ATTN_BIAS: one more tensor behind everything else, rope.* included); bit 29 = LayerNorm inside the SwiGLU MLP
+    // (VH_FLAG_SUB_LN: subln.width, subln.weight, subln.bias at the very end; never beside bit 27).
     uint32_t sum_lo, sum_hi, flags, pad[2];
 };
 static_assert(sizeof(BlobHeader) == 64, "blob header is 64 bytes");
 constexpr uint32_t kBlobSum = 1, kBlobPreLn = 2, kBlobQuickGelu = 4, kBlobRegisters = VH_FLAG_REGISTERS_MASK,
-                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU, kBlobRope = VH_FLAG_ROPE, kBlobSwiglu = VH_FLAG_SWIGLU, kBlobAttnBias = VH_FLAG_ATTN_BIAS,
-                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu | kBlobRope | kBlobSwiglu | kBlobAttnBias,   // at their vh_config.flags positions
+                   kBlobNoCls = VH_FLAG_NO_CLS, kBlobPool = VH_FLAG_POOL_MASK, kBlobMapHead = VH_FLAG_MAP_HEAD, kBlobTanhGelu = VH_FLAG_TANH_GELU, kBlobRope = VH_FLAG_ROPE, kBlobSwiglu = VH_FLAG_SWIGLU, kBlobAttnBias = VH_FLAG_ATTN_BIAS, kBlobSubLn = VH_FLAG_SUB_LN,
+                   kBlobSameBits = kBlobRegisters | kBlobNoCls | kBlobPool | kBlobMapHead | kBlobTanhGelu | kBlobRope | kBlobSwiglu | kBlobAttnBias | kBlobSubLn,   // at their vh_config.flags positions
                    kBlobModelBits = kBlobPreLn | kBlobQuickGelu | kBlobSameBits;
 uint32_t blob_model_bits(const vh_config& c) {
     return ((c.flags & VH_FLAG_PRE_LN) ? kBlobPreLn : 0u) | ((c.flags & VH_FLAG_QUICK_GELU) ? kBlobQuickGelu : 0u) |
@@ -112,6 +113,9 @@ struct Layout {
     // VH_FLAG_ATTN_BIAS: attn_bias [layers][H][T][T], the last tensor of the blob (vithip.h)
     bool abias = false;
     size_t attn_bias = 0;
+    // VH_FLAG_SUB_LN: subln.width [1], subln.weight [layers][M], subln.bias [layers][M], the last tensors of the blob (vithip.h)
+    bool subln = false;
+    size_t subln_n = 0, subln_w = 0, subln_b = 0;
     std::vector<LayerOff> layer;
 };
 
@@ -155,6 +159,8 @@ Layout make_layout(const vh_config& c) {
     if (L.rope) { const size_t n = (size_t)L.NP * (size_t)(c.dim / c.heads / 2); L.rope_cos = take(n); L.rope_sin = take(n); }
     L.abias = (c.flags & VH_FLAG_ATTN_BIAS) != 0;
     if (L.abias) L.attn_bias = take((size_t)c.layers * c.heads * L.T * L.T);
+    L.subln = (c.flags & VH_FLAG_SUB_LN) != 0;
+    if (L.subln) { L.subln_n = take(1); L.subln_w = take((size_t)c.layers * M); L.subln_b = take((size_t)c.layers * M); }
     L.total = o;
     return L;
 }
@@ -170,7 +176,8 @@ size_t blob_bytes_of(const vh_config& c) {
     const size_t map = (c.flags & VH_FLAG_MAP_HEAD) ? (size_t)c.heads * D + 2 * (D * D + D) + 2 * D + (M * D + M) + (D * M + D) : 0;
     const size_t rope = (c.flags & VH_FLAG_ROPE) ? 2 * g * g * (D / (size_t)c.heads / 2) : 0;
     const size_t abias = (c.flags & VH_FLAG_ATTN_BIAS) ? (size_t)c.layers * c.heads * T * T : 0;
-    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C + map + rope + abias);
+    const size_t subln = (c.flags & VH_FLAG_SUB_LN) ? 1 + 2 * (size_t)c.layers * M : 0;
+    return sizeof(BlobHeader) + 4 * (D * KP + D + ncls * D + T * D + pre_ln + (size_t)c.layers * per_layer + 2 * D + C * HW + C + map + rope + abias + subln);
 }
 
 const char* check_config(const vh_config& c) {
@@ -188,10 +195,15 @@ const char* check_config(const vh_config& c) {
     if (c.max_batch <= 0) return "max_batch must be positive";
     if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
     if (c.flags & ~(VH_FLAG_LN_FOLD_OFF | VH_FLAG_LN_FOLD_ON | VH_FLAG_W8_E4M3 | VH_FLAG_CLS_TAIL | VH_FLAG_PRE_LN | VH_FLAG_QUICK_GELU | VH_FLAG_REGISTERS_MASK |
-                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU | VH_FLAG_ROPE | VH_FLAG_SWIGLU | VH_FLAG_ATTN_BIAS)) return "unknown bits in flags";
+                    VH_FLAG_NO_CLS | VH_FLAG_POOL_MASK | VH_FLAG_MAP_HEAD | VH_FLAG_TANH_GELU | VH_FLAG_ROPE | VH_FLAG_SWIGLU | VH_FLAG_ATTN_BIAS | VH_FLAG_SUB_LN)) return "unknown bits in flags";
     if (c.flags & VH_FLAG_ATTN_BIAS) {
         if (c.flags & VH_FLAG_CLS_TAIL) return "flags: VH_FLAG_ATTN_BIAS excludes VH_FLAG_CLS_TAIL (the tail's one-query attention kernel adds no bias)";
         if (c.dtype == VH_DTYPE_FP8) return "flags: VH_FLAG_ATTN_BIAS excludes VH_DTYPE_FP8 (the biased attention kernel is bf16 / fp16)";
+    }
+    if (c.flags & VH_FLAG_SUB_LN) {   // (SWIGLU's own exclusions follow below)
+        if (!(c.flags & VH_FLAG_SWIGLU)) return "flags: VH_FLAG_SUB_LN needs VH_FLAG_SWIGLU (the LayerNorm sits between the gate and fc2)";
+        if (c.flags & VH_FLAG_ATTN_BIAS) return "flags: VH_FLAG_SUB_LN excludes VH_FLAG_ATTN_BIAS (each puts its tensors at the very end of the blob)";
+        if (c.mlp_dim > 4096) return "flags: VH_FLAG_SUB_LN needs mlp_dim <= 4096 (a lane of the gate pass holds at most 64 products of its row)";
     }
     if (c.flags & VH_FLAG_SWIGLU) {
         if (c.flags & (VH_FLAG_QUICK_GELU | VH_FLAG_TANH_GELU)) return "flags: VH_FLAG_SWIGLU excludes VH_FLAG_QUICK_GELU and VH_FLAG_TANH_GELU (one MLP activation)";
@@ -330,6 +342,10 @@ struct vh_ctx {
     bool h_tiled = false;     // VH_H_TILED=0 (read when the context is created) keeps the row-major h (A/B, tests)
     bool att_tiled = true;    // VH_ATT_TILED=0 (read when the context is created) keeps the attention output row-major
     bool qkv_hm = true;       // VH_QKV_HM=0 keeps q|k|v row-major ([rows][3 D]) instead of head-major ([3][heads][rows][64]; needs att_tiled)
+    int subln_width = 0;      // VH_FLAG_SUB_LN: the blob's subln.width, n in 1 .. mlp_dim (set by every weight entry point)
+    // VH_FLAG_SUB_LN: subln.weight | subln.bias [2][layers][M], copied by prepare_weights: behind the one-word subln.width the blob's
+    // own tensors are 4-byte aligned only, and the gate pass reads them in 16-byte pieces
+    float* subln_wb = nullptr;
     bool swiglu_skip = false; // VH_SWIGLU_SKIP=1 (measurement only, tools/swiglu_bench.py): a VH_FLAG_SWIGLU context leaves the gate pass out
     bool weights_ready_tiled = false;   // the tiled copies exist for the CURRENT weights (prepared with the fold on)
     // VH_DTYPE_FP8: the four per-layer matrices hold e4m3 bytes (in the same arena) + one fp32 scale per output channel;
@@ -663,6 +679,8 @@ int prepare_weights(vh_ctx* c) {
     }
     for (int l = 0; l < f.layers && L.abias; ++l)
         HIPCHK(&c->err, launch_attention_bias_image(P + L.attn_bias + (size_t)l * f.heads * L.T * L.T, f.heads, L.T, c->bias_img + (size_t)l * c->bias_img_layer, s));
+    if (L.subln)   // (subln.bias follows subln.weight in the blob: one copy)
+        HIPCHK(&c->err, hipMemcpyAsync(c->subln_wb, P + L.subln_w, 2 * (size_t)f.layers * f.mlp_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(&c->err, hipStreamSynchronize(s));
     c->weights_ready = true;
     c->weights_ready_tiled = c->h_tiled && (!c->fp8 || c->ln_fold);   // (e4m3 operands: prepared in the folded branch only)
@@ -683,6 +701,14 @@ int guard_reset(vh_ctx* c) {
     // tripped holds graphs of the stand-alone-LayerNorm sequence, and replaying those against re-folded weights would be
     // silently wrong.  New weights, new graphs.
     drop_graphs(c);
+    return VH_OK;
+}
+
+// VH_FLAG_SUB_LN: the blob's subln.width word must hold an integer n in 1 .. mlp_dim
+int subln_width_of(std::string* err, float word, int mlp_dim, int* n) {
+    if (!(word >= 1.f) || !(word <= (float)mlp_dim) || word != (float)(int)word)
+        return fail(err, VH_ERR_INVALID, "weight blob: subln.width is %g, not an integer in 1 .. mlp_dim = %d", (double)word, mlp_dim);
+    *n = (int)word;
     return VH_OK;
 }
 
@@ -720,6 +746,9 @@ int check_blob_header(vh_ctx* c, const BlobHeader& h) {
     if ((h.flags ^ want) & kBlobAttnBias)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 27 (additive attention bias) is %d, the context's VH_FLAG_ATTN_BIAS is %d",
                     (h.flags & kBlobAttnBias) != 0, (want & kBlobAttnBias) != 0);
+    if ((h.flags ^ want) & kBlobSubLn)
+        return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 29 (LayerNorm inside the SwiGLU MLP) is %d, the context's VH_FLAG_SUB_LN is %d",
+                    (h.flags & kBlobSubLn) != 0, (want & kBlobSubLn) != 0);
     if ((h.flags ^ want) & kBlobRope)
         return fail(&c->err, VH_ERR_INVALID, "weight blob: header bit 23 (rotary position embedding) is %d, the context's VH_FLAG_ROPE is %d",
                     (h.flags & kBlobRope) != 0, (want & kBlobRope) != 0);
@@ -847,9 +876,14 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
     // (tiled under h_tiled's condition) -- one launch per layer.  Without the flag: no launch.  (No stage of its own, as for the rotation:
     // the stage table is pinned; tools/swiglu_bench.py reports the pass as a step difference.  VH_SWIGLU_SKIP=1, read when the context
     // is created, is that tool's switch: fc2 then reads whatever h16 holds, and the logits mean nothing.)
-    auto gate = [&](int64_t nrows, bool tiled) -> int {
+    // VH_FLAG_SUB_LN: the same place and layouts, the pass that also normalises the products with layer l's subln.weight / subln.bias.
+    auto gate = [&](int l, int64_t nrows, bool tiled) -> int {
         if (!L.swiglu || c->swiglu_skip) return VH_OK;
-        HIPCHK(&c->err, launch_swiglu(A.gu16, dt16, nrows, M, A.h16, tiled ? 1 : 0, s));
+        if (L.subln)
+            HIPCHK(&c->err, launch_swiglu_ln(A.gu16, dt16, nrows, M, c->subln_width, c->subln_wb + (size_t)l * M, c->subln_wb + (size_t)(f.layers + l) * M,
+                                             f.ln_eps, A.h16, tiled ? 1 : 0, s));
+        else
+            HIPCHK(&c->err, launch_swiglu(A.gu16, dt16, nrows, M, A.h16, tiled ? 1 : 0, s));
         return VH_OK;
     };
     // Patch embedding: the im2col pass + the persistent GEMM.
@@ -998,7 +1032,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         g1.wscale = w.s_fc1;
         set_tiled(g1, h_tiled && !swiglu, false);
         if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
-        if ((rc = gate(rows_g, h_tiled))) return rc;
+        if ((rc = gate(l, rows_g, h_tiled))) return rc;
         GemmArgs g2 = gemm_args(op_dt, A.h16, h_tiled ? w.fc2_t : w.fc2, P + o.f2b, c->split ? A.xn16 : A.x, rows_g, D, M,
                                 c->split ? VH_EPI_RESID_SPLIT : (l + 1 < nl ? VH_EPI_RESID_LN : VH_EPI_BIAS_RESID));
         g2.out16 = c->split ? A.xlo16 : A.xn16;
@@ -1043,7 +1077,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         GemmArgs g1 = gemm_args(op_dt, A.xn16, w.fc1, P + o.f1b, swiglu ? A.gu16 : A.h16, rows, M1, D, epi_fc1_plain);
         g1.wscale = w.s_fc1;
         if ((rc = stage(ST_FC1, [&] { return launch_gemm(g1, s); }))) return rc;
-        if ((rc = gate(rows, false))) return rc;
+        if ((rc = gate(l, rows, false))) return rc;
         const bool more = l + 1 < nl;   // the next layer's LN1 follows this layer's fc2
         if ((rc = resid_gemm_ln(A.h16, w.fc2, P + o.f2b, w.s_fc2, M, more ? P + L.layer[l + 1].ln1w : nullptr,
                                 more ? P + L.layer[l + 1].ln1b : nullptr, ST_FC2))) return rc;
@@ -1671,6 +1705,7 @@ int vh_create(const vh_config* cfg, int device, vh_ctx** out) {
         c->bias_img_layer = attention_bias_image_bytes(cfg->heads, L.T) / sizeof(float);
         CK(hipMalloc((void**)&c->bias_img, (size_t)cfg->layers * c->bias_img_layer * sizeof(float)));
     }
+    if (L.subln) CK(hipMalloc((void**)&c->subln_wb, 2 * nl * M * sizeof(float)));
     c->wp16 = c->w16 + o_wp;
     c->layer.resize(cfg->layers);
     for (int l = 0; l < cfg->layers; ++l) {
@@ -1718,6 +1753,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->attn_store) hipFree(c->attn_store);
     if (c->w16) hipFree(c->w16);
     if (c->bias_img) hipFree(c->bias_img);
+    if (c->subln_wb) hipFree(c->subln_wb);
     if (c->blob) hipFree(c->blob);
     for (hipEvent_t e : c->tev) hipEventDestroy(e);
     for (hipEvent_t e : c->sev) hipEventDestroy(e);
@@ -1782,6 +1818,11 @@ int vh_load_weights(vh_ctx* c, const void* host_blob, size_t nbytes) {
     memcpy(&h, host_blob, sizeof h);
     int rc = check_blob_header(c, h);
     if (rc) return rc;
+    if (c->L.subln) {
+        float word;
+        memcpy(&word, (const char*)host_blob + sizeof h + 4 * c->L.subln_n, 4);
+        if ((rc = subln_width_of(&c->err, word, c->cfg.mlp_dim, &c->subln_width))) return rc;
+    }
     HIPCHK(&c->err, hipSetDevice(c->device));
     c->weights_ready = false;
     HIPCHK(&c->err, hipMemcpyAsync(c->blob, host_blob, nbytes, hipMemcpyHostToDevice, c->stream));
@@ -1799,6 +1840,11 @@ int vh_load_weights_device(vh_ctx* c, const void* dev_blob, size_t nbytes) {
     HIPCHK(&c->err, hipMemcpy(&h, dev_blob, sizeof h, hipMemcpyDeviceToHost));
     int rc = check_blob_header(c, h);
     if (rc) return rc;
+    if (c->L.subln) {
+        float word;
+        HIPCHK(&c->err, hipMemcpy(&word, (const char*)dev_blob + sizeof h + 4 * c->L.subln_n, 4, hipMemcpyDeviceToHost));
+        if ((rc = subln_width_of(&c->err, word, c->cfg.mlp_dim, &c->subln_width))) return rc;
+    }
     c->weights_ready = false;
     if (dev_blob != c->blob) HIPCHK(&c->err, hipMemcpyAsync(c->blob, dev_blob, nbytes, hipMemcpyDeviceToDevice, c->stream));
     if ((rc = guard_reset(c))) return rc;
@@ -1854,6 +1900,13 @@ int vh_init_weights_seeded(vh_ctx* c, uint64_t seed) {
     }
     if (L.abias) GEN(L.attn_bias, (size_t)f.layers * f.heads * L.T * L.T, TID_ATTN_BIAS, 3.0f, 0.f);   // sigma 3 (BEiT's trained tables span several units): it moves the logits of a seeded model, whose sigma 0.02 weights
                                                                                                       // leave the scores near zero, by ~20 % in a float64 forward
+    if (L.subln) {   // n = M (nothing is padded), weight around 1 and bias as a LayerNorm's; the ids are attn_bias's, which the flag excludes
+        GEN(L.subln_w, (size_t)f.layers * M, TID_SUBLN + 0, sg, 1.f); GEN(L.subln_b, (size_t)f.layers * M, TID_SUBLN + 1, sb, 0.f);
+        const float word = (float)f.mlp_dim;
+        HIPCHK(&c->err, hipMemcpyAsync(P + L.subln_n, &word, 4, hipMemcpyHostToDevice, s));
+        HIPCHK(&c->err, hipStreamSynchronize(s));   // word leaves scope
+        c->subln_width = f.mlp_dim;
+    }
 #undef GEN
     if (L.rope) {
         // angles of the generator's uniform stream, a = pi u; the tables are their cosine and sine, made on the host in double and
@@ -1909,6 +1962,15 @@ static int blob_file_header(const char* path, vh_config* cfg, size_t* need_out) 
     if (const char* why = check_config(c)) return fail(nullptr, VH_ERR_INVALID, "%s: header describes an unsupported model (%s)", path, why);
     const size_t need = blob_bytes_of(c);
     if (fsize != (long long)need) return fail(nullptr, VH_ERR_INVALID, "%s: %lld bytes, the header implies %zu", path, fsize, need);
+    if (c.flags & VH_FLAG_SUB_LN) {   // subln.width, in front of the two [layers][M] tensors that end the file
+        float word = 0.f;
+        int n;
+        f = fopen(path, "rb");
+        const bool ok = f && fseek(f, (long)(need - 4 * (1 + 2 * (size_t)c.layers * c.mlp_dim)), SEEK_SET) == 0 && fread(&word, 4, 1, f) == 1;
+        if (f) fclose(f);
+        if (!ok) return fail(nullptr, VH_ERR_INVALID, "%s: short read", path);
+        if (int rc = subln_width_of(nullptr, word, c.mlp_dim, &n)) return rc;
+    }
     *cfg = c;
     if (need_out) *need_out = need;
     return VH_OK;
@@ -3526,6 +3588,16 @@ int vh_op_swiglu(const void* gu16, int dtype, int64_t rows, int mlp_dim, void* h
     hipError_t e = launch_swiglu(gu16, dtype, rows, mlp_dim, h16, out_tiled, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "swiglu failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the VH_FLAG_SUB_LN gate pass on caller-made fc1 output
+int vh_op_swiglu_ln(const void* gu16, int dtype, int64_t rows, int mlp_dim, int width, const float* weight, const float* bias, float eps, void* h16,
+                    int out_tiled, void* stream) {
+    if (const char* why = swiglu_ln_check(gu16, dtype, rows, mlp_dim, width, weight, bias, eps, h16, out_tiled))
+        return fail(nullptr, VH_ERR_INVALID, "swiglu_ln: %s", why);
+    hipError_t e = launch_swiglu_ln(gu16, dtype, rows, mlp_dim, width, weight, bias, eps, h16, out_tiled, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "swiglu_ln failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 int vh_op_fill(float* out, int64_t n, uint64_t seed, uint32_t tensor_id, int kind, float sigma, void* stream) {

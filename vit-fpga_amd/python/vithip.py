@@ -61,6 +61,10 @@ FLAG_SWIGLU = 1 << 25
 # Additive per-head attention bias (VH_FLAG_ATTN_BIAS; vithip.h): a model bit, in the blob header too.  The blob's last tensor is
 # attn_bias [layers][heads][T][T] (natural-log units, finite).  Excludes FLAG_CLS_TAIL and DTYPE_FP8; no attention maps.
 FLAG_ATTN_BIAS = 1 << 27
+# LayerNorm inside the SwiGLU MLP (VH_FLAG_SUB_LN; vithip.h; EVA-02-B/L): a model bit, in the blob header too.  Needs FLAG_SWIGLU; the blob's
+# last tensors are subln.width [1] (the true gated width n as one fp32 word), subln.weight and subln.bias [layers, mlp_dim] (zero from
+# column n on).  Excludes FLAG_ATTN_BIAS and mlp_dim > 4096
+FLAG_SUB_LN = 1 << 29
 
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_LNFOLD, EPI_LNFOLD_GELU, EPI_RESID_LN, EPI_RESID_SPLIT, EPI_PATCH_SPLIT = range(10)
@@ -364,6 +368,7 @@ SYMBOLS = {
     "vh_op_map_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i, _vp, _vp]),
     "vh_op_rope": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
     "vh_op_swiglu": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp]),
+    "vh_op_swiglu_ln": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _f, _vp, _i, _vp]),
     "vh_op_fill": (_i, [_vp, _i64, _u64, C.c_uint32, _i, _f, _vp]),
     "vh_bench_gemm": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double)]),
     "vh_group_create": (_i, [C.POINTER(Config), _pi, _i, C.POINTER(_vp)]),
@@ -431,7 +436,7 @@ def blob_file_config(path):
 
 def blob_file_flags(path):
     """The model bits of a VHBLOB1 file's header as vh_config flags (FLAG_PRE_LN, FLAG_QUICK_GELU, FLAG_REGISTERS(n), FLAG_NO_CLS,
-    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU, FLAG_ROPE, FLAG_SWIGLU, FLAG_ATTN_BIAS); host only."""
+    FLAG_POOL(m), FLAG_MAP_HEAD, FLAG_TANH_GELU, FLAG_ROPE, FLAG_SWIGLU, FLAG_ATTN_BIAS, FLAG_SUB_LN); host only."""
     c = Config()
     _check(lib().vh_blob_file_config(os.fsencode(path), C.byref(c)))
     return c.flags
@@ -440,7 +445,7 @@ def blob_file_flags(path):
 # The header's flags word (byte 52) carries the model bits of vh_config flags: these two at header positions of their own, the rest at
 # their flag positions (bit 0 of the word belongs to the file form's checksum).
 _HEADER_BITS = ((FLAG_PRE_LN, 2), (FLAG_QUICK_GELU, 4))
-_SAME_BITS = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE | FLAG_SWIGLU | FLAG_ATTN_BIAS
+_SAME_BITS = FLAG_REGISTERS_MASK | FLAG_NO_CLS | FLAG_POOL_MASK | FLAG_MAP_HEAD | FLAG_TANH_GELU | FLAG_ROPE | FLAG_SWIGLU | FLAG_ATTN_BIAS | FLAG_SUB_LN
 
 
 def _blob_bits(flags):
@@ -491,6 +496,8 @@ def blob_tensor_table(cfg, flags=0):
     if flags & FLAG_ATTN_BIAS:
         T = NP + cls + R
         t.append(("attn_bias", (cfg["layers"], H, T, T)))
+    if flags & FLAG_SUB_LN:
+        t += [("subln.width", (1,)), ("subln.weight", (cfg["layers"], M)), ("subln.bias", (cfg["layers"], M))]
     return t
 
 
@@ -563,7 +570,7 @@ def _register_count(me, cfg, sd, key):
     return R
 
 
-def _gated_mlp(me, take, sd, cfg, l, gate, up, down, lname):
+def _gated_mlp(me, take, sd, cfg, l, gate, up, down, lname, optional=False):
     """The four MLP tensors of layer l of a FLAG_SWIGLU blob from a gated checkpoint.  gate / up: (tensor name stem, first row, rows) of
     the two halves of fc1 (one tensor `weights_in`, or `gate_proj` and `up_proj`); down: fc2's stem; LayerScale `lname` is folded into
     fc2 in float64, one rounding.  A hidden width M' that is no multiple of 64 is zero-padded to cfg['mlp_dim'], a larger multiple of 64:
@@ -579,7 +586,7 @@ def _gated_mlp(me, take, sd, cfg, l, gate, up, down, lname):
     for half, (stem, r0, total) in enumerate((gate, up)):
         w1[half * M:half * M + Mc] = take(stem + ".weight", (total, D)).reshape(total, D)[r0:r0 + Mc]
         b1[half * M:half * M + Mc] = take(stem + ".bias", (total,))[r0:r0 + Mc]
-    w2c, b2 = _scaled(take, sd, D, Mc, down, lname)
+    w2c, b2 = _scaled(take, sd, D, Mc, down, lname, optional)
     w2 = np.zeros((D, M), np.float32)
     w2[:, :Mc] = w2c.reshape(D, Mc)
     return {f"l{l}.fc1.weight": w1, f"l{l}.fc1.bias": b1, f"l{l}.fc2.weight": w2, f"l{l}.fc2.bias": b2}
@@ -868,6 +875,74 @@ def blob_from_dinov3_state_dict(sd, cfg, ln_eps=1e-5, head=None, pool=POOL_CLS, 
             t[f"l{l}.fc2.weight"], t[f"l{l}.fc2.bias"] = _scaled(take, sd, D, M, b + "mlp.down_proj", b + "layer_scale2.lambda1")
     t["head.weight"], t["head.bias"] = _head(me, head, E, 2 * D if pool == POOL_CLS_AVG else D)
     t["rope.cos"], t["rope.sin"] = rope_tables_dinov3(g, D // H, theta)
+    return _pack_blob(me, cfg, ln_eps, flags, t)
+
+
+def rope_tables_eva02(grid, head_dim, temperature=10000.0, ref_grid=None):
+    """(cos, sin) [grid * grid, head_dim / 2] fp32: the rope.cos / rope.sin tensors of an EVA-02 tower, one column per rotated PAIR.  Patch
+    (y, x) has coordinates t_y = y * ref_grid / grid and t_x likewise (ref_grid = the pre-training grid, default: grid); pair i <
+    head_dim / 4 turns by t_y * temperature^(-i / (head_dim / 4)), pair head_dim / 4 + i by t_x times the same band.  Computed in float64,
+    rounded once.  WRITTEN FROM MEMORY of timm's RotaryEmbeddingCat(in_pixels=False) and NOT compared with timm (none was at hand): check
+    the bands against the checkpoint's own `rope` buffers before trusting a converted model, or pass tables of your own."""
+    if head_dim % 4:
+        raise ValueError(f"rope_tables_eva02: head_dim = {head_dim} is not a multiple of 4")
+    q = head_dim // 4
+    t = np.arange(grid, dtype=np.float64) * (float(ref_grid or grid) / grid)
+    ty, tx = (a.reshape(-1) for a in np.meshgrid(t, t, indexing="ij"))
+    bands = float(temperature) ** (-np.arange(q, dtype=np.float64) / q)
+    ang = np.concatenate([ty[:, None] * bands[None, :], tx[:, None] * bands[None, :]], axis=1)
+    return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+
+
+def blob_from_eva02_state_dict(sd, cfg, ln_eps=1e-6, rope=None, temperature=10000.0, ref_grid=None):
+    """Canonical blob of a timm EVA-02 classifier or CLIP vision tower from a dict of arrays under timm's `Eva` parameter names (numpy
+    only): `patch_embed.proj.*`, `cls_token`, `pos_embed` [1, NP + 1, dim], `blocks.N.{norm1, attn.{q_proj, k_proj, v_proj}.weight or
+    attn.qkv.weight, attn.q_bias, attn.v_bias, attn.proj, norm2, mlp.{fc1_g, fc1_x, norm, fc2}}`, `norm` or `fc_norm`, `head`.  NOT run
+    against a timm install or a real checkpoint (neither was at hand): the test builds the state dict under those names.
+      Header flags: FLAG_ROPE | FLAG_SWIGLU | FLAG_SUB_LN, plus FLAG_POOL(POOL_AVG_FCNORM) where the dict has `fc_norm` (lnf = fc_norm; else
+      lnf = norm and the class-token head).  A checkpoint without `mlp.norm` (scale_mlp=False: EVA-02-Ti/S) gets no FLAG_SUB_LN.
+      Attention: the key projection has no bias (zeros); missing q_bias / v_bias are zeros.  EVA-02 rotates the INTERLEAVED pairs
+      (2 i, 2 i + 1) of every head, the library the pairs (d, d + head_dim / 2): the q and k rows and biases of every head are permuted
+      by the same permutation (row i <- 2 i, row head_dim / 2 + i <- 2 i + 1), which leaves every score q . k as it was, and column i of
+      the tables holds pair i's angle.  v and the out-projection are untouched.
+      rope = (cos, sin) [NP, head_dim / 2], else rope_tables_eva02(grid, head_dim, temperature, ref_grid) (unverified: see there).
+      MLP: fc1 = fc1_g rows (gate), then fc1_x rows; a gated width n that is no multiple of 64 is zero-padded to cfg['mlp_dim'] (any
+      larger multiple of 64; a multiple of 256 reaches the folded layer loop): fc1 rows and biases, fc2 columns and the subln.*
+      entries, all zeros; subln.width = n.  A width that IS a multiple of 64 is taken as it is and not padded (_gated_mlp's rule): such a
+      model reaches the folded loop only if its width is a multiple of 256 already (EVA-02-B: 2048).
+    Refused by name: a missing or wrongly shaped tensor, a hidden width cfg['mlp_dim'] cannot hold."""
+    me = "blob_from_eva02_state_dict"
+    D, M, H, E = cfg["dim"], cfg["mlp_dim"], cfg["heads"], cfg["classes"]
+    g = cfg["image_size"] // cfg["patch_size"]
+    NP, hd, nl = g * g, D // H, cfg["layers"]
+    sub_ln = any(k.endswith("mlp.norm.weight") for k in sd)
+    mean = "fc_norm.weight" in sd
+    flags = FLAG_ROPE | FLAG_SWIGLU | (FLAG_SUB_LN if sub_ln else 0) | FLAG_POOL(POOL_AVG_FCNORM if mean else POOL_CLS)
+    take = _taker(sd, me)
+    ln = "fc_norm" if mean else "norm"
+    top = {"patch.weight": "patch_embed.proj.weight", "patch.bias": "patch_embed.proj.bias", "cls": ("cls_token", (1, 1, D)),
+           "pos": ("pos_embed", (1, NP + 1, D)), "lnf.weight": ln + ".weight", "lnf.bias": ln + ".bias", "head.weight": "head.weight",
+           "head.bias": "head.bias"}
+    t = _take_named(take, cfg, flags, top, "blocks.{}.", {"ln1": "norm1", "ln2": "norm2", "o": "attn.proj"})
+    perm = (np.arange(H)[:, None] * hd + np.concatenate([np.arange(0, hd, 2), np.arange(1, hd, 2)])[None, :]).reshape(-1)
+    n, sw, sb = M, np.zeros((nl, M), np.float32), np.zeros((nl, M), np.float32)
+    for l in range(nl):
+        b = f"blocks.{l}."
+        if b + "attn.qkv.weight" in sd:
+            w = dict(zip("qkv", take(b + "attn.qkv.weight", (3 * D, D)).reshape(3, D, D)))
+        else:
+            w = {x: take(f"{b}attn.{x}_proj.weight", (D, D)).reshape(D, D) for x in "qkv"}
+        bias = {x: take(f"{b}attn.{x}_bias", (D,)) if f"{b}attn.{x}_bias" in sd else np.zeros(D, np.float32) for x in "qv"}
+        t[f"l{l}.q.weight"], t[f"l{l}.q.bias"] = w["q"][perm], bias["q"][perm]
+        t[f"l{l}.k.weight"], t[f"l{l}.k.bias"] = w["k"][perm], np.zeros(D, np.float32)
+        t[f"l{l}.v.weight"], t[f"l{l}.v.bias"] = w["v"], bias["v"]
+        n = int(np.asarray(sd[b + "mlp.fc2.weight"]).shape[-1]) if b + "mlp.fc2.weight" in sd else M
+        t.update(_gated_mlp(me, take, sd, cfg, l, (b + "mlp.fc1_g", 0, n), (b + "mlp.fc1_x", 0, n), b + "mlp.fc2", b + "gamma_2", optional=True))
+        if sub_ln:
+            sw[l, :n], sb[l, :n] = take(b + "mlp.norm.weight", (n,)), take(b + "mlp.norm.bias", (n,))
+    if sub_ln:
+        t["subln.width"], t["subln.weight"], t["subln.bias"] = np.array([n], np.float32), sw, sb
+    t["rope.cos"], t["rope.sin"] = rope if rope is not None else rope_tables_eva02(g, hd, temperature, ref_grid)
     return _pack_blob(me, cfg, ln_eps, flags, t)
 
 
@@ -2467,6 +2542,12 @@ def op_swiglu(gu_ptr, dtype, rows, mlp_dim, h_ptr, out_tiled=False):
     """The VH_FLAG_SWIGLU gate pass on its own (vh_op_swiglu): gu [rows, 2 * mlp_dim] row-major `dtype` elements (gate columns first) ->
     h = silu(g) * u [rows, mlp_dim], row-major or (out_tiled; rows a multiple of 16) in the layout unpack_tiled reads."""
     _check(lib().vh_op_swiglu(gu_ptr, dtype, rows, mlp_dim, h_ptr, 1 if out_tiled else 0, None))
+
+
+def op_swiglu_ln(gu_ptr, dtype, rows, mlp_dim, width, weight_ptr, bias_ptr, eps, h_ptr, out_tiled=False):
+    """The VH_FLAG_SUB_LN gate pass on its own (vh_op_swiglu_ln): op_swiglu's gu and h; h = LayerNorm over the first `width` columns of
+    silu(g) * u, times weight [mlp_dim] plus bias [mlp_dim] (fp32, device); columns >= width are +0."""
+    _check(lib().vh_op_swiglu_ln(gu_ptr, dtype, rows, mlp_dim, width, weight_ptr, bias_ptr, eps, h_ptr, 1 if out_tiled else 0, None))
 
 
 def op_layernorm(x_ptr, rows, dim, row_stride, gamma_ptr, beta_ptr, eps, out_ptr, dtype):
