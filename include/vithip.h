@@ -1111,6 +1111,61 @@ int vh_read_attention(vh_ctx* ctx, const vh_attention_maps* out_host);
 int vh_read_attention_device(vh_ctx* ctx, const vh_attention_maps* out_dev);
 int vh_read_attention_device_async(vh_ctx* ctx, const vh_attention_maps* out_dev);
 
+/* ---- Dense heads -----------------------------------------------------------------------------
+ * What the consumers of the patch features run next: a linear head on every patch row -- DINOv2's linear segmentation and depth heads
+ * (a 1x1 convolution on x_norm_patchtokens with its BatchNorm folded in), MaskCLIP-style dense CLIP, linear-probe segmentation on any
+ * backbone -- then a bilinear upsample of the per-patch logits and an argmax.  With a head set, one forward plus two small launches
+ * return a class map per image and the patch rows (540 MB at ViT-B/16, batch 512) never leave the device.  A PULL interface like the
+ * token features: the calls read the rows the LAST forward enqueued on the context left (any entry point, eager or graph replay; "WHICH
+ * FORWARD" above), no forward knows of the head, and setting or clearing it drops no cached graph and changes no logit.
+ *
+ * ARITHMETIC, for bits.  gh = gw = image_size / patch_size, NP = gh * gw, C = classes, D = vh_config.dim, T16 = the context's operand
+ * type (VH_DTYPE_BF16 / VH_DTYPE_FP16).
+ *   w16[c][k]      = RNE_T16(w[c][k]), rounded once when the head is set; b stays fp32 (NULL: nothing is added).
+ *   a16[b][p][k]   = RNE_T16(v), v = the fp32 value vh_read_features(patch, elem VH_ELEM_F32, the head's norm) writes for patch row p of
+ *                    image b: x = hi + lo as it is (VH_FEAT_RAW) or through the final LayerNorm with the two-pass statistics of "Token
+ *                    features" (VH_FEAT_NORM).  Class-token and register rows are skipped.
+ *   logit[b][c][p] = (sum_k a16[b][p][k] * w16[c][k]) + b[c]: the products are exact in fp32; the sum starts at +0 and takes k ascending
+ *                    in groups of 16, one v_mfma_f32_32x32x16 (gfx950) per group -- 16 exact products and the running sum, rounded the
+ *                    way that instruction rounds; the bias is ONE fp32 add at the end.  The order depends on D alone: never on the
+ *                    batch, on C, on the patch index or on the output element type.  Where every product and partial sum is an
+ *                    integer below 2^24 the result is exact.
+ *   elem           a 16-bit output is the round-to-nearest-even of exactly the fp32 value.
+ *   map[b][y][x]   s_y = max(sc_y * (y + 0.5) - 0.5, 0) with sc_y = (float)gh / (float)out_h, every operation one fp32 rounding;
+ *                    i0 = floor(s_y), i1 = min(i0 + 1, gh - 1), l1 = s_y - i0, l0 = 1 - l1; the same along x.  For class c:
+ *                    u = (ly0 * (lx0 * L[i0][j0] + lx1 * L[i0][j1])) + (ly1 * (lx0 * L[i1][j0] + lx1 * L[i1][j1])), L = the fp32
+ *                    logits [gh][gw] of (b, c): plain fp32 multiplies and adds in exactly this order, no fused multiply-add.  That is
+ *                    torch.nn.functional.interpolate(mode="bilinear", align_corners=False).  classes_out = the lowest c whose u is
+ *                    largest (a strict > over ascending c, starting from -inf at class 0: a NaN never wins), score_out = that u.
+ *                    The logits are finite.  vh_read_dense_map computes the fp32 logits of the same forward into a buffer the context
+ *                    owns (allocated by vh_set_dense_head: max_batch * C * NP floats) and interpolates those.
+ *
+ *   vh_set_dense_head      w_host [C][D], b_host [C] or NULL, classes 1 .. VH_DENSE_MAX_CLASSES, norm VH_FEAT_NORM / VH_FEAT_RAW; w_host
+ *                          NULL clears the head (the other arguments are ignored).  Synchronous.
+ *   vh_dense_dims          any of the four may be NULL; *classes = 0 while no head is set; *batch = the last forward's
+ *   vh_read_dense_logits   out [batch][C][gh][gw] of elem VH_ELEM_F32 / F16 / BF16, images 0 .. batch - 1 of the last forward
+ *                          (batch <= the last forward's); host buffer, synchronous
+ *   vh_read_dense_map      classes_out [batch][out_h][out_w] bytes, score_out floats of the same shape or NULL; out_h, out_w 1 ..
+ *                          VH_DENSE_MAX_SIDE; host buffers, synchronous
+ *   .._device / .._device_async   device buffers; enqueue on the context's stream and wait / enqueue only
+ *
+ * REFUSED with VH_ERR_INVALID, each with a message of its own, before a device is touched, nothing enqueued and no output written: a
+ * null context, w with a null output or a null class map; classes outside 1 .. 256; norm not VH_FEAT_NORM / VH_FEAT_RAW; elem not
+ * VH_ELEM_F32 / F16 / BF16; batch below 1 or above the last forward's; no forward has run; no head is set; a device pointer that is not
+ * 16-byte aligned; out_h or out_w outside 1 .. 4096; a VH_FLAG_CLS_TAIL context (its last layer updates the class-token rows only); a
+ * VH_DTYPE_FP8 context (the head's operand type is the context's 16-bit type, and an fp8 context has none to name).  VH_ERR_STATE: a
+ * ring exists on the context (its forwards belong to slots).  The calls go through neither the rings nor the device groups. */
+#define VH_DENSE_MAX_CLASSES 256
+#define VH_DENSE_MAX_SIDE 4096
+int vh_set_dense_head(vh_ctx* ctx, const float* w_host, const float* b_host, int classes, int norm);
+int vh_dense_dims(const vh_ctx* ctx, int* batch, int* classes, int* grid_h, int* grid_w);
+int vh_read_dense_logits(vh_ctx* ctx, int batch, void* out_host, int elem);
+int vh_read_dense_logits_device(vh_ctx* ctx, int batch, void* out_dev, int elem);
+int vh_read_dense_logits_device_async(vh_ctx* ctx, int batch, void* out_dev, int elem);
+int vh_read_dense_map(vh_ctx* ctx, int batch, int out_h, int out_w, uint8_t* classes_out_host, float* score_out_host);
+int vh_read_dense_map_device(vh_ctx* ctx, int batch, int out_h, int out_w, uint8_t* classes_out_dev, float* score_out_dev);
+int vh_read_dense_map_device_async(vh_ctx* ctx, int batch, int out_h, int out_w, uint8_t* classes_out_dev, float* score_out_dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1432,6 +1487,18 @@ int vh_op_pool_rows(const void* hi_or_x32_dev, const void* lo_dev, int form, int
 int vh_op_map_pool(const void* hi_or_x32_dev, const void* lo_dev, int form, int batch, int tokens, int lead, int dim,
                    const float* gamma_dev, const float* beta_dev, float eps, const float* qk_dev, int heads, float* z_out_dev,
                    void* stream);
+/* The dense head's GEMM on its own ("Dense heads"): rows16_dev [rows][dim] and w16_dev [classes][dim] of `dtype` (VH_DTYPE_BF16 /
+ * VH_DTYPE_FP16), bias_dev [classes] fp32 or NULL -> out_f32_dev [rows / group][classes][group] fp32 = the logit of "Dense heads" with
+ * a16 = rows16 (group = the rows of one image, gh * gw).  classes 1 .. 256, dim % 16 == 0, 64 <= dim <= 2048, group 1 .. 4096, rows a
+ * multiple of group; every pointer 16-byte aligned.  Every argument is checked before a device is touched, each refusal with a message
+ * of its own. */
+int vh_op_dense_head(const void* rows16_dev, int64_t rows, int dim, const void* w16_dev, const float* bias_dev, int classes, int group,
+                     float* out_f32_dev, int dtype, void* stream);
+/* The upsample + argmax on its own ("Dense heads", map): logits_f32_dev [batch][classes][gh][gw] -> classes_out_dev [batch][out_h][out_w]
+ * bytes and score_out_dev (floats of the same shape, or NULL).  classes 1 .. 256, gh and gw 1 .. 64, out_h and out_w 1 .. 4096; every
+ * pointer 16-byte aligned.  Every argument is checked before a device is touched, each refusal with a message of its own. */
+int vh_op_dense_argmax(const float* logits_f32_dev, int batch, int classes, int gh, int gw, int out_h, int out_w, uint8_t* classes_out_dev,
+                       float* score_out_dev, void* stream);
 /* The rotation of a VH_FLAG_ROPE context on its own ("THE FUNCTION" at VH_FLAG_ROPE), in place on caller-made q|k|v of `dtype`
  * (VH_DTYPE_BF16 / VH_DTYPE_FP16) elements: q and k of rows lead .. tokens - 1 of every image and head are rotated by cos_dev / sin_dev
  * [tokens - lead][head_dim / 2] fp32; v, the lead rows and every row beyond batch * tokens are never written.

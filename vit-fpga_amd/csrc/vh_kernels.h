@@ -328,6 +328,37 @@ int map_pool_group(int dim, int heads);
 // bytes_lo of the lo plane (0: none), in ONE launch.  Pointers and byte counts are multiples of 16.
 hipError_t launch_feature_capture(const void* src_hi, void* dst_hi, size_t bytes_hi, const void* src_lo, void* dst_lo, size_t bytes_lo,
                                   hipStream_t stream);
+// Dense heads (kernels_dense.hip; contract: vithip.h, "Dense heads").  launch_dense_head: out [rows / group][classes][group] of `elem`
+// <- bias[c] + the rows' 16-bit image against w16 [classes][dim] of `dtype` (VH_DTYPE_BF16 / FP16), fp32 accumulation.  The rows:
+// form VH_DENSE_FORM_ROWS16 = plain rows of `dtype` in hi; form == dtype = the split planes of that type; VH_FEAT_FORM_F32 = fp32 rows
+// -- the latter two optionally through LayerNorm(gamma, beta, eps) (norm VH_FEAT_NORM) and rounded to nearest even, with the arithmetic
+// of the token features.  Patch row m is source row (m / group) * tokens + lead + m % group; tokens = lead + group.  dim % 16 == 0.
+// launch_dense_argmax: logits fp32 [batch][classes][gh][gw] -> classes_out [batch][out_h][out_w] = the argmax over the classes of the
+// bilinear interpolation (align_corners = False), score_out (optional) the winning value.  The *_check functions: nullptr, or why
+// the launch is refused; host arithmetic only.  No scratch, no allocation, no counter.
+constexpr int VH_DENSE_FORM_ROWS16 = -2;
+struct DenseHeadArgs {
+    const void* hi;
+    const void* lo;
+    int form, dtype;
+    int64_t rows;
+    int group, tokens, lead, dim;
+    const float* gamma;
+    const float* beta;
+    float eps;
+    int norm;
+    const void* w16;
+    const float* bias;   // [classes] or null
+    int classes;
+    void* out;
+    int elem;
+};
+const char* dense_head_check(const DenseHeadArgs& a);
+hipError_t launch_dense_head(const DenseHeadArgs& a, hipStream_t stream);
+const char* dense_argmax_check(const float* logits, int batch, int classes, int gh, int gw, int out_h, int out_w, const uint8_t* classes_out,
+                               const float* score_out);
+hipError_t launch_dense_argmax(const float* logits, int batch, int classes, int gh, int gw, int out_h, int out_w, uint8_t* classes_out,
+                               float* score_out, hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln
 hipError_t launch_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim,
                              float scale, void* w8, float* wscale, float* c, float* d, hipStream_t stream);

@@ -429,6 +429,11 @@ struct vh_ctx {
     char* attn_store = nullptr;
     size_t attn_slot = 0;
     int acap_layers[VH_MAX_ATTENTION_LAYERS] = {0}, acap_n = 0, acap_nl = -1;
+    // Dense head (vh_set_dense_head; vithip.h "Dense heads"): w rounded to the operand type, the fp32 bias (null: none) and the fp32
+    // logits vh_read_dense_map interpolates, [max_batch][classes][NP].  Only the dense read-outs touch them: no forward knows.
+    void* dense_w16 = nullptr;
+    float *dense_b = nullptr, *dense_logits = nullptr;
+    int dense_classes = 0, dense_norm = VH_FEAT_NORM;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
     struct RingSlot {
         float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;   // h_in / d_in hold bytes in a u8 ring
@@ -1751,6 +1756,9 @@ int vh_destroy(vh_ctx* c) {
     if (c->act[1].base) hipFree(c->act[1].base);
     if (c->feat_store) hipFree(c->feat_store);
     if (c->attn_store) hipFree(c->attn_store);
+    if (c->dense_w16) hipFree(c->dense_w16);
+    if (c->dense_b) hipFree(c->dense_b);
+    if (c->dense_logits) hipFree(c->dense_logits);
     if (c->w16) hipFree(c->w16);
     if (c->bias_img) hipFree(c->bias_img);
     if (c->subln_wb) hipFree(c->subln_wb);
@@ -3052,6 +3060,161 @@ int vh_read_attention(vh_ctx* c, const vh_attention_maps* f) {
     return VH_OK;
 }
 
+// ---- dense heads (vithip.h "Dense heads"; kernels_dense.hip) ----------------------------------------------------------------
+// A pull interface like the token features: the head lives beside the forward's state, the read-outs run the head GEMM (and the
+// upsample + argmax) on the context's main stream over the rows features_live names.  Every refusal is VH_ERR_INVALID and comes
+// before a device is touched.
+static int dense_ctx_check(vh_ctx* c, const char* who) {
+    if (c->cfg.flags & VH_FLAG_CLS_TAIL)
+        return fail(&c->err, VH_ERR_INVALID, "%s: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only", who);
+    if (c->fp8) return fail(&c->err, VH_ERR_INVALID, "%s: a VH_DTYPE_FP8 context has no 16-bit operand type for the head", who);
+    return VH_OK;
+}
+int vh_set_dense_head(vh_ctx* c, const float* w, const float* b, int classes, int norm) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "set_dense_head: null context");
+    if (int rc = dense_ctx_check(c, "set_dense_head")) return rc;
+    if (w) {
+        if (classes < 1 || classes > VH_DENSE_MAX_CLASSES) return fail(&c->err, VH_ERR_INVALID, "set_dense_head: %d classes, outside 1..%d", classes, VH_DENSE_MAX_CLASSES);
+        if (norm != VH_FEAT_NORM && norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "set_dense_head: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", norm);
+        if (c->cfg.dim % 16) return fail(&c->err, VH_ERR_INVALID, "set_dense_head: dim %d is not a multiple of 16", c->cfg.dim);
+    }
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    HIPCHK(&c->err, sync_compute(c));   // a read-out in flight may still read the old head
+    void* w16 = nullptr;
+    float *w32 = nullptr, *b32 = nullptr, *logits = nullptr;
+    if (w) {
+        const size_t n = (size_t)classes * c->cfg.dim;
+        auto drop = [&]() { hipFree(w16); hipFree(w32); hipFree(b32); hipFree(logits); };
+        hipError_t e = hipMalloc(&w16, n * 2);
+        if (e == hipSuccess) e = hipMalloc((void**)&w32, n * 4);
+        if (e == hipSuccess && b) e = hipMalloc((void**)&b32, (size_t)classes * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&logits, (size_t)c->cfg.max_batch * classes * c->L.NP * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(w32, w, n * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && b) e = hipMemcpyAsync(b32, b, (size_t)classes * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = launch_cast(w32, w16, (int64_t)n, c->dt16, c->stream);   // one RNE rounding to the operand type
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            drop();
+            return fail(&c->err, VH_ERR_HIP, "set_dense_head failed: %s", hipGetErrorString(e));
+        }
+        hipFree(w32);
+    }
+    if (c->dense_w16) hipFree(c->dense_w16);
+    if (c->dense_b) hipFree(c->dense_b);
+    if (c->dense_logits) hipFree(c->dense_logits);
+    c->dense_w16 = w16; c->dense_b = b32; c->dense_logits = logits;
+    c->dense_classes = w ? classes : 0;
+    c->dense_norm = w ? norm : VH_FEAT_NORM;
+    return VH_OK;
+}
+int vh_dense_dims(const vh_ctx* c, int* batch, int* classes, int* grid_h, int* grid_w) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "dense_dims: null context");
+    if (batch) *batch = c->last_batch;
+    if (classes) *classes = c->dense_classes;
+    if (grid_h) *grid_h = c->cfg.image_size / c->cfg.patch_size;
+    if (grid_w) *grid_w = c->cfg.image_size / c->cfg.patch_size;
+    return VH_OK;
+}
+static int dense_check_call(vh_ctx* c, const char* who, int batch) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "%s: null context", who);
+    if (int rc = dense_ctx_check(c, who)) return rc;
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "%s: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first", who);
+    if (!c->dense_w16) return fail(&c->err, VH_ERR_INVALID, "%s: no dense head is set (vh_set_dense_head)", who);
+    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_INVALID, "%s: no forward has run", who);
+    if (batch < 1 || batch > c->last_batch) return fail(&c->err, VH_ERR_INVALID, "%s: batch %d is outside 1..%d, the last forward's", who, batch, c->last_batch);
+    return VH_OK;
+}
+static int dense_logits_check(vh_ctx* c, int batch, const void* out, int elem, bool device) {
+    if (int rc = dense_check_call(c, "read_dense_logits", batch)) return rc;
+    if (!out) return fail(&c->err, VH_ERR_INVALID, "read_dense_logits: null output");
+    if (elem != VH_ELEM_F32 && elem != VH_ELEM_F16 && elem != VH_ELEM_BF16)
+        return fail(&c->err, VH_ERR_INVALID, "read_dense_logits: elem %d is not VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16", elem);
+    if (device && ((uintptr_t)out & 15)) return fail(&c->err, VH_ERR_INVALID, "read_dense_logits: the device output pointer %p is not 16-byte aligned", out);
+    return VH_OK;
+}
+static int dense_map_check(vh_ctx* c, int batch, int out_h, int out_w, const uint8_t* classes_out, const float* score_out, bool device) {
+    if (int rc = dense_check_call(c, "read_dense_map", batch)) return rc;
+    if (!classes_out) return fail(&c->err, VH_ERR_INVALID, "read_dense_map: null class map");
+    if (out_h < 1 || out_h > VH_DENSE_MAX_SIDE || out_w < 1 || out_w > VH_DENSE_MAX_SIDE)
+        return fail(&c->err, VH_ERR_INVALID, "read_dense_map: output size %d x %d is outside 1..%d per side", out_h, out_w, VH_DENSE_MAX_SIDE);
+    if (device && (((uintptr_t)classes_out | (uintptr_t)score_out) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "read_dense_map: a device output pointer is not 16-byte aligned (classes %p, score %p)", (const void*)classes_out, (const void*)score_out);
+    return VH_OK;
+}
+// the head GEMM over the live rows of images 0 .. batch - 1 -> out [batch][C][NP] of elem
+static int dense_enqueue_logits(vh_ctx* c, int batch, void* out, int elem, const char* who) {
+    const FeatSource src = features_live(c);
+    DenseHeadArgs a{};
+    a.hi = src.hi; a.lo = src.lo; a.form = src.form; a.dtype = c->dt16;
+    a.rows = (int64_t)batch * c->L.NP; a.group = c->L.NP; a.tokens = c->L.T; a.lead = c->L.lead; a.dim = c->cfg.dim;
+    a.gamma = c->params + c->L.lnfw; a.beta = c->params + c->L.lnfb; a.eps = c->cfg.ln_eps; a.norm = c->dense_norm;
+    a.w16 = c->dense_w16; a.bias = c->dense_b; a.classes = c->dense_classes; a.out = out; a.elem = elem;
+    if (const char* why = dense_head_check(a)) return fail(&c->err, VH_ERR_INVALID, "%s: %s", who, why);
+    HIPCHK(&c->err, launch_dense_head(a, c->stream));
+    return VH_OK;
+}
+static int dense_enqueue_map(vh_ctx* c, int batch, int out_h, int out_w, uint8_t* classes_out, float* score_out) {
+    if (int rc = dense_enqueue_logits(c, batch, c->dense_logits, VH_ELEM_F32, "read_dense_map")) return rc;
+    const int g = c->cfg.image_size / c->cfg.patch_size;
+    if (const char* why = dense_argmax_check(c->dense_logits, batch, c->dense_classes, g, g, out_h, out_w, classes_out, score_out))
+        return fail(&c->err, VH_ERR_INVALID, "read_dense_map: %s", why);
+    HIPCHK(&c->err, launch_dense_argmax(c->dense_logits, batch, c->dense_classes, g, g, out_h, out_w, classes_out, score_out, c->stream));
+    return VH_OK;
+}
+int vh_read_dense_logits_device_async(vh_ctx* c, int batch, void* out, int elem) {
+    if (int rc = dense_logits_check(c, batch, out, elem, true)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return dense_enqueue_logits(c, batch, out, elem, "read_dense_logits");
+}
+int vh_read_dense_logits_device(vh_ctx* c, int batch, void* out, int elem) {
+    if (int rc = vh_read_dense_logits_device_async(c, batch, out, elem)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+// the host forms stage through device memory of the call's own (synchronous calls, outside any captured graph)
+int vh_read_dense_logits(vh_ctx* c, int batch, void* out, int elem) {
+    if (int rc = dense_logits_check(c, batch, out, elem, false)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t n = (size_t)batch * c->dense_classes * c->L.NP * (elem == VH_ELEM_F32 ? 4 : 2);
+    void* d = nullptr;
+    HIPCHK(&c->err, hipMalloc(&d, n));
+    int rc = dense_enqueue_logits(c, batch, d, elem, "read_dense_logits");
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(out, d, n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_compute(c);
+    hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(&c->err, VH_ERR_HIP, "read_dense_logits failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+int vh_read_dense_map_device_async(vh_ctx* c, int batch, int out_h, int out_w, uint8_t* classes_out, float* score_out) {
+    if (int rc = dense_map_check(c, batch, out_h, out_w, classes_out, score_out, true)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return dense_enqueue_map(c, batch, out_h, out_w, classes_out, score_out);
+}
+int vh_read_dense_map_device(vh_ctx* c, int batch, int out_h, int out_w, uint8_t* classes_out, float* score_out) {
+    if (int rc = vh_read_dense_map_device_async(c, batch, out_h, out_w, classes_out, score_out)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+int vh_read_dense_map(vh_ctx* c, int batch, int out_h, int out_w, uint8_t* classes_out, float* score_out) {
+    if (int rc = dense_map_check(c, batch, out_h, out_w, classes_out, score_out, false)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t n = (size_t)batch * out_h * out_w;
+    uint8_t* d_cls = nullptr;
+    float* d_score = nullptr;
+    HIPCHK(&c->err, hipMalloc((void**)&d_cls, n));
+    hipError_t e = score_out ? hipMalloc((void**)&d_score, n * 4) : hipSuccess;
+    int rc = e == hipSuccess ? dense_enqueue_map(c, batch, out_h, out_w, d_cls, d_score) : 0;
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(classes_out, d_cls, n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !rc && score_out) e = hipMemcpyAsync(score_out, d_score, n * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_compute(c);
+    hipFree(d_cls);
+    hipFree(d_score);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(&c->err, VH_ERR_HIP, "read_dense_map failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
@@ -3571,6 +3734,27 @@ int vh_op_map_pool(const void* hi, const void* lo, int form, int batch, int toke
     hipError_t e = launch_map_pool(a, qk, heads, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "map_pool failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the dense head's GEMM on caller-made rows of the operand type ("Dense heads")
+int vh_op_dense_head(const void* rows16, int64_t rows, int dim, const void* w16, const float* bias, int classes, int group, float* out, int dtype,
+                     void* stream) {
+    DenseHeadArgs a{};
+    a.hi = rows16; a.form = VH_DENSE_FORM_ROWS16; a.dtype = dtype; a.rows = rows; a.group = group; a.tokens = group; a.dim = dim;
+    a.norm = VH_FEAT_RAW; a.w16 = w16; a.bias = bias; a.classes = classes; a.out = out; a.elem = VH_ELEM_F32;
+    if (const char* why = dense_head_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_dense_head(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "dense_head failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the upsample + argmax on caller-made fp32 logits
+int vh_op_dense_argmax(const float* logits, int batch, int classes, int gh, int gw, int out_h, int out_w, uint8_t* classes_out, float* score_out,
+                       void* stream) {
+    if (const char* why = dense_argmax_check(logits, batch, classes, gh, gw, out_h, out_w, classes_out, score_out)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_dense_argmax(logits, batch, classes, gh, gw, out_h, out_w, classes_out, score_out, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "dense_argmax failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 // the VH_FLAG_ROPE rotation on caller-made q|k|v

@@ -362,6 +362,16 @@ SYMBOLS = {
     "vh_op_resize_bgra": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_resize_y410": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "vh_op_cast": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "vh_set_dense_head": (_i, [_vp, _vp, _vp, _i, _i]),
+    "vh_dense_dims": (_i, [_vp, _pi, _pi, _pi, _pi]),
+    "vh_read_dense_logits": (_i, [_vp, _i, _vp, _i]),
+    "vh_read_dense_logits_device": (_i, [_vp, _i, _vp, _i]),
+    "vh_read_dense_logits_device_async": (_i, [_vp, _i, _vp, _i]),
+    "vh_read_dense_map": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "vh_read_dense_map_device": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "vh_read_dense_map_device_async": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "vh_op_dense_head": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "vh_op_dense_argmax": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
@@ -2084,6 +2094,51 @@ class VitContext:
         """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
         _check(lib().vh_read_features_device_async(self.h, C.byref(desc)), self.h)
 
+    # ---- dense heads on the patch rows of the last forward (vithip.h "Dense heads") ----
+    def set_dense_head(self, w, b=None, norm=True):
+        """A linear head for every patch row: w [classes, dim], b [classes] or None; norm: the rows pass the model's final LayerNorm.
+        w = None clears the head.  No forward knows of it: logits and cached graphs stay as they are."""
+        if w is None:
+            _check(lib().vh_set_dense_head(self.h, None, None, 0, FEAT_NORM), self.h)
+            return
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        if w.ndim != 2 or w.shape[1] != self.cfg["dim"]:
+            raise ValueError(f"set_dense_head: w must be [classes, {self.cfg['dim']}], got {w.shape}")
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float32)
+            if b.shape != (w.shape[0],):
+                raise ValueError(f"set_dense_head: b must be [{w.shape[0]}], got {b.shape}")
+        _check(lib().vh_set_dense_head(self.h, w.ctypes.data, b.ctypes.data if b is not None else None, w.shape[0],
+                                       FEAT_NORM if norm else FEAT_RAW), self.h)
+
+    def dense_dims(self):
+        """(batch of the last forward, classes of the head or 0, grid height, grid width)."""
+        v = [C.c_int(0) for _ in range(4)]
+        _check(lib().vh_dense_dims(self.h, *(C.byref(x) for x in v)), self.h)
+        return tuple(x.value for x in v)
+
+    def dense_logits(self, batch=None, dtype=ELEM_F32):
+        """The head's logits of images 0 .. batch - 1 of the last forward (None: all), [batch, classes, gh, gw], channels first:
+        float32 / float16, or uint16 holding bf16 bits for ELEM_BF16."""
+        b, c, gh, gw = self.dense_dims()
+        batch = b if batch is None else int(batch)
+        dt = {ELEM_F32: np.float32, ELEM_F16: np.float16, ELEM_BF16: np.uint16}.get(dtype, np.float32)
+        out = np.empty((max(batch, 1), max(c, 1), gh, gw), dtype=dt)   # (a refused call raises below, with the library's message)
+        _check(lib().vh_read_dense_logits(self.h, batch, out.ctypes.data, dtype), self.h)
+        return out
+
+    def dense_map(self, batch=None, out_hw=None, scores=False):
+        """The class map of images 0 .. batch - 1 at out_hw = (height, width) (None: the patch grid): the argmax over the classes of
+        the bilinearly interpolated logits (align_corners=False), uint8 [batch, h, w]; with scores also the winning value, float32."""
+        b, _, gh, gw = self.dense_dims()
+        batch = b if batch is None else int(batch)
+        oh, ow = (gh, gw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        shape = (max(batch, 1), min(max(oh, 1), 4096), min(max(ow, 1), 4096))
+        cls = np.empty(shape, dtype=np.uint8)
+        sc = np.empty(shape, dtype=np.float32) if scores else None
+        _check(lib().vh_read_dense_map(self.h, batch, oh, ow, cls.ctypes.data, sc.ctypes.data if scores else None), self.h)
+        return (cls, sc) if scores else cls
+
     # ---- layer features: several layers of one forward (vithip.h "Layer features") ----
     def set_feature_layers(self, layers):
         """The layers every following forward captures: strictly ascending, each 1 .. layers (k = the residual stream after k
@@ -2529,6 +2584,50 @@ def op_map_pool(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_
     """The attention-pooling head's one-pass kernel on its own (vh_op_map_pool): z [batch, heads, dim] fp32 = the softmax(qk[h] . y_t)-
     weighted sum of y_t = LayerNorm(row t; gamma, beta, eps) over rows lead .. tokens - 1 of every image; qk [heads, dim] fp32."""
     _check(lib().vh_op_map_pool(hi_ptr, lo_ptr, form, batch, tokens, lead, dim, gamma_ptr, beta_ptr, eps, qk_ptr, heads, z_ptr, None))
+
+
+def op_dense_head(rows_ptr, rows, dim, w_ptr, bias_ptr, classes, group, out_ptr, dtype):
+    """The dense head's GEMM on its own (vh_op_dense_head): rows [rows, dim] and w [classes, dim] of `dtype`, bias [classes] fp32 or None
+    -> out [rows / group, classes, group] fp32 (group = the rows of one image)."""
+    _check(lib().vh_op_dense_head(rows_ptr, rows, dim, w_ptr, bias_ptr, classes, group, out_ptr, dtype, None))
+
+
+def op_dense_argmax(logits_ptr, batch, classes, gh, gw, out_h, out_w, classes_ptr, score_ptr=None):
+    """The upsample + argmax on its own (vh_op_dense_argmax): logits [batch, classes, gh, gw] fp32 -> classes [batch, out_h, out_w] bytes
+    and, optionally, the winning interpolated logit as fp32."""
+    _check(lib().vh_op_dense_argmax(logits_ptr, batch, classes, gh, gw, out_h, out_w, classes_ptr, score_ptr, None))
+
+
+def dense_head_from_dinov2_bnhead(sd, eps=None, dtype=np.float32):
+    """(w [classes, dim], b [classes]) of DINOv2's single-layer "linear" segmentation head (mmseg BNHead: SyncBatchNorm on the
+    channels, then a 1x1 convolution) with the BatchNorm folded in, in float64 and rounded once to `dtype`:
+        y = conv(bn(x)),  bn(x) = (x - running_mean) / sqrt(running_var + eps) * weight + bias
+          = (W * s) x + (W (bias - running_mean * s) + conv_bias),  s = weight / sqrt(running_var + eps).
+    Keys: decode_head.bn.{weight, bias, running_mean, running_var} and decode_head.conv_seg.{weight, bias}, with or without the
+    "decode_head." prefix; eps: decode_head.bn.eps if present, else 1e-5.  Feed it x_norm_patchtokens: set_dense_head(w, b, norm=True).
+    The four-layer multi-scale ("ms") head concatenates four layers' features and is out of scope."""
+    def get(name, optional=False):
+        for k in ("decode_head." + name, name):
+            if k in sd:
+                v = sd[k]
+                return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64)
+        if optional:
+            return None
+        raise KeyError(f"dense_head_from_dinov2_bnhead: {name} is missing")
+    cw = get("conv_seg.weight")
+    cw = cw.reshape(cw.shape[0], -1)
+    cb = get("conv_seg.bias", optional=True)
+    g, be, mu, var = get("bn.weight"), get("bn.bias"), get("bn.running_mean"), get("bn.running_var")
+    if cw.shape[1] != g.shape[0]:
+        raise ValueError(f"dense_head_from_dinov2_bnhead: the convolution takes {cw.shape[1]} channels, the BatchNorm has {g.shape[0]} "
+                         "(the multi-scale head is out of scope)")
+    if eps is None:
+        e = get("bn.eps", optional=True)
+        eps = float(e) if e is not None else 1e-5
+    s = g / np.sqrt(var + eps)
+    w = cw * s[None, :]
+    b = cw @ (be - mu * s) + (cb if cb is not None else 0.0)
+    return w.astype(dtype), b.astype(dtype)
 
 
 def op_rope(qkv_ptr, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_ptr, sin_ptr):
