@@ -1166,6 +1166,67 @@ int vh_read_dense_map(vh_ctx* ctx, int batch, int out_h, int out_w, uint8_t* cla
 int vh_read_dense_map_device(vh_ctx* ctx, int batch, int out_h, int out_w, uint8_t* classes_out_dev, float* score_out_dev);
 int vh_read_dense_map_device_async(vh_ctx* ctx, int batch, int out_h, int out_w, uint8_t* classes_out_dev, float* score_out_dev);
 
+/* ---- Embedding search ------------------------------------------------------------------------
+ * What the consumers of an embedding run next: the inner product of every image's embedding with a bank of vectors, and the best few --
+ * CLIP / SigLIP zero-shot classification (the bank: the text embeddings of the class prompts), DINOv2 / DINOv3 / I-JEPA k-NN evaluation
+ * (the bank: 10^5 .. 10^6 training features, top 10 .. 20, a weighted vote), retrieval and de-duplication.  With a bank set, one
+ * forward plus one search return [batch][k] (index, score) pairs; the [batch][n] scores are never written: the scan streams the bank
+ * once, multiplies on the matrix cores and selects while the scores are in registers.  A PULL interface like the dense heads: the call
+ * reads what the LAST forward enqueued on the context left (any entry point, eager or graph replay; "WHICH FORWARD" above) or rows of
+ * the caller's, no forward knows of the bank, and setting or clearing it drops no cached graph and changes no logit.
+ *
+ * ARITHMETIC, for bits.  W = the bank's width, T16 = the context's operand type (VH_DTYPE_BF16 / VH_DTYPE_FP16; bf16 on a VH_DTYPE_FP8
+ * context).
+ *   b16[m][j]   = RNE_T16(b[m][j] * s_m), rounded once when the bank is set; s_m = 1, or with normalise 1 / sqrt(sum_j b^2) -- sum,
+ *                 root, quotient and product in float64 on the host; a zero row stays zero.
+ *   q16[i][j]   = RNE_T16(q[i][j] * r_i); r_i = 1, or with normalise r_i = 1 / sqrt(S_i) in fp32 (a correctly rounded root, then a
+ *                 correctly rounded quotient), S_i = sum_j q^2 in the row-sum order of the wave-per-row skeleton (csrc/kernels_rows.hip):
+ *                 lane l of 64 adds its float4 chunks l, l + 64, .. in that order from +0, each chunk as (q0^2 + q1^2) + (q2^2 + q3^2)
+ *                 with every square and sum rounded to fp32, then the xor butterfly over lane distances 32, 16, .. 1.  S_i = 0: r_i = 1.
+ *   score[i][m] = sum_j q16[i][j] * b16[m][j]: the products are exact in fp32; the sum starts at +0 and takes j ascending in groups of
+ *                 16, one v_mfma_f32_32x32x16 (gfx950) per group -- the dense head's sum.  It depends on (i, m, W) alone: never on nq,
+ *                 n, k or on how the launcher splits the bank.  Where every product and partial sum is an integer below 2^24 it is exact.
+ *   result      the first k bank rows under the total order (score descending, index ascending), in that order; with n < k the tail is
+ *                 index -1 and score -inf.  The inputs are finite.  One well-defined array, the same bits whatever the geometry.
+ *
+ *   vh_set_bank      vectors_host [n][width] of elem VH_ELEM_F32 / F16 / BF16; n 1 .. VH_SEARCH_MAX_ROWS; width a multiple of 16 in 16 ..
+ *                    VH_SEARCH_MAX_WIDTH; normalise 0 / 1.  NULL clears the bank (the other arguments are ignored).  Synchronous.  It
+ *                    allocates the bank (2 n width bytes) and the workspace of the widest search the calls accept (about 40 MB).
+ *   vh_bank_dims     either may be NULL; both 0 while no bank is set
+ *   vh_search_bank   index [nq][k] int32 and score [nq][k] fp32, best first.  source VH_SEARCH_HEAD_INPUT: the queries are rows 0 ..
+ *                    nq - 1 of the head's input of the last forward (nq <= its batch; `rows` is ignored); VH_SEARCH_ROWS: the queries
+ *                    are rows [nq][W] fp32 of the caller's, nq 1 .. VH_SEARCH_MAX_QUERIES, unrelated to any forward and legal before
+ *                    the first one.  Host buffers, synchronous.
+ *   .._device / .._device_async   device buffers; enqueue on the context's stream and wait / enqueue only: no allocation and no host
+ *                    state, eager and inside a stream capture alike
+ *
+ * REFUSED with VH_ERR_INVALID, each with a message of its own, before a device is touched, nothing enqueued and no output written: a
+ * null context, descriptor, output or (VH_SEARCH_ROWS) rows; n, width, elem, normalise, source, k or nq out of range; a bank whose
+ * width is not the head input's (VH_SEARCH_HEAD_INPUT); no bank is set; no forward has run (VH_SEARCH_HEAD_INPUT); a device pointer
+ * that is not 16-byte aligned.  VH_ERR_STATE: a ring exists on the context (its forwards belong to slots).  The calls go through
+ * neither the rings nor the device groups. */
+#define VH_SEARCH_MAX_K 32
+#define VH_SEARCH_MAX_WIDTH 4096
+#define VH_SEARCH_MAX_QUERIES 4096
+#define VH_SEARCH_MAX_ROWS (1 << 28)
+#define VH_SEARCH_HEAD_INPUT 0 /* the [batch][W] fp32 rows the head multiplies in the last forward: LN(class token), or what the
+                                  VH_FLAG_POOL mode / the MAP head computes (W = D, or 2 D with VH_POOL_CLS_AVG) */
+#define VH_SEARCH_ROWS 1       /* the caller's fp32 rows [nq][W] (a device pointer for the _device forms): a CLIP tower's logits */
+typedef struct vh_search { /* sizeof == 40: source 0, k 4, normalise 8, nq 12, rows 16, index 24, score 32 */
+    int32_t source;        /* VH_SEARCH_HEAD_INPUT / VH_SEARCH_ROWS */
+    int32_t k;             /* 1 .. VH_SEARCH_MAX_K */
+    int32_t normalise;     /* 1: every query row is divided by its L2 norm first */
+    int32_t nq;            /* query rows */
+    const float* rows;     /* VH_SEARCH_ROWS: [nq][W] fp32 */
+    int32_t* index;        /* [nq][k] */
+    float* score;          /* [nq][k] */
+} vh_search;
+int vh_set_bank(vh_ctx* ctx, const void* vectors_host, int64_t n, int width, int elem, int normalise);
+int vh_bank_dims(const vh_ctx* ctx, int64_t* n, int* width);
+int vh_search_bank(vh_ctx* ctx, const vh_search* host);
+int vh_search_bank_device(vh_ctx* ctx, const vh_search* dev);
+int vh_search_bank_device_async(vh_ctx* ctx, const vh_search* dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1499,6 +1560,15 @@ int vh_op_dense_head(const void* rows16_dev, int64_t rows, int dim, const void* 
  * pointer 16-byte aligned.  Every argument is checked before a device is touched, each refusal with a message of its own. */
 int vh_op_dense_argmax(const float* logits_f32_dev, int batch, int classes, int gh, int gw, int out_h, int out_w, uint8_t* classes_out_dev,
                        float* score_out_dev, void* stream);
+/* The search on its own ("Embedding search"): rows_f32_dev [nq][width] fp32 and bank16_dev [n][width] of `dtype` (VH_DTYPE_BF16 /
+ * VH_DTYPE_FP16) -> index_dev [nq][k] int32, score_dev [nq][k] fp32; workspace_dev of vh_op_search_workspace_bytes(nq, n, k) bytes
+ * (0: an argument is out of range).  Ranges as above; every pointer 16-byte aligned.  Every argument is checked before a device is
+ * touched, each refusal with a message of its own.  vh_op_search_slabs: the number of bank slabs the launcher splits n rows into for
+ * nq queries (a function of the two alone; 0: out of range). */
+int vh_op_search(const float* rows_f32_dev, int nq, int width, int normalise, const void* bank16_dev, int64_t n, int dtype, int k,
+                 void* workspace_dev, int32_t* index_dev, float* score_dev, void* stream);
+size_t vh_op_search_workspace_bytes(int nq, int64_t n, int k);
+int vh_op_search_slabs(int nq, int64_t n);
 /* The rotation of a VH_FLAG_ROPE context on its own ("THE FUNCTION" at VH_FLAG_ROPE), in place on caller-made q|k|v of `dtype`
  * (VH_DTYPE_BF16 / VH_DTYPE_FP16) elements: q and k of rows lead .. tokens - 1 of every image and head are rotated by cos_dev / sin_dev
  * [tokens - lead][head_dim / 2] fp32; v, the lead rows and every row beyond batch * tokens are never written.

@@ -359,6 +359,28 @@ const char* dense_argmax_check(const float* logits, int batch, int classes, int 
                                const float* score_out);
 hipError_t launch_dense_argmax(const float* logits, int batch, int classes, int gh, int gw, int out_h, int out_w, uint8_t* classes_out,
                                float* score_out, hipStream_t stream);
+// Embedding search (kernels_search.hip; contract: vithip.h, "Embedding search").  launch_search: index [nq][k] / score [nq][k] <- the k
+// first rows of bank16 [n][width] of `dtype` under (score descending, index ascending), score = the inner product with the 16-bit
+// image of rows [nq][row_stride] fp32 (normalise: each row scaled by 1 / its L2 norm first).  Three launches on `stream` -- the query
+// image, the scan, the merge of the slabs (none with one slab) -- in the caller's workspace of search_workspace_bytes(nq, n, k).
+// search_plan: the split the launcher uses, a function of nq and n alone.  search_check: nullptr, or why the launch is refused; host
+// arithmetic only.  No scratch, no allocation, no counter.
+struct SearchArgs {
+    const float* rows;
+    int64_t row_stride;   // floats between query rows (>= width, a multiple of 4)
+    int nq, width, normalise;
+    const void* bank16;
+    int64_t n;
+    int dtype, k;
+    void* workspace;
+    int32_t* index;
+    float* score;
+};
+struct SearchPlan { int nq_pad, slabs; int64_t slab_len; };
+SearchPlan search_plan(int nq, int64_t n);
+size_t search_workspace_bytes(int nq, int64_t n, int k);   // 0: an argument is out of range
+const char* search_check(const SearchArgs& a);
+hipError_t launch_search(const SearchArgs& a, hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln
 hipError_t launch_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim,
                              float scale, void* w8, float* wscale, float* c, float* d, hipStream_t stream);

@@ -434,6 +434,11 @@ struct vh_ctx {
     void* dense_w16 = nullptr;
     float *dense_b = nullptr, *dense_logits = nullptr;
     int dense_classes = 0, dense_norm = VH_FEAT_NORM;
+    // Embedding search (vh_set_bank; vithip.h "Embedding search"): the bank as rows of the operand type and the workspace of the widest
+    // search the context serves.  Only vh_search_bank touches them: no forward knows.
+    void *bank16 = nullptr, *search_ws = nullptr;
+    int64_t bank_n = 0;
+    int bank_w = 0;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
     struct RingSlot {
         float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;   // h_in / d_in hold bytes in a u8 ring
@@ -1759,6 +1764,8 @@ int vh_destroy(vh_ctx* c) {
     if (c->dense_w16) hipFree(c->dense_w16);
     if (c->dense_b) hipFree(c->dense_b);
     if (c->dense_logits) hipFree(c->dense_logits);
+    if (c->bank16) hipFree(c->bank16);
+    if (c->search_ws) hipFree(c->search_ws);
     if (c->w16) hipFree(c->w16);
     if (c->bias_img) hipFree(c->bias_img);
     if (c->subln_wb) hipFree(c->subln_wb);
@@ -3215,6 +3222,161 @@ int vh_read_dense_map(vh_ctx* c, int batch, int out_h, int out_w, uint8_t* class
     return VH_OK;
 }
 
+// ---- embedding search (vithip.h "Embedding search"; kernels_search.hip) --------------------------------------------------------
+// A pull interface like the dense heads: the bank lives beside the forward's state and vh_search_bank enqueues the query image, the
+// scan and the merge on the context's main stream.  Every refusal comes before a device is touched.
+static double search_elem(const void* p, size_t i, int elem) {
+    if (elem == VH_ELEM_F32) return (double)((const float*)p)[i];
+    const uint16_t h = ((const uint16_t*)p)[i];
+    if (elem == VH_ELEM_BF16) {
+        const uint32_t u = (uint32_t)h << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return (double)f;
+    }
+    const int e = (h >> 10) & 31, m = h & 1023;
+    const double v = e ? ldexp(1.0 + m / 1024.0, e - 15) : ldexp(m / 1024.0, -14);   // (the inputs are finite)
+    return (h & 0x8000) ? -v : v;
+}
+// one round-to-nearest-even from float64 to the bits of the 16-bit operand type
+static uint16_t search_round16(double x, bool bf) {
+    const uint16_t sign = std::signbit(x) ? 0x8000 : 0;
+    const double a = fabs(x);
+    if (a == 0.0) return sign;
+    const int mant = bf ? 7 : 10, emin = bf ? -126 : -14, emax = bf ? 127 : 15, bias = bf ? 127 : 15;
+    int e;
+    frexp(a, &e);
+    e = e - 1 < emin ? emin : e - 1;
+    const double v = nearbyint(ldexp(a, mant - e)) * ldexp(1.0, e - mant);   // a multiple of the quantum at a's exponent
+    if (v == 0.0) return sign;
+    if (v >= ldexp(1.0, emax + 1)) return sign | (uint16_t)((2 * bias + 1) << mant);
+    frexp(v, &e);
+    e -= 1;
+    if (e < emin) return sign | (uint16_t)ldexp(v, mant - emin);
+    return sign | (uint16_t)(((e + bias) << mant) + ((int)ldexp(v, mant - e) - (1 << mant)));
+}
+int vh_set_bank(vh_ctx* c, const void* vectors, int64_t n, int width, int elem, int normalise) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "set_bank: null context");
+    if (vectors) {
+        if (n < 1 || n > VH_SEARCH_MAX_ROWS) return fail(&c->err, VH_ERR_INVALID, "set_bank: %lld rows, outside 1..%d", (long long)n, VH_SEARCH_MAX_ROWS);
+        if (width < 16 || width > VH_SEARCH_MAX_WIDTH || width % 16)
+            return fail(&c->err, VH_ERR_INVALID, "set_bank: width %d is not a multiple of 16 in 16..%d", width, VH_SEARCH_MAX_WIDTH);
+        if (elem != VH_ELEM_F32 && elem != VH_ELEM_F16 && elem != VH_ELEM_BF16)
+            return fail(&c->err, VH_ERR_INVALID, "set_bank: elem %d is not VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16", elem);
+        if (normalise != 0 && normalise != 1) return fail(&c->err, VH_ERR_INVALID, "set_bank: normalise %d is not 0 or 1", normalise);
+    }
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    HIPCHK(&c->err, sync_compute(c));   // a search in flight may still read the old bank
+    void *bank = nullptr, *ws = nullptr;
+    if (vectors) {
+        size_t ws_bytes = 0;   // the widest search the calls accept: any nq up to VH_SEARCH_MAX_QUERIES, k = VH_SEARCH_MAX_K
+        for (int nq = 64; nq <= VH_SEARCH_MAX_QUERIES; nq += 64) {
+            const size_t b = search_workspace_bytes(nq, n, VH_SEARCH_MAX_K);
+            ws_bytes = b > ws_bytes ? b : ws_bytes;
+        }
+        hipError_t e = hipMalloc(&bank, (size_t)n * width * 2);
+        if (e == hipSuccess) e = hipMalloc(&ws, ws_bytes);
+        const bool bf = c->dt16 == VH_DTYPE_BF16;
+        const int64_t chunk = 4096;
+        std::vector<uint16_t> stage((size_t)(n < chunk ? n : chunk) * width);
+        for (int64_t r0 = 0; e == hipSuccess && r0 < n; r0 += chunk) {
+            const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
+            for (int64_t r = 0; r < rows; ++r) {
+                const size_t o = (size_t)(r0 + r) * width;
+                double scale = 1.0;
+                if (normalise) {
+                    double ss = 0.0;
+                    for (int j = 0; j < width; ++j) { const double v = search_elem(vectors, o + j, elem); ss += v * v; }
+                    if (ss > 0.0) scale = 1.0 / sqrt(ss);
+                }
+                for (int j = 0; j < width; ++j) stage[(size_t)r * width + j] = search_round16(search_elem(vectors, o + j, elem) * scale, bf);
+            }
+            e = hipMemcpy((char*)bank + (size_t)r0 * width * 2, stage.data(), (size_t)rows * width * 2, hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) {
+            hipFree(bank);
+            hipFree(ws);
+            return fail(&c->err, VH_ERR_HIP, "set_bank failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (c->bank16) hipFree(c->bank16);
+    if (c->search_ws) hipFree(c->search_ws);
+    c->bank16 = bank; c->search_ws = ws;
+    c->bank_n = vectors ? n : 0;
+    c->bank_w = vectors ? width : 0;
+    return VH_OK;
+}
+int vh_bank_dims(const vh_ctx* c, int64_t* n, int* width) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "bank_dims: null context");
+    if (n) *n = c->bank_n;
+    if (width) *width = c->bank_w;
+    return VH_OK;
+}
+static int search_check_call(vh_ctx* c, const vh_search* d, bool device) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "search_bank: null context");
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "search_bank: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
+    if (!d) return fail(&c->err, VH_ERR_INVALID, "search_bank: null descriptor");
+    if (!c->bank16) return fail(&c->err, VH_ERR_INVALID, "search_bank: no bank is set (vh_set_bank)");
+    if (d->source != VH_SEARCH_HEAD_INPUT && d->source != VH_SEARCH_ROWS)
+        return fail(&c->err, VH_ERR_INVALID, "search_bank: source %d is not VH_SEARCH_HEAD_INPUT (0) or VH_SEARCH_ROWS (1)", d->source);
+    if (d->k < 1 || d->k > VH_SEARCH_MAX_K) return fail(&c->err, VH_ERR_INVALID, "search_bank: k %d is outside 1..%d", d->k, VH_SEARCH_MAX_K);
+    if (d->normalise != 0 && d->normalise != 1) return fail(&c->err, VH_ERR_INVALID, "search_bank: normalise %d is not 0 or 1", d->normalise);
+    if (d->source == VH_SEARCH_HEAD_INPUT) {
+        if (c->last_batch <= 0) return fail(&c->err, VH_ERR_INVALID, "search_bank: no forward has run");
+        if (d->nq < 1 || d->nq > c->last_batch) return fail(&c->err, VH_ERR_INVALID, "search_bank: nq %d is outside 1..%d, the last forward's batch", d->nq, c->last_batch);
+        if (c->bank_w != c->L.HW) return fail(&c->err, VH_ERR_INVALID, "search_bank: the bank's width %d is not the head input's %d", c->bank_w, c->L.HW);
+    } else {
+        if (!d->rows) return fail(&c->err, VH_ERR_INVALID, "search_bank: null rows with VH_SEARCH_ROWS");
+        if (d->nq < 1 || d->nq > VH_SEARCH_MAX_QUERIES) return fail(&c->err, VH_ERR_INVALID, "search_bank: nq %d is outside 1..%d", d->nq, VH_SEARCH_MAX_QUERIES);
+    }
+    if (!d->index || !d->score) return fail(&c->err, VH_ERR_INVALID, "search_bank: null output (index and score are both required)");
+    if (device && (((uintptr_t)d->index | (uintptr_t)d->score | (d->source == VH_SEARCH_ROWS ? (uintptr_t)d->rows : 0)) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "search_bank: a device pointer is not 16-byte aligned (rows %p, index %p, score %p)", (const void*)d->rows, (void*)d->index, (void*)d->score);
+    return VH_OK;
+}
+static int search_enqueue(vh_ctx* c, const vh_search& d, const float* rows_dev, int32_t* index_dev, float* score_dev) {
+    SearchArgs a{};
+    a.rows = d.source == VH_SEARCH_HEAD_INPUT ? c->act[c->last_set].clsn32 : rows_dev;
+    a.row_stride = c->bank_w; a.nq = d.nq; a.width = c->bank_w; a.normalise = d.normalise;
+    a.bank16 = c->bank16; a.n = c->bank_n; a.dtype = c->dt16; a.k = d.k;
+    a.workspace = c->search_ws; a.index = index_dev; a.score = score_dev;
+    if (const char* why = search_check(a)) return fail(&c->err, VH_ERR_INVALID, "search_bank: %s", why);
+    HIPCHK(&c->err, launch_search(a, c->stream));
+    return VH_OK;
+}
+int vh_search_bank_device_async(vh_ctx* c, const vh_search* d) {
+    if (int rc = search_check_call(c, d, true)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return search_enqueue(c, *d, d->rows, d->index, d->score);
+}
+int vh_search_bank_device(vh_ctx* c, const vh_search* d) {
+    if (int rc = vh_search_bank_device_async(c, d)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+// the host form stages through device memory of the call's own (a synchronous call, outside any captured graph)
+int vh_search_bank(vh_ctx* c, const vh_search* d) {
+    if (int rc = search_check_call(c, d, false)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t n_out = (size_t)d->nq * d->k, n_rows = d->source == VH_SEARCH_ROWS ? (size_t)d->nq * c->bank_w : 0;
+    float *d_rows = nullptr, *d_score = nullptr;
+    int32_t* d_index = nullptr;
+    hipError_t e = hipMalloc((void**)&d_index, n_out * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_score, n_out * 4);
+    if (e == hipSuccess && n_rows) e = hipMalloc((void**)&d_rows, n_rows * 4);
+    if (e == hipSuccess && n_rows) e = hipMemcpyAsync(d_rows, d->rows, n_rows * 4, hipMemcpyHostToDevice, c->stream);
+    const int rc = e == hipSuccess ? search_enqueue(c, *d, d_rows, d_index, d_score) : 0;
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(d->index, d_index, n_out * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(d->score, d_score, n_out * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_compute(c);
+    hipFree(d_index);
+    hipFree(d_score);
+    hipFree(d_rows);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(&c->err, VH_ERR_HIP, "search_bank failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
@@ -3756,6 +3918,23 @@ int vh_op_dense_argmax(const float* logits, int batch, int classes, int gh, int 
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "dense_argmax failed: %s", hipGetErrorString(e));
     return VH_OK;
+}
+// the search on caller-made rows, bank and workspace ("Embedding search")
+int vh_op_search(const float* rows, int nq, int width, int normalise, const void* bank16, int64_t n, int dtype, int k, void* workspace,
+                 int32_t* index, float* score, void* stream) {
+    SearchArgs a{};
+    a.rows = rows; a.row_stride = width; a.nq = nq; a.width = width; a.normalise = normalise; a.bank16 = bank16; a.n = n; a.dtype = dtype;
+    a.k = k; a.workspace = workspace; a.index = index; a.score = score;
+    if (const char* why = search_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_search(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "search failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+size_t vh_op_search_workspace_bytes(int nq, int64_t n, int k) { return search_workspace_bytes(nq, n, k); }
+int vh_op_search_slabs(int nq, int64_t n) {
+    if (nq < 1 || nq > VH_SEARCH_MAX_QUERIES || n < 1 || n > VH_SEARCH_MAX_ROWS) return 0;
+    return search_plan(nq, n).slabs;
 }
 // the VH_FLAG_ROPE rotation on caller-made q|k|v
 int vh_op_rope(void* qkv16, int dtype, int batch, int tokens, int heads, int head_dim, int lead, int64_t hm_rows, const float* cos_t,

@@ -149,6 +149,17 @@ class LayerFeatures(C.Structure):
                 ("norm", C.c_int32), ("layer", C.c_int32), ("patch_layout", C.c_int32)]
 
 
+SEARCH_HEAD_INPUT, SEARCH_ROWS = 0, 1   # vh_search.source (VH_SEARCH_*): the head's input of the last forward / the caller's rows
+SEARCH_MAX_K, SEARCH_MAX_WIDTH, SEARCH_MAX_QUERIES = 32, 4096, 4096
+
+
+class Search(C.Structure):
+    """vh_search: the queries (source SEARCH_HEAD_INPUT, or SEARCH_ROWS with rows [nq, W] fp32), k, normalise, and where index [nq, k]
+    int32 and score [nq, k] fp32 go (host or device pointers).  40 bytes."""
+    _fields_ = [("source", C.c_int32), ("k", C.c_int32), ("normalise", C.c_int32), ("nq", C.c_int32), ("rows", C.c_void_p),
+                ("index", C.c_void_p), ("score", C.c_void_p)]
+
+
 MAX_ATTENTION_LAYERS = 64
 ATTN_Q_CLS, ATTN_Q_LEAD = 0, 1        # vh_set_attention_layers queries (VH_ATTN_Q_*): the class token's row / every leading row
 ATTN_KEYS_ALL, ATTN_KEYS_PATCH = 0, 1  # vh_attention_maps.keys (VH_ATTN_KEYS_*): all key columns / the patch columns
@@ -372,6 +383,14 @@ SYMBOLS = {
     "vh_read_dense_map_device_async": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "vh_op_dense_head": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "vh_op_dense_argmax": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vh_set_bank": (_i, [_vp, _vp, _i64, _i, _i, _i]),
+    "vh_bank_dims": (_i, [_vp, C.POINTER(C.c_int64), _pi]),
+    "vh_search_bank": (_i, [_vp, _vp]),
+    "vh_search_bank_device": (_i, [_vp, _vp]),
+    "vh_search_bank_device_async": (_i, [_vp, _vp]),
+    "vh_op_search": (_i, [_vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "vh_op_search_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "vh_op_search_slabs": (_i, [_i, _i64]),
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
@@ -2139,6 +2158,52 @@ class VitContext:
         _check(lib().vh_read_dense_map(self.h, batch, oh, ow, cls.ctypes.data, sc.ctypes.data if scores else None), self.h)
         return (cls, sc) if scores else cls
 
+    # ---- embedding search against a device-resident bank (vithip.h "Embedding search") ----
+    def set_bank(self, vectors, normalise=True):
+        """The bank the searches run against: vectors [n, width] float32 / float16 (or uint16 holding bf16 bits), each row divided by its
+        L2 norm first (normalise) and kept on the device in the context's operand type.  None clears it.  No forward knows of it."""
+        if vectors is None:
+            _check(lib().vh_set_bank(self.h, None, 0, 0, ELEM_F32, 0), self.h)
+            return
+        v = np.ascontiguousarray(vectors)
+        if v.dtype not in (np.float16, np.uint16):
+            v = np.ascontiguousarray(v, dtype=np.float32)
+        if v.ndim != 2:
+            raise ValueError(f"set_bank: vectors must be [n, width], got {v.shape}")
+        elem = {np.dtype(np.float32): ELEM_F32, np.dtype(np.float16): ELEM_F16, np.dtype(np.uint16): ELEM_BF16}[v.dtype]
+        _check(lib().vh_set_bank(self.h, v.ctypes.data, v.shape[0], v.shape[1], elem, 1 if normalise else 0), self.h)
+
+    def bank_dims(self):
+        """(rows, width) of the bank; (0, 0) while none is set."""
+        n, w = C.c_int64(0), C.c_int(0)
+        _check(lib().vh_bank_dims(self.h, C.byref(n), C.byref(w)), self.h)
+        return n.value, w.value
+
+    def search(self, k, rows=None, normalise=True, nq=None):
+        """(index [nq, k] int32, score [nq, k] float32), best first, of the bank rows closest to each query: the head's input of the
+        last forward (rows None; nq None: the whole batch), or rows [nq, width] float32 of the caller's -- a CLIP tower's logits."""
+        if rows is None:
+            src, r, rp = SEARCH_HEAD_INPUT, None, None
+            nq = self.dense_dims()[0] if nq is None else int(nq)   # (the last forward's batch)
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.float32)
+            if r.ndim != 2 or r.shape[1] != self.bank_dims()[1]:
+                raise ValueError(f"search: rows must be [nq, {self.bank_dims()[1]}], got {r.shape}")
+            src, rp, nq = SEARCH_ROWS, r.ctypes.data, r.shape[0]
+        shape = (min(max(nq, 1), SEARCH_MAX_QUERIES), min(max(int(k), 1), SEARCH_MAX_K))   # (a refused call raises below)
+        index, score = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.float32)
+        d = Search(src, int(k), 1 if normalise else 0, nq, rp, index.ctypes.data, score.ctypes.data)
+        _check(lib().vh_search_bank(self.h, C.byref(d)), self.h)
+        return index, score
+
+    def search_device(self, desc):
+        """vh_search_bank_device: desc is a Search whose pointers are device pointers."""
+        _check(lib().vh_search_bank_device(self.h, C.byref(desc)), self.h)
+
+    def search_device_async(self, desc):
+        """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
+        _check(lib().vh_search_bank_device_async(self.h, C.byref(desc)), self.h)
+
     # ---- layer features: several layers of one forward (vithip.h "Layer features") ----
     def set_feature_layers(self, layers):
         """The layers every following forward captures: strictly ascending, each 1 .. layers (k = the residual stream after k
@@ -2628,6 +2693,32 @@ def dense_head_from_dinov2_bnhead(sd, eps=None, dtype=np.float32):
     w = cw * s[None, :]
     b = cw @ (be - mu * s) + (cb if cb is not None else 0.0)
     return w.astype(dtype), b.astype(dtype)
+
+
+def op_search(rows_ptr, nq, width, normalise, bank_ptr, n, dtype, k, workspace_ptr, index_ptr, score_ptr):
+    """The search on its own (vh_op_search): rows [nq, width] fp32 and bank [n, width] of `dtype` -> index [nq, k] int32 and score
+    [nq, k] fp32, in a workspace of op_search_workspace_bytes(nq, n, k) bytes."""
+    _check(lib().vh_op_search(rows_ptr, nq, width, normalise, bank_ptr, n, dtype, k, workspace_ptr, index_ptr, score_ptr, None))
+
+
+def op_search_workspace_bytes(nq, n, k):
+    return int(lib().vh_op_search_workspace_bytes(nq, n, k))
+
+
+def op_search_slabs(nq, n):
+    """The number of bank slabs the search splits n rows into for nq queries."""
+    return int(lib().vh_op_search_slabs(nq, n))
+
+
+def knn_vote(index, score, labels, classes, temperature=0.07):
+    """DINOv2's weighted k-NN vote on a search result: neighbour j of query i votes exp(score[i, j] / temperature) for
+    labels[index[i, j]] (an index of -1 does not vote).  Returns (predicted class [nq], votes [nq, classes] float64)."""
+    index, labels = np.asarray(index), np.asarray(labels)
+    w = np.where(index >= 0, np.exp(np.asarray(score, dtype=np.float64) / temperature), 0.0)
+    votes = np.zeros((index.shape[0], classes), dtype=np.float64)
+    for j in range(index.shape[1]):
+        np.add.at(votes, (np.arange(index.shape[0]), labels[np.maximum(index[:, j], 0)]), w[:, j])
+    return votes.argmax(axis=1), votes
 
 
 def op_rope(qkv_ptr, dtype, batch, tokens, heads, head_dim, lead, hm_rows, cos_ptr, sin_ptr):
