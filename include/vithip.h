@@ -1227,6 +1227,65 @@ int vh_search_bank(vh_ctx* ctx, const vh_search* host);
 int vh_search_bank_device(vh_ctx* ctx, const vh_search* dev);
 int vh_search_bank_device_async(vh_ctx* ctx, const vh_search* dev);
 
+/* ---- Dense correspondence ---------------------------------------------------------------------
+ * What the consumers of DINOv2 / DINOv3 / CLIP patch features run between two images: for every patch of image A the most similar patch
+ * of image B -- keypoint transfer, video object tracking and label propagation, co-segmentation, change detection, most of them
+ * filtered by a mutual nearest-neighbour test (the caller also passes the swapped pair and compares).  One call matches any list of
+ * image pairs of the LAST forward; the [NP][NP] similarities are never written and no patch row leaves the device: a prepare pass makes
+ * the 16-bit operand rows where the forward left the residual stream, the match kernel multiplies on the matrix cores and selects while
+ * the scores are in registers.  A PULL interface like the token features: no forward knows of it, and a call drops no cached graph and
+ * changes no logit.
+ *
+ * ARITHMETIC, for bits.  D = cfg.dim, T16 = the context's operand type (VH_DTYPE_BF16 / VH_DTYPE_FP16).
+ *   x16[b][p]   = RNE_T16(v), v = patch row p of image b exactly as vh_read_features / vh_read_layer_features give it in VH_ELEM_F32
+ *                 (VH_FEAT_RAW or VH_FEAT_NORM; class-token and register rows skipped).  The operand of VH_MATCH_DOT.
+ *   y16[b][p]   = RNE_T16(x16 / n), the operand of VH_MATCH_COSINE: n = sqrtf(S) in fp32 (a correctly rounded root), every quotient a
+ *                 correctly rounded fp32 division, S = the sum of x16^2 over the ROUNDED row in the order of the wave-per-row skeleton
+ *                 (csrc/kernels_rows.hip): lane l of 64 adds its pieces of 8 consecutive elements l, l + 64, .. in that order from +0,
+ *                 each piece as ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)) of the squares, every square and sum rounded to fp32,
+ *                 then the xor butterfly over lane distances 32, 16, .. 1.  S = 0: the row stays zero (every score with it is 0).
+ *   s(i, j)     = sum_k A16[i][k] * B16[j][k]: the products are exact in fp32; the sum starts at +0 and takes k ascending in groups of
+ *                 16, one v_mfma_f32_32x32x16 (gfx950) per group.  It depends on the two rows and D alone: never on npairs, on the
+ *                 pair's place in the list or on the stream.  Where every product and partial sum is an integer below 2^24 it is exact.
+ *   result      idx[p][i] = the first j of 0 .. NP - 1 under (s(i, j) descending, j ascending): TIES GO TO THE LOWER j; score[p][i] =
+ *                 that s in fp32.  The inputs are finite (a row without a finite score reports index 0 and -inf).
+ * A context's result is bit for bit vh_op_match's on those operand rows: for VH_MATCH_DOT on the vh_read_features patch rows rounded to
+ * T16, for VH_MATCH_COSINE on what vh_match_operands returns.
+ *
+ *   vh_match_patches    pairs_host [npairs][2] = (a, b), image indices of the last forward, 0 .. its batch - 1; a == b is legal and an
+ *                       image may appear in any number of pairs; 1 <= npairs <= 4 * max_batch.  idx_host [npairs][NP] int32,
+ *                       score_host [npairs][NP] fp32.  layer: -1 = the final state, or a layer as vh_read_layer_features takes it.
+ *                       Host buffers, synchronous.
+ *   .._device / .._device_async   device buffers (16-byte aligned) on the context's stream; wait / enqueue only.  The pairs are then
+ *                       unknown to the host: a pair that names an image outside the last batch gets index -1 and score -inf in all
+ *                       its rows, and nothing is read for it.
+ *   vh_match_operands   rows16_host [NP][D] of T16 <- the operand rows of one image as the match kernel reads them (desc->npairs is
+ *                       ignored).  For tests and for callers that keep descriptors.  Synchronous.
+ * The operand rows of the whole last batch live in a scratch of max_batch * NP * D 16-bit elements that the FIRST match call allocates
+ * (a context that never matches pays nothing); that call is therefore not legal inside a stream capture, later ones allocate nothing.
+ *
+ * REFUSED, each with a message of its own, before a device is touched, nothing enqueued and no output written.  VH_ERR_INVALID: a null
+ * context, descriptor, pair list or output; norm, metric, layer or npairs out of range; a pair (host list) outside the last batch; a
+ * device pointer that is not 16-byte aligned; D not a multiple of 64 or above 2048.  VH_ERR_UNSUPPORTED: a VH_FLAG_CLS_TAIL context (its
+ * last layer updates the class-token rows only); a VH_DTYPE_FP8 context (no 16-bit operand type).  VH_ERR_STATE: a ring exists on the
+ * context; no forward has run; a layer that was not listed when the last forward was enqueued or that it did not reach.  The calls go
+ * through neither the rings nor the device groups. */
+#define VH_MATCH_COSINE 0
+#define VH_MATCH_DOT 1
+#define VH_MATCH_MAX_ROWS 4096
+#define VH_MATCH_MAX_WIDTH 2048
+#define VH_MATCH_MAX_PAIRS 65536
+typedef struct vh_match_desc { /* sizeof == 16 */
+    int32_t norm;   /* VH_FEAT_NORM or VH_FEAT_RAW */
+    int32_t layer;  /* -1, or a layer as in vh_layer_features */
+    int32_t metric; /* VH_MATCH_COSINE or VH_MATCH_DOT */
+    int32_t npairs; /* 1 .. 4 * max_batch */
+} vh_match_desc;
+int vh_match_patches(vh_ctx* ctx, const vh_match_desc* desc, const int32_t* pairs_host, int32_t* idx_host, float* score_host);
+int vh_match_patches_device(vh_ctx* ctx, const vh_match_desc* desc, const int32_t* pairs_dev, int32_t* idx_dev, float* score_dev);
+int vh_match_patches_device_async(vh_ctx* ctx, const vh_match_desc* desc, const int32_t* pairs_dev, int32_t* idx_dev, float* score_dev);
+int vh_match_operands(vh_ctx* ctx, const vh_match_desc* desc, int image, void* rows16_host);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1569,6 +1628,14 @@ int vh_op_search(const float* rows_f32_dev, int nq, int width, int normalise, co
                  void* workspace_dev, int32_t* index_dev, float* score_dev, void* stream);
 size_t vh_op_search_workspace_bytes(int nq, int64_t n, int k);
 int vh_op_search_slabs(int nq, int64_t n);
+/* The match on its own ("Dense correspondence"): a16_dev [npairs][na][width] and b16_dev [npairs][nb][width] of `dtype` (VH_DTYPE_BF16 /
+ * VH_DTYPE_FP16), the operand rows as they are -> idx_dev [npairs][na] int32, score_dev [npairs][na] fp32: for row i of pair p the first
+ * row j of B under (s(i, j) descending, j ascending).  metric is checked and changes nothing: with VH_MATCH_COSINE the caller hands in
+ * unit rows (vh_match_operands, or its own normalisation).  npairs 1 .. 65536, na and nb 1 .. 4096, width a multiple of 64 in 64 ..
+ * 2048; every pointer 16-byte aligned.  Nothing outside idx / score [npairs][na] is written.  Every argument is checked before a device
+ * is touched, each refusal with a message of its own. */
+int vh_op_match(const void* a16_dev, const void* b16_dev, int dtype, int npairs, int na, int nb, int width, int metric, int32_t* idx_dev,
+                float* score_dev, void* stream);
 /* The rotation of a VH_FLAG_ROPE context on its own ("THE FUNCTION" at VH_FLAG_ROPE), in place on caller-made q|k|v of `dtype`
  * (VH_DTYPE_BF16 / VH_DTYPE_FP16) elements: q and k of rows lead .. tokens - 1 of every image and head are rotated by cos_dev / sin_dev
  * [tokens - lead][head_dim / 2] fp32; v, the lead rows and every row beyond batch * tokens are never written.

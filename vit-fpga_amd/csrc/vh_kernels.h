@@ -381,6 +381,38 @@ SearchPlan search_plan(int nq, int64_t n);
 size_t search_workspace_bytes(int nq, int64_t n, int k);   // 0: an argument is out of range
 const char* search_check(const SearchArgs& a);
 hipError_t launch_search(const SearchArgs& a, hipStream_t stream);
+// Dense correspondence (kernels_match.hip; contract: vithip.h, "Dense correspondence").  launch_match_prep: the patch rows of `batch`
+// images of a residual stream (form == dtype: split planes; VH_FEAT_FORM_F32: fp32 rows in hi) -> out16 [batch][np][dim] of `dtype`,
+// through LayerNorm(gamma, beta, eps) with VH_FEAT_NORM, rounded to nearest even, and with VH_MATCH_COSINE divided by the rounded row's
+// L2 norm and rounded again.  launch_match: idx / score [npairs][na] <- for every row of A the first row of B under (score descending,
+// index ascending).  pairs == nullptr: pair p is image p of a16 [npairs][na][width] and b16 [npairs][nb][width] (images == npairs);
+// otherwise pairs [npairs][2] on the device names images of a16 == b16 [images][na][width] (na == nb).  match_query_rows: the query rows
+// per workgroup the launcher picks (64 or 128).  The *_check functions: nullptr, or why the launch is refused; host arithmetic only.
+// No scratch, no allocation, no counter.
+struct MatchPrepArgs {
+    const void* hi;
+    const void* lo;
+    int form, dtype;
+    int batch, np, tokens, lead, dim;
+    const float* gamma;
+    const float* beta;
+    float eps;
+    int norm, metric;
+    void* out16;
+};
+const char* match_prep_check(const MatchPrepArgs& a);
+hipError_t launch_match_prep(const MatchPrepArgs& a, hipStream_t stream);
+struct MatchArgs {
+    const void* a16;
+    const void* b16;
+    const int32_t* pairs;
+    int images, dtype, npairs, na, nb, width, metric;
+    int32_t* idx;
+    float* score;
+};
+int match_query_rows(int npairs, int na);
+const char* match_check(const MatchArgs& a);
+hipError_t launch_match(const MatchArgs& a, hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln
 hipError_t launch_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim,
                              float scale, void* w8, float* wscale, float* c, float* d, hipStream_t stream);

@@ -437,6 +437,9 @@ struct vh_ctx {
     // Embedding search (vh_set_bank; vithip.h "Embedding search"): the bank as rows of the operand type and the workspace of the widest
     // search the context serves.  Only vh_search_bank touches them: no forward knows.
     void *bank16 = nullptr, *search_ws = nullptr;
+    // Dense correspondence (vh_match_patches; vithip.h "Dense correspondence"): the operand rows of the last batch, [max_batch][NP][D]
+    // of the operand type, allocated by the first match call.  Only the match calls touch it: no forward knows.
+    void* match16 = nullptr;
     int64_t bank_n = 0;
     int bank_w = 0;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
@@ -1766,6 +1769,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->dense_logits) hipFree(c->dense_logits);
     if (c->bank16) hipFree(c->bank16);
     if (c->search_ws) hipFree(c->search_ws);
+    if (c->match16) hipFree(c->match16);
     if (c->w16) hipFree(c->w16);
     if (c->bias_img) hipFree(c->bias_img);
     if (c->subln_wb) hipFree(c->subln_wb);
@@ -3377,6 +3381,122 @@ int vh_search_bank(vh_ctx* c, const vh_search* d) {
     return VH_OK;
 }
 
+// ---- dense correspondence (vithip.h "Dense correspondence"; kernels_match.hip) ------------------------------------------------
+// A pull interface like the token features: the prepare pass reads the rows features_live / slot_view name and writes the operand rows
+// of the whole last batch into c->match16, the match kernel reads them through the pair list; both on the context's main stream.
+// Every refusal comes before a device is touched.  *src: where the layer's rows live.
+static int match_check_call(vh_ctx* c, const vh_match_desc* d, bool need_pairs, const void* pairs, const void* idx, const void* score, bool device,
+                            FeatSource* src) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "match_patches: null context");
+    if (!d) return fail(&c->err, VH_ERR_INVALID, "match_patches: null descriptor");
+    if (!idx || !score) return fail(&c->err, VH_ERR_INVALID, "match_patches: null output (idx and score are both required)");
+    if (d->norm != VH_FEAT_NORM && d->norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "match_patches: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", d->norm);
+    if (d->metric != VH_MATCH_COSINE && d->metric != VH_MATCH_DOT)
+        return fail(&c->err, VH_ERR_INVALID, "match_patches: metric %d is not VH_MATCH_COSINE (0) or VH_MATCH_DOT (1)", d->metric);
+    const int layers = c->cfg.layers;
+    if (d->layer != -1 && (d->layer < 1 || d->layer > layers)) return fail(&c->err, VH_ERR_INVALID, "match_patches: layer %d is not -1 or 1..%d", d->layer, layers);
+    if (need_pairs) {
+        if (!pairs) return fail(&c->err, VH_ERR_INVALID, "match_patches: null pair list");
+        if (d->npairs < 1 || d->npairs > 4 * c->cfg.max_batch)
+            return fail(&c->err, VH_ERR_INVALID, "match_patches: npairs %d is outside 1..%d (4 x max_batch)", d->npairs, 4 * c->cfg.max_batch);
+    }
+    if (device && (((uintptr_t)pairs | (uintptr_t)idx | (uintptr_t)score) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "match_patches: a device pointer is not 16-byte aligned (pairs %p, idx %p, score %p)", pairs, idx, score);
+    if (c->cfg.dim % 64 || c->cfg.dim > VH_MATCH_MAX_WIDTH)
+        return fail(&c->err, VH_ERR_INVALID, "match_patches: dim %d is not a multiple of 64 up to %d", c->cfg.dim, VH_MATCH_MAX_WIDTH);
+    if (c->cfg.flags & VH_FLAG_CLS_TAIL)
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "match_patches: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
+    if (c->fp8) return fail(&c->err, VH_ERR_UNSUPPORTED, "match_patches: a VH_DTYPE_FP8 context has no 16-bit operand type for the rows");
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "match_patches: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
+    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "match_patches: no forward has run");
+    if (d->layer == -1) { *src = features_live(c); return VH_OK; }
+    int slot = -1;
+    for (int i = 0; i < c->cap_n; ++i) if (c->cap_layers[i] == d->layer) slot = i;
+    if (d->layer < layers && slot < 0)
+        return fail(&c->err, VH_ERR_STATE, "match_patches: layer %d was not in the list when the last forward was enqueued (vh_set_feature_layers)", d->layer);
+    if (d->layer > c->cap_nl)
+        return fail(&c->err, VH_ERR_STATE, "match_patches: the last forward ran %d layers and did not reach layer %d (vh_debug_set_layers)", c->cap_nl, d->layer);
+    if (d->layer == c->cap_nl) *src = features_live(c);   // the live residual
+    else *src = FeatSource{slot_view(c, slot, c->cap_form), false};
+    return VH_OK;
+}
+// the operand rows of the last batch -> c->match16 (allocated here, once)
+static int match_prepare(vh_ctx* c, const vh_match_desc& d, const FeatSource& src) {
+    if (!c->match16) {
+        const hipError_t e = hipMalloc(&c->match16, (size_t)c->cfg.max_batch * c->L.NP * c->cfg.dim * 2);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(&c->err, VH_ERR_HIP, "match_patches: no room for the operand rows: %s", hipGetErrorString(e));
+        }
+    }
+    MatchPrepArgs a{};
+    a.hi = src.hi; a.lo = src.lo; a.form = src.form; a.dtype = c->dt16;
+    a.batch = c->last_batch; a.np = c->L.NP; a.tokens = c->L.T; a.lead = c->L.lead; a.dim = c->cfg.dim;
+    a.gamma = c->params + c->L.lnfw; a.beta = c->params + c->L.lnfb; a.eps = c->cfg.ln_eps;
+    a.norm = d.norm; a.metric = d.metric; a.out16 = c->match16;
+    if (const char* why = match_prep_check(a)) return fail(&c->err, VH_ERR_INVALID, "match_patches: %s", why);
+    HIPCHK(&c->err, launch_match_prep(a, c->stream));
+    return VH_OK;
+}
+static int match_enqueue(vh_ctx* c, const vh_match_desc& d, const FeatSource& src, const int32_t* pairs_dev, int32_t* idx_dev, float* score_dev) {
+    if (int rc = match_prepare(c, d, src)) return rc;
+    MatchArgs a{};
+    a.a16 = c->match16; a.b16 = c->match16; a.pairs = pairs_dev; a.images = c->last_batch; a.dtype = c->dt16;
+    a.npairs = d.npairs; a.na = c->L.NP; a.nb = c->L.NP; a.width = c->cfg.dim; a.metric = d.metric; a.idx = idx_dev; a.score = score_dev;
+    if (const char* why = match_check(a)) return fail(&c->err, VH_ERR_INVALID, "match_patches: %s", why);
+    HIPCHK(&c->err, launch_match(a, c->stream));
+    return VH_OK;
+}
+int vh_match_patches_device_async(vh_ctx* c, const vh_match_desc* d, const int32_t* pairs, int32_t* idx, float* score) {
+    FeatSource src{};
+    if (int rc = match_check_call(c, d, true, pairs, idx, score, true, &src)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return match_enqueue(c, *d, src, pairs, idx, score);
+}
+int vh_match_patches_device(vh_ctx* c, const vh_match_desc* d, const int32_t* pairs, int32_t* idx, float* score) {
+    if (int rc = vh_match_patches_device_async(c, d, pairs, idx, score)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+// the host form stages through device memory of the call's own (a synchronous call, outside any captured graph)
+int vh_match_patches(vh_ctx* c, const vh_match_desc* d, const int32_t* pairs, int32_t* idx, float* score) {
+    FeatSource src{};
+    if (int rc = match_check_call(c, d, true, pairs, idx, score, false, &src)) return rc;
+    for (int i = 0; i < 2 * d->npairs; ++i)
+        if (pairs[i] < 0 || pairs[i] >= c->last_batch)
+            return fail(&c->err, VH_ERR_INVALID, "match_patches: pair %d names image %d, outside 0..%d, the last forward's batch", i / 2, pairs[i], c->last_batch - 1);
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t n_out = (size_t)d->npairs * c->L.NP;
+    int32_t *d_pairs = nullptr, *d_idx = nullptr;
+    float* d_score = nullptr;
+    hipError_t e = hipMalloc((void**)&d_pairs, (size_t)d->npairs * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_idx, n_out * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_score, n_out * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pairs, pairs, (size_t)d->npairs * 8, hipMemcpyHostToDevice, c->stream);
+    const int rc = e == hipSuccess ? match_enqueue(c, *d, src, d_pairs, d_idx, d_score) : 0;
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(idx, d_idx, n_out * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(score, d_score, n_out * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_compute(c);
+    hipFree(d_pairs);
+    hipFree(d_idx);
+    hipFree(d_score);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(&c->err, VH_ERR_HIP, "match_patches failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+int vh_match_operands(vh_ctx* c, const vh_match_desc* d, int image, void* rows16) {
+    FeatSource src{};
+    if (int rc = match_check_call(c, d, false, nullptr, rows16, rows16, false, &src)) return rc;
+    if (image < 0 || image >= c->last_batch)
+        return fail(&c->err, VH_ERR_INVALID, "match_patches: image %d is outside 0..%d, the last forward's batch", image, c->last_batch - 1);
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    if (int rc = match_prepare(c, *d, src)) return rc;
+    const size_t n = (size_t)c->L.NP * c->cfg.dim * 2;
+    HIPCHK(&c->err, hipMemcpyAsync(rows16, (const char*)c->match16 + (size_t)image * n, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
@@ -3929,6 +4049,18 @@ int vh_op_search(const float* rows, int nq, int width, int normalise, const void
     hipError_t e = launch_search(a, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "search failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the match on caller-made operand rows ("Dense correspondence")
+int vh_op_match(const void* a16, const void* b16, int dtype, int npairs, int na, int nb, int width, int metric, int32_t* idx, float* score,
+                void* stream) {
+    MatchArgs a{};
+    a.a16 = a16; a.b16 = b16; a.images = npairs; a.dtype = dtype; a.npairs = npairs; a.na = na; a.nb = nb; a.width = width; a.metric = metric;
+    a.idx = idx; a.score = score;
+    if (const char* why = match_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_match(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "match failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 size_t vh_op_search_workspace_bytes(int nq, int64_t n, int k) { return search_workspace_bytes(nq, n, k); }

@@ -160,6 +160,15 @@ class Search(C.Structure):
                 ("index", C.c_void_p), ("score", C.c_void_p)]
 
 
+MATCH_COSINE, MATCH_DOT = 0, 1   # vh_match_desc.metric (VH_MATCH_*)
+
+
+class MatchDesc(C.Structure):
+    """vh_match_desc: norm (FEAT_NORM / FEAT_RAW), layer (-1 = the final state, else a listed layer), metric (MATCH_*), npairs.
+    16 bytes."""
+    _fields_ = [("norm", C.c_int32), ("layer", C.c_int32), ("metric", C.c_int32), ("npairs", C.c_int32)]
+
+
 MAX_ATTENTION_LAYERS = 64
 ATTN_Q_CLS, ATTN_Q_LEAD = 0, 1        # vh_set_attention_layers queries (VH_ATTN_Q_*): the class token's row / every leading row
 ATTN_KEYS_ALL, ATTN_KEYS_PATCH = 0, 1  # vh_attention_maps.keys (VH_ATTN_KEYS_*): all key columns / the patch columns
@@ -391,6 +400,11 @@ SYMBOLS = {
     "vh_op_search": (_i, [_vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "vh_op_search_workspace_bytes": (_sz, [_i, _i64, _i]),
     "vh_op_search_slabs": (_i, [_i, _i64]),
+    "vh_match_patches": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "vh_match_patches_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "vh_match_patches_device_async": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "vh_match_operands": (_i, [_vp, _vp, _i, _vp]),
+    "vh_op_match": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
@@ -2204,6 +2218,36 @@ class VitContext:
         """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
         _check(lib().vh_search_bank_device_async(self.h, C.byref(desc)), self.h)
 
+    # ---- dense correspondence between images of the last forward (vithip.h "Dense correspondence") ----
+    def _match_desc(self, npairs, norm, layer, metric):
+        m = {"cosine": MATCH_COSINE, "dot": MATCH_DOT}.get(metric, metric)
+        return MatchDesc(FEAT_NORM if norm else FEAT_RAW, int(layer), int(m), int(npairs))
+
+    def match_patches(self, pairs, norm=True, layer=-1, metric="cosine"):
+        """(idx [npairs, NP] int32, score [npairs, NP] float32): for every patch of image a of each pair (a, b) of the last forward the
+        most similar patch of image b (ties: the lower index) and its similarity, by the cosine or the inner product ("dot") of the
+        patch rows in the context's operand type.  a == b is legal; pass (b, a) as well for the mutual test (mutual_matches)."""
+        p = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        npatch = self.features_dims()[2]
+        idx = np.empty((max(p.shape[0], 1), npatch), dtype=np.int32)
+        score = np.empty(idx.shape, dtype=np.float32)
+        d = self._match_desc(p.shape[0], norm, layer, metric)
+        _check(lib().vh_match_patches(self.h, C.byref(d), p.ctypes.data, idx.ctypes.data, score.ctypes.data), self.h)
+        return idx, score
+
+    def match_patches_device(self, desc, pairs_ptr, idx_ptr, score_ptr, sync=True):
+        """vh_match_patches_device (sync) / _device_async: desc is a MatchDesc, the pointers are device pointers."""
+        f = lib().vh_match_patches_device if sync else lib().vh_match_patches_device_async
+        _check(f(self.h, C.byref(desc), pairs_ptr, idx_ptr, score_ptr), self.h)
+
+    def match_operands(self, image, norm=True, layer=-1, metric="cosine"):
+        """The operand rows [NP, D] of one image as the match kernel reads them: uint16 holding the bits of the context's operand type."""
+        _, _, npatch, dim = self.features_dims()
+        rows = np.empty((npatch, dim), dtype=np.uint16)
+        d = self._match_desc(0, norm, layer, metric)
+        _check(lib().vh_match_operands(self.h, C.byref(d), int(image), rows.ctypes.data), self.h)
+        return rows
+
     # ---- layer features: several layers of one forward (vithip.h "Layer features") ----
     def set_feature_layers(self, layers):
         """The layers every following forward captures: strictly ascending, each 1 .. layers (k = the residual stream after k
@@ -2708,6 +2752,20 @@ def op_search_workspace_bytes(nq, n, k):
 def op_search_slabs(nq, n):
     """The number of bank slabs the search splits n rows into for nq queries."""
     return int(lib().vh_op_search_slabs(nq, n))
+
+
+def op_match(a_ptr, b_ptr, dtype, npairs, na, nb, width, metric, idx_ptr, score_ptr):
+    """The match on its own (vh_op_match): operand rows a [npairs, na, width] and b [npairs, nb, width] of `dtype` -> idx [npairs, na]
+    int32 (the best row of b for every row of a, ties to the lower index) and score [npairs, na] fp32."""
+    _check(lib().vh_op_match(a_ptr, b_ptr, dtype, npairs, na, nb, width, metric, idx_ptr, score_ptr, None))
+
+
+def mutual_matches(idx_ab, idx_ba):
+    """The mutual-nearest-neighbour mask of two match results: True where patch i of a picks j in b and j picks i back.  idx_ab
+    [..., NPa] and idx_ba [..., NPb] are the idx of the pairs (a, b) and (b, a)."""
+    idx_ab, idx_ba = np.asarray(idx_ab), np.asarray(idx_ba)
+    back = np.take_along_axis(idx_ba, np.maximum(idx_ab, 0), axis=-1)
+    return (idx_ab >= 0) & (back == np.arange(idx_ab.shape[-1]))
 
 
 def knn_vote(index, score, labels, classes, temperature=0.07):
