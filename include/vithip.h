@@ -1286,6 +1286,74 @@ int vh_match_patches_device(vh_ctx* ctx, const vh_match_desc* desc, const int32_
 int vh_match_patches_device_async(vh_ctx* ctx, const vh_match_desc* desc, const int32_t* pairs_dev, int32_t* idx_dev, float* score_dev);
 int vh_match_operands(vh_ctx* ctx, const vh_match_desc* desc, int image, void* rows16_host);
 
+/* ---- Patch clustering -------------------------------------------------------------------------
+ * k-means of the patch rows of an image, the most common operation on DINO / DINOv2 / DINOv3 patch features: unsupervised object and
+ * part segmentation, foreground masks, bag-of-visual-words; with given centroids and no iterations, vector quantisation of the patches
+ * against a codebook.  Every listed image of the LAST forward is clustered ON ITS OWN -- an image's result is a function of its own rows
+ * only -- by one workgroup that stays alive across all iterations; no patch row leaves the device.  A PULL interface like the match: it
+ * reads the operand rows the match's prepare pass makes (vh_match_operands returns them), no forward knows of it, a call drops no cached
+ * graph and changes no logit.
+ *
+ * THE FUNCTION, for bits.  T16 = the operand type; x = the operand rows of the image (VH_KMEANS_COSINE: the unit rows y16 of
+ * VH_MATCH_COSINE; VH_KMEANS_L2: the rounded rows x16 of VH_MATCH_DOT), c = the K centroids, T16 as well; W = the row width.
+ *   init     VH_KMEANS_INIT_STRIDE: c_j = row floor((2 j + 1) NP / (2 K)) of the image.  VH_KMEANS_INIT_GIVEN: c_j = RNE_T16(init[j]),
+ *            [K][W] fp32 of the caller's, shared by all listed images, not renormalised.
+ *   score    COSINE: s(i, j) = sum_w x[i][w] c[j][w], accumulated in fp32 as the match's s (k ascending in groups of 16, one
+ *            v_mfma_f32_32x32x16 per group).  L2: s(i, j) = that sum - h_j, one fp32 subtraction, h_j = 0.5 * sum_w c[j][w]^2 in fp32 in
+ *            the piece order stated for S under "Dense correspondence" (argmax of s = argmin of |x - c|^2).
+ *   label    the first j of 0 .. K - 1 under (s descending, j ascending): TIES GO TO THE LOWER j.
+ *   run      `iters` times { assign; update }, then a FINAL ASSIGN: the returned labels and counts belong to the returned centroids.
+ *            iters = 0 is pure assignment to the initial centroids (the codebook case).  A fixed count, no early stop, no host state.
+ *   update   sum_j = the fp32 sum of the rows with label j, n_j their count.  L2: c_j = RNE_T16(sum_j / (float)n_j), a correctly
+ *            rounded fp32 division.  COSINE: c_j = RNE_T16(sum_j / sqrtf(S_j)), S_j = the sum of sum_j^2 over the UNROUNDED fp32 sums
+ *            in the same piece order (a correctly rounded root and division).  A cluster with n_j = 0, or with S_j = 0, KEEPS its
+ *            centroid.  The sum over rows runs on the matrix cores (a one-hot operand, exact in both types) with the row index
+ *            ascending in groups of 16 from +0; the order is the kernel's own and fixed for a given (NP, W, K).
+ *   outputs  labels [n][NP] int32, counts [n][K] int32, centroids [n][K][W]: the T16 centroid widened to fp32 (it can be fed back as
+ *            init without loss).
+ * The result is EXACT -- equal to the function above in real arithmetic followed by the stated roundings -- whenever every partial
+ * sum is exactly representable in fp32 (integer data below 2^24, say); otherwise every fp32 sum carries the usual bound of a sum of
+ * that length in the stated order, and a label may differ from an exact evaluation's where two scores are closer than that bound.
+ * The run is deterministic.
+ *
+ *   vh_cluster_patches   images_host [nimages] = indices into the last forward's batch, repeats legal, 1 <= nimages <= 4 * max_batch;
+ *                        init_host [K][D] fp32 (VH_KMEANS_INIT_GIVEN) or NULL (VH_KMEANS_INIT_STRIDE); labels_host [n][NP] int32;
+ *                        centroids_host [n][K][D] fp32 or NULL; counts_host [n][K] int32 or NULL.  Host buffers, synchronous.
+ *   .._device / .._device_async   the same with device pointers (16-byte aligned) on the context's stream; wait / enqueue only.  An
+ *                        image index outside the last batch (unknown to the host): labels -1, counts 0, its centroids unspecified.
+ * The context form reuses the match's operand scratch (allocated by the first match or cluster call) and keeps a 16-bit centroid
+ * scratch of its own, nimages * K * D elements plus the rounded init, which grows when a call needs more than any call before it: such
+ * a call allocates and is not legal inside a stream capture; every other call allocates nothing.  A context that never clusters pays
+ * nothing.
+ *
+ * REFUSED, each with a message of its own, before a device is touched: a null context, descriptor, image list or labels; norm, layer,
+ * metric, k (2 .. 64, <= NP), iters (0 .. 64), init or nimages out of range; init and init_host that do not agree; a listed image
+ * (host list) outside the last batch; a device pointer that is not 16-byte aligned; NP above 4096 or D not a multiple of 64 up to 2048;
+ * and everything the match refuses a context for (VH_FLAG_CLS_TAIL, VH_DTYPE_FP8, a ring, no forward, a layer not captured), under
+ * this call's name.  Joint clustering across images is out of range. */
+#define VH_KMEANS_COSINE 0      /* spherical k-means on the unit rows (the VH_MATCH_COSINE operand) */
+#define VH_KMEANS_L2 1          /* Lloyd's k-means on the rounded rows (the VH_MATCH_DOT operand)   */
+#define VH_KMEANS_INIT_STRIDE 0 /* centroid j = operand row of patch floor((2j+1)*NP / (2K)) of the image */
+#define VH_KMEANS_INIT_GIVEN 1  /* init [K][W] fp32 of the caller's, shared by all listed images, RNE to T16, not renormalised */
+#define VH_KMEANS_MAX_K 64
+#define VH_KMEANS_MAX_ITERS 64
+typedef struct vh_kmeans_desc { /* sizeof == 32 */
+    int32_t norm;     /* VH_FEAT_NORM or VH_FEAT_RAW */
+    int32_t layer;    /* -1, or a layer as in vh_layer_features */
+    int32_t metric;   /* VH_KMEANS_COSINE or VH_KMEANS_L2 */
+    int32_t k;        /* 2 .. 64, <= NP */
+    int32_t iters;    /* 0 .. 64 */
+    int32_t init;     /* VH_KMEANS_INIT_STRIDE or VH_KMEANS_INIT_GIVEN */
+    int32_t nimages;  /* 1 .. 4 * max_batch */
+    int32_t reserved; /* 0 */
+} vh_kmeans_desc;
+int vh_cluster_patches(vh_ctx* ctx, const vh_kmeans_desc* desc, const int32_t* images_host, const float* init_host, int32_t* labels_host,
+                       float* centroids_host, int32_t* counts_host);
+int vh_cluster_patches_device(vh_ctx* ctx, const vh_kmeans_desc* desc, const int32_t* images_dev, const float* init_dev, int32_t* labels_dev,
+                              float* centroids_dev, int32_t* counts_dev);
+int vh_cluster_patches_device_async(vh_ctx* ctx, const vh_kmeans_desc* desc, const int32_t* images_dev, const float* init_dev,
+                                    int32_t* labels_dev, float* centroids_dev, int32_t* counts_dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1636,6 +1704,14 @@ int vh_op_search_slabs(int nq, int64_t n);
  * is touched, each refusal with a message of its own. */
 int vh_op_match(const void* a16_dev, const void* b16_dev, int dtype, int npairs, int na, int nb, int width, int metric, int32_t* idx_dev,
                 float* score_dev, void* stream);
+/* The clustering on its own ("Patch clustering"): x16_dev [n][np][width] of `dtype` (VH_DTYPE_BF16 / VH_DTYPE_FP16), image i clustered on
+ * its own into k clusters by `iters` rounds of { assign; update } and a final assign.  init16_dev [k][width] of `dtype`, shared by all
+ * images, or NULL = the stride init.  labels_dev [n][np] int32; cent16_dev [n][k][width] of `dtype` is the working state AND the result
+ * (no workspace); counts_dev [n][k] int32 or NULL.  With VH_KMEANS_COSINE the caller hands in unit rows.  k 2 .. 64 and k <= np, iters
+ * 0 .. 64, np 1 .. 4096, width a multiple of 64 in 64 .. 2048, n 1 .. 65536; every pointer 16-byte aligned.  Nothing outside the three
+ * outputs is written.  Every argument is checked before a device is touched, each refusal with a message of its own. */
+int vh_op_kmeans(const void* x16_dev, int dtype, int n, int np, int width, int k, int iters, int metric, const void* init16_dev,
+                 int32_t* labels_dev, void* cent16_dev, int32_t* counts_dev, void* stream);
 /* The rotation of a VH_FLAG_ROPE context on its own ("THE FUNCTION" at VH_FLAG_ROPE), in place on caller-made q|k|v of `dtype`
  * (VH_DTYPE_BF16 / VH_DTYPE_FP16) elements: q and k of rows lead .. tokens - 1 of every image and head are rotated by cos_dev / sin_dev
  * [tokens - lead][head_dim / 2] fp32; v, the lead rows and every row beyond batch * tokens are never written.

@@ -413,6 +413,25 @@ struct MatchArgs {
 int match_query_rows(int npairs, int na);
 const char* match_check(const MatchArgs& a);
 hipError_t launch_match(const MatchArgs& a, hipStream_t stream);
+// Patch clustering (kernels_kmeans.hip; contract: vithip.h, "Patch clustering").  launch_kmeans: k-means of the rows of every listed
+// image on its own, one workgroup per image: labels [n][np], cent16 [n][k][width] of `dtype` (working state and result), counts [n][k]
+// or nullptr.  images == nullptr: image i of x16 [n][np][width]; otherwise images [n] on the device names images of x16 [nimg][np][width]
+// (an index outside 0 .. nimg - 1: labels -1, counts 0, centroids untouched, nothing read).  init16 [k][width] of `dtype` shared by all
+// images, or nullptr = the stride init.  launch_kmeans_round / _widen: n elements (a multiple of 4) fp32 -> `dtype` (RNE) and back.
+// kmeans_check: nullptr, or why the launch is refused; host arithmetic only.  No scratch, no allocation, no counter.
+struct KmeansArgs {
+    const void* x16;
+    const int32_t* images;
+    int nimg, dtype, n, np, width, k, iters, metric;
+    const void* init16;
+    int32_t* labels;
+    void* cent16;
+    int32_t* counts;
+};
+const char* kmeans_check(const KmeansArgs& a);
+hipError_t launch_kmeans(const KmeansArgs& a, hipStream_t stream);
+hipError_t launch_kmeans_round(const float* in, void* out16, int dtype, int64_t n, hipStream_t stream);
+hipError_t launch_kmeans_widen(const void* in16, float* out, int dtype, int64_t n, hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln
 hipError_t launch_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim,
                              float scale, void* w8, float* wscale, float* c, float* d, hipStream_t stream);

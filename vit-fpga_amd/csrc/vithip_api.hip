@@ -440,6 +440,10 @@ struct vh_ctx {
     // Dense correspondence (vh_match_patches; vithip.h "Dense correspondence"): the operand rows of the last batch, [max_batch][NP][D]
     // of the operand type, allocated by the first match call.  Only the match calls touch it: no forward knows.
     void* match16 = nullptr;
+    // Patch clustering (vh_cluster_patches; vithip.h "Patch clustering"): the rounded init [64][D], then the centroids [nimages][K][D],
+    // of the operand type; grows when a call needs more than any call before it.  Only the cluster calls touch it.
+    void* kmeans16 = nullptr;
+    size_t kmeans16_bytes = 0;
     int64_t bank_n = 0;
     int bank_w = 0;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
@@ -1770,6 +1774,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->bank16) hipFree(c->bank16);
     if (c->search_ws) hipFree(c->search_ws);
     if (c->match16) hipFree(c->match16);
+    if (c->kmeans16) hipFree(c->kmeans16);
     if (c->w16) hipFree(c->w16);
     if (c->bias_img) hipFree(c->bias_img);
     if (c->subln_wb) hipFree(c->subln_wb);
@@ -3386,47 +3391,47 @@ int vh_search_bank(vh_ctx* c, const vh_search* d) {
 // of the whole last batch into c->match16, the match kernel reads them through the pair list; both on the context's main stream.
 // Every refusal comes before a device is touched.  *src: where the layer's rows live.
 static int match_check_call(vh_ctx* c, const vh_match_desc* d, bool need_pairs, const void* pairs, const void* idx, const void* score, bool device,
-                            FeatSource* src) {
-    if (!c) return fail(nullptr, VH_ERR_INVALID, "match_patches: null context");
-    if (!d) return fail(&c->err, VH_ERR_INVALID, "match_patches: null descriptor");
-    if (!idx || !score) return fail(&c->err, VH_ERR_INVALID, "match_patches: null output (idx and score are both required)");
-    if (d->norm != VH_FEAT_NORM && d->norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "match_patches: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", d->norm);
+                            FeatSource* src, const char* who = "match_patches") {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "%s: null context", who);
+    if (!d) return fail(&c->err, VH_ERR_INVALID, "%s: null descriptor", who);
+    if (!idx || !score) return fail(&c->err, VH_ERR_INVALID, "%s: null output (idx and score are both required)", who);
+    if (d->norm != VH_FEAT_NORM && d->norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "%s: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", who, d->norm);
     if (d->metric != VH_MATCH_COSINE && d->metric != VH_MATCH_DOT)
-        return fail(&c->err, VH_ERR_INVALID, "match_patches: metric %d is not VH_MATCH_COSINE (0) or VH_MATCH_DOT (1)", d->metric);
+        return fail(&c->err, VH_ERR_INVALID, "%s: metric %d is not VH_MATCH_COSINE (0) or VH_MATCH_DOT (1)", who, d->metric);
     const int layers = c->cfg.layers;
-    if (d->layer != -1 && (d->layer < 1 || d->layer > layers)) return fail(&c->err, VH_ERR_INVALID, "match_patches: layer %d is not -1 or 1..%d", d->layer, layers);
+    if (d->layer != -1 && (d->layer < 1 || d->layer > layers)) return fail(&c->err, VH_ERR_INVALID, "%s: layer %d is not -1 or 1..%d", who, d->layer, layers);
     if (need_pairs) {
-        if (!pairs) return fail(&c->err, VH_ERR_INVALID, "match_patches: null pair list");
+        if (!pairs) return fail(&c->err, VH_ERR_INVALID, "%s: null pair list", who);
         if (d->npairs < 1 || d->npairs > 4 * c->cfg.max_batch)
-            return fail(&c->err, VH_ERR_INVALID, "match_patches: npairs %d is outside 1..%d (4 x max_batch)", d->npairs, 4 * c->cfg.max_batch);
+            return fail(&c->err, VH_ERR_INVALID, "%s: npairs %d is outside 1..%d (4 x max_batch)", who, d->npairs, 4 * c->cfg.max_batch);
     }
     if (device && (((uintptr_t)pairs | (uintptr_t)idx | (uintptr_t)score) & 15))
-        return fail(&c->err, VH_ERR_INVALID, "match_patches: a device pointer is not 16-byte aligned (pairs %p, idx %p, score %p)", pairs, idx, score);
+        return fail(&c->err, VH_ERR_INVALID, "%s: a device pointer is not 16-byte aligned (pairs %p, idx %p, score %p)", who, pairs, idx, score);
     if (c->cfg.dim % 64 || c->cfg.dim > VH_MATCH_MAX_WIDTH)
-        return fail(&c->err, VH_ERR_INVALID, "match_patches: dim %d is not a multiple of 64 up to %d", c->cfg.dim, VH_MATCH_MAX_WIDTH);
+        return fail(&c->err, VH_ERR_INVALID, "%s: dim %d is not a multiple of 64 up to %d", who, c->cfg.dim, VH_MATCH_MAX_WIDTH);
     if (c->cfg.flags & VH_FLAG_CLS_TAIL)
-        return fail(&c->err, VH_ERR_UNSUPPORTED, "match_patches: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only");
-    if (c->fp8) return fail(&c->err, VH_ERR_UNSUPPORTED, "match_patches: a VH_DTYPE_FP8 context has no 16-bit operand type for the rows");
-    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "match_patches: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
-    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "match_patches: no forward has run");
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "%s: a VH_FLAG_CLS_TAIL context's last layer updates the class-token rows only", who);
+    if (c->fp8) return fail(&c->err, VH_ERR_UNSUPPORTED, "%s: a VH_DTYPE_FP8 context has no 16-bit operand type for the rows", who);
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "%s: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first", who);
+    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "%s: no forward has run", who);
     if (d->layer == -1) { *src = features_live(c); return VH_OK; }
     int slot = -1;
     for (int i = 0; i < c->cap_n; ++i) if (c->cap_layers[i] == d->layer) slot = i;
     if (d->layer < layers && slot < 0)
-        return fail(&c->err, VH_ERR_STATE, "match_patches: layer %d was not in the list when the last forward was enqueued (vh_set_feature_layers)", d->layer);
+        return fail(&c->err, VH_ERR_STATE, "%s: layer %d was not in the list when the last forward was enqueued (vh_set_feature_layers)", who, d->layer);
     if (d->layer > c->cap_nl)
-        return fail(&c->err, VH_ERR_STATE, "match_patches: the last forward ran %d layers and did not reach layer %d (vh_debug_set_layers)", c->cap_nl, d->layer);
+        return fail(&c->err, VH_ERR_STATE, "%s: the last forward ran %d layers and did not reach layer %d (vh_debug_set_layers)", who, c->cap_nl, d->layer);
     if (d->layer == c->cap_nl) *src = features_live(c);   // the live residual
     else *src = FeatSource{slot_view(c, slot, c->cap_form), false};
     return VH_OK;
 }
 // the operand rows of the last batch -> c->match16 (allocated here, once)
-static int match_prepare(vh_ctx* c, const vh_match_desc& d, const FeatSource& src) {
+static int match_prepare(vh_ctx* c, const vh_match_desc& d, const FeatSource& src, const char* who = "match_patches") {
     if (!c->match16) {
         const hipError_t e = hipMalloc(&c->match16, (size_t)c->cfg.max_batch * c->L.NP * c->cfg.dim * 2);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            return fail(&c->err, VH_ERR_HIP, "match_patches: no room for the operand rows: %s", hipGetErrorString(e));
+            return fail(&c->err, VH_ERR_HIP, "%s: no room for the operand rows: %s", who, hipGetErrorString(e));
         }
     }
     MatchPrepArgs a{};
@@ -3434,7 +3439,7 @@ static int match_prepare(vh_ctx* c, const vh_match_desc& d, const FeatSource& sr
     a.batch = c->last_batch; a.np = c->L.NP; a.tokens = c->L.T; a.lead = c->L.lead; a.dim = c->cfg.dim;
     a.gamma = c->params + c->L.lnfw; a.beta = c->params + c->L.lnfb; a.eps = c->cfg.ln_eps;
     a.norm = d.norm; a.metric = d.metric; a.out16 = c->match16;
-    if (const char* why = match_prep_check(a)) return fail(&c->err, VH_ERR_INVALID, "match_patches: %s", why);
+    if (const char* why = match_prep_check(a)) return fail(&c->err, VH_ERR_INVALID, "%s: %s", who, why);
     HIPCHK(&c->err, launch_match_prep(a, c->stream));
     return VH_OK;
 }
@@ -3494,6 +3499,118 @@ int vh_match_operands(vh_ctx* c, const vh_match_desc* d, int image, void* rows16
     const size_t n = (size_t)c->L.NP * c->cfg.dim * 2;
     HIPCHK(&c->err, hipMemcpyAsync(rows16, (const char*)c->match16 + (size_t)image * n, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+
+// ---- patch clustering (vithip.h "Patch clustering"; kernels_kmeans.hip) ----------------------------------------------------------
+// A pull interface on top of the match's: match_prepare makes the operand rows of the last batch, the rounding pass makes the given
+// init, kmeans_kernel clusters the listed images in c->kmeans16, the widening pass returns the centroids; all on the main stream.
+// The descriptor's own fields are refused here; what the match refuses a context for is refused by match_check_call, under this call's name.
+static int cluster_check_call(vh_ctx* c, const vh_kmeans_desc* d, const void* images, const void* init, const void* labels, const void* cents,
+                              const void* counts, bool device, vh_match_desc* md, FeatSource* src) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "cluster_patches: null context");
+    if (!d) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: null descriptor");
+    if (!images) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: null image list");
+    if (!labels) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: null labels (centroids and counts may be null)");
+    if (d->norm != VH_FEAT_NORM && d->norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", d->norm);
+    if (d->metric != VH_KMEANS_COSINE && d->metric != VH_KMEANS_L2)
+        return fail(&c->err, VH_ERR_INVALID, "cluster_patches: metric %d is not VH_KMEANS_COSINE (0) or VH_KMEANS_L2 (1)", d->metric);
+    if (d->layer != -1 && (d->layer < 1 || d->layer > c->cfg.layers)) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: layer %d is not -1 or 1..%d", d->layer, c->cfg.layers);
+    if (d->k < 2 || d->k > VH_KMEANS_MAX_K) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: k %d is outside 2..%d", d->k, VH_KMEANS_MAX_K);
+    if (d->k > c->L.NP) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: k %d exceeds the %d patches of an image", d->k, c->L.NP);
+    if (d->iters < 0 || d->iters > VH_KMEANS_MAX_ITERS) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: iters %d is outside 0..%d", d->iters, VH_KMEANS_MAX_ITERS);
+    if (d->init != VH_KMEANS_INIT_STRIDE && d->init != VH_KMEANS_INIT_GIVEN)
+        return fail(&c->err, VH_ERR_INVALID, "cluster_patches: init %d is not VH_KMEANS_INIT_STRIDE (0) or VH_KMEANS_INIT_GIVEN (1)", d->init);
+    if ((d->init == VH_KMEANS_INIT_GIVEN) != (init != nullptr))
+        return fail(&c->err, VH_ERR_INVALID, "cluster_patches: VH_KMEANS_INIT_GIVEN, and only it, takes an init");
+    if (d->nimages < 1 || d->nimages > 4 * c->cfg.max_batch)
+        return fail(&c->err, VH_ERR_INVALID, "cluster_patches: nimages %d is outside 1..%d (4 x max_batch)", d->nimages, 4 * c->cfg.max_batch);
+    if (d->reserved) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: reserved is not 0");
+    if (device && (((uintptr_t)images | (uintptr_t)init | (uintptr_t)labels | (uintptr_t)cents | (uintptr_t)counts) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "cluster_patches: a device pointer is not 16-byte aligned");
+    *md = vh_match_desc{d->norm, d->layer, d->metric == VH_KMEANS_COSINE ? VH_MATCH_COSINE : VH_MATCH_DOT, 1};
+    if (int rc = match_check_call(c, md, false, nullptr, labels, labels, false, src, "cluster_patches")) return rc;
+    // the launch's own bounds (NP above 4096, say) with stand-ins for the pointers, which are checked above: no device is touched yet
+    KmeansArgs a{};
+    a.x16 = a.labels = (int32_t*)16; a.cent16 = (void*)16; a.dtype = c->dt16; a.n = a.nimg = d->nimages; a.np = c->L.NP; a.width = c->cfg.dim;
+    a.k = d->k; a.iters = d->iters; a.metric = d->metric;
+    if (const char* why = kmeans_check(a)) return fail(&c->err, VH_ERR_INVALID, "cluster_patches: %s", why);
+    return VH_OK;
+}
+static int cluster_enqueue(vh_ctx* c, const vh_kmeans_desc& d, const vh_match_desc& md, const FeatSource& src, const int32_t* images_dev,
+                           const float* init_dev, int32_t* labels_dev, float* cents_dev, int32_t* counts_dev) {
+    KmeansArgs a{};
+    a.images = images_dev; a.nimg = c->last_batch; a.dtype = c->dt16; a.n = d.nimages; a.np = c->L.NP; a.width = c->cfg.dim;
+    a.k = d.k; a.iters = d.iters; a.metric = d.metric; a.labels = labels_dev; a.counts = counts_dev;
+    const size_t row = (size_t)c->cfg.dim * 2, init_bytes = VH_KMEANS_MAX_K * row;
+    const size_t need = init_bytes + (size_t)d.nimages * d.k * row;
+    if (c->kmeans16_bytes < need) {
+        if (c->kmeans16) hipFree(c->kmeans16);
+        c->kmeans16 = nullptr;
+        c->kmeans16_bytes = 0;
+        const hipError_t e = hipMalloc(&c->kmeans16, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(&c->err, VH_ERR_HIP, "cluster_patches: no room for the centroids: %s", hipGetErrorString(e));
+        }
+        c->kmeans16_bytes = need;
+    }
+    if (int rc = match_prepare(c, md, src, "cluster_patches")) return rc;
+    void* const cent16 = (char*)c->kmeans16 + init_bytes;
+    const int64_t ncent = (int64_t)d.nimages * d.k * c->cfg.dim;
+    if (init_dev) HIPCHK(&c->err, launch_kmeans_round(init_dev, c->kmeans16, c->dt16, (int64_t)d.k * c->cfg.dim, c->stream));
+    a.x16 = c->match16; a.init16 = init_dev ? c->kmeans16 : nullptr; a.cent16 = cent16;
+    HIPCHK(&c->err, launch_kmeans(a, c->stream));
+    if (cents_dev) HIPCHK(&c->err, launch_kmeans_widen(cent16, cents_dev, c->dt16, ncent, c->stream));
+    return VH_OK;
+}
+int vh_cluster_patches_device_async(vh_ctx* c, const vh_kmeans_desc* d, const int32_t* images, const float* init, int32_t* labels, float* cents,
+                                    int32_t* counts) {
+    FeatSource src{};
+    vh_match_desc md{};
+    if (int rc = cluster_check_call(c, d, images, init, labels, cents, counts, true, &md, &src)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return cluster_enqueue(c, *d, md, src, images, init, labels, cents, counts);
+}
+int vh_cluster_patches_device(vh_ctx* c, const vh_kmeans_desc* d, const int32_t* images, const float* init, int32_t* labels, float* cents,
+                              int32_t* counts) {
+    if (int rc = vh_cluster_patches_device_async(c, d, images, init, labels, cents, counts)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+// the host form stages through device memory of the call's own (a synchronous call, outside any captured graph)
+int vh_cluster_patches(vh_ctx* c, const vh_kmeans_desc* d, const int32_t* images, const float* init, int32_t* labels, float* cents,
+                       int32_t* counts) {
+    FeatSource src{};
+    vh_match_desc md{};
+    if (int rc = cluster_check_call(c, d, images, init, labels, cents, counts, false, &md, &src)) return rc;
+    for (int i = 0; i < d->nimages; ++i)
+        if (images[i] < 0 || images[i] >= c->last_batch)
+            return fail(&c->err, VH_ERR_INVALID, "cluster_patches: entry %d names image %d, outside 0..%d, the last forward's batch", i, images[i], c->last_batch - 1);
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t n_img = (size_t)d->nimages * 4, n_lab = (size_t)d->nimages * c->L.NP * 4, n_cnt = (size_t)d->nimages * d->k * 4;
+    const size_t n_init = (size_t)d->k * c->cfg.dim * 4, n_cent = (size_t)d->nimages * n_init;
+    int32_t *d_img = nullptr, *d_lab = nullptr, *d_cnt = nullptr;
+    float *d_init = nullptr, *d_cent = nullptr;
+    hipError_t e = hipMalloc((void**)&d_img, n_img);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_lab, n_lab);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_cnt, n_cnt);
+    if (e == hipSuccess && init) e = hipMalloc((void**)&d_init, n_init);
+    if (e == hipSuccess && cents) e = hipMalloc((void**)&d_cent, n_cent);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_img, images, n_img, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && init) e = hipMemcpyAsync(d_init, init, n_init, hipMemcpyHostToDevice, c->stream);
+    const int rc = e == hipSuccess ? cluster_enqueue(c, *d, md, src, d_img, d_init, d_lab, d_cent, d_cnt) : 0;
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(labels, d_lab, n_lab, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !rc && counts) e = hipMemcpyAsync(counts, d_cnt, n_cnt, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !rc && cents) e = hipMemcpyAsync(cents, d_cent, n_cent, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_compute(c);
+    hipFree(d_img);
+    hipFree(d_lab);
+    hipFree(d_cnt);
+    hipFree(d_init);
+    hipFree(d_cent);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(&c->err, VH_ERR_HIP, "cluster_patches failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 
@@ -4061,6 +4178,18 @@ int vh_op_match(const void* a16, const void* b16, int dtype, int npairs, int na,
     hipError_t e = launch_match(a, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "match failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the clustering on caller-made operand rows ("Patch clustering")
+int vh_op_kmeans(const void* x16, int dtype, int n, int np, int width, int k, int iters, int metric, const void* init16, int32_t* labels,
+                 void* cent16, int32_t* counts, void* stream) {
+    KmeansArgs a{};
+    a.x16 = x16; a.dtype = dtype; a.n = n; a.nimg = n; a.np = np; a.width = width; a.k = k; a.iters = iters; a.metric = metric; a.init16 = init16;
+    a.labels = labels; a.cent16 = cent16; a.counts = counts;
+    if (const char* why = kmeans_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_kmeans(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "kmeans failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 size_t vh_op_search_workspace_bytes(int nq, int64_t n, int k) { return search_workspace_bytes(nq, n, k); }

@@ -169,6 +169,17 @@ class MatchDesc(C.Structure):
     _fields_ = [("norm", C.c_int32), ("layer", C.c_int32), ("metric", C.c_int32), ("npairs", C.c_int32)]
 
 
+KMEANS_COSINE, KMEANS_L2 = 0, 1               # vh_kmeans_desc.metric (VH_KMEANS_*)
+KMEANS_INIT_STRIDE, KMEANS_INIT_GIVEN = 0, 1   # vh_kmeans_desc.init
+KMEANS_MAX_K, KMEANS_MAX_ITERS = 64, 64
+
+
+class KmeansDesc(C.Structure):
+    """vh_kmeans_desc: norm, layer (as MatchDesc), metric (KMEANS_*), k, iters, init (KMEANS_INIT_*), nimages, reserved 0.  32 bytes."""
+    _fields_ = [("norm", C.c_int32), ("layer", C.c_int32), ("metric", C.c_int32), ("k", C.c_int32), ("iters", C.c_int32),
+                ("init", C.c_int32), ("nimages", C.c_int32), ("reserved", C.c_int32)]
+
+
 MAX_ATTENTION_LAYERS = 64
 ATTN_Q_CLS, ATTN_Q_LEAD = 0, 1        # vh_set_attention_layers queries (VH_ATTN_Q_*): the class token's row / every leading row
 ATTN_KEYS_ALL, ATTN_KEYS_PATCH = 0, 1  # vh_attention_maps.keys (VH_ATTN_KEYS_*): all key columns / the patch columns
@@ -405,6 +416,10 @@ SYMBOLS = {
     "vh_match_patches_device_async": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "vh_match_operands": (_i, [_vp, _vp, _i, _vp]),
     "vh_op_match": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vh_cluster_patches": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_cluster_patches_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_cluster_patches_device_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_op_kmeans": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
@@ -2248,6 +2263,36 @@ class VitContext:
         _check(lib().vh_match_operands(self.h, C.byref(d), int(image), rows.ctypes.data), self.h)
         return rows
 
+    # ---- k-means of the patch rows of images of the last forward (vithip.h "Patch clustering") ----
+    def cluster_patches(self, images, k, iters=10, metric="cosine", layer=-1, norm=True, init=None, return_centroids=False):
+        """labels [n, gh, gw] int32 ([n, NP] where the patches form no square grid): every listed image of the last forward clustered
+        on its own into k clusters by `iters` rounds of k-means and a final assignment, spherical ("cosine") or Lloyd's ("l2").
+        init: None = the stride init, or [k, D] float32 centroids shared by all images (iters=0: vector quantisation against a
+        codebook).  return_centroids: also (centroids [n, k, D] float32, counts [n, k] int32)."""
+        img = np.ascontiguousarray(images, dtype=np.int32).reshape(-1)
+        _, _, npatch, dim = self.features_dims()
+        m = {"cosine": KMEANS_COSINE, "l2": KMEANS_L2}.get(metric, metric)
+        ini = None if init is None else np.ascontiguousarray(init, dtype=np.float32)
+        if ini is not None and ini.shape != (int(k), dim):
+            raise ValueError(f"init must be [k, D] = [{int(k)}, {dim}], got {list(ini.shape)}")
+        n = max(img.size, 1)
+        labels = np.empty((n, npatch), dtype=np.int32)
+        cents = np.empty((n, max(int(k), 1), dim), dtype=np.float32) if return_centroids else None
+        counts = np.empty((n, max(int(k), 1)), dtype=np.int32) if return_centroids else None
+        d = KmeansDesc(FEAT_NORM if norm else FEAT_RAW, int(layer), int(m), int(k), int(iters),
+                       KMEANS_INIT_STRIDE if ini is None else KMEANS_INIT_GIVEN, img.size, 0)
+        _check(lib().vh_cluster_patches(self.h, C.byref(d), img.ctypes.data, None if ini is None else ini.ctypes.data, labels.ctypes.data,
+                                        None if cents is None else cents.ctypes.data, None if counts is None else counts.ctypes.data), self.h)
+        g = int(round(npatch ** 0.5))
+        if g * g == npatch:
+            labels = labels.reshape(n, g, g)
+        return (labels, cents, counts) if return_centroids else labels
+
+    def cluster_patches_device(self, desc, images_ptr, init_ptr, labels_ptr, centroids_ptr, counts_ptr, sync=True):
+        """vh_cluster_patches_device (sync) / _device_async: desc is a KmeansDesc, the pointers are device pointers (or None)."""
+        f = lib().vh_cluster_patches_device if sync else lib().vh_cluster_patches_device_async
+        _check(f(self.h, C.byref(desc), images_ptr, init_ptr, labels_ptr, centroids_ptr, counts_ptr), self.h)
+
     # ---- layer features: several layers of one forward (vithip.h "Layer features") ----
     def set_feature_layers(self, layers):
         """The layers every following forward captures: strictly ascending, each 1 .. layers (k = the residual stream after k
@@ -2758,6 +2803,18 @@ def op_match(a_ptr, b_ptr, dtype, npairs, na, nb, width, metric, idx_ptr, score_
     """The match on its own (vh_op_match): operand rows a [npairs, na, width] and b [npairs, nb, width] of `dtype` -> idx [npairs, na]
     int32 (the best row of b for every row of a, ties to the lower index) and score [npairs, na] fp32."""
     _check(lib().vh_op_match(a_ptr, b_ptr, dtype, npairs, na, nb, width, metric, idx_ptr, score_ptr, None))
+
+
+def op_kmeans(x_ptr, dtype, n, np_rows, width, k, iters, metric, init_ptr, labels_ptr, cent_ptr, counts_ptr):
+    """The clustering on its own (vh_op_kmeans): operand rows x [n, np_rows, width] of `dtype`, init [k, width] of `dtype` or None (the
+    stride init) -> labels [n, np_rows] int32, centroids [n, k, width] of `dtype` (working state and result), counts [n, k] int32."""
+    _check(lib().vh_op_kmeans(x_ptr, dtype, n, np_rows, width, k, iters, metric, init_ptr, labels_ptr, cent_ptr, counts_ptr, None))
+
+
+def segment_masks(labels, k):
+    """One-hot masks [..., k, gh, gw] bool of a cluster_patches result [..., gh, gw] (a label of -1 is in no mask)."""
+    labels = np.asarray(labels)
+    return np.moveaxis(labels[..., None] == np.arange(int(k)), -1, -3)
 
 
 def mutual_matches(idx_ab, idx_ba):
