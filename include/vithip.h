@@ -1354,6 +1354,68 @@ int vh_cluster_patches_device(vh_ctx* ctx, const vh_kmeans_desc* desc, const int
 int vh_cluster_patches_device_async(vh_ctx* ctx, const vh_kmeans_desc* desc, const int32_t* images_dev, const float* init_dev,
                                     int32_t* labels_dev, float* centroids_dev, int32_t* counts_dev);
 
+/* ---- Feature moments --------------------------------------------------------------------------
+ * Second-order statistics of the patch rows of a set of images: the column sums and the second-moment matrix X^T X.  They are what the
+ * PCA-to-RGB visualisation and the first-component foreground mask of DINOv2 are made of (jointly over several images), what PCA
+ * whitening and dimension reduction of descriptors need before retrieval (the result feeds vh_set_bank), the feature mean and
+ * covariance of Frechet distances over many forwards, and the X^T X of closed-form ridge probes.  The heavy part -- a symmetric rank-R
+ * update with the ROW index contracted -- runs on the matrix cores and no patch row leaves the device; everything behind it (centring,
+ * the eigen-solve, the projection as a dense head: weight V [m][W], bias -V mu, vh_set_dense_head) is small.  A PULL interface like the
+ * match: it reads the operand rows the match's prepare pass makes, no forward knows of it, a call drops no cached graph and changes no
+ * logit.
+ *
+ * THE FUNCTION, for bits.  T16 = the operand type; W = the row width; x[r][w] = the operand rows of VH_MATCH_DOT (the patch rows rounded
+ * to T16, exactly what vh_match_operands(.., metric = VH_MATCH_DOT) returns) of the listed images in list order, R = (listed images
+ * inside the last batch) * NP rows.
+ *   sum[w]      = sum_r x[r][w] in fp32, in the order of gram (a product with 1 is exact).
+ *   gram[i][j]  = sum_r x[r][i] * x[r][j]: the products are exact in fp32.  The rows are cut into S = vh_op_moments_slabs(R, W) slabs
+ *                 of P consecutive rows (the last one shorter).  Inside a slab r ascends in groups of 16 from +0, one
+ *                 v_mfma_f32_32x32x16 (gfx950) per group; the slabs are then added in ascending order from +0; with `accumulate` the
+ *                 previous content of the buffer is added last, one fp32 addition.
+ *   the slabs   T = nb (nb + 1) / 2 with nb = ceil(W / 128), the 128 x 128 tiles of the upper triangle; s = min(max(1, 512 / T),
+ *                 ceil(R / 256)); P = ceil(R / s) rounded up to a multiple of 32; S = ceil(R / P).  A function of (R, W) alone.
+ *   symmetry    only tiles I <= J, and of a diagonal tile only i <= j, are computed; gram[i][j] and gram[j][i] are stored from the same
+ *                 value: the full [W][W] matrix is written and is exactly symmetric.
+ *   count       one int64, R; added to the previous value under `accumulate`.
+ *   tail rows   rows behind a slab's last row enter as exact zeros (masked by index).
+ * The result is EXACT whenever every partial sum is representable in fp32 (integer data below 2^24, say); otherwise every element carries
+ * the bound of an fp32 sum of R exact products, R * 2^-24 * sum_r |x[r][i] x[r][j]|.  It depends on the rows, R and W alone: never on the
+ * stream, the batch, or where an image sits in the batch.
+ * NOT in the kernel: centring and the division by n.  The caller forms cov = (gram - n mu mu^T) / (n - 1) in float64 and accumulates
+ * across calls in float64 (vithip.FeatureMoments does).  That difference cancels: where |mu_i mu_j| dwarfs cov[i][j] the fp32 bound above
+ * is relative to gram, not to cov -- LayerNormed rows (VH_FEAT_NORM) have small means; for VH_FEAT_RAW rows with massive activations
+ * prefer several short calls to one long accumulate chain.
+ *
+ *   vh_patch_moments    images_host [nimages] = indices into the last forward's batch, repeats legal, 1 <= nimages <= 4 * max_batch;
+ *                       sum_host [D] fp32, gram_host [D][D] fp32, count_host one int64.  Host buffers, synchronous; accumulate must be
+ *                       0 (the host sums across calls itself, in float64).
+ *   .._device / .._device_async   device buffers (16-byte aligned) on the context's stream; wait / enqueue only.  accumulate 0 overwrites
+ *                       whatever the buffers held, accumulate 1 adds to them.  A listed image outside the last batch (unknown to the
+ *                       host) contributes nothing and is not counted: the result is that of the list without it.
+ * The context form reuses the match's operand scratch (allocated by the first match, cluster or moments call) and keeps a workspace of
+ * partial tiles, at most 32 MiB + 512 * D * 4 bytes + the packed list, which grows when a call needs more than any call before it: such a
+ * call allocates and is not legal inside a stream capture; every other call allocates nothing.  A context that never asks pays nothing.
+ *
+ * REFUSED, each with a message of its own, before a device is touched: a null context, descriptor, image list or output; norm, layer,
+ * accumulate or nimages out of range; a listed image (host list) outside the last batch; a device pointer that is not 16-byte aligned;
+ * accumulate on the host form; D not a multiple of 64 up to 2048; operand rows of more than 4 GiB; and everything the match refuses a
+ * context for (VH_FLAG_CLS_TAIL, VH_DTYPE_FP8, a ring, no forward, a layer not captured), under this call's name.
+ * Out of range: centring or scaling inside the kernel; per-image covariances (one workgroup per image leaves no parallelism for W^2;
+ * "Patch clustering" covers the per-image case); the eigen-decomposition on the device; fp8 contexts; the rings and the device groups. */
+#define VH_MOMENTS_MAX_WIDTH 2048
+typedef struct vh_moments_desc { /* sizeof == 16 */
+    int32_t norm;       /* VH_FEAT_NORM or VH_FEAT_RAW */
+    int32_t layer;      /* -1, or a layer as in vh_layer_features */
+    int32_t accumulate; /* 0 = overwrite, 1 = add to the buffers (device forms only) */
+    int32_t nimages;    /* 1 .. 4 * max_batch */
+} vh_moments_desc;
+int vh_patch_moments(vh_ctx* ctx, const vh_moments_desc* desc, const int32_t* images_host, float* sum_host, float* gram_host,
+                     int64_t* count_host);
+int vh_patch_moments_device(vh_ctx* ctx, const vh_moments_desc* desc, const int32_t* images_dev, float* sum_dev, float* gram_dev,
+                            int64_t* count_dev);
+int vh_patch_moments_device_async(vh_ctx* ctx, const vh_moments_desc* desc, const int32_t* images_dev, float* sum_dev, float* gram_dev,
+                                  int64_t* count_dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1712,6 +1774,16 @@ int vh_op_match(const void* a16_dev, const void* b16_dev, int dtype, int npairs,
  * outputs is written.  Every argument is checked before a device is touched, each refusal with a message of its own. */
 int vh_op_kmeans(const void* x16_dev, int dtype, int n, int np, int width, int k, int iters, int metric, const void* init16_dev,
                  int32_t* labels_dev, void* cent16_dev, int32_t* counts_dev, void* stream);
+/* The moments on their own ("Feature moments"): x16_dev [rows][width] contiguous rows of `dtype` (VH_DTYPE_BF16 / VH_DTYPE_FP16) -- patch,
+ * class-token or pooled rows alike -> sum_dev [width] fp32, gram_dev [width][width] fp32, count_dev one int64, overwritten (accumulate 0)
+ * or added to (1).  workspace_dev of vh_op_moments_workspace_bytes(rows, width) bytes (0: an argument is out of range).  width a multiple
+ * of 64 in 64 .. 2048, rows >= 1 and rows * width * 2 below 4 GiB; every pointer 16-byte aligned.  vh_op_moments_slabs: the number of
+ * row slabs S of "Feature moments" (a function of the two alone; 0: out of range).  Every argument is checked before a device is
+ * touched, each refusal with a message of its own. */
+int vh_op_moments(const void* x16_dev, int dtype, int64_t rows, int width, int accumulate, float* sum_dev, float* gram_dev, int64_t* count_dev,
+                  void* workspace_dev, void* stream);
+size_t vh_op_moments_workspace_bytes(int64_t rows, int width);
+int vh_op_moments_slabs(int64_t rows, int width);
 /* The rotation of a VH_FLAG_ROPE context on its own ("THE FUNCTION" at VH_FLAG_ROPE), in place on caller-made q|k|v of `dtype`
  * (VH_DTYPE_BF16 / VH_DTYPE_FP16) elements: q and k of rows lead .. tokens - 1 of every image and head are rotated by cos_dev / sin_dev
  * [tokens - lead][head_dim / 2] fp32; v, the lead rows and every row beyond batch * tokens are never written.

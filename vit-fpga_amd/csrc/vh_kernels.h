@@ -432,6 +432,48 @@ const char* kmeans_check(const KmeansArgs& a);
 hipError_t launch_kmeans(const KmeansArgs& a, hipStream_t stream);
 hipError_t launch_kmeans_round(const float* in, void* out16, int dtype, int64_t n, hipStream_t stream);
 hipError_t launch_kmeans_widen(const void* in16, float* out, int dtype, int64_t n, hipStream_t stream);
+// Feature moments (kernels_moments.hip; contract: vithip.h, "Feature moments").  launch_moments: sum [width], gram [width][width] fp32
+// and count (one int64) of 16-bit operand rows, overwritten or (accumulate) added to.  list == nullptr: the `rows` contiguous rows of
+// x16.  Otherwise x16 is [nimg][np][width], list [n + 8] on the device holds *nvalid <= n image indices 0 .. nimg - 1 (made by
+// launch_moments_list from a caller's list of n, entries outside 0 .. nimg - 1 dropped) and row r is patch r % np of image list[r / np].
+// workspace: moments_workspace_bytes(rows or n * np, width) bytes.  moments_plan: the split, a function of (rows, width) alone, the
+// same on the host and in the kernels.  moments_check: nullptr, or why the launch is refused; host arithmetic only.
+constexpr int kMomentsTargetWgs = 512;    // tiles x slabs aims at two workgroups per CU; also caps the workspace at 32 MiB of tiles
+constexpr int kMomentsMinSlabRows = 256;  // a slab is not made shorter than this
+struct MomentsPlan {
+    int nb, tiles;   // 128-column blocks of the width; tiles of the upper triangle
+    int smax;        // upper bound of slabs, monotone in rows: the grid and the workspace are sized by it
+    int slab_rows;   // rows per slab, a multiple of 32
+    int slabs;       // slabs that hold rows
+};
+__host__ __device__ inline MomentsPlan moments_plan(int64_t rows, int width) {
+    MomentsPlan p;
+    p.nb = (width + 127) / 128;
+    p.tiles = p.nb * (p.nb + 1) / 2;
+    const int want = kMomentsTargetWgs / p.tiles > 1 ? kMomentsTargetWgs / p.tiles : 1;
+    const int64_t cap = (rows + kMomentsMinSlabRows - 1) / kMomentsMinSlabRows;
+    p.smax = (int)(cap < want ? cap : want);
+    if (rows < 1) { p.smax = 0; p.slab_rows = 32; p.slabs = 0; return p; }
+    const int64_t per = ((rows + p.smax - 1) / p.smax + 31) / 32 * 32;
+    p.slab_rows = (int)per;
+    p.slabs = (int)((rows + per - 1) / per);
+    return p;
+}
+struct MomentsArgs {
+    const void* x16;
+    const int32_t* list;
+    const int32_t* nvalid;
+    int nimg, n, np, dtype, width, accumulate;
+    int64_t rows;
+    float* sum;
+    float* gram;
+    int64_t* count;
+    void* workspace;
+};
+size_t moments_workspace_bytes(int64_t rows, int width);
+const char* moments_check(const MomentsArgs& a);
+hipError_t launch_moments_list(const int32_t* images, int n, int nimg, int32_t* list, int32_t* nvalid, hipStream_t stream);
+hipError_t launch_moments(const MomentsArgs& a, hipStream_t stream);
 // fp8 path: the folded weights as e4m3 rows + scales (wscale), c = wscale * sum of the decoded row, d as launch_fold_ln
 hipError_t launch_fold_ln_f8(const float* w, const float* b, const float* gamma, const float* beta, int rows, int dim,
                              float scale, void* w8, float* wscale, float* c, float* d, hipStream_t stream);

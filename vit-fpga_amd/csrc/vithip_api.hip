@@ -444,6 +444,10 @@ struct vh_ctx {
     // of the operand type; grows when a call needs more than any call before it.  Only the cluster calls touch it.
     void* kmeans16 = nullptr;
     size_t kmeans16_bytes = 0;
+    // Feature moments (vh_patch_moments; vithip.h "Feature moments"): the packed image list [nimages + 8] and its count (16 bytes) in
+    // front of the partials workspace; grows when a call needs more than any call before it.  Only the moments calls touch it.
+    void* moments_ws = nullptr;
+    size_t moments_ws_bytes = 0;
     int64_t bank_n = 0;
     int bank_w = 0;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
@@ -1775,6 +1779,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->search_ws) hipFree(c->search_ws);
     if (c->match16) hipFree(c->match16);
     if (c->kmeans16) hipFree(c->kmeans16);
+    if (c->moments_ws) hipFree(c->moments_ws);
     if (c->w16) hipFree(c->w16);
     if (c->bias_img) hipFree(c->bias_img);
     if (c->subln_wb) hipFree(c->subln_wb);
@@ -3614,6 +3619,104 @@ int vh_cluster_patches(vh_ctx* c, const vh_kmeans_desc* d, const int32_t* images
     return VH_OK;
 }
 
+// ---- feature moments (vithip.h "Feature moments"; kernels_moments.hip) ------------------------------------------------------------
+// A pull interface on top of the match's: match_prepare makes the VH_MATCH_DOT operand rows of the last batch, the list kernel packs the
+// listed images that lie inside it, moments_kernel writes partial tiles into c->moments_ws, the merge writes the caller's buffers; all on
+// the main stream.  The descriptor's own fields are refused here; what the match refuses a context for is refused by match_check_call.
+static int moments_check_call(vh_ctx* c, const vh_moments_desc* d, const void* images, const void* sum, const void* gram, const void* count,
+                              bool device, vh_match_desc* md, FeatSource* src) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "patch_moments: null context");
+    if (!d) return fail(&c->err, VH_ERR_INVALID, "patch_moments: null descriptor");
+    if (!images) return fail(&c->err, VH_ERR_INVALID, "patch_moments: null image list");
+    if (!sum || !gram || !count) return fail(&c->err, VH_ERR_INVALID, "patch_moments: null output (sum, gram and count are all required)");
+    if (d->norm != VH_FEAT_NORM && d->norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "patch_moments: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", d->norm);
+    if (d->layer != -1 && (d->layer < 1 || d->layer > c->cfg.layers)) return fail(&c->err, VH_ERR_INVALID, "patch_moments: layer %d is not -1 or 1..%d", d->layer, c->cfg.layers);
+    if (d->accumulate != 0 && d->accumulate != 1) return fail(&c->err, VH_ERR_INVALID, "patch_moments: accumulate %d is not 0 or 1", d->accumulate);
+    if (!device && d->accumulate) return fail(&c->err, VH_ERR_INVALID, "patch_moments: accumulate is for the device forms (the host form overwrites; sum across calls in float64)");
+    if (d->nimages < 1 || d->nimages > 4 * c->cfg.max_batch)
+        return fail(&c->err, VH_ERR_INVALID, "patch_moments: nimages %d is outside 1..%d (4 x max_batch)", d->nimages, 4 * c->cfg.max_batch);
+    if (device && (((uintptr_t)images | (uintptr_t)sum | (uintptr_t)gram | (uintptr_t)count) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "patch_moments: a device pointer is not 16-byte aligned (images %p, sum %p, gram %p, count %p)", images, sum, gram, count);
+    *md = vh_match_desc{d->norm, d->layer, VH_MATCH_DOT, 1};
+    if (int rc = match_check_call(c, md, false, nullptr, sum, sum, false, src, "patch_moments")) return rc;
+    // the launch's own bounds (operand rows above 4 GiB, say) with stand-ins for the pointers, which are checked above: no device is touched yet
+    MomentsArgs a{};
+    a.x16 = a.sum = a.gram = (float*)16; a.count = (int64_t*)16; a.workspace = (void*)16; a.list = a.nvalid = (const int32_t*)16;
+    a.nimg = c->cfg.max_batch; a.n = d->nimages; a.np = c->L.NP; a.dtype = c->dt16; a.width = c->cfg.dim; a.accumulate = d->accumulate;
+    if (const char* why = moments_check(a)) return fail(&c->err, VH_ERR_INVALID, "patch_moments: %s", why);
+    return VH_OK;
+}
+static int moments_enqueue(vh_ctx* c, const vh_moments_desc& d, const vh_match_desc& md, const FeatSource& src, const int32_t* images_dev,
+                           float* sum_dev, float* gram_dev, int64_t* count_dev) {
+    const size_t list_bytes = ((size_t)(d.nimages + 8) * 4 + 15) / 16 * 16 + 16;   // the packed list, then its count
+    const size_t need = list_bytes + moments_workspace_bytes((int64_t)d.nimages * c->L.NP, c->cfg.dim);
+    if (c->moments_ws_bytes < need) {
+        if (c->moments_ws) hipFree(c->moments_ws);
+        c->moments_ws = nullptr;
+        c->moments_ws_bytes = 0;
+        const hipError_t e = hipMalloc(&c->moments_ws, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(&c->err, VH_ERR_HIP, "patch_moments: no room for the workspace: %s", hipGetErrorString(e));
+        }
+        c->moments_ws_bytes = need;
+    }
+    if (int rc = match_prepare(c, md, src, "patch_moments")) return rc;
+    int32_t* const list = (int32_t*)c->moments_ws;
+    int32_t* const nvalid = (int32_t*)((char*)c->moments_ws + list_bytes - 16);
+    HIPCHK(&c->err, launch_moments_list(images_dev, d.nimages, c->last_batch, list, nvalid, c->stream));
+    MomentsArgs a{};
+    a.x16 = c->match16; a.list = list; a.nvalid = nvalid; a.nimg = c->last_batch; a.n = d.nimages; a.np = c->L.NP; a.dtype = c->dt16;
+    a.width = c->cfg.dim; a.accumulate = d.accumulate; a.sum = sum_dev; a.gram = gram_dev; a.count = count_dev;
+    a.workspace = (char*)c->moments_ws + list_bytes;
+    if (const char* why = moments_check(a)) return fail(&c->err, VH_ERR_INVALID, "patch_moments: %s", why);
+    HIPCHK(&c->err, launch_moments(a, c->stream));
+    return VH_OK;
+}
+int vh_patch_moments_device_async(vh_ctx* c, const vh_moments_desc* d, const int32_t* images, float* sum, float* gram, int64_t* count) {
+    FeatSource src{};
+    vh_match_desc md{};
+    if (int rc = moments_check_call(c, d, images, sum, gram, count, true, &md, &src)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return moments_enqueue(c, *d, md, src, images, sum, gram, count);
+}
+int vh_patch_moments_device(vh_ctx* c, const vh_moments_desc* d, const int32_t* images, float* sum, float* gram, int64_t* count) {
+    if (int rc = vh_patch_moments_device_async(c, d, images, sum, gram, count)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+// the host form stages through device memory of the call's own (a synchronous call, outside any captured graph)
+int vh_patch_moments(vh_ctx* c, const vh_moments_desc* d, const int32_t* images, float* sum, float* gram, int64_t* count) {
+    FeatSource src{};
+    vh_match_desc md{};
+    if (int rc = moments_check_call(c, d, images, sum, gram, count, false, &md, &src)) return rc;
+    for (int i = 0; i < d->nimages; ++i)
+        if (images[i] < 0 || images[i] >= c->last_batch)
+            return fail(&c->err, VH_ERR_INVALID, "patch_moments: entry %d names image %d, outside 0..%d, the last forward's batch", i, images[i], c->last_batch - 1);
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t w = (size_t)c->cfg.dim, n_img = (size_t)d->nimages * 4;
+    int32_t* d_img = nullptr;
+    float *d_sum = nullptr, *d_gram = nullptr;
+    int64_t* d_cnt = nullptr;
+    hipError_t e = hipMalloc((void**)&d_img, n_img);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_sum, w * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_gram, w * w * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_cnt, 16);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_img, images, n_img, hipMemcpyHostToDevice, c->stream);
+    const int rc = e == hipSuccess ? moments_enqueue(c, *d, md, src, d_img, d_sum, d_gram, d_cnt) : 0;
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(sum, d_sum, w * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(gram, d_gram, w * w * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(count, d_cnt, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_compute(c);
+    hipFree(d_img);
+    hipFree(d_sum);
+    hipFree(d_gram);
+    hipFree(d_cnt);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(&c->err, VH_ERR_HIP, "patch_moments failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
@@ -4192,6 +4295,23 @@ int vh_op_kmeans(const void* x16, int dtype, int n, int np, int width, int k, in
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "kmeans failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
+// the moments of caller-made operand rows ("Feature moments")
+int vh_op_moments(const void* x16, int dtype, int64_t rows, int width, int accumulate, float* sum, float* gram, int64_t* count, void* workspace,
+                  void* stream) {
+    MomentsArgs a{};
+    a.x16 = x16; a.dtype = dtype; a.rows = rows; a.width = width; a.accumulate = accumulate; a.sum = sum; a.gram = gram; a.count = count;
+    a.workspace = workspace;
+    if (const char* why = moments_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_moments(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "moments failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+static bool moments_in_range(int64_t rows, int width) {
+    return rows >= 1 && width >= 64 && width <= VH_MOMENTS_MAX_WIDTH && width % 64 == 0 && rows * width * 2 <= (int64_t)UINT32_MAX;
+}
+size_t vh_op_moments_workspace_bytes(int64_t rows, int width) { return moments_in_range(rows, width) ? moments_workspace_bytes(rows, width) : 0; }
+int vh_op_moments_slabs(int64_t rows, int width) { return moments_in_range(rows, width) ? moments_plan(rows, width).slabs : 0; }
 size_t vh_op_search_workspace_bytes(int nq, int64_t n, int k) { return search_workspace_bytes(nq, n, k); }
 int vh_op_search_slabs(int nq, int64_t n) {
     if (nq < 1 || nq > VH_SEARCH_MAX_QUERIES || n < 1 || n > VH_SEARCH_MAX_ROWS) return 0;

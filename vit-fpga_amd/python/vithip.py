@@ -180,6 +180,11 @@ class KmeansDesc(C.Structure):
                 ("init", C.c_int32), ("nimages", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MomentsDesc(C.Structure):
+    """vh_moments_desc: norm, layer (as MatchDesc), accumulate (0 / 1, device forms only), nimages.  16 bytes."""
+    _fields_ = [("norm", C.c_int32), ("layer", C.c_int32), ("accumulate", C.c_int32), ("nimages", C.c_int32)]
+
+
 MAX_ATTENTION_LAYERS = 64
 ATTN_Q_CLS, ATTN_Q_LEAD = 0, 1        # vh_set_attention_layers queries (VH_ATTN_Q_*): the class token's row / every leading row
 ATTN_KEYS_ALL, ATTN_KEYS_PATCH = 0, 1  # vh_attention_maps.keys (VH_ATTN_KEYS_*): all key columns / the patch columns
@@ -420,6 +425,12 @@ SYMBOLS = {
     "vh_cluster_patches_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vh_cluster_patches_device_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vh_op_kmeans": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "vh_patch_moments": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_patch_moments_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_patch_moments_device_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_op_moments": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "vh_op_moments_workspace_bytes": (_sz, [_i64, _i]),
+    "vh_op_moments_slabs": (_i, [_i64, _i]),
     "vh_op_token_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "vh_op_token_features2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "vh_op_pool_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
@@ -2293,6 +2304,22 @@ class VitContext:
         f = lib().vh_cluster_patches_device if sync else lib().vh_cluster_patches_device_async
         _check(f(self.h, C.byref(desc), images_ptr, init_ptr, labels_ptr, centroids_ptr, counts_ptr), self.h)
 
+    # ---- mean and second moments of the patch rows of images of the last forward (vithip.h "Feature moments") ----
+    def patch_moments(self, images, norm=True, layer=-1):
+        """(sum [D] float32, gram [D, D] float32, count int) over the patch rows of the listed images of the last forward: the column
+        sums and X^T X of the rows rounded to the operand type.  Feed them to FeatureMoments.add, which accumulates in float64."""
+        img = np.ascontiguousarray(images, dtype=np.int32).reshape(-1)
+        dim = self.cfg["dim"]
+        s, g, n = np.empty(dim, dtype=np.float32), np.empty((dim, dim), dtype=np.float32), np.zeros(1, dtype=np.int64)
+        d = MomentsDesc(FEAT_NORM if norm else FEAT_RAW, int(layer), 0, img.size)
+        _check(lib().vh_patch_moments(self.h, C.byref(d), img.ctypes.data, s.ctypes.data, g.ctypes.data, n.ctypes.data), self.h)
+        return s, g, int(n[0])
+
+    def patch_moments_device(self, desc, images_ptr, sum_ptr, gram_ptr, count_ptr, sync=True):
+        """vh_patch_moments_device (sync) / _device_async: desc is a MomentsDesc, the pointers are device pointers."""
+        f = lib().vh_patch_moments_device if sync else lib().vh_patch_moments_device_async
+        _check(f(self.h, C.byref(desc), images_ptr, sum_ptr, gram_ptr, count_ptr), self.h)
+
     # ---- layer features: several layers of one forward (vithip.h "Layer features") ----
     def set_feature_layers(self, layers):
         """The layers every following forward captures: strictly ascending, each 1 .. layers (k = the residual stream after k
@@ -2809,6 +2836,66 @@ def op_kmeans(x_ptr, dtype, n, np_rows, width, k, iters, metric, init_ptr, label
     """The clustering on its own (vh_op_kmeans): operand rows x [n, np_rows, width] of `dtype`, init [k, width] of `dtype` or None (the
     stride init) -> labels [n, np_rows] int32, centroids [n, k, width] of `dtype` (working state and result), counts [n, k] int32."""
     _check(lib().vh_op_kmeans(x_ptr, dtype, n, np_rows, width, k, iters, metric, init_ptr, labels_ptr, cent_ptr, counts_ptr, None))
+
+
+def op_moments(x_ptr, dtype, rows, width, accumulate, sum_ptr, gram_ptr, count_ptr, workspace_ptr):
+    """The moments on their own (vh_op_moments): contiguous operand rows x [rows, width] of `dtype` -> sum [width] fp32, gram
+    [width, width] fp32, count (one int64), overwritten or (accumulate) added to, in a workspace of op_moments_workspace_bytes bytes."""
+    _check(lib().vh_op_moments(x_ptr, dtype, rows, width, accumulate, sum_ptr, gram_ptr, count_ptr, workspace_ptr, None))
+
+
+def op_moments_workspace_bytes(rows, width):
+    return int(lib().vh_op_moments_workspace_bytes(rows, width))
+
+
+def op_moments_slabs(rows, width):
+    """The number of row slabs the moments split `rows` rows of `width` elements into."""
+    return int(lib().vh_op_moments_slabs(rows, width))
+
+
+class FeatureMoments:
+    """A float64 accumulator of (sum, gram, count) triples, e.g. of patch_moments over many forwards: mean, covariance, PCA, whitening."""
+
+    def __init__(self, width):
+        self.width = int(width)
+        self.sum = np.zeros(self.width, dtype=np.float64)
+        self.gram = np.zeros((self.width, self.width), dtype=np.float64)
+        self.count = 0
+
+    def add(self, sum, gram, count):
+        self.sum += np.asarray(sum, dtype=np.float64).reshape(self.width)
+        self.gram += np.asarray(gram, dtype=np.float64).reshape(self.width, self.width)
+        self.count += int(count)
+        return self
+
+    def mean(self):
+        return self.sum / self.count
+
+    def covariance(self):
+        """(gram - n mu mu^T) / (n - 1), symmetrised."""
+        mu = self.mean()
+        c = (self.gram - self.count * np.outer(mu, mu)) / (self.count - 1)
+        return 0.5 * (c + c.T)
+
+    def pca(self, m):
+        """(eigenvalues [m], components [m, width]) of the covariance (numpy.linalg.eigh), descending; the sign of every component is
+        fixed so that its entry of largest magnitude is positive."""
+        w, v = np.linalg.eigh(self.covariance())
+        w, v = w[::-1][:int(m)], v[:, ::-1][:, :int(m)].T
+        big = v[np.arange(v.shape[0]), np.argmax(np.abs(v), axis=1)]
+        return w, v * np.where(big < 0, -1.0, 1.0)[:, None]
+
+    def whitening(self, m, eps=1e-6):
+        """(mean, matrix [m, width]): matrix @ (x - mean) has unit covariance on the m leading components."""
+        w, v = self.pca(m)
+        return self.mean(), v / np.sqrt(np.maximum(w, 0.0) + eps)[:, None]
+
+
+def pca_head(mean, components):
+    """(weight [m, W], bias [m]) float64 with weight @ x + bias == components @ (x - mean): ctx.set_dense_head(weight, bias) and
+    dense_logits() then give the per-patch projections [batch, m, gh, gw] on the GPU."""
+    v = np.array(components, dtype=np.float64)
+    return v, -v @ np.asarray(mean, dtype=np.float64)
 
 
 def segment_masks(labels, k):
