@@ -1416,6 +1416,74 @@ int vh_patch_moments_device(vh_ctx* ctx, const vh_moments_desc* desc, const int3
 int vh_patch_moments_device_async(vh_ctx* ctx, const vh_moments_desc* desc, const int32_t* images_dev, float* sum_dev, float* gram_dev,
                                   int64_t* count_dev);
 
+/* ---- Label propagation ------------------------------------------------------------------------
+ * What video object segmentation (DINO's DAVIS protocol: 7 context frames, top-5, temperature 0.1, window 12), in-context segmentation
+ * (memory patches with labels, attention over the k nearest), few-shot mask transfer and keypoint heat-map transfer run on patch
+ * features: for every patch of a target image the k most similar patches among the patches of SEVERAL source images, optionally only
+ * inside a spatial window around the patch, and the softmax-weighted sum of those patches' label vectors.  One kernel: the [NP][S NP]
+ * similarities are never written and no patch row leaves the device.  A PULL interface like the match: it reads the operand rows the
+ * match's prepare pass makes, no forward knows of it, a call drops no cached graph and changes no logit.
+ *
+ * THE FUNCTION, for bits.  T16 = the operand type; the operand rows are the match's (VH_MATCH_DOT: the rows rounded to T16,
+ * VH_MATCH_COSINE: the unit rows; vh_match_operands returns them); W = the row width; NP = gh * gw patches (a context has gh = gw =
+ * image / patch), patch p at (p / gw, p % gw).
+ *   item        items[i] = (t, s_0 .. s_{S-1}), image indices of the last batch; S = nsrc is fixed per call.  A slot < 0 is ABSENT (the
+ *               first frames of a clip); t may be among its own sources; a source may repeat.
+ *   candidates  of query patch q of t: the patches j of every present slot sigma, key id g = sigma * NP + j.  radius = 0: all of them;
+ *               radius >= 1: only |j / gw - q / gw| <= radius and |j % gw - q % gw| <= radius (a square window).
+ *   score       s(q, g) = the match's s on the two rows: products exact in fp32, the sum from +0 with k ascending in groups of 16, one
+ *               v_mfma_f32_32x32x16 (gfx950) per group.  It depends on the two rows and W alone.
+ *   selection   the first min(k, candidates) ids under (score descending, g ascending): TIES GO TO THE LOWER g.  idx [n][NP][k] int32
+ *               (g; the tail -1) and score [n][NP][k] fp32 (the tail -inf), sorted.  The kept set does not depend on how the kernel
+ *               tiles the keys.
+ *   vote        c = (float)(log2(e) / (double)tau), made once on the host.  w_e = exp2((s_e - s_0) * c): an fp32 subtraction, an fp32
+ *               product, the hardware exponential (v_exp_f32), so w_0 = 1 exactly.  Z = w_0 + w_1 + .. ascending in e.
+ *               out[i][q][c] = (sum_e w_e * L[src(sigma_e)][j_e][c]) / Z: a fused multiply-add chain ascending in e from +0, then one
+ *               correctly rounded division.  labels L [batch][NP][C] fp32 is indexed by IMAGE, out [n][NP][C] fp32.  Without a
+ *               candidate (every slot absent) the row of out is zero.
+ * Everything but exp2 is defined to the bit: the scores, the kept set and its order, and -- given the weights -- Z, the chain and the
+ * quotient.  With k = 1, or where all kept scores are equal, the weights are exactly 1 and out is bit-defined as well.
+ *
+ *   vh_propagate_labels   items_host [nitems][1 + nsrc] int32, labels_host [batch of the last forward][NP][classes] fp32, out_host
+ *                         [nitems][NP][classes] fp32, idx_host / score_host [nitems][NP][k] or NULL.  Host buffers, synchronous.  The
+ *                         staging memory grows when a call needs more than any call before it (not legal inside a stream capture).
+ *   .._device / .._device_async   the same with device pointers (16-byte aligned) on the context's stream; wait / enqueue only.  A t or
+ *                         a present s outside the last batch is unknown to the host: the item gets idx -1, score -inf and out 0, and
+ *                         nothing is read for it.  out MAY point into the labels array at an image slot that is NOT A SOURCE of any item
+ *                         of the same call (the video chain: frame t's result becomes the labels of image t for the next call); a slot
+ *                         that is a source of the call must not be written -- this is the caller's obligation and is not checked.
+ * The context form reuses the match's operand scratch (allocated by the first match, cluster, moments or propagate call).
+ *
+ * REFUSED, each with a message of its own, before a device is touched: a null context, descriptor, item list, labels or out; norm,
+ * layer, metric, nitems (1 .. 4 * max_batch), nsrc (1 .. 8), k (1 .. 16), radius (0 .. 4096), classes (1 .. 256) out of range; tau not
+ * finite or not positive; reserved not 0; a host item outside the last batch; a device pointer that is not 16-byte aligned; NP above
+ * 4096 or D not a multiple of 64 up to 2048; and everything the match refuses a context for (VH_FLAG_CLS_TAIL, VH_DTYPE_FP8, a ring, no
+ * forward, a layer not captured), under this call's name.
+ * Out of range: k > 16 (a list that long belongs in LDS, like the search's); sources from earlier forwards or from a device-resident
+ * memory of patch rows; non-square grids in the context form (the tap vh_op_propagate takes gh != gw); fp8 contexts; the rings and the
+ * device groups; a circular window; upsampling the propagated map. */
+#define VH_PROP_MAX_SOURCES 8
+#define VH_PROP_MAX_K 16
+#define VH_PROP_MAX_CLASSES 256
+typedef struct vh_propagate_desc { /* sizeof == 40 */
+    int32_t norm;     /* VH_FEAT_NORM or VH_FEAT_RAW */
+    int32_t layer;    /* -1, or a layer as in vh_layer_features */
+    int32_t metric;   /* VH_MATCH_COSINE or VH_MATCH_DOT */
+    int32_t nitems;   /* 1 .. 4 * max_batch */
+    int32_t nsrc;     /* 1 .. 8 source slots per item */
+    int32_t k;        /* 1 .. 16 */
+    int32_t radius;   /* 0 = no window, else 1 .. 4096 */
+    int32_t classes;  /* 1 .. 256 */
+    float tau;        /* finite, > 0 */
+    int32_t reserved; /* 0 */
+} vh_propagate_desc;
+int vh_propagate_labels(vh_ctx* ctx, const vh_propagate_desc* desc, const int32_t* items_host, const float* labels_host, float* out_host,
+                        int32_t* idx_host, float* score_host);
+int vh_propagate_labels_device(vh_ctx* ctx, const vh_propagate_desc* desc, const int32_t* items_dev, const float* labels_dev,
+                               float* out_dev, int32_t* idx_dev, float* score_dev);
+int vh_propagate_labels_device_async(vh_ctx* ctx, const vh_propagate_desc* desc, const int32_t* items_dev, const float* labels_dev,
+                                     float* out_dev, int32_t* idx_dev, float* score_dev);
+
 /* ---- operator-level entry points (device pointers, dtype = VH_DTYPE_*) ----------------- */
 /* Each is the kernel the forward uses, exposed so that parity tests and micro-benchmarks
  * can drive it alone.  `stream` is a hipStream_t passed as void* (NULL = default stream);
@@ -1766,6 +1834,15 @@ int vh_op_search_slabs(int nq, int64_t n);
  * is touched, each refusal with a message of its own. */
 int vh_op_match(const void* a16_dev, const void* b16_dev, int dtype, int npairs, int na, int nb, int width, int metric, int32_t* idx_dev,
                 float* score_dev, void* stream);
+/* The propagation on its own ("Label propagation"): rows16_dev [images][gh * gw][width] of `dtype` (VH_DTYPE_BF16 / VH_DTYPE_FP16), the
+ * operand rows as they are; items_dev [nitems][1 + nsrc] int32; labels_dev [images][gh * gw][classes] fp32 -> out_dev [nitems][gh * gw]
+ * [classes] fp32, idx_dev / score_dev [nitems][gh * gw][k] or NULL.  gh != gw is legal here.  images 1 .. 2^20, gh * gw 1 .. 4096, width
+ * a multiple of 64 in 64 .. 2048, nitems 1 .. 65536, nsrc 1 .. 8, k 1 .. 16, radius 0 .. 4096, tau finite and positive, classes 1 ..
+ * 256; every pointer 16-byte aligned.  Nothing outside the three outputs is written.  Every argument is checked before a device is
+ * touched, each refusal with a message of its own. */
+int vh_op_propagate(const void* rows16_dev, int dtype, int images, int gh, int gw, int width, const int32_t* items_dev, int nitems, int nsrc,
+                    int k, int radius, float tau, const float* labels_dev, int classes, float* out_dev, int32_t* idx_dev, float* score_dev,
+                    void* stream);
 /* The clustering on its own ("Patch clustering"): x16_dev [n][np][width] of `dtype` (VH_DTYPE_BF16 / VH_DTYPE_FP16), image i clustered on
  * its own into k clusters by `iters` rounds of { assign; update } and a final assign.  init16_dev [k][width] of `dtype`, shared by all
  * images, or NULL = the stride init.  labels_dev [n][np] int32; cent16_dev [n][k][width] of `dtype` is the working state AND the result

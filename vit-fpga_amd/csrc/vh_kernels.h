@@ -413,6 +413,27 @@ struct MatchArgs {
 int match_query_rows(int npairs, int na);
 const char* match_check(const MatchArgs& a);
 hipError_t launch_match(const MatchArgs& a, hipStream_t stream);
+// Label propagation (kernels_propagate.hip; contract: vithip.h, "Label propagation").  launch_propagate: for item i = items [nitems]
+// [1 + nsrc] = (t, s_0 ..) on the device, images of rows16 [images][gh * gw][width] of `dtype` (the match's operand rows), and every
+// patch of t: the first k patches of the present sources (a slot < 0 is absent) under (score descending, id ascending), inside the
+// square window of `radius` (0: everywhere) -> idx / score [nitems][gh * gw][k] (either may be nullptr) and out [nitems][gh * gw]
+// [classes] = the softmax(score / tau)-weighted sum of the rows of labels [images][gh * gw][classes] those patches name.  A t or a
+// present s outside 0 .. images - 1: idx -1, score -inf, out 0 for the item, nothing read.  propagate_check: nullptr, or why the launch
+// is refused; host arithmetic only.  No scratch, no allocation, no counter.
+struct PropagateArgs {
+    const void* rows16;
+    int dtype, images, gh, gw, width;
+    const int32_t* items;
+    int nitems, nsrc, k, radius;
+    float tau;
+    const float* labels;
+    int classes;
+    float* out;
+    int32_t* idx;
+    float* score;
+};
+const char* propagate_check(const PropagateArgs& a);
+hipError_t launch_propagate(const PropagateArgs& a, hipStream_t stream);
 // Patch clustering (kernels_kmeans.hip; contract: vithip.h, "Patch clustering").  launch_kmeans: k-means of the rows of every listed
 // image on its own, one workgroup per image: labels [n][np], cent16 [n][k][width] of `dtype` (working state and result), counts [n][k]
 // or nullptr.  images == nullptr: image i of x16 [n][np][width]; otherwise images [n] on the device names images of x16 [nimg][np][width]

@@ -448,6 +448,10 @@ struct vh_ctx {
     // front of the partials workspace; grows when a call needs more than any call before it.  Only the moments calls touch it.
     void* moments_ws = nullptr;
     size_t moments_ws_bytes = 0;
+    // Label propagation (vh_propagate_labels; vithip.h "Label propagation"): the HOST form's device staging -- items, labels, out, idx,
+    // score -- which grows when a call needs more than any call before it.  The device forms touch nothing but the operand rows.
+    void* prop_stage = nullptr;
+    size_t prop_stage_bytes = 0;
     int64_t bank_n = 0;
     int bank_w = 0;
     // pipelined host path (vh_ring_*): slots of pinned host staging + device buffers, copies on their own streams
@@ -1780,6 +1784,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->match16) hipFree(c->match16);
     if (c->kmeans16) hipFree(c->kmeans16);
     if (c->moments_ws) hipFree(c->moments_ws);
+    if (c->prop_stage) hipFree(c->prop_stage);
     if (c->w16) hipFree(c->w16);
     if (c->bias_img) hipFree(c->bias_img);
     if (c->subln_wb) hipFree(c->subln_wb);
@@ -3717,6 +3722,113 @@ int vh_patch_moments(vh_ctx* c, const vh_moments_desc* d, const int32_t* images,
     return VH_OK;
 }
 
+// ---- label propagation (vithip.h "Label propagation"; kernels_propagate.hip) ---------------------------------------------------------
+// A pull interface on top of the match's: match_prepare makes the operand rows of the last batch, propagate_kernel selects and votes;
+// both on the main stream.  The descriptor's own fields are refused here; what the match refuses a context for is refused by
+// match_check_call, under this call's name.
+static PropagateArgs propagate_args(vh_ctx* c, const vh_propagate_desc& d, const int32_t* items, const float* labels, float* out, int32_t* idx,
+                                    float* score) {
+    const int g = c->cfg.image_size / c->cfg.patch_size;
+    PropagateArgs a{};
+    a.rows16 = c->match16; a.dtype = c->dt16; a.images = c->last_batch; a.gh = g; a.gw = g; a.width = c->cfg.dim; a.items = items;
+    a.nitems = d.nitems; a.nsrc = d.nsrc; a.k = d.k; a.radius = d.radius; a.tau = d.tau; a.labels = labels; a.classes = d.classes;
+    a.out = out; a.idx = idx; a.score = score;
+    return a;
+}
+static int propagate_check_call(vh_ctx* c, const vh_propagate_desc* d, const void* items, const void* labels, const void* out, const void* idx,
+                                const void* score, bool device, vh_match_desc* md, FeatSource* src) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "propagate_labels: null context");
+    if (!d) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: null descriptor");
+    if (!items) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: null item list");
+    if (!labels || !out) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: null labels or out (idx and score may be null)");
+    if (d->norm != VH_FEAT_NORM && d->norm != VH_FEAT_RAW) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: norm %d is not VH_FEAT_NORM (0) or VH_FEAT_RAW (1)", d->norm);
+    if (d->layer != -1 && (d->layer < 1 || d->layer > c->cfg.layers)) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: layer %d is not -1 or 1..%d", d->layer, c->cfg.layers);
+    if (d->metric != VH_MATCH_COSINE && d->metric != VH_MATCH_DOT)
+        return fail(&c->err, VH_ERR_INVALID, "propagate_labels: metric %d is not VH_MATCH_COSINE (0) or VH_MATCH_DOT (1)", d->metric);
+    if (d->nitems < 1 || d->nitems > 4 * c->cfg.max_batch)
+        return fail(&c->err, VH_ERR_INVALID, "propagate_labels: nitems %d is outside 1..%d (4 x max_batch)", d->nitems, 4 * c->cfg.max_batch);
+    if (d->nsrc < 1 || d->nsrc > VH_PROP_MAX_SOURCES) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: nsrc %d is outside 1..%d", d->nsrc, VH_PROP_MAX_SOURCES);
+    if (d->k < 1 || d->k > VH_PROP_MAX_K) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: k %d is outside 1..%d", d->k, VH_PROP_MAX_K);
+    if (d->radius < 0 || d->radius > 4096) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: radius %d is outside 0..4096", d->radius);
+    if (d->classes < 1 || d->classes > VH_PROP_MAX_CLASSES)
+        return fail(&c->err, VH_ERR_INVALID, "propagate_labels: classes %d is outside 1..%d", d->classes, VH_PROP_MAX_CLASSES);
+    if (!(d->tau > 0.f) || !std::isfinite(d->tau)) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: tau %g is not finite and positive", (double)d->tau);
+    if (d->reserved) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: reserved is not 0");
+    if (device && (((uintptr_t)items | (uintptr_t)labels | (uintptr_t)out | (uintptr_t)idx | (uintptr_t)score) & 15))
+        return fail(&c->err, VH_ERR_INVALID, "propagate_labels: a device pointer is not 16-byte aligned (items %p, labels %p, out %p, idx %p, score %p)",
+                    items, labels, out, idx, score);
+    *md = vh_match_desc{d->norm, d->layer, d->metric, 1};
+    if (int rc = match_check_call(c, md, false, nullptr, out, out, false, src, "propagate_labels")) return rc;
+    // the launch's own bounds (NP above 4096, say) with stand-ins for the pointers, which are checked above: no device is touched yet
+    PropagateArgs a = propagate_args(c, *d, (const int32_t*)16, (const float*)16, (float*)16, nullptr, nullptr);
+    a.rows16 = (const void*)16;
+    if (const char* why = propagate_check(a)) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: %s", why);
+    return VH_OK;
+}
+static int propagate_enqueue(vh_ctx* c, const vh_propagate_desc& d, const vh_match_desc& md, const FeatSource& src, const int32_t* items_dev,
+                             const float* labels_dev, float* out_dev, int32_t* idx_dev, float* score_dev) {
+    if (int rc = match_prepare(c, md, src, "propagate_labels")) return rc;
+    const PropagateArgs a = propagate_args(c, d, items_dev, labels_dev, out_dev, idx_dev, score_dev);
+    if (const char* why = propagate_check(a)) return fail(&c->err, VH_ERR_INVALID, "propagate_labels: %s", why);
+    HIPCHK(&c->err, launch_propagate(a, c->stream));
+    return VH_OK;
+}
+int vh_propagate_labels_device_async(vh_ctx* c, const vh_propagate_desc* d, const int32_t* items, const float* labels, float* out, int32_t* idx,
+                                     float* score) {
+    FeatSource src{};
+    vh_match_desc md{};
+    if (int rc = propagate_check_call(c, d, items, labels, out, idx, score, true, &md, &src)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return propagate_enqueue(c, *d, md, src, items, labels, out, idx, score);
+}
+int vh_propagate_labels_device(vh_ctx* c, const vh_propagate_desc* d, const int32_t* items, const float* labels, float* out, int32_t* idx,
+                               float* score) {
+    if (int rc = vh_propagate_labels_device_async(c, d, items, labels, out, idx, score)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+// the host form stages through c->prop_stage (a synchronous call, outside any captured graph)
+int vh_propagate_labels(vh_ctx* c, const vh_propagate_desc* d, const int32_t* items, const float* labels, float* out, int32_t* idx, float* score) {
+    FeatSource src{};
+    vh_match_desc md{};
+    if (int rc = propagate_check_call(c, d, items, labels, out, idx, score, false, &md, &src)) return rc;
+    for (int i = 0; i < d->nitems; ++i)
+        for (int s = 0; s <= d->nsrc; ++s) {
+            const int v = items[(size_t)i * (d->nsrc + 1) + s];
+            if (v >= c->last_batch || (v < 0 && s == 0))
+                return fail(&c->err, VH_ERR_INVALID, "propagate_labels: item %d names image %d, outside 0..%d, the last forward's batch", i, v, c->last_batch - 1);
+        }
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    auto up16 = [](size_t n) { return (n + 15) / 16 * 16; };
+    const size_t rows = (size_t)d->nitems * c->L.NP;
+    const size_t n_items = (size_t)d->nitems * (d->nsrc + 1) * 4, n_lab = (size_t)c->last_batch * c->L.NP * d->classes * 4;
+    const size_t n_out = rows * d->classes * 4, n_sel = rows * d->k * 4;
+    const size_t o_lab = up16(n_items), o_out = o_lab + up16(n_lab), o_idx = o_out + up16(n_out), o_score = o_idx + up16(n_sel);
+    const size_t need = o_score + up16(n_sel);
+    if (c->prop_stage_bytes < need) {
+        if (c->prop_stage) hipFree(c->prop_stage);
+        c->prop_stage = nullptr;
+        c->prop_stage_bytes = 0;
+        const hipError_t e = hipMalloc(&c->prop_stage, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(&c->err, VH_ERR_HIP, "propagate_labels: no room for the staging memory: %s", hipGetErrorString(e));
+        }
+        c->prop_stage_bytes = need;
+    }
+    char* const st = (char*)c->prop_stage;
+    int32_t* const d_idx = idx ? (int32_t*)(st + o_idx) : nullptr;
+    float* const d_score = score ? (float*)(st + o_score) : nullptr;
+    HIPCHK(&c->err, hipMemcpyAsync(st, items, n_items, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(&c->err, hipMemcpyAsync(st + o_lab, labels, n_lab, hipMemcpyHostToDevice, c->stream));
+    if (int rc = propagate_enqueue(c, *d, md, src, (const int32_t*)st, (const float*)(st + o_lab), (float*)(st + o_out), d_idx, d_score)) return rc;
+    HIPCHK(&c->err, hipMemcpyAsync(out, st + o_out, n_out, hipMemcpyDeviceToHost, c->stream));
+    if (idx) HIPCHK(&c->err, hipMemcpyAsync(idx, d_idx, n_sel, hipMemcpyDeviceToHost, c->stream));
+    if (score) HIPCHK(&c->err, hipMemcpyAsync(score, d_score, n_sel, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+
 // ---- operator-level entry points ------------------------------------------------------------------
 #define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(nullptr, VH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
@@ -4281,6 +4393,18 @@ int vh_op_match(const void* a16, const void* b16, int dtype, int npairs, int na,
     hipError_t e = launch_match(a, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "match failed: %s", hipGetErrorString(e));
+    return VH_OK;
+}
+// the propagation on caller-made operand rows ("Label propagation")
+int vh_op_propagate(const void* rows16, int dtype, int images, int gh, int gw, int width, const int32_t* items, int nitems, int nsrc, int k,
+                    int radius, float tau, const float* labels, int classes, float* out, int32_t* idx, float* score, void* stream) {
+    PropagateArgs a{};
+    a.rows16 = rows16; a.dtype = dtype; a.images = images; a.gh = gh; a.gw = gw; a.width = width; a.items = items; a.nitems = nitems;
+    a.nsrc = nsrc; a.k = k; a.radius = radius; a.tau = tau; a.labels = labels; a.classes = classes; a.out = out; a.idx = idx; a.score = score;
+    if (const char* why = propagate_check(a)) return fail(nullptr, VH_ERR_INVALID, "%s", why);
+    hipError_t e = launch_propagate(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, VH_ERR_HIP, "propagate failed: %s", hipGetErrorString(e));
     return VH_OK;
 }
 // the clustering on caller-made operand rows ("Patch clustering")

@@ -185,6 +185,16 @@ class MomentsDesc(C.Structure):
     _fields_ = [("norm", C.c_int32), ("layer", C.c_int32), ("accumulate", C.c_int32), ("nimages", C.c_int32)]
 
 
+PROP_MAX_SOURCES, PROP_MAX_K, PROP_MAX_CLASSES = 8, 16, 256   # VH_PROP_MAX_*
+
+
+class PropagateDesc(C.Structure):
+    """vh_propagate_desc: norm, layer, metric (as MatchDesc), nitems, nsrc, k, radius (0 = no window), classes, tau, reserved 0.
+    40 bytes."""
+    _fields_ = [("norm", C.c_int32), ("layer", C.c_int32), ("metric", C.c_int32), ("nitems", C.c_int32), ("nsrc", C.c_int32),
+                ("k", C.c_int32), ("radius", C.c_int32), ("classes", C.c_int32), ("tau", C.c_float), ("reserved", C.c_int32)]
+
+
 MAX_ATTENTION_LAYERS = 64
 ATTN_Q_CLS, ATTN_Q_LEAD = 0, 1        # vh_set_attention_layers queries (VH_ATTN_Q_*): the class token's row / every leading row
 ATTN_KEYS_ALL, ATTN_KEYS_PATCH = 0, 1  # vh_attention_maps.keys (VH_ATTN_KEYS_*): all key columns / the patch columns
@@ -421,6 +431,10 @@ SYMBOLS = {
     "vh_match_patches_device_async": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "vh_match_operands": (_i, [_vp, _vp, _i, _vp]),
     "vh_op_match": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vh_propagate_labels": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_propagate_labels_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_propagate_labels_device_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vh_op_propagate": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp]),
     "vh_cluster_patches": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vh_cluster_patches_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vh_cluster_patches_device_async": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -2320,6 +2334,36 @@ class VitContext:
         f = lib().vh_patch_moments_device if sync else lib().vh_patch_moments_device_async
         _check(f(self.h, C.byref(desc), images_ptr, sum_ptr, gram_ptr, count_ptr), self.h)
 
+    # ---- top-k patch neighbours across images and the soft vote of their labels (vithip.h "Label propagation") ----
+    def _propagate_desc(self, nitems, nsrc, k, tau, radius, classes, metric, norm, layer):
+        m = {"cosine": MATCH_COSINE, "dot": MATCH_DOT}.get(metric, metric)
+        return PropagateDesc(int(norm), int(layer), int(m), int(nitems), int(nsrc), int(k), int(radius), int(classes), float(tau), 0)
+
+    def propagate_labels(self, items, labels, k=5, tau=0.1, radius=0, metric=MATCH_COSINE, norm=FEAT_NORM, layer=-1, topk=False):
+        """out [n, NP, C] float32: for every patch of image t of each item (t, s_0, .., s_{S-1}) of the last forward the
+        softmax(score / tau)-weighted sum of the label rows of its k most similar patches among the sources' patches (a slot < 0 is
+        absent; radius >= 1: only inside the square window around the patch).  labels [batch, NP, C] float32, indexed by image.
+        topk: also (idx [n, NP, k] int32 = slot * NP + patch, tails -1; score [n, NP, k] float32, tails -inf)."""
+        it = np.ascontiguousarray(items, dtype=np.int32)
+        it = it.reshape(-1, it.shape[-1]) if it.ndim > 1 else it.reshape(1, -1)
+        batch, _, npatch, _ = self.features_dims()
+        lab = np.ascontiguousarray(labels, dtype=np.float32)
+        if lab.ndim != 3 or lab.shape[:2] != (batch, npatch):
+            raise ValueError(f"labels must be [batch, NP, C] = [{batch}, {npatch}, C], got {list(lab.shape)}")
+        n, classes = max(it.shape[0], 1), lab.shape[2]
+        out = np.empty((n, npatch, classes), dtype=np.float32)
+        idx = np.empty((n, npatch, max(int(k), 1)), dtype=np.int32) if topk else None
+        score = np.empty(idx.shape, dtype=np.float32) if topk else None
+        d = self._propagate_desc(it.shape[0], it.shape[1] - 1, k, tau, radius, classes, metric, norm, layer)
+        _check(lib().vh_propagate_labels(self.h, C.byref(d), it.ctypes.data, lab.ctypes.data, out.ctypes.data,
+                                         None if idx is None else idx.ctypes.data, None if score is None else score.ctypes.data), self.h)
+        return (out, idx, score) if topk else out
+
+    def propagate_labels_device(self, desc, items_ptr, labels_ptr, out_ptr, idx_ptr=None, score_ptr=None, sync=True):
+        """vh_propagate_labels_device (sync) / _device_async: desc is a PropagateDesc, the pointers are device pointers (or None)."""
+        f = lib().vh_propagate_labels_device if sync else lib().vh_propagate_labels_device_async
+        _check(f(self.h, C.byref(desc), items_ptr, labels_ptr, out_ptr, idx_ptr, score_ptr), self.h)
+
     # ---- layer features: several layers of one forward (vithip.h "Layer features") ----
     def set_feature_layers(self, layers):
         """The layers every following forward captures: strictly ascending, each 1 .. layers (k = the residual stream after k
@@ -2830,6 +2874,51 @@ def op_match(a_ptr, b_ptr, dtype, npairs, na, nb, width, metric, idx_ptr, score_
     """The match on its own (vh_op_match): operand rows a [npairs, na, width] and b [npairs, nb, width] of `dtype` -> idx [npairs, na]
     int32 (the best row of b for every row of a, ties to the lower index) and score [npairs, na] fp32."""
     _check(lib().vh_op_match(a_ptr, b_ptr, dtype, npairs, na, nb, width, metric, idx_ptr, score_ptr, None))
+
+
+def op_propagate(rows_ptr, dtype, images, gh, gw, width, items_ptr, nitems, nsrc, k, radius, tau, labels_ptr, classes, out_ptr,
+                 idx_ptr=None, score_ptr=None):
+    """The propagation on its own (vh_op_propagate): operand rows [images, gh * gw, width] of `dtype`, items [nitems, 1 + nsrc] int32,
+    labels [images, gh * gw, classes] fp32 -> out [nitems, gh * gw, classes] fp32, idx / score [nitems, gh * gw, k] or None."""
+    _check(lib().vh_op_propagate(rows_ptr, dtype, images, gh, gw, width, items_ptr, nitems, nsrc, k, radius, tau, labels_ptr, classes,
+                                 out_ptr, idx_ptr, score_ptr, None))
+
+
+def propagate_video(ctx, first_labels, n_ctx=7, **kw):
+    """DINO's video label propagation over the frames of the last forward, in batch order: frame 0 carries first_labels [NP, C], frame
+    t takes the sources {0} and {t - n_ctx .. t - 1} (absent slots -1) with propagate_labels' keywords (k, tau, radius, metric, norm,
+    layer) and its result becomes the labels of frame t.  The label array stays on the device: one asynchronous call per frame, each
+    writing slot t, which is no source of its own call.  Returns labels [batch, NP, C] float32."""
+    batch, _, npatch, _ = ctx.features_dims()
+    first = np.ascontiguousarray(first_labels, dtype=np.float32)
+    if first.ndim != 2 or first.shape[0] != npatch:
+        raise ValueError(f"first_labels must be [NP, C] = [{npatch}, C], got {list(first.shape)}")
+    classes, nsrc = first.shape[1], 1 + int(n_ctx)
+    if not 1 <= int(n_ctx) < PROP_MAX_SOURCES:
+        raise ValueError(f"n_ctx must be 1..{PROP_MAX_SOURCES - 1}, got {n_ctx}")
+    k, tau, radius = kw.pop("k", 5), kw.pop("tau", 0.1), kw.pop("radius", 0)
+    metric, norm, layer = kw.pop("metric", MATCH_COSINE), kw.pop("norm", FEAT_NORM), kw.pop("layer", -1)
+    if kw:
+        raise TypeError(f"unknown keywords {sorted(kw)}")
+    items = np.full((batch, 4 * ((nsrc + 4) // 4)), -1, dtype=np.int32)   # a row per frame, padded to 16 bytes: every row is aligned
+    for t in range(1, batch):
+        ctxf = [s for s in range(t - int(n_ctx), t) if s > 0]   # frame 0 is in its own slot
+        items[t, :2 + len(ctxf)] = [t, 0] + ctxf
+    labels = np.zeros((batch, npatch, classes), dtype=np.float32)
+    labels[0] = first
+    d_items, d_labels = DeviceBuffer.from_numpy(items, ctx.device), DeviceBuffer.from_numpy(labels, ctx.device)
+    try:
+        desc = ctx._propagate_desc(1, nsrc, k, tau, radius, classes, metric, norm, layer)
+        frame = npatch * classes * 4
+        if frame % 16:
+            raise ValueError(f"NP * C * 4 = {frame} bytes per frame is not a multiple of 16: the label slots would be unaligned")
+        for t in range(1, batch):
+            ctx.propagate_labels_device(desc, d_items.ptr + t * items.shape[1] * 4, d_labels.ptr, d_labels.ptr + t * frame, sync=False)
+        ctx.synchronize()
+        return d_labels.to_numpy(np.float32, labels.shape)
+    finally:
+        d_items.free()
+        d_labels.free()
 
 
 def op_kmeans(x_ptr, dtype, n, np_rows, width, k, iters, metric, init_ptr, labels_ptr, cent_ptr, counts_ptr):
