@@ -906,7 +906,11 @@ int vh_get_step_timing(vh_ctx* ctx, double* step_ms, int max_steps, int* steps);
  *           context creation keeps it row-major): same values, same logit bits, fc1's result leaves the registers without an
  *           LDS transposition,
  *       4 = one float: 1 when the last forward kept q|k|v head-major ([3][heads][rows][64]) between the projection's epilogue
- *           and the attention kernel (default where the attention output is tiled; VH_QKV_HM=0 keeps [rows][3 D]; same bits). */
+ *           and the attention kernel (default where the attention output is tiled; VH_QKV_HM=0 keeps [rows][3 D]; same bits),
+ *       5 = q|k|v of the last layer run as its attention read it (rotated under VH_FLAG_ROPE), [batch*T, 3 D] widened to fp32;
+ *           VH_ERR_STATE when that forward kept q|k|v head-major or ran no layer (vh_debug_set_layers(k): layer k's).  Valid only
+ *           directly behind the forward: the host read-outs (vh_read_features, vh_read_attention, vh_read_rollout, ..) stage their
+ *           results in the same buffer. */
 int vh_debug_read(vh_ctx* ctx, int what, float* host_out, size_t n_floats);
 /* run only the first `n_layers` encoder layers on the next forwards (-1 = all) */
 int vh_debug_set_layers(vh_ctx* ctx, int n_layers);
@@ -1088,7 +1092,7 @@ int vh_read_layer_features_device_async(vh_ctx* ctx, const vh_layer_features* ou
  * forward did not reach it.  vh_set_attention_layers: VH_ERR_INVALID for a null context, a bad count, a list that is not strictly
  * ascending within 1 .. cfg.layers, a queries value that is neither constant or that the context has no rows for; VH_ERR_STATE
  * while a ring exists.
- * Not covered: all-query maps [tokens][tokens] (attention rollout), rings, device groups. */
+ * Not covered: stored all-query maps [tokens][tokens] per head (their head-fused chain is "Attention rollout"), rings, device groups. */
 #define VH_MAX_ATTENTION_LAYERS 64
 #define VH_ATTN_Q_CLS 0      /* the class token's row                                      */
 #define VH_ATTN_Q_LEAD 1     /* every leading row: the class token and the register tokens */
@@ -1110,6 +1114,72 @@ int vh_attention_dims(const vh_ctx* ctx, int* batch, int* heads, int* queries, i
 int vh_read_attention(vh_ctx* ctx, const vh_attention_maps* out_host);
 int vh_read_attention_device(vh_ctx* ctx, const vh_attention_maps* out_dev);
 int vh_read_attention_device_async(vh_ctx* ctx, const vh_attention_maps* out_dev);
+
+/* ---- Attention rollout -----------------------------------------------------------------------
+ * The explanation asked for right after the class-token maps (Abnar & Zuidema, "Quantifying Attention Flow in Transformers"; the
+ * vit-explain recipe): the head-fused attention of EVERY query, with the residual connection added, multiplied through the layers.
+ * It needs the full [tokens][tokens] softmax of every head and layer -- 954 MB of fp32 per layer at ViT-B/16, batch 512, if it were
+ * stored -- so nothing is stored: a listed layer runs one more kernel behind its q|k|v projection (and the rotary pass) that
+ * recomputes the scores on the matrix cores, fuses the heads in registers and multiplies the result into the running product.
+ *
+ * THE OPERATION.  P_h = the [T][T] softmax of head h over all queries and keys, from the q|k|v the projection wrote (q arrives scaled
+ * by head_dim^-1/2 * log2(e): the exp2 domain, as in "Attention maps").  For one image and listed layer l:
+ *   F = fuse_h P_h, elementwise: VH_ROLLOUT_MEAN (serial fp32 adds over ascending heads, then * (float)(1.0 / H)) or VH_ROLLOUT_MAX;
+ *   A = F + I;   A^[r][:] = A[r][:] / sum_t A[r][t];   R_l = A^ R_(l-1), with R = I in front of the first listed layer.
+ * The result is R after the last listed layer the forward reached; row 0 is the class-token rollout map.  The chain is fp32
+ * throughout: rows of R sum to 1 and its entries shrink like 1 / T per layer, which a 16-bit chain would not survive.
+ *
+ * ARITHMETIC.  The scores are fp32 sums of exact 16-bit products on v_mfma_f32_16x16x32 (head_dim zero-padded to a multiple of 32);
+ * m = the row maximum, l = sum_t exp2(s[t] - m) by v_exp_f32 (results below 2^-126 are zero), p = exp2(s - m) * (1 / l) with one IEEE
+ * reciprocal per (row, head); the product A R_(l-1) runs on v_mfma_f32_16x16x4_f32 in ascending 64-key chunks and the division by
+ * the row sum of A happens once, on the product.  The summation order inside the matrix instructions is the hardware's: the values
+ * are fp32-accurate, not specified for bits against another implementation.  They ARE the same bits for one image whatever the
+ * batch, the batch part and stream, the q|k|v layout, eager or graph replay: an image's result depends on its own rows alone.
+ *
+ * THE RANGE.  vh_set_rollout(ctx, first_layer, last_layer, fusion): layers 1 .. cfg.layers, first_layer <= last_layer; last_layer -1 =
+ * cfg.layers; first_layer 0 clears the rollout and frees the stores.  The call waits for the context's stream, drops the cached
+ * graphs and allocates two ping-pong stores [max_batch][tokens][tokens] of fp32 (ViT-B/16 at max_batch 512: 2 x 79 MB).  When the
+ * allocation fails the call returns VH_ERR_HIP and the previous state stays in force.  Independent of vh_set_attention_layers: both
+ * may be set.  vh_get_rollout reads the range back (any pointer may be NULL; first_layer 0: none).  Every forward enqueued while a
+ * range is set runs one launch per listed layer it reaches and batch part, captured into graphs like every other launch; with no
+ * range a forward enqueues exactly what it enqueued before this section existed, and with one the logits keep their bits.  While a
+ * range is set consecutive forwards do not overlap (the stores are one per context), as with the feature and attention lists.
+ *
+ * READ-OUT.  vh_rollout, of the LAST forward; B = its batch (vh_rollout_dims, which also names the layers that forward chained:
+ * first 0 = none):
+ *   out        [B][rows][K]: rows 0 .. rows-1 of R, rows in 1 .. tokens;
+ *   elem       VH_ELEM_F32, or VH_ELEM_F16 / VH_ELEM_BF16 = the round-to-nearest-even of exactly the fp32 value;
+ *   keys       VH_ATTN_KEYS_ALL: K = tokens.  VH_ATTN_KEYS_PATCH: K = NP, columns lead .. tokens - 1; with rows = 1 out is [B][gh][gw]
+ *              as it lies.  The values are NOT renormalised.
+ * vh_read_rollout writes a host buffer (staged through activation scratch) and waits; _device enqueues on the context's stream and
+ * waits; _device_async only enqueues.  The device pointer is 16-byte aligned.
+ *
+ * REFUSED, each with a message of its own, nothing enqueued and no output touched.  VH_ERR_INVALID: a null context or descriptor; out
+ * NULL; elem, rows or keys outside their values; reserved != 0; a device pointer that is not 16-byte aligned; vh_set_rollout: a
+ * first_layer outside 0 .. cfg.layers, a last_layer that is not -1 or first_layer .. cfg.layers, a fusion that is neither constant.
+ * VH_ERR_UNSUPPORTED (vh_set_rollout and the reads): a VH_FLAG_CLS_TAIL context (its last layer runs another attention kernel); a
+ * VH_FLAG_ATTN_BIAS context (the kernel adds no bias); more than 640 tokens (the accumulator slices of the kernel are sized for the
+ * lengths at which vh_op_attention keeps a head's K on chip).  VH_ERR_STATE: a ring exists; no forward has run; no rollout was set
+ * when the last forward was enqueued; that forward did not reach the first listed layer (vh_debug_set_layers).
+ * Not covered: the discard-ratio variant (a per-image quantile over tokens^2 values), min fusion, gradient-weighted rollout, rings,
+ * device groups. */
+#define VH_ROLLOUT_MEAN 0 /* F = the mean of the heads */
+#define VH_ROLLOUT_MAX 1  /* F = their maximum         */
+typedef struct vh_rollout { /* sizeof == 24: out 0, elem 8, rows 12, keys 16, reserved 20 */
+    void* out;            /* [batch][rows][K] */
+    int32_t elem;         /* VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16 */
+    int32_t rows;         /* 1 .. tokens: the leading rows of R       */
+    int32_t keys;         /* VH_ATTN_KEYS_ALL or VH_ATTN_KEYS_PATCH   */
+    int32_t reserved;     /* 0 */
+} vh_rollout;
+int vh_set_rollout(vh_ctx* ctx, int first_layer, int last_layer, int fusion);
+int vh_get_rollout(const vh_ctx* ctx, int* first_layer, int* last_layer, int* fusion);
+/* any of the five may be NULL; *batch = 0 before the first forward; *first_layer .. *last_layer = the layers the last forward chained
+ * (0, 0: none); *tokens = all key columns, *patches = NP */
+int vh_rollout_dims(const vh_ctx* ctx, int* batch, int* tokens, int* patches, int* first_layer, int* last_layer);
+int vh_read_rollout(vh_ctx* ctx, const vh_rollout* out_host);
+int vh_read_rollout_device(vh_ctx* ctx, const vh_rollout* out_dev);
+int vh_read_rollout_device_async(vh_ctx* ctx, const vh_rollout* out_dev);
 
 /* ---- Dense heads -----------------------------------------------------------------------------
  * What the consumers of the patch features run next: a linear head on every patch row -- DINOv2's linear segmentation and depth heads
@@ -1708,6 +1778,14 @@ int vh_op_attention_probs(const void* qkv16_dev, int batch, int tokens, int head
  * VH_ATTN_KEYS_PATCH: K = tokens - lead, columns lead .. tokens - 1 (lead 0 .. tokens-1).  Pointers 16-byte aligned. */
 int vh_op_attention_readout(const float* store_f32_dev, int batch, int heads, int queries, int tokens, int lead, int elem, int keys,
                             void* probs_out_dev, void* head_mean_out_dev, void* stream);
+/* One step of "Attention rollout" on its own, the context's kernel: r_new[b] = rownorm(fuse_h softmax(q_h k_h^T) + I) r_prev[b] for every
+ * image, both fp32 [batch][tokens][tokens]; r_prev NULL = the identity (the first listed layer).  qkv16 in vh_op_attention_probs's two
+ * layouts (row-major at head_dim 32, 48, ..., 128; head-major with in_hm_rows >= batch*tokens at head_dim 64), q pre-scaled by
+ * head_dim^-1/2 * log2(e); heads*head_dim <= 2048, dtype VH_DTYPE_BF16 or VH_DTYPE_FP16, fusion VH_ROLLOUT_MEAN or VH_ROLLOUT_MAX, qkv16
+ * 16-byte and r_prev / r_new 4-byte aligned (an image's R starts at b*tokens^2 floats), r_prev and r_new not overlapping.  Nothing outside r_new's batch*tokens*tokens values is written.  tokens above
+ * 640 is VH_ERR_UNSUPPORTED, every other bad argument VH_ERR_INVALID, each with a message of its own, before a device is touched. */
+int vh_op_rollout(const void* qkv16_dev, int batch, int tokens, int heads, int head_dim, int64_t in_hm_rows, int dtype, int fusion,
+                  const float* r_prev_f32_dev, float* r_new_f32_dev, void* stream);
 /* NHWC fp32 images -> patch matrix [batch*np, patch*patch*channels] in `dtype` */
 int vh_op_im2col(const float* in_nhwc_dev, int batch, int image, int patch, int channels,
                  void* out16_dev, int dtype, void* stream);

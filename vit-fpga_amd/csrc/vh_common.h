@@ -53,6 +53,10 @@ struct FP16 {
     }
 };
 
+// The fp32 matrix instruction, v_mfma_f32_16x16x4_f32: D[16][16] = A[16][4] B[4][16] + C with fp32 operands and fp32 fused
+// multiply-adds.  Lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15]; its four results are D[4 (l >> 4) + r][l & 15], r = 0..3.
+__device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
 // fp32 "output type" of the kernels templated on their result element (final LayerNorm of the CLS rows -> fp32 head)
 constexpr int VH_DTYPE_F32_INTERNAL = 100;   // its launcher code, next to the public VH_DTYPE_*; never crosses the C ABI
 struct F32OUT {

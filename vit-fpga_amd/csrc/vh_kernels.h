@@ -145,6 +145,23 @@ hipError_t launch_swiglu_ln(const void* gu16, int dtype, int64_t rows, int mlp_d
 const char* attention_readout_check(int batch, int heads, int Q, int tokens, int lead, int elem, int keys);
 hipError_t launch_attention_readout(const float* store, int batch, int heads, int Q, int tokens, int lead, int elem, int keys, void* probs_out,
                                     void* mean_out, hipStream_t stream);
+// Attention rollout (kernels_rollout.hip; contract: vithip.h, "Attention rollout").  launch_rollout: one step of the chain for every
+// image, r_new[b] = rownorm(fuse_h softmax(q_h k_h^T) + I) r_prev[b], all [tokens][tokens] fp32; r_prev == nullptr: the identity (the
+// first listed layer).  q|k|v in launch_attention_probs's two layouts; tokens 1..kRolloutMaxTokens.  r_prev and r_new must not overlap.
+// launch_rollout_readout: rows 0 .. rows-1 and key columns k0 .. tokens-1 of such a store -> out [batch][rows][tokens - k0] in `elem`.
+// No allocation, no atomics (graph capture, split batches).  The *_check functions: nullptr, or why the launch is refused.
+constexpr int kRolloutMaxTokens = 640;   // where vh_op_attention still keeps a head's K on chip; the accumulator slices are sized for it
+struct RolloutArgs {
+    const void* qkv16;
+    int64_t in_hm_rows;
+    int batch, tokens, heads, head_dim, dtype, fusion;   // fusion: VH_ROLLOUT_MEAN / VH_ROLLOUT_MAX
+    const float* r_prev;
+    float* r_new;
+};
+const char* rollout_check(const RolloutArgs& a);
+hipError_t launch_rollout(const RolloutArgs& a, hipStream_t stream);
+const char* rollout_readout_check(int batch, int tokens, int rows, int k0, int elem);
+hipError_t launch_rollout_readout(const float* store, int batch, int tokens, int rows, int k0, int elem, void* out, hipStream_t stream);
 // the factor folded into Wq and bq: head_dim^-1/2 * log2(e); exactly kAttnQScale at head dim 64
 inline float attention_q_scale(int head_dim) {
     return head_dim == 64 ? kAttnQScale : (float)(1.4426950408889634 / __builtin_sqrt((double)head_dim));

@@ -429,6 +429,12 @@ struct vh_ctx {
     char* attn_store = nullptr;
     size_t attn_slot = 0;
     int acap_layers[VH_MAX_ATTENTION_LAYERS] = {0}, acap_n = 0, acap_nl = -1;
+    // Attention rollout (vh_set_rollout): layers roll_first .. roll_last (0: none) are chained with roll_fusion through two ping-pong
+    // stores [max_batch][T][T] of fp32; listed layer k writes roll_store[(k - roll_first) & 1].  What the LAST forward chained
+    // (enqueue_forward records it; the set call clears it): layers rcap_first .. rcap_last, rcap_last < rcap_first meaning none.
+    int roll_first = 0, roll_last = 0, roll_fusion = VH_ROLLOUT_MEAN;
+    float* roll_store[2] = {nullptr, nullptr};
+    int rcap_first = 0, rcap_last = -1;
     // Dense head (vh_set_dense_head; vithip.h "Dense heads"): w rounded to the operand type, the fp32 bias (null: none) and the fp32
     // logits vh_read_dense_map interpolates, [max_batch][classes][NP].  Only the dense read-outs touch them: no forward knows.
     void* dense_w16 = nullptr;
@@ -889,6 +895,19 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         }
         return VH_OK;
     };
+    // Attention rollout: in the same place, when l + 1 lies in roll_first .. roll_last, one step of the chain for this part's images:
+    // from the store the layer before wrote (the first listed layer: the identity) into the other one -- one launch.
+    c->rcap_first = c->roll_first;
+    c->rcap_last = c->roll_first ? (nl < c->roll_last ? nl : c->roll_last) : -1;
+    auto rollout = [&](int l, int64_t hm_rows) -> int {
+        if (!c->roll_first || l + 1 < c->roll_first || l + 1 > c->roll_last) return VH_OK;
+        const int k = l + 1 - c->roll_first;
+        const size_t at = (size_t)img0 * T * T;
+        const RolloutArgs ra{A.qkv16, hm_rows, batch, T, f.heads, c->head_dim, dt16, c->roll_fusion, k ? c->roll_store[(k - 1) & 1] + at : nullptr,
+                             c->roll_store[k & 1] + at};
+        HIPCHK(&c->err, launch_rollout(ra, s));
+        return VH_OK;
+    };
     // VH_FLAG_ROPE: behind the q|k|v projection and in front of the capture above and of attention, q and k of this part's patch rows
     // are rotated in place by the blob's tables -- one launch per layer, in the layout this part holds (hm_rows != 0: head-major).
     // Without the flag: no launch.  (No stage of its own: it is neither the projection's time nor attention's.)
@@ -1004,6 +1023,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
         if ((rc = rope(qkv_hm ? (int64_t)rows_g : 0))) return rc;
         if ((rc = capture_attention(l, qkv_hm ? (int64_t)rows_g : 0))) return rc;
+        if ((rc = rollout(l, qkv_hm ? (int64_t)rows_g : 0))) return rc;
         if (tail && l + 1 == nl) {
             // VH_FLAG_CLS_TAIL, last layer: only the class-token row of every image reaches the head, so attention runs for that
             // one query (all keys and values), and out-proj, fc1 and fc2 run on the `batch` class rows, gathered into compact
@@ -1093,6 +1113,7 @@ int enqueue_forward(vh_ctx* c, ImgIn in, int batch, float* logits, std::vector<s
         if ((rc = stage(ST_QKV, [&] { return launch_gemm(gq, s); }))) return rc;
         if ((rc = rope(0))) return rc;
         if ((rc = capture_attention(l, 0))) return rc;
+        if ((rc = rollout(l, 0))) return rc;
         if ((rc = stage(ST_ATTN, [&] {
                  return hd64 ? launch_attention(A.qkv16, batch, T, f.heads, A.att16, op_dt, A.tickets + l, s, true)
                              : attention_rm(l);
@@ -1297,7 +1318,7 @@ bool second_set(vh_ctx* c) {
 // list is set (the feature and attention stores are one per context).
 bool two_in_flight_allowed(const vh_ctx* c) {
     return c->inflight_max == 2 && c->timing_stage < 0 && !c->step_timing && !c->use_graph && c->nstreams == 1 && c->feat_n == 0 &&
-           c->attn_n == 0;
+           c->attn_n == 0 && c->roll_first == 0;
 }
 bool two_in_flight(vh_ctx* c) { return two_in_flight_allowed(c) && second_set(c); }
 // every compute stream of the context idle: c->stream, and the second stream where ring submits left forwards on it that
@@ -1776,6 +1797,7 @@ int vh_destroy(vh_ctx* c) {
     if (c->act[1].base) hipFree(c->act[1].base);
     if (c->feat_store) hipFree(c->feat_store);
     if (c->attn_store) hipFree(c->attn_store);
+    if (c->roll_store[0]) hipFree(c->roll_store[0]);   // one allocation holds both stores
     if (c->dense_w16) hipFree(c->dense_w16);
     if (c->dense_b) hipFree(c->dense_b);
     if (c->dense_logits) hipFree(c->dense_logits);
@@ -2734,6 +2756,18 @@ int vh_debug_read(vh_ctx* c, int what, float* host_out, size_t n_floats) {
         host_out[0] = c->last_qkv_hm ? 1.f : 0.f;
         return VH_OK;
     }
+    if (what == 5) {   // q|k|v of the last layer run as attention read it, [batch * T][3 D] widened to fp32; row-major forwards only
+        const size_t n = (size_t)c->last_batch * c->L.T * 3 * D;
+        if (n_floats != n) return fail(&c->err, VH_ERR_INVALID, "expected %zu floats", n);
+        if (c->last_qkv_hm || layers_to_run(c) < 1) return fail(&c->err, VH_ERR_STATE, "tap 5: the last forward kept q|k|v head-major, or ran no layer");
+        std::vector<uint16_t> raw(n);
+        HIPCHK(&c->err, hipMemcpy(raw.data(), c->act[c->last_set].qkv16, n * 2, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            if (c->dt16 == VH_DTYPE_BF16) { const uint32_t u = (uint32_t)raw[i] << 16; memcpy(&host_out[i], &u, 4); }
+            else { _Float16 hv; memcpy(&hv, &raw[i], 2); host_out[i] = (float)hv; }
+        }
+        return VH_OK;
+    }
     return fail(&c->err, VH_ERR_INVALID, "unknown tap %d", what);
 }
 
@@ -3082,6 +3116,126 @@ int vh_read_attention(vh_ctx* c, const vh_attention_maps* f) {
     if (int rc = attention_enqueue(c, d, slot)) return rc;
     if (f->probs) HIPCHK(&c->err, hipMemcpyAsync(f->probs, d.probs, n_probs, hipMemcpyDeviceToHost, c->stream));
     if (f->head_mean) HIPCHK(&c->err, hipMemcpyAsync(f->head_mean, d.head_mean, n_mean, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+
+// ---- attention rollout (vithip.h "Attention rollout"; kernels_rollout.hip) ---------------------------------------------------
+// The layer range and the two ping-pong stores; enqueue_forward runs one step per listed layer and records what it chained (rcap_*).
+int vh_set_rollout(vh_ctx* c, int first_layer, int last_layer, int fusion) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "set_rollout: null context");
+    const int layers = c->cfg.layers;
+    const int last = last_layer == -1 ? layers : last_layer;
+    if (first_layer < 0 || first_layer > layers) return fail(&c->err, VH_ERR_INVALID, "set_rollout: first_layer %d is not 0 (clear) or 1..%d", first_layer, layers);
+    if (first_layer) {
+        if (last < first_layer || last > layers)
+            return fail(&c->err, VH_ERR_INVALID, "set_rollout: last_layer %d is not -1 or %d..%d", last_layer, first_layer, layers);
+        if (fusion != VH_ROLLOUT_MEAN && fusion != VH_ROLLOUT_MAX)
+            return fail(&c->err, VH_ERR_INVALID, "set_rollout: fusion %d is not VH_ROLLOUT_MEAN (0) or VH_ROLLOUT_MAX (1)", fusion);
+        if (c->cfg.flags & VH_FLAG_ATTN_BIAS)
+            return fail(&c->err, VH_ERR_UNSUPPORTED, "set_rollout: a VH_FLAG_ATTN_BIAS context's rollout would leave the bias out (the kernel adds none)");
+        if (c->cfg.flags & VH_FLAG_CLS_TAIL)
+            return fail(&c->err, VH_ERR_UNSUPPORTED, "set_rollout: a VH_FLAG_CLS_TAIL context's last layer runs the class-token attention kernel");
+        if (c->L.T > kRolloutMaxTokens)
+            return fail(&c->err, VH_ERR_UNSUPPORTED, "set_rollout: %d tokens, the rollout kernel takes at most %d", c->L.T, kRolloutMaxTokens);
+    }
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "set_rollout: a ring exists on this context; vh_ring_destroy first");
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    HIPCHK(&c->err, sync_compute(c));
+    const size_t one = align_up((size_t)c->cfg.max_batch * c->L.T * c->L.T * sizeof(float), 256);
+    float* store = nullptr;
+    if (first_layer && !c->roll_store[0]) {   // the stores depend on max_batch and T alone: a new range reuses them
+        const hipError_t e = hipMalloc((void**)&store, 2 * one);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(&c->err, VH_ERR_HIP, "set_rollout: no room for the two stores (2 x %zu bytes): %s; the previous state stays", one, hipGetErrorString(e));
+        }
+    }
+    drop_graphs(c);   // captured launch sequences hold the old range's launches
+    if (!first_layer && c->roll_store[0]) {
+        hipFree(c->roll_store[0]);
+        c->roll_store[0] = c->roll_store[1] = nullptr;
+    }
+    if (store) {
+        c->roll_store[0] = store;
+        c->roll_store[1] = (float*)((char*)store + one);
+    }
+    c->roll_first = first_layer;
+    c->roll_last = first_layer ? last : 0;
+    c->roll_fusion = first_layer ? fusion : VH_ROLLOUT_MEAN;
+    c->rcap_first = 0;   // what the last forward chained belonged to the old range
+    c->rcap_last = -1;
+    return VH_OK;
+}
+int vh_get_rollout(const vh_ctx* c, int* first_layer, int* last_layer, int* fusion) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "get_rollout: null context");
+    if (first_layer) *first_layer = c->roll_first;
+    if (last_layer) *last_layer = c->roll_last;
+    if (fusion) *fusion = c->roll_fusion;
+    return VH_OK;
+}
+int vh_rollout_dims(const vh_ctx* c, int* batch, int* tokens, int* patches, int* first_layer, int* last_layer) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "rollout_dims: null context");
+    const bool any = c->rcap_last >= c->rcap_first && c->rcap_first > 0;
+    if (batch) *batch = c->last_batch;
+    if (tokens) *tokens = c->L.T;
+    if (patches) *patches = c->L.NP;
+    if (first_layer) *first_layer = any ? c->rcap_first : 0;
+    if (last_layer) *last_layer = any ? c->rcap_last : 0;
+    return VH_OK;
+}
+// every refusal of the three read calls; on success *store holds the result of the last chained layer
+static int rollout_check_call(vh_ctx* c, const vh_rollout* f, bool device, const float** store) {
+    if (!c) return fail(nullptr, VH_ERR_INVALID, "read_rollout: null context");
+    if (!f) return fail(&c->err, VH_ERR_INVALID, "read_rollout: null descriptor");
+    if (!f->out) return fail(&c->err, VH_ERR_INVALID, "read_rollout: out is NULL");
+    if (f->elem != VH_ELEM_F32 && f->elem != VH_ELEM_F16 && f->elem != VH_ELEM_BF16)
+        return fail(&c->err, VH_ERR_INVALID, "read_rollout: elem %d is not VH_ELEM_F32, VH_ELEM_F16 or VH_ELEM_BF16", f->elem);
+    if (f->rows < 1 || f->rows > c->L.T) return fail(&c->err, VH_ERR_INVALID, "read_rollout: rows %d outside 1..%d", f->rows, c->L.T);
+    if (f->keys != VH_ATTN_KEYS_ALL && f->keys != VH_ATTN_KEYS_PATCH)
+        return fail(&c->err, VH_ERR_INVALID, "read_rollout: keys %d is not VH_ATTN_KEYS_ALL (0) or VH_ATTN_KEYS_PATCH (1)", f->keys);
+    if (f->reserved != 0) return fail(&c->err, VH_ERR_INVALID, "read_rollout: reserved is %d, not 0", f->reserved);
+    if (device && ((uintptr_t)f->out & 15)) return fail(&c->err, VH_ERR_INVALID, "read_rollout: the device output pointer %p is not 16-byte aligned", f->out);
+    if (c->cfg.flags & VH_FLAG_CLS_TAIL)
+        return fail(&c->err, VH_ERR_UNSUPPORTED, "read_rollout: a VH_FLAG_CLS_TAIL context's last layer runs the class-token attention kernel");
+    if (c->cfg.flags & VH_FLAG_ATTN_BIAS) return fail(&c->err, VH_ERR_UNSUPPORTED, "read_rollout: a VH_FLAG_ATTN_BIAS context has no rollout (the kernel adds no bias)");
+    if (c->L.T > kRolloutMaxTokens) return fail(&c->err, VH_ERR_UNSUPPORTED, "read_rollout: %d tokens, the rollout kernel takes at most %d", c->L.T, kRolloutMaxTokens);
+    if (!c->ring.empty()) return fail(&c->err, VH_ERR_STATE, "read_rollout: a ring exists on this context (its forwards belong to slots); vh_ring_destroy first");
+    if (c->last_batch <= 0) return fail(&c->err, VH_ERR_STATE, "read_rollout: no forward has run");
+    if (c->rcap_first < 1) return fail(&c->err, VH_ERR_STATE, "read_rollout: no rollout was set when the last forward was enqueued (vh_set_rollout)");
+    if (c->rcap_last < c->rcap_first)
+        return fail(&c->err, VH_ERR_STATE, "read_rollout: the last forward ran %d layers and did not reach layer %d (vh_debug_set_layers)", c->rcap_last, c->rcap_first);
+    *store = c->roll_store[(c->rcap_last - c->rcap_first) & 1];
+    return VH_OK;
+}
+static int rollout_enqueue(vh_ctx* c, const vh_rollout& f, const float* store) {
+    HIPCHK(&c->err, launch_rollout_readout(store, c->last_batch, c->L.T, f.rows, f.keys == VH_ATTN_KEYS_PATCH ? c->L.lead : 0, f.elem, f.out, c->stream));
+    return VH_OK;
+}
+int vh_read_rollout_device_async(vh_ctx* c, const vh_rollout* f) {
+    const float* store = nullptr;
+    if (int rc = rollout_check_call(c, f, true, &store)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return rollout_enqueue(c, *f, store);
+}
+int vh_read_rollout_device(vh_ctx* c, const vh_rollout* f) {
+    if (int rc = vh_read_rollout_device_async(c, f)) return rc;
+    HIPCHK(&c->err, sync_compute(c));
+    return VH_OK;
+}
+// the host form: staged in the q|k|v buffer, as vh_read_attention does
+int vh_read_rollout(vh_ctx* c, const vh_rollout* f) {
+    const float* store = nullptr;
+    if (int rc = rollout_check_call(c, f, false, &store)) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    const size_t K = f->keys == VH_ATTN_KEYS_PATCH ? c->L.NP : c->L.T;
+    const size_t n = (size_t)c->last_batch * f->rows * K * (f->elem == VH_ELEM_F32 ? 4 : 2);
+    Staging st(c);
+    vh_rollout d = *f;
+    d.out = st.take(f->out, n);
+    if (st.at > st.cap) return fail(&c->err, VH_ERR_STATE, "read_rollout: staging needs %zu bytes, the scratch holds %zu", st.at, st.cap);
+    if (int rc = rollout_enqueue(c, d, store)) return rc;
+    HIPCHK(&c->err, hipMemcpyAsync(f->out, d.out, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(&c->err, sync_compute(c));
     return VH_OK;
 }
@@ -4184,6 +4338,18 @@ int vh_op_attention_readout(const float* store, int batch, int heads, int querie
                     probs_out, head_mean_out);
     if (const char* why = attention_readout_check(batch, heads, queries, tokens, lead, elem, keys)) return fail(nullptr, VH_ERR_INVALID, "attention_readout: %s", why);
     OPCHK(launch_attention_readout(store, batch, heads, queries, tokens, lead, elem, keys, probs_out, head_mean_out, (hipStream_t)stream));
+    OPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return VH_OK;
+}
+int vh_op_rollout(const void* qkv16, int batch, int tokens, int heads, int head_dim, int64_t in_hm_rows, int dtype, int fusion, const float* r_prev,
+                  float* r_new, void* stream) {
+    // one list of refusals, rollout_check's; the token limit alone is a shape the kernel does not serve rather than a bad argument
+    const RolloutArgs ra{qkv16, in_hm_rows, batch, tokens, heads, head_dim, dtype, fusion, r_prev, r_new};
+    if (tokens > kRolloutMaxTokens) return fail(nullptr, VH_ERR_UNSUPPORTED, "rollout: tokens %d, the kernel takes at most %d", tokens, kRolloutMaxTokens);
+    if (const char* why = rollout_check(ra))
+        return fail(nullptr, VH_ERR_INVALID, "rollout: %s (batch %d, tokens %d, heads %d, head_dim %d, in_hm_rows %lld, dtype %d, fusion %d, qkv16 %p, r_prev %p, r_new %p)",
+                    why, batch, tokens, heads, head_dim, (long long)in_hm_rows, dtype, fusion, qkv16, (const void*)r_prev, (void*)r_new);
+    OPCHK(launch_rollout(ra, (hipStream_t)stream));
     OPCHK(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }

@@ -208,6 +208,16 @@ class AttentionMaps(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+ROLLOUT_MEAN, ROLLOUT_MAX = 0, 1   # vh_set_rollout / vh_op_rollout fusion (VH_ROLLOUT_*): the heads' mean / maximum
+ROLLOUT_MAX_TOKENS = 640
+
+
+class Rollout(C.Structure):
+    """vh_rollout: where the attention rollout of the last forward goes (a host or device pointer): out [B, rows, K], the element
+    type, the leading rows wanted (1 .. tokens), keys (ATTN_KEYS_*) and a reserved 0.  24 bytes."""
+    _fields_ = [("out", C.c_void_p), ("elem", C.c_int32), ("rows", C.c_int32), ("keys", C.c_int32), ("reserved", C.c_int32)]
+
+
 L422_YUYV, L422_UYVY, L422_YVYU, L422_VYUY, L422_V210 = range(5)   # vh_frame_yuy2.layout (VH_422_*); V210: the 16-bit entry points only
 class FrameBGRA(C.Structure):
     """vh_frame_bgra: one packed 4:4:4 frame (one plane of pixels whose samples lie as `layout`, L444_*, says) inside the buffer of a
@@ -359,6 +369,12 @@ SYMBOLS = {
     "vh_read_attention": (_i, [_vp, _vp]),
     "vh_read_attention_device": (_i, [_vp, _vp]),
     "vh_read_attention_device_async": (_i, [_vp, _vp]),
+    "vh_set_rollout": (_i, [_vp, _i, _i, _i]),
+    "vh_get_rollout": (_i, [_vp, _pi, _pi, _pi]),
+    "vh_rollout_dims": (_i, [_vp, _pi, _pi, _pi, _pi, _pi]),
+    "vh_read_rollout": (_i, [_vp, _vp]),
+    "vh_read_rollout_device": (_i, [_vp, _vp]),
+    "vh_read_rollout_device_async": (_i, [_vp, _vp]),
     "vh_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "vh_op_gemm_fp8_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -394,6 +410,7 @@ SYMBOLS = {
     "vh_op_attention_layout": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _vp]),
     "vh_op_attention_probs": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _i, _vp, _vp]),
     "vh_op_attention_readout": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vh_op_rollout": (_i, [_vp, _i, _i, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "vh_op_im2col": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_padded": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "vh_op_im2col_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
@@ -2487,6 +2504,55 @@ class VitContext:
         g = self.cfg["image_size"] // self.cfg["patch_size"]
         return p.reshape(p.shape[0], p.shape[1], g, g)
 
+    # ---- attention rollout: the head-fused all-query maps chained over the layers (vithip.h "Attention rollout") ----
+    def set_rollout(self, first_layer=1, last_layer=-1, fusion=ROLLOUT_MEAN):
+        """Chain layers first_layer .. last_layer (1 .. layers; -1 = the last) in every following forward; first_layer 0 clears it
+        and frees the two stores."""
+        _check(lib().vh_set_rollout(self.h, int(first_layer), int(last_layer), int(fusion)), self.h)
+
+    def rollout(self):
+        """(first layer, last layer, fusion) of the range in force; first layer 0: none."""
+        v = [C.c_int(0) for _ in range(3)]
+        _check(lib().vh_get_rollout(self.h, *(C.byref(x) for x in v)), self.h)
+        return tuple(x.value for x in v)
+
+    def rollout_dims(self):
+        """(batch of the last forward, tokens, patches, first and last layer that forward chained; 0, 0: none)."""
+        v = [C.c_int(0) for _ in range(5)]
+        _check(lib().vh_rollout_dims(self.h, *(C.byref(x) for x in v)), self.h)
+        return tuple(x.value for x in v)
+
+    def read_rollout(self, rows=1, elem=ELEM_F32, keys=ATTN_KEYS_ALL):
+        """The first `rows` rows of the rollout of the last forward, [B, rows, K] of float32 / float16, or uint16 holding bf16
+        bits for ELEM_BF16; K = tokens, or the patches with ATTN_KEYS_PATCH."""
+        b, t, n, _, _ = self.rollout_dims()
+        dt = {ELEM_F32: np.float32, ELEM_F16: np.float16, ELEM_BF16: np.uint16}.get(elem, np.float32)
+        out = np.empty((max(b, 1), max(int(rows), 1), n if keys == ATTN_KEYS_PATCH else t), dtype=dt)   # (bad arguments: refused below)
+        desc = Rollout(out.ctypes.data, elem, int(rows), keys, 0)
+        _check(lib().vh_read_rollout(self.h, C.byref(desc)), self.h)
+        return out
+
+    def read_rollout_device(self, desc):
+        """desc: a Rollout with a device pointer (16-byte aligned); enqueues on the context's stream and waits."""
+        _check(lib().vh_read_rollout_device(self.h, C.byref(desc)), self.h)
+
+    def read_rollout_device_async(self, desc):
+        """The same, enqueue only: synchronize(), or stream order with a following call on the context."""
+        _check(lib().vh_read_rollout_device_async(self.h, C.byref(desc)), self.h)
+
+    def attention_rollout(self, fusion="mean"):
+        """The class-token rollout map of the images of the LAST forward over all layers, [B, gh, gw] float32 (the patch columns of
+        row 0, not renormalised).  The chain runs inside a forward: if that range and fusion are not set, this call sets them and
+        raises VhError (state, 3) saying so -- run the forward again, then call again (or call set_rollout() before the forward)."""
+        want = (1, self.cfg["layers"], {"mean": ROLLOUT_MEAN, "max": ROLLOUT_MAX}[fusion])
+        if self.rollout() != want:
+            self.set_rollout(*want)
+            raise VhError(3, f"attention_rollout: layers 1..{want[1]} with fusion '{fusion}' were not set when the last forward ran; "
+                             "they are set now: run the forward again, then call attention_rollout() again")
+        p = self.read_rollout(1, keys=ATTN_KEYS_PATCH)[:, 0]
+        g = self.cfg["image_size"] // self.cfg["patch_size"]
+        return p.reshape(p.shape[0], g, g)
+
 
 def group_shard_bounds(batch, n, r):
     lo, hi = C.c_int(0), C.c_int(0)
@@ -3084,6 +3150,12 @@ def op_attention_readout(store_ptr, batch, heads, queries, tokens, lead, elem, k
     """The read-out kernel of the attention maps alone: store fp32 [batch, heads, queries, tokens] -> probs [batch, heads, queries, K]
     and / or head_mean [batch, queries, K] in `elem`; K = tokens, or tokens - lead with ATTN_KEYS_PATCH."""
     _check(lib().vh_op_attention_readout(store_ptr, batch, heads, queries, tokens, lead, elem, keys, probs_ptr, head_mean_ptr, None))
+
+
+def op_rollout(qkv_ptr, batch, tokens, heads, head_dim, dtype, fusion, r_prev_ptr, r_new_ptr, in_hm_rows=0):
+    """One step of the attention rollout alone: r_new = rownorm(fuse_h softmax(q_h k_h^T) + I) r_prev per image, fp32 [batch, tokens,
+    tokens]; r_prev_ptr None = the identity; q|k|v row-major, or head-major (pack_head_major) with in_hm_rows at head_dim 64."""
+    _check(lib().vh_op_rollout(qkv_ptr, batch, tokens, heads, head_dim, in_hm_rows, dtype, fusion, r_prev_ptr, r_new_ptr, None))
 
 
 def op_im2col(in_ptr, batch, image, patch, channels, out_ptr, dtype):
